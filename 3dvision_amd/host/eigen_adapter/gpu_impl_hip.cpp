@@ -7,10 +7,9 @@
 //   PointCloud GPUPointCloud::generate(depth, rgb, fx,fy,cx,cy)  src/gpu_impl.cpp:69-128
 //   bool    GPURegistration::isCudaAvailable()                   src/gpu_impl.cpp:131-139
 //   RegistrationResult GPURegistration::icpRefine(...)           src/gpu_impl.cpp:141-260
-// Not BUILT in this repository (the image has neither Eigen nor OpenCV); PARSED by tests/test_adapter_syntax.py against the
-// reference's own headers (g++ -fsyntax-only -Werror, stand-in Eigen / cv::Mat declarations): a signature that drifts from
-// include/gpu_depth.hpp / include/gpu_registration.hpp fails that test.  The same calls are exercised through
-// ../tdv_registration.cpp (layout-compatible plain types) on the GPU box.
+// Not BUILT in this repository (it needs Eigen, OpenCV and the reference's own headers, none of which are part of it); its
+// signatures must match include/gpu_depth.hpp / include/gpu_registration.hpp of the reference.  The same calls are exercised
+// through ../tdv_registration.cpp (layout-compatible plain types) on the GPU.
 #include "gpu_depth.hpp"
 #include "gpu_registration.hpp"
 #include "tdv_hip.h"

@@ -3,7 +3,7 @@
 RANSAC hypotheses/s + ICP iterations/s at 200k-point clouds, with the roofline of the dominant
 kernel and a CPU baseline (the oracle) timed beside it.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 One STEP = one pass of the hot path over one batch of synthetic input at the headline size
@@ -14,7 +14,10 @@ of BASELINE.json's two targets (1e6 hyps/s : 50 iters/s), so `value` >= 50 steps
 targets are met at once.  At this size the ICP correspondences come from the exact box-pruned search (same
 correspondences as the reference's brute-force scan, bit for bit: tests/test_gpu_fullsize.py); the brute-force scan
 is timed after the K steps as a supplementary roofline entry.  The two rates are also reported separately (icp_iters_per_s,
-ransac_hyps_per_s), each from its own synchronized sub-region of the same K steps.
+ransac_hyps_per_s), each from its own synchronized sub-region of the same K steps.  The timed region is exactly K steps: one ICP call of
+K iterations and one RANSAC call of K x 20,000 hypotheses; `ms_per_step` is its wall time over K.  --dump-outputs DIR writes what the
+last of those steps returned to its caller (the two calls' results) as DIR/<name>.npy; the inputs are seeded, so two builds can be
+compared output for output.
 
 Inputs are resident in HBM before the timed region (torch CUDA tensors; the C ABI's *_dev entry
 points take their device pointers).  Multi-GPU: instances shard across ranks (one scene/model pair
@@ -50,8 +53,8 @@ def parse():
     ap.add_argument("--c5-timeout-s", type=float, default=300.0, help="N > 1: deadline of the C5 share; past it the line is printed without C5")
     ap.add_argument("--c5-instances", type=int, default=1024, help="N > 1: instances per rank of the C5 tray measured after the timed region")
     ap.add_argument("--cpu-budget-s", type=float, default=16.0)
-    ap.add_argument("--min-region-ms", type=float, default=100.0,
-                    help="the timed region is repeated (whole multiples of K steps) until it is at least this long; 0 = exactly K steps once")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the results of the last one (ICP and RANSAC) as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--launch-check", action="store_true",
                     help="CPU-only rehearsal of the N-rank launch (gloo, no GPU work): the same spawn / barrier / max-over-ranks / one-line skeleton")
     return ap.parse_args()
@@ -98,6 +101,19 @@ def launch_check(args):
                           "per_rank": [{"rank": int(x[1]), "steps_per_s": float(x[0])} for x in per_rank]}))
     if world > 1:
         dist.destroy_process_group()
+
+
+def dump_outputs(out_dir, r_icp, r_rs, prefix=""):
+    """What the timed path hands its caller for its last step - the ICP and the RANSAC result - one DIR/<prefix><name>.npy per field:
+    transforms and the float32 scores as float32, counts as float64 (exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    fields = {"icp_transformation": r_icp.transformation, "icp_fitness": r_icp.fitness, "icp_rmse": r_icp.rmse,
+              "icp_iterations": r_icp.iterations, "icp_n_corr": r_icp.n_corr,
+              "ransac_transformation": r_rs.transformation, "ransac_fitness": r_rs.fitness, "ransac_rmse": r_rs.rmse,
+              "ransac_inliers": r_rs.inliers, "ransac_best_iteration": r_rs.best_iteration, "ransac_iterations_run": r_rs.iterations_run}
+    for name, v in fields.items():
+        a = np.atleast_1d(np.asarray(v))
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a.astype(np.float32 if a.dtype == np.float32 else np.float64))
 
 
 def cpu_baseline(orc, src, tgt, nrm, corr, T0, thr, voxel, budget_s):
@@ -232,38 +248,24 @@ def main():
         c = time.perf_counter()
         return b - a, c - b, r_icp, r_rs
 
-    region_est = None
     if args.warmup > 0:
         run(args.warmup, False)
-        w = run(args.warmup, False)                  # second pass: workspaces sized, clocks up - its wall time sizes the timed region
-        region_est = (w[0] + w[1]) * args.steps / args.warmup
-    # A timed region shorter than ~100 ms is dominated by box noise (and invisible to a 1 Hz utilisation sampler): the K-step
-    # pass is repeated `regions` times inside ONE barrier/sync bracket; every figure below is per step over all K x regions steps.
-    regions = 1
-    if args.min_region_ms > 0 and region_est is not None:
-        # (the estimate comes from W-step passes, whose per-call overheads weigh more than in a K-step pass: 25 % of margin, so that the
-        #  region does not end up a few milliseconds under the floor)
-        regions = max(1, int(np.ceil(1.25 * args.min_region_ms * 1e-3 / max(region_est, 1e-6))))
-    rg = torch.tensor([regions], dtype=torch.int64, device=cdev)
-    if distributed:
-        dist.all_reduce(rg, op=dist.ReduceOp.MAX)      # same count on every rank
-    regions = int(rg.item())
+        run(args.warmup, False)                      # second pass: workspaces sized, clocks up
     ctx.timing_enable(True)
     ctx.timing_read(tdv.TIMER_ICP_NN); ctx.timing_read(tdv.TIMER_RANSAC_SCORE)
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
     t_start = time.perf_counter()
-    t_icp = t_rs = 0.0
-    for _ in range(regions):
-        a_, b_, r_icp, r_rs = run(args.steps, True)
-        t_icp += a_; t_rs += b_
+    t_icp, t_rs, r_icp, r_rs = run(args.steps, True)
     torch.cuda.synchronize()
     t_local = time.perf_counter() - t_start
     if distributed:
         dist.barrier()
     elapsed = time.perf_counter() - t_start
-    steps_timed = args.steps * regions
+    steps_timed = args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, r_icp, r_rs, "rank%d_" % rank if world > 1 else "")
     sc_ms, sc_launches = ctx.timing_read(tdv.TIMER_RANSAC_SCORE)
     icp_search_used = ctx.last_icp_search()   # before the supplementary scan below changes it
     # the search kernel of the timed region, timed on its own: one more ICP call of the same shape, outside `value`
@@ -390,9 +392,9 @@ def main():
         # bail-out a batch of hypotheses is two dispatches: every hypothesis over a prefix of the points, then the hypotheses that
         # can still beat the best count of the earlier batches over the rest - together they read the pair array once.
         # (batching rule of csrc/ransac.hip: batches of 65,536 hypotheses, the first one 8,192 when the bail-out is on)
-        hyps_call = args.steps * HYPS_PER_STEP        # one RANSAC call per region
+        hyps_call = args.steps * HYPS_PER_STEP        # the timed region's one RANSAC call
         bail = (os.environ.get("TDV_RANSAC_BAILOUT", "1") != "0") and hyps_call > 16384
-        sc_batches = regions * ((1 + -(-(hyps_call - 8192) // 65536)) if bail else max(1, -(-hyps_call // 65536)))
+        sc_batches = (1 + -(-(hyps_call - 8192) // 65536)) if bail else max(1, -(-hyps_call // 65536))
         sc_hyps_per_launch = hyps_total / max(sc_launches, 1)
         fast = rescore_share >= 0.0
         ops_per_test = (16.6 + 28.0 * rescore_share) if fast else 28.0
@@ -484,7 +486,7 @@ def main():
             "value": steps_total / elapsed,
             "unit": "steps/s (1 step = 1 ICP iteration + %d RANSAC hypotheses, N_s=N_t=%d)" % (HYPS_PER_STEP, n),
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "timed_regions": regions, "steps_timed": steps_timed, "timed_region_ms": elapsed * 1e3,
+            "steps_timed": steps_timed, "timed_region_ms": elapsed * 1e3,
             "ms_per_step": elapsed / steps_timed * 1e3,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -494,8 +496,8 @@ def main():
             "icp_iters_per_s_reference_order_sums": ref_iters_per_s,
             "targets": {"icp_iters_per_s": 50, "ransac_hyps_per_s": 1e6},
             "config": {"workload": "headline: N_s=N_t=%d, point-to-plane ICP (fixed %d iterations per call, %s correspondence search) + RANSAC scoring (%d hyps per call), "
-                                   "%d call(s) of each in the timed region, one instance pair per GPU"
-                                   % (n, args.steps, {"grid": "exact hash-grid", "pruned": "exact pruned"}.get(icp_search_used, "brute-force"), args.steps * HYPS_PER_STEP, regions),
+                                   "one call of each in the timed region, one instance pair per GPU"
+                                   % (n, args.steps, {"grid": "exact hash-grid", "pruned": "exact pruned"}.get(icp_search_used, "brute-force"), args.steps * HYPS_PER_STEP),
                        "n_src": n, "n_tgt": n, "hyps_per_step": HYPS_PER_STEP, "parallelism": "instances sharded, %d rank(s)%s" % (world, " - REHEARSAL: all ranks on GPU 0, gloo" if rehearse else ""),
                        "icp_start": "0.3 deg / 0.5 mm from the ground truth (inside the basin of the reference's 0.4-voxel threshold; SURVEY 8d's 3 deg / 5 mm start "
                                     "lies outside it and every iteration count is fixed, so the start only decides how many correspondences are accepted)",

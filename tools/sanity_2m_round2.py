@@ -1,7 +1,7 @@
 """One pass of the new code paths at 2,000,000 points: voxel (LDS bucket staging), descriptor index build (radix sorts) + match on a
 subset, hash-grid ICP (no-wrap table), RANSAC with the bail-out."""
-import importlib, sys, time, numpy as np, torch
-sys.path.insert(0, "/root/repo")
+import importlib, os, sys, time, numpy as np, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 tdv = importlib.import_module('3dvision_amd'); synth = importlib.import_module('3dvision_amd.synth')
 ctx = tdv.Context(0); dev = torch.device("cuda", 0)
 n = 2000000

@@ -3,8 +3,8 @@ saved under build/ for the pruning studies in this directory.  CPU only.
 
     python tools/studies/fpfh_descriptors.py
 """
-import sys, importlib, time
-sys.path.insert(0, '/root/repo')
+import os, sys, importlib, time
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 from oracle import pyoracle as orc
 synth = importlib.import_module('3dvision_amd.synth')

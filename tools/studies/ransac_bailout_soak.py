@@ -1,7 +1,8 @@
 """One-off soak (GPU box): 150 random RANSAC calls (sizes, inlier shares, thresholds, 16k-140k iterations, stopping confidences incl. 0) -
 the default run without a trace (exact bail-out) against the exact scoring kernel.  Result at the end of round 2: 0 mismatches."""
-import importlib, sys, numpy as np
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import importlib, os, sys, numpy as np
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 tdv = importlib.import_module("3dvision_amd"); synth = importlib.import_module("3dvision_amd.synth")
 import test_gpu_ransac as T
 ctx = tdv.Context(0)

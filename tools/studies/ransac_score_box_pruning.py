@@ -3,8 +3,8 @@
 (random pairs fill 6-D too sparsely), and the per-hypothesis L2 traffic would be ~7x the brute-force kernel's, so the
 idea was NOT built: k_ransac_score stays a brute-force VALU-roofline kernel.  CPU only (needs scipy).
 """
-import sys, importlib
-sys.path.insert(0, '/root/repo')
+import os, sys, importlib
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np
 synth = importlib.import_module('3dvision_amd.synth')
 n = 200000
