@@ -526,8 +526,22 @@ void k_vh_insert(const float* __restrict__ xyz, int total, const int* __restrict
 // member rows, no counts, no limit on the members of a voxel, and nothing depends on a race.
 // Anything the argument does not cover makes the tile raise *fail (the caller redoes the call through the table): a window
 // above VS_WIN_MAX (coarse voxels), rows too long for the halo, a pixel map or a key range that does not fit, points that are not
-// in row-major pixel order (the cloud is not what the caller said it was), non-positive depth.
+// in row-major pixel order (the cloud is not what the caller said it was), non-positive depth, and points OFF THE PIXEL GRID.
+// The window is a bound on continuous pixel distances, and the map holds rint'ed pixels: two members whose positions lie within
+// VS_GRID_TOL of their pixels are at most 2 VS_GRID_TOL farther apart on the map than the bound, which the +0.01 of the windows'
+// floors absorbs.  A cloud unprojected with other intrinsics than the caller's (another scale or principal point), or moved by a
+// fraction of a pixel, can still be in row-major order, but its points sit up to half a pixel off their rint: a member would then
+// fall one pixel outside its neighbour's window and the voxel would be split.  Such a point fails the tile.
 struct VoxelPinhole { float fx, fy, cx, cy; };
+// How far a recovered position cx + fx * x / z may lie from its pixel.  For a point the call's own intrinsics unprojected,
+// x = (u - cx) * z / fx and a = x * rcp(z) carry ~5 roundings (2^-24 relative each: 3e-7 of |u - cx|, 2e-4 px at 640 px from the
+// principal point), and cx + fx * a two more at the magnitude of the pixel (6e-5 px each below 2,048): 4e-4 px in all.
+// VS_GRID_TOL is 10x that, and 2 VS_GRID_TOL = 0.008 stays inside the windows' 0.01 of slack, so on-grid clouds keep the windows
+// they had.  The error grows with |u - cx| (3e-7 of it) and with the pixel's magnitude (half an ulp per rounding: 6e-5 px below
+// 2,048, 4.9e-4 px from 8,192 to 16,383): the 10x margin holds within ~1,000 px of the principal point (frames up to ~2k px wide),
+// and on-grid points stay within VS_GRID_TOL up to ~8k px from it.  Beyond that an on-grid cloud may be handed to the table: the
+// same result, by the slower path.
+constexpr float VS_GRID_TOL = 0.004f;
 #ifndef VS_TILE_VALUE
 #define VS_TILE_VALUE 4096
 #endif
@@ -585,10 +599,12 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
             if (rx < 0 || rx >= (1 << VS_KX) || ry < 0 || ry >= (1 << VS_KY) || rq < 0 || rq >= (1 << VS_KZ)) bad = true;     // a tile wider than the packed cell: the table
             pk[q] = (unsigned)rx | ((unsigned)ry << VS_KX) | ((unsigned)rq << (VS_KX + VS_KY));
             key[i] = pk[q];
-            const float rz = __frcp_rn(z);                               // (a reciprocal is plenty: the pixel is recovered to 1e-3, rint needs 0.5)
+            const float rz = __frcp_rn(z);                               // (a reciprocal is plenty: the pixel is recovered to 4e-4, VS_GRID_TOL is 4e-3)
             const float a = x * rz, b = y * rz;
-            const float fu = rintf(cam.cx + cam.fx * a), fv = rintf(cam.cy + cam.fy * b);
+            const float pu = cam.cx + cam.fx * a, pv = cam.cy + cam.fy * b;
+            const float fu = rintf(pu), fv = rintf(pv);
             if (!(z > 0.f) || !(fu >= 0.f && fu < 65535.f && fv >= 0.f && fv < 65535.f)) bad = true;
+            else if (!(fabsf(pu - fu) <= VS_GRID_TOL && fabsf(pv - fv) <= VS_GRID_TOL)) bad = true;      // off the pixel grid: the table
             else {
                 const int u = (int)fu, v = (int)fv;
                 pvu[q] = ((unsigned)v << 16) | (unsigned)u;

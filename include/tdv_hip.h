@@ -315,8 +315,9 @@ int tdv_voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* 
  * order tdv_depth_to_cloud*_dev emits (src/pipeline.cpp:68-83): the members of a voxel then lie within a few pixels of each other, and the
  * points are grouped through pixel windows in LDS instead of a hash table (no device-scope atomics; csrc/voxel.hip: k_vs_group) - what
  * tdv_register_batch_dev does for its own clouds.  Same voxels, means and order, bit for bit; a cloud or voxel size the window argument
- * does not cover (coarse voxels, rows longer than the halo, points not in pixel order) is redone through the table inside the call
- * (tdv_ctx_last_voxel_grouping tells). */
+ * does not cover (coarse voxels, rows longer than the halo, points not in pixel order, points whose position cx + fx * x / z or
+ * cy + fy * y / z lies more than 0.004 px off an integer pixel: a cloud unprojected with other intrinsics than the ones passed, or moved
+ * by a fraction of a pixel) is redone through the table inside the call (tdv_ctx_last_voxel_grouping tells). */
 int tdv_voxel_downsample_batch_pinhole_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size,
                                            float fx, float fy, float cx, float cy, float* d_out_xyz, int* h_voxel_offsets);
 

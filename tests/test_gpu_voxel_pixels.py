@@ -82,9 +82,15 @@ def test_pixel_windows_equal_the_table_and_the_oracle(ctx, orc, seed, n_inst, bo
     print("seed %d: %d instances, %d points -> %d voxels (%.2f points per voxel), grouped by %s" % (seed, n_inst, off[-1], voff[-1], off[-1] / max(voff[-1], 1), how))
 
 
-@pytest.mark.parametrize("what", ["coarse_voxels", "full_width_rows", "not_pixel_order", "wrong_intrinsics", "many_members", "huge_key_range", "empty_clouds"])
+@pytest.mark.parametrize("what", ["coarse_voxels", "full_width_rows", "not_pixel_order", "wrong_intrinsics", "many_members", "huge_key_range", "empty_clouds",
+                                  "scaled_intrinsics", "scaled_intrinsics_small", "scaled_u_only", "scaled_v_only", "subpixel_jitter", "subpixel_jitter_v"])
 def test_hand_over_to_the_table(ctx, orc, what):
-    """Cases the window argument does not cover: the call must notice and give the table path's result."""
+    """Cases the window argument does not cover: the call must notice and give the table path's result.  The last six are OFF THE PIXEL
+    GRID and still in row-major order (the order check does not catch them): intrinsics other than the ones that made the cloud, and
+    true intrinsics with every point moved by a fraction of a pixel - the recovered pixels are rint'ed continuous positions up to half
+    a pixel away, and a voxel's members can land one pixel outside each other's windows.  The scaled cameras scale about pixel (0, 0)
+    (principal point s * CX + shift): every recovered pixel stays inside the frame's range, and with s > 1 the points keep distinct
+    pixels in row-major order, so neither the range check nor the order check can catch them - only the test of the grid can."""
     rng = np.random.default_rng(11)
     voxel = float(np.float32(1.2 * 0.45 / F)); cam = CAM; expect = "table"
     if what == "full_width_rows":
@@ -101,6 +107,19 @@ def test_hand_over_to_the_table(ctx, orc, what):
         d_xyz = torch.from_numpy(x).to(d_xyz.device)
     elif what == "wrong_intrinsics":
         cam = (F * 0.5, F * 0.5, CX + 300.0, CY)                                # several points land on one pixel / out of order
+    elif what == "scaled_intrinsics":                                          # recovered u = 1.3 * u + 0.05: 0.05-0.45 px off the grid
+        cam = (1.3 * F, 1.3 * F, 1.3 * CX + 0.05, 1.3 * CY + 0.05)
+    elif what == "scaled_intrinsics_small":
+        cam = (1.15 * F, 1.15 * F, 1.15 * CX + 0.02, 1.15 * CY + 0.02)
+    elif what == "scaled_u_only":                                              # v on the grid, u off it
+        cam = (1.3 * F, F, 1.3 * CX + 0.05, CY)
+    elif what == "scaled_v_only":                                              # u on the grid, v off it
+        cam = (F, 1.3 * F, CX, 1.3 * CY + 0.05)
+    elif what in ("subpixel_jitter", "subpixel_jitter_v"):                    # true intrinsics, every point 0.1-0.3 px off its pixel in u and v (in v only)
+        x = d_xyz.cpu().numpy().astype(np.float64)
+        for c in ((0, 1) if what == "subpixel_jitter" else (1,)):
+            x[:, c] += rng.choice([-1.0, 1.0], len(x)) * rng.uniform(0.1, 0.3, len(x)) * x[:, 2] / F
+        d_xyz = torch.from_numpy(x.astype(np.float32)).to(d_xyz.device)
     elif what == "many_members":
         voxel = 0.0016                                                          # ~3 pixels per voxel, tilted surfaces: some voxels hold more than 16 points -> per-cloud legacy path
         expect = None
@@ -123,7 +142,13 @@ def test_hand_over_to_the_table(ctx, orc, what):
 
 @pytest.mark.parametrize("seed", range(6))
 def test_fuzz_random_frames(ctx, seed):
-    """Random surfaces, boxes, voxel sizes and intrinsics: whichever way a call goes, it returns the table path's bytes."""
+    """Random surfaces, boxes, voxel sizes and intrinsics: whichever way a call goes, it returns the table path's bytes.  The frame is
+    unprojected with CAM; the call is made with CAM (the pixel windows may apply) and with perturbed intrinsics: a scale s in [0.8, 1.6]
+    per axis about pixel (0, 0) and a principal-point shift in [0, 1) px, so that every recovered pixel stays in range.  Such a cloud is
+    off the caller's pixel grid, and the call must hand it to the table.  A scale below 1 puts several points on one pixel, and the
+    order check hands the cloud over (seeds 3, 5).  Where both scales are above 1 the points keep distinct pixels in row-major order:
+    in seeds 1 and 4 only the test of the grid hands the cloud over (without it, voxels are split); in seeds 0 and 2 the larger scales
+    also trip one of the other checks at every voxel size."""
     rng = np.random.default_rng(100 + seed)
     box = (int(rng.integers(10, 500)), int(rng.integers(10, 300)))
     depth, label, n_inst = _frame(200 + seed, int(rng.integers(1, 60)), box, tilt=float(rng.uniform(0, 4)), base=float(rng.uniform(0.25, 1.2)), steps=bool(seed % 2))
@@ -132,3 +157,10 @@ def test_fuzz_random_frames(ctx, seed):
         voxel = float(np.float32(voxel_px * 0.45 / F))
         voff, _, how = _both(ctx, d_xyz, off, voxel)
         print("seed %d box %s voxel %.1f px: %d points -> %d voxels by %s" % (seed, box, voxel_px, off[-1], voff[-1], how))
+    sx, sy = rng.uniform(0.8, 1.6, 2); du, dv = rng.uniform(0.0, 1.0, 2)
+    cam = (F * sx, F * sy, CX * sx + du, CY * sy + dv)
+    for voxel_px in (0.7, 1.2, 1.9, 3.3):
+        voxel = float(np.float32(voxel_px * 0.45 / F))
+        voff, _, how = _both(ctx, d_xyz, off, voxel, cam)
+        assert how == "table", (cam, voxel_px)
+        print("seed %d cam (%.3f F, %.3f F, %.3f CX + %.2f, %.3f CY + %.2f) voxel %.1f px: %d voxels by %s" % (seed, sx, sy, sx, du, sy, dv, voxel_px, voff[-1], how))
