@@ -54,6 +54,7 @@ ABI_SYMBOLS = [
     "tdv_depth_to_cloud_dev", "tdv_voxel_downsample_dev", "tdv_sample_triples", "tdv_pose_compose",
     "tdv_register_batch_dev", "tdv_prepare_model_dev", "tdv_bilateral_filter", "tdv_filter_duplicates", "tdv_load_ply_ascii", "tdv_load_mask_png", "tdv_load_masks_from_dir",
     "tdv_depth_to_cloud_batch_dev", "tdv_broadcast_model", "tdv_gather_results", "tdv_mask_resize_nearest", "tdv_mask_resize_nearest_dev", "tdv_voxel_downsample_batch_dev", "tdv_voxel_downsample_batch_pinhole_dev",
+    "tdv_icp_batch_dev", "tdv_refine_batch_dev",
 ]
 
 
@@ -410,6 +411,33 @@ class Context:
         return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
                                   iterations=res.iterations, n_corr=res.n_corr)
 
+    def icp_batch_dev(self, d_src, offsets, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane=True, fixed_iterations=False):
+        """ICP of many clouds against one target in one call (device pointers): cloud b = points [offsets[b], offsets[b + 1]) of d_src,
+        start pose T0s[b] ((B, 4, 4)).  Per instance what icp_dev returns for that cloud, bit for bit."""
+        off = np.ascontiguousarray(offsets, np.int32)
+        n = len(off) - 1
+        T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
+        t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
+        res = (IcpResultC * max(n, 1))()
+        _check(self._h, lib().tdv_icp_batch_dev(self._h, _ptr(d_src), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals), nt, _ptr(t0), C.c_float(thr),
+                                                max_iterations, int(point_to_plane), int(fixed_iterations), res), "tdv_icp_batch_dev")
+        return [RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
+                                   iterations=r.iterations, n_corr=r.n_corr) for r in res[:n]]
+
+    def icp_batch(self, sources, tgt, tgt_normals, T0s, thr, max_iterations=200, point_to_plane=True):
+        """icp_batch_dev on host clouds: a list of (n_b, 3) arrays against one target, uploaded with torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        srcs = [_f32(a).reshape(-1, 3) for a in sources]
+        off = np.zeros(len(srcs) + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in srcs])
+        cat = np.concatenate(srcs) if srcs and off[-1] else np.zeros((1, 3), np.float32)
+        tgt = _f32(tgt); tn = _f32(tgt_normals)
+        d_src = torch.from_numpy(cat).to(dev); d_tgt = torch.from_numpy(tgt if len(tgt) else np.zeros((1, 3), np.float32)).to(dev)
+        d_tn = torch.from_numpy(tn).to(dev) if tn is not None else None
+        return self.icp_batch_dev(d_src.data_ptr(), off, d_tgt.data_ptr(), None if d_tn is None else d_tn.data_ptr(), len(tgt), T0s, thr,
+                                  max_iterations, point_to_plane)
+
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every
         (hypothesis, point) test: the exact bail-out only runs when no trace is asked for."""
@@ -491,16 +519,30 @@ def _register_batch_dev(self, d_raw, d_bgr, d_masks, n_instances, params, d_mode
     _check(self._h, lib().tdv_register_batch_dev(self._h, _ptr(d_raw), _ptr(d_bgr), _ptr(d_masks), n_instances, C.byref(params),
                                                  _ptr(d_model_xyz), _ptr(d_model_normals), _ptr(d_model_fpfh), n_model, res),
            "tdv_register_batch_dev")
+    return _instance_results(res, n_instances)
+
+
+def _instance_results(res, n_instances):
     # one structured view over the result array instead of a ctypes attribute walk per instance (1,024 instances: 6 ms -> 0.6 ms)
     dt = np.dtype([("T", np.float32, 16), ("fitness", np.float32), ("rmse", np.float32), ("coarse_fitness", np.float32), ("coarse_inliers", np.int32),
                    ("icp_iterations", np.int32), ("n_points", np.int32), ("n_voxels", np.int32), ("status", np.int32)])
     assert dt.itemsize == C.sizeof(InstanceResultC)
     a = np.frombuffer(res, dtype=dt, count=n_instances).copy() if n_instances else np.zeros(0, dt)
     Ts = a["T"].reshape(-1, 4, 4).transpose(0, 2, 1).copy()          # column-major float[16] -> row-major [4, 4]
-    out = [dict(T=Ts[i], fitness=a["fitness"][i], rmse=a["rmse"][i], coarse_fitness=a["coarse_fitness"][i], coarse_inliers=int(a["coarse_inliers"][i]),
-                icp_iterations=int(a["icp_iterations"][i]), n_points=int(a["n_points"][i]), n_voxels=int(a["n_voxels"][i]), status=int(a["status"][i]))
-           for i in range(n_instances)]
-    return out
+    return [dict(T=Ts[i], fitness=a["fitness"][i], rmse=a["rmse"][i], coarse_fitness=a["coarse_fitness"][i], coarse_inliers=int(a["coarse_inliers"][i]),
+                 icp_iterations=int(a["icp_iterations"][i]), n_points=int(a["n_points"][i]), n_voxels=int(a["n_voxels"][i]), status=int(a["status"][i]))
+            for i in range(n_instances)]
+
+
+def _refine_batch_dev(self, d_raw, d_bgr, d_masks, n_instances, params, T0s, d_model_xyz, d_model_normals, n_model):
+    """tdv_register_batch_dev's clouds and voxels, then ICP from the caller's poses T0s ((B, 4, 4)); the same dicts as register_batch_dev
+    (coarse_fitness / coarse_inliers -1: no coarse stage)."""
+    T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
+    t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
+    res = (InstanceResultC * max(n_instances, 1))()
+    _check(self._h, lib().tdv_refine_batch_dev(self._h, _ptr(d_raw), _ptr(d_bgr), _ptr(d_masks), n_instances, C.byref(params), _ptr(t0),
+                                               _ptr(d_model_xyz), _ptr(d_model_normals), n_model, res), "tdv_refine_batch_dev")
+    return _instance_results(res, n_instances)
 
 
 def _prepare_model_dev(self, d_xyz, n, voxel, k, radius_factor, d_out_xyz, d_out_normals, d_out_fpfh, order=TDV_VOXEL_ORDER_REFERENCE):
@@ -542,6 +584,7 @@ Context.depth_to_cloud_batch_dev = _depth_to_cloud_batch_dev
 Context.broadcast_model = _broadcast_model
 Context.gather_results = _gather_results
 Context.register_batch_dev = _register_batch_dev
+Context.refine_batch_dev = _refine_batch_dev
 Context.voxel_downsample_batch_dev = _voxel_downsample_batch_dev
 Context.prepare_model_dev = _prepare_model_dev
 

@@ -5,6 +5,7 @@
 #include "tdv_internal.hpp"
 #include <cstring>
 #include <algorithm>
+#include <vector>
 
 using namespace tdv;
 
@@ -295,6 +296,22 @@ int tdv_icp_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 int fixed_iterations, tdv_icp_result* out) {
     TDV_TRY(begin(ctx));
     return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, fixed_iterations, out);
+}
+int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets, int n_instances, const float* d_tgt, const float* d_tgt_normals,
+                      int nt, const float* h_T0, float distance_threshold, int max_iterations, int point_to_plane, int fixed_iterations,
+                      tdv_icp_result* out) {
+    // every argument before anything is enqueued or written
+    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
+    if (n_instances == 0) return begin(ctx);
+    if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
+    for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
+    if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    std::vector<int> count((size_t)n_instances);
+    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
+    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                              point_to_plane, fixed_iterations, out));
+    return finish(ctx);
 }
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,

@@ -27,23 +27,33 @@ __global__ void k_gather_i32(const int* __restrict__ in, const int* __restrict__
     if (p < n) out[p] = in[idx[p]];
 }
 
-int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
-                       const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
-                       const float* d_model_fpfh, int n_model, tdv_instance_result* results) {
-    if (!ctx || !d_raw || !d_masks || !prm || !results || n_instances < 0 || n_model < 0) return TDV_ERR_BAD_ARG;
-    if (n_model > 0 && (!d_model_xyz || !d_model_fpfh)) return TDV_ERR_BAD_ARG;
-    if (n_instances == 0) return TDV_OK;
-    // all clouds of the frame in two launches (count + emit), back to back in one buffer
+namespace {
+
+// The front end every batched entry point shares: the arguments it checks, all clouds of the frame(s) in one pass, and the voxels of
+// all clouds with their reference order (pixel-window or table grouping; the host replay as the fall-back of a degenerate hash).
+int batch_check(const tdv_batch_params* prm, int n_instances) {
     if (prm->voxel_order != TDV_VOXEL_ORDER_FIRST && prm->voxel_order != TDV_VOXEL_ORDER_REFERENCE) return TDV_ERR_BAD_ARG;
     if (prm->mask_format < 0 || prm->mask_format > 2) return TDV_ERR_BAD_ARG;
     if (prm->mask_format != 0 && prm->n_frames > 1) return TDV_ERR_BAD_ARG;                     // a label image belongs to one frame
     if (prm->mask_format == 1 && n_instances > 255) return TDV_ERR_BAD_ARG;                     // u8 labels: instance b is label b + 1
     if (prm->mask_format == 2 && n_instances > 65535) return TDV_ERR_BAD_ARG;
+    const int mw = prm->mask_width > 0 ? prm->mask_width : prm->width, mh = prm->mask_height > 0 ? prm->mask_height : prm->height;
+    if ((mw != prm->width || mh != prm->height) && prm->mask_format == 2) return TDV_ERR_BAD_ARG;   // (a u16 label image is never resized: no such input in the reference)
+    return TDV_OK;
+}
+
+struct BatchClouds {
+    std::vector<int> off;             // instance b's points: [off[b], off[b + 1]) of xyz (n_instances + 1 entries)
+    float* xyz = nullptr;             // workspace
+    std::vector<int> empty_status;    // 0, or the status (1 / 2) of an instance without points
+};
+
+int batch_clouds(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, int n_instances, const tdv_batch_params* prm, BatchClouds& cl) {
+    // all clouds of the frame in two launches (count + emit), back to back in one buffer
     const int layout = prm->mask_format == 0 ? 1 : (prm->mask_format == 1 ? 0 : 2);            // depth.hip's `stacked` argument
     // masks of another size than the frame: nearest-neighbour resize first (src/pipeline.cpp:38-41)
     const int mw = prm->mask_width > 0 ? prm->mask_width : prm->width, mh = prm->mask_height > 0 ? prm->mask_height : prm->height;
     if (mw != prm->width || mh != prm->height) {
-        if (prm->mask_format == 2) return TDV_ERR_BAD_ARG;                                      // (a u16 label image is never resized: no such input in the reference)
         uint8_t* resized;
         const int n_masks = prm->mask_format == 0 ? n_instances : 1;
         TDV_TRY(ws_alloc(ctx, (size_t)n_masks * prm->width * prm->height + 16, &resized));
@@ -51,17 +61,17 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         TDV_TRY(mask_resize_nearest_dev(ctx, d_masks, n_masks, mw, mh, prm->width, prm->height, resized));
         d_masks = resized;
     }
-    std::vector<int> off((size_t)n_instances + 1, 0);
+    std::vector<int>& off = cl.off;
+    off.assign((size_t)n_instances + 1, 0);
     int* d_off = nullptr;
     const int* d_frame_of = nullptr;
     TDV_TRY(frame_map_dev(ctx, n_instances, prm->n_frames, prm->frame_of_instance, &d_frame_of));
     TDV_TRY(depth_to_cloud_batch_count(ctx, d_raw, d_frame_of, d_masks, n_instances, layout, prm->width, prm->height, prm->scale_to_meters, prm->mask_mode,
                                        prm->zmax, &d_off, off.data()));
-    float *all_xyz = nullptr;
     if (off[n_instances] > 0) {
-        TDV_TRY(ws_alloc(ctx, (size_t)off[n_instances] * 3, &all_xyz));
+        TDV_TRY(ws_alloc(ctx, (size_t)off[n_instances] * 3, &cl.xyz));
         TDV_TRY(depth_to_cloud_batch_emit(ctx, d_raw, d_frame_of, d_masks, nullptr, n_instances, layout, prm->width, prm->height, prm->scale_to_meters,
-                                          prm->mask_mode, prm->fx, prm->fy, prm->cx, prm->cy, prm->zmax, d_off, all_xyz, nullptr));
+                                          prm->mask_mode, prm->fx, prm->fy, prm->cx, prm->cy, prm->zmax, d_off, cl.xyz, nullptr));
     }
     // instances without a point: status 1 when the masked depth image holds no non-zero value at all (pipeline.cpp:57-60),
     // status 2 when it does but nothing survives the z clip (:86-89)
@@ -70,8 +80,72 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     empty_nonzero.assign(empty_inst.size(), 0);
     TDV_TRY(depth_batch_nonzero_any(ctx, d_raw, d_frame_of, d_masks, layout, prm->width, prm->height, prm->scale_to_meters, prm->mask_mode,
                                     empty_inst.data(), (int)empty_inst.size(), empty_nonzero.data()));
-    std::vector<int> empty_status((size_t)n_instances, 0);
-    for (size_t e = 0; e < empty_inst.size(); ++e) empty_status[empty_inst[e]] = empty_nonzero[e] ? 2 : 1;
+    cl.empty_status.assign((size_t)n_instances, 0);
+    for (size_t e = 0; e < empty_inst.size(); ++e) cl.empty_status[empty_inst[e]] = empty_nonzero[e] ? 2 : 1;
+    return TDV_OK;
+}
+
+struct BatchVoxels {
+    bool batched = false;             // the voxels below exist (else: per-instance voxel_downsample_dev)
+    std::vector<int> voff;            // instance b's voxels: [voff[b], voff[b + 1]) of the arrays below
+    int* d_voff = nullptr;            // the same on the device (n_instances + 2 ints)
+    float* first = nullptr; int* rank = nullptr; int4* leaders = nullptr;    // first-occurrence order; what the host replay needs
+    float* ref = nullptr; int *r2f = nullptr, *f2r = nullptr;                // reference order made on the device, and the permutation
+    std::vector<int> ref_failed;      // 1: instance b's reference order is (still) to be made by the host replay
+};
+
+int batch_voxels(tdv_ctx* ctx, int n_instances, const tdv_batch_params* prm, const BatchClouds& cl, BatchVoxels& vx) {
+    // voxels of ALL instances in first-occurrence order with one memset + two launches (voxel.hip, hash-table path); a lane then
+    // only finishes its instance's reference order.  A voxel too full for the table's member rows (a very coarse grid) sends the
+    // whole batch back to per-instance calls.
+    const bool batched_voxel_env = !(getenv("TDV_BATCH_VOXEL") && atoi(getenv("TDV_BATCH_VOXEL")) == 0);          // A/B knob (read per call: the tests switch it)
+    const bool want_ref = prm->voxel_order == TDV_VOXEL_ORDER_REFERENCE;
+    const std::vector<int>& off = cl.off;
+    vx.voff.assign((size_t)n_instances + 1, 0);
+    vx.ref_failed.assign((size_t)n_instances, 1);
+    const int total_pts = off[n_instances];
+    if (batched_voxel_env && total_pts > 0 && !study_env("TDV_VOXEL_LEGACY") && !study_env("TDV_VOXEL_SORT")) {
+        TDV_TRY(ws_alloc(ctx, (size_t)total_pts * 3, &vx.first));
+        if (want_ref) { TDV_TRY(ws_alloc(ctx, (size_t)total_pts, &vx.rank)); TDV_TRY(ws_alloc(ctx, (size_t)total_pts, &vx.leaders)); }
+        int* d_off_inst;
+        TDV_TRY(ws_alloc(ctx, (size_t)n_instances + 1, &d_off_inst));
+        TDV_TRY(ws_alloc(ctx, (size_t)n_instances + 2, &vx.d_voff));
+        TDV_HIP(ctx, hipMemcpyAsync(d_off_inst, off.data(), ((size_t)n_instances + 1) * 4, hipMemcpyHostToDevice, ctx->stream));   // (off outlives the call's sync below)
+        const WsMark vmark = ws_mark(ctx);                   // the table and member rows are scratch: given back after the call
+        int overflowed = 0;
+        const float pinhole[4] = {prm->fx, prm->fy, prm->cx, prm->cy};     // the clouds come from this call's own unprojection: row-major pixel order, these intrinsics
+        TDV_TRY(voxel_downsample_batch_dev(ctx, cl.xyz, total_pts, d_off_inst, n_instances, prm->voxel_size, vx.first, vx.rank, vx.leaders,
+                                           vx.voff.data(), &overflowed, vx.d_voff, pinhole, off.data()));
+        ws_rewind(ctx, vmark);
+        vx.batched = !overflowed;
+        // ... and their reference order, on the device too (the host replay stays as the fall-back of a cloud whose hash degenerates)
+        const bool device_order_env = !(getenv("TDV_VOXEL_DEVICE_ORDER") && atoi(getenv("TDV_VOXEL_DEVICE_ORDER")) == 0);   // A/B knob (read per call: the tests switch it)
+        if (vx.batched && want_ref && device_order_env && vx.voff[n_instances] > 0) {
+            const size_t tv = (size_t)vx.voff[n_instances];
+            TDV_TRY(ws_alloc(ctx, tv * 3, &vx.ref));
+            TDV_TRY(ws_alloc(ctx, tv, &vx.r2f));
+            TDV_TRY(ws_alloc(ctx, tv, &vx.f2r));
+            TDV_TRY(voxel_reference_order_batch_dev(ctx, n_instances, vx.voff.data(), vx.d_voff, vx.leaders, vx.first, vx.ref, vx.r2f, vx.f2r,
+                                                    vx.ref_failed.data()));
+        }
+    }
+    return TDV_OK;
+}
+
+}  // namespace
+
+int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
+                       const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
+                       const float* d_model_fpfh, int n_model, tdv_instance_result* results) {
+    if (!ctx || !d_raw || !d_masks || !prm || !results || n_instances < 0 || n_model < 0) return TDV_ERR_BAD_ARG;
+    if (n_model > 0 && (!d_model_xyz || !d_model_fpfh)) return TDV_ERR_BAD_ARG;
+    if (n_instances == 0) return TDV_OK;
+    TDV_TRY(batch_check(prm, n_instances));
+    BatchClouds cl;
+    TDV_TRY(batch_clouds(ctx, d_raw, d_masks, n_instances, prm, cl));
+    const std::vector<int>& off = cl.off;
+    float* all_xyz = cl.xyz;
+    const std::vector<int>& empty_status = cl.empty_status;
     (void)d_bgr;  // colours do not enter the registration chain (voxelDownsample keeps them, nothing downstream reads them)
     // the model's descriptors are packed once; every instance, on either lane, searches the same read-only index
     FmIndex model_index; bool have_index = false;
@@ -95,43 +169,15 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         }
     }
     const bool coherent_stages = !(study_env("TDV_BATCH_COHERENT") && atoi(study_env("TDV_BATCH_COHERENT")) == 0);   // A/B knob (read per call: the tests switch it)
-    // voxels of ALL instances in first-occurrence order with one memset + two launches (voxel.hip, hash-table path); a lane then
-    // only finishes its instance's reference order.  A voxel too full for the table's member rows (a very coarse grid) sends the
-    // whole batch back to per-instance calls.
-    const bool batched_voxel_env = !(getenv("TDV_BATCH_VOXEL") && atoi(getenv("TDV_BATCH_VOXEL")) == 0);          // A/B knob (read per call: the tests switch it)
     const bool want_ref = prm->voxel_order == TDV_VOXEL_ORDER_REFERENCE;
-    std::vector<int> voff((size_t)n_instances + 1, 0);
-    float* vox_first_all = nullptr; int* vox_rank_all = nullptr; int4* vox_leaders_all = nullptr;
-    float* vox_ref_all = nullptr; int *vox_r2f_all = nullptr, *vox_f2r_all = nullptr;
-    std::vector<int> ref_failed((size_t)n_instances, 1);        // 1: this instance's reference order is (still) to be made by the host replay
-    int* d_voff = nullptr;                                      // voxel offsets of the instances on the device (n_instances + 2 ints)
-    bool batched_voxel = false;
-    const int total_pts = off[n_instances];
-    if (batched_voxel_env && total_pts > 0 && !study_env("TDV_VOXEL_LEGACY") && !study_env("TDV_VOXEL_SORT")) {
-        TDV_TRY(ws_alloc(ctx, (size_t)total_pts * 3, &vox_first_all));
-        if (want_ref) { TDV_TRY(ws_alloc(ctx, (size_t)total_pts, &vox_rank_all)); TDV_TRY(ws_alloc(ctx, (size_t)total_pts, &vox_leaders_all)); }
-        int* d_off_inst;
-        TDV_TRY(ws_alloc(ctx, (size_t)n_instances + 1, &d_off_inst));
-        TDV_TRY(ws_alloc(ctx, (size_t)n_instances + 2, &d_voff));
-        TDV_HIP(ctx, hipMemcpyAsync(d_off_inst, off.data(), ((size_t)n_instances + 1) * 4, hipMemcpyHostToDevice, ctx->stream));   // (off outlives the call's sync below)
-        const WsMark vmark = ws_mark(ctx);                   // the table and member rows are scratch: given back after the call
-        int overflowed = 0;
-        const float pinhole[4] = {prm->fx, prm->fy, prm->cx, prm->cy};     // the clouds come from this call's own unprojection: row-major pixel order, these intrinsics
-        TDV_TRY(voxel_downsample_batch_dev(ctx, all_xyz, total_pts, d_off_inst, n_instances, prm->voxel_size, vox_first_all, vox_rank_all, vox_leaders_all,
-                                           voff.data(), &overflowed, d_voff, pinhole, off.data()));
-        ws_rewind(ctx, vmark);
-        batched_voxel = !overflowed;
-        // ... and their reference order, on the device too (the host replay stays as the fall-back of a cloud whose hash degenerates)
-        const bool device_order_env = !(getenv("TDV_VOXEL_DEVICE_ORDER") && atoi(getenv("TDV_VOXEL_DEVICE_ORDER")) == 0);   // A/B knob (read per call: the tests switch it)
-        if (batched_voxel && want_ref && device_order_env && voff[n_instances] > 0) {
-            const size_t tv = (size_t)voff[n_instances];
-            TDV_TRY(ws_alloc(ctx, tv * 3, &vox_ref_all));
-            TDV_TRY(ws_alloc(ctx, tv, &vox_r2f_all));
-            TDV_TRY(ws_alloc(ctx, tv, &vox_f2r_all));
-            TDV_TRY(voxel_reference_order_batch_dev(ctx, n_instances, voff.data(), d_voff, vox_leaders_all, vox_first_all, vox_ref_all, vox_r2f_all, vox_f2r_all,
-                                                    ref_failed.data()));
-        }
-    }
+    BatchVoxels bv;
+    TDV_TRY(batch_voxels(ctx, n_instances, prm, cl, bv));
+    const std::vector<int>& voff = bv.voff;
+    float* vox_first_all = bv.first; int* vox_rank_all = bv.rank; int4* vox_leaders_all = bv.leaders;
+    float* vox_ref_all = bv.ref; int *vox_r2f_all = bv.r2f, *vox_f2r_all = bv.f2r;
+    const std::vector<int>& ref_failed = bv.ref_failed;
+    int* d_voff = bv.d_voff;
+    const bool batched_voxel = bv.batched;
     // one instance: voxel -> normals + FPFH -> match -> RANSAC -> ICP on context c (its stream, its workspace)
     auto run_instance = [&](tdv_ctx* c, int b) -> int {
         tdv_instance_result& r = results[b];
@@ -418,6 +464,63 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     return TDV_OK;
 }
 
+// register_batch_dev's front end (clouds, voxels in the requested order), then ICP of every instance from the caller's pose through
+// icp_batch_run_dev: the batch's clouds are one array, instance b at [start[b], start[b] + count[b]).
+int refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, int n_instances, const tdv_batch_params* prm, const float* h_T0,
+                     const float* d_model_xyz, const float* d_model_normals, int n_model, tdv_instance_result* results) {
+    if (n_instances == 0) return TDV_OK;
+    BatchClouds cl;
+    TDV_TRY(batch_clouds(ctx, d_raw, d_masks, n_instances, prm, cl));
+    BatchVoxels bv;
+    TDV_TRY(batch_voxels(ctx, n_instances, prm, cl, bv));
+    const std::vector<int>& off = cl.off;
+    const bool want_ref = prm->voxel_order == TDV_VOXEL_ORDER_REFERENCE;
+    std::vector<int> start((size_t)n_instances, 0), count((size_t)n_instances, 0);
+    const float* clouds = nullptr;
+    if (bv.batched) {
+        // voxels of every instance at voff: first-occurrence order as they are, the reference order from the device pass - an instance
+        // it could not order is replayed on the host into its own slot
+        const size_t tv = (size_t)bv.voff[n_instances];
+        float* ref = bv.ref;
+        if (want_ref && !ref && tv > 0) TDV_TRY(ws_alloc(ctx, tv * 3, &ref));
+        for (int b = 0; b < n_instances; ++b) {
+            start[b] = bv.voff[b]; count[b] = bv.voff[b + 1] - bv.voff[b];
+            const int n = off[b + 1] - off[b];
+            if (want_ref && n > 0 && (bv.ref_failed[b] || !bv.ref))
+                TDV_TRY(voxel_reference_order(ctx, count[b], n, bv.leaders + bv.voff[b], bv.first + (size_t)bv.voff[b] * 3, nullptr, bv.rank + off[b], bv.voff[b],
+                                              ref + (size_t)bv.voff[b] * 3, nullptr, nullptr));
+        }
+        clouds = want_ref ? ref : bv.first;
+    } else {
+        // per instance, into the slot of its points (a cloud has at most as many voxels as points)
+        float* vox = nullptr;
+        if (off[n_instances] > 0) TDV_TRY(ws_alloc(ctx, (size_t)off[n_instances] * 3, &vox));
+        for (int b = 0; b < n_instances; ++b) {
+            const int n = off[b + 1] - off[b];
+            start[b] = off[b];
+            if (n > 0) TDV_TRY(voxel_downsample_dev(ctx, cl.xyz + (size_t)off[b] * 3, nullptr, n, prm->voxel_size, prm->voxel_order, vox + (size_t)off[b] * 3, nullptr, n,
+                                                    &count[b]));
+        }
+        clouds = vox;
+    }
+    std::vector<tdv_icp_result> fine((size_t)n_instances);
+    const float icp_thr = prm->voxel_size * prm->icp_distance_factor;  // pipeline.cpp:104
+    TDV_TRY(icp_batch_run_dev(ctx, clouds, start.data(), count.data(), n_instances, d_model_xyz, d_model_normals, n_model, h_T0, icp_thr,
+                              prm->icp_max_iterations, prm->point_to_plane, 0, fine.data()));
+    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < n_instances; ++b) {
+        tdv_instance_result& r = results[b];
+        std::memset(&r, 0, sizeof(r));
+        std::memcpy(r.T, fine[b].T, 64);     // an instance without points: its start pose (no points to refine with)
+        r.coarse_fitness = -1.f; r.coarse_inliers = -1;     // no coarse stage
+        r.n_points = off[b + 1] - off[b];
+        r.n_voxels = r.n_points > 0 ? count[b] : 0;
+        r.status = cl.empty_status[b];
+        if (r.status == 0) { r.fitness = fine[b].fitness; r.rmse = fine[b].rmse; r.icp_iterations = fine[b].iterations; }
+    }
+    return TDV_OK;
+}
+
 }  // namespace tdv
 
 using namespace tdv;
@@ -432,6 +535,21 @@ int tdv_register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d
     ctx->err[0] = 0;
     TDV_TRY(ws_reset(ctx));
     return register_batch_dev(ctx, d_raw, d_bgr, d_masks, n_instances, prm, d_model_xyz, d_model_normals, d_model_fpfh, n_model, results);
+}
+
+int tdv_refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
+                         const tdv_batch_params* prm, const float* h_T0, const float* d_model_xyz, const float* d_model_normals, int n_model,
+                         tdv_instance_result* results) {
+    if (!ctx || !d_raw || !d_masks || !prm || n_instances < 0 || n_model < 0) return TDV_ERR_BAD_ARG;
+    if (n_instances > 0 && (!h_T0 || !results)) return TDV_ERR_BAD_ARG;
+    if (n_model > 0 && !d_model_xyz) return TDV_ERR_BAD_ARG;
+    if (prm->icp_max_iterations < 0 || !(prm->voxel_size > 0.f)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(batch_check(prm, n_instances));
+    (void)d_bgr;  // colours do not enter the registration chain
+    TDV_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->err[0] = 0;
+    TDV_TRY(ws_reset(ctx));
+    return refine_batch_dev(ctx, d_raw, d_masks, n_instances, prm, h_T0, d_model_xyz, d_model_normals, n_model, results);
 }
 
 int tdv_depth_to_cloud_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, const uint8_t* d_bgr,

@@ -29,6 +29,9 @@
 //    (bound = the inclusive acceptance threshold, then the best distance found).  Float subtraction, multiplication
 //    and addition are monotone under round-to-nearest, so the box bound needs no margin; ties keep the lowest
 //    original target index as the scan does.  accumulate/solve run unchanged.
+//  * many instances against one target (icp_batch_run_dev: tdv_icp_batch_dev, tdv_refine_batch_dev): one hash grid over the target
+//    for the call, then k_icp_nn_grid_multi + k_icp_accumulate_multi - two launches per iteration for the whole batch, blocks padded
+//    per instance, each instance with the slab layout its single call would use, so that its bits are the single call's.
 // No float atomics anywhere: two runs give identical bits.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
@@ -470,11 +473,130 @@ __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_it
 }
 
 
-// MODE 0: point-to-plane (21 upper-triangular JtJ + 6 Jtr), MODE 1: point-to-point moments,
-// MODE 2: outputs only (no accumulation beyond count / error).
-// One launch per iteration: every block reduces its points to one slab (fixed order: per lane -> wave64 shuffles ->
-// LDS); the block that finishes LAST (atomic ticket) folds all slabs in a fixed order, solves, and updates the state
-// on the device — the result does not depend on which block that is.
+// The pieces of one accumulation launch, shared by k_icp_accumulate (one problem) and k_icp_accumulate_multi (one problem per
+// instance of a batch): the sums of one accepted correspondence, the block's slab and the fold of the last block, the update.
+// MODE 0: point-to-plane (21 upper-triangular JtJ + 6 Jtr), MODE 1: point-to-point moments, MODE 2: count / error only.
+template <int MODE>
+constexpr int acc_nv() { return MODE == 0 ? 29 : (MODE == 1 ? 17 : 2); }
+
+// the pose a launch reads at its start: the 3x4 part column by column, and the bottom row
+__device__ __forceinline__ void acc_load_pose(const IcpState* st, float* T /* 12 */, float* Tb /* 4 */) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int r = 0; r < 3; ++r) T[c * 3 + r] = st->T[c * 4 + r];
+    Tb[0] = st->T[3]; Tb[1] = st->T[7]; Tb[2] = st->T[11]; Tb[3] = st->T[15];     // (0 0 0 1 unless the caller's start pose says otherwise)
+}
+
+// p = R*s + t with each row evaluated as r0*sx + (r1*sy + r2*sz), then + t (see transform_point), from acc_load_pose's T
+__device__ __forceinline__ void acc_transform(const float* T, float sx, float sy, float sz, float& px, float& py, float& pz) {
+    px = (T[0] * sx + (T[3] * sy + T[6] * sz)) + T[9];
+    py = (T[1] * sx + (T[4] * sy + T[7] * sz)) + T[10];
+    pz = (T[2] * sx + (T[5] * sy + T[8] * sz)) + T[11];
+}
+
+// this lane's sums += one accepted correspondence (p, target idx at squared distance best)
+template <int MODE>
+__device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
+                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals) {
+    v[0] += 1.0; v[1] += (double)best;
+    const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
+    if (MODE == 0) {
+        const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
+        const float J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
+        const float ex = px - qx, ey = py - qy, ez = pz - qz;
+        const float r = ex * nx + (ey * ny + ez * nz);
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) v[k++] += (double)(J[a] * J[b]);
+#pragma unroll
+        for (int a = 0; a < 6; ++a) v[k++] += (double)(J[a] * r);
+    } else if (MODE == 1) {
+        const double P[3] = {px, py, pz}, Q[3] = {qx, qy, qz};
+        v[2] += P[0]; v[3] += P[1]; v[4] += P[2];
+        v[5] += Q[0]; v[6] += Q[1]; v[7] += Q[2];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) v[8 + a * 3 + b] += P[a] * Q[b];
+    }
+}
+
+// LDS of one accumulation block
+struct AccShared {
+    double red[8][ACC_NV];
+    double tot[ACC_NV];
+    float solve_ws[56];
+    bool is_last;
+};
+
+// Every block reduces its lanes' sums v[] to its slab slabs[slab] (fixed order: wave64 DPP -> LDS); the block that takes the last
+// of nblocks tickets folds slabs[0 .. nblocks) in a fixed order into sh.tot[] and returns true (all its threads) - the result
+// does not depend on which block that is.  The caller's thread 0 of that block then resets *ticket and updates the state.
+template <int MODE>
+__device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, int slab, int nblocks, unsigned* ticket, AccShared& sh) {
+    constexpr int NV = acc_nv<MODE>();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const double s = wave_sum_lane63(v[k]);
+        if (lane == 63) sh.red[wave][k] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < ACC_NV) {
+        double s = 0.0;
+        if (threadIdx.x < NV) s = (sh.red[0][threadIdx.x] + sh.red[1][threadIdx.x]) + (sh.red[2][threadIdx.x] + sh.red[3][threadIdx.x]);
+        slabs[(size_t)slab * ACC_NV + threadIdx.x] = s;
+    }
+    // ---- last block: fold ----------------------------------------------------------------------------------------------
+    // Release by the wave that wrote the slab (wave 0; thread 0 then moves the ticket), acquire by the block that folds.
+    // __threadfence() by every thread was a write-back AND an invalidate of the XCD's L2 (buffer_wbl2 + buffer_inv) from all
+    // four waves of all 196 blocks - invalidating the target lines the blocks still running were gathering.
+    if (threadIdx.x < 64) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    __syncthreads();
+    if (threadIdx.x == 0) sh.is_last = atomicAdd(ticket, 1u) == (unsigned)nblocks - 1u;
+    __syncthreads();
+    if (!sh.is_last) return false;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const int vv = threadIdx.x & 31, g = threadIdx.x >> 5;
+    {
+        // slabs were written by other blocks of this launch: the agent-scope fence above makes them visible to plain loads
+        // sixteen slab rows per thread and round, all loads of a round in flight together (the fold is a chain of round trips:
+        // 196 blocks at 200k points were 7 rounds of 4 loads, now 2 rounds of 16); fixed order, as before
+        const double* sl = slabs;
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
+        for (int b2 = g; b2 < nblocks; b2 += 128) {
+            double a[16];
+#pragma unroll
+            for (int j = 0; j < 16; ++j) a[j] = b2 + 8 * j < nblocks ? sl[(size_t)(b2 + 8 * j) * ACC_NV + vv] : 0.0;
+#pragma unroll
+            for (int j = 0; j < 16; j += 4) { s0 += a[j]; s1 += a[j + 1]; s2 += a[j + 2]; s3 += a[j + 3]; }
+        }
+        sh.red[g][vv] = (s0 + s1) + (s2 + s3);
+    }
+    __syncthreads();
+    if (threadIdx.x < ACC_NV)
+        sh.tot[vv] = ((sh.red[0][vv] + sh.red[1][vv]) + (sh.red[2][vv] + sh.red[3][vv])) + ((sh.red[4][vv] + sh.red[5][vv]) + (sh.red[6][vv] + sh.red[7][vv]));
+    __syncthreads();
+    return true;
+}
+
+// thread 0 of the folding block: solve, update, stopping rule from the folded sums (pose as acc_load_pose read it)
+template <int MODE>
+__device__ __forceinline__ void acc_finish(AccShared& sh, int ns, IcpState* st, int fixed_iterations, int iter0, float rmse0, const float* T, const float* Tb) {
+    if (MODE == 2) st->n_corr = (int)(sh.tot[0] + 0.5);
+    else {
+        float T16[16];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { T16[c * 4] = T[c * 3]; T16[c * 4 + 1] = T[c * 3 + 1]; T16[c * 4 + 2] = T[c * 3 + 2]; T16[c * 4 + 3] = Tb[c]; }
+        icp_update<MODE>(sh.tot, ns, st, fixed_iterations, iter0, rmse0, T16, sh.solve_ws);
+    }
+}
+
+// One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
+// slabs in a fixed order, solves, and updates the state on the device.
 template <int MODE, int ACC_PPT>   // ACC_PPT source points per thread (summed per lane in index order)
 __global__ __launch_bounds__(256)
 void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
@@ -489,21 +611,14 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
     double v[ACC_NV];
 #pragma unroll
     for (int k = 0; k < ACC_NV; ++k) v[k] = 0.0;
-    float T[12];
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-        for (int r = 0; r < 3; ++r) T[c * 3 + r] = st->T[c * 4 + r];
-    const float Tb[4] = {st->T[3], st->T[7], st->T[11], st->T[15]};     // bottom row (0 0 0 1 unless the caller's start pose says otherwise)
+    float T[12], Tb[4];
+    acc_load_pose(st, T, Tb);
 #pragma unroll 1
     for (int q = 0; q < ACC_PPT; ++q) {
         const int i = blockIdx.x * (256 * ACC_PPT) + q * 256 + threadIdx.x;
         if (i >= ns) continue;
-        const float sx = src[3 * i], sy = src[3 * i + 1], sz = src[3 * i + 2];
-        // p = R*s + t with each row evaluated as r0*sx + (r1*sy + r2*sz), then + t (see transform_point)
-        const float px = (T[0] * sx + (T[3] * sy + T[6] * sz)) + T[9];
-        const float py = (T[1] * sx + (T[4] * sy + T[7] * sz)) + T[10];
-        const float pz = (T[2] * sx + (T[5] * sy + T[8] * sz)) + T[11];
+        float px, py, pz;
+        acc_transform(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
         float best = FLT_MAX; int bc = 0;
         for (int s = 0; s < nsplit; ++s) {
             float d = pd2[(size_t)s * ns_pad + i];
@@ -527,87 +642,86 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
         if (out_d2) out_d2[i] = best;
         if (out_acc) out_acc[i] = acc ? 1 : 0;
         if (!acc) continue;
-        v[0] += 1.0; v[1] += (double)best;
-        const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
-        if (MODE == 0) {
-            const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-            const float J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-            const float ex = px - qx, ey = py - qy, ez = pz - qz;
-            const float r = ex * nx + (ey * ny + ez * nz);
-            int k = 2;
-#pragma unroll
-            for (int a = 0; a < 6; ++a)
-#pragma unroll
-                for (int b = a; b < 6; ++b) v[k++] += (double)(J[a] * J[b]);
-#pragma unroll
-            for (int a = 0; a < 6; ++a) v[k++] += (double)(J[a] * r);
-        } else if (MODE == 1) {
-            const double P[3] = {px, py, pz}, Q[3] = {qx, qy, qz};
-            v[2] += P[0]; v[3] += P[1]; v[4] += P[2];
-            v[5] += Q[0]; v[6] += Q[1]; v[7] += Q[2];
-#pragma unroll
-            for (int a = 0; a < 3; ++a)
-#pragma unroll
-                for (int b = 0; b < 3; ++b) v[8 + a * 3 + b] += P[a] * Q[b];
-        }
+        acc_add<MODE>(v, px, py, pz, best, idx, tgt, tgt_normals);
     }
-    constexpr int NV = MODE == 0 ? 29 : (MODE == 1 ? 17 : 2);
-    __shared__ double red[8][ACC_NV];
-    __shared__ double tot[ACC_NV];
-    __shared__ float solve_ws[56];
-    __shared__ bool is_last;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const double s = wave_sum_lane63(v[k]);
-        if (lane == 63) red[wave][k] = s;
-    }
-    __syncthreads();
-    if (threadIdx.x < ACC_NV) {
-        double s = 0.0;
-        if (threadIdx.x < NV) s = (red[0][threadIdx.x] + red[1][threadIdx.x]) + (red[2][threadIdx.x] + red[3][threadIdx.x]);
-        slabs[(size_t)blockIdx.x * ACC_NV + threadIdx.x] = s;
-    }
-    // ---- last block: fold, solve, update -----------------------------------------------------------------------
-    // Release by the wave that wrote the slab (wave 0; thread 0 then moves the ticket), acquire by the block that folds.
-    // __threadfence() by every thread was a write-back AND an invalidate of the XCD's L2 (buffer_wbl2 + buffer_inv) from all
-    // four waves of all 196 blocks - invalidating the target lines the blocks still running were gathering.
-    if (threadIdx.x < 64) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    __syncthreads();
-    if (threadIdx.x == 0) is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-    __syncthreads();
-    if (!is_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    const int nblocks = gridDim.x;
-    const int vv = threadIdx.x & 31, g = threadIdx.x >> 5;
-    {
-        // slabs were written by other blocks of this launch: the agent-scope fence above makes them visible to plain loads
-        // sixteen slab rows per thread and round, all loads of a round in flight together (the fold is a chain of round trips:
-        // 196 blocks at 200k points were 7 rounds of 4 loads, now 2 rounds of 16); fixed order, as before
-        const double* sl = slabs;
-        double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
-        for (int b2 = g; b2 < nblocks; b2 += 128) {
-            double a[16];
-#pragma unroll
-            for (int j = 0; j < 16; ++j) a[j] = b2 + 8 * j < nblocks ? sl[(size_t)(b2 + 8 * j) * ACC_NV + vv] : 0.0;
-#pragma unroll
-            for (int j = 0; j < 16; j += 4) { s0 += a[j]; s1 += a[j + 1]; s2 += a[j + 2]; s3 += a[j + 3]; }
-        }
-        red[g][vv] = (s0 + s1) + (s2 + s3);
-    }
-    __syncthreads();
-    if (threadIdx.x < ACC_NV)
-        tot[vv] = ((red[0][vv] + red[1][vv]) + (red[2][vv] + red[3][vv])) + ((red[4][vv] + red[5][vv]) + (red[6][vv] + red[7][vv]));
-    __syncthreads();
+    __shared__ AccShared sh;
+    if (!acc_slab_fold<MODE>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
     if (threadIdx.x != 0) return;
     *ticket = 0u;   // ready for the next launch (stream order)
-    if (MODE == 2) st->n_corr = (int)(tot[0] + 0.5);
-    else {
-        float T16[16];
+    acc_finish<MODE>(sh, ns, st, fixed_iterations, iter0, rmse0, T, Tb);
+}
+
+// ---- many instances against one target: two launches per iteration for the whole batch -------------------------------------
+// Instance b = source points [src_off, src_off + ns) of the concatenated clouds with its own state st[b].  Each instance's range is
+// padded to whole blocks in both kernels, so no block straddles two instances; blk_inst maps a block to its instance (the NN
+// blocks first, then the accumulation blocks: one table, uploaded once per call).  The accumulation keeps, per instance, the
+// points-per-thread and slab layout icp_run_dev picks for that instance alone (1 on the brute-force path, make_plan's 4 on the
+// pruned and grid paths): the f64 tree - and therefore every bit of the result - is the single call's.
+struct IcpInst {
+    int src_off, ns;            // the instance's points in the concatenated clouds
+    int nn_blk0;                // its first block in k_icp_nn_grid_multi's grid (256 points per block)
+    int acc_blk0, acc_blocks;   // its first block in k_icp_accumulate_multi's grid, and how many (= its slabs, from slab acc_blk0 on)
+    int ppt;                    // source points per thread of its accumulation
+};
+
+// k_icp_nn_grid for every instance: one lane per source point, transformed by its own instance's pose; blocks of finished
+// instances return at once.  Output in the direct format at the point's position in the concatenated clouds.
+__global__ __launch_bounds__(256)
+void k_icp_nn_grid_multi(const float* __restrict__ src, const IcpInst* __restrict__ inst, const int* __restrict__ blk_inst,
+                         const GridEntry* __restrict__ table, const float4* __restrict__ node, unsigned mask, int shift, float inv_cell,
+                         const IcpState* __restrict__ st_all, float tau, float* __restrict__ out_d2, int* __restrict__ out_idx) {
+    const int b = blk_inst[blockIdx.x];
+    const IcpState* __restrict__ st = st_all + b;
+    if (st->done) return;
+    const IcpInst in = inst[b];
+    const int i = (blockIdx.x - in.nn_blk0) * 256 + threadIdx.x;
+    if (i >= in.ns) return;
+    const int g = in.src_off + i;
+    float px, py, pz;
+    transform_point(st->T, src[3 * g], src[3 * g + 1], src[3 * g + 2], px, py, pz);
+    float bd; int bo;
+    grid_nearest(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo);
+    out_d2[g] = bo == INT_MAX ? FLT_MAX : bd;
+    out_idx[g] = bo == INT_MAX ? 0 : bo;
+}
+
+// k_icp_accumulate for every instance: instance b's blocks write its slabs and take its ticket word tickets[b]; the last of them
+// folds, solves and updates st[b].  The points-per-thread count is uniform over a block (runtime loop, as the single kernel's).
+template <int MODE>
+__global__ __launch_bounds__(256)
+void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __restrict__ inst, const int* __restrict__ blk_inst,
+                            const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
+                            const float* __restrict__ pd2, const int* __restrict__ pidx,
+                            IcpState* st_all, float tau_accept, int fixed_iterations, double* slabs, unsigned* tickets) {
+    const int b = blk_inst[blockIdx.x];
+    IcpState* st = st_all + b;
+    if (st->done) return;
+    const IcpInst in = inst[b];
+    const int iter0 = st->iter; const float rmse0 = st->rmse;
+    double v[ACC_NV];
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { T16[c * 4] = T[c * 3]; T16[c * 4 + 1] = T[c * 3 + 1]; T16[c * 4 + 2] = T[c * 3 + 2]; T16[c * 4 + 3] = Tb[c]; }
-        icp_update<MODE>(tot, ns, st, fixed_iterations, iter0, rmse0, T16, solve_ws);
+    for (int k = 0; k < ACC_NV; ++k) v[k] = 0.0;
+    float T[12], Tb[4];
+    acc_load_pose(st, T, Tb);
+    const int lb = blockIdx.x - in.acc_blk0;
+    const float* __restrict__ s0 = src + (size_t)in.src_off * 3;
+#pragma unroll 1
+    for (int q = 0; q < in.ppt; ++q) {
+        const int i = lb * (256 * in.ppt) + q * 256 + threadIdx.x;
+        if (i >= in.ns) continue;
+        float px, py, pz;
+        acc_transform(T, s0[3 * i], s0[3 * i + 1], s0[3 * i + 2], px, py, pz);
+        const float d = pd2[in.src_off + i];
+        const float best = d < FLT_MAX ? d : FLT_MAX;
+        const int idx = d < FLT_MAX ? pidx[in.src_off + i] : 0;
+        if (!(best <= tau_accept)) continue;
+        acc_add<MODE>(v, px, py, pz, best, idx, tgt, tgt_normals);
     }
+    __shared__ AccShared sh;
+    if (!acc_slab_fold<MODE>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
+    if (threadIdx.x != 0) return;
+    tickets[b] = 0u;   // ready for the next launch (stream order)
+    acc_finish<MODE>(sh, in.ns, st, fixed_iterations, iter0, rmse0, T, Tb);
 }
 
 // ---- reference-order accumulation (round 4; TDV_ICP_ACCUMULATE_REFERENCE) ------------------------------------------------
@@ -1323,6 +1437,143 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
     TDV_HIP(ctx, hipStreamSynchronize(s));
     ctx->last_icp_search = TDV_ICP_SEARCH_BRUTE;
     for (int b = 0; b < n_prob; ++b) {
+        std::memcpy(out[b].T, h[b].res_T, 64);
+        out[b].fitness = h[b].fitness; out[b].rmse = h[b].rmse; out[b].iterations = h[b].applied; out[b].n_corr = h[b].last_n_corr_applied;
+    }
+    return TDV_OK;
+}
+
+// icp_run_dev for n instances against one target in one call: instance b = h_count[b] points from point h_start[b] of d_src, start
+// pose T0s + 16 b.  Arguments are the caller's to check.  Per instance the result is icp_run_dev's for that cloud on this ctx, bit for
+// bit.  With tree sums, the AUTO or GRID search and a usable hash grid over the target (built once here) all instances iterate
+// together: k_icp_nn_grid_multi + k_icp_accumulate_multi, two launches per iteration for the whole batch, one read-back of all
+// states per burst.  Otherwise: small problems in one k_icp_small launch (icp_small_batch_dev), else icp_run_dev per instance with
+// the shared grid or Morton order.
+int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
+                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out) {
+    for (int b = 0; b < n; ++b) {    // result defaults: registration.cpp:309-311
+        std::memcpy(out[b].T, T0s + 16 * (size_t)b, 64);
+        out[b].fitness = 0.f; out[b].rmse = 0.f; out[b].iterations = 0; out[b].n_corr = 0;
+    }
+    if (n == 0) return TDV_OK;
+    int ns_max = 0, span = 0;
+    bool contiguous = h_start[0] == 0;
+    for (int b = 0; b < n; ++b) {
+        ns_max = std::max(ns_max, h_count[b]);
+        span = std::max(span, h_start[b] + h_count[b]);
+        if (b + 1 < n && h_start[b + 1] != h_start[b] + h_count[b]) contiguous = false;
+    }
+    if (n == 0 || max_iterations == 0 || nt == 0 || ns_max == 0) return TDV_OK;
+    hipStream_t s = ctx->stream;
+    const float tau = tau_le(thr);
+    const int search = ctx->icp_search;
+    const bool ref_acc = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
+    const bool small_off = getenv("TDV_ICP_SMALL") && atoi(getenv("TDV_ICP_SMALL")) == 0;   // icp_run_dev's A/B knob (read per call)
+    // (1) small problems: every instance in one launch of the kernel the single call runs for them (it has no fixed-iteration mode)
+    if (!fixed_iterations && !small_off && contiguous && (search == TDV_ICP_SEARCH_AUTO || search == TDV_ICP_SEARCH_BRUTE) &&
+        nt <= SM_MAX_N && ns_max <= SM_MAX_N && (long long)ns_max * nt <= SM_MAX_PAIRS_BATCH) {
+        std::vector<int> off((size_t)n + 1, 0);
+        for (int b = 0; b < n; ++b) off[b + 1] = off[b] + h_count[b];
+        int* d_off;
+        TDV_TRY(ws_alloc(ctx, (size_t)n + 1, &d_off));
+        TDV_HIP(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));   // (off outlives the call's sync)
+        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out, ns_max);
+    }
+    // the target's hash grid at this threshold, once for the call (icp_run_dev uses a grid under AUTO or GRID)
+    CellGrid cg{}; bool have_grid = false;
+    if (tau < FLT_MAX && (search == TDV_ICP_SEARCH_AUTO || search == TDV_ICP_SEARCH_GRID)) {
+        TDV_TRY(cell_grid_build(ctx, d_tgt, nt, thr, &cg));
+        have_grid = true;
+    }
+    if (ref_acc || !cg.usable) {
+        // (3) one icp_run_dev per instance, with the shared grid or the shared Morton order
+        bool any_pruned = search == TDV_ICP_SEARCH_PRUNED || search == TDV_ICP_SEARCH_GRID;
+        for (int b = 0; b < n && !any_pruned; ++b)
+            any_pruned = search == TDV_ICP_SEARCH_AUTO && nt >= PRUNED_MIN_TARGETS && (double)h_count[b] * (double)nt >= PRUNED_MIN_PAIRS;
+        SortedCloud sorted{}; bool have_sorted = false;
+        if (tau < FLT_MAX && !cg.usable && any_pruned) { TDV_TRY(spatial_sort_cloud(ctx, d_tgt, nt, sorted)); have_sorted = true; }
+        for (int b = 0; b < n; ++b) {
+            const WsMark mark = ws_mark(ctx);
+            TDV_TRY(icp_run_dev(ctx, d_src + (size_t)h_start[b] * 3, h_count[b], d_tgt, d_tgt_normals, nt, T0s + 16 * (size_t)b, thr, max_iterations,
+                                point_to_plane, fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr));
+            ws_rewind(ctx, mark);
+        }
+        return TDV_OK;
+    }
+    // (2) all instances together.  Per instance, the accumulation shape icp_run_dev would take for it alone: make_plan's points per
+    // thread where it searches with the grid (GRID, or AUTO at >= PRUNED_MIN_TARGETS targets and PRUNED_MIN_PAIRS pairs), else the
+    // brute-force path's 1 (which the one-launch path k_icp_small reproduces).
+    std::vector<IcpInst> inst((size_t)n);
+    int nn_blocks = 0, acc_blocks = 0;
+    for (int b = 0; b < n; ++b) {
+        const int ns = h_count[b];
+        const bool grid_b = search == TDV_ICP_SEARCH_GRID || (nt >= PRUNED_MIN_TARGETS && (double)ns * (double)nt >= PRUNED_MIN_PAIRS);
+        const bool small_b = !small_off && !grid_b && ns <= SM_MAX_N && nt <= SM_MAX_N && (long long)ns * nt <= SM_MAX_PAIRS_SINGLE;
+        const int plan_ppt = make_plan(std::max(ns, 1), nt).acc_ppt;
+        const int ppt = grid_b ? plan_ppt : ((small_b || !study_env("TDV_ICP_PPT")) ? 1 : plan_ppt);
+        IcpInst& in = inst[b];
+        in.src_off = h_start[b]; in.ns = ns; in.ppt = ppt;
+        in.nn_blk0 = nn_blocks; in.acc_blk0 = acc_blocks;
+        in.acc_blocks = (ns + 256 * ppt - 1) / (256 * ppt);
+        nn_blocks += (ns + 255) / 256;
+        acc_blocks += in.acc_blocks;
+    }
+    // one upload: initial states | instance table | block -> instance (NN blocks, then accumulation blocks); pinned staging of the ctx
+    const size_t st_bytes = (size_t)n * sizeof(IcpState), inst_bytes = (size_t)n * sizeof(IcpInst);
+    const size_t up_bytes = st_bytes + inst_bytes + ((size_t)nn_blocks + acc_blocks) * sizeof(int);
+    TDV_TRY(pin_reserve(ctx, up_bytes));      // (after cell_grid_build, which reads its flags back through the same staging)
+    IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
+    std::memset(h, 0, st_bytes);
+    for (int b = 0; b < n; ++b) {
+        std::memcpy(h[b].T, T0s + 16 * (size_t)b, 64); std::memcpy(h[b].res_T, T0s + 16 * (size_t)b, 64);
+        if (h_count[b] == 0) h[b].done = 1;   // no points: n_corr = 0 < 3, the result is the start pose
+    }
+    std::memcpy(ctx->pin + st_bytes, inst.data(), inst_bytes);
+    int* h_blk = reinterpret_cast<int*>(ctx->pin + st_bytes + inst_bytes);
+    for (int b = 0; b < n; ++b) {
+        for (int k = 0; k < (h_count[b] + 255) / 256; ++k) *h_blk++ = b;
+    }
+    for (int b = 0; b < n; ++b) {
+        for (int k = 0; k < inst[b].acc_blocks; ++k) *h_blk++ = b;
+    }
+    char* d_up; float* pd2; int* pidx; double* slabs; unsigned* tickets;
+    TDV_TRY(ws_alloc(ctx, up_bytes, &d_up));
+    TDV_TRY(ws_alloc(ctx, (size_t)span, &pd2));
+    TDV_TRY(ws_alloc(ctx, (size_t)span, &pidx));
+    TDV_TRY(ws_alloc(ctx, (size_t)acc_blocks * ACC_NV, &slabs));
+    TDV_TRY(ws_alloc(ctx, (size_t)n, &tickets));
+    TDV_HIP(ctx, hipMemcpyAsync(d_up, ctx->pin, up_bytes, hipMemcpyHostToDevice, s));
+    TDV_HIP(ctx, hipMemsetAsync(tickets, 0, (size_t)n * sizeof(unsigned), s));      // the last block of an instance resets its word
+    IcpState* d_st = reinterpret_cast<IcpState*>(d_up);
+    const IcpInst* d_inst = reinterpret_cast<const IcpInst*>(d_up + st_bytes);
+    const int* d_blk_nn = reinterpret_cast<const int*>(d_up + st_bytes + inst_bytes);
+    const int* d_blk_acc = d_blk_nn + nn_blocks;
+    const GridEntry* gtable = reinterpret_cast<const GridEntry*>(cg.table);
+    const float4* gnode = reinterpret_cast<const float4*>(cg.node);
+    const bool p2pl = point_to_plane && d_tgt_normals;
+    ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
+    // bursts between two looks at the states, as icp_run_dev's; the loop ends when every instance is done
+    int it = 0;
+    while (it < max_iterations) {
+        const int poll = fixed_iterations ? 32 : (it == 0 ? 4 : 8);
+        const int burst = std::min(poll, max_iterations - it);
+        for (int k = 0; k < burst; ++k) {
+            {
+                ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
+                k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);
+            }
+            if (p2pl) k_icp_accumulate_multi<0><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
+            else k_icp_accumulate_multi<1><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, nullptr, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
+        }
+        TDV_CHECK_LAUNCH(ctx);
+        it += burst;
+        TDV_HIP(ctx, hipMemcpyAsync(h, d_st, st_bytes, hipMemcpyDeviceToHost, s));
+        TDV_HIP(ctx, hipStreamSynchronize(s));
+        bool all_done = true;
+        for (int b = 0; b < n && all_done; ++b) all_done = h[b].done != 0;
+        if (all_done) break;
+    }
+    for (int b = 0; b < n; ++b) {
         std::memcpy(out[b].T, h[b].res_T, 64);
         out[b].fitness = h[b].fitness; out[b].rmse = h[b].rmse; out[b].iterations = h[b].applied; out[b].n_corr = h[b].last_n_corr_applied;
     }

@@ -153,6 +153,10 @@ int icp_small_max_points();
 long long icp_small_max_pairs_batch();
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
                         const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, int ns_max = 0 /* largest problem, if known */);
+// icp_run_dev for n instances against one target (icp.hip): instance b = h_count[b] points from point h_start[b] of d_src (host arrays), start
+// pose T0s + 16 b; per instance icp_run_dev's result bit for bit.  Arguments are not checked.
+int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
+                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out);
 int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                             const float* T, float thr, IcpOutputs outs, int* n_corr);
 int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
@@ -246,6 +250,9 @@ int normals_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float radiu
 int normals_fpfh_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_voff, const int* d_voff, int n_clouds, int k, float radius,
                            float* d_normals, float* d_desc, const int* d_tie_ids = nullptr, const int* d_tie_ids_inv = nullptr);
 
+// tdv_refine_batch_dev: register_batch_dev's clouds and voxels, then ICP of every instance from h_T0 + 16 b (batch.hip)
+int refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, int n_instances, const tdv_batch_params* prm, const float* h_T0,
+                     const float* d_model_xyz, const float* d_model_normals, int n_model, tdv_instance_result* results);
 int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
                        const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
                        const float* d_model_fpfh, int n_model, tdv_instance_result* results);

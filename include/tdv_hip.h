@@ -275,6 +275,23 @@ int tdv_icp_correspondences(tdv_ctx* ctx, const float* src, int ns, const float*
 int tdv_icp_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
                 int fixed_iterations, tdv_icp_result* out);
+/* Registration::icpRefine (src/registration.cpp:297-414) for n_instances source clouds against ONE target, in one call: refining
+ * many instances from poses the caller already has (a bin imaged again after a pick, a pose from another estimator).
+ * Cloud b = points [h_src_offsets[b], h_src_offsets[b+1]) of d_src (host array, n_instances + 1 entries, starting at 0,
+ * non-decreasing); start pose h_T0 + 16*b (host, column-major); out: host array of n_instances results.
+ * Per instance the result is, bit for bit, what tdv_icp_dev returns for that cloud on the same ctx (search mode and
+ * accumulation mode included).  fixed_iterations as in tdv_icp_dev.  A cloud with 0 points, nt == 0 or max_iterations == 0
+ * returns its start pose with fitness, rmse, iterations and n_corr 0, as tdv_icp_dev does.
+ * With tree sums, the AUTO or GRID search and a target whose hash grid is usable (built once per call), all instances iterate
+ * together: two launches per iteration for the whole batch and one read-back of all states every few iterations.  Small
+ * problems (target and every cloud within 2,048 points) run in one launch; otherwise (BRUTE / PRUNED forced, an unusable grid,
+ * reference-order sums) the call runs the single-instance loop per instance with the target's grid or Morton order built once.
+ * tdv_ctx_last_icp_search reports the search that ran.  Every argument is checked before anything is enqueued: TDV_ERR_BAD_ARG
+ * writes nothing to out. */
+int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets, int n_instances,
+                      const float* d_tgt, const float* d_tgt_normals /* may be NULL */, int nt, const float* h_T0,
+                      float distance_threshold, int max_iterations, int point_to_plane, int fixed_iterations,
+                      tdv_icp_result* out);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
@@ -391,6 +408,20 @@ int tdv_register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw_depth, const uint
                            const uint8_t* d_masks, int n_instances, const tdv_batch_params* params,
                            const float* d_model_xyz, const float* d_model_normals, const float* d_model_fpfh, int n_model,
                            tdv_instance_result* results);
+/* tdv_register_batch_dev with the caller's poses in place of normals + FPFH + match + RANSAC:
+ *   mask -> depth scale+mask -> unproject -> voxelDownsample(voxel_order) -> ICP from h_T0 + 16*b (host, column-major),
+ * with the front end (clouds in one pass, the voxels and their reference order) of tdv_register_batch_dev and the ICP of
+ * tdv_icp_batch_dev: per instance, bit for bit, the stagewise chain depth_to_cloud -> voxel_downsample(voxel_order) -> icp(T0).
+ * Honoured fields of params: the frame, intrinsics and zmax; mask_mode, mask_format, mask_width and mask_height; n_frames and
+ * frame_of_instance; voxel_size, voxel_order, icp_distance_factor, icp_max_iterations and point_to_plane.  Ignored: normals_k,
+ * fpfh_radius_factor, ransac_* and seed.
+ * Results: coarse_fitness = -1 and coarse_inliers = -1 (there is no coarse stage); status, n_points and n_voxels as in
+ * tdv_register_batch_dev; an instance with status 1 or 2 gets back its T0 with fitness, rmse and icp_iterations 0.
+ * n_instances == 0 is accepted.  Every argument is checked before anything is enqueued: TDV_ERR_BAD_ARG writes nothing to results. */
+int tdv_refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw_depth, const uint8_t* d_bgr /* may be NULL */,
+                         const uint8_t* d_masks, int n_instances, const tdv_batch_params* params, const float* h_T0,
+                         const float* d_model_xyz, const float* d_model_normals /* may be NULL */, int n_model,
+                         tdv_instance_result* results);
 /* Model preparation of src/pipeline.cpp:291-294 on device buffers: voxelDownsample(voxel_order) ->
  * estimateNormals(k) -> computeFPFH(voxel * radius_factor).  Outputs have capacity n. */
 int tdv_prepare_model_dev(tdv_ctx* ctx, const float* d_xyz, int n, float voxel_size, int voxel_order, int normals_k,

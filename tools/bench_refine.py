@@ -1,0 +1,155 @@
+#!/usr/bin/env python3
+"""Refinement of many instances from poses the caller already has (a bin imaged again after a pick): C4's scene, ICP only.
+
+The scene is tools/bench_batch.py's (B distinct instances of the relief part, each in its own 1280x720 frame with its own mask,
+one shared model).  One tdv_register_batch_dev run gives the poses; each is then moved by a seeded small motion (--angle-deg,
+--trans-mm), standing in for a bin that was imaged again, and refined three ways:
+  refine     tdv_refine_batch_dev: clouds -> voxels -> ICP of every instance, one call;
+  icp_batch  tdv_icp_batch_dev on the instances' voxel clouds, one call;
+  icp_loop   tdv_icp_dev once per instance on the same clouds (what a caller had before).
+After a warm-up the three alternate over --repeats rounds.  Prints one JSON line with instances/s and ICP iterations/s of each
+(median, min, max over the rounds).  Exits 1 when any instance of the batched call differs in bits from its tdv_icp_dev result, when
+the refine call differs from the batched call, or when an instance lies further than --max-angle rad / --max-trans m from its
+ground truth.
+
+    python tools/bench_refine.py [--instances 256] [--repeats 5] [--icp-iters 50] [--order first|reference]
+"""
+import argparse
+import importlib
+import importlib.util
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def _bench_batch():
+    spec = importlib.util.spec_from_file_location("bench_batch", os.path.join(ROOT, "tools", "bench_batch.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--instances", type=int, default=256)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--hyps", type=int, default=10000, help="RANSAC hypotheses of the register run that gives the poses")
+    ap.add_argument("--icp-iters", type=int, default=50)
+    ap.add_argument("--voxel-px", type=float, default=1.2)
+    ap.add_argument("--part-px", type=int, default=448)
+    ap.add_argument("--icp-factor", type=float, default=0.4)
+    ap.add_argument("--order", choices=["first", "reference"], default="reference")
+    ap.add_argument("--angle-deg", type=float, default=0.5, help="size of the seeded motion applied to every pose")
+    ap.add_argument("--trans-mm", type=float, default=0.5)
+    ap.add_argument("--max-angle", type=float, default=1.5e-4)
+    ap.add_argument("--max-trans", type=float, default=6e-5)
+    ap.add_argument("--seed", type=int, default=3)
+    args = ap.parse_args()
+    import torch
+    bb = _bench_batch()
+    tdv = importlib.import_module("3dvision_amd")
+    synth = importlib.import_module("3dvision_amd.synth")
+    dev = torch.device("cuda", 0)
+    ctx = tdv.Context(0)
+    B = args.instances
+    order = tdv.TDV_VOXEL_ORDER_REFERENCE if args.order == "reference" else tdv.TDV_VOXEL_ORDER_FIRST
+    wl = bb.build_workload(tdv, synth, ctx, B, args.voxel_px, args.part_px, args.seed, order, dev)
+    d_mx, d_mn, d_mf, nm = wl["model"]
+    voxel = wl["voxel"]
+    thr = voxel * args.icp_factor
+    W, H = bb.W, bb.H
+    prm = tdv.batch_params(width=W, height=H, scale_to_meters=bb.SCALE, fx=bb.F, fy=bb.F, cx=bb.CX, cy=bb.CY, zmax=bb.ZMAX, voxel_size=voxel,
+                           ransac_max_iterations=args.hyps, icp_max_iterations=args.icp_iters, icp_distance_factor=args.icp_factor,
+                           voxel_order=order, n_frames=B)
+    d_raw, d_masks = wl["depth"].data_ptr(), wl["masks"].data_ptr()
+
+    # the poses: one full registration, then a seeded small motion of each (the bin imaged again)
+    reg = ctx.register_batch_dev(d_raw, None, d_masks, B, prm, d_mx.data_ptr(), d_mn.data_ptr(), d_mf.data_ptr(), nm)
+    T0s = np.stack([synth.perturb(r["T"], seed=1000 + b, angle_deg=args.angle_deg, trans=args.trans_mm * 1e-3) for b, r in enumerate(reg)])
+
+    # the voxel clouds the refine call builds, made with the stagewise device calls: clouds of all frames, then voxels per instance
+    cap = int(sum(wl["mask_px"]))
+    d_xyz = torch.empty((cap, 3), dtype=torch.float32, device=dev)
+    off = ctx.depth_to_cloud_batch_dev(d_raw, d_masks, None, B, W, H, bb.SCALE, bb.F, bb.F, bb.CX, bb.CY, bb.ZMAX, d_xyz.data_ptr(), None, cap, n_frames=B)
+    d_vox = torch.empty_like(d_xyz)
+    voff = np.zeros(B + 1, np.int32)
+    for b in range(B):
+        n = int(off[b + 1] - off[b])
+        v = ctx.voxel_downsample_dev(d_xyz.data_ptr() + 12 * int(off[b]), None, n, voxel, d_vox.data_ptr() + 12 * int(voff[b]), None, n, order=order) if n else 0
+        voff[b + 1] = voff[b] + v
+    d_vx = d_vox.data_ptr()
+
+    def run_refine():
+        r = ctx.refine_batch_dev(d_raw, None, d_masks, B, prm, T0s, d_mx.data_ptr(), d_mn.data_ptr(), nm)
+        return [x["T"] for x in r], [x["icp_iterations"] for x in r], r
+
+    def run_batch():
+        r = ctx.icp_batch_dev(d_vx, voff, d_mx.data_ptr(), d_mn.data_ptr(), nm, T0s, thr, args.icp_iters)
+        return [x.transformation for x in r], [x.iterations for x in r], r
+
+    def run_loop():
+        r = [ctx.icp_dev(d_vx + 12 * int(voff[b]), int(voff[b + 1] - voff[b]), d_mx.data_ptr(), d_mn.data_ptr(), nm, T0s[b], thr, args.icp_iters)
+             for b in range(B)]
+        return [x.transformation for x in r], [x.iterations for x in r], r
+
+    runs = dict(refine=run_refine, icp_batch=run_batch, icp_loop=run_loop)
+    for f in runs.values():           # warm-up: arena growth, code load
+        f()
+    torch.cuda.synchronize()
+    times = {k: [] for k in runs}
+    last = {}
+    for _ in range(args.repeats):
+        for k, f in runs.items():     # alternating, so that a slow phase of the machine hits all three
+            t = time.perf_counter()
+            last[k] = f()
+            torch.cuda.synchronize()
+            times[k].append(time.perf_counter() - t)
+
+    # checks: the batched call against the single calls bit for bit, the refine call against the batched call, ground truth
+    Tb, ib, rb = last["icp_batch"]
+    Tl, il, rl = last["icp_loop"]
+    Tr, ir, rr = last["refine"]
+    differ = [b for b in range(B) if not (Tb[b].tobytes() == Tl[b].tobytes() and ib[b] == il[b] and np.float32(rb[b].rmse).tobytes() == np.float32(rl[b].rmse).tobytes()
+                                          and np.float32(rb[b].fitness).tobytes() == np.float32(rl[b].fitness).tobytes() and rb[b].n_corr == rl[b].n_corr)]
+    refine_differ = [b for b in range(B) if not (Tr[b].tobytes() == Tb[b].tobytes() and ir[b] == ib[b] and rr[b]["n_voxels"] == voff[b + 1] - voff[b])]
+    err = [synth.pose_error(T, Tg) for T, Tg in zip(Tb, wl["T_gt"])]
+    ang = np.array([e[0] for e in err]); tr = np.array([e[1] for e in err])
+    far = [int(b) for b in np.nonzero(~((ang <= args.max_angle) & (tr <= args.max_trans)))[0]]
+    iters = int(sum(ib))
+
+    def rates(k):
+        t = np.array(times[k])
+        return dict(instances_per_s=dict(median=float(B / np.median(t)), min=float(B / t.max()), max=float(B / t.min())),
+                    icp_iters_per_s=dict(median=float(iters / np.median(t)), min=float(iters / t.max()), max=float(iters / t.min())),
+                    ms_per_call=dict(median=float(np.median(t) * 1e3), min=float(t.min() * 1e3), max=float(t.max() * 1e3)))
+
+    out = dict(config="C4 refine: %d instances from perturbed poses (%.2f deg, %.2f mm) vs one %d-pt model; voxel %.3f mm; ICP <= %d iterations"
+                      % (B, args.angle_deg, args.trans_mm, nm, voxel * 1e3, args.icp_iters),
+               instances=B, repeats=args.repeats, voxel_order=args.order, model_points=nm,
+               voxels_per_instance=dict(min=int(np.diff(voff).min()), mean=float(np.diff(voff).mean()), max=int(np.diff(voff).max())),
+               icp_iterations_run=iters, icp_iterations_per_instance=iters / B, last_icp_search=ctx.last_icp_search(),
+               refine=rates("refine"), icp_batch=rates("icp_batch"), icp_loop=rates("icp_loop"),
+               angle_to_gt_rad=dict(max=float(ang.max()), mean=float(ang.mean())), translation_to_gt_m=dict(max=float(tr.max()), mean=float(tr.mean())),
+               batch_differs_from_single=differ[:16], refine_differs_from_batch=refine_differ[:16], off_ground_truth=far[:16])
+    print(json.dumps(out))
+    ctx.close()
+    fail = []
+    if differ:
+        fail.append("%d instances of tdv_icp_batch_dev differ from tdv_icp_dev" % len(differ))
+    if refine_differ:
+        fail.append("%d instances of tdv_refine_batch_dev differ from tdv_icp_batch_dev" % len(refine_differ))
+    if far:
+        fail.append("%d instances further than %.1e rad / %.1e m from ground truth" % (len(far), args.max_angle, args.max_trans))
+    if fail:
+        sys.stderr.write("FAILED: " + "; ".join(fail) + "\n")
+        sys.exit(1)
+
+
+if __name__ == "__main__":
+    main()
