@@ -37,6 +37,7 @@
 #include <algorithm>
 #include <numeric>
 #include <limits>
+#include <climits>
 #include <cmath>
 #include <fstream>
 #include <string>
@@ -88,6 +89,109 @@ void find_radius_nn(const float* pts, int n, const float* query, float radius, i
 }
 
 inline void set_identity44(float* T) { for (int i = 0; i < 16; ++i) T[i] = 0.f; T[0] = T[5] = T[10] = T[15] = 1.f; }
+
+// ---------------------------------------------------------------- exact sums (the exact-sum mode of orc_icp / orc_ransac)
+// The device's default ICP accumulation (csrc/icp.hip, k_icp_accumulate and its relatives) and its RANSAC rmse
+// (k_ransac_rmse_partial / _final) add f32 terms in f64 along a fixed tree.  Such a sum is within
+// gamma_D * sum|t| of the exact sum (D = the most additions any term passes through), so the f32 the device takes
+// from it is the exact sum rounded to f32 unless the exact sum lies within that bound of an f32 rounding midpoint.
+// XSum holds a sum exactly (Shewchuk's non-overlapping partials, as Python's math.fsum), x32 rounds it to f32 once
+// and reports that ambiguity.  Needs IEEE double without contraction (-ffp-contract=off, no -ffast-math).
+struct XSum {
+    std::vector<double> p;     // non-overlapping partials, ascending magnitude: their exact sum is the sum
+    double abs = 0.0;          // sum of |terms| (rounded: enters the error bound only, with margin)
+    int grid = INT_MAX;        // every term is a multiple of 2^grid (the lowest set bit of any term)
+    void add_exact(double x) {
+        size_t i = 0;
+        for (double y : p) {
+            if (std::fabs(x) < std::fabs(y)) std::swap(x, y);
+            const double hi = x + y, lo = y - (hi - x);
+            if (lo != 0.0) p[i++] = lo;
+            x = hi;
+        }
+        p.resize(i);
+        p.push_back(x);
+    }
+    void add(double x) {
+        add_exact(x);
+        abs += std::fabs(x);
+        if (x != 0.0) {
+            int e;
+            const uint64_t m = (uint64_t)std::ldexp(std::frexp(std::fabs(x), &e), 53);   // |x| = m * 2^(e - 53)
+            grid = std::min(grid, e - 53 + __builtin_ctzll(m));
+        }
+    }
+    // bound of the device's f64 tree sum of these terms when no term passes through more than `depth` additions:
+    // gamma_depth * sum|t| (with margin), or 0 when every partial sum of every tree is a multiple of 2^grid below
+    // 2^(53 + grid) in magnitude, hence exact in f64
+    double tree_bound(int depth) const {
+        if (abs == 0.0 || abs < 0.5 * std::ldexp(1.0, 53 + grid)) return 0.0;
+        return 1.01 * depth * std::ldexp(abs, -53);
+    }
+    // the exact sum correctly rounded to double (math.fsum's last step)
+    double value() const {
+        size_t n = p.size();
+        if (n == 0) return 0.0;
+        double hi = p[--n], lo = 0.0;
+        while (n > 0) {
+            const double x = hi, y = p[--n];
+            hi = x + y;
+            lo = y - (hi - x);
+            if (lo != 0.0) break;
+        }
+        if (n > 0 && ((lo < 0.0 && p[n - 1] < 0.0) || (lo > 0.0 && p[n - 1] > 0.0))) {
+            const double y = lo * 2.0, x = hi + y;
+            if (y == x - hi) hi = x;
+        }
+        return hi;
+    }
+};
+
+// x * y as two doubles (exact: fma is correctly rounded)
+inline void two_prod(double x, double y, XSum& into, double sign) {
+    const double h = x * y;
+    into.add_exact(sign * h);
+    into.add_exact(sign * std::fma(x, y, -h));
+}
+
+// f32 rounding midpoints either side of f (exact in double)
+inline void midpoints32(float f, double& lo, double& hi) {
+    lo = 0.5 * ((double)f + (double)std::nextafter(f, -INFINITY));
+    hi = 0.5 * ((double)f + (double)std::nextafter(f, INFINITY));
+}
+inline float tie_even32(float a, float b) {   // of two adjacent floats, the one with the even significand
+    uint32_t ua; std::memcpy(&ua, &a, 4);
+    return (ua & 1u) ? b : a;
+}
+
+// X / den rounded to f32 once, X exact (den > 0; den = 1 for a plain sum), and whether X / den lies within `bound` of
+// an f32 rounding midpoint.  sign(X - den * m) is evaluated exactly for the candidate midpoints m.
+float x32(const XSum& X, double den, double bound, bool* ambiguous) {
+    auto side = [&](double m) {   // sign of X - den * m, and |X - den * m| / den
+        XSum c = X;
+        two_prod(den, m, c, -1.0);
+        return c.value() / den;
+    };
+    float f = (float)(X.value() / den);
+    double lo, hi, dlo, dhi;
+    for (int step = 0; step < 4; ++step) {    // the estimate is within a few f64 ulps: at most one step is ever taken
+        midpoints32(f, lo, hi);
+        dlo = side(lo); dhi = side(hi);
+        if (dhi > 0.0) f = std::nextafter(f, INFINITY);
+        else if (dlo < 0.0) f = std::nextafter(f, -INFINITY);
+        else break;
+    }
+    if (dhi == 0.0) f = tie_even32(f, std::nextafter(f, INFINITY));
+    else if (dlo == 0.0) f = tie_even32(f, std::nextafter(f, -INFINITY));
+    if (ambiguous && bound > 0.0 && std::min(std::fabs(dlo), std::fabs(dhi)) <= bound) *ambiguous = true;
+    return f;
+}
+
+// most additions a term passes through in the device's ICP tree for ns source points (any path: up to 4 points per lane,
+// the wave's 6 DPP levels, 2 in the block, 4 per 128-slab round of the fold and 5 more levels; k_icp_small's tree is shallower)
+inline int icp_tree_depth(int ns) { return 20 + 4 * ((((ns + 255) / 256) + 127) / 128); }
+// ... and in k_ransac_rmse_partial / _final (6 shuffle levels, 2 in the block; the final kernel's strided loop and 8 levels)
+inline int ransac_tree_depth(int ns) { return 20 + (((ns + 255) / 256) + 255) / 256; }
 
 }  // namespace
 
@@ -380,11 +484,15 @@ void orc_hypothesis_from_pairs(const float* s3x3, const float* t3x3, float* T) {
 // running the feature match (lets tests isolate the hypothesis loop).  Optional traces:
 // trace_inliers[max_iterations] (-1 for skipped iterations, untouched past an early exit),
 // out_corr[ns], out_best_iter, out_iters_run.
-void orc_ransac(const float* src, int ns, const float* tgt, int nt,
-                const float* fs, const float* ft, const int* corr_in,
-                float voxel_size, int max_iterations, float confidence,
-                float* T_out, float* fitness_out, float* rmse_out,
-                int* trace_inliers, int* out_corr, int* out_best_iter, int* out_iters_run) {
+// exact != 0: the winner's error sum (err * err over its inliers, registration.cpp:275-282) is summed exactly and
+// rounded to f32 once; *ambiguous_out (optional): whether it lies within the device tree's error bound of an f32
+// rounding midpoint (see XSum).  Everything else is unchanged.
+static void ransac_impl(const float* src, int ns, const float* tgt, int nt,
+                        const float* fs, const float* ft, const int* corr_in,
+                        float voxel_size, int max_iterations, float confidence,
+                        float* T_out, float* fitness_out, float* rmse_out,
+                        int* trace_inliers, int* out_corr, int* out_best_iter, int* out_iters_run, int exact, int* ambiguous_out) {
+    if (ambiguous_out) *ambiguous_out = 0;
     float distance_threshold = voxel_size * 1.5f;
     std::vector<size_t> corr(ns);
     if (corr_in) for (int i = 0; i < ns; ++i) corr[i] = corr_in[i];
@@ -426,10 +534,43 @@ void orc_ransac(const float* src, int ns, const float* tgt, int nt,
         }
         if (fitness > confidence) break;
     }
+    if (exact && best_iter >= 0) {
+        M3 R; float t[3];
+        for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) R(r, c) = bestT[c * 4 + r];
+        for (int r = 0; r < 3; ++r) t[r] = bestT[12 + r];
+        int inliers = 0;
+        XSum total_error;
+        for (int i = 0; i < ns; ++i) {
+            float p[3]; mulv(R, src + 3 * i, p);
+            for (int a = 0; a < 3; ++a) p[a] += t[a];
+            float err = std::sqrt(sqnorm_diff(p, tgt + 3 * corr[i]));
+            if (err < distance_threshold) { ++inliers; total_error.add(err * err); }
+        }
+        bool amb = false;
+        const float te = x32(total_error, 1.0, total_error.tree_bound(ransac_tree_depth(ns)), &amb);
+        best_rmse = inliers > 0 ? std::sqrt(te / inliers) : 999.0f;
+        if (ambiguous_out) *ambiguous_out = amb ? 1 : 0;
+    }
     std::memcpy(T_out, bestT, 64);
     *fitness_out = best_fitness; *rmse_out = best_rmse;
     if (out_best_iter) *out_best_iter = best_iter;
     if (out_iters_run) *out_iters_run = iters_run;
+}
+void orc_ransac(const float* src, int ns, const float* tgt, int nt,
+                const float* fs, const float* ft, const int* corr_in,
+                float voxel_size, int max_iterations, float confidence,
+                float* T_out, float* fitness_out, float* rmse_out,
+                int* trace_inliers, int* out_corr, int* out_best_iter, int* out_iters_run) {
+    ransac_impl(src, ns, tgt, nt, fs, ft, corr_in, voxel_size, max_iterations, confidence, T_out, fitness_out, rmse_out,
+                trace_inliers, out_corr, out_best_iter, out_iters_run, 0, nullptr);
+}
+void orc_ransac_ex(const float* src, int ns, const float* tgt, int nt,
+                   const float* fs, const float* ft, const int* corr_in,
+                   float voxel_size, int max_iterations, float confidence,
+                   float* T_out, float* fitness_out, float* rmse_out,
+                   int* trace_inliers, int* out_corr, int* out_best_iter, int* out_iters_run, int exact, int* ambiguous_out) {
+    ransac_impl(src, ns, tgt, nt, fs, ft, corr_in, voxel_size, max_iterations, confidence, T_out, fitness_out, rmse_out,
+                trace_inliers, out_corr, out_best_iter, out_iters_run, exact, ambiguous_out);
 }
 
 // ---------------------------------------------------------------- ICP
@@ -474,10 +615,19 @@ void orc_icp_correspondences(const float* src, int ns, const float* tgt, const f
 
 // registration.cpp:297-414.  tgt_normals may be NULL (hasNormals() false).
 // trace (optional): per iteration 20 floats = T after the update (16, column-major), rmse,
-// fitness, n_corr, 0.  Returns the number of iterations whose update was applied.
-int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
-            const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
-            float* T_out, float* fitness_out, float* rmse_out, float* trace) {
+// fitness, n_corr, ambiguous.  Returns the number of iterations whose update was applied.
+//
+// exact != 0: the exact-sum mode (see XSum).  n_corr, total_error, the 21 + 6 point-to-plane terms (each product
+// rounded to f32 as below) are summed exactly and rounded to f32 once.  Point-to-point follows the device's algebra
+// (csrc/icp.hip: icp_update): the means are f32(f64(sum P) / n), H[a][b] = f32(sum P_a Q_b - sum P_a sum Q_b / n)
+// from exact sums.  Solve, rotation, composition, rmse, fitness and the stopping rule are the code below.  trace[19]
+// is 1 for an iteration where some rounded value lies within the device tree's error bound of an f32 rounding
+// midpoint (the device may then round the other way), else 0; *ambiguous_out (optional) ORs them over the run.
+static int icp_impl(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
+                    const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
+                    float* T_out, float* fitness_out, float* rmse_out, float* trace, int exact, int* ambiguous_out) {
+    if (ambiguous_out) *ambiguous_out = 0;
+    const int depth = icp_tree_depth(ns);
     float T[16]; std::memcpy(T, T0, 64);
     float res_T[16]; std::memcpy(res_T, T, 64);
     float res_fitness = 0.f, res_rmse = 0.f;
@@ -490,6 +640,7 @@ int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals
         for (int r = 0; r < 3; ++r) t[r] = T[12 + r];
         int n_corr = 0; float total_error = 0;
         float ATA[36] = {0}, ATb[6] = {0};
+        XSum x_err, x_ata[21], x_atb[6], x_p[3], x_q[3], x_pq[9];   // exact mode
         sc.clear(); tc.clear();
         for (int i = 0; i < ns; ++i) {
             float p[3]; mulv(R, src + 3 * i, p);
@@ -501,20 +652,39 @@ int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals
             }
             float d = std::sqrt(best);
             if (d > distance_threshold) continue;
-            ++n_corr; total_error += best;
+            ++n_corr;
+            if (exact) x_err.add(best); else total_error += best;
             if (p2pl) {
                 const float* q = tgt + 3 * bi; const float* n = tgt_normals + 3 * bi;
                 float J[6] = {p[1] * n[2] - p[2] * n[1], p[2] * n[0] - p[0] * n[2], p[0] * n[1] - p[1] * n[0], n[0], n[1], n[2]};
                 float pq[3] = {p[0] - q[0], p[1] - q[1], p[2] - q[2]};
                 float residual = dot3(pq, n);
-                for (int r = 0; r < 6; ++r) { for (int c = 0; c < 6; ++c) ATA[r * 6 + c] += J[r] * J[c]; ATb[r] += J[r] * residual; }
+                if (exact) {
+                    int k = 0;
+                    for (int r = 0; r < 6; ++r) { for (int c = r; c < 6; ++c) x_ata[k++].add(J[r] * J[c]); x_atb[r].add(J[r] * residual); }
+                } else {
+                    for (int r = 0; r < 6; ++r) { for (int c = 0; c < 6; ++c) ATA[r * 6 + c] += J[r] * J[c]; ATb[r] += J[r] * residual; }
+                }
+            } else if (exact) {
+                const float* q = tgt + 3 * bi;
+                for (int a = 0; a < 3; ++a) { x_p[a].add(p[a]); x_q[a].add(q[a]); }
+                for (int a = 0; a < 3; ++a) for (int b = 0; b < 3; ++b) x_pq[a * 3 + b].add((double)p[a] * (double)q[b]);  // exact in double
             } else {
                 for (int a = 0; a < 3; ++a) { sc.push_back(p[a]); tc.push_back(tgt[3 * bi + a]); }
             }
         }
+        bool amb = false;
+        if (exact) total_error = x32(x_err, 1.0, x_err.tree_bound(depth), &amb);
         if (n_corr < 3) break;
         float delta[16]; set_identity44(delta);
         if (p2pl) {
+            if (exact) {
+                int k = 0;
+                for (int r = 0; r < 6; ++r) {
+                    for (int c = r; c < 6; ++c, ++k) ATA[r * 6 + c] = ATA[c * 6 + r] = x32(x_ata[k], 1.0, x_ata[k].tree_bound(depth), &amb);
+                    ATb[r] = x32(x_atb[r], 1.0, x_atb[r].tree_bound(depth), &amb);
+                }
+            }
             float nb[6], x[6];
             for (int i = 0; i < 6; ++i) nb[i] = -ATb[i];
             ldlt6_solve(ATA, nb, x);
@@ -522,15 +692,43 @@ int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals
             for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) delta[c * 4 + r] = dR(r, c);
             for (int r = 0; r < 3; ++r) delta[12 + r] = x[3 + r];
         } else {
-            size_t m = sc.size() / 3;
             float sm[3] = {0, 0, 0}, tm[3] = {0, 0, 0};
-            for (size_t i = 0; i < m; ++i) for (int a = 0; a < 3; ++a) { sm[a] += sc[3 * i + a]; tm[a] += tc[3 * i + a]; }
-            for (int a = 0; a < 3; ++a) { sm[a] /= static_cast<float>(m); tm[a] /= static_cast<float>(m); }
             M3 H; for (int a = 0; a < 9; ++a) H.m[a] = 0.f;
-            for (size_t i = 0; i < m; ++i) {
-                float a3[3] = {sc[3 * i] - sm[0], sc[3 * i + 1] - sm[1], sc[3 * i + 2] - sm[2]};
-                float b3[3] = {tc[3 * i] - tm[0], tc[3 * i + 1] - tm[1], tc[3 * i + 2] - tm[2]};
-                for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) H(r, c) += a3[r] * b3[c];
+            if (exact) {
+                // device (icp_update<1, false>): sm = f64(sum P) / n in f64, H = f32(sum PQ - n * sm * tm) in f64
+                const double n = (double)n_corr, u = std::ldexp(1.0, -53);
+                double SP[3], SQ[3], BP[3], BQ[3];
+                for (int a = 0; a < 3; ++a) {
+                    SP[a] = x_p[a].value(); SQ[a] = x_q[a].value();
+                    BP[a] = x_p[a].tree_bound(depth); BQ[a] = x_q[a].tree_bound(depth);
+                    sm[a] = (float)(SP[a] / n); tm[a] = (float)(SQ[a] / n);
+                    // the f32 of the f64 quotient: ambiguous if sum / n lies within (device error of the sum) / n + 2 f64 ulps of a
+                    // midpoint; an exact f64 sum (bound 0) gives the device this very quotient
+                    x32(x_p[a], n, BP[a] > 0.0 ? BP[a] / n + 4.0 * u * std::fabs(SP[a] / n) : 0.0, &amb);
+                    x32(x_q[a], n, BQ[a] > 0.0 ? BQ[a] / n + 4.0 * u * std::fabs(SQ[a] / n) : 0.0, &amb);
+                }
+                for (int a = 0; a < 3; ++a)
+                    for (int b = 0; b < 3; ++b) {
+                        // X = n * sum P_a Q_b - sum P_a * sum Q_b, exactly; H = X / n rounded once
+                        const XSum& pq = x_pq[a * 3 + b];
+                        XSum X;
+                        for (double v : pq.p) two_prod(v, n, X, 1.0);
+                        for (double v : x_p[a].p) for (double w : x_q[b].p) two_prod(v, w, X, -1.0);
+                        const double cen = std::fabs(SP[a]) * std::fabs(SQ[b]) / n;
+                        const double B = pq.tree_bound(depth) + (std::fabs(SP[a]) * BQ[b] + std::fabs(SQ[b]) * BP[a] + BP[a] * BQ[b]) / n +
+                                         5.0 * u * (cen + (std::fabs(SP[a]) + BP[a]) * (std::fabs(SQ[b]) + BQ[b]) / n) +
+                                         2.0 * u * (std::fabs(pq.value()) + pq.tree_bound(depth));
+                        H(a, b) = x32(X, n, 1.01 * B, &amb);
+                    }
+            } else {
+                size_t m = sc.size() / 3;
+                for (size_t i = 0; i < m; ++i) for (int a = 0; a < 3; ++a) { sm[a] += sc[3 * i + a]; tm[a] += tc[3 * i + a]; }
+                for (int a = 0; a < 3; ++a) { sm[a] /= static_cast<float>(m); tm[a] /= static_cast<float>(m); }
+                for (size_t i = 0; i < m; ++i) {
+                    float a3[3] = {sc[3 * i] - sm[0], sc[3 * i + 1] - sm[1], sc[3 * i + 2] - sm[2]};
+                    float b3[3] = {tc[3 * i] - tm[0], tc[3 * i + 1] - tm[1], tc[3 * i + 2] - tm[2]};
+                    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) H(r, c) += a3[r] * b3[c];
+                }
             }
             M3 dR = kabsch_rotation(H);
             float Rs[3]; mulv(dR, sm, Rs);
@@ -545,13 +743,37 @@ int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals
         applied = iter + 1;
         if (trace) {
             float* tr = trace + (size_t)iter * 20;
-            std::memcpy(tr, T, 64); tr[16] = res_rmse; tr[17] = res_fitness; tr[18] = (float)n_corr; tr[19] = 0.f;
+            std::memcpy(tr, T, 64); tr[16] = res_rmse; tr[17] = res_fitness; tr[18] = (float)n_corr; tr[19] = amb ? 1.f : 0.f;
         }
+        if (amb && ambiguous_out) *ambiguous_out = 1;
         if (iter > 0 && std::abs(prev_rmse - res_rmse) < 1e-6f) break;
     }
     std::memcpy(T_out, res_T, 64);
     *fitness_out = res_fitness; *rmse_out = res_rmse;
     return applied;
+}
+int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
+            const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
+            float* T_out, float* fitness_out, float* rmse_out, float* trace) {
+    return icp_impl(src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, T_out, fitness_out, rmse_out,
+                    trace, 0, nullptr);
+}
+int orc_icp_ex(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
+               const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
+               float* T_out, float* fitness_out, float* rmse_out, float* trace, int exact, int* ambiguous_out) {
+    return icp_impl(src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, T_out, fitness_out, rmse_out,
+                    trace, exact, ambiguous_out);
+}
+
+// exact sum of x[0..n) (math.fsum's value) -> *f64; rounded to f32 once -> *f32; *ambiguous: whether the sum lies within
+// the error bound of a `depth`-level f64 tree of an f32 rounding midpoint (tests of the exact-sum mode)
+void orc_exact_sum(const double* x, int n, int depth, double* f64, float* f32, int* ambiguous) {
+    XSum s;
+    for (int i = 0; i < n; ++i) s.add(x[i]);
+    bool amb = false;
+    *f64 = s.value();
+    *f32 = x32(s, 1.0, s.tree_bound(depth), &amb);
+    *ambiguous = amb ? 1 : 0;
 }
 
 // ---------------------------------------------------------------- neighbours of the path

@@ -38,6 +38,7 @@ def lib():
         _LIB.orc_voxel_downsample.restype = C.c_int
         _LIB.orc_self_adjoint_eig3.restype = C.c_int
         _LIB.orc_icp.restype = C.c_int
+        _LIB.orc_icp_ex.restype = C.c_int
         _LIB.orc_filter_duplicates.restype = C.c_int
         _LIB.orc_load_ply.restype = C.c_int
     return _LIB
@@ -194,21 +195,34 @@ def sample_triples(n, count, seed=42):
     return out
 
 
-def ransac(src, tgt, fs=None, ft=None, corr=None, voxel=0.001, max_iterations=100000, confidence=0.999, trace=False):
+def ransac(src, tgt, fs=None, ft=None, corr=None, voxel=0.001, max_iterations=100000, confidence=0.999, trace=False, exact=False):
+    """exact=True: the winner's rmse from its error sum taken exactly and rounded to f32 once (the device's f64 tree sum
+    rounds the same way unless the result's `rmse_ambiguous` is True; see oracle.cpp: XSum)."""
     src = _f32(src); tgt = _f32(tgt); fs = _f32(fs); ft = _f32(ft)
     c = None if corr is None else np.ascontiguousarray(corr, np.int32)
     T = np.zeros(16, np.float32); fit = C.c_float(); rmse = C.c_float()
     tr = np.full(max_iterations, -2, np.int32) if trace else None
     oc = np.empty(len(src), np.int32)
-    bi = C.c_int(); ir = C.c_int()
-    lib().orc_ransac(_p(src), len(src), _p(tgt), len(tgt), _p(fs), _p(ft), _p(c),
-                     C.c_float(voxel), max_iterations, C.c_float(confidence),
-                     _p(T), C.byref(fit), C.byref(rmse), _p(tr), _p(oc), C.byref(bi), C.byref(ir))
+    bi = C.c_int(); ir = C.c_int(); amb = C.c_int()
+    lib().orc_ransac_ex(_p(src), len(src), _p(tgt), len(tgt), _p(fs), _p(ft), _p(c),
+                        C.c_float(voxel), max_iterations, C.c_float(confidence),
+                        _p(T), C.byref(fit), C.byref(rmse), _p(tr), _p(oc), C.byref(bi), C.byref(ir), int(exact), C.byref(amb))
     res = dict(T=from_colmajor16(T), fitness=np.float32(fit.value), rmse=np.float32(rmse.value),
                corr=oc, best_iter=bi.value, iters_run=ir.value)
+    if exact:
+        res["rmse_ambiguous"] = bool(amb.value)
     if trace:
         res["inliers"] = tr
     return res
+
+
+def exact_sum(terms, depth):
+    """The exact sum of float64 terms: (its correctly rounded float64 - math.fsum's value, its float32 rounded once, whether it lies
+    within the error bound of a `depth`-level float64 tree sum of an f32 rounding midpoint)."""
+    x = np.ascontiguousarray(terms, np.float64)
+    f64 = C.c_double(); f32 = C.c_float(); amb = C.c_int()
+    lib().orc_exact_sum(_p(x), len(x), int(depth), C.byref(f64), C.byref(f32), C.byref(amb))
+    return f64.value, np.float32(f32.value), bool(amb.value)
 
 
 def icp_correspondences(src, tgt, tgt_normals, T, thr, point_to_plane=True):
@@ -223,14 +237,19 @@ def icp_correspondences(src, tgt, tgt_normals, T, thr, point_to_plane=True):
                 ATA=ATA.reshape(6, 6), ATb=ATb)
 
 
-def icp(src, tgt, tgt_normals, T0, thr, max_iterations=200, point_to_plane=True, trace=False):
+def icp(src, tgt, tgt_normals, T0, thr, max_iterations=200, point_to_plane=True, trace=False, exact=False):
+    """exact=True: the exact-sum mode (oracle.cpp: icp_impl), what the device's f64 tree sums give bit for bit unless the
+    result's `ambiguous` is True (some sum within the tree's error bound of an f32 rounding midpoint; per iteration in
+    trace[:, 19])."""
     src = _f32(src); tgt = _f32(tgt); tn = _f32(tgt_normals)
-    T = np.zeros(16, np.float32); fit = C.c_float(); rmse = C.c_float()
+    T = np.zeros(16, np.float32); fit = C.c_float(); rmse = C.c_float(); amb = C.c_int()
     tr = np.zeros((max_iterations, 20), np.float32) if trace else None
     t0 = to_colmajor16(T0)
-    it = lib().orc_icp(_p(src), len(src), _p(tgt), _p(tn), len(tgt), _p(t0), C.c_float(thr), max_iterations,
-                       int(point_to_plane), _p(T), C.byref(fit), C.byref(rmse), _p(tr))
+    it = lib().orc_icp_ex(_p(src), len(src), _p(tgt), _p(tn), len(tgt), _p(t0), C.c_float(thr), max_iterations,
+                          int(point_to_plane), _p(T), C.byref(fit), C.byref(rmse), _p(tr), int(exact), C.byref(amb))
     res = dict(T=from_colmajor16(T), fitness=np.float32(fit.value), rmse=np.float32(rmse.value), iterations=it)
+    if exact:
+        res["ambiguous"] = bool(amb.value)
     if trace:
         res["trace"] = tr[:it]
     return res
