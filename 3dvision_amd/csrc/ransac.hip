@@ -239,10 +239,13 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 //                         chunks (= what a job-A workgroup of that batch walked, so all workgroups of a dispatch cost the same).
 // By default the two jobs are dispatched one after the other (job B alone, see ransac_run_dev); with TDV_RANSAC_MERGE=1 job B
 // rides behind the NEXT batch's job A.
+//   job B also scores phase 1 of a batch whose dead hypotheses k_ransac_bound has taken out (RansacLeafBound, below): n_live set,
+//                         the live list (*n_live of them) over the chunks [0, plan[0]) in ranges cut for that many blocks.
 struct ScoreJob {
     const float* hyp; int* counts; const int* plan; const int* list;
-    int hb;      // hypothesis blocks (A: of the batch; B: upper bound - the real number comes from plan[1])
+    int hb;      // hypothesis blocks (A: of the batch; B: upper bound - the real number comes from plan[1] or *n_live)
     int ps;      // A: point ranges
+    const int* n_live;   // B: phase 1 over the live list (nullptr: phase 2)
 };
 // One block of hypotheses (lane = hypothesis `base`, -1: none) over the chunks [c0, c1) of the point pairs; returns the lane's
 // inlier count, adds the point PAIRS the wave scored twice to n_rescored (wave-uniform; RS_PCH / 2 per chunk that was re-scored whole).
@@ -371,16 +374,20 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         // are therefore dealt so that an XCD (workgroup id mod 8) runs ALL surviving blocks of one range next to each other; a
         // workgroup takes every (job-B workgroups / 8)-th item of its XCD, so any grid of at least 8 workgroups covers any
         // number of survivors and any prefix.
-        const int n_list = b.plan[1];
+        const int n_list = b.n_live ? *b.n_live : b.plan[1];
         const int n_blk = (n_list + RS_BLOCK - 1) / RS_BLOCK;
         if (n_blk == 0) return;
         const int j0 = id - g1, xcd = j0 & 7, stride = ((int)gridDim.x - g1) >> 3;
-        const int c_split = b.plan[0], per = max(b.plan[3], 1);
-        const int ranges = (n_pchunks - c_split + per - 1) / per;
+        // phase 2: the chunks [plan[0], n_pchunks) in ranges of plan[3]; phase 1 of the live list: [0, plan[0]) in as many ranges
+        // as a job A of n_blk blocks would cut (ranges_for in ransac_run_dev)
+        const int r0 = b.n_live ? 0 : b.plan[0], r1 = b.n_live ? b.plan[0] : n_pchunks;
+        const int ps_live = min(min((RS_WG_TARGET + n_blk - 1) / n_blk, max(1, n_pchunks / 32)), 512);
+        const int per = b.n_live ? max((r1 + ps_live - 1) / ps_live, 1) : max(b.plan[3], 1);
+        const int ranges = (r1 - r0 + per - 1) / per;
         for (int t = j0 >> 3; ; t += stride) {
             const int split = (t / n_blk) * 8 + xcd, hblock = t % n_blk;
             if (split >= ranges) break;                              // workgroup-uniform
-            const int c0 = c_split + split * per, c1 = min(n_pchunks, c0 + per);
+            const int c0 = r0 + split * per, c1 = min(r1, c0 + per);
             const int slot = hblock * RS_BLOCK + threadIdx.x;
             const int base = slot < n_list ? b.list[slot] : -1;
             const int cnt = score_range_fast(b.hyp, h_pad, base, pq2, c0, c1, tau, n_rescored);
@@ -412,8 +419,9 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
 // state[0] = best count known so far (a lower bound of the best count of every batch already enqueued: full counts of the
 // batches that are complete, prefix counts of the one whose phase 2 is still to run).  plan = { chunks in phase 1, survivors,
 // largest PREFIX count of this batch, chunks per workgroup } - one plan per batch buffer, the state shared.
-__global__ void k_ransac_plan(int* __restrict__ state, int* __restrict__ plan, int ns, int n_pchunks, int ps, int drop_permille) {
+__global__ void k_ransac_plan(int* __restrict__ state, int* __restrict__ plan, int ns, int n_pchunks, int ps, int drop_permille, int* __restrict__ n_live) {
     const int best = state[0];
+    if (n_live) *n_live = 0;                                  // (RansacLeafBound: k_ransac_bound appends to it next)
     int c_split = n_pchunks;
     const int rest = best - max((int)((long long)best * drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
     if (rest >= ns / 8)                                      // (below an eighth of the points a second phase costs more than it saves)
@@ -450,14 +458,16 @@ void k_ransac_best(const int4* __restrict__ triples, int count, const int* __res
 //       that fires at a kept iteration e returns e itself: anything earlier with at least its count would have ended the loop
 //       before, and every dropped iteration has a count below the confidence bar that e passed.  [round 3]
 // Either way the counts of the dropped hypotheses stay partial and compare as the true ones would: below the result's.
+// With RansacLeafBound, bnd[h] is a second upper bound of the full count (k_ransac_bound; INT_MAX where it has none): a dead
+// hypothesis, never scored, has bnd <= best and is dropped by rule (a) - it never enters phase 2.
 __global__ void k_ransac_select(const int4* __restrict__ triples, int count, const int* __restrict__ counts, int ns, float confidence,
-                                const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list) {
+                                const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list, const int* __restrict__ bnd) {
     const int h = blockIdx.x * blockDim.x + threadIdx.x;
     const int c_split = plan[0], best = state[0], in_batch = plan[2];
     const int rest = max(0, ns - min(ns, c_split * RS_PCH));     // (the padding past ns is never an inlier)
     bool keep = h < count && triples[h].w != 0 && rest > 0;
     if (keep) {
-        const int ub = counts[h] + rest;
+        const int ub = bnd ? min(counts[h] + rest, bnd[h]) : counts[h] + rest;
         const bool passes = static_cast<float>(ub) / static_cast<float>((size_t)ns) > confidence;   // registration.cpp:281,290 on the bound
         keep = ub > best && (ub >= in_batch || passes);
     }
@@ -468,6 +478,203 @@ __global__ void k_ransac_select(const int4* __restrict__ triples, int count, con
     if (lane == 0) at = atomicAdd(&plan[1], __popcll(m));
     at = __shfl(at, 0, 64);
     if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
+}
+
+// ------------------------------------------------------------------ RansacLeafBound
+// Rule (a) above needs only an UPPER bound of a hypothesis' count.  The bail-out's bound is "every unscored point is an
+// inlier"; this one is far tighter and costs a few percent of a full scoring.  Once per call the point pairs (p, q) are
+// ordered along a 6-D Morton curve (5 bits per coordinate, the curve over the pairs' own bounding box) and cut into leaves
+// of RL_LEAF pairs; a leaf keeps its p box (centre, half-extent), its q box (lo, hi) and its number of pairs.  Per batch,
+// k_ransac_bound adds up, for each hypothesis, the sizes of the leaves whose boxes could hold an inlier: UB(h).  A hypothesis
+// with UB(h) <= best count of the EARLIER batches is dead: it is not scored at all, its count stays 0, and k_ransac_select
+// drops it like any other hypothesis of rule (a).  Only the summary is reordered: pq / pq2, the hypotheses, the scoring and
+// the rmse pass keep the original order, so every count and every sum keeps its bits.
+//
+// Exactness.  A leaf fails only if g2 > Tb, g2 the squared length of the per-axis gaps between the interval R [pc - pe,
+// pc + pe] + t and [qlo, qhi] evaluated in f32, Tb = (s + 3E)^2 (1 + 1e-6), s = sqrt(tau) rounded up, E = 16 u (A + s) the
+// band of k_ransac_hypotheses (A = max over rows of (|r0| + |r1| + |r2|) P + |t|, P = the largest |source coordinate|).
+//   (1) f32 evaluation of the bound.  xc = R pc + t and xe = |R| pe as FMA chains are within gamma_3 A of their real values
+//       (|pc|, pe <= P), xc -+ xe one more rounding (<= 2 u A), the subtraction of qlo/qhi one relative rounding: each f32 gap
+//       exceeds (1 + u) times (real gap + 8.1 u A), and |gap_f32| <= (1 + u) |gap| + 14.1 u A; the squared norm (three
+//       roundings) adds a factor (1 + 2 u) in length.  So sqrt(g2) <= (1 + 3 u) G + 14.2 u A, G the real gap length - a lower
+//       bound of |R p + t - q| for every pair of the leaf.  (Even with every operation unfused - were the compiler to split
+//       the FMAs - the chains stay within gamma_4 and the total within 18 u A.)
+//   (2) the reference's rounding.  d2_ref = fl((x_ref - qx)^2 + ...) with x_ref within gamma_4 A of the real value: in
+//       distance sqrt(d2_ref) >= D (1 - 3 u) - 7 u A, D = |R p + t - q| (real).  D >= s + E therefore gives d2_ref >= s^2 >= tau.
+// g2 > Tb gives sqrt(g2) > s + 3E, so G > (s + 3E - 18 u A) / (1 + 3 u) >= s + E (E >= 16 u A + 16 u s, E < s / 4): every
+// pair of the leaf has D >= s + E and is no inlier in the reference arithmetic.  The margin (3E against the band's E) is at
+// least as conservative as the band; tests/test_ransac_leaf_bound_margin.py checks (1) and (2) in emulated f32 on leaves
+// whose boxes touch the threshold shell.  Where the band is off (non-finite data, coordinates far from the origin: E not
+// below s / 4) the bound is off too: the hypothesis is live.  A leaf with any non-finite coordinate always passes.
+constexpr int RL_LEAF = 32;          // pairs per leaf (the study: 32 prunes 11.7 % -> 15 % survivors at 64)
+constexpr int RL_BITS = 5;           // Morton bits per coordinate (30-bit key)
+__device__ __forceinline__ unsigned rl_enc(float f) { const unsigned b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }   // order-preserving
+__device__ __forceinline__ float rl_dec(unsigned e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
+// per-axis bounds of the finite coordinates of p and q: enc[0..5] = min (memset to 0xff), enc[6..11] = max (memset to 0)
+__global__ __launch_bounds__(256)
+void k_leaf_bounds(const float* __restrict__ pq, int ns, unsigned* __restrict__ enc) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    __shared__ unsigned s_enc[12];
+    if (threadIdx.x < 12) s_enc[threadIdx.x] = threadIdx.x < 6 ? 0xffffffffu : 0u;
+    __syncthreads();
+    unsigned lo[6], hi[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        lo[c] = 0xffffffffu; hi[c] = 0u;
+        if (i < ns) {
+            const float v = pq[(size_t)i * 8 + c];
+            if (fabsf(v) <= FLT_MAX) { lo[c] = rl_enc(v); hi[c] = lo[c]; }
+        }
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { lo[c] = min(lo[c], (unsigned)__shfl_xor((int)lo[c], off, 64)); hi[c] = max(hi[c], (unsigned)__shfl_xor((int)hi[c], off, 64)); }
+    }
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { atomicMin(&s_enc[c], lo[c]); atomicMax(&s_enc[6 + c], hi[c]); }
+    __syncthreads();
+    if (threadIdx.x < 12) {
+        const unsigned v = s_enc[threadIdx.x];
+        if (threadIdx.x < 6) { if (v != 0xffffffffu) atomicMin(&enc[threadIdx.x], v); }
+        else if (v != 0u) atomicMax(&enc[threadIdx.x], v);
+    }
+}
+// 6-D Morton key of every pair (bit 6 b + c = bit b of coordinate c's cell); a non-finite coordinate takes cell 0
+__global__ __launch_bounds__(256)
+void k_leaf_keys(const float* __restrict__ pq, int ns, const unsigned* __restrict__ enc, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= ns) return;
+    unsigned key = 0u;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const float lo = rl_dec(enc[c]), hi = rl_dec(enc[6 + c]);
+        const float v = pq[(size_t)i * 8 + c];
+        int cell = 0;
+        if (fabsf(v) <= FLT_MAX && hi > lo) cell = min(max((int)((v - lo) * ((float)(1 << RL_BITS) / (hi - lo))), 0), (1 << RL_BITS) - 1);
+#pragma unroll
+        for (int b = 0; b < RL_BITS; ++b) key |= (unsigned)((cell >> b) & 1) << (6 * b + c);
+    }
+    keys[i] = key; vals[i] = (unsigned)i;
+}
+// One leaf per RL_LEAF sorted pairs, 16 values {pc, n, pe, 0, qlo, 0, qhi, 0}, stored in PAIRS of leaves with the two leaves'
+// values interleaved (value v of leaf 2k + j at [32 k + 2 v + j]) so that k_ransac_bound reads aligned SGPR pairs for its packed
+// instructions; the buffer is zeroed first, so an odd last leaf is paired with an empty one (n = 0).  A leaf with a non-finite
+// coordinate gets pc = pe = 0 and the q box (-inf, inf): it passes for every finite hypothesis.
+__global__ __launch_bounds__(256)
+void k_leaf_build(const float* __restrict__ pq, int ns, const unsigned* __restrict__ order, float* __restrict__ leaves) {
+    const int i = blockIdx.x * 256 + threadIdx.x;     // sorted position; the grid covers whole leaves
+    float lo[6], hi[6];
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { lo[c] = INFINITY; hi[c] = -INFINITY; }
+    if (i < ns) {
+        const float* g = pq + (size_t)order[i] * 8;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { const float v = g[c]; lo[c] = v; hi[c] = v; bad |= !(fabsf(v) <= FLT_MAX); }
+    }
+#pragma unroll
+    for (int off = RL_LEAF / 2; off > 0; off >>= 1) {        // within the leaf's 32 lanes (half a wave)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], off, 64)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], off, 64)); }
+        bad |= __shfl_xor((int)bad, off, 64) != 0;
+    }
+    if ((threadIdx.x & (RL_LEAF - 1)) || i >= ns) return;
+    const int n = min(RL_LEAF, ns - i), leaf = i / RL_LEAF;
+    float* o = leaves + (size_t)(leaf >> 1) * 32 + (leaf & 1);
+    o[6] = (float)n;
+    if (bad) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { o[2 * c] = 0.f; o[8 + 2 * c] = 0.f; o[16 + 2 * c] = -INFINITY; o[24 + 2 * c] = INFINITY; }
+        return;
+    }
+    float pc[3], pe[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        pc[c] = 0.5f * lo[c] + 0.5f * hi[c];
+        // half-extent rounded up past the exact max(hi - pc, pc - lo): every p of the leaf lies in [pc - pe, pc + pe]
+        const double d = fmax((double)hi[c] - (double)pc[c], (double)pc[c] - (double)lo[c]);
+        pe[c] = nextafterf((float)d, INFINITY);
+    }
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { o[2 * c] = pc[c]; o[8 + 2 * c] = pe[c]; o[16 + 2 * c] = lo[3 + c]; o[24 + 2 * c] = hi[3 + c]; }
+}
+// A workgroup per 64 hypotheses (lane = hypothesis), its RB_SPLIT waves walking RB_SPLIT ranges of the leaf pairs; leaf values are
+// wave-uniform (scalar loads), two leaves per packed instruction.  A lane stops adding once its partial bound exceeds the best count
+// of the earlier batches (the hypothesis is live then: the whole bound can only be larger); a wave stops when every lane has, so
+// where nothing can be pruned the pass ends early by itself.  The partial bounds meet in LDS.  Writes bnd[h] (the full bound of a
+// dead hypothesis, INT_MAX for a live one, 0 for a skipped iteration) and appends the live hypotheses to `live` (*n_live of them,
+// zeroed by k_ransac_plan).  (One lane per hypothesis walking all the leaves alone gives one wave per SIMD for a 65,536-hypothesis
+// batch, every scalar load's latency exposed.)
+constexpr int RB_SPLIT = 16;
+__global__ __launch_bounds__(64 * RB_SPLIT)
+void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __restrict__ triples, int count, const float* __restrict__ leaves, int n_lpairs,
+                    const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
+                    int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = blockIdx.x * 64 + lane;
+    __shared__ int s_ub[64];
+    if (wave == 0) s_ub[lane] = 0;
+    const bool valid = h < count && triples[h].w != 0;
+    float r[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) r[e] = valid ? hyp[(size_t)e * h_pad + h] : 0.f;
+    // the band's E (k_ransac_hypotheses), from the same f32 operations
+    const float P = __uint_as_float(*pmax);
+    float A = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) A = fmaxf(A, (fabsf(r[c]) + fabsf(r[3 + c]) + fabsf(r[6 + c])) * P + fabsf(r[9 + c]));
+    const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
+    const bool bounded = E < 0.25f * sqrt_tau;                    // false for NaN (non-finite data or hypothesis)
+    const float sb = sqrt_tau + 3.f * E;
+    const float tb = sb * sb * (1.0f + 1e-6f);
+    const int best = state[0];
+    // Gate: with the best under a 32nd of the points nothing is pruned (true share 0.02: best 0.017 N), and the walk - whose RB_SPLIT
+    // partial sums each have to pass the best before a wave stops - cost 8.5 % there: every hypothesis is live without it.  At a true
+    // share of 0.1 (best 0.09 N) it still prunes 14 % of the tests and gains a point.
+    const bool walk = best >= ns / 32;
+    int ub = 0;
+    bool done = !valid || !bounded || !walk;
+    v2f rr[12], ar[9];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) rr[e] = (v2f){r[e], r[e]};
+#pragma unroll
+    for (int e = 0; e < 9; ++e) ar[e] = (v2f){fabsf(r[e]), fabsf(r[e])};
+    const int per = (n_lpairs + RB_SPLIT - 1) / RB_SPLIT, k0 = __builtin_amdgcn_readfirstlane(wave) * per, k1 = min(n_lpairs, k0 + per);   // (uniform: scalar loads)
+    for (int k = k0; k < k1; ++k) {
+        if (((k - k0) & 7) == 0 && !__any(!done)) break;
+        const float* __restrict__ g = leaves + (size_t)k * 32;
+        float v[32];
+#pragma unroll
+        for (int e = 0; e < 32; ++e) v[e] = g[e];
+        const v2f pcx = {v[0], v[1]}, pcy = {v[2], v[3]}, pcz = {v[4], v[5]};
+        const v2f pex = {v[8], v[9]}, pey = {v[10], v[11]}, pez = {v[12], v[13]};
+        v2f g2 = {0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const v2f xc = fma2(rr[c], pcx, fma2(rr[3 + c], pcy, fma2(rr[6 + c], pcz, rr[9 + c])));
+            const v2f xe = fma2(ar[c], pex, fma2(ar[3 + c], pey, ar[6 + c] * pez));
+            const v2f qlo = {v[16 + 2 * c], v[17 + 2 * c]}, qhi = {v[24 + 2 * c], v[25 + 2 * c]};
+            const v2f lo_gap = (xc - xe) - qhi, hi_gap = qlo - (xc + xe);
+            const v2f gp = {fmaxf(fmaxf(lo_gap.x, hi_gap.x), 0.f), fmaxf(fmaxf(lo_gap.y, hi_gap.y), 0.f)};
+            g2 = fma2(gp, gp, g2);
+        }
+        // a leaf fails only on g2 > tb; NaN passes
+        const int n2 = (!(g2.x > tb) ? (int)v[6] : 0) + (!(g2.y > tb) ? (int)v[7] : 0);
+        if (!done) { ub += n2; done = ub > best; }
+    }
+    __syncthreads();                                 // (s_ub zeroed)
+    if (ub) atomicAdd(&s_ub[lane], ub);
+    __syncthreads();
+    if (wave != 0 || h >= count) return;
+    const int total = s_ub[lane];
+    const bool is_live = valid && (!bounded || !walk || total > best);
+    bnd[h] = is_live ? INT_MAX : (valid ? total : 0);
+    const unsigned long long m = __ballot(is_live);
+    if (!m) return;
+    const int lead = (int)__builtin_ctzll(m);
+    int at = 0;
+    if (lane == lead) at = atomicAdd(n_live, __popcll(m));
+    at = __shfl(at, lead, 64);
+    if (is_live) live[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
 }
 
 #ifdef TDV_STUDY
@@ -727,6 +934,27 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     int* d_state = d_bad + 8;                       // [0] best count known so far
     int* d_plan[2] = {d_bad + 10, d_bad + 28};   // per batch buffer: phase-1 chunks, survivors, largest prefix count, chunks per workgroup
     const int drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 100;   // tuning knob (5 to 100 measured equal)
+    const bool merge_on = study_env("TDV_RANSAC_MERGE") && atoi(study_env("TDV_RANSAC_MERGE")) == 1;     // (study build; read per call: the tests switch it)
+    // RansacLeafBound: the leaf summary once per call, the bound in front of phase 1 of every batch after the first (whose best is 0)
+    const bool bound_env_off = getenv("TDV_RANSAC_BOUND") && atoi(getenv("TDV_RANSAC_BOUND")) == 0;   // A/B knob (read per call: the tests switch it)
+    const bool bound = bailout && !merge_on && !bound_env_off;
+    const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_lpairs = (n_leaves + 1) / 2;
+    float* leaves = nullptr;
+    if (bound) {
+        unsigned* enc = nullptr; unsigned long long* keys = nullptr; unsigned* vals = nullptr;
+        TDV_TRY(ws_alloc(ctx, 12, &enc));
+        TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &keys));
+        TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &vals));
+        TDV_TRY(ws_alloc(ctx, (size_t)n_lpairs * 32, &leaves));
+        TDV_HIP(ctx, hipMemsetAsync(leaves, 0, (size_t)n_lpairs * 32 * sizeof(float), s));
+        TDV_HIP(ctx, hipMemsetAsync(enc, 0xff, 24, s));
+        TDV_HIP(ctx, hipMemsetAsync(enc + 6, 0, 24, s));
+        k_leaf_bounds<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc);
+        k_leaf_keys<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc, keys, vals);
+        TDV_TRY(radix_sort_pairs_dev(ctx, keys, keys + ns, vals, vals + ns, (size_t)ns, 6 * RL_BITS));
+        k_leaf_build<<<(n_leaves * RL_LEAF + 255) / 256, 256, 0, s>>>(pq, ns, vals + ns, leaves);
+        TDV_CHECK_LAUNCH(ctx);
+    }
     float* pq2 = nullptr;
 #ifdef TDV_STUDY
     float* pq3 = nullptr;
@@ -757,12 +985,17 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     float* hyp[2] = {nullptr, nullptr}; int* counts[2] = {nullptr, nullptr}; int4* d_tri[2] = {nullptr, nullptr};
     double* slabs = nullptr; double* d_out2 = nullptr; float* d_best12 = nullptr;
     int* d_list[2] = {nullptr, nullptr};
+    int* d_live[2] = {nullptr, nullptr}; int* d_bnd[2] = {nullptr, nullptr}; int* d_nlive = nullptr;
     for (int q = 0; q < 2; ++q) {
         TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &hyp[q]));
         TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &counts[q]));
         TDV_TRY(ws_alloc(ctx, (size_t)batch, &d_tri[q]));
     }
     if (bailout) for (int q = 0; q < 2; ++q) TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_list[q]));   // a batch's list lives until its phase 2 has run, behind the next batch's phase 1
+    if (bound) {
+        for (int q = 0; q < 2; ++q) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_live[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_bnd[q])); }
+        TDV_TRY(ws_alloc(ctx, 2, &d_nlive));
+    }
     const int rblocks = (ns + 255) / 256;
     TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
     d_best12 = reinterpret_cast<float*>(d_bad + 16);
@@ -807,7 +1040,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     auto finish_pending = [&](const ScoreJob* a, int g1) -> int {
         const int p = pending;
         const int hbp = (int)(align_up((size_t)pending_cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK);
-        ScoreJob jb{hyp[p], counts[p], d_plan[p], d_list[p], hbp, 0};
+        ScoreJob jb{hyp[p], counts[p], d_plan[p], d_list[p], hbp, 0, nullptr};
         // job B's grid: the host knows neither how many hypotheses survived nor how long phase 1 was; its workgroups stride over
         // the (range, block) items, so any multiple of 8 is enough - a quarter of a full grid covers the usual eighth of
         // survivors in one pass, surplus workgroups return at once
@@ -824,10 +1057,10 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
         pending = -1;
         return TDV_OK;
     };
-    auto enqueue = [&](int q, int cnt) -> int {     // device: hypotheses + scoring + counts back to the host
+    auto enqueue = [&](int q, int cnt, bool first) -> int {     // device: hypotheses + scoring + counts back to the host
         TDV_HIP(ctx, hipMemcpyAsync(d_tri[q], h_tri[q], (size_t)cnt * 16, hipMemcpyHostToDevice, s));
-        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, d_tri[q], cnt, h_pad, hyp[q], d_pmax, sqrt_tau, counts[q],
-                                                                 (score_mfma ? 24.f : 16.f) * 5.9604644775390625e-08f);
+        const float band_u = (score_mfma ? 24.f : 16.f) * 5.9604644775390625e-08f;
+        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, d_tri[q], cnt, h_pad, hyp[q], d_pmax, sqrt_tau, counts[q], band_u);
         const int hb = (int)(align_up((size_t)cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK);
         {   // TDV_TIMER_RANSAC_SCORE brackets every dispatch of a scoring kernel on its own
 #ifdef TDV_STUDY
@@ -848,19 +1081,28 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
                     // One dispatch per batch: its phase 1 (job A) and, behind it, phase 2 of the batch before (job B).  The plan
                     // of this batch is made from the best count known now: full counts of the batches whose phase 2 has run,
                     // the prefix counts of the pending one (a lower bound of its full counts - a bound is all the rule needs).
-                    k_ransac_plan<<<1, 1, 0, s>>>(d_state, d_plan[q], ns, n_pchunks, ps, drop_permille);
-                    ScoreJob ja{hyp[q], counts[q], d_plan[q], nullptr, hb, ps};
+                    const bool bounded = bound && !first;
+                    k_ransac_plan<<<1, 1, 0, s>>>(d_state, d_plan[q], ns, n_pchunks, ps, drop_permille, bounded ? d_nlive + q : nullptr);
+                    ScoreJob ja{hyp[q], counts[q], d_plan[q], nullptr, hb, ps, nullptr};
                     const int g1 = score_grid(hb, ps);        // (a multiple of 8: job B's XCD numbering starts there)
-                    if (pending >= 0) TDV_TRY(finish_pending(&ja, g1));
+                    if (bounded) {
+                        // RansacLeafBound: the dead hypotheses out, then phase 1 of the live ones as job B (workgroups stride over its
+                        // items; a grid of job A's size covers them in about one pass whatever the number of live blocks)
+                        k_ransac_bound<<<(cnt + 63) / 64, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, d_tri[q], cnt, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
+                                                                          d_state, ns, d_bnd[q], d_live[q], d_nlive + q);
+                        ScoreJob jl{hyp[q], counts[q], d_plan[q], d_live[q], hb, 0, d_nlive + q};
+                        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
+                        k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, d_rescored);
+                    } else if (pending >= 0) TDV_TRY(finish_pending(&ja, g1));
                     else {
                         ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
                         k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(ja, ja, g1, h_pad, pq2, n_pchunks, tau, d_rescored);
                     }
                     // survivors of this batch: the in-batch bound first (largest prefix count), then the list; the prefix counts
                     // also raise the best known for the batches after this one
-                    const bool merge_on = study_env("TDV_RANSAC_MERGE") && atoi(study_env("TDV_RANSAC_MERGE")) == 1;     // (study build; read per call: the tests switch it)
                     k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(d_tri[q], cnt, counts[q], d_plan[q] + 2);
-                    k_ransac_select<<<(cnt + 255) / 256, 256, 0, s>>>(d_tri[q], cnt, counts[q], ns, confidence, d_state, d_plan[q], d_list[q]);
+                    k_ransac_select<<<(cnt + 255) / 256, 256, 0, s>>>(d_tri[q], cnt, counts[q], ns, confidence, d_state, d_plan[q], d_list[q],
+                                                                   bounded ? d_bnd[q] : nullptr);
                     // (merged mode only: phase 2 comes a dispatch later, the prefix counts raise the bound for the batch in between;
                     //  otherwise the full counts do that right after phase 2)
                     if (merge_on) k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(d_tri[q], cnt, counts[q], d_state);
@@ -899,14 +1141,14 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     int status = TDV_OK;
     int cur = 0, it0 = 0;
     int cnt_cur = prepare(cur, it0);
-    status = enqueue(cur, cnt_cur);
+    status = enqueue(cur, cnt_cur, true);
     while (status == TDV_OK && cnt_cur > 0 && !stop) {
         const int nxt = cur ^ 1;
         const int it_next = it0 + cnt_cur;
         int cnt_next = 0;
         if (it_next < max_iterations) {             // overlap: prepare and enqueue the next batch behind the current one
             cnt_next = prepare(nxt, it_next);
-            status = enqueue(nxt, cnt_next);           // (with the bail-out this also runs phase 2 of `cur` and sends its counts)
+            status = enqueue(nxt, cnt_next, false);           // (with the bail-out this also runs phase 2 of `cur` and sends its counts)
             if (status != TDV_OK) break;
         } else if (pending == cur) {                  // last batch: its phase 2 runs alone
             status = finish_pending(nullptr, 0);
