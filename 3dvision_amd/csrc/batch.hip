@@ -42,6 +42,19 @@ int batch_check(const tdv_batch_params* prm, int n_instances) {
     return TDV_OK;
 }
 
+// an instance's result before its stages run: zeros and the identity pose
+void reset_result(tdv_instance_result& r) {
+    std::memset(&r, 0, sizeof(r));
+    for (int i = 0; i < 16; ++i) r.T[i] = (i % 5 == 0) ? 1.f : 0.f;
+}
+
+// the ICP stage's outcome: the refined pose and its figures, and the instance done (status 0)
+void set_icp_result(tdv_instance_result& r, const tdv_icp_result& fine) {
+    std::memcpy(r.T, fine.T, 64);
+    r.fitness = fine.fitness; r.rmse = fine.rmse; r.icp_iterations = fine.iterations;
+    r.status = 0;
+}
+
 struct BatchClouds {
     std::vector<int> off;             // instance b's points: [off[b], off[b + 1]) of xyz (n_instances + 1 entries)
     float* xyz = nullptr;             // workspace
@@ -181,8 +194,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     // one instance: voxel -> normals + FPFH -> match -> RANSAC -> ICP on context c (its stream, its workspace)
     auto run_instance = [&](tdv_ctx* c, int b) -> int {
         tdv_instance_result& r = results[b];
-        std::memset(&r, 0, sizeof(r));
-        for (int i = 0; i < 16; ++i) r.T[i] = (i % 5 == 0) ? 1.f : 0.f;
+        reset_result(r);
         const WsMark mark = ws_mark(c);
         int n = off[b + 1] - off[b];
         r.n_points = n;
@@ -245,9 +257,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         tdv_icp_result fine;
         TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, prm->point_to_plane, 0, &fine,
                             have_sorted ? &model_sorted : nullptr, have_grid ? &model_grid : nullptr));
-        std::memcpy(r.T, fine.T, 64);
-        r.fitness = fine.fitness; r.rmse = fine.rmse; r.icp_iterations = fine.iterations;
-        r.status = 0;
+        set_icp_result(r, fine);
         ws_rewind(c, mark);
         return TDV_OK;
     };
@@ -343,8 +353,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     };
     auto stage_features = [&](tdv_ctx* c, int b) -> int {
         tdv_instance_result& r = results[b];
-        std::memset(&r, 0, sizeof(r));
-        for (int i = 0; i < 16; ++i) r.T[i] = (i % 5 == 0) ? 1.f : 0.f;
+        reset_result(r);
         const int n = off[b + 1] - off[b], v = voff[b + 1] - voff[b];
         r.n_points = n; r.n_voxels = v;
         if (n == 0) { r.status = empty_status[b]; return TDV_OK; }
@@ -367,8 +376,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     if (batched_features) {
         for (int b = 0; b < n_instances; ++b) {
             tdv_instance_result& r = results[b];
-            std::memset(&r, 0, sizeof(r));
-            for (int i = 0; i < 16; ++i) r.T[i] = (i % 5 == 0) ? 1.f : 0.f;
+            reset_result(r);
             r.n_points = off[b + 1] - off[b]; r.n_voxels = voff[b + 1] - voff[b];
             if (r.n_points == 0) r.status = empty_status[b];
         }
@@ -394,10 +402,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     // RANSAC pass - same kernel as the per-instance call, same bits
     int v_max = 0;
     for (int b = 0; b < n_instances; ++b) v_max = std::max(v_max, voff[b + 1] - voff[b]);
-    const bool icp_small_off = getenv("TDV_ICP_SMALL") && atoi(getenv("TDV_ICP_SMALL")) == 0;   // (read per call: the tests switch it)
-    const bool batched_icp = !icp_small_off && d_voff && v_max <= icp_small_max_points() && n_model <= icp_small_max_points() && n_model > 0 &&
-                             (long long)v_max * n_model <= icp_small_max_pairs_batch() &&
-                             (ctx->icp_search == TDV_ICP_SEARCH_AUTO || ctx->icp_search == TDV_ICP_SEARCH_BRUTE);
+    const bool batched_icp = d_voff && n_model > 0 && icp_small_batch_fits(ctx, v_max, n_model);
     std::vector<float> coarse_T(batched_icp ? (size_t)n_instances * 16 : 0, 0.f);
     auto stage_register = [&](tdv_ctx* c, int b) -> int {
         tdv_instance_result& r = results[b];
@@ -421,9 +426,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         tdv_icp_result fine;
         TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, prm->point_to_plane, 0, &fine,
                             have_sorted ? &model_sorted : nullptr, have_grid ? &model_grid : nullptr));
-        std::memcpy(r.T, fine.T, 64);
-        r.fitness = fine.fitness; r.rmse = fine.rmse; r.icp_iterations = fine.iterations;
-        r.status = 0;
+        set_icp_result(r, fine);
         ws_rewind(c, mark);
         return TDV_OK;
     };
@@ -452,14 +455,9 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     if (batched_icp) {
         std::vector<tdv_icp_result> fine((size_t)n_instances);
         TDV_TRY(icp_small_batch_dev(ctx, want_ref ? vox_ref_all : vox_first_all, d_voff, n_instances, d_model_xyz, d_model_normals, n_model, coarse_T.data(), icp_thr,
-                                    prm->icp_max_iterations, prm->point_to_plane, fine.data(), v_max));
-        for (int b = 0; b < n_instances; ++b) {
-            if (off[b + 1] == off[b]) continue;
-            tdv_instance_result& r = results[b];
-            std::memcpy(r.T, fine[b].T, 64);
-            r.fitness = fine[b].fitness; r.rmse = fine[b].rmse; r.icp_iterations = fine[b].iterations;
-            r.status = 0;
-        }
+                                    prm->icp_max_iterations, prm->point_to_plane, fine.data()));
+        for (int b = 0; b < n_instances; ++b)
+            if (off[b + 1] != off[b]) set_icp_result(results[b], fine[b]);
     }
     return TDV_OK;
 }

@@ -495,33 +495,56 @@ __device__ __forceinline__ void acc_transform(const float* T, float sx, float sy
     pz = (T[2] * sx + (T[5] * sy + T[8] * sz)) + T[11];
 }
 
-// this lane's sums += one accepted correspondence (p, target idx at squared distance best)
+// One accepted correspondence, source point p (transformed) paired with target idx, in the float steps of registration.cpp: its
+// target q and, point-to-plane, J = [p x n | n] (:346-349) and r = (p - q) . n (:351).  Every path's sums and records are built
+// from these (acc_terms, ref_record), so that every path sees the same bits.
 template <int MODE>
-__device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
-                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals) {
-    v[0] += 1.0; v[1] += (double)best;
-    const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
+__device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx, const float* tgt, const float* tgt_normals,
+                                           float* q /* 3 */, float* J /* 6 */, float& r) {
+    q[0] = tgt[3 * idx]; q[1] = tgt[3 * idx + 1]; q[2] = tgt[3 * idx + 2];
     if (MODE == 0) {
         const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-        const float J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-        const float ex = px - qx, ey = py - qy, ez = pz - qz;
-        const float r = ex * nx + (ey * ny + ez * nz);
+        J[0] = py * nz - pz * ny; J[1] = pz * nx - px * nz; J[2] = px * ny - py * nx; J[3] = nx; J[4] = ny; J[5] = nz;
+        const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
+        r = ex * nx + (ey * ny + ez * nz);
+    }
+}
+
+// the tree sums' terms of one accepted correspondence at squared distance d2, handed to put(k, term) for k = 0 .. acc_nv<MODE>() - 1:
+// {1, d2, then MODE 0 the 21 upper-triangular J[a] * J[b] and the 6 J[a] * r, each product formed in float and widened; MODE 1 p, q
+// and the 9 p[a] * q[b], p and q widened first}.  put is the caller's way of combining them (+= into a lane's sums, = into a fresh
+// slab row: 0.0 + -0.0 is +0.0); each term is put as it is formed.
+template <int MODE, class Put>
+__device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
+                                          Put put) {
+    put(0, 1.0); put(1, (double)d2);
+    if (MODE == 2) return;
+    float q[3], J[6], r;
+    corr_terms<MODE>(px, py, pz, idx, tgt, tgt_normals, q, J, r);
+    if (MODE == 0) {
         int k = 2;
 #pragma unroll
         for (int a = 0; a < 6; ++a)
 #pragma unroll
-            for (int b = a; b < 6; ++b) v[k++] += (double)(J[a] * J[b]);
+            for (int b = a; b < 6; ++b) put(k++, (double)(J[a] * J[b]));
 #pragma unroll
-        for (int a = 0; a < 6; ++a) v[k++] += (double)(J[a] * r);
-    } else if (MODE == 1) {
-        const double P[3] = {px, py, pz}, Q[3] = {qx, qy, qz};
-        v[2] += P[0]; v[3] += P[1]; v[4] += P[2];
-        v[5] += Q[0]; v[6] += Q[1]; v[7] += Q[2];
+        for (int a = 0; a < 6; ++a) put(k++, (double)(J[a] * r));
+    } else {
+        const double P[3] = {px, py, pz}, Q[3] = {q[0], q[1], q[2]};
+        put(2, P[0]); put(3, P[1]); put(4, P[2]);
+        put(5, Q[0]); put(6, Q[1]); put(7, Q[2]);
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) v[8 + a * 3 + b] += P[a] * Q[b];
+            for (int b = 0; b < 3; ++b) put(8 + a * 3 + b, P[a] * Q[b]);
     }
+}
+
+// this lane's sums += one accepted correspondence (p, target idx at squared distance best)
+template <int MODE>
+__device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
+                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals) {
+    acc_terms<MODE>(px, py, pz, best, idx, tgt, tgt_normals, [v](int k, double t) { v[k] += t; });
 }
 
 // LDS of one accumulation block
@@ -595,6 +618,29 @@ __device__ __forceinline__ void acc_finish(AccShared& sh, int ns, IcpState* st, 
     }
 }
 
+// nearest target of source i from the search's output: (best d2, index).  direct (pruned / grid search): the one entry is the final
+// (d2, target index); else (brute-force scan) the minimum over the splits, in the lowest target of its chunk at that distance
+__device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const float* __restrict__ pd2, const int* __restrict__ pchunk, int direct,
+                                           const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz,
+                                           float px, float py, float pz, float& best, int& idx) {
+    best = FLT_MAX; int bc = 0;
+    for (int s = 0; s < nsplit; ++s) {
+        const float d = pd2[(size_t)s * ns_pad + i];
+        const int c = pchunk[(size_t)s * ns_pad + i];
+        if (d < best) { best = d; bc = c; }
+    }
+    idx = 0;
+    if (direct) idx = bc;
+    else if (best < FLT_MAX) {
+        idx = bc;
+#pragma unroll
+        for (int t = NN_CH - 1; t >= 0; --t) {
+            const float dx = px - tx[bc + t], dy = py - ty[bc + t], dz = pz - tz[bc + t];
+            if (dx * dx + (dy * dy + dz * dz) == best) idx = bc + t;
+        }
+    }
+}
+
 // One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
 // slabs in a fixed order, solves, and updates the state on the device.
 template <int MODE, int ACC_PPT>   // ACC_PPT source points per thread (summed per lane in index order)
@@ -619,24 +665,8 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
         if (i >= ns) continue;
         float px, py, pz;
         acc_transform(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
-        float best = FLT_MAX; int bc = 0;
-        for (int s = 0; s < nsplit; ++s) {
-            float d = pd2[(size_t)s * ns_pad + i];
-            int c = pchunk[(size_t)s * ns_pad + i];
-            if (d < best) { best = d; bc = c; }
-        }
-        int idx = 0;
-        if (direct) {   // pruned / grid search: (best, bc) are the final (d2, target index)
-            idx = bc;
-        } else if (best < FLT_MAX) {
-            idx = bc;
-#pragma unroll
-            for (int t = NN_CH - 1; t >= 0; --t) {
-                float dx = px - tx[bc + t], dy = py - ty[bc + t], dz = pz - tz[bc + t];
-                float d2 = dx * dx + (dy * dy + dz * dz);
-                if (d2 == best) idx = bc + t;
-            }
-        }
+        float best; int idx;
+        resolve_nn(i, ns_pad, nsplit, pd2, pchunk, direct, tx, ty, tz, px, py, pz, best, idx);
         const bool acc = best <= tau_accept;
         if (out_corr) out_corr[i] = idx;
         if (out_d2) out_d2[i] = best;
@@ -752,26 +782,15 @@ constexpr int REF_TILE = 512;        // records per LDS tile
 constexpr int REF_LD = REF_TILE + 4; // row pitch in LDS (floats): lane k's 16-byte reads start 4 banks after lane k-1's
 constexpr int REF_RING = 3;          // register stages of a loader lane (tiles in flight ahead of the expansion)
 
-// nearest target of source i from the search's output: (best d2, index) - what k_icp_accumulate does in line
-__device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const float* __restrict__ pd2, const int* __restrict__ pchunk, int direct,
-                                           const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz,
-                                           float px, float py, float pz, float& best, int& idx) {
-    best = FLT_MAX; int bc = 0;
-    for (int s = 0; s < nsplit; ++s) {
-        const float d = pd2[(size_t)s * ns_pad + i];
-        const int c = pchunk[(size_t)s * ns_pad + i];
-        if (d < best) { best = d; bc = c; }
-    }
-    idx = 0;
-    if (direct) idx = bc;
-    else if (best < FLT_MAX) {
-        idx = bc;
-#pragma unroll
-        for (int t = NN_CH - 1; t >= 0; --t) {
-            const float dx = px - tx[bc + t], dy = py - ty[bc + t], dz = pz - tz[bc + t];
-            if (dx * dx + (dy * dy + dz * dz) == best) idx = bc + t;
-        }
-    }
+// the dense record of one accepted correspondence at squared distance d2 (corr_terms):
+//   point-to-plane {d2, J0, J1, J2 | J3, J4, J5, r}     point-to-point {d2, px, py, pz | qx, qy, qz, 0}
+template <int MODE>
+__device__ __forceinline__ void ref_record(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
+                                           float4& a, float4& b) {
+    float q[3], J[6], r;
+    corr_terms<MODE>(px, py, pz, idx, tgt, tgt_normals, q, J, r);
+    if (MODE == 0) { a = make_float4(d2, J[0], J[1], J[2]); b = make_float4(J[3], J[4], J[5], r); }
+    else { a = make_float4(d2, px, py, pz); b = make_float4(q[0], q[1], q[2], 0.f); }
 }
 
 // accepted correspondences per block of 256 source points
@@ -816,8 +835,7 @@ void k_icp_scan_counts(const int* __restrict__ cnt, int nblocks, const IcpState*
     if (threadIdx.x == 0) off[nblocks] = s_carry;
 }
 
-// the accepted correspondences as records rec[2 * pos], rec[2 * pos + 1] (pos ascending with the source index):
-//   point-to-plane {d2, J0, J1, J2 | J3, J4, J5, r}     point-to-point {d2, px, py, pz | qx, qy, qz, 0}
+// the accepted correspondences as records rec[2 * pos], rec[2 * pos + 1] (ref_record; pos ascending with the source index)
 template <int MODE>
 __global__ __launch_bounds__(256)
 void k_icp_rows(const float* __restrict__ src, int ns, int ns_pad,
@@ -841,16 +859,7 @@ void k_icp_rows(const float* __restrict__ src, int ns, int ns_pad,
     if (!acc) return;
     int pos = off[blockIdx.x] + __popcll(m & ((1ull << lane) - 1ull));
     for (int w = 0; w < wave; ++w) pos += s_w[w];
-    const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
-    if (MODE == 0) {
-        const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-        const float ex = px - qx, ey = py - qy, ez = pz - qz;
-        rec[2 * (size_t)pos] = make_float4(best, py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx);      // J = [p x n | n], registration.cpp:346-349
-        rec[2 * (size_t)pos + 1] = make_float4(nx, ny, nz, ex * nx + (ey * ny + ez * nz));                      // r = (p - q) . n, :351
-    } else {
-        rec[2 * (size_t)pos] = make_float4(best, px, py, pz);
-        rec[2 * (size_t)pos + 1] = make_float4(qx, qy, qz, 0.f);
-    }
+    ref_record<MODE>(px, py, pz, best, idx, tgt, tgt_normals, rec[2 * (size_t)pos], rec[2 * (size_t)pos + 1]);
 }
 
 // lane's running sum += the entries [0, m) of its LDS row, in order (m a multiple of 4): REF_CHAIN_G x 16 bytes of LDS reads, then
@@ -979,12 +988,13 @@ void k_icp_fold_ref(const float4* __restrict__ rec, const int* __restrict__ d_to
 //    added as (w0 + w1) + (w2 + w3) into a slab, slabs folded in the same pattern - so a call gives the same bits whichever path
 //    its size selects.
 constexpr int SM_MAX_N = 2048;           // sources and targets the one-launch loop takes
+constexpr int SM_THREADS = 1024;         // lanes of its workgroup
 constexpr long long SM_MAX_PAIRS_SINGLE = 1ll << 18;    // ... in a single call (tools/studies/icp_small_probe.py)
 constexpr long long SM_MAX_PAIRS_BATCH = 1ll << 20;     // ... per problem of a batch
 // A grid of several workgroups runs one problem each (the batch's small instances against the shared model): problem b takes the
 // source points [src_off[b], src_off[b + 1]) of src0 and the states st_in[b] / st_out[b]; src_off == nullptr: one problem.
 // 1,024 lanes and room for 2,048 x 2,048 points.
-template <int MODE, int SM_THREADS, int SM_CAP, bool REF = false>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS
+template <int MODE, bool REF>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS
 __global__ __launch_bounds__(SM_THREADS)
 void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict__ src_off, const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
                  const IcpState* __restrict__ st_in0, float tau_accept, int max_iterations, int fixed_iterations,
@@ -995,11 +1005,11 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
     const IcpState* __restrict__ st_in = st_in0 + prob;
     IcpState* __restrict__ st_out = st_out0 + prob;
     if (ns == 0) { if (threadIdx.x == 0) *st_out = *st_in; return; }   // (an instance without points: the caller ignores its state)
-    __shared__ __attribute__((aligned(16))) float tx[SM_CAP], ty[SM_CAP], tz[SM_CAP];
-    __shared__ float sbest[SM_CAP];
-    __shared__ int sidx[SM_CAP];
+    __shared__ __attribute__((aligned(16))) float tx[SM_MAX_N], ty[SM_MAX_N], tz[SM_MAX_N];
+    __shared__ float sbest[SM_MAX_N];
+    __shared__ int sidx[SM_MAX_N];
     __shared__ double red[SM_THREADS / 64][ACC_NV];       // wave sums, four per virtual block
-    __shared__ double slab[SM_CAP / 256][ACC_NV];
+    __shared__ double slab[SM_MAX_N / 256][ACC_NV];
     __shared__ double fold[8][ACC_NV];
     __shared__ double tot[ACC_NV];
     __shared__ float solve_ws[56];
@@ -1016,7 +1026,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
     }
     if (threadIdx.x == 0) st = *st_in;
     __syncthreads();
-    constexpr int NV = MODE == 0 ? 29 : 17;
+    constexpr int NV = acc_nv<MODE>();
     const int nblocks = (ns + 255) / 256;
     for (int it = 0; it < max_iterations; ++it) {
         float T[16];
@@ -1078,14 +1088,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
                             if (acc) {
                                 float px, py, pz;
                                 transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
-                                const int idx = sidx[i];
-                                const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
-                                if (MODE == 0) {
-                                    const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-                                    const float ex = px - qx, ey = py - qy, ez = pz - qz;
-                                    ra = make_float4(best, py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx);
-                                    rb = make_float4(nx, ny, nz, ex * nx + (ey * ny + ez * nz));
-                                } else { ra = make_float4(best, px, py, pz); rb = make_float4(qx, qy, qz, 0.f); }
+                                ref_record<MODE>(px, py, pz, best, sidx[i], tgt, tgt_normals, ra, rb);
                             }
                         }
                         if (pass == 0) ref_expand<MODE, 0>(rrows, threadIdx.x, ra, rb, acc, rmeans);
@@ -1123,31 +1126,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
                 float px, py, pz;
                 transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
                 const float best = sbest[i]; const int idx = sidx[i];
-                if (best <= tau_accept) {
-                    v[0] = 1.0; v[1] = (double)best;
-                    const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
-                    if (MODE == 0) {
-                        const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-                        const float J[6] = {py * nz - pz * ny, pz * nx - px * nz, px * ny - py * nx, nx, ny, nz};
-                        const float ex = px - qx, ey = py - qy, ez = pz - qz;
-                        const float r = ex * nx + (ey * ny + ez * nz);
-                        int k = 2;
-#pragma unroll
-                        for (int a = 0; a < 6; ++a)
-#pragma unroll
-                            for (int b = a; b < 6; ++b) v[k++] = (double)(J[a] * J[b]);
-#pragma unroll
-                        for (int a = 0; a < 6; ++a) v[k++] = (double)(J[a] * r);
-                    } else {
-                        const double P[3] = {px, py, pz}, Q[3] = {qx, qy, qz};
-                        v[2] = P[0]; v[3] = P[1]; v[4] = P[2];
-                        v[5] = Q[0]; v[6] = Q[1]; v[7] = Q[2];
-#pragma unroll
-                        for (int a = 0; a < 3; ++a)
-#pragma unroll
-                            for (int b = 0; b < 3; ++b) v[8 + a * 3 + b] = P[a] * Q[b];
-                    }
-                }
+                if (best <= tau_accept) acc_terms<MODE>(px, py, pz, best, idx, tgt, tgt_normals, [&v](int k, double t) { v[k] = t; });
             }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -1198,7 +1177,7 @@ NnPlan make_plan(int ns, int nt) {
     p.n_chunks = p.nt_pad / NN_CH;
     p.blocks_x = p.ns_pad / NN_SRC_PER_BLOCK;
     // aim for ~12k workgroups (48 per CU: measured best at 200k x 200k) but keep >= 16 chunks (256 targets) per split
-    int want = (NN_WG_TARGET + p.blocks_x - 1) / p.blocks_x;
+    int want = (NN_WG_TARGET + p.blocks_x - 1) / std::max(p.blocks_x, 1);     // (ns = 0: an empty instance of a batch)
     int max_split = std::max(1, p.n_chunks / 16);
     p.nsplit = std::max(1, std::min(std::min(want, max_split), 64));
     p.chunks_per_split = (p.n_chunks + p.nsplit - 1) / p.nsplit;
@@ -1208,6 +1187,48 @@ NnPlan make_plan(int ns, int nt) {
     p.acc_ppt = (kStudyBuild && (ppt_env == 1 || ppt_env == 2 || ppt_env == 4 || ppt_env == 8)) ? ppt_env : 4;   // 4: make_plan's default; the brute-force path uses 1
     p.acc_blocks = (ns + 256 * p.acc_ppt - 1) / (256 * p.acc_ppt);
     return p;
+}
+
+// whether the one-launch loop (k_icp_small) takes ns x nt points, at most max_pairs pairs
+bool small_fits(int ns, int nt, long long max_pairs) {
+    const bool off = getenv("TDV_ICP_SMALL") && atoi(getenv("TDV_ICP_SMALL")) == 0;   // A/B knob (read per call: the tests switch it)
+    return !off && ns <= SM_MAX_N && nt <= SM_MAX_N && (long long)ns * nt <= max_pairs;
+}
+
+// The path of one problem of ns source x nt target points at threshold thr on ctx.  icp_run_dev takes it, and icp_batch_run_dev
+// follows it per instance: that is what gives an instance the single call's bits.
+struct IcpPlan {
+    int search;     // TDV_ICP_SEARCH_GRID / _PRUNED / _BRUTE, what ctx->last_icp_search reports
+    bool direct;    // pruned walk or grid: one search result per source, the final (d2, original target index)
+    bool small;     // the whole loop in one launch (k_icp_small)
+    CellGrid cg;    // the target's hash grid, searched when cg.usable
+    NnPlan p;       // the scan's shape and the accumulation's acc_ppt / acc_blocks
+};
+
+// Search: brute force for small problems (the two Morton sorts cost more than they save), the exact pruned walk for large ones, the
+// hash grid (tgt_grid if it was built for this nt and thr, else built here) on request or by size like the walk, used when its build
+// says the cells are small enough.  All give the same correspondences bit for bit.
+int icp_plan(tdv_ctx* ctx, const float* d_tgt, int ns, int nt, float thr, const CellGrid* tgt_grid, IcpPlan& pl) {
+    const int mode = ctx->icp_search;
+    const float tau = tau_le(thr);
+    bool pruned = tau < FLT_MAX &&      // (unbounded threshold: keep the scan's handling of overflowing distances)
+                  (mode == TDV_ICP_SEARCH_PRUNED || (mode == TDV_ICP_SEARCH_AUTO && nt >= PRUNED_MIN_TARGETS && (double)ns * (double)nt >= PRUNED_MIN_PAIRS));
+    pl.cg = CellGrid{};
+    if (tau < FLT_MAX && (mode == TDV_ICP_SEARCH_GRID || (mode == TDV_ICP_SEARCH_AUTO && pruned))) {
+        if (tgt_grid && tgt_grid->n == nt && tgt_grid->thr == thr) pl.cg = *tgt_grid;
+        else TDV_TRY(cell_grid_build(ctx, d_tgt, nt, thr, &pl.cg));
+        pruned = true;              // the grid's results arrive in the walk's format; an unusable grid falls back to the walk
+    }
+    pl.search = pl.cg.usable ? TDV_ICP_SEARCH_GRID : (pruned ? TDV_ICP_SEARCH_PRUNED : TDV_ICP_SEARCH_BRUTE);
+    pl.direct = pruned;
+    // (one workgroup walks all ns x nt pairs of an iteration: measured per iteration 22 us at 400 x 398 against 28 us for the two
+    //  launches, but 65 us at 1,000 x 1,000 and 237 us at 2,000 x 2,000 against 25-27: a single problem only takes this path while the
+    //  pair count is small; a BATCH of such problems is another matter - there the grid is the parallelism, icp_small_batch_dev)
+    pl.small = !pruned && small_fits(ns, nt, SM_MAX_PAIRS_SINGLE);
+    pl.p = make_plan(ns, nt);
+    if (pruned) pl.p.nsplit = 1;
+    else if (pl.small || !study_env("TDV_ICP_PPT")) { pl.p.acc_ppt = 1; pl.p.acc_blocks = (ns + 255) / 256; }   // (k_icp_small's tree is the 1's)
+    return TDV_OK;                                     // measured: 50k x 10k brute 7.6k vs 6.4k iters/s with 1 point per thread
 }
 
 struct IcpBuffers {
@@ -1223,6 +1244,54 @@ int alloc_buffers(tdv_ctx* ctx, const NnPlan& p, IcpBuffers& b) {
     TDV_TRY(ws_alloc(ctx, (size_t)p.acc_blocks * ACC_NV, &b.slabs));
     TDV_TRY(ws_alloc(ctx, 1, &b.st));
     b.ticket = ctx->scan_ticket + 1;     // the ctx's persistent ticket words (zero between launches: the last workgroup resets it)
+    return TDV_OK;
+}
+
+// n states before the first iteration: start pose T0s + 16 b (host, column-major), everything else 0
+void init_states(IcpState* h, const float* T0s, int n) {
+    std::memset(h, 0, (size_t)n * sizeof(IcpState));
+    for (int b = 0; b < n; ++b) { std::memcpy(h[b].T, T0s + 16 * (size_t)b, 64); std::memcpy(h[b].res_T, T0s + 16 * (size_t)b, 64); }
+}
+
+// the result before any iteration: registration.cpp:309-311
+void result_defaults(const float* T0, tdv_icp_result& out) {
+    std::memcpy(out.T, T0, 64);
+    out.fitness = 0.f; out.rmse = 0.f; out.iterations = 0; out.n_corr = 0;
+}
+
+// the result of a final state
+void state_result(const IcpState& h, tdv_icp_result& out) {
+    std::memcpy(out.T, h.res_T, 64);
+    out.fitness = h.fitness; out.rmse = h.rmse; out.iterations = h.applied; out.n_corr = h.last_n_corr_applied;
+}
+
+// k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points), point-to-plane where normals are given, with the
+// ctx's accumulation
+void launch_icp_small(tdv_ctx* ctx, int n_prob, const float* d_src, int ns, const int* d_src_off, const float* d_tgt, const float* d_tgt_normals, int nt,
+                      int point_to_plane, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host) {
+    const bool p2pl = point_to_plane && d_tgt_normals, ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
+    const auto kernel = p2pl ? (ref ? k_icp_small<0, true> : k_icp_small<0, false>) : (ref ? k_icp_small<1, true> : k_icp_small<1, false>);
+    kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, p2pl ? d_tgt_normals : nullptr, nt, st_in, tau, max_iterations, fixed_iterations,
+                                                   st_out, st_host);
+}
+
+// Iterations are enqueued in bursts between two looks at the n states d_st (read back into the pinned h[0 .. n)); once a state is done
+// the remaining launches of a burst return at once, and the loop ends when all are.  The reference's stopping rule fires after 3-4
+// iterations in the pipeline's setting (0.4-voxel threshold from a RANSAC start), so the first burst is short; fixed-iteration runs
+// take long bursts.  iteration() enqueues one iteration.
+template <class F>
+int run_bursts(tdv_ctx* ctx, IcpState* h, const IcpState* d_st, int n, int max_iterations, int fixed_iterations, const F& iteration) {
+    for (int it = 0; it < max_iterations;) {
+        const int burst = std::min(fixed_iterations ? 32 : (it == 0 ? 4 : 8), max_iterations - it);
+        for (int k = 0; k < burst; ++k) iteration();
+        TDV_CHECK_LAUNCH(ctx);
+        it += burst;
+        TDV_HIP(ctx, hipMemcpyAsync(h, d_st, (size_t)n * sizeof(IcpState), hipMemcpyDeviceToHost, ctx->stream));
+        TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        bool all_done = true;
+        for (int b = 0; b < n && all_done; ++b) all_done = h[b].done != 0;
+        if (all_done) break;
+    }
     return TDV_OK;
 }
 
@@ -1262,41 +1331,22 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid) {
     if (!ctx || !d_src || !d_tgt || !T0 || !out || ns < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
     TDV_HIP(ctx, hipSetDevice(ctx->device));
-    // result defaults: registration.cpp:309-311
-    std::memcpy(out->T, T0, 64);
-    out->fitness = 0.f; out->rmse = 0.f; out->iterations = 0; out->n_corr = 0;
+    result_defaults(T0, *out);
     if (max_iterations == 0) return TDV_OK;
     if (ns == 0 || nt == 0) return TDV_OK;  // n_corr == 0 < 3 -> break at the first iteration
     const float tau = tau_le(thr);
-    // search: brute force for small problems (the two Morton sorts cost more than they save), exact pruned walk
-    // for large ones; both give the same correspondences bit for bit
-    bool pruned = ctx->icp_search == TDV_ICP_SEARCH_PRUNED ||
-                  (ctx->icp_search == TDV_ICP_SEARCH_AUTO && nt >= PRUNED_MIN_TARGETS && (double)ns * (double)nt >= PRUNED_MIN_PAIRS);
-    if (!(tau < FLT_MAX)) pruned = false;   // unbounded threshold: keep the scan's handling of overflowing distances
-    // hash grid: on request, or by size like the pruned walk; used when its build says the cells are small enough
-    CellGrid cg{};
-    if (tau < FLT_MAX && (ctx->icp_search == TDV_ICP_SEARCH_GRID || (ctx->icp_search == TDV_ICP_SEARCH_AUTO && pruned))) {
-        if (tgt_grid && tgt_grid->n == nt && tgt_grid->thr == thr) cg = *tgt_grid;
-        else TDV_TRY(cell_grid_build(ctx, d_tgt, nt, thr, &cg));
-        if (cg.usable) pruned = true;           // results arrive in the pruned walk's format (one entry per source, original indices)
-        else if (ctx->icp_search == TDV_ICP_SEARCH_GRID) pruned = true;   // fall back to the walk
-    }
-    ctx->last_icp_search = cg.usable ? TDV_ICP_SEARCH_GRID : (pruned ? TDV_ICP_SEARCH_PRUNED : TDV_ICP_SEARCH_BRUTE);
-    NnPlan p = make_plan(ns, nt);
-    if (pruned) p.nsplit = 1;
-    else if (!study_env("TDV_ICP_PPT")) { p.acc_ppt = 1; p.acc_blocks = (ns + 255) / 256; }   // measured: 50k x 10k brute 7.6k vs 6.4k iters/s
+    IcpPlan pl;
+    TDV_TRY(icp_plan(ctx, d_tgt, ns, nt, thr, tgt_grid, pl));
+    ctx->last_icp_search = pl.search;
+    const NnPlan& p = pl.p;
+    const CellGrid& cg = pl.cg;
     const bool ref_acc = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
     TDV_TRY(pin_reserve(ctx, 2 * sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    std::memset(h, 0, sizeof(IcpState));
-    std::memcpy(h->T, T0, 64); std::memcpy(h->res_T, T0, 64);
+    init_states(h, T0, 1);
     hipStream_t s = ctx->stream;
     // small problems: the whole loop in one launch (k_icp_small), same bits as the launches below
-    const bool small_off = getenv("TDV_ICP_SMALL") && atoi(getenv("TDV_ICP_SMALL")) == 0;   // A/B knob (read per call: the tests switch it)
-    // (one workgroup walks all ns x nt pairs of an iteration: measured per iteration 22 us at 400 x 398 against 28 us for the two
-    //  launches, but 65 us at 1,000 x 1,000 and 237 us at 2,000 x 2,000 against 25-27: a single call only takes this path while the pair
-    //  count is small; a BATCH of such problems is another matter - there the grid is the parallelism, icp_small_batch_dev)
-    if (!small_off && !pruned && !cg.usable && ns <= SM_MAX_N && nt <= SM_MAX_N && (long long)ns * nt <= SM_MAX_PAIRS_SINGLE) {
+    if (pl.small) {
         IcpState* d_st;
         TDV_TRY(ws_alloc(ctx, 2, &d_st));
         IcpState* h_res = h + 1;                          // the kernel stores its final state here itself (pinned memory: no copy kernel)
@@ -1304,19 +1354,12 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
         TDV_HIP(ctx, hipMemcpyAsync(d_st, h, sizeof(IcpState), hipMemcpyHostToDevice, s));
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-            if (point_to_plane && d_tgt_normals) {
-                if (ref_acc) k_icp_small<0, 1024, SM_MAX_N, true><<<1, 1024, 0, s>>>(d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
-                else k_icp_small<0, 1024, SM_MAX_N><<<1, 1024, 0, s>>>(d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
-            } else {
-                if (ref_acc) k_icp_small<1, 1024, SM_MAX_N, true><<<1, 1024, 0, s>>>(d_src, ns, nullptr, d_tgt, nullptr, nt, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
-                else k_icp_small<1, 1024, SM_MAX_N><<<1, 1024, 0, s>>>(d_src, ns, nullptr, d_tgt, nullptr, nt, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
-            }
+            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
         }
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipStreamSynchronize(s));
         if (h_res->iter < 0) { snprintf(ctx->err, sizeof(ctx->err), "icp: the result did not reach the host"); return TDV_ERR_INTERNAL; }
-        std::memcpy(out->T, h_res->res_T, 64);
-        out->fitness = h_res->fitness; out->rmse = h_res->rmse; out->iterations = h_res->applied; out->n_corr = h_res->last_n_corr_applied;
+        state_result(*h_res, *out);
         return TDV_OK;
     }
     IcpBuffers b;
@@ -1325,7 +1368,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     SortedCloud st{};
     if (cg.usable) {
         // nothing to prepare
-    } else if (pruned) {
+    } else if (pl.direct) {
         if (tgt_sorted && tgt_sorted->n == nt) st = *tgt_sorted;   // the batch orders the shared model once
         else TDV_TRY(spatial_sort_cloud(ctx, d_tgt, nt, st));
     } else {
@@ -1333,7 +1376,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     }
     TDV_CHECK_LAUNCH(ctx);
     const bool p2pl = point_to_plane && d_tgt_normals;
-    const int direct = pruned ? 1 : 0;
+    const int direct = pl.direct ? 1 : 0;
     // reference-order accumulation: dense records of the accepted correspondences + one-workgroup ordered fold instead of k_icp_accumulate
     const int ref_blocks = (ns + 255) / 256;
     float4* ref_rec = nullptr; int *ref_cnt = nullptr, *ref_off = nullptr;
@@ -1345,67 +1388,56 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     const GridEntry* gtable = cg.usable ? reinterpret_cast<const GridEntry*>(cg.table) : nullptr;
     const float4* gnode = cg.usable ? reinterpret_cast<const float4*>(cg.node) : nullptr;
     const dim3 grid(p.blocks_x, p.nsplit);
-    // iterations are enqueued in bursts between two looks at the state; once `done` is set the remaining launches of a burst
-    // return at once.  The reference's stopping rule fires after 3-4 iterations in the pipeline's setting (0.4-voxel
-    // threshold from a RANSAC start), so the first burst is short; fixed-iteration runs take long bursts.
-    int it = 0;
-    while (it < max_iterations) {
-        const int poll = fixed_iterations ? 32 : (it == 0 ? 4 : 8);
-        int burst = std::min(poll, max_iterations - it);
-        for (int k = 0; k < burst; ++k) {
-            {
-                ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-                if (gtable)
-                    k_icp_nn_grid<<<(ns + 255) / 256, 256, 0, s>>>(d_src, ns, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau, b.pd2, b.pchunk);
-                else if (pruned)
-                    k_icp_nn_pruned<<<(ns + PN_WAVES * PN_PTS - 1) / (PN_WAVES * PN_PTS), 64 * PN_WAVES, 0, s>>>(
-                        d_src, ns, st.sx, st.sy, st.sz, st.orig, nt, st.lbox, st.n_leaf, st.tbox, st.n_top, b.st, tau, b.pd2, b.pchunk);
-                else
-                    k_icp_nn_scan<<<grid, NN_BLOCK, 0, s>>>(d_src, ns, p.ns_pad, b.tx, b.ty, b.tz, p.n_chunks,
-                                                            p.chunks_per_split, b.st, b.pd2, b.pchunk);
+    TDV_TRY(run_bursts(ctx, h, b.st, 1, max_iterations, fixed_iterations, [&]() {
+        {
+            ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
+            if (gtable)
+                k_icp_nn_grid<<<(ns + 255) / 256, 256, 0, s>>>(d_src, ns, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau, b.pd2, b.pchunk);
+            else if (pl.direct)
+                k_icp_nn_pruned<<<(ns + PN_WAVES * PN_PTS - 1) / (PN_WAVES * PN_PTS), 64 * PN_WAVES, 0, s>>>(
+                    d_src, ns, st.sx, st.sy, st.sz, st.orig, nt, st.lbox, st.n_leaf, st.tbox, st.n_top, b.st, tau, b.pd2, b.pchunk);
+            else
+                k_icp_nn_scan<<<grid, NN_BLOCK, 0, s>>>(d_src, ns, p.ns_pad, b.tx, b.ty, b.tz, p.n_chunks,
+                                                        p.chunks_per_split, b.st, b.pd2, b.pchunk);
+        }
+        if (ref_acc) {
+            k_icp_flags<<<ref_blocks, 256, 0, s>>>(ns, p.ns_pad, p.nsplit, b.pd2, b.st, tau, ref_cnt);
+            k_icp_scan_counts<<<1, 1024, 0, s>>>(ref_cnt, ref_blocks, b.st, ref_off);
+            if (p2pl) {
+                k_icp_rows<0><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
+                k_icp_fold_ref<0><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
+            } else {
+                k_icp_rows<1><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nullptr, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
+                k_icp_fold_ref<1><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
             }
-            if (ref_acc) {
-                k_icp_flags<<<ref_blocks, 256, 0, s>>>(ns, p.ns_pad, p.nsplit, b.pd2, b.st, tau, ref_cnt);
-                k_icp_scan_counts<<<1, 1024, 0, s>>>(ref_cnt, ref_blocks, b.st, ref_off);
-                if (p2pl) {
-                    k_icp_rows<0><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
-                    k_icp_fold_ref<0><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
-                } else {
-                    k_icp_rows<1><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nullptr, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
-                    k_icp_fold_ref<1><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
-                }
-            } else if (p2pl) {
+        } else if (p2pl) {
 #define TDV_ACC1(MM, PP, NRM) k_icp_accumulate<MM, PP><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, NRM, b.tx, b.ty, b.tz, \
-                                   p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, b.slabs, b.ticket, nullptr, nullptr, nullptr)
+                               p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, b.slabs, b.ticket, nullptr, nullptr, nullptr)
 #ifdef TDV_STUDY
 #define TDV_ACC(MM, NRM) do { if (p.acc_ppt == 8) TDV_ACC1(MM, 8, NRM); else if (p.acc_ppt == 4) TDV_ACC1(MM, 4, NRM); else if (p.acc_ppt == 2) TDV_ACC1(MM, 2, NRM); else TDV_ACC1(MM, 1, NRM); } while (0)
 #else
 #define TDV_ACC(MM, NRM) do { if (p.acc_ppt == 4) TDV_ACC1(MM, 4, NRM); else TDV_ACC1(MM, 1, NRM); } while (0)     // (2 and 8 points per thread: study build)
 #endif
-                TDV_ACC(0, d_tgt_normals);
-            } else {
-                TDV_ACC(1, nullptr);
-            }
+            TDV_ACC(0, d_tgt_normals);
+        } else {
+            TDV_ACC(1, nullptr);
         }
-        TDV_CHECK_LAUNCH(ctx);
-        it += burst;
-        TDV_HIP(ctx, hipMemcpyAsync(h, b.st, sizeof(IcpState), hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-        if (h->done) break;
-    }
-    std::memcpy(out->T, h->res_T, 64);
-    out->fitness = h->fitness; out->rmse = h->rmse; out->iterations = h->applied; out->n_corr = h->last_n_corr_applied;
+    }));
+    state_result(*h, *out);
     return TDV_OK;
 }
 
-int icp_small_max_points() { return SM_MAX_N; }
-long long icp_small_max_pairs_batch() { return SM_MAX_PAIRS_BATCH; }
+// whether icp_small_batch_dev takes problems of up to ns_max points against nt targets on this ctx (its kernel scans: no search but
+// AUTO or BRUTE asks for anything else)
+bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt) {
+    return (ctx->icp_search == TDV_ICP_SEARCH_AUTO || ctx->icp_search == TDV_ICP_SEARCH_BRUTE) && small_fits(ns_max, nt, SM_MAX_PAIRS_BATCH);
+}
 
 // icp_run_dev for n_prob small problems against one target in ONE launch: problem b = source points [d_src_off[b], d_src_off[b+1])
-// of d_src (each at most icp_small_max_points(), as nt), start pose T0s[b] (host, column-major).  Results as icp_run_dev's, bit for
-// bit (the same kernel).  One upload, one launch, one download.
+// of d_src (each at most SM_MAX_N, as nt), start pose T0s[b] (host, column-major).  Results as icp_run_dev's, bit for bit (the same
+// kernel).  One upload, one launch, one download.
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, int ns_max) {
+                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out) {
     if (!ctx || !d_src || !d_src_off || !d_tgt || !T0s || !out || n_prob < 0 || nt <= 0 || nt > SM_MAX_N || max_iterations < 0) return TDV_ERR_BAD_ARG;
     if (n_prob == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
@@ -1414,32 +1446,20 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
     TDV_TRY(ws_alloc(ctx, (size_t)2 * n_prob, &d_st));
     TDV_TRY(pin_reserve(ctx, (size_t)n_prob * sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    std::memset(h, 0, (size_t)n_prob * sizeof(IcpState));
-    for (int b = 0; b < n_prob; ++b) { std::memcpy(h[b].T, T0s + 16 * (size_t)b, 64); std::memcpy(h[b].res_T, T0s + 16 * (size_t)b, 64); }
+    init_states(h, T0s, n_prob);
     TDV_HIP(ctx, hipMemcpyAsync(d_st, h, (size_t)n_prob * sizeof(IcpState), hipMemcpyHostToDevice, s));
     if (max_iterations > 0) {
         ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-        const bool p2pl = point_to_plane && d_tgt_normals;
         // (A quarter-size shape - 256 lanes, more problems resident at once - was measured against this one on C5's 1,024 instances in
         // round 3: 1.59 ms against 1.33 ms.  The pass lasts as long as its slowest problem and a lone workgroup iterates faster with
         // 16 waves; the variant is gone, profiles/r3/history keeps the numbers.)
-        (void)ns_max;
-        if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
-            if (p2pl) k_icp_small<0, 1024, SM_MAX_N, true><<<n_prob, 1024, 0, s>>>(d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
-            else k_icp_small<1, 1024, SM_MAX_N, true><<<n_prob, 1024, 0, s>>>(d_src, 0, d_src_off, d_tgt, nullptr, nt, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
-        } else {
-            if (p2pl) k_icp_small<0, 1024, SM_MAX_N><<<n_prob, 1024, 0, s>>>(d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
-            else k_icp_small<1, 1024, SM_MAX_N><<<n_prob, 1024, 0, s>>>(d_src, 0, d_src_off, d_tgt, nullptr, nt, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
-        }
+        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipMemcpyAsync(h, d_st + n_prob, (size_t)n_prob * sizeof(IcpState), hipMemcpyDeviceToHost, s));
     }
     TDV_HIP(ctx, hipStreamSynchronize(s));
     ctx->last_icp_search = TDV_ICP_SEARCH_BRUTE;
-    for (int b = 0; b < n_prob; ++b) {
-        std::memcpy(out[b].T, h[b].res_T, 64);
-        out[b].fitness = h[b].fitness; out[b].rmse = h[b].rmse; out[b].iterations = h[b].applied; out[b].n_corr = h[b].last_n_corr_applied;
-    }
+    for (int b = 0; b < n_prob; ++b) state_result(h[b], out[b]);
     return TDV_OK;
 }
 
@@ -1451,10 +1471,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
 // the shared grid or Morton order.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
                       int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out) {
-    for (int b = 0; b < n; ++b) {    // result defaults: registration.cpp:309-311
-        std::memcpy(out[b].T, T0s + 16 * (size_t)b, 64);
-        out[b].fitness = 0.f; out[b].rmse = 0.f; out[b].iterations = 0; out[b].n_corr = 0;
-    }
+    for (int b = 0; b < n; ++b) result_defaults(T0s + 16 * (size_t)b, out[b]);
     if (n == 0) return TDV_OK;
     int ns_max = 0, span = 0;
     bool contiguous = h_start[0] == 0;
@@ -1463,21 +1480,18 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         span = std::max(span, h_start[b] + h_count[b]);
         if (b + 1 < n && h_start[b + 1] != h_start[b] + h_count[b]) contiguous = false;
     }
-    if (n == 0 || max_iterations == 0 || nt == 0 || ns_max == 0) return TDV_OK;
+    if (max_iterations == 0 || nt == 0 || ns_max == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
     const float tau = tau_le(thr);
     const int search = ctx->icp_search;
-    const bool ref_acc = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
-    const bool small_off = getenv("TDV_ICP_SMALL") && atoi(getenv("TDV_ICP_SMALL")) == 0;   // icp_run_dev's A/B knob (read per call)
     // (1) small problems: every instance in one launch of the kernel the single call runs for them (it has no fixed-iteration mode)
-    if (!fixed_iterations && !small_off && contiguous && (search == TDV_ICP_SEARCH_AUTO || search == TDV_ICP_SEARCH_BRUTE) &&
-        nt <= SM_MAX_N && ns_max <= SM_MAX_N && (long long)ns_max * nt <= SM_MAX_PAIRS_BATCH) {
+    if (!fixed_iterations && contiguous && icp_small_batch_fits(ctx, ns_max, nt)) {
         std::vector<int> off((size_t)n + 1, 0);
         for (int b = 0; b < n; ++b) off[b + 1] = off[b] + h_count[b];
         int* d_off;
         TDV_TRY(ws_alloc(ctx, (size_t)n + 1, &d_off));
         TDV_HIP(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));   // (off outlives the call's sync)
-        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out, ns_max);
+        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out);
     }
     // the target's hash grid at this threshold, once for the call (icp_run_dev uses a grid under AUTO or GRID)
     CellGrid cg{}; bool have_grid = false;
@@ -1485,13 +1499,14 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         TDV_TRY(cell_grid_build(ctx, d_tgt, nt, thr, &cg));
         have_grid = true;
     }
-    if (ref_acc || !cg.usable) {
-        // (3) one icp_run_dev per instance, with the shared grid or the shared Morton order
-        bool any_pruned = search == TDV_ICP_SEARCH_PRUNED || search == TDV_ICP_SEARCH_GRID;
-        for (int b = 0; b < n && !any_pruned; ++b)
-            any_pruned = search == TDV_ICP_SEARCH_AUTO && nt >= PRUNED_MIN_TARGETS && (double)h_count[b] * (double)nt >= PRUNED_MIN_PAIRS;
+    IcpPlan pl;     // (with the grid above icp_plan builds nothing)
+    if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE || !cg.usable) {
+        // (3) one icp_run_dev per instance, with the shared grid or, if any instance walks it, the shared Morton order
         SortedCloud sorted{}; bool have_sorted = false;
-        if (tau < FLT_MAX && !cg.usable && any_pruned) { TDV_TRY(spatial_sort_cloud(ctx, d_tgt, nt, sorted)); have_sorted = true; }
+        for (int b = 0; b < n && !have_sorted; ++b) {
+            TDV_TRY(icp_plan(ctx, d_tgt, h_count[b], nt, thr, have_grid ? &cg : nullptr, pl));
+            if (pl.search == TDV_ICP_SEARCH_PRUNED) { TDV_TRY(spatial_sort_cloud(ctx, d_tgt, nt, sorted)); have_sorted = true; }
+        }
         for (int b = 0; b < n; ++b) {
             const WsMark mark = ws_mark(ctx);
             TDV_TRY(icp_run_dev(ctx, d_src + (size_t)h_start[b] * 3, h_count[b], d_tgt, d_tgt_normals, nt, T0s + 16 * (size_t)b, thr, max_iterations,
@@ -1500,21 +1515,17 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         }
         return TDV_OK;
     }
-    // (2) all instances together.  Per instance, the accumulation shape icp_run_dev would take for it alone: make_plan's points per
-    // thread where it searches with the grid (GRID, or AUTO at >= PRUNED_MIN_TARGETS targets and PRUNED_MIN_PAIRS pairs), else the
-    // brute-force path's 1 (which the one-launch path k_icp_small reproduces).
+    // (2) all instances together.  Per instance, the accumulation shape icp_run_dev would take for it alone (icp_plan): make_plan's
+    // points per thread where it searches with the grid, else the brute-force path's 1 (which the one-launch path k_icp_small reproduces).
     std::vector<IcpInst> inst((size_t)n);
     int nn_blocks = 0, acc_blocks = 0;
     for (int b = 0; b < n; ++b) {
         const int ns = h_count[b];
-        const bool grid_b = search == TDV_ICP_SEARCH_GRID || (nt >= PRUNED_MIN_TARGETS && (double)ns * (double)nt >= PRUNED_MIN_PAIRS);
-        const bool small_b = !small_off && !grid_b && ns <= SM_MAX_N && nt <= SM_MAX_N && (long long)ns * nt <= SM_MAX_PAIRS_SINGLE;
-        const int plan_ppt = make_plan(std::max(ns, 1), nt).acc_ppt;
-        const int ppt = grid_b ? plan_ppt : ((small_b || !study_env("TDV_ICP_PPT")) ? 1 : plan_ppt);
+        TDV_TRY(icp_plan(ctx, d_tgt, ns, nt, thr, &cg, pl));
         IcpInst& in = inst[b];
-        in.src_off = h_start[b]; in.ns = ns; in.ppt = ppt;
+        in.src_off = h_start[b]; in.ns = ns; in.ppt = pl.p.acc_ppt;
         in.nn_blk0 = nn_blocks; in.acc_blk0 = acc_blocks;
-        in.acc_blocks = (ns + 256 * ppt - 1) / (256 * ppt);
+        in.acc_blocks = pl.p.acc_blocks;
         nn_blocks += (ns + 255) / 256;
         acc_blocks += in.acc_blocks;
     }
@@ -1523,11 +1534,8 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const size_t up_bytes = st_bytes + inst_bytes + ((size_t)nn_blocks + acc_blocks) * sizeof(int);
     TDV_TRY(pin_reserve(ctx, up_bytes));      // (after cell_grid_build, which reads its flags back through the same staging)
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    std::memset(h, 0, st_bytes);
-    for (int b = 0; b < n; ++b) {
-        std::memcpy(h[b].T, T0s + 16 * (size_t)b, 64); std::memcpy(h[b].res_T, T0s + 16 * (size_t)b, 64);
-        if (h_count[b] == 0) h[b].done = 1;   // no points: n_corr = 0 < 3, the result is the start pose
-    }
+    init_states(h, T0s, n);
+    for (int b = 0; b < n; ++b) if (h_count[b] == 0) h[b].done = 1;   // no points: n_corr = 0 < 3, the result is the start pose
     std::memcpy(ctx->pin + st_bytes, inst.data(), inst_bytes);
     int* h_blk = reinterpret_cast<int*>(ctx->pin + st_bytes + inst_bytes);
     for (int b = 0; b < n; ++b) {
@@ -1552,31 +1560,15 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const float4* gnode = reinterpret_cast<const float4*>(cg.node);
     const bool p2pl = point_to_plane && d_tgt_normals;
     ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
-    // bursts between two looks at the states, as icp_run_dev's; the loop ends when every instance is done
-    int it = 0;
-    while (it < max_iterations) {
-        const int poll = fixed_iterations ? 32 : (it == 0 ? 4 : 8);
-        const int burst = std::min(poll, max_iterations - it);
-        for (int k = 0; k < burst; ++k) {
-            {
-                ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-                k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);
-            }
-            if (p2pl) k_icp_accumulate_multi<0><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
-            else k_icp_accumulate_multi<1><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, nullptr, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
+    TDV_TRY(run_bursts(ctx, h, d_st, n, max_iterations, fixed_iterations, [&]() {
+        {
+            ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
+            k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);
         }
-        TDV_CHECK_LAUNCH(ctx);
-        it += burst;
-        TDV_HIP(ctx, hipMemcpyAsync(h, d_st, st_bytes, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-        bool all_done = true;
-        for (int b = 0; b < n && all_done; ++b) all_done = h[b].done != 0;
-        if (all_done) break;
-    }
-    for (int b = 0; b < n; ++b) {
-        std::memcpy(out[b].T, h[b].res_T, 64);
-        out[b].fitness = h[b].fitness; out[b].rmse = h[b].rmse; out[b].iterations = h[b].applied; out[b].n_corr = h[b].last_n_corr_applied;
-    }
+        if (p2pl) k_icp_accumulate_multi<0><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
+        else k_icp_accumulate_multi<1><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, nullptr, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
+    }));
+    for (int b = 0; b < n; ++b) state_result(h[b], out[b]);
     return TDV_OK;
 }
 
@@ -1595,8 +1587,7 @@ int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const floa
     TDV_TRY(alloc_buffers(ctx, p, b));
     TDV_TRY(pin_reserve(ctx, sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    std::memset(h, 0, sizeof(IcpState));
-    std::memcpy(h->T, T, 64);
+    init_states(h, T, 1);
     hipStream_t s = ctx->stream;
     TDV_HIP(ctx, hipMemcpyAsync(b.st, h, sizeof(IcpState), hipMemcpyHostToDevice, s));
     const float tau = tau_le(thr);

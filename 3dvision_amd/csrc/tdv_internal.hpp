@@ -148,11 +148,10 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
                 tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr);
-// many small problems against one target in one launch (icp.hip: k_icp_small); sizes up to icp_small_max_points() each
-int icp_small_max_points();
-long long icp_small_max_pairs_batch();
+// many small problems against one target in one launch (icp.hip: k_icp_small), when icp_small_batch_fits(ctx, largest problem, nt)
+bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt);
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, int ns_max = 0 /* largest problem, if known */);
+                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out);
 // icp_run_dev for n instances against one target (icp.hip): instance b = h_count[b] points from point h_start[b] of d_src (host arrays), start
 // pose T0s + 16 b; per instance icp_run_dev's result bit for bit.  Arguments are not checked.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,

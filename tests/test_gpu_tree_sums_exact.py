@@ -1,6 +1,6 @@
 """The default ICP accumulation (f64 tree sums) and RANSAC's rmse, bit for bit against the oracle's exact-sum mode.
 
-The device adds f32 terms in f64 along a fixed tree (csrc/icp.hip: acc_add, acc_slab_fold, k_icp_small; csrc/ransac.hip:
+The device adds f32 terms in f64 along a fixed tree (csrc/icp.hip: acc_terms, acc_slab_fold, k_icp_small; csrc/ransac.hip:
 k_ransac_rmse_partial / _final).  That is within the tree's error bound of the exact sum, so every f32 the device takes from it is the
 exact sum rounded once - unless the exact sum lies within that bound of an f32 rounding midpoint, which the oracle detects
 (oracle.cpp: XSum, x32).  Every input here must report no such sum, so the device's T, rmse, fitness, iteration count and n_corr
