@@ -54,7 +54,7 @@ ABI_SYMBOLS = [
     "tdv_depth_to_cloud_dev", "tdv_voxel_downsample_dev", "tdv_sample_triples", "tdv_pose_compose",
     "tdv_register_batch_dev", "tdv_prepare_model_dev", "tdv_bilateral_filter", "tdv_filter_duplicates", "tdv_load_ply_ascii", "tdv_load_mask_png", "tdv_load_masks_from_dir",
     "tdv_depth_to_cloud_batch_dev", "tdv_broadcast_model", "tdv_gather_results", "tdv_mask_resize_nearest", "tdv_mask_resize_nearest_dev", "tdv_voxel_downsample_batch_dev", "tdv_voxel_downsample_batch_pinhole_dev",
-    "tdv_icp_batch_dev", "tdv_refine_batch_dev",
+    "tdv_icp_batch_dev", "tdv_refine_batch_dev", "tdv_ctx_set_icp_loss", "tdv_ctx_get_icp_loss",
 ]
 
 
@@ -220,6 +220,25 @@ class Context:
         ascending source index as registration.cpp:340-358,374-386: transform, rmse, fitness and iteration count equal the
         CPU path's bit for bit; a serial chain per iteration)."""
         _check(self._h, lib().tdv_ctx_set_icp_accumulation(self._h, {"tree": 0, "reference": 1}[mode]), "tdv_ctx_set_icp_accumulation")
+
+    ICP_LOSS = {"l2": 0, "huber": 1, "tukey": 2, "cauchy": 3}
+
+    def set_icp_loss(self, kind, scale=None):
+        """ICP's robust loss on this context (include/tdv_hip.h: tdv_ctx_set_icp_loss): 'l2' (default: every accepted
+        correspondence has weight 1), 'huber', 'tukey' or 'cauchy' with its scale k in metres (finite, > 0; 'l2' ignores it).
+        Residuals: point-to-plane (p - q) . n, point-to-point |p - q|.  Refused with reference-order accumulation at call time."""
+        if kind not in self.ICP_LOSS:
+            raise ValueError("unknown ICP loss %r (one of %s)" % (kind, ", ".join(self.ICP_LOSS)))
+        if kind != "l2" and scale is None:
+            raise ValueError("the %s loss needs a scale" % kind)
+        _check(self._h, lib().tdv_ctx_set_icp_loss(self._h, self.ICP_LOSS[kind], C.c_float(0.0 if scale is None else float(scale))),
+               "tdv_ctx_set_icp_loss")
+
+    def icp_loss(self):
+        """(kind, scale) of this context's ICP loss; scale is 0.0 for 'l2'."""
+        k = C.c_int(); sc = C.c_float()
+        _check(self._h, lib().tdv_ctx_get_icp_loss(self._h, C.byref(k), C.byref(sc)), "tdv_ctx_get_icp_loss")
+        return {v: n for n, v in self.ICP_LOSS.items()}[k.value], float(sc.value)
 
     def set_ransac_score(self, mode):
         """'fast' (default: FMA pass, chunks inside the rounding band re-scored with the reference arithmetic) or 'exact'

@@ -260,6 +260,7 @@ int tdv_icp(tdv_ctx* ctx, const float* src, int ns, const float* tgt, const floa
             tdv_icp_result* out) {
     if (!out || !T0 || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tgt)) return TDV_ERR_BAD_ARG;
     TDV_TRY(begin(ctx));
+    TDV_TRY(icp_loss_check(ctx));
     float *d_src, *d_tgt, *d_nrm;
     TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
     TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
@@ -295,6 +296,7 @@ int tdv_icp_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
                 int fixed_iterations, tdv_icp_result* out) {
     TDV_TRY(begin(ctx));
+    TDV_TRY(icp_loss_check(ctx));
     return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, fixed_iterations, out);
 }
 int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets, int n_instances, const float* d_tgt, const float* d_tgt_normals,
@@ -307,6 +309,7 @@ int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets
     for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
     if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
     TDV_TRY(begin(ctx));
+    TDV_TRY(icp_loss_check(ctx));
     std::vector<int> count((size_t)n_instances);
     for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
     TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,

@@ -298,7 +298,8 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         std::vector<std::thread> workers;
         for (int l = 1; l < L; ++l) {
             tdv_ctx* h = lane_ctx[l];
-            h->timing = ctx->timing; h->icp_search = ctx->icp_search; h->icp_accumulate = ctx->icp_accumulate; h->ransac_score_mode = ctx->ransac_score_mode; h->err[0] = 0;
+            h->timing = ctx->timing; h->icp_search = ctx->icp_search; h->icp_accumulate = ctx->icp_accumulate;
+            h->icp_loss = ctx->icp_loss; h->icp_loss_scale = ctx->icp_loss_scale; h->ransac_score_mode = ctx->ransac_score_mode; h->err[0] = 0;
             workers.emplace_back([&, h, l]() {
                 try {
                     if (hipSetDevice(h->device) != hipSuccess) { status[l] = TDV_ERR_NO_DEVICE; return; }
@@ -531,6 +532,7 @@ int tdv_register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d
     if (!ctx) return TDV_ERR_BAD_ARG;
     TDV_HIP(ctx, hipSetDevice(ctx->device));
     ctx->err[0] = 0;
+    TDV_TRY(icp_loss_check(ctx));
     TDV_TRY(ws_reset(ctx));
     return register_batch_dev(ctx, d_raw, d_bgr, d_masks, n_instances, prm, d_model_xyz, d_model_normals, d_model_fpfh, n_model, results);
 }
@@ -546,6 +548,7 @@ int tdv_refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_b
     (void)d_bgr;  // colours do not enter the registration chain
     TDV_HIP(ctx, hipSetDevice(ctx->device));
     ctx->err[0] = 0;
+    TDV_TRY(icp_loss_check(ctx));
     TDV_TRY(ws_reset(ctx));
     return refine_batch_dev(ctx, d_raw, d_masks, n_instances, prm, h_T0, d_model_xyz, d_model_normals, n_model, results);
 }

@@ -218,6 +218,21 @@ int tdv_ctx_set_icp_accumulation(tdv_ctx* ctx, int mode) {
     return TDV_OK;
 }
 
+int tdv_ctx_set_icp_loss(tdv_ctx* ctx, int loss, float scale) {
+    if (!ctx || loss < TDV_ICP_LOSS_L2 || loss > TDV_ICP_LOSS_CAUCHY) return TDV_ERR_BAD_ARG;
+    if (loss != TDV_ICP_LOSS_L2 && !(std::isfinite(scale) && scale > 0.f)) return TDV_ERR_BAD_ARG;
+    ctx->icp_loss = loss;
+    ctx->icp_loss_scale = loss == TDV_ICP_LOSS_L2 ? 0.f : scale;
+    return TDV_OK;
+}
+
+int tdv_ctx_get_icp_loss(tdv_ctx* ctx, int* loss, float* scale) {
+    if (!ctx) return TDV_ERR_BAD_ARG;
+    if (loss) *loss = ctx->icp_loss;
+    if (scale) *scale = ctx->icp_loss_scale;
+    return TDV_OK;
+}
+
 int tdv_ctx_set_icp_search(tdv_ctx* ctx, int mode) {
     if (!ctx || mode < TDV_ICP_SEARCH_AUTO || mode > TDV_ICP_SEARCH_GRID) return TDV_ERR_BAD_ARG;
     ctx->icp_search = mode;

@@ -32,6 +32,8 @@
 //  * many instances against one target (icp_batch_run_dev: tdv_icp_batch_dev, tdv_refine_batch_dev): one hash grid over the target
 //    for the call, then k_icp_nn_grid_multi + k_icp_accumulate_multi - two launches per iteration for the whole batch, blocks padded
 //    per instance, each instance with the slab layout its single call would use, so that its bits are the single call's.
+//  * robust losses (tdv_ctx_set_icp_loss): every accepted correspondence's terms are scaled by its weight in acc_terms, the one place
+//    all tree-sum paths form them; the kernels take ROBUST as a template parameter, so the L2 instantiations are the code without it.
 // No float atomics anywhere: two runs give identical bits.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
@@ -56,7 +58,22 @@ constexpr int NN_BLOCK = NN_BLOCK_VALUE;    // two waves per workgroup (no LDS, 
 constexpr int NN_SRC_PER_BLOCK = NN_SPL * NN_BLOCK;
 constexpr double PRUNED_MIN_PAIRS = 1e8;   // auto mode: pruned search from this many source x target pairs ...
 constexpr int PRUNED_MIN_TARGETS = 4096;    // ... and targets (measured: 50k x 10k 0.042 vs 0.081 ms, 128k x 9.4k see DESIGN)
-constexpr int ACC_NV = 32;     // reduction slots per block (29 used p2plane, 17 p2point)
+constexpr int ACC_NV = 32;     // reduction slots per block (29 used p2plane, 17 p2point; with a robust loss 30 and 19)
+
+// a robust loss as the kernels take it: TDV_ICP_LOSS_HUBER / _TUKEY / _CAUCHY and its scale k (include/tdv_hip.h)
+struct IcpLoss { int kind; float scale; };
+
+// the IRLS weight of an accepted correspondence with residual e (f32, no contraction: -ffp-contract=off)
+__device__ __forceinline__ float loss_weight(IcpLoss L, float e) {
+    const float a = fabsf(e), k = L.scale;
+    if (L.kind == TDV_ICP_LOSS_HUBER) return a <= k ? 1.f : k / a;
+    const float u = a / k;
+    if (L.kind == TDV_ICP_LOSS_TUKEY) {
+        const float t = 1.f - u * u;
+        return a <= k ? t * t : 0.f;
+    }
+    return 1.f / (1.f + u * u);   // Cauchy
+}
 
 struct IcpState {
     float T[16];       // current transform, column-major
@@ -423,12 +440,16 @@ __device__ __forceinline__ double wave_sum(double v) {
 // tail of the iteration does not begin with another round trip to memory)
 // REF (reference-order accumulation, below): tot[] holds float sums; in point-to-point mode tot[2..4] / tot[5..7] are the two
 // MEANS (already divided, registration.cpp:380-381) and tot[8..16] the centred cross-covariance of :383-386.
-template <int MODE, bool REF = false>
+// ROBUST (weighted sums, acc_terms): tot[acc_nv - 1] counts the correspondences of weight > 0, and point-to-point divides by the
+// weight sum tot[17] instead of n_corr.
+template <int MODE, bool REF = false, bool ROBUST = false>
 __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_iterations, int iter, float prev_rmse, const float* Tcur, float* solve_ws /* LDS, 54 words */) {
+    static_assert(!(REF && ROBUST), "reference-order sums have no loss");
     const int n_corr = (int)(tot[0] + 0.5);
     st->iter = iter + 1;
     st->n_corr = n_corr;
-    if (n_corr < 3) {  // registration.cpp:361 — break, keeping the previous result
+    if (n_corr < 3 ||  // registration.cpp:361 — break, keeping the previous result
+        (ROBUST && (int)(tot[MODE == 0 ? 29 : 18] + 0.5) < 3)) {   // (the same break when fewer than 3 have a weight: Tukey beyond its scale)
         if (!fixed_iterations) st->done = 1;
         return;
     }
@@ -446,7 +467,7 @@ __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_it
         for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) delta[c * 4 + r] = dl::el(dR, r, c);
         delta[12] = x[3]; delta[13] = x[4]; delta[14] = x[5];
     } else {
-        const double n = (double)n_corr;
+        const double n = ROBUST ? tot[17] : (double)n_corr;
         double sm[3] = {tot[2], tot[3], tot[4]};
         double tm[3] = {tot[5], tot[6], tot[7]};
         if (!REF) for (int a = 0; a < 3; ++a) { sm[a] /= n; tm[a] /= n; }
@@ -476,8 +497,9 @@ __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_it
 // The pieces of one accumulation launch, shared by k_icp_accumulate (one problem) and k_icp_accumulate_multi (one problem per
 // instance of a batch): the sums of one accepted correspondence, the block's slab and the fold of the last block, the update.
 // MODE 0: point-to-plane (21 upper-triangular JtJ + 6 Jtr), MODE 1: point-to-point moments, MODE 2: count / error only.
-template <int MODE>
-constexpr int acc_nv() { return MODE == 0 ? 29 : (MODE == 1 ? 17 : 2); }
+// ROBUST: + n_eff (correspondences of weight > 0) last, point-to-point the weight sum W before it.
+template <int MODE, bool ROBUST = false>
+constexpr int acc_nv() { return MODE == 0 ? (ROBUST ? 30 : 29) : (MODE == 1 ? (ROBUST ? 19 : 17) : 2); }
 
 // the pose a launch reads at its start: the 3x4 part column by column, and the bottom row
 __device__ __forceinline__ void acc_load_pose(const IcpState* st, float* T /* 12 */, float* Tb /* 4 */) {
@@ -514,37 +536,50 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // {1, d2, then MODE 0 the 21 upper-triangular J[a] * J[b] and the 6 J[a] * r, each product formed in float and widened; MODE 1 p, q
 // and the 9 p[a] * q[b], p and q widened first}.  put is the caller's way of combining them (+= into a lane's sums, = into a fresh
 // slab row: 0.0 + -0.0 is +0.0); each term is put as it is formed.
-template <int MODE, class Put>
+// ROBUST: the weight w = loss_weight(L, e) of this correspondence (e = r point-to-plane, sqrtf(d2) point-to-point) scales every
+// term after the first two: (double)w * term, exact for the f32 products of point-to-plane and for p and q; w * (P[a] * Q[b]) is
+// rounded once.  Then point-to-point W = w, and last n_eff = (w > 0).  {1, d2} stay unweighted: n_corr, rmse and fitness are L2's.
+template <int MODE, bool ROBUST = false, class Put>
 __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
-                                          Put put) {
+                                          IcpLoss L, Put put) {
     put(0, 1.0); put(1, (double)d2);
     if (MODE == 2) return;
     float q[3], J[6], r;
     corr_terms<MODE>(px, py, pz, idx, tgt, tgt_normals, q, J, r);
+    float w = 1.f;
+    if (ROBUST) w = loss_weight(L, MODE == 0 ? r : sqrtf(d2));
+    const double wd = w;
     if (MODE == 0) {
         int k = 2;
 #pragma unroll
         for (int a = 0; a < 6; ++a)
 #pragma unroll
-            for (int b = a; b < 6; ++b) put(k++, (double)(J[a] * J[b]));
+            for (int b = a; b < 6; ++b) put(k++, ROBUST ? wd * (double)(J[a] * J[b]) : (double)(J[a] * J[b]));
 #pragma unroll
-        for (int a = 0; a < 6; ++a) put(k++, (double)(J[a] * r));
+        for (int a = 0; a < 6; ++a) put(k++, ROBUST ? wd * (double)(J[a] * r) : (double)(J[a] * r));
+        if (ROBUST) put(29, w > 0.f ? 1.0 : 0.0);
     } else {
         const double P[3] = {px, py, pz}, Q[3] = {q[0], q[1], q[2]};
-        put(2, P[0]); put(3, P[1]); put(4, P[2]);
-        put(5, Q[0]); put(6, Q[1]); put(7, Q[2]);
+        if (ROBUST) {
+            put(2, wd * P[0]); put(3, wd * P[1]); put(4, wd * P[2]);
+            put(5, wd * Q[0]); put(6, wd * Q[1]); put(7, wd * Q[2]);
+        } else {
+            put(2, P[0]); put(3, P[1]); put(4, P[2]);
+            put(5, Q[0]); put(6, Q[1]); put(7, Q[2]);
+        }
 #pragma unroll
         for (int a = 0; a < 3; ++a)
 #pragma unroll
-            for (int b = 0; b < 3; ++b) put(8 + a * 3 + b, P[a] * Q[b]);
+            for (int b = 0; b < 3; ++b) put(8 + a * 3 + b, ROBUST ? wd * (P[a] * Q[b]) : P[a] * Q[b]);
+        if (ROBUST) { put(17, wd); put(18, w > 0.f ? 1.0 : 0.0); }
     }
 }
 
 // this lane's sums += one accepted correspondence (p, target idx at squared distance best)
-template <int MODE>
+template <int MODE, bool ROBUST = false>
 __device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
-                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals) {
-    acc_terms<MODE>(px, py, pz, best, idx, tgt, tgt_normals, [v](int k, double t) { v[k] += t; });
+                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L) {
+    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, [v](int k, double t) { v[k] += t; });
 }
 
 // LDS of one accumulation block
@@ -558,9 +593,9 @@ struct AccShared {
 // Every block reduces its lanes' sums v[] to its slab slabs[slab] (fixed order: wave64 DPP -> LDS); the block that takes the last
 // of nblocks tickets folds slabs[0 .. nblocks) in a fixed order into sh.tot[] and returns true (all its threads) - the result
 // does not depend on which block that is.  The caller's thread 0 of that block then resets *ticket and updates the state.
-template <int MODE>
+template <int MODE, bool ROBUST = false>
 __device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, int slab, int nblocks, unsigned* ticket, AccShared& sh) {
-    constexpr int NV = acc_nv<MODE>();
+    constexpr int NV = acc_nv<MODE, ROBUST>();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < NV; ++k) {
@@ -607,14 +642,14 @@ __device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, in
 }
 
 // thread 0 of the folding block: solve, update, stopping rule from the folded sums (pose as acc_load_pose read it)
-template <int MODE>
+template <int MODE, bool ROBUST = false>
 __device__ __forceinline__ void acc_finish(AccShared& sh, int ns, IcpState* st, int fixed_iterations, int iter0, float rmse0, const float* T, const float* Tb) {
     if (MODE == 2) st->n_corr = (int)(sh.tot[0] + 0.5);
     else {
         float T16[16];
 #pragma unroll
         for (int c = 0; c < 4; ++c) { T16[c * 4] = T[c * 3]; T16[c * 4 + 1] = T[c * 3 + 1]; T16[c * 4 + 2] = T[c * 3 + 2]; T16[c * 4 + 3] = Tb[c]; }
-        icp_update<MODE>(sh.tot, ns, st, fixed_iterations, iter0, rmse0, T16, sh.solve_ws);
+        icp_update<MODE, false, ROBUST>(sh.tot, ns, st, fixed_iterations, iter0, rmse0, T16, sh.solve_ws);
     }
 }
 
@@ -643,13 +678,13 @@ __device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const 
 
 // One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
 // slabs in a fixed order, solves, and updates the state on the device.
-template <int MODE, int ACC_PPT>   // ACC_PPT source points per thread (summed per lane in index order)
+template <int MODE, int ACC_PPT, bool ROBUST = false>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
 __global__ __launch_bounds__(256)
 void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
                       const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz,
                       int nsplit, const float* __restrict__ pd2, const int* __restrict__ pchunk, int direct,
-                      IcpState* st, float tau_accept, int fixed_iterations,
+                      IcpState* st, float tau_accept, int fixed_iterations, IcpLoss loss,
                       double* slabs, unsigned* ticket,
                       int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc) {
     if (st->done) return;
@@ -672,13 +707,13 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
         if (out_d2) out_d2[i] = best;
         if (out_acc) out_acc[i] = acc ? 1 : 0;
         if (!acc) continue;
-        acc_add<MODE>(v, px, py, pz, best, idx, tgt, tgt_normals);
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss);
     }
     __shared__ AccShared sh;
-    if (!acc_slab_fold<MODE>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
+    if (!acc_slab_fold<MODE, ROBUST>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
     if (threadIdx.x != 0) return;
     *ticket = 0u;   // ready for the next launch (stream order)
-    acc_finish<MODE>(sh, ns, st, fixed_iterations, iter0, rmse0, T, Tb);
+    acc_finish<MODE, ROBUST>(sh, ns, st, fixed_iterations, iter0, rmse0, T, Tb);
 }
 
 // ---- many instances against one target: two launches per iteration for the whole batch -------------------------------------
@@ -717,12 +752,12 @@ void k_icp_nn_grid_multi(const float* __restrict__ src, const IcpInst* __restric
 
 // k_icp_accumulate for every instance: instance b's blocks write its slabs and take its ticket word tickets[b]; the last of them
 // folds, solves and updates st[b].  The points-per-thread count is uniform over a block (runtime loop, as the single kernel's).
-template <int MODE>
+template <int MODE, bool ROBUST = false>
 __global__ __launch_bounds__(256)
 void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __restrict__ inst, const int* __restrict__ blk_inst,
                             const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
                             const float* __restrict__ pd2, const int* __restrict__ pidx,
-                            IcpState* st_all, float tau_accept, int fixed_iterations, double* slabs, unsigned* tickets) {
+                            IcpState* st_all, float tau_accept, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* tickets) {
     const int b = blk_inst[blockIdx.x];
     IcpState* st = st_all + b;
     if (st->done) return;
@@ -745,13 +780,13 @@ void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __rest
         const float best = d < FLT_MAX ? d : FLT_MAX;
         const int idx = d < FLT_MAX ? pidx[in.src_off + i] : 0;
         if (!(best <= tau_accept)) continue;
-        acc_add<MODE>(v, px, py, pz, best, idx, tgt, tgt_normals);
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss);
     }
     __shared__ AccShared sh;
-    if (!acc_slab_fold<MODE>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
+    if (!acc_slab_fold<MODE, ROBUST>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
     if (threadIdx.x != 0) return;
     tickets[b] = 0u;   // ready for the next launch (stream order)
-    acc_finish<MODE>(sh, in.ns, st, fixed_iterations, iter0, rmse0, T, Tb);
+    acc_finish<MODE, ROBUST>(sh, in.ns, st, fixed_iterations, iter0, rmse0, T, Tb);
 }
 
 // ---- reference-order accumulation (round 4; TDV_ICP_ACCUMULATE_REFERENCE) ------------------------------------------------
@@ -994,11 +1029,12 @@ constexpr long long SM_MAX_PAIRS_BATCH = 1ll << 20;     // ... per problem of a 
 // A grid of several workgroups runs one problem each (the batch's small instances against the shared model): problem b takes the
 // source points [src_off[b], src_off[b + 1]) of src0 and the states st_in[b] / st_out[b]; src_off == nullptr: one problem.
 // 1,024 lanes and room for 2,048 x 2,048 points.
-template <int MODE, bool REF>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS
+template <int MODE, bool REF, bool ROBUST = false>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS; ROBUST: loss
 __global__ __launch_bounds__(SM_THREADS)
 void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict__ src_off, const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
-                 const IcpState* __restrict__ st_in0, float tau_accept, int max_iterations, int fixed_iterations,
+                 const IcpState* __restrict__ st_in0, float tau_accept, int max_iterations, int fixed_iterations, IcpLoss loss,
                  IcpState* __restrict__ st_out0, IcpState* __restrict__ st_host) {
+    static_assert(!(REF && ROBUST), "reference-order sums have no loss");
     const int prob = blockIdx.x;
     const float* __restrict__ src = src_off ? src0 + (size_t)src_off[prob] * 3 : src0;
     const int ns = src_off ? src_off[prob + 1] - src_off[prob] : ns0;
@@ -1026,7 +1062,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
     }
     if (threadIdx.x == 0) st = *st_in;
     __syncthreads();
-    constexpr int NV = acc_nv<MODE>();
+    constexpr int NV = acc_nv<MODE, ROBUST>();
     const int nblocks = (ns + 255) / 256;
     for (int it = 0; it < max_iterations; ++it) {
         float T[16];
@@ -1126,7 +1162,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
                 float px, py, pz;
                 transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
                 const float best = sbest[i]; const int idx = sidx[i];
-                if (best <= tau_accept) acc_terms<MODE>(px, py, pz, best, idx, tgt, tgt_normals, [&v](int k, double t) { v[k] = t; });
+                if (best <= tau_accept) acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, [&v](int k, double t) { v[k] = t; });
             }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -1154,7 +1190,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
         }
         __syncthreads();
         // (d) solve, update, stopping rule
-        if (threadIdx.x == 0) icp_update<MODE>(tot, ns, &st, fixed_iterations, iter0, rmse0, T, solve_ws);
+        if (threadIdx.x == 0) icp_update<MODE, false, ROBUST>(tot, ns, &st, fixed_iterations, iter0, rmse0, T, solve_ws);
         __syncthreads();
         if (st.done) break;
     }
@@ -1265,14 +1301,19 @@ void state_result(const IcpState& h, tdv_icp_result& out) {
     out.fitness = h.fitness; out.rmse = h.rmse; out.iterations = h.applied; out.n_corr = h.last_n_corr_applied;
 }
 
+// the ctx's loss as the kernels take it, and whether it is a robust one (the ROBUST instantiations)
+IcpLoss ctx_loss(const tdv_ctx* ctx) { return IcpLoss{ctx->icp_loss, ctx->icp_loss_scale}; }
+bool ctx_robust(const tdv_ctx* ctx) { return ctx->icp_loss != TDV_ICP_LOSS_L2; }
+
 // k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points), point-to-plane where normals are given, with the
-// ctx's accumulation
+// ctx's accumulation and loss (icp_loss_check: no loss with reference-order sums)
 void launch_icp_small(tdv_ctx* ctx, int n_prob, const float* d_src, int ns, const int* d_src_off, const float* d_tgt, const float* d_tgt_normals, int nt,
                       int point_to_plane, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host) {
-    const bool p2pl = point_to_plane && d_tgt_normals, ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
-    const auto kernel = p2pl ? (ref ? k_icp_small<0, true> : k_icp_small<0, false>) : (ref ? k_icp_small<1, true> : k_icp_small<1, false>);
+    const bool p2pl = point_to_plane && d_tgt_normals, ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE, robust = ctx_robust(ctx);
+    const auto kernel = p2pl ? (ref ? k_icp_small<0, true> : robust ? k_icp_small<0, false, true> : k_icp_small<0, false>)
+                             : (ref ? k_icp_small<1, true> : robust ? k_icp_small<1, false, true> : k_icp_small<1, false>);
     kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, p2pl ? d_tgt_normals : nullptr, nt, st_in, tau, max_iterations, fixed_iterations,
-                                                   st_out, st_host);
+                                                   ctx_loss(ctx), st_out, st_host);
 }
 
 // Iterations are enqueued in bursts between two looks at the n states d_st (read back into the pinned h[0 .. n)); once a state is done
@@ -1341,6 +1382,8 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     const NnPlan& p = pl.p;
     const CellGrid& cg = pl.cg;
     const bool ref_acc = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
+    const bool robust = ctx_robust(ctx);
+    const IcpLoss loss = ctx_loss(ctx);
     TDV_TRY(pin_reserve(ctx, 2 * sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
     init_states(h, T0, 1);
@@ -1411,8 +1454,9 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 k_icp_fold_ref<1><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
             }
         } else if (p2pl) {
-#define TDV_ACC1(MM, PP, NRM) k_icp_accumulate<MM, PP><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, NRM, b.tx, b.ty, b.tz, \
-                               p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, b.slabs, b.ticket, nullptr, nullptr, nullptr)
+#define TDV_ACC2(MM, PP, RR, NRM) k_icp_accumulate<MM, PP, RR><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, NRM, b.tx, b.ty, b.tz, \
+                               p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr)
+#define TDV_ACC1(MM, PP, NRM) do { if (robust) TDV_ACC2(MM, PP, true, NRM); else TDV_ACC2(MM, PP, false, NRM); } while (0)
 #ifdef TDV_STUDY
 #define TDV_ACC(MM, NRM) do { if (p.acc_ppt == 8) TDV_ACC1(MM, 8, NRM); else if (p.acc_ppt == 4) TDV_ACC1(MM, 4, NRM); else if (p.acc_ppt == 2) TDV_ACC1(MM, 2, NRM); else TDV_ACC1(MM, 1, NRM); } while (0)
 #else
@@ -1558,20 +1602,31 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const int* d_blk_acc = d_blk_nn + nn_blocks;
     const GridEntry* gtable = reinterpret_cast<const GridEntry*>(cg.table);
     const float4* gnode = reinterpret_cast<const float4*>(cg.node);
-    const bool p2pl = point_to_plane && d_tgt_normals;
+    const bool p2pl = point_to_plane && d_tgt_normals, robust = ctx_robust(ctx);
+    const IcpLoss loss = ctx_loss(ctx);
     ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
     TDV_TRY(run_bursts(ctx, h, d_st, n, max_iterations, fixed_iterations, [&]() {
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
             k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);
         }
-        if (p2pl) k_icp_accumulate_multi<0><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
-        else k_icp_accumulate_multi<1><<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, nullptr, pd2, pidx, d_st, tau, fixed_iterations, slabs, tickets);
+        const auto acc = p2pl ? (robust ? k_icp_accumulate_multi<0, true> : k_icp_accumulate_multi<0>) : (robust ? k_icp_accumulate_multi<1, true> : k_icp_accumulate_multi<1>);
+        acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, p2pl ? d_tgt_normals : nullptr, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets);
     }));
     for (int b = 0; b < n; ++b) state_result(h[b], out[b]);
     return TDV_OK;
 }
 
+int icp_loss_check(tdv_ctx* ctx) {
+    if (ctx->icp_loss != TDV_ICP_LOSS_L2 && ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
+        snprintf(ctx->err, sizeof(ctx->err), "icp: a robust loss (tdv_ctx_set_icp_loss) cannot run with reference-order accumulation, whose float "
+                 "sums are the reference's and have no loss; set TDV_ICP_LOSS_L2 or TDV_ICP_ACCUMULATE_TREE");
+        return TDV_ERR_BAD_ARG;
+    }
+    return TDV_OK;
+}
+
+// (the loss does not enter: one correspondence pass, its outputs and n_corr only)
 int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                             const float* T, float thr, IcpOutputs outs, int* n_corr) {
     if (!ctx || !d_src || !d_tgt || !T || ns <= 0 || nt <= 0) return TDV_ERR_BAD_ARG;
@@ -1605,7 +1660,7 @@ int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const floa
                                                                       p.chunks_per_split, b.st, b.pd2, b.pchunk);
     }
     k_icp_accumulate<2, 1><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nullptr, b.tx, b.ty, b.tz, p.nsplit,
-                                                        b.pd2, b.pchunk, pruned ? 1 : 0, b.st, tau, 0, b.slabs, b.ticket, outs.corr, outs.d2, outs.accepted);
+                                                        b.pd2, b.pchunk, pruned ? 1 : 0, b.st, tau, 0, IcpLoss{TDV_ICP_LOSS_L2, 0.f}, b.slabs, b.ticket, outs.corr, outs.d2, outs.accepted);
     TDV_CHECK_LAUNCH(ctx);
     TDV_HIP(ctx, hipMemcpyAsync(h, b.st, sizeof(IcpState), hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipStreamSynchronize(s));

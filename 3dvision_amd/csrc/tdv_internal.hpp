@@ -35,6 +35,8 @@ struct tdv_ctx {
     bool timing = false;
     int icp_search = 0;      // TDV_ICP_SEARCH_AUTO / _BRUTE / _PRUNED / _GRID (tdv_ctx_set_icp_search)
     int icp_accumulate = 0;  // TDV_ICP_ACCUMULATE_TREE (f64 fixed tree) / _REFERENCE (f32, ascending source index: the CPU path's sums bit for bit)
+    int icp_loss = 0;        // TDV_ICP_LOSS_L2 / _HUBER / _TUKEY / _CAUCHY (tdv_ctx_set_icp_loss)
+    float icp_loss_scale = 0.f;   // its scale k (0 with L2)
     int ransac_score_mode = 0;    // TDV_RANSAC_SCORE_FAST (FMA pass + exact band) / _EXACT (the reference arithmetic only) / _MATRIX (tdv_ctx_set_ransac_score)
     double last_ransac_rescore = -1.0;   // fraction of (wave, 8-point chunk) pairs of the last RANSAC call that the fast pass scored again exactly (-1: exact mode)
     double last_ransac_scored = 1.0;     // share of the (hypothesis, point) tests the last RANSAC call evaluated (< 1: the exact bail-out left the rest out)
@@ -158,6 +160,9 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
                       int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out);
 int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                             const float* T, float thr, IcpOutputs outs, int* n_corr);
+// TDV_ERR_BAD_ARG (reason in ctx->err) when the ctx's ICP loss cannot run with its accumulation mode (a robust loss with
+// reference-order sums); the ICP entry points ask before they enqueue or write anything
+int icp_loss_check(tdv_ctx* ctx);
 int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel, int max_iterations, float confidence, uint32_t seed,

@@ -79,6 +79,32 @@ int tdv_ctx_set_icp_search(tdv_ctx* ctx, int mode);
 #define TDV_ICP_ACCUMULATE_TREE 0
 #define TDV_ICP_ACCUMULATE_REFERENCE 1
 int tdv_ctx_set_icp_accumulation(tdv_ctx* ctx, int mode);
+/* ICP robust loss: iteratively reweighted least squares, one weight w per accepted correspondence (d2 <= thr^2, unchanged), set
+ * per ctx and honoured by tdv_icp, tdv_icp_dev, tdv_icp_batch_dev, tdv_refine_batch_dev and tdv_register_batch_dev (batch lanes
+ * included).  tdv_icp_correspondences is unaffected.  L2 (default) gives every accepted correspondence weight 1: today's results,
+ * bit for bit.
+ *   Residual e: point-to-plane the signed r = (p - q) . n the sums use; point-to-point e = sqrtf(d2).
+ *   Weight, in f32 without contraction, a = |e|, k = scale:
+ *     HUBER   w = a <= k ? 1 : k / a
+ *     TUKEY   w = a <= k ? t * t : 0,  t = 1 - u * u,  u = a / k
+ *     CAUCHY  w = 1 / (1 + u * u),     u = a / k
+ *   Point-to-plane sums: (double)w * (double)(J[a] * J[b]) and (double)w * (double)(J[a] * r) - exact products in f64.
+ *   Point-to-point (weighted Kabsch): W = sum (double)w, sums of (double)w * (double)p[a] and (double)w * (double)q[a] (exact),
+ *   and of (double)w * ((double)p[a] * (double)q[b]) (the f64 product of p and q is exact; the one rounding is the product with w);
+ *   means sm = sum w p / W, tm = sum w q / W and H = f32(sum w p q^T - (W * sm[a]) * tm[b]), all in f64.
+ *   Unweighted, as with L2: n_corr, fitness = n_corr / ns, rmse = sqrt(sum d2 / n_corr) and the stopping rule |delta rmse| < 1e-6.
+ *   An iteration where fewer than 3 accepted correspondences have w > 0 (Tukey only) breaks as n_corr < 3 does: the pose is kept,
+ *   and with fixed_iterations the loop goes on.
+ * An unknown loss, or a scale that is not finite and > 0 for a non-L2 loss, returns TDV_ERR_BAD_ARG and leaves the setting as it
+ * was; L2 ignores scale (and reads back 0).  No environment variable selects a loss.  Reference-order accumulation reproduces the
+ * reference's float sums, which have no loss: with TDV_ICP_ACCUMULATE_REFERENCE and a non-L2 loss, the five ICP entry points above
+ * return TDV_ERR_BAD_ARG before anything is enqueued or written, with the reason in tdv_last_error. */
+#define TDV_ICP_LOSS_L2 0
+#define TDV_ICP_LOSS_HUBER 1
+#define TDV_ICP_LOSS_TUKEY 2
+#define TDV_ICP_LOSS_CAUCHY 3
+int tdv_ctx_set_icp_loss(tdv_ctx* ctx, int loss, float scale);
+int tdv_ctx_get_icp_loss(tdv_ctx* ctx, int* loss, float* scale);
 /* RANSAC hypothesis scoring.  FAST (default; env TDV_RANSAC_SCORE=exact overrides) evaluates every (hypothesis, point) with
  * fused multiply-adds and re-scores, with the reference's unfused arithmetic, every chunk of points in which a distance
  * falls inside the rounding band where the two could disagree: the inlier counts are those of EXACT, which runs the

@@ -12,7 +12,12 @@ After a warm-up the three alternate over --repeats rounds.  Prints one JSON line
 the refine call differs from the batched call, or when an instance lies further than --max-angle rad / --max-trans m from its
 ground truth.
 
+--loss / --loss-scale set ICP's robust loss (tdv_ctx_set_icp_loss) for the three refinements; the poses come from an L2 registration
+either way, and the default l2 measures what it always did.  --clutter-px N lets every mask bleed N pixels onto a bin floor: the
+background pixels of that ring get a flat depth --clutter-gap-mm behind the instance's farthest pixel (mask bleed at C4 size).
+
     python tools/bench_refine.py [--instances 256] [--repeats 5] [--icp-iters 50] [--order first|reference]
+                                 [--loss l2|huber|tukey|cauchy --loss-scale K] [--clutter-px N --clutter-gap-mm G]
 """
 import argparse
 import importlib
@@ -35,6 +40,21 @@ def _bench_batch():
     return mod
 
 
+def add_floor_bleed(torch, wl, px, gap):
+    """Every mask grows by px pixels; where that ring has no depth, a flat floor gap depth units behind the instance's farthest pixel."""
+    depth, masks = wl["depth"], wl["masks"]
+    for b in range(depth.shape[0]):
+        m = masks[b] > 0
+        if not bool(m.any()):
+            continue
+        far = int(depth[b][m].to(torch.int32).max().item())     # (int16 storage of uint16 depth: the frames stay below 2^15 units)
+        grown = torch.nn.functional.max_pool2d(m[None, None].float(), 2 * px + 1, stride=1, padding=px)[0, 0] > 0
+        ring = grown & ~m & (depth[b] == 0)
+        depth[b][ring] = min(far + gap, 32767)
+        masks[b][ring] = 255
+    wl["mask_px"] = [int(x) for x in (masks > 0).sum((1, 2)).tolist()]
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--instances", type=int, default=256)
@@ -50,6 +70,10 @@ def main():
     ap.add_argument("--max-angle", type=float, default=1.5e-4)
     ap.add_argument("--max-trans", type=float, default=6e-5)
     ap.add_argument("--seed", type=int, default=3)
+    ap.add_argument("--loss", choices=["l2", "huber", "tukey", "cauchy"], default="l2", help="ICP's robust loss for the refinements")
+    ap.add_argument("--loss-scale", type=float, default=None, help="its scale in metres (default: the acceptance threshold)")
+    ap.add_argument("--clutter-px", type=int, default=0, help="mask bleed onto a bin floor, in pixels (0: none)")
+    ap.add_argument("--clutter-gap-mm", type=float, default=2.0, help="the floor's distance behind each instance's farthest pixel")
     args = ap.parse_args()
     import torch
     bb = _bench_batch()
@@ -67,11 +91,14 @@ def main():
     prm = tdv.batch_params(width=W, height=H, scale_to_meters=bb.SCALE, fx=bb.F, fy=bb.F, cx=bb.CX, cy=bb.CY, zmax=bb.ZMAX, voxel_size=voxel,
                            ransac_max_iterations=args.hyps, icp_max_iterations=args.icp_iters, icp_distance_factor=args.icp_factor,
                            voxel_order=order, n_frames=B)
+    if args.clutter_px > 0:
+        add_floor_bleed(torch, wl, args.clutter_px, int(round(args.clutter_gap_mm * 1e-3 * bb.SCALE)))
     d_raw, d_masks = wl["depth"].data_ptr(), wl["masks"].data_ptr()
 
     # the poses: one full registration, then a seeded small motion of each (the bin imaged again)
     reg = ctx.register_batch_dev(d_raw, None, d_masks, B, prm, d_mx.data_ptr(), d_mn.data_ptr(), d_mf.data_ptr(), nm)
     T0s = np.stack([synth.perturb(r["T"], seed=1000 + b, angle_deg=args.angle_deg, trans=args.trans_mm * 1e-3) for b, r in enumerate(reg)])
+    ctx.set_icp_loss(args.loss, None if args.loss == "l2" else (args.loss_scale if args.loss_scale is not None else thr))
 
     # the voxel clouds the refine call builds, made with the stagewise device calls: clouds of all frames, then voxels per instance
     cap = int(sum(wl["mask_px"]))
@@ -137,6 +164,8 @@ def main():
                refine=rates("refine"), icp_batch=rates("icp_batch"), icp_loop=rates("icp_loop"),
                angle_to_gt_rad=dict(max=float(ang.max()), mean=float(ang.mean())), translation_to_gt_m=dict(max=float(tr.max()), mean=float(tr.mean())),
                batch_differs_from_single=differ[:16], refine_differs_from_batch=refine_differ[:16], off_ground_truth=far[:16])
+    if args.loss != "l2" or args.clutter_px > 0:       # (the default run prints what it always printed)
+        out.update(icp_loss=list(ctx.icp_loss()), clutter_px=args.clutter_px, clutter_gap_mm=args.clutter_gap_mm)
     print(json.dumps(out))
     ctx.close()
     fail = []
