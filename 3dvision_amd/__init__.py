@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "tdv_register_batch_dev", "tdv_prepare_model_dev", "tdv_bilateral_filter", "tdv_filter_duplicates", "tdv_load_ply_ascii", "tdv_load_mask_png", "tdv_load_masks_from_dir",
     "tdv_depth_to_cloud_batch_dev", "tdv_broadcast_model", "tdv_gather_results", "tdv_mask_resize_nearest", "tdv_mask_resize_nearest_dev", "tdv_voxel_downsample_batch_dev", "tdv_voxel_downsample_batch_pinhole_dev",
     "tdv_icp_batch_dev", "tdv_refine_batch_dev", "tdv_ctx_set_icp_loss", "tdv_ctx_get_icp_loss",
+    "tdv_gicp", "tdv_gicp_dev", "tdv_gicp_batch_dev",
 ]
 
 
@@ -456,6 +457,58 @@ class Context:
         d_tn = torch.from_numpy(tn).to(dev) if tn is not None else None
         return self.icp_batch_dev(d_src.data_ptr(), off, d_tgt.data_ptr(), None if d_tn is None else d_tn.data_ptr(), len(tgt), T0s, thr,
                                   max_iterations, point_to_plane)
+
+    # ---------------------------------------------------------------- generalized ICP (include/tdv_hip.h: tdv_gicp)
+    def gicp(self, src, src_normals, tgt, tgt_normals, T0, thr, max_iterations=200, epsilon=1e-3):
+        """Plane-to-plane ICP from both clouds' normals; the result as icp's."""
+        src = _f32(src); sn = _f32(src_normals); tgt = _f32(tgt); tn = _f32(tgt_normals)
+        res = IcpResultC()
+        t0 = to_colmajor16(T0)
+        _check(self._h, lib().tdv_gicp(self._h, _ptr(src), _ptr(sn), len(src), _ptr(tgt), _ptr(tn), len(tgt), _ptr(t0), C.c_float(thr),
+                                       max_iterations, C.c_float(epsilon), C.byref(res)), "tdv_gicp")
+        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
+                                  iterations=res.iterations, n_corr=res.n_corr)
+
+    def gicp_dev(self, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, T0, thr, max_iterations, epsilon=1e-3, fixed_iterations=False):
+        res = IcpResultC()
+        t0 = to_colmajor16(T0)
+        _check(self._h, lib().tdv_gicp_dev(self._h, _ptr(d_src), _ptr(d_src_normals), ns, _ptr(d_tgt), _ptr(d_tgt_normals), nt, _ptr(t0),
+                                           C.c_float(thr), max_iterations, C.c_float(epsilon), int(fixed_iterations), C.byref(res)), "tdv_gicp_dev")
+        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
+                                  iterations=res.iterations, n_corr=res.n_corr)
+
+    def gicp_batch_dev(self, d_src, d_src_normals, offsets, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, epsilon=1e-3, fixed_iterations=False):
+        """GICP of many clouds against one target in one call (device pointers; the source normals laid out like d_src).  Per instance
+        what gicp_dev returns for that cloud, bit for bit."""
+        off = np.ascontiguousarray(offsets, np.int32)
+        n = len(off) - 1
+        T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
+        t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
+        res = (IcpResultC * max(n, 1))()
+        _check(self._h, lib().tdv_gicp_batch_dev(self._h, _ptr(d_src), _ptr(d_src_normals), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals), nt,
+                                                 _ptr(t0), C.c_float(thr), max_iterations, C.c_float(epsilon), int(fixed_iterations), res),
+               "tdv_gicp_batch_dev")
+        return [RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
+                                   iterations=r.iterations, n_corr=r.n_corr) for r in res[:n]]
+
+    def gicp_batch(self, sources, source_normals, tgt, tgt_normals, T0s, thr, max_iterations=200, epsilon=1e-3):
+        """gicp_batch_dev on host clouds: lists of (n_b, 3) points and normals against one target, uploaded with torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        srcs = [_f32(a).reshape(-1, 3) for a in sources]
+        sns = [_f32(a).reshape(-1, 3) for a in source_normals]
+        if [len(a) for a in sns] != [len(a) for a in srcs]:
+            raise ValueError("gicp_batch: one normal per source point")
+        off = np.zeros(len(srcs) + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in srcs])
+        cat = np.concatenate(srcs) if srcs and off[-1] else np.zeros((1, 3), np.float32)
+        catn = np.concatenate(sns) if sns and off[-1] else np.zeros((1, 3), np.float32)
+        tgt = _f32(tgt); tn = _f32(tgt_normals)
+        d_src = torch.from_numpy(cat).to(dev); d_sn = torch.from_numpy(catn).to(dev)
+        d_tgt = torch.from_numpy(tgt if len(tgt) else np.zeros((1, 3), np.float32)).to(dev)
+        d_tn = torch.from_numpy(tn if len(tn) else np.zeros((1, 3), np.float32)).to(dev)
+        return self.gicp_batch_dev(d_src.data_ptr(), d_sn.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), len(tgt), T0s, thr,
+                                   max_iterations, epsilon)
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

@@ -316,6 +316,49 @@ int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets
                               point_to_plane, fixed_iterations, out));
     return finish(ctx);
 }
+// ---- generalized ICP: tdv_icp / tdv_icp_dev / tdv_icp_batch_dev with the source normals, plane-to-plane terms (icp.hip, MODE 3)
+int tdv_gicp(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
+             const float* T0, float distance_threshold, int max_iterations, float epsilon, tdv_icp_result* out) {
+    if (!out || !T0 || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tgt)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    TDV_TRY(gicp_check(ctx, src_normals, tgt_normals, epsilon));          // (reference-order sums refused: no loss check needed)
+    float *d_src, *d_sn, *d_tgt, *d_tn;
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    TDV_TRY(upload(ctx, src_normals, (size_t)ns * 3, &d_sn));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
+    TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_tn));
+    if (ns == 0 || nt == 0) {
+        std::memcpy(out->T, T0, 64); out->fitness = 0.f; out->rmse = 0.f; out->iterations = 0; out->n_corr = 0;
+        return TDV_OK;
+    }
+    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tn, nt, T0, distance_threshold, max_iterations, 1, 0, out, nullptr, nullptr, IcpGicp{d_sn, 1.f - epsilon});
+}
+int tdv_gicp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
+                 const float* T0, float distance_threshold, int max_iterations, float epsilon, int fixed_iterations, tdv_icp_result* out) {
+    TDV_TRY(begin(ctx));
+    TDV_TRY(gicp_check(ctx, d_src_normals, d_tgt_normals, epsilon));      // (reference-order sums refused: no loss check needed)
+    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, 1, fixed_iterations, out, nullptr, nullptr,
+                       IcpGicp{d_src_normals, 1.f - epsilon});
+}
+int tdv_gicp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances,
+                       const float* d_tgt, const float* d_tgt_normals, int nt, const float* h_T0, float distance_threshold,
+                       int max_iterations, float epsilon, int fixed_iterations, tdv_icp_result* out) {
+    // every argument before anything is enqueued or written (tdv_icp_batch_dev's, then GICP's)
+    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
+    if (n_instances > 0) {
+        if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
+        for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
+        if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
+    }
+    TDV_TRY(begin(ctx));
+    TDV_TRY(gicp_check(ctx, d_src_normals, d_tgt_normals, epsilon));      // (reference-order sums refused: no loss check needed)
+    if (n_instances == 0) return TDV_OK;
+    std::vector<int> count((size_t)n_instances);
+    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
+    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                              1, fixed_iterations, out, IcpGicp{d_src_normals, 1.f - epsilon}));
+    return finish(ctx);
+}
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,

@@ -34,6 +34,9 @@
 //    per instance, each instance with the slab layout its single call would use, so that its bits are the single call's.
 //  * robust losses (tdv_ctx_set_icp_loss): every accepted correspondence's terms are scaled by its weight in acc_terms, the one place
 //    all tree-sum paths form them; the kernels take ROBUST as a template parameter, so the L2 instantiations are the code without it.
+//  * generalized ICP (tdv_gicp, MODE 3): plane-to-plane terms from both clouds' normals in acc_terms, the same 6x6 system, slab layout
+//    and solve as point-to-plane.  Its extra kernel arguments (the source normals, c = 1 - epsilon) arrive as a trailing parameter pack
+//    that is empty for the other modes, so that their kernels keep their arguments and their code.
 // No float atomics anywhere: two runs give identical bits.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
@@ -101,6 +104,13 @@ __device__ __forceinline__ void transform_point(const float* __restrict__ T, flo
     px = (T[0] * sx + (T[4] * sy + T[8] * sz)) + T[12];
     py = (T[1] * sx + (T[5] * sy + T[9] * sz)) + T[13];
     pz = (T[2] * sx + (T[6] * sy + T[10] * sz)) + T[14];
+}
+
+// a = R*s, transform_point without the translation (GICP: a source normal into the pose)
+__device__ __forceinline__ void rotate_point(const float* __restrict__ T, float sx, float sy, float sz, float& ax, float& ay, float& az) {
+    ax = T[0] * sx + (T[4] * sy + T[8] * sz);
+    ay = T[1] * sx + (T[5] * sy + T[9] * sz);
+    az = T[2] * sx + (T[6] * sy + T[10] * sz);
 }
 
 __global__ __launch_bounds__(NN_BLOCK)
@@ -442,21 +452,23 @@ __device__ __forceinline__ double wave_sum(double v) {
 // MEANS (already divided, registration.cpp:380-381) and tot[8..16] the centred cross-covariance of :383-386.
 // ROBUST (weighted sums, acc_terms): tot[acc_nv - 1] counts the correspondences of weight > 0, and point-to-point divides by the
 // weight sum tot[17] instead of n_corr.
+// MODE 3 (GICP) solves its system as point-to-plane does.
 template <int MODE, bool REF = false, bool ROBUST = false>
 __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_iterations, int iter, float prev_rmse, const float* Tcur, float* solve_ws /* LDS, 54 words */) {
     static_assert(!(REF && ROBUST), "reference-order sums have no loss");
+    static_assert(!(REF && MODE == 3), "reference-order sums have no GICP");
     const int n_corr = (int)(tot[0] + 0.5);
     st->iter = iter + 1;
     st->n_corr = n_corr;
     if (n_corr < 3 ||  // registration.cpp:361 — break, keeping the previous result
-        (ROBUST && (int)(tot[MODE == 0 ? 29 : 18] + 0.5) < 3)) {   // (the same break when fewer than 3 have a weight: Tukey beyond its scale)
+        (ROBUST && (int)(tot[(MODE == 0 || MODE == 3) ? 29 : 18] + 0.5) < 3)) {   // (the same break when fewer than 3 have a weight: Tukey beyond its scale)
         if (!fixed_iterations) st->done = 1;
         return;
     }
     float delta[16];
     for (int i = 0; i < 16; ++i) delta[i] = 0.f;
     delta[0] = delta[5] = delta[10] = delta[15] = 1.f;
-    if (MODE == 0) {
+    if (MODE == 0 || MODE == 3) {
         float ATA[36], nb[6], x[6];
         int k = 2;
         for (int a = 0; a < 6; ++a)
@@ -496,10 +508,11 @@ __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_it
 
 // The pieces of one accumulation launch, shared by k_icp_accumulate (one problem) and k_icp_accumulate_multi (one problem per
 // instance of a batch): the sums of one accepted correspondence, the block's slab and the fold of the last block, the update.
-// MODE 0: point-to-plane (21 upper-triangular JtJ + 6 Jtr), MODE 1: point-to-point moments, MODE 2: count / error only.
-// ROBUST: + n_eff (correspondences of weight > 0) last, point-to-point the weight sum W before it.
+// MODE 0: point-to-plane (21 upper-triangular JtJ + 6 Jtr), MODE 1: point-to-point moments, MODE 2: count / error only, MODE 3: GICP
+// (21 upper-triangular JtMJ + 6 JtMe, point-to-plane's slots).  ROBUST: + n_eff (correspondences of weight > 0) last, point-to-point
+// the weight sum W before it.
 template <int MODE, bool ROBUST = false>
-constexpr int acc_nv() { return MODE == 0 ? (ROBUST ? 30 : 29) : (MODE == 1 ? (ROBUST ? 19 : 17) : 2); }
+constexpr int acc_nv() { return (MODE == 0 || MODE == 3) ? (ROBUST ? 30 : 29) : (MODE == 1 ? (ROBUST ? 19 : 17) : 2); }
 
 // the pose a launch reads at its start: the 3x4 part column by column, and the bottom row
 __device__ __forceinline__ void acc_load_pose(const IcpState* st, float* T /* 12 */, float* Tb /* 4 */) {
@@ -516,6 +529,21 @@ __device__ __forceinline__ void acc_transform(const float* T, float sx, float sy
     py = (T[1] * sx + (T[4] * sy + T[7] * sz)) + T[10];
     pz = (T[2] * sx + (T[5] * sy + T[8] * sz)) + T[11];
 }
+
+// a = R*s, the rotation of acc_transform without the translation (a source normal into the current pose)
+__device__ __forceinline__ void acc_rotate(const float* T, float sx, float sy, float sz, float& ax, float& ay, float& az) {
+    ax = T[0] * sx + (T[3] * sy + T[6] * sz);
+    ay = T[1] * sx + (T[4] * sy + T[7] * sz);
+    az = T[2] * sx + (T[5] * sy + T[8] * sz);
+}
+
+// GICP's per-correspondence input besides p and the target: a = R ns, the source normal in the current pose, and c = 1 - epsilon
+// (unused by the other modes)
+struct GicpPt { float ax, ay, az, c; };
+
+// The kernels' GICP arguments from their trailing parameter pack: empty (no GICP) or one IcpGicp
+__device__ __forceinline__ IcpGicp gicp_of() { return IcpGicp{nullptr, 0.f}; }
+__device__ __forceinline__ IcpGicp gicp_of(IcpGicp g) { return g; }
 
 // One accepted correspondence, source point p (transformed) paired with target idx, in the float steps of registration.cpp: its
 // target q and, point-to-plane, J = [p x n | n] (:346-349) and r = (p - q) . n (:351).  Every path's sums and records are built
@@ -536,14 +564,54 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // {1, d2, then MODE 0 the 21 upper-triangular J[a] * J[b] and the 6 J[a] * r, each product formed in float and widened; MODE 1 p, q
 // and the 9 p[a] * q[b], p and q widened first}.  put is the caller's way of combining them (+= into a lane's sums, = into a fresh
 // slab row: 0.0 + -0.0 is +0.0); each term is put as it is formed.
-// ROBUST: the weight w = loss_weight(L, e) of this correspondence (e = r point-to-plane, sqrtf(d2) point-to-point) scales every
-// term after the first two: (double)w * term, exact for the f32 products of point-to-plane and for p and q; w * (P[a] * Q[b]) is
-// rounded once.  Then point-to-point W = w, and last n_eff = (w > 0).  {1, d2} stay unweighted: n_corr, rmse and fitness are L2's.
+// MODE 3 (GICP): the 21 + 6 terms of include/tdv_hip.h (tdv_gicp) from p, the target point and normal and G, each formed in float in
+// the header's order and widened.
+// ROBUST: the weight w = loss_weight(L, e) of this correspondence (e = r point-to-plane, sqrtf(d2) point-to-point, GICP the
+// Mahalanobis residual sqrtf(fmaxf(0, e . g))) scales every term after the first two: (double)w * term, exact for the f32 products of
+// point-to-plane and GICP and for p and q; w * (P[a] * Q[b]) is rounded once.  Then point-to-point W = w, and last n_eff = (w > 0).
+// {1, d2} stay unweighted: n_corr, rmse and fitness are L2's.
 template <int MODE, bool ROBUST = false, class Put>
 __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
-                                          IcpLoss L, Put put) {
+                                          IcpLoss L, GicpPt G, Put put) {
     put(0, 1.0); put(1, (double)d2);
     if (MODE == 2) return;
+    if (MODE == 3) {
+        const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
+        const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
+        const float c = G.c, ax = G.ax, ay = G.ay, az = G.az;
+        // C = 2 I - c (a a^T + n n^T) in f32; M = C^-1 from the cofactors in f64 (C's condition number is about 1 / epsilon: in f32 the
+        // cancellation in the cofactors and the determinant would cost ~1e-7 / epsilon of M), rounded to f32
+        const float C00 = 2.f - c * (ax * ax + nx * nx), C11 = 2.f - c * (ay * ay + ny * ny), C22 = 2.f - c * (az * az + nz * nz);
+        const float C01 = -(c * (ax * ay + nx * ny)), C02 = -(c * (ax * az + nx * nz)), C12 = -(c * (ay * az + ny * nz));
+        const double D00 = C00, D11 = C11, D22 = C22, D01 = C01, D02 = C02, D12 = C12;
+        const double A00 = D11 * D22 - D12 * D12, A11 = D00 * D22 - D02 * D02, A22 = D00 * D11 - D01 * D01;
+        const double A01 = D02 * D12 - D01 * D22, A02 = D01 * D12 - D02 * D11, A12 = D01 * D02 - D00 * D12;
+        const double sdet = 1.0 / (D00 * A00 + (D01 * A01 + D02 * A02));
+        const float M00 = (float)(A00 * sdet), M11 = (float)(A11 * sdet), M22 = (float)(A22 * sdet);
+        const float M01 = (float)(A01 * sdet), M02 = (float)(A02 * sdet), M12 = (float)(A12 * sdet);
+        // e = p - q, g = M e
+        const float ex = px - qx, ey = py - qy, ez = pz - qz;
+        const float gx = M00 * ex + (M01 * ey + M02 * ez), gy = M01 * ex + (M11 * ey + M12 * ez), gz = M02 * ex + (M12 * ey + M22 * ez);
+        float w = 1.f;
+        if (ROBUST) w = loss_weight(L, sqrtf(fmaxf(0.f, ex * gx + (ey * gy + ez * gz))));
+        const double wd = w;
+        const auto term = [&](int k, float t) { put(k, ROBUST ? wd * (double)t : (double)t); };
+        // J = [-[p]x | I]: J_a . x = (p x x)_a for a < 3.  P_j = p x (row j of M) = the column j of J_w^T M; K_b = (P_0[b], P_1[b], P_2[b]) = M J_b
+        const float P00 = py * M02 - pz * M01, P01 = pz * M00 - px * M02, P02 = px * M01 - py * M00;
+        const float P10 = py * M12 - pz * M11, P11 = pz * M01 - px * M12, P12 = px * M11 - py * M01;
+        const float P20 = py * M22 - pz * M12, P21 = pz * M02 - px * M22, P22 = px * M12 - py * M02;
+        term(2, py * P20 - pz * P10);  term(3, py * P21 - pz * P11);  term(4, py * P22 - pz * P12);       // H00, H01, H02 = (p x K_b)_0
+        term(5, P00);  term(6, P10);  term(7, P20);                                                       // H03, H04, H05
+        term(8, pz * P01 - px * P21);  term(9, pz * P02 - px * P22);                                      // H11, H12 = (p x K_b)_1
+        term(10, P01); term(11, P11); term(12, P21);                                                      // H13, H14, H15
+        term(13, px * P12 - py * P02);                                                                    // H22 = (p x K_2)_2
+        term(14, P02); term(15, P12); term(16, P22);                                                      // H23, H24, H25
+        term(17, M00); term(18, M01); term(19, M02); term(20, M11); term(21, M12); term(22, M22);         // H33 .. H55
+        term(23, py * gz - pz * gy); term(24, pz * gx - px * gz); term(25, px * gy - py * gx);           // v0..2 = p x g
+        term(26, gx); term(27, gy); term(28, gz);                                                         // v3..5 = g
+        if (ROBUST) put(29, w > 0.f ? 1.0 : 0.0);
+        return;
+    }
     float q[3], J[6], r;
     corr_terms<MODE>(px, py, pz, idx, tgt, tgt_normals, q, J, r);
     float w = 1.f;
@@ -578,8 +646,8 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
 // this lane's sums += one accepted correspondence (p, target idx at squared distance best)
 template <int MODE, bool ROBUST = false>
 __device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
-                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L) {
-    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, [v](int k, double t) { v[k] += t; });
+                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L, GicpPt G = GicpPt{}) {
+    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, G, [v](int k, double t) { v[k] += t; });
 }
 
 // LDS of one accumulation block
@@ -678,7 +746,8 @@ __device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const 
 
 // One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
 // slabs in a fixed order, solves, and updates the state on the device.
-template <int MODE, int ACC_PPT, bool ROBUST = false>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
+// (Gicp: one IcpGicp for MODE 3, empty otherwise)
+template <int MODE, int ACC_PPT, bool ROBUST = false, class... Gicp>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
 __global__ __launch_bounds__(256)
 void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
@@ -686,8 +755,10 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       int nsplit, const float* __restrict__ pd2, const int* __restrict__ pchunk, int direct,
                       IcpState* st, float tau_accept, int fixed_iterations, IcpLoss loss,
                       double* slabs, unsigned* ticket,
-                      int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc) {
+                      int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc, Gicp... gicp_arg) {
+    static_assert((MODE == 3) == (sizeof...(Gicp) == 1), "GICP takes its arguments, the other modes none");
     if (st->done) return;
+    const IcpGicp gicp = gicp_of(gicp_arg...);
     const int iter0 = st->iter; const float rmse0 = st->rmse;
     double v[ACC_NV];
 #pragma unroll
@@ -707,7 +778,12 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
         if (out_d2) out_d2[i] = best;
         if (out_acc) out_acc[i] = acc ? 1 : 0;
         if (!acc) continue;
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss);
+        GicpPt G{};
+        if (MODE == 3) {
+            acc_rotate(T, gicp.src_normals[3 * i], gicp.src_normals[3 * i + 1], gicp.src_normals[3 * i + 2], G.ax, G.ay, G.az);
+            G.c = gicp.c;
+        }
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
@@ -752,12 +828,16 @@ void k_icp_nn_grid_multi(const float* __restrict__ src, const IcpInst* __restric
 
 // k_icp_accumulate for every instance: instance b's blocks write its slabs and take its ticket word tickets[b]; the last of them
 // folds, solves and updates st[b].  The points-per-thread count is uniform over a block (runtime loop, as the single kernel's).
-template <int MODE, bool ROBUST = false>
+// (Gicp: one IcpGicp for MODE 3, its source normals laid out like src; empty otherwise)
+template <int MODE, bool ROBUST = false, class... Gicp>
 __global__ __launch_bounds__(256)
 void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __restrict__ inst, const int* __restrict__ blk_inst,
                             const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
                             const float* __restrict__ pd2, const int* __restrict__ pidx,
-                            IcpState* st_all, float tau_accept, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* tickets) {
+                            IcpState* st_all, float tau_accept, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* tickets,
+                            Gicp... gicp_arg) {
+    static_assert((MODE == 3) == (sizeof...(Gicp) == 1), "GICP takes its arguments, the other modes none");
+    const IcpGicp gicp = gicp_of(gicp_arg...);
     const int b = blk_inst[blockIdx.x];
     IcpState* st = st_all + b;
     if (st->done) return;
@@ -780,7 +860,13 @@ void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __rest
         const float best = d < FLT_MAX ? d : FLT_MAX;
         const int idx = d < FLT_MAX ? pidx[in.src_off + i] : 0;
         if (!(best <= tau_accept)) continue;
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss);
+        GicpPt G{};
+        if (MODE == 3) {
+            const float* __restrict__ sn = gicp.src_normals + ((size_t)in.src_off + i) * 3;
+            acc_rotate(T, sn[0], sn[1], sn[2], G.ax, G.ay, G.az);
+            G.c = gicp.c;
+        }
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
@@ -1029,12 +1115,15 @@ constexpr long long SM_MAX_PAIRS_BATCH = 1ll << 20;     // ... per problem of a 
 // A grid of several workgroups runs one problem each (the batch's small instances against the shared model): problem b takes the
 // source points [src_off[b], src_off[b + 1]) of src0 and the states st_in[b] / st_out[b]; src_off == nullptr: one problem.
 // 1,024 lanes and room for 2,048 x 2,048 points.
-template <int MODE, bool REF, bool ROBUST = false>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS; ROBUST: loss
+// Gicp: one IcpGicp for MODE 3 (source normals laid out like src0), empty otherwise.
+template <int MODE, bool REF, bool ROBUST = false, class... Gicp>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS; ROBUST: loss
 __global__ __launch_bounds__(SM_THREADS)
 void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict__ src_off, const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
                  const IcpState* __restrict__ st_in0, float tau_accept, int max_iterations, int fixed_iterations, IcpLoss loss,
-                 IcpState* __restrict__ st_out0, IcpState* __restrict__ st_host) {
+                 IcpState* __restrict__ st_out0, IcpState* __restrict__ st_host, Gicp... gicp_arg) {
     static_assert(!(REF && ROBUST), "reference-order sums have no loss");
+    static_assert((MODE == 3) == (sizeof...(Gicp) == 1) && !(REF && MODE == 3), "GICP takes its arguments and tree sums, the other modes no arguments");
+    const IcpGicp gicp = gicp_of(gicp_arg...);
     const int prob = blockIdx.x;
     const float* __restrict__ src = src_off ? src0 + (size_t)src_off[prob] * 3 : src0;
     const int ns = src_off ? src_off[prob + 1] - src_off[prob] : ns0;
@@ -1162,7 +1251,13 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
                 float px, py, pz;
                 transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
                 const float best = sbest[i]; const int idx = sidx[i];
-                if (best <= tau_accept) acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, [&v](int k, double t) { v[k] = t; });
+                GicpPt G{};
+                if (MODE == 3 && best <= tau_accept) {
+                    const float* __restrict__ sn = gicp.src_normals + ((src_off ? (size_t)src_off[prob] : 0) + i) * 3;
+                    rotate_point(T, sn[0], sn[1], sn[2], G.ax, G.ay, G.az);
+                    G.c = gicp.c;
+                }
+                if (best <= tau_accept) acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, G, [&v](int k, double t) { v[k] = t; });
             }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -1305,11 +1400,18 @@ void state_result(const IcpState& h, tdv_icp_result& out) {
 IcpLoss ctx_loss(const tdv_ctx* ctx) { return IcpLoss{ctx->icp_loss, ctx->icp_loss_scale}; }
 bool ctx_robust(const tdv_ctx* ctx) { return ctx->icp_loss != TDV_ICP_LOSS_L2; }
 
-// k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points), point-to-plane where normals are given, with the
-// ctx's accumulation and loss (icp_loss_check: no loss with reference-order sums)
+// k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points), point-to-plane where normals are given, GICP where
+// gicp has source normals (gicp_check: tree sums), with the ctx's accumulation and loss (icp_loss_check: no loss with reference-order sums)
 void launch_icp_small(tdv_ctx* ctx, int n_prob, const float* d_src, int ns, const int* d_src_off, const float* d_tgt, const float* d_tgt_normals, int nt,
-                      int point_to_plane, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host) {
+                      int point_to_plane, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host,
+                      IcpGicp gicp) {
     const bool p2pl = point_to_plane && d_tgt_normals, ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE, robust = ctx_robust(ctx);
+    if (gicp.src_normals) {
+        const auto kernel = robust ? k_icp_small<3, false, true, IcpGicp> : k_icp_small<3, false, false, IcpGicp>;
+        kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations,
+                                                       ctx_loss(ctx), st_out, st_host, gicp);
+        return;
+    }
     const auto kernel = p2pl ? (ref ? k_icp_small<0, true> : robust ? k_icp_small<0, false, true> : k_icp_small<0, false>)
                              : (ref ? k_icp_small<1, true> : robust ? k_icp_small<1, false, true> : k_icp_small<1, false>);
     kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, p2pl ? d_tgt_normals : nullptr, nt, st_in, tau, max_iterations, fixed_iterations,
@@ -1369,8 +1471,9 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
-                tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid) {
+                tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid, IcpGicp gicp) {
     if (!ctx || !d_src || !d_tgt || !T0 || !out || ns < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
+    if (gicp.src_normals && (!d_tgt_normals || ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE)) return TDV_ERR_BAD_ARG;   // (gicp_check's)
     TDV_HIP(ctx, hipSetDevice(ctx->device));
     result_defaults(T0, *out);
     if (max_iterations == 0) return TDV_OK;
@@ -1397,7 +1500,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
         TDV_HIP(ctx, hipMemcpyAsync(d_st, h, sizeof(IcpState), hipMemcpyHostToDevice, s));
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
+            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res, gicp);
         }
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipStreamSynchronize(s));
@@ -1453,6 +1556,15 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 k_icp_rows<1><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nullptr, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
                 k_icp_fold_ref<1><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
             }
+        } else if (gicp.src_normals) {
+#define TDV_GACC1(PP) do { if (robust) TDV_GACC2(PP, true); else TDV_GACC2(PP, false); } while (0)
+#define TDV_GACC2(PP, RR) k_icp_accumulate<3, PP, RR, IcpGicp><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, \
+                              p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr, gicp)
+#ifdef TDV_STUDY
+            if (p.acc_ppt == 8) TDV_GACC1(8); else if (p.acc_ppt == 4) TDV_GACC1(4); else if (p.acc_ppt == 2) TDV_GACC1(2); else TDV_GACC1(1);
+#else
+            if (p.acc_ppt == 4) TDV_GACC1(4); else TDV_GACC1(1);
+#endif
         } else if (p2pl) {
 #define TDV_ACC2(MM, PP, RR, NRM) k_icp_accumulate<MM, PP, RR><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, NRM, b.tx, b.ty, b.tz, \
                                p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr)
@@ -1481,7 +1593,7 @@ bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt) {
 // of d_src (each at most SM_MAX_N, as nt), start pose T0s[b] (host, column-major).  Results as icp_run_dev's, bit for bit (the same
 // kernel).  One upload, one launch, one download.
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out) {
+                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp) {
     if (!ctx || !d_src || !d_src_off || !d_tgt || !T0s || !out || n_prob < 0 || nt <= 0 || nt > SM_MAX_N || max_iterations < 0) return TDV_ERR_BAD_ARG;
     if (n_prob == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
@@ -1497,7 +1609,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
         // (A quarter-size shape - 256 lanes, more problems resident at once - was measured against this one on C5's 1,024 instances in
         // round 3: 1.59 ms against 1.33 ms.  The pass lasts as long as its slowest problem and a lone workgroup iterates faster with
         // 16 waves; the variant is gone, profiles/r3/history keeps the numbers.)
-        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
+        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr, gicp);
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipMemcpyAsync(h, d_st + n_prob, (size_t)n_prob * sizeof(IcpState), hipMemcpyDeviceToHost, s));
     }
@@ -1514,7 +1626,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
 // states per burst.  Otherwise: small problems in one k_icp_small launch (icp_small_batch_dev), else icp_run_dev per instance with
 // the shared grid or Morton order.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
-                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out) {
+                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out, IcpGicp gicp) {
     for (int b = 0; b < n; ++b) result_defaults(T0s + 16 * (size_t)b, out[b]);
     if (n == 0) return TDV_OK;
     int ns_max = 0, span = 0;
@@ -1535,7 +1647,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         int* d_off;
         TDV_TRY(ws_alloc(ctx, (size_t)n + 1, &d_off));
         TDV_HIP(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));   // (off outlives the call's sync)
-        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out);
+        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out, gicp);
     }
     // the target's hash grid at this threshold, once for the call (icp_run_dev uses a grid under AUTO or GRID)
     CellGrid cg{}; bool have_grid = false;
@@ -1553,8 +1665,10 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         }
         for (int b = 0; b < n; ++b) {
             const WsMark mark = ws_mark(ctx);
+            IcpGicp g = gicp;
+            if (g.src_normals) g.src_normals += (size_t)h_start[b] * 3;
             TDV_TRY(icp_run_dev(ctx, d_src + (size_t)h_start[b] * 3, h_count[b], d_tgt, d_tgt_normals, nt, T0s + 16 * (size_t)b, thr, max_iterations,
-                                point_to_plane, fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr));
+                                point_to_plane, fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr, g));
             ws_rewind(ctx, mark);
         }
         return TDV_OK;
@@ -1610,6 +1724,11 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
             k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);
         }
+        if (gicp.src_normals) {
+            const auto acc = robust ? k_icp_accumulate_multi<3, true, IcpGicp> : k_icp_accumulate_multi<3, false, IcpGicp>;
+            acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets, gicp);
+            return;
+        }
         const auto acc = p2pl ? (robust ? k_icp_accumulate_multi<0, true> : k_icp_accumulate_multi<0>) : (robust ? k_icp_accumulate_multi<1, true> : k_icp_accumulate_multi<1>);
         acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, p2pl ? d_tgt_normals : nullptr, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets);
     }));
@@ -1621,6 +1740,16 @@ int icp_loss_check(tdv_ctx* ctx) {
     if (ctx->icp_loss != TDV_ICP_LOSS_L2 && ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
         snprintf(ctx->err, sizeof(ctx->err), "icp: a robust loss (tdv_ctx_set_icp_loss) cannot run with reference-order accumulation, whose float "
                  "sums are the reference's and have no loss; set TDV_ICP_LOSS_L2 or TDV_ICP_ACCUMULATE_TREE");
+        return TDV_ERR_BAD_ARG;
+    }
+    return TDV_OK;
+}
+
+int gicp_check(tdv_ctx* ctx, const float* src_normals, const float* tgt_normals, float epsilon) {
+    if (!src_normals || !tgt_normals || !std::isfinite(epsilon) || !(epsilon > 0.f && epsilon <= 1.f)) return TDV_ERR_BAD_ARG;
+    if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
+        snprintf(ctx->err, sizeof(ctx->err), "gicp: reference-order accumulation reproduces the reference's float sums, and the reference has no "
+                 "generalized ICP; set TDV_ICP_ACCUMULATE_TREE");
         return TDV_ERR_BAD_ARG;
     }
     return TDV_OK;

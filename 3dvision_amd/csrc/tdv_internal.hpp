@@ -138,6 +138,9 @@ struct ScopedTimer {
 struct IcpOutputs {  // optional per-source outputs of one correspondence pass (device pointers)
     int* corr = nullptr; float* d2 = nullptr; uint8_t* accepted = nullptr;
 };
+// Generalized ICP (plane-to-plane, include/tdv_hip.h: tdv_gicp): the source normals, laid out like the source points (device), and
+// c = 1 - epsilon in f32.  src_normals == nullptr: not GICP - the ICP objective the other arguments select.
+struct IcpGicp { const float* src_normals; float c; };
 struct SortedCloud;
 // Hash grid over a target cloud for ICP's correspondence search at one acceptance threshold (icp.hip): cells of 2.2 x
 // the threshold, open-addressing table of (32-bit cell tag, list head), the points of a cell as a linked list of (x, y, z, next) nodes indexed like the cloud.  Lives
@@ -149,20 +152,24 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 // (cell_grid_build, for this thr), built once and reused across calls
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
-                tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr);
+                tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr, IcpGicp gicp = IcpGicp{nullptr, 0.f});
 // many small problems against one target in one launch (icp.hip: k_icp_small), when icp_small_batch_fits(ctx, largest problem, nt)
 bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt);
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out);
+                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp = IcpGicp{nullptr, 0.f});
 // icp_run_dev for n instances against one target (icp.hip): instance b = h_count[b] points from point h_start[b] of d_src (host arrays), start
 // pose T0s + 16 b; per instance icp_run_dev's result bit for bit.  Arguments are not checked.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
-                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out);
+                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out,
+                      IcpGicp gicp = IcpGicp{nullptr, 0.f});
 int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                             const float* T, float thr, IcpOutputs outs, int* n_corr);
 // TDV_ERR_BAD_ARG (reason in ctx->err) when the ctx's ICP loss cannot run with its accumulation mode (a robust loss with
 // reference-order sums); the ICP entry points ask before they enqueue or write anything
 int icp_loss_check(tdv_ctx* ctx);
+// TDV_ERR_BAD_ARG (reason in ctx->err) for GICP's own arguments: a NULL normal array, epsilon not finite or outside (0, 1], or a ctx
+// in reference-order accumulation (the reference has no GICP)
+int gicp_check(tdv_ctx* ctx, const float* src_normals, const float* tgt_normals, float epsilon);
 int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel, int max_iterations, float confidence, uint32_t seed,

@@ -318,6 +318,43 @@ int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets
                       const float* d_tgt, const float* d_tgt_normals /* may be NULL */, int nt, const float* h_T0,
                       float distance_threshold, int max_iterations, int point_to_plane, int fixed_iterations,
                       tdv_icp_result* out);
+/* Generalized ICP, plane-to-plane (Segal et al. 2009, plane-regularised covariances): both surfaces are modelled as planes with a
+ * normal variance epsilon, C_x = I - (1 - epsilon) n n^T per point (eigenvalues 1, 1, epsilon about the normal).  tdv_gicp /
+ * tdv_gicp_dev / tdv_gicp_batch_dev are tdv_icp / tdv_icp_dev / tdv_icp_batch_dev (same search on every path, same acceptance
+ * d2 <= thr^2, same batch paths and bit-for-bit batch = single guarantee, same tdv_ctx_last_icp_search) with the source normals
+ * (laid out like the source points) and these per-correspondence terms in place of point-to-plane's.  f32 without contraction except
+ * where stated;
+ * p = the transformed source point (as ICP forms it), q / nt the target point and normal, ns the source normal, R the pose's 3x3,
+ * c = 1 - epsilon (f32):
+ *   a    = R ns, each row R_r0 * ns_x + (R_r1 * ns_y + R_r2 * ns_z)              (the transform's row form, no translation)
+ *   C_ii = 2 - c * (a_i * a_i + nt_i * nt_i)                                     (C = 2 I - c (a a^T + nt nt^T) = C_t + R C_s R^T)
+ *   C_ij = -(c * (a_i * a_j + nt_i * nt_j))                  i < j, C symmetric
+ *   in f64 from the f32 C_ij (C's condition number is ~1 / epsilon; the products of two f32 are exact in f64):
+ *   A00 = C11 * C22 - C12 * C12   A11 = C00 * C22 - C02 * C02   A22 = C00 * C11 - C01 * C01     (cofactors, A symmetric)
+ *   A01 = C02 * C12 - C01 * C22   A02 = C01 * C12 - C02 * C11   A12 = C01 * C02 - C00 * C12
+ *   s    = 1 / (C00 * A00 + (C01 * A01 + C02 * A02)),  M_ij = (float)(A_ij * s)           (M = C^-1, symmetric; f32 from here on)
+ *   e    = p - q per component;  g_i = M_i0 * e_0 + (M_i1 * e_1 + M_i2 * e_2)          (g = M e)
+ *   p x v = (p_y * v_2 - p_z * v_1,  p_z * v_0 - p_x * v_2,  p_x * v_1 - p_y * v_0)
+ *   P_j  = p x (M_j0, M_j1, M_j2) for j = 0, 1, 2;  K_b = (P_0[b], P_1[b], P_2[b])
+ * With J = [-[p]x | I] (d p / d(omega, t)), H_ab = J_a . M J_b (a <= b) and v_a = J_a . g are:
+ *   H_ab = (p x K_b)[a] for a <= b < 3;  H_a,3+j = P_j[a];  H_3+i,3+j = M_ij;  v_a = (p x g)[a] for a < 3;  v_3+j = g_j
+ * each widened to f64 and summed in point-to-plane's slots and tree; the step is point-to-plane's (x = ldlt6_solve(H, -v), rotation
+ * euler_xyz(x0, x1, x2), translation x3..5).  n_corr, fitness, rmse = sqrt(sum d2 / n_corr) (Euclidean d2), the |delta rmse| < 1e-6
+ * rule, the n_corr < 3 break and fixed_iterations are ICP's: the results compare directly with ICP's.
+ * Normals are used as given: unit or zero length (a zero normal makes that cloud's covariance I).  An epsilon below ~3e-8 rounds c to
+ * 1 and can leave C singular.  The ctx's loss (tdv_ctx_set_icp_loss) weighs each correspondence by its Mahalanobis residual
+ * e_m = sqrtf(fmaxf(0, e_0 * g_0 + (e_1 * g_1 + e_2 * g_2))): (double)w * term for the 27 terms, n_eff last, as for point-to-plane.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written to out: either normal array NULL, epsilon not finite or outside (0, 1], a ctx
+ * in TDV_ICP_ACCUMULATE_REFERENCE mode (the reference has no GICP; the reason is in tdv_last_error), or what the ICP entry point
+ * checks.  0 points, nt == 0 or max_iterations == 0 return what ICP returns. */
+int tdv_gicp(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
+             const float* T0, float distance_threshold, int max_iterations, float epsilon, tdv_icp_result* out);
+int tdv_gicp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals,
+                 int nt, const float* T0, float distance_threshold, int max_iterations, float epsilon, int fixed_iterations,
+                 tdv_icp_result* out);
+int tdv_gicp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances,
+                       const float* d_tgt, const float* d_tgt_normals, int nt, const float* h_T0, float distance_threshold,
+                       int max_iterations, float epsilon, int fixed_iterations, tdv_icp_result* out);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
