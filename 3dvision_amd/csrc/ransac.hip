@@ -48,10 +48,10 @@ __global__ void k_gather_pq(const float* __restrict__ src, const float* __restri
             a = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], tgt[3 * c]);
             b = make_float4(tgt[3 * c + 1], tgt[3 * c + 2], 0.f, 0.f);
             am = fmaxf(fabsf(a.x), fmaxf(fabsf(a.y), fabsf(a.z)));
-            if (!(am <= FLT_MAX)) am = INFINITY;      // NaN or inf
-            // a NaN target coordinate makes d2 NaN, whose sign bit the fast pass would read as "inlier": such a cloud is
-            // scored with the reference arithmetic throughout (an infinite one gives d2 = +inf in both and is harmless)
-            if (a.w != a.w || b.x != b.x || b.y != b.y) am = INFINITY;
+            if (!(am <= FLT_MAX)) am = INFINITY;      // inf (fmaxf drops a NaN: checked below)
+            // a NaN coordinate - source or target - makes d2 NaN, whose sign bit the fast pass would read as "inlier" where it is
+            // set: such a cloud is scored with the reference arithmetic throughout (an infinite target gives d2 = +inf in both)
+            if (a.x != a.x || a.y != a.y || a.z != a.z || a.w != a.w || b.x != b.x || b.y != b.y) am = INFINITY;
         } else {
             a = make_float4(0.f, 0.f, 0.f, INFINITY);
             b = make_float4(INFINITY, INFINITY, 0.f, 0.f);
@@ -71,6 +71,20 @@ __global__ void k_gather_pq(const float* __restrict__ src, const float* __restri
 }
 
 __device__ __forceinline__ float tau_mid_default(float sqrt_tau) { return sqrt_tau * sqrt_tau; }
+
+// A of the band (RansacBand below) for the hypothesis o[12] (column-major R, t): max over rows of (|r0| + |r1| + |r2|) P + |t|.
+// A row that is NaN makes A NaN (fmaxf would drop it).  A NaN hypothesis - sampled from a pair with an infinite target or a NaN
+// source - then gets no band: with a small one, the fast pass would read the sign bits of its NaN d2_fma as inliers wherever they
+// are set.  Without a band the reference arithmetic scores it: no inliers.
+__device__ __forceinline__ float ransac_band_reach(const float* o, float P) {
+    float A = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float a = (fabsf(o[c]) + fabsf(o[3 + c]) + fabsf(o[6 + c])) * P + fabsf(o[9 + c]);
+        A = (a > A || a != a) ? a : A;
+    }
+    return A;
+}
 
 // hyp layout: SoA [14][h_pad]: r00 r10 r20 r01 r11 r21 r02 r12 r22 t0 t1 t2 (column-major R).
 // Invalid (skipped) iterations get NaN so that no comparison is ever true -> 0 inliers.
@@ -124,10 +138,7 @@ __device__ __forceinline__ void ransac_hypothesis_lane(const float* __restrict__
     // twice; its count is garbage and the host never reads it)
     float mid = tau_mid_default(sqrt_tau), half = valid ? __builtin_nanf("") : 0.f;
     if (valid) {
-        const float P = __uint_as_float(*pmax);
-        float A = 0.f;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) A = fmaxf(A, (fabsf(o[c]) + fabsf(o[3 + c]) + fabsf(o[6 + c])) * P + fabsf(o[9 + c]));
+        const float A = ransac_band_reach(o, __uint_as_float(*pmax));
         const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
         if (E < 0.25f * sqrt_tau) {
             const float lo = sqrt_tau - E, hi = sqrt_tau + E;
@@ -618,10 +629,7 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __rest
 #pragma unroll
     for (int e = 0; e < 12; ++e) r[e] = valid ? hyp[(size_t)e * h_pad + h] : 0.f;
     // the band's E (k_ransac_hypotheses), from the same f32 operations
-    const float P = __uint_as_float(*pmax);
-    float A = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) A = fmaxf(A, (fabsf(r[c]) + fabsf(r[3 + c]) + fabsf(r[6 + c])) * P + fabsf(r[9 + c]));
+    const float A = ransac_band_reach(r, __uint_as_float(*pmax));
     const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
     const bool bounded = E < 0.25f * sqrt_tau;                    // false for NaN (non-finite data or hypothesis)
     const float sb = sqrt_tau + 3.f * E;
@@ -1281,7 +1289,7 @@ __global__ void k_rb_gather_pq(const float* __restrict__ src, const float* __res
         Bq = make_float4(tgt[3 * c + 1], tgt[3 * c + 2], 0.f, 0.f);
         float am = fmaxf(fabsf(A.x), fmaxf(fabsf(A.y), fabsf(A.z)));
         if (!(am <= FLT_MAX)) am = INFINITY;
-        if (A.w != A.w || Bq.x != Bq.x || Bq.y != Bq.y) am = INFINITY;      // as k_gather_pq
+        if (A.x != A.x || A.y != A.y || A.z != A.z || A.w != A.w || Bq.x != Bq.x || Bq.y != Bq.y) am = INFINITY;      // as k_gather_pq
         if (am > 0.f) atomicMax(&pmax[a], __float_as_uint(am));
     } else {
         A = make_float4(0.f, 0.f, 0.f, INFINITY);

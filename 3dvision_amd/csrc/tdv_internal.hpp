@@ -3,6 +3,7 @@
 // per-kernel HIP-event timers.  Steady state performs no hipMalloc.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <climits>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -78,6 +79,11 @@ inline int set_err(tdv_ctx* ctx, hipError_t e, const char* what, int line) {
 #define TDV_CHECK_LAUNCH(ctx) TDV_HIP((ctx), hipGetLastError())
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+// float -> int as x86's cvttss2si converts (include/tdv_hip.h, tdv_voxel_downsample): truncation inside int range, INT_MIN for NaN
+// and for everything outside it.  The reference's static_cast<int>(std::floor(x * inv)) is undefined in C++ there and compiles to
+// cvttss2si on x86; the device's own conversion (v_cvt_i32_f32) gives 0 for NaN and saturates.  Every voxel key goes through this.
+__host__ __device__ __forceinline__ int cvt_i32_x86(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN; }
 
 // Study build (-DTDV_STUDY -> lib3dvision_hip_study.so, used by tools/studies/ and by the tests marked `study`): keeps the A/B
 // variants that LOST their measurement (the matrix-core scoring pass, the merged scoring dispatch, round 1's key-ordered descriptor

@@ -2,7 +2,7 @@
 //
 // Replaces Registration::voxelDownsample (/root/reference/src/registration.cpp:29-60; key/hash
 // :15-27), which has no GPU entry point in the reference (src/pipeline.cpp:92 calls the CPU static).
-// Semantics kept: key = (int)floor(p * (1/voxel)) per axis; per-voxel mean = f32 sum of the member
+// Semantics kept: key = (int)floor(p * (1/voxel)) per axis, converted as x86 does (cvt_i32_x86: NaN and out of range -> INT_MIN); per-voxel mean = f32 sum of the member
 // points IN ASCENDING INPUT INDEX divided by float(count); colours likewise; normals dropped.
 //
 // The reference groups with std::unordered_map and emits voxels in that container's iteration
@@ -45,9 +45,9 @@ __global__ void k_voxel_records(const float* __restrict__ xyz, int n, int n_pow2
     if (i >= n_pow2) return;
     uint4 r;
     if (i < n) {
-        r.x = (unsigned)(int)floorf(xyz[3 * i] * inv);
-        r.y = (unsigned)(int)floorf(xyz[3 * i + 1] * inv);
-        r.z = (unsigned)(int)floorf(xyz[3 * i + 2] * inv);
+        r.x = (unsigned)cvt_i32_x86(floorf(xyz[3 * i] * inv));
+        r.y = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 1] * inv));
+        r.z = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 2] * inv));
         r.w = (unsigned)i;
     } else {
         r = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);  // padding sorts last
@@ -192,9 +192,9 @@ __global__ void k_voxel_hist(const float* __restrict__ xyz, int n, float inv, un
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     uint4 r;
-    r.x = (unsigned)(int)floorf(xyz[3 * i] * inv);
-    r.y = (unsigned)(int)floorf(xyz[3 * i + 1] * inv);
-    r.z = (unsigned)(int)floorf(xyz[3 * i + 2] * inv);
+    r.x = (unsigned)cvt_i32_x86(floorf(xyz[3 * i] * inv));
+    r.y = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 1] * inv));
+    r.z = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 2] * inv));
     r.w = (unsigned)i;
     rec_in[i] = r;
     atomicAdd(&hist[voxel_hash(r.x, r.y, r.z) & mask], 1);
@@ -290,8 +290,8 @@ __global__ void k_voxel_leader_list(const int* __restrict__ leader, const int* _
                                     int n, int4* __restrict__ leaders) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n && leader[i])
-        leaders[rank[i]] = make_int4((int)floorf(xyz[3 * (size_t)i] * inv), (int)floorf(xyz[3 * (size_t)i + 1] * inv),
-                                     (int)floorf(xyz[3 * (size_t)i + 2] * inv), i);
+        leaders[rank[i]] = make_int4(cvt_i32_x86(floorf(xyz[3 * (size_t)i] * inv)), cvt_i32_x86(floorf(xyz[3 * (size_t)i + 1] * inv)),
+                                     cvt_i32_x86(floorf(xyz[3 * (size_t)i + 2] * inv)), i);
 }
 
 // exclusive scan of n ints in TWO launches: per-block (4096 items: 1024 threads x 4) reduce whose LAST workgroup (atomic
@@ -441,7 +441,7 @@ __device__ __forceinline__ int vh_segment(const int* __restrict__ seg_off, int n
     return lo;
 }
 __device__ __forceinline__ void vh_cell(const float* __restrict__ xyz, size_t g, float inv, int& cx, int& cy, int& cz) {
-    cx = (int)floorf(xyz[3 * g] * inv); cy = (int)floorf(xyz[3 * g + 1] * inv); cz = (int)floorf(xyz[3 * g + 2] * inv);   // registration.cpp:33-36
+    cx = cvt_i32_x86(floorf(xyz[3 * g] * inv)); cy = cvt_i32_x86(floorf(xyz[3 * g + 1] * inv)); cz = cvt_i32_x86(floorf(xyz[3 * g + 2] * inv));   // registration.cpp:33-36
 }
 
 __global__ __launch_bounds__(256)
@@ -581,9 +581,9 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
     __syncthreads();
     // pass 1: pixel and tag of every loaded point (thread t holds points t, t + 1024, ...: the owned ones among them are its own in pass 3)
     unsigned pvu[VS_PER], pk[VS_PER];                                     // v << 16 | u; the cell relative to the first loaded point's, biased to the middle of its bit field
-    int ox, oy, oz;
-    vh_cell(xyz, (size_t)l0, inv, ox, oy, oz);
-    ox -= 1 << (VS_KX - 1); oy -= 1 << (VS_KY - 1); oz -= 1 << (VS_KZ - 1);
+    int cx0, cy0, cz0;
+    vh_cell(xyz, (size_t)l0, inv, cx0, cy0, cz0);
+    const long long ox = (long long)cx0 - (1 << (VS_KX - 1)), oy = (long long)cy0 - (1 << (VS_KY - 1)), oz = (long long)cz0 - (1 << (VS_KZ - 1));   // (a poisoned first point has cell INT_MIN)
     int umin = INT_MAX, umax = INT_MIN;
     float zmin = INFINITY, amax = 0.f, bmax = 0.f; bool bad = false;
 #pragma unroll
@@ -1334,6 +1334,7 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
         if (hashed) k_voxel_compact<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, n, mean_xyz, mean_rgb, capacity, d_out_xyz, d_out_rgb);
         else k_voxel_means<<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, capacity, d_out_xyz, d_out_rgb);
         TDV_CHECK_LAUNCH(ctx);
+        TDV_HIP(ctx, hipStreamSynchronize(s));      // the device entry points return with their results in place (include/tdv_hip.h)
         return TDV_OK;
     }
     // reference order: replay the container on the host to get its iteration order

@@ -224,7 +224,11 @@ int tdv_depth_to_cloud_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint
  * order: TDV_VOXEL_ORDER_FIRST = voxels ordered by their smallest input index (deterministic,
  * computed on the GPU); TDV_VOXEL_ORDER_REFERENCE = libstdc++ std::unordered_map iteration order
  * of the reference (the slot order is replayed on the host with the reference's hash,
- * registration.cpp:20-27; the means are still computed on the GPU). */
+ * registration.cpp:20-27; the means are still computed on the GPU).
+ * Key of a point: static_cast<int>(std::floor(x * (1 / voxel_size))) per axis, as the reference - undefined in C++ for NaN and
+ * for values outside int range.  The rule here is what that cast does on x86 (cvttss2si): every such coordinate gets INT_MIN.
+ * So NaN, +-inf and far-out points (|x / voxel_size| >= 2^31) share a cell with each other and with x / voxel_size in
+ * [-2^31, -2^31 + 1); their voxel's mean is NaN or infinite as the f32 sum makes it. */
 #define TDV_VOXEL_ORDER_FIRST 0
 #define TDV_VOXEL_ORDER_REFERENCE 1
 int tdv_voxel_downsample(tdv_ctx* ctx, const float* xyz, const float* rgb, int n, float voxel_size, int order,

@@ -35,6 +35,11 @@ int main() {
     if (n <= 0) { n = 300; for (int i = 0; i < n * 3; ++i) xyz[i] = frand(); }
     std::vector<float> vx(n * 3), vc(n * 3); std::vector<int> first(n);
     int m = orc_voxel_downsample(xyz.data(), rgb.data(), n, 0.02f, vx.data(), vc.data(), first.data(), n);
+    // poisoned coordinates: NaN, +-inf and cells outside int range (the x86 rule: all of them key INT_MIN)
+    const float poison[6] = {NAN, INFINITY, -INFINITY, 3e7f, -3e7f, 1e19f};
+    std::vector<float> pz(xyz.begin(), xyz.begin() + n * 3);
+    for (int i = 0; i < 6 && i < n; ++i) pz[3 * i + i % 3] = poison[i];
+    m += orc_voxel_downsample(pz.data(), rgb.data(), n, 0.01f, vx.data(), vc.data(), first.data(), n);
     const int ns = 400, nt = 300;
     std::vector<float> src(ns * 3), tgt(nt * 3), nrm(nt * 3), fs(ns * 33), ft(nt * 33), desc(nt * 33);
     for (auto& v : src) v = frand(); for (auto& v : tgt) v = frand();

@@ -27,6 +27,7 @@
 // Build: g++ -O3 -DNDEBUG -ffp-contract=off -fPIC -shared (see oracle/Makefile).
 #include "small_linalg.hpp"
 
+#include <climits>
 #include <cstdint>
 #include <cstring>
 #include <cstdio>
@@ -320,14 +321,20 @@ int orc_demo_model(float* xyz, float* normals, int capacity) {
 // registration.cpp:29-60.  Output order = libstdc++ unordered_map iteration order.
 // out_first_index (optional) receives, per output voxel, the smallest input index in it
 // (lets a test match voxels between differently-ordered outputs).  Returns the voxel count.
+// The key is static_cast<int>(std::floor(x * inv)) in the reference, undefined in C++ for NaN and for values outside int
+// range.  x86 compiles it to cvttss2si, which gives INT_MIN for all of those: that is the rule (include/tdv_hip.h), restated
+// here without the undefined cast.  Same results on x86.
+static inline int cvt_i32_x86(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? static_cast<int>(f) : INT_MIN; }
+void orc_voxel_key(const float* v, int n, int* out) { for (int i = 0; i < n; ++i) out[i] = cvt_i32_x86(std::floor(v[i])); }
+
 int orc_voxel_downsample(const float* xyz, const float* rgb, int n, float voxel_size,
                          float* out_xyz, float* out_rgb, int* out_first_index, int capacity) {
     std::unordered_map<VoxelKey, std::vector<size_t>, VoxelKeyHash> grid;
     float inv = 1.0f / voxel_size;
     for (int i = 0; i < n; ++i) {
-        VoxelKey key{static_cast<int>(std::floor(xyz[3 * i] * inv)),
-                     static_cast<int>(std::floor(xyz[3 * i + 1] * inv)),
-                     static_cast<int>(std::floor(xyz[3 * i + 2] * inv))};
+        VoxelKey key{cvt_i32_x86(std::floor(xyz[3 * i] * inv)),
+                     cvt_i32_x86(std::floor(xyz[3 * i + 1] * inv)),
+                     cvt_i32_x86(std::floor(xyz[3 * i + 2] * inv))};
         grid[key].push_back(i);
     }
     int m = 0;

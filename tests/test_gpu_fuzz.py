@@ -36,15 +36,34 @@ def _make(kind, n, rng):
     elif kind == "mixed":
         a = rng.random((n // 2, 3)); b = np.full((n - n // 2, 3), 0.5) + rng.normal(0, 1e-6, (n - n // 2, 3))
         p = np.concatenate([a, b], 0)[rng.permutation(n)]
+    elif kind in ("nan_rows", "inf_rows", "huge"):   # a uniform cloud with poisoned rows: row 0, the last row, rows around 256, a few at random
+        p = rng.random((n, 3))
+        rows = np.unique(np.concatenate([[0, n - 1], [r for r in (255, 256) if r < n], rng.integers(0, n, max(1, n // 100))]).astype(np.int64))
+        val = {"nan_rows": np.nan, "inf_rows": np.inf, "huge": 1e19}[kind]
+        cols = rng.integers(0, 4, len(rows))               # 3: the whole row
+        for r, c in zip(rows, cols):
+            if c == 3:
+                p[r] = val
+            else:
+                p[r, c] = val if r % 2 == 0 else -val
     else:
         raise ValueError(kind)
     return np.ascontiguousarray(p, np.float32)
 
 
-KINDS = ["uniform", "flat", "line", "grid", "dups", "clusters", "offset", "tiny", "mixed", "identical"]
+def _extent(p):
+    """Largest axis extent of the clean rows: the poisoned kinds keep radii and thresholds at the clean cloud's scale."""
+    q = p[(np.abs(p) < 1e18).all(1)]
+    return float(np.ptp(q, axis=0).max()) if len(q) else 0.0
 
 
-@pytest.mark.parametrize("kind", KINDS)
+KINDS = ["uniform", "flat", "line", "grid", "dups", "clusters", "offset", "tiny", "mixed", "identical", "nan_rows", "inf_rows", "huge"]
+
+
+# NaN rows: every query's distances hold NaN, and the reference's std::partial_sort over (d2, index) pairs has no strict weak order
+# to follow - its lists are then an artefact of libstdc++'s algorithm, not a defined answer.  Infinite rows: only their own queries
+# see NaN (inf - inf); the lists and normals of the finite queries (distances finite or +inf) are compared.
+@pytest.mark.parametrize("kind", [k for k in KINDS if k != "nan_rows"])
 def test_knn_lists_fuzz(ctx, orc, kind):
     rng = np.random.default_rng(zlib.crc32(kind.encode()))
     for trial in range(3):
@@ -53,9 +72,17 @@ def test_knn_lists_fuzz(ctx, orc, kind):
         pts = _make(kind, n, rng)
         ref_n, ref_knn = orc.estimate_normals(pts, k, want_knn=True)
         got_n, got_knn = ctx.estimate_normals(pts, k, want_knn=True)
-        assert np.array_equal(got_knn, ref_knn), (kind, n, k)
-        # normals come from an eigen-solver on the same sums: identical inputs -> identical bits (NaN rows compare as bytes)
-        assert got_n.tobytes() == ref_n.tobytes(), (kind, n, k)
+        if kind != "inf_rows":
+            assert np.array_equal(got_knn, ref_knn), (kind, n, k)
+            # normals come from an eigen-solver on the same sums: identical inputs -> identical bits (NaN rows compare as bytes)
+            assert got_n.tobytes() == ref_n.tobytes(), (kind, n, k)
+            continue
+        q = np.isfinite(pts).all(1)
+        assert (~q).any() and q.any()
+        assert np.array_equal(got_knn[q], ref_knn[q]), (kind, n, k)
+        gn, rn = got_n[q], ref_n[q]           # (NaN positions, then the other bytes: NaN payloads differ between x86 and the GPU)
+        assert np.array_equal(np.isnan(gn), np.isnan(rn)), (kind, n, k)
+        assert gn[~np.isnan(gn)].tobytes() == rn[~np.isnan(rn)].tobytes(), (kind, n, k)
 
 
 @pytest.mark.parametrize("kind", KINDS)
@@ -64,7 +91,7 @@ def test_radius_lists_fuzz(ctx, orc, kind):
     for trial in range(3):
         n = int(rng.integers(40, 2200))
         pts = _make(kind, n, rng)
-        ext = float(np.ptp(pts, axis=0).max()) or 1.0
+        ext = _extent(pts) or 1.0
         radius = float(ext * rng.choice([0.01, 0.05, 0.2, 2.0]))   # from a handful of neighbours to everything (cap 100)
         nrm = np.zeros_like(pts); nrm[:, 2] = 1.0
         ref = orc.compute_fpfh(pts, nrm, radius, want_neighbors=True)
@@ -82,7 +109,7 @@ def test_icp_pruned_correspondences_fuzz(ctx, orc, synth, kind):
             ns, nt = int(rng.integers(1, 3000)), int(rng.integers(1, 3000))
             tgt = _make(kind, nt, rng)
             src = _make(kind, ns, rng)
-            ext = float(np.ptp(tgt, axis=0).max()) or 1.0
+            ext = _extent(tgt) or 1.0
             thr = float(ext * rng.choice([1e-3, 0.02, 0.3, 5.0]))
             T = synth.make_transform(rng.normal(size=3), float(rng.uniform(0, 10)), tuple(rng.normal(0, 0.01 * ext, 3)))
             ref = orc.icp_correspondences(src, tgt, None, T, thr, point_to_plane=False)

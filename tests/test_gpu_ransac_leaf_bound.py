@@ -126,8 +126,7 @@ def test_leaf_bound_matches_on_the_threshold_shell(ctx, orc, seed):
 @pytest.mark.parametrize("kind", ["nan_target", "inf_source", "ninf_source"])
 def test_leaf_bound_non_finite_coordinates(ctx, orc, synth, kind):
     """A NaN anywhere or an infinite source coordinate turns the band, and with it the bound, off.  Equal to the oracle.
-    (Infinite target and NaN source coordinates are not covered: on such clouds the fast scoring pass can fail its rmse
-    cross-check - seen for infinite targets with and without the bound and the bail-out.)"""
+    (Infinite target and NaN source coordinates: tests/test_gpu_nonfinite.py.)"""
     src, tgt, corr, voxel = _scene(ctx, synth, 20000, 0.5, 11)
     rng = np.random.default_rng(5)
     rows = rng.choice(len(src), 40, replace=False)
