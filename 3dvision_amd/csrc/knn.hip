@@ -515,9 +515,11 @@ void k_spfh(const float* __restrict__ xyz, const float* __restrict__ nrm, int n,
                 float wn = wx * njx + (wy * njy + wz * njz);
                 float un = ux * njx + (uy * njy + uz * njz);
                 float theta = lm::atan2f_glibc(wn, un);      // glibc's atan2f, the function registration.cpp:154 calls (libm_f32.hpp)
-                bin_a = min(max((int)((alpha + 1.0f) * 5.5f), 0), 10);
-                bin_p = min(max((int)((phi + 1.0f) * 5.5f), 0), 10);
-                bin_t = min(max((int)(((double)theta / 3.14159265358979323846 + (double)1.0f) * (double)5.5f), 0), 10);
+                // the x86 rule (include/tdv_hip.h, tdv_compute_fpfh): NaN and values outside int range are INT_MIN, bin 0
+                // (v_cvt_i32_f32 alone saturates: +inf or alpha >= ~3.9e8 would land in bin 10)
+                bin_a = min(max(cvt_i32_x86((alpha + 1.0f) * 5.5f), 0), 10);
+                bin_p = min(max(cvt_i32_x86((phi + 1.0f) * 5.5f), 0), 10);
+                bin_t = min(max(cvt_i32_x86_f64(((double)theta / 3.14159265358979323846 + (double)1.0f) * (double)5.5f), 0), 10);
             }
         }
         if (valid) { atomicAdd(&myhist[bin_a], 1); atomicAdd(&myhist[11 + bin_p], 1); atomicAdd(&myhist[22 + bin_t], 1); }
@@ -641,9 +643,11 @@ void k_spfh_pairs(const float* __restrict__ xyz, const float* __restrict__ nrm, 
                 float wn = wx * njx + (wy * njy + wz * njz);
                 float un = ux * njx + (uy * njy + uz * njz);
                 float theta = lm::atan2f_glibc(wn, un);      // glibc's atan2f, the function registration.cpp:154 calls (libm_f32.hpp)
-                bin_a = min(max((int)((alpha + 1.0f) * 5.5f), 0), 10);
-                bin_p = min(max((int)((phi + 1.0f) * 5.5f), 0), 10);
-                bin_t = min(max((int)(((double)theta / 3.14159265358979323846 + (double)1.0f) * (double)5.5f), 0), 10);
+                // the x86 rule (include/tdv_hip.h, tdv_compute_fpfh): NaN and values outside int range are INT_MIN, bin 0
+                // (v_cvt_i32_f32 alone saturates: +inf or alpha >= ~3.9e8 would land in bin 10)
+                bin_a = min(max(cvt_i32_x86((alpha + 1.0f) * 5.5f), 0), 10);
+                bin_p = min(max(cvt_i32_x86((phi + 1.0f) * 5.5f), 0), 10);
+                bin_t = min(max(cvt_i32_x86_f64(((double)theta / 3.14159265358979323846 + (double)1.0f) * (double)5.5f), 0), 10);
             }
         }
         if (valid) { int* h = myhist[sel ? 1 : 0]; atomicAdd(&h[bin_a], 1); atomicAdd(&h[11 + bin_p], 1); atomicAdd(&h[22 + bin_t], 1); }

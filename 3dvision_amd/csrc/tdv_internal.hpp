@@ -84,6 +84,8 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 // and for everything outside it.  The reference's static_cast<int>(std::floor(x * inv)) is undefined in C++ there and compiles to
 // cvttss2si on x86; the device's own conversion (v_cvt_i32_f32) gives 0 for NaN and saturates.  Every voxel key goes through this.
 __host__ __device__ __forceinline__ int cvt_i32_x86(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? (int)f : INT_MIN; }
+// ... and double -> int as cvttsd2si converts (the FPFH theta bin is formed in double: include/tdv_hip.h, tdv_compute_fpfh).
+__host__ __device__ __forceinline__ int cvt_i32_x86_f64(double f) { return (f > -2147483649.0 && f < 2147483648.0) ? (int)f : INT_MIN; }
 
 // Study build (-DTDV_STUDY -> lib3dvision_hip_study.so, used by tools/studies/ and by the tests marked `study`): keeps the A/B
 // variants that LOST their measurement (the matrix-core scoring pass, the merged scoring dispatch, round 1's key-ordered descriptor

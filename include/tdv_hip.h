@@ -95,6 +95,9 @@ int tdv_ctx_set_icp_accumulation(tdv_ctx* ctx, int mode);
  *   Unweighted, as with L2: n_corr, fitness = n_corr / ns, rmse = sqrt(sum d2 / n_corr) and the stopping rule |delta rmse| < 1e-6.
  *   An iteration where fewer than 3 accepted correspondences have w > 0 (Tukey only) breaks as n_corr < 3 does: the pose is kept,
  *   and with fixed_iterations the loop goes on.
+ *   A non-finite residual or term has no special case: w follows the formulas above (an infinite e gives w = 0, a NaN e gives NaN
+ *   except Tukey's 0) and its products still enter the sums, so 0 * inf is NaN there, and a sum with an infinite product (and no
+ *   NaN, no infinity of the other sign) is that infinity.
  * An unknown loss, or a scale that is not finite and > 0 for a non-L2 loss, returns TDV_ERR_BAD_ARG and leaves the setting as it
  * was; L2 ignores scale (and reads back 0).  No environment variable selects a loss.  Reference-order accumulation reproduces the
  * reference's float sums, which have no loss: with TDV_ICP_ACCUMULATE_REFERENCE and a non-L2 loss, the five ICP entry points above
@@ -242,7 +245,10 @@ int tdv_estimate_normals(tdv_ctx* ctx, const float* xyz, int n, int k, float* ou
 
 /* ---- R4b: FPFH ---------------------------------------------------------------------------- */
 /* Replaces Registration::computeFPFH (src/registration.cpp:133-201): radius search d2 <= r^2,
- * (d2, idx) order, capped at 100 neighbours; SPFH + weighted FPFH, 33 bins. */
+ * (d2, idx) order, capped at 100 neighbours; SPFH + weighted FPFH, 33 bins.  Normals are taken as given (unit length is not
+ * checked).  A bin is static_cast<int>((alpha + 1) * 5.5), likewise for phi and (theta / pi + 1) * 5.5, clamped to [0, 10]; the
+ * cast is undefined in C++ for NaN and outside int range, and the rule here is what it does on x86 (cvttss2si / cvttsd2si): such a
+ * value gets INT_MIN, so bin 0 - e.g. alpha = +inf or >= ~3.9e8 from an infinite or far from unit normal. */
 int tdv_compute_fpfh(tdv_ctx* ctx, const float* xyz, const float* normals, int n, float radius,
                      float* out_desc33, int* out_nbr /* optional int[n*100] */, int* out_nbr_cnt /* optional int[n] */);
 

@@ -47,6 +47,13 @@ int main() {
     std::vector<int> knn(nt * 30), nb(nt * 100), cnt(nt), corr(ns), trace(200);
     orc_estimate_normals(tgt.data(), nt, 30, nrm.data(), knn.data());
     orc_compute_fpfh(tgt.data(), nrm.data(), nt, 0.2f, desc.data(), nb.data(), cnt.data());
+    // poisoned normals: +-inf, NaN, 1e19 and length-3e4 normals put the bins' casts at NaN and outside int range (the x86 rule)
+    {
+        std::vector<float> pn(nrm);
+        const float npoison[5] = {INFINITY, -INFINITY, NAN, 1e19f, 3e4f};
+        for (int i = 0; i < nt; i += 2) pn[3 * i + (i / 2) % 3] = npoison[(i / 2) % 5];
+        orc_compute_fpfh(tgt.data(), pn.data(), nt, 0.2f, desc.data(), nb.data(), cnt.data());
+    }
     orc_feature_match(fs.data(), ns, ft.data(), nt, corr.data());
     float T[16], fit, rmse; int bi, ir;
     orc_ransac(src.data(), ns, tgt.data(), nt, fs.data(), ft.data(), nullptr, 0.05f, 200, 0.999f, T, &fit, &rmse, trace.data(), corr.data(), &bi, &ir);

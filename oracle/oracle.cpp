@@ -99,9 +99,18 @@ inline void set_identity44(float* T) { for (int i = 0; i < 16; ++i) T[i] = 0.f; 
 // XSum holds a sum exactly (Shewchuk's non-overlapping partials, as Python's math.fsum), x32 rounds it to f32 once
 // and reports that ambiguity.  Needs IEEE double without contraction (-ffp-contract=off, no -ffast-math).
 struct XSum {
-    std::vector<double> p;     // non-overlapping partials, ascending magnitude: their exact sum is the sum
+    std::vector<double> p;     // non-overlapping partials, ascending magnitude: their exact sum is the sum of the finite terms
     double abs = 0.0;          // sum of |terms| (rounded: enters the error bound only, with margin)
     int grid = INT_MAX;        // every term is a multiple of 2^grid (the lowest set bit of any term)
+    // Non-finite terms stay out of the partials.  The sum is then what IEEE addition gives in ANY order, so the device's f64 tree
+    // gives it too: a NaN term, or +inf and -inf together, make NaN; otherwise an infinite term makes that infinity.  This holds
+    // because no partial sum of finite terms overflows f64: every term here is built from f32 values (an f32, an f32 product
+    // widened, the exact f64 product of two f32s, scaled by a weight <= 1), so |term| < 2^256, and fewer than 2^31 of them sum to
+    // less than 2^287, far below DBL_MAX.  A finite subtree of any tree stays finite, one with infinities of one sign only gives
+    // that infinity, and the lowest node whose subtree holds both signs (or a NaN) gives NaN, which every later addition keeps.
+    bool nan = false, pinf = false, ninf = false;
+    bool finite() const { return !nan && !pinf && !ninf; }
+    double nonfinite() const { return (nan || (pinf && ninf)) ? std::numeric_limits<double>::quiet_NaN() : pinf ? INFINITY : -INFINITY; }
     void add_exact(double x) {
         size_t i = 0;
         for (double y : p) {
@@ -114,6 +123,10 @@ struct XSum {
         p.push_back(x);
     }
     void add(double x) {
+        if (!std::isfinite(x)) {
+            if (std::isnan(x)) nan = true; else if (x > 0.0) pinf = true; else ninf = true;
+            return;
+        }
         add_exact(x);
         abs += std::fabs(x);
         if (x != 0.0) {
@@ -131,6 +144,7 @@ struct XSum {
     }
     // the exact sum correctly rounded to double (math.fsum's last step)
     double value() const {
+        if (!finite()) return nonfinite();
         size_t n = p.size();
         if (n == 0) return 0.0;
         double hi = p[--n], lo = 0.0;
@@ -173,6 +187,7 @@ float x32(const XSum& X, double den, double bound, bool* ambiguous) {
         two_prod(den, m, c, -1.0);
         return c.value() / den;
     };
+    if (!X.finite()) return (float)(X.nonfinite() / den);   // NaN or an infinity: no rounding to decide
     float f = (float)(X.value() / den);
     double lo, hi, dlo, dhi;
     for (int step = 0; step < 4; ++step) {    // the estimate is within a few f64 ulps: at most one step is ever taken
@@ -325,6 +340,7 @@ int orc_demo_model(float* xyz, float* normals, int capacity) {
 // range.  x86 compiles it to cvttss2si, which gives INT_MIN for all of those: that is the rule (include/tdv_hip.h), restated
 // here without the undefined cast.  Same results on x86.
 static inline int cvt_i32_x86(float f) { return (f >= -2147483648.0f && f < 2147483648.0f) ? static_cast<int>(f) : INT_MIN; }
+static inline int cvt_i32_x86_f64(double f) { return (f > -2147483649.0 && f < 2147483648.0) ? static_cast<int>(f) : INT_MIN; }
 void orc_voxel_key(const float* v, int n, int* out) { for (int i = 0; i < n; ++i) out[i] = cvt_i32_x86(std::floor(v[i])); }
 
 int orc_voxel_downsample(const float* xyz, const float* rgb, int n, float voxel_size,
@@ -409,9 +425,11 @@ void orc_compute_fpfh(const float* xyz, const float* normals, int n, float radiu
             float alpha = dot3(v, nj);
             float phi = dot3(u, dn);
             float theta = std::atan2(dot3(w, nj), dot3(u, nj));
-            int bin_a = std::clamp(static_cast<int>((alpha + 1.0f) * 5.5f), 0, 10);
-            int bin_p = std::clamp(static_cast<int>((phi + 1.0f) * 5.5f), 0, 10);
-            int bin_t = std::clamp(static_cast<int>((theta / M_PI + 1.0f) * 5.5f), 0, 10);
+            // static_cast<int> in the reference, undefined in C++ for NaN and outside int range: the x86 rule (cvttss2si /
+            // cvttsd2si, INT_MIN there: bin 0) of include/tdv_hip.h, tdv_compute_fpfh, restated without the undefined cast
+            int bin_a = std::clamp(cvt_i32_x86((alpha + 1.0f) * 5.5f), 0, 10);
+            int bin_p = std::clamp(cvt_i32_x86((phi + 1.0f) * 5.5f), 0, 10);
+            int bin_t = std::clamp(cvt_i32_x86_f64((theta / M_PI + 1.0f) * 5.5f), 0, 10);
             hist[bin_a] += 1.0f; hist[11 + bin_p] += 1.0f; hist[22 + bin_t] += 1.0f;
         }
         float sum = 0;

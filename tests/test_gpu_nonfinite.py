@@ -263,10 +263,14 @@ def _poison_icp(src, tgt, nrm, kind, rng):
         tgt[rt, rng.integers(0, 3, len(rt))] = 1e19
     elif kind == "nrm_nan":
         nrm[rt] = np.nan
+    elif kind == "nrm_inf":                             # r = (p - q) . n and J are infinite or NaN
+        nrm[rt, rng.integers(0, 3, len(rt))] = np.where(rng.random(len(rt)) < 0.5, np.inf, -np.inf).astype(np.float32)
+    elif kind == "nrm_huge":                            # r finite, J[a] * J[b] overflows f32 to +inf
+        nrm[rt, rng.integers(0, 3, len(rt))] = 1e20
     return src, tgt, nrm
 
 
-ICP_KINDS = ["src_nan", "src_inf", "tgt_inf", "tgt_nan", "tgt_huge", "nrm_nan"]
+ICP_KINDS = ["src_nan", "src_inf", "tgt_inf", "tgt_nan", "tgt_huge", "nrm_nan", "nrm_inf", "nrm_huge"]
 
 
 @pytest.mark.parametrize("kind", ICP_KINDS)
@@ -360,3 +364,131 @@ def test_register_batch_poisoned_model(ctx, tdv, synth, knobs):
         assert r["icp_iterations"] == fine.iterations, (knobs, b)
         _same(r["T"], fine.transformation, (knobs, b))
         _same(np.float32(r["fitness"]), np.float32(fine.fitness)); _same(np.float32(r["rmse"]), np.float32(fine.rmse))
+
+
+# ---------------------------------------------------------------- FPFH
+# The three bins are static_cast<int> of (alpha + 1) * 5.5, (phi + 1) * 5.5 and (theta / pi + 1) * 5.5 in the reference, undefined in
+# C++ for NaN and outside int range; the rule (include/tdv_hip.h, tdv_compute_fpfh) is x86's: INT_MIN there, so bin 0.  A normal with
+# an infinite component or one far from unit length puts alpha or phi there (+inf, or >= ~3.9e8: the device's own conversion
+# saturates those to bin 10).  Poisoned points are in no radius list but their own (d2 <= r2 is false for NaN and for 1e19's
+# overflowing square), so every descriptor row is defined.
+NORMAL_POISON = {"inf": np.inf, "ninf": -np.inf, "nan": NEG_NAN, "pnan": np.nan, "huge": 1e19, "len3e4": None, "zero": 0.0,
+                 "negzero": -0.0, "subnormal": 1e-40}
+FPFH_N, FPFH_RADIUS = 5000, 0.008
+
+
+def _fpfh_cloud(synth):
+    from test_gpu_features import _cloud
+    return _cloud(synth, FPFH_N)
+
+
+def _fpfh_rows(where):
+    if where == "half":
+        return _rows(FPFH_N, "half")
+    return _rows(FPFH_N, "first") + _rows(FPFH_N, "last") + _rows(FPFH_N, "edges") + _rows(FPFH_N, "few")
+
+
+def _poison_normals(nrm, kind, rows, seed):
+    nrm = nrm.copy()
+    rng = np.random.default_rng(seed)
+    if kind == "len3e4":                       # random directions of length 3e4: |alpha| reaches ~9e8
+        v = rng.normal(size=(len(rows), 3))
+        nrm[rows] = (v / np.linalg.norm(v, axis=1, keepdims=True) * 3e4).astype(np.float32)
+    elif kind in ("zero", "negzero", "subnormal"):
+        nrm[rows] = np.float32(NORMAL_POISON[kind])
+    else:                                      # one component, alternating columns
+        nrm[rows, np.arange(len(rows)) % 3] = np.float32(NORMAL_POISON[kind])
+    return nrm
+
+
+def _fpfh_all_entry_points(ctx, orc, pts, nrm, what):
+    """tdv_compute_fpfh and tdv_compute_fpfh_dev against the oracle: neighbour lists exact, descriptors bit for bit."""
+    ref_d, ref_nb, ref_cnt = orc.compute_fpfh(pts, nrm, FPFH_RADIUS, want_neighbors=True)
+    got_d, got_nb, got_cnt = ctx.compute_fpfh(pts, nrm, FPFH_RADIUS, want_neighbors=True)
+    assert np.array_equal(got_cnt, ref_cnt) and np.array_equal(got_nb, ref_nb), what
+    assert not np.isnan(ref_d).any(), what
+    bad = np.nonzero((got_d.view(np.uint32) != ref_d.view(np.uint32)).any(1))[0]
+    assert len(bad) == 0, (what, "host entry: %d rows differ, first %s" % (len(bad), bad[:8].tolist()))
+    n = len(pts)
+    d_x, d_n = _dev(pts), _dev(nrm)
+    d_f = torch.empty((n, 33), dtype=torch.float32, device=DEV)
+    d_nb = torch.empty((n, 100), dtype=torch.int32, device=DEV); d_c = torch.empty(n, dtype=torch.int32, device=DEV)
+    ctx.compute_fpfh_dev(d_x.data_ptr(), d_n.data_ptr(), n, FPFH_RADIUS, d_f.data_ptr(), d_nb.data_ptr(), d_c.data_ptr())
+    assert np.array_equal(d_c.cpu().numpy(), ref_cnt) and np.array_equal(d_nb.cpu().numpy(), ref_nb), what
+    assert d_f.cpu().numpy().tobytes() == ref_d.tobytes(), (what, "device entry")
+    return ref_d
+
+
+@pytest.mark.parametrize("kind", list(NORMAL_POISON))
+@pytest.mark.parametrize("where", ["ends_and_edges", "half"])
+def test_fpfh_poisoned_normals(ctx, orc, synth, kind, where):
+    pts = _fpfh_cloud(synth)
+    nrm = orc.estimate_normals(pts, 30)
+    rows = _fpfh_rows(where)
+    _fpfh_all_entry_points(ctx, orc, pts, _poison_normals(nrm, kind, rows, 1), (kind, where))
+
+
+def _pairs_where_the_rules_differ(orc, pts, nrm):
+    """Pairs (i, j) of the radius lists whose alpha or phi bin a saturating conversion puts in bin 10 and x86's in bin 0:
+    (x + 1) * 5.5 = +inf or >= 2^31, in f32 as the kernels form it."""
+    _, nb, cnt = orc.compute_fpfh(pts, nrm, FPFH_RADIUS, want_neighbors=True)
+    i = np.repeat(np.arange(len(pts)), cnt)
+    j = nb[np.arange(100)[None, :] < cnt[:, None]]
+    keep = i != j
+    i, j = i[keep], j[keep]
+    with np.errstate(all="ignore"):
+        d = pts[j] - pts[i]
+        e = (d / np.sqrt((d * d).sum(1, dtype=np.float32))[:, None]).astype(np.float32)
+        u, nj = nrm[i], nrm[j]
+        v = np.cross(u, e).astype(np.float32)
+        alpha = (v * nj).sum(1, dtype=np.float32); phi = (u * e).sum(1, dtype=np.float32)
+        far = lambda x: ((x + np.float32(1)) * np.float32(5.5)) >= np.float32(2147483648.0)   # noqa: E731  (+inf included)
+        return int((far(alpha) | far(phi)).sum())
+
+
+def test_fpfh_saturating_bins_are_reached(orc, synth):
+    """The normal poisons above reach the bins where a saturating conversion and x86's differ: else they would test nothing."""
+    pts = _fpfh_cloud(synth)
+    nrm = orc.estimate_normals(pts, 30)
+    for kind, where in (("inf", "ends_and_edges"), ("inf", "half"), ("huge", "ends_and_edges"), ("huge", "half"), ("len3e4", "half")):
+        assert _pairs_where_the_rules_differ(orc, pts, _poison_normals(nrm, kind, _fpfh_rows(where), 1)) > 0, (kind, where)
+
+
+@pytest.mark.parametrize("kind", ["nan", "inf", "ninf", "sq_overflow"])
+@pytest.mark.parametrize("col", [0, "row"])
+def test_fpfh_poisoned_points(ctx, orc, synth, kind, col):
+    """Poisoned coordinates with clean normals, and with infinite normals on the same cloud's half rows."""
+    pts = _fpfh_cloud(synth)
+    nrm = orc.estimate_normals(pts, 30)
+    rows = _rows(FPFH_N, "first") + _rows(FPFH_N, "last") + _rows(FPFH_N, "edges") + list(range(1, FPFH_N, 7))
+    bad = _poison(pts, POISON[kind], rows, col)
+    _fpfh_all_entry_points(ctx, orc, bad, nrm, (kind, col, "clean normals"))
+    _fpfh_all_entry_points(ctx, orc, bad, _poison_normals(nrm, "inf", _rows(FPFH_N, "half"), 2), (kind, col, "inf normals"))
+
+
+@pytest.mark.parametrize("kind", ["inf", "ninf", "sq_overflow"])
+@pytest.mark.parametrize("col", [1, "row"])
+def test_normals_fpfh_dev_poisoned_points(ctx, orc, synth, kind, col):
+    """tdv_normals_fpfh_dev on a cloud with +-inf / 1e19 rows: normals equal the oracle's on the finite rows (an infinite row's own
+    kNN list meets NaN distances, which the reference's partial_sort does not order: test_gpu_fuzz.py); descriptors equal the
+    oracle's FPFH of the device's normals on every row."""
+    pts = _fpfh_cloud(synth)
+    rows = _rows(FPFH_N, "first") + _rows(FPFH_N, "last") + _rows(FPFH_N, "edges") + list(range(2, FPFH_N, 11))
+    bad = _poison(pts, POISON[kind], rows, col)
+    d_x = _dev(bad); d_n = torch.empty_like(d_x); d_f = torch.empty((FPFH_N, 33), dtype=torch.float32, device=DEV)
+    ctx.normals_fpfh_dev(d_x.data_ptr(), FPFH_N, 30, FPFH_RADIUS, d_n.data_ptr(), d_f.data_ptr())
+    got_n, got_f = d_n.cpu().numpy(), d_f.cpu().numpy()
+    q = np.isfinite(bad).all(1)
+    _same(got_n[q], orc.estimate_normals(bad, 30)[q], (kind, col, "normals"))
+    assert got_f.tobytes() == orc.compute_fpfh(bad, got_n, FPFH_RADIUS).tobytes(), (kind, col, "descriptors")
+
+
+@pytest.mark.study
+@pytest.mark.parametrize("kind", ["inf", "nan", "huge", "len3e4"])
+def test_fpfh_one_point_per_wave_poisoned(ctx, orc, synth, kind):
+    """The study library's one-point-per-wave SPFH / FPFH (TDV_FPFH_PAIRS=0) holds the same bins on poisoned normals."""
+    pts = _fpfh_cloud(synth)
+    nrm = _poison_normals(orc.estimate_normals(pts, 30), kind, _rows(FPFH_N, "half"), 3)
+    with _env(TDV_FPFH_PAIRS=0):
+        _fpfh_all_entry_points(ctx, orc, pts, nrm, (kind, "one point per wave"))
+    _fpfh_all_entry_points(ctx, orc, pts, nrm, (kind, "two points per wave"))

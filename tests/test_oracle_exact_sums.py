@@ -183,3 +183,52 @@ def test_ransac_exact_rmse_is_the_exact_sum(orc, synth, ns):
     te = _f32_of_fraction(sum((Fraction(float(v)) for v in e2), Fraction(0)))
     assert int(inl.sum()) == round(float(b["fitness"]) * ns)
     assert b["rmse"] == np.sqrt(np.float32(te / np.float32(inl.sum())))
+
+
+# ---------------------------------------------------------------- non-finite terms
+@pytest.mark.parametrize("terms,expect", [
+    ([1.0, np.inf, 2.0], np.inf),
+    ([np.inf], np.inf),
+    ([-3.0, -np.inf, 1e300, -np.inf], -np.inf),
+    ([np.inf, 5.0, -np.inf], np.nan),
+    ([1.0, np.nan, 2.0], np.nan),
+    ([np.nan, np.inf], np.nan),
+    ([-np.nan, -np.inf, -1.0], np.nan),
+])
+def test_exact_sum_of_non_finite_terms(orc, terms, expect):
+    """What the device's f64 tree gives in any order (oracle.cpp, XSum): a NaN term or both infinities make NaN, else an infinite
+    term makes that infinity; the f32 is the same value and nothing is ambiguous."""
+    for order in (terms, terms[::-1], terms[1:] + terms[:1]):
+        for reps in (1, 1000):
+            t = np.array(order * reps, np.float64)
+            f64, f32, amb = orc.exact_sum(t, 30)
+            if np.isnan(expect):
+                assert np.isnan(f64) and np.isnan(f32), (order, reps, f64, f32)
+            else:
+                assert f64 == expect and f32 == np.float32(expect), (order, reps, f64, f32)
+            assert not amb
+            if reps == 1:
+                with np.errstate(invalid="ignore"):
+                    assert np.array_equal(np.float64(np.sum(t)), f64, equal_nan=True)   # one more order, numpy's pairwise sum
+
+
+def test_exact_sum_finite_terms_unchanged_next_to_overflowing_f32_products(orc):
+    """An f32 product that overflows to +inf in one term set leaves another set of finite terms exact (the infinities are per sum)."""
+    big = np.float32(1e20)
+    with np.errstate(over="ignore"):
+        sq = np.float32(big * big)
+    assert np.isinf(sq)
+    f64, f32, _ = orc.exact_sum(np.array([sq, 1.0], np.float64), 30)
+    assert f64 == np.inf and f32 == np.inf
+    t = np.array([1e38, 1.0, -1e38, 2.0 ** -60], np.float64)
+    assert orc.exact_sum(t, 30)[0] == math.fsum(t.tolist())
+
+
+def test_oracle_svd_ends_on_non_finite_entries(orc):
+    """The oracle's Jacobi SVD loop has no iteration count: a NaN or an infinite entry must end it (every comparison with NaN is
+    false; an infinite scale turns the other entries into 0 or NaN)."""
+    for v in (np.inf, -np.inf, np.nan, 1e38):
+        H = np.eye(3, dtype=np.float32) * 0.3 + 0.01
+        H[1, 2] = v
+        R = orc.kabsch_rotation(H)
+        assert R.shape == (3, 3)
