@@ -1,10 +1,17 @@
 #!/usr/bin/env python3
 """bench.py — BASELINE.json's headline metric on MI355X:
-RANSAC hypotheses/s + ICP iterations/s at 200k-point clouds, with the roofline of the dominant
-kernel and a CPU baseline (the oracle) timed beside it.
+RANSAC hypotheses/s + ICP iterations/s at 200k-point clouds; with --full also the roofline of the
+dominant kernel, a CPU baseline (the oracle) timed beside it and the other configurations.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
+
+A plain run does only what the headline needs: it sets up, warms up, times the K steps, writes the outputs of
+--dump-outputs and prints the line (`value`, `ms_per_step`, the two sub-rates, the per-rank table and the
+results of the last step).  --full adds everything measured after the timed region, outside `value`: the
+search kernel timed on its own, the brute-force scan, the reference-order sums, the every-test-scored RANSAC
+call, the `roofline` block built from them, config C5's share (N > 1), the `operators` block and the
+`cpu_baseline`.  The timed K steps are the same either way.
 
 One STEP = one pass of the hot path over one batch of synthetic input at the headline size
 (N_s = N_t = 200,000, the reference's settings: ICP threshold 0.4 x voxel, RANSAC threshold 1.5 x voxel):   1 ICP iteration (nearest-neighbour correspondences + normal equations + 6x6 solve +
@@ -48,11 +55,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--points", type=int, default=200000, help="N_s = N_t (headline: 200000)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-operators", action="store_true", help="skip the per-operator block measured after the timed region")
-    ap.add_argument("--c5-timeout-s", type=float, default=300.0, help="N > 1: deadline of the C5 share; past it the line is printed without C5")
-    ap.add_argument("--c5-instances", type=int, default=1024, help="N > 1: instances per rank of the C5 tray measured after the timed region")
-    ap.add_argument("--cpu-budget-s", type=float, default=16.0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also measure the roofline figures, C5 (N > 1), the operators and the CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-operators", action="store_true", help="--full: skip the per-operator block (and C5 at N > 1) measured after the timed region")
+    ap.add_argument("--c5-timeout-s", type=float, default=300.0, help="--full, N > 1: deadline of the C5 share; past it the line is printed without C5")
+    ap.add_argument("--c5-instances", type=int, default=1024, help="--full, N > 1: instances per rank of the C5 tray measured after the timed region")
+    ap.add_argument("--cpu-budget-s", type=float, default=16.0, help="--full: time budget of the CPU baseline's single-thread sample, in seconds")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write the results of the last one (ICP and RANSAC) as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--launch-check", action="store_true",
@@ -267,11 +276,7 @@ def main():
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, r_icp, r_rs, "rank%d_" % rank if world > 1 else "")
     sc_ms, sc_launches = ctx.timing_read(tdv.TIMER_RANSAC_SCORE)
-    icp_search_used = ctx.last_icp_search()   # before the supplementary scan below changes it
-    # the search kernel of the timed region, timed on its own: one more ICP call of the same shape, outside `value`
-    ctx.timing_read(tdv.TIMER_ICP_NN)
-    ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, args.steps, True, fixed_iterations=True)
-    nn_ms, nn_launches = ctx.timing_read(tdv.TIMER_ICP_NN)
+    icp_search_used = ctx.last_icp_search()   # before the supplementary scan of --full changes it
     ctx.timing_enable(False)
     rescore_share = ctx.last_ransac_rescore()  # fast scoring pass: share of the tests scored a second time exactly (whole waves on a pair of points); -1: exact mode
     scored_share = ctx.last_ransac_scored()    # share of the (hypothesis, point) tests evaluated at all (exact bail-out: DESIGN.md 4)
@@ -291,37 +296,42 @@ def main():
         per_rank = [mine]
     per_rank = [[float(v) for v in x.cpu()] for x in per_rank]
 
-    # supplementary: the brute-force NN scan (the reference kernel's algorithm) on the same inputs, outside `value`
-    ctx.timing_enable(True)
-    ctx.set_icp_search("brute")
-    ctx.timing_read(tdv.TIMER_ICP_NN)
-    ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, 3, True, fixed_iterations=True)
-    bf_ms, bf_launches = ctx.timing_read(tdv.TIMER_ICP_NN)
-    ctx.timing_enable(False)
-    BF_ITERS = 10                                     # whole iterations with the reference's scan (search + sums + solve), wall clock
-    torch.cuda.synchronize(); t_bf0 = time.perf_counter()
-    ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, BF_ITERS, True, fixed_iterations=True)
-    torch.cuda.synchronize(); bf_iters_per_s = BF_ITERS / (time.perf_counter() - t_bf0)
-    ctx.set_icp_search("auto")
-    # supplementary: the same ICP call with the reference's accumulation order (bit-equal to the CPU path; a serial chain per iteration)
-    REF_ITERS = 10
-    ctx.set_icp_accumulation("reference")
-    ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, 2, True, fixed_iterations=True)
-    torch.cuda.synchronize(); t_r0 = time.perf_counter()
-    ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, REF_ITERS, True, fixed_iterations=True)
-    torch.cuda.synchronize(); ref_iters_per_s = REF_ITERS / (time.perf_counter() - t_r0)
-    ctx.set_icp_accumulation("tree")
+    if args.full:
+        # supplementary: the search kernel of the timed region, timed on its own - one more ICP call of the same shape, outside `value`
+        ctx.timing_enable(True)
+        ctx.timing_read(tdv.TIMER_ICP_NN)
+        ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, args.steps, True, fixed_iterations=True)
+        nn_ms, nn_launches = ctx.timing_read(tdv.TIMER_ICP_NN)
+        # supplementary: the brute-force NN scan (the reference kernel's algorithm) on the same inputs, outside `value`
+        ctx.set_icp_search("brute")
+        ctx.timing_read(tdv.TIMER_ICP_NN)
+        ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, 3, True, fixed_iterations=True)
+        bf_ms, bf_launches = ctx.timing_read(tdv.TIMER_ICP_NN)
+        ctx.timing_enable(False)
+        BF_ITERS = 10                                     # whole iterations with the reference's scan (search + sums + solve), wall clock
+        torch.cuda.synchronize(); t_bf0 = time.perf_counter()
+        ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, BF_ITERS, True, fixed_iterations=True)
+        torch.cuda.synchronize(); bf_iters_per_s = BF_ITERS / (time.perf_counter() - t_bf0)
+        ctx.set_icp_search("auto")
+        # supplementary: the same ICP call with the reference's accumulation order (bit-equal to the CPU path; a serial chain per iteration)
+        REF_ITERS = 10
+        ctx.set_icp_accumulation("reference")
+        ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, 2, True, fixed_iterations=True)
+        torch.cuda.synchronize(); t_r0 = time.perf_counter()
+        ctx.icp_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), d_nrm.data_ptr(), n, T0, icp_thr, REF_ITERS, True, fixed_iterations=True)
+        torch.cuda.synchronize(); ref_iters_per_s = REF_ITERS / (time.perf_counter() - t_r0)
+        ctx.set_icp_accumulation("tree")
 
-    # supplementary: RANSAC with EVERY (hypothesis, point) test evaluated (a traced call: the exact bail-out is off), outside `value`
-    full_hyps = 4 * 65536
-    ctx.timing_enable(True); ctx.timing_read(tdv.TIMER_RANSAC_SCORE)
-    torch.cuda.synchronize(); t_f0 = time.perf_counter()
-    r_full = ctx.ransac_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), n, None, None, d_corr.data_ptr(), voxel, full_hyps, 2.0, 42, trace=True)
-    torch.cuda.synchronize(); t_full = time.perf_counter() - t_f0
-    full_ms, full_launches = ctx.timing_read(tdv.TIMER_RANSAC_SCORE); ctx.timing_enable(False)
-    full_rescore = ctx.last_ransac_rescore(); full_scored = ctx.last_ransac_scored()
+        # supplementary: RANSAC with EVERY (hypothesis, point) test evaluated (a traced call: the exact bail-out is off), outside `value`
+        full_hyps = 4 * 65536
+        ctx.timing_enable(True); ctx.timing_read(tdv.TIMER_RANSAC_SCORE)
+        torch.cuda.synchronize(); t_f0 = time.perf_counter()
+        r_full = ctx.ransac_dev(d_src.data_ptr(), n, d_tgt.data_ptr(), n, None, None, d_corr.data_ptr(), voxel, full_hyps, 2.0, 42, trace=True)
+        torch.cuda.synchronize(); t_full = time.perf_counter() - t_f0
+        full_ms, full_launches = ctx.timing_read(tdv.TIMER_RANSAC_SCORE); ctx.timing_enable(False)
+        full_rescore = ctx.last_ransac_rescore(); full_scored = ctx.last_ransac_scored()
 
-    # N > 1: config C5 (BASELINE.json configs[4]) rides in the same line - every rank registers its own 1,024-instance tray, the model
+    # N > 1, --full: config C5 (BASELINE.json configs[4]) rides in the same line - every rank registers its own 1,024-instance tray, the model
     # moved once by tdv_broadcast_model and the results gathered once by tdv_gather_results (C ABI, ncclComm_t over RCCL); in the one-GPU
     # rehearsal (gloo) the same two steps go through torch.distributed.  Outside `value`.
     # The share has never met more than one device (no multi-GPU box in the builder's reach), so it must not be able to take the headline
@@ -329,7 +339,7 @@ def main():
     # collective at the deadline is abandoned - the line is printed without C5 and every rank leaves through os._exit (all ranks share the
     # deadline, so they leave together).
     c5_out = None; c5_error = None; c5_hung = False
-    if distributed and not args.no_operators:
+    if distributed and args.full and not args.no_operators:
         import threading
         sys.path.insert(0, os.path.join(ROOT, "tools"))
         import bench_c5
@@ -355,132 +365,8 @@ def main():
 
     if rank == 0:
         steps_total = steps_timed * world
-        pairs = float(n) * float(n)
-        nn_avg_ms = nn_ms / max(nn_launches, 1)
-        sc_avg_ms = sc_ms / max(sc_launches, 1)
-        bf_avg_ms = bf_ms / max(bf_launches, 1)
-        hyps_total = float(steps_timed) * HYPS_PER_STEP
-        pruned_default = icp_search_used in ("pruned", "grid")
-        # HBM traffic per launch from the PMC passes (rocprofv3 --pmc cannot run inside this process): taken from the
-        # committed summary of the same command when it covers this workload, else null
-        pm = None
-        try:
-            for pm_round in ("r4", "r3", "r2"):
-                pm_path = os.path.join(ROOT, "profiles", pm_round, "pmc_summary.json")
-                if os.path.exists(pm_path):
-                    break
-            pm = json.load(open(pm_path))
-            if not (pm["workload"]["n_src"] == n and pm["workload"]["n_tgt"] == n):
-                pm = None
-        except Exception:
-            pm = None
-
-        def traffic(kernel):
-            try:
-                return pm["kernels"]["tdv::" + kernel]["hbm_bytes_per_launch"]
-            except Exception:
-                return None
-
-        # Scoring kernel of the timed region.  Reference arithmetic (k_ransac_score): per hypothesis-point 18 ops transform +
-        # 3 sub + 5 squared norm + 1 compare + 1 count = 28 VALU lane-ops (issued as packed f32 pairs).  Default
-        # (k_ransac_score_fast): 16.6 lane-ops per hypothesis-point in the FMA pass (per 8 points 60 packed instructions -
-        # 48 fma, 12 add - and 13 scalar-f32 ones) + 28 for every test scored again exactly: a wave re-scores the PAIR of points that
-        # one of its 64 hypotheses has inside its rounding band (round 4; the whole 8-point chunk until then)
-        # (rescore_share, counted by the kernel).  An FMA is ONE lane-op here, as in the peak (lane-instructions, not flops).
-        # Algorithmic HBM bytes per launch: the packed pairs once (24 B per point) + 48 B per hypothesis in, 4 B out.
-        # A "launch" is one dispatch of the scoring kernel (what rocprofv3's kernel statistics average over).  With the exact
-        # bail-out a batch of hypotheses is two dispatches: every hypothesis over a prefix of the points, then the hypotheses that
-        # can still beat the best count of the earlier batches over the rest - together they read the pair array once.
-        # (batching rule of csrc/ransac.hip: batches of 65,536 hypotheses, the first one 8,192 when the bail-out is on)
-        hyps_call = args.steps * HYPS_PER_STEP        # the timed region's one RANSAC call
-        bail = (os.environ.get("TDV_RANSAC_BAILOUT", "1") != "0") and hyps_call > 16384
-        sc_batches = (1 + -(-(hyps_call - 8192) // 65536)) if bail else max(1, -(-hyps_call // 65536))
-        sc_hyps_per_launch = hyps_total / max(sc_launches, 1)
-        fast = rescore_share >= 0.0
-        ops_per_test = (16.6 + 28.0 * rescore_share) if fast else 28.0
-        sc_tops = ops_per_test * scored_share * n * hyps_total / max(sc_ms * 1e-3, 1e-12) / 1e12
-        sc_bytes = (24.0 * n * sc_batches + 56.0 * hyps_total) / max(sc_launches, 1)
-        sc_kernel = "k_ransac_score_fast" if fast else "k_ransac_score"
-        score = {
-            "kernel": sc_kernel, "bound": "valu_f32",
-            "achieved": sc_tops, "peak": VALU_PEAK_TOPS,
-            "unit": ("T VALU lane-ops/s executed: %.1f per hypothesis-point = 16.6 in the FMA pass + 28 x the %.3f of the tests (whole waves on a pair of "
-                     "points) scored again with the reference arithmetic; same inlier counts as the 28-op reference arithmetic" % (ops_per_test, rescore_share))
-                    if fast else "Tops/s (f32 VALU, FMA contraction forbidden by parity; 28 ops per hypothesis-point)",
-            "frac": sc_tops / VALU_PEAK_TOPS, "avg_launch_ms": sc_avg_ms, "launches": sc_launches,
-            "hyps_per_launch": sc_hyps_per_launch, "batches": sc_batches, "total_ms": sc_ms,
-            "hbm": {"algorithmic_bytes_per_launch": sc_bytes, "achieved": sc_bytes / max(sc_avg_ms * 1e-3, 1e-12) / 1e9,
-                    "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": sc_bytes / max(sc_avg_ms * 1e-3, 1e-12) / 1e9 / HBM_PEAK_GBPS},
-            "traffic": traffic(sc_kernel),
-        }
-        full_ops = (16.6 + 28.0 * full_rescore) if full_rescore >= 0.0 else 28.0
-        score["every_test_scored"] = {
-            "note": "the same kernel with the bail-out off (a call that asks for the per-iteration trace): %d hypotheses x all %d points, one dispatch per batch" % (full_hyps, n),
-            "hyps_per_s": full_hyps / t_full, "avg_launch_ms": full_ms / max(full_launches, 1), "launches": full_launches,
-            "scored_share": full_scored, "achieved": full_ops * n * full_hyps / max(full_ms * 1e-3, 1e-12) / 1e12, "peak": VALU_PEAK_TOPS,
-            "frac": full_ops * n * full_hyps / max(full_ms * 1e-3, 1e-12) / 1e12 / VALU_PEAK_TOPS,
-            "best_inliers": int(r_full.inliers), "best_iteration": int(r_full.best_iteration)}
-        if fast:
-            score["rescore_share"] = rescore_share
-            score["scored_share"] = scored_share
-            score["note"] = ("%.3f of the hypothesis-point tests were evaluated: a hypothesis whose count over a prefix of the points plus all remaining points "
-                             "cannot exceed the best count of the earlier batches is not scored further (exact: same best hypothesis, count, "
-                             "fitness, rmse); `achieved` counts executed lane-ops only" % scored_share)
-            score["reference_arithmetic_equivalent_tops"] = 28.0 * n * hyps_total / max(sc_ms * 1e-3, 1e-12) / 1e12
-        # NN search of the timed region.  Algorithmic HBM bytes of one ICP iteration: 12*N_s + 24*N_t + 124
-        icp_bytes = 12.0 * n + 24.0 * n + 124
-        nn_kernel = {"grid": "k_icp_nn_grid", "pruned": "k_icp_nn_pruned"}.get(icp_search_used, "k_icp_nn_scan")
-        nn_equiv = 8.0 * pairs / max(nn_avg_ms * 1e-3, 1e-12) / 1e12
-        nn = {
-            "kernel": nn_kernel, "avg_launch_ms": nn_avg_ms, "launches": nn_launches, "total_ms": nn_ms,
-            "hbm": {"algorithmic_bytes_per_launch": icp_bytes, "achieved": icp_bytes / max(nn_avg_ms * 1e-3, 1e-12) / 1e9,
-                    "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": icp_bytes / max(nn_avg_ms * 1e-3, 1e-12) / 1e9 / HBM_PEAK_GBPS},
-            "traffic": traffic(nn_kernel),
-        }
-        if icp_search_used == "grid":
-            nn.update({"bound": "latency (hash-grid probes: 8 table entries + the points of the occupied cells per source point)",
-                       "search": "grid", "bruteforce_equivalent_tops": nn_equiv,
-                       "note": "exact hash-grid search (cells of 2.2 x the acceptance threshold, one lane per source point): identical "
-                               "correspondences to the scan; no VALU roofline fraction is claimed for it"})
-        elif pruned_default:
-            nn.update({"bound": "latency (box walk: few pairs evaluated)", "search": "pruned", "bruteforce_equivalent_tops": nn_equiv,
-                       "note": "exact pruned search: evaluates only boxes that can hold a neighbour within the bound, so the "
-                               "brute-force pair count / time exceeds the VALU peak; no VALU roofline fraction is claimed for it"})
-        else:
-            nn.update({"bound": "valu_f32", "achieved": nn_equiv, "peak": VALU_PEAK_TOPS, "frac": nn_equiv / VALU_PEAK_TOPS})
-        # brute-force scan (3 sub + 3 mul + 2 add per pair = 8 VALU ops), supplementary
-        bf_tops = 8.0 * pairs / max(bf_avg_ms * 1e-3, 1e-12) / 1e12
-        brute = {
-            "kernel": "k_icp_nn_scan", "bound": "valu_f32", "achieved": bf_tops, "peak": VALU_PEAK_TOPS,
-            "unit": "Tops/s (8 ops per pair)", "frac": bf_tops / VALU_PEAK_TOPS, "avg_launch_ms": bf_avg_ms, "launches": bf_launches,
-            "traffic": traffic("k_icp_nn_scan"),
-            "note": "reference-algorithm scan, timed after the K steps (TDV_ICP_SEARCH=brute makes it the default)",
-        }
-        dominant, other = (score, nn) if sc_ms >= nn_ms else (nn, score)
-        roofline = dict(dominant)
-        roofline["traffic_unit"] = "HBM bytes per launch (FETCH_SIZE + WRITE_SIZE, mean over the dispatches of the same command)"
-        roofline["traffic_source"] = ("FROM A COMMITTED PROFILE, not measured by this run: profiles/%s/pmc_summary.json (separate rocprofv3 --pmc FETCH_SIZE / "
-                                      "WRITE_SIZE passes of this command on the builder's box; PMC counters cannot be read from inside the benchmarked process)" % pm_round) \
-            if roofline.get("traffic") is not None else None
-        roofline["second_kernel"] = other
-        roofline["icp_nn_bruteforce_scan"] = brute
-        # BASELINE.json's metric, flat, in the dict the driver keeps: hypotheses/s and iterations/s at 200k points (whole job), each from
-        # its own synchronized sub-region of the timed steps; beside them the figures the docs promise next to every headline number
         hyps_per_s = steps_timed * HYPS_PER_STEP * world / t_rs
         iters_per_s = steps_timed * world / t_icp
-        roofline.update({
-            "ransac_hyps_per_s": hyps_per_s, "icp_iters_per_s": iters_per_s,
-            "ransac_hyps_per_s_every_test_scored": full_hyps / t_full,
-            "icp_iters_per_s_bruteforce_scan": bf_iters_per_s,
-            "icp_iters_per_s_reference_order_sums": ref_iters_per_s,
-            "icp_search": icp_search_used,
-            "target_ransac_hyps_per_s": 1e6, "target_icp_iters_per_s": 50,
-            "hbm_algorithmic_bytes_per_launch": score["hbm"]["algorithmic_bytes_per_launch"] if dominant is score else nn["hbm"]["algorithmic_bytes_per_launch"],
-            "hbm_achieved_GBps": dominant["hbm"]["achieved"], "hbm_frac": dominant["hbm"]["frac"],
-            "every_test_scored_frac": score["every_test_scored"]["frac"], "every_test_scored_avg_launch_ms": score["every_test_scored"]["avg_launch_ms"],
-            "bruteforce_scan_frac": brute["frac"], "bruteforce_scan_avg_launch_ms": brute["avg_launch_ms"],
-            "second_kernel_name": other["kernel"], "second_kernel_avg_launch_ms": other["avg_launch_ms"],
-        })
         out = {
             "metric": "RANSAC hyps/s + ICP iters/s @ 200k-pt clouds",
             "value": steps_total / elapsed,
@@ -492,8 +378,6 @@ def main():
             "dtype": "f32", "data": "synthetic",
             "icp_iters_per_s": iters_per_s,
             "ransac_hyps_per_s": hyps_per_s,
-            "icp_iters_per_s_bruteforce_scan": bf_iters_per_s,
-            "icp_iters_per_s_reference_order_sums": ref_iters_per_s,
             "targets": {"icp_iters_per_s": 50, "ransac_hyps_per_s": 1e6},
             "config": {"workload": "headline: N_s=N_t=%d, point-to-plane ICP (fixed %d iterations per call, %s correspondence search) + RANSAC scoring (%d hyps per call), "
                                    "one call of each in the timed region, one instance pair per GPU"
@@ -506,10 +390,137 @@ def main():
             "model_bcast_ms": bcast_ms if distributed else None,
             "per_rank": [{"rank": int(x[0]), "steps_per_s": x[1], "dominant_kernel_avg_ms": x[2], "dominant_kernel_frac": x[3], "model_bcast_ms": x[4] if distributed else None}
                          for x in per_rank],
-            "roofline": roofline,
             "result_check": {"icp_fitness": float(r_icp.fitness), "icp_rmse": float(r_icp.rmse), "ransac_inliers": int(r_rs.inliers),
                              "ransac_iterations_run": int(r_rs.iterations_run)},
         }
+        if args.full:
+            # the roofline of the timed region's two kernels, with the supplementary runs above beside it
+            pairs = float(n) * float(n)
+            nn_avg_ms = nn_ms / max(nn_launches, 1)
+            sc_avg_ms = sc_ms / max(sc_launches, 1)
+            bf_avg_ms = bf_ms / max(bf_launches, 1)
+            hyps_total = float(steps_timed) * HYPS_PER_STEP
+            pruned_default = icp_search_used in ("pruned", "grid")
+            # HBM traffic per launch from the PMC passes (rocprofv3 --pmc cannot run inside this process): taken from the
+            # committed summary of the same command when it covers this workload, else null
+            pm = None
+            try:
+                for pm_round in ("r4", "r3", "r2"):
+                    pm_path = os.path.join(ROOT, "profiles", pm_round, "pmc_summary.json")
+                    if os.path.exists(pm_path):
+                        break
+                pm = json.load(open(pm_path))
+                if not (pm["workload"]["n_src"] == n and pm["workload"]["n_tgt"] == n):
+                    pm = None
+            except Exception:
+                pm = None
+
+            def traffic(kernel):
+                try:
+                    return pm["kernels"]["tdv::" + kernel]["hbm_bytes_per_launch"]
+                except Exception:
+                    return None
+
+            # Scoring kernel of the timed region.  Reference arithmetic (k_ransac_score): per hypothesis-point 18 ops transform +
+            # 3 sub + 5 squared norm + 1 compare + 1 count = 28 VALU lane-ops (issued as packed f32 pairs).  Default
+            # (k_ransac_score_fast): 16.6 lane-ops per hypothesis-point in the FMA pass (per 8 points 60 packed instructions -
+            # 48 fma, 12 add - and 13 scalar-f32 ones) + 28 for every test scored again exactly: a wave re-scores the PAIR of points that
+            # one of its 64 hypotheses has inside its rounding band (round 4; the whole 8-point chunk until then)
+            # (rescore_share, counted by the kernel).  An FMA is ONE lane-op here, as in the peak (lane-instructions, not flops).
+            # Algorithmic HBM bytes per launch: the packed pairs once (24 B per point) + 48 B per hypothesis in, 4 B out.
+            # A "launch" is one dispatch of the scoring kernel (what rocprofv3's kernel statistics average over).  With the exact
+            # bail-out a batch of hypotheses is two dispatches: every hypothesis over a prefix of the points, then the hypotheses that
+            # can still beat the best count of the earlier batches over the rest - together they read the pair array once.
+            # (batching rule of csrc/ransac.hip: batches of 65,536 hypotheses, the first one 8,192 when the bail-out is on)
+            hyps_call = args.steps * HYPS_PER_STEP        # the timed region's one RANSAC call
+            bail = (os.environ.get("TDV_RANSAC_BAILOUT", "1") != "0") and hyps_call > 16384
+            sc_batches = (1 + -(-(hyps_call - 8192) // 65536)) if bail else max(1, -(-hyps_call // 65536))
+            sc_hyps_per_launch = hyps_total / max(sc_launches, 1)
+            fast = rescore_share >= 0.0
+            ops_per_test = (16.6 + 28.0 * rescore_share) if fast else 28.0
+            sc_tops = ops_per_test * scored_share * n * hyps_total / max(sc_ms * 1e-3, 1e-12) / 1e12
+            sc_bytes = (24.0 * n * sc_batches + 56.0 * hyps_total) / max(sc_launches, 1)
+            sc_kernel = "k_ransac_score_fast" if fast else "k_ransac_score"
+            score = {
+                "kernel": sc_kernel, "bound": "valu_f32",
+                "achieved": sc_tops, "peak": VALU_PEAK_TOPS,
+                "unit": ("T VALU lane-ops/s executed: %.1f per hypothesis-point = 16.6 in the FMA pass + 28 x the %.3f of the tests (whole waves on a pair of "
+                         "points) scored again with the reference arithmetic; same inlier counts as the 28-op reference arithmetic" % (ops_per_test, rescore_share))
+                        if fast else "Tops/s (f32 VALU, FMA contraction forbidden by parity; 28 ops per hypothesis-point)",
+                "frac": sc_tops / VALU_PEAK_TOPS, "avg_launch_ms": sc_avg_ms, "launches": sc_launches,
+                "hyps_per_launch": sc_hyps_per_launch, "batches": sc_batches, "total_ms": sc_ms,
+                "hbm": {"algorithmic_bytes_per_launch": sc_bytes, "achieved": sc_bytes / max(sc_avg_ms * 1e-3, 1e-12) / 1e9,
+                        "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": sc_bytes / max(sc_avg_ms * 1e-3, 1e-12) / 1e9 / HBM_PEAK_GBPS},
+                "traffic": traffic(sc_kernel),
+            }
+            full_ops = (16.6 + 28.0 * full_rescore) if full_rescore >= 0.0 else 28.0
+            score["every_test_scored"] = {
+                "note": "the same kernel with the bail-out off (a call that asks for the per-iteration trace): %d hypotheses x all %d points, one dispatch per batch" % (full_hyps, n),
+                "hyps_per_s": full_hyps / t_full, "avg_launch_ms": full_ms / max(full_launches, 1), "launches": full_launches,
+                "scored_share": full_scored, "achieved": full_ops * n * full_hyps / max(full_ms * 1e-3, 1e-12) / 1e12, "peak": VALU_PEAK_TOPS,
+                "frac": full_ops * n * full_hyps / max(full_ms * 1e-3, 1e-12) / 1e12 / VALU_PEAK_TOPS,
+                "best_inliers": int(r_full.inliers), "best_iteration": int(r_full.best_iteration)}
+            if fast:
+                score["rescore_share"] = rescore_share
+                score["scored_share"] = scored_share
+                score["note"] = ("%.3f of the hypothesis-point tests were evaluated: a hypothesis whose count over a prefix of the points plus all remaining points "
+                                 "cannot exceed the best count of the earlier batches is not scored further (exact: same best hypothesis, count, "
+                                 "fitness, rmse); `achieved` counts executed lane-ops only" % scored_share)
+                score["reference_arithmetic_equivalent_tops"] = 28.0 * n * hyps_total / max(sc_ms * 1e-3, 1e-12) / 1e12
+            # NN search of the timed region.  Algorithmic HBM bytes of one ICP iteration: 12*N_s + 24*N_t + 124
+            icp_bytes = 12.0 * n + 24.0 * n + 124
+            nn_kernel = {"grid": "k_icp_nn_grid", "pruned": "k_icp_nn_pruned"}.get(icp_search_used, "k_icp_nn_scan")
+            nn_equiv = 8.0 * pairs / max(nn_avg_ms * 1e-3, 1e-12) / 1e12
+            nn = {
+                "kernel": nn_kernel, "avg_launch_ms": nn_avg_ms, "launches": nn_launches, "total_ms": nn_ms,
+                "hbm": {"algorithmic_bytes_per_launch": icp_bytes, "achieved": icp_bytes / max(nn_avg_ms * 1e-3, 1e-12) / 1e9,
+                        "peak": HBM_PEAK_GBPS, "unit": "GB/s", "frac": icp_bytes / max(nn_avg_ms * 1e-3, 1e-12) / 1e9 / HBM_PEAK_GBPS},
+                "traffic": traffic(nn_kernel),
+            }
+            if icp_search_used == "grid":
+                nn.update({"bound": "latency (hash-grid probes: 8 table entries + the points of the occupied cells per source point)",
+                           "search": "grid", "bruteforce_equivalent_tops": nn_equiv,
+                           "note": "exact hash-grid search (cells of 2.2 x the acceptance threshold, one lane per source point): identical "
+                                   "correspondences to the scan; no VALU roofline fraction is claimed for it"})
+            elif pruned_default:
+                nn.update({"bound": "latency (box walk: few pairs evaluated)", "search": "pruned", "bruteforce_equivalent_tops": nn_equiv,
+                           "note": "exact pruned search: evaluates only boxes that can hold a neighbour within the bound, so the "
+                                   "brute-force pair count / time exceeds the VALU peak; no VALU roofline fraction is claimed for it"})
+            else:
+                nn.update({"bound": "valu_f32", "achieved": nn_equiv, "peak": VALU_PEAK_TOPS, "frac": nn_equiv / VALU_PEAK_TOPS})
+            # brute-force scan (3 sub + 3 mul + 2 add per pair = 8 VALU ops), supplementary
+            bf_tops = 8.0 * pairs / max(bf_avg_ms * 1e-3, 1e-12) / 1e12
+            brute = {
+                "kernel": "k_icp_nn_scan", "bound": "valu_f32", "achieved": bf_tops, "peak": VALU_PEAK_TOPS,
+                "unit": "Tops/s (8 ops per pair)", "frac": bf_tops / VALU_PEAK_TOPS, "avg_launch_ms": bf_avg_ms, "launches": bf_launches,
+                "traffic": traffic("k_icp_nn_scan"),
+                "note": "reference-algorithm scan, timed after the K steps (TDV_ICP_SEARCH=brute makes it the default)",
+            }
+            dominant, other = (score, nn) if sc_ms >= nn_ms else (nn, score)
+            roofline = dict(dominant)
+            roofline["traffic_unit"] = "HBM bytes per launch (FETCH_SIZE + WRITE_SIZE, mean over the dispatches of the same command)"
+            roofline["traffic_source"] = ("FROM A COMMITTED PROFILE, not measured by this run: profiles/%s/pmc_summary.json (separate rocprofv3 --pmc FETCH_SIZE / "
+                                          "WRITE_SIZE passes of this command on the builder's box; PMC counters cannot be read from inside the benchmarked process)" % pm_round) \
+                if roofline.get("traffic") is not None else None
+            roofline["second_kernel"] = other
+            roofline["icp_nn_bruteforce_scan"] = brute
+            # BASELINE.json's metric, flat, in the dict the driver keeps: hypotheses/s and iterations/s at 200k points (whole job), each from
+            # its own synchronized sub-region of the timed steps; beside them the figures the docs promise next to every headline number
+            roofline.update({
+                "ransac_hyps_per_s": hyps_per_s, "icp_iters_per_s": iters_per_s,
+                "ransac_hyps_per_s_every_test_scored": full_hyps / t_full,
+                "icp_iters_per_s_bruteforce_scan": bf_iters_per_s,
+                "icp_iters_per_s_reference_order_sums": ref_iters_per_s,
+                "icp_search": icp_search_used,
+                "target_ransac_hyps_per_s": 1e6, "target_icp_iters_per_s": 50,
+                "hbm_algorithmic_bytes_per_launch": score["hbm"]["algorithmic_bytes_per_launch"] if dominant is score else nn["hbm"]["algorithmic_bytes_per_launch"],
+                "hbm_achieved_GBps": dominant["hbm"]["achieved"], "hbm_frac": dominant["hbm"]["frac"],
+                "every_test_scored_frac": score["every_test_scored"]["frac"], "every_test_scored_avg_launch_ms": score["every_test_scored"]["avg_launch_ms"],
+                "bruteforce_scan_frac": brute["frac"], "bruteforce_scan_avg_launch_ms": brute["avg_launch_ms"],
+                "second_kernel_name": other["kernel"], "second_kernel_avg_launch_ms": other["avg_launch_ms"],
+            })
+            out.update({"icp_iters_per_s_bruteforce_scan": bf_iters_per_s, "icp_iters_per_s_reference_order_sums": ref_iters_per_s,
+                        "roofline": roofline})
         if c5_error is not None:
             out["config"]["c5_error"] = c5_error[:120]
             out["c5_error"] = c5_error
@@ -517,7 +528,7 @@ def main():
             out["c5"] = c5_out
             out["config"].update({"c5_instances_per_s": c5_out["instances_per_s"], "c5_instances": c5_out["instances"], "c5_model_bcast_ms": c5_out["model_bcast_ms"],
                                   "c5_gather_ms": c5_out["gather_ms"], "c5_registered_share": c5_out["registered_share"], "c5_collectives": c5_out["collectives"]})
-        if not args.no_operators and world == 1:
+        if args.full and not args.no_operators and world == 1:
             # every other stage of the path, measured after the timed region (outside `value`): median of 3 repetitions each
             sys.path.insert(0, os.path.join(ROOT, "tools"))
             import opbench
@@ -530,7 +541,7 @@ def main():
                 if row.get("op") == "register_batch_c5": out["config"]["c5_one_rank_instances_per_s"] = row.get("instances_per_s")
                 if row.get("op", "").startswith("register_batch") and "instances_per_s" in row and "c4" in json.dumps(row.get("workload", "")).lower():
                     out["config"].setdefault("c4_instances_per_s", row.get("instances_per_s"))
-        if not args.no_cpu_baseline and world == 1:   # the CPU baseline is a single-GPU-run item (rank 0, N = 1)
+        if args.full and not args.no_cpu_baseline and world == 1:   # the CPU baseline is a single-GPU-run item (rank 0, N = 1)
             from oracle import pyoracle as orc
             out["cpu_baseline"] = cpu_baseline(orc, src_np, model[:, :3].cpu().numpy(), model[:, 3:6].cpu().numpy(), corr_np, T0, icp_thr, voxel, args.cpu_budget_s)
             out["cpu_baseline"]["host_cores_available"] = os.cpu_count()

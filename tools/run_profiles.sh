@@ -7,9 +7,9 @@ ROUND="${TDV_ROUND:-r4}"
 R="$GRAFT_REPO_ROOT"; O="$R/gpurun_out/${ROUND}prof"
 [ -f "$R/bench.py" ] || { echo "no bench.py under $R" >&2; exit 1; }
 rm -rf "$O"; mkdir -p "$O"
-python3 $R/bench.py > $O/bench.json 2> $O/bench.err
+python3 $R/bench.py --full > $O/bench.json 2> $O/bench.err
 cd /tmp && export TMPDIR=/tmp
-B="python3 $R/bench.py --no-cpu-baseline --no-operators"
+B="python3 $R/bench.py --full --no-cpu-baseline --no-operators"
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_bench -- $B > $O/bench_under_rocprof.json 2> $O/kt_bench.err
 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/pmc_fetch_bench -- $B > /dev/null 2> $O/pmc_fetch_bench.err
 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/pmc_write_bench -- $B > /dev/null 2> $O/pmc_write_bench.err
@@ -33,7 +33,7 @@ rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_icpref -- python3 
 # fold the PMC passes here (the per-dispatch counter tables are hundreds of MB with the 256- and 1,024-instance batches in the run;
 # gpurun copies back at most 64 MiB), then keep only statistics and summaries
 nf() { ls -t $O/$1/*/*$2 2>/dev/null | head -1; }
-N1="rocprofv3 --pmc passes, one counter group per pass, no tracing combined; means over every dispatch of the command. Command: python3 bench.py --no-cpu-baseline --no-operators (100 steps + 5 warm-up at 200k x 200k)."
+N1="rocprofv3 --pmc passes, one counter group per pass, no tracing combined; means over every dispatch of the command. Command: python3 bench.py --full --no-cpu-baseline --no-operators (100 steps + 5 warm-up at 200k x 200k)."
 N2="rocprofv3 --pmc passes, one counter group per pass, no tracing combined; means over every dispatch of the command. Command: python3 tools/bench_ops.py (every operator of tools/opbench.py: each kernel is dispatched several times)."
 python3 $R/tools/summarize_pmc.py --out $O/pmc_summary.json --n 200000 --note "$N1" $(nf pmc_fetch_bench counter_collection.csv) $(nf pmc_write_bench counter_collection.csv) || echo "pmc fold (bench) failed" >> $O/notes.txt
 python3 $R/tools/summarize_pmc.py --out $O/pmc_ops_summary.json --n 200000 --note "$N2" $(nf pmc_fetch_ops counter_collection.csv) $(nf pmc_write_ops counter_collection.csv) $(nf pmc_sq_ops counter_collection.csv) || echo "pmc fold (ops) failed" >> $O/notes.txt
