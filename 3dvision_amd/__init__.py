@@ -56,6 +56,7 @@ ABI_SYMBOLS = [
     "tdv_depth_to_cloud_batch_dev", "tdv_broadcast_model", "tdv_gather_results", "tdv_mask_resize_nearest", "tdv_mask_resize_nearest_dev", "tdv_voxel_downsample_batch_dev", "tdv_voxel_downsample_batch_pinhole_dev",
     "tdv_icp_batch_dev", "tdv_refine_batch_dev", "tdv_ctx_set_icp_loss", "tdv_ctx_get_icp_loss",
     "tdv_gicp", "tdv_gicp_dev", "tdv_gicp_batch_dev",
+    "tdv_color_gradients", "tdv_color_gradients_dev", "tdv_colored_icp", "tdv_colored_icp_dev", "tdv_colored_icp_batch_dev",
 ]
 
 
@@ -509,6 +510,74 @@ class Context:
         d_tn = torch.from_numpy(tn if len(tn) else np.zeros((1, 3), np.float32)).to(dev)
         return self.gicp_batch_dev(d_src.data_ptr(), d_sn.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), len(tgt), T0s, thr,
                                    max_iterations, epsilon)
+
+    # ---------------------------------------------------------------- colored ICP (include/tdv_hip.h: tdv_colored_icp)
+    def color_gradients(self, xyz, rgb, normals, k=30):
+        """(n, 4) float32 per point: intensity I and its gradient d on the tangent plane, from the k nearest neighbours."""
+        xyz = _f32(xyz); rgb = _f32(rgb); nrm = _f32(normals); n = len(xyz)
+        out = np.empty((n, 4), np.float32)
+        _check(self._h, lib().tdv_color_gradients(self._h, _ptr(xyz), _ptr(rgb), _ptr(nrm), n, k, _ptr(out)), "tdv_color_gradients")
+        return out
+
+    def color_gradients_dev(self, d_xyz, d_rgb, d_normals, n, k, d_color, d_knn=None):
+        """d_knn (optional): estimate_normals_dev's list for the same cloud and k; None runs that search."""
+        _check(self._h, lib().tdv_color_gradients_dev(self._h, _ptr(d_xyz), _ptr(d_rgb), _ptr(d_normals), n, k, _ptr(d_knn), _ptr(d_color)),
+               "tdv_color_gradients_dev")
+
+    def colored_icp(self, src, src_rgb, tgt, tgt_normals, tgt_color, T0, thr, max_iterations=200, lambda_geometric=0.968):
+        """Point-to-plane plus photometric ICP; tgt_color = color_gradients of the target.  The result as icp's."""
+        src = _f32(src); rgb = _f32(src_rgb); tgt = _f32(tgt); tn = _f32(tgt_normals); tc = _f32(tgt_color)
+        res = IcpResultC()
+        t0 = to_colmajor16(T0)
+        _check(self._h, lib().tdv_colored_icp(self._h, _ptr(src), _ptr(rgb), len(src), _ptr(tgt), _ptr(tn), _ptr(tc), len(tgt), _ptr(t0),
+                                              C.c_float(thr), max_iterations, C.c_float(lambda_geometric), C.byref(res)), "tdv_colored_icp")
+        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
+                                  iterations=res.iterations, n_corr=res.n_corr)
+
+    def colored_icp_dev(self, d_src, d_src_rgb, ns, d_tgt, d_tgt_normals, d_tgt_color, nt, T0, thr, max_iterations, lambda_geometric=0.968,
+                        fixed_iterations=False):
+        res = IcpResultC()
+        t0 = to_colmajor16(T0)
+        _check(self._h, lib().tdv_colored_icp_dev(self._h, _ptr(d_src), _ptr(d_src_rgb), ns, _ptr(d_tgt), _ptr(d_tgt_normals), _ptr(d_tgt_color), nt,
+                                                  _ptr(t0), C.c_float(thr), max_iterations, C.c_float(lambda_geometric), int(fixed_iterations),
+                                                  C.byref(res)), "tdv_colored_icp_dev")
+        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
+                                  iterations=res.iterations, n_corr=res.n_corr)
+
+    def colored_icp_batch_dev(self, d_src, d_src_rgb, offsets, d_tgt, d_tgt_normals, d_tgt_color, nt, T0s, thr, max_iterations,
+                              lambda_geometric=0.968, fixed_iterations=False):
+        """Colored ICP of many clouds against one target in one call (device pointers; the source colours laid out like d_src).  Per
+        instance what colored_icp_dev returns for that cloud, bit for bit."""
+        off = np.ascontiguousarray(offsets, np.int32)
+        n = len(off) - 1
+        T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
+        t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
+        res = (IcpResultC * max(n, 1))()
+        _check(self._h, lib().tdv_colored_icp_batch_dev(self._h, _ptr(d_src), _ptr(d_src_rgb), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals),
+                                                        _ptr(d_tgt_color), nt, _ptr(t0), C.c_float(thr), max_iterations,
+                                                        C.c_float(lambda_geometric), int(fixed_iterations), res), "tdv_colored_icp_batch_dev")
+        return [RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
+                                   iterations=r.iterations, n_corr=r.n_corr) for r in res[:n]]
+
+    def colored_icp_batch(self, sources, source_rgbs, tgt, tgt_normals, tgt_color, T0s, thr, max_iterations=200, lambda_geometric=0.968):
+        """colored_icp_batch_dev on host clouds: lists of (n_b, 3) points and colours against one target, uploaded with torch."""
+        import torch
+        dev = torch.device("cuda", self.device)
+        srcs = [_f32(a).reshape(-1, 3) for a in sources]
+        rgbs = [_f32(a).reshape(-1, 3) for a in source_rgbs]
+        if [len(a) for a in rgbs] != [len(a) for a in srcs]:
+            raise ValueError("colored_icp_batch: one colour per source point")
+        off = np.zeros(len(srcs) + 1, np.int32)
+        off[1:] = np.cumsum([len(a) for a in srcs])
+        cat = np.concatenate(srcs) if srcs and off[-1] else np.zeros((1, 3), np.float32)
+        catc = np.concatenate(rgbs) if rgbs and off[-1] else np.zeros((1, 3), np.float32)
+        tgt = _f32(tgt); tn = _f32(tgt_normals); tc = _f32(tgt_color).reshape(-1, 4)
+        d_src = torch.from_numpy(cat).to(dev); d_rgb = torch.from_numpy(catc).to(dev)
+        d_tgt = torch.from_numpy(tgt if len(tgt) else np.zeros((1, 3), np.float32)).to(dev)
+        d_tn = torch.from_numpy(tn if len(tn) else np.zeros((1, 3), np.float32)).to(dev)
+        d_tc = torch.from_numpy(tc if len(tc) else np.zeros((1, 4), np.float32)).to(dev)
+        return self.colored_icp_batch_dev(d_src.data_ptr(), d_rgb.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), d_tc.data_ptr(), len(tgt),
+                                          T0s, thr, max_iterations, lambda_geometric)
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

@@ -3,6 +3,7 @@
 // dispatch layer /root/reference/src/gpu_impl.cpp (per-call cudaMalloc/cudaMemcpy/launch/cudaFree)
 // with arena-backed staging on one stream per ctx.
 #include "tdv_internal.hpp"
+#include <cmath>
 #include <cstring>
 #include <algorithm>
 #include <vector>
@@ -357,6 +358,75 @@ int tdv_gicp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_norm
     for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
     TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
                               1, fixed_iterations, out, IcpGicp{d_src_normals, 1.f - epsilon}));
+    return finish(ctx);
+}
+// ---- colored ICP: the target's colour gradients (color.hip), then tdv_icp / tdv_icp_dev / tdv_icp_batch_dev with the source colours
+// and the target's colour table, point-to-plane plus photometric terms (icp.hip, MODE 4)
+int tdv_color_gradients(tdv_ctx* ctx, const float* xyz, const float* rgb, const float* normals, int n, int k, float* out_color) {
+    if (n < 0 || k <= 0 || k > 255 || (n > 0 && (!xyz || !rgb || !normals || !out_color))) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    if (n == 0) return TDV_OK;
+    float *d_xyz, *d_rgb, *d_nrm, *d_color;
+    TDV_TRY(upload(ctx, xyz, (size_t)n * 3, &d_xyz));
+    TDV_TRY(upload(ctx, rgb, (size_t)n * 3, &d_rgb));
+    TDV_TRY(upload(ctx, normals, (size_t)n * 3, &d_nrm));
+    TDV_TRY(ws_alloc(ctx, (size_t)n * 4, &d_color));
+    TDV_TRY(color_gradients_dev(ctx, d_xyz, d_rgb, d_nrm, n, k, nullptr, d_color));
+    TDV_TRY(download(ctx, out_color, d_color, (size_t)n * 4));
+    return finish(ctx);
+}
+int tdv_color_gradients_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, const float* d_normals, int n, int k, const int* d_knn,
+                            float* d_color) {
+    if (n < 0 || k <= 0 || k > 255 || (n > 0 && (!d_xyz || !d_rgb || !d_normals || !d_color))) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    TDV_TRY(color_gradients_dev(ctx, d_xyz, d_rgb, d_normals, n, k, d_knn, d_color));
+    return finish(ctx);
+}
+int tdv_colored_icp(tdv_ctx* ctx, const float* src, const float* src_rgb, int ns, const float* tgt, const float* tgt_normals,
+                    const float* tgt_color, int nt, const float* T0, float distance_threshold, int max_iterations, float lambda_geometric,
+                    tdv_icp_result* out) {
+    if (!out || !T0 || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tgt)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    TDV_TRY(colored_check(ctx, src_rgb, tgt_normals, tgt_color, lambda_geometric, false));   // (reference-order sums refused: no loss check needed)
+    float *d_src, *d_rgb, *d_tgt, *d_tn, *d_tc;
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    TDV_TRY(upload(ctx, src_rgb, (size_t)ns * 3, &d_rgb));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
+    TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_tn));
+    TDV_TRY(upload(ctx, tgt_color, (size_t)nt * 4, &d_tc));
+    if (ns == 0 || nt == 0) {
+        std::memcpy(out->T, T0, 64); out->fitness = 0.f; out->rmse = 0.f; out->iterations = 0; out->n_corr = 0;
+        return TDV_OK;
+    }
+    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tn, nt, T0, distance_threshold, max_iterations, 1, 0, out, nullptr, nullptr, IcpGicp{nullptr, 0.f},
+                       IcpColor{d_rgb, d_tc, sqrtf(lambda_geometric), sqrtf(1.f - lambda_geometric)});
+}
+int tdv_colored_icp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_rgb, int ns, const float* d_tgt, const float* d_tgt_normals,
+                        const float* d_tgt_color, int nt, const float* T0, float distance_threshold, int max_iterations,
+                        float lambda_geometric, int fixed_iterations, tdv_icp_result* out) {
+    TDV_TRY(begin(ctx));
+    TDV_TRY(colored_check(ctx, d_src_rgb, d_tgt_normals, d_tgt_color, lambda_geometric, true));
+    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, 1, fixed_iterations, out, nullptr, nullptr,
+                       IcpGicp{nullptr, 0.f}, IcpColor{d_src_rgb, d_tgt_color, sqrtf(lambda_geometric), sqrtf(1.f - lambda_geometric)});
+}
+int tdv_colored_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_rgb, const int* h_src_offsets, int n_instances,
+                              const float* d_tgt, const float* d_tgt_normals, const float* d_tgt_color, int nt, const float* h_T0,
+                              float distance_threshold, int max_iterations, float lambda_geometric, int fixed_iterations, tdv_icp_result* out) {
+    // every argument before anything is enqueued or written (tdv_icp_batch_dev's, then colored ICP's)
+    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
+    if (n_instances > 0) {
+        if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
+        for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
+        if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
+    }
+    TDV_TRY(begin(ctx));
+    TDV_TRY(colored_check(ctx, d_src_rgb, d_tgt_normals, d_tgt_color, lambda_geometric, true));
+    if (n_instances == 0) return TDV_OK;
+    std::vector<int> count((size_t)n_instances);
+    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
+    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                              1, fixed_iterations, out, IcpGicp{nullptr, 0.f},
+                              IcpColor{d_src_rgb, d_tgt_color, sqrtf(lambda_geometric), sqrtf(1.f - lambda_geometric)}));
     return finish(ctx);
 }
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,

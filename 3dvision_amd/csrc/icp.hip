@@ -37,6 +37,9 @@
 //  * generalized ICP (tdv_gicp, MODE 3): plane-to-plane terms from both clouds' normals in acc_terms, the same 6x6 system, slab layout
 //    and solve as point-to-plane.  Its extra kernel arguments (the source normals, c = 1 - epsilon) arrive as a trailing parameter pack
 //    that is empty for the other modes, so that their kernels keep their arguments and their code.
+//  * colored ICP (tdv_colored_icp, MODE 4): point-to-plane's row plus a photometric row on the target's tangent plane in acc_terms, the
+//    same 6x6 system and slab layout.  Its extra arguments (source colours, the target's colour table, lg, lc) come in the same
+//    trailing pack as one IcpColor.
 // No float atomics anywhere: two runs give identical bits.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
@@ -452,23 +455,24 @@ __device__ __forceinline__ double wave_sum(double v) {
 // MEANS (already divided, registration.cpp:380-381) and tot[8..16] the centred cross-covariance of :383-386.
 // ROBUST (weighted sums, acc_terms): tot[acc_nv - 1] counts the correspondences of weight > 0, and point-to-point divides by the
 // weight sum tot[17] instead of n_corr.
-// MODE 3 (GICP) solves its system as point-to-plane does.
+// MODE 3 (GICP) and MODE 4 (colored ICP) solve their systems as point-to-plane does.
 template <int MODE, bool REF = false, bool ROBUST = false>
 __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_iterations, int iter, float prev_rmse, const float* Tcur, float* solve_ws /* LDS, 54 words */) {
     static_assert(!(REF && ROBUST), "reference-order sums have no loss");
     static_assert(!(REF && MODE == 3), "reference-order sums have no GICP");
+    static_assert(!(REF && MODE == 4), "reference-order sums have no colored ICP");
     const int n_corr = (int)(tot[0] + 0.5);
     st->iter = iter + 1;
     st->n_corr = n_corr;
     if (n_corr < 3 ||  // registration.cpp:361 — break, keeping the previous result
-        (ROBUST && (int)(tot[(MODE == 0 || MODE == 3) ? 29 : 18] + 0.5) < 3)) {   // (the same break when fewer than 3 have a weight: Tukey beyond its scale)
+        (ROBUST && (int)(tot[(MODE == 0 || MODE >= 3) ? 29 : 18] + 0.5) < 3)) {   // (the same break when fewer than 3 have a weight: Tukey beyond its scale)
         if (!fixed_iterations) st->done = 1;
         return;
     }
     float delta[16];
     for (int i = 0; i < 16; ++i) delta[i] = 0.f;
     delta[0] = delta[5] = delta[10] = delta[15] = 1.f;
-    if (MODE == 0 || MODE == 3) {
+    if (MODE == 0 || MODE >= 3) {
         float ATA[36], nb[6], x[6];
         int k = 2;
         for (int a = 0; a < 6; ++a)
@@ -509,10 +513,11 @@ __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_it
 // The pieces of one accumulation launch, shared by k_icp_accumulate (one problem) and k_icp_accumulate_multi (one problem per
 // instance of a batch): the sums of one accepted correspondence, the block's slab and the fold of the last block, the update.
 // MODE 0: point-to-plane (21 upper-triangular JtJ + 6 Jtr), MODE 1: point-to-point moments, MODE 2: count / error only, MODE 3: GICP
-// (21 upper-triangular JtMJ + 6 JtMe, point-to-plane's slots).  ROBUST: + n_eff (correspondences of weight > 0) last, point-to-point
+// (21 upper-triangular JtMJ + 6 JtMe, point-to-plane's slots), MODE 4: colored ICP (point-to-plane's slots, two rows per
+// correspondence).  ROBUST: + n_eff (correspondences of weight > 0) last, point-to-point
 // the weight sum W before it.
 template <int MODE, bool ROBUST = false>
-constexpr int acc_nv() { return (MODE == 0 || MODE == 3) ? (ROBUST ? 30 : 29) : (MODE == 1 ? (ROBUST ? 19 : 17) : 2); }
+constexpr int acc_nv() { return (MODE == 0 || MODE >= 3) ? (ROBUST ? 30 : 29) : (MODE == 1 ? (ROBUST ? 19 : 17) : 2); }
 
 // the pose a launch reads at its start: the 3x4 part column by column, and the bottom row
 __device__ __forceinline__ void acc_load_pose(const IcpState* st, float* T /* 12 */, float* Tb /* 4 */) {
@@ -544,6 +549,19 @@ struct GicpPt { float ax, ay, az, c; };
 // The kernels' GICP arguments from their trailing parameter pack: empty (no GICP) or one IcpGicp
 __device__ __forceinline__ IcpGicp gicp_of() { return IcpGicp{nullptr, 0.f}; }
 __device__ __forceinline__ IcpGicp gicp_of(IcpGicp g) { return g; }
+__device__ __forceinline__ IcpGicp gicp_of(IcpColor) { return IcpGicp{nullptr, 0.f}; }
+
+// Colored ICP's per-correspondence input besides p and the target: the target's colour table (float4 (I, d) per point), the source
+// point's intensity Is = ((r + g) + b) / 3.0f, lg = sqrtf(lambda), lc = sqrtf(1 - lambda) (unused by the other modes)
+struct ColorPt { const float* tgt_color; float Is, lg, lc; };
+__device__ __forceinline__ IcpColor color_of() { return IcpColor{nullptr, nullptr, 0.f, 0.f}; }
+__device__ __forceinline__ IcpColor color_of(IcpGicp) { return IcpColor{nullptr, nullptr, 0.f, 0.f}; }
+__device__ __forceinline__ IcpColor color_of(IcpColor c) { return c; }
+// source point i (index into the colours laid out like the source points)
+__device__ __forceinline__ ColorPt color_pt(const IcpColor& c, size_t i) {
+    const float* __restrict__ rgb = c.src_rgb + 3 * i;
+    return ColorPt{c.tgt_color, ((rgb[0] + rgb[1]) + rgb[2]) / 3.0f, c.lg, c.lc};
+}
 
 // One accepted correspondence, source point p (transformed) paired with target idx, in the float steps of registration.cpp: its
 // target q and, point-to-plane, J = [p x n | n] (:346-349) and r = (p - q) . n (:351).  Every path's sums and records are built
@@ -566,15 +584,50 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // slab row: 0.0 + -0.0 is +0.0); each term is put as it is formed.
 // MODE 3 (GICP): the 21 + 6 terms of include/tdv_hip.h (tdv_gicp) from p, the target point and normal and G, each formed in float in
 // the header's order and widened.
+// MODE 4 (colored ICP): the 21 + 6 terms of include/tdv_hip.h (tdv_colored_icp) from p, the target point and normal and C: per slot
+// (double)(JG[a] * JG[b]) + (double)(JC[a] * JC[b]), resp. * rG and * rC, each product formed in float.  ROBUST: each row weighted
+// by its own residual, (double)wG * (JG product) + (double)wC * (JC product), n_eff = (wG > 0 || wC > 0).
 // ROBUST: the weight w = loss_weight(L, e) of this correspondence (e = r point-to-plane, sqrtf(d2) point-to-point, GICP the
 // Mahalanobis residual sqrtf(fmaxf(0, e . g))) scales every term after the first two: (double)w * term, exact for the f32 products of
 // point-to-plane and GICP and for p and q; w * (P[a] * Q[b]) is rounded once.  Then point-to-point W = w, and last n_eff = (w > 0).
 // {1, d2} stay unweighted: n_corr, rmse and fitness are L2's.
 template <int MODE, bool ROBUST = false, class Put>
 __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
-                                          IcpLoss L, GicpPt G, Put put) {
+                                          IcpLoss L, GicpPt G, ColorPt C, Put put) {
     put(0, 1.0); put(1, (double)d2);
     if (MODE == 2) return;
+    if (MODE == 4) {
+        float q[3], J[6], en;
+        corr_terms<0>(px, py, pz, idx, tgt, tgt_normals, q, J, en);     // J = [p x n | n], en = (p - q) . n
+        const float nx = J[3], ny = J[4], nz = J[5];
+        const float4 tc = reinterpret_cast<const float4*>(C.tgt_color)[idx];   // (Iq, d)
+        const float lg = C.lg, lc = C.lc;
+        // e_t = e - en n, the source point's offset projected on the target's tangent plane; g = (d . n) n - d = -m
+        const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
+        const float etx = ex - en * nx, ety = ey - en * ny, etz = ez - en * nz;
+        const float dn = tc.y * nx + (tc.z * ny + tc.w * nz);
+        const float gx = dn * nx - tc.y, gy = dn * ny - tc.z, gz = dn * nz - tc.w;
+        const float de = tc.y * etx + (tc.z * ety + tc.w * etz);
+        const float rG = lg * en, rC = lc * (C.Is - (tc.x + de));
+        float JG[6], JC[6];
+#pragma unroll
+        for (int a = 0; a < 6; ++a) JG[a] = lg * J[a];
+        JC[0] = lc * (py * gz - pz * gy); JC[1] = lc * (pz * gx - px * gz); JC[2] = lc * (px * gy - py * gx);
+        JC[3] = lc * gx; JC[4] = lc * gy; JC[5] = lc * gz;
+        float wG = 1.f, wC = 1.f;
+        if (ROBUST) { wG = loss_weight(L, rG); wC = loss_weight(L, rC); }
+        const double wGd = wG, wCd = wC;
+        const auto term = [&](float g, float c) { return ROBUST ? wGd * (double)g + wCd * (double)c : (double)g + (double)c; };
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) put(k++, term(JG[a] * JG[b], JC[a] * JC[b]));
+#pragma unroll
+        for (int a = 0; a < 6; ++a) put(k++, term(JG[a] * rG, JC[a] * rC));
+        if (ROBUST) put(29, (wG > 0.f || wC > 0.f) ? 1.0 : 0.0);
+        return;
+    }
     if (MODE == 3) {
         const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
         const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
@@ -646,8 +699,9 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
 // this lane's sums += one accepted correspondence (p, target idx at squared distance best)
 template <int MODE, bool ROBUST = false>
 __device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
-                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L, GicpPt G = GicpPt{}) {
-    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, G, [v](int k, double t) { v[k] += t; });
+                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L, GicpPt G = GicpPt{},
+                                        ColorPt C = ColorPt{}) {
+    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, G, C, [v](int k, double t) { v[k] += t; });
 }
 
 // LDS of one accumulation block
@@ -746,7 +800,7 @@ __device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const 
 
 // One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
 // slabs in a fixed order, solves, and updates the state on the device.
-// (Gicp: one IcpGicp for MODE 3, empty otherwise)
+// (Gicp: one IcpGicp for MODE 3, one IcpColor for MODE 4, empty otherwise)
 template <int MODE, int ACC_PPT, bool ROBUST = false, class... Gicp>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
 __global__ __launch_bounds__(256)
 void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
@@ -756,9 +810,10 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       IcpState* st, float tau_accept, int fixed_iterations, IcpLoss loss,
                       double* slabs, unsigned* ticket,
                       int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc, Gicp... gicp_arg) {
-    static_assert((MODE == 3) == (sizeof...(Gicp) == 1), "GICP takes its arguments, the other modes none");
+    static_assert((MODE >= 3) == (sizeof...(Gicp) == 1), "GICP and colored ICP take their arguments, the other modes none");
     if (st->done) return;
     const IcpGicp gicp = gicp_of(gicp_arg...);
+    const IcpColor color = color_of(gicp_arg...);
     const int iter0 = st->iter; const float rmse0 = st->rmse;
     double v[ACC_NV];
 #pragma unroll
@@ -783,7 +838,9 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
             acc_rotate(T, gicp.src_normals[3 * i], gicp.src_normals[3 * i + 1], gicp.src_normals[3 * i + 2], G.ax, G.ay, G.az);
             G.c = gicp.c;
         }
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G);
+        ColorPt C{};
+        if (MODE == 4) C = color_pt(color, (size_t)i);
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G, C);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
@@ -828,7 +885,8 @@ void k_icp_nn_grid_multi(const float* __restrict__ src, const IcpInst* __restric
 
 // k_icp_accumulate for every instance: instance b's blocks write its slabs and take its ticket word tickets[b]; the last of them
 // folds, solves and updates st[b].  The points-per-thread count is uniform over a block (runtime loop, as the single kernel's).
-// (Gicp: one IcpGicp for MODE 3, its source normals laid out like src; empty otherwise)
+// (Gicp: one IcpGicp for MODE 3, its source normals laid out like src; one IcpColor for MODE 4, its source colours laid out like src;
+// empty otherwise)
 template <int MODE, bool ROBUST = false, class... Gicp>
 __global__ __launch_bounds__(256)
 void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __restrict__ inst, const int* __restrict__ blk_inst,
@@ -836,8 +894,9 @@ void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __rest
                             const float* __restrict__ pd2, const int* __restrict__ pidx,
                             IcpState* st_all, float tau_accept, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* tickets,
                             Gicp... gicp_arg) {
-    static_assert((MODE == 3) == (sizeof...(Gicp) == 1), "GICP takes its arguments, the other modes none");
+    static_assert((MODE >= 3) == (sizeof...(Gicp) == 1), "GICP and colored ICP take their arguments, the other modes none");
     const IcpGicp gicp = gicp_of(gicp_arg...);
+    const IcpColor color = color_of(gicp_arg...);
     const int b = blk_inst[blockIdx.x];
     IcpState* st = st_all + b;
     if (st->done) return;
@@ -866,7 +925,9 @@ void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __rest
             acc_rotate(T, sn[0], sn[1], sn[2], G.ax, G.ay, G.az);
             G.c = gicp.c;
         }
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G);
+        ColorPt C{};
+        if (MODE == 4) C = color_pt(color, (size_t)in.src_off + i);
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G, C);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
@@ -1115,15 +1176,17 @@ constexpr long long SM_MAX_PAIRS_BATCH = 1ll << 20;     // ... per problem of a 
 // A grid of several workgroups runs one problem each (the batch's small instances against the shared model): problem b takes the
 // source points [src_off[b], src_off[b + 1]) of src0 and the states st_in[b] / st_out[b]; src_off == nullptr: one problem.
 // 1,024 lanes and room for 2,048 x 2,048 points.
-// Gicp: one IcpGicp for MODE 3 (source normals laid out like src0), empty otherwise.
+// Gicp: one IcpGicp for MODE 3 (source normals laid out like src0), one IcpColor for MODE 4 (source colours laid out like src0), empty
+// otherwise.
 template <int MODE, bool REF, bool ROBUST = false, class... Gicp>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS; ROBUST: loss
 __global__ __launch_bounds__(SM_THREADS)
 void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict__ src_off, const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
                  const IcpState* __restrict__ st_in0, float tau_accept, int max_iterations, int fixed_iterations, IcpLoss loss,
                  IcpState* __restrict__ st_out0, IcpState* __restrict__ st_host, Gicp... gicp_arg) {
     static_assert(!(REF && ROBUST), "reference-order sums have no loss");
-    static_assert((MODE == 3) == (sizeof...(Gicp) == 1) && !(REF && MODE == 3), "GICP takes its arguments and tree sums, the other modes no arguments");
+    static_assert((MODE >= 3) == (sizeof...(Gicp) == 1) && !(REF && MODE >= 3), "GICP and colored ICP take their arguments and tree sums, the other modes no arguments");
     const IcpGicp gicp = gicp_of(gicp_arg...);
+    const IcpColor color = color_of(gicp_arg...);
     const int prob = blockIdx.x;
     const float* __restrict__ src = src_off ? src0 + (size_t)src_off[prob] * 3 : src0;
     const int ns = src_off ? src_off[prob + 1] - src_off[prob] : ns0;
@@ -1257,7 +1320,9 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
                     rotate_point(T, sn[0], sn[1], sn[2], G.ax, G.ay, G.az);
                     G.c = gicp.c;
                 }
-                if (best <= tau_accept) acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, G, [&v](int k, double t) { v[k] = t; });
+                ColorPt C{};
+                if (MODE == 4 && best <= tau_accept) C = color_pt(color, (src_off ? (size_t)src_off[prob] : 0) + i);
+                if (best <= tau_accept) acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, G, C, [&v](int k, double t) { v[k] = t; });
             }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -1401,11 +1466,18 @@ IcpLoss ctx_loss(const tdv_ctx* ctx) { return IcpLoss{ctx->icp_loss, ctx->icp_lo
 bool ctx_robust(const tdv_ctx* ctx) { return ctx->icp_loss != TDV_ICP_LOSS_L2; }
 
 // k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points), point-to-plane where normals are given, GICP where
-// gicp has source normals (gicp_check: tree sums), with the ctx's accumulation and loss (icp_loss_check: no loss with reference-order sums)
+// gicp has source normals (gicp_check: tree sums), colored ICP where color has source colours (colored_check: tree sums), with the ctx's
+// accumulation and loss (icp_loss_check: no loss with reference-order sums)
 void launch_icp_small(tdv_ctx* ctx, int n_prob, const float* d_src, int ns, const int* d_src_off, const float* d_tgt, const float* d_tgt_normals, int nt,
                       int point_to_plane, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host,
-                      IcpGicp gicp) {
+                      IcpGicp gicp, IcpColor color) {
     const bool p2pl = point_to_plane && d_tgt_normals, ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE, robust = ctx_robust(ctx);
+    if (color.src_rgb) {
+        const auto kernel = robust ? k_icp_small<4, false, true, IcpColor> : k_icp_small<4, false, false, IcpColor>;
+        kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations,
+                                                       ctx_loss(ctx), st_out, st_host, color);
+        return;
+    }
     if (gicp.src_normals) {
         const auto kernel = robust ? k_icp_small<3, false, true, IcpGicp> : k_icp_small<3, false, false, IcpGicp>;
         kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations,
@@ -1471,9 +1543,11 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
-                tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid, IcpGicp gicp) {
+                tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid, IcpGicp gicp, IcpColor color) {
     if (!ctx || !d_src || !d_tgt || !T0 || !out || ns < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
     if (gicp.src_normals && (!d_tgt_normals || ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE)) return TDV_ERR_BAD_ARG;   // (gicp_check's)
+    if (color.src_rgb && (!d_tgt_normals || !color.tgt_color || gicp.src_normals || ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE))
+        return TDV_ERR_BAD_ARG;                                                                                          // (colored_check's)
     TDV_HIP(ctx, hipSetDevice(ctx->device));
     result_defaults(T0, *out);
     if (max_iterations == 0) return TDV_OK;
@@ -1500,7 +1574,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
         TDV_HIP(ctx, hipMemcpyAsync(d_st, h, sizeof(IcpState), hipMemcpyHostToDevice, s));
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res, gicp);
+            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res, gicp, color);
         }
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipStreamSynchronize(s));
@@ -1565,6 +1639,15 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
 #else
             if (p.acc_ppt == 4) TDV_GACC1(4); else TDV_GACC1(1);
 #endif
+        } else if (color.src_rgb) {
+#define TDV_CACC1(PP) do { if (robust) TDV_CACC2(PP, true); else TDV_CACC2(PP, false); } while (0)
+#define TDV_CACC2(PP, RR) k_icp_accumulate<4, PP, RR, IcpColor><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, \
+                              p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr, color)
+#ifdef TDV_STUDY
+            if (p.acc_ppt == 8) TDV_CACC1(8); else if (p.acc_ppt == 4) TDV_CACC1(4); else if (p.acc_ppt == 2) TDV_CACC1(2); else TDV_CACC1(1);
+#else
+            if (p.acc_ppt == 4) TDV_CACC1(4); else TDV_CACC1(1);
+#endif
         } else if (p2pl) {
 #define TDV_ACC2(MM, PP, RR, NRM) k_icp_accumulate<MM, PP, RR><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, NRM, b.tx, b.ty, b.tz, \
                                p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr)
@@ -1593,7 +1676,7 @@ bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt) {
 // of d_src (each at most SM_MAX_N, as nt), start pose T0s[b] (host, column-major).  Results as icp_run_dev's, bit for bit (the same
 // kernel).  One upload, one launch, one download.
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp) {
+                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp, IcpColor color) {
     if (!ctx || !d_src || !d_src_off || !d_tgt || !T0s || !out || n_prob < 0 || nt <= 0 || nt > SM_MAX_N || max_iterations < 0) return TDV_ERR_BAD_ARG;
     if (n_prob == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
@@ -1609,7 +1692,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
         // (A quarter-size shape - 256 lanes, more problems resident at once - was measured against this one on C5's 1,024 instances in
         // round 3: 1.59 ms against 1.33 ms.  The pass lasts as long as its slowest problem and a lone workgroup iterates faster with
         // 16 waves; the variant is gone, profiles/r3/history keeps the numbers.)
-        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr, gicp);
+        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr, gicp, color);
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipMemcpyAsync(h, d_st + n_prob, (size_t)n_prob * sizeof(IcpState), hipMemcpyDeviceToHost, s));
     }
@@ -1626,7 +1709,8 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
 // states per burst.  Otherwise: small problems in one k_icp_small launch (icp_small_batch_dev), else icp_run_dev per instance with
 // the shared grid or Morton order.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
-                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out, IcpGicp gicp) {
+                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out, IcpGicp gicp,
+                      IcpColor color) {
     for (int b = 0; b < n; ++b) result_defaults(T0s + 16 * (size_t)b, out[b]);
     if (n == 0) return TDV_OK;
     int ns_max = 0, span = 0;
@@ -1647,7 +1731,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         int* d_off;
         TDV_TRY(ws_alloc(ctx, (size_t)n + 1, &d_off));
         TDV_HIP(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));   // (off outlives the call's sync)
-        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out, gicp);
+        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out, gicp, color);
     }
     // the target's hash grid at this threshold, once for the call (icp_run_dev uses a grid under AUTO or GRID)
     CellGrid cg{}; bool have_grid = false;
@@ -1667,8 +1751,10 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
             const WsMark mark = ws_mark(ctx);
             IcpGicp g = gicp;
             if (g.src_normals) g.src_normals += (size_t)h_start[b] * 3;
+            IcpColor c = color;
+            if (c.src_rgb) c.src_rgb += (size_t)h_start[b] * 3;
             TDV_TRY(icp_run_dev(ctx, d_src + (size_t)h_start[b] * 3, h_count[b], d_tgt, d_tgt_normals, nt, T0s + 16 * (size_t)b, thr, max_iterations,
-                                point_to_plane, fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr, g));
+                                point_to_plane, fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr, g, c));
             ws_rewind(ctx, mark);
         }
         return TDV_OK;
@@ -1729,6 +1815,11 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
             acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets, gicp);
             return;
         }
+        if (color.src_rgb) {
+            const auto acc = robust ? k_icp_accumulate_multi<4, true, IcpColor> : k_icp_accumulate_multi<4, false, IcpColor>;
+            acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets, color);
+            return;
+        }
         const auto acc = p2pl ? (robust ? k_icp_accumulate_multi<0, true> : k_icp_accumulate_multi<0>) : (robust ? k_icp_accumulate_multi<1, true> : k_icp_accumulate_multi<1>);
         acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, p2pl ? d_tgt_normals : nullptr, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets);
     }));
@@ -1750,6 +1841,21 @@ int gicp_check(tdv_ctx* ctx, const float* src_normals, const float* tgt_normals,
     if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
         snprintf(ctx->err, sizeof(ctx->err), "gicp: reference-order accumulation reproduces the reference's float sums, and the reference has no "
                  "generalized ICP; set TDV_ICP_ACCUMULATE_TREE");
+        return TDV_ERR_BAD_ARG;
+    }
+    return TDV_OK;
+}
+
+int colored_check(tdv_ctx* ctx, const float* src_rgb, const float* tgt_normals, const float* tgt_color, float lambda_geometric, bool device) {
+    if (!src_rgb || !tgt_normals || !tgt_color || !std::isfinite(lambda_geometric) || !(lambda_geometric >= 0.f && lambda_geometric <= 1.f))
+        return TDV_ERR_BAD_ARG;
+    if (device && (reinterpret_cast<uintptr_t>(tgt_color) & 15) != 0) {
+        snprintf(ctx->err, sizeof(ctx->err), "colored_icp: the target colour table is read as float4 and must be 16-byte aligned");
+        return TDV_ERR_BAD_ARG;
+    }
+    if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
+        snprintf(ctx->err, sizeof(ctx->err), "colored_icp: reference-order accumulation reproduces the reference's float sums, and the reference has "
+                 "no colored ICP; set TDV_ICP_ACCUMULATE_TREE");
         return TDV_ERR_BAD_ARG;
     }
     return TDV_OK;

@@ -149,6 +149,10 @@ struct IcpOutputs {  // optional per-source outputs of one correspondence pass (
 // Generalized ICP (plane-to-plane, include/tdv_hip.h: tdv_gicp): the source normals, laid out like the source points (device), and
 // c = 1 - epsilon in f32.  src_normals == nullptr: not GICP - the ICP objective the other arguments select.
 struct IcpGicp { const float* src_normals; float c; };
+// Colored ICP (Park et al. 2017, include/tdv_hip.h: tdv_colored_icp): the source colours, laid out like the source points (device),
+// the target's colour table (float4 (I, d) per point, tdv_color_gradients), lg = sqrtf(lambda) and lc = sqrtf(1 - lambda).
+// src_rgb == nullptr: not colored ICP.
+struct IcpColor { const float* src_rgb; const float* tgt_color; float lg, lc; };
 struct SortedCloud;
 // Hash grid over a target cloud for ICP's correspondence search at one acceptance threshold (icp.hip): cells of 2.2 x
 // the threshold, open-addressing table of (32-bit cell tag, list head), the points of a cell as a linked list of (x, y, z, next) nodes indexed like the cloud.  Lives
@@ -160,16 +164,18 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 // (cell_grid_build, for this thr), built once and reused across calls
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
-                tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr, IcpGicp gicp = IcpGicp{nullptr, 0.f});
+                tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr, IcpGicp gicp = IcpGicp{nullptr, 0.f},
+                IcpColor color = IcpColor{nullptr, nullptr, 0.f, 0.f});
 // many small problems against one target in one launch (icp.hip: k_icp_small), when icp_small_batch_fits(ctx, largest problem, nt)
 bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt);
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp = IcpGicp{nullptr, 0.f});
+                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp = IcpGicp{nullptr, 0.f},
+                        IcpColor color = IcpColor{nullptr, nullptr, 0.f, 0.f});
 // icp_run_dev for n instances against one target (icp.hip): instance b = h_count[b] points from point h_start[b] of d_src (host arrays), start
 // pose T0s + 16 b; per instance icp_run_dev's result bit for bit.  Arguments are not checked.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
                       int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out,
-                      IcpGicp gicp = IcpGicp{nullptr, 0.f});
+                      IcpGicp gicp = IcpGicp{nullptr, 0.f}, IcpColor color = IcpColor{nullptr, nullptr, 0.f, 0.f});
 int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                             const float* T, float thr, IcpOutputs outs, int* n_corr);
 // TDV_ERR_BAD_ARG (reason in ctx->err) when the ctx's ICP loss cannot run with its accumulation mode (a robust loss with
@@ -178,6 +184,10 @@ int icp_loss_check(tdv_ctx* ctx);
 // TDV_ERR_BAD_ARG (reason in ctx->err) for GICP's own arguments: a NULL normal array, epsilon not finite or outside (0, 1], or a ctx
 // in reference-order accumulation (the reference has no GICP)
 int gicp_check(tdv_ctx* ctx, const float* src_normals, const float* tgt_normals, float epsilon);
+// TDV_ERR_BAD_ARG (reason in ctx->err) for colored ICP's own arguments: a NULL colour, colour table or normal array, lambda not finite
+// or outside [0, 1], or a ctx in reference-order accumulation (the reference has no colored ICP).  device: the colour table is a device
+// pointer, which the kernels read as float4 - it must be 16-byte aligned.
+int colored_check(tdv_ctx* ctx, const float* src_rgb, const float* tgt_normals, const float* tgt_color, float lambda_geometric, bool device);
 int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel, int max_iterations, float confidence, uint32_t seed,
@@ -224,6 +234,10 @@ void resize_nn_tables(int sw, int sh, int dw, int dh, int* x_ofs, int* y_ofs);
 int depth_batch_nonzero_any(tdv_ctx* ctx, const uint16_t* d_raw, const int* d_frame_of, const uint8_t* d_masks, int layout, int w, int h, float scale,
                             int mask_mode, const int* h_inst, int n_list, int* h_flags);
 int estimate_normals_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float* d_normals, int* d_knn);
+// colour gradients of a cloud (color.hip, include/tdv_hip.h: tdv_color_gradients): float4 (I, d) per point from the kNN lists d_knn
+// (int[n * k], tdv_estimate_normals' for the same k) or, d_knn == nullptr, from estimate_normals_dev's search
+int color_gradients_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, const float* d_normals, int n, int k, const int* d_knn,
+                        float* d_color);
 int compute_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, int n, float radius,
                      float* d_desc, int* d_nbr, int* d_nbr_cnt);
 // With TDV_VOXEL_ORDER_REFERENCE, `both` (optional) also receives the cloud in first-occurrence order and the permutation

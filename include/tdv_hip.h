@@ -365,6 +365,63 @@ int tdv_gicp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, i
 int tdv_gicp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances,
                        const float* d_tgt, const float* d_tgt_normals, int nt, const float* h_T0, float distance_threshold,
                        int max_iterations, float epsilon, int fixed_iterations, tdv_icp_result* out);
+/* Colored ICP (Park, Zhou, Koltun, ICCV 2017; Open3D's registration_colored_icp): point-to-plane's geometric row plus a photometric
+ * row on the target's tangent plane, which pins the in-plane slide and the spin about the normal on textured surfaces.
+ *
+ * tdv_color_gradients / tdv_color_gradients_dev: out_color / d_color = float[n * 4], per point (I, d_x, d_y, d_z), the intensity
+ * and its gradient on the point's tangent plane.  f32 without contraction except where stated:
+ *   I_i  = ((r_i + g_i) + b_i) / 3.0f                                            (correctly rounded division)
+ *   neighbours: point i's exact kNN list for k, as tdv_estimate_normals returns it ((d2, idx) order, self included, -1 padded) -
+ *   self (index i) and the pads dropped, in list order; m = how many are left.  d_knn == NULL: that search runs inside the call;
+ *   otherwise d_knn must be tdv_estimate_normals' int[n * k] list for the same cloud and k, and no search runs.
+ *   per neighbour j, with q the point and n its normal:
+ *     t_j = (q_j - q)_x * n_x + ((q_j - q)_y * n_y + (q_j - q)_z * n_z);  u_j = (q_j - q) - t_j * n per component;  b_j = I_j - I_i
+ *   in f64 from the f32 values, summed from 0.0 in list order:  S_ab = sum u_j[a] * u_j[b],  c_a = sum u_j[a] * b_j
+ *   A_ab = S_ab + ((m * m) * n_a) * n_b                                         (Open3D's tangent row m n; m * m in f64)
+ *   cofactors  C00 = A11 * A22 - A12 * A12   C11 = A00 * A22 - A02 * A02   C22 = A00 * A11 - A01 * A01
+ *              C01 = A02 * A12 - A01 * A22   C02 = A01 * A12 - A02 * A11   C12 = A01 * A02 - A00 * A12   (C symmetric)
+ *   det = A00 * C00 + (A01 * C01 + A02 * C02);  d_a = (float)((C_a0 * c_0 + (C_a1 * c_1 + C_a2 * c_2)) / det)
+ *   d = 0 when m < 3 or det is not > 0 and finite.
+ * Normals are taken as given.  TDV_ERR_BAD_ARG: k <= 0 or k > 255 (as tdv_estimate_normals), a NULL array with n > 0.
+ *
+ * tdv_colored_icp / tdv_colored_icp_dev / tdv_colored_icp_batch_dev are tdv_icp / tdv_icp_dev / tdv_icp_batch_dev, point-to-plane
+ * (same search on every path, same acceptance d2 <= thr^2, same batch paths and bit-for-bit batch = single guarantee, same
+ * tdv_ctx_last_icp_search) with the source colours (float[ns * 3], laid out like the source points), the target's colour table
+ * tgt_color = tdv_color_gradients of the target (float[nt * 4]; on the device 16-byte aligned) and lambda = lambda_geometric in
+ * [0, 1] (Open3D's default 0.968).  Per accepted correspondence, f32 without contraction, lg = sqrtf(lambda), lc = sqrtf(1 - lambda):
+ *   p = the transformed source point (as ICP forms it), q / n the target point and normal, (I_q, d) its colour table entry,
+ *   I_s = ((r + g) + b) / 3.0f of the source point's colour
+ *   e    = p - q per component;  en = e_x * n_x + (e_y * n_y + e_z * n_z)      (point-to-plane's r)
+ *   J    = [p x n | n], p x v = (p_y * v_z - p_z * v_y,  p_z * v_x - p_x * v_z,  p_x * v_y - p_y * v_x)   (point-to-plane's row)
+ *   e_t  = e - en * n per component                                             (p's offset on the target's tangent plane)
+ *   dn   = d_x * n_x + (d_y * n_y + d_z * n_z);  g = dn * n - d per component    (g = -m, m = d - (d . n) n)
+ *   de   = d_x * e_t,x + (d_y * e_t,y + d_z * e_t,z)
+ *   r_G  = lg * en                          J_G[a] = lg * J[a]
+ *   r_C  = lc * (I_s - (I_q + de))          J_C = [lc * (p x g) | lc * g]
+ * H_ab (a <= b, point-to-plane's 21 slots in its order) = (double)(J_G[a] * J_G[b]) + (double)(J_C[a] * J_C[b]);
+ * v_a (its 6 slots) = (double)(J_G[a] * r_G) + (double)(J_C[a] * r_C): each product formed in f32, widened, the two added in f64.
+ * The f64 tree, the step (x = ldlt6_solve(H, -v), rotation euler_xyz(x0, x1, x2), translation x3..5), n_corr, fitness, rmse
+ * (Euclidean d2), the |delta rmse| < 1e-6 rule, the n_corr < 3 break and fixed_iterations are ICP's: the results compare directly
+ * with ICP's and GICP's.  At lambda = 1 the terms equal point-to-plane's in value.  The ctx's loss (tdv_ctx_set_icp_loss) weighs
+ * each row by its own residual: w_G = weight(r_G), w_C = weight(r_C), each slot (double)w_G * (J_G product) + (double)w_C * (J_C
+ * product), and n_eff counts the correspondences with w_G > 0 || w_C > 0.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written to out: a NULL colour, colour table or normal array, lambda not finite or
+ * outside [0, 1], a device colour table not 16-byte aligned, a ctx in TDV_ICP_ACCUMULATE_REFERENCE mode (the reference has no
+ * colored ICP; the reason is in tdv_last_error), or what the ICP entry point checks.  0 points, nt == 0 or max_iterations == 0
+ * return what ICP returns. */
+int tdv_color_gradients(tdv_ctx* ctx, const float* xyz, const float* rgb, const float* normals, int n, int k, float* out_color);
+int tdv_color_gradients_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, const float* d_normals, int n, int k,
+                            const int* d_knn /* may be NULL */, float* d_color);
+int tdv_colored_icp(tdv_ctx* ctx, const float* src, const float* src_rgb, int ns, const float* tgt, const float* tgt_normals,
+                    const float* tgt_color /* float[nt*4] */, int nt, const float* T0, float distance_threshold, int max_iterations,
+                    float lambda_geometric, tdv_icp_result* out);
+int tdv_colored_icp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_rgb, int ns, const float* d_tgt, const float* d_tgt_normals,
+                        const float* d_tgt_color, int nt, const float* T0, float distance_threshold, int max_iterations,
+                        float lambda_geometric, int fixed_iterations, tdv_icp_result* out);
+int tdv_colored_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_rgb, const int* h_src_offsets, int n_instances,
+                              const float* d_tgt, const float* d_tgt_normals, const float* d_tgt_color, int nt, const float* h_T0,
+                              float distance_threshold, int max_iterations, float lambda_geometric, int fixed_iterations,
+                              tdv_icp_result* out);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
