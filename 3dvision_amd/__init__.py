@@ -57,6 +57,7 @@ ABI_SYMBOLS = [
     "tdv_icp_batch_dev", "tdv_refine_batch_dev", "tdv_ctx_set_icp_loss", "tdv_ctx_get_icp_loss",
     "tdv_gicp", "tdv_gicp_dev", "tdv_gicp_batch_dev",
     "tdv_color_gradients", "tdv_color_gradients_dev", "tdv_colored_icp", "tdv_colored_icp_dev", "tdv_colored_icp_batch_dev",
+    "tdv_fgr_default_params", "tdv_fgr", "tdv_fgr_dev", "tdv_fgr_correspondences",
 ]
 
 
@@ -88,6 +89,28 @@ class InstanceResultC(C.Structure):
 class IcpResultC(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("fitness", C.c_float), ("rmse", C.c_float), ("iterations", C.c_int),
                 ("n_corr", C.c_int)]
+
+
+class FgrParamsC(C.Structure):
+    _fields_ = [("division_factor", C.c_float), ("maximum_correspondence_distance", C.c_float), ("tuple_scale", C.c_float),
+                ("iteration_number", C.c_int), ("maximum_tuple_count", C.c_int), ("use_absolute_scale", C.c_int),
+                ("decrease_mu", C.c_int), ("tuple_test", C.c_int), ("seed", C.c_uint32)]
+
+
+class FgrResultC(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("fitness", C.c_float), ("rmse", C.c_float), ("inliers", C.c_int), ("n_mutual", C.c_int),
+                ("n_tuple", C.c_int), ("degenerate", C.c_int), ("trials_run", C.c_longlong)]
+
+
+def fgr_params(**kw):
+    """tdv_fgr_default_params with the given fields replaced (Open3D's FastGlobalRegistrationOption names)."""
+    p = FgrParamsC()
+    lib().tdv_fgr_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(FgrParamsC._fields_):
+            raise TypeError("unknown FGR parameter %r" % k)
+        setattr(p, k, v)
+    return p
 
 
 _lib = None
@@ -127,6 +150,7 @@ def lib():
             l.tdv_ctx_workspace_bytes.restype = C.c_ulonglong
             l.tdv_ctx_last_ransac_rescore.restype = C.c_double
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
+            l.tdv_fgr_default_params.restype = None
             _lib = l
     return _lib
 
@@ -578,6 +602,41 @@ class Context:
         d_tc = torch.from_numpy(tc if len(tc) else np.zeros((1, 4), np.float32)).to(dev)
         return self.colored_icp_batch_dev(d_src.data_ptr(), d_rgb.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), d_tc.data_ptr(), len(tgt),
                                           T0s, thr, max_iterations, lambda_geometric)
+
+    # ---------------------------------------------------------------- Fast Global Registration
+    @staticmethod
+    def _fgr_result(res):
+        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
+                                  inliers=res.inliers), dict(n_mutual=res.n_mutual, n_tuple=res.n_tuple, degenerate=bool(res.degenerate),
+                                                             trials_run=res.trials_run)
+
+    def fgr(self, src, tgt, fs, ft, voxel, **params):
+        """tdv_fgr: (RegistrationResult with transformation, fitness, rmse, inliers; dict n_mutual, n_tuple, degenerate, trials_run)."""
+        src = _f32(src).reshape(-1, 3); tgt = _f32(tgt).reshape(-1, 3); fs = _f32(fs).reshape(-1, 33); ft = _f32(ft).reshape(-1, 33)
+        res = FgrResultC(); p = fgr_params(**params)
+        _check(self._h, lib().tdv_fgr(self._h, _ptr(src), len(src), _ptr(tgt), len(tgt), _ptr(fs), _ptr(ft), C.c_float(voxel), C.byref(p),
+                                      C.byref(res)), "tdv_fgr")
+        return self._fgr_result(res)
+
+    def fgr_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, voxel, **params):
+        res = FgrResultC(); p = fgr_params(**params)
+        _check(self._h, lib().tdv_fgr_dev(self._h, _ptr(d_src), ns, _ptr(d_tgt), nt, _ptr(d_fs), _ptr(d_ft), C.c_float(voxel), C.byref(p),
+                                          C.byref(res)), "tdv_fgr_dev")
+        return self._fgr_result(res)
+
+    def fgr_correspondences(self, src, tgt, fs, ft, **params):
+        """tdv_fgr_correspondences: dict(mutual (k, 2) int32 pairs, tuples (m, 2), n_mutual, n_tuple, trials_run)."""
+        src = _f32(src).reshape(-1, 3); tgt = _f32(tgt).reshape(-1, 3); fs = _f32(fs).reshape(-1, 33); ft = _f32(ft).reshape(-1, 33)
+        p = fgr_params(**params)
+        nm = C.c_int(); nu = C.c_int(); tr = C.c_longlong()
+        args = (self._h, _ptr(src), len(src), _ptr(tgt), len(tgt), _ptr(fs), _ptr(ft), C.byref(p))
+        st = lib().tdv_fgr_correspondences(*args, None, 0, None, 0, C.byref(nm), C.byref(nu), C.byref(tr))   # size query
+        if st not in (0, -2) or (st == -2 and nm.value == 0 and nu.value == 0):
+            _check(self._h, st, "tdv_fgr_correspondences")
+        mutual = np.zeros((nm.value, 2), np.int32); tuples = np.zeros((nu.value, 2), np.int32)
+        _check(self._h, lib().tdv_fgr_correspondences(*args, _ptr(mutual), nm.value, _ptr(tuples), nu.value, C.byref(nm), C.byref(nu),
+                                                      C.byref(tr)), "tdv_fgr_correspondences")
+        return dict(mutual=mutual, tuples=tuples, n_mutual=nm.value, n_tuple=nu.value, trials_run=tr.value)
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

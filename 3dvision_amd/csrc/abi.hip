@@ -477,4 +477,69 @@ int tdv_voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rg
     return voxel_downsample_dev(ctx, d_xyz, d_rgb, n, voxel_size, order, d_out_xyz, d_out_rgb, capacity, n_out);
 }
 
+// ---- Fast Global Registration (fgr.hip)
+void tdv_fgr_default_params(tdv_fgr_params* p) {
+    if (!p) return;
+    p->division_factor = 1.4f; p->maximum_correspondence_distance = 0.025f; p->tuple_scale = 0.95f; p->iteration_number = 64;
+    p->maximum_tuple_count = 1000; p->use_absolute_scale = 0; p->decrease_mu = 1; p->tuple_test = 1; p->seed = 42u;
+}
+// every argument, before anything is enqueued (include/tdv_hip.h: tdv_fgr)
+static bool fgr_args_ok(const tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft,
+                        float voxel_size, const tdv_fgr_params* p) {
+    if (!ctx || !p || ns < 0 || nt < 0) return false;
+    if (ns > 0 && (!src || !fs)) return false;
+    if (nt > 0 && (!tgt || !ft)) return false;
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0.f)) return false;
+    if (!std::isfinite(p->division_factor) || !(p->division_factor > 1.f)) return false;
+    if (!std::isfinite(p->tuple_scale) || !(p->tuple_scale > 0.f && p->tuple_scale <= 1.f)) return false;
+    if (!std::isfinite(p->maximum_correspondence_distance) || !(p->maximum_correspondence_distance > 0.f)) return false;
+    return p->iteration_number >= 0 && p->maximum_tuple_count >= 1;
+}
+static void fgr_empty(tdv_fgr_result* out) {
+    std::memset(out, 0, sizeof(*out));
+    for (int i = 0; i < 16; ++i) out->T[i] = (i % 5 == 0) ? 1.f : 0.f;
+    out->degenerate = 1;
+}
+int tdv_fgr(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft, float voxel_size,
+            const tdv_fgr_params* params, tdv_fgr_result* out) {
+    if (!out || !fgr_args_ok(ctx, src, ns, tgt, nt, fs, ft, voxel_size, params)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    if (ns == 0 || nt == 0) { fgr_empty(out); return TDV_OK; }
+    float *d_src, *d_tgt, *d_fs, *d_ft;
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
+    TDV_TRY(upload(ctx, fs, (size_t)ns * 33, &d_fs));
+    TDV_TRY(upload(ctx, ft, (size_t)nt * 33, &d_ft));
+    return fgr_run_dev(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, voxel_size, *params, out, nullptr);
+}
+int tdv_fgr_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, float voxel_size,
+                const tdv_fgr_params* params, tdv_fgr_result* out) {
+    if (!out || !fgr_args_ok(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, voxel_size, params)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    if (ns == 0 || nt == 0) { fgr_empty(out); return TDV_OK; }
+    return fgr_run_dev(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, voxel_size, *params, out, nullptr);
+}
+int tdv_fgr_correspondences(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft,
+                            const tdv_fgr_params* params, int* out_mutual, int cap_mutual, int* out_tuple, int cap_tuple,
+                            int* n_mutual, int* n_tuple, long long* trials_run) {
+    if (!n_mutual || !n_tuple || !trials_run || cap_mutual < 0 || cap_tuple < 0 || (cap_mutual > 0 && !out_mutual) ||
+        (cap_tuple > 0 && !out_tuple) || !fgr_args_ok(ctx, src, ns, tgt, nt, fs, ft, 1.f, params))
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    *n_mutual = 0; *n_tuple = 0; *trials_run = 0;
+    if (ns == 0 || nt == 0) return TDV_OK;
+    float *d_src, *d_tgt, *d_fs, *d_ft;
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
+    TDV_TRY(upload(ctx, fs, (size_t)ns * 33, &d_fs));
+    TDV_TRY(upload(ctx, ft, (size_t)nt * 33, &d_ft));
+    FgrPairs pr;
+    TDV_TRY(fgr_run_dev(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, 1.f, *params, nullptr, &pr));
+    *n_mutual = pr.n_mutual; *n_tuple = pr.n_tuple; *trials_run = pr.trials_run;
+    if (pr.n_mutual > cap_mutual || pr.n_tuple > cap_tuple) return TDV_ERR_BAD_ARG;
+    TDV_TRY(download(ctx, reinterpret_cast<int2*>(out_mutual), pr.mutual, (size_t)pr.n_mutual));
+    TDV_TRY(download(ctx, reinterpret_cast<int2*>(out_tuple), pr.tuple, (size_t)pr.n_tuple));
+    return finish(ctx);
+}
+
 }  // extern "C"

@@ -893,6 +893,23 @@ __global__ void k_ransac_rmse_final(const double* __restrict__ slabs, int nblock
     if (threadIdx.x == 0) { out2[0] = pe[0]; out2[1] = pn[0]; }
 }
 
+int ransac_score_pose_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const int* d_corr, const float* d_hyp12,
+                          float voxel, double* d_out2) {
+    if (ns <= 0 || nt <= 0) return TDV_ERR_BAD_ARG;
+    hipStream_t s = ctx->stream;
+    const int ns_pad = (int)align_up((size_t)ns, 256), rblocks = (ns + 255) / 256;
+    float* pq = nullptr; double* slabs = nullptr; int* flags = nullptr;
+    TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 8, &pq));
+    TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
+    TDV_TRY(ws_alloc(ctx, 2, &flags));
+    TDV_HIP(ctx, hipMemsetAsync(flags, 0, 8, s));
+    k_gather_pq<<<ns_pad / 256, 256, 0, s>>>(d_src, d_tgt, d_corr, ns, ns_pad, nt, pq, flags, reinterpret_cast<unsigned*>(flags + 1));
+    k_ransac_rmse_partial<<<rblocks, 256, 0, s>>>(pq, ns, d_hyp12, tau_lt(voxel * 1.5f), slabs);
+    k_ransac_rmse_final<<<1, 256, 0, s>>>(slabs, rblocks, d_out2);
+    TDV_CHECK_LAUNCH(ctx);
+    return TDV_OK;
+}
+
 int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr_in,
                    float voxel, int max_iterations, float confidence, uint32_t seed,

@@ -192,6 +192,15 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel, int max_iterations, float confidence, uint32_t seed,
                    tdv_ransac_result* out, int* trace_inliers);
+// the winner scoring of ransac_run_dev for one pose (ransac.hip): d_hyp12 = column-major R then t (device, f32); d_out2 (device) receives
+// the f64 tree sum of (double)(err * err) over the inliers (sqrtf(d2) < 1.5 voxel) of the matches d_corr and the inlier count
+int ransac_score_pose_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const int* d_corr, const float* d_hyp12,
+                          float voxel, double* d_out2);
+// Fast Global Registration (fgr.hip, include/tdv_hip.h: tdv_fgr).  want_pairs: stop after the tuple test and leave the device pair lists
+// in *pairs (mutual pairs as int2 at [0], tuple pairs at [1]) - for tdv_fgr_correspondences
+struct FgrPairs { const int2* mutual = nullptr; const int2* tuple = nullptr; int n_mutual = 0, n_tuple = 0; long long trials_run = 0; };
+int fgr_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, float voxel,
+                const tdv_fgr_params& prm, tdv_fgr_result* out, FgrPairs* pairs);
 // ransac_run_dev for many small clouds against one target in a handful of launches (ransac.hip): cloud b = points
 // [h_off[b], h_off[b+1]) of d_src with correspondences d_corr (same indexing); out[b].rmse is NOT evaluated (0).  *fell_back = 1:
 // nothing was computed (a cloud too large, too many hypotheses, or the index sampler ran out of draws) - use ransac_run_dev.

@@ -422,6 +422,87 @@ int tdv_colored_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_s
                               const float* d_tgt, const float* d_tgt_normals, const float* d_tgt_color, int nt, const float* h_T0,
                               float distance_threshold, int max_iterations, float lambda_geometric, int fixed_iterations,
                               tdv_icp_result* out);
+/* Fast Global Registration (Zhou, Park, Koltun, ECCV 2016; Open3D's registration_fgr_based_on_feature_matching): a global pose from the
+ * FPFH matches without hypotheses - mutual nearest descriptors, a tuple test, then iteration_number Geman-McClure weighted Gauss-Newton
+ * steps under a graduated non-convexity schedule.  Open3D's options and defaults; its rand() and its pair order are replaced by the
+ * deterministic rules below.  Every step, in order:
+ *  1. Matching: cst[i] = the target index tdv_feature_match gives source i (exact, strict <, lowest index on ties); cts[j] the same from
+ *     target j to the source.
+ *  2. Mutual filter: pair (i, cst[i]) is kept iff cts[cst[i]] == i; kept pairs in ascending i; n_mutual = their count.
+ *  3. Tuple test (tuple_test != 0): trials t = 0 .. 100 * n_mutual - 1 (64-bit).  Trial t takes words x0, x1, x2 of Philox4x32-10 with
+ *     counter (lo32(t), hi32(t), 0, 0) and key (seed, 0); index k = (uint32)(((uint64)x_k * n_mutual) >> 32) into the mutual list (a
+ *     multiply-shift: index m comes up floor or ceil of 2^32 / n_mutual times, a bias of at most n_mutual / 2^32).  With a_k / b_k the
+ *     source / target points of the three pairs: l_a0 = |a0 - a1|, l_a1 = |a1 - a2|, l_a2 = |a2 - a0|, likewise l_b, each component
+ *     difference in f64 from the f32 inputs, |d| = sqrt((dx*dx + dy*dy) + dz*dz) without contraction.  The trial passes iff
+ *     l_a*s < l_b && l_b < l_a/s for all three, s = (double)tuple_scale (a repeated index gives 0 < 0 and fails, as in Open3D; a NaN
+ *     fails).  The tuple set is the pairs of the FIRST maximum_tuple_count passing trials in trial order, three per trial as (pair 0,
+ *     pair 1, pair 2); n_tuple = 3 x (trials kept).  Trials are evaluated in chunks: chunk k holds TDV_FGR_TRIAL_CHUNK << min(k, 5)
+ *     trials, and the test stops after the chunk in which the count was reached or at 100 * n_mutual trials; trials_run = the trials
+ *     evaluated.  tuple_test == 0: the mutual set is used as it is (n_tuple = 0, trials_run = 0).  The test reads the raw points, so
+ *     these sets depend on no sum.
+ *  4. Normalisation (Open3D's NormalizePointCloud): mu_s, mu_t = f64 means of ALL points of each cloud (f64 sums); sigma = the largest
+ *     |x - mu| = sqrt((dx*dx + dy*dy) + dz*dz) (f64) over both clouds (a NaN never wins; 0 if no value is > 0), or 1 with
+ *     use_absolute_scale; p = (x_s - mu_s) / sigma, q = (x_t - mu_t) / sigma per component in f64.
+ *  5. Optimisation (Open3D's OptimizePairwise) over the pair list (tuples, or the mutual pairs with tuple_test == 0).  Fewer than 10
+ *     pairs: T = identity (f32), degenerate = 1, no optimisation.  Otherwise, f64 throughout: T = I; mu = 1 (with use_absolute_scale the
+ *     largest |x - mu|, Open3D's scale_start); iterations itr = 0 .. iteration_number - 1, no early exit:
+ *       if decrease_mu && itr % 4 == 0 && mu > maximum_correspondence_distance: mu = mu / division_factor  (a squared distance against a
+ *       distance, as Open3D); per pair q'_a = ((T_a0 q_x + T_a1 q_y) + T_a2 q_z) + T_a3, r = p - q', rr = (r_x r_x + r_y r_y) + r_z r_z,
+ *       w = (mu / (rr + mu))^2 (the quotient squared); rows (0, -q'z, q'y, -1, 0, 0 | r_x), (q'z, 0, -q'x, 0, -1, 0 | r_y),
+ *       (-q'y, q'x, 0, 0, 0, -1 | r_z); per pair JtJ_ab = (w (J0_a J0_b) + w (J1_a J1_b)) + w (J2_a J2_b) (a <= b) and Jtr_a likewise
+ *       with r, summed over the pairs in a fixed tree (the order is fixed, not the restatement's);
+ *       step: JtJ = L D L^T unpivoted, for j = 0..5, i = j..5: s = A_ij - sum_{k<j} (L_ik d_k) L_jk (k ascending), d_j = s (i == j) or
+ *       L_ij = s / d_j; a d_j not > 0 or not finite gives x = 0; else y = L^-1 Jtr, z_i = y_i / d_i, back substitution, x = -(L^-T z)
+ *       (the solution of (-JtJ) x = Jtr);  delta = [Rz(x2) Ry(x1) Rx(x0) | x3..5] with c_i = cos x_i, s_i = sin x_i:
+ *         [c2 c1, (c2 s1) s0 - s2 c0, (c2 s1) c0 + s2 s0;  s2 c1, (s2 s1) s0 + c2 c0, (s2 s1) c0 - c2 s0;  -s1, c1 s0, c1 c0];
+ *       T = delta T (4x4 product, k ascending).
+ *     T moves the target onto the source in normalised units; the result is Open3D's GetInvTransformationOriginalScale:
+ *     R' = R^T, t' = -R^T u with u = (mu_s + sigma t) - R mu_t (products k ascending), rounded to f32 (column-major).
+ *  6. Score, as tdv_ransac scores its winner (src/registration.cpp:276-288): over the one-way matches cst, threshold 1.5 * voxel_size,
+ *     inlier iff sqrtf(d2) < thr, error sum of (double)(err * err) in ransac's f64 tree; fitness = inliers / ns, rmse = sqrtf((float)sum /
+ *     inliers), 999 with no inlier.  The numbers compare directly with tdv_ransac_result; either pose can seed tdv_icp.
+ * Non-finite coordinates have no special case: they propagate through the means (a NaN or infinite coordinate makes mu, sigma, and from
+ * there the pose NaN, unless the pair list is degenerate) and fail every tuple trial they enter.
+ * The ctx's ICP switches (search, accumulation, loss) do not apply.  Not provided: FGR inside tdv_register_batch_dev /
+ * tdv_refine_batch_dev (a tdv_batch_params field: an ABI change), a batched form, the C++ operator mirror, FGR on given correspondences.
+ * TDV_ERR_BAD_ARG, before anything is enqueued and with out untouched: a NULL ctx, params or out; a NULL cloud or descriptor array of a
+ * non-empty cloud; ns or nt < 0; voxel_size not finite or not > 0; division_factor not > 1; tuple_scale outside (0, 1];
+ * maximum_correspondence_distance not > 0; iteration_number < 0; maximum_tuple_count < 1; any non-finite float parameter.
+ * ns == 0 or nt == 0: identity, zero counts, fitness and rmse 0, degenerate = 1.
+ * tdv_fgr takes host arrays; tdv_fgr_dev device pointers (it synchronises and returns a host struct, as tdv_ransac_dev).
+ * tdv_fgr_correspondences (host arrays, for parity tests) writes steps 1-3: the mutual pairs as (i, j) int pairs into out_mutual (room
+ * for cap_mutual pairs) and the tuple pairs into out_tuple (cap_tuple pairs), with *n_mutual, *n_tuple and *trials_run; when a buffer is
+ * too small (NULL with capacity 0 is a query) it returns TDV_ERR_BAD_ARG with the three counts written. */
+#define TDV_FGR_TRIAL_CHUNK 131072
+typedef struct tdv_fgr_params {
+    float division_factor;                 /* 1.4   */
+    float maximum_correspondence_distance; /* 0.025 */
+    float tuple_scale;                     /* 0.95  */
+    int   iteration_number;                /* 64    */
+    int   maximum_tuple_count;             /* 1000  */
+    int   use_absolute_scale;              /* 0     */
+    int   decrease_mu;                     /* 1     */
+    int   tuple_test;                      /* 1     */
+    uint32_t seed;                         /* 42    */
+} tdv_fgr_params;
+typedef struct tdv_fgr_result {
+    float T[16];          /* column-major, source onto target */
+    float fitness;        /* inliers / ns of T over the one-way matches */
+    float rmse;           /* 999 with no inlier */
+    int inliers;
+    int n_mutual;         /* mutual pairs */
+    int n_tuple;          /* pairs kept by the tuple test (3 per trial; 0 with tuple_test == 0) */
+    int degenerate;       /* 1: fewer than 10 pairs, T is the identity */
+    long long trials_run; /* tuple trials evaluated */
+} tdv_fgr_result;
+void tdv_fgr_default_params(tdv_fgr_params* p);
+int tdv_fgr(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft, float voxel_size,
+            const tdv_fgr_params* params, tdv_fgr_result* out);
+int tdv_fgr_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, float voxel_size,
+                const tdv_fgr_params* params, tdv_fgr_result* out);
+int tdv_fgr_correspondences(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft,
+                            const tdv_fgr_params* params, int* out_mutual, int cap_mutual, int* out_tuple, int cap_tuple,
+                            int* n_mutual, int* n_tuple, long long* trials_run);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
