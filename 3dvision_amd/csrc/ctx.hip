@@ -4,6 +4,8 @@
 #include <cmath>
 #include <cfloat>
 #include <algorithm>
+#include <cstring>
+#include <vector>
 
 namespace tdv {
 
@@ -78,62 +80,117 @@ ScopedTimer::~ScopedTimer() {
 // ---- mt19937 + libstdc++-11 uniform_int_distribution<size_t> (Lemire's nearly-divisionless
 // method on 32-bit draws when the range fits in 32 bits; for larger ranges libstdc++ composes
 // two draws — clouds never reach 2^32 points, so that branch is rejected up front).
+// Bulk form (round 6): the state is twisted a whole block of 624 words at a time - the twist split into its three index ranges,
+// no modulo - and the block tempered at once; both loops vectorise.  Lemire's rejection loop is a per-word predicate: a word r is
+// accepted iff (uint32)(r * range) >= (2^32 - range) mod range, and an accepted word gives the index (r * range) >> 32.  A draw
+// of m indices therefore maps m words at a time (every word gives at most one index, so m words never overshoot), with a
+// vectorised pass when none of them is rejected (about 8 words of a 65,536-hypothesis batch at 200k points are) and a
+// branch-free compaction otherwise, until m indices have been produced: the same indices, from the same words, as the loop of
+// std::uniform_int_distribution, and the stream continues exactly where that loop would.
 namespace {
+#if defined(__x86_64__) && !defined(__HIP_DEVICE_COMPILE__)
+#define TDV_HOST_VECTOR __attribute__((target_clones("avx2", "default")))   // the two bulk loops below: 8 lanes where the host has them
+#else
+#define TDV_HOST_VECTOR
+#endif
+constexpr int MT_N = 624, MT_M = 397;
+inline uint32_t mt_mix(uint32_t a, uint32_t b, uint32_t c) {   // mt[i] from mt[i] (a), mt[i + 1] (b) and mt[i + 397] (c)
+    const uint32_t y = (a & 0x80000000u) | (b & 0x7fffffffu);
+    return c ^ (y >> 1) ^ ((0u - (y & 1u)) & 0x9908b0dfu);
+}
+// the twist of a whole block, then its tempering into out[]
+// (the sequential twist updates mt[i] in place in order i = 0..623; mt[i + 397] is still the old word for i < 227
+// and already the new one from then on (index i - 227), mt[i + 1] is old except for i = 623 (mt[0], new))
+TDV_HOST_VECTOR void mt_block(uint32_t* __restrict__ mt, uint32_t* __restrict__ out) {
+    for (int i = 0; i < MT_N - MT_M; ++i) mt[i] = mt_mix(mt[i], mt[i + 1], mt[i + MT_M]);
+    for (int i = MT_N - MT_M; i < MT_N - 1; ++i) mt[i] = mt_mix(mt[i], mt[i + 1], mt[i + MT_M - MT_N]);
+    mt[MT_N - 1] = mt_mix(mt[MT_N - 1], mt[0], mt[MT_M - 1]);
+    for (int i = 0; i < MT_N; ++i) {
+        uint32_t y = mt[i];
+        y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
+        out[i] = y;
+    }
+}
+// Lemire's index of every word (r * range) >> 32 into d; returns whether any word is rejected ((uint32)(r * range) < thr)
+TDV_HOST_VECTOR uint32_t lemire_map(const uint32_t* __restrict__ w, int k, uint32_t range, uint32_t thr, uint32_t* __restrict__ d) {
+    uint32_t rejected = 0;
+    for (int i = 0; i < k; ++i) {
+        const uint64_t p = (uint64_t)w[i] * range;
+        d[i] = (uint32_t)(p >> 32);
+        rejected |= (uint32_t)((uint32_t)p < thr);
+    }
+    return rejected;
+}
 struct Mt19937 {
-    uint32_t mt[624]; int idx;
+    uint32_t mt[MT_N], out[MT_N]; int idx;
     explicit Mt19937(uint32_t seed) {
         mt[0] = seed;
-        for (int i = 1; i < 624; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
-        idx = 624;
+        for (int i = 1; i < MT_N; ++i) mt[i] = 1812433253u * (mt[i - 1] ^ (mt[i - 1] >> 30)) + (uint32_t)i;
+        idx = MT_N;
     }
+    void refill() { mt_block(mt, out); idx = 0; }   // the next 624 outputs into out[]
     uint32_t next() {
-        if (idx >= 624) {
-            for (int i = 0; i < 624; ++i) {
-                uint32_t y = (mt[i] & 0x80000000u) | (mt[(i + 1) % 624] & 0x7fffffffu);
-                mt[i] = mt[(i + 397) % 624] ^ (y >> 1) ^ ((y & 1u) ? 0x9908b0dfu : 0u);
+        if (idx >= MT_N) refill();
+        return out[idx++];
+    }
+    // m uniform indices in [0, range) (range 0: 2^32, the raw words) into dst, in stream order
+    void draw(uint32_t range, size_t m, uint32_t* dst) {
+        const uint32_t thr = range ? (0u - range) % range : 0u;
+        size_t got = 0;
+        while (got < m) {
+            if (idx >= MT_N) refill();
+            const int k = (int)std::min((size_t)(MT_N - idx), m - got);
+            const uint32_t* w = out + idx;
+            uint32_t* d = dst + got;
+            idx += k;
+            if (!range) { std::memcpy(d, w, (size_t)k * 4); got += k; continue; }
+            if (!lemire_map(w, k, range, thr, d)) { got += k; continue; }
+            int j = 0;
+            for (int i = 0; i < k; ++i) {
+                const uint64_t p = (uint64_t)w[i] * range;
+                d[j] = (uint32_t)(p >> 32);          // (j <= i < k: inside what this round may write)
+                j += (uint32_t)p >= thr;
             }
-            idx = 0;
+            got += j;
         }
-        uint32_t y = mt[idx++];
-        y ^= y >> 11; y ^= (y << 7) & 0x9d2c5680u; y ^= (y << 15) & 0xefc60000u; y ^= y >> 18;
-        return y;
     }
 };
-inline uint32_t lemire(Mt19937& g, uint32_t range) {  // uniform in [0, range)
-    uint64_t product = (uint64_t)g.next() * (uint64_t)range;
-    uint32_t low = (uint32_t)product;
-    if (low < range) {
-        uint32_t threshold = (uint32_t)(-range) % range;
-        while (low < threshold) {
-            product = (uint64_t)g.next() * (uint64_t)range;
-            low = (uint32_t)product;
-        }
-    }
-    return (uint32_t)(product >> 32);
-}
 }  // namespace
 
 void mt19937_lemire_triples(uint32_t seed, uint64_t n, int count, uint64_t* out) {
-    TripleStream ts(seed, n);
-    for (int i = 0; i < count; ++i) ts.next(out + 3 * (size_t)i);
+    Mt19937 g(seed);
+    const uint32_t range = (uint32_t)n;      // n = 2^32 -> 0: the raw words
+    uint32_t buf[3 * 1024];
+    for (int i0 = 0; i0 < count; i0 += 1024) {
+        const int c = std::min(1024, count - i0);
+        g.draw(range, 3 * (size_t)c, buf);
+        for (int k = 0; k < 3 * c; ++k) out[3 * (size_t)i0 + k] = buf[k];
+    }
 }
 
 // the raw 32-bit outputs of mt19937(seed), for the device-side index sampler of the batched RANSAC (ransac.hip)
 void mt19937_raw(uint32_t seed, size_t count, uint32_t* out) {
     Mt19937 g(seed);
-    for (size_t i = 0; i < count; ++i) out[i] = g.next();
+    g.draw(0u, count, out);
 }
 
-struct TripleStream::Impl { Mt19937 g; explicit Impl(uint32_t seed) : g(seed) {} };
+struct TripleStream::Impl { Mt19937 g; std::vector<uint32_t> buf; explicit Impl(uint32_t seed) : g(seed) {} };
 TripleStream::TripleStream(uint32_t seed, uint64_t n) : impl_(new Impl(seed)), n_(n) {}
 TripleStream::~TripleStream() { delete impl_; }
 void TripleStream::next(uint64_t* out3) {
-    if (n_ == ((uint64_t)1 << 32)) {  // urange == urng range: one raw draw each
-        for (int k = 0; k < 3; ++k) out3[k] = impl_->g.next();
-        return;
+    uint32_t d[3];
+    impl_->g.draw((uint32_t)n_, 3, d);       // n = 2^32 -> range 0: one raw draw each
+    for (int k = 0; k < 3; ++k) out3[k] = d[k];
+}
+void TripleStream::next_batch(int count, int* out4) {
+    auto& b = impl_->buf;
+    if (b.size() < 3 * (size_t)count) b.resize(3 * (size_t)count);
+    impl_->g.draw((uint32_t)n_, 3 * (size_t)count, b.data());
+    for (int k = 0; k < count; ++k) {
+        const int a = (int)b[3 * k], c = (int)b[3 * k + 1], e = (int)b[3 * k + 2];
+        out4[4 * k] = a; out4[4 * k + 1] = c; out4[4 * k + 2] = e;
+        out4[4 * k + 3] = !(a == c || c == e || a == e);     // registration.cpp:240
     }
-    const uint32_t range = (uint32_t)n_;
-    for (int k = 0; k < 3; ++k) out3[k] = lemire(impl_->g, range);
 }
 
 float tau_le(float thr) {  // largest f with sqrtf(f) <= thr ; returns -1 if none (thr < 0 or NaN)

@@ -5,7 +5,7 @@
 // Sub-steps and their kernels:
 //  (i)   feature correspondences (registration.cpp:216-232): csrc/fmatch.hip.
 //  (ii)  index triples (registration.cpp:235-239): host, mt19937 + Lemire (ctx.hip), one batch at
-//        a time; a batch is uploaded as int4 (i0,i1,i2,valid).
+//        a time in bulk (whole twist blocks, Lemire's test per word); a batch is uploaded as int4 (i0,i1,i2,valid).
 //  (iii) k_ransac_hypotheses: one lane per hypothesis — centroids, H = S_c T_c^T, Jacobi SVD,
 //        R = V U^T with reflection fix, t = c_t - R c_s (registration.cpp:242-268).
 //  (iv)  k_ransac_score: one hypothesis per lane (R,t in VGPRs); points (source p and its
@@ -432,7 +432,7 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
 // largest PREFIX count of this batch, chunks per workgroup } - one plan per batch buffer, the state shared.
 __global__ void k_ransac_plan(int* __restrict__ state, int* __restrict__ plan, int ns, int n_pchunks, int ps, int drop_permille, int* __restrict__ n_live) {
     const int best = state[0];
-    if (n_live) *n_live = 0;                                  // (RansacLeafBound: k_ransac_bound appends to it next)
+    if (n_live) { n_live[0] = 0; n_live[2] = 0; }            // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided)
     int c_split = n_pchunks;
     const int rest = best - max((int)((long long)best * drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
     if (rest >= ns / 8)                                      // (below an eighth of the points a second phase costs more than it saves)
@@ -518,6 +518,7 @@ __global__ void k_ransac_select(const int4* __restrict__ triples, int count, con
 // whose boxes touch the threshold shell.  Where the band is off (non-finite data, coordinates far from the origin: E not
 // below s / 4) the bound is off too: the hypothesis is live.  A leaf with any non-finite coordinate always passes.
 constexpr int RL_LEAF = 32;          // pairs per leaf (the study: 32 prunes 11.7 % -> 15 % survivors at 64)
+constexpr int RL_COARSE = 128;       // pairs per coarse leaf (4 fine leaves): the first of the bound's two levels, see k_ransac_bound
 constexpr int RL_BITS = 5;           // Morton bits per coordinate (30-bit key)
 __device__ __forceinline__ unsigned rl_enc(float f) { const unsigned b = __float_as_uint(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }   // order-preserving
 __device__ __forceinline__ float rl_dec(unsigned e) { return __uint_as_float((e & 0x80000000u) ? (e & 0x7fffffffu) : ~e); }
@@ -570,27 +571,10 @@ void k_leaf_keys(const float* __restrict__ pq, int ns, const unsigned* __restric
 // values interleaved (value v of leaf 2k + j at [32 k + 2 v + j]) so that k_ransac_bound reads aligned SGPR pairs for its packed
 // instructions; the buffer is zeroed first, so an odd last leaf is paired with an empty one (n = 0).  A leaf with a non-finite
 // coordinate gets pc = pe = 0 and the q box (-inf, inf): it passes for every finite hypothesis.
-__global__ __launch_bounds__(256)
-void k_leaf_build(const float* __restrict__ pq, int ns, const unsigned* __restrict__ order, float* __restrict__ leaves) {
-    const int i = blockIdx.x * 256 + threadIdx.x;     // sorted position; the grid covers whole leaves
-    float lo[6], hi[6];
-    bool bad = false;
-#pragma unroll
-    for (int c = 0; c < 6; ++c) { lo[c] = INFINITY; hi[c] = -INFINITY; }
-    if (i < ns) {
-        const float* g = pq + (size_t)order[i] * 8;
-#pragma unroll
-        for (int c = 0; c < 6; ++c) { const float v = g[c]; lo[c] = v; hi[c] = v; bad |= !(fabsf(v) <= FLT_MAX); }
-    }
-#pragma unroll
-    for (int off = RL_LEAF / 2; off > 0; off >>= 1) {        // within the leaf's 32 lanes (half a wave)
-#pragma unroll
-        for (int c = 0; c < 6; ++c) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], off, 64)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], off, 64)); }
-        bad |= __shfl_xor((int)bad, off, 64) != 0;
-    }
-    if ((threadIdx.x & (RL_LEAF - 1)) || i >= ns) return;
-    const int n = min(RL_LEAF, ns - i), leaf = i / RL_LEAF;
-    float* o = leaves + (size_t)(leaf >> 1) * 32 + (leaf & 1);
+// The same launch writes the COARSE leaves (RL_COARSE pairs each: the RL_COARSE / RL_LEAF consecutive fine leaves of one coarse
+// leaf, same sorted order) to `coarse`, in the same layout and by the same rules: the min / max over its pairs are the min / max
+// of its fine leaves' (exact), pc and pe follow from them as for a fine leaf.
+__device__ __forceinline__ void rl_leaf_store(float* o, int n, bool bad, const float* lo, const float* hi) {
     o[6] = (float)n;
     if (bad) {
 #pragma unroll
@@ -608,45 +592,96 @@ void k_leaf_build(const float* __restrict__ pq, int ns, const unsigned* __restri
 #pragma unroll
     for (int c = 0; c < 3; ++c) { o[2 * c] = pc[c]; o[8 + 2 * c] = pe[c]; o[16 + 2 * c] = lo[3 + c]; o[24 + 2 * c] = hi[3 + c]; }
 }
+__global__ __launch_bounds__(256)
+void k_leaf_build(const float* __restrict__ pq, int ns, const unsigned* __restrict__ order, float* __restrict__ leaves, float* __restrict__ coarse) {
+    const int i = blockIdx.x * 256 + threadIdx.x;     // sorted position; the grid covers whole leaves (and so whole coarse leaves)
+    float lo[6], hi[6];
+    bool bad = false;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { lo[c] = INFINITY; hi[c] = -INFINITY; }
+    if (i < ns) {
+        const float* g = pq + (size_t)order[i] * 8;
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { const float v = g[c]; lo[c] = v; hi[c] = v; bad |= !(fabsf(v) <= FLT_MAX); }
+    }
+#pragma unroll
+    for (int off = RL_LEAF / 2; off > 0; off >>= 1) {        // within the leaf's 32 lanes (half a wave)
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { lo[c] = fminf(lo[c], __shfl_xor(lo[c], off, 64)); hi[c] = fmaxf(hi[c], __shfl_xor(hi[c], off, 64)); }
+        bad |= __shfl_xor((int)bad, off, 64) != 0;
+    }
+    constexpr int FINE = 256 / RL_LEAF, PER = RL_COARSE / RL_LEAF;          // fine leaves per workgroup, per coarse leaf
+    __shared__ float s_lo[FINE][6], s_hi[FINE][6];
+    __shared__ int s_bad[FINE];
+    const int f = threadIdx.x / RL_LEAF;
+    if (!(threadIdx.x & (RL_LEAF - 1))) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { s_lo[f][c] = lo[c]; s_hi[f][c] = hi[c]; }
+        s_bad[f] = bad;
+        if (i < ns) {
+            const int leaf = i / RL_LEAF;
+            rl_leaf_store(leaves + (size_t)(leaf >> 1) * 32 + (leaf & 1), min(RL_LEAF, ns - i), bad, lo, hi);
+        }
+    }
+    __syncthreads();
+    const int k = threadIdx.x;                                             // coarse leaf of this workgroup
+    const int i0 = blockIdx.x * 256 + k * RL_COARSE;
+    if (k >= 256 / RL_COARSE || i0 >= ns) return;
+    float clo[6], chi[6];
+    bool cbad = false;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) { clo[c] = INFINITY; chi[c] = -INFINITY; }
+#pragma unroll
+    for (int j = 0; j < PER; ++j) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) { clo[c] = fminf(clo[c], s_lo[k * PER + j][c]); chi[c] = fmaxf(chi[c], s_hi[k * PER + j][c]); }
+        cbad |= s_bad[k * PER + j] != 0;
+    }
+    const int leaf = i0 / RL_COARSE;
+    rl_leaf_store(coarse + (size_t)(leaf >> 1) * 32 + (leaf & 1), min(RL_COARSE, ns - i0), cbad, clo, chi);
+}
 // A workgroup per 64 hypotheses (lane = hypothesis), its RB_SPLIT waves walking RB_SPLIT ranges of the leaf pairs; leaf values are
 // wave-uniform (scalar loads), two leaves per packed instruction.  A lane stops adding once its partial bound exceeds the best count
-// of the earlier batches (the hypothesis is live then: the whole bound can only be larger); a wave stops when every lane has, so
-// where nothing can be pruned the pass ends early by itself.  The partial bounds meet in LDS.  Writes bnd[h] (the full bound of a
-// dead hypothesis, INT_MAX for a live one, 0 for a skipped iteration) and appends the live hypotheses to `live` (*n_live of them,
-// zeroed by k_ransac_plan).  (One lane per hypothesis walking all the leaves alone gives one wave per SIMD for a 65,536-hypothesis
-// batch, every scalar load's latency exposed.)
+// of the earlier batches (the hypothesis cannot be proven dead on these leaves then: the whole bound can only be larger); a wave
+// stops when every lane has, so where nothing can be pruned the pass ends early by itself.  The partial bounds meet in LDS.
+// (One lane per hypothesis walking all the leaves alone gives one wave per SIMD for a 65,536-hypothesis batch, every scalar load's
+// latency exposed.)
+// Two levels (round 6).  88 % of the hypotheses are dead, and a dead one walks every leaf.  The coarse leaves (RL_COARSE pairs,
+// each the union of 4 fine leaves) already prove 81 % of them dead at a quarter of the leaf tests, so the bound runs twice:
+//   RB_COARSE   every hypothesis of the batch over the coarse leaves.  Coarse sum <= best: dead, bnd[h] = the coarse sum (an
+//               upper bound of the count, <= best: all k_ransac_select needs).  No band or the gate closed: live.  The rest is
+//               undecided and appended to `und` (*n_und of them, zeroed by k_ransac_plan).
+//   k_ransac_bound_fine   the undecided hypotheses over the fine leaves: the one-level walk, early stop included; dead with
+//               bnd[h] = the fine sum, or live.
+// A fine leaf's pairs lie inside its coarse leaf's boxes, so in real arithmetic a coarse leaf that fails has children that all
+// fail, the coarse sum is >= the fine sum and coarse-dead implies fine-dead.  In f32 the two tests round differently (other pc,
+// pe; a fine box's rounded-up pe may poke an ulp past its parent's): so the coarse test fails a leaf only on g2 > (s + 5 E)^2,
+// not 3 E.  By (1) below, run both ways, a coarse f32 gap above s + 5 E puts every child's f32 gap above s + 5 E - 2 (14.2 u A +
+// 3 u (s + 5 E)) - 2 u A > s + 3 E (E >= 16 u (A + s)): every child fails its own test too.  Each coarse level verdict is thus
+// the fine walk's, and the live list is exactly the one-level walk's (RB_ONE, kept for the study build's A/B:
+// TDV_RANSAC_BOUND_LEVELS=1; tests/test_ransac_leaf_bound_two_levels.py checks the implication in emulated f32).  A dead
+// hypothesis' bnd is its coarse or its fine sum, whichever level decided it; a live one's is INT_MAX, a skipped iteration's 0.
+// Live hypotheses are appended to `live` (*n_live of them, zeroed by k_ransac_plan).
 constexpr int RB_SPLIT = 16;
-__global__ __launch_bounds__(64 * RB_SPLIT)
-void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __restrict__ triples, int count, const float* __restrict__ leaves, int n_lpairs,
-                    const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
-                    int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int h = blockIdx.x * 64 + lane;
-    __shared__ int s_ub[64];
-    if (wave == 0) s_ub[lane] = 0;
-    const bool valid = h < count && triples[h].w != 0;
-    float r[12];
-#pragma unroll
-    for (int e = 0; e < 12; ++e) r[e] = valid ? hyp[(size_t)e * h_pad + h] : 0.f;
-    // the band's E (k_ransac_hypotheses), from the same f32 operations
-    const float A = ransac_band_reach(r, __uint_as_float(*pmax));
-    const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
-    const bool bounded = E < 0.25f * sqrt_tau;                    // false for NaN (non-finite data or hypothesis)
-    const float sb = sqrt_tau + 3.f * E;
-    const float tb = sb * sb * (1.0f + 1e-6f);
-    const int best = state[0];
-    // Gate: with the best under a 32nd of the points nothing is pruned (true share 0.02: best 0.017 N), and the walk - whose RB_SPLIT
-    // partial sums each have to pass the best before a wave stops - cost 8.5 % there: every hypothesis is live without it.  At a true
-    // share of 0.1 (best 0.09 N) it still prunes 14 % of the tests and gains a point.
-    const bool walk = best >= ns / 32;
+enum { RB_ONE = 0, RB_COARSE = 1 };
+__device__ __forceinline__ void rb_append(bool take, int lane, int h, int* __restrict__ list, int* __restrict__ n) {
+    const unsigned long long m = __ballot(take);
+    if (!m) return;
+    const int lead = (int)__builtin_ctzll(m);
+    int at = 0;
+    if (lane == lead) at = atomicAdd(n, __popcll(m));
+    at = __shfl(at, lead, 64);
+    if (take) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
+}
+// One wave's share [k0, k1) of the leaf pairs for its lane's hypothesis (r: column-major R, t): the sizes of the leaves that
+// may hold an inlier, added until the sum exceeds `best` (done).  tb = (s + margin E)^2 (1 + 1e-6).
+__device__ __forceinline__ int rb_walk(const float* r, const float* __restrict__ leaves, int k0, int k1, float tb, int best, bool done) {
     int ub = 0;
-    bool done = !valid || !bounded || !walk;
     v2f rr[12], ar[9];
 #pragma unroll
     for (int e = 0; e < 12; ++e) rr[e] = (v2f){r[e], r[e]};
 #pragma unroll
     for (int e = 0; e < 9; ++e) ar[e] = (v2f){fabsf(r[e]), fabsf(r[e])};
-    const int per = (n_lpairs + RB_SPLIT - 1) / RB_SPLIT, k0 = __builtin_amdgcn_readfirstlane(wave) * per, k1 = min(n_lpairs, k0 + per);   // (uniform: scalar loads)
     for (int k = k0; k < k1; ++k) {
         if (((k - k0) & 7) == 0 && !__any(!done)) break;
         const float* __restrict__ g = leaves + (size_t)k * 32;
@@ -669,20 +704,104 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __rest
         const int n2 = (!(g2.x > tb) ? (int)v[6] : 0) + (!(g2.y > tb) ? (int)v[7] : 0);
         if (!done) { ub += n2; done = ub > best; }
     }
+    return ub;
+}
+// The hypothesis' band test and its bound threshold (k_ransac_hypotheses' E, from the same f32 operations)
+struct RbHyp { float r[12]; float tb; bool bounded; };
+__device__ __forceinline__ RbHyp rb_load(const float* __restrict__ hyp, int h_pad, int h, bool valid, const unsigned* __restrict__ pmax,
+                                         float sqrt_tau, float band_u, float margin) {
+    RbHyp o;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) o.r[e] = valid ? hyp[(size_t)e * h_pad + h] : 0.f;
+    const float A = ransac_band_reach(o.r, __uint_as_float(*pmax));
+    const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
+    o.bounded = E < 0.25f * sqrt_tau;                             // false for NaN (non-finite data or hypothesis)
+    const float sb = sqrt_tau + margin * E;
+    o.tb = sb * sb * (1.0f + 1e-6f);
+    return o;
+}
+// RB_ONE / RB_COARSE: a workgroup per 64 hypotheses of the batch.  RB_COARSE also zeroes the fine level's per-slot sums (acc) of
+// the hypotheses it leaves undecided and the ticket of its slot block.
+template <int MODE>
+__global__ __launch_bounds__(64 * RB_SPLIT)
+void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __restrict__ triples, int count, const float* __restrict__ leaves, int n_lpairs,
+                    const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
+                    int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
+                    int* __restrict__ acc, int* __restrict__ ticket) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int h = blockIdx.x * 64 + lane;
+    __shared__ int s_ub[64];
+    if (wave == 0) s_ub[lane] = 0;
+    if (MODE == RB_COARSE && threadIdx.x == 0) ticket[blockIdx.x] = 0;
+    const bool valid = h < count && triples[h].w != 0;
+    const RbHyp o = rb_load(hyp, h_pad, h, valid, pmax, sqrt_tau, band_u, MODE == RB_COARSE ? 5.f : 3.f);   // (coarse margin 5 E: see above)
+    const int best = state[0];
+    // Gate: with the best under a 32nd of the points nothing is pruned (true share 0.02: best 0.017 N), and the walk - whose RB_SPLIT
+    // partial sums each have to pass the best before a wave stops - cost 8.5 % there: every hypothesis is live without it.  At a true
+    // share of 0.1 (best 0.09 N) it still prunes 14 % of the tests and gains a point.
+    const bool walk = best >= ns / 32;
+    const int per = (n_lpairs + RB_SPLIT - 1) / RB_SPLIT, k0 = __builtin_amdgcn_readfirstlane(wave) * per, k1 = min(n_lpairs, k0 + per);   // (uniform: scalar loads)
+    const int ub = rb_walk(o.r, leaves, k0, k1, o.tb, best, !valid || !o.bounded || !walk);
     __syncthreads();                                 // (s_ub zeroed)
     if (ub) atomicAdd(&s_ub[lane], ub);
     __syncthreads();
-    if (wave != 0 || h >= count) return;
+    if (wave != 0) return;
+    const bool here = h < count;
     const int total = s_ub[lane];
-    const bool is_live = valid && (!bounded || !walk || total > best);
-    bnd[h] = is_live ? INT_MAX : (valid ? total : 0);
-    const unsigned long long m = __ballot(is_live);
-    if (!m) return;
-    const int lead = (int)__builtin_ctzll(m);
-    int at = 0;
-    if (lane == lead) at = atomicAdd(n_live, __popcll(m));
-    at = __shfl(at, lead, 64);
-    if (is_live) live[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
+    const bool gated = valid && (!o.bounded || !walk);            // live without a walk
+    const bool undecided = MODE == RB_COARSE && valid && !gated && total > best;
+    const bool is_live = gated || (MODE == RB_ONE && valid && total > best);
+    if (here && !undecided) bnd[h] = is_live ? INT_MAX : (valid ? total : 0);
+    rb_append(is_live, lane, h, live, n_live);
+    if (MODE == RB_COARSE) {
+        const unsigned long long m = __ballot(undecided);
+        if (!m) return;
+        const int lead = (int)__builtin_ctzll(m);
+        int at = 0;
+        if (lane == lead) at = atomicAdd(n_und, __popcll(m));
+        at = __shfl(at, lead, 64);
+        if (undecided) { const int slot = at + __popcll(m & ((1ull << lane) - 1ull)); und[slot] = h; acc[slot] = 0; }
+    }
+}
+// k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a fifth of the batch, too few workgroups to fill the chip with
+// one workgroup per 64 of them, so the leaf pairs are cut into RB_FINE_Y ranges as well (blockIdx.y); a workgroup adds its 64 partial
+// sums to acc[slot], and the last workgroup of a slot block (ticket) decides: live on a total > best, dead with bnd = the total
+// otherwise.  A partial sum that stopped early exceeds best alone, so a stop anywhere makes the total exceed it too; without one
+// the total is the full fine sum - the one-level walk's verdict and bnd.  The grid covers the whole batch (the host does not know
+// how many hypotheses are undecided); the workgroups past the list return at once.
+constexpr int RB_FINE_Y = 4;
+__global__ __launch_bounds__(64 * RB_SPLIT)
+void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* __restrict__ leaves, int n_lpairs,
+                         const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state,
+                         int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live, const int* __restrict__ und, const int* __restrict__ n_und,
+                         int* __restrict__ acc, int* __restrict__ ticket) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int n = *n_und, best = state[0];
+    const int per_y = (n_lpairs + RB_FINE_Y - 1) / RB_FINE_Y, y0 = blockIdx.y * per_y, y1 = min(n_lpairs, y0 + per_y);
+    const int per = (y1 - y0 + RB_SPLIT - 1) / RB_SPLIT;
+    const int k0 = min(y1, y0 + __builtin_amdgcn_readfirstlane(wave) * per), k1 = min(y1, k0 + per);
+    __shared__ int s_ub[64];
+    const int xb = blockIdx.x;
+    if (xb * 64 >= n) return;                        // workgroup-uniform (the grid is sized for the whole batch)
+    const int slot = xb * 64 + lane;
+    const int h = slot < n ? und[slot] : -1;
+    if (wave == 0) s_ub[lane] = 0;
+    const RbHyp o = rb_load(hyp, h_pad, h, h >= 0, pmax, sqrt_tau, band_u, 3.f);
+    const int ub = rb_walk(o.r, leaves, k0, k1, o.tb, best, h < 0);
+    __syncthreads();                                 // (s_ub zeroed)
+    if (ub) atomicAdd(&s_ub[lane], ub);
+    __syncthreads();
+    if (wave != 0) return;
+    const int part = s_ub[lane];
+    if (h >= 0 && part) atomicAdd(&acc[slot], part);
+    __threadfence();
+    int arrived = 0;
+    if (lane == 0) arrived = atomicAdd(&ticket[xb], 1);
+    if (__shfl(arrived, 0, 64) != (int)gridDim.y - 1) return;    // not the last workgroup of this slot block
+    const int total = h >= 0 ? atomicAdd(&acc[slot], 0) : 0;
+    const bool is_live = h >= 0 && total > best;
+    if (h >= 0) bnd[h] = is_live ? INT_MAX : total;
+    rb_append(is_live, lane, h, live, n_live);
 }
 
 #ifdef TDV_STUDY
@@ -964,20 +1083,24 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     const bool bound_env_off = getenv("TDV_RANSAC_BOUND") && atoi(getenv("TDV_RANSAC_BOUND")) == 0;   // A/B knob (read per call: the tests switch it)
     const bool bound = bailout && !merge_on && !bound_env_off;
     const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_lpairs = (n_leaves + 1) / 2;
-    float* leaves = nullptr;
+    const int n_cleaves = (ns + RL_COARSE - 1) / RL_COARSE, n_cpairs = (n_cleaves + 1) / 2;
+    const bool one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
+    float* leaves = nullptr; float* cleaves = nullptr;
     if (bound) {
         unsigned* enc = nullptr; unsigned long long* keys = nullptr; unsigned* vals = nullptr;
         TDV_TRY(ws_alloc(ctx, 12, &enc));
         TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &keys));
         TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &vals));
         TDV_TRY(ws_alloc(ctx, (size_t)n_lpairs * 32, &leaves));
+        TDV_TRY(ws_alloc(ctx, (size_t)n_cpairs * 32, &cleaves));
         TDV_HIP(ctx, hipMemsetAsync(leaves, 0, (size_t)n_lpairs * 32 * sizeof(float), s));
+        TDV_HIP(ctx, hipMemsetAsync(cleaves, 0, (size_t)n_cpairs * 32 * sizeof(float), s));
         TDV_HIP(ctx, hipMemsetAsync(enc, 0xff, 24, s));
         TDV_HIP(ctx, hipMemsetAsync(enc + 6, 0, 24, s));
         k_leaf_bounds<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc);
         k_leaf_keys<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc, keys, vals);
         TDV_TRY(radix_sort_pairs_dev(ctx, keys, keys + ns, vals, vals + ns, (size_t)ns, 6 * RL_BITS));
-        k_leaf_build<<<(n_leaves * RL_LEAF + 255) / 256, 256, 0, s>>>(pq, ns, vals + ns, leaves);
+        k_leaf_build<<<(n_leaves * RL_LEAF + 255) / 256, 256, 0, s>>>(pq, ns, vals + ns, leaves, cleaves);
         TDV_CHECK_LAUNCH(ctx);
     }
     float* pq2 = nullptr;
@@ -1010,7 +1133,8 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     float* hyp[2] = {nullptr, nullptr}; int* counts[2] = {nullptr, nullptr}; int4* d_tri[2] = {nullptr, nullptr};
     double* slabs = nullptr; double* d_out2 = nullptr; float* d_best12 = nullptr;
     int* d_list[2] = {nullptr, nullptr};
-    int* d_live[2] = {nullptr, nullptr}; int* d_bnd[2] = {nullptr, nullptr}; int* d_nlive = nullptr;
+    int* d_live[2] = {nullptr, nullptr}; int* d_bnd[2] = {nullptr, nullptr}; int* d_und[2] = {nullptr, nullptr}; int* d_nlive = nullptr;
+    int* d_acc[2] = {nullptr, nullptr}; int* d_ticket[2] = {nullptr, nullptr};
     for (int q = 0; q < 2; ++q) {
         TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &hyp[q]));
         TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &counts[q]));
@@ -1018,8 +1142,11 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     }
     if (bailout) for (int q = 0; q < 2; ++q) TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_list[q]));   // a batch's list lives until its phase 2 has run, behind the next batch's phase 1
     if (bound) {
-        for (int q = 0; q < 2; ++q) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_live[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_bnd[q])); }
-        TDV_TRY(ws_alloc(ctx, 2, &d_nlive));
+        for (int q = 0; q < 2; ++q) {
+            TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_live[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_bnd[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_und[q]));
+            TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_acc[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad / 64, &d_ticket[q]));
+        }
+        TDV_TRY(ws_alloc(ctx, 4, &d_nlive));     // [q]: live hypotheses of batch buffer q, [2 + q]: undecided ones after the coarse level
     }
     const int rblocks = (ns + 255) / 256;
     TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
@@ -1045,12 +1172,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     const int first_batch = bailout ? 8 * RS_HYP_PER_BLOCK : batch;
     auto prepare = [&](int q, int it0) -> int {    // host: draw + pack the triples of one batch
         const int cnt = std::min(it0 == 0 ? first_batch : batch, max_iterations - it0);
-        uint64_t d[3];
-        for (int k = 0; k < cnt; ++k) {
-            stream_idx.next(d);
-            int valid = !(d[0] == d[1] || d[1] == d[2] || d[0] == d[2]);  // registration.cpp:240
-            h_tri[q][k] = make_int4((int)d[0], (int)d[1], (int)d[2], valid);
-        }
+        stream_idx.next_batch(cnt, reinterpret_cast<int*>(h_tri[q]));     // (i0, i1, i2, valid: registration.cpp:240)
         return cnt;
     };
     // point ranges of a scoring dispatch with hb hypothesis blocks (counts are accumulated by atomics, so the cut may differ per dispatch)
@@ -1113,8 +1235,18 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
                     if (bounded) {
                         // RansacLeafBound: the dead hypotheses out, then phase 1 of the live ones as job B (workgroups stride over its
                         // items; a grid of job A's size covers them in about one pass whatever the number of live blocks)
-                        k_ransac_bound<<<(cnt + 63) / 64, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, d_tri[q], cnt, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
-                                                                          d_state, ns, d_bnd[q], d_live[q], d_nlive + q);
+                        const int bgrid = (cnt + 63) / 64;
+                        if (one_level)
+                            k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, d_tri[q], cnt, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
+                                                                                   d_state, ns, d_bnd[q], d_live[q], d_nlive + q, nullptr, nullptr, nullptr, nullptr);
+                        else {
+                            k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, d_tri[q], cnt, cleaves, n_cpairs, d_pmax, sqrt_tau, band_u,
+                                                                                      d_state, ns, d_bnd[q], d_live[q], d_nlive + q, d_und[q], d_nlive + 2 + q,
+                                                                                      d_acc[q], d_ticket[q]);
+                            k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
+                                                                                                      d_state, d_bnd[q], d_live[q], d_nlive + q, d_und[q], d_nlive + 2 + q,
+                                                                                                      d_acc[q], d_ticket[q]);
+                        }
                         ScoreJob jl{hyp[q], counts[q], d_plan[q], d_live[q], hb, 0, d_nlive + q};
                         ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
                         k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, d_rescored);

@@ -309,6 +309,9 @@ public:
     TripleStream(uint32_t seed, uint64_t n);
     ~TripleStream();
     void next(uint64_t* out3);
+    // `count` triples at once, as int4 (i0, i1, i2, valid) with valid = the three indices differ (registration.cpp:240);
+    // indices are below n <= 2^31 here (the batch loop's clouds)
+    void next_batch(int count, int* out4);
 private:
     struct Impl; Impl* impl_; uint64_t n_;
     TripleStream(const TripleStream&) = delete;
