@@ -58,6 +58,7 @@ ABI_SYMBOLS = [
     "tdv_gicp", "tdv_gicp_dev", "tdv_gicp_batch_dev",
     "tdv_color_gradients", "tdv_color_gradients_dev", "tdv_colored_icp", "tdv_colored_icp_dev", "tdv_colored_icp_batch_dev",
     "tdv_fgr_default_params", "tdv_fgr", "tdv_fgr_dev", "tdv_fgr_correspondences",
+    "tdv_plane_default_params", "tdv_segment_planes", "tdv_segment_planes_dev",
 ]
 
 
@@ -113,6 +114,37 @@ def fgr_params(**kw):
     return p
 
 
+TDV_PLANE_CHUNK = 1024
+TDV_PLANE_MAX = 16
+
+
+class PlaneParamsC(C.Structure):
+    _fields_ = [("probability", C.c_double), ("distance_threshold", C.c_float), ("num_iterations", C.c_int), ("max_planes", C.c_int),
+                ("min_inliers", C.c_int), ("refit", C.c_int), ("seed", C.c_uint32)]
+
+
+class PlaneResultC(C.Structure):
+    _fields_ = [("plane", C.c_float * 4), ("hypothesis", C.c_float * 4), ("fitness", C.c_float), ("rmse", C.c_float),
+                ("inliers", C.c_int), ("candidates", C.c_int), ("best_iteration", C.c_int), ("iterations_run", C.c_int)]
+
+
+def plane_params(**kw):
+    """tdv_plane_default_params with the given fields replaced (Open3D's segment_plane names, plus max_planes, min_inliers, refit, seed)."""
+    p = PlaneParamsC()
+    lib().tdv_plane_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(PlaneParamsC._fields_):
+            raise TypeError("unknown plane parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _plane_results(res, n):
+    return [dict(plane=np.array(r.plane[:], np.float32), hypothesis=np.array(r.hypothesis[:], np.float32), fitness=np.float32(r.fitness),
+                 rmse=np.float32(r.rmse), inliers=r.inliers, candidates=r.candidates, best_iteration=r.best_iteration,
+                 iterations_run=r.iterations_run) for r in res[:n]]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -151,6 +183,7 @@ def lib():
             l.tdv_ctx_last_ransac_rescore.restype = C.c_double
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
             l.tdv_fgr_default_params.restype = None
+            l.tdv_plane_default_params.restype = None
             _lib = l
     return _lib
 
@@ -637,6 +670,37 @@ class Context:
         _check(self._h, lib().tdv_fgr_correspondences(*args, _ptr(mutual), nm.value, _ptr(tuples), nu.value, C.byref(nm), C.byref(nu),
                                                       C.byref(tr)), "tdv_fgr_correspondences")
         return dict(mutual=mutual, tuples=tuples, n_mutual=nm.value, n_tuple=nu.value, trials_run=tr.value)
+
+    # ---------------------------------------------------------------- plane segmentation (include/tdv_hip.h: tdv_segment_planes)
+    def segment_planes(self, xyz, **params):
+        """tdv_segment_planes: (list of one dict per plane kept - plane, hypothesis, fitness, rmse, inliers, candidates, best_iteration,
+        iterations_run - and labels int32[n]: k for the points of plane k, -1 for the rest)."""
+        xyz = _f32(xyz).reshape(-1, 3); n = len(xyz)
+        p = plane_params(**params)
+        res = (PlaneResultC * TDV_PLANE_MAX)(); npl = C.c_int()
+        labels = np.empty(max(n, 1), np.int32)
+        _check(self._h, lib().tdv_segment_planes(self._h, _ptr(xyz), n, C.byref(p), res, C.byref(npl), _ptr(labels)), "tdv_segment_planes")
+        return _plane_results(res, npl.value), labels[:n]
+
+    def segment_planes_dev(self, d_xyz, n, d_labels=None, d_rest=None, **params):
+        """tdv_segment_planes_dev on device pointers: (list of plane dicts as segment_planes, n_rest).  d_labels (int32[n]) and d_rest
+        (float[3n]: the unlabelled points in ascending index) are optional."""
+        p = plane_params(**params)
+        res = (PlaneResultC * TDV_PLANE_MAX)(); npl = C.c_int(); nr = C.c_int()
+        _check(self._h, lib().tdv_segment_planes_dev(self._h, _ptr(d_xyz), n, C.byref(p), res, C.byref(npl), _ptr(d_labels), _ptr(d_rest),
+                                                     C.byref(nr)), "tdv_segment_planes_dev")
+        return _plane_results(res, npl.value), nr.value
+
+    def segment_plane(self, xyz, distance_threshold=0.01, ransac_n=3, num_iterations=100, probability=0.99999999, seed=42):
+        """Open3D's PointCloud.segment_plane: (plane_model float32[4], inlier indices int64, ascending).  One plane; a search
+        that keeps none gives zeros and no index."""
+        if ransac_n != 3:
+            raise ValueError("segment_plane: only ransac_n = 3 is provided (got %r)" % (ransac_n,))
+        planes, labels = self.segment_planes(xyz, distance_threshold=distance_threshold, num_iterations=num_iterations,
+                                             probability=probability, seed=seed, max_planes=1)
+        if not planes:
+            return np.zeros(4, np.float32), np.zeros(0, np.int64)
+        return planes[0]["plane"], np.nonzero(labels == 0)[0]
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

@@ -503,6 +503,69 @@ int tdv_fgr_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, in
 int tdv_fgr_correspondences(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft,
                             const tdv_fgr_params* params, int* out_mutual, int cap_mutual, int* out_tuple, int cap_tuple,
                             int* n_mutual, int* n_tuple, long long* trials_run);
+/* Plane segmentation by RANSAC (Open3D's PointCloud::segment_plane(distance_threshold, ransac_n = 3, num_iterations, probability)),
+ * repeated to strip several planes in one call (floor, then walls).  Open3D's rand() and its OpenMP order are replaced by the
+ * deterministic rules below.  Plane k = 0, 1, ... is searched among the CANDIDATES of round k: the points no earlier plane labelled, in
+ * ascending original index; m_k = their count (m_0 = n).  Every step, in order:
+ *  1. Draw: hypothesis t = 0 .. num_iterations - 1 of round k takes words x0, x1, x2 of Philox4x32-10 with counter (t, k, 0, 0) and key
+ *     (seed, 1) (FGR's key is (seed, 0): the streams differ); candidate j = (uint32)(((uint64)x_j * m_k) >> 32).  A repeated index makes
+ *     the hypothesis invalid.
+ *  2. Plane, f64 from the f32 inputs without contraction (Open3D's ComputeTrianglePlane, the order made explicit): u = p1 - p0,
+ *     v = p2 - p0 per component; n = (u_y v_z - u_z v_y, u_z v_x - u_x v_z, u_x v_y - u_y v_x); s = (n_x n_x + n_y n_y) + n_z n_z;
+ *     invalid iff !(s > 0) or s is not finite; r = sqrt(s), (a, b, c) = n / r per component, d = -((a p0x + b p0y) + c p0z).
+ *  3. Score: dist(p) = |((a p_x + b p_y) + c p_z) + d|; a candidate is an inlier iff dist < (double)distance_threshold (strict, as
+ *     Open3D; a NaN distance never is); count = the inlier candidates.  An invalid hypothesis scores nothing but counts as run.
+ *  4. Winner and early stop: hypotheses run in chunks of TDV_PLANE_CHUNK; the winner is the largest count, ties to the LOWEST t (Open3D
+ *     breaks ties by rmse in OpenMP order, which does not reproduce).  After each chunk, with b the best count so far and
+ *     f = (double)b / m_k: the round stops iff probability < 1 and b > 0 and (f >= 1 or (L = log(1 - (f * f) * f) < 0 and
+ *     run >= log(1 - probability) / L)), run = the hypotheses evaluated so far - Open3D's break rule at chunk granularity.  Two
+ *     deliberate differences: probability = 1 never stops early (Open3D stops at f = 1), and L = 0 (f^3 below half an ulp of 1, where
+ *     Open3D's bound is -inf) does not stop.  iterations_run = the hypotheses of the chunks evaluated.
+ *  5. Acceptance: plane k is kept iff its winner is valid and count >= min_inliers; its inliers (the winner's membership, as Open3D
+ *     returns it) get label k and leave the candidate set.  Otherwise the search ends and that round labels nothing.  Rounds run until
+ *     max_planes planes are kept, fewer than 3 candidates remain, or a round is rejected.
+ *  6. Reported plane: hypothesis = (a, b, c, d) rounded to f32, negated as a whole if d < 0 (the camera origin lies on the positive
+ *     side: a floor's normal faces the sensor).  With refit (Open3D's closing GetPlaneFromPoints), plane = the least-squares plane of the
+ *     inliers: f64 mean mu and covariance sum_i (p_i - mu)(p_i - mu)^T over the inliers in a fixed order (no division), the unit
+ *     eigenvector of its smallest eigenvalue (cyclic Jacobi in f64), negated if its dot product with the hypothesis normal is < 0,
+ *     d = -((n_x mu_x + n_y mu_y) + n_z mu_z), rounded to f32; plane = hypothesis if that is not finite.  Without refit,
+ *     plane = hypothesis.  fitness = (float)((double)count / m_k); rmse = (float)sqrt(sum dist^2 / count) over the inliers, the sum an
+ *     f64 fixed tree.
+ *  7. Non-finite coordinates have no special case: a hypothesis that draws one is invalid (s is NaN or infinite), such a point is never
+ *     an inlier, and it stays unlabelled.
+ * labels (optional, int[n]): k for the points of plane k, -1 for every other.  d_rest_xyz (optional, float[3n]) receives the unlabelled
+ * points in ascending original index, *n_rest their count (ready for tdv_voxel_downsample_dev).  n < 3: n_planes = 0, every label -1,
+ * rest = the input.  The ctx's ICP switches do not apply.  Not provided: ransac_n > 3, a batched per-instance form, plane removal inside
+ * tdv_register_batch_dev / tdv_refine_batch_dev (a tdv_batch_params field: an ABI change), the C++ operator mirror.
+ * TDV_ERR_BAD_ARG, before anything is enqueued and with out untouched: a NULL ctx, params, out or n_planes; a NULL cloud with n > 0;
+ * n < 0; distance_threshold not finite or not > 0; probability outside (0, 1] or NaN; num_iterations < 1; max_planes outside
+ * [1, TDV_PLANE_MAX]; min_inliers < 3.  tdv_segment_planes takes host arrays; tdv_segment_planes_dev device pointers (it reads back
+ * once, at the end, and returns host structs). */
+#define TDV_PLANE_CHUNK 1024
+#define TDV_PLANE_MAX   16
+typedef struct tdv_plane_params {
+    double   probability;        /* 0.99999999 (Open3D); a double: in f32 it rounds to 1.0 */
+    float    distance_threshold; /* 0.01 */
+    int      num_iterations;     /* 100 (Open3D) */
+    int      max_planes;         /* 1, at most TDV_PLANE_MAX */
+    int      min_inliers;        /* 3 */
+    int      refit;              /* 1 */
+    uint32_t seed;               /* 42 */
+} tdv_plane_params;
+typedef struct tdv_plane_result {
+    float plane[4];        /* (a, b, c, d): a x + b y + c z + d = 0, unit normal */
+    float hypothesis[4];   /* the winning hypothesis' plane */
+    float fitness, rmse;
+    int inliers;           /* points labelled with this plane */
+    int candidates;        /* m_k */
+    int best_iteration;    /* t of the winner */
+    int iterations_run;
+} tdv_plane_result;
+void tdv_plane_default_params(tdv_plane_params* p);
+int tdv_segment_planes(tdv_ctx* ctx, const float* xyz, int n, const tdv_plane_params* params, tdv_plane_result* out /* [max_planes] */,
+                       int* n_planes, int* labels /* int[n], optional */);
+int tdv_segment_planes_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_plane_params* params, tdv_plane_result* out, int* n_planes,
+                           int* d_labels /* optional */, float* d_rest_xyz /* optional, float[3n] */, int* n_rest /* host, optional */);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
