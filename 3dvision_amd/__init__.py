@@ -255,6 +255,38 @@ class RegistrationResult:
     trace_inliers: Optional[np.ndarray] = None
 
 
+def _icp_result(r):
+    """An IcpResultC as the RegistrationResult every ICP call returns."""
+    return RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
+                              iterations=r.iterations, n_corr=r.n_corr)
+
+
+def _icp_batch_args(offsets, T0s):
+    """What a batch call passes for its instances: the offsets as int32, their count, the start poses column-major back to back and the result array."""
+    off = np.ascontiguousarray(offsets, np.int32)
+    n = len(off) - 1
+    T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
+    t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
+    return off, n, t0, (IcpResultC * max(n, 1))()
+
+
+def _instance_rows(arrays):
+    """Per-instance host arrays as (n_b, 3) float32, and their offsets."""
+    rows = [_f32(a).reshape(-1, 3) for a in arrays]
+    off = np.zeros(len(rows) + 1, np.int32)
+    off[1:] = np.cumsum([len(a) for a in rows])
+    return rows, off
+
+
+def _upload_rows(device, rows, width=3):
+    """Host rows - one (n, width) array, or a list of per-instance arrays back to back - as a torch tensor on `device`; one dummy row
+    where there are none, so that the call gets a valid pointer."""
+    import torch
+    if isinstance(rows, list):
+        rows = np.concatenate(rows) if rows else np.zeros((0, width), np.float32)
+    return torch.from_numpy(rows if len(rows) else np.zeros((1, width), np.float32)).to(torch.device("cuda", device))
+
+
 class Context:
     """One tdv_ctx (stream + workspace).  Not thread-safe; one per host thread."""
 
@@ -468,8 +500,7 @@ class Context:
         t0 = to_colmajor16(T0)
         _check(self._h, lib().tdv_icp(self._h, _ptr(src), len(src), _ptr(tgt), _ptr(tn), len(tgt), _ptr(t0), C.c_float(thr),
                                       max_iterations, int(point_to_plane), C.byref(res)), "tdv_icp")
-        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
-                                  iterations=res.iterations, n_corr=res.n_corr)
+        return _icp_result(res)
 
     def icp_correspondences(self, src, tgt, T, thr):
         src = _f32(src); tgt = _f32(tgt)
@@ -486,33 +517,23 @@ class Context:
         t0 = to_colmajor16(T0)
         _check(self._h, lib().tdv_icp_dev(self._h, _ptr(d_src), ns, _ptr(d_tgt), _ptr(d_tgt_normals), nt, _ptr(t0), C.c_float(thr),
                                           max_iterations, int(point_to_plane), int(fixed_iterations), C.byref(res)), "tdv_icp_dev")
-        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
-                                  iterations=res.iterations, n_corr=res.n_corr)
+        return _icp_result(res)
 
     def icp_batch_dev(self, d_src, offsets, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane=True, fixed_iterations=False):
         """ICP of many clouds against one target in one call (device pointers): cloud b = points [offsets[b], offsets[b + 1]) of d_src,
         start pose T0s[b] ((B, 4, 4)).  Per instance what icp_dev returns for that cloud, bit for bit."""
-        off = np.ascontiguousarray(offsets, np.int32)
-        n = len(off) - 1
-        T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
-        t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
-        res = (IcpResultC * max(n, 1))()
+        off, n, t0, res = _icp_batch_args(offsets, T0s)
         _check(self._h, lib().tdv_icp_batch_dev(self._h, _ptr(d_src), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals), nt, _ptr(t0), C.c_float(thr),
                                                 max_iterations, int(point_to_plane), int(fixed_iterations), res), "tdv_icp_batch_dev")
-        return [RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
-                                   iterations=r.iterations, n_corr=r.n_corr) for r in res[:n]]
+        return [_icp_result(r) for r in res[:n]]
 
     def icp_batch(self, sources, tgt, tgt_normals, T0s, thr, max_iterations=200, point_to_plane=True):
         """icp_batch_dev on host clouds: a list of (n_b, 3) arrays against one target, uploaded with torch."""
         import torch
-        dev = torch.device("cuda", self.device)
-        srcs = [_f32(a).reshape(-1, 3) for a in sources]
-        off = np.zeros(len(srcs) + 1, np.int32)
-        off[1:] = np.cumsum([len(a) for a in srcs])
-        cat = np.concatenate(srcs) if srcs and off[-1] else np.zeros((1, 3), np.float32)
+        srcs, off = _instance_rows(sources)
         tgt = _f32(tgt); tn = _f32(tgt_normals)
-        d_src = torch.from_numpy(cat).to(dev); d_tgt = torch.from_numpy(tgt if len(tgt) else np.zeros((1, 3), np.float32)).to(dev)
-        d_tn = torch.from_numpy(tn).to(dev) if tn is not None else None
+        d_src = _upload_rows(self.device, srcs); d_tgt = _upload_rows(self.device, tgt)
+        d_tn = torch.from_numpy(tn).to(torch.device("cuda", self.device)) if tn is not None else None
         return self.icp_batch_dev(d_src.data_ptr(), off, d_tgt.data_ptr(), None if d_tn is None else d_tn.data_ptr(), len(tgt), T0s, thr,
                                   max_iterations, point_to_plane)
 
@@ -524,47 +545,33 @@ class Context:
         t0 = to_colmajor16(T0)
         _check(self._h, lib().tdv_gicp(self._h, _ptr(src), _ptr(sn), len(src), _ptr(tgt), _ptr(tn), len(tgt), _ptr(t0), C.c_float(thr),
                                        max_iterations, C.c_float(epsilon), C.byref(res)), "tdv_gicp")
-        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
-                                  iterations=res.iterations, n_corr=res.n_corr)
+        return _icp_result(res)
 
     def gicp_dev(self, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, T0, thr, max_iterations, epsilon=1e-3, fixed_iterations=False):
         res = IcpResultC()
         t0 = to_colmajor16(T0)
         _check(self._h, lib().tdv_gicp_dev(self._h, _ptr(d_src), _ptr(d_src_normals), ns, _ptr(d_tgt), _ptr(d_tgt_normals), nt, _ptr(t0),
                                            C.c_float(thr), max_iterations, C.c_float(epsilon), int(fixed_iterations), C.byref(res)), "tdv_gicp_dev")
-        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
-                                  iterations=res.iterations, n_corr=res.n_corr)
+        return _icp_result(res)
 
     def gicp_batch_dev(self, d_src, d_src_normals, offsets, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, epsilon=1e-3, fixed_iterations=False):
         """GICP of many clouds against one target in one call (device pointers; the source normals laid out like d_src).  Per instance
         what gicp_dev returns for that cloud, bit for bit."""
-        off = np.ascontiguousarray(offsets, np.int32)
-        n = len(off) - 1
-        T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
-        t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
-        res = (IcpResultC * max(n, 1))()
+        off, n, t0, res = _icp_batch_args(offsets, T0s)
         _check(self._h, lib().tdv_gicp_batch_dev(self._h, _ptr(d_src), _ptr(d_src_normals), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals), nt,
                                                  _ptr(t0), C.c_float(thr), max_iterations, C.c_float(epsilon), int(fixed_iterations), res),
                "tdv_gicp_batch_dev")
-        return [RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
-                                   iterations=r.iterations, n_corr=r.n_corr) for r in res[:n]]
+        return [_icp_result(r) for r in res[:n]]
 
     def gicp_batch(self, sources, source_normals, tgt, tgt_normals, T0s, thr, max_iterations=200, epsilon=1e-3):
         """gicp_batch_dev on host clouds: lists of (n_b, 3) points and normals against one target, uploaded with torch."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        srcs = [_f32(a).reshape(-1, 3) for a in sources]
-        sns = [_f32(a).reshape(-1, 3) for a in source_normals]
-        if [len(a) for a in sns] != [len(a) for a in srcs]:
+        srcs, off = _instance_rows(sources)
+        sns, offn = _instance_rows(source_normals)
+        if list(offn) != list(off):
             raise ValueError("gicp_batch: one normal per source point")
-        off = np.zeros(len(srcs) + 1, np.int32)
-        off[1:] = np.cumsum([len(a) for a in srcs])
-        cat = np.concatenate(srcs) if srcs and off[-1] else np.zeros((1, 3), np.float32)
-        catn = np.concatenate(sns) if sns and off[-1] else np.zeros((1, 3), np.float32)
         tgt = _f32(tgt); tn = _f32(tgt_normals)
-        d_src = torch.from_numpy(cat).to(dev); d_sn = torch.from_numpy(catn).to(dev)
-        d_tgt = torch.from_numpy(tgt if len(tgt) else np.zeros((1, 3), np.float32)).to(dev)
-        d_tn = torch.from_numpy(tn if len(tn) else np.zeros((1, 3), np.float32)).to(dev)
+        d_src = _upload_rows(self.device, srcs); d_sn = _upload_rows(self.device, sns)
+        d_tgt = _upload_rows(self.device, tgt); d_tn = _upload_rows(self.device, tn)
         return self.gicp_batch_dev(d_src.data_ptr(), d_sn.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), len(tgt), T0s, thr,
                                    max_iterations, epsilon)
 
@@ -588,8 +595,7 @@ class Context:
         t0 = to_colmajor16(T0)
         _check(self._h, lib().tdv_colored_icp(self._h, _ptr(src), _ptr(rgb), len(src), _ptr(tgt), _ptr(tn), _ptr(tc), len(tgt), _ptr(t0),
                                               C.c_float(thr), max_iterations, C.c_float(lambda_geometric), C.byref(res)), "tdv_colored_icp")
-        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
-                                  iterations=res.iterations, n_corr=res.n_corr)
+        return _icp_result(res)
 
     def colored_icp_dev(self, d_src, d_src_rgb, ns, d_tgt, d_tgt_normals, d_tgt_color, nt, T0, thr, max_iterations, lambda_geometric=0.968,
                         fixed_iterations=False):
@@ -598,41 +604,27 @@ class Context:
         _check(self._h, lib().tdv_colored_icp_dev(self._h, _ptr(d_src), _ptr(d_src_rgb), ns, _ptr(d_tgt), _ptr(d_tgt_normals), _ptr(d_tgt_color), nt,
                                                   _ptr(t0), C.c_float(thr), max_iterations, C.c_float(lambda_geometric), int(fixed_iterations),
                                                   C.byref(res)), "tdv_colored_icp_dev")
-        return RegistrationResult(transformation=from_colmajor16(res.T), fitness=np.float32(res.fitness), rmse=np.float32(res.rmse),
-                                  iterations=res.iterations, n_corr=res.n_corr)
+        return _icp_result(res)
 
     def colored_icp_batch_dev(self, d_src, d_src_rgb, offsets, d_tgt, d_tgt_normals, d_tgt_color, nt, T0s, thr, max_iterations,
                               lambda_geometric=0.968, fixed_iterations=False):
         """Colored ICP of many clouds against one target in one call (device pointers; the source colours laid out like d_src).  Per
         instance what colored_icp_dev returns for that cloud, bit for bit."""
-        off = np.ascontiguousarray(offsets, np.int32)
-        n = len(off) - 1
-        T0s = np.asarray(T0s, np.float32).reshape(-1, 4, 4)
-        t0 = np.concatenate([to_colmajor16(T) for T in T0s]) if len(T0s) else np.zeros(0, np.float32)
-        res = (IcpResultC * max(n, 1))()
+        off, n, t0, res = _icp_batch_args(offsets, T0s)
         _check(self._h, lib().tdv_colored_icp_batch_dev(self._h, _ptr(d_src), _ptr(d_src_rgb), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals),
                                                         _ptr(d_tgt_color), nt, _ptr(t0), C.c_float(thr), max_iterations,
                                                         C.c_float(lambda_geometric), int(fixed_iterations), res), "tdv_colored_icp_batch_dev")
-        return [RegistrationResult(transformation=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse),
-                                   iterations=r.iterations, n_corr=r.n_corr) for r in res[:n]]
+        return [_icp_result(r) for r in res[:n]]
 
     def colored_icp_batch(self, sources, source_rgbs, tgt, tgt_normals, tgt_color, T0s, thr, max_iterations=200, lambda_geometric=0.968):
         """colored_icp_batch_dev on host clouds: lists of (n_b, 3) points and colours against one target, uploaded with torch."""
-        import torch
-        dev = torch.device("cuda", self.device)
-        srcs = [_f32(a).reshape(-1, 3) for a in sources]
-        rgbs = [_f32(a).reshape(-1, 3) for a in source_rgbs]
-        if [len(a) for a in rgbs] != [len(a) for a in srcs]:
+        srcs, off = _instance_rows(sources)
+        rgbs, offc = _instance_rows(source_rgbs)
+        if list(offc) != list(off):
             raise ValueError("colored_icp_batch: one colour per source point")
-        off = np.zeros(len(srcs) + 1, np.int32)
-        off[1:] = np.cumsum([len(a) for a in srcs])
-        cat = np.concatenate(srcs) if srcs and off[-1] else np.zeros((1, 3), np.float32)
-        catc = np.concatenate(rgbs) if rgbs and off[-1] else np.zeros((1, 3), np.float32)
         tgt = _f32(tgt); tn = _f32(tgt_normals); tc = _f32(tgt_color).reshape(-1, 4)
-        d_src = torch.from_numpy(cat).to(dev); d_rgb = torch.from_numpy(catc).to(dev)
-        d_tgt = torch.from_numpy(tgt if len(tgt) else np.zeros((1, 3), np.float32)).to(dev)
-        d_tn = torch.from_numpy(tn if len(tn) else np.zeros((1, 3), np.float32)).to(dev)
-        d_tc = torch.from_numpy(tc if len(tc) else np.zeros((1, 4), np.float32)).to(dev)
+        d_src = _upload_rows(self.device, srcs); d_rgb = _upload_rows(self.device, rgbs)
+        d_tgt = _upload_rows(self.device, tgt); d_tn = _upload_rows(self.device, tn); d_tc = _upload_rows(self.device, tc, 4)
         return self.colored_icp_batch_dev(d_src.data_ptr(), d_rgb.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), d_tc.data_ptr(), len(tgt),
                                           T0s, thr, max_iterations, lambda_geometric)
 

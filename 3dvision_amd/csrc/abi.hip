@@ -256,21 +256,58 @@ int tdv_ransac(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt,
     return ransac_run_dev(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel_size, max_iterations, confidence, seed, out, trace_inliers);
 }
 
-int tdv_icp(tdv_ctx* ctx, const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
-            const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
-            tdv_icp_result* out) {
+// ---- ICP: each entry point builds its objective (tdv_internal.hpp: IcpObjective) and runs the body of its call shape
+// host arrays: stage the clouds, the target's normals and the objective's own arrays (obj arrives with the caller's host pointers), run
+static int icp_host(tdv_ctx* ctx, const float* src, int ns, const float* tgt, const float* tgt_normals, int nt, const float* T0,
+                    float distance_threshold, int max_iterations, IcpObjective obj, tdv_icp_result* out) {
     if (!out || !T0 || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tgt)) return TDV_ERR_BAD_ARG;
     TDV_TRY(begin(ctx));
-    TDV_TRY(icp_loss_check(ctx));
-    float *d_src, *d_tgt, *d_nrm;
+    TDV_TRY(icp_objective_check(ctx, obj, tgt_normals, false));
+    float *d_src, *d_tgt, *d_nrm, *d_own;
     TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    if (obj.src_normals) { TDV_TRY(upload(ctx, obj.src_normals, (size_t)ns * 3, &d_own)); obj.src_normals = d_own; }
+    if (obj.src_rgb) { TDV_TRY(upload(ctx, obj.src_rgb, (size_t)ns * 3, &d_own)); obj.src_rgb = d_own; }
     TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
     TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_nrm));
+    if (obj.tgt_color) { TDV_TRY(upload(ctx, obj.tgt_color, (size_t)nt * 4, &d_own)); obj.tgt_color = d_own; }
     if (ns == 0 || nt == 0) {
         std::memcpy(out->T, T0, 64); out->fitness = 0.f; out->rmse = 0.f; out->iterations = 0; out->n_corr = 0;
         return TDV_OK;
     }
-    return icp_run_dev(ctx, d_src, ns, d_tgt, d_nrm, nt, T0, distance_threshold, max_iterations, point_to_plane, 0, out);
+    return icp_run_dev(ctx, d_src, ns, d_tgt, d_nrm, nt, T0, distance_threshold, max_iterations, obj, 0, out);
+}
+// device pointers (pointer and size checks are icp_run_dev's)
+static int icp_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt, const float* T0,
+                   float distance_threshold, int max_iterations, const IcpObjective& obj, int fixed_iterations, tdv_icp_result* out) {
+    TDV_TRY(begin(ctx));
+    TDV_TRY(icp_objective_check(ctx, obj, d_tgt_normals, true));
+    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, obj, fixed_iterations, out);
+}
+// a batch: every argument before anything is enqueued or written
+static int icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets, int n_instances, const float* d_tgt, const float* d_tgt_normals,
+                         int nt, const float* h_T0, float distance_threshold, int max_iterations, const IcpObjective& obj, int fixed_iterations,
+                         tdv_icp_result* out) {
+    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
+    if (n_instances > 0) {
+        if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
+        for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
+        if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
+    }
+    TDV_TRY(begin(ctx));
+    if (n_instances == 0 && obj.kind < ICP_GICP) return TDV_OK;   // (an empty batch: GICP and colored ICP still check their own arguments, the loss is not looked at)
+    TDV_TRY(icp_objective_check(ctx, obj, d_tgt_normals, true));
+    if (n_instances == 0) return TDV_OK;
+    std::vector<int> count((size_t)n_instances);
+    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
+    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                              obj, fixed_iterations, out));
+    return finish(ctx);
+}
+
+int tdv_icp(tdv_ctx* ctx, const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
+            const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
+            tdv_icp_result* out) {
+    return icp_host(ctx, src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, IcpObjective::plain(point_to_plane), out);
 }
 
 int tdv_icp_correspondences(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt,
@@ -296,69 +333,29 @@ int tdv_icp_correspondences(tdv_ctx* ctx, const float* src, int ns, const float*
 int tdv_icp_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                 const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
                 int fixed_iterations, tdv_icp_result* out) {
-    TDV_TRY(begin(ctx));
-    TDV_TRY(icp_loss_check(ctx));
-    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, fixed_iterations, out);
+    return icp_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, IcpObjective::plain(point_to_plane), fixed_iterations, out);
 }
 int tdv_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_src_offsets, int n_instances, const float* d_tgt, const float* d_tgt_normals,
                       int nt, const float* h_T0, float distance_threshold, int max_iterations, int point_to_plane, int fixed_iterations,
                       tdv_icp_result* out) {
-    // every argument before anything is enqueued or written
-    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
-    if (n_instances == 0) return begin(ctx);
-    if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
-    for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
-    if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
-    TDV_TRY(begin(ctx));
-    TDV_TRY(icp_loss_check(ctx));
-    std::vector<int> count((size_t)n_instances);
-    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
-    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
-                              point_to_plane, fixed_iterations, out));
-    return finish(ctx);
+    return icp_batch_dev(ctx, d_src, h_src_offsets, n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                         IcpObjective::plain(point_to_plane), fixed_iterations, out);
 }
 // ---- generalized ICP: tdv_icp / tdv_icp_dev / tdv_icp_batch_dev with the source normals, plane-to-plane terms (icp.hip, MODE 3)
 int tdv_gicp(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
              const float* T0, float distance_threshold, int max_iterations, float epsilon, tdv_icp_result* out) {
-    if (!out || !T0 || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tgt)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(begin(ctx));
-    TDV_TRY(gicp_check(ctx, src_normals, tgt_normals, epsilon));          // (reference-order sums refused: no loss check needed)
-    float *d_src, *d_sn, *d_tgt, *d_tn;
-    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
-    TDV_TRY(upload(ctx, src_normals, (size_t)ns * 3, &d_sn));
-    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
-    TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_tn));
-    if (ns == 0 || nt == 0) {
-        std::memcpy(out->T, T0, 64); out->fitness = 0.f; out->rmse = 0.f; out->iterations = 0; out->n_corr = 0;
-        return TDV_OK;
-    }
-    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tn, nt, T0, distance_threshold, max_iterations, 1, 0, out, nullptr, nullptr, IcpGicp{d_sn, 1.f - epsilon});
+    return icp_host(ctx, src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, IcpObjective::gicp(src_normals, epsilon), out);
 }
 int tdv_gicp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                  const float* T0, float distance_threshold, int max_iterations, float epsilon, int fixed_iterations, tdv_icp_result* out) {
-    TDV_TRY(begin(ctx));
-    TDV_TRY(gicp_check(ctx, d_src_normals, d_tgt_normals, epsilon));      // (reference-order sums refused: no loss check needed)
-    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, 1, fixed_iterations, out, nullptr, nullptr,
-                       IcpGicp{d_src_normals, 1.f - epsilon});
+    return icp_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, IcpObjective::gicp(d_src_normals, epsilon),
+                   fixed_iterations, out);
 }
 int tdv_gicp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances,
                        const float* d_tgt, const float* d_tgt_normals, int nt, const float* h_T0, float distance_threshold,
                        int max_iterations, float epsilon, int fixed_iterations, tdv_icp_result* out) {
-    // every argument before anything is enqueued or written (tdv_icp_batch_dev's, then GICP's)
-    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
-    if (n_instances > 0) {
-        if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
-        for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
-        if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
-    }
-    TDV_TRY(begin(ctx));
-    TDV_TRY(gicp_check(ctx, d_src_normals, d_tgt_normals, epsilon));      // (reference-order sums refused: no loss check needed)
-    if (n_instances == 0) return TDV_OK;
-    std::vector<int> count((size_t)n_instances);
-    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
-    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
-                              1, fixed_iterations, out, IcpGicp{d_src_normals, 1.f - epsilon}));
-    return finish(ctx);
+    return icp_batch_dev(ctx, d_src, h_src_offsets, n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                         IcpObjective::gicp(d_src_normals, epsilon), fixed_iterations, out);
 }
 // ---- colored ICP: the target's colour gradients (color.hip), then tdv_icp / tdv_icp_dev / tdv_icp_batch_dev with the source colours
 // and the target's colour table, point-to-plane plus photometric terms (icp.hip, MODE 4)
@@ -385,49 +382,20 @@ int tdv_color_gradients_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb
 int tdv_colored_icp(tdv_ctx* ctx, const float* src, const float* src_rgb, int ns, const float* tgt, const float* tgt_normals,
                     const float* tgt_color, int nt, const float* T0, float distance_threshold, int max_iterations, float lambda_geometric,
                     tdv_icp_result* out) {
-    if (!out || !T0 || ns < 0 || nt < 0 || (ns > 0 && !src) || (nt > 0 && !tgt)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(begin(ctx));
-    TDV_TRY(colored_check(ctx, src_rgb, tgt_normals, tgt_color, lambda_geometric, false));   // (reference-order sums refused: no loss check needed)
-    float *d_src, *d_rgb, *d_tgt, *d_tn, *d_tc;
-    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
-    TDV_TRY(upload(ctx, src_rgb, (size_t)ns * 3, &d_rgb));
-    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
-    TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_tn));
-    TDV_TRY(upload(ctx, tgt_color, (size_t)nt * 4, &d_tc));
-    if (ns == 0 || nt == 0) {
-        std::memcpy(out->T, T0, 64); out->fitness = 0.f; out->rmse = 0.f; out->iterations = 0; out->n_corr = 0;
-        return TDV_OK;
-    }
-    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tn, nt, T0, distance_threshold, max_iterations, 1, 0, out, nullptr, nullptr, IcpGicp{nullptr, 0.f},
-                       IcpColor{d_rgb, d_tc, sqrtf(lambda_geometric), sqrtf(1.f - lambda_geometric)});
+    return icp_host(ctx, src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations,
+                    IcpObjective::colored(src_rgb, tgt_color, lambda_geometric), out);
 }
 int tdv_colored_icp_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_rgb, int ns, const float* d_tgt, const float* d_tgt_normals,
                         const float* d_tgt_color, int nt, const float* T0, float distance_threshold, int max_iterations,
                         float lambda_geometric, int fixed_iterations, tdv_icp_result* out) {
-    TDV_TRY(begin(ctx));
-    TDV_TRY(colored_check(ctx, d_src_rgb, d_tgt_normals, d_tgt_color, lambda_geometric, true));
-    return icp_run_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations, 1, fixed_iterations, out, nullptr, nullptr,
-                       IcpGicp{nullptr, 0.f}, IcpColor{d_src_rgb, d_tgt_color, sqrtf(lambda_geometric), sqrtf(1.f - lambda_geometric)});
+    return icp_dev(ctx, d_src, ns, d_tgt, d_tgt_normals, nt, T0, distance_threshold, max_iterations,
+                   IcpObjective::colored(d_src_rgb, d_tgt_color, lambda_geometric), fixed_iterations, out);
 }
 int tdv_colored_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_rgb, const int* h_src_offsets, int n_instances,
                               const float* d_tgt, const float* d_tgt_normals, const float* d_tgt_color, int nt, const float* h_T0,
                               float distance_threshold, int max_iterations, float lambda_geometric, int fixed_iterations, tdv_icp_result* out) {
-    // every argument before anything is enqueued or written (tdv_icp_batch_dev's, then colored ICP's)
-    if (!ctx || n_instances < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
-    if (n_instances > 0) {
-        if (!h_src_offsets || !h_T0 || !out || h_src_offsets[0] != 0 || (nt > 0 && !d_tgt)) return TDV_ERR_BAD_ARG;
-        for (int b = 0; b < n_instances; ++b) if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
-        if (h_src_offsets[n_instances] > 0 && !d_src) return TDV_ERR_BAD_ARG;
-    }
-    TDV_TRY(begin(ctx));
-    TDV_TRY(colored_check(ctx, d_src_rgb, d_tgt_normals, d_tgt_color, lambda_geometric, true));
-    if (n_instances == 0) return TDV_OK;
-    std::vector<int> count((size_t)n_instances);
-    for (int b = 0; b < n_instances; ++b) count[b] = h_src_offsets[b + 1] - h_src_offsets[b];
-    TDV_TRY(icp_batch_run_dev(ctx, d_src, h_src_offsets, count.data(), n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
-                              1, fixed_iterations, out, IcpGicp{nullptr, 0.f},
-                              IcpColor{d_src_rgb, d_tgt_color, sqrtf(lambda_geometric), sqrtf(1.f - lambda_geometric)}));
-    return finish(ctx);
+    return icp_batch_dev(ctx, d_src, h_src_offsets, n_instances, d_tgt, d_tgt_normals, nt, h_T0, distance_threshold, max_iterations,
+                         IcpObjective::colored(d_src_rgb, d_tgt_color, lambda_geometric), fixed_iterations, out);
 }
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,

@@ -255,7 +255,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
                                prm->ransac_confidence, prm->seed, &coarse, nullptr));
         r.coarse_fitness = coarse.fitness; r.coarse_inliers = coarse.inliers;
         tdv_icp_result fine;
-        TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, prm->point_to_plane, 0, &fine,
+        TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, IcpObjective::plain(prm->point_to_plane), 0, &fine,
                             have_sorted ? &model_sorted : nullptr, have_grid ? &model_grid : nullptr));
         set_icp_result(r, fine);
         ws_rewind(c, mark);
@@ -425,7 +425,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         r.coarse_fitness = coarse.fitness; r.coarse_inliers = coarse.inliers;
         if (batched_icp) { std::memcpy(&coarse_T[(size_t)b * 16], coarse.T, 64); ws_rewind(c, mark); return TDV_OK; }
         tdv_icp_result fine;
-        TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, prm->point_to_plane, 0, &fine,
+        TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, IcpObjective::plain(prm->point_to_plane), 0, &fine,
                             have_sorted ? &model_sorted : nullptr, have_grid ? &model_grid : nullptr));
         set_icp_result(r, fine);
         ws_rewind(c, mark);
@@ -456,7 +456,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     if (batched_icp) {
         std::vector<tdv_icp_result> fine((size_t)n_instances);
         TDV_TRY(icp_small_batch_dev(ctx, want_ref ? vox_ref_all : vox_first_all, d_voff, n_instances, d_model_xyz, d_model_normals, n_model, coarse_T.data(), icp_thr,
-                                    prm->icp_max_iterations, prm->point_to_plane, fine.data()));
+                                    prm->icp_max_iterations, IcpObjective::plain(prm->point_to_plane), fine.data()));
         for (int b = 0; b < n_instances; ++b)
             if (off[b + 1] != off[b]) set_icp_result(results[b], fine[b]);
     }
@@ -505,7 +505,7 @@ int refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks
     std::vector<tdv_icp_result> fine((size_t)n_instances);
     const float icp_thr = prm->voxel_size * prm->icp_distance_factor;  // pipeline.cpp:104
     TDV_TRY(icp_batch_run_dev(ctx, clouds, start.data(), count.data(), n_instances, d_model_xyz, d_model_normals, n_model, h_T0, icp_thr,
-                              prm->icp_max_iterations, prm->point_to_plane, 0, fine.data()));
+                              prm->icp_max_iterations, IcpObjective::plain(prm->point_to_plane), 0, fine.data()));
     TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     for (int b = 0; b < n_instances; ++b) {
         tdv_instance_result& r = results[b];

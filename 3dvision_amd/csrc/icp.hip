@@ -35,11 +35,12 @@
 //  * robust losses (tdv_ctx_set_icp_loss): every accepted correspondence's terms are scaled by its weight in acc_terms, the one place
 //    all tree-sum paths form them; the kernels take ROBUST as a template parameter, so the L2 instantiations are the code without it.
 //  * generalized ICP (tdv_gicp, MODE 3): plane-to-plane terms from both clouds' normals in acc_terms, the same 6x6 system, slab layout
-//    and solve as point-to-plane.  Its extra kernel arguments (the source normals, c = 1 - epsilon) arrive as a trailing parameter pack
-//    that is empty for the other modes, so that their kernels keep their arguments and their code.
+//    and solve as point-to-plane.  Its extra kernel arguments (the source normals, c = 1 - epsilon) are IcpArgs<3>, the kernels' last
+//    parameter: a struct typed by MODE that is empty for modes 0-2, so that their kernels keep their arguments and their code.
 //  * colored ICP (tdv_colored_icp, MODE 4): point-to-plane's row plus a photometric row on the target's tangent plane in acc_terms, the
-//    same 6x6 system and slab layout.  Its extra arguments (source colours, the target's colour table, lg, lc) come in the same
-//    trailing pack as one IcpColor.
+//    same 6x6 system and slab layout.  Its extra arguments (source colours, the target's colour table, lg, lc) are IcpArgs<4>.
+//    Per correspondence, corr_pt turns IcpArgs<MODE> into the CorrPt<MODE> that acc_terms takes; on the host, icp_dispatch picks the
+//    instantiation from the call's IcpObjective.
 // No float atomics anywhere: two runs give identical bits.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
@@ -107,13 +108,6 @@ __device__ __forceinline__ void transform_point(const float* __restrict__ T, flo
     px = (T[0] * sx + (T[4] * sy + T[8] * sz)) + T[12];
     py = (T[1] * sx + (T[5] * sy + T[9] * sz)) + T[13];
     pz = (T[2] * sx + (T[6] * sy + T[10] * sz)) + T[14];
-}
-
-// a = R*s, transform_point without the translation (GICP: a source normal into the pose)
-__device__ __forceinline__ void rotate_point(const float* __restrict__ T, float sx, float sy, float sz, float& ax, float& ay, float& az) {
-    ax = T[0] * sx + (T[4] * sy + T[8] * sz);
-    ay = T[1] * sx + (T[5] * sy + T[9] * sz);
-    az = T[2] * sx + (T[6] * sy + T[10] * sz);
 }
 
 __global__ __launch_bounds__(NN_BLOCK)
@@ -535,32 +529,41 @@ __device__ __forceinline__ void acc_transform(const float* T, float sx, float sy
     pz = (T[2] * sx + (T[5] * sy + T[8] * sz)) + T[11];
 }
 
-// a = R*s, the rotation of acc_transform without the translation (a source normal into the current pose)
+// a = R*s, the rotation of acc_transform without the translation (a source normal into the current pose); LD: the pose's column
+// pitch, 3 for acc_load_pose's T, 4 for a column-major 4x4
+template <int LD = 3>
 __device__ __forceinline__ void acc_rotate(const float* T, float sx, float sy, float sz, float& ax, float& ay, float& az) {
-    ax = T[0] * sx + (T[3] * sy + T[6] * sz);
-    ay = T[1] * sx + (T[4] * sy + T[7] * sz);
-    az = T[2] * sx + (T[5] * sy + T[8] * sz);
+    ax = T[0] * sx + (T[LD] * sy + T[2 * LD] * sz);
+    ay = T[1] * sx + (T[LD + 1] * sy + T[2 * LD + 1] * sz);
+    az = T[2] * sx + (T[LD + 2] * sy + T[2 * LD + 2] * sz);
 }
 
-// GICP's per-correspondence input besides p and the target: a = R ns, the source normal in the current pose, and c = 1 - epsilon
-// (unused by the other modes)
-struct GicpPt { float ax, ay, az, c; };
+// What MODE's kernels take beyond the common arguments, by value as their LAST parameter (the other arguments keep their places):
+// nothing, GICP's source normals (laid out like the source points) and c = 1 - epsilon, or colored ICP's source colours (laid out
+// like the source points), the target's colour table (float4 (I, d) per point), lg = sqrtf(lambda) and lc = sqrtf(1 - lambda).
+template <int MODE> struct IcpArgs {};
+template <> struct IcpArgs<3> { const float* src_normals; float c; };
+template <> struct IcpArgs<4> { const float* src_rgb; const float* tgt_color; float lg, lc; };
 
-// The kernels' GICP arguments from their trailing parameter pack: empty (no GICP) or one IcpGicp
-__device__ __forceinline__ IcpGicp gicp_of() { return IcpGicp{nullptr, 0.f}; }
-__device__ __forceinline__ IcpGicp gicp_of(IcpGicp g) { return g; }
-__device__ __forceinline__ IcpGicp gicp_of(IcpColor) { return IcpGicp{nullptr, 0.f}; }
+// ... and what acc_terms takes per correspondence besides p and the target: nothing, GICP's a = R ns (the source normal in the
+// current pose) and c, or colored ICP's colour table, the source point's intensity Is = ((r + g) + b) / 3.0f, lg and lc.
+template <int MODE> struct CorrPt {};
+template <> struct CorrPt<3> { float ax, ay, az, c; };
+template <> struct CorrPt<4> { const float* tgt_color; float Is, lg, lc; };
 
-// Colored ICP's per-correspondence input besides p and the target: the target's colour table (float4 (I, d) per point), the source
-// point's intensity Is = ((r + g) + b) / 3.0f, lg = sqrtf(lambda), lc = sqrtf(1 - lambda) (unused by the other modes)
-struct ColorPt { const float* tgt_color; float Is, lg, lc; };
-__device__ __forceinline__ IcpColor color_of() { return IcpColor{nullptr, nullptr, 0.f, 0.f}; }
-__device__ __forceinline__ IcpColor color_of(IcpGicp) { return IcpColor{nullptr, nullptr, 0.f, 0.f}; }
-__device__ __forceinline__ IcpColor color_of(IcpColor c) { return c; }
-// source point i (index into the colours laid out like the source points)
-__device__ __forceinline__ ColorPt color_pt(const IcpColor& c, size_t i) {
-    const float* __restrict__ rgb = c.src_rgb + 3 * i;
-    return ColorPt{c.tgt_color, ((rgb[0] + rgb[1]) + rgb[2]) / 3.0f, c.lg, c.lc};
+// CorrPt of source point i (its index in the arrays laid out like the source points, in the caller's index type: the address
+// arithmetic stays the caller's) in the pose T of column pitch LD (acc_rotate)
+template <int MODE, int LD = 3, class Index>
+__device__ __forceinline__ CorrPt<MODE> corr_pt(const IcpArgs<MODE>& a, const float* T, Index i) {
+    if constexpr (MODE == 3) {
+        CorrPt<3> x;
+        acc_rotate<LD>(T, a.src_normals[3 * i], a.src_normals[3 * i + 1], a.src_normals[3 * i + 2], x.ax, x.ay, x.az);
+        x.c = a.c;
+        return x;
+    } else if constexpr (MODE == 4) {
+        const float* __restrict__ rgb = a.src_rgb + 3 * (size_t)i;
+        return CorrPt<4>{a.tgt_color, ((rgb[0] + rgb[1]) + rgb[2]) / 3.0f, a.lg, a.lc};
+    } else return {};
 }
 
 // One accepted correspondence, source point p (transformed) paired with target idx, in the float steps of registration.cpp: its
@@ -582,9 +585,9 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // {1, d2, then MODE 0 the 21 upper-triangular J[a] * J[b] and the 6 J[a] * r, each product formed in float and widened; MODE 1 p, q
 // and the 9 p[a] * q[b], p and q widened first}.  put is the caller's way of combining them (+= into a lane's sums, = into a fresh
 // slab row: 0.0 + -0.0 is +0.0); each term is put as it is formed.
-// MODE 3 (GICP): the 21 + 6 terms of include/tdv_hip.h (tdv_gicp) from p, the target point and normal and G, each formed in float in
+// MODE 3 (GICP): the 21 + 6 terms of include/tdv_hip.h (tdv_gicp) from p, the target point and normal and X, each formed in float in
 // the header's order and widened.
-// MODE 4 (colored ICP): the 21 + 6 terms of include/tdv_hip.h (tdv_colored_icp) from p, the target point and normal and C: per slot
+// MODE 4 (colored ICP): the 21 + 6 terms of include/tdv_hip.h (tdv_colored_icp) from p, the target point and normal and X: per slot
 // (double)(JG[a] * JG[b]) + (double)(JC[a] * JC[b]), resp. * rG and * rC, each product formed in float.  ROBUST: each row weighted
 // by its own residual, (double)wG * (JG product) + (double)wC * (JC product), n_eff = (wG > 0 || wC > 0).
 // ROBUST: the weight w = loss_weight(L, e) of this correspondence (e = r point-to-plane, sqrtf(d2) point-to-point, GICP the
@@ -593,22 +596,22 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // {1, d2} stay unweighted: n_corr, rmse and fitness are L2's.
 template <int MODE, bool ROBUST = false, class Put>
 __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
-                                          IcpLoss L, GicpPt G, ColorPt C, Put put) {
+                                          IcpLoss L, CorrPt<MODE> X, Put put) {
     put(0, 1.0); put(1, (double)d2);
     if (MODE == 2) return;
-    if (MODE == 4) {
+    if constexpr (MODE == 4) {
         float q[3], J[6], en;
         corr_terms<0>(px, py, pz, idx, tgt, tgt_normals, q, J, en);     // J = [p x n | n], en = (p - q) . n
         const float nx = J[3], ny = J[4], nz = J[5];
-        const float4 tc = reinterpret_cast<const float4*>(C.tgt_color)[idx];   // (Iq, d)
-        const float lg = C.lg, lc = C.lc;
+        const float4 tc = reinterpret_cast<const float4*>(X.tgt_color)[idx];   // (Iq, d)
+        const float lg = X.lg, lc = X.lc;
         // e_t = e - en n, the source point's offset projected on the target's tangent plane; g = (d . n) n - d = -m
         const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
         const float etx = ex - en * nx, ety = ey - en * ny, etz = ez - en * nz;
         const float dn = tc.y * nx + (tc.z * ny + tc.w * nz);
         const float gx = dn * nx - tc.y, gy = dn * ny - tc.z, gz = dn * nz - tc.w;
         const float de = tc.y * etx + (tc.z * ety + tc.w * etz);
-        const float rG = lg * en, rC = lc * (C.Is - (tc.x + de));
+        const float rG = lg * en, rC = lc * (X.Is - (tc.x + de));
         float JG[6], JC[6];
 #pragma unroll
         for (int a = 0; a < 6; ++a) JG[a] = lg * J[a];
@@ -628,10 +631,10 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
         if (ROBUST) put(29, (wG > 0.f || wC > 0.f) ? 1.0 : 0.0);
         return;
     }
-    if (MODE == 3) {
+    if constexpr (MODE == 3) {
         const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
         const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-        const float c = G.c, ax = G.ax, ay = G.ay, az = G.az;
+        const float c = X.c, ax = X.ax, ay = X.ay, az = X.az;
         // C = 2 I - c (a a^T + n n^T) in f32; M = C^-1 from the cofactors in f64 (C's condition number is about 1 / epsilon: in f32 the
         // cancellation in the cofactors and the determinant would cost ~1e-7 / epsilon of M), rounded to f32
         const float C00 = 2.f - c * (ax * ax + nx * nx), C11 = 2.f - c * (ay * ay + ny * ny), C22 = 2.f - c * (az * az + nz * nz);
@@ -699,9 +702,8 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
 // this lane's sums += one accepted correspondence (p, target idx at squared distance best)
 template <int MODE, bool ROBUST = false>
 __device__ __forceinline__ void acc_add(double* v, float px, float py, float pz, float best, int idx,
-                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L, GicpPt G = GicpPt{},
-                                        ColorPt C = ColorPt{}) {
-    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, G, C, [v](int k, double t) { v[k] += t; });
+                                        const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss L, CorrPt<MODE> X) {
+    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, L, X, [v](int k, double t) { v[k] += t; });
 }
 
 // LDS of one accumulation block
@@ -800,8 +802,7 @@ __device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const 
 
 // One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
 // slabs in a fixed order, solves, and updates the state on the device.
-// (Gicp: one IcpGicp for MODE 3, one IcpColor for MODE 4, empty otherwise)
-template <int MODE, int ACC_PPT, bool ROBUST = false, class... Gicp>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
+template <int MODE, int ACC_PPT, bool ROBUST = false>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
 __global__ __launch_bounds__(256)
 void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
@@ -809,11 +810,9 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       int nsplit, const float* __restrict__ pd2, const int* __restrict__ pchunk, int direct,
                       IcpState* st, float tau_accept, int fixed_iterations, IcpLoss loss,
                       double* slabs, unsigned* ticket,
-                      int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc, Gicp... gicp_arg) {
-    static_assert((MODE >= 3) == (sizeof...(Gicp) == 1), "GICP and colored ICP take their arguments, the other modes none");
+                      int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc, IcpArgs<MODE> args) {
     if (st->done) return;
-    const IcpGicp gicp = gicp_of(gicp_arg...);
-    const IcpColor color = color_of(gicp_arg...);
+    const IcpArgs<MODE> a = args;
     const int iter0 = st->iter; const float rmse0 = st->rmse;
     double v[ACC_NV];
 #pragma unroll
@@ -833,14 +832,8 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
         if (out_d2) out_d2[i] = best;
         if (out_acc) out_acc[i] = acc ? 1 : 0;
         if (!acc) continue;
-        GicpPt G{};
-        if (MODE == 3) {
-            acc_rotate(T, gicp.src_normals[3 * i], gicp.src_normals[3 * i + 1], gicp.src_normals[3 * i + 2], G.ax, G.ay, G.az);
-            G.c = gicp.c;
-        }
-        ColorPt C{};
-        if (MODE == 4) C = color_pt(color, (size_t)i);
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G, C);
+        const CorrPt<MODE> X = corr_pt(a, T, i);
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, X);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
@@ -885,18 +878,13 @@ void k_icp_nn_grid_multi(const float* __restrict__ src, const IcpInst* __restric
 
 // k_icp_accumulate for every instance: instance b's blocks write its slabs and take its ticket word tickets[b]; the last of them
 // folds, solves and updates st[b].  The points-per-thread count is uniform over a block (runtime loop, as the single kernel's).
-// (Gicp: one IcpGicp for MODE 3, its source normals laid out like src; one IcpColor for MODE 4, its source colours laid out like src;
-// empty otherwise)
-template <int MODE, bool ROBUST = false, class... Gicp>
+template <int MODE, bool ROBUST = false>
 __global__ __launch_bounds__(256)
 void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __restrict__ inst, const int* __restrict__ blk_inst,
                             const float* __restrict__ tgt, const float* __restrict__ tgt_normals,
                             const float* __restrict__ pd2, const int* __restrict__ pidx,
                             IcpState* st_all, float tau_accept, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* tickets,
-                            Gicp... gicp_arg) {
-    static_assert((MODE >= 3) == (sizeof...(Gicp) == 1), "GICP and colored ICP take their arguments, the other modes none");
-    const IcpGicp gicp = gicp_of(gicp_arg...);
-    const IcpColor color = color_of(gicp_arg...);
+                            IcpArgs<MODE> args) {
     const int b = blk_inst[blockIdx.x];
     IcpState* st = st_all + b;
     if (st->done) return;
@@ -919,15 +907,8 @@ void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __rest
         const float best = d < FLT_MAX ? d : FLT_MAX;
         const int idx = d < FLT_MAX ? pidx[in.src_off + i] : 0;
         if (!(best <= tau_accept)) continue;
-        GicpPt G{};
-        if (MODE == 3) {
-            const float* __restrict__ sn = gicp.src_normals + ((size_t)in.src_off + i) * 3;
-            acc_rotate(T, sn[0], sn[1], sn[2], G.ax, G.ay, G.az);
-            G.c = gicp.c;
-        }
-        ColorPt C{};
-        if (MODE == 4) C = color_pt(color, (size_t)in.src_off + i);
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, G, C);
+        const CorrPt<MODE> X = corr_pt(args, T, (size_t)in.src_off + i);
+        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, X);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
@@ -1176,17 +1157,14 @@ constexpr long long SM_MAX_PAIRS_BATCH = 1ll << 20;     // ... per problem of a 
 // A grid of several workgroups runs one problem each (the batch's small instances against the shared model): problem b takes the
 // source points [src_off[b], src_off[b + 1]) of src0 and the states st_in[b] / st_out[b]; src_off == nullptr: one problem.
 // 1,024 lanes and room for 2,048 x 2,048 points.
-// Gicp: one IcpGicp for MODE 3 (source normals laid out like src0), one IcpColor for MODE 4 (source colours laid out like src0), empty
-// otherwise.
-template <int MODE, bool REF, bool ROBUST = false, class... Gicp>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS; ROBUST: loss
+// args' arrays are laid out like src0.
+template <int MODE, bool REF, bool ROBUST = false>   // REF: reference-order accumulation (see k_icp_fold_ref), tile by tile in LDS; ROBUST: loss
 __global__ __launch_bounds__(SM_THREADS)
 void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict__ src_off, const float* __restrict__ tgt, const float* __restrict__ tgt_normals, int nt,
                  const IcpState* __restrict__ st_in0, float tau_accept, int max_iterations, int fixed_iterations, IcpLoss loss,
-                 IcpState* __restrict__ st_out0, IcpState* __restrict__ st_host, Gicp... gicp_arg) {
+                 IcpState* __restrict__ st_out0, IcpState* __restrict__ st_host, IcpArgs<MODE> args) {
     static_assert(!(REF && ROBUST), "reference-order sums have no loss");
-    static_assert((MODE >= 3) == (sizeof...(Gicp) == 1) && !(REF && MODE >= 3), "GICP and colored ICP take their arguments and tree sums, the other modes no arguments");
-    const IcpGicp gicp = gicp_of(gicp_arg...);
-    const IcpColor color = color_of(gicp_arg...);
+    static_assert(!(REF && MODE >= 3), "GICP and colored ICP take tree sums");
     const int prob = blockIdx.x;
     const float* __restrict__ src = src_off ? src0 + (size_t)src_off[prob] * 3 : src0;
     const int ns = src_off ? src_off[prob + 1] - src_off[prob] : ns0;
@@ -1314,15 +1292,10 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
                 float px, py, pz;
                 transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
                 const float best = sbest[i]; const int idx = sidx[i];
-                GicpPt G{};
-                if (MODE == 3 && best <= tau_accept) {
-                    const float* __restrict__ sn = gicp.src_normals + ((src_off ? (size_t)src_off[prob] : 0) + i) * 3;
-                    rotate_point(T, sn[0], sn[1], sn[2], G.ax, G.ay, G.az);
-                    G.c = gicp.c;
+                if (best <= tau_accept) {
+                    const CorrPt<MODE> X = corr_pt<MODE, 4>(args, T, (src_off ? (size_t)src_off[prob] : 0) + i);
+                    acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, X, [&v](int k, double t) { v[k] = t; });
                 }
-                ColorPt C{};
-                if (MODE == 4 && best <= tau_accept) C = color_pt(color, (src_off ? (size_t)src_off[prob] : 0) + i);
-                if (best <= tau_accept) acc_terms<MODE, ROBUST>(px, py, pz, best, idx, tgt, tgt_normals, loss, G, C, [&v](int k, double t) { v[k] = t; });
             }
 #pragma unroll
             for (int k = 0; k < NV; ++k) {
@@ -1379,7 +1352,7 @@ NnPlan make_plan(int ns, int nt) {
     p.chunks_per_split = (p.n_chunks + p.nsplit - 1) / p.nsplit;
     p.nsplit = (p.n_chunks + p.chunks_per_split - 1) / p.chunks_per_split;
     static const int ppt_env = study_env("TDV_ICP_PPT") ? atoi(study_env("TDV_ICP_PPT")) : 0;
-    // only 1, 2, 4 and 8 points per thread are instantiated (TDV_ACC below); anything else would size the grid for a kernel that is never launched
+    // only 1, 2, 4 and 8 points per thread are instantiated (ppt_dispatch below); anything else would size the grid for a kernel that is never launched
     p.acc_ppt = (kStudyBuild && (ppt_env == 1 || ppt_env == 2 || ppt_env == 4 || ppt_env == 8)) ? ppt_env : 4;   // 4: make_plan's default; the brute-force path uses 1
     p.acc_blocks = (ns + 256 * p.acc_ppt - 1) / (256 * p.acc_ppt);
     return p;
@@ -1465,29 +1438,53 @@ void state_result(const IcpState& h, tdv_icp_result& out) {
 IcpLoss ctx_loss(const tdv_ctx* ctx) { return IcpLoss{ctx->icp_loss, ctx->icp_loss_scale}; }
 bool ctx_robust(const tdv_ctx* ctx) { return ctx->icp_loss != TDV_ICP_LOSS_L2; }
 
-// k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points), point-to-plane where normals are given, GICP where
-// gicp has source normals (gicp_check: tree sums), colored ICP where color has source colours (colored_check: tree sums), with the ctx's
-// accumulation and loss (icp_loss_check: no loss with reference-order sums)
+// The kernels' extra arguments from an objective of kind MODE
+template <int MODE> IcpArgs<MODE> kernel_args(const IcpObjective& o) {
+    if constexpr (MODE == ICP_GICP) return {o.src_normals, o.c};
+    else if constexpr (MODE == ICP_COLORED) return {o.src_rgb, o.tgt_color, o.lg, o.lc};
+    else return {};
+}
+
+// The one place that turns an objective's kind and the ctx's loss and accumulation into template arguments: calls f(MODE, ROBUST, REF)
+// with integral constants, for the combinations that are instantiated - reference-order sums exist for point-to-plane and
+// point-to-point and take no loss (the entry points refuse the rest: icp_objective_check).  Point-to-plane without target normals is
+// point-to-point.
+template <class F>
+void icp_dispatch(const tdv_ctx* ctx, const IcpObjective& obj, const float* d_tgt_normals, const F& f) {
+    const IcpKind kind = (obj.kind == ICP_POINT_TO_PLANE && !d_tgt_normals) ? ICP_POINT_TO_POINT : obj.kind;
+    const bool robust = ctx_robust(ctx), ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
+    const auto mode = [&](auto M) {
+        if constexpr (decltype(M)::value < ICP_GICP) { if (ref) return f(M, std::false_type{}, std::true_type{}); }
+        return robust ? f(M, std::true_type{}, std::false_type{}) : f(M, std::false_type{}, std::false_type{});
+    };
+    switch (kind) {
+    case ICP_POINT_TO_PLANE: return mode(std::integral_constant<int, ICP_POINT_TO_PLANE>{});
+    case ICP_POINT_TO_POINT: return mode(std::integral_constant<int, ICP_POINT_TO_POINT>{});
+    case ICP_GICP: return mode(std::integral_constant<int, ICP_GICP>{});
+    case ICP_COLORED: return mode(std::integral_constant<int, ICP_COLORED>{});
+    }
+}
+
+// ... and k_icp_accumulate's points per thread: f(ACC_PPT) for make_plan's values (2 and 8 points per thread: study build)
+template <class F>
+void ppt_dispatch(int ppt, const F& f) {
+#ifdef TDV_STUDY
+    if (ppt == 8) return f(std::integral_constant<int, 8>{});
+    if (ppt == 2) return f(std::integral_constant<int, 2>{});
+#endif
+    if (ppt == 4) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 1>{});
+}
+
+// k_icp_small over n_prob workgroups (src_off == nullptr: one problem of ns points) for obj, with the ctx's accumulation and loss
 void launch_icp_small(tdv_ctx* ctx, int n_prob, const float* d_src, int ns, const int* d_src_off, const float* d_tgt, const float* d_tgt_normals, int nt,
-                      int point_to_plane, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host,
-                      IcpGicp gicp, IcpColor color) {
-    const bool p2pl = point_to_plane && d_tgt_normals, ref = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE, robust = ctx_robust(ctx);
-    if (color.src_rgb) {
-        const auto kernel = robust ? k_icp_small<4, false, true, IcpColor> : k_icp_small<4, false, false, IcpColor>;
-        kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations,
-                                                       ctx_loss(ctx), st_out, st_host, color);
-        return;
-    }
-    if (gicp.src_normals) {
-        const auto kernel = robust ? k_icp_small<3, false, true, IcpGicp> : k_icp_small<3, false, false, IcpGicp>;
-        kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations,
-                                                       ctx_loss(ctx), st_out, st_host, gicp);
-        return;
-    }
-    const auto kernel = p2pl ? (ref ? k_icp_small<0, true> : robust ? k_icp_small<0, false, true> : k_icp_small<0, false>)
-                             : (ref ? k_icp_small<1, true> : robust ? k_icp_small<1, false, true> : k_icp_small<1, false>);
-    kernel<<<n_prob, SM_THREADS, 0, ctx->stream>>>(d_src, ns, d_src_off, d_tgt, p2pl ? d_tgt_normals : nullptr, nt, st_in, tau, max_iterations, fixed_iterations,
-                                                   ctx_loss(ctx), st_out, st_host);
+                      const IcpObjective& obj, const IcpState* st_in, float tau, int max_iterations, int fixed_iterations, IcpState* st_out, IcpState* st_host) {
+    icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto REF) {
+        constexpr int MODE = decltype(M)::value;
+        k_icp_small<MODE, decltype(REF)::value, decltype(R)::value><<<n_prob, SM_THREADS, 0, ctx->stream>>>(
+            d_src, ns, d_src_off, d_tgt, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations, ctx_loss(ctx),
+            st_out, st_host, kernel_args<MODE>(obj));
+    });
 }
 
 // Iterations are enqueued in bursts between two looks at the n states d_st (read back into the pinned h[0 .. n)); once a state is done
@@ -1542,12 +1539,13 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 }
 
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
-                const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
-                tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid, IcpGicp gicp, IcpColor color) {
+                const float* T0, float thr, int max_iterations, IcpObjective obj, int fixed_iterations,
+                tdv_icp_result* out, const SortedCloud* tgt_sorted, const CellGrid* tgt_grid) {
     if (!ctx || !d_src || !d_tgt || !T0 || !out || ns < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
-    if (gicp.src_normals && (!d_tgt_normals || ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE)) return TDV_ERR_BAD_ARG;   // (gicp_check's)
-    if (color.src_rgb && (!d_tgt_normals || !color.tgt_color || gicp.src_normals || ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE))
-        return TDV_ERR_BAD_ARG;                                                                                          // (colored_check's)
+    const bool ref_acc = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
+    if (obj.kind >= ICP_GICP && (!d_tgt_normals || ref_acc || !(obj.kind == ICP_GICP ? obj.src_normals : obj.src_rgb) ||
+                                 (obj.kind == ICP_COLORED && !obj.tgt_color)))
+        return TDV_ERR_BAD_ARG;                                                              // (icp_objective_check's)
     TDV_HIP(ctx, hipSetDevice(ctx->device));
     result_defaults(T0, *out);
     if (max_iterations == 0) return TDV_OK;
@@ -1558,8 +1556,6 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     ctx->last_icp_search = pl.search;
     const NnPlan& p = pl.p;
     const CellGrid& cg = pl.cg;
-    const bool ref_acc = ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE;
-    const bool robust = ctx_robust(ctx);
     const IcpLoss loss = ctx_loss(ctx);
     TDV_TRY(pin_reserve(ctx, 2 * sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
@@ -1574,7 +1570,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
         TDV_HIP(ctx, hipMemcpyAsync(d_st, h, sizeof(IcpState), hipMemcpyHostToDevice, s));
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
-            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res, gicp, color);
+            launch_icp_small(ctx, 1, d_src, ns, nullptr, d_tgt, d_tgt_normals, nt, obj, d_st, tau, max_iterations, fixed_iterations, d_st + 1, h_res);
         }
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipStreamSynchronize(s));
@@ -1595,7 +1591,6 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
         k_aos_to_soa_pad<<<(p.nt_pad + 255) / 256, 256, 0, s>>>(d_tgt, nt, p.nt_pad, INFINITY, b.tx, b.ty, b.tz);
     }
     TDV_CHECK_LAUNCH(ctx);
-    const bool p2pl = point_to_plane && d_tgt_normals;
     const int direct = pl.direct ? 1 : 0;
     // reference-order accumulation: dense records of the accepted correspondences + one-workgroup ordered fold instead of k_icp_accumulate
     const int ref_blocks = (ns + 255) / 256;
@@ -1620,47 +1615,22 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 k_icp_nn_scan<<<grid, NN_BLOCK, 0, s>>>(d_src, ns, p.ns_pad, b.tx, b.ty, b.tz, p.n_chunks,
                                                         p.chunks_per_split, b.st, b.pd2, b.pchunk);
         }
-        if (ref_acc) {
-            k_icp_flags<<<ref_blocks, 256, 0, s>>>(ns, p.ns_pad, p.nsplit, b.pd2, b.st, tau, ref_cnt);
-            k_icp_scan_counts<<<1, 1024, 0, s>>>(ref_cnt, ref_blocks, b.st, ref_off);
-            if (p2pl) {
-                k_icp_rows<0><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
-                k_icp_fold_ref<0><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
+        icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto REF) {
+            constexpr int MODE = decltype(M)::value;
+            const float* nrm = MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals;
+            if constexpr (decltype(REF)::value) {
+                k_icp_flags<<<ref_blocks, 256, 0, s>>>(ns, p.ns_pad, p.nsplit, b.pd2, b.st, tau, ref_cnt);
+                k_icp_scan_counts<<<1, 1024, 0, s>>>(ref_cnt, ref_blocks, b.st, ref_off);
+                k_icp_rows<MODE><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nrm, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
+                k_icp_fold_ref<MODE><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
             } else {
-                k_icp_rows<1><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nullptr, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
-                k_icp_fold_ref<1><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
+                ppt_dispatch(p.acc_ppt, [&](auto P) {
+                    k_icp_accumulate<MODE, decltype(P)::value, decltype(R)::value><<<p.acc_blocks, 256, 0, s>>>(
+                        d_src, ns, p.ns_pad, d_tgt, nrm, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket,
+                        nullptr, nullptr, nullptr, kernel_args<MODE>(obj));
+                });
             }
-        } else if (gicp.src_normals) {
-#define TDV_GACC1(PP) do { if (robust) TDV_GACC2(PP, true); else TDV_GACC2(PP, false); } while (0)
-#define TDV_GACC2(PP, RR) k_icp_accumulate<3, PP, RR, IcpGicp><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, \
-                              p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr, gicp)
-#ifdef TDV_STUDY
-            if (p.acc_ppt == 8) TDV_GACC1(8); else if (p.acc_ppt == 4) TDV_GACC1(4); else if (p.acc_ppt == 2) TDV_GACC1(2); else TDV_GACC1(1);
-#else
-            if (p.acc_ppt == 4) TDV_GACC1(4); else TDV_GACC1(1);
-#endif
-        } else if (color.src_rgb) {
-#define TDV_CACC1(PP) do { if (robust) TDV_CACC2(PP, true); else TDV_CACC2(PP, false); } while (0)
-#define TDV_CACC2(PP, RR) k_icp_accumulate<4, PP, RR, IcpColor><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, d_tgt_normals, b.tx, b.ty, b.tz, \
-                              p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr, color)
-#ifdef TDV_STUDY
-            if (p.acc_ppt == 8) TDV_CACC1(8); else if (p.acc_ppt == 4) TDV_CACC1(4); else if (p.acc_ppt == 2) TDV_CACC1(2); else TDV_CACC1(1);
-#else
-            if (p.acc_ppt == 4) TDV_CACC1(4); else TDV_CACC1(1);
-#endif
-        } else if (p2pl) {
-#define TDV_ACC2(MM, PP, RR, NRM) k_icp_accumulate<MM, PP, RR><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, NRM, b.tx, b.ty, b.tz, \
-                               p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket, nullptr, nullptr, nullptr)
-#define TDV_ACC1(MM, PP, NRM) do { if (robust) TDV_ACC2(MM, PP, true, NRM); else TDV_ACC2(MM, PP, false, NRM); } while (0)
-#ifdef TDV_STUDY
-#define TDV_ACC(MM, NRM) do { if (p.acc_ppt == 8) TDV_ACC1(MM, 8, NRM); else if (p.acc_ppt == 4) TDV_ACC1(MM, 4, NRM); else if (p.acc_ppt == 2) TDV_ACC1(MM, 2, NRM); else TDV_ACC1(MM, 1, NRM); } while (0)
-#else
-#define TDV_ACC(MM, NRM) do { if (p.acc_ppt == 4) TDV_ACC1(MM, 4, NRM); else TDV_ACC1(MM, 1, NRM); } while (0)     // (2 and 8 points per thread: study build)
-#endif
-            TDV_ACC(0, d_tgt_normals);
-        } else {
-            TDV_ACC(1, nullptr);
-        }
+        });
     }));
     state_result(*h, *out);
     return TDV_OK;
@@ -1676,7 +1646,7 @@ bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt) {
 // of d_src (each at most SM_MAX_N, as nt), start pose T0s[b] (host, column-major).  Results as icp_run_dev's, bit for bit (the same
 // kernel).  One upload, one launch, one download.
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp, IcpColor color) {
+                        const float* T0s, float thr, int max_iterations, IcpObjective obj, tdv_icp_result* out) {
     if (!ctx || !d_src || !d_src_off || !d_tgt || !T0s || !out || n_prob < 0 || nt <= 0 || nt > SM_MAX_N || max_iterations < 0) return TDV_ERR_BAD_ARG;
     if (n_prob == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
@@ -1692,7 +1662,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
         // (A quarter-size shape - 256 lanes, more problems resident at once - was measured against this one on C5's 1,024 instances in
         // round 3: 1.59 ms against 1.33 ms.  The pass lasts as long as its slowest problem and a lone workgroup iterates faster with
         // 16 waves; the variant is gone, profiles/r3/history keeps the numbers.)
-        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, point_to_plane, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr, gicp, color);
+        launch_icp_small(ctx, n_prob, d_src, 0, d_src_off, d_tgt, d_tgt_normals, nt, obj, d_st, tau, max_iterations, 0, d_st + n_prob, nullptr);
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipMemcpyAsync(h, d_st + n_prob, (size_t)n_prob * sizeof(IcpState), hipMemcpyDeviceToHost, s));
     }
@@ -1709,8 +1679,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
 // states per burst.  Otherwise: small problems in one k_icp_small launch (icp_small_batch_dev), else icp_run_dev per instance with
 // the shared grid or Morton order.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
-                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out, IcpGicp gicp,
-                      IcpColor color) {
+                      int nt, const float* T0s, float thr, int max_iterations, IcpObjective obj, int fixed_iterations, tdv_icp_result* out) {
     for (int b = 0; b < n; ++b) result_defaults(T0s + 16 * (size_t)b, out[b]);
     if (n == 0) return TDV_OK;
     int ns_max = 0, span = 0;
@@ -1731,7 +1700,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         int* d_off;
         TDV_TRY(ws_alloc(ctx, (size_t)n + 1, &d_off));
         TDV_HIP(ctx, hipMemcpyAsync(d_off, off.data(), ((size_t)n + 1) * sizeof(int), hipMemcpyHostToDevice, s));   // (off outlives the call's sync)
-        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, point_to_plane, out, gicp, color);
+        return icp_small_batch_dev(ctx, d_src, d_off, n, d_tgt, d_tgt_normals, nt, T0s, thr, max_iterations, obj, out);
     }
     // the target's hash grid at this threshold, once for the call (icp_run_dev uses a grid under AUTO or GRID)
     CellGrid cg{}; bool have_grid = false;
@@ -1749,12 +1718,8 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         }
         for (int b = 0; b < n; ++b) {
             const WsMark mark = ws_mark(ctx);
-            IcpGicp g = gicp;
-            if (g.src_normals) g.src_normals += (size_t)h_start[b] * 3;
-            IcpColor c = color;
-            if (c.src_rgb) c.src_rgb += (size_t)h_start[b] * 3;
             TDV_TRY(icp_run_dev(ctx, d_src + (size_t)h_start[b] * 3, h_count[b], d_tgt, d_tgt_normals, nt, T0s + 16 * (size_t)b, thr, max_iterations,
-                                point_to_plane, fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr, g, c));
+                                obj.at(h_start[b]), fixed_iterations, &out[b], have_sorted ? &sorted : nullptr, have_grid ? &cg : nullptr));
             ws_rewind(ctx, mark);
         }
         return TDV_OK;
@@ -1802,7 +1767,6 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const int* d_blk_acc = d_blk_nn + nn_blocks;
     const GridEntry* gtable = reinterpret_cast<const GridEntry*>(cg.table);
     const float4* gnode = reinterpret_cast<const float4*>(cg.node);
-    const bool p2pl = point_to_plane && d_tgt_normals, robust = ctx_robust(ctx);
     const IcpLoss loss = ctx_loss(ctx);
     ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
     TDV_TRY(run_bursts(ctx, h, d_st, n, max_iterations, fixed_iterations, [&]() {
@@ -1810,18 +1774,12 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
             k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);
         }
-        if (gicp.src_normals) {
-            const auto acc = robust ? k_icp_accumulate_multi<3, true, IcpGicp> : k_icp_accumulate_multi<3, false, IcpGicp>;
-            acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets, gicp);
-            return;
-        }
-        if (color.src_rgb) {
-            const auto acc = robust ? k_icp_accumulate_multi<4, true, IcpColor> : k_icp_accumulate_multi<4, false, IcpColor>;
-            acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets, color);
-            return;
-        }
-        const auto acc = p2pl ? (robust ? k_icp_accumulate_multi<0, true> : k_icp_accumulate_multi<0>) : (robust ? k_icp_accumulate_multi<1, true> : k_icp_accumulate_multi<1>);
-        acc<<<acc_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_acc, d_tgt, p2pl ? d_tgt_normals : nullptr, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets);
+        icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto) {      // (tree sums: see above)
+            constexpr int MODE = decltype(M)::value;
+            k_icp_accumulate_multi<MODE, decltype(R)::value><<<acc_blocks, 256, 0, s>>>(
+                d_src, d_inst, d_blk_acc, d_tgt, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets,
+                kernel_args<MODE>(obj));
+        });
     }));
     for (int b = 0; b < n; ++b) state_result(h[b], out[b]);
     return TDV_OK;
@@ -1836,26 +1794,22 @@ int icp_loss_check(tdv_ctx* ctx) {
     return TDV_OK;
 }
 
-int gicp_check(tdv_ctx* ctx, const float* src_normals, const float* tgt_normals, float epsilon) {
-    if (!src_normals || !tgt_normals || !std::isfinite(epsilon) || !(epsilon > 0.f && epsilon <= 1.f)) return TDV_ERR_BAD_ARG;
-    if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
-        snprintf(ctx->err, sizeof(ctx->err), "gicp: reference-order accumulation reproduces the reference's float sums, and the reference has no "
-                 "generalized ICP; set TDV_ICP_ACCUMULATE_TREE");
-        return TDV_ERR_BAD_ARG;
-    }
-    return TDV_OK;
-}
-
-int colored_check(tdv_ctx* ctx, const float* src_rgb, const float* tgt_normals, const float* tgt_color, float lambda_geometric, bool device) {
-    if (!src_rgb || !tgt_normals || !tgt_color || !std::isfinite(lambda_geometric) || !(lambda_geometric >= 0.f && lambda_geometric <= 1.f))
-        return TDV_ERR_BAD_ARG;
-    if (device && (reinterpret_cast<uintptr_t>(tgt_color) & 15) != 0) {
-        snprintf(ctx->err, sizeof(ctx->err), "colored_icp: the target colour table is read as float4 and must be 16-byte aligned");
-        return TDV_ERR_BAD_ARG;
+int icp_objective_check(tdv_ctx* ctx, const IcpObjective& obj, const float* tgt_normals, bool device) {
+    if (obj.kind < ICP_GICP) return icp_loss_check(ctx);
+    // (below, reference-order sums are refused: no loss check needed)
+    const bool gicp = obj.kind == ICP_GICP;
+    if (gicp) {
+        if (!obj.src_normals || !tgt_normals || !std::isfinite(obj.param) || !(obj.param > 0.f && obj.param <= 1.f)) return TDV_ERR_BAD_ARG;
+    } else {
+        if (!obj.src_rgb || !tgt_normals || !obj.tgt_color || !std::isfinite(obj.param) || !(obj.param >= 0.f && obj.param <= 1.f)) return TDV_ERR_BAD_ARG;
+        if (device && (reinterpret_cast<uintptr_t>(obj.tgt_color) & 15) != 0) {
+            snprintf(ctx->err, sizeof(ctx->err), "colored_icp: the target colour table is read as float4 and must be 16-byte aligned");
+            return TDV_ERR_BAD_ARG;
+        }
     }
     if (ctx->icp_accumulate == TDV_ICP_ACCUMULATE_REFERENCE) {
-        snprintf(ctx->err, sizeof(ctx->err), "colored_icp: reference-order accumulation reproduces the reference's float sums, and the reference has "
-                 "no colored ICP; set TDV_ICP_ACCUMULATE_TREE");
+        snprintf(ctx->err, sizeof(ctx->err), "%s: reference-order accumulation reproduces the reference's float sums, and the reference has no "
+                 "%s ICP; set TDV_ICP_ACCUMULATE_TREE", gicp ? "gicp" : "colored_icp", gicp ? "generalized" : "colored");
         return TDV_ERR_BAD_ARG;
     }
     return TDV_OK;
@@ -1895,7 +1849,7 @@ int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const floa
                                                                       p.chunks_per_split, b.st, b.pd2, b.pchunk);
     }
     k_icp_accumulate<2, 1><<<p.acc_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nullptr, b.tx, b.ty, b.tz, p.nsplit,
-                                                        b.pd2, b.pchunk, pruned ? 1 : 0, b.st, tau, 0, IcpLoss{TDV_ICP_LOSS_L2, 0.f}, b.slabs, b.ticket, outs.corr, outs.d2, outs.accepted);
+                                                        b.pd2, b.pchunk, pruned ? 1 : 0, b.st, tau, 0, IcpLoss{TDV_ICP_LOSS_L2, 0.f}, b.slabs, b.ticket, outs.corr, outs.d2, outs.accepted, IcpArgs<2>{});
     TDV_CHECK_LAUNCH(ctx);
     TDV_HIP(ctx, hipMemcpyAsync(h, b.st, sizeof(IcpState), hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipStreamSynchronize(s));

@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <climits>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -146,13 +147,30 @@ struct ScopedTimer {
 struct IcpOutputs {  // optional per-source outputs of one correspondence pass (device pointers)
     int* corr = nullptr; float* d2 = nullptr; uint8_t* accepted = nullptr;
 };
-// Generalized ICP (plane-to-plane, include/tdv_hip.h: tdv_gicp): the source normals, laid out like the source points (device), and
-// c = 1 - epsilon in f32.  src_normals == nullptr: not GICP - the ICP objective the other arguments select.
-struct IcpGicp { const float* src_normals; float c; };
-// Colored ICP (Park et al. 2017, include/tdv_hip.h: tdv_colored_icp): the source colours, laid out like the source points (device),
-// the target's colour table (float4 (I, d) per point, tdv_color_gradients), lg = sqrtf(lambda) and lc = sqrtf(1 - lambda).
-// src_rgb == nullptr: not colored ICP.
-struct IcpColor { const float* src_rgb; const float* tgt_color; float lg, lc; };
+// What an ICP call minimises: the kind (its value is the kernels' MODE, icp.hip; point-to-plane without target normals runs as
+// point-to-point: icp_dispatch) and what the kind needs beyond the clouds and the
+// target's normals.  GICP (plane-to-plane, include/tdv_hip.h: tdv_gicp): the source normals and c = 1 - epsilon in f32.  Colored ICP
+// (Park et al. 2017, tdv_colored_icp): the source colours, the target's colour table (float4 (I, d) per point, tdv_color_gradients),
+// lg = sqrtf(lambda) and lc = sqrtf(1 - lambda).  Source normals and colours are laid out like the source points.
+enum IcpKind { ICP_POINT_TO_PLANE = 0, ICP_POINT_TO_POINT = 1, ICP_GICP = 3, ICP_COLORED = 4 };
+struct IcpObjective {
+    IcpKind kind;
+    const float* src_normals; float c;                            // GICP
+    const float *src_rgb, *tgt_color; float lg, lc;               // colored ICP
+    float param;                                                  // epsilon resp. lambda as the caller gave it (icp_objective_check)
+    static IcpObjective plain(int point_to_plane) { return {point_to_plane ? ICP_POINT_TO_PLANE : ICP_POINT_TO_POINT, nullptr, 0.f, nullptr, nullptr, 0.f, 0.f, 0.f}; }
+    static IcpObjective gicp(const float* src_normals, float epsilon) { return {ICP_GICP, src_normals, 1.f - epsilon, nullptr, nullptr, 0.f, 0.f, epsilon}; }
+    static IcpObjective colored(const float* src_rgb, const float* tgt_color, float lambda) {
+        return {ICP_COLORED, nullptr, 0.f, src_rgb, tgt_color, sqrtf(lambda), sqrtf(1.f - lambda), lambda};
+    }
+    // the objective of an instance whose source points start at point `start` of the arrays
+    IcpObjective at(int start) const {
+        IcpObjective o = *this;
+        if (o.src_normals) o.src_normals += (size_t)start * 3;
+        if (o.src_rgb) o.src_rgb += (size_t)start * 3;
+        return o;
+    }
+};
 struct SortedCloud;
 // Hash grid over a target cloud for ICP's correspondence search at one acceptance threshold (icp.hip): cells of 2.2 x
 // the threshold, open-addressing table of (32-bit cell tag, list head), the points of a cell as a linked list of (x, y, z, next) nodes indexed like the cloud.  Lives
@@ -163,31 +181,27 @@ int cell_grid_build(tdv_ctx* ctx, const float* d_tgt, int nt, float thr, CellGri
 // tgt_sorted / tgt_grid (optional): the target in Morton order with its boxes (spatial_sort_cloud) resp. its hash grid
 // (cell_grid_build, for this thr), built once and reused across calls
 int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
-                const float* T0, float thr, int max_iterations, int point_to_plane, int fixed_iterations,
-                tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr, IcpGicp gicp = IcpGicp{nullptr, 0.f},
-                IcpColor color = IcpColor{nullptr, nullptr, 0.f, 0.f});
+                const float* T0, float thr, int max_iterations, IcpObjective obj, int fixed_iterations,
+                tdv_icp_result* out, const SortedCloud* tgt_sorted = nullptr, const CellGrid* tgt_grid = nullptr);
 // many small problems against one target in one launch (icp.hip: k_icp_small), when icp_small_batch_fits(ctx, largest problem, nt)
 bool icp_small_batch_fits(const tdv_ctx* ctx, int ns_max, int nt);
 int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, int n_prob, const float* d_tgt, const float* d_tgt_normals, int nt,
-                        const float* T0s, float thr, int max_iterations, int point_to_plane, tdv_icp_result* out, IcpGicp gicp = IcpGicp{nullptr, 0.f},
-                        IcpColor color = IcpColor{nullptr, nullptr, 0.f, 0.f});
+                        const float* T0s, float thr, int max_iterations, IcpObjective obj, tdv_icp_result* out);
 // icp_run_dev for n instances against one target (icp.hip): instance b = h_count[b] points from point h_start[b] of d_src (host arrays), start
-// pose T0s + 16 b; per instance icp_run_dev's result bit for bit.  Arguments are not checked.
+// pose T0s + 16 b, obj's source arrays laid out like d_src; per instance icp_run_dev's result bit for bit.  Arguments are not checked.
 int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, const int* h_count, int n, const float* d_tgt, const float* d_tgt_normals,
-                      int nt, const float* T0s, float thr, int max_iterations, int point_to_plane, int fixed_iterations, tdv_icp_result* out,
-                      IcpGicp gicp = IcpGicp{nullptr, 0.f}, IcpColor color = IcpColor{nullptr, nullptr, 0.f, 0.f});
+                      int nt, const float* T0s, float thr, int max_iterations, IcpObjective obj, int fixed_iterations, tdv_icp_result* out);
 int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                             const float* T, float thr, IcpOutputs outs, int* n_corr);
 // TDV_ERR_BAD_ARG (reason in ctx->err) when the ctx's ICP loss cannot run with its accumulation mode (a robust loss with
 // reference-order sums); the ICP entry points ask before they enqueue or write anything
 int icp_loss_check(tdv_ctx* ctx);
-// TDV_ERR_BAD_ARG (reason in ctx->err) for GICP's own arguments: a NULL normal array, epsilon not finite or outside (0, 1], or a ctx
-// in reference-order accumulation (the reference has no GICP)
-int gicp_check(tdv_ctx* ctx, const float* src_normals, const float* tgt_normals, float epsilon);
-// TDV_ERR_BAD_ARG (reason in ctx->err) for colored ICP's own arguments: a NULL colour, colour table or normal array, lambda not finite
-// or outside [0, 1], or a ctx in reference-order accumulation (the reference has no colored ICP).  device: the colour table is a device
-// pointer, which the kernels read as float4 - it must be 16-byte aligned.
-int colored_check(tdv_ctx* ctx, const float* src_rgb, const float* tgt_normals, const float* tgt_color, float lambda_geometric, bool device);
+// what an entry point asks of its objective before it enqueues or writes anything: TDV_ERR_BAD_ARG (reason in ctx->err where there is
+// more to say than "bad argument").  Point-to-plane and point-to-point: icp_loss_check.  GICP: a NULL normal array, epsilon not finite or
+// outside (0, 1], or a ctx in reference-order accumulation (the reference has no GICP).  Colored ICP: a NULL colour, colour table or
+// normal array, lambda not finite or outside [0, 1], or reference-order accumulation; device: the colour table is a device pointer,
+// which the kernels read as float4 - it must be 16-byte aligned.
+int icp_objective_check(tdv_ctx* ctx, const IcpObjective& obj, const float* tgt_normals, bool device);
 int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel, int max_iterations, float confidence, uint32_t seed,
@@ -286,7 +300,7 @@ int spatial_sort_cloud(tdv_ctx* ctx, const float* d_xyz, int n, SortedCloud& out
 // d_tie_ids / d_tie_ids_inv (optional, both or neither): neighbour lists are ordered by (d2, d_tie_ids[index]) instead of
 // (d2, index) — the results are those of the cloud permuted so that point i sits at position d_tie_ids[i]
 int normals_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float radius, float* d_normals, float* d_desc,
-                     const int* d_tie_ids = nullptr, const int* d_tie_ids_inv = nullptr);                                      // padded record count for sort_records_dev
+                     const int* d_tie_ids = nullptr, const int* d_tie_ids_inv = nullptr);
 
 // the same for many small clouds stored back to back, in one set of launches (knn.hip); tie ids / their inverse are GLOBAL here
 int normals_fpfh_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_voff, const int* d_voff, int n_clouds, int k, float radius,
