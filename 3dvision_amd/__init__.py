@@ -724,6 +724,32 @@ class Context:
         _check(self._h, lib().tdv_radix_sort_pairs_dev(self._h, _ptr(d_keys_in), _ptr(d_keys_out), _ptr(d_vals_in), _ptr(d_vals_out), C.c_size_t(n), end_bit),
                "tdv_radix_sort_pairs_dev")
 
+    # op -> (code, floats in, floats out per problem) of tdv_study_probe (csrc/probe.hip)
+    STUDY_PROBE_OPS = {"svd3": (0, 9, 21), "kabsch_rotation": (1, 9, 9), "smallest_eigvec3": (2, 6, 4), "ldlt6_solve": (3, 42, 6),
+                       "euler_xyz": (4, 3, 9), "mul44": (5, 32, 16), "sinf": (6, 1, 1), "cosf": (7, 1, 1), "atanf": (8, 1, 1),
+                       "atan2f": (9, 2, 1), "ransac_hypothesis": (10, 24, 12)}
+
+    def study_probe(self, op, inputs):
+        """One per-lane device function (csrc/device_linalg.hpp, libm_f32.hpp, ransac_hypothesis_lane) on n problems, one per lane:
+        `inputs` is float32 [n, floats in] - a numpy array (the result is one too) or a torch tensor on this context's device (the
+        result stays there).  The study library only: raises TdvError on the product library, which has no such entry point."""
+        import torch
+        if not hasattr(lib(), "tdv_study_probe"):
+            raise TdvError("study_probe needs the study library (TDV_LIB_VARIANT=study); the product library has no probe")
+        code, k_in, k_out = self.STUDY_PROBE_OPS[op]
+        host = not isinstance(inputs, torch.Tensor)
+        d_in = torch.from_numpy(np.ascontiguousarray(inputs, np.float32)).to(torch.device("cuda", self.device)) if host else inputs.contiguous()
+        if d_in.device != torch.device("cuda", self.device):
+            raise ValueError("study_probe: the tensor lies on %s, this context runs on cuda:%d" % (d_in.device, self.device))
+        if d_in.dtype != torch.float32 or d_in.numel() % k_in:
+            raise ValueError("%s takes float32 [n, %d]" % (op, k_in))
+        n = d_in.numel() // k_in
+        d_out = torch.empty((n, k_out), dtype=torch.float32, device=d_in.device)
+        torch.cuda.synchronize(d_in.device)
+        _check(self._h, lib().tdv_study_probe(self._h, code, C.c_longlong(n), C.c_void_p(d_in.data_ptr() if n else 0), C.c_void_p(d_out.data_ptr() if n else 0)),
+               "tdv_study_probe")
+        return d_out.cpu().numpy() if host else d_out
+
     def depth_to_cloud_dev(self, d_raw, d_mask, d_bgr, w, h, scale, fx, fy, cx, cy, zmax, d_xyz, d_rgb, capacity,
                            mask_mode=TDV_MASK_THRESHOLD10):
         n = C.c_int()

@@ -24,6 +24,11 @@ namespace dl {
 #define TDV_DI __device__ __forceinline__
 
 TDV_DI float s3(float a, float b, float c) { return a + (b + c); }
+// Eigen's numext::maxi / mini (std::max / std::min): a NaN in the FIRST argument is returned, one in the second is dropped.  The
+// IEEE maxNum / minNum of the C library drop both, and a solver's scale, maxDiag or threshold then differs from the CPU's on a
+// matrix with a NaN entry (tests/test_gpu_solver_probe.py).
+TDV_DI float maxi(float a, float b) { return a < b ? b : a; }
+TDV_DI float mini(float a, float b) { return b < a ? b : a; }
 
 struct Mat3 { float a[9]; };
 TDV_DI float& el(Mat3& m, int r, int c) { return m.a[c * 3 + r]; }
@@ -112,7 +117,7 @@ template <int P, int Q> TDV_DI void rot_cols(Mat3& m, Rot2 j) {
 template <int P, int Q>
 TDV_DI bool svd_sweep_pair(Mat3& W, Mat3& U, Mat3& V, float& maxDiag) {
     const float precision = 2.f * FLT_EPSILON;
-    float threshold = fmaxf(FLT_MIN, precision * maxDiag);
+    float threshold = maxi(FLT_MIN, precision * maxDiag);
     if (!(fabsf(el(W, P, Q)) > threshold || fabsf(el(W, Q, P)) > threshold)) return false;
     float m00 = el(W, P, P), m01 = el(W, P, Q), m10 = el(W, Q, P), m11 = el(W, Q, Q);
     Rot2 rot1;
@@ -134,7 +139,7 @@ TDV_DI bool svd_sweep_pair(Mat3& W, Mat3& U, Mat3& V, float& maxDiag) {
     rot_cols<P, Q>(U, rtrans(jl));
     rot_cols<P, Q>(W, jr);
     rot_cols<P, Q>(V, jr);
-    maxDiag = fmaxf(maxDiag, fmaxf(fabsf(el(W, P, P)), fabsf(el(W, Q, Q))));
+    maxDiag = maxi(maxDiag, maxi(fabsf(el(W, P, P)), fabsf(el(W, Q, Q))));
     return true;
 }
 
@@ -147,13 +152,13 @@ template <int A, int B> TDV_DI void swap_cols(Mat3& m) {
 TDV_DI void svd3(const Mat3& A, Mat3& U, Mat3& V, float& s0, float& s1, float& s2) {
     float scale = 0.f;
 #pragma unroll
-    for (int i = 0; i < 9; ++i) scale = fmaxf(scale, fabsf(A.a[i]));
+    for (int i = 0; i < 9; ++i) scale = maxi(scale, fabsf(A.a[i]));
     if (scale == 0.f) scale = 1.f;
     Mat3 W;
 #pragma unroll
     for (int i = 0; i < 9; ++i) W.a[i] = A.a[i] / scale;
     U = ident3(); V = ident3();
-    float maxDiag = fmaxf(fabsf(el(W, 0, 0)), fmaxf(fabsf(el(W, 1, 1)), fabsf(el(W, 2, 2))));
+    float maxDiag = maxi(fabsf(el(W, 0, 0)), maxi(fabsf(el(W, 1, 1)), fabsf(el(W, 2, 2))));
     bool finished = false;
     int guard = 0;  // the sweep converges in a handful of passes; bound it so no lane can spin
     while (!finished && guard < 64) {
@@ -196,9 +201,9 @@ TDV_DI Mat3 kabsch_rotation(const Mat3& H) {
 
 TDV_DI float hypot_pos(float x, float y) {
     x = fabsf(x); y = fabsf(y);
-    float p = fmaxf(x, y);
+    float p = maxi(x, y);
     if (p == 0.f) return 0.f;
-    float qp = fminf(y, x) / p;
+    float qp = mini(y, x) / p;
     return p * sqrtf(1.f + qp * qp);
 }
 
@@ -212,7 +217,7 @@ TDV_DI void rot_cols_dyn(Mat3& Q, int k, Rot2 j) {
 // as the reference's solver would leave it).
 TDV_DI bool smallest_eigvec3(float a00, float a10, float a20, float a11, float a21, float a22,
                              float& vx, float& vy, float& vz) {
-    float scale = fmaxf(fmaxf(fabsf(a00), fabsf(a10)), fmaxf(fmaxf(fabsf(a20), fabsf(a11)), fmaxf(fabsf(a21), fabsf(a22))));
+    float scale = maxi(maxi(fabsf(a00), fabsf(a10)), maxi(maxi(fabsf(a20), fabsf(a11)), maxi(fabsf(a21), fabsf(a22))));
     if (scale == 0.f) scale = 1.f;
     a00 /= scale; a10 /= scale; a20 /= scale; a11 /= scale; a21 /= scale; a22 /= scale;
     float d0, d1, d2, e0, e1;

@@ -1621,4 +1621,30 @@ int ransac_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_off, c
     return TDV_OK;
 }
 
+#ifdef TDV_STUDY
+// ------------------------------------------------------------------ probe (probe.hip: tdv_study_probe, op 10)
+// ransac_hypothesis_lane on n hand-made triples: problem h's three records of d_in are points 3h, 3h + 1, 3h + 2 of a pq array, its
+// lane writes column h of a [14][n] hyp, and rows 0-11 go out as d_out[h][12].  pmax = 0 and sqrt_tau = 1: they enter the band rows only.
+__global__ void k_probe_hypotheses(const float* __restrict__ pq, int n, float* __restrict__ hyp, const unsigned* __restrict__ pmax) {
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n) return;
+    ransac_hypothesis_lane(pq, make_int4(3 * h, 3 * h + 1, 3 * h + 2, 1), true, h, n, hyp, pmax, 1.f, 16.f * 5.9604644775390625e-08f);
+}
+__global__ void k_probe_hypotheses_out(const float* __restrict__ hyp, int n, float* __restrict__ out) {
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h >= n) return;
+    for (int k = 0; k < 12; ++k) out[(size_t)h * 12 + k] = hyp[(size_t)k * n + h];
+}
+int probe_hypotheses_dev(tdv_ctx* ctx, int n, const float* d_in, float* d_out) {
+    float* hyp; unsigned* d_pmax;
+    TDV_TRY(ws_alloc(ctx, (size_t)14 * n, &hyp));
+    TDV_TRY(ws_alloc(ctx, 1, &d_pmax));
+    TDV_HIP(ctx, hipMemsetAsync(d_pmax, 0, 4, ctx->stream));
+    k_probe_hypotheses<<<(n + 255) / 256, 256, 0, ctx->stream>>>(d_in, n, hyp, d_pmax);
+    k_probe_hypotheses_out<<<(n + 255) / 256, 256, 0, ctx->stream>>>(hyp, n, d_out);
+    TDV_CHECK_LAUNCH(ctx);
+    return TDV_OK;
+}
+#endif  // TDV_STUDY
+
 }  // namespace tdv

@@ -20,6 +20,14 @@ int orc_filter_duplicates(const float*, int, float, float*);
 void orc_demo_scene(int, int, float, uint16_t*, uint8_t*);
 void orc_demo_mask(int, int, uint8_t*);
 int orc_demo_model(float*, float*, int);
+void orc_jacobi_svd3_batch(int, const float*, float*, float*, float*, int*);
+void orc_kabsch_rotation_batch(int, const float*, float*);
+void orc_self_adjoint_eig3_batch(int, const float*, float*, float*, int*, int*);
+void orc_ldlt6_solve_batch(int, const float*, const float*, float*);
+void orc_euler_xyz_matrix_batch(int, const float*, float*);
+void orc_mul44_batch(int, const float*, const float*, float*);
+void orc_hypothesis_from_pairs_batch(int, const float*, const float*, float*);
+int orc_libm_f32_batch(int, long long, const float*, const float*, float*);
 }
 static float frand() { return (float)rand() / (float)RAND_MAX; }
 int main() {
@@ -66,6 +74,25 @@ int main() {
     int k = orc_filter_duplicates(poses.data(), 10, 0.1f, kept.data());
     std::vector<float> mx(3 * 2000), mn(3 * 2000);
     int nm = orc_demo_model(mx.data(), mn.data(), 2000);
+    // the batch solver exports, poisoned entries included
+    {
+        const int nb = 64;
+        std::vector<float> A9(nb * 9), U(nb * 9), S(nb * 3), V(nb * 9), w(nb * 3), A36(nb * 36), b6(nb * 6), x6(nb * 6), abg(nb * 3), A16(nb * 16), B16(nb * 16), C16(nb * 16), lm(nb * 3);
+        std::vector<int> sw(nb), rc(nb), qr(nb);
+        for (auto& v : A9) v = frand() - 0.5f; for (auto& v : A36) v = frand() - 0.5f; for (auto& v : b6) v = frand();
+        for (auto& v : abg) v = 300.f * (frand() - 0.5f); for (auto& v : A16) v = frand(); for (auto& v : B16) v = frand();
+        for (int i = 0; i < 6; ++i) { A9[9 * i + i] = poison[i % 3]; A36[36 * (i + 8) + 7 * i] = poison[i % 3]; abg[3 * i] = poison[i % 3]; A16[16 * i + i] = poison[i % 3]; }
+        for (int i = 0; i < 9; ++i) A9[9 * 10 + i] = 0.f;
+        orc_jacobi_svd3_batch(nb, A9.data(), U.data(), S.data(), V.data(), sw.data());
+        orc_kabsch_rotation_batch(nb, A9.data(), U.data());
+        orc_self_adjoint_eig3_batch(nb, A9.data(), w.data(), V.data(), rc.data(), qr.data());
+        orc_ldlt6_solve_batch(nb, A36.data(), b6.data(), x6.data());
+        orc_euler_xyz_matrix_batch(nb, abg.data(), U.data());
+        orc_mul44_batch(nb, A16.data(), B16.data(), C16.data());
+        orc_hypothesis_from_pairs_batch(nb / 2, A9.data(), A9.data() + 9 * (nb / 2), C16.data());
+        for (int op = 0; op < 4; ++op) it += orc_libm_f32_batch(op, nb * 3, abg.data(), A9.data(), lm.data());
+        it += sw[0] - sw[0] + qr[1] - qr[1];
+    }
     printf("asan_check ok: cloud %d voxels %d ransac best %d icp iters %d kept %d model %d\n", n, m, bi, it, k, nm);
     return 0;
 }

@@ -234,6 +234,53 @@ void orc_ldlt6_solve(const float* A_rowmajor, const float* b, float* x) { ldlt6_
 void orc_euler_xyz_matrix(float a, float b, float g, float* R_colmajor) {
     M3 r = euler_xyz_matrix(a, b, g); std::memcpy(R_colmajor, r.m, 36);
 }
+// T = A * B for column-major 4x4 (the product of ICP's T = delta * T)
+void orc_mul44(const float* A, const float* B, float* C) { mul44(A, B, C); }
+
+// Batch forms of the solver exports: n problems back to back in the single call's layout, the single call's results byte for
+// byte (tests/test_oracle_solver_batch.py).  sweeps[i]: passes of problem i's Jacobi sweep loop, the last, idle one included;
+// iters[i]: its QR step count (91 = the iteration gave up).
+void orc_jacobi_svd3_batch(int n, const float* A, float* U, float* S, float* V, int* sweeps) {
+    for (int i = 0; i < n; ++i) {
+        M3 a; std::memcpy(a.m, A + 9 * (size_t)i, 36);
+        int sw = 0;
+        SVD3 r = jacobi_svd3(a, &sw);
+        std::memcpy(U + 9 * (size_t)i, r.U.m, 36); std::memcpy(V + 9 * (size_t)i, r.V.m, 36); std::memcpy(S + 3 * (size_t)i, r.s, 12);
+        if (sweeps) sweeps[i] = sw;
+    }
+}
+void orc_kabsch_rotation_batch(int n, const float* H, float* R) {
+    for (int i = 0; i < n; ++i) orc_kabsch_rotation(H + 9 * (size_t)i, R + 9 * (size_t)i);
+}
+void orc_self_adjoint_eig3_batch(int n, const float* A, float* w, float* V, int* rc, int* iters) {
+    for (int i = 0; i < n; ++i) {
+        M3 a; std::memcpy(a.m, A + 9 * (size_t)i, 36);
+        Eig3 r = self_adjoint_eig3(a);
+        std::memcpy(w + 3 * (size_t)i, r.w, 12); std::memcpy(V + 9 * (size_t)i, r.V.m, 36);
+        rc[i] = r.ok ? 0 : 1;
+        if (iters) iters[i] = r.iter;
+    }
+}
+void orc_ldlt6_solve_batch(int n, const float* A, const float* b, float* x) {
+    for (int i = 0; i < n; ++i) ldlt6_solve(A + 36 * (size_t)i, b + 6 * (size_t)i, x + 6 * (size_t)i);
+}
+void orc_euler_xyz_matrix_batch(int n, const float* abg, float* R) {
+    for (int i = 0; i < n; ++i) orc_euler_xyz_matrix(abg[3 * (size_t)i], abg[3 * (size_t)i + 1], abg[3 * (size_t)i + 2], R + 9 * (size_t)i);
+}
+void orc_mul44_batch(int n, const float* A, const float* B, float* C) {
+    for (int i = 0; i < n; ++i) mul44(A + 16 * (size_t)i, B + 16 * (size_t)i, C + 16 * (size_t)i);
+}
+// The RUNNING libm's float functions: op 0 sinf, 1 cosf, 2 atanf, 3 atan2f(x[i], y[i]) - x holds the first argument; y is read by
+// op 3 only.  Returns 0, or 1 for an unknown op.
+int orc_libm_f32_batch(int op, long long n, const float* x, const float* y, float* out) {
+    switch (op) {
+        case 0: for (long long i = 0; i < n; ++i) out[i] = sinf(x[i]); return 0;
+        case 1: for (long long i = 0; i < n; ++i) out[i] = cosf(x[i]); return 0;
+        case 2: for (long long i = 0; i < n; ++i) out[i] = atanf(x[i]); return 0;
+        case 3: for (long long i = 0; i < n; ++i) out[i] = atan2f(x[i], y[i]); return 0;
+    }
+    return 1;
+}
 
 // ---------------------------------------------------------------- depth + unprojection
 // pipeline.cpp:46-54.  cv::Mat::convertTo(CV_32FC1, alpha) computes in float with
@@ -503,6 +550,9 @@ void orc_hypothesis_from_pairs(const float* s3x3, const float* t3x3, float* T) {
     set_identity44(T);
     for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) T[c * 4 + r] = R(r, c);
     for (int r = 0; r < 3; ++r) T[12 + r] = t[r];
+}
+void orc_hypothesis_from_pairs_batch(int n, const float* s, const float* t, float* T) {
+    for (int i = 0; i < n; ++i) orc_hypothesis_from_pairs(s + 9 * (size_t)i, t + 9 * (size_t)i, T + 16 * (size_t)i);
 }
 
 // registration.cpp:204-295.  corr_in (optional): use these correspondences instead of

@@ -41,6 +41,7 @@ def lib():
         _LIB.orc_icp_ex.restype = C.c_int
         _LIB.orc_filter_duplicates.restype = C.c_int
         _LIB.orc_load_ply.restype = C.c_int
+        _LIB.orc_libm_f32_batch.restype = C.c_int
     return _LIB
 
 
@@ -99,6 +100,90 @@ def hypothesis_from_pairs(s3, t3):
     s = _f32(s3).reshape(9); t = _f32(t3).reshape(9); T = np.zeros(16, np.float32)
     lib().orc_hypothesis_from_pairs(_p(s), _p(t), _p(T))
     return from_colmajor16(T)
+
+
+# ----------------------------------------------------------------- solvers, many problems per call
+# The arrays cross these calls in the library's own layouts, not as numpy matrices: 3x3 COLUMN-MAJOR float32 [n,9], 6x6 row-major
+# [n,36], 4x4 column-major [n,16].  Per problem they give the single call's bytes (tests/test_oracle_solver_batch.py).
+def _rows(a, k):
+    a = np.ascontiguousarray(a, np.float32).reshape(-1, k)
+    return a, len(a)
+
+
+def jacobi_svd3_batch(A9):
+    """U [n,9], S [n,3], V [n,9] and the sweep-loop passes [n] (the last, idle pass included)."""
+    a, n = _rows(A9, 9)
+    U = np.zeros((n, 9), np.float32); S = np.zeros((n, 3), np.float32); V = np.zeros((n, 9), np.float32); sw = np.zeros(n, np.int32)
+    lib().orc_jacobi_svd3_batch(n, _p(a), _p(U), _p(S), _p(V), _p(sw))
+    return U, S, V, sw
+
+
+def kabsch_rotation_batch(H9):
+    h, n = _rows(H9, 9)
+    R = np.zeros((n, 9), np.float32)
+    lib().orc_kabsch_rotation_batch(n, _p(h), _p(R))
+    return R
+
+
+def self_adjoint_eig3_batch(A9):
+    """w [n,3], V [n,9], rc [n] (1: the QR iteration gave up) and its step count [n]."""
+    a, n = _rows(A9, 9)
+    w = np.zeros((n, 3), np.float32); V = np.zeros((n, 9), np.float32); rc = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
+    lib().orc_self_adjoint_eig3_batch(n, _p(a), _p(w), _p(V), _p(rc), _p(it))
+    return w, V, rc, it
+
+
+def ldlt6_solve_batch(A36, b6):
+    a, n = _rows(A36, 36); b, nb = _rows(b6, 6)
+    assert n == nb
+    x = np.zeros((n, 6), np.float32)
+    lib().orc_ldlt6_solve_batch(n, _p(a), _p(b), _p(x))
+    return x
+
+
+def euler_xyz_matrix_batch(abg):
+    a, n = _rows(abg, 3)
+    R = np.zeros((n, 9), np.float32)
+    lib().orc_euler_xyz_matrix_batch(n, _p(a), _p(R))
+    return R
+
+
+def mul44(A16, B16):
+    """Column-major A * B, the product of ICP's T = delta * T."""
+    a, _ = _rows(A16, 16); b, _ = _rows(B16, 16); c = np.zeros(16, np.float32)
+    lib().orc_mul44(_p(a), _p(b), _p(c))
+    return c
+
+
+def mul44_batch(A16, B16):
+    a, n = _rows(A16, 16); b, nb = _rows(B16, 16)
+    assert n == nb
+    c = np.zeros((n, 16), np.float32)
+    lib().orc_mul44_batch(n, _p(a), _p(b), _p(c))
+    return c
+
+
+def hypothesis_from_pairs_batch(s9, t9):
+    """Three source and three target points per problem ([n,9] each, point after point): T column-major [n,16]."""
+    s, n = _rows(s9, 9); t, nt = _rows(t9, 9)
+    assert n == nt
+    T = np.zeros((n, 16), np.float32)
+    lib().orc_hypothesis_from_pairs_batch(n, _p(s), _p(t), _p(T))
+    return T
+
+
+LIBM_OPS = {"sinf": 0, "cosf": 1, "atanf": 2, "atan2f": 3}
+
+
+def libm_f32_batch(name, x, y=None):
+    """The running libm's float function `name` on every x (atan2f: atan2f(x, y))."""
+    x = np.ascontiguousarray(x, np.float32).reshape(-1)
+    y = None if y is None else np.ascontiguousarray(y, np.float32).reshape(-1)
+    assert (y is not None and len(y) == len(x)) == (name == "atan2f")
+    out = np.empty(len(x), np.float32)
+    rc = lib().orc_libm_f32_batch(LIBM_OPS[name], C.c_longlong(len(x)), _p(x), _p(y), _p(out))
+    assert rc == 0
+    return out
 
 
 # ----------------------------------------------------------------- depth / unproject

@@ -121,8 +121,10 @@ template <class M> static inline void apply_right(M& w, int p, int q, Rot j, int
 
 // JacobiSVD<Matrix3f>(H, ComputeFullU|ComputeFullV) — registration.cpp:255,388.
 struct SVD3 { M3 U, V; float s[3]; };
-static inline SVD3 jacobi_svd3(const M3& A) {
+// sweeps_out (optional): passes of the sweep loop, the last one - which rotates nothing - included.
+static inline SVD3 jacobi_svd3(const M3& A, int* sweeps_out = nullptr) {
     SVD3 out;
+    int sweeps = 0;
     const float precision = 2.f * FLT_EPSILON;
     const float considerAsZero = FLT_MIN;
     float scale = 0.f;
@@ -135,6 +137,7 @@ static inline SVD3 jacobi_svd3(const M3& A) {
     bool finished = false;
     while (!finished) {
         finished = true;
+        ++sweeps;
         for (int p = 1; p < 3; ++p) {
             for (int q = 0; q < p; ++q) {
                 float threshold = std::max(considerAsZero, precision * maxDiag);
@@ -166,6 +169,7 @@ static inline SVD3 jacobi_svd3(const M3& A) {
             }
         }
     }
+    if (sweeps_out) *sweeps_out = sweeps;
     for (int i = 0; i < 3; ++i) {
         float a = W(i, i);
         out.s[i] = std::fabs(a);
@@ -208,7 +212,7 @@ static inline float pos_hypot(float x, float y) {  // Eigen numext::hypot (posit
     float qp = std::min(y, x) / p;
     return p * std::sqrt(1.f + qp * qp);
 }
-struct Eig3 { float w[3]; M3 V; bool ok; };
+struct Eig3 { float w[3]; M3 V; bool ok; int iter; };  // iter: QR steps counted as Eigen counts them (91 = gave up)
 static inline Eig3 self_adjoint_eig3(const M3& A) {
     Eig3 out;
     // mat = lower triangle of A, scaled into [-1,1]
@@ -283,6 +287,7 @@ static inline Eig3 self_adjoint_eig3(const M3& A) {
         }
     }
     out.ok = iter <= maxIterations * n;
+    out.iter = iter;
     if (out.ok) {
         for (int i = 0; i < n - 1; ++i) {
             int k = 0; float mn = diag[i];

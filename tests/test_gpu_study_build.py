@@ -12,7 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 VARIANT_TESTS = ("four_paths or fast_scoring_equals_exact or fast_scoring_over_magnitudes or bailout_returns_the_reference or in_batch_rule "
-                 "or two_points_per_wave or leaf_major_fuzz or c3_features_at_100k or three_launch_path or fpfh_one_point_per_wave_poisoned")
+                 "or two_points_per_wave or leaf_major_fuzz or c3_features_at_100k or three_launch_path or fpfh_one_point_per_wave_poisoned or probed_")
 
 
 def test_variant_parity_on_the_study_library(tdv):
