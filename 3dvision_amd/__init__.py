@@ -51,7 +51,7 @@ ABI_SYMBOLS = [
     "tdv_depth_preprocess", "tdv_deproject", "tdv_depth_to_cloud", "tdv_voxel_downsample", "tdv_estimate_normals",
     "tdv_compute_fpfh", "tdv_feature_match", "tdv_ransac", "tdv_icp", "tdv_icp_correspondences",
     "tdv_icp_dev", "tdv_ransac_dev", "tdv_feature_match_dev", "tdv_estimate_normals_dev", "tdv_compute_fpfh_dev", "tdv_normals_fpfh_dev", "tdv_radix_sort_pairs_dev",
-    "tdv_depth_to_cloud_dev", "tdv_voxel_downsample_dev", "tdv_sample_triples", "tdv_pose_compose",
+    "tdv_depth_to_cloud_dev", "tdv_voxel_downsample_dev", "tdv_sample_triples", "tdv_sample_triples_batch", "tdv_pose_compose",
     "tdv_register_batch_dev", "tdv_prepare_model_dev", "tdv_bilateral_filter", "tdv_filter_duplicates", "tdv_load_ply_ascii", "tdv_load_mask_png", "tdv_load_masks_from_dir",
     "tdv_depth_to_cloud_batch_dev", "tdv_broadcast_model", "tdv_gather_results", "tdv_mask_resize_nearest", "tdv_mask_resize_nearest_dev", "tdv_voxel_downsample_batch_dev", "tdv_voxel_downsample_batch_pinhole_dev",
     "tdv_icp_batch_dev", "tdv_refine_batch_dev", "tdv_ctx_set_icp_loss", "tdv_ctx_get_icp_loss",
@@ -875,6 +875,25 @@ def sample_triples(n, count, seed=42):
     out = np.empty((count, 3), np.uint64)
     _check(None, lib().tdv_sample_triples(C.c_uint32(seed), C.c_uint64(n), count, _ptr(out)), "tdv_sample_triples")
     return out
+
+
+def sample_triples_batch(n, count, seed=42):
+    """The index stream as RANSAC's batch loop uploads it (tdv_sample_triples_batch): (raw, packed) - raw is uint64[count] when
+    packed, int32[count, 4] (i0, i1, i2, valid) otherwise.  unpack_triples turns either into (triples uint64[count, 3], valid bool[count])."""
+    buf = np.zeros(2 * count, np.uint64)
+    packed = C.c_int(-1)
+    _check(None, lib().tdv_sample_triples_batch(C.c_uint32(seed), C.c_uint64(n), count, _ptr(buf), C.byref(packed)), "tdv_sample_triples_batch")
+    if packed.value:
+        return buf[:count].copy(), True
+    return buf.view(np.int32).reshape(count, 4).copy(), False
+
+
+def unpack_triples(raw, packed):
+    if packed:
+        m = np.uint64(0x1fffff)
+        tri = np.stack([raw & m, (raw >> np.uint64(21)) & m, (raw >> np.uint64(42)) & m], axis=1)
+        return tri, (raw >> np.uint64(63)) != 0
+    return raw[:, :3].astype(np.uint64), raw[:, 3] != 0
 
 
 def filter_duplicates(poses, min_distance=0.1):

@@ -192,6 +192,12 @@ void TripleStream::next_batch(int count, int* out4) {
         out4[4 * k + 3] = !(a == c || c == e || a == e);     // registration.cpp:240
     }
 }
+void TripleStream::next_batch_packed(int count, uint64_t* out) {
+    auto& b = impl_->buf;
+    if (b.size() < 3 * (size_t)count) b.resize(3 * (size_t)count);
+    impl_->g.draw((uint32_t)n_, 3 * (size_t)count, b.data());
+    for (int k = 0; k < count; ++k) out[k] = triple_pack(b[3 * k], b[3 * k + 1], b[3 * k + 2]);
+}
 
 float tau_le(float thr) {  // largest f with sqrtf(f) <= thr ; returns -1 if none (thr < 0 or NaN)
     if (!(thr >= 0.f)) return -1.f;
@@ -378,6 +384,15 @@ int tdv_timing_read(tdv_ctx* ctx, int slot, double* total_ms, int* launches) {
 int tdv_sample_triples(uint32_t seed, uint64_t n, int count, uint64_t* out) {
     if (!out || count < 0 || n == 0 || n > ((uint64_t)1 << 32)) return TDV_ERR_BAD_ARG;
     mt19937_lemire_triples(seed, n, count, out);
+    return TDV_OK;
+}
+
+int tdv_sample_triples_batch(uint32_t seed, uint64_t n, int count, void* out, int* packed) {
+    if (!out || !packed || count < 0 || n == 0 || n > ((uint64_t)1 << 31)) return TDV_ERR_BAD_ARG;
+    TripleStream stream(seed, n);
+    *packed = n <= kTriplePackMaxN;
+    if (*packed) stream.next_batch_packed(count, static_cast<uint64_t*>(out));
+    else stream.next_batch(count, static_cast<int*>(out));
     return TDV_OK;
 }
 

@@ -5,7 +5,9 @@
 // Sub-steps and their kernels:
 //  (i)   feature correspondences (registration.cpp:216-232): csrc/fmatch.hip.
 //  (ii)  index triples (registration.cpp:235-239): host, mt19937 + Lemire (ctx.hip), one batch at
-//        a time in bulk (whole twist blocks, Lemire's test per word); a batch is uploaded as int4 (i0,i1,i2,valid).
+//        a time in bulk (whole twist blocks, Lemire's test per word); a batch is uploaded as one 64-bit word per triple
+//        (three 21-bit indices and the valid bit: triple_pack, tdv_internal.hpp) for clouds of at most 2^21 points,
+//        as int4 (i0,i1,i2,valid) above that; the kernels read either through a TriView.
 //  (iii) k_ransac_hypotheses: one lane per hypothesis — centroids, H = S_c T_c^T, Jacobi SVD,
 //        R = V U^T with reflection fix, t = c_t - R c_s (registration.cpp:242-268).
 //  (iv)  k_ransac_score: one hypothesis per lane (R,t in VGPRs); points (source p and its
@@ -15,8 +17,10 @@
 //        d2 < tau with tau = min{f : sqrtf(f) >= thr} (exactly equivalent, no sqrt in the loop).
 //        Inlier counts are integers: partial counts per point-split are added with integer
 //        atomics, which are order-independent, so counts are bit-exact and reproducible.
-//  (v)   selection (registration.cpp:281-290) on the host over the batch's counts in iteration
-//        order: strict > on float(inliers)/ns, stop at the first fitness > confidence.
+//  (v)   selection (registration.cpp:281-290) on the device, k_ransac_finish at the end of every batch: the first
+//        iteration whose fitness passes the confidence, then the first largest fitness up to it - strict > on
+//        float(inliers)/ns against the running best, which stays on the device with the winner's 12 floats; the host
+//        reads one four-int record per batch.  A traced call downloads every count and runs the loop on the host.
 //  (vi)  k_ransac_rmse: error sum of the winning hypothesis only, fixed-order reduction.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
@@ -150,15 +154,21 @@ __device__ __forceinline__ void ransac_hypothesis_lane(const float* __restrict__
     hyp[(size_t)12 * h_pad + h] = mid;
     hyp[(size_t)13 * h_pad + h] = half;
 }
-__global__ void k_ransac_hypotheses(const float* __restrict__ pq, const int4* __restrict__ triples, int count, int h_pad,
+// RansacPlan's set-up of a batch (see k_ransac_score_fast and k_ransac_select below), done by one thread of k_ransac_hypotheses:
+// stream order puts the previous batch's final state[0] in front of that kernel, and the bound and scoring kernels that read the
+// plan and append to the zeroed counters come after it.  plan == nullptr: a batch without bail-out.
+struct PlanJob { int* state; int* plan; int ns, n_pchunks, ps, drop_permille; int* n_live; };
+__device__ __forceinline__ void ransac_plan(const PlanJob& j);
+__global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, int count, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
-                                    float band_u /* E = band_u (A + s): 16 u for the FMA pass, 24 u for the matrix-core pass */) {
+                                    float band_u /* E = band_u (A + s): 16 u for the FMA pass, 24 u for the matrix-core pass */, const PlanJob plan) {
     int h = blockIdx.x * blockDim.x + threadIdx.x;
+    if (h == 0 && plan.plan) ransac_plan(plan);
     if (h >= h_pad) return;
     counts[h] = 0;                       // the scoring kernel adds its point-splits' counts here (one memset launch less per batch)
     bool valid = false;
     int4 tr = make_int4(0, 0, 0, 0);
-    if (h < count) { tr = triples[h]; valid = tr.w != 0; }
+    if (h < count) { tr = triples.load(h); valid = tr.w != 0; }
     ransac_hypothesis_lane(pq, tr, valid, h, h_pad, hyp, pmax, sqrt_tau, band_u);
 }
 
@@ -430,21 +440,22 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
 // state[0] = best count known so far (a lower bound of the best count of every batch already enqueued: full counts of the
 // batches that are complete, prefix counts of the one whose phase 2 is still to run).  plan = { chunks in phase 1, survivors,
 // largest PREFIX count of this batch, chunks per workgroup } - one plan per batch buffer, the state shared.
-__global__ void k_ransac_plan(int* __restrict__ state, int* __restrict__ plan, int ns, int n_pchunks, int ps, int drop_permille, int* __restrict__ n_live) {
-    const int best = state[0];
-    if (n_live) { n_live[0] = 0; n_live[2] = 0; }            // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided)
+// (One thread of k_ransac_hypotheses makes the plan: a launch of its own - one thread behind a stream barrier - cost as much as k_ransac_best.)
+__device__ __forceinline__ void ransac_plan(const PlanJob& j) {
+    const int best = j.state[0], ns = j.ns, n_pchunks = j.n_pchunks;
+    if (j.n_live) { j.n_live[0] = 0; j.n_live[2] = 0; }      // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided)
     int c_split = n_pchunks;
-    const int rest = best - max((int)((long long)best * drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
+    const int rest = best - max((int)((long long)best * j.drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
     if (rest >= ns / 8)                                      // (below an eighth of the points a second phase costs more than it saves)
         c_split = min(n_pchunks, (ns - rest + RS_PCH - 1) / RS_PCH);
-    plan[0] = c_split; plan[1] = 0; plan[2] = 0; plan[3] = (c_split + ps - 1) / ps;
+    j.plan[0] = c_split; j.plan[1] = 0; j.plan[2] = 0; j.plan[3] = (c_split + j.ps - 1) / j.ps;
 }
 // largest count of a batch (prefix counts after phase 1, full counts after phase 2) -> *dst by atomic max, one atomic per
 // workgroup (one per wave on the same address cost 12 us for a 65,536-hypothesis batch)
 __global__ __launch_bounds__(1024)
-void k_ransac_best(const int4* __restrict__ triples, int count, const int* __restrict__ counts, int* __restrict__ dst) {
+void k_ransac_best(const TriView triples, int count, const int* __restrict__ counts, int* __restrict__ dst) {
     const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    int c = (h < count && triples[h].w != 0) ? counts[h] : 0;
+    int c = (h < count && triples.valid(h)) ? counts[h] : 0;
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) c = max(c, __shfl_xor(c, off, 64));
     __shared__ int s_max[16];
@@ -471,12 +482,12 @@ void k_ransac_best(const int4* __restrict__ triples, int count, const int* __res
 // Either way the counts of the dropped hypotheses stay partial and compare as the true ones would: below the result's.
 // With RansacLeafBound, bnd[h] is a second upper bound of the full count (k_ransac_bound; INT_MAX where it has none): a dead
 // hypothesis, never scored, has bnd <= best and is dropped by rule (a) - it never enters phase 2.
-__global__ void k_ransac_select(const int4* __restrict__ triples, int count, const int* __restrict__ counts, int ns, float confidence,
+__global__ void k_ransac_select(const TriView triples, int count, const int* __restrict__ counts, int ns, float confidence,
                                 const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list, const int* __restrict__ bnd) {
     const int h = blockIdx.x * blockDim.x + threadIdx.x;
     const int c_split = plan[0], best = state[0], in_batch = plan[2];
     const int rest = max(0, ns - min(ns, c_split * RS_PCH));     // (the padding past ns is never an inlier)
-    bool keep = h < count && triples[h].w != 0 && rest > 0;
+    bool keep = h < count && triples.valid(h) && rest > 0;
     if (keep) {
         const int ub = bnd ? min(counts[h] + rest, bnd[h]) : counts[h] + rest;
         const bool passes = static_cast<float>(ub) / static_cast<float>((size_t)ns) > confidence;   // registration.cpp:281,290 on the bound
@@ -489,6 +500,120 @@ __global__ void k_ransac_select(const int4* __restrict__ triples, int count, con
     if (lane == 0) at = atomicAdd(&plan[1], __popcll(m));
     at = __shfl(at, 0, 64);
     if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
+}
+// The two kernels above for a BOUNDED batch, in one launch over its live list (`live`, *n_live entries, in no order).  A dead
+// hypothesis was never scored: its count is 0, which leaves the prefix maximum alone, and its bnd <= best drops it by rule (a).
+// So the largest prefix count of the live ones is the batch's (plan[2]), and the list is built from them under the same rules
+// with ub = count + rest (a live hypothesis' bnd is INT_MAX).  Phase 2's list holds the same hypotheses as k_ransac_select's,
+// in another order: counts are integer atomics, the order does not matter.  One workgroup: the live list is an eighth of a batch.
+__global__ __launch_bounds__(1024)
+void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ n_live, const int* __restrict__ counts, int ns, float confidence,
+                          const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list) {
+    const int n = *n_live, c_split = plan[0], best = state[0];
+    const int rest = max(0, ns - min(ns, c_split * RS_PCH));     // (the padding past ns is never an inlier)
+    __shared__ int s_max, s_n;
+    if (threadIdx.x == 0) { s_max = 0; s_n = 0; }
+    __syncthreads();
+    int c = 0;
+    for (int i = threadIdx.x; i < n; i += 1024) c = max(c, counts[live[i]]);
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) c = max(c, __shfl_xor(c, off, 64));
+    if ((threadIdx.x & 63) == 0 && c > 0) atomicMax(&s_max, c);
+    __syncthreads();
+    const int in_batch = s_max, lane = threadIdx.x & 63;
+    for (int i0 = 0; i0 < n; i0 += 1024) {                       // (workgroup-uniform trip count: every lane reaches the ballot)
+        const int i = i0 + threadIdx.x;
+        bool keep = i < n && rest > 0;
+        int h = 0;
+        if (keep) {
+            h = live[i];
+            const int ub = counts[h] + rest;
+            const bool passes = static_cast<float>(ub) / static_cast<float>((size_t)ns) > confidence;   // registration.cpp:281,290 on the bound
+            keep = ub > best && (ub >= in_batch || passes);
+        }
+        const unsigned long long m = __ballot(keep);
+        if (!m) continue;
+        int at = 0;
+        if (lane == 0) at = atomicAdd(&s_n, __popcll(m));
+        at = __shfl(at, 0, 64);
+        if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) { plan[1] = s_n; plan[2] = in_batch; }
+}
+
+// RansacFinish - the end of a batch: the loop of registration.cpp:281-290 over the batch's counts in iteration order, on the device,
+// as k_rb_select's two reductions: the first iteration whose fitness passes the confidence ends the loop (:290), and the first
+// largest fitness up to it is the batch's candidate, a new best if it beats - strictly, in the float expression of :281 itself -
+// the best of the earlier batches.  sel = { best fitness (bits), its count, its iteration, stopped } carries the loop's state from
+// batch to batch on the device; once `stopped` is set the batches still in flight change nothing (the host discards them too).
+// The winning hypothesis' 12 floats go to best12, and the host gets ONE record per batch - { best local index or -1, its count,
+// local stop index or -1, bad correspondence flag } - where it used to download every count and walk them.  The same launch
+// raises state[0] to the batch's largest full count, as k_ransac_best did (state == nullptr: a batch without bail-out).
+// live != nullptr (a bounded batch, confidence >= 0): only the live list is read.  A dead hypothesis has count 0: no new best
+// (strict > on a best fitness >= 0), no exit (0 > confidence is false), nothing to raise.
+// One workgroup; the first batch and the live lists are a few thousand entries (a whole batch is walked only with the bound off).
+__global__ __launch_bounds__(1024)
+void k_ransac_finish(const TriView triples, int count, const int* __restrict__ counts, const int* __restrict__ live, const int* __restrict__ n_live,
+                     const float* __restrict__ hyp, int h_pad, int ns, float confidence, int it0,
+                     int* __restrict__ state, int* __restrict__ sel, float* __restrict__ best12, const int* __restrict__ bad, int* __restrict__ rec) {
+    const int n = live ? *n_live : count;
+    const float fn = static_cast<float>((size_t)ns);
+    __shared__ int s_stop, s_max;
+    __shared__ unsigned long long s_best[16];
+    if (threadIdx.x == 0) { s_stop = INT_MAX; s_max = 0; }
+    __syncthreads();
+    int stop = INT_MAX, cmax = 0;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int h = live ? live[i] : i;
+        if (!live && !triples.valid(h)) continue;                // a skipped iteration (registration.cpp:240)
+        const int c = counts[h];
+        cmax = max(cmax, c);
+        if (static_cast<float>(c) / fn > confidence) stop = min(stop, h);
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { stop = min(stop, __shfl_xor(stop, off, 64)); cmax = max(cmax, __shfl_xor(cmax, off, 64)); }
+    if ((threadIdx.x & 63) == 0) {
+        if (stop != INT_MAX) atomicMin(&s_stop, stop);
+        if (cmax > 0) atomicMax(&s_max, cmax);
+    }
+    __syncthreads();
+    const int k_stop = s_stop;
+    // the first largest fitness among the iterations up to k_stop: key = fitness bits (positive floats order as their bits), then
+    // the EARLIEST iteration (largest INT_MAX - h)
+    unsigned long long best = 0ull;
+#pragma unroll 4
+    for (int i = threadIdx.x; i < n; i += 1024) {
+        const int h = live ? live[i] : i;
+        if (h > k_stop || (!live && !triples.valid(h))) continue;
+        const float fit = static_cast<float>(counts[h]) / fn;    // registration.cpp:281
+        if (!(fit > 0.f)) continue;
+        const unsigned long long key = ((unsigned long long)__float_as_uint(fit) << 32) | (unsigned)(INT_MAX - h);
+        best = key > best ? key : best;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = shfl_u64_down(best, o); best = x > best ? x : best; }
+    if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    for (int w = 1; w < 16; ++w) best = s_best[w] > best ? s_best[w] : best;
+    if (state && s_max > 0) atomicMax(state, s_max);
+    int best_local = -1, best_count = 0, stop_local = -1;
+    if (!sel[3]) {
+        if (best != 0ull) {
+            const int h = INT_MAX - (int)(unsigned)(best & 0xffffffffull);
+            const float fit = __uint_as_float((unsigned)(best >> 32));
+            if (fit > __int_as_float(sel[0])) {                  // registration.cpp:284
+                best_local = h; best_count = counts[h];
+                sel[0] = __float_as_int(fit); sel[1] = best_count; sel[2] = it0 + h;
+                for (int e = 0; e < 12; ++e) best12[e] = hyp[(size_t)e * h_pad + h];
+            }
+        }
+        if (k_stop != INT_MAX) { stop_local = k_stop; sel[3] = 1; }
+    }
+    rec[0] = best_local; rec[1] = best_count; rec[2] = stop_local; rec[3] = *bad;
+    __threadfence_system();                                      // (the record may live in pinned host memory)
 }
 
 // ------------------------------------------------------------------ RansacLeafBound
@@ -724,7 +849,7 @@ __device__ __forceinline__ RbHyp rb_load(const float* __restrict__ hyp, int h_pa
 // the hypotheses it leaves undecided and the ticket of its slot block.
 template <int MODE>
 __global__ __launch_bounds__(64 * RB_SPLIT)
-void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __restrict__ triples, int count, const float* __restrict__ leaves, int n_lpairs,
+void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView triples, int count, const float* __restrict__ leaves, int n_lpairs,
                     const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
                     int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
                     int* __restrict__ acc, int* __restrict__ ticket) {
@@ -733,7 +858,7 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const int4* __rest
     __shared__ int s_ub[64];
     if (wave == 0) s_ub[lane] = 0;
     if (MODE == RB_COARSE && threadIdx.x == 0) ticket[blockIdx.x] = 0;
-    const bool valid = h < count && triples[h].w != 0;
+    const bool valid = h < count && triples.valid(h);
     const RbHyp o = rb_load(hyp, h_pad, h, valid, pmax, sqrt_tau, band_u, MODE == RB_COARSE ? 5.f : 3.f);   // (coarse margin 5 E: see above)
     const int best = state[0];
     // Gate: with the best under a 32nd of the points nothing is pruned (true share 0.02: best 0.017 N), and the walk - whose RB_SPLIT
@@ -1057,12 +1182,13 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 8, &pq));
     // one device block: [0] bad index flag, [1] largest |source coordinate|, [2..3] rescored chunks, [4..5] scored chunks (u64 each),
     // [8] the best count known so far, [10..13] and [12+..] the two batch buffers' bail-out plans (4 ints each at [10] and [14]), [16..27] the winning
-    // hypothesis, [32..35] its error sum and inlier count (2 doubles): one memset at the start, one copy back at the end
+    // hypothesis, [32..35] its error sum and inlier count (2 doubles): one memset at the start, one copy back at the end;
+    // [40..43] RansacFinish's loop state (best fitness, its count, its iteration, stopped), [48..55] and [56..63] the two batch buffers' records
     int* d_bad = nullptr;
-    TDV_TRY(ws_alloc(ctx, 40, &d_bad));
+    TDV_TRY(ws_alloc(ctx, 64, &d_bad));
     unsigned* d_pmax = reinterpret_cast<unsigned*>(d_bad + 1);
     unsigned long long* d_rescored = reinterpret_cast<unsigned long long*>(d_bad + 2);
-    TDV_HIP(ctx, hipMemsetAsync(d_bad, 0, 160, s));
+    TDV_HIP(ctx, hipMemsetAsync(d_bad, 0, 256, s));
     double wave_chunks = 0.0;    // wave x chunk pairs scored by the fast pass in this call
     k_gather_pq<<<(ns_pad + 255) / 256, 256, 0, s>>>(d_src, d_tgt, d_corr, ns, ns_pad, nt, pq, d_bad, d_pmax);
     // sqrt(tau) rounded up: the boundary of `d2 < tau` in distance, for the band of the fast scoring pass
@@ -1077,6 +1203,13 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     const bool bailout = score_fast && !score_mfma && !trace_inliers && !bailout_env_off && max_iterations > 16384;
     int* d_state = d_bad + 8;                       // [0] best count known so far
     int* d_plan[2] = {d_bad + 10, d_bad + 28};   // per batch buffer: phase-1 chunks, survivors, largest prefix count, chunks per workgroup
+    int* d_sel = d_bad + 40;
+    int* d_rec[2] = {d_bad + 48, d_bad + 56};
+    // RansacFinish: the batch's winner is chosen on the device; a traced call needs every count on the host and keeps the host loop
+    const bool device_select = !trace_inliers;
+    // the record reaches the host by the kernel's own stores into pinned memory; TDV_RANSAC_RECORD=copy (study build): by a 32-byte copy
+    const bool record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");
+    const int packed = (uint64_t)ns <= kTriplePackMaxN;      // triples as one 64-bit word each (tdv_internal.hpp: triple_pack)
     const int drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 100;   // tuning knob (5 to 100 measured equal)
     const bool merge_on = study_env("TDV_RANSAC_MERGE") && atoi(study_env("TDV_RANSAC_MERGE")) == 1;     // (study build; read per call: the tests switch it)
     // RansacLeafBound: the leaf summary once per call, the bound in front of phase 1 of every batch after the first (whose best is 0)
@@ -1130,7 +1263,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
 
     // two sets of batch buffers: batch k+1 is prepared on the host (index stream, triple packing) and enqueued while
     // the GPU scores batch k; results are consumed in iteration order, so the outcome is that of the sequential loop
-    float* hyp[2] = {nullptr, nullptr}; int* counts[2] = {nullptr, nullptr}; int4* d_tri[2] = {nullptr, nullptr};
+    float* hyp[2] = {nullptr, nullptr}; int* counts[2] = {nullptr, nullptr}; void* d_tri[2] = {nullptr, nullptr};
     double* slabs = nullptr; double* d_out2 = nullptr; float* d_best12 = nullptr;
     int* d_list[2] = {nullptr, nullptr};
     int* d_live[2] = {nullptr, nullptr}; int* d_bnd[2] = {nullptr, nullptr}; int* d_und[2] = {nullptr, nullptr}; int* d_nlive = nullptr;
@@ -1138,7 +1271,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     for (int q = 0; q < 2; ++q) {
         TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &hyp[q]));
         TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &counts[q]));
-        TDV_TRY(ws_alloc(ctx, (size_t)batch, &d_tri[q]));
+        TDV_TRY(ws_alloc_bytes(ctx, (size_t)batch * (packed ? 8 : 16), &d_tri[q]));
     }
     if (bailout) for (int q = 0; q < 2; ++q) TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_list[q]));   // a batch's list lives until its phase 2 has run, behind the next batch's phase 1
     if (bound) {
@@ -1152,15 +1285,16 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
     d_best12 = reinterpret_cast<float*>(d_bad + 16);
     d_out2 = reinterpret_cast<double*>(d_bad + 32);
-    // pinned: 2 x triples (int4 * batch) | 2 x counts (int * batch) | best12 (12 floats) | out2 (2 doubles)
-    const size_t sz_tri = align_up((size_t)batch * 16, 64), sz_cnt = align_up((size_t)batch * 4, 64);
-    const size_t pin_b12 = 2 * sz_tri + 2 * sz_cnt, pin_bad = pin_b12 + 192, pin_total = pin_bad + 64;   // pin_b12: the 160-byte result block
+    // pinned: 2 x triples (a word or an int4 * batch) | 2 x counts (int * batch, traced calls only) | best12 (12 floats) | out2 (2 doubles) | bad | 2 x record
+    const size_t sz_tri = align_up((size_t)batch * (packed ? 8 : 16), 64), sz_cnt = device_select ? 0 : align_up((size_t)batch * 4, 64);
+    const size_t pin_b12 = 2 * sz_tri + 2 * sz_cnt, pin_bad = pin_b12 + 192, pin_rec = pin_bad + 64, pin_total = pin_rec + 64;   // pin_b12: the 160-byte result block
     TDV_TRY(pin_reserve(ctx, pin_total));
     int* h_bad = reinterpret_cast<int*>(ctx->pin + pin_bad);
     *h_bad = 0;
-    TDV_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts
-    int4* h_tri[2] = {reinterpret_cast<int4*>(ctx->pin), reinterpret_cast<int4*>(ctx->pin + sz_tri)};
+    if (!device_select) TDV_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts (RansacFinish: the flag comes in the record)
+    void* h_tri[2] = {ctx->pin, ctx->pin + sz_tri};
     int* h_cnt[2] = {reinterpret_cast<int*>(ctx->pin + 2 * sz_tri), reinterpret_cast<int*>(ctx->pin + 2 * sz_tri + sz_cnt)};
+    volatile int* h_rec[2] = {reinterpret_cast<int*>(ctx->pin + pin_rec), reinterpret_cast<int*>(ctx->pin + pin_rec + 32)};
     const int* h_block = reinterpret_cast<const int*>(ctx->pin + pin_b12);      // host copy of d_bad[0..40): same layout
     const float* h_b12 = reinterpret_cast<const float*>(h_block + 16);
     const double* h_o2 = reinterpret_cast<const double*>(h_block + 32);
@@ -1172,7 +1306,8 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     const int first_batch = bailout ? 8 * RS_HYP_PER_BLOCK : batch;
     auto prepare = [&](int q, int it0) -> int {    // host: draw + pack the triples of one batch
         const int cnt = std::min(it0 == 0 ? first_batch : batch, max_iterations - it0);
-        stream_idx.next_batch(cnt, reinterpret_cast<int*>(h_tri[q]));     // (i0, i1, i2, valid: registration.cpp:240)
+        if (packed) stream_idx.next_batch_packed(cnt, static_cast<uint64_t*>(h_tri[q]));
+        else stream_idx.next_batch(cnt, static_cast<int*>(h_tri[q]));     // (i0, i1, i2, valid: registration.cpp:240)
         return cnt;
     };
     // point ranges of a scoring dispatch with hb hypothesis blocks (counts are accumulated by atomics, so the cut may differ per dispatch)
@@ -1182,8 +1317,24 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
         const int per = (n_pchunks + ps - 1) / ps;
         return (n_pchunks + per - 1) / per;
     };
-    int pending = -1, pending_cnt = 0;   // bail-out: the batch buffer whose phase 2 has not been enqueued yet
-    // phase 2 of the pending batch (alone, or riding behind job A of the batch in `a`), then its final counts: best, copy, event
+    int pending = -1, pending_cnt = 0, pending_it0 = 0;   // bail-out: the batch buffer whose phase 2 has not been enqueued yet
+    bool pending_bounded = false;
+    // the end of batch buffer q (cnt hypotheses from iteration it0 on): RansacFinish and its record, or - traced - every count to the host; then the event
+    auto finish = [&](int q, int cnt, int it0, bool use_state, bool bounded) -> int {
+        if (device_select) {
+            const bool live_only = bounded && confidence >= 0.f;      // (see k_ransac_finish)
+            int* rec = record_copy ? d_rec[q] : const_cast<int*>(h_rec[q]);
+            k_ransac_finish<<<1, 1024, 0, s>>>(TriView{d_tri[q], packed}, cnt, counts[q], live_only ? d_live[q] : nullptr, live_only ? d_nlive + q : nullptr,
+                                               hyp[q], h_pad, ns, confidence, it0, use_state ? d_state : nullptr, d_sel, d_best12, d_bad, rec);
+            TDV_CHECK_LAUNCH(ctx);
+            if (record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(h_rec[q]), d_rec[q], 32, hipMemcpyDeviceToHost, s));
+        } else {             // (a traced call runs without bail-out: no state to raise)
+            TDV_HIP(ctx, hipMemcpyAsync(h_cnt[q], counts[q], (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
+        }
+        TDV_HIP(ctx, hipEventRecord(ev[q], s));
+        return TDV_OK;
+    };
+    // phase 2 of the pending batch (alone, or riding behind job A of the batch in `a`), then its end (finish)
     auto finish_pending = [&](const ScoreJob* a, int g1) -> int {
         const int p = pending;
         const int hbp = (int)(align_up((size_t)pending_cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK);
@@ -1197,18 +1348,22 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
             if (a) k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(*a, jb, g1, h_pad, pq2, n_pchunks, tau, d_rescored);
             else k_ransac_score_fast<<<g2, RS_BLOCK, 0, s>>>(jb, jb, 0, h_pad, pq2, n_pchunks, tau, d_rescored);
         }
-        k_ransac_best<<<(pending_cnt + 1023) / 1024, 1024, 0, s>>>(d_tri[p], pending_cnt, counts[p], d_state);
         TDV_CHECK_LAUNCH(ctx);
-        TDV_HIP(ctx, hipMemcpyAsync(h_cnt[p], counts[p], (size_t)pending_cnt * 4, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipEventRecord(ev[p], s));
         pending = -1;
-        return TDV_OK;
+        return finish(p, pending_cnt, pending_it0, true, pending_bounded);
     };
-    auto enqueue = [&](int q, int cnt, bool first) -> int {     // device: hypotheses + scoring + counts back to the host
-        TDV_HIP(ctx, hipMemcpyAsync(d_tri[q], h_tri[q], (size_t)cnt * 16, hipMemcpyHostToDevice, s));
+    auto enqueue = [&](int q, int cnt, int it0) -> int {     // device: hypotheses + scoring + the batch's end (finish)
+        const bool first = it0 == 0;
+        TDV_HIP(ctx, hipMemcpyAsync(d_tri[q], h_tri[q], (size_t)cnt * (packed ? 8 : 16), hipMemcpyHostToDevice, s));
         const float band_u = (score_mfma ? 24.f : 16.f) * 5.9604644775390625e-08f;
-        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, d_tri[q], cnt, h_pad, hyp[q], d_pmax, sqrt_tau, counts[q], band_u);
+        const TriView tri{d_tri[q], packed};
         const int hb = (int)(align_up((size_t)cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK);
+        const bool bounded = bailout && bound && !first;
+        // the batch's plan is made from the best count known now: full counts of the batches whose phase 2 has run, the prefix
+        // counts of the pending one (a lower bound of its full counts - a bound is all the rule needs)
+        const int ps_plan = ranges_for(hb);
+        const PlanJob plan{d_state, bailout ? d_plan[q] : nullptr, ns, n_pchunks, ps_plan, drop_permille, bounded ? d_nlive + q : nullptr};
+        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri, cnt, h_pad, hyp[q], d_pmax, sqrt_tau, counts[q], band_u, plan);
         {   // TDV_TIMER_RANSAC_SCORE brackets every dispatch of a scoring kernel on its own
 #ifdef TDV_STUDY
             if (score_mfma) {
@@ -1223,13 +1378,9 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
             else
 #endif
             if (score_fast) {
-                const int ps = ranges_for(hb);
+                const int ps = ps_plan;
                 if (bailout) {
-                    // One dispatch per batch: its phase 1 (job A) and, behind it, phase 2 of the batch before (job B).  The plan
-                    // of this batch is made from the best count known now: full counts of the batches whose phase 2 has run,
-                    // the prefix counts of the pending one (a lower bound of its full counts - a bound is all the rule needs).
-                    const bool bounded = bound && !first;
-                    k_ransac_plan<<<1, 1, 0, s>>>(d_state, d_plan[q], ns, n_pchunks, ps, drop_permille, bounded ? d_nlive + q : nullptr);
+                    // One dispatch per batch: its phase 1 (job A) and, behind it, phase 2 of the batch before (job B).
                     ScoreJob ja{hyp[q], counts[q], d_plan[q], nullptr, hb, ps, nullptr};
                     const int g1 = score_grid(hb, ps);        // (a multiple of 8: job B's XCD numbering starts there)
                     if (bounded) {
@@ -1237,10 +1388,10 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
                         // items; a grid of job A's size covers them in about one pass whatever the number of live blocks)
                         const int bgrid = (cnt + 63) / 64;
                         if (one_level)
-                            k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, d_tri[q], cnt, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
+                            k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, tri, cnt, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
                                                                                    d_state, ns, d_bnd[q], d_live[q], d_nlive + q, nullptr, nullptr, nullptr, nullptr);
                         else {
-                            k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, d_tri[q], cnt, cleaves, n_cpairs, d_pmax, sqrt_tau, band_u,
+                            k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, tri, cnt, cleaves, n_cpairs, d_pmax, sqrt_tau, band_u,
                                                                                       d_state, ns, d_bnd[q], d_live[q], d_nlive + q, d_und[q], d_nlive + 2 + q,
                                                                                       d_acc[q], d_ticket[q]);
                             k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
@@ -1257,13 +1408,16 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
                     }
                     // survivors of this batch: the in-batch bound first (largest prefix count), then the list; the prefix counts
                     // also raise the best known for the batches after this one
-                    k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(d_tri[q], cnt, counts[q], d_plan[q] + 2);
-                    k_ransac_select<<<(cnt + 255) / 256, 256, 0, s>>>(d_tri[q], cnt, counts[q], ns, confidence, d_state, d_plan[q], d_list[q],
-                                                                   bounded ? d_bnd[q] : nullptr);
+                    // (a bounded batch: both in one launch over its live list)
+                    if (bounded) k_ransac_select_live<<<1, 1024, 0, s>>>(d_live[q], d_nlive + q, counts[q], ns, confidence, d_state, d_plan[q], d_list[q]);
+                    else {
+                        k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(tri, cnt, counts[q], d_plan[q] + 2);
+                        k_ransac_select<<<(cnt + 255) / 256, 256, 0, s>>>(tri, cnt, counts[q], ns, confidence, d_state, d_plan[q], d_list[q], nullptr);
+                    }
                     // (merged mode only: phase 2 comes a dispatch later, the prefix counts raise the bound for the batch in between;
                     //  otherwise the full counts do that right after phase 2)
-                    if (merge_on) k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(d_tri[q], cnt, counts[q], d_state);
-                    pending = q; pending_cnt = cnt;
+                    if (merge_on) k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(tri, cnt, counts[q], d_state);
+                    pending = q; pending_cnt = cnt; pending_it0 = it0; pending_bounded = bounded;
                     wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
                     TDV_CHECK_LAUNCH(ctx);
                     // Phase 2 runs as a dispatch of its own right away.  Letting it ride behind the NEXT batch's phase 1 (TDV_RANSAC_MERGE=1:
@@ -1288,9 +1442,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
             }
         }
         TDV_CHECK_LAUNCH(ctx);
-        TDV_HIP(ctx, hipMemcpyAsync(h_cnt[q], counts[q], (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipEventRecord(ev[q], s));
-        return TDV_OK;
+        return finish(q, cnt, it0, false, false);
     };
 
     float best_fitness = 0.f; int best_iter = -1, best_inliers = 0; bool stop = false;
@@ -1298,30 +1450,41 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     int status = TDV_OK;
     int cur = 0, it0 = 0;
     int cnt_cur = prepare(cur, it0);
-    status = enqueue(cur, cnt_cur, true);
+    status = enqueue(cur, cnt_cur, 0);
     while (status == TDV_OK && cnt_cur > 0 && !stop) {
         const int nxt = cur ^ 1;
         const int it_next = it0 + cnt_cur;
         int cnt_next = 0;
         if (it_next < max_iterations) {             // overlap: prepare and enqueue the next batch behind the current one
             cnt_next = prepare(nxt, it_next);
-            status = enqueue(nxt, cnt_next, false);           // (with the bail-out this also runs phase 2 of `cur` and sends its counts)
+            status = enqueue(nxt, cnt_next, it_next);         // (with the bail-out this also runs phase 2 of `cur` and sends its counts)
             if (status != TDV_OK) break;
         } else if (pending == cur) {                  // last batch: its phase 2 runs alone
             status = finish_pending(nullptr, 0);
             if (status != TDV_OK) break;
         }
         if (hipEventSynchronize(ev[cur]) != hipSuccess) { status = TDV_ERR_LAUNCH; break; }
-        if (*h_bad) { std::snprintf(ctx->err, sizeof(ctx->err), "ransac: a correspondence index lies outside [0, %d)", nt); status = TDV_ERR_BAD_ARG; break; }
+        if (device_select ? h_rec[cur][3] : *h_bad) { std::snprintf(ctx->err, sizeof(ctx->err), "ransac: a correspondence index lies outside [0, %d)", nt); status = TDV_ERR_BAD_ARG; break; }
         int batch_best = -1;
-        for (int k = 0; k < cnt_cur; ++k) {
-            done_iters = it0 + k + 1;
-            if (!h_tri[cur][k].w) { if (trace_inliers) trace_inliers[it0 + k] = -1; continue; }
-            int inl = h_cnt[cur][k];
-            if (trace_inliers) trace_inliers[it0 + k] = inl;
-            float fitness = static_cast<float>(inl) / static_cast<float>((size_t)ns);  // registration.cpp:281
-            if (fitness > best_fitness) { best_fitness = fitness; best_iter = it0 + k; best_inliers = inl; batch_best = k; }
-            if (fitness > confidence) { stop = true; break; }
+        if (device_select) {     // RansacFinish ran the loop below on the device: its record
+            const int k_best = h_rec[cur][0], k_stop = h_rec[cur][2];
+            if (k_best >= 0) {
+                best_inliers = h_rec[cur][1]; best_iter = it0 + k_best;
+                best_fitness = static_cast<float>(best_inliers) / static_cast<float>((size_t)ns);  // registration.cpp:281
+            }
+            stop = k_stop >= 0;
+            done_iters = it0 + (stop ? k_stop + 1 : cnt_cur);
+        } else {
+            const TriView tri{h_tri[cur], packed};
+            for (int k = 0; k < cnt_cur; ++k) {
+                done_iters = it0 + k + 1;
+                if (!tri.valid(k)) { if (trace_inliers) trace_inliers[it0 + k] = -1; continue; }
+                int inl = h_cnt[cur][k];
+                if (trace_inliers) trace_inliers[it0 + k] = inl;
+                float fitness = static_cast<float>(inl) / static_cast<float>((size_t)ns);  // registration.cpp:281
+                if (fitness > best_fitness) { best_fitness = fitness; best_iter = it0 + k; best_inliers = inl; batch_best = k; }
+                if (fitness > confidence) { stop = true; break; }
+            }
         }
         if (batch_best >= 0) {  // keep the winning (R,t) of this batch (hyp[cur] is not overwritten before batch cur+2 is enqueued)
             hipError_t e = hipMemcpy2DAsync(d_best12, 4, hyp[cur] + batch_best, (size_t)h_pad * 4, 4, 12, hipMemcpyDeviceToDevice, s);

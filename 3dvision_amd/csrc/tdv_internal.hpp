@@ -313,6 +313,26 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
                        const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
                        const float* d_model_fpfh, int n_model, tdv_instance_result* results);
 
+// A RANSAC index triple in one 64-bit word, for clouds of at most 2^21 points: i0 in bits 0..20, i1 in 21..41, i2 in 42..62, bit 63 =
+// valid (the three indices differ, registration.cpp:240).  A batch is uploaded in this form where the cloud allows it, as int4
+// (i0, i1, i2, valid) above that; TriView gives the kernels either.
+constexpr uint64_t kTriplePackMaxN = (uint64_t)1 << 21;
+__host__ __device__ __forceinline__ uint64_t triple_pack(uint32_t a, uint32_t b, uint32_t c) {
+    const uint64_t valid = !(a == b || b == c || a == c);
+    return (uint64_t)a | ((uint64_t)b << 21) | ((uint64_t)c << 42) | (valid << 63);
+}
+struct TriView {
+    const void* p; int packed;
+    __host__ __device__ __forceinline__ bool valid(int h) const {
+        return packed ? (static_cast<const uint64_t*>(p)[h] >> 63) != 0 : static_cast<const int4*>(p)[h].w != 0;
+    }
+    __host__ __device__ __forceinline__ int4 load(int h) const {
+        if (!packed) return static_cast<const int4*>(p)[h];
+        const uint64_t w = static_cast<const uint64_t*>(p)[h];
+        return make_int4((int)(w & 0x1fffffu), (int)((w >> 21) & 0x1fffffu), (int)((w >> 42) & 0x1fffffu), (int)(w >> 63));
+    }
+};
+
 // host helpers
 void mt19937_lemire_triples(uint32_t seed, uint64_t n, int count, uint64_t* out);
 void mt19937_raw(uint32_t seed, size_t count, uint32_t* out);
@@ -326,6 +346,8 @@ public:
     // `count` triples at once, as int4 (i0, i1, i2, valid) with valid = the three indices differ (registration.cpp:240);
     // indices are below n <= 2^31 here (the batch loop's clouds)
     void next_batch(int count, int* out4);
+    // the same triples as one 64-bit word each (triple_pack below): for n <= kTriplePackMaxN, half the bytes of a batch's upload
+    void next_batch_packed(int count, uint64_t* out);
 private:
     struct Impl; Impl* impl_; uint64_t n_;
     TripleStream(const TripleStream&) = delete;

@@ -728,6 +728,11 @@ int tdv_gather_results(tdv_ctx* ctx, void* rccl_comm, const tdv_instance_result*
 /* The RANSAC index stream: count triples from mt19937(seed) + Lemire uniform over [0, n-1]
  * (src/registration.cpp:235-239 on libstdc++ 11).  Own implementation, no <random>. */
 int tdv_sample_triples(uint32_t seed, uint64_t n, int count, uint64_t* out_triples);
+/* The same stream in the form tdv_ransac uploads a batch of it (host only; n <= 2^31).  n <= 2^21: *packed = 1 and out
+ * receives one 64-bit word per triple - i0 in bits 0..20, i1 in 21..41, i2 in 42..62, bit 63 = the three indices differ
+ * (src/registration.cpp:240).  Above: *packed = 0 and out receives four ints per triple (i0, i1, i2, valid).
+ * out holds 16 * count bytes either way. */
+int tdv_sample_triples_batch(uint32_t seed, uint64_t n, int count, void* out, int* packed);
 /* Pose composition of src/pipeline.cpp:136-137: out = extrinsics * inverse(T). */
 int tdv_pose_compose(const float* extrinsics, const float* T, float* out);
 /* Pipeline::filterDuplicates (src/pipeline.cpp:153-180): greedy pass over n column-major 4x4 poses; a pose
