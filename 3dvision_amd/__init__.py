@@ -59,6 +59,7 @@ ABI_SYMBOLS = [
     "tdv_color_gradients", "tdv_color_gradients_dev", "tdv_colored_icp", "tdv_colored_icp_dev", "tdv_colored_icp_batch_dev",
     "tdv_fgr_default_params", "tdv_fgr", "tdv_fgr_dev", "tdv_fgr_correspondences",
     "tdv_plane_default_params", "tdv_segment_planes", "tdv_segment_planes_dev",
+    "tdv_cluster_default_params", "tdv_cluster_dbscan", "tdv_cluster_dbscan_dev",
 ]
 
 
@@ -145,6 +146,30 @@ def _plane_results(res, n):
                  iterations_run=r.iterations_run) for r in res[:n]]
 
 
+class ClusterParamsC(C.Structure):
+    _fields_ = [("eps", C.c_float), ("min_points", C.c_int), ("min_cluster_size", C.c_int)]
+
+
+class ClusterResultC(C.Structure):
+    _fields_ = [("n_clusters", C.c_int), ("n_core", C.c_int), ("n_border", C.c_int), ("n_noise", C.c_int), ("n_dropped", C.c_int),
+                ("largest", C.c_int)]
+
+
+def cluster_params(**kw):
+    """tdv_cluster_default_params (min_cluster_size = 1; eps and min_points have no default) with the given fields replaced."""
+    p = ClusterParamsC()
+    lib().tdv_cluster_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(ClusterParamsC._fields_):
+            raise TypeError("unknown cluster parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _cluster_result(r):
+    return {k: getattr(r, k) for k, _ in ClusterResultC._fields_}
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -184,6 +209,7 @@ def lib():
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
             l.tdv_fgr_default_params.restype = None
             l.tdv_plane_default_params.restype = None
+            l.tdv_cluster_default_params.restype = None
             _lib = l
     return _lib
 
@@ -693,6 +719,35 @@ class Context:
         if not planes:
             return np.zeros(4, np.float32), np.zeros(0, np.int64)
         return planes[0]["plane"], np.nonzero(labels == 0)[0]
+
+    # ---------------------------------------------------------------- clustering (include/tdv_hip.h: tdv_cluster_dbscan)
+    def cluster(self, xyz, eps, min_points, min_cluster_size=1, grouped=False):
+        """tdv_cluster_dbscan: (result dict - n_clusters, n_core, n_border, n_noise, n_dropped, largest, n_labelled -, labels int32[n],
+        order int32[n]: the labelled points by (label, index), then the noise, offsets int32[n_clusters + 1] into order).
+        grouped=True appends the cloud's rows in that order."""
+        xyz = _f32(xyz).reshape(-1, 3); n = len(xyz)
+        p = cluster_params(eps=eps, min_points=min_points, min_cluster_size=min_cluster_size)
+        res = ClusterResultC(); nl = C.c_int()
+        labels = np.empty(max(n, 1), np.int32); order = np.empty(max(n, 1), np.int32); offsets = np.empty(n + 1, np.int32)
+        rows = np.empty((max(n, 1), 3), np.float32) if grouped else None
+        _check(self._h, lib().tdv_cluster_dbscan(self._h, _ptr(xyz), n, C.byref(p), C.byref(res), _ptr(labels), _ptr(order), _ptr(rows),
+                                                 _ptr(offsets), n, C.byref(nl)), "tdv_cluster_dbscan")
+        out = (dict(_cluster_result(res), n_labelled=nl.value), labels[:n], order[:n], offsets[:res.n_clusters + 1].copy())
+        return out + (rows[:n],) if grouped else out
+
+    def cluster_dbscan(self, xyz, eps, min_points, min_cluster_size=1):
+        """Open3D's PointCloud.cluster_dbscan: labels int32[n], -1 for noise."""
+        return self.cluster(xyz, eps, min_points, min_cluster_size)[1]
+
+    def cluster_dbscan_dev(self, d_xyz, n, eps, min_points, min_cluster_size=1, d_labels=None, d_order=None, d_grouped=None):
+        """tdv_cluster_dbscan_dev on device pointers: (result dict as cluster's, offsets int32[n_clusters + 1] on the host).  d_labels
+        (int32[n]), d_order (int32[n]) and d_grouped (float[3n]) are optional; (d_grouped, offsets) is what the batch calls take."""
+        p = cluster_params(eps=eps, min_points=min_points, min_cluster_size=min_cluster_size)
+        res = ClusterResultC(); nl = C.c_int()
+        offsets = np.empty(n + 1, np.int32)
+        _check(self._h, lib().tdv_cluster_dbscan_dev(self._h, _ptr(d_xyz), n, C.byref(p), C.byref(res), _ptr(d_labels), _ptr(d_order),
+                                                     _ptr(d_grouped), _ptr(offsets), n, C.byref(nl)), "tdv_cluster_dbscan_dev")
+        return dict(_cluster_result(res), n_labelled=nl.value), offsets[:res.n_clusters + 1].copy()
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

@@ -566,6 +566,60 @@ int tdv_segment_planes(tdv_ctx* ctx, const float* xyz, int n, const tdv_plane_pa
                        int* n_planes, int* labels /* int[n], optional */);
 int tdv_segment_planes_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_plane_params* params, tdv_plane_result* out, int* n_planes,
                            int* d_labels /* optional */, float* d_rest_xyz /* optional, float[3n] */, int* n_rest /* host, optional */);
+/* Euclidean clustering (DBSCAN; Open3D's PointCloud::cluster_dbscan(eps, min_points)): which points of a cloud form an instance.  Every
+ * output is an integer and every rule below is exact, so the result does not depend on the order in which the device works:
+ *  1. Distance: d2(i, j) = (dx * dx + dy * dy) + dz * dz in f32 without contraction, dx, dy, dz the differences of the raw coordinates
+ *     (their sign does not matter: negation is exact); eps2 = eps * eps in f32, FLT_MAX where that overflows (so that an infinite d2
+ *     never passes).
+ *  2. Neighbour: j is a neighbour of i iff d2(i, j) <= eps2 - this library's radius convention (tdv_compute_fpfh), a deliberate
+ *     difference from the strict test of nanoflann behind Open3D's search.  A point counts itself (d2 = 0), as in Open3D.
+ *  3. Non-finite coordinates have no special case: a row with a NaN or infinite coordinate has d2 NaN or +inf to every row, itself
+ *     included, so it is nobody's neighbour, has no neighbour, and ends as noise.
+ *  4. Core: a point with at least min_points neighbours (itself included).
+ *  5. Clusters: the connected components of the core points under the neighbour relation, numbered 0, 1, ... in ascending order of
+ *     their lowest-index core point.  That is the order in which Open3D's ascending scan opens them: on core points the labels equal
+ *     Open3D's (wherever the two neighbour tests agree).
+ *  6. Border: a non-core point with at least one core neighbour.  Open3D gives it to the cluster that reaches it first, which depends
+ *     on the scan order; here it joins the cluster of its NEAREST core neighbour, ties in d2 to the lowest index - the order of the
+ *     64-bit key (d2 bits, index) that the neighbour lists of this library follow.  A border point joins, it does not connect.
+ *  7. Noise: every other point; label -1.
+ *  8. min_cluster_size (1: Open3D's behaviour): a cluster's size is its core plus its border points; clusters below it become noise and
+ *     the others are numbered again by rule 5.
+ * result: n_clusters (after rule 8), n_core and n_border (rules 4 and 6, before rule 8), n_noise (labels of -1 at the end), n_dropped
+ * (clusters rule 8 removed), largest (members of the largest kept cluster, 0 without one).
+ * labels (optional, int[n]).  order (optional, int[n]): the original indices of the labelled points sorted by (label, index), then the
+ * noise points in ascending index; *n_labelled (optional) = the labelled ones.  grouped_xyz (optional, float[3n]): the rows of the
+ * cloud in that order.  offsets (HOST memory in either entry point, room for offsets_capacity + 1 ints): cluster b is
+ * [offsets[b], offsets[b + 1]) of order and grouped_xyz, offsets[n_clusters] = n_labelled - the (d_src, h_src_offsets) layout of
+ * tdv_icp_batch_dev, tdv_gicp_batch_dev and tdv_voxel_downsample_batch_dev: cluster b goes straight into a batch call.  When
+ * n_clusters > offsets_capacity (NULL with capacity 0 is a query) the call returns TDV_ERR_BAD_ARG with result, labels, order,
+ * grouped_xyz and n_labelled written and offsets untouched.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params or result; a NULL cloud with n > 0; n < 0; eps not finite
+ * or not > 0; min_points < 1; min_cluster_size < 1; offsets_capacity < 0, or > 0 with NULL offsets.  n == 0 is accepted (zero counts,
+ * offsets[0] = 0).  tdv_cluster_default_params sets min_cluster_size = 1 and leaves eps = 0 and min_points = 0 for the caller (Open3D has
+ * no defaults for them).  tdv_cluster_dbscan takes host arrays; tdv_cluster_dbscan_dev device pointers (it reads back the result, then
+ * the offsets, at the end).  The ctx's ICP switches do not apply.  Not provided: clustering inside tdv_register_batch_dev (an ABI
+ * change), a batched per-frame form, the C++ operator mirror, normal- or colour-aware region growing, HDBSCAN / OPTICS. */
+typedef struct tdv_cluster_params {
+    float eps;               /* no default: the caller's */
+    int   min_points;        /* no default: the caller's */
+    int   min_cluster_size;  /* 1 */
+} tdv_cluster_params;
+typedef struct tdv_cluster_result {
+    int n_clusters;
+    int n_core;
+    int n_border;
+    int n_noise;
+    int n_dropped;
+    int largest;
+} tdv_cluster_result;
+void tdv_cluster_default_params(tdv_cluster_params* p);
+int tdv_cluster_dbscan(tdv_ctx* ctx, const float* xyz, int n, const tdv_cluster_params* params, tdv_cluster_result* result,
+                       int* labels /* optional */, int* order /* optional */, float* grouped_xyz /* optional */,
+                       int* offsets /* optional */, int offsets_capacity, int* n_labelled /* optional */);
+int tdv_cluster_dbscan_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_cluster_params* params, tdv_cluster_result* result,
+                           int* d_labels /* optional */, int* d_order /* optional */, float* d_grouped_xyz /* optional */,
+                           int* offsets /* host, optional */, int offsets_capacity, int* n_labelled /* host, optional */);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
