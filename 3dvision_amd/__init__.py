@@ -60,6 +60,7 @@ ABI_SYMBOLS = [
     "tdv_fgr_default_params", "tdv_fgr", "tdv_fgr_dev", "tdv_fgr_correspondences",
     "tdv_plane_default_params", "tdv_segment_planes", "tdv_segment_planes_dev",
     "tdv_cluster_default_params", "tdv_cluster_dbscan", "tdv_cluster_dbscan_dev",
+    "tdv_remove_statistical_outlier", "tdv_remove_statistical_outlier_dev", "tdv_remove_radius_outlier", "tdv_remove_radius_outlier_dev",
 ]
 
 
@@ -168,6 +169,14 @@ def cluster_params(**kw):
 
 def _cluster_result(r):
     return {k: getattr(r, k) for k, _ in ClusterResultC._fields_}
+
+
+class OutlierResultC(C.Structure):
+    _fields_ = [("n_valid", C.c_int), ("n_kept", C.c_int), ("cloud_mean", C.c_double), ("std_dev", C.c_double), ("threshold", C.c_double)]
+
+
+def _outlier_result(r):
+    return {k: getattr(r, k) for k, _ in OutlierResultC._fields_}
 
 
 _lib = None
@@ -748,6 +757,64 @@ class Context:
         _check(self._h, lib().tdv_cluster_dbscan_dev(self._h, _ptr(d_xyz), n, C.byref(p), C.byref(res), _ptr(d_labels), _ptr(d_order),
                                                      _ptr(d_grouped), _ptr(offsets), n, C.byref(nl)), "tdv_cluster_dbscan_dev")
         return dict(_cluster_result(res), n_labelled=nl.value), offsets[:res.n_clusters + 1].copy()
+
+    # ---------------------------------------------------------------- outlier removal (include/tdv_hip.h: tdv_remove_statistical_outlier)
+    def _outlier_host(self, fn, what, xyz, rgb, a, b, per_point_dtype):
+        xyz = _f32(xyz).reshape(-1, 3); n = len(xyz)
+        rgb = None if rgb is None else _f32(rgb).reshape(-1, 3)
+        if rgb is not None and len(rgb) != n:
+            raise ValueError("%s: one colour per point" % what)
+        res = OutlierResultC()
+        mask = np.zeros(max(n, 1), np.uint8); per = np.zeros(max(n, 1), per_point_dtype); index = np.zeros(max(n, 1), np.int32)
+        rows = np.zeros((max(n, 1), 3), np.float32); cols = None if rgb is None else np.zeros((max(n, 1), 3), np.float32)
+        _check(self._h, fn(self._h, _ptr(xyz), _ptr(rgb), n, a, b, C.byref(res), _ptr(mask), _ptr(per), _ptr(index), _ptr(rows), _ptr(cols)), what)
+        m = res.n_kept
+        return dict(_outlier_result(res), mask=mask[:n], per_point=per[:n], index=index[:m], xyz=rows[:m], rgb=None if cols is None else cols[:m])
+
+    def statistical_outlier(self, xyz, nb_neighbors, std_ratio, rgb=None):
+        """tdv_remove_statistical_outlier, every output: dict(n_valid, n_kept, cloud_mean, std_dev, threshold, mask uint8[n], mean float64[n],
+        index int32[n_kept], xyz float32[n_kept, 3], rgb or None)."""
+        r = self._outlier_host(lib().tdv_remove_statistical_outlier, "tdv_remove_statistical_outlier", xyz, rgb, int(nb_neighbors),
+                               C.c_double(std_ratio), np.float64)
+        r["mean"] = r.pop("per_point")
+        return r
+
+    def radius_outlier(self, xyz, nb_points, radius, rgb=None):
+        """tdv_remove_radius_outlier, every output: as statistical_outlier, with count int32[n] (saturated at nb_points + 1) for mean."""
+        r = self._outlier_host(lib().tdv_remove_radius_outlier, "tdv_remove_radius_outlier", xyz, rgb, int(nb_points), C.c_float(radius), np.int32)
+        r["count"] = r.pop("per_point")
+        return r
+
+    def remove_statistical_outlier(self, xyz, nb_neighbors, std_ratio, rgb=None):
+        """Open3D's PointCloud.remove_statistical_outlier: (the kept rows, ind - their indices, int64 ascending); with rgb, (rows, colours, ind)."""
+        r = self.statistical_outlier(xyz, nb_neighbors, std_ratio, rgb)
+        ind = r["index"].astype(np.int64)
+        return (r["xyz"], ind) if rgb is None else (r["xyz"], r["rgb"], ind)
+
+    def remove_radius_outlier(self, xyz, nb_points, radius, rgb=None):
+        """Open3D's PointCloud.remove_radius_outlier: (the kept rows, ind); with rgb, (rows, colours, ind)."""
+        r = self.radius_outlier(xyz, nb_points, radius, rgb)
+        ind = r["index"].astype(np.int64)
+        return (r["xyz"], ind) if rgb is None else (r["xyz"], r["rgb"], ind)
+
+    def remove_statistical_outlier_dev(self, d_xyz, n, nb_neighbors, std_ratio, d_rgb=None, d_mask=None, d_mean=None, d_index=None,
+                                       d_out_xyz=None, d_out_rgb=None):
+        """tdv_remove_statistical_outlier_dev on device pointers: the result dict (n_valid, n_kept, cloud_mean, std_dev, threshold).  d_mask
+        (uint8[n]), d_mean (float64[n]), d_index (int32[n]), d_out_xyz and d_out_rgb (float[3n]) are optional; n_kept rows are written."""
+        res = OutlierResultC()
+        _check(self._h, lib().tdv_remove_statistical_outlier_dev(self._h, _ptr(d_xyz), _ptr(d_rgb), n, int(nb_neighbors), C.c_double(std_ratio),
+                                                                 C.byref(res), _ptr(d_mask), _ptr(d_mean), _ptr(d_index), _ptr(d_out_xyz),
+                                                                 _ptr(d_out_rgb)), "tdv_remove_statistical_outlier_dev")
+        return _outlier_result(res)
+
+    def remove_radius_outlier_dev(self, d_xyz, n, nb_points, radius, d_rgb=None, d_mask=None, d_count=None, d_index=None, d_out_xyz=None,
+                                  d_out_rgb=None):
+        """tdv_remove_radius_outlier_dev on device pointers: the result dict; d_count (int32[n]) takes d_mean's place."""
+        res = OutlierResultC()
+        _check(self._h, lib().tdv_remove_radius_outlier_dev(self._h, _ptr(d_xyz), _ptr(d_rgb), n, int(nb_points), C.c_float(radius), C.byref(res),
+                                                            _ptr(d_mask), _ptr(d_count), _ptr(d_index), _ptr(d_out_xyz), _ptr(d_out_rgb)),
+               "tdv_remove_radius_outlier_dev")
+        return _outlier_result(res)
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

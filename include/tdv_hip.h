@@ -620,6 +620,60 @@ int tdv_cluster_dbscan(tdv_ctx* ctx, const float* xyz, int n, const tdv_cluster_
 int tdv_cluster_dbscan_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_cluster_params* params, tdv_cluster_result* result,
                            int* d_labels /* optional */, int* d_order /* optional */, float* d_grouped_xyz /* optional */,
                            int* offsets /* host, optional */, int offsets_capacity, int* n_labelled /* host, optional */);
+/* Outlier removal (Open3D's PointCloud::remove_statistical_outlier(nb_neighbors, std_ratio) and remove_radius_outlier(nb_points,
+ * radius)): the flying pixels and speckle of a depth frame, taken out before anything fits a model to the cloud.  Every rule is exact.
+ * Statistical filter:
+ *  1. Neighbours: the library's kNN list of point i for k = nb_neighbors - what tdv_estimate_normals(_dev) returns in out_knn:
+ *     d2 = dx * dx + (dy * dy + dz * dz) in f32 without contraction over every row j whose d2 is not NaN, ordered by (d2 bits, index),
+ *     self included (d2 = 0), the first min(nb_neighbors, n) entries.  count_i = the entries found; a query with a NaN coordinate finds
+ *     none, and a d2 of +inf (an infinite row, an overflow) is a distance like any other.
+ *  2. mean_i = (sum over the list in list order, sequentially from 0.0, of sqrt((double)d2_r)) / (double)count_i, in f64 with the
+ *     correctly rounded sqrt: Open3D's std::accumulate order.  count_i = 0: the quiet NaN 0x7ff8000000000000.
+ *  3. valid_i iff count_i > 0 and mean_i is finite and > 0 (Open3D's > 0 guard: a point with nb_neighbors exact duplicates of itself is
+ *     not valid).  Non-finite rows and overflowing distances fall out by the arithmetic alone (their mean is NaN or +inf).
+ *  4. n_valid = the valid points.  cloud_mean = (sum of mean_i over them) / n_valid, std_dev = sqrt((sum of (mean_i - cloud_mean)^2) /
+ *     (n_valid - 1)), threshold = cloud_mean + std_ratio * std_dev, all f64, two passes (no sum of squares).  Either sum runs in ONE fixed
+ *     order, so that two calls give the same bits: the term of point i (+0.0 where it is not valid) belongs to workgroup i / 256, thread
+ *     t = i % 256; a workgroup sum is the shuffle tree over each wave of 64 (v += v[lane + off] for off = 32, 16, 8, 4, 2, 1; lane 0
+ *     holds it), then (w0 + w1) + (w2 + w3) over its four waves; one workgroup then adds the workgroup sums b = t, t + 256, t + 512,
+ *     ... in that order into thread t and sums its 256 threads the same way.  No float atomics.  n_valid = 0: cloud_mean, std_dev and
+ *     threshold are NaN; n_valid = 1: std_dev and threshold are NaN.  Nothing is kept in either case.
+ *  5. Kept iff valid_i and mean_i < threshold (strict; NaN fails it).
+ * Radius filter: d2 and eps2 = radius * radius are rule 1 of tdv_cluster_dbscan (the tree (dx * dx + dy * dy) + dz * dz, FLT_MAX where
+ * eps2 overflows), neighbour iff d2 <= eps2 (rule 2 there: this library's radius convention), self counts, rows with a NaN or infinite
+ * coordinate have no neighbour (rule 3 there).  Kept iff the count > nb_points, as in Open3D: the core flag of tdv_cluster_dbscan at
+ * min_points = nb_points + 1.  count[i] is saturated at nb_points + 1 (the walk stops there).
+ * result: n_valid (statistical: rule 4; radius: the rows that count themselves, i.e. the finite ones), n_kept, and cloud_mean, std_dev,
+ * threshold (0 from the radius filter).  Optional outputs, NULL to skip: mask (uint8[n], 1 = kept), mean (double[n], rule 2) resp.
+ * count (int[n]), index (int[n]: the kept original indices in ascending order, n_kept of them), out_xyz and out_rgb (float[3n]: the kept
+ * rows in that order, n_kept of them - a cloud ready for tdv_voxel_downsample_dev or tdv_cluster_dbscan_dev; out_rgb needs rgb).  Entries
+ * beyond n_kept are not written.  rgb is optional.  The host entry points take host arrays and read back twice (the result with mask and
+ * mean / count, then the n_kept rows); the _dev entry points take device pointers and read back once, the result.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx or result; a NULL cloud with n > 0; n < 0; nb_neighbors outside
+ * [1, 255]; std_ratio NaN or infinite (a negative one is allowed); nb_points < 0; radius not finite or not > 0.  n == 0 is accepted (zero
+ * counts; the statistical doubles are NaN).  The ctx's ICP switches do not apply.  Not provided: a per-instance (offsets) form, the filter
+ * inside tdv_register_batch_dev / tdv_refine_batch_dev (an ABI change), the C++ operator mirror, normals pass-through (gather with
+ * index). */
+typedef struct tdv_outlier_result {
+    int    n_valid;
+    int    n_kept;
+    double cloud_mean;
+    double std_dev;
+    double threshold;
+} tdv_outlier_result;
+int tdv_remove_statistical_outlier(tdv_ctx* ctx, const float* xyz, const float* rgb /* optional */, int n, int nb_neighbors, double std_ratio,
+                                   tdv_outlier_result* result, uint8_t* mask /* optional */, double* mean /* optional */,
+                                   int* index /* optional */, float* out_xyz /* optional */, float* out_rgb /* optional */);
+int tdv_remove_statistical_outlier_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb /* optional */, int n, int nb_neighbors,
+                                       double std_ratio, tdv_outlier_result* result, uint8_t* d_mask /* optional */,
+                                       double* d_mean /* optional */, int* d_index /* optional */, float* d_out_xyz /* optional */,
+                                       float* d_out_rgb /* optional */);
+int tdv_remove_radius_outlier(tdv_ctx* ctx, const float* xyz, const float* rgb /* optional */, int n, int nb_points, float radius,
+                              tdv_outlier_result* result, uint8_t* mask /* optional */, int* count /* optional */, int* index /* optional */,
+                              float* out_xyz /* optional */, float* out_rgb /* optional */);
+int tdv_remove_radius_outlier_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb /* optional */, int n, int nb_points, float radius,
+                                  tdv_outlier_result* result, uint8_t* d_mask /* optional */, int* d_count /* optional */,
+                                  int* d_index /* optional */, float* d_out_xyz /* optional */, float* d_out_rgb /* optional */);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
