@@ -46,7 +46,7 @@ DEPTH_BATCH_MASK_PASSES = 1   # the B masks cross HBM once in tdv_depth_to_cloud
 
 # every symbol include/tdv_hip.h declares (checked by the CPU test-suite against the built library)
 ABI_SYMBOLS = [
-    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_set_ransac_score", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
+    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
     "tdv_ctx_destroy", "tdv_status_string", "tdv_last_error", "tdv_version", "tdv_timing_enable", "tdv_timing_read",
     "tdv_depth_preprocess", "tdv_deproject", "tdv_depth_to_cloud", "tdv_voxel_downsample", "tdv_estimate_normals",
     "tdv_compute_fpfh", "tdv_feature_match", "tdv_ransac", "tdv_icp", "tdv_icp_correspondences",
@@ -400,6 +400,16 @@ class Context:
     def workspace_high_water(self):
         """Bytes of device memory held by this ctx's workspace arenas (its batch lanes' included): the high-water mark so far."""
         return int(lib().tdv_ctx_workspace_bytes(self._h))
+
+    def workspace_fill(self, byte):
+        """Test aid (include/tdv_hip.h: tdv_ctx_workspace_fill): every byte of this ctx's workspace arenas and pinned staging, its batch
+        lanes' included, becomes `byte` (0..255).  The persistent ticket and status words are left alone."""
+        _check(self._h, lib().tdv_ctx_workspace_fill(self._h, int(byte)), "tdv_ctx_workspace_fill")
+
+    def set_stream(self, handle):
+        """Run this ctx's work on the caller's stream `handle` from now on (0 = the null stream, torch.cuda.Stream().cuda_stream, ...);
+        the ctx waits for and destroys the stream it made itself, and never destroys the caller's."""
+        _check(self._h, lib().tdv_ctx_set_stream(self._h, C.c_void_p(int(handle))), "tdv_ctx_set_stream")
 
     def close(self):
         if self._h:

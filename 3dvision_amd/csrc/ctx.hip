@@ -323,6 +323,18 @@ unsigned long long tdv_ctx_workspace_bytes(tdv_ctx* ctx) {
     return total;
 }
 
+// test aid (include/tdv_hip.h): arena blocks and pinned staging of the ctx and its lanes; scan_ticket and chain_status stay as they are
+int tdv_ctx_workspace_fill(tdv_ctx* ctx, int byte) {
+    if (!ctx || byte < 0 || byte > 255) return TDV_ERR_BAD_ARG;
+    for (tdv_ctx* c = ctx; c; c = c->helper) {
+        TDV_HIP(ctx, hipSetDevice(c->device));
+        for (auto& b : c->blocks) TDV_HIP(ctx, hipMemsetAsync(b.p, byte, b.cap, c->stream));
+        TDV_HIP(ctx, hipStreamSynchronize(c->stream));
+        if (c->pin) memset(c->pin, byte, c->pin_cap);
+    }
+    return TDV_OK;
+}
+
 int tdv_ctx_set_stream(tdv_ctx* ctx, void* s) {
     if (!ctx) return TDV_ERR_BAD_ARG;
     if (ctx->own_stream && ctx->stream) { (void)hipStreamSynchronize(ctx->stream); (void)hipStreamDestroy(ctx->stream); }

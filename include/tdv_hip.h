@@ -148,6 +148,14 @@ int tdv_ctx_last_batch_lanes(tdv_ctx* ctx);
 /* Device memory this ctx holds in its grow-only workspace arenas, its batch lanes' included: the high-water mark of every
  * call made on it so far (the arena never shrinks; steady state allocates nothing). */
 unsigned long long tdv_ctx_workspace_bytes(tdv_ctx* ctx);
+/* Test aid: sets every byte of every workspace arena block this ctx holds, and of every batch lane's, to `byte` (on each
+ * one's stream, then waits for it), and every byte of their pinned host staging as well.  A call's outputs are a function of its
+ * arguments and the ctx's settings only, so a call made after this gives the bytes it gives on a fresh ctx
+ * (tests/test_gpu_ctx_state.py).  The persistent device words - the last-workgroup tickets and the chained scan's status words
+ * with its epoch and ticket base - are NOT touched: they carry an invariant from one call to the next (every kernel that uses a
+ * ticket leaves it at zero; a status word is told apart by its epoch), and a kernel that waits on them would wait for ever.
+ * The ctx must be idle.  A NULL ctx or a byte outside 0..255 returns TDV_ERR_BAD_ARG.  Not for production use. */
+int tdv_ctx_workspace_fill(tdv_ctx* ctx, int byte);
 const char* tdv_status_string(int status);
 /* Text of the last HIP error seen by this ctx ("" if none). */
 const char* tdv_last_error(tdv_ctx* ctx);

@@ -28,12 +28,14 @@ def _up(a):
     base = torch.zeros((len(a) + 2) * row, dtype=getattr(torch, str(a.dtype)), device=DEV)
     if a.size:
         base[row:row + a.size].copy_(torch.from_numpy(a.reshape(-1)).to(DEV))
+    torch.cuda.synchronize()                                           # filled on the null stream; the ctx reads it on its own non-blocking stream
     return base, base.data_ptr() + row * a.itemsize                    # (from the base: an empty view's data_ptr() is 0)
 
 
 def _out(n, row, dtype=torch.float32):
     """An output for n rows of `row` elements plus one more, every element the sentinel's bits."""
     t = torch.full(((n + 1) * row,), int(SENTINEL), dtype=torch.int32, device=DEV)
+    torch.cuda.synchronize()                                           # the fill must have landed before the ctx's stream writes the buffer
     return t.view(dtype)
 
 
