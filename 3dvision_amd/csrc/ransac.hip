@@ -21,17 +21,25 @@
 //        iteration whose fitness passes the confidence, then the first largest fitness up to it - strict > on
 //        float(inliers)/ns against the running best, which stays on the device with the winner's 12 floats; the host
 //        reads one four-int record per batch.  A traced call downloads every count and runs the loop on the host.
-//  (vi)  k_ransac_rmse: error sum of the winning hypothesis only, fixed-order reduction.
+//  (vi)  k_ransac_rmse_partial / k_ransac_rmse_final: error sum of the winning hypothesis only, fixed-order reduction (per-workgroup
+//        slabs, then one workgroup over the slabs).
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <algorithm>
+#include <type_traits>
 #include <vector>
 
 namespace tdv {
+
+// The band unit: E = band_u (A + s) in RansacBand (ransac_hypothesis_lane), u = 2^-24.
+constexpr float kUnitRoundoff = 5.9604644775390625e-08f;
+constexpr float kBandUnit = 16.f * kUnitRoundoff;            // the FMA pass
+constexpr float kBandUnitMatrix = 24.f * kUnitRoundoff;      // the study build's matrix-core pass
 
 // ------------------------------------------------------------------ hypotheses
 // pq layout: 8 floats per point: px py pz qx qy qz 0 0  (q = tgt[corr[i]]); padding points have
@@ -40,26 +48,33 @@ namespace tdv {
 // faulting; the host turns the flag into TDV_ERR_BAD_ARG at its first synchronisation.
 // *pmax receives (integer atomic max on the bits of a non-negative float) the largest |source coordinate|, +inf for a
 // non-finite one or a NaN in a matched target: it scales the rounding band of the fast scoring pass (k_ransac_score_fast).
+// One pair record (a = px py pz qx, b = qy qz 0 0) of source point i and its match; returns the record's am, the pmax term.
+template <class I>
+__device__ __forceinline__ float pair_record(const float* __restrict__ src, const float* __restrict__ tgt, const int* __restrict__ corr, I i, int nt,
+                                             int* __restrict__ bad, float4& a, float4& b) {
+    int c = corr[i];
+    if ((unsigned)c >= (unsigned)nt) { *bad = 1; c = 0; }
+    a = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], tgt[3 * c]);
+    b = make_float4(tgt[3 * c + 1], tgt[3 * c + 2], 0.f, 0.f);
+    float am = fmaxf(fabsf(a.x), fmaxf(fabsf(a.y), fabsf(a.z)));
+    if (!(am <= FLT_MAX)) am = INFINITY;      // inf (fmaxf drops a NaN: checked below)
+    // a NaN coordinate - source or target - makes d2 NaN, whose sign bit the fast pass would read as "inlier" where it is
+    // set: such a cloud is scored with the reference arithmetic throughout (an infinite target gives d2 = +inf in both)
+    if (a.x != a.x || a.y != a.y || a.z != a.z || a.w != a.w || b.x != b.x || b.y != b.y) am = INFINITY;
+    return am;
+}
+__device__ __forceinline__ void pair_record_padding(float4& a, float4& b) {
+    a = make_float4(0.f, 0.f, 0.f, INFINITY);
+    b = make_float4(INFINITY, INFINITY, 0.f, 0.f);
+}
 __global__ void k_gather_pq(const float* __restrict__ src, const float* __restrict__ tgt, const int* __restrict__ corr,
                             int ns, int ns_pad, int nt, float* __restrict__ pq, int* __restrict__ bad, unsigned* __restrict__ pmax) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     float am = 0.f;
     if (i < ns_pad) {
         float4 a, b;
-        if (i < ns) {
-            int c = corr[i];
-            if ((unsigned)c >= (unsigned)nt) { *bad = 1; c = 0; }
-            a = make_float4(src[3 * i], src[3 * i + 1], src[3 * i + 2], tgt[3 * c]);
-            b = make_float4(tgt[3 * c + 1], tgt[3 * c + 2], 0.f, 0.f);
-            am = fmaxf(fabsf(a.x), fmaxf(fabsf(a.y), fabsf(a.z)));
-            if (!(am <= FLT_MAX)) am = INFINITY;      // inf (fmaxf drops a NaN: checked below)
-            // a NaN coordinate - source or target - makes d2 NaN, whose sign bit the fast pass would read as "inlier" where it is
-            // set: such a cloud is scored with the reference arithmetic throughout (an infinite target gives d2 = +inf in both)
-            if (a.x != a.x || a.y != a.y || a.z != a.z || a.w != a.w || b.x != b.x || b.y != b.y) am = INFINITY;
-        } else {
-            a = make_float4(0.f, 0.f, 0.f, INFINITY);
-            b = make_float4(INFINITY, INFINITY, 0.f, 0.f);
-        }
+        if (i < ns) am = pair_record(src, tgt, corr, i, nt, bad, a, b);
+        else pair_record_padding(a, b);
         reinterpret_cast<float4*>(pq)[2 * (size_t)i] = a;
         reinterpret_cast<float4*>(pq)[2 * (size_t)i + 1] = b;
     }
@@ -161,7 +176,7 @@ struct PlanJob { int* state; int* plan; int ns, n_pchunks, ps, drop_permille; in
 __device__ __forceinline__ void ransac_plan(const PlanJob& j);
 __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, int count, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
-                                    float band_u /* E = band_u (A + s): 16 u for the FMA pass, 24 u for the matrix-core pass */, const PlanJob plan) {
+                                    float band_u /* E = band_u (A + s): kBandUnit or kBandUnitMatrix */, const PlanJob plan) {
     int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h == 0 && plan.plan) ransac_plan(plan);
     if (h >= h_pad) return;
@@ -175,6 +190,14 @@ __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView 
 __device__ __forceinline__ unsigned long long shfl_u64_down(unsigned long long v, int o) {
     const unsigned lo = __shfl_down((unsigned)v, o, 64), hi = __shfl_down((unsigned)(v >> 32), o, 64);
     return ((unsigned long long)hi << 32) | lo;
+}
+// "The first largest fitness" as one maximum (k_ransac_finish, k_rb_select): key = fitness bits (positive floats order as their
+// bits), then `earlier`, which is larger for the EARLIER iteration; 0 = none.  first_best_wave: lane 0 gets the wave's largest key.
+__device__ __forceinline__ unsigned long long first_best_key(float fit, int earlier) { return ((unsigned long long)__float_as_uint(fit) << 32) | (unsigned)earlier; }
+__device__ __forceinline__ unsigned long long first_best_wave(unsigned long long best) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = shfl_u64_down(best, o); best = x > best ? x : best; }
+    return best;
 }
 
 // ------------------------------------------------------------------ scoring
@@ -194,6 +217,10 @@ constexpr int RS_HYP_PER_BLOCK = RS_BLOCK;   // one hypothesis per lane (measure
 #define RS_PCH_VALUE 8
 #endif
 constexpr int RS_PCH = RS_PCH_VALUE;   // points per scalar chunk: 4 records of 12 floats (8 measured 81 % of peak, 4: 80 %)
+// The point-range cut: into how many ranges a scoring dispatch with hb hypothesis blocks cuts the points, so that it has about
+// RS_WG_TARGET workgroups, of at least 32 chunks each (at least 1: the first term is, whatever hb).  Host (range_cut) and
+// k_ransac_score_fast's job B agree through this one function.
+__host__ __device__ __forceinline__ int point_ranges(int hb, int n_pchunks) { return min(min((RS_WG_TARGET + hb - 1) / hb, max(1, n_pchunks / 32)), 512); }
 
 // The scoring loop reads a second pair array that holds TWO points per record, component-interleaved
 // [px0 px1 | py0 py1 | pz0 pz1 | qx0 qx1 | qy0 qy1 | qz0 qz1] (48 B per 2 points), so that every arithmetic op is one
@@ -201,6 +228,21 @@ constexpr int RS_PCH = RS_PCH_VALUE;   // points per scalar chunk: 4 records of 
 // instructions, no SGPR shuffling (measured 81 % of the VALU peak against 79 % for the loop vectoriser's packing of
 // the 8-float layout and 71 % for scalar code).
 typedef float v2f __attribute__((ext_vector_type(2)));
+struct Pair2 { v2f px, py, pz, qx, qy, qz; };
+__device__ __forceinline__ Pair2 pair2(const float* v, int p) {      // record p of a chunk held in v
+    return Pair2{{v[12 * p + 0], v[12 * p + 1]}, {v[12 * p + 2], v[12 * p + 3]}, {v[12 * p + 4], v[12 * p + 5]},
+                 {v[12 * p + 6], v[12 * p + 7]}, {v[12 * p + 8], v[12 * p + 9]}, {v[12 * p + 10], v[12 * p + 11]}};
+}
+// The pair test in the reference's arithmetic (registration.cpp:270-279, no contraction) for a record's two points under the
+// hypothesis r (each of the 12 values in both halves): the two d2, and their test.
+__device__ __forceinline__ v2f ref_pair_d2(const v2f* r, const Pair2& a) {
+    const v2f x = (r[0] * a.px + (r[3] * a.py + r[6] * a.pz)) + r[9];
+    const v2f y = (r[1] * a.px + (r[4] * a.py + r[7] * a.pz)) + r[10];
+    const v2f z = (r[2] * a.px + (r[5] * a.py + r[8] * a.pz)) + r[11];
+    const v2f dx = x - a.qx, dy = y - a.qy, dz = z - a.qz;
+    return dx * dx + (dy * dy + dz * dz);
+}
+__device__ __forceinline__ void count_inliers(v2f d2, float tau, int& cnt) { cnt += (d2.x < tau) ? 1 : 0; cnt += (d2.y < tau) ? 1 : 0; }
 __global__ void k_pack_pq2(const float* __restrict__ pq, int ns_pad, float* __restrict__ pq2) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;   // pair index
     if (2 * i >= ns_pad) return;
@@ -227,15 +269,7 @@ void k_ransac_score(const float* __restrict__ hyp, int h_pad, const float* __res
         for (int e = 0; e < 6 * RS_PCH; ++e) v[e] = g[e];
 #pragma unroll
         for (int p = 0; p < RS_PCH / 2; ++p) {
-            const v2f px = {v[12 * p + 0], v[12 * p + 1]}, py = {v[12 * p + 2], v[12 * p + 3]}, pz = {v[12 * p + 4], v[12 * p + 5]};
-            const v2f qx = {v[12 * p + 6], v[12 * p + 7]}, qy = {v[12 * p + 8], v[12 * p + 9]}, qz = {v[12 * p + 10], v[12 * p + 11]};
-            const v2f x = (r[0] * px + (r[3] * py + r[6] * pz)) + r[9];
-            const v2f y = (r[1] * px + (r[4] * py + r[7] * pz)) + r[10];
-            const v2f z = (r[2] * px + (r[5] * py + r[8] * pz)) + r[11];
-            const v2f dx = x - qx, dy = y - qy, dz = z - qz;
-            const v2f d2 = dx * dx + (dy * dy + dz * dz);
-            cnt += (d2.x < tau) ? 1 : 0;
-            cnt += (d2.y < tau) ? 1 : 0;
+            count_inliers(ref_pair_d2(r, pair2(v, p)), tau, cnt);
         }
     }
     atomicAdd(&counts[base], cnt);
@@ -258,7 +292,7 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 //   job B (the ids after): phase 2 of the PREVIOUS batch - the hypotheses its selection listed (plan[1] of them: those that
 //                         can still beat the best count known) over the chunks its phase 1 left out, in ranges of plan[3]
 //                         chunks (= what a job-A workgroup of that batch walked, so all workgroups of a dispatch cost the same).
-// By default the two jobs are dispatched one after the other (job B alone, see ransac_run_dev); with TDV_RANSAC_MERGE=1 job B
+// By default the two jobs are dispatched one after the other (job B alone, see RansacRun::enqueue); with TDV_RANSAC_MERGE=1 job B
 // rides behind the NEXT batch's job A.
 //   job B also scores phase 1 of a batch whose dead hypotheses k_ransac_bound has taken out (RansacLeafBound, below): n_live set,
 //                         the live list (*n_live of them) over the chunks [0, plan[0]) in ranges cut for that many blocks.
@@ -298,11 +332,10 @@ __device__ __forceinline__ int score_range_fast(const float* __restrict__ hyp, c
         v2f tt[RS_PCH / 2];      // d2_fma - mid of every test, kept for the re-scoring branch (which pairs are inside a band)
 #pragma unroll
         for (int p = 0; p < RS_PCH / 2; ++p) {
-            const v2f px = {v[12 * p + 0], v[12 * p + 1]}, py = {v[12 * p + 2], v[12 * p + 3]}, pz = {v[12 * p + 4], v[12 * p + 5]};
-            const v2f qx = {v[12 * p + 6], v[12 * p + 7]}, qy = {v[12 * p + 8], v[12 * p + 9]}, qz = {v[12 * p + 10], v[12 * p + 11]};
-            const v2f dx = fma2(r[0], px, fma2(r[3], py, fma2(r[6], pz, r[9]))) - qx;
-            const v2f dy = fma2(r[1], px, fma2(r[4], py, fma2(r[7], pz, r[10]))) - qy;
-            const v2f dz = fma2(r[2], px, fma2(r[5], py, fma2(r[8], pz, r[11]))) - qz;
+            const Pair2 a = pair2(v, p);
+            const v2f dx = fma2(r[0], a.px, fma2(r[3], a.py, fma2(r[6], a.pz, r[9]))) - a.qx;
+            const v2f dy = fma2(r[1], a.px, fma2(r[4], a.py, fma2(r[7], a.pz, r[10]))) - a.qy;
+            const v2f dz = fma2(r[2], a.px, fma2(r[5], a.py, fma2(r[8], a.pz, r[11]))) - a.qz;
             // d2_fma - mid as one chain ending in -mid: its own rounding, at most 3 u mid = 1.5 u s in distance, sits inside
             // the 3.7 u A + 4 u s that the band's E keeps in reserve over the proven bound
             const v2f t = fma2(dx, dx, fma2(dy, dy, fma2(dz, dz, nmid)));
@@ -320,17 +353,10 @@ __device__ __forceinline__ int score_range_fast(const float* __restrict__ hyp, c
                 const float mp = fminf(fminf(INFINITY, fabsf(tt[p].x)), fabsf(tt[p].y));       // (NaN - an invalid hypothesis - leaves INFINITY)
                 if (!ADAPT && !__any(!(mp >= half))) continue;                                 // (the small-cloud pass keeps re-scoring whole chunks: its ADAPT rule counts them)
                 ++n_rescored;
-                const v2f px = {v[12 * p + 0], v[12 * p + 1]}, py = {v[12 * p + 2], v[12 * p + 3]}, pz = {v[12 * p + 4], v[12 * p + 5]};
-                const v2f qx = {v[12 * p + 6], v[12 * p + 7]}, qy = {v[12 * p + 8], v[12 * p + 9]}, qz = {v[12 * p + 10], v[12 * p + 11]};
-                const v2f x = (r[0] * px + (r[3] * py + r[6] * pz)) + r[9];
-                const v2f y = (r[1] * px + (r[4] * py + r[7] * pz)) + r[10];
-                const v2f z = (r[2] * px + (r[5] * py + r[8] * pz)) + r[11];
-                const v2f dx = x - qx, dy = y - qy, dz = z - qz;
-                const v2f d2 = dx * dx + (dy * dy + dz * dz);
+                const v2f d2 = ref_pair_d2(r, pair2(v, p));
                 // the pair's two sign bits in sgn: test 2p at bit RS_PCH - 1 - 2p, test 2p + 1 right below it
                 cf -= __popc((sgn >> (RS_PCH - 2 - 2 * p)) & 3u);
-                cf += (d2.x < tau) ? 1 : 0;
-                cf += (d2.y < tau) ? 1 : 0;
+                count_inliers(d2, tau, cf);
             }
         }
         cnt += cf;
@@ -343,19 +369,26 @@ __device__ __forceinline__ int score_range_fast(const float* __restrict__ hyp, c
             for (int e = 0; e < 6 * RS_PCH; ++e) v[e] = g[e];
 #pragma unroll
             for (int p = 0; p < RS_PCH / 2; ++p) {
-                const v2f px = {v[12 * p + 0], v[12 * p + 1]}, py = {v[12 * p + 2], v[12 * p + 3]}, pz = {v[12 * p + 4], v[12 * p + 5]};
-                const v2f qx = {v[12 * p + 6], v[12 * p + 7]}, qy = {v[12 * p + 8], v[12 * p + 9]}, qz = {v[12 * p + 10], v[12 * p + 11]};
-                const v2f x = (r[0] * px + (r[3] * py + r[6] * pz)) + r[9];
-                const v2f y = (r[1] * px + (r[4] * py + r[7] * pz)) + r[10];
-                const v2f z = (r[2] * px + (r[5] * py + r[8] * pz)) + r[11];
-                const v2f dx = x - qx, dy = y - qy, dz = z - qz;
-                const v2f d2 = dx * dx + (dy * dy + dz * dz);
-                cnt += (d2.x < tau) ? 1 : 0;
-                cnt += (d2.y < tau) ? 1 : 0;
+                count_inliers(ref_pair_d2(r, pair2(v, p)), tau, cnt);
             }
         }
     }
     return cnt;
+}
+
+// statistics only (tdv_ctx_last_ransac_rescore / _scored): two atomics per workgroup - point pairs scored twice (n_rescored, wave-uniform),
+// and (wave, chunk) pairs scored (chunks, workgroup-uniform); every thread of the workgroup calls it
+template <class C>
+__device__ __forceinline__ void score_stats(unsigned n_rescored, C chunks, unsigned long long* __restrict__ rescored) {
+    __shared__ unsigned s_rescored;
+    if (threadIdx.x == 0) s_rescored = 0u;
+    __syncthreads();
+    if (n_rescored && (threadIdx.x & 63) == 0) atomicAdd(&s_rescored, n_rescored);
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s_rescored) atomicAdd(rescored, (unsigned long long)s_rescored);
+        atomicAdd(rescored + 1, (unsigned long long)(RS_BLOCK / 64) * (unsigned long long)chunks);
+    }
 }
 
 // Occupancy (round 4).  The loop keeps a chunk's 48 floats in SGPRs and the compiler took 106 of them: 7 waves per SIMD on paper, but a
@@ -400,9 +433,9 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         if (n_blk == 0) return;
         const int j0 = id - g1, xcd = j0 & 7, stride = ((int)gridDim.x - g1) >> 3;
         // phase 2: the chunks [plan[0], n_pchunks) in ranges of plan[3]; phase 1 of the live list: [0, plan[0]) in as many ranges
-        // as a job A of n_blk blocks would cut (ranges_for in ransac_run_dev)
+        // as a job A of n_blk blocks would cut (point_ranges)
         const int r0 = b.n_live ? 0 : b.plan[0], r1 = b.n_live ? b.plan[0] : n_pchunks;
-        const int ps_live = min(min((RS_WG_TARGET + n_blk - 1) / n_blk, max(1, n_pchunks / 32)), 512);
+        const int ps_live = point_ranges(n_blk, n_pchunks);
         const int per = b.n_live ? max((r1 + ps_live - 1) / ps_live, 1) : max(b.plan[3], 1);
         const int ranges = (r1 - r0 + per - 1) / per;
         for (int t = j0 >> 3; ; t += stride) {
@@ -417,16 +450,7 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         }
         if (!chunks) return;
     }
-    // statistics only (tdv_ctx_last_ransac_rescore / _scored): two atomics per workgroup — (wave, chunk) pairs scored, and scored twice
-    __shared__ unsigned s_rescored;
-    if (threadIdx.x == 0) s_rescored = 0u;
-    __syncthreads();
-    if (n_rescored && (threadIdx.x & 63) == 0) atomicAdd(&s_rescored, n_rescored);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_rescored) atomicAdd(rescored, (unsigned long long)s_rescored);
-        atomicAdd(rescored + 1, (unsigned long long)(RS_BLOCK / 64) * (unsigned long long)chunks);
-    }
+    score_stats(n_rescored, chunks, rescored);
 }
 
 // RansacPlan — exact bail-out.  The loop of ransacRegistration (registration.cpp:284-290) uses an iteration's inlier count only
@@ -480,37 +504,41 @@ void k_ransac_best(const TriView triples, int count, const int* __restrict__ cou
 //       that fires at a kept iteration e returns e itself: anything earlier with at least its count would have ended the loop
 //       before, and every dropped iteration has a count below the confidence bar that e passed.  [round 3]
 // Either way the counts of the dropped hypotheses stay partial and compare as the true ones would: below the result's.
-// With RansacLeafBound, bnd[h] is a second upper bound of the full count (k_ransac_bound; INT_MAX where it has none): a dead
-// hypothesis, never scored, has bnd <= best and is dropped by rule (a) - it never enters phase 2.
-__global__ void k_ransac_select(const TriView triples, int count, const int* __restrict__ counts, int ns, float confidence,
-                                const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list, const int* __restrict__ bnd) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    const int c_split = plan[0], best = state[0], in_batch = plan[2];
-    const int rest = max(0, ns - min(ns, c_split * RS_PCH));     // (the padding past ns is never an inlier)
-    bool keep = h < count && triples.valid(h) && rest > 0;
-    if (keep) {
-        const int ub = bnd ? min(counts[h] + rest, bnd[h]) : counts[h] + rest;
-        const bool passes = static_cast<float>(ub) / static_cast<float>((size_t)ns) > confidence;   // registration.cpp:281,290 on the bound
-        keep = ub > best && (ub >= in_batch || passes);
-    }
-    const unsigned long long m = __ballot(keep);
-    if (!m) return;
-    const int lane = threadIdx.x & 63;
+// Appends h to list (*n entries so far) for the lanes that `take`, one atomic per wave; returns the lane's slot.
+__device__ __forceinline__ int rb_append(bool take, int lane, int h, int* __restrict__ list, int* __restrict__ n) {
+    const unsigned long long m = __ballot(take);
+    if (!m) return 0;
+    const int lead = (int)__builtin_ctzll(m);
     int at = 0;
-    if (lane == 0) at = atomicAdd(&plan[1], __popcll(m));
-    at = __shfl(at, 0, 64);
-    if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
+    if (lane == lead) at = atomicAdd(n, __popcll(m));
+    at = __shfl(at, lead, 64) + __popcll(m & ((1ull << lane) - 1ull));
+    if (take) list[at] = h;
+    return at;
+}
+// `prefix` = the hypothesis' count over phase 1, `best` = rule (a)'s, `in_batch` = rule (b)'s L.
+__device__ __forceinline__ bool ransac_keep(int prefix, int rest, int best, int in_batch, int ns, float confidence) {
+    const int ub = prefix + rest;
+    const bool passes = static_cast<float>(ub) / static_cast<float>((size_t)ns) > confidence;   // registration.cpp:281,290 on the bound
+    return ub > best && (ub >= in_batch || passes);
+}
+__device__ __forceinline__ int ransac_rest(int ns, int c_split) { return max(0, ns - min(ns, c_split * RS_PCH)); }   // points phase 1 left out (the padding past ns is never an inlier)
+__global__ void k_ransac_select(const TriView triples, int count, const int* __restrict__ counts, int ns, float confidence,
+                                const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list) {
+    const int h = blockIdx.x * blockDim.x + threadIdx.x;
+    const int best = state[0], in_batch = plan[2], rest = ransac_rest(ns, plan[0]);
+    bool keep = h < count && triples.valid(h) && rest > 0;
+    if (keep) keep = ransac_keep(counts[h], rest, best, in_batch, ns, confidence);
+    rb_append(keep, threadIdx.x & 63, h, list, &plan[1]);
 }
 // The two kernels above for a BOUNDED batch, in one launch over its live list (`live`, *n_live entries, in no order).  A dead
-// hypothesis was never scored: its count is 0, which leaves the prefix maximum alone, and its bnd <= best drops it by rule (a).
-// So the largest prefix count of the live ones is the batch's (plan[2]), and the list is built from them under the same rules
-// with ub = count + rest (a live hypothesis' bnd is INT_MAX).  Phase 2's list holds the same hypotheses as k_ransac_select's,
+// hypothesis was never scored: its count is 0, which leaves the prefix maximum alone, and its leaf-box bound <= best drops it by
+// rule (a).  So the largest prefix count of the live ones is the batch's (plan[2]), and the list is built from them under the same
+// rules.  Phase 2's list holds the same hypotheses as k_ransac_select's,
 // in another order: counts are integer atomics, the order does not matter.  One workgroup: the live list is an eighth of a batch.
 __global__ __launch_bounds__(1024)
 void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ n_live, const int* __restrict__ counts, int ns, float confidence,
                           const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list) {
-    const int n = *n_live, c_split = plan[0], best = state[0];
-    const int rest = max(0, ns - min(ns, c_split * RS_PCH));     // (the padding past ns is never an inlier)
+    const int n = *n_live, c_split = plan[0], best = state[0], rest = ransac_rest(ns, c_split);
     __shared__ int s_max, s_n;
     if (threadIdx.x == 0) { s_max = 0; s_n = 0; }
     __syncthreads();
@@ -527,9 +555,7 @@ void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ 
         int h = 0;
         if (keep) {
             h = live[i];
-            const int ub = counts[h] + rest;
-            const bool passes = static_cast<float>(ub) / static_cast<float>((size_t)ns) > confidence;   // registration.cpp:281,290 on the bound
-            keep = ub > best && (ub >= in_batch || passes);
+            keep = ransac_keep(counts[h], rest, best, in_batch, ns, confidence);
         }
         const unsigned long long m = __ballot(keep);
         if (!m) continue;
@@ -580,8 +606,7 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     }
     __syncthreads();
     const int k_stop = s_stop;
-    // the first largest fitness among the iterations up to k_stop: key = fitness bits (positive floats order as their bits), then
-    // the EARLIEST iteration (largest INT_MAX - h)
+    // the first largest fitness among the iterations up to k_stop (earlier = INT_MAX - h)
     unsigned long long best = 0ull;
 #pragma unroll 4
     for (int i = threadIdx.x; i < n; i += 1024) {
@@ -589,11 +614,10 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
         if (h > k_stop || (!live && !triples.valid(h))) continue;
         const float fit = static_cast<float>(counts[h]) / fn;    // registration.cpp:281
         if (!(fit > 0.f)) continue;
-        const unsigned long long key = ((unsigned long long)__float_as_uint(fit) << 32) | (unsigned)(INT_MAX - h);
+        const unsigned long long key = first_best_key(fit, INT_MAX - h);
         best = key > best ? key : best;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = shfl_u64_down(best, o); best = x > best ? x : best; }
+    best = first_best_wave(best);
     if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x != 0) return;
@@ -773,31 +797,19 @@ void k_leaf_build(const float* __restrict__ pq, int ns, const unsigned* __restri
 // latency exposed.)
 // Two levels (round 6).  88 % of the hypotheses are dead, and a dead one walks every leaf.  The coarse leaves (RL_COARSE pairs,
 // each the union of 4 fine leaves) already prove 81 % of them dead at a quarter of the leaf tests, so the bound runs twice:
-//   RB_COARSE   every hypothesis of the batch over the coarse leaves.  Coarse sum <= best: dead, bnd[h] = the coarse sum (an
-//               upper bound of the count, <= best: all k_ransac_select needs).  No band or the gate closed: live.  The rest is
-//               undecided and appended to `und` (*n_und of them, zeroed by k_ransac_plan).
-//   k_ransac_bound_fine   the undecided hypotheses over the fine leaves: the one-level walk, early stop included; dead with
-//               bnd[h] = the fine sum, or live.
+//   RB_COARSE   every hypothesis of the batch over the coarse leaves.  Coarse sum <= best: dead.  No band or the gate closed: live.
+//               The rest is undecided and appended to `und` (*n_und of them, zeroed by ransac_plan).
+//   k_ransac_bound_fine   the undecided hypotheses over the fine leaves: the one-level walk, early stop included; dead or live.
 // A fine leaf's pairs lie inside its coarse leaf's boxes, so in real arithmetic a coarse leaf that fails has children that all
 // fail, the coarse sum is >= the fine sum and coarse-dead implies fine-dead.  In f32 the two tests round differently (other pc,
 // pe; a fine box's rounded-up pe may poke an ulp past its parent's): so the coarse test fails a leaf only on g2 > (s + 5 E)^2,
 // not 3 E.  By (1) below, run both ways, a coarse f32 gap above s + 5 E puts every child's f32 gap above s + 5 E - 2 (14.2 u A +
 // 3 u (s + 5 E)) - 2 u A > s + 3 E (E >= 16 u (A + s)): every child fails its own test too.  Each coarse level verdict is thus
 // the fine walk's, and the live list is exactly the one-level walk's (RB_ONE, kept for the study build's A/B:
-// TDV_RANSAC_BOUND_LEVELS=1; tests/test_ransac_leaf_bound_two_levels.py checks the implication in emulated f32).  A dead
-// hypothesis' bnd is its coarse or its fine sum, whichever level decided it; a live one's is INT_MAX, a skipped iteration's 0.
-// Live hypotheses are appended to `live` (*n_live of them, zeroed by k_ransac_plan).
+// TDV_RANSAC_BOUND_LEVELS=1; tests/test_ransac_leaf_bound_two_levels.py checks the implication in emulated f32).
+// Live hypotheses are appended to `live` (*n_live of them, zeroed by ransac_plan); a dead one leaves no trace: it is on no list.
 constexpr int RB_SPLIT = 16;
 enum { RB_ONE = 0, RB_COARSE = 1 };
-__device__ __forceinline__ void rb_append(bool take, int lane, int h, int* __restrict__ list, int* __restrict__ n) {
-    const unsigned long long m = __ballot(take);
-    if (!m) return;
-    const int lead = (int)__builtin_ctzll(m);
-    int at = 0;
-    if (lane == lead) at = atomicAdd(n, __popcll(m));
-    at = __shfl(at, lead, 64);
-    if (take) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
-}
 // One wave's share [k0, k1) of the leaf pairs for its lane's hypothesis (r: column-major R, t): the sizes of the leaves that
 // may hold an inlier, added until the sum exceeds `best` (done).  tb = (s + margin E)^2 (1 + 1e-6).
 __device__ __forceinline__ int rb_walk(const float* r, const float* __restrict__ leaves, int k0, int k1, float tb, int best, bool done) {
@@ -851,7 +863,7 @@ template <int MODE>
 __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView triples, int count, const float* __restrict__ leaves, int n_lpairs,
                     const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
-                    int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
+                    int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
                     int* __restrict__ acc, int* __restrict__ ticket) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.x * 64 + lane;
@@ -871,34 +883,24 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView trip
     if (ub) atomicAdd(&s_ub[lane], ub);
     __syncthreads();
     if (wave != 0) return;
-    const bool here = h < count;
     const int total = s_ub[lane];
     const bool gated = valid && (!o.bounded || !walk);            // live without a walk
     const bool undecided = MODE == RB_COARSE && valid && !gated && total > best;
     const bool is_live = gated || (MODE == RB_ONE && valid && total > best);
-    if (here && !undecided) bnd[h] = is_live ? INT_MAX : (valid ? total : 0);
     rb_append(is_live, lane, h, live, n_live);
-    if (MODE == RB_COARSE) {
-        const unsigned long long m = __ballot(undecided);
-        if (!m) return;
-        const int lead = (int)__builtin_ctzll(m);
-        int at = 0;
-        if (lane == lead) at = atomicAdd(n_und, __popcll(m));
-        at = __shfl(at, lead, 64);
-        if (undecided) { const int slot = at + __popcll(m & ((1ull << lane) - 1ull)); und[slot] = h; acc[slot] = 0; }
-    }
+    if (MODE == RB_COARSE) { const int slot = rb_append(undecided, lane, h, und, n_und); if (undecided) acc[slot] = 0; }
 }
 // k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a fifth of the batch, too few workgroups to fill the chip with
 // one workgroup per 64 of them, so the leaf pairs are cut into RB_FINE_Y ranges as well (blockIdx.y); a workgroup adds its 64 partial
-// sums to acc[slot], and the last workgroup of a slot block (ticket) decides: live on a total > best, dead with bnd = the total
+// sums to acc[slot], and the last workgroup of a slot block (ticket) decides: live on a total > best, dead
 // otherwise.  A partial sum that stopped early exceeds best alone, so a stop anywhere makes the total exceed it too; without one
-// the total is the full fine sum - the one-level walk's verdict and bnd.  The grid covers the whole batch (the host does not know
+// the total is the full fine sum - the one-level walk's verdict.  The grid covers the whole batch (the host does not know
 // how many hypotheses are undecided); the workgroups past the list return at once.
 constexpr int RB_FINE_Y = 4;
 __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* __restrict__ leaves, int n_lpairs,
                          const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state,
-                         int* __restrict__ bnd, int* __restrict__ live, int* __restrict__ n_live, const int* __restrict__ und, const int* __restrict__ n_und,
+                         int* __restrict__ live, int* __restrict__ n_live, const int* __restrict__ und, const int* __restrict__ n_und,
                          int* __restrict__ acc, int* __restrict__ ticket) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = *n_und, best = state[0];
@@ -925,180 +927,14 @@ void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* 
     if (__shfl(arrived, 0, 64) != (int)gridDim.y - 1) return;    // not the last workgroup of this slot block
     const int total = h >= 0 ? atomicAdd(&acc[slot], 0) : 0;
     const bool is_live = h >= 0 && total > best;
-    if (h >= 0) bnd[h] = is_live ? INT_MAX : total;
     rb_append(is_live, lane, h, live, n_live);
 }
 
 #ifdef TDV_STUDY
-// ------------------------------------------------------------------ scoring on the matrix cores (A/B variant, not the default)
-// R p + t is a [3H x 4] x [4 x N] product, so the transform can run on the matrix cores (v_mfma_f32_32x32x2_f32, twice for
-// K = 4 with a row of ones under the points for t) and leave the vector ALUs the subtraction of q, the squared norm and the
-// classification: 27 vector instructions per 32 points x 10 hypotheses (320 tests) instead of 73 per 8 points x 64
-// hypotheses (512 tests).  Built, parity-green (tests/test_gpu_ransac.py runs every scoring test in this mode too) and
-// MEASURED SLOWER than k_ransac_score_fast: 5.4 ms against 4.0 ms per 65,536 hypotheses x 200k points on the same box
-// (profiles/r2/history/ransac_score_matrix_cores.md).  The probes recorded there show why: the f32 matrix instruction and
-// the vector instructions of a SIMD do not overlap — the kernel's time is the SUM of its matrix time (3.1 ms alone) and its
-// vector time, from one wave or from four per SIMD — and the K = 4 product spends a quarter of its multiply-adds on the
-// constant row and a sixteenth on the unused accumulator row, so per test the matrix pipe is slower than nine packed FMAs.
-// Kept behind TDV_RANSAC_SCORE_MATRIX / TDV_RANSAC_SCORE=mfma as the record of that experiment.
-//
-// Counts stay the reference's: the classification is the band scheme of k_ransac_score_fast (sign of d2 - mid outside the
-// rounding band, the reference arithmetic inside it), with the band widened from 16 u to 24 u (A + s) for the accumulation
-// of the matrix core — taken as at most one rounding per product and per addition of the K = 4 chain, i.e. within gamma_8 of
-// the real value where the FMA chain is within gamma_3: 5 u A more per component, 8.7 u A in distance; an assumption about
-// the hardware's arithmetic that only the count-for-count tests against the exact kernel back — and taken as the union over
-// the wave's 10 hypotheses.
-//
-// Accumulator layout (32 x 32 tile, 16 registers per lane): lane l holds column l % 32 (a point), rows
-// 8 (v / 4) + 4 (l / 32) + v % 4 for v = 0..15.  Rows are assigned so that the x, y, z of one (hypothesis, point) meet in
-// one lane and two hypotheses share aligned register pairs (packed f32 operations): each half of the wave owns 5
-// hypotheses a..e: v0..5 = ax bx ay by az bz, v6..11 = cx dx cy dy cz dz, v12..14 = ex ey ez, v15 unused.
-typedef float v16f __attribute__((ext_vector_type(16)));
-#ifndef RM_WAVES_VALUE
-#define RM_WAVES_VALUE 8
+#include "ransac_study.hpp"     // the matrix-core scoring variant and the hypothesis probe
 #endif
-constexpr int RM_WAVES = RM_WAVES_VALUE;          // hypothesis groups per workgroup, walking the same points
-constexpr int RM_HPW = 10;           // hypotheses per wave
-constexpr int RM_REC_FLOATS = 1280;  // per record of 4 tiles (128 points): [b0 | b1 | qx | qy | qz][lane][tile] — one 16-B load per lane and array
-constexpr unsigned long long RM_E_OF_V = 0xF444323232101010ull, RM_C_OF_V = 0x0210221100221100ull;   // nibble v: hypothesis a..e, component
-typedef float v4f __attribute__((ext_vector_type(4)));
 
-// B operands as the lanes read them: lane l of tile j holds b0 = (l < 32 ? px : py), b1 = (l < 32 ? pz : 1) of point l % 32, and q of that point
-__global__ void k_pack_pq3(const float* __restrict__ pq, int ns_pad, int n_rec, float* __restrict__ pq3) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;      // (point, half)
-    if (idx >= n_rec * 256) return;
-    const int i = idx >> 1, hf = idx & 1;
-    float px = 0.f, py = 0.f, pz = 0.f, qx = INFINITY, qy = INFINITY, qz = INFINITY;   // padding: never an inlier
-    if (i < ns_pad) { const float* a = pq + (size_t)i * 8; px = a[0]; py = a[1]; pz = a[2]; qx = a[3]; qy = a[4]; qz = a[5]; }
-    float* o = pq3 + (size_t)(i >> 7) * RM_REC_FLOATS + (hf * 32 + (i & 31)) * 4 + ((i >> 5) & 3);
-    o[0] = hf ? py : px; o[256] = hf ? 1.f : pz; o[512] = qx; o[768] = qy; o[1024] = qz;
-}
-
-__global__ __launch_bounds__(64 * RM_WAVES)
-void k_ransac_score_mfma(const float* __restrict__ hyp, int h_pad, const float* __restrict__ pq3, int n_rec, int rec_per_split,
-                         float tau, int* __restrict__ counts, unsigned long long* __restrict__ rescored) {
-    __shared__ float s_hyp[RM_WAVES][RM_HPW][12];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int hf = lane >> 5, col = lane & 31;
-    const int hb = (blockIdx.x * RM_WAVES + wave) * RM_HPW;
-    const int g0 = blockIdx.y * rec_per_split, g1 = min(n_rec, g0 + rec_per_split);
-    // A operand: lane l supplies row l % 32, k = l / 32 (first instruction: k = 0, 1; second: k = 2, 3 with t as column 3)
-    float a0 = 0.f, a1 = 0.f;
-    {
-        const int v = 4 * (col >> 3) + (col & 3), hfrow = (col >> 2) & 1;
-        const int e = (int)((RM_E_OF_V >> (4 * v)) & 15), c = (int)((RM_C_OF_V >> (4 * v)) & 15);
-        const int h = hb + hfrow * 5 + e;
-        if (e < 5 && h < h_pad) { a0 = hyp[(size_t)(c + 3 * hf) * h_pad + h]; a1 = hyp[(size_t)(c + 3 * (hf + 2)) * h_pad + h]; }
-    }
-    for (int idx = lane; idx < RM_HPW * 12; idx += 64) {
-        const int h = idx / 12, e = idx - 12 * h;
-        s_hyp[wave][h][e] = (hb + h < h_pad) ? hyp[(size_t)e * h_pad + hb + h] : __builtin_nanf("");
-    }
-    __syncthreads();
-    // one band for the wave: the union of its hypotheses' bands (a skipped iteration has none; an unbounded one makes every tile exact)
-    float lo = INFINITY, hi = -INFINITY; bool unbounded = false;
-#pragma unroll
-    for (int e = 0; e < 5; ++e) {
-        const int h = hb + hf * 5 + e;
-        if (h < h_pad) {
-            const float mid_h = hyp[(size_t)12 * h_pad + h], half_h = hyp[(size_t)13 * h_pad + h];
-            if (half_h != 0.f) { lo = fminf(lo, mid_h - half_h); hi = fmaxf(hi, mid_h + half_h); unbounded |= half_h != half_h; }
-        }
-    }
-    lo = fminf(lo, __shfl_xor(lo, 32, 64)); hi = fmaxf(hi, __shfl_xor(hi, 32, 64));
-    unbounded = __any(unbounded);
-    float mid = tau, half = 0.f;
-    if (lo <= hi) { mid = 0.5f * (lo + hi); half = 0.5f * (hi - lo) * (1.0f + 1e-5f) + mid * 1e-6f; }
-    if (unbounded) half = __builtin_nanf("");
-    const v2f nmid2 = {-mid, -mid};
-    const float (*rt)[12] = &s_hyp[wave][hf * 5];
-
-    int cnt[5] = {0, 0, 0, 0, 0};
-    unsigned sgn[5] = {0u, 0u, 0u, 0u, 0u};     // signs of d2 - mid, one bit per tile (1 = below mid = inlier), harvested every 32 tiles
-    unsigned n_rescored = 0;
-    const v16f zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-
-    // subtract q, square, classify: 25 vector instructions for the lane's 5 hypotheses x 1 point
-    auto classify = [&](const v16f& d, float b0, float b1, float qx, float qy, float qz) {
-        const v2f q2x = {qx, qx}, q2y = {qy, qy}, q2z = {qz, qz};
-        const v2f dxab = (v2f){d[0], d[1]} - q2x, dyab = (v2f){d[2], d[3]} - q2y, dzab = (v2f){d[4], d[5]} - q2z;
-        const v2f dxcd = (v2f){d[6], d[7]} - q2x, dycd = (v2f){d[8], d[9]} - q2y, dzcd = (v2f){d[10], d[11]} - q2z;
-        const v2f dxye = (v2f){d[12], d[13]} - (v2f){qx, qy};
-        const float dze = d[14] - qz;
-        const v2f tab = fma2(dxab, dxab, fma2(dyab, dyab, fma2(dzab, dzab, nmid2)));
-        const v2f tcd = fma2(dxcd, dxcd, fma2(dycd, dycd, fma2(dzcd, dzcd, nmid2)));
-        const float tee = __builtin_fmaf(dxye.x, dxye.x, __builtin_fmaf(dxye.y, dxye.y, __builtin_fmaf(dze, dze, -mid)));
-        float m = fminf(fminf(fabsf(tab.x), fabsf(tab.y)), fabsf(tee));
-        m = fminf(fminf(m, fabsf(tcd.x)), fabsf(tcd.y));
-        sgn[0] = __builtin_amdgcn_alignbit(sgn[0], __float_as_uint(tab.x), 31);
-        sgn[1] = __builtin_amdgcn_alignbit(sgn[1], __float_as_uint(tab.y), 31);
-        sgn[2] = __builtin_amdgcn_alignbit(sgn[2], __float_as_uint(tcd.x), 31);
-        sgn[3] = __builtin_amdgcn_alignbit(sgn[3], __float_as_uint(tcd.y), 31);
-        sgn[4] = __builtin_amdgcn_alignbit(sgn[4], __float_as_uint(tee), 31);
-        if (__any(!(m >= half))) {     // a test of this tile lies inside the band: the reference arithmetic decides the tile
-            ++n_rescored;
-            const float px = __shfl(b0, col, 64), py = __shfl(b0, col + 32, 64), pz = __shfl(b1, col, 64);
-#pragma unroll
-            for (int e = 0; e < 5; ++e) {
-                const float* r = rt[e];
-                const float x = (r[0] * px + (r[3] * py + r[6] * pz)) + r[9];
-                const float y = (r[1] * px + (r[4] * py + r[7] * pz)) + r[10];
-                const float z = (r[2] * px + (r[5] * py + r[8] * pz)) + r[11];
-                const float dx = x - qx, dy = y - qy, dz = z - qz;
-                const float d2 = dx * dx + (dy * dy + dz * dz);
-                sgn[e] = (sgn[e] & ~1u) | ((d2 < tau) ? 1u : 0u);
-            }
-        }
-    };
-    auto transform = [&](float b0, float b1) {
-        v16f d = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, zero16, 0, 0, 0);
-        return __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, d, 0, 0, 0);
-    };
-    auto load5 = [&](int g, v4f (&r)[5]) {
-        const v4f* __restrict__ rec = reinterpret_cast<const v4f*>(pq3 + (size_t)g * RM_REC_FLOATS) + lane;
-#pragma unroll
-        for (int a = 0; a < 5; ++a) r[a] = rec[a * 64];
-    };
-    if (g0 < g1) {
-        v4f cur[5], nxt[5];
-        load5(g0, cur);
-        int since = 0;
-        for (int g = g0; g < g1; ++g) {
-            load5(min(g + 1, g1 - 1), nxt);       // the next record's operands are in flight while this one is scored
-            // the matrix pipe works on tile j + 1 while the vector pipe classifies tile j
-            v16f dA = transform(cur[0][0], cur[1][0]);
-            v16f dB = transform(cur[0][1], cur[1][1]);
-            classify(dA, cur[0][0], cur[1][0], cur[2][0], cur[3][0], cur[4][0]);
-            dA = transform(cur[0][2], cur[1][2]);
-            classify(dB, cur[0][1], cur[1][1], cur[2][1], cur[3][1], cur[4][1]);
-            dB = transform(cur[0][3], cur[1][3]);
-            classify(dA, cur[0][2], cur[1][2], cur[2][2], cur[3][2], cur[4][2]);
-            classify(dB, cur[0][3], cur[1][3], cur[2][3], cur[3][3], cur[4][3]);
-            if (++since == 8) {
-                since = 0;
-#pragma unroll
-                for (int e = 0; e < 5; ++e) { cnt[e] += __popc(sgn[e]); sgn[e] = 0u; }
-            }
-#pragma unroll
-            for (int a = 0; a < 5; ++a) cur[a] = nxt[a];
-        }
-#pragma unroll
-        for (int e = 0; e < 5; ++e) cnt[e] += __popc(sgn[e]);
-    }
-    // a hypothesis' count: the sum over the 32 lanes (points) of its half
-#pragma unroll
-    for (int e = 0; e < 5; ++e) {
-        int c = cnt[e];
-#pragma unroll
-        for (int off = 16; off > 0; off >>= 1) c += __shfl_xor(c, off, 64);
-        if (col == 0 && hb + hf * 5 + e < h_pad) atomicAdd(&counts[hb + hf * 5 + e], c);
-    }
-    if (n_rescored && lane == 0) atomicAdd(rescored, (unsigned long long)n_rescored);
-}
-
-// error sum of one hypothesis (column-major R in T[0..8], t in T[9..11]) over all points
-#endif  // TDV_STUDY
-
+// error sum of one hypothesis (column-major R in hyp12[0..8], t in hyp12[9..11]) over all points: a slab of (sum, count) per workgroup
 __global__ __launch_bounds__(256)
 void k_ransac_rmse_partial(const float* __restrict__ pq, int ns, const float* __restrict__ hyp12, float tau,
                            double* __restrict__ slabs) {
@@ -1154,385 +990,387 @@ int ransac_score_pose_dev(tdv_ctx* ctx, const float* d_src, int ns, const float*
     return TDV_OK;
 }
 
-int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
-                   const float* d_fs, const float* d_ft, const int* d_corr_in,
-                   float voxel, int max_iterations, float confidence, uint32_t seed,
-                   tdv_ransac_result* out, int* trace_inliers) {
-    if (!ctx || !out || ns < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
-    if (ns > 0 && (!d_src || !d_tgt)) return TDV_ERR_BAD_ARG;
-    if (!d_corr_in && ns > 0 && nt > 0 && (!d_fs || !d_ft)) return TDV_ERR_BAD_ARG;
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    // RegistrationResult defaults (include/registration.hpp:26-30)
+// ------------------------------------------------------------------ the driver
+// RegistrationResult defaults (include/registration.hpp:26-30)
+static void result_defaults(tdv_ransac_result* out) {
     for (int i = 0; i < 16; ++i) out->T[i] = (i % 5 == 0) ? 1.f : 0.f;
     out->fitness = 0.f; out->rmse = 0.f; out->inliers = 0; out->best_iteration = -1; out->iterations_run = 0;
-    if (ns == 0 || nt == 0 || max_iterations == 0) return TDV_OK;  // uniform_int over an empty range is UB in the reference
-    hipStream_t s = ctx->stream;
-    const float thr = voxel * 1.5f;  // registration.cpp:213
-    const float tau = tau_lt(thr);
+}
+// a hypothesis' 12 floats (column-major R, then t) into the column-major 4x4 T, whose last row keeps its defaults
+static void pose_to_T16(const float* h12, float* T) {
+    for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) T[c * 4 + r] = h12[c * 3 + r];
+    T[12] = h12[9]; T[13] = h12[10]; T[14] = h12[11];
+}
 
-    const int* d_corr = d_corr_in;
-    if (!d_corr) {
-        int* c = nullptr;
-        TDV_TRY(ws_alloc(ctx, (size_t)ns, &c));
-        TDV_TRY(feature_match_dev(ctx, d_fs, ns, d_ft, nt, c));
-        d_corr = c;
-    }
-    const int ns_pad = (int)align_up((size_t)ns, (size_t)RS_PCH * 64);
-    float* pq = nullptr;
-    TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 8, &pq));
-    // one device block: [0] bad index flag, [1] largest |source coordinate|, [2..3] rescored chunks, [4..5] scored chunks (u64 each),
-    // [8] the best count known so far, [10..13] and [12+..] the two batch buffers' bail-out plans (4 ints each at [10] and [14]), [16..27] the winning
-    // hypothesis, [32..35] its error sum and inlier count (2 doubles): one memset at the start, one copy back at the end;
-    // [40..43] RansacFinish's loop state (best fitness, its count, its iteration, stopped), [48..55] and [56..63] the two batch buffers' records
-    int* d_bad = nullptr;
-    TDV_TRY(ws_alloc(ctx, 64, &d_bad));
-    unsigned* d_pmax = reinterpret_cast<unsigned*>(d_bad + 1);
-    unsigned long long* d_rescored = reinterpret_cast<unsigned long long*>(d_bad + 2);
-    TDV_HIP(ctx, hipMemsetAsync(d_bad, 0, 256, s));
-    double wave_chunks = 0.0;    // wave x chunk pairs scored by the fast pass in this call
-    k_gather_pq<<<(ns_pad + 255) / 256, 256, 0, s>>>(d_src, d_tgt, d_corr, ns, ns_pad, nt, pq, d_bad, d_pmax);
-    // sqrt(tau) rounded up: the boundary of `d2 < tau` in distance, for the band of the fast scoring pass
-    const float sqrt_tau = std::nextafter((float)std::sqrt((double)tau), INFINITY);
+// A call's device block: one memset at the start, and the part in front of `sel` comes back in one copy at the end.  The pinned
+// host block that copy lands in has the same type; its `bad` (traced calls) and `rec` also receive what a batch reports.
+struct RansacBlock {
+    int bad;                                 // a correspondence index outside [0, nt) was met
+    unsigned pmax;                           // the largest |source coordinate| (bits of a non-negative float)
+    unsigned long long rescored, scored;     // the fast pass' statistics: point pairs scored twice, (wave, chunk) pairs scored
+    int state[2];                            // [0] the best count known so far (RansacPlan)
+    int plan[2][4];                          // per batch buffer: phase-1 chunks, survivors, largest prefix count, chunks per workgroup
+    float best12[12];                        // the winning hypothesis
+    double out2[2];                          // its error sum and inlier count
+    int sel[4];                              // RansacFinish's loop state: best fitness (bits), its count, its iteration, stopped
+    int rec[2][8];                           // per batch buffer: RansacFinish's record (4 ints; moved as 32 bytes under TDV_RANSAC_RECORD=copy)
+};
+constexpr size_t kRansacReadBack = offsetof(RansacBlock, sel);
+static_assert(std::is_trivially_copyable<RansacBlock>::value, "memset, copied back");
+static_assert(offsetof(RansacBlock, rescored) % 8 == 0 && offsetof(RansacBlock, scored) == offsetof(RansacBlock, rescored) + 8, "the kernels index the two as one u64[2]");
+static_assert(offsetof(RansacBlock, out2) % 8 == 0 && offsetof(RansacBlock, out2) + sizeof(double[2]) == kRansacReadBack, "the part read back is a prefix that ends with out2");
+// RansacLeafBound's list lengths per batch buffer; ransac_plan zeroes both of a buffer through &n_live[q]: [0] and [2]
+struct RansacLive { int n_live[2], n_und[2]; };
+static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * sizeof(int), "ransac_plan's n_live[2]");
+
+// Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
+// call (the tests switch them); study_env() is a constant nullptr in the product library.
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, merge, record_copy; int drop_permille; };
+static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
+    RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
-    const bool score_fast = !score_exact_env && ctx->ransac_score_mode != TDV_RANSAC_SCORE_EXACT;
+    k.score_fast = !score_exact_env && ctx->ransac_score_mode != TDV_RANSAC_SCORE_EXACT;
     const bool score_mfma_env = study_env("TDV_RANSAC_SCORE") && !strcmp(study_env("TDV_RANSAC_SCORE"), "mfma");
-    const bool score_mfma = kStudyBuild && score_fast && (score_mfma_env || ctx->ransac_score_mode == TDV_RANSAC_SCORE_MATRIX);   // study build only
+    k.score_mfma = kStudyBuild && k.score_fast && (score_mfma_env || ctx->ransac_score_mode == TDV_RANSAC_SCORE_MATRIX);   // study build only
     static const bool bailout_env_off = getenv("TDV_RANSAC_BAILOUT") && atoi(getenv("TDV_RANSAC_BAILOUT")) == 0;   // A/B knob
-    // RansacPlan; short calls run as one batch without it (C4's 10,000 iterations: a short first batch was tried for them and lost
-    // 2 % - their best fitness is 0.1-0.2, so at most a fifth of the points could be left out)
-    const bool bailout = score_fast && !score_mfma && !trace_inliers && !bailout_env_off && max_iterations > 16384;
-    int* d_state = d_bad + 8;                       // [0] best count known so far
-    int* d_plan[2] = {d_bad + 10, d_bad + 28};   // per batch buffer: phase-1 chunks, survivors, largest prefix count, chunks per workgroup
-    int* d_sel = d_bad + 40;
-    int* d_rec[2] = {d_bad + 48, d_bad + 56};
-    // RansacFinish: the batch's winner is chosen on the device; a traced call needs every count on the host and keeps the host loop
-    const bool device_select = !trace_inliers;
-    // the record reaches the host by the kernel's own stores into pinned memory; TDV_RANSAC_RECORD=copy (study build): by a 32-byte copy
-    const bool record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");
-    const int packed = (uint64_t)ns <= kTriplePackMaxN;      // triples as one 64-bit word each (tdv_internal.hpp: triple_pack)
-    const int drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 100;   // tuning knob (5 to 100 measured equal)
-    const bool merge_on = study_env("TDV_RANSAC_MERGE") && atoi(study_env("TDV_RANSAC_MERGE")) == 1;     // (study build; read per call: the tests switch it)
+    // RansacPlan; short calls run as one batch without it (C4's 10,000 iterations: a short first batch lost 2 % - best fitness 0.1-0.2)
+    k.bailout = k.score_fast && !k.score_mfma && !traced && !bailout_env_off && max_iterations > 16384;
+    k.merge = study_env("TDV_RANSAC_MERGE") && atoi(study_env("TDV_RANSAC_MERGE")) == 1;     // phase 2 rides behind the next batch's phase 1
     // RansacLeafBound: the leaf summary once per call, the bound in front of phase 1 of every batch after the first (whose best is 0)
-    const bool bound_env_off = getenv("TDV_RANSAC_BOUND") && atoi(getenv("TDV_RANSAC_BOUND")) == 0;   // A/B knob (read per call: the tests switch it)
-    const bool bound = bailout && !merge_on && !bound_env_off;
-    const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_lpairs = (n_leaves + 1) / 2;
-    const int n_cleaves = (ns + RL_COARSE - 1) / RL_COARSE, n_cpairs = (n_cleaves + 1) / 2;
-    const bool one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
-    float* leaves = nullptr; float* cleaves = nullptr;
-    if (bound) {
+    const bool bound_env_off = getenv("TDV_RANSAC_BOUND") && atoi(getenv("TDV_RANSAC_BOUND")) == 0;   // A/B knob
+    k.bound = k.bailout && !k.merge && !bound_env_off;
+    k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
+    k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
+    k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 100;   // tuning knob (5 to 100 measured equal)
+    return k;
+}
+
+// One of the two sets of batch buffers: batch k+1 is drawn on the host and enqueued while the GPU scores batch k; results are
+// consumed in iteration order, so the outcome is that of the sequential loop.
+struct RansacBuf {
+    float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the uploaded triples; bail-out: phase 2's list
+    int *live, *und, *acc, *ticket;                   // RansacLeafBound: live list, undecided list, its fine sums and tickets
+    int *plan, *rec, *n_live, *n_und;                 // this buffer's fields of the RansacBlock and of RansacLive
+    void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
+    hipEvent_t ev;                                    // the batch's end
+};
+struct RansacBatch { int q, cnt, it0; bool bounded; };        // buffer q holds cnt hypotheses from iteration it0 on
+struct RangeCut { int per, ranges; };                 // chunks per point range, point ranges
+static RangeCut range_cut(int hb, int n_pchunks) {    // of a dispatch with hb hypothesis blocks (counts are added by atomics: the cut may differ per dispatch)
+    const int per = (n_pchunks + point_ranges(hb, n_pchunks) - 1) / point_ranges(hb, n_pchunks);
+    return RangeCut{per, (n_pchunks + per - 1) / per};
+}
+static int hyp_blocks(int cnt) { return (int)(align_up((size_t)cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK); }
+static int score_grid(int hb, int ps) { return 8 * ((hb + 8 / RS_XCD_R - 1) / (8 / RS_XCD_R)) * ((ps + RS_XCD_R - 1) / RS_XCD_R); }   // k_ransac_score_fast's job-A workgroups
+
+// One call of ransac_run_dev: what its steps share, and the steps in the order a batch takes them.
+struct RansacRun {
+    tdv_ctx* ctx; hipStream_t s; RansacKnobs k;
+    int ns, nt, max_iterations; float confidence; int* trace;
+    float tau, sqrt_tau, band_u;
+    int ns_pad, n_pchunks, batch, first_batch, h_pad, packed, rblocks, n_lpairs = 0, n_cpairs = 0;
+    size_t tri_bytes;                                 // per triple: one packed word or an int4
+    float *pq = nullptr, *pq2 = nullptr, *pq3 = nullptr, *leaves = nullptr, *cleaves = nullptr; double* slabs = nullptr;
+    RansacBlock *d = nullptr, *h = nullptr; RansacLive* lv = nullptr;
+    RansacBuf buf[2] = {};
+    RansacBatch pending = {}; bool has_pending = false;       // merged dispatch (study build): the batch whose phase 2 is not enqueued yet
+    double wave_chunks = 0.0;                         // wave x chunk pairs the call would score without bail-out
+    float best_fitness = 0.f; int best_iter = -1, best_inliers = 0, done_iters = 0; bool stop = false;   // the reference loop's state
+
+    TriView tri(const RansacBuf& B) const { return TriView{B.tri, packed}; }
+    // ---- set-up: pair gather, optional leaf summary, pair packing, the batch buffers
+    int setup(const float* d_src, const float* d_tgt, const int* d_corr) {
+        ns_pad = (int)align_up((size_t)ns, (size_t)RS_PCH * 64);
+        TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 8, &pq)); TDV_TRY(ws_alloc(ctx, 1, &d));
+        TDV_HIP(ctx, hipMemsetAsync(d, 0, sizeof(RansacBlock), s));
+        k_gather_pq<<<(ns_pad + 255) / 256, 256, 0, s>>>(d_src, d_tgt, d_corr, ns, ns_pad, nt, pq, &d->bad, &d->pmax);
+        if (k.bound) TDV_TRY(leaf_summary());
+#ifdef TDV_STUDY
+        if (k.score_mfma) TDV_TRY(mfma_pack(ctx, pq, ns, ns_pad, &pq3));
+        else
+#endif
+        {
+            TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 6, &pq2));
+            k_pack_pq2<<<(ns_pad / 2 + 255) / 256, 256, 0, s>>>(pq, ns_pad, pq2);
+        }
+        TDV_CHECK_LAUNCH(ctx);
+        // batch size: enough hypotheses to fill the chip, bounded for early exit granularity
+        batch = std::min(std::max(max_iterations, 1), 65536);  // per-batch host sync is ~0.3 ms: amortise it
+        first_batch = k.bailout ? 8 * RS_HYP_PER_BLOCK : batch;    // with the bail-out a shorter first batch establishes a best count for the rest
+        h_pad = (int)align_up((size_t)batch, RS_HYP_PER_BLOCK); n_pchunks = ns_pad / RS_PCH;
+        packed = (uint64_t)ns <= kTriplePackMaxN;      // triples as one 64-bit word each (tdv_internal.hpp: triple_pack)
+        tri_bytes = packed ? 8 : 16;
+        for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &B.hyp)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.counts)); TDV_TRY(ws_alloc_bytes(ctx, (size_t)batch * tri_bytes, &B.tri)); }
+        if (k.bailout) for (RansacBuf& B : buf) TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list));
+        if (k.bound) {
+            for (RansacBuf& B : buf) {
+                TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.live)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.und));
+                TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.acc)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad / 64, &B.ticket));
+            }
+            TDV_TRY(ws_alloc(ctx, 1, &lv));
+        }
+        rblocks = (ns + 255) / 256; TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
+        // pinned: the block | 2 x triples | 2 x counts (traced calls only)
+        const size_t sz_blk = align_up(sizeof(RansacBlock), 64), sz_tri = align_up((size_t)batch * tri_bytes, 64), sz_cnt = trace ? align_up((size_t)batch * 4, 64) : 0;
+        TDV_TRY(pin_reserve(ctx, sz_blk + 2 * sz_tri + 2 * sz_cnt));
+        h = reinterpret_cast<RansacBlock*>(ctx->pin); h->bad = 0;
+        if (trace) TDV_HIP(ctx, hipMemcpyAsync(&h->bad, &d->bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts (RansacFinish: the flag comes in the record)
+        for (int q = 0; q < 2; ++q) {
+            RansacBuf& B = buf[q];
+            B.plan = d->plan[q]; B.rec = d->rec[q]; B.n_live = lv ? &lv->n_live[q] : nullptr; B.n_und = lv ? &lv->n_und[q] : nullptr;
+            B.h_tri = ctx->pin + sz_blk + q * sz_tri; B.h_cnt = reinterpret_cast<int*>(ctx->pin + sz_blk + 2 * sz_tri + q * sz_cnt); B.h_rec = h->rec[q];
+        }
+        buf[0].ev = event_acquire(ctx); buf[1].ev = event_acquire(ctx);   // from the ctx's pool: no create/destroy per call
+        if (!buf[0].ev || !buf[1].ev) { release_events(); return TDV_ERR_OOM; }
+        return TDV_OK;
+    }
+    void release_events() { for (RansacBuf& B : buf) event_release(ctx, B.ev); }
+    // RansacLeafBound's summary of the pairs: fine and coarse leaves along the Morton order
+    int leaf_summary() {
+        const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_cleaves = (ns + RL_COARSE - 1) / RL_COARSE;
+        n_lpairs = (n_leaves + 1) / 2; n_cpairs = (n_cleaves + 1) / 2;
         unsigned* enc = nullptr; unsigned long long* keys = nullptr; unsigned* vals = nullptr;
-        TDV_TRY(ws_alloc(ctx, 12, &enc));
-        TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &keys));
-        TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &vals));
-        TDV_TRY(ws_alloc(ctx, (size_t)n_lpairs * 32, &leaves));
-        TDV_TRY(ws_alloc(ctx, (size_t)n_cpairs * 32, &cleaves));
+        TDV_TRY(ws_alloc(ctx, 12, &enc)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &keys)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &vals));
+        TDV_TRY(ws_alloc(ctx, (size_t)n_lpairs * 32, &leaves)); TDV_TRY(ws_alloc(ctx, (size_t)n_cpairs * 32, &cleaves));
         TDV_HIP(ctx, hipMemsetAsync(leaves, 0, (size_t)n_lpairs * 32 * sizeof(float), s));
         TDV_HIP(ctx, hipMemsetAsync(cleaves, 0, (size_t)n_cpairs * 32 * sizeof(float), s));
-        TDV_HIP(ctx, hipMemsetAsync(enc, 0xff, 24, s));
-        TDV_HIP(ctx, hipMemsetAsync(enc + 6, 0, 24, s));
+        TDV_HIP(ctx, hipMemsetAsync(enc, 0xff, 24, s)); TDV_HIP(ctx, hipMemsetAsync(enc + 6, 0, 24, s));
         k_leaf_bounds<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc);
         k_leaf_keys<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc, keys, vals);
         TDV_TRY(radix_sort_pairs_dev(ctx, keys, keys + ns, vals, vals + ns, (size_t)ns, 6 * RL_BITS));
         k_leaf_build<<<(n_leaves * RL_LEAF + 255) / 256, 256, 0, s>>>(pq, ns, vals + ns, leaves, cleaves);
-        TDV_CHECK_LAUNCH(ctx);
+        TDV_CHECK_LAUNCH(ctx); return TDV_OK;
     }
-    float* pq2 = nullptr;
-#ifdef TDV_STUDY
-    float* pq3 = nullptr;
-    const int n_rec = (ns + 127) / 128;
-    if (score_mfma) {
-        TDV_TRY(ws_alloc(ctx, (size_t)n_rec * RM_REC_FLOATS, &pq3));
-        k_pack_pq3<<<n_rec, 256, 0, s>>>(pq, ns_pad, n_rec, pq3);
-    } else
-#endif
-    {
-        TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 6, &pq2));
-        k_pack_pq2<<<(ns_pad / 2 + 255) / 256, 256, 0, s>>>(pq, ns_pad, pq2);
-    }
-    TDV_CHECK_LAUNCH(ctx);
 
-    // batch size: enough hypotheses to fill the chip, bounded for early exit granularity
-    const int batch = std::min(std::max(max_iterations, 1), 65536);  // per-batch host sync is ~0.3 ms: amortise it
-    const int h_pad = (int)align_up((size_t)batch, RS_HYP_PER_BLOCK);
-    const int hblocks = h_pad / RS_HYP_PER_BLOCK;
-    const int n_pchunks = ns_pad / RS_PCH;
-    int want = (RS_WG_TARGET + hblocks - 1) / hblocks;
-    int psplit = std::max(1, std::min(std::min(want, std::max(1, n_pchunks / 32)), 512));
-    int pchunks_per_split = (n_pchunks + psplit - 1) / psplit;
-    psplit = (n_pchunks + pchunks_per_split - 1) / pchunks_per_split;
-
-    // two sets of batch buffers: batch k+1 is prepared on the host (index stream, triple packing) and enqueued while
-    // the GPU scores batch k; results are consumed in iteration order, so the outcome is that of the sequential loop
-    float* hyp[2] = {nullptr, nullptr}; int* counts[2] = {nullptr, nullptr}; void* d_tri[2] = {nullptr, nullptr};
-    double* slabs = nullptr; double* d_out2 = nullptr; float* d_best12 = nullptr;
-    int* d_list[2] = {nullptr, nullptr};
-    int* d_live[2] = {nullptr, nullptr}; int* d_bnd[2] = {nullptr, nullptr}; int* d_und[2] = {nullptr, nullptr}; int* d_nlive = nullptr;
-    int* d_acc[2] = {nullptr, nullptr}; int* d_ticket[2] = {nullptr, nullptr};
-    for (int q = 0; q < 2; ++q) {
-        TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &hyp[q]));
-        TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &counts[q]));
-        TDV_TRY(ws_alloc_bytes(ctx, (size_t)batch * (packed ? 8 : 16), &d_tri[q]));
-    }
-    if (bailout) for (int q = 0; q < 2; ++q) TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_list[q]));   // a batch's list lives until its phase 2 has run, behind the next batch's phase 1
-    if (bound) {
-        for (int q = 0; q < 2; ++q) {
-            TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_live[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_bnd[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_und[q]));
-            TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &d_acc[q])); TDV_TRY(ws_alloc(ctx, (size_t)h_pad / 64, &d_ticket[q]));
-        }
-        TDV_TRY(ws_alloc(ctx, 4, &d_nlive));     // [q]: live hypotheses of batch buffer q, [2 + q]: undecided ones after the coarse level
-    }
-    const int rblocks = (ns + 255) / 256;
-    TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
-    d_best12 = reinterpret_cast<float*>(d_bad + 16);
-    d_out2 = reinterpret_cast<double*>(d_bad + 32);
-    // pinned: 2 x triples (a word or an int4 * batch) | 2 x counts (int * batch, traced calls only) | best12 (12 floats) | out2 (2 doubles) | bad | 2 x record
-    const size_t sz_tri = align_up((size_t)batch * (packed ? 8 : 16), 64), sz_cnt = device_select ? 0 : align_up((size_t)batch * 4, 64);
-    const size_t pin_b12 = 2 * sz_tri + 2 * sz_cnt, pin_bad = pin_b12 + 192, pin_rec = pin_bad + 64, pin_total = pin_rec + 64;   // pin_b12: the 160-byte result block
-    TDV_TRY(pin_reserve(ctx, pin_total));
-    int* h_bad = reinterpret_cast<int*>(ctx->pin + pin_bad);
-    *h_bad = 0;
-    if (!device_select) TDV_HIP(ctx, hipMemcpyAsync(h_bad, d_bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts (RansacFinish: the flag comes in the record)
-    void* h_tri[2] = {ctx->pin, ctx->pin + sz_tri};
-    int* h_cnt[2] = {reinterpret_cast<int*>(ctx->pin + 2 * sz_tri), reinterpret_cast<int*>(ctx->pin + 2 * sz_tri + sz_cnt)};
-    volatile int* h_rec[2] = {reinterpret_cast<int*>(ctx->pin + pin_rec), reinterpret_cast<int*>(ctx->pin + pin_rec + 32)};
-    const int* h_block = reinterpret_cast<const int*>(ctx->pin + pin_b12);      // host copy of d_bad[0..40): same layout
-    const float* h_b12 = reinterpret_cast<const float*>(h_block + 16);
-    const double* h_o2 = reinterpret_cast<const double*>(h_block + 32);
-    hipEvent_t ev[2] = {event_acquire(ctx), event_acquire(ctx)};   // from the ctx's pool: no create/destroy per call
-    if (!ev[0] || !ev[1]) { event_release(ctx, ev[0]); event_release(ctx, ev[1]); return TDV_ERR_OOM; }
-
-    TripleStream stream_idx(seed, (uint64_t)ns);   // sequential over the whole run (registration.cpp:235-239)
-    // with the bail-out a shorter first batch establishes a best count for the rest
-    const int first_batch = bailout ? 8 * RS_HYP_PER_BLOCK : batch;
-    auto prepare = [&](int q, int it0) -> int {    // host: draw + pack the triples of one batch
+    // ---- a batch's steps.  TDV_TIMER_RANSAC_SCORE brackets every dispatch of a scoring kernel on its own.
+    // host: the next cnt triples of the index stream into buffer q (i0, i1, i2, valid: registration.cpp:240)
+    int draw(TripleStream& idx, int q, int it0) {
         const int cnt = std::min(it0 == 0 ? first_batch : batch, max_iterations - it0);
-        if (packed) stream_idx.next_batch_packed(cnt, static_cast<uint64_t*>(h_tri[q]));
-        else stream_idx.next_batch(cnt, static_cast<int*>(h_tri[q]));     // (i0, i1, i2, valid: registration.cpp:240)
+        if (packed) idx.next_batch_packed(cnt, static_cast<uint64_t*>(buf[q].h_tri));
+        else idx.next_batch(cnt, static_cast<int*>(buf[q].h_tri));
         return cnt;
-    };
-    // point ranges of a scoring dispatch with hb hypothesis blocks (counts are accumulated by atomics, so the cut may differ per dispatch)
-    auto score_grid = [](int hb, int ps) { return 8 * ((hb + 8 / RS_XCD_R - 1) / (8 / RS_XCD_R)) * ((ps + RS_XCD_R - 1) / RS_XCD_R); };   // k_ransac_score_fast's job-A workgroups
-    auto ranges_for = [&](int hb) {
-        const int ps = std::max(1, std::min(std::min((RS_WG_TARGET + hb - 1) / hb, std::max(1, n_pchunks / 32)), 512));
-        const int per = (n_pchunks + ps - 1) / ps;
-        return (n_pchunks + per - 1) / per;
-    };
-    int pending = -1, pending_cnt = 0, pending_it0 = 0;   // bail-out: the batch buffer whose phase 2 has not been enqueued yet
-    bool pending_bounded = false;
-    // the end of batch buffer q (cnt hypotheses from iteration it0 on): RansacFinish and its record, or - traced - every count to the host; then the event
-    auto finish = [&](int q, int cnt, int it0, bool use_state, bool bounded) -> int {
-        if (device_select) {
-            const bool live_only = bounded && confidence >= 0.f;      // (see k_ransac_finish)
-            int* rec = record_copy ? d_rec[q] : const_cast<int*>(h_rec[q]);
-            k_ransac_finish<<<1, 1024, 0, s>>>(TriView{d_tri[q], packed}, cnt, counts[q], live_only ? d_live[q] : nullptr, live_only ? d_nlive + q : nullptr,
-                                               hyp[q], h_pad, ns, confidence, it0, use_state ? d_state : nullptr, d_sel, d_best12, d_bad, rec);
-            TDV_CHECK_LAUNCH(ctx);
-            if (record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(h_rec[q]), d_rec[q], 32, hipMemcpyDeviceToHost, s));
-        } else {             // (a traced call runs without bail-out: no state to raise)
-            TDV_HIP(ctx, hipMemcpyAsync(h_cnt[q], counts[q], (size_t)cnt * 4, hipMemcpyDeviceToHost, s));
-        }
-        TDV_HIP(ctx, hipEventRecord(ev[q], s));
+    }
+    // upload and hypotheses; one thread makes the batch's plan from the best count known now: full counts of the batches whose
+    // phase 2 has run, the prefix counts of a pending one (a lower bound of its full counts - a bound is all the rule needs)
+    int hypotheses(const RansacBatch& b) {
+        const RansacBuf& B = buf[b.q];
+        TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
+        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, k.drop_permille, b.bounded ? B.n_live : nullptr};
+        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan);
         return TDV_OK;
-    };
-    // phase 2 of the pending batch (alone, or riding behind job A of the batch in `a`), then its end (finish)
-    auto finish_pending = [&](const ScoreJob* a, int g1) -> int {
-        const int p = pending;
-        const int hbp = (int)(align_up((size_t)pending_cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK);
-        ScoreJob jb{hyp[p], counts[p], d_plan[p], d_list[p], hbp, 0, nullptr};
+    }
+    // every test of the batch, no plan: the exact kernel, the fast one, or (study build) the matrix cores
+    int score_all(const RansacBatch& b) {
+        const RansacBuf& B = buf[b.q]; const int hb = hyp_blocks(b.cnt);
+        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
+#ifdef TDV_STUDY
+        if (k.score_mfma) wave_chunks += mfma_score(s, B.hyp, h_pad, pq3, ns, b.cnt, tau, B.counts, &d->rescored);
+        else
+#endif
+        if (k.score_fast) {
+            const ScoreJob ja{B.hyp, B.counts, nullptr, nullptr, hb, range_cut(hb, n_pchunks).ranges};
+            const int gA = score_grid(hb, ja.ps);
+            k_ransac_score_fast<<<gA, RS_BLOCK, 0, s>>>(ja, ja, gA, h_pad, pq2, n_pchunks, tau, &d->rescored);
+            wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
+        } else {
+            const RangeCut c = range_cut(h_pad / RS_HYP_PER_BLOCK, n_pchunks);
+            k_ransac_score<<<dim3(hb, c.ranges), RS_BLOCK, 0, s>>>(B.hyp, h_pad, pq2, n_pchunks, c.per, tau, B.counts);
+        }
+        return TDV_OK;
+    }
+    // RansacLeafBound: the dead hypotheses out - the batch's live list
+    void bound(const RansacBatch& b) {
+        const RansacBuf& B = buf[b.q]; const int bgrid = (b.cnt + 63) / 64;
+        if (k.one_level)
+            k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
+                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr);
+        else {
+            k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, cleaves, n_cpairs, &d->pmax, sqrt_tau, band_u,
+                                                                      d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket);
+            k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
+                                                                                  d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket);
+        }
+    }
+    ScoreJob job_a(const RansacBatch& b) const { return ScoreJob{buf[b.q].hyp, buf[b.q].counts, buf[b.q].plan, nullptr, hyp_blocks(b.cnt), range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, nullptr}; }
+    // phase 1: the batch's hypotheses (job A) - or, bounded, its live list as a job B, whose workgroups stride over their items: a
+    // grid of job A's size covers them in about one pass whatever the number of live blocks - over the chunks its plan sets
+    void phase1(const RansacBatch& b) {
+        const RansacBuf& B = buf[b.q];
+        const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, ja.hb, 0, B.n_live};
+        const int g1 = score_grid(ja.hb, ja.ps);          // (a multiple of 8: job B's XCD numbering starts there)
+        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
+        if (b.bounded) k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, &d->rescored);
+        else k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(ja, ja, g1, h_pad, pq2, n_pchunks, tau, &d->rescored);
+    }
+    // survivors of the batch: the in-batch bound first (largest prefix count), then the list (bounded: both in one launch over its live list)
+    int select(const RansacBatch& b) {
+        const RansacBuf& B = buf[b.q];
+        if (b.bounded) k_ransac_select_live<<<1, 1024, 0, s>>>(B.live, B.n_live, B.counts, ns, confidence, d->state, B.plan, B.list);
+        else {
+            k_ransac_best<<<(b.cnt + 1023) / 1024, 1024, 0, s>>>(tri(B), b.cnt, B.counts, B.plan + 2);
+            k_ransac_select<<<(b.cnt + 255) / 256, 256, 0, s>>>(tri(B), b.cnt, B.counts, ns, confidence, d->state, B.plan, B.list);
+        }
+        // (merged dispatch only: phase 2 comes a dispatch later, so the prefix counts raise the best for the batch in between)
+        if (k.merge) k_ransac_best<<<(b.cnt + 1023) / 1024, 1024, 0, s>>>(tri(B), b.cnt, B.counts, d->state);
+        wave_chunks += (double)hyp_blocks(b.cnt) * (RS_BLOCK / 64) * (double)n_pchunks;
+        TDV_CHECK_LAUNCH(ctx); return TDV_OK;
+    }
+    // phase 2 of batch b: the hypotheses on its list over the chunks its phase 1 left out - alone, or (merged dispatch) riding as
+    // job B behind the phase 1 `a` of the next batch, g1 workgroups
+    int phase2(const RansacBatch& b, const ScoreJob* a = nullptr, int g1 = 0) {
+        const RansacBuf& B = buf[b.q]; const int hbp = hyp_blocks(b.cnt);
+        const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbp, 0, nullptr};
         // job B's grid: the host knows neither how many hypotheses survived nor how long phase 1 was; its workgroups stride over
         // the (range, block) items, so any multiple of 8 is enough - a quarter of a full grid covers the usual eighth of
         // survivors in one pass, surplus workgroups return at once
-        const int g2 = std::max(8, (hbp * ranges_for(hbp) / 4 + 7) / 8 * 8);
-        {
-            ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-            if (a) k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(*a, jb, g1, h_pad, pq2, n_pchunks, tau, d_rescored);
-            else k_ransac_score_fast<<<g2, RS_BLOCK, 0, s>>>(jb, jb, 0, h_pad, pq2, n_pchunks, tau, d_rescored);
-        }
+        const int g2 = std::max(8, (hbp * range_cut(hbp, n_pchunks).ranges / 4 + 7) / 8 * 8);
+        { ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE); k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(a ? *a : jb, jb, g1, h_pad, pq2, n_pchunks, tau, &d->rescored); }
+        TDV_CHECK_LAUNCH(ctx); return TDV_OK;
+    }
+    // the batch's end: RansacFinish and its record, or - traced - every count to the host; then the event.  with_state: the batch's
+    // largest full count raises state[0] (a batch with bail-out)
+    int finish(const RansacBatch& b, bool with_state) {
+        const RansacBuf& B = buf[b.q];
         TDV_CHECK_LAUNCH(ctx);
-        pending = -1;
-        return finish(p, pending_cnt, pending_it0, true, pending_bounded);
-    };
-    auto enqueue = [&](int q, int cnt, int it0) -> int {     // device: hypotheses + scoring + the batch's end (finish)
-        const bool first = it0 == 0;
-        TDV_HIP(ctx, hipMemcpyAsync(d_tri[q], h_tri[q], (size_t)cnt * (packed ? 8 : 16), hipMemcpyHostToDevice, s));
-        const float band_u = (score_mfma ? 24.f : 16.f) * 5.9604644775390625e-08f;
-        const TriView tri{d_tri[q], packed};
-        const int hb = (int)(align_up((size_t)cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK);
-        const bool bounded = bailout && bound && !first;
-        // the batch's plan is made from the best count known now: full counts of the batches whose phase 2 has run, the prefix
-        // counts of the pending one (a lower bound of its full counts - a bound is all the rule needs)
-        const int ps_plan = ranges_for(hb);
-        const PlanJob plan{d_state, bailout ? d_plan[q] : nullptr, ns, n_pchunks, ps_plan, drop_permille, bounded ? d_nlive + q : nullptr};
-        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri, cnt, h_pad, hyp[q], d_pmax, sqrt_tau, counts[q], band_u, plan);
-        {   // TDV_TIMER_RANSAC_SCORE brackets every dispatch of a scoring kernel on its own
-#ifdef TDV_STUDY
-            if (score_mfma) {
-                ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-                const int groups = (cnt + RM_HPW - 1) / RM_HPW, gblocks = (groups + RM_WAVES - 1) / RM_WAVES;
-                int splits = std::max(1, std::min((16384 + groups - 1) / groups, std::max(1, n_rec / 16)));
-                const int rec_per_split = (n_rec + splits - 1) / splits;
-                splits = (n_rec + rec_per_split - 1) / rec_per_split;
-                k_ransac_score_mfma<<<dim3(gblocks, splits), 64 * RM_WAVES, 0, s>>>(hyp[q], h_pad, pq3, n_rec, rec_per_split, tau, counts[q], d_rescored);
-                wave_chunks += (double)gblocks * RM_WAVES * 4.0 * (double)n_rec;
-            }
-            else
-#endif
-            if (score_fast) {
-                const int ps = ps_plan;
-                if (bailout) {
-                    // One dispatch per batch: its phase 1 (job A) and, behind it, phase 2 of the batch before (job B).
-                    ScoreJob ja{hyp[q], counts[q], d_plan[q], nullptr, hb, ps, nullptr};
-                    const int g1 = score_grid(hb, ps);        // (a multiple of 8: job B's XCD numbering starts there)
-                    if (bounded) {
-                        // RansacLeafBound: the dead hypotheses out, then phase 1 of the live ones as job B (workgroups stride over its
-                        // items; a grid of job A's size covers them in about one pass whatever the number of live blocks)
-                        const int bgrid = (cnt + 63) / 64;
-                        if (one_level)
-                            k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, tri, cnt, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
-                                                                                   d_state, ns, d_bnd[q], d_live[q], d_nlive + q, nullptr, nullptr, nullptr, nullptr);
-                        else {
-                            k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, tri, cnt, cleaves, n_cpairs, d_pmax, sqrt_tau, band_u,
-                                                                                      d_state, ns, d_bnd[q], d_live[q], d_nlive + q, d_und[q], d_nlive + 2 + q,
-                                                                                      d_acc[q], d_ticket[q]);
-                            k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(hyp[q], h_pad, leaves, n_lpairs, d_pmax, sqrt_tau, band_u,
-                                                                                                      d_state, d_bnd[q], d_live[q], d_nlive + q, d_und[q], d_nlive + 2 + q,
-                                                                                                      d_acc[q], d_ticket[q]);
-                        }
-                        ScoreJob jl{hyp[q], counts[q], d_plan[q], d_live[q], hb, 0, d_nlive + q};
-                        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-                        k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, d_rescored);
-                    } else if (pending >= 0) TDV_TRY(finish_pending(&ja, g1));
-                    else {
-                        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-                        k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(ja, ja, g1, h_pad, pq2, n_pchunks, tau, d_rescored);
-                    }
-                    // survivors of this batch: the in-batch bound first (largest prefix count), then the list; the prefix counts
-                    // also raise the best known for the batches after this one
-                    // (a bounded batch: both in one launch over its live list)
-                    if (bounded) k_ransac_select_live<<<1, 1024, 0, s>>>(d_live[q], d_nlive + q, counts[q], ns, confidence, d_state, d_plan[q], d_list[q]);
-                    else {
-                        k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(tri, cnt, counts[q], d_plan[q] + 2);
-                        k_ransac_select<<<(cnt + 255) / 256, 256, 0, s>>>(tri, cnt, counts[q], ns, confidence, d_state, d_plan[q], d_list[q], nullptr);
-                    }
-                    // (merged mode only: phase 2 comes a dispatch later, the prefix counts raise the bound for the batch in between;
-                    //  otherwise the full counts do that right after phase 2)
-                    if (merge_on) k_ransac_best<<<(cnt + 1023) / 1024, 1024, 0, s>>>(tri, cnt, counts[q], d_state);
-                    pending = q; pending_cnt = cnt; pending_it0 = it0; pending_bounded = bounded;
-                    wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
-                    TDV_CHECK_LAUNCH(ctx);
-                    // Phase 2 runs as a dispatch of its own right away.  Letting it ride behind the NEXT batch's phase 1 (TDV_RANSAC_MERGE=1:
-                    // one scoring dispatch per batch, job B of k_ransac_score_fast) was built and measured: the dispatches gain a point
-                    // of lane-op utilisation (0.667 vs 0.660 of the peak on the same box) but a batch's counts then reach the host one
-                    // dispatch later, the host prepares the next index batch with nothing queued behind it, and the call loses 11 %
-                    // end to end (19.0 vs 21.7 M hypotheses/s; profiles/r3/history/ransac_merged_dispatch.md).  Two batches in flight
-                    // (three buffer sets) would hide that for one point of utilisation - not built.
-                    if (!merge_on) return finish_pending(nullptr, 0);
-                    return TDV_OK;                           // counts and event follow with this batch's phase 2 (finish_pending)
-                } else {
-                    ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-                    ScoreJob ja{hyp[q], counts[q], nullptr, nullptr, hb, ps};
-                    const int gA = score_grid(hb, ps);
-                    k_ransac_score_fast<<<gA, RS_BLOCK, 0, s>>>(ja, ja, gA, h_pad, pq2, n_pchunks, tau, d_rescored);
-                }
-                wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
-            }
-            else {
-                ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-                k_ransac_score<<<dim3(hb, psplit), RS_BLOCK, 0, s>>>(hyp[q], h_pad, pq2, n_pchunks, pchunks_per_split, tau, counts[q]);
-            }
-        }
-        TDV_CHECK_LAUNCH(ctx);
-        return finish(q, cnt, it0, false, false);
-    };
+        if (!trace) {
+            const bool live_only = b.bounded && confidence >= 0.f;      // (see k_ransac_finish)
+            int* rec = k.record_copy ? B.rec : const_cast<int*>(B.h_rec);
+            k_ransac_finish<<<1, 1024, 0, s>>>(tri(B), b.cnt, B.counts, live_only ? B.live : nullptr, live_only ? B.n_live : nullptr,
+                                               B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec);
+            TDV_CHECK_LAUNCH(ctx);
+            if (k.record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(B.h_rec), B.rec, sizeof(d->rec[0]), hipMemcpyDeviceToHost, s));
+        } else TDV_HIP(ctx, hipMemcpyAsync(B.h_cnt, B.counts, (size_t)b.cnt * 4, hipMemcpyDeviceToHost, s));
+        TDV_HIP(ctx, hipEventRecord(B.ev, s));
+        return TDV_OK;
+    }
+    // Study build, TDV_RANSAC_MERGE=1: one scoring dispatch per batch - its phase 1 and, behind it, phase 2 of the batch before, whose
+    // end follows.  Measured: a point of lane-op utilisation gained, but the counts reach the host a dispatch later and the call loses
+    // 11 % (profiles/r3/history/ransac_merged_dispatch.md); two batches in flight (three buffer sets) would hide that - not built.
+    int enqueue_merged(const RansacBatch& b) {
+        if (has_pending) {
+            const ScoreJob ja = job_a(b);
+            TDV_TRY(phase2(pending, &ja, score_grid(ja.hb, ja.ps)));
+            TDV_TRY(finish(pending, true));
+        } else phase1(b);
+        TDV_TRY(select(b));
+        pending = b; has_pending = true;
+        return TDV_OK;                           // counts and event follow with this batch's phase 2
+    }
+    int finish_pending() { has_pending = false; TDV_TRY(phase2(pending)); return finish(pending, true); }
 
-    float best_fitness = 0.f; int best_iter = -1, best_inliers = 0; bool stop = false;
-    int done_iters = 0;
-    int status = TDV_OK;
-    int cur = 0, it0 = 0;
-    int cnt_cur = prepare(cur, it0);
-    status = enqueue(cur, cnt_cur, 0);
-    while (status == TDV_OK && cnt_cur > 0 && !stop) {
-        const int nxt = cur ^ 1;
-        const int it_next = it0 + cnt_cur;
-        int cnt_next = 0;
-        if (it_next < max_iterations) {             // overlap: prepare and enqueue the next batch behind the current one
-            cnt_next = prepare(nxt, it_next);
-            status = enqueue(nxt, cnt_next, it_next);         // (with the bail-out this also runs phase 2 of `cur` and sends its counts)
-            if (status != TDV_OK) break;
-        } else if (pending == cur) {                  // last batch: its phase 2 runs alone
-            status = finish_pending(nullptr, 0);
-            if (status != TDV_OK) break;
+    // ---- the device side of one batch: the four paths
+    int enqueue(int q, int cnt, int it0) {
+        const RansacBatch b{q, cnt, it0, k.bound && it0 != 0};
+        TDV_TRY(hypotheses(b));
+        if (!k.bailout) { TDV_TRY(score_all(b)); return finish(b, false); }   // exact, traced, short or matrix-core calls: every test is scored
+        if (k.merge) return enqueue_merged(b);
+        if (b.bounded) bound(b);                             // bail-out with bound: phase 1 over the live list only
+        phase1(b);
+        TDV_TRY(select(b));
+        TDV_TRY(phase2(b));
+        return finish(b, true);
+    }
+
+    // ---- the host side of one batch, after its event
+    // RansacFinish ran the loop of registration.cpp:281-290 on the device: its record
+    void consume_record(const RansacBuf& B, int it0, int cnt) {
+        const int k_best = B.h_rec[0], k_stop = B.h_rec[2];
+        if (k_best >= 0) {
+            best_inliers = B.h_rec[1]; best_iter = it0 + k_best;
+            best_fitness = static_cast<float>(best_inliers) / static_cast<float>((size_t)ns);  // registration.cpp:281
         }
-        if (hipEventSynchronize(ev[cur]) != hipSuccess) { status = TDV_ERR_LAUNCH; break; }
-        if (device_select ? h_rec[cur][3] : *h_bad) { std::snprintf(ctx->err, sizeof(ctx->err), "ransac: a correspondence index lies outside [0, %d)", nt); status = TDV_ERR_BAD_ARG; break; }
+        stop = k_stop >= 0; done_iters = it0 + (stop ? k_stop + 1 : cnt);
+    }
+    // a traced call: the loop itself over the downloaded counts
+    int consume_trace(const RansacBuf& B, int it0, int cnt) {
+        const TriView t{B.h_tri, packed};
         int batch_best = -1;
-        if (device_select) {     // RansacFinish ran the loop below on the device: its record
-            const int k_best = h_rec[cur][0], k_stop = h_rec[cur][2];
-            if (k_best >= 0) {
-                best_inliers = h_rec[cur][1]; best_iter = it0 + k_best;
-                best_fitness = static_cast<float>(best_inliers) / static_cast<float>((size_t)ns);  // registration.cpp:281
-            }
-            stop = k_stop >= 0;
-            done_iters = it0 + (stop ? k_stop + 1 : cnt_cur);
-        } else {
-            const TriView tri{h_tri[cur], packed};
-            for (int k = 0; k < cnt_cur; ++k) {
-                done_iters = it0 + k + 1;
-                if (!tri.valid(k)) { if (trace_inliers) trace_inliers[it0 + k] = -1; continue; }
-                int inl = h_cnt[cur][k];
-                if (trace_inliers) trace_inliers[it0 + k] = inl;
-                float fitness = static_cast<float>(inl) / static_cast<float>((size_t)ns);  // registration.cpp:281
-                if (fitness > best_fitness) { best_fitness = fitness; best_iter = it0 + k; best_inliers = inl; batch_best = k; }
-                if (fitness > confidence) { stop = true; break; }
-            }
+        for (int j = 0; j < cnt; ++j) {
+            done_iters = it0 + j + 1;
+            if (!t.valid(j)) { trace[it0 + j] = -1; continue; }
+            const int inl = trace[it0 + j] = B.h_cnt[j];
+            const float fitness = static_cast<float>(inl) / static_cast<float>((size_t)ns);  // registration.cpp:281
+            if (fitness > best_fitness) { best_fitness = fitness; best_iter = it0 + j; best_inliers = inl; batch_best = j; }
+            if (fitness > confidence) { stop = true; break; }
         }
-        if (batch_best >= 0) {  // keep the winning (R,t) of this batch (hyp[cur] is not overwritten before batch cur+2 is enqueued)
-            hipError_t e = hipMemcpy2DAsync(d_best12, 4, hyp[cur] + batch_best, (size_t)h_pad * 4, 4, 12, hipMemcpyDeviceToDevice, s);
-            if (e != hipSuccess) { status = set_err(ctx, e, "hipMemcpy2DAsync", __LINE__); break; }
+        if (batch_best >= 0)    // keep the winning (R,t) of this batch (its hyp is not overwritten before the batch after the next is enqueued)
+            TDV_HIP(ctx, hipMemcpy2DAsync(d->best12, 4, B.hyp + batch_best, (size_t)h_pad * 4, 4, 12, hipMemcpyDeviceToDevice, s));
+        return TDV_OK;
+    }
+    int loop(uint32_t seed) {
+        TripleStream idx(seed, (uint64_t)ns);   // sequential over the whole run (registration.cpp:235-239)
+        int cur = 0, it0 = 0, cnt_cur = draw(idx, cur, it0);
+        TDV_TRY(enqueue(cur, cnt_cur, 0));
+        while (cnt_cur > 0 && !stop) {
+            const int nxt = cur ^ 1, it_next = it0 + cnt_cur; int cnt_next = 0;
+            if (it_next < max_iterations) {             // overlap: draw and enqueue the next batch behind the current one
+                cnt_next = draw(idx, nxt, it_next);
+                TDV_TRY(enqueue(nxt, cnt_next, it_next));
+            } else if (has_pending) TDV_TRY(finish_pending());      // (merged dispatch) the last batch's phase 2 runs alone
+            const RansacBuf& B = buf[cur];
+            if (hipEventSynchronize(B.ev) != hipSuccess) return TDV_ERR_LAUNCH;
+            if (trace ? h->bad : B.h_rec[3]) { std::snprintf(ctx->err, sizeof(ctx->err), "ransac: a correspondence index lies outside [0, %d)", nt); return TDV_ERR_BAD_ARG; }
+            if (trace) TDV_TRY(consume_trace(B, it0, cnt_cur));
+            else consume_record(B, it0, cnt_cur);
+            cur = nxt; it0 = it_next; cnt_cur = cnt_next;
         }
-        cur = nxt; it0 = it_next; cnt_cur = cnt_next;
+        return TDV_OK;
     }
-    (void)hipStreamSynchronize(s);   // a speculative batch may still be in flight after an early exit
-    ctx->last_ransac_rescore = -1.0; ctx->last_ransac_scored = 1.0;
-    // statistics of the fast pass: (wave, chunk) pairs scored twice / scored (the FMA kernel counts the latter itself: the
-    // bail-out leaves chunks out), and the scored share of all pairs
-    auto stats = [&](const unsigned long long* r) {
-        const double scored = r[1] ? (double)r[1] : wave_chunks;
-        ctx->last_ransac_rescore = (double)r[0] / (scored * (score_mfma ? 1.0 : (double)(RS_PCH / 2)));      // the FMA kernel counts point pairs scored twice, the matrix-core study kernel chunks
-        ctx->last_ransac_scored = scored / wave_chunks;
-    };
-    for (int q = 0; q < 2; ++q) event_release(ctx, ev[q]);
-    if (status != TDV_OK) return status;
-    out->iterations_run = done_iters;
-    // the result block comes back in one copy: winning hypothesis, its error sum and count, the fast pass's statistics
-    const unsigned long long* h_res = reinterpret_cast<const unsigned long long*>(h_block + 2);
-    const bool want_stats = score_fast && wave_chunks > 0.0;
-    if (best_iter < 0 && want_stats) {
-        TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + pin_b12, d_bad, 160, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-    }
-    if (best_iter >= 0) {
-        k_ransac_rmse_partial<<<rblocks, 256, 0, s>>>(pq, ns, d_best12, tau, slabs);
-        k_ransac_rmse_final<<<1, 256, 0, s>>>(slabs, rblocks, d_out2);
-        TDV_CHECK_LAUNCH(ctx);
-        TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + pin_b12, d_bad, 160, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-        if (want_stats) stats(h_res);
-        for (int c = 0; c < 3; ++c) for (int r = 0; r < 3; ++r) out->T[c * 4 + r] = h_b12[c * 3 + r];
-        out->T[12] = h_b12[9]; out->T[13] = h_b12[10]; out->T[14] = h_b12[11];
-        out->fitness = best_fitness;
-        out->inliers = best_inliers;
-        out->best_iteration = best_iter;
+
+    // ---- the result: the winner's rmse, then the block comes back in one copy - winning hypothesis, its error sum and count, the
+    // fast pass' statistics ((wave, chunk) pairs scored twice / scored - the FMA kernel counts the latter itself: the bail-out
+    // leaves chunks out - and the scored share of all pairs)
+    int result(tdv_ransac_result* out) {
+        out->iterations_run = done_iters;
+        const bool want_stats = k.score_fast && wave_chunks > 0.0;
+        if (best_iter >= 0) {
+            k_ransac_rmse_partial<<<rblocks, 256, 0, s>>>(pq, ns, d->best12, tau, slabs);
+            k_ransac_rmse_final<<<1, 256, 0, s>>>(slabs, rblocks, d->out2);
+            TDV_CHECK_LAUNCH(ctx);
+        }
+        if (best_iter >= 0 || want_stats) { TDV_HIP(ctx, hipMemcpyAsync(h, d, kRansacReadBack, hipMemcpyDeviceToHost, s)); TDV_HIP(ctx, hipStreamSynchronize(s)); }
+        if (want_stats) {
+            const double scored = h->scored ? (double)h->scored : wave_chunks;
+            ctx->last_ransac_rescore = (double)h->rescored / (scored * (k.score_mfma ? 1.0 : (double)(RS_PCH / 2)));      // the FMA kernel counts point pairs scored twice, the matrix-core study kernel chunks
+            ctx->last_ransac_scored = scored / wave_chunks;
+        }
+        if (best_iter < 0) return TDV_OK;
+        pose_to_T16(h->best12, out->T);
+        out->fitness = best_fitness; out->inliers = best_inliers; out->best_iteration = best_iter;
         // registration.cpp:282 (float total_error / int inliers)
-        out->rmse = best_inliers > 0 ? std::sqrt((float)h_o2[0] / (float)best_inliers) : 999.0f;
-        if ((int)(h_o2[1] + 0.5) != best_inliers) {
-            snprintf(ctx->err, sizeof(ctx->err), "ransac: rmse pass counted %d inliers, scoring pass %d", (int)(h_o2[1] + 0.5), best_inliers);
+        out->rmse = best_inliers > 0 ? std::sqrt((float)h->out2[0] / (float)best_inliers) : 999.0f;
+        if ((int)(h->out2[1] + 0.5) != best_inliers) {
+            snprintf(ctx->err, sizeof(ctx->err), "ransac: rmse pass counted %d inliers, scoring pass %d", (int)(h->out2[1] + 0.5), best_inliers);
             return TDV_ERR_INTERNAL;
         }
-    } else if (want_stats) {
-        stats(h_res);
+        return TDV_OK;
     }
-    return TDV_OK;
+};
+
+int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, const int* d_corr_in,
+                   float voxel, int max_iterations, float confidence, uint32_t seed, tdv_ransac_result* out, int* trace_inliers) {
+    if (!ctx || !out || ns < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
+    if (ns > 0 && (!d_src || !d_tgt)) return TDV_ERR_BAD_ARG;
+    if (!d_corr_in && ns > 0 && nt > 0 && (!d_fs || !d_ft)) return TDV_ERR_BAD_ARG;
+    TDV_HIP(ctx, hipSetDevice(ctx->device));
+    result_defaults(out);
+    if (ns == 0 || nt == 0 || max_iterations == 0) return TDV_OK;  // uniform_int over an empty range is UB in the reference
+    int* d_match = nullptr;
+    if (!d_corr_in) { TDV_TRY(ws_alloc(ctx, (size_t)ns, &d_match)); TDV_TRY(feature_match_dev(ctx, d_fs, ns, d_ft, nt, d_match)); }
+    const int* d_corr = d_corr_in ? d_corr_in : d_match;
+    RansacRun r;
+    r.ctx = ctx; r.s = ctx->stream; r.k = ransac_knobs(ctx, trace_inliers != nullptr, max_iterations);
+    r.ns = ns; r.nt = nt; r.max_iterations = max_iterations; r.confidence = confidence; r.trace = trace_inliers;
+    r.tau = tau_lt(voxel * 1.5f);  // registration.cpp:213
+    // sqrt(tau) rounded up: the boundary of `d2 < tau` in distance, for the band of the fast scoring pass
+    r.sqrt_tau = std::nextafter((float)std::sqrt((double)r.tau), INFINITY);
+    r.band_u = r.k.score_mfma ? kBandUnitMatrix : kBandUnit;
+    TDV_TRY(r.setup(d_src, d_tgt, d_corr));
+    const int status = r.loop(seed);
+    (void)hipStreamSynchronize(r.s);   // a speculative batch may still be in flight after an early exit
+    ctx->last_ransac_rescore = -1.0; ctx->last_ransac_scored = 1.0;
+    r.release_events();
+    return status != TDV_OK ? status : r.result(out);
 }
 
 
@@ -1594,19 +1432,9 @@ __global__ void k_rb_gather_pq(const float* __restrict__ src, const float* __res
     const int i = pos - pos_off[a], n = off[a + 1] - off[a];
     float4 A, Bq;
     if (i < n) {
-        const size_t P = (size_t)off[a] + i;
-        int c = corr[P];
-        if ((unsigned)c >= (unsigned)nt) { *bad = 1; c = 0; }
-        A = make_float4(src[3 * P], src[3 * P + 1], src[3 * P + 2], tgt[3 * c]);
-        Bq = make_float4(tgt[3 * c + 1], tgt[3 * c + 2], 0.f, 0.f);
-        float am = fmaxf(fabsf(A.x), fmaxf(fabsf(A.y), fabsf(A.z)));
-        if (!(am <= FLT_MAX)) am = INFINITY;
-        if (A.x != A.x || A.y != A.y || A.z != A.z || A.w != A.w || Bq.x != Bq.x || Bq.y != Bq.y) am = INFINITY;      // as k_gather_pq
+        const float am = pair_record(src, tgt, corr, (size_t)off[a] + i, nt, bad, A, Bq);
         if (am > 0.f) atomicMax(&pmax[a], __float_as_uint(am));
-    } else {
-        A = make_float4(0.f, 0.f, 0.f, INFINITY);
-        Bq = make_float4(INFINITY, INFINITY, 0.f, 0.f);
-    }
+    } else pair_record_padding(A, Bq);
     reinterpret_cast<float4*>(pq)[2 * (size_t)pos] = A;
     reinterpret_cast<float4*>(pq)[2 * (size_t)pos + 1] = Bq;
 }
@@ -1637,16 +1465,7 @@ void k_rb_score(const float* __restrict__ hyp, int h_pad, const float* __restric
     unsigned n_rescored = 0;
     const int cnt = score_range_fast<true>(hyp + (size_t)b * 14 * h_pad, h_pad, base, pq2 + (size_t)pos_off[b] * 6, 0, chunks, tau, n_rescored);
     counts[(size_t)b * h_pad + base] = cnt;
-    // statistics only (tdv_ctx_last_ransac_rescore): two atomics per workgroup
-    __shared__ unsigned s_rescored;
-    if (threadIdx.x == 0) s_rescored = 0u;
-    __syncthreads();
-    if (n_rescored && (threadIdx.x & 63) == 0) atomicAdd(&s_rescored, n_rescored);
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        if (s_rescored) atomicAdd(rescored, (unsigned long long)s_rescored);
-        atomicAdd(rescored + 1, (unsigned long long)(RS_BLOCK / 64) * (unsigned long long)chunks);
-    }
+    score_stats(n_rescored, chunks, rescored);
 }
 
 __global__ __launch_bounds__(256)
@@ -1671,19 +1490,17 @@ void k_rb_select(const int* __restrict__ idx, const int* __restrict__ counts, co
     atomicMin(&s_stop, stop);
     __syncthreads();
     const int k_end = s_stop < H ? s_stop + 1 : H;
-    // the first largest fitness among iterations [0, k_end): key = fitness bits (positive floats order as their bits), then
-    // the EARLIEST iteration (largest H - h)
+    // the first largest fitness among iterations [0, k_end) (earlier = H - h)
     unsigned long long best = 0ull;
     for (int h = threadIdx.x; h < k_end; h += 256) {
         const bool valid = !(t[3 * h] == t[3 * h + 1] || t[3 * h + 1] == t[3 * h + 2] || t[3 * h] == t[3 * h + 2]);
         if (!valid) continue;
         const float fit = static_cast<float>(c[h]) / fn;                     // registration.cpp:281
         if (!(fit > 0.f)) continue;                                          // has to beat the initial best fitness 0 (:284)
-        const unsigned long long key = ((unsigned long long)__float_as_uint(fit) << 32) | (unsigned)(H - h);
+        const unsigned long long key = first_best_key(fit, H - h);
         best = key > best ? key : best;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const unsigned long long x = shfl_u64_down(best, o); best = x > best ? x : best; }
+    best = first_best_wave(best);
     if ((threadIdx.x & 63) == 0) s_best[threadIdx.x >> 6] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -1703,10 +1520,7 @@ int ransac_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_off, c
                            float voxel, int max_iterations, float confidence, uint32_t seed, tdv_ransac_result* out, int* fell_back) {
     if (!ctx || !h_off || !d_off || !out || !fell_back || n_clouds < 0 || nt < 0 || max_iterations < 0) return TDV_ERR_BAD_ARG;
     *fell_back = 0;
-    for (int b = 0; b < n_clouds; ++b) {      // RegistrationResult defaults (include/registration.hpp:26-30)
-        for (int i = 0; i < 16; ++i) out[b].T[i] = (i % 5 == 0) ? 1.f : 0.f;
-        out[b].fitness = 0.f; out[b].rmse = 0.f; out[b].inliers = 0; out[b].best_iteration = -1; out[b].iterations_run = 0;
-    }
+    for (int b = 0; b < n_clouds; ++b) result_defaults(&out[b]);
     const int total = n_clouds ? h_off[n_clouds] : 0;
     if (total == 0 || nt == 0 || max_iterations == 0) return TDV_OK;
     if (!d_src || !d_tgt || !d_corr) return TDV_ERR_BAD_ARG;
@@ -1753,7 +1567,7 @@ int ransac_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_off, c
     k_rb_sample<<<n_clouds, 1024, 0, s>>>(d_raw, n_raw, d_off, H, d_idx, d_flags + 1);
     k_rb_gather_pq<<<(total_pos + 255) / 256, 256, 0, s>>>(d_src, d_tgt, d_corr, d_off, d_pos_off, n_clouds, total_pos, nt, pq, d_flags, d_pmax);
     k_pack_pq2<<<(total_pos / 2 + 255) / 256, 256, 0, s>>>(pq, total_pos, pq2);
-    k_rb_hypotheses<<<dim3((h_pad + 255) / 256, n_clouds), 256, 0, s>>>(pq, d_pos_off, d_off, d_idx, H, h_pad, hyp, d_pmax, sqrt_tau, 16.f * 5.9604644775390625e-08f);
+    k_rb_hypotheses<<<dim3((h_pad + 255) / 256, n_clouds), 256, 0, s>>>(pq, d_pos_off, d_off, d_idx, H, h_pad, hyp, d_pmax, sqrt_tau, kBandUnit);
     {
         ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
         k_rb_score<<<dim3(n_clouds, hb), RS_BLOCK, 0, s>>>(hyp, h_pad, pq2, d_pos_off, d_off, tau, counts, d_stats);
@@ -1776,38 +1590,11 @@ int ransac_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_off, c
         const RbResult& r = h_res[b];
         out[b].iterations_run = r.iterations_run;
         if (r.best_iter < 0) continue;
-        for (int c = 0; c < 3; ++c) for (int q = 0; q < 3; ++q) out[b].T[c * 4 + q] = r.T[c * 3 + q];
-        out[b].T[12] = r.T[9]; out[b].T[13] = r.T[10]; out[b].T[14] = r.T[11];
+        pose_to_T16(r.T, out[b].T);
         out[b].inliers = r.inliers; out[b].best_iteration = r.best_iter;
         out[b].fitness = static_cast<float>(r.inliers) / static_cast<float>((size_t)n);
     }
     return TDV_OK;
 }
-
-#ifdef TDV_STUDY
-// ------------------------------------------------------------------ probe (probe.hip: tdv_study_probe, op 10)
-// ransac_hypothesis_lane on n hand-made triples: problem h's three records of d_in are points 3h, 3h + 1, 3h + 2 of a pq array, its
-// lane writes column h of a [14][n] hyp, and rows 0-11 go out as d_out[h][12].  pmax = 0 and sqrt_tau = 1: they enter the band rows only.
-__global__ void k_probe_hypotheses(const float* __restrict__ pq, int n, float* __restrict__ hyp, const unsigned* __restrict__ pmax) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= n) return;
-    ransac_hypothesis_lane(pq, make_int4(3 * h, 3 * h + 1, 3 * h + 2, 1), true, h, n, hyp, pmax, 1.f, 16.f * 5.9604644775390625e-08f);
-}
-__global__ void k_probe_hypotheses_out(const float* __restrict__ hyp, int n, float* __restrict__ out) {
-    const int h = blockIdx.x * blockDim.x + threadIdx.x;
-    if (h >= n) return;
-    for (int k = 0; k < 12; ++k) out[(size_t)h * 12 + k] = hyp[(size_t)k * n + h];
-}
-int probe_hypotheses_dev(tdv_ctx* ctx, int n, const float* d_in, float* d_out) {
-    float* hyp; unsigned* d_pmax;
-    TDV_TRY(ws_alloc(ctx, (size_t)14 * n, &hyp));
-    TDV_TRY(ws_alloc(ctx, 1, &d_pmax));
-    TDV_HIP(ctx, hipMemsetAsync(d_pmax, 0, 4, ctx->stream));
-    k_probe_hypotheses<<<(n + 255) / 256, 256, 0, ctx->stream>>>(d_in, n, hyp, d_pmax);
-    k_probe_hypotheses_out<<<(n + 255) / 256, 256, 0, ctx->stream>>>(hyp, n, d_out);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-#endif  // TDV_STUDY
 
 }  // namespace tdv
