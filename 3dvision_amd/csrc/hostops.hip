@@ -1,6 +1,7 @@
 // Host-side steps that sit directly before / after the GPU path: the ASCII-PLY
 // reference-model loader, the duplicate-pose filter and the mask-directory loader.  Plain C++; no device code.
 #include "tdv_hip.h"
+#include "ransac_cut.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cstdlib>
@@ -89,6 +90,17 @@ int tdv_load_ply_ascii(const char* path, float* out_xyz, float* out_rgb, int cap
     *n_out = n;
     return (n > capacity && (out_xyz || out_rgb)) ? TDV_ERR_BAD_ARG : TDV_OK;
 }
+
+// The cut of k_ransac_score_fast's job B (ransac_cut.hpp), for the CPU suite.
+int tdv_ransac_score_unit(int ticket, int r0, int r1, int xcd, int* c0, int* c1) {
+    if (!c0 || !c1 || xcd < 0 || xcd > 7) return TDV_ERR_BAD_ARG;
+    return tdv::score_unit(ticket, r0, r1, xcd, *c0, *c1) ? 1 : 0;
+}
+int tdv_ransac_score_unit_block(int wg, int visit, int n_blk) {
+    if (wg < 0 || visit < 0 || n_blk < 1) return TDV_ERR_BAD_ARG;
+    return tdv::score_unit_block(wg, visit, n_blk);
+}
+int tdv_ransac_score_unit_chunks(void) { return RS_UNIT; }
 
 }  // extern "C"
 

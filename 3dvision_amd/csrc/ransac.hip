@@ -25,6 +25,7 @@
 //        slabs, then one workgroup over the slabs).
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
+#include "ransac_cut.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -172,13 +173,14 @@ __device__ __forceinline__ void ransac_hypothesis_lane(const float* __restrict__
 // RansacPlan's set-up of a batch (see k_ransac_score_fast and k_ransac_select below), done by one thread of k_ransac_hypotheses:
 // stream order puts the previous batch's final state[0] in front of that kernel, and the bound and scoring kernels that read the
 // plan and append to the zeroed counters come after it.  plan == nullptr: a batch without bail-out.
-struct PlanJob { int* state; int* plan; int ns, n_pchunks, ps, drop_permille; int* n_live; };
+struct PlanJob { int* state; int* plan; int ns, n_pchunks, drop_permille; int* n_live; int* units; int n_units; };   // units: the batch's ticket words (k_ransac_score_fast, job B)
 __device__ __forceinline__ void ransac_plan(const PlanJob& j);
 __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, int count, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
                                     float band_u /* E = band_u (A + s): kBandUnit or kBandUnitMatrix */, const PlanJob plan) {
     int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h == 0 && plan.plan) ransac_plan(plan);
+    if (h < plan.n_units) plan.units[h] = 0;     // job B of this batch's two scoring dispatches draws its units from them (n_units <= h_pad)
     if (h >= h_pad) return;
     counts[h] = 0;                       // the scoring kernel adds its point-splits' counts here (one memset launch less per batch)
     bool valid = false;
@@ -207,9 +209,6 @@ __device__ __forceinline__ unsigned long long first_best_wave(unsigned long long
 #ifndef RS_XCD_R
 #define RS_XCD_R 8           // XCD groups over the point ranges (1, 2, 4 or 8); 8 / RS_XCD_R groups over the hypothesis blocks
 #endif
-#ifndef RS_WG_TARGET
-#define RS_WG_TARGET 6144
-#endif
 constexpr int RS_BLOCK = RS_BLOCK_VALUE;   // 16 waves per workgroup walk the same points together (measured at 200k x 57k hyps: 128 threads 74 %,
                                            // 256 82 %, 512 85 %, 1024 87 % of the VALU peak; 3-12k workgroups make no difference)
 constexpr int RS_HYP_PER_BLOCK = RS_BLOCK;   // one hypothesis per lane (measured best: R,t in 24 VGPRs, highest occupancy)
@@ -217,10 +216,7 @@ constexpr int RS_HYP_PER_BLOCK = RS_BLOCK;   // one hypothesis per lane (measure
 #define RS_PCH_VALUE 8
 #endif
 constexpr int RS_PCH = RS_PCH_VALUE;   // points per scalar chunk: 4 records of 12 floats (8 measured 81 % of peak, 4: 80 %)
-// The point-range cut: into how many ranges a scoring dispatch with hb hypothesis blocks cuts the points, so that it has about
-// RS_WG_TARGET workgroups, of at least 32 chunks each (at least 1: the first term is, whatever hb).  Host (range_cut) and
-// k_ransac_score_fast's job B agree through this one function.
-__host__ __device__ __forceinline__ int point_ranges(int hb, int n_pchunks) { return min(min((RS_WG_TARGET + hb - 1) / hb, max(1, n_pchunks / 32)), 512); }
+// (The cuts of a scoring dispatch - point_ranges for job A, score_unit for job B - are in ransac_cut.hpp.)
 
 // The scoring loop reads a second pair array that holds TWO points per record, component-interleaved
 // [px0 px1 | py0 py1 | pz0 pz1 | qx0 qx1 | qy0 qy1 | qz0 qz1] (48 B per 2 points), so that every arithmetic op is one
@@ -290,17 +286,24 @@ __device__ __forceinline__ v2f fma2(v2f a, v2f b, v2f c) { return __builtin_elem
 //                         same amount of work, whatever the prefix (the first version cut the whole point range and let the
 //                         workgroups past the prefix exit: 3,648 busy workgroups on 512 slots, an eighth of the last round idle);
 //   job B (the ids after): phase 2 of the PREVIOUS batch - the hypotheses its selection listed (plan[1] of them: those that
-//                         can still beat the best count known) over the chunks its phase 1 left out, in ranges of plan[3]
-//                         chunks (= what a job-A workgroup of that batch walked, so all workgroups of a dispatch cost the same).
+//                         can still beat the best count known) over the chunks its phase 1 left out.
 // By default the two jobs are dispatched one after the other (job B alone, see RansacRun::enqueue); with TDV_RANSAC_MERGE=1 job B
 // rides behind the NEXT batch's job A.
 //   job B also scores phase 1 of a batch whose dead hypotheses k_ransac_bound has taken out (RansacLeafBound, below): n_live set,
-//                         the live list (*n_live of them) over the chunks [0, plan[0]) in ranges cut for that many blocks.
+//                         the live list (*n_live of them) over the chunks [0, plan[0]).
+// Job B's workgroups are RESIDENT and pull their work (round 10; until then one (range of 30-155 chunks, block) item each, and per
+// item a gather through the list, 14 strided loads, 1,024 scattered atomics and the statistics' two barriers - which a job-A
+// workgroup of a full batch pays once per 260 chunks): a workgroup holds one hypothesis block in registers and draws units of
+// RS_UNIT chunks of its XCD's share for that block from the block's ticket word (score_unit), the next ticket travelling while a unit
+// is scored; the counts stay in registers until the block's units are drained - one atomicAdd per lane - and the workgroup moves to
+// the next block (score_unit_block), so the tail balances itself.  Tickets only: no workgroup waits for another, any grid of at
+// least 8 workgroups drains any list.  The words are zeroed by the batch's k_ransac_hypotheses.
 struct ScoreJob {
     const float* hyp; int* counts; const int* plan; const int* list;
     int hb;      // hypothesis blocks (A: of the batch; B: upper bound - the real number comes from plan[1] or *n_live)
     int ps;      // A: point ranges
     const int* n_live;   // B: phase 1 over the live list (nullptr: phase 2)
+    int* units;          // B: this dispatch's ticket words, [8 XCDs][hb]
 };
 // One block of hypotheses (lane = hypothesis `base`, -1: none) over the chunks [c0, c1) of the point pairs; returns the lane's
 // inlier count, adds the point PAIRS the wave scored twice to n_rescored (wave-uniform; RS_PCH / 2 per chunk that was re-scored whole).
@@ -310,13 +313,19 @@ struct ScoreJob {
 // ADAPT: a wave that had to re-score three of its first eight chunks stops trying the FMA pass and scores the rest of its range with
 // the reference arithmetic alone (28 ops per test instead of 16.6 + 28: cheaper from a re-scoring share of 0.4 on).  Measured on C5:
 // per-chunk band test 2.30 ms, per-pair band test 2.52 ms (the share stays at 49 % even for 128 tests), adaptive exact: see k_rb_score.
-template <bool ADAPT = false>
-__device__ __forceinline__ int score_range_fast(const float* __restrict__ hyp, const int h_pad, const int base, const float* __restrict__ pq2,
-                                                const int c0, const int c1, const float tau, unsigned& n_rescored) {
-    v2f r[12];
+// A lane's hypothesis in registers: each of the 12 values in both halves of a packed operand, and its band.
+struct HypLane { v2f r[12]; float mid, half; };
+__device__ __forceinline__ HypLane load_hyp(const float* __restrict__ hyp, const int h_pad, const int base, const float tau) {
+    HypLane l;
 #pragma unroll
-    for (int e = 0; e < 12; ++e) { const float t = base >= 0 ? hyp[(size_t)e * h_pad + base] : __builtin_nanf(""); r[e] = (v2f){t, t}; }
-    const float mid = base >= 0 ? hyp[(size_t)12 * h_pad + base] : tau, half = base >= 0 ? hyp[(size_t)13 * h_pad + base] : 0.f;   // a lane without a hypothesis has no band
+    for (int e = 0; e < 12; ++e) { const float t = base >= 0 ? hyp[(size_t)e * h_pad + base] : __builtin_nanf(""); l.r[e] = (v2f){t, t}; }
+    l.mid = base >= 0 ? hyp[(size_t)12 * h_pad + base] : tau; l.half = base >= 0 ? hyp[(size_t)13 * h_pad + base] : 0.f;   // a lane without a hypothesis has no band
+    return l;
+}
+template <bool ADAPT = false>
+__device__ __forceinline__ int score_chunks(const HypLane& l, const float* __restrict__ pq2, const int c0, const int c1, const float tau, unsigned& n_rescored) {
+    const v2f* const r = l.r;
+    const float mid = l.mid, half = l.half;
     const v2f nmid = {-mid, -mid};
     int cnt = 0;
     int c_fast_end = c1;         // ADAPT: where the FMA pass gives up (wave-uniform)
@@ -375,6 +384,29 @@ __device__ __forceinline__ int score_range_fast(const float* __restrict__ hyp, c
     }
     return cnt;
 }
+template <bool ADAPT = false>
+__device__ __forceinline__ int score_range_fast(const float* __restrict__ hyp, const int h_pad, const int base, const float* __restrict__ pq2,
+                                                const int c0, const int c1, const float tau, unsigned& n_rescored) {
+    return score_chunks<ADAPT>(load_hyp(hyp, h_pad, base, tau), pq2, c0, c1, tau, n_rescored);
+}
+// One value from thread 0 to its whole workgroup, as a wave-uniform scalar (job B's tickets).  One barrier per call: s[2] is used in
+// turns (`flip`), and a wave can be at most one call behind thread 0, which writes the other word then.
+__device__ __forceinline__ int workgroup_value(int mine, int* s, int& flip) {
+    if (threadIdx.x == 0) s[flip] = mine;
+    __syncthreads();
+    const int v = __builtin_amdgcn_readfirstlane(s[flip]);
+    flip ^= 1;
+    return v;
+}
+
+// A lane's returning atomicAdd(word, 1) whose result is awaited where it is USED.  The compiler's atomic optimizer turns an add to an
+// address it can prove wave-uniform into a wave reduction and waits for the result right there; behind an offset it cannot see
+// through, the add stays one plain atomic of the calling lane and travels while the lane goes on.
+__device__ __forceinline__ int draw_ticket(int* word) {
+    int zero = 0;
+    asm volatile("" : "+v"(zero));
+    return atomicAdd(word + zero, 1);
+}
 
 // statistics only (tdv_ctx_last_ransac_rescore / _scored): two atomics per workgroup - point pairs scored twice (n_rescored, wave-uniform),
 // and (wave, chunk) pairs scored (chunks, workgroup-uniform); every thread of the workgroup calls it
@@ -423,30 +455,36 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         atomicAdd(&a.counts[base], cnt);
         chunks = (unsigned)(c1 - c0);
     } else {
-        // Few hypothesis blocks are left, and the points reach the scalar cache through the XCD's L2: a workgroup that walks a
-        // point range alone misses on every chunk (measured 1.2 ms for 5 % of the work).  Items (point range, surviving block)
-        // are therefore dealt so that an XCD (workgroup id mod 8) runs ALL surviving blocks of one range next to each other; a
-        // workgroup takes every (job-B workgroups / 8)-th item of its XCD, so any grid of at least 8 workgroups covers any
-        // number of survivors and any prefix.
+        // Few hypothesis blocks are left, and the points reach the scalar cache through the XCD's L2: an XCD (workgroup id mod 8)
+        // walks its own eighth of the chunks for ALL surviving blocks, its workgroups spread over the blocks and advancing through
+        // the share at the same pace (a workgroup that walked a point range alone missed on every chunk: 1.2 ms for 5 % of the work).
         const int n_list = b.n_live ? *b.n_live : b.plan[1];
         const int n_blk = (n_list + RS_BLOCK - 1) / RS_BLOCK;
         if (n_blk == 0) return;
-        const int j0 = id - g1, xcd = j0 & 7, stride = ((int)gridDim.x - g1) >> 3;
-        // phase 2: the chunks [plan[0], n_pchunks) in ranges of plan[3]; phase 1 of the live list: [0, plan[0]) in as many ranges
-        // as a job A of n_blk blocks would cut (point_ranges)
+        const int j0 = id - g1, xcd = j0 & 7, wg = j0 >> 3;
+        // phase 2: the chunks [plan[0], n_pchunks); phase 1 of the live list: [0, plan[0])
         const int r0 = b.n_live ? 0 : b.plan[0], r1 = b.n_live ? b.plan[0] : n_pchunks;
-        const int ps_live = point_ranges(n_blk, n_pchunks);
-        const int per = b.n_live ? max((r1 + ps_live - 1) / ps_live, 1) : max(b.plan[3], 1);
-        const int ranges = (r1 - r0 + per - 1) / per;
-        for (int t = j0 >> 3; ; t += stride) {
-            const int split = (t / n_blk) * 8 + xcd, hblock = t % n_blk;
-            if (split >= ranges) break;                              // workgroup-uniform
-            const int c0 = r0 + split * per, c1 = min(r1, c0 + per);
+        __shared__ int s_ticket[2];
+        int flip = 0;
+        for (int visit = 0; visit < n_blk; ++visit) {
+            const int hblock = score_unit_block(wg, visit, n_blk);
+            int* const word = b.units + (size_t)xcd * b.hb + hblock;
+            int next = 0, c0 = 0, c1 = 0;
+            if (threadIdx.x == 0) next = draw_ticket(word);
+            if (!score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1)) continue;   // drained (workgroup-uniform)
             const int slot = hblock * RS_BLOCK + threadIdx.x;
             const int base = slot < n_list ? b.list[slot] : -1;
-            const int cnt = score_range_fast(b.hyp, h_pad, base, pq2, c0, c1, tau, n_rescored);
+            // a wave whose 64 slots are all past the end of the list has nothing to count: it keeps out of the issue slots of
+            // the waves that do, and only joins the barriers
+            const bool wave_scores = __builtin_amdgcn_readfirstlane(slot - (int)(threadIdx.x & 63)) < n_list;
+            const HypLane l = load_hyp(b.hyp, h_pad, base, tau);
+            int cnt = 0;
+            do {
+                if (threadIdx.x == 0) next = draw_ticket(word);       // in flight while this unit is scored
+                if (wave_scores) cnt += score_chunks(l, pq2, c0, c1, tau, n_rescored);
+                chunks += (unsigned)(c1 - c0);
+            } while (score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1));
             if (base >= 0) atomicAdd(&b.counts[base], cnt);
-            chunks += (unsigned)(c1 - c0);
         }
         if (!chunks) return;
     }
@@ -463,7 +501,7 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
 // Used only when the caller asked for no per-iteration trace.
 // state[0] = best count known so far (a lower bound of the best count of every batch already enqueued: full counts of the
 // batches that are complete, prefix counts of the one whose phase 2 is still to run).  plan = { chunks in phase 1, survivors,
-// largest PREFIX count of this batch, chunks per workgroup } - one plan per batch buffer, the state shared.
+// largest PREFIX count of this batch } - one plan per batch buffer, the state shared.
 // (One thread of k_ransac_hypotheses makes the plan: a launch of its own - one thread behind a stream barrier - cost as much as k_ransac_best.)
 __device__ __forceinline__ void ransac_plan(const PlanJob& j) {
     const int best = j.state[0], ns = j.ns, n_pchunks = j.n_pchunks;
@@ -472,7 +510,7 @@ __device__ __forceinline__ void ransac_plan(const PlanJob& j) {
     const int rest = best - max((int)((long long)best * j.drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
     if (rest >= ns / 8)                                      // (below an eighth of the points a second phase costs more than it saves)
         c_split = min(n_pchunks, (ns - rest + RS_PCH - 1) / RS_PCH);
-    j.plan[0] = c_split; j.plan[1] = 0; j.plan[2] = 0; j.plan[3] = (c_split + j.ps - 1) / j.ps;
+    j.plan[0] = c_split; j.plan[1] = 0; j.plan[2] = 0;
 }
 // largest count of a batch (prefix counts after phase 1, full counts after phase 2) -> *dst by atomic max, one atomic per
 // workgroup (one per wave on the same address cost 12 us for a 65,536-hypothesis batch)
@@ -1009,7 +1047,7 @@ struct RansacBlock {
     unsigned pmax;                           // the largest |source coordinate| (bits of a non-negative float)
     unsigned long long rescored, scored;     // the fast pass' statistics: point pairs scored twice, (wave, chunk) pairs scored
     int state[2];                            // [0] the best count known so far (RansacPlan)
-    int plan[2][4];                          // per batch buffer: phase-1 chunks, survivors, largest prefix count, chunks per workgroup
+    int plan[2][4];                          // per batch buffer: phase-1 chunks, survivors, largest prefix count (one word unused)
     float best12[12];                        // the winning hypothesis
     double out2[2];                          // its error sum and inlier count
     int sel[4];                              // RansacFinish's loop state: best fitness (bits), its count, its iteration, stopped
@@ -1050,6 +1088,7 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
 struct RansacBuf {
     float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the uploaded triples; bail-out: phase 2's list
     int *live, *und, *acc, *ticket;                   // RansacLeafBound: live list, undecided list, its fine sums and tickets
+    int* units;                                       // bail-out: job B's ticket words, [2 phases][8 XCDs][h_pad / RS_BLOCK], zeroed by the batch's k_ransac_hypotheses
     int *plan, *rec, *n_live, *n_und;                 // this buffer's fields of the RansacBlock and of RansacLive
     void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
     hipEvent_t ev;                                    // the batch's end
@@ -1062,13 +1101,17 @@ static RangeCut range_cut(int hb, int n_pchunks) {    // of a dispatch with hb h
 }
 static int hyp_blocks(int cnt) { return (int)(align_up((size_t)cnt, RS_HYP_PER_BLOCK) / RS_HYP_PER_BLOCK); }
 static int score_grid(int hb, int ps) { return 8 * ((hb + 8 / RS_XCD_R - 1) / (8 / RS_XCD_R)) * ((ps + RS_XCD_R - 1) / RS_XCD_R); }   // k_ransac_score_fast's job-A workgroups
+// ... and its job-B workgroups: as many as the device holds at once (two of 16 waves per CU at the kernel's 8 waves per SIMD), a
+// multiple of 8.  Only speed depends on it: the host knows neither how many hypotheses are listed nor how long phase 1 was, and
+// the workgroups pull their units, so any grid of at least 8 drains any list.
+static int unit_grid(int cus) { return std::max(8, (2 * cus + 7) / 8 * 8); }
 
 // One call of ransac_run_dev: what its steps share, and the steps in the order a batch takes them.
 struct RansacRun {
     tdv_ctx* ctx; hipStream_t s; RansacKnobs k;
     int ns, nt, max_iterations; float confidence; int* trace;
     float tau, sqrt_tau, band_u;
-    int ns_pad, n_pchunks, batch, first_batch, h_pad, packed, rblocks, n_lpairs = 0, n_cpairs = 0;
+    int ns_pad, n_pchunks, batch, first_batch, h_pad, packed, rblocks, n_lpairs = 0, n_cpairs = 0, cus = 0;
     size_t tri_bytes;                                 // per triple: one packed word or an int4
     float *pq = nullptr, *pq2 = nullptr, *pq3 = nullptr, *leaves = nullptr, *cleaves = nullptr; double* slabs = nullptr;
     RansacBlock *d = nullptr, *h = nullptr; RansacLive* lv = nullptr;
@@ -1101,7 +1144,10 @@ struct RansacRun {
         packed = (uint64_t)ns <= kTriplePackMaxN;      // triples as one 64-bit word each (tdv_internal.hpp: triple_pack)
         tri_bytes = packed ? 8 : 16;
         for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &B.hyp)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.counts)); TDV_TRY(ws_alloc_bytes(ctx, (size_t)batch * tri_bytes, &B.tri)); }
-        if (k.bailout) for (RansacBuf& B : buf) TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list));
+        if (k.bailout) {
+            for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list)); TDV_TRY(ws_alloc(ctx, (size_t)unit_words(), &B.units)); }
+            TDV_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
+        }
         if (k.bound) {
             for (RansacBuf& B : buf) {
                 TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.live)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.und));
@@ -1124,6 +1170,7 @@ struct RansacRun {
         if (!buf[0].ev || !buf[1].ev) { release_events(); return TDV_ERR_OOM; }
         return TDV_OK;
     }
+    int unit_words() const { return 2 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's
     void release_events() { for (RansacBuf& B : buf) event_release(ctx, B.ev); }
     // RansacLeafBound's summary of the pairs: fine and coarse leaves along the Morton order
     int leaf_summary() {
@@ -1155,7 +1202,7 @@ struct RansacRun {
     int hypotheses(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
         TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
-        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, k.drop_permille, b.bounded ? B.n_live : nullptr};
+        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words() : 0};
         k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan);
         return TDV_OK;
     }
@@ -1168,7 +1215,7 @@ struct RansacRun {
         else
 #endif
         if (k.score_fast) {
-            const ScoreJob ja{B.hyp, B.counts, nullptr, nullptr, hb, range_cut(hb, n_pchunks).ranges};
+            const ScoreJob ja{B.hyp, B.counts, nullptr, nullptr, hb, range_cut(hb, n_pchunks).ranges, nullptr, nullptr};
             const int gA = score_grid(hb, ja.ps);
             k_ransac_score_fast<<<gA, RS_BLOCK, 0, s>>>(ja, ja, gA, h_pad, pq2, n_pchunks, tau, &d->rescored);
             wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
@@ -1191,15 +1238,15 @@ struct RansacRun {
                                                                                   d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket);
         }
     }
-    ScoreJob job_a(const RansacBatch& b) const { return ScoreJob{buf[b.q].hyp, buf[b.q].counts, buf[b.q].plan, nullptr, hyp_blocks(b.cnt), range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, nullptr}; }
-    // phase 1: the batch's hypotheses (job A) - or, bounded, its live list as a job B, whose workgroups stride over their items: a
-    // grid of job A's size covers them in about one pass whatever the number of live blocks - over the chunks its plan sets
+    ScoreJob job_a(const RansacBatch& b) const { return ScoreJob{buf[b.q].hyp, buf[b.q].counts, buf[b.q].plan, nullptr, hyp_blocks(b.cnt), range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, nullptr, nullptr}; }
+    // phase 1: the batch's hypotheses (job A) - or, bounded, its live list as a job B (resident workgroups that pull units) - over
+    // the chunks its plan sets
     void phase1(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
-        const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, ja.hb, 0, B.n_live};
+        const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, h_pad / RS_BLOCK, 0, B.n_live, B.units};
         const int g1 = score_grid(ja.hb, ja.ps);          // (a multiple of 8: job B's XCD numbering starts there)
         ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-        if (b.bounded) k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, &d->rescored);
+        if (b.bounded) k_ransac_score_fast<<<unit_grid(cus), RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, &d->rescored);
         else k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(ja, ja, g1, h_pad, pq2, n_pchunks, tau, &d->rescored);
     }
     // survivors of the batch: the in-batch bound first (largest prefix count), then the list (bounded: both in one launch over its live list)
@@ -1218,12 +1265,9 @@ struct RansacRun {
     // phase 2 of batch b: the hypotheses on its list over the chunks its phase 1 left out - alone, or (merged dispatch) riding as
     // job B behind the phase 1 `a` of the next batch, g1 workgroups
     int phase2(const RansacBatch& b, const ScoreJob* a = nullptr, int g1 = 0) {
-        const RansacBuf& B = buf[b.q]; const int hbp = hyp_blocks(b.cnt);
-        const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbp, 0, nullptr};
-        // job B's grid: the host knows neither how many hypotheses survived nor how long phase 1 was; its workgroups stride over
-        // the (range, block) items, so any multiple of 8 is enough - a quarter of a full grid covers the usual eighth of
-        // survivors in one pass, surplus workgroups return at once
-        const int g2 = std::max(8, (hbp * range_cut(hbp, n_pchunks).ranges / 4 + 7) / 8 * 8);
+        const RansacBuf& B = buf[b.q]; const int hbw = h_pad / RS_BLOCK;
+        const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbw, 0, nullptr, B.units + 8 * hbw};
+        const int g2 = unit_grid(cus);
         { ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE); k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(a ? *a : jb, jb, g1, h_pad, pq2, n_pchunks, tau, &d->rescored); }
         TDV_CHECK_LAUNCH(ctx); return TDV_OK;
     }

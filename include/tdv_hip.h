@@ -855,6 +855,14 @@ int tdv_pose_compose(const float* extrinsics, const float* T, float* out);
  * within min_distance of a kept one is a duplicate and replaces it only if it is closer to the origin.
  * out_poses has room for n poses; *n_out = kept count. */
 int tdv_filter_duplicates(const float* poses, int n, float min_distance, float* out_poses, int* n_out);
+/* Test aids (host only): how the scoring dispatches over a RANSAC batch's live list hand out their work.  The chunks [r0, r1) of the
+ * point pairs go to the eight XCDs in contiguous shares; an XCD's share of one hypothesis block is drawn in units of
+ * tdv_ransac_score_unit_chunks() chunks, ticket by ticket.  tdv_ransac_score_unit: 1 and the unit's chunks [*c0, *c1) for `ticket`
+ * of XCD `xcd` (0..7), 0 when the share has no such unit.  tdv_ransac_score_unit_block: the block that workgroup `wg` of an XCD
+ * takes at its visit-th move (0 <= visit < n_blk) among n_blk blocks.  TDV_ERR_BAD_ARG for arguments outside these ranges. */
+int tdv_ransac_score_unit(int ticket, int r0, int r1, int xcd, int* c0, int* c1);
+int tdv_ransac_score_unit_block(int wg, int visit, int n_blk);
+int tdv_ransac_score_unit_chunks(void);
 /* Registration::loadReferenceModel (src/registration.cpp:416-461): ASCII PLY, x y z [r g b] per vertex.
  * Keeps the reference's behaviour: colours are detected by "red" appearing in any header line and are
  * divided by 255 when r > 1; the header loop consumes the line AFTER end_header, so the first vertex is
