@@ -162,7 +162,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     (void)d_bgr;  // colours do not enter the registration chain (voxelDownsample keeps them, nothing downstream reads them)
     // the model's descriptors are packed once; every instance, on either lane, searches the same read-only index
     FmIndex model_index; bool have_index = false;
-    if (n_model >= 2048 && !getenv("TDV_FM_BRUTE") && !study_env("TDV_FM_KEYORDER")) {
+    if (fm_wants_index(n_model)) {
         TDV_TRY(fm_index_build(ctx, d_model_fpfh, n_model, &model_index));
         have_index = true;
     }
@@ -245,7 +245,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         TDV_TRY(normals_fpfh_dev(c, coherent ? both.first_xyz : vx, v, prm->normals_k, prm->voxel_size * prm->fpfh_radius_factor, nrm, fpfh,
                                  coherent ? both.first2ref : nullptr, coherent ? both.ref2first : nullptr));
         tdv_ransac_result coarse;
-        if (have_index && v >= 4096) TDV_TRY(feature_match_indexed_dev(c, fpfh, v, model_index, corr_stage));
+        if (have_index && fm_indexes_sources(v)) TDV_TRY(feature_match_indexed_dev(c, fpfh, v, model_index, corr_stage));
         else TDV_TRY(feature_match_dev(c, fpfh, v, d_model_fpfh, n_model, corr_stage));
         if (coherent && v > 0) {
             k_gather_i32<<<(v + 255) / 256, 256, 0, c->stream>>>(corr_stage, both.ref2first, v, corr);
@@ -397,7 +397,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     } else {
         TDV_TRY(for_all_instances(stage_features));
     }
-    if (have_index && tv >= 4096) TDV_TRY(feature_match_indexed_dev(ctx, fpfh_all, (int)tv, model_index, corr_all));
+    if (have_index && fm_indexes_sources((int)tv)) TDV_TRY(feature_match_indexed_dev(ctx, fpfh_all, (int)tv, model_index, corr_all));
     else TDV_TRY(feature_match_dev(ctx, fpfh_all, (int)tv, d_model_fpfh, n_model, corr_all));
     // small instances and a small model: all ICP refinements in ONE launch (icp.hip: k_icp_small, a workgroup per instance) after the
     // RANSAC pass - same kernel as the per-instance call, same bits

@@ -2,23 +2,28 @@
 //
 // Replaces the matching loop of Registration::ransacRegistration (/root/reference/src/registration.cpp:216-232):
 // for every source descriptor the target with the smallest 33-D squared distance, accumulated in d order without FMA,
-// strict <, lowest target index on ties.  Three implementations with identical results:
-//   * k_feature_match_scan      the reference's scan (small problems, TDV_FM_BRUTE=1): source descriptors in VGPRs,
-//                               targets broadcast through the scalar data path, 98 VALU ops per pair;
-//   * k_fm_query (default)      exact search over a packed index of the targets (below): STR packing along the
-//                               targets' principal directions, 33-D boxes of 64-row leaves and 4096-row groups;
-//   * k_feature_match_pruned    round 1's pruned scan over a scalar key order (TDV_FM_KEYORDER=1, kept for A/B).
+// strict <, lowest target index on ties.  Which search answers a call (fm_wants_index, fm_indexes_sources):
+//   * fewer than 4,096 sources or 2,048 targets, or TDV_FM_BRUTE set: the reference's scan (k_feature_match_scan) - source
+//     descriptors in VGPRs, targets broadcast through the scalar data path, 98 VALU ops per pair;
+//   * otherwise a packed index of the targets is built (fmatch_index.hip; layouts in fmatch_layout.hpp) and searched
+//     LEAF-MAJOR (k_lm_*, the default): the sources are located and ordered by their home leaf, every source meets its home
+//     leaf, one round of box tests collects the (leaf, source) pairs that are left, and the pairs are evaluated leaf by leaf
+//     with full waves;
+//   * descriptors without structure overflow the leaf-major pair room (and TDV_FM_LEAFMAJOR=0, or more than 16,384 leaves,
+//     skip it): the call then WALKS the same index, one wave per two sources (k_fm_query); what a wave gives up on goes to
+//     8 waves per source pair (k_fm_query_overflow) or, if nearly every box passes, to the plain scan over just those sources.
+// The study build (fmatch_study.hpp) adds the variants that lost their measurement: round 1's key-ordered pruned scan, the
+// walk with 1 or 4 sources per wave, two rounds of box tests, the scan without early exit, and the statistics reports.
 // Every distance that is evaluated is the reference's expression; every target that is not evaluated is excluded by a
 // box lower bound computed with the same expression on the per-dimension gaps (float sub/mul/add are monotone, so
 // lb <= fl(dist) for every row of the box, no margin), or by the tie rule (equal bound, only higher indices inside).
-// The order of rows, the principal directions and the host eigen-solver only decide WHICH rows are looked at first.
 #include "tdv_internal.hpp"
+#include "fmatch_layout.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
 #include <algorithm>
 #include <cstdlib>
-#include <vector>
 
 namespace tdv {
 
@@ -28,7 +33,6 @@ constexpr int FM_SPL = 2;
 #endif
 constexpr int FM_BLOCK = FM_BLOCK_VALUE;
 constexpr int FM_SRC_PER_BLOCK = FM_SPL * FM_BLOCK;
-constexpr int FD = 33;
 constexpr int FM_SEED = 256;   // targets of the seeding launch
 
 // EARLY: partial-distance early exit.  dist accumulates non-negative terms in d order, and fl(a + b) >= a for b >= 0,
@@ -137,67 +141,12 @@ __global__ void k_feature_match_combine(int ns, int ns_pad, int nparts, const fl
     corr[i] = bj;
 }
 
-// ---- exact pruned descriptor match (large problems) -------------------------------------------------------------
-// FPFH descriptors of a real part are strongly clustered (most of their variance lies along one direction), so both
-// sides are ordered by a cheap scalar key (the three centre bins) with a counting sort, 33-D bounding boxes are built
-// over runs of 64 ordered targets, and a wave of neighbouring sources skips every box whose lower bound exceeds all
-// its lanes' current best.  The bound is the distance expression itself applied to the per-dimension gaps, summed in
-// the same order: every term is <= the corresponding term of any target inside the box and float addition /
-// multiplication are monotone, so lb <= fl(dist) holds exactly and no margin is needed.  Targets are visited
-// inside-out from the wave's own key position; ties keep the lowest ORIGINAL target index, as the CPU scan does.
-// The order only affects speed: any key (and the arbitrary order inside a bucket) gives the same correspondences.
-constexpr int FMP_KEY_BITS = 7;                       // bits per key of the 2-D Morton bucket
+// The sources of an indexed call are ordered by a counting sort over buckets of home leaves (a bucket = a leaf up to 16,384 leaves).
+constexpr int FMP_KEY_BITS = 7;
 constexpr int FMP_BUCKETS = 1 << (2 * FMP_KEY_BITS);   // 16384 (64 KB of LDS counters in the ordering kernels)
-#ifdef TDV_STUDY
-constexpr int FMP_BOX = 64;
-constexpr int FMP_TWO_KEYS_MAX_TARGETS = 32768;
-#endif
-
-#ifdef TDV_STUDY
-__device__ __forceinline__ int fm_bucket(const float* __restrict__ f, int two_keys) {
-    // key 1: the three centre bins (descriptors sum to 1, so it lies in [0, 1]); key 2: the first moment of the phi
-    // sub-histogram (in [0, 10]).  two_keys: FMP_KEY_BITS bits each, interleaved (a 128 x 128 Morton grid) — measured
-    // better against a small model (C4: 128k x 9.4k, 0.71 -> 0.60 ms); else key 1 alone at full resolution — better
-    // when the target side is large (100k x 100k: 8.3 vs 9.6 ms).  An offline study on real descriptors
-    // (tools/studies/feature_match_box_pruning.py) put this pair ahead of every other cheap pair.
-    const float c1 = f[5] + (f[16] + f[27]);
-    if (!two_keys) {
-        const float k = c1 * (float)FMP_BUCKETS;
-        return (k == k) ? (int)fminf(fmaxf(k, 0.f), (float)(FMP_BUCKETS - 1)) : 0;
-    }
-    constexpr float LEVELS = (float)(1 << FMP_KEY_BITS);
-    const float k1 = c1 * LEVELS;
-    float k2 = 0.f;
-#pragma unroll
-    for (int b = 1; b < 11; ++b) k2 += (float)b * f[11 + b];
-    k2 *= LEVELS * 0.1f;
-    const unsigned a = (k1 == k1) ? (unsigned)fminf(fmaxf(k1, 0.f), LEVELS - 1.f) : 0u;
-    const unsigned c = (k2 == k2) ? (unsigned)fminf(fmaxf(k2, 0.f), LEVELS - 1.f) : 0u;
-    unsigned m = 0;
-#pragma unroll
-    for (int i = 0; i < FMP_KEY_BITS; ++i) m |= (((a >> i) & 1u) << (2 * i + 1)) | (((c >> i) & 1u) << (2 * i));
-    return (int)m;
-}
-#endif  // TDV_STUDY
 // Real descriptors crowd a few buckets, so both passes count in an LDS histogram first (one global atomic per
 // non-empty bucket and workgroup instead of one per row).
 constexpr int FMP_SORT_BLOCK = 1024;
-#ifdef TDV_STUDY
-__global__ __launch_bounds__(FMP_SORT_BLOCK)
-void k_fm_hist(const float* __restrict__ f, int n, int two_keys, int* __restrict__ bucket_of, int* __restrict__ hist) {
-    __shared__ int h[FMP_BUCKETS];
-    for (int b = threadIdx.x; b < FMP_BUCKETS; b += FMP_SORT_BLOCK) h[b] = 0;
-    __syncthreads();
-    const int i = blockIdx.x * FMP_SORT_BLOCK + threadIdx.x;
-    if (i < n) {
-        const int b = fm_bucket(f + (size_t)i * FD, two_keys);
-        bucket_of[i] = b;
-        atomicAdd(&h[b], 1);
-    }
-    __syncthreads();
-    for (int b = threadIdx.x; b < FMP_BUCKETS; b += FMP_SORT_BLOCK) if (h[b]) atomicAdd(&hist[b], h[b]);
-}
-#endif  // TDV_STUDY
 __global__ __launch_bounds__(FMP_SORT_BLOCK)
 void k_fm_scatter(const int* __restrict__ bucket_of, int n, const int* __restrict__ start, int* __restrict__ cursor,
                   int* __restrict__ perm) {
@@ -212,24 +161,6 @@ void k_fm_scatter(const int* __restrict__ bucket_of, int n, const int* __restric
     __syncthreads();
     if (i < n) perm[start[b] + h[b] + local] = i;   // order inside a bucket is irrelevant to the result
 }
-#ifdef TDV_STUDY
-__global__ void k_fm_gather_targets(const float* __restrict__ ft, const int* __restrict__ perm, int nt, int nt_pad,
-                                    float* __restrict__ T, int* __restrict__ torig) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)nt_pad * FD) return;
-    const int row = (int)(e / FD), d = (int)(e % FD);
-    T[e] = row < nt ? ft[(size_t)perm[row] * FD + d] : INFINITY;   // padding rows: distance +inf, never chosen
-    if (d == 0) torig[row] = row < nt ? perm[row] : INT_MAX;
-}
-__global__ void k_fm_boxes(const float* __restrict__ T, int nt, int nbox, float* __restrict__ bmin, float* __restrict__ bmax) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nbox * FD) return;
-    const int b = e / FD, d = e % FD;
-    float mn = INFINITY, mx = -INFINITY;
-    for (int r = b * FMP_BOX; r < min(nt, (b + 1) * FMP_BOX); ++r) { float v = T[(size_t)r * FD + d]; mn = fminf(mn, v); mx = fmaxf(mx, v); }
-    bmin[e] = mn; bmax[e] = mx;
-}
-#endif  // TDV_STUDY
 
 // The set bit of m nearest to position c, the higher one on a tie (the inside-out order c, c+1, c-1, c+2, ... restricted to
 // the set bits), or -1: two shifts, a find-first and a count-leading on the wave's scalar unit instead of walking the
@@ -243,415 +174,9 @@ __device__ __forceinline__ int nearest_set_bit(unsigned long long m, int c) {
     return du <= dd ? c + du : c - dd;
 }
 
-// box visited at position v of the inside-out order centred at box c (bijection onto [0, nbox))
-__device__ __forceinline__ int visit_inside_out(int v, int c, int nbox) {
-    const int L = c, R = nbox - 1 - c;
-    const int m = min(L, R);
-    if (v <= 2 * m) { int k = (v + 1) >> 1; return (v & 1) ? c + k : c - k; }
-    return R > L ? c + (v - m) : c - (v - m);
-}
-
-#ifdef TDV_STUDY
-template <int SPL>
-__global__ __launch_bounds__(FM_BLOCK)
-void k_feature_match_pruned(const float* __restrict__ fs, const int* __restrict__ sperm, int ns, int ns_pad,
-                            const float* __restrict__ T, const int* __restrict__ torig, int nbox,
-                            const float* __restrict__ bmin, const float* __restrict__ bmax, const int* __restrict__ tstart,
-                            int two_keys, int nsplit, float* __restrict__ pd, int* __restrict__ pj) {
-    const int split = blockIdx.y;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int wbase = (blockIdx.x * (FM_BLOCK / 64) + wave) * (64 * SPL);   // the wave's 64*SPL consecutive ordered sources
-    float f[SPL][FD];
-    float best[SPL]; int bj[SPL]; int src[SPL];
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-        const int t = wbase + s * 64 + lane;
-        const int i = sperm[min(t, ns - 1)];
-        src[s] = t < ns ? i : -1;   // padding lanes duplicate the last source and write nothing
-#pragma unroll
-        for (int d = 0; d < FD; ++d) f[s][d] = fs[(size_t)i * FD + d];
-        best[s] = INFINITY; bj[s] = INT_MAX;
-    }
-    // start where the targets with the wave's own key begin
-    const int c = min(nbox - 1, tstart[__builtin_amdgcn_readfirstlane(fm_bucket(f[0], two_keys))] / FMP_BOX);
-    for (int v = split; v < nbox; v += nsplit) {
-        const int b = visit_inside_out(v, c, nbox);
-        const float* __restrict__ lo = bmin + (size_t)b * FD;   // wave-uniform -> scalar loads
-        const float* __restrict__ hi = bmax + (size_t)b * FD;
-        float lb[SPL];
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) lb[s] = 0.f;
-#pragma unroll
-        for (int d = 0; d < FD; ++d) {
-            const float l = lo[d], h = hi[d];
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) { float g = fmaxf(fmaxf(l - f[s][d], f[s][d] - h), 0.f); lb[s] += g * g; }
-        }
-        bool alive = false;
-#pragma unroll
-        for (int s = 0; s < SPL; ++s) alive = alive || (lb[s] <= best[s]);   // <=: an equal distance with a lower index still wins
-        if (!__any(alive)) continue;
-#pragma unroll 1
-        for (int t = 0; t < FMP_BOX; ++t) {
-            const int j = b * FMP_BOX + t;
-            const float* __restrict__ g = T + (size_t)j * FD;
-            const int o = torig[j];
-            float q[FD];
-#pragma unroll
-            for (int d = 0; d < FD; ++d) q[d] = g[d];
-#pragma unroll
-            for (int s = 0; s < SPL; ++s) {
-                float dist = 0.f;
-#pragma unroll
-                for (int d = 0; d < FD; ++d) { float diff = f[s][d] - q[d]; dist += diff * diff; }
-                const bool take = dist < best[s] || (dist == best[s] && o < bj[s]);
-                best[s] = take ? dist : best[s];
-                bj[s] = take ? o : bj[s];
-            }
-        }
-    }
-#pragma unroll
-    for (int s = 0; s < SPL; ++s) {
-        if (src[s] < 0) continue;
-        const size_t o = (size_t)split * ns_pad + src[s];
-        pd[o] = best[s]; pj[o] = bj[s];
-    }
-}
-
-// partials of the pruned match: lexicographic (distance, original index) minimum, order-independent
-__global__ void k_feature_match_combine_lex(int ns, int ns_pad, int nparts, const float* __restrict__ pd,
-                                            const int* __restrict__ pj, int* __restrict__ corr) {
-    int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= ns) return;
-    float best = INFINITY; int bj = INT_MAX;
-    for (int s = 0; s < nparts; ++s) {
-        const float d = pd[(size_t)s * ns_pad + i]; const int j = pj[(size_t)s * ns_pad + i];
-        if (d < best || (d == best && j < bj)) { best = d; bj = j; }
-    }
-    corr[i] = bj == INT_MAX ? 0 : bj;   // nothing finite: the CPU loop keeps its initial index 0
-}
-#endif  // TDV_STUDY
-
-namespace {
-#ifdef TDV_STUDY
-// counting sort of n descriptors by key bucket: perm (ordered position -> row) and, optionally, the bucket starts
-int fm_order(tdv_ctx* ctx, const float* d_f, int n, int two_keys, int* perm, int* start /* FMP_BUCKETS + 1 */) {
-    hipStream_t s = ctx->stream;
-    int *hist, *cursor, *d_total, *bucket_of;
-    TDV_TRY(ws_alloc(ctx, (size_t)FMP_BUCKETS, &hist));
-    TDV_TRY(ws_alloc(ctx, (size_t)FMP_BUCKETS, &cursor));
-    TDV_TRY(ws_alloc(ctx, 1, &d_total));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &bucket_of));
-    TDV_HIP(ctx, hipMemsetAsync(hist, 0, (size_t)FMP_BUCKETS * 4, s));
-    TDV_HIP(ctx, hipMemsetAsync(cursor, 0, (size_t)FMP_BUCKETS * 4, s));
-    const int blocks = (n + FMP_SORT_BLOCK - 1) / FMP_SORT_BLOCK;
-    k_fm_hist<<<blocks, FMP_SORT_BLOCK, 0, s>>>(d_f, n, two_keys, bucket_of, hist);
-    TDV_TRY(exclusive_scan_dev(ctx, hist, FMP_BUCKETS, start, d_total));
-    k_fm_scatter<<<blocks, FMP_SORT_BLOCK, 0, s>>>(bucket_of, n, start, cursor, perm);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-#endif  // TDV_STUDY
-
-#ifdef TDV_STUDY
-constexpr int FMP_SPL = 1;   // 1 measured better than 2 (C4: 0.84 vs 0.93 ms)
-int feature_match_keyorder_dev(tdv_ctx* ctx, const float* d_fs, int ns, const float* d_ft, int nt, int* d_corr) {
-    hipStream_t s = ctx->stream;
-    const int nt_pad = (int)align_up((size_t)nt, FMP_BOX);
-    const int nbox = nt_pad / FMP_BOX;
-    constexpr int SRC_PER_BLOCK = FM_BLOCK * FMP_SPL;
-    const int ns_pad = (int)align_up((size_t)ns, SRC_PER_BLOCK);
-    const int blocks_x = ns_pad / SRC_PER_BLOCK;
-    int want = (4096 + blocks_x - 1) / blocks_x;
-    const int nsplit = std::max(1, std::min(std::min(want, std::max(1, nbox / 8)), 32));
-    int *sperm, *tperm, *tstart, *sstart, *torig; float *T, *bmin, *bmax, *pd; int* pj;
-    TDV_TRY(ws_alloc(ctx, (size_t)ns, &sperm));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &tperm));
-    TDV_TRY(ws_alloc(ctx, (size_t)FMP_BUCKETS + 1, &tstart));
-    TDV_TRY(ws_alloc(ctx, (size_t)FMP_BUCKETS + 1, &sstart));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt_pad, &torig));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt_pad * FD, &T));
-    TDV_TRY(ws_alloc(ctx, (size_t)nbox * FD, &bmin));
-    TDV_TRY(ws_alloc(ctx, (size_t)nbox * FD, &bmax));
-    TDV_TRY(ws_alloc(ctx, (size_t)nsplit * ns_pad, &pd));
-    TDV_TRY(ws_alloc(ctx, (size_t)nsplit * ns_pad, &pj));
-    ScopedTimer tm(ctx, TDV_TIMER_FEATURE_MATCH);
-    const int two_keys = nt <= FMP_TWO_KEYS_MAX_TARGETS ? 1 : 0;
-    TDV_TRY(fm_order(ctx, d_ft, nt, two_keys, tperm, tstart));
-    TDV_TRY(fm_order(ctx, d_fs, ns, two_keys, sperm, sstart));
-    k_fm_gather_targets<<<(unsigned)(((size_t)nt_pad * FD + 255) / 256), 256, 0, s>>>(d_ft, tperm, nt, nt_pad, T, torig);
-    k_fm_boxes<<<(nbox * FD + 255) / 256, 256, 0, s>>>(T, nt, nbox, bmin, bmax);
-    k_feature_match_pruned<FMP_SPL><<<dim3(blocks_x, nsplit), FM_BLOCK, 0, s>>>(d_fs, sperm, ns, ns_pad, T, torig, nbox, bmin, bmax, tstart,
-                                                                               two_keys, nsplit, pd, pj);
-    k_feature_match_combine_lex<<<(ns + 255) / 256, 256, 0, s>>>(ns, ns_pad, nsplit, pd, pj, d_corr);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-#endif  // TDV_STUDY
-}  // namespace
-
-// ---- packed target index -----------------------------------------------------------------------------------------
-// FPFH descriptors of a surface live close to a 3-D manifold of R^33 (96 % of their variance in three principal
-// directions on the relief part).  The targets are therefore packed sort-tile-recursive along those directions:
-// equal-count slabs along p0, equal-count columns along p1 inside every slab, rows sorted along p2 inside every column
-// (two full sorts of 16-B records and one segmented sort inside the columns; slab / column counts proportional to the spread, chosen on the host from the
-// eigenvalues).  Columns are padded to a multiple of 64 rows (+inf rows that never win), so a leaf = 64 consecutive
-// rows never straddles two columns; group = 64 consecutive leaves.  Offline study on real descriptors
-// (tools/studies/feature_match_pca_tree.py): a wave of 64 neighbouring sources has to open 2.3 % of the leaves with
-// this packing against 17.8 % with round 1's scalar key.
-constexpr int FX_LEAF = 64;
-constexpr int FX_GROUP = 64;          // leaves per group
-constexpr int FX_MAX_S = 64;          // slabs / columns per slab at most
-constexpr int FX_NMOM = 561 + 33;     // upper triangle of sum f f^T, then sum f
 #ifndef FMQ_WAVES_PER_SIMD
 #define FMQ_WAVES_PER_SIMD 4
 #endif
-
-__device__ __forceinline__ unsigned sortable_bits(float v) {   // ascending float order as ascending unsigned order; NaN last
-    if (v != v) return 0xffffffffu;
-    unsigned u = __float_as_uint(v);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
-// raw moments of the rows, per workgroup, in double; fixed order (deterministic basis -> deterministic packing)
-constexpr int FX_MOM_BLOCK = 640;
-constexpr int FX_MOM_TILE = 32;
-__global__ __launch_bounds__(FX_MOM_BLOCK)
-void k_fm_moments(const float* __restrict__ f, int n, int rows_per_block, double* __restrict__ partial) {
-    __shared__ float tile[FX_MOM_TILE][FD + 1];
-    const int t = threadIdx.x;
-    int a = 0, b = 0;   // thread t < 561: pair (a <= b); 561 <= t < 594: column sum
-    if (t < 561) { int r = t; a = 0; while (r >= FD - a) { r -= FD - a; ++a; } b = a + r; }
-    const int r0 = blockIdx.x * rows_per_block, r1 = min(n, r0 + rows_per_block);
-    double acc = 0.0;
-    for (int base = r0; base < r1; base += FX_MOM_TILE) {
-        const int m = min(FX_MOM_TILE, r1 - base);
-        for (int e = t; e < m * FD; e += FX_MOM_BLOCK) tile[e / FD][e % FD] = f[(size_t)base * FD + e];
-        __syncthreads();
-        if (t < 561) { for (int r = 0; r < m; ++r) acc += (double)tile[r][a] * (double)tile[r][b]; }
-        else if (t < FX_NMOM) { for (int r = 0; r < m; ++r) acc += (double)tile[r][t - 561]; }
-        __syncthreads();
-    }
-    if (t < FX_NMOM) partial[(size_t)blockIdx.x * FX_NMOM + t] = acc;
-}
-// one wave per moment: the workgroups' partial sums in a fixed order (lane l takes blocks l, l + 64, ...; then a fixed tree)
-__global__ __launch_bounds__(64)
-void k_fm_moments_fold(const double* __restrict__ partial, int nblocks, double* __restrict__ out) {
-    const int t = blockIdx.x;
-    double s = 0.0;
-    for (int b = threadIdx.x; b < nblocks; b += 64) s += partial[(size_t)b * FX_NMOM + t];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
-    if (threadIdx.x == 0) out[t] = s;
-}
-
-// Principal coordinates p_r(x) = sum_d (x_d - mean_d) * b_r[d], r = 0..2, as evaluated HERE (plain f32, d ascending):
-// the one routine both sides use.  *amax receives (integer atomic max on the bits of a non-negative float) the largest
-// |x_d - mean_d| seen, +inf for non-finite input: it scales the rounding margin of the principal-direction boxes.
-// basis: [3][33] directions, then mean[33]
-__device__ __forceinline__ void principal_coords(const float* __restrict__ x, const float* __restrict__ basis, float& a0, float& a1, float& a2, float& am) {
-    a0 = 0.f; a1 = 0.f; a2 = 0.f; am = 0.f;
-#pragma unroll
-    for (int d = 0; d < FD; ++d) {
-        const float v = x[d] - basis[3 * FD + d];
-        a0 += v * basis[d]; a1 += v * basis[FD + d]; a2 += v * basis[2 * FD + d];
-        const float av = fabsf(v);
-        am = (av <= am) ? am : av;          // NaN: the comparison is false -> am = NaN, mapped to +inf below
-    }
-    if (!(am <= FLT_MAX)) am = INFINITY;
-}
-__global__ void k_fm_project(const float* __restrict__ f, int n, const float* __restrict__ basis, float* __restrict__ p0,
-                             float* __restrict__ p1, float* __restrict__ p2, unsigned* __restrict__ amax) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    float a0 = 0.f, a1 = 0.f, a2 = 0.f, am = 0.f;
-    if (i < n) { principal_coords(f + (size_t)i * FD, basis, a0, a1, a2, am); p0[i] = a0; p1[i] = a1; p2[i] = a2; }
-    __shared__ unsigned s_max;
-    if (threadIdx.x == 0) s_max = 0u;
-    __syncthreads();
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) am = fmaxf(am, __shfl_xor(am, off, 64));
-    if ((threadIdx.x & 63) == 0) atomicMax(&s_max, __float_as_uint(am));
-    __syncthreads();
-    if (threadIdx.x == 0) atomicMax(amax, s_max);
-}
-
-// Bit-identical target rows (the descriptor of a flat patch: a quarter of the relief model's rows are two such values)
-// give bit-identical distances, and the tie rule hands the match to the lowest index among them: only that row can ever
-// win, so the packed index holds it alone.  Without this every source on such a plateau has to open every leaf holding
-// a copy.  Two levels of open addressing keyed by a hash of the row's bits, rows always compared in full (a hash
-// collision costs a probe, never a row): a workgroup first folds its own 512 rows in LDS - a popular value would
-// otherwise queue tens of thousands of atomics on one L2 address - and only the lowest row of every value it holds
-// goes to the global table.  After the kernel table[slot_of[i]] == i exactly for the lowest row of every distinct value.
-constexpr int FX_DD_ROWS = 512;
-constexpr int FX_DD_SLOTS = 1024;
-__device__ __forceinline__ unsigned row_hash(const float* x) {
-    unsigned h = 0x9e3779b9u;
-#pragma unroll
-    for (int d = 0; d < FD; ++d) { h ^= __float_as_uint(x[d]); h *= 0x85ebca6bu; h ^= h >> 13; }
-    h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
-__global__ __launch_bounds__(FX_DD_ROWS)
-void k_fm_dedupe_insert(const float* __restrict__ f, int n, int* table, unsigned mask, int* __restrict__ slot_of, int* __restrict__ kept) {
-    __shared__ float tile[FX_DD_ROWS * FD];          // row-major, stride 33 dwords: lanes = consecutive rows hit distinct banks
-    __shared__ int ltab[FX_DD_SLOTS], lres[FX_DD_SLOTS];
-    __shared__ int claimed;
-    const int t = threadIdx.x, base = blockIdx.x * FX_DD_ROWS, m = min(FX_DD_ROWS, n - base);
-    for (int e = t; e < m * FD; e += FX_DD_ROWS) tile[e] = f[(size_t)base * FD + e];
-    for (int e = t; e < FX_DD_SLOTS; e += FX_DD_ROWS) ltab[e] = -1;
-    if (t == 0) claimed = 0;
-    __syncthreads();
-    const float* x = tile + t * FD;
-    unsigned h = 0, ls = 0;
-    if (t < m) {
-        h = row_hash(x);
-        ls = h & (FX_DD_SLOTS - 1);
-        for (;;) {
-            int cur = atomicCAS(&ltab[ls], -1, t);
-            if (cur < 0) break;
-            const float* y = tile + cur * FD;
-            bool same = true;
-#pragma unroll
-            for (int d = 0; d < FD; ++d) same = same && (__float_as_uint(x[d]) == __float_as_uint(y[d]));
-            if (same) { if (t < cur) atomicMin(&ltab[ls], t); break; }
-            ls = (ls + 1) & (FX_DD_SLOTS - 1);       // half full at most: the probe ends
-        }
-    }
-    __syncthreads();
-    bool claim = false;
-    if (t < m && ltab[ls] == t) {                    // lowest row of its value in this workgroup
-        const int i = base + t;
-        unsigned slot = h & mask;
-        for (;;) {
-            // plain load: a stale owner is still a row with the slot's value, a stale "empty" is corrected by the CAS
-            int cur = table[slot];
-            if (cur < 0) { cur = atomicCAS(&table[slot], -1, i); if (cur < 0) { claim = true; break; } }
-            const float* y = f + (size_t)cur * FD;
-            bool same = true;
-#pragma unroll
-            for (int d = 0; d < FD; ++d) same = same && (__float_as_uint(x[d]) == __float_as_uint(y[d]));
-            if (same) { if (i < cur) atomicMin(&table[slot], i); break; }
-            slot = (slot + 1) & mask;
-        }
-        lres[ls] = (int)slot;
-    }
-    // every distinct value claims exactly one empty slot of the global table: the claims count the rows that stay
-    const unsigned long long cm = __ballot(claim);
-    if ((t & 63) == 0 && cm) atomicAdd(&claimed, __popcll(cm));
-    __syncthreads();
-    if (t < m) slot_of[base + t] = lres[ls];
-    if (t == 0 && claimed) atomicAdd(kept, claimed);
-}
-
-// first key: p0 of the rows that stay; the others sort behind every real row together with the padding
-// Keys of the three sorts of the packing.  The first two are stable radix sorts of (key, row) pairs: rows enter in index order,
-// so equal keys keep the lower row first.
-__global__ void k_fm_key_p0(const float* __restrict__ p0, int n, const int* __restrict__ table, const int* __restrict__ slot_of,
-                            unsigned long long* __restrict__ key, unsigned* __restrict__ row) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const bool keep = table[slot_of[i]] == i;             // a bit-identical copy of an earlier row stays out of the index: it sorts last
-    key[i] = keep ? (unsigned long long)sortable_bits(p0[i]) : (1ull << 32);
-    row[i] = (unsigned)i;
-}
-// number of entries of the ascending array `starts` (m + 1 entries, starts[0] = 0) that are <= r, minus 1
-__device__ __forceinline__ int segment_of(const int* __restrict__ starts, int m, int r) {
-    int lo = 0, hi = m;   // invariant: starts[lo] <= r < starts[hi]
-    while (hi - lo > 1) { const int mid = (lo + hi) >> 1; if (starts[mid] <= r) lo = mid; else hi = mid; }
-    return lo;
-}
-// after the sort along p0: rank -> slab (equal counts); next key = (slab, p1); slab boundary values for locating
-__global__ void k_fm_key_p1(const unsigned* __restrict__ row_in, int n, const int* __restrict__ slab_start, int S0, const float* __restrict__ p0,
-                            const float* __restrict__ p1, float* __restrict__ b0, unsigned long long* __restrict__ key) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const unsigned idx = row_in[r];
-    const int k = segment_of(slab_start, S0, r);
-    if (r == slab_start[k]) b0[k] = p0[idx];
-    key[r] = ((unsigned long long)(unsigned)k << 32) | sortable_bits(p1[idx]);
-}
-// after the sort along (slab, p1): rank -> column; last key = (column, p2, row), as 16-byte records for the per-column sort
-__global__ void k_fm_rec_p2(const unsigned* __restrict__ row_in, int n, const int* __restrict__ col_start, int ncol, const float* __restrict__ p1,
-                            const float* __restrict__ p2, float* __restrict__ b1, uint4* __restrict__ rec) {
-    const int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= n) return;
-    const unsigned idx = row_in[r];
-    const int c = segment_of(col_start, ncol, r);
-    if (r == col_start[c]) b1[c] = p1[idx];
-    rec[r] = make_uint4((unsigned)c, sortable_bits(p2[idx]), idx, 0u);
-}
-__global__ void k_fm_fill_rows(float* __restrict__ T, int* __restrict__ torig, size_t n_rows) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < n_rows * FD) T[e] = INFINITY;
-    if (e < n_rows) torig[e] = INT_MAX;
-}
-// Row r of the packed table lives in leaf r / 64 as column r % 64 of a [33][64] block: a wave reads one dimension of a
-// whole leaf with one coalesced 256-B load (lane = row) and hands rows to its lanes' arithmetic with v_readlane.
-__device__ __forceinline__ size_t row_elem(size_t row, int d) { return (row / FX_LEAF) * (size_t)(FD * FX_LEAF) + (size_t)d * FX_LEAF + row % FX_LEAF; }
-// after the sort along (column, p2, row): rows to their padded positions
-__global__ void k_fm_place_rows(const uint4* __restrict__ rec, int n, const int* __restrict__ col_start, const int* __restrict__ col_row0, int ncol,
-                                const float* __restrict__ ft, const float* __restrict__ p0, const float* __restrict__ p1, const float* __restrict__ p2,
-                                float* __restrict__ T, int* __restrict__ torig, float* __restrict__ leaf_p2, float* __restrict__ prow /* [3][rows] */, size_t rows) {
-    const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (size_t)n * FD) return;
-    const int r = (int)(e / FD), d = (int)(e % FD);
-    const unsigned idx = rec[r].z;
-    const int c = segment_of(col_start, ncol, r);
-    const size_t row = (size_t)col_row0[c] + (size_t)(r - col_start[c]);
-    T[row_elem(row, d)] = ft[(size_t)idx * FD + d];
-    if (d == 0) {
-        torig[row] = (int)idx;
-        if (row % FX_LEAF == 0) leaf_p2[row / FX_LEAF] = p2[idx];
-        prow[row] = p0[idx]; prow[rows + row] = p1[idx]; prow[2 * rows + row] = p2[idx];
-    }
-}
-// Leaf boxes over the real rows of 64 padded rows; a leaf of padding only gets the empty box (+inf, -inf): its bound is
-// +inf.  Stored per group, transposed: lbox[group][min | max][33][64 leaves], so a wave reads one dimension of a group's
-// 64 boxes with one coalesced load (lane = leaf); leaves past the end are empty.  Beside the 33-D box every leaf has a
-// 3-D box of its rows' principal coordinates, pbox[group][min | max][3][64 leaves]: a leaf IS a cell of the packing in
-// those coordinates, so this box is tight where the 33-D box (axis-aligned, the data are not) is loose; together they
-// open 8 leaves per source where the 33-D box alone opens 19 (tools/studies/feature_match_tail.py).
-constexpr int PD = 3;
-__global__ void k_fm_leaf_boxes(const float* __restrict__ T, const int* __restrict__ torig, const float* __restrict__ prow, size_t rows,
-                                int nleaf, int ngroup, float* __restrict__ lbox, float* __restrict__ pbox) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= ngroup * FX_GROUP * (FD + PD)) return;
-    const int b = e / (FD + PD), d = e % (FD + PD);
-    float mn = INFINITY, mx = -INFINITY;
-    if (b < nleaf)
-        for (int r = b * FX_LEAF; r < (b + 1) * FX_LEAF; ++r) {
-            if (torig[r] == INT_MAX) continue;
-            const float v = d < FD ? T[row_elem((size_t)r, d)] : prow[(size_t)(d - FD) * rows + r];
-            mn = fminf(mn, v); mx = fmaxf(mx, v);
-        }
-    if (d < FD) {
-        float* gb = lbox + (size_t)(b / FX_GROUP) * (2 * FD * FX_GROUP);
-        gb[d * FX_GROUP + b % FX_GROUP] = mn; gb[(FD + d) * FX_GROUP + b % FX_GROUP] = mx;
-    } else {
-        float* gb = pbox + (size_t)(b / FX_GROUP) * (2 * PD * FX_GROUP);
-        gb[(d - FD) * FX_GROUP + b % FX_GROUP] = mn; gb[(PD + d - FD) * FX_GROUP + b % FX_GROUP] = mx;
-    }
-}
-// group boxes, same transposed layouts one level up: gbox[chunk of 64 groups][min | max][33][64], gpbox[chunk][min | max][3][64]
-__global__ void k_fm_group_boxes(const float* __restrict__ lbox, const float* __restrict__ pbox, int ngroup, int nchunk,
-                                 float* __restrict__ gbox, float* __restrict__ gpbox) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= nchunk * 64 * (FD + PD)) return;
-    const int g = e / (FD + PD), d = e % (FD + PD);
-    float mn = INFINITY, mx = -INFINITY;
-    if (g < ngroup) {
-        const float* gb = d < FD ? lbox + (size_t)g * (2 * FD * FX_GROUP) : pbox + (size_t)g * (2 * PD * FX_GROUP);
-        const int dd = d < FD ? d : d - FD, nd = d < FD ? FD : PD;
-        for (int l = 0; l < FX_GROUP; ++l) { mn = fminf(mn, gb[dd * FX_GROUP + l]); mx = fmaxf(mx, gb[(nd + dd) * FX_GROUP + l]); }
-    }
-    if (d < FD) {
-        float* cb = gbox + (size_t)(g / 64) * (2 * FD * 64);
-        cb[d * 64 + g % 64] = mn; cb[(FD + d) * 64 + g % 64] = mx;
-    } else {
-        float* cb = gpbox + (size_t)(g / 64) * (2 * PD * 64);
-        cb[(d - FD) * 64 + g % 64] = mn; cb[(PD + d - FD) * 64 + g % 64] = mx;
-    }
-}
 
 // home leaf of every source: its cell of the target packing (slab by p0, column by p1, leaf by p2)
 __global__ void k_fm_locate(const float* __restrict__ fs, int ns, const float* __restrict__ basis, int S0, int S1,
@@ -697,14 +222,22 @@ void k_fm_bucket_hist(const int* __restrict__ bucket_of, int n, int* __restrict_
     for (int b = threadIdx.x; b < FMP_BUCKETS; b += FMP_SORT_BLOCK) if (h[b]) atomicAdd(&hist[b], h[b]);
 }
 
-__device__ __forceinline__ float box_bound(const float (&f)[FD], const float* __restrict__ lo, const float* __restrict__ hi) {
-    float lb = 0.f;
-#pragma unroll
-    for (int d = 0; d < FD; ++d) { const float g = fmaxf(fmaxf(lo[d] - f[d], f[d] - hi[d]), 0.f); lb += g * g; }
-    return lb;
-}
-
 typedef float v2f __attribute__((ext_vector_type(2)));
+// a candidate as one word, (distance bits : original index): for distances >= 0 unsigned order is (distance, index) order, and NaN
+// and +inf have larger bit patterns than FLT_MAX - a strict < on keys takes the lowest index among equal distances and nothing the
+// reference's `dist < best_dist` would not take
+__device__ __forceinline__ unsigned long long fm_key(float dist, int orig) { return ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)orig; }
+// A lane's descriptor (a row of a leaf, or a source): 33 floats kept as 17 aligned register pairs, so that packed arithmetic can name
+// either half of a pair (op_sel) instead of the compiler giving every element a pair of its own.
+struct FmRow {
+    v2f p[(FD + 1) / 2];
+    __device__ __forceinline__ float at(int d) const { return (d & 1) ? p[d >> 1].y : p[d >> 1].x; }
+    __device__ __forceinline__ void load(const float* __restrict__ f, int stride) {      // element d at f[d * stride]
+#pragma unroll
+        for (int d = 0; d < FD; ++d) { if (d & 1) p[d >> 1].y = f[d * stride]; else p[d >> 1].x = f[d * stride]; }
+        p[FD >> 1].y = 0.f;
+    }
+};
 
 // the descriptors of the K sources of every wave, interleaved: fsk[wave][d][k] = fs[sperm[K wave + k]][d] (a wave past the
 // end of an uneven count repeats the last source, as FmWave does): (q_k[d], q_k+1[d]) is then one aligned SGPR pair
@@ -736,12 +269,7 @@ __device__ __forceinline__ float wave_min_f32(float v) {
 // useful, distinct work, and the K source descriptors are wave-uniform (scalar loads of the wave's own 132-B rows, which
 // stay in the scalar cache).  The sources of a wave share a home leaf (they were ordered by it), so they need nearly the
 // same leaves: a leaf fetched once (33 coalesced 256-B loads, lane = row) serves all K of them.
-//   round-2 history of this kernel at 143k x 151k real descriptors (profiles/r2/history/feature_match_designs.md):
-//   lane = source, rows through the scalar path 7.5 ms (every wave opens its own leaves: the scalar cache misses on all
-//   of them); lane = source, rows through v_readlane 7.6 ms (175 issue slots per row, and a wave of 64 sources opens the
-//   union of their leaves: 78 against 19 for a single source); lane = row with K = 8 / 4 / 2 / 1 sources per wave:
-//   12.8 (register spills) / 5.8 / 1.6 / 2.0 ms; four waves sharing one source pair through LDS bounds: 3.1 ms (the
-//   table is then read 36 GB instead of 28 GB per call — the kernel is bound by L2 / Infinity-Cache bandwidth).
+//   (what was tried on the way, at 143k x 151k real descriptors: profiles/r2/history/feature_match_designs.md)
 // Per source and lane a running (distance, original index) minimum over the rows that lane has seen; its wave minimum is
 // the source's bound.  A box is opened when its bound <= the source's bound (<=: an equal distance with a lower index
 // could still win; the exact lowest-index rule is applied by the final lexicographic reduction).
@@ -790,14 +318,9 @@ struct FmWave {
             for (int k = 0; k < K; ++k) bound[k] = fminf(bound[k], __int_as_float(__builtin_amdgcn_readfirstlane(s_bound[k])));
         }
     }
-    // a lane's row of a leaf: 33 floats kept as 17 aligned register pairs, so that the packed arithmetic below can name
-    // either half of a pair (op_sel) instead of the compiler giving every element a pair of its own
-    struct RowBuf { v2f p[(FD + 1) / 2]; __device__ __forceinline__ float at(int d) const { return (d & 1) ? p[d >> 1].y : p[d >> 1].x; } };
+    using RowBuf = FmRow;
     __device__ __forceinline__ void load_leaf(int leaf, RowBuf& row, int& ro) const {
-        const float* __restrict__ blk = t.T + (size_t)leaf * (FD * FX_LEAF);
-#pragma unroll
-        for (int d = 0; d < FD; ++d) { if (d & 1) row.p[d >> 1].y = blk[d * FX_LEAF + lane]; else row.p[d >> 1].x = blk[d * FX_LEAF + lane]; }
-        row.p[FD >> 1].y = 0.f;
+        row.load(t.T + (size_t)leaf * (FD * FX_LEAF) + lane, FX_LEAF);
         ro = t.torig[(size_t)leaf * FX_LEAF + lane];
     }
     __device__ __forceinline__ void eval_leaf(const RowBuf& row, int ro) {
@@ -823,8 +346,8 @@ struct FmWave {
             }
 #pragma unroll
             for (int j = 0; j < K / 2; ++j) {
-                const unsigned long long k0 = ((unsigned long long)__float_as_uint(dist[j].x) << 32) | (unsigned)ro;
-                const unsigned long long k1 = ((unsigned long long)__float_as_uint(dist[j].y) << 32) | (unsigned)ro;
+                const unsigned long long k0 = fm_key(dist[j].x, ro);
+                const unsigned long long k1 = fm_key(dist[j].y, ro);
                 lkey[2 * j] = k0 < lkey[2 * j] ? k0 : lkey[2 * j];
                 lkey[(2 * j + 1) % K] = k1 < lkey[(2 * j + 1) % K] ? k1 : lkey[(2 * j + 1) % K];
             }
@@ -839,7 +362,7 @@ struct FmWave {
             for (int d = 0; d < FD; ++d) { const float diff = q[d] - row.at(d); dist += diff * diff; }   // registration.cpp:222-224
             // strict < on (distance, index): the lowest index among equal distances; NaN and +inf have larger bit patterns than
             // FLT_MAX and are never taken, like `dist < best_dist` in the reference
-            const unsigned long long key = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned)ro;
+            const unsigned long long key = fm_key(dist, ro);
             lkey[k] = key < lkey[k] ? key : lkey[k];
         }
         ++n_open;
@@ -985,6 +508,9 @@ struct FmWave {
     }
 };
 
+// where the scan class starts in the walk's overflow list (pass B's class starts at 0; each class holds at most ns wave starts)
+__host__ __device__ __forceinline__ int fm_scan_class_offset(int ns) { return ns + 1; }
+
 // Pass A: one wave per K sources.  Home leaf, home group, then every group whose box passes (tested once per chunk of 64
 // groups, lane = group, with the bounds the home group left), inside-out from the home group.  A wave whose sources
 // turn out to be outliers (far from every target: most boxes pass) stops after `leaf_limit` leaves, stores what it has
@@ -1040,7 +566,7 @@ void k_fm_query(FmTables t, int blocks_per_xcd, int leaf_limit, int heavy_groups
     if (overflow && w.lane == 0) {
         if (!to_scan) overflow_list[slot] = s0;
         else {
-            overflow_list[t.ns + 1 + slot] = s0;     // second half of the list: the scan class, as wave starts ...
+            overflow_list[fm_scan_class_offset(t.ns) + slot] = s0;     // second half of the list: the scan class, as wave starts ...
 #pragma unroll
             for (int k = 0; k < K; ++k) overflow_src[slot * K + k] = s0 + k < t.ns ? w.src[k] : -1;   // ... and as sources
         }
@@ -1145,12 +671,7 @@ void k_fm_query_overflow(FmTables t, const int* __restrict__ overflow_count, con
 // emitted early is at worst superfluous.  The result is the minimum over 64-bit (distance bits : original index) keys,
 // which does not depend on the order of the atomics.  Descriptors without structure (every box passes) overflow the entry
 // pools or the pair room (32 per source): the call then falls back to k_fm_query and its scan class.
-// What was measured on the way (143k x 151k relief descriptors; profiles/r3/history/feature_match_leaf_major.md): rows and boxes
-// through the scalar path 0.84 ms (a leaf is 8.4 KB, the scalar cache 16 KB per CU with a slow fill path); one global cursor for
-// the pairs / one global counter per leaf for the positions: 9,000 and ~20 same-address returning atomics wait for each other
-// (50 us / 45 us); two rounds of box tests (home groups first) 9.7 instead of 12.1 pairs per source but 0.525 instead of
-// 0.487 ms; two sources per lane in k_lm_eval (half the LDS reads) and the next group's boxes prefetched into registers: no gain.
-constexpr int LM_BOX = 72;        // floats per box as this search stores them: min[33] | max[33] | pmin[3] | pmax[3]
+// What was measured on the way (143k x 151k relief descriptors): profiles/r3/history/feature_match_leaf_major.md.
 constexpr int LM_WAVES = 4;       // waves per workgroup of the evaluation
 #ifndef LM_BOX_WAVES_VALUE
 #define LM_BOX_WAVES_VALUE 4
@@ -1173,30 +694,14 @@ struct LmLists {
     unsigned long long* keys;                             // [ns]
     int unit_cap;                                         // room in unit_leaf
 };
-struct LmSrc { v2f p[(FD + 1) / 2]; float pq[PD]; };     // a lane's source: descriptor as 17 register pairs, principal coordinates
+struct LmSrc : FmRow { float pq[PD]; };     // a lane's source: its descriptor and principal coordinates
 // The original row indices of a leaf as k_lm_eval reads them (rarely: only where a lane can improve): the "constant" address space
 // tells the compiler that nothing in the kernel writes them, which lets it use the scalar path although the kernel stores keys.
 typedef const __attribute__((address_space(4))) int* lm_cint_p;
 
-__global__ void k_lm_box_layout(const float* __restrict__ lbox, const float* __restrict__ pbox, const float* __restrict__ gbox, const float* __restrict__ gpbox,
-                                int nleaf, int ngroup, float* __restrict__ sleaf, float* __restrict__ sgroup) {
-    const int e = blockIdx.x * blockDim.x + threadIdx.x;
-    if (e >= (nleaf + ngroup) * LM_BOX) return;
-    const int b = e / LM_BOX, f = e % LM_BOX;
-    if (b < nleaf) {
-        const int g = b / FX_GROUP, l = b % FX_GROUP;
-        sleaf[e] = f < 2 * FD ? lbox[(size_t)g * (2 * FD * FX_GROUP) + f * FX_GROUP + l] : pbox[(size_t)g * (2 * PD * FX_GROUP) + (f - 2 * FD) * FX_GROUP + l];
-    } else {
-        const int gi = b - nleaf, c = gi / 64, k = gi % 64;
-        sgroup[(size_t)gi * LM_BOX + f] = f < 2 * FD ? gbox[(size_t)c * (2 * FD * 64) + f * 64 + k] : gpbox[(size_t)c * (2 * PD * 64) + (f - 2 * FD) * 64 + k];
-    }
-}
 
 __device__ __forceinline__ void lm_load_source(const FmTables& t, int src, LmSrc& q) {
-    const float* __restrict__ f = t.fs + (size_t)src * FD;
-#pragma unroll
-    for (int d = 0; d < FD; ++d) { if (d & 1) q.p[d >> 1].y = f[d]; else q.p[d >> 1].x = f[d]; }
-    q.p[FD >> 1].y = 0.f;
+    q.load(t.fs + (size_t)src * FD, 1);
 #pragma unroll
     for (int r = 0; r < PD; ++r) q.pq[r] = t.sp[(size_t)src * 4 + r];
 }
@@ -1241,8 +746,8 @@ __device__ __forceinline__ void lm_eval_leaf(const float* rows, const int* __res
         if (__any(mn <= __uint_as_float((unsigned)(key >> 32)))) {
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const unsigned long long k0 = ((unsigned long long)__float_as_uint(acc[j].x) << 32) | (unsigned)ro[r0 + 2 * j];
-                const unsigned long long k1 = ((unsigned long long)__float_as_uint(acc[j].y) << 32) | (unsigned)ro[r0 + 2 * j + 1];
+                const unsigned long long k0 = fm_key(acc[j].x, ro[r0 + 2 * j]);
+                const unsigned long long k1 = fm_key(acc[j].y, ro[r0 + 2 * j + 1]);
                 key = k0 < key ? k0 : key;      // strict < on (distance, index): NaN and +inf have larger bit patterns than FLT_MAX
                 key = k1 < key ? k1 : key;
             }
@@ -1512,234 +1017,183 @@ __global__ void k_lm_finish(const unsigned long long* __restrict__ keys, int ns,
     corr[i] = (unsigned)(k >> 32) == 0x7f7fffffu ? 0 : (int)(unsigned)k;   // nothing finite -> the reference keeps index 0
 }
 
-namespace {
-
-// cyclic Jacobi eigen-solver for a symmetric n x n matrix (host, double): eigenvalues descending, eigenvectors in rows
-void jacobi_eigen_host(std::vector<double>& A, int n, std::vector<double>& evals, std::vector<double>& evecs) {
-    std::vector<double> V((size_t)n * n, 0.0);
-    for (int i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
-    for (int sweep = 0; sweep < 60; ++sweep) {
-        double off = 0.0;
-        for (int p = 0; p < n; ++p) for (int q = p + 1; q < n; ++q) off += A[(size_t)p * n + q] * A[(size_t)p * n + q];
-        if (!(off > 1e-30)) break;
-        for (int p = 0; p < n; ++p)
-            for (int q = p + 1; q < n; ++q) {
-                const double apq = A[(size_t)p * n + q];
-                if (std::fabs(apq) < 1e-300) continue;
-                const double theta = (A[(size_t)q * n + q] - A[(size_t)p * n + p]) / (2.0 * apq);
-                const double tt = (theta >= 0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-                const double c = 1.0 / std::sqrt(tt * tt + 1.0), s = tt * c;
-                for (int k = 0; k < n; ++k) {
-                    const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-                    A[(size_t)k * n + p] = c * akp - s * akq; A[(size_t)k * n + q] = s * akp + c * akq;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-                    A[(size_t)p * n + k] = c * apk - s * aqk; A[(size_t)q * n + k] = s * apk + c * aqk;
-                }
-                for (int k = 0; k < n; ++k) {
-                    const double vkp = V[(size_t)k * n + p], vkq = V[(size_t)k * n + q];
-                    V[(size_t)k * n + p] = c * vkp - s * vkq; V[(size_t)k * n + q] = s * vkp + c * vkq;
-                }
-            }
-    }
-    std::vector<int> order(n);
-    for (int i = 0; i < n; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](int a, int b) { return A[(size_t)a * n + a] > A[(size_t)b * n + b]; });
-    evals.resize(n); evecs.assign((size_t)n * n, 0.0);
-    for (int r = 0; r < n; ++r) {
-        evals[r] = A[(size_t)order[r] * n + order[r]];
-        for (int k = 0; k < n; ++k) evecs[(size_t)r * n + k] = V[(size_t)k * n + order[r]];
-    }
+// ---- host side: each rule once ------------------------------------------------------------------------------------------
+// Every TDV_FM_* / TDV_LM_* switch is read here and nowhere else; none of them changes a correspondence.  The first two are real
+// getenv()s read per call in both libraries; the rest exist in the study library only: A/B switches per call, tuning values once.
+struct FmKnobs {
+    bool brute, walk_only;   // TDV_FM_BRUTE: the plain scan whatever the sizes.  TDV_FM_LEAFMAJOR=0: the walk instead of the leaf-major search
+    bool keyorder, stats;    // TDV_FM_KEYORDER: round 1's key-ordered scan instead of the index.  TDV_FM_STATS: box-test / leaf counts on stderr
+    int lm_rounds;           // TDV_LM_ROUNDS=2: the home groups' boxes first, the other groups with the bounds those left
+    int leaf_limit;          // TDV_FM_LIMIT: leaves a wave of pass A opens before it hands over (32 while a leaf cost what it did in the middle
+                             // of round 2; 128 since: relief part 0.81 -> 0.73 ms, cuboid 200k x 200k 4.05 -> 2.04 ms, random rows 16.8 -> 17.7 ms)
+    int heavy_groups;        // TDV_FM_HEAVY: a wave that gives up with this many groups left hands its sources to the scan class
+    int force_k;             // TDV_FM_K: sources per wave of the walk (0 = the default, 2; 1 and 4 measured slower)
+    int eval_blocks;         // TDV_LM_EVAL_BLOCKS: a multiple of 8 (1024 / 2048 / 4096 / 8192: 0.51 / 0.49 / 0.477 / 0.478 ms at 143k x 151k)
+    bool early;              // TDV_FM_NO_EARLY_EXIT unset: the plain scan drops a target once no lane of the wave can still take it
+};
+static FmKnobs fm_knobs() {
+    auto number = [](const char* v, int otherwise) { return v ? atoi(v) : otherwise; };
+    static const int leaf_limit = number(study_env("TDV_FM_LIMIT"), 128), heavy_groups = number(study_env("TDV_FM_HEAVY"), 8);
+    static const int force_k = number(study_env("TDV_FM_K"), 0), eval_blocks = number(study_env("TDV_LM_EVAL_BLOCKS"), 4096);
+    static const bool early = study_env("TDV_FM_NO_EARLY_EXIT") == nullptr;
+    const char* lm = getenv("TDV_FM_LEAFMAJOR");
+    FmKnobs k;
+    k.brute = getenv("TDV_FM_BRUTE") != nullptr; k.walk_only = lm && atoi(lm) == 0;
+    k.keyorder = study_env("TDV_FM_KEYORDER") != nullptr; k.stats = study_env("TDV_FM_STATS") != nullptr;
+    k.lm_rounds = number(study_env("TDV_LM_ROUNDS"), 1) == 2 ? 2 : 1;
+    k.leaf_limit = leaf_limit; k.heavy_groups = heavy_groups; k.force_k = force_k; k.eval_blocks = eval_blocks; k.early = early;
+    return k;
 }
 
-}  // namespace
+// "This call uses the index" (tdv_internal.hpp): targets worth indexing and no switch that asks for another search; enough
+// sources to pay for locating and ordering them.
+constexpr int FM_INDEX_MIN_TARGETS = 2048, FM_INDEX_MIN_SOURCES = 4096;
+bool fm_wants_index(int nt) { const FmKnobs k = fm_knobs(); return nt >= FM_INDEX_MIN_TARGETS && !k.brute && !k.keyorder; }
+bool fm_indexes_sources(int ns) { return ns >= FM_INDEX_MIN_SOURCES; }
 
-int fm_index_build(tdv_ctx* ctx, const float* d_ft, int nt, FmIndex* ix) {
-    if (!ctx || !d_ft || !ix || nt <= 0) return TDV_ERR_BAD_ARG;
+// A scan's second grid dimension: n items (targets, or boxes of them) cut so that blocks_x * splits comes to about want_blocks
+// workgroups, at least min_per_split items in a split, at most max_splits of them: `asked`.  nsplit = the splits of per_split items
+// that hold something.
+struct ScanSplits { int asked, nsplit, per_split; };
+static ScanSplits scan_splits(int blocks_x, int n, int want_blocks, int min_per_split, int max_splits) {
+    if (n <= 0) return ScanSplits{0, 0, 0};
+    const int want = (want_blocks + blocks_x - 1) / blocks_x;
+    const int asked = std::max(1, std::min(std::min(want, std::max(1, n / min_per_split)), max_splits));
+    const int per_split = (n + asked - 1) / asked;
+    return ScanSplits{asked, (n + per_split - 1) / per_split, per_split};
+}
+
+// The plain scan over every target.  Part 0: the first FM_SEED targets in one split; its exact best seeds the bound of every later
+// split.  EARLY = false (study build, TDV_FM_NO_EARLY_EXIT): everything in one launch without bounds.
+template <bool EARLY>
+static int fm_scan_all(tdv_ctx* ctx, const float* d_fs, int ns, const float* d_ft, int nt, int* d_corr) {
     hipStream_t s = ctx->stream;
-    ScopedTimer tm(ctx, TDV_TIMER_FM_INDEX);
-    // 1. principal directions of the targets: raw moments on the device, 33 x 33 eigen-problem on the host
-    const int mblocks = std::max(1, std::min(512, (nt + 255) / 256));
-    const int rows_per_block = (nt + mblocks - 1) / mblocks;
-    double *partial, *mom;
-    TDV_TRY(ws_alloc(ctx, (size_t)mblocks * FX_NMOM, &partial));
-    TDV_TRY(ws_alloc(ctx, (size_t)FX_NMOM, &mom));
-    k_fm_moments<<<mblocks, FX_MOM_BLOCK, 0, s>>>(d_ft, nt, rows_per_block, partial);
-    k_fm_moments_fold<<<FX_NMOM, 64, 0, s>>>(partial, mblocks, mom);
-    // ... and, for the same round trip, which rows are copies of an earlier row (k_fm_dedupe_insert)
-    const size_t table_size = sort_pow2((size_t)nt) * 2;
-    int *table, *slot_of, *d_kept;
-    TDV_TRY(ws_alloc(ctx, table_size, &table));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &slot_of));
-    TDV_TRY(ws_alloc(ctx, 1, &d_kept));
-    TDV_HIP(ctx, hipMemsetAsync(table, 0xff, table_size * 4, s));
-    TDV_HIP(ctx, hipMemsetAsync(d_kept, 0, 4, s));
-    k_fm_dedupe_insert<<<(unsigned)((nt + FX_DD_ROWS - 1) / FX_DD_ROWS), FX_DD_ROWS, 0, s>>>(d_ft, nt, table, (unsigned)(table_size - 1), slot_of, d_kept);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(pin_reserve(ctx, 64 * 1024));
-    double* h_mom = reinterpret_cast<double*>(ctx->pin);
-    TDV_HIP(ctx, hipMemcpyAsync(h_mom, mom, FX_NMOM * sizeof(double), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + 6144, d_kept, 4, hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
-    const int nk = *reinterpret_cast<const int*>(ctx->pin + 6144);   // distinct rows: what the index packs
-    if (nk <= 0 || nk > nt) return TDV_ERR_INTERNAL;
-    std::vector<double> C((size_t)FD * FD), mean(FD), evals, evecs;
-    bool finite = true;
-    for (int d = 0; d < FD; ++d) { mean[d] = h_mom[561 + d] / nt; finite = finite && std::isfinite(mean[d]); }
-    for (int a = 0, e = 0; a < FD; ++a)
-        for (int b = a; b < FD; ++b, ++e) {
-            const double c = h_mom[e] / nt - mean[a] * mean[b];
-            finite = finite && std::isfinite(c);
-            C[(size_t)a * FD + b] = C[(size_t)b * FD + a] = c;
-        }
-    float h_basis[4 * FD];
-    double e0 = 1, e1 = 1, e2 = 1;
-    if (finite) {
-        jacobi_eigen_host(C, FD, evals, evecs);
-        for (int r = 0; r < 3; ++r) for (int d = 0; d < FD; ++d) h_basis[r * FD + d] = (float)evecs[(size_t)r * FD + d];
-        for (int d = 0; d < FD; ++d) h_basis[3 * FD + d] = (float)mean[d];
-        e0 = std::sqrt(std::max(evals[0], 0.0)); e1 = std::sqrt(std::max(evals[1], 0.0)); e2 = std::sqrt(std::max(evals[2], 0.0));
-    } else {   // non-finite descriptors: any directions will do (the order only affects speed)
-        for (int r = 0; r < 3; ++r) for (int d = 0; d < FD; ++d) h_basis[r * FD + d] = (d % 3 == r) ? 1.f : 0.f;
-        for (int d = 0; d < FD; ++d) h_basis[3 * FD + d] = 0.f;
-    }
-    // how far the f32 directions are from orthonormal decides whether their boxes may be used (k_fm_query, principal_bound_note)
+    const int ns_pad = (int)align_up((size_t)ns, FM_SRC_PER_BLOCK), blocks_x = ns_pad / FM_SRC_PER_BLOCK;
+    const int n_seed = EARLY ? std::min(nt, FM_SEED) : 0;
+    const ScanSplits sp = scan_splits(blocks_x, nt - n_seed, 4096, 64, 64);
+    const int nparts = sp.nsplit + (n_seed ? 1 : 0);
+    float* pd; int* pj;
+    TDV_TRY(ws_alloc(ctx, (size_t)nparts * ns_pad, &pd));
+    TDV_TRY(ws_alloc(ctx, (size_t)nparts * ns_pad, &pj));
     {
-        double dev = 0.0;
-        for (int a = 0; a < 3; ++a)
-            for (int b = 0; b < 3; ++b) {
-                double g = 0.0;
-                for (int d = 0; d < FD; ++d) g += (double)h_basis[a * FD + d] * (double)h_basis[b * FD + d];
-                dev += (g - (a == b ? 1.0 : 0.0)) * (g - (a == b ? 1.0 : 0.0));
-            }
-        ix->pscale = (std::sqrt(dev) <= 1e-6) ? (1.0f - 1e-4f) : 0.0f;
+        ScopedTimer tm(ctx, TDV_TIMER_FEATURE_MATCH);
+        if constexpr (EARLY) {
+            k_feature_match_scan<true, true><<<dim3(blocks_x, 1), FM_BLOCK, 0, s>>>(d_fs, ns, ns_pad, d_ft, 0, n_seed, n_seed, nullptr, nullptr, 0, pd, pj);
+            if (sp.nsplit)   // (ordering the sources by seed distance was measured: no gain on FPFH descriptors, so rows stay in place)
+                k_feature_match_scan<true, true><<<dim3(blocks_x, sp.nsplit), FM_BLOCK, 0, s>>>(d_fs, ns, ns_pad, d_ft, n_seed, nt, sp.per_split, pd, nullptr, 0, pd + ns_pad, pj + ns_pad);
+        } else {
+            k_feature_match_scan<false, true><<<dim3(blocks_x, sp.nsplit), FM_BLOCK, 0, s>>>(d_fs, ns, ns_pad, d_ft, 0, nt, sp.per_split, nullptr, nullptr, 0, pd, pj);
+        }
     }
-    // 2. slab / column counts: S0 * S1 * S2 = number of leaves with S_d proportional to the spread along p_d
-    const double nleaf_t = std::max(1.0, (double)nk / FX_LEAF);
-    const double tiny = 1e-6 * std::max(e0, 1e-30);
-    e0 = std::max(e0, tiny); e1 = std::max(e1, tiny); e2 = std::max(e2, tiny);
-    double g = std::cbrt(nleaf_t / (e0 * e1 * e2));
-    double s0 = e0 * g, s1 = e1 * g, s2 = e2 * g;
-    if (s2 < 1.0) { const double k = std::sqrt(s2); s0 *= k; s1 *= k; s2 = 1.0; }
-    if (s1 < 1.0) { s0 *= s1; s1 = 1.0; }
-    const int S0 = std::max(1, std::min(FX_MAX_S, (int)std::lround(s0)));
-    const int S1 = std::max(1, std::min(FX_MAX_S, (int)std::lround(s1)));
-    const int ncol = S0 * S1;
-    // equal-count cuts by rank are known without looking at the data
-    std::vector<int> h_int((size_t)(S0 + 1) + 3 * ((size_t)ncol + 1));
-    int* slab_start = h_int.data(); int* col_start = slab_start + S0 + 1; int* col_row0 = col_start + ncol + 1; int* col_leaf0 = col_row0 + ncol + 1;
-    for (int k = 0; k <= S0; ++k) slab_start[k] = (int)((long long)nk * k / S0);
-    for (int k = 0; k < S0; ++k) {
-        const int c0 = slab_start[k], cnt = slab_start[k + 1] - c0;
-        for (int j = 0; j < S1; ++j) col_start[k * S1 + j] = c0 + (int)((long long)cnt * j / S1);
-    }
-    col_start[ncol] = nk;
-    size_t rows = 0;
-    for (int c = 0; c < ncol; ++c) {
-        col_row0[c] = (int)rows; col_leaf0[c] = (int)(rows / FX_LEAF);
-        rows += align_up((size_t)(col_start[c + 1] - col_start[c]), FX_LEAF);
-    }
-    col_row0[ncol] = (int)rows; col_leaf0[ncol] = (int)(rows / FX_LEAF);
-    if (rows == 0) rows = FX_LEAF;
-    const int nleaf = (int)(rows / FX_LEAF), ngroup = (nleaf + FX_GROUP - 1) / FX_GROUP;
-    // 3. device side
-    float *basis, *p0, *p1, *p2; int* d_int; uint4* rec;
-    size_t n_pow2 = sort_pow2((size_t)nt);
-    TDV_TRY(ws_alloc(ctx, (size_t)4 * FD, &basis));
-    TDV_TRY(ws_alloc(ctx, h_int.size(), &d_int));
-    TDV_TRY(ws_alloc(ctx, (size_t)S0 + 1, &ix->b0));
-    TDV_TRY(ws_alloc(ctx, (size_t)ncol + 1, &ix->b1));
-    TDV_TRY(ws_alloc(ctx, (size_t)nleaf, &ix->leaf_p2));
-    TDV_TRY(ws_alloc(ctx, rows * FD, &ix->T));
-    TDV_TRY(ws_alloc(ctx, rows, &ix->torig));
-    const int nchunk = (ngroup + 63) / 64;
-    TDV_TRY(ws_alloc(ctx, (size_t)ngroup * 2 * FD * FX_GROUP, &ix->lbox));
-    TDV_TRY(ws_alloc(ctx, (size_t)nchunk * 2 * FD * 64, &ix->gbox));
-    TDV_TRY(ws_alloc(ctx, (size_t)ngroup * 2 * PD * FX_GROUP, &ix->pbox));
-    TDV_TRY(ws_alloc(ctx, (size_t)nchunk * 2 * PD * 64, &ix->gpbox));
-    TDV_TRY(ws_alloc(ctx, 1, &ix->amax));
-    TDV_TRY(ws_alloc(ctx, (size_t)nleaf * LM_BOX, &ix->sleaf));
-    TDV_TRY(ws_alloc(ctx, (size_t)ngroup * LM_BOX, &ix->sgroup));
-    const WsMark scratch = ws_mark(ctx);   // everything below is build scratch
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &p0));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &p1));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &p2));
-    TDV_TRY(ws_alloc(ctx, n_pow2, &rec));
-    unsigned long long *key_a, *key_b; unsigned *row_a, *row_b;
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &key_a));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &key_b));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &row_a));
-    TDV_TRY(ws_alloc(ctx, (size_t)nt, &row_b));
-    float* prow;
-    TDV_TRY(ws_alloc(ctx, rows * PD, &prow));
-    char* stage = ctx->pin + 8192;   // the moments occupied the first bytes
-    std::memcpy(stage, h_basis, sizeof(h_basis));
-    std::memcpy(stage + sizeof(h_basis), h_int.data(), h_int.size() * 4);
-    TDV_HIP(ctx, hipMemcpyAsync(basis, stage, sizeof(h_basis), hipMemcpyHostToDevice, s));
-    TDV_HIP(ctx, hipMemcpyAsync(d_int, stage + sizeof(h_basis), h_int.size() * 4, hipMemcpyHostToDevice, s));
-    const int* d_slab_start = d_int; const int* d_col_start = d_int + S0 + 1; const int* d_col_row0 = d_col_start + ncol + 1;
-    ix->col_leaf0 = d_col_row0 + ncol + 1;
-    ix->ft = d_ft; ix->basis = basis; ix->nt = nt; ix->rows = (int)rows; ix->nleaf = nleaf; ix->ngroup = ngroup; ix->S0 = S0; ix->S1 = S1;
-    TDV_HIP(ctx, hipMemsetAsync(ix->leaf_p2, 0, (size_t)nleaf * 4, s));
-    TDV_HIP(ctx, hipMemsetAsync(ix->b0, 0, ((size_t)S0 + 1) * 4, s));
-    TDV_HIP(ctx, hipMemsetAsync(ix->b1, 0, ((size_t)ncol + 1) * 4, s));
-    const unsigned gn = (unsigned)((nt + 255) / 256);
-    TDV_HIP(ctx, hipMemsetAsync(ix->amax, 0, 4, s));
-    k_fm_project<<<gn, 256, 0, s>>>(d_ft, nt, basis, p0, p1, p2, ix->amax);
-    // slabs along p0, columns along p1: two stable radix sorts of (key, row) pairs (csrc/sort.hip; two bitonic sorts of 16-byte records,
-    // ~30 launches and 0.19 ms each at 150k rows, until the end of round 2)
-    k_fm_key_p0<<<gn, 256, 0, s>>>(p0, nt, table, slot_of, key_a, row_a);
-    TDV_TRY(radix_sort_pairs_dev(ctx, key_a, key_b, row_a, row_b, (size_t)nt, 33));   // the distinct rows lead; the copies follow
-    k_fm_key_p1<<<gn, 256, 0, s>>>(row_b, nk, d_slab_start, S0, p0, p1, ix->b0, key_a);
-    int slab_bits = 1;
-    while ((1 << slab_bits) < S0) ++slab_bits;
-    TDV_TRY(radix_sort_pairs_dev(ctx, key_a, key_b, row_b, row_a, (size_t)nk, 32 + slab_bits));
-    k_fm_rec_p2<<<gn, 256, 0, s>>>(row_a, nk, d_col_start, ncol, p1, p2, ix->b1, rec);
-    // the third key only orders the rows INSIDE their column: columns of up to 2,048 rows are sorted by one workgroup each,
-    // all in one launch, instead of a third full sort
-    int max_col = 0;
-    for (int c = 0; c < ncol; ++c) max_col = std::max(max_col, col_start[c + 1] - col_start[c]);
-    if (max_col <= segment_sort_max_len()) TDV_TRY(segment_sort_records_dev(ctx, rec, d_col_start, ncol));
-    else {
-        const size_t nk_pow2 = sort_pow2((size_t)nk);
-        if (nk_pow2 > (size_t)nk) TDV_HIP(ctx, hipMemsetAsync(rec + nk, 0xff, (nk_pow2 - (size_t)nk) * sizeof(uint4), s));   // padding sorts last
-        TDV_TRY(sort_records_dev(ctx, rec, nk_pow2));
-    }
-    k_fm_fill_rows<<<(unsigned)((rows * FD + 255) / 256), 256, 0, s>>>(ix->T, ix->torig, rows);
-    k_fm_place_rows<<<(unsigned)(((size_t)nk * FD + 255) / 256), 256, 0, s>>>(rec, nk, d_col_start, d_col_row0, ncol, d_ft, p0, p1, p2, ix->T, ix->torig, ix->leaf_p2, prow, rows);
-    k_fm_leaf_boxes<<<(ngroup * FX_GROUP * (FD + PD) + 255) / 256, 256, 0, s>>>(ix->T, ix->torig, prow, rows, nleaf, ngroup, ix->lbox, ix->pbox);
-    k_fm_group_boxes<<<(nchunk * 64 * (FD + PD) + 255) / 256, 256, 0, s>>>(ix->lbox, ix->pbox, ngroup, nchunk, ix->gbox, ix->gpbox);
-    k_lm_box_layout<<<((nleaf + ngroup) * LM_BOX + 255) / 256, 256, 0, s>>>(ix->lbox, ix->pbox, ix->gbox, ix->gpbox, nleaf, ngroup, ix->sleaf, ix->sgroup);
+    k_feature_match_combine<<<(ns + 255) / 256, 256, 0, s>>>(ns, ns_pad, nparts, pd, pj, d_corr);
     TDV_CHECK_LAUNCH(ctx);
-    TDV_HIP(ctx, hipStreamSynchronize(s));   // the pinned staging is reused by later calls; the scratch is released here
-    ws_rewind(ctx, scratch);
     return TDV_OK;
 }
 
-// Pass A over every source, then the sources it gave up on: few of them -> pass B (8 waves each on the packed index);
-// many of them (descriptors without structure, or a plateau of near-identical rows: no box can exclude anything) -> the
+// ---- one indexed call: locate and order the sources; the leaf-major search; where that does not answer, the walk ----------
+struct FmZeroed {          // what one memset clears before the sources are located
+    int hist[FMP_BUCKETS], cursor[FMP_BUCKETS];   // sources per bucket of home leaves (bucket = leaf up to FMP_BUCKETS leaves); k_fm_scatter's write positions
+    int overflow_count[2];                        // the walk: waves given up to pass B, waves given up to the scan class
+    unsigned amax_s; int unused;                  // largest |x_d - mean_d| over the sources, as float bits
+};
+static_assert(sizeof(FmZeroed) == ((size_t)2 * FMP_BUCKETS + 4) * 4, "one memset: hist | cursor | overflow_count[2] | amax_s");
+struct FmRun {             // the call's arguments and switches, and what it allocated
+    tdv_ctx* ctx; const FmIndex& ix; const float* fs; int ns; int* corr; FmKnobs knobs;
+    int bucket_shift = 0;          // home leaf -> bucket of the ordering's histogram
+    FmZeroed* z = nullptr;
+    int *home = nullptr, *bucket_of = nullptr, *sperm = nullptr, *start = nullptr, *d_total = nullptr;   // per source: home leaf, its bucket; the search order; bucket starts
+    float* sp = nullptr;           // [ns][4]: the sources' principal coordinates
+    // the walk's hand-over: the wave starts given up to pass B | to the scan class (one array, the second list fm_scan_class_offset
+    // into it), the scan class once more as sources, pass A's partial answers
+    int *overflow_walk = nullptr, *overflow_scan = nullptr, *overflow_src = nullptr, *part_j = nullptr; float* part_d = nullptr;
+};
+static int fm_alloc(FmRun& r) {
+    tdv_ctx* ctx = r.ctx; const size_t ns = (size_t)r.ns;
+    while ((r.ix.nleaf >> r.bucket_shift) > FMP_BUCKETS) ++r.bucket_shift;
+    TDV_TRY(ws_alloc(ctx, 1, &r.z));
+    TDV_TRY(ws_alloc(ctx, 2 * ns + 8, &r.overflow_walk));
+    r.overflow_scan = r.overflow_walk + fm_scan_class_offset(r.ns);
+    TDV_TRY(ws_alloc(ctx, ns + 8, &r.overflow_src));
+    TDV_TRY(ws_alloc(ctx, ns, &r.part_d));
+    TDV_TRY(ws_alloc(ctx, ns, &r.part_j));
+    TDV_TRY(ws_alloc(ctx, ns * 4, &r.sp));
+    TDV_TRY(ws_alloc(ctx, ns, &r.home));
+    TDV_TRY(ws_alloc(ctx, ns, &r.bucket_of));
+    TDV_TRY(ws_alloc(ctx, ns, &r.sperm));
+    TDV_TRY(ws_alloc(ctx, (size_t)FMP_BUCKETS + 1, &r.start));
+    return ws_alloc(ctx, 1, &r.d_total);
+}
+// Step 1: every source's home leaf (its cell of the target packing), and the search order: the sources sorted by home leaf.
+static int fm_locate_and_order(FmRun& r) {
+    tdv_ctx* ctx = r.ctx; hipStream_t s = ctx->stream; const FmIndex& ix = r.ix; const int ns = r.ns;
+    TDV_HIP(ctx, hipMemsetAsync(r.z, 0, sizeof(FmZeroed), s));
+    k_fm_locate<<<(ns + 255) / 256, 256, 0, s>>>(r.fs, ns, ix.basis, ix.S0, ix.S1, ix.b0, ix.b1, ix.col_leaf0, ix.leaf_p2, r.bucket_shift, r.home, r.bucket_of, r.sp, &r.z->amax_s);
+    const int sblocks = (ns + FMP_SORT_BLOCK - 1) / FMP_SORT_BLOCK;
+    k_fm_bucket_hist<<<sblocks, FMP_SORT_BLOCK, 0, s>>>(r.bucket_of, ns, r.z->hist);
+    TDV_TRY(exclusive_scan_dev(ctx, r.z->hist, FMP_BUCKETS, r.start, r.d_total));
+    k_fm_scatter<<<sblocks, FMP_SORT_BLOCK, 0, s>>>(r.bucket_of, ns, r.start, r.z->cursor, r.sperm);
+    return TDV_OK;
+}
+static FmTables fm_tables(const FmRun& r, const float* fs2) {
+    const FmIndex& ix = r.ix;
+    FmTables t;
+    t.fs = r.fs; t.sperm = r.sperm; t.home_of = r.home; t.ns = r.ns; t.fs2 = fs2;
+    t.T = ix.T; t.torig = ix.torig; t.nleaf = ix.nleaf; t.ngroup = ix.ngroup;
+    t.lbox = ix.lbox; t.gbox = ix.gbox; t.pbox = ix.pbox; t.gpbox = ix.gpbox;
+    t.sp = r.sp; t.amax_t = ix.amax; t.amax_s = &r.z->amax_s; t.pscale = ix.pscale;
+    return t;
+}
+
+// Step 2, the leaf-major search.  What one memset clears for it: per round of box tests [LM_POOLS][nleaf] pool_count | [LM_POOLS]
+// entry_cursor | overflow (two rounds: the second is the study build's), then round 0's overflow word.  The sizes depend on nleaf, so
+// instead of a struct with a static_assert this is the one place that knows the offsets.
+struct LmZeroed {
+    int* base; int nleaf;
+    size_t per_round() const { return (size_t)LM_POOLS * nleaf + LM_POOLS + 1; }
+    size_t words() const { return 2 * per_round() + 1; }
+    int* pool_count(int round) const { return base + (size_t)(round - 1) * per_round(); }     // round = 1, 2
+    int* entry_cursor(int round) const { return pool_count(round) + (size_t)LM_POOLS * nleaf; }
+    int* overflow(int round) const { return round == 0 ? base + 2 * per_round() : entry_cursor(round) + LM_POOLS; }
+};
+struct LmRun {
+    LmZeroed z; size_t pair_cap, pool_cap, unit_cap;
+    int4* entries; int *sorted_src, *leaf_count, *pool_start, *leaf_start, *unit_start, *unit_leaf; unsigned long long* keys;
+    unsigned long long* d_stats;       // study build, TDV_FM_STATS: [2][8] (k_lm_boxes)
+};
+// The lists of one round.  Round 0 (every source against its home leaf): the search order is sorted by home leaf, so it IS the
+// sorted pair list, and the histogram the ordering made is the count per leaf.
+static LmLists lm_lists(const FmRun& r, const LmRun& m, int round) {
+    LmLists L{};
+    L.overflow = m.z.overflow(round); L.keys = m.keys;
+    L.leaf_start = m.leaf_start; L.unit_start = m.unit_start; L.unit_leaf = m.unit_leaf; L.unit_cap = (int)m.unit_cap;
+    if (round == 0) { L.leaf_count = r.z->hist; L.sorted_src = r.sperm; L.pair_cap = INT_MAX; return L; }
+    L.pool_count = m.z.pool_count(round); L.entry_cursor = m.z.entry_cursor(round); L.pool_start = m.pool_start;
+    L.entries = m.entries; L.pool_cap = (int)m.pool_cap;
+    L.leaf_count = m.leaf_count; L.sorted_src = m.sorted_src; L.pair_cap = (int)m.pair_cap;
+    return L;
+}
+
+// Step 3, the walk.  Pass A over every source, then the sources it gave up on: few of them -> pass B (8 waves each on the packed
+// index); many of them (descriptors without structure, or a plateau of near-identical rows: no box can exclude anything) -> the
 // plain scan over just those sources, seeded with pass A's distances, which is the efficient way to do brute force.
-template <int K>
-static int launch_fm_query(tdv_ctx* ctx, const FmTables& t, const FmIndex& ix, int* overflow_count, int* overflow_list, int* overflow_src,
-                           float* part_d, int* part_j, int* d_corr) {
-    hipStream_t s = ctx->stream;
+// K sources per wave: 2.  K = 1 / 4 and STATS are instantiated by the study build alone (fmatch_study.hpp).
+int fm_walk_report(tdv_ctx* ctx, const FmTables& t, int K, const unsigned long long* d_stats, int n_b, int n_scan);   // fmatch_study.hpp
+template <int K, bool STATS>
+static int fm_walk(FmRun& r) {
+    tdv_ctx* ctx = r.ctx; hipStream_t s = ctx->stream; const FmIndex& ix = r.ix;
+    float* fs2 = nullptr;
+    if constexpr (K % 2 == 0) {
+        const size_t n2 = ((size_t)r.ns + K - 1) / K * K * FD;
+        TDV_TRY(ws_alloc(ctx, n2, &fs2));
+        k_fm_interleave_rows<<<(unsigned)((n2 + 255) / 256), 256, 0, s>>>(r.fs, r.sperm, r.ns, K, fs2);
+    }
+    const FmTables t = fm_tables(r, fs2);
+    int* overflow_count = r.z->overflow_count;
     const int waves = (t.ns + K - 1) / K;
     const int blocks_per_xcd = ((waves + FM_BLOCK / 64 - 1) / (FM_BLOCK / 64) + 7) / 8, blocks = blocks_per_xcd * 8;
-    // tuning knobs.  The leaf budget of pass A was 32 while a leaf cost what it did in the middle of round 2; with the packed
-    // arithmetic and the scalar-side savings a wave is better off opening up to 128 leaves itself than handing over early
-    // (143k x 151k relief part 0.81 -> 0.73 ms, cuboid 200k x 200k 4.05 -> 2.04 ms, random rows 100k x 100k 16.8 -> 17.7 ms)
-    static const int leaf_limit = study_env("TDV_FM_LIMIT") ? atoi(study_env("TDV_FM_LIMIT")) : 128;
-    static const int heavy_groups = study_env("TDV_FM_HEAVY") ? atoi(study_env("TDV_FM_HEAVY")) : 8;
-    const bool stats = study_env("TDV_FM_STATS") != nullptr;   // study knob: counts of box tests and leaf openings, printed to stderr
     unsigned long long* d_stats = nullptr;
-    if (stats) {
-        TDV_TRY(ws_alloc(ctx, 12, &d_stats));
-        TDV_HIP(ctx, hipMemsetAsync(d_stats, 0, 96, s));
-        k_fm_query<K, true><<<blocks, FM_BLOCK, 0, s>>>(t, blocks_per_xcd, leaf_limit, heavy_groups, overflow_count, overflow_list, overflow_src, part_d, part_j, d_corr, d_stats);
-    } else {
-        k_fm_query<K, false><<<blocks, FM_BLOCK, 0, s>>>(t, blocks_per_xcd, leaf_limit, heavy_groups, overflow_count, overflow_list, overflow_src, part_d, part_j, d_corr, nullptr);
-    }
+    if constexpr (STATS) { TDV_TRY(ws_alloc(ctx, 12, &d_stats)); TDV_HIP(ctx, hipMemsetAsync(d_stats, 0, 96, s)); }
+    k_fm_query<K, STATS><<<blocks, FM_BLOCK, 0, s>>>(t, blocks_per_xcd, r.knobs.leaf_limit, r.knobs.heavy_groups, overflow_count, r.overflow_walk, r.overflow_src, r.part_d, r.part_j, r.corr, d_stats);
     TDV_CHECK_LAUNCH(ctx);
     TDV_TRY(pin_reserve(ctx, 256));
     int* h_over = reinterpret_cast<int*>(ctx->pin);
@@ -1750,212 +1204,116 @@ static int launch_fm_query(tdv_ctx* ctx, const FmTables& t, const FmIndex& ix, i
     const bool scan_them = (long long)n_scan * K >= 2048;
     for (int cls = 0; cls < 2; ++cls) {
         const int n = cls == 0 ? n_b : (scan_them ? 0 : n_scan);
-        if (n <= 0) continue;
-        const int* list = overflow_list + (cls ? t.ns + 1 : 0);
-        const int bblocks = std::min(n, 1024);
-        if (stats) k_fm_query_overflow<K, true><<<bblocks, FMB_WAVES * 64, 0, s>>>(t, overflow_count + cls, list, part_d, part_j, d_corr, d_stats);
-        else k_fm_query_overflow<K, false><<<bblocks, FMB_WAVES * 64, 0, s>>>(t, overflow_count + cls, list, part_d, part_j, d_corr, nullptr);
+        if (n > 0) k_fm_query_overflow<K, STATS><<<std::min(n, 1024), FMB_WAVES * 64, 0, s>>>(t, overflow_count + cls, cls ? r.overflow_scan : r.overflow_walk, r.part_d, r.part_j, r.corr, d_stats);
     }
     if (n_scan > 0 && scan_them) {
         const int n_list = n_scan * K;
-        const int ns_pad = (int)align_up((size_t)t.ns, FM_SRC_PER_BLOCK);
-        const int blocks_x = (n_list + FM_SRC_PER_BLOCK - 1) / FM_SRC_PER_BLOCK;
-        const int want = (6144 + blocks_x - 1) / blocks_x;
-        int nsplit = std::max(1, std::min(std::min(want, std::max(1, ix.nt / 128)), 256));   // few sources: many target splits, or the chip stays empty
-        const int per_split = (ix.nt + nsplit - 1) / nsplit;
-        nsplit = (ix.nt + per_split - 1) / per_split;
+        const int ns_pad = (int)align_up((size_t)t.ns, FM_SRC_PER_BLOCK), blocks_x = (n_list + FM_SRC_PER_BLOCK - 1) / FM_SRC_PER_BLOCK;
+        const ScanSplits sp = scan_splits(blocks_x, ix.nt, 6144, 128, 256);   // few sources: many target splits, or the chip stays empty
         float* pd; int* pj;
-        TDV_TRY(ws_alloc(ctx, (size_t)nsplit * ns_pad, &pd));
-        TDV_TRY(ws_alloc(ctx, (size_t)nsplit * ns_pad, &pj));
-        k_feature_match_scan<true, false><<<dim3(blocks_x, nsplit), FM_BLOCK, 0, s>>>(t.fs, t.ns, ns_pad, ix.ft, 0, ix.nt, per_split, part_d, overflow_src, n_list, pd, pj);
-        k_feature_match_combine_list<<<(n_list + 255) / 256, 256, 0, s>>>(overflow_src, n_list, t.ns, ns_pad, nsplit, pd, pj, d_corr);
+        TDV_TRY(ws_alloc(ctx, (size_t)sp.nsplit * ns_pad, &pd));
+        TDV_TRY(ws_alloc(ctx, (size_t)sp.nsplit * ns_pad, &pj));
+        k_feature_match_scan<true, false><<<dim3(blocks_x, sp.nsplit), FM_BLOCK, 0, s>>>(t.fs, t.ns, ns_pad, ix.ft, 0, ix.nt, sp.per_split, r.part_d, r.overflow_src, n_list, pd, pj);
+        k_feature_match_combine_list<<<(n_list + 255) / 256, 256, 0, s>>>(r.overflow_src, n_list, t.ns, ns_pad, sp.nsplit, pd, pj, r.corr);
     }
     TDV_CHECK_LAUNCH(ctx);
-    if (stats) {
-        unsigned long long h[12];
-        TDV_HIP(ctx, hipMemcpyAsync(h, d_stats, 96, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-        fprintf(stderr, "[tdv] fm query: %d sources x %d leaves, %d groups, %d sources per wave, %llu waves: per wave %.1f group-chunk tests, "
-                "%.1f groups visited, %.1f leaves opened (max %llu); wave time mean %.1f us max %.1f us; gave up: %d waves to pass B "
-                "(%llu helper waves, %.1f leaves each, max %llu), %d waves to the plain scan\n",
-                t.ns, t.nleaf, t.ngroup, K, h[0], (double)h[1] / h[0], (double)h[2] / h[0], (double)h[3] / h[0], h[4],
-                (double)h[5] / h[0] * 0.01, (double)h[6] * 0.01, n_b, h[8], h[8] ? (double)h[9] / h[8] : 0.0, h[10], n_scan);
-    }
+    if constexpr (STATS) TDV_TRY(fm_walk_report(ctx, t, K, d_stats, n_b, n_scan));
     return TDV_OK;
 }
 
-// The leaf-major search (kernels above).  *done = false: the pair pool ran over (descriptors without structure) - the caller
-// runs k_fm_query and its fall-backs instead.  One synchronisation, like launch_fm_query.
-static int launch_fm_leafmajor(tdv_ctx* ctx, const FmTables& t, const FmIndex& ix, int* home_hist /* sources per home leaf: what the ordering counted */, int* d_corr, bool* done) {
-    hipStream_t s = ctx->stream;
+#ifdef TDV_STUDY
+#include "fmatch_study.hpp"     // the key-ordered scan, the K = 1 / 4 walks, the second round of box tests, the statistics reports
+#endif
+
+// *done = false: the pair pool ran over (descriptors without structure) - the caller walks the index instead.  One synchronisation,
+// like the walk.  One round of box tests after the home leaves: 12.1 pairs per source at 143k x 151k.  (Study build, TDV_LM_ROUNDS=2:
+// 9.7 pairs per source, but a second set of launches: 0.525 against 0.487 ms.)
+static int fm_leaf_major(FmRun& r, bool* done) {
+    tdv_ctx* ctx = r.ctx; hipStream_t s = ctx->stream; const FmIndex& ix = r.ix;
     *done = false;
-    const int nleaf = ix.nleaf;
-    const size_t pair_cap = (size_t)LM_PAIRS_PER_SOURCE * (size_t)t.ns + 4096;
-    const size_t pool_cap = ((size_t)t.ns + 4096) / LM_POOLS + 64;     // entries: one box x up to 64 sources each
-    if (pair_cap > (size_t)INT_MAX / 2) return TDV_OK;
-    const size_t unit_cap = pair_cap / 64 + (size_t)nleaf + 2, per_round = (size_t)LM_POOLS * nleaf + LM_POOLS + 1;
-    const int waves = (t.ns + 63) / 64;
-    int *zeroed, *sorted_src, *leaf_count, *pool_start, *leaf_start, *unit_start, *unit_leaf; unsigned long long* keys;
-    TDV_TRY(ws_alloc(ctx, 2 * per_round + 1, &zeroed));
-    int4* entries;
-    TDV_TRY(ws_alloc(ctx, pool_cap * LM_POOLS, &entries));
-    TDV_TRY(ws_alloc(ctx, pair_cap, &sorted_src));
-    TDV_TRY(ws_alloc(ctx, (size_t)nleaf, &leaf_count));
-    TDV_TRY(ws_alloc(ctx, (size_t)LM_POOLS * nleaf, &pool_start));
-    TDV_TRY(ws_alloc(ctx, (size_t)nleaf + 1, &leaf_start));
-    TDV_TRY(ws_alloc(ctx, (size_t)nleaf + 1, &unit_start));
-    TDV_TRY(ws_alloc(ctx, unit_cap, &unit_leaf));
-    TDV_TRY(ws_alloc(ctx, (size_t)t.ns, &keys));
+    const int nleaf = ix.nleaf, ns = r.ns, waves = (ns + 63) / 64;
+    LmRun m{};
+    m.z.nleaf = nleaf;
+    m.pair_cap = (size_t)LM_PAIRS_PER_SOURCE * (size_t)ns + 4096;
+    m.pool_cap = ((size_t)ns + 4096) / LM_POOLS + 64;     // entries: one box x up to 64 sources each
+    if (m.pair_cap > (size_t)INT_MAX / 2) return TDV_OK;
+    m.unit_cap = m.pair_cap / 64 + (size_t)nleaf + 2;
+    TDV_TRY(ws_alloc(ctx, m.z.words(), &m.z.base));
+    TDV_TRY(ws_alloc(ctx, m.pool_cap * LM_POOLS, &m.entries));
+    TDV_TRY(ws_alloc(ctx, m.pair_cap, &m.sorted_src));
+    TDV_TRY(ws_alloc(ctx, (size_t)nleaf, &m.leaf_count));
+    TDV_TRY(ws_alloc(ctx, (size_t)LM_POOLS * nleaf, &m.pool_start));
+    TDV_TRY(ws_alloc(ctx, (size_t)nleaf + 1, &m.leaf_start));
+    TDV_TRY(ws_alloc(ctx, (size_t)nleaf + 1, &m.unit_start));
+    TDV_TRY(ws_alloc(ctx, m.unit_cap, &m.unit_leaf));
+    TDV_TRY(ws_alloc(ctx, (size_t)ns, &m.keys));
     TDV_TRY(pin_reserve(ctx, 256));
     int* h_flag = reinterpret_cast<int*>(ctx->pin);
     h_flag[0] = 1;
-    TDV_HIP(ctx, hipMemsetAsync(zeroed, 0, (2 * per_round + 1) * 4, s));
-    LmLists L[3];
-    for (int r = 0; r < 2; ++r) {
-        int* z = zeroed + r * per_round;
-        L[r + 1] = LmLists{z, z + (size_t)LM_POOLS * nleaf, z + (size_t)LM_POOLS * nleaf + LM_POOLS, leaf_count, pool_start, entries, (int)pool_cap, (int)pair_cap, leaf_start, unit_start, unit_leaf, sorted_src, keys, (int)unit_cap};
+    TDV_HIP(ctx, hipMemsetAsync(m.z.base, 0, m.z.words() * 4, s));
+    const FmTables t = fm_tables(r, nullptr);
+    if (r.knobs.stats) { TDV_TRY(ws_alloc(ctx, 16, &m.d_stats)); TDV_HIP(ctx, hipMemsetAsync(m.d_stats, 0, 128, s)); }
+    const int rounds = ix.ngroup > 1 ? r.knobs.lm_rounds : 1;
+    const LmLists L0 = lm_lists(r, m, 0);
+    k_lm_plan<false><<<1, 1024, 0, s>>>(L0, nleaf);
+    k_lm_eval<true><<<r.knobs.eval_blocks, 64 * LM_WAVES, 0, s>>>(t, L0);
+    for (int round = 1; round <= rounds; ++round) {
+        const LmLists L = lm_lists(r, m, round);
+        if (rounds == 1 && ix.ngroup > 1) k_lm_boxes<3><<<waves, 64 * LM_BOX_WAVES, 0, s>>>(t, ix.sleaf, ix.sgroup, L, m.d_stats);      // every group, group boxes first
+        else if (round == 1) k_lm_boxes<1><<<waves, 64 * LM_BOX_WAVES, 0, s>>>(t, ix.sleaf, ix.sgroup, L, m.d_stats);                   // a single group (or the first of two rounds): the home groups' leaves
+#ifdef TDV_STUDY
+        else lm_study_second_round(s, t, ix, L, waves, m.d_stats);
+#endif
+        k_lm_plan<true><<<1, 1024, 0, s>>>(L, nleaf);
+        k_lm_scatter<<<LM_POOLS, 1024, (size_t)nleaf * 4, s>>>(L, nleaf);
+        k_lm_eval<false><<<r.knobs.eval_blocks, 64 * LM_WAVES, 0, s>>>(t, L);
     }
-    // round 0: every source against its home leaf.  The search order is sorted by home leaf, so it IS the sorted pair list.
-    L[0] = LmLists{nullptr, nullptr, zeroed + 2 * per_round, home_hist, nullptr, nullptr, 0, INT_MAX, leaf_start, unit_start, unit_leaf, const_cast<int*>(t.sperm), keys, (int)unit_cap};
-    unsigned long long* d_stats = nullptr;
-    if (study_env("TDV_FM_STATS")) { TDV_TRY(ws_alloc(ctx, 16, &d_stats)); TDV_HIP(ctx, hipMemsetAsync(d_stats, 0, 128, s)); }
-    static const int eval_blocks = study_env("TDV_LM_EVAL_BLOCKS") ? atoi(study_env("TDV_LM_EVAL_BLOCKS")) : 4096;   // tuning knob (a multiple of 8; 1024 / 2048 / 4096 / 8192: 0.51 / 0.49 / 0.477 / 0.478 ms at 143k x 151k)
-    // One round of box tests after the home leaves (12.1 pairs per source at 143k x 151k).  TDV_LM_ROUNDS=2: the home groups first, the
-    // other groups with the bounds those left (9.7 pairs per source, but a second set of launches: 0.525 against 0.487 ms).
-    const char* rounds_env = study_env("TDV_LM_ROUNDS");
-    const int rounds = (ix.ngroup > 1 && rounds_env && atoi(rounds_env) == 2) ? 2 : 1;
-    k_lm_plan<false><<<1, 1024, 0, s>>>(L[0], nleaf);
-    k_lm_eval<true><<<eval_blocks, 64 * LM_WAVES, 0, s>>>(t, L[0]);
-    for (int r = 1; r <= rounds; ++r) {
-        if (rounds == 1 && ix.ngroup > 1) k_lm_boxes<3><<<waves, 64 * LM_BOX_WAVES, 0, s>>>(t, ix.sleaf, ix.sgroup, L[r], d_stats);
-        else if (r == 1) k_lm_boxes<1><<<waves, 64 * LM_BOX_WAVES, 0, s>>>(t, ix.sleaf, ix.sgroup, L[r], d_stats);
-        else k_lm_boxes<2><<<waves, 64 * LM_BOX_WAVES, 0, s>>>(t, ix.sleaf, ix.sgroup, L[r], d_stats ? d_stats + 8 : nullptr);
-        k_lm_plan<true><<<1, 1024, 0, s>>>(L[r], nleaf);
-        k_lm_scatter<<<LM_POOLS, 1024, (size_t)nleaf * 4, s>>>(L[r], nleaf);
-        k_lm_eval<false><<<eval_blocks, 64 * LM_WAVES, 0, s>>>(t, L[r]);
-    }
-    k_lm_finish<<<(t.ns + 255) / 256, 256, 0, s>>>(keys, t.ns, L[1].overflow, L[2].overflow, d_corr, h_flag);
+    k_lm_finish<<<(ns + 255) / 256, 256, 0, s>>>(m.keys, ns, m.z.overflow(1), m.z.overflow(2), r.corr, h_flag);
     TDV_CHECK_LAUNCH(ctx);
     TDV_HIP(ctx, hipStreamSynchronize(s));
     *done = h_flag[0] == 0;
-    if (d_stats) {                                           // study knob
-        int h[2][LM_POOLS + 1];
-        long long pairs[2] = {0, 0};
-        for (int r = 0; r < 2; ++r) {
-            TDV_HIP(ctx, hipMemcpy(h[r], L[r + 1].entry_cursor, (LM_POOLS + 1) * 4, hipMemcpyDeviceToHost));
-            for (int k = 0; k < LM_POOLS; ++k) pairs[r] += h[r][k];
-        }
-        fprintf(stderr, "[tdv] fm leaf-major: %d sources x %d leaves in %d groups: round 1 %lld entries (%.2f per source)%s, round 2 %lld entries (%.2f per source)%s\n",
-                t.ns, nleaf, ix.ngroup, pairs[0], (double)pairs[0] / t.ns, h[0][LM_POOLS] ? " OVERFLOW" : "", pairs[1], (double)pairs[1] / t.ns, h[1][LM_POOLS] ? " OVERFLOW" : "");
-        unsigned long long st[16];
-        TDV_HIP(ctx, hipMemcpy(st, d_stats, 128, hipMemcpyDeviceToHost));
-        for (int r = 0; r < 2; ++r) {
-            const unsigned long long* q = st + 8 * r; const double w = (double)std::max(1ull, q[0]);
-            fprintf(stderr, "[tdv]   boxes round %d: %llu waves, per wave %.1f us (max %.1f), %.1f us until the source is loaded, %.1f us last flush; %.1f 3-D tests, %.1f 33-D tests, %.1f boxes emitted\n",
-                    r + 1, q[0], q[1] / w * 0.01, q[7] * 0.01, q[2] / w * 0.01, q[3] / w * 0.01, q[4] / w, q[5] / w, q[6] / w);
-        }
-    }
+#ifdef TDV_STUDY
+    if (m.d_stats) TDV_TRY(lm_study_report(r, m));
+#endif
     return TDV_OK;
 }
 
 int feature_match_indexed_dev(tdv_ctx* ctx, const float* d_fs, int ns, const FmIndex& ix, int* d_corr) {
     if (!ctx || !d_fs || !d_corr || ns < 0) return TDV_ERR_BAD_ARG;
     if (ns == 0) return TDV_OK;
-    hipStream_t s = ctx->stream;
-    int bucket_shift = 0;
-    while ((ix.nleaf >> bucket_shift) > FMP_BUCKETS) ++bucket_shift;
-    int *home, *bucket_of, *sperm, *hist, *cursor, *start, *d_total; float* sp; unsigned* amax_s;
-    int *overflow_count, *overflow_list, *overflow_src, *part_j; float* part_d;
-    int* zeroed;                                                   // hist | cursor | overflow_count[2] | amax_s: one memset
-    TDV_TRY(ws_alloc(ctx, (size_t)2 * FMP_BUCKETS + 4, &zeroed));
-    hist = zeroed; cursor = zeroed + FMP_BUCKETS; overflow_count = zeroed + 2 * FMP_BUCKETS; amax_s = reinterpret_cast<unsigned*>(zeroed + 2 * FMP_BUCKETS + 2);
-    TDV_TRY(ws_alloc(ctx, (size_t)2 * ns + 8, &overflow_list));   // two halves: pass-B class, scan class
-    TDV_TRY(ws_alloc(ctx, (size_t)ns + 8, &overflow_src));
-    TDV_TRY(ws_alloc(ctx, (size_t)ns, &part_d));
-    TDV_TRY(ws_alloc(ctx, (size_t)ns, &part_j));
-    TDV_TRY(ws_alloc(ctx, (size_t)ns * 4, &sp));
-    TDV_TRY(ws_alloc(ctx, (size_t)ns, &home));
-    TDV_TRY(ws_alloc(ctx, (size_t)ns, &bucket_of));
-    TDV_TRY(ws_alloc(ctx, (size_t)ns, &sperm));
-    TDV_TRY(ws_alloc(ctx, (size_t)FMP_BUCKETS + 1, &start));
-    TDV_TRY(ws_alloc(ctx, 1, &d_total));
+    FmRun r{ctx, ix, d_fs, ns, d_corr, fm_knobs()};
+    TDV_TRY(fm_alloc(r));
     ScopedTimer tm(ctx, TDV_TIMER_FEATURE_MATCH);
-    TDV_HIP(ctx, hipMemsetAsync(zeroed, 0, ((size_t)2 * FMP_BUCKETS + 4) * 4, s));
-    k_fm_locate<<<(ns + 255) / 256, 256, 0, s>>>(d_fs, ns, ix.basis, ix.S0, ix.S1, ix.b0, ix.b1, ix.col_leaf0, ix.leaf_p2, bucket_shift, home, bucket_of, sp, amax_s);
-    const int sblocks = (ns + FMP_SORT_BLOCK - 1) / FMP_SORT_BLOCK;
-    k_fm_bucket_hist<<<sblocks, FMP_SORT_BLOCK, 0, s>>>(bucket_of, ns, hist);
-    TDV_TRY(exclusive_scan_dev(ctx, hist, FMP_BUCKETS, start, d_total));
-    k_fm_scatter<<<sblocks, FMP_SORT_BLOCK, 0, s>>>(bucket_of, ns, start, cursor, sperm);
-    static const int force_k = study_env("TDV_FM_K") ? atoi(study_env("TDV_FM_K")) : 0;   // tuning knob (sources per wave)
-    const int k = force_k ? force_k : 2;
-    float* fs2 = nullptr;
-    const char* lm = getenv("TDV_FM_LEAFMAJOR");                  // A/B knob, read per call: 0 = round 2's walk (k_fm_query) for everything
-    if (!(lm && atoi(lm) == 0) && ix.sleaf && bucket_shift == 0) {     // (bucket_shift: more than 16,384 leaves - the ordering's histogram is then not per leaf)
-        FmTables t{d_fs, sperm, home, ns, nullptr, ix.T, ix.torig, ix.nleaf, ix.ngroup, ix.lbox, ix.gbox, ix.pbox, ix.gpbox, sp, ix.amax, amax_s, ix.pscale};
+    TDV_TRY(fm_locate_and_order(r));
+    if (!r.knobs.walk_only && ix.sleaf && r.bucket_shift == 0) {     // (bucket_shift: more than 16,384 leaves - the ordering's histogram is then not per leaf)
         bool done = false;
-        TDV_TRY(launch_fm_leafmajor(ctx, t, ix, hist, d_corr, &done));
+        TDV_TRY(fm_leaf_major(r, &done));
         if (done) { ctx->last_fm_path = TDV_FM_PATH_LEAF_MAJOR; return TDV_OK; }
     }
     ctx->last_fm_path = TDV_FM_PATH_WALK;
-    if (k >= 2) {
-        const int kk = k >= 4 ? 4 : 2;
-        const size_t n2 = ((size_t)ns + kk - 1) / kk * kk * FD;
-        TDV_TRY(ws_alloc(ctx, n2, &fs2));
-        k_fm_interleave_rows<<<(unsigned)((n2 + 255) / 256), 256, 0, s>>>(d_fs, sperm, ns, kk, fs2);
-    }
-    FmTables t{d_fs, sperm, home, ns, fs2, ix.T, ix.torig, ix.nleaf, ix.ngroup, ix.lbox, ix.gbox, ix.pbox, ix.gpbox, sp, ix.amax, amax_s, ix.pscale};
 #ifdef TDV_STUDY
-    if (k >= 4) return launch_fm_query<4>(ctx, t, ix, overflow_count, overflow_list, overflow_src, part_d, part_j, d_corr);
-    if (k < 2) return launch_fm_query<1>(ctx, t, ix, overflow_count, overflow_list, overflow_src, part_d, part_j, d_corr);
+    return fm_study_walk(r);
+#else
+    return fm_walk<2, false>(r);
 #endif
-    return launch_fm_query<2>(ctx, t, ix, overflow_count, overflow_list, overflow_src, part_d, part_j, d_corr);      // two sources per wave (1 and 4: measured slower, study build)
 }
 
 int feature_match_dev(tdv_ctx* ctx, const float* d_fs, int ns, const float* d_ft, int nt, int* d_corr) {
     if (!ctx || !d_fs || !d_ft || !d_corr || ns < 0 || nt < 0) return TDV_ERR_BAD_ARG;
     if (ns == 0) return TDV_OK;
-    hipStream_t s = ctx->stream;
-    if (nt == 0) { TDV_HIP(ctx, hipMemsetAsync(d_corr, 0, (size_t)ns * 4, s)); return TDV_OK; }
+    if (nt == 0) { TDV_HIP(ctx, hipMemsetAsync(d_corr, 0, (size_t)ns * 4, ctx->stream)); return TDV_OK; }
     ctx->last_fm_path = TDV_FM_PATH_SCAN;
-    const char* brute = getenv("TDV_FM_BRUTE");         // A/B knobs: same results every way
-    const char* keyorder = study_env("TDV_FM_KEYORDER");
-    if (!brute && ns >= 4096 && nt >= 2048) {
-#ifdef TDV_STUDY
-        if (keyorder) return feature_match_keyorder_dev(ctx, d_fs, ns, d_ft, nt, d_corr);      // round 1's key-ordered pruned scan
-#endif
-        (void)keyorder;
+    if (fm_indexes_sources(ns) && fm_wants_index(nt)) {
         FmIndex ix;
         TDV_TRY(fm_index_build(ctx, d_ft, nt, &ix));
         return feature_match_indexed_dev(ctx, d_fs, ns, ix, d_corr);
     }
-    static const bool early = study_env("TDV_FM_NO_EARLY_EXIT") == nullptr;   // A/B knob: same results either way
-    const int ns_pad = (int)align_up((size_t)ns, FM_SRC_PER_BLOCK);
-    const int blocks_x = ns_pad / FM_SRC_PER_BLOCK;
-    // part 0: the first n_seed targets in one split (its exact best seeds the bound of every later split)
-    const int n_seed = early ? std::min(nt, FM_SEED) : 0;
-    const int rest = nt - n_seed;
-    int want = (4096 + blocks_x - 1) / blocks_x;
-    int nsplit = rest > 0 ? std::max(1, std::min(std::min(want, std::max(1, rest / 64)), 64)) : 0;
-    int per_split = nsplit ? (rest + nsplit - 1) / nsplit : 0;
-    nsplit = nsplit ? (rest + per_split - 1) / per_split : 0;
-    const int nparts = nsplit + (n_seed ? 1 : 0);
-    float* pd; int* pj;
-    TDV_TRY(ws_alloc(ctx, (size_t)nparts * ns_pad, &pd));
-    TDV_TRY(ws_alloc(ctx, (size_t)nparts * ns_pad, &pj));
-    {
-        ScopedTimer tm(ctx, TDV_TIMER_FEATURE_MATCH);
-        if (early) {
-            k_feature_match_scan<true, true><<<dim3(blocks_x, 1), FM_BLOCK, 0, s>>>(d_fs, ns, ns_pad, d_ft, 0, n_seed, n_seed, nullptr, nullptr, 0, pd, pj);
-            if (nsplit)   // (ordering the sources by seed distance was measured: no gain on FPFH descriptors, so rows stay in place)
-                k_feature_match_scan<true, true><<<dim3(blocks_x, nsplit), FM_BLOCK, 0, s>>>(d_fs, ns, ns_pad, d_ft, n_seed, nt, per_split, pd, nullptr, 0,
-                                                                                      pd + ns_pad, pj + ns_pad);
-        } else {
-            k_feature_match_scan<false, true><<<dim3(blocks_x, nsplit), FM_BLOCK, 0, s>>>(d_fs, ns, ns_pad, d_ft, 0, nt, per_split, nullptr, nullptr, 0, pd, pj);
-        }
-    }
-    k_feature_match_combine<<<(ns + 255) / 256, 256, 0, s>>>(ns, ns_pad, nparts, pd, pj, d_corr);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
+#ifdef TDV_STUDY
+    bool answered = false;
+    const int rc = fm_study_match(ctx, d_fs, ns, d_ft, nt, d_corr, &answered);      // the key-ordered scan, the scan without early exit
+    if (answered) return rc;
+#endif
+    return fm_scan_all<true>(ctx, d_fs, ns, d_ft, nt, d_corr);
 }
 
 }  // namespace tdv

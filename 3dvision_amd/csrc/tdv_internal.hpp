@@ -103,6 +103,13 @@ constexpr bool kStudyBuild = false;
 #endif
 
 #ifdef __HIPCC__
+// ascending order of the 16-byte records that sort.hip sorts: (x, y, z, w) as unsigned words
+__device__ __forceinline__ bool rec_less(const uint4& a, const uint4& b) {
+    if (a.x != b.x) return a.x < b.x;
+    if (a.y != b.y) return a.y < b.y;
+    if (a.z != b.z) return a.z < b.z;
+    return a.w < b.w;
+}
 // Sum over the 64 lanes of a wave with DPP row operations (no LDS crossbar traffic, unlike __shfl_down): the result is
 // valid in lane 63 and returned wave-uniform.
 __device__ __forceinline__ int wave_sum_i32(int v) {
@@ -220,19 +227,23 @@ int fgr_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, in
 // nothing was computed (a cloud too large, too many hypotheses, or the index sampler ran out of draws) - use ransac_run_dev.
 int ransac_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* h_off, const int* d_off, int n_clouds, const float* d_tgt, int nt, const int* d_corr,
                            float voxel, int max_iterations, float confidence, uint32_t seed, tdv_ransac_result* out, int* fell_back);
+// The descriptor match (fmatch.hip).  Which calls use the packed index, said once: a target set is indexed when fm_wants_index(nt)
+// (at least 2,048 targets, and neither TDV_FM_BRUTE nor the study build's TDV_FM_KEYORDER asks for another search; read per call),
+// and a call searches the index when it brings fm_indexes_sources(ns) (at least 4,096 sources); every other call is the plain scan.
+bool fm_wants_index(int nt);
+bool fm_indexes_sources(int ns);
 int feature_match_dev(tdv_ctx* ctx, const float* d_fs, int ns, const float* d_ft, int nt, int* d_corr);
-// Packed index of a target descriptor set (fmatch.hip): rows in sort-tile-recursive order along the set's principal
-// directions, padded per column, with 33-D boxes of the 64-row leaves and the 64-leaf groups.  Lives in the workspace
-// of the ctx that built it (valid until that ctx's next ws_reset / rewind below the build); read-only afterwards, so a
+// Packed index of a target descriptor set (fmatch_index.hip; every array's layout: fmatch_layout.hpp): rows in sort-tile-recursive
+// order along the set's principal directions, padded per column, with boxes of the 64-row leaves and the 64-leaf groups.  Lives in
+// the workspace of the ctx that built it (valid until that ctx's next ws_reset / rewind below the build); read-only afterwards, so a
 // batch builds it once for the model and every instance (on either lane) queries it.
 struct FmIndex {
     const float* ft = nullptr;                                      // the caller's rows, [nt][33] (must outlive the index: the fallback scan reads them)
-    float* T = nullptr; int* torig = nullptr;                       // [leaf][33][64] (row r = column r % 64 of leaf r / 64), [rows] (INT_MAX = padding)
-    float* lbox = nullptr;                                          // leaf boxes [group][min | max][33][64 leaves]
-    float* gbox = nullptr;                                          // group boxes [chunk of 64 groups][min | max][33][64 groups]
-    float *pbox = nullptr, *gpbox = nullptr;                        // the same for the 3 principal coordinates: [..][min | max][3][64]
-    float *sleaf = nullptr, *sgroup = nullptr;                      // the same boxes once more, one box = 72 consecutive floats (min[33] | max[33] | pmin[3] | pmax[3]): staged in LDS by the leaf-major search (k_lm_boxes)
-    unsigned* amax = nullptr; float pscale = 0.f;                   // largest |x_d - mean_d| of the targets (float bits); 0 disables the 3-D boxes
+    float* T = nullptr; int* torig = nullptr;                       // the packed rows and their original indices
+    float *lbox = nullptr, *gbox = nullptr;                         // 33-D boxes of the leaves and of the groups
+    float *pbox = nullptr, *gpbox = nullptr;                        // ... and their boxes in the 3 principal coordinates
+    float *sleaf = nullptr, *sgroup = nullptr;                      // the same boxes as the leaf-major search stages them
+    unsigned* amax = nullptr; float pscale = 0.f;                   // largest |x_d - mean_d| of the targets (float bits); pscale 0 disables the 3-D boxes
     float *basis = nullptr, *b0 = nullptr, *b1 = nullptr, *leaf_p2 = nullptr; const int* col_leaf0 = nullptr;   // locating a source's cell
     int nt = 0, rows = 0, nleaf = 0, ngroup = 0, S0 = 1, S1 = 1;
 };
@@ -281,15 +292,15 @@ int voxel_reference_order_batch_dev(tdv_ctx* ctx, int n_clouds, const int* h_vof
 int voxel_reference_order(tdv_ctx* ctx, int v, int n, const int4* d_leaders, const float* tmp_xyz, const float* tmp_rgb, const int* d_rank, int rank_base,
                           float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both);
 
-int sort_records_dev(tdv_ctx* ctx, uint4* rec, size_t n_pow2);  // voxel.hip: ascending bitonic sort, n_pow2 >= 2048
+int sort_records_dev(tdv_ctx* ctx, uint4* rec, size_t n_pow2);  // sort.hip: ascending bitonic sort, n_pow2 >= 2048
 // sort.hip: stable LSD radix sort (hand-written) of (key, value) pairs on the low end_bit bits of the 64-bit key; any n; scratch from the workspace
 int radix_sort_pairs_dev(tdv_ctx* ctx, const unsigned long long* d_keys_in, unsigned long long* d_keys_out,
                          const unsigned* d_vals_in, unsigned* d_vals_out, size_t n, int end_bit);
-// every segment [d_seg_start[c], d_seg_start[c + 1]) sorted on its own in one launch; segments of at most segment_sort_max_len() records
+// sort.hip: every segment [d_seg_start[c], d_seg_start[c + 1]) sorted on its own in one launch; segments of at most segment_sort_max_len() records
 int segment_sort_records_dev(tdv_ctx* ctx, uint4* rec, const int* d_seg_start, int nseg);
 int segment_sort_max_len();
 size_t sort_pow2(size_t n);
-int exclusive_scan_dev(tdv_ctx* ctx, const int* d_in, int n, int* d_out, int* d_total);  // voxel.hip
+int exclusive_scan_dev(tdv_ctx* ctx, const int* d_in, int n, int* d_out, int* d_total);  // sort.hip
 // Morton-ordered copy of a cloud with the bounding boxes of its 64-point leaves and 4096-point groups (workspace memory):
 // sx/sy/sz are padded with +inf to `pad` (a multiple of 256), orig[i] = original index of sorted position i.
 // Box arrays are [6][count]: min x,y,z then max x,y,z.

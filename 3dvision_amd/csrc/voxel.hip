@@ -8,11 +8,11 @@
 // The reference groups with std::unordered_map and emits voxels in that container's iteration
 // order.  Here grouping is by hashing + tiny per-bucket sorts (below), with a full sort as the fallback:
 //   1. k_voxel_records   : record (kx, ky, kz, idx) per point
-//   2. bitonic sort      : ascending by (kx, ky, kz, idx) as unsigned words — members of a voxel
+//   2. bitonic sort      : (sort.hip) ascending by (kx, ky, kz, idx) as unsigned words — members of a voxel
 //                          become one run, in ascending input index (LDS-tiled local passes,
 //                          global passes only for strides >= the 2048-record tile)
 //   3. k_voxel_heads     : run heads; a run's first record carries the voxel's smallest index
-//   4. exclusive scan    : rank of every leader index = voxel position in FIRST-OCCURRENCE order
+//   4. exclusive scan    : (sort.hip) rank of every leader index = voxel position in FIRST-OCCURRENCE order
 //   5. k_voxel_means     : one lane per run, sequential sum in run order -> mean -> out[rank]
 // TDV_VOXEL_ORDER_FIRST stops here.  TDV_VOXEL_ORDER_REFERENCE additionally replays the
 // reference's container on the host (same key, same hash, the node-list manipulation of this libstdc++'s
@@ -30,15 +30,6 @@
 
 namespace tdv {
 
-constexpr int BT_TILE = 2048;     // records per LDS tile (32 KB)
-constexpr int BT_THREADS = 1024;  // one compare-exchange per thread per pass
-
-__device__ __forceinline__ bool rec_less(const uint4& a, const uint4& b) {
-    if (a.x != b.x) return a.x < b.x;
-    if (a.y != b.y) return a.y < b.y;
-    if (a.z != b.z) return a.z < b.z;
-    return a.w < b.w;
-}
 
 __global__ void k_voxel_records(const float* __restrict__ xyz, int n, int n_pow2, float inv, uint4* __restrict__ rec) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,127 +45,6 @@ __global__ void k_voxel_records(const float* __restrict__ xyz, int n, int n_pow2
     }
     rec[i] = r;
 }
-
-__device__ __forceinline__ void cmpxchg(uint4& a, uint4& b, bool ascending) {
-    bool sw = ascending ? rec_less(b, a) : rec_less(a, b);
-    if (sw) { uint4 t = a; a = b; b = t; }
-}
-
-// full bitonic sort of each 2048-record tile (all k <= BT_TILE)
-__global__ __launch_bounds__(BT_THREADS)
-void k_bitonic_local_sort(uint4* __restrict__ rec) {
-    __shared__ uint4 s[BT_TILE];
-    const size_t base = (size_t)blockIdx.x * BT_TILE;
-    const int t = threadIdx.x;
-    s[t] = rec[base + t]; s[t + BT_THREADS] = rec[base + t + BT_THREADS];
-    __syncthreads();
-    for (int k = 2; k <= BT_TILE; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            int i = ((t / j) * (j << 1)) + (t % j);
-            bool asc = (((base + i) & (size_t)k) == 0);
-            cmpxchg(s[i], s[i + j], asc);
-            __syncthreads();
-        }
-    }
-    rec[base + t] = s[t]; rec[base + t + BT_THREADS] = s[t + BT_THREADS];
-}
-
-// one global compare-exchange pass (stride j >= BT_TILE)
-__global__ __launch_bounds__(256)
-void k_bitonic_global_step(uint4* __restrict__ rec, size_t n_pairs, unsigned k, unsigned j) {
-    size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_pairs) return;
-    size_t i = ((t / j) * ((size_t)j << 1)) + (t % j);
-    uint4 a = rec[i], b = rec[i + j];
-    bool asc = ((i & (size_t)k) == 0);
-    bool sw = asc ? rec_less(b, a) : rec_less(a, b);
-    if (sw) { rec[i] = b; rec[i + j] = a; }
-}
-
-// two global passes in one launch (strides j and j / 2, both >= BT_TILE): a thread holds the four records its two
-// compare-exchanges per pass touch.  The sort of 131k-262k records is a chain of ~30 tiny launches; this removes a third.
-__global__ __launch_bounds__(256)
-void k_bitonic_global_step2(uint4* __restrict__ rec, size_t n_quads, unsigned k, unsigned j) {
-    const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (t >= n_quads) return;
-    const size_t h = j >> 1;                                              // the second stride
-    const size_t i = ((t / h) * ((size_t)j << 1)) + (t % h);              // bits j and h of i are clear
-    uint4 a = rec[i], b = rec[i + h], c = rec[i + j], d = rec[i + j + h];
-    const bool asc = ((i & (size_t)k) == 0);                              // k > j: the same for all four
-    cmpxchg(a, c, asc); cmpxchg(b, d, asc);                               // stride j
-    cmpxchg(a, b, asc); cmpxchg(c, d, asc);                               // stride j / 2
-    rec[i] = a; rec[i + h] = b; rec[i + j] = c; rec[i + j + h] = d;
-}
-
-// all passes with stride < BT_TILE of merge stage k, inside LDS
-__global__ __launch_bounds__(BT_THREADS)
-void k_bitonic_local_merge(uint4* __restrict__ rec, unsigned k) {
-    __shared__ uint4 s[BT_TILE];
-    const size_t base = (size_t)blockIdx.x * BT_TILE;
-    const int t = threadIdx.x;
-    s[t] = rec[base + t]; s[t + BT_THREADS] = rec[base + t + BT_THREADS];
-    __syncthreads();
-    for (int j = BT_TILE >> 1; j > 0; j >>= 1) {
-        int i = ((t / j) * (j << 1)) + (t % j);
-        bool asc = (((base + i) & (size_t)k) == 0);
-        cmpxchg(s[i], s[i + j], asc);
-        __syncthreads();
-    }
-    rec[base + t] = s[t]; rec[base + t + BT_THREADS] = s[t + BT_THREADS];
-}
-
-// ascending bitonic sort of n_pow2 (power of two, >= BT_TILE) uint4 records by (x, y, z, w); also used by knn.hip
-int sort_records_dev(tdv_ctx* ctx, uint4* rec, size_t n_pow2) {
-    hipStream_t s = ctx->stream;
-    const unsigned tiles = (unsigned)(n_pow2 / BT_TILE);
-    k_bitonic_local_sort<<<tiles, BT_THREADS, 0, s>>>(rec);
-    for (size_t k = (size_t)BT_TILE << 1; k <= n_pow2; k <<= 1) {
-        for (size_t j = k >> 1; j >= BT_TILE; j >>= 1) {
-            if ((j >> 1) >= BT_TILE) {
-                k_bitonic_global_step2<<<(unsigned)((n_pow2 / 4 + 255) / 256), 256, 0, s>>>(rec, n_pow2 / 4, (unsigned)k, (unsigned)j);
-                j >>= 1;
-            } else {
-                k_bitonic_global_step<<<(unsigned)((n_pow2 / 2 + 255) / 256), 256, 0, s>>>(rec, n_pow2 / 2, (unsigned)k, (unsigned)j);
-            }
-        }
-        k_bitonic_local_merge<<<tiles, BT_THREADS, 0, s>>>(rec, (unsigned)k);
-    }
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-
-// Every segment [seg_start[c], seg_start[c + 1]) of rec sorted on its own, one workgroup and one launch for all of them:
-// for segments of at most BT_TILE records (the caller checks), e.g. the columns of the descriptor index, whose records
-// only have to be ordered inside their column.
-__global__ __launch_bounds__(BT_THREADS)
-void k_bitonic_segment_sort(uint4* __restrict__ rec, const int* __restrict__ seg_start) {
-    __shared__ uint4 s[BT_TILE];
-    const int c0 = seg_start[blockIdx.x], m = seg_start[blockIdx.x + 1] - c0;
-    if (m <= 1) return;
-    const int t = threadIdx.x;
-    const uint4 pad = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);
-    s[t] = t < m ? rec[(size_t)c0 + t] : pad;
-    s[t + BT_THREADS] = t + BT_THREADS < m ? rec[(size_t)c0 + t + BT_THREADS] : pad;
-    __syncthreads();
-    int span = 2;
-    while (span < m) span <<= 1;                      // the padded power of two that holds the segment
-    for (int k = 2; k <= span; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            const int i = ((t / j) * (j << 1)) + (t % j);
-            if (i + j < span) cmpxchg(s[i], s[i + j], (i & k) == 0);
-            __syncthreads();
-        }
-    }
-    if (t < m) rec[(size_t)c0 + t] = s[t];
-    if (t + BT_THREADS < m) rec[(size_t)c0 + t + BT_THREADS] = s[t + BT_THREADS];
-}
-int segment_sort_records_dev(tdv_ctx* ctx, uint4* rec, const int* d_seg_start, int nseg) {
-    if (nseg <= 0) return TDV_OK;
-    k_bitonic_segment_sort<<<nseg, BT_THREADS, 0, ctx->stream>>>(rec, d_seg_start);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-int segment_sort_max_len() { return BT_TILE; }
 
 // ---- grouping by hashing (the default; the bitonic sort above is the fallback) -------------------------------------
 // Members of a voxel only have to become one run in ascending input index; the order of the runs is irrelevant
@@ -292,87 +162,6 @@ __global__ void k_voxel_leader_list(const int* __restrict__ leader, const int* _
     if (i < n && leader[i])
         leaders[rank[i]] = make_int4(cvt_i32_x86(floorf(xyz[3 * (size_t)i] * inv)), cvt_i32_x86(floorf(xyz[3 * (size_t)i + 1] * inv)),
                                      cvt_i32_x86(floorf(xyz[3 * (size_t)i + 2] * inv)), i);
-}
-
-// exclusive scan of n ints in TWO launches: per-block (4096 items: 1024 threads x 4) reduce whose LAST workgroup (atomic
-// ticket) scans the block sums, then the local scan.  (Round 1 used three launches; the scan sits on every grouping path —
-// voxel x2, Morton order, descriptor buckets, batched depth — and each launch costs ~5 us on a path that is launch-bound
-// anyway.  Four items per thread: a quarter of the workgroups, tickets and barriers for the 524k-bucket tables of the voxel
-// hash, whose scan took 50 us with one item per thread.)
-constexpr int SCAN_IPT = 4;
-constexpr int SCAN_BLOCK_ITEMS = 1024 * SCAN_IPT;
-__device__ __forceinline__ void scan_load4(const int* __restrict__ in, int n, int i0, int (&x)[SCAN_IPT]) {
-    if (i0 + SCAN_IPT <= n && (((size_t)in & 15) == 0)) {
-        const int4 q = *reinterpret_cast<const int4*>(in + i0);
-        x[0] = q.x; x[1] = q.y; x[2] = q.z; x[3] = q.w;
-    } else {
-#pragma unroll
-        for (int e = 0; e < SCAN_IPT; ++e) x[e] = i0 + e < n ? in[i0 + e] : 0;
-    }
-}
-__global__ __launch_bounds__(1024)
-void k_scan_reduce(const int* __restrict__ in, int n, int* __restrict__ sums, int* __restrict__ total, unsigned* __restrict__ ticket) {
-    __shared__ int w[16];
-    __shared__ int carry_s;
-    __shared__ bool is_last;
-    const int i0 = (blockIdx.x * 1024 + threadIdx.x) * SCAN_IPT;
-    int x[SCAN_IPT];
-    scan_load4(in, n, i0, x);
-    int v = (x[0] + x[1]) + (x[2] + x[3]);
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    if ((threadIdx.x & 63) == 0) w[threadIdx.x >> 6] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int s = 0;
-        for (int k = 0; k < 16; ++k) s += w[k];
-        sums[blockIdx.x] = s;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");       // the sum is visible device-wide before the ticket moves (release only: __threadfence() would also invalidate the XCD's L2 under the workgroups still loading)
-        is_last = atomicAdd(ticket, 1u) == gridDim.x - 1;
-        carry_s = 0;
-    }
-    __syncthreads();
-    if (!is_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");           // acquire: the other workgroups' sums
-    const int nblocks = gridDim.x;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    volatile int* vs = sums;                                    // written by other workgroups of this launch
-    for (int b0 = 0; b0 < nblocks; b0 += 1024) {
-        int k = b0 + threadIdx.x;
-        int xs = k < nblocks ? vs[k] : 0;
-        int incl = xs;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
-        if (lane == 63) w[wave] = incl;
-        __syncthreads();
-        int wbase = 0;
-        for (int q = 0; q < wave; ++q) wbase += w[q];
-        int carry = carry_s;
-        if (k < nblocks) vs[k] = carry + wbase + incl - xs;
-        __syncthreads();
-        if (threadIdx.x == 1023) carry_s = carry + wbase + incl;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) { *total = carry_s; *ticket = 0u; }   // ready for the next launch (stream order)
-}
-__global__ __launch_bounds__(1024)
-void k_scan_local(const int* __restrict__ in, int n, const int* __restrict__ sums, int* __restrict__ out) {
-    __shared__ int wsum[16];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int i0 = (blockIdx.x * 1024 + threadIdx.x) * SCAN_IPT;
-    int x[SCAN_IPT];
-    scan_load4(in, n, i0, x);
-    const int v = (x[0] + x[1]) + (x[2] + x[3]);
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { int t = __shfl_up(incl, off, 64); if (lane >= off) incl += t; }
-    if (lane == 63) wsum[wave] = incl;
-    __syncthreads();
-    int wbase = 0;
-    for (int q = 0; q < wave; ++q) wbase += wsum[q];
-    int run = sums[blockIdx.x] + wbase + incl - v;          // exclusive prefix of this thread's first item
-#pragma unroll
-    for (int e = 0; e < SCAN_IPT; ++e) { if (i0 + e < n) out[i0 + e] = run; run += x[e]; }
 }
 
 // one lane per run head: sequential sum over the run (ascending input index), mean -> out[rank]
@@ -995,21 +784,6 @@ private:
 #endif
 }  // namespace
 
-// exclusive scan of n ints on the ctx stream; *d_total receives the sum (device pointer)
-int exclusive_scan_dev(tdv_ctx* ctx, const int* d_in, int n, int* d_out, int* d_total) {
-    if (n <= 0) return TDV_OK;
-    const int sblocks = (n + SCAN_BLOCK_ITEMS - 1) / SCAN_BLOCK_ITEMS;
-    int* sums;
-    TDV_TRY(ws_alloc(ctx, (size_t)sblocks, &sums));
-    hipStream_t s = ctx->stream;
-    k_scan_reduce<<<sblocks, 1024, 0, s>>>(d_in, n, sums, d_total, ctx->scan_ticket);
-    k_scan_local<<<sblocks, 1024, 0, s>>>(d_in, n, sums, d_out);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-
-size_t sort_pow2(size_t n) { size_t p = BT_TILE; while (p < n) p <<= 1; return p; }
-
 static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
                                  float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both);
 
@@ -1279,13 +1053,10 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
     if (n == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
     const float inv = 1.0f / voxel;  // registration.cpp:32
-    size_t n_pow2 = BT_TILE;
-    while (n_pow2 < (size_t)n) n_pow2 <<= 1;
-    uint4* rec; int *leader, *rank, *sums, *d_total;
+    const size_t n_pow2 = sort_pow2((size_t)n);
+    uint4* rec; int *leader, *rank, *d_total;
     TDV_TRY(ws_alloc(ctx, n_pow2, &rec));
     TDV_TRY(ws_alloc(ctx, (size_t)n, &rank));
-    const int sblocks = (n + SCAN_BLOCK_ITEMS - 1) / SCAN_BLOCK_ITEMS;
-    TDV_TRY(ws_alloc(ctx, (size_t)sblocks, &sums));
     TDV_TRY(ws_alloc(ctx, 1, &d_total));
     TDV_TRY(pin_reserve(ctx, 64));
     ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
@@ -1317,9 +1088,7 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
         TDV_HIP(ctx, hipMemsetAsync(leader, 0, (size_t)n * 4, s));
         k_voxel_heads<<<(n + 255) / 256, 256, 0, s>>>(rec, n, leader);
     }
-    k_scan_reduce<<<sblocks, 1024, 0, s>>>(leader, n, sums, d_total, ctx->scan_ticket);
-    k_scan_local<<<sblocks, 1024, 0, s>>>(leader, n, sums, rank);
-    TDV_CHECK_LAUNCH(ctx);
+    TDV_TRY(exclusive_scan_dev(ctx, leader, n, rank, d_total));
     int* h_total = reinterpret_cast<int*>(ctx->pin);
     h_total[1] = 0;
     TDV_HIP(ctx, hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));

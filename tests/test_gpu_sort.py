@@ -1,4 +1,4 @@
-"""csrc/sort.hip: the hand-written stable LSD radix sort of (u64 key, u32 value) pairs behind the descriptor index build (csrc/fmatch.hip)
+"""csrc/sort.hip: the hand-written stable LSD radix sort of (u64 key, u32 value) pairs behind the descriptor index build (csrc/fmatch_index.hip)
 against numpy's stable argsort - every size class (one workgroup, a ragged last workgroup, hundreds of workgroups), every pass count
 (1 to 64 bits), keys with many duplicates (stability is what the index build relies on: rows enter in index order and ties keep it)."""
 import numpy as np

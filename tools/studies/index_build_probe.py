@@ -1,4 +1,4 @@
-"""Study: the descriptor index build (csrc/fmatch.hip, two radix sorts of csrc/sort.hip inside) and the query on tools/opbench.py's relief parts."""
+"""Study: the descriptor index build (csrc/fmatch_index.hip, two radix sorts of csrc/sort.hip inside) and the query on tools/opbench.py's relief parts."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tools"))
