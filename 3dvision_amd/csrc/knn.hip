@@ -716,7 +716,7 @@ int normals_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float radiu
     TDV_HIP(ctx, hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipStreamSynchronize(s));
     const int nsel = *h_total;
-    if (getenv("TDV_DEBUG")) fprintf(stderr, "[tdv] normals_fpfh: n=%d deficient=%d (k=%d)\n", n, nsel, kk);
+    if (study_env("TDV_DEBUG")) fprintf(stderr, "[tdv] normals_fpfh: n=%d deficient=%d (k=%d)\n", n, nsel, kk);
     TDV_TRY(knn_to_lists(ctx, so, n, p, kk, qsel, nsel, listsK, cntK));
     k_normals_from_lists<<<p.blocks_x, KN_BLOCK, 0, s>>>(d_xyz, n, so.orig, kk, nbr, FP_MAXNN, cnt, listsK, kk, cntK, d_normals, nullptr, 0);
     TDV_CHECK_LAUNCH(ctx);

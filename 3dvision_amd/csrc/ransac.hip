@@ -21,6 +21,8 @@
 //        iteration whose fitness passes the confidence, then the first largest fitness up to it - strict > on
 //        float(inliers)/ns against the running best, which stays on the device with the winner's 12 floats; the host
 //        reads one four-int record per batch.  A traced call downloads every count and runs the loop on the host.
+//  (iv') k_order_flags / k_order_scatter: once per call with bail-out, after the first batch, the scoring pass' pair array again with
+//        the running best's outliers first (RansacPointOrder): counts are order-free, the bail-out drops far more.
 //  (vi)  k_ransac_rmse_partial / k_ransac_rmse_final: error sum of the winning hypothesis only, fixed-order reduction (per-workgroup
 //        slabs, then one workgroup over the slabs).
 #include "tdv_internal.hpp"
@@ -409,9 +411,13 @@ __device__ __forceinline__ int draw_ticket(int* word) {
 }
 
 // statistics only (tdv_ctx_last_ransac_rescore / _scored): two atomics per workgroup - point pairs scored twice (n_rescored, wave-uniform),
-// and (wave, chunk) pairs scored (chunks, workgroup-uniform); every thread of the workgroup calls it
+// and (wave, chunk) pairs scored: `waves` x `chunks`, both workgroup-uniform; every thread of the workgroup calls it.
+// The scored share counts the 16 waves of a block for every chunk the block walks - job A and the small-cloud pass, where every wave
+// scores (padding lanes included), and phase 1 over a live list, so that a bounded batch whose hypotheses are all live reports job A's
+// share.  Phase 2 alone counts, per block, the waves that hold a listed hypothesis (the caller passes waves = 1 and their sum in
+// `chunks`): its list may fill a fraction of one block, whose other waves skip the arithmetic.  DESIGN.md 4 states the definition.
 template <class C>
-__device__ __forceinline__ void score_stats(unsigned n_rescored, C chunks, unsigned long long* __restrict__ rescored) {
+__device__ __forceinline__ void score_stats(unsigned n_rescored, C chunks, unsigned long long* __restrict__ rescored, unsigned waves = RS_BLOCK / 64) {
     __shared__ unsigned s_rescored;
     if (threadIdx.x == 0) s_rescored = 0u;
     __syncthreads();
@@ -419,7 +425,7 @@ __device__ __forceinline__ void score_stats(unsigned n_rescored, C chunks, unsig
     __syncthreads();
     if (threadIdx.x == 0) {
         if (s_rescored) atomicAdd(rescored, (unsigned long long)s_rescored);
-        atomicAdd(rescored + 1, (unsigned long long)(RS_BLOCK / 64) * (unsigned long long)chunks);
+        atomicAdd(rescored + 1, (unsigned long long)waves * (unsigned long long)chunks);
     }
 }
 
@@ -466,6 +472,7 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         const int r0 = b.n_live ? 0 : b.plan[0], r1 = b.n_live ? b.plan[0] : n_pchunks;
         __shared__ int s_ticket[2];
         int flip = 0;
+        unsigned long long wave_chunks = 0ull;       // statistics: (wave, chunk) pairs this workgroup counts (score_stats)
         for (int visit = 0; visit < n_blk; ++visit) {
             const int hblock = score_unit_block(wg, visit, n_blk);
             int* const word = b.units + (size_t)xcd * b.hb + hblock;
@@ -478,15 +485,18 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
             // the waves that do, and only joins the barriers
             const bool wave_scores = __builtin_amdgcn_readfirstlane(slot - (int)(threadIdx.x & 63)) < n_list;
             const HypLane l = load_hyp(b.hyp, h_pad, base, tau);
+            const int stat_waves = b.n_live ? RS_BLOCK / 64 : min(RS_BLOCK / 64, (n_list - hblock * RS_BLOCK + 63) / 64);   // (see score_stats)
             int cnt = 0;
             do {
                 if (threadIdx.x == 0) next = draw_ticket(word);       // in flight while this unit is scored
                 if (wave_scores) cnt += score_chunks(l, pq2, c0, c1, tau, n_rescored);
-                chunks += (unsigned)(c1 - c0);
+                wave_chunks += (unsigned long long)stat_waves * (unsigned)(c1 - c0);
             } while (score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1));
             if (base >= 0) atomicAdd(&b.counts[base], cnt);
         }
-        if (!chunks) return;
+        if (!wave_chunks) return;
+        score_stats(n_rescored, wave_chunks, rescored, 1u);
+        return;
     }
     score_stats(n_rescored, chunks, rescored);
 }
@@ -604,6 +614,74 @@ void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ 
     }
     __syncthreads();
     if (threadIdx.x == 0) { plan[1] = s_n; plan[2] = in_batch; }
+}
+
+// RansacPointOrder - the order of the scored points.  An inlier count does not depend on the order its points are scored in, and pq2
+// alone fixes that order (the triples index pq, the rmse pass sums over pq, the leaf summary has its Morton order).  The bail-out
+// drops a hypothesis whose count over the prefix plus ALL the remaining points cannot exceed the best; in the natural order a
+// good-but-not-best pose (an eighth of the triples where half of the correspondences are true) collects a third of the prefix and
+// is scored to the end.  So once per call, after the first batch has set a best, pq2 is written again from pq: the points the
+// running best (d->best12) calls outliers first, its inliers behind them, both in their original relative order; the padding
+// [ns, ns_pad) stays where k_pack_pq2 put it.  Those outliers are mostly the false correspondences, outliers of every good pose: a
+// good pose collects next to nothing over the first N - best points and has to match the best inlier for inlier from there on.
+// The plan, the lists, the rules of k_ransac_select and the scoring kernels see positions only and keep their shape.
+// A stable partition without atomics on positions, so that two calls give the same pq2 and the same scored share:
+//   k_order_flags    per block of RO_BLOCK points the ballot words of "outlier of the best" and their count.  The reference's test
+//                    (ref_pair_d2, as the exact kernel), negated: a NaN is an outlier.  No best yet (state[0] == 0): all are.
+//   k_order_scatter  a block adds up the counts in front of it and all of them (integers: any order), then every point goes to its
+//                    slot of pq2's pair-interleaved layout.
+// (Two launches, not the flags / scan / scatter of icp.hip: every block of the scatter re-reads all block counts, blocks^2 / 256 loads per
+// thread in total - 782 blocks at 200k points, 11 us for both launches; 7,800 blocks and 6e7 cached loads at 2M points, where a
+// call's batches take milliseconds each.  A scan launch of its own pays from some 10M points on, which no caller has.)
+// Stream order puts the first batch's dispatches, which read pq2, in front of the two launches, and the second batch's behind.
+constexpr int RO_BLOCK = 256;
+__global__ __launch_bounds__(RO_BLOCK)
+void k_order_flags(const float* __restrict__ pq, int ns, const int* __restrict__ state, const float* __restrict__ best12, float tau,
+                   unsigned long long* __restrict__ mask, int* __restrict__ cnt) {
+    const int i = blockIdx.x * RO_BLOCK + threadIdx.x;
+    __shared__ int s_w[RO_BLOCK / 64];
+    bool out = false;
+    if (i < ns) {
+        out = true;
+        if (state[0] != 0) {
+            const float* g = pq + (size_t)i * 8;
+            v2f r[12];
+#pragma unroll
+            for (int e = 0; e < 12; ++e) r[e] = (v2f){best12[e], best12[e]};
+            const Pair2 a{{g[0], g[0]}, {g[1], g[1]}, {g[2], g[2]}, {g[3], g[3]}, {g[4], g[4]}, {g[5], g[5]}};
+            out = !(ref_pair_d2(r, a).x < tau);
+        }
+    }
+    const unsigned long long m = __ballot(out);
+    if ((threadIdx.x & 63) == 0) { mask[i >> 6] = m; s_w[threadIdx.x >> 6] = __popcll(m); }     // (mask: RO_BLOCK / 64 words per block of the grid)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int c = 0;
+        for (int w = 0; w < RO_BLOCK / 64; ++w) c += s_w[w];
+        cnt[blockIdx.x] = c;
+    }
+}
+__global__ __launch_bounds__(RO_BLOCK)
+void k_order_scatter(const float* __restrict__ pq, int ns, const unsigned long long* __restrict__ mask, const int* __restrict__ cnt,
+                     float* __restrict__ pq2) {
+    const int i = blockIdx.x * RO_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    __shared__ int s_before[RO_BLOCK / 64], s_all[RO_BLOCK / 64], s_w[RO_BLOCK / 64];
+    int before = 0, all = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += RO_BLOCK) { const int c = cnt[b]; all += c; if (b < (int)blockIdx.x) before += c; }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) { before += __shfl_xor(before, off, 64); all += __shfl_xor(all, off, 64); }
+    const unsigned long long m = mask[i >> 6];
+    if (lane == 0) { s_before[wave] = before; s_all[wave] = all; s_w[wave] = __popcll(m); }
+    __syncthreads();
+    if (i >= ns) return;
+    int out_before = 0, out_all = 0, rank = __popcll(m & ((1ull << lane) - 1ull));      // rank: the block's outliers in front of this point
+    for (int w = 0; w < RO_BLOCK / 64; ++w) { out_before += s_before[w]; out_all += s_all[w]; if (w < wave) rank += s_w[w]; }
+    const bool out = (m >> lane) & 1ull;
+    // outliers: [0, out_all) ; inliers behind them: the points in front of this one that are no outliers
+    const int pos = out ? out_before + rank : out_all + (i - out_before - rank);
+    const float4 a = reinterpret_cast<const float4*>(pq)[2 * (size_t)i], b = reinterpret_cast<const float4*>(pq)[2 * (size_t)i + 1];
+    float* o = pq2 + (size_t)(pos >> 1) * 12 + (pos & 1);
+    o[0] = a.x; o[2] = a.y; o[4] = a.z; o[6] = a.w; o[8] = b.x; o[10] = b.y;
 }
 
 // RansacFinish - the end of a batch: the loop of registration.cpp:281-290 over the batch's counts in iteration order, on the device,
@@ -1063,7 +1141,7 @@ static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * 
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, merge, record_copy; int drop_permille; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, merge, record_copy, order; int drop_permille; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1077,9 +1155,13 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     // RansacLeafBound: the leaf summary once per call, the bound in front of phase 1 of every batch after the first (whose best is 0)
     const bool bound_env_off = getenv("TDV_RANSAC_BOUND") && atoi(getenv("TDV_RANSAC_BOUND")) == 0;   // A/B knob
     k.bound = k.bailout && !k.merge && !bound_env_off;
+    // RansacPointOrder: the best's outliers first, once per call after the first batch (the merged dispatch has no best12 by then)
+    const bool order_env_off = getenv("TDV_RANSAC_ORDER") && atoi(getenv("TDV_RANSAC_ORDER")) == 0;   // A/B knob
+    k.order = k.bailout && !k.merge && !order_env_off;
     k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
     k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
-    k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 100;   // tuning knob (5 to 100 measured equal)
+    k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 50;   // tuning knob: phase 1 over the first N - 0.95 best points (natural order: 5 to 100 measured equal;
+                                                                                                                     // best's outliers first, round 12: 25, 50 and 75 above 100, profiles/r12/ransac_point_order.md)
     return k;
 }
 
@@ -1115,6 +1197,7 @@ struct RansacRun {
     size_t tri_bytes;                                 // per triple: one packed word or an int4
     float *pq = nullptr, *pq2 = nullptr, *pq3 = nullptr, *leaves = nullptr, *cleaves = nullptr; double* slabs = nullptr;
     RansacBlock *d = nullptr, *h = nullptr; RansacLive* lv = nullptr;
+    unsigned long long* ord_mask = nullptr; int* ord_cnt = nullptr; bool ordered = false;     // RansacPointOrder: ballot words, block counts; done for this call
     RansacBuf buf[2] = {};
     RansacBatch pending = {}; bool has_pending = false;       // merged dispatch (study build): the batch whose phase 2 is not enqueued yet
     double wave_chunks = 0.0;                         // wave x chunk pairs the call would score without bail-out
@@ -1148,6 +1231,7 @@ struct RansacRun {
             for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list)); TDV_TRY(ws_alloc(ctx, (size_t)unit_words(), &B.units)); }
             TDV_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         }
+        if (k.order) { TDV_TRY(ws_alloc(ctx, (size_t)order_blocks() * (RO_BLOCK / 64), &ord_mask)); TDV_TRY(ws_alloc(ctx, (size_t)order_blocks(), &ord_cnt)); }
         if (k.bound) {
             for (RansacBuf& B : buf) {
                 TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.live)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.und));
@@ -1171,6 +1255,7 @@ struct RansacRun {
         return TDV_OK;
     }
     int unit_words() const { return 2 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's
+    int order_blocks() const { return (ns + RO_BLOCK - 1) / RO_BLOCK; }
     void release_events() { for (RansacBuf& B : buf) event_release(ctx, B.ev); }
     // RansacLeafBound's summary of the pairs: fine and coarse leaves along the Morton order
     int leaf_summary() {
@@ -1237,6 +1322,12 @@ struct RansacRun {
             k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
                                                                                   d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket);
         }
+    }
+    // RansacPointOrder: pq2 again from pq, the outliers of the best so far (best12, state[0]: the batches enqueued before) first
+    void point_order() {
+        k_order_flags<<<order_blocks(), RO_BLOCK, 0, s>>>(pq, ns, d->state, d->best12, tau, ord_mask, ord_cnt);
+        k_order_scatter<<<order_blocks(), RO_BLOCK, 0, s>>>(pq, ns, ord_mask, ord_cnt, pq2);
+        ordered = true;
     }
     ScoreJob job_a(const RansacBatch& b) const { return ScoreJob{buf[b.q].hyp, buf[b.q].counts, buf[b.q].plan, nullptr, hyp_blocks(b.cnt), range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, nullptr, nullptr}; }
     // phase 1: the batch's hypotheses (job A) - or, bounded, its live list as a job B (resident workgroups that pull units) - over
@@ -1308,6 +1399,7 @@ struct RansacRun {
         TDV_TRY(hypotheses(b));
         if (!k.bailout) { TDV_TRY(score_all(b)); return finish(b, false); }   // exact, traced, short or matrix-core calls: every test is scored
         if (k.merge) return enqueue_merged(b);
+        if (k.order && it0 != 0 && !ordered) point_order();  // once per call: the first batch has set a best, nothing reads pq2 in between
         if (b.bounded) bound(b);                             // bail-out with bound: phase 1 over the live list only
         phase1(b);
         TDV_TRY(select(b));
