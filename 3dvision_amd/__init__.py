@@ -61,6 +61,7 @@ ABI_SYMBOLS = [
     "tdv_plane_default_params", "tdv_segment_planes", "tdv_segment_planes_dev",
     "tdv_cluster_default_params", "tdv_cluster_dbscan", "tdv_cluster_dbscan_dev",
     "tdv_remove_statistical_outlier", "tdv_remove_statistical_outlier_dev", "tdv_remove_radius_outlier", "tdv_remove_radius_outlier_dev",
+    "tdv_iss_default_params", "tdv_iss_keypoints", "tdv_iss_keypoints_dev",
 ]
 
 
@@ -179,6 +180,32 @@ def _outlier_result(r):
     return {k: getattr(r, k) for k, _ in OutlierResultC._fields_}
 
 
+class IssParamsC(C.Structure):
+    _fields_ = [("salient_radius", C.c_float), ("non_max_radius", C.c_float), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
+                ("min_neighbors", C.c_int)]
+
+
+class IssResultC(C.Structure):
+    _fields_ = [("n_finite", C.c_int), ("n_supported", C.c_int), ("n_salient", C.c_int), ("n_keypoints", C.c_int),
+                ("salient_radius", C.c_float), ("non_max_radius", C.c_float), ("resolution", C.c_double)]
+
+
+def iss_params(**kw):
+    """tdv_iss_default_params (radii 0: from the cloud's resolution; gammas 0.975; min_neighbors 5) with the given fields replaced
+    (Open3D's compute_iss_keypoints names)."""
+    p = IssParamsC()
+    lib().tdv_iss_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(IssParamsC._fields_):
+            raise TypeError("unknown ISS parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _iss_result(r):
+    return {k: getattr(r, k) for k, _ in IssResultC._fields_}
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -219,6 +246,7 @@ def lib():
             l.tdv_fgr_default_params.restype = None
             l.tdv_plane_default_params.restype = None
             l.tdv_cluster_default_params.restype = None
+            l.tdv_iss_default_params.restype = None
             _lib = l
     return _lib
 
@@ -825,6 +853,48 @@ class Context:
                                                             _ptr(d_mask), _ptr(d_count), _ptr(d_index), _ptr(d_out_xyz), _ptr(d_out_rgb)),
                "tdv_remove_radius_outlier_dev")
         return _outlier_result(res)
+
+    # ---------------------------------------------------------------- ISS keypoints (include/tdv_hip.h: tdv_iss_keypoints)
+    def iss(self, xyz, attr=None, **params):
+        """tdv_iss_keypoints, every output: dict(n_finite, n_supported, n_salient, n_keypoints, salient_radius, non_max_radius, resolution,
+        mask uint8[n], saliency float64[n], eigenvalues float64[n, 3], support int32[n], index int32[n_keypoints], xyz
+        float32[n_keypoints, 3], attr float32[n_keypoints, width] or None).  attr: one row of floats per point, gathered beside xyz."""
+        xyz = _f32(xyz).reshape(-1, 3); n = len(xyz)
+        width = 0
+        if attr is not None:
+            attr = _f32(attr)
+            if attr.ndim != 2 or len(attr) != n:
+                raise ValueError("tdv_iss_keypoints: one attr row per point")
+            width = attr.shape[1]
+        p = iss_params(**params)
+        res = IssResultC()
+        m1 = max(n, 1)
+        mask = np.zeros(m1, np.uint8); sal = np.zeros(m1, np.float64); eig = np.zeros((m1, 3), np.float64); sup = np.zeros(m1, np.int32)
+        index = np.zeros(m1, np.int32); rows = np.zeros((m1, 3), np.float32)
+        cols = None if attr is None else np.zeros((m1, max(width, 1)), np.float32)
+        _check(self._h, lib().tdv_iss_keypoints(self._h, _ptr(xyz), n, C.byref(p), _ptr(attr), width, C.byref(res), _ptr(mask), _ptr(sal), _ptr(eig),
+                                                _ptr(sup), _ptr(index), _ptr(rows), _ptr(cols)), "tdv_iss_keypoints")
+        m = res.n_keypoints
+        return dict(_iss_result(res), mask=mask[:n], saliency=sal[:n], eigenvalues=eig[:n], support=sup[:n], index=index[:m], xyz=rows[:m],
+                    attr=None if cols is None else cols.reshape(-1)[:m * width].reshape(m, width))
+
+    def compute_iss_keypoints(self, xyz, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
+        """Open3D's geometry.keypoint.compute_iss_keypoints: (the keypoints' rows, ind - their indices, int64 ascending)."""
+        r = self.iss(xyz, salient_radius=salient_radius, non_max_radius=non_max_radius, gamma_21=gamma_21, gamma_32=gamma_32,
+                     min_neighbors=min_neighbors)
+        return r["xyz"], r["index"].astype(np.int64)
+
+    def iss_keypoints_dev(self, d_xyz, n, d_attr=None, attr_width=0, d_mask=None, d_saliency=None, d_eigenvalues=None, d_support=None,
+                          d_index=None, d_out_xyz=None, d_out_attr=None, **params):
+        """tdv_iss_keypoints_dev on device pointers: the result dict.  d_mask (uint8[n]), d_saliency (float64[n]), d_eigenvalues
+        (float64[3n]), d_support (int32[n]), d_index (int32[n]), d_out_xyz (float[3n]) and d_out_attr (float[attr_width * n]) are optional;
+        n_keypoints rows are written - (d_out_xyz, d_out_attr) are the (src, fs) of ransac_dev and fgr_dev."""
+        p = iss_params(**params)
+        res = IssResultC()
+        _check(self._h, lib().tdv_iss_keypoints_dev(self._h, _ptr(d_xyz), n, C.byref(p), _ptr(d_attr), int(attr_width), C.byref(res), _ptr(d_mask),
+                                                    _ptr(d_saliency), _ptr(d_eigenvalues), _ptr(d_support), _ptr(d_index), _ptr(d_out_xyz),
+                                                    _ptr(d_out_attr)), "tdv_iss_keypoints_dev")
+        return _iss_result(res)
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

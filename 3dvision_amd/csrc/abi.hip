@@ -510,4 +510,27 @@ int tdv_fgr_correspondences(tdv_ctx* ctx, const float* src, int ns, const float*
     return finish(ctx);
 }
 
+// ---- ISS keypoints (iss.hip)
+void tdv_iss_default_params(tdv_iss_params* p) {
+    if (!p) return;
+    p->salient_radius = 0.f; p->non_max_radius = 0.f; p->gamma_21 = 0.975; p->gamma_32 = 0.975; p->min_neighbors = 5;
+}
+
+int tdv_iss_keypoints(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params* params, const float* attr, int attr_width, tdv_iss_result* result,
+                      uint8_t* mask, double* saliency, double* eigenvalues, int* support, int* index, float* out_xyz, float* out_attr) {
+    if (!iss_args_ok(ctx, xyz, n, params, attr, attr_width, result, out_attr)) return TDV_ERR_BAD_ARG;
+    IssOut h; h.mask = mask; h.saliency = saliency; h.eig = eigenvalues; h.support = support; h.index = index; h.xyz = out_xyz; h.attr = out_attr;
+    return iss_run_host(ctx, xyz, n, *params, attr, attr_width, result, h);
+}
+
+int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params* params, const float* d_attr, int attr_width,
+                          tdv_iss_result* result, uint8_t* d_mask, double* d_saliency, double* d_eigenvalues, int* d_support, int* d_index,
+                          float* d_out_xyz, float* d_out_attr) {
+    if (!iss_args_ok(ctx, d_xyz, n, params, d_attr, attr_width, result, d_out_attr)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(iss_begin(ctx));
+    IssOut d; d.mask = d_mask; d.saliency = d_saliency; d.eig = d_eigenvalues; d.support = d_support; d.index = d_index; d.xyz = d_out_xyz;
+    d.attr = d_out_attr;
+    return iss_run_dev(ctx, d_xyz, n, *params, d_attr, attr_width, result, d, nullptr);
+}
+
 }  // extern "C"

@@ -1,0 +1,48 @@
+// The fixed f64 summation tree of include/tdv_hip.h (tdv_remove_statistical_outlier, rule 4), shared by the kernels that sum one f64 term
+// per point of a cloud in ORIGINAL index order: outlier.hip (cloud_mean, std_dev) and iss.hip (the cloud's resolution).  The term of
+// point i belongs to workgroup i / 256, thread i % 256; a workgroup sum is the shuffle tree over each wave, then (w0 + w1) + (w2 + w3);
+// one workgroup then adds the workgroup sums t, t + 256, ... into thread t and sums its 256 threads the same way.  One order, so two calls
+// give the same bits.  Device code for workgroups of 256 threads; include after `#pragma clang fp contract(off)`.
+#pragma once
+#include "tdv_internal.hpp"
+
+namespace tdv {
+
+namespace {   // per translation unit, as the kernels that use it
+
+__device__ __forceinline__ double tree_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
+
+// f64 sum over the 256 threads of a workgroup in plane.hip's fixed order (wave shuffles, then the four waves in order); valid in thread 0
+__device__ __forceinline__ double tree_block_sum(double v, double* lds4) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+__device__ __forceinline__ int tree_block_count(int v, int* lds4) {
+    v = wave_sum_i32(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+// the nb workgroup sums (counts) added by one workgroup: thread t takes t, t + 256, ... in order, then the block sum; valid in thread 0
+__device__ __forceinline__ double tree_partials_sum(const double* __restrict__ part, int nb, double* lds4) {
+    double v = 0.0;
+    for (int b = threadIdx.x; b < nb; b += 256) v += part[b];
+    return tree_block_sum(v, lds4);
+}
+
+__device__ __forceinline__ int tree_partials_count(const int* __restrict__ cnt, int nb, int* lds4) {
+    int c = 0;
+    for (int b = threadIdx.x; b < nb; b += 256) c += cnt[b];
+    return tree_block_count(c, lds4);
+}
+
+}  // namespace
+
+}  // namespace tdv

@@ -6,17 +6,19 @@
 //  (ii)  k_outlier_mean: ONE WAVE PER QUERY in curve order, the walk of k_query_wave (query_wave.hpp).  When the walk ends the query's
 //        sorted row is in the wave's registers: every lane takes the f64 square root of its entries, lane order is list order, and the
 //        k additions run serially over the lanes' values (readlane).  One f64 leaves the kernel per query: no n x k list is written.
-//  (iii) k_outlier_partial (pass 0): per workgroup of 256 points in ORIGINAL index order the f64 sum of the valid means (plane.hip's
+//  (iii) k_outlier_partial (pass 0): per workgroup of 256 points in ORIGINAL index order the f64 sum of the valid means (fixed_tree.hpp's
 //        fixed order: shuffle tree over the wave, then the four waves) and the valid count; k_outlier_tree: one workgroup adds the
 //        partials (thread t takes t, t + 256, ... in order, then the same block sum) and one lane forms cloud_mean.
 //  (iv)  k_outlier_partial (pass 1) and k_outlier_tree again on (mean - cloud_mean)^2: std_dev and threshold in one lane.
-//  (v)   k_outlier_flag, exclusive_scan_dev, k_outlier_gather: mask, then index, xyz and rgb of the kept rows in ascending index.
+//  (v)   k_outlier_flag, exclusive_scan_dev, k_gather_flagged (flag_gather.hpp): mask, then index, xyz and rgb of the kept rows in ascending index.
 // Radius filter: k_outlier_count is k_cluster_count's walk (cluster_walk.hpp) with its early stop at nb_points + 1; then (v).
 // No float atomics: the counts are integers, the f64 sums have the one order above, so two calls give the same bits.
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
 #include "query_wave.hpp"
 #include "cluster_walk.hpp"
+#include "fixed_tree.hpp"
+#include "flag_gather.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -35,8 +37,6 @@ struct OutlierState {
     int n_valid, n_kept;
     double cloud_mean, std_dev, threshold;
 };
-
-__device__ __forceinline__ double outlier_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
 // rule 3: a point's mean takes part in the statistics (count_i = 0 left the NaN above, which fails here)
 __device__ __forceinline__ bool outlier_valid(double m) { return m > 0.0 && m < (double)INFINITY; }
@@ -69,25 +69,7 @@ void k_outlier_mean(const float* __restrict__ sx, const float* __restrict__ sy, 
             s += __longlong_as_double((long long)b);
         }
     }
-    if (lane == 0) mean[orig[sp]] = c > 0 ? s / (double)c : outlier_nan();
-}
-
-// f64 sum over the 256 threads of a workgroup in plane.hip's fixed order (wave shuffles, then the four waves in order); valid in thread 0
-__device__ __forceinline__ double outlier_block_sum(double v, double* lds4) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
-
-__device__ __forceinline__ int outlier_block_count(int v, int* lds4) {
-    v = wave_sum_i32(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+    if (lane == 0) mean[orig[sp]] = c > 0 ? s / (double)c : tree_nan();
 }
 
 // part[b] = the sum over points [256 b, 256 b + 256) of: pass 0, the valid means (cnt[b] = how many); pass 1, their squared deviations
@@ -103,10 +85,10 @@ __global__ __launch_bounds__(256) void k_outlier_partial(const double* __restric
         if (pass == 0) v = m;
         else { const double d = m - st->cloud_mean; v = d * d; }
     }
-    const double s = outlier_block_sum(v, lds4);
+    const double s = tree_block_sum(v, lds4);
     if (threadIdx.x == 0) part[blockIdx.x] = s;
     if (pass == 0) {
-        const int c = outlier_block_count(valid ? 1 : 0, ldc4);
+        const int c = tree_block_count(valid ? 1 : 0, ldc4);
         if (threadIdx.x == 0) cnt[blockIdx.x] = c;
     }
 }
@@ -116,20 +98,16 @@ __global__ __launch_bounds__(256) void k_outlier_tree(OutlierState* st, const do
                                                       int pass, double std_ratio) {
     __shared__ double lds4[4];
     __shared__ int ldc4[4];
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) v += part[b];
-    const double s = outlier_block_sum(v, lds4);
+    const double s = tree_partials_sum(part, nb, lds4);
     if (pass == 0) {
-        int c = 0;
-        for (int b = threadIdx.x; b < nb; b += 256) c += cnt[b];
-        c = outlier_block_count(c, ldc4);
+        const int c = tree_partials_count(cnt, nb, ldc4);
         if (threadIdx.x == 0) {
             st->n_valid = c; st->n_kept = 0;
-            st->cloud_mean = c > 0 ? s / (double)c : outlier_nan();
+            st->cloud_mean = c > 0 ? s / (double)c : tree_nan();
         }
     } else if (threadIdx.x == 0) {
         const int c = st->n_valid;
-        const double sd = c > 1 ? sqrt(s / (double)(c - 1)) : outlier_nan();
+        const double sd = c > 1 ? sqrt(s / (double)(c - 1)) : tree_nan();
         st->std_dev = sd;
         st->threshold = st->cloud_mean + std_ratio * sd;
     }
@@ -181,7 +159,7 @@ __global__ __launch_bounds__(256) void k_outlier_radius_state(const float* __res
         const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
         v = cluster_d2(x, y, z, x, y, z) <= eps2 ? 1 : 0;
     }
-    const int c = outlier_block_count(v, ldc4);
+    const int c = tree_block_count(v, ldc4);
     if (threadIdx.x == 0 && c) atomicAdd(&st->n_valid, c);
 }
 
@@ -189,18 +167,6 @@ __global__ void k_outlier_init(OutlierState* st) {
     if (threadIdx.x != 0) return;
     OutlierState z{};
     *st = z;
-}
-
-// the kept rows in ascending original index: index, xyz, rgb (each optional)
-__global__ __launch_bounds__(256) void k_outlier_gather(const int* __restrict__ flag, const int* __restrict__ pos, const float* __restrict__ xyz,
-                                                        const float* __restrict__ rgb, int n, int* __restrict__ index,
-                                                        float* __restrict__ out_xyz, float* __restrict__ out_rgb) {
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || !flag[i]) return;
-    const size_t o = (size_t)pos[i], j = (size_t)i;
-    if (index) index[o] = i;
-    if (out_xyz) { out_xyz[3 * o] = xyz[3 * j]; out_xyz[3 * o + 1] = xyz[3 * j + 1]; out_xyz[3 * o + 2] = xyz[3 * j + 2]; }
-    if (out_rgb) { out_rgb[3 * o] = rgb[3 * j]; out_rgb[3 * o + 1] = rgb[3 * j + 1]; out_rgb[3 * o + 2] = rgb[3 * j + 2]; }
 }
 
 int outlier_begin(tdv_ctx* ctx) {
@@ -273,7 +239,7 @@ int outlier_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n,
     }
     TDV_CHECK_LAUNCH(ctx);
     TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, &st->n_kept));
-    if (d.index || d.xyz || d.rgb) k_outlier_gather<<<nb, 256, 0, s>>>(flag, pos, d_xyz, d_rgb, n, d.index, d.xyz, d.rgb);
+    if (d.index || d.xyz || d.rgb) k_gather_flagged<<<nb, 256, 0, s>>>(flag, pos, d_xyz, d_rgb, 3, n, d.index, d.xyz, d.rgb);
     TDV_CHECK_LAUNCH(ctx);
     TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, st, sizeof(OutlierState), hipMemcpyDeviceToHost, s));
     if (h && h->mask) TDV_HIP(ctx, hipMemcpyAsync(h->mask, d.mask, (size_t)n, hipMemcpyDeviceToHost, s));

@@ -307,6 +307,20 @@ int exclusive_scan_dev(tdv_ctx* ctx, const int* d_in, int n, int* d_out, int* d_
 struct SortedCloud { float *sx, *sy, *sz; int* orig; float *lbox, *tbox; int n, pad, n_leaf, n_top; };
 int spatial_sort_cloud(tdv_ctx* ctx, const float* d_xyz, int n, SortedCloud& out);
 
+// ISS keypoints (iss.hip, include/tdv_hip.h: tdv_iss_keypoints): the outputs of a call (each optional), the argument check of both entry
+// points, and the call on host arrays resp. on device pointers (h: where a host call's device outputs go; iss_begin resets the workspace)
+struct IssOut {
+    uint8_t* mask = nullptr; double* saliency = nullptr; double* eig = nullptr; int* support = nullptr; int* index = nullptr;
+    float* xyz = nullptr; float* attr = nullptr;
+};
+bool iss_args_ok(const tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params* p, const float* attr, int attr_width,
+                 const tdv_iss_result* result, const float* out_attr);
+int iss_begin(tdv_ctx* ctx);
+int iss_run_host(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params& prm, const float* attr, int attr_width, tdv_iss_result* result,
+                 const IssOut& h);
+int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& prm, const float* d_attr, int attr_width, tdv_iss_result* result,
+                IssOut d, const IssOut* h);
+
 // normals + FPFH in one go, sharing one spatial sort and one radius scan (batch path; identical results)
 // d_tie_ids / d_tie_ids_inv (optional, both or neither): neighbour lists are ordered by (d2, d_tie_ids[index]) instead of
 // (d2, index) — the results are those of the cloud permuted so that point i sits at position d_tie_ids[i]

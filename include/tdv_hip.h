@@ -682,6 +682,81 @@ int tdv_remove_radius_outlier(tdv_ctx* ctx, const float* xyz, const float* rgb /
 int tdv_remove_radius_outlier_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb /* optional */, int n, int nb_points, float radius,
                                   tdv_outlier_result* result, uint8_t* d_mask /* optional */, int* d_count /* optional */,
                                   int* d_index /* optional */, float* d_out_xyz /* optional */, float* d_out_rgb /* optional */);
+/* ISS keypoints (Intrinsic Shape Signatures, Zhong 2009; Open3D's keypoint::ComputeISSKeypoints(salient_radius, non_max_radius, gamma_21,
+ * gamma_32, min_neighbors)): the few percent of a cloud's points whose neighbourhood has three distinct principal extents - fewer source
+ * points for the descriptor match, RANSAC or FGR without a coarser voxel.  The sums are defined over integers, so every output is fixed bit
+ * for bit whatever order the device works in:
+ *  1. Distance and neighbour: rules 1-3 of tdv_cluster_dbscan for each of the two radii: d2 = (dx * dx + dy * dy) + dz * dz in f32 without
+ *     contraction, r2 = r * r in f32, FLT_MAX where that overflows, j is a neighbour of i iff d2 <= r2, a point counts itself, a row with a
+ *     NaN or infinite coordinate has no neighbour and is nobody's.
+ *  2. Support: support_i = the neighbours of i within salient_radius.  support_i < min_neighbors: saliency 0 (Open3D's `continue`), and
+ *     the eigenvalues reported for i are +0.0.
+ *  3. Scatter, in integers: salient_radius = m * 2^E with m in [0.5, 1) (frexpf; E = 0 for a radius of 0), sh = 20 - E.  For every
+ *     neighbour j and axis a: d_a = p_j,a - p_i,a in f32 (one rounding), u_a = (int64)rintf(ldexpf(d_a, sh)), round-half-even; |u_a| <=
+ *     2^20 + 1 follows from rule 1 (wherever r * r is a normal f32; u_a is saturated to [-2^31, 2^31 - 128] beyond, and the sums wrap).
+ *     S_a = sum of u_a, S_ab = sum of u_a * u_b over the support: three first and six second moments, all int64.  Integer sums are
+ *     associative: neither the walk order nor the reduction tree matters.  The quantum is 2^-21 of the radius's binade - coordinates
+ *     differences are rounded to it, the price of exactness (it moves the eigenvalues by parts in 10^6: tests/test_iss_abi.py derives the
+ *     bound).  n > TDV_ISS_MAX_POINTS (2^22) is refused, which keeps S_ab below 2^63.
+ *  4. Covariance, f64 without contraction, c = (double)support_i, a <= b: C_ab = ((double)S_ab - ((double)S_a * (double)S_b) / c) / c:
+ *     Open3D's covariance about the neighbourhood's own mean, in units of the quantum squared.
+ *  5. Eigenvalues: f64 cyclic Jacobi on the symmetric 3 x 3, TDV_ISS_JACOBI_SWEEPS (6) sweeps, each over the pairs (p, q) = (0, 1), (0, 2),
+ *     (1, 2) in that order.  A pair whose a_pq is exactly 0 is skipped; otherwise theta = (a_qq - a_pp) / (2 a_pq), t = sign / (|theta| +
+ *     sqrt(theta * theta + 1)) with sign = -1 if theta < 0, else 1, c = 1 / sqrt(t * t + 1), s = t * c, h = t * a_pq, a_pp -= h, a_qq += h,
+ *     and with r the third index a_rp' = c * a_rp - s * a_rq, a_rq' = s * a_rp + c * a_rq (from the old a_rp, a_rq), a_pq = 0.  Only +, -, *,
+ *     / and the correctly rounded sqrt.  (On the 3 x 3 matrices of noisy clouds the off-diagonal is below 1e-44 of the largest eigenvalue
+ *     after 4 sweeps and exactly 0 after 6.)  lambda1 >= lambda2 >= lambda3: the diagonal through the exchanges (0, 1), (1, 2), (0, 1),
+ *     each swapping iff first < second.  Reported: ldexp(lambda, -2 sh), exact, in m^2.
+ *  6. salient_i iff support_i >= min_neighbors and lambda2 / lambda1 < gamma_21 and lambda3 / lambda2 < gamma_32 and lambda3 > 0 (IEEE
+ *     comparisons: the NaN of 0 / 0 fails).  saliency_i = lambda3 (reported scale) if salient, else +0.0.  A perfectly flat or collinear
+ *     neighbourhood has lambda3 == 0 exactly and is never a keypoint.
+ *  7. Non-maximum suppression: i is a keypoint iff saliency_i > 0, i has at least min_neighbors neighbours within non_max_radius (itself
+ *     included), and no neighbour j within that radius has saliency_j > saliency_i.  Ties keep both points, as Open3D's IsLocalMaxima.
+ *  8. Default radii (salient_radius == 0 and non_max_radius == 0): from the cloud's resolution, Open3D's ComputeModelResolution.  nn_i =
+ *     sqrt((double)d2) of entry 1 of the library's kNN list of i at k = 2 (rule 1 of the statistical filter above); valid_i iff the list
+ *     has two entries and nn_i is finite; resolution = (sum of the valid nn_i) / (their number) in the fixed f64 tree of the statistical
+ *     filter's rule 4 (NaN without a valid one); salient_radius = (float)(6.0 * resolution), non_max_radius = (float)(4.0 * resolution).
+ *     A NaN radius has no neighbours: every count is then 0.
+ * result: n_finite (support_i >= 1: the rows that count themselves), n_supported (support_i >= min_neighbors), n_salient (saliency_i > 0),
+ * n_keypoints, the two radii used, resolution (NaN when the radii were given).
+ * attr (optional): one companion array of attr_width floats per point - FPFH rows (33), normals or colours (3), colored ICP's colour
+ * table (4).  Optional outputs, NULL to skip: mask (uint8[n], 1 = keypoint), saliency (double[n]), eigenvalues (double[3n]: lambda1,
+ * lambda2, lambda3 per point), support (int[n]), index (int[n]: the keypoints' original indices in ascending order, n_keypoints of them),
+ * out_xyz (float[3n]) and out_attr (float[attr_width * n]; needs attr): their rows in that order - (out_xyz, out_attr) of a cloud and its
+ * FPFH rows are the (src, fs) of tdv_ransac_dev or tdv_fgr_dev as they stand.  Entries beyond n_keypoints are not written.  The FPFH rows
+ * are those of the full cloud: the descriptor stage costs what it did.  tdv_iss_keypoints takes host arrays and reads back twice (the
+ * result with the per-point arrays, then the n_keypoints rows); tdv_iss_keypoints_dev takes device pointers and reads back once, the result.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params or result; a NULL cloud with n > 0; n < 0; n >
+ * TDV_ISS_MAX_POINTS; a radius that is negative, NaN or infinite; exactly one radius 0; a gamma that is NaN or <= 0; min_neighbors < 1;
+ * attr_width < 0; attr_width > 0 with a NULL attr; out_attr without attr.  n == 0 is accepted (zero counts).  The ctx's ICP switches do
+ * not apply.  Not provided: keypoints inside tdv_register_batch_dev / tdv_refine_batch_dev (an ABI change), a per-instance (offsets) form,
+ * the C++ operator mirror, other detectors, a descriptor computed at the keypoints only. */
+#define TDV_ISS_JACOBI_SWEEPS 6
+#define TDV_ISS_MAX_POINTS (1 << 22)
+typedef struct tdv_iss_params {
+    float  salient_radius;  /* 0 (with non_max_radius 0): 6 x the cloud's resolution */
+    float  non_max_radius;  /* 0: 4 x the cloud's resolution */
+    double gamma_21;        /* 0.975 */
+    double gamma_32;        /* 0.975 */
+    int    min_neighbors;   /* 5 */
+} tdv_iss_params;
+typedef struct tdv_iss_result {
+    int    n_finite;
+    int    n_supported;
+    int    n_salient;
+    int    n_keypoints;
+    float  salient_radius;
+    float  non_max_radius;
+    double resolution;
+} tdv_iss_result;
+void tdv_iss_default_params(tdv_iss_params* p);
+int tdv_iss_keypoints(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params* params, const float* attr /* optional */, int attr_width,
+                      tdv_iss_result* result, uint8_t* mask /* optional */, double* saliency /* optional */, double* eigenvalues /* optional */,
+                      int* support /* optional */, int* index /* optional */, float* out_xyz /* optional */, float* out_attr /* optional */);
+int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params* params, const float* d_attr /* optional */,
+                          int attr_width, tdv_iss_result* result, uint8_t* d_mask /* optional */, double* d_saliency /* optional */,
+                          double* d_eigenvalues /* optional */, int* d_support /* optional */, int* d_index /* optional */,
+                          float* d_out_xyz /* optional */, float* d_out_attr /* optional */);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
