@@ -22,7 +22,9 @@
 //        float(inliers)/ns against the running best, which stays on the device with the winner's 12 floats; the host
 //        reads one four-int record per batch.  A traced call downloads every count and runs the loop on the host.
 //  (iv') k_order_flags / k_order_scatter: once per call with bail-out, after the first batch, the scoring pass' pair array again with
-//        the running best's outliers first (RansacPointOrder): counts are order-free, the bail-out drops far more.
+//        the running best's outliers first (RansacPointOrder): counts are order-free, the bail-out drops far more.  The outliers
+//        come in two classes, the far ones first: a live hypothesis close to that best skips them in phase 1 under a bound on how
+//        many of them it can hold (RansacFarBound: rf_near, with the bound kernels).
 //  (vi)  k_ransac_rmse_partial / k_ransac_rmse_final: error sum of the winning hypothesis only, fixed-order reduction (per-workgroup
 //        slabs, then one workgroup over the slabs).
 #include "tdv_internal.hpp"
@@ -175,7 +177,9 @@ __device__ __forceinline__ void ransac_hypothesis_lane(const float* __restrict__
 // RansacPlan's set-up of a batch (see k_ransac_score_fast and k_ransac_select below), done by one thread of k_ransac_hypotheses:
 // stream order puts the previous batch's final state[0] in front of that kernel, and the bound and scoring kernels that read the
 // plan and append to the zeroed counters come after it.  plan == nullptr: a batch without bail-out.
-struct PlanJob { int* state; int* plan; int ns, n_pchunks, drop_permille; int* n_live; int* units; int n_units; };   // units: the batch's ticket words (k_ransac_score_fast, job B)
+struct RansacFar;
+struct PlanJob { int* state; int* plan; int ns, n_pchunks, drop_permille; int* n_live; int* units; int n_units;   // units: the batch's ticket words (k_ransac_score_fast, job B)
+                 const RansacFar* far; int a_permille; };                                                  // RansacFarBound: the classes, and the near lists' share of I in phase 1
 __device__ __forceinline__ void ransac_plan(const PlanJob& j);
 __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, int count, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
@@ -306,6 +310,7 @@ struct ScoreJob {
     int ps;      // A: point ranges
     const int* n_live;   // B: phase 1 over the live list (nullptr: phase 2)
     int* units;          // B: this dispatch's ticket words, [8 XCDs][hb]
+    const int* c_far;    // B: a NEAR list (RansacFarBound): the chunks wholly inside F, which its phase 1 skips (nullptr: a far list)
 };
 // One block of hypotheses (lane = hypothesis `base`, -1: none) over the chunks [c0, c1) of the point pairs; returns the lane's
 // inlier count, adds the point PAIRS the wave scored twice to n_rescored (wave-uniform; RS_PCH / 2 per chunk that was re-scored whole).
@@ -324,8 +329,10 @@ __device__ __forceinline__ HypLane load_hyp(const float* __restrict__ hyp, const
     l.mid = base >= 0 ? hyp[(size_t)12 * h_pad + base] : tau; l.half = base >= 0 ? hyp[(size_t)13 * h_pad + base] : 0.f;   // a lane without a hypothesis has no band
     return l;
 }
-template <bool ADAPT = false>
-__device__ __forceinline__ int score_chunks(const HypLane& l, const float* __restrict__ pq2, const int c0, const int c1, const float tau, unsigned& n_rescored) {
+// WRAP: [c0, c1) is a VIRTUAL chunk range that may run past the array's `wrap` chunks and goes on at chunk 0 (phase 2 of a near list:
+// the tail, then the F chunks its phase 1 skipped).
+template <bool ADAPT = false, bool WRAP = false>
+__device__ __forceinline__ int score_chunks(const HypLane& l, const float* __restrict__ pq2, const int c0, const int c1, const float tau, unsigned& n_rescored, const int wrap = 0) {
     const v2f* const r = l.r;
     const float mid = l.mid, half = l.half;
     const v2f nmid = {-mid, -mid};
@@ -333,7 +340,8 @@ __device__ __forceinline__ int score_chunks(const HypLane& l, const float* __res
     int c_fast_end = c1;         // ADAPT: where the FMA pass gives up (wave-uniform)
     for (int c = c0; c < c_fast_end; ++c) {
         if (ADAPT && c == c0 + 8 && n_rescored >= 3u * (RS_PCH / 2)) { c_fast_end = c; break; }      // (n_rescored counts pairs: three whole chunks)
-        const float* __restrict__ g = pq2 + (size_t)c * (6 * RS_PCH);  // RS_PCH points = RS_PCH/2 records of 12 floats, wave-uniform
+        const int pc = (WRAP && c >= wrap) ? c - wrap : c;
+        const float* __restrict__ g = pq2 + (size_t)pc * (6 * RS_PCH);  // RS_PCH points = RS_PCH/2 records of 12 floats, wave-uniform
         float v[6 * RS_PCH];
 #pragma unroll
         for (int e = 0; e < 6 * RS_PCH; ++e) v[e] = g[e];
@@ -464,35 +472,43 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         // Few hypothesis blocks are left, and the points reach the scalar cache through the XCD's L2: an XCD (workgroup id mod 8)
         // walks its own eighth of the chunks for ALL surviving blocks, its workgroups spread over the blocks and advancing through
         // the share at the same pace (a workgroup that walked a point range alone missed on every chunk: 1.2 ms for 5 % of the work).
-        const int n_list = b.n_live ? *b.n_live : b.plan[1];
-        const int n_blk = (n_list + RS_BLOCK - 1) / RS_BLOCK;
-        if (n_blk == 0) return;
+        // One dispatch drains up to two lists, b's and then (g1 == 0 and other ticket words) a's: a bounded batch's far and near list.
+        // A far list's phase 1 is the chunks [0, plan[0]), its phase 2 [plan[0], n_pchunks); a near list's phase 1 is [c_far, plan[3]),
+        // its phase 2 the rest as one virtual range [plan[3], n_pchunks + c_far) that wraps to chunk 0.
         const int j0 = id - g1, xcd = j0 & 7, wg = j0 >> 3;
-        // phase 2: the chunks [plan[0], n_pchunks); phase 1 of the live list: [0, plan[0])
-        const int r0 = b.n_live ? 0 : b.plan[0], r1 = b.n_live ? b.plan[0] : n_pchunks;
         __shared__ int s_ticket[2];
         int flip = 0;
         unsigned long long wave_chunks = 0ull;       // statistics: (wave, chunk) pairs this workgroup counts (score_stats)
-        for (int visit = 0; visit < n_blk; ++visit) {
-            const int hblock = score_unit_block(wg, visit, n_blk);
-            int* const word = b.units + (size_t)xcd * b.hb + hblock;
-            int next = 0, c0 = 0, c1 = 0;
-            if (threadIdx.x == 0) next = draw_ticket(word);
-            if (!score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1)) continue;   // drained (workgroup-uniform)
-            const int slot = hblock * RS_BLOCK + threadIdx.x;
-            const int base = slot < n_list ? b.list[slot] : -1;
-            // a wave whose 64 slots are all past the end of the list has nothing to count: it keeps out of the issue slots of
-            // the waves that do, and only joins the barriers
-            const bool wave_scores = __builtin_amdgcn_readfirstlane(slot - (int)(threadIdx.x & 63)) < n_list;
-            const HypLane l = load_hyp(b.hyp, h_pad, base, tau);
-            const int stat_waves = b.n_live ? RS_BLOCK / 64 : min(RS_BLOCK / 64, (n_list - hblock * RS_BLOCK + 63) / 64);   // (see score_stats)
-            int cnt = 0;
-            do {
-                if (threadIdx.x == 0) next = draw_ticket(word);       // in flight while this unit is scored
-                if (wave_scores) cnt += score_chunks(l, pq2, c0, c1, tau, n_rescored);
-                wave_chunks += (unsigned long long)stat_waves * (unsigned)(c1 - c0);
-            } while (score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1));
-            if (base >= 0) atomicAdd(&b.counts[base], cnt);
+        for (int pass = 0; pass < 2; ++pass) {
+            if (pass && (g1 != 0 || a.units == b.units)) break;
+            const ScoreJob& j = pass ? a : b;
+            const bool phase1 = j.n_live != nullptr;
+            const int n_list = phase1 ? *j.n_live : j.plan[j.c_far ? 4 : 1];
+            const int n_blk = (n_list + RS_BLOCK - 1) / RS_BLOCK;
+            if (n_blk == 0) continue;
+            const int skip = j.c_far ? *j.c_far : 0, cut = j.plan[j.c_far ? 3 : 0];
+            const int r0 = phase1 ? skip : cut, r1 = phase1 ? cut : n_pchunks + skip;
+            for (int visit = 0; visit < n_blk; ++visit) {
+                const int hblock = score_unit_block(wg, visit, n_blk);
+                int* const word = j.units + (size_t)xcd * j.hb + hblock;
+                int next = 0, c0 = 0, c1 = 0;
+                if (threadIdx.x == 0) next = draw_ticket(word);
+                if (!score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1)) continue;   // drained (workgroup-uniform)
+                const int slot = hblock * RS_BLOCK + threadIdx.x;
+                const int base = slot < n_list ? j.list[slot] : -1;
+                // a wave whose 64 slots are all past the end of the list has nothing to count: it keeps out of the issue slots of
+                // the waves that do, and only joins the barriers
+                const bool wave_scores = __builtin_amdgcn_readfirstlane(slot - (int)(threadIdx.x & 63)) < n_list;
+                const HypLane l = load_hyp(j.hyp, h_pad, base, tau);
+                const int stat_waves = phase1 ? RS_BLOCK / 64 : min(RS_BLOCK / 64, (n_list - hblock * RS_BLOCK + 63) / 64);   // (see score_stats)
+                int cnt = 0;
+                do {
+                    if (threadIdx.x == 0) next = draw_ticket(word);       // in flight while this unit is scored
+                    if (wave_scores) cnt += score_chunks<false, true>(l, pq2, c0, c1, tau, n_rescored, n_pchunks);
+                    wave_chunks += (unsigned long long)stat_waves * (unsigned)(c1 - c0);
+                } while (score_unit(workgroup_value(next, s_ticket, flip), r0, r1, xcd, c0, c1));
+                if (base >= 0) atomicAdd(&j.counts[base], cnt);
+            }
         }
         if (!wave_chunks) return;
         score_stats(n_rescored, wave_chunks, rescored, 1u);
@@ -501,6 +517,28 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
     score_stats(n_rescored, chunks, rescored);
 }
 
+// RansacFarBound's per-call state (the rules are with the bound kernels below).  The pairs are ordered [F | M | I] by the ORDERING
+// pose B - the running best when k_order_flags ran, kept here because the running best may change later in the call:
+//   F  finite pairs with d2_B >= rF2, d2_B the reference arithmetic's squared distance under B (ref_pair_d2);
+//   M  the other outliers of B - every pair with a non-finite coordinate or a NaN d2_B among them;
+//   I  B's inliers.
+// cum is a count table over d2_B of the F pairs: bin = the leading bits of the non-negative float (monotone in its value), so
+// cum[bin(t)] counts every F pair whose bin is at most t's, which holds all of them with d2_B < t: the lookup errs upward only.
+constexpr int RF_SHIFT = 20, RF_BINS = 2048;                      // sign (0), exponent and three mantissa bits
+struct RansacFar {
+    float ord12[12];            // B
+    int n_far, n_mid;           // |F|, |M|
+    int c_far;                  // chunks wholly inside F: what a near hypothesis' phase 1 skips
+    int pad;
+    unsigned hist[RF_BINS];     // F pairs per bin (zeroed with the call's block, added up by k_order_flags)
+    unsigned cum[RF_BINS];      // ... and in the bins up to and including this one (k_order_scatter)
+};
+__device__ __forceinline__ int rf_bin(float t) { return (int)(__float_as_uint(t) >> RF_SHIFT); }      // t >= 0, no NaN
+// Where phase 1 of the near lists ends: behind M and the first a_permille of I (at least at F's end, at most at the array's).
+__device__ __forceinline__ int ransac_near_end(const RansacFar& f, int ns, int n_pchunks, int a_permille) {
+    const int out = f.n_far + f.n_mid, a = (int)((long long)(ns - out) * a_permille / 1000);
+    return min(n_pchunks, (out + a + RS_PCH - 1) / RS_PCH);
+}
 // RansacPlan — exact bail-out.  The loop of ransacRegistration (registration.cpp:284-290) uses an iteration's inlier count only
 // to ask whether it beats the best so far (strictly) — the early exit `fitness > confidence` can fire only on such a new best,
 // the loop having stopped otherwise when the earlier best passed it.  So a hypothesis whose count over the first chunks plus
@@ -515,12 +553,13 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
 // (One thread of k_ransac_hypotheses makes the plan: a launch of its own - one thread behind a stream barrier - cost as much as k_ransac_best.)
 __device__ __forceinline__ void ransac_plan(const PlanJob& j) {
     const int best = j.state[0], ns = j.ns, n_pchunks = j.n_pchunks;
-    if (j.n_live) { j.n_live[0] = 0; j.n_live[2] = 0; }      // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided)
+    if (j.n_live) { j.n_live[0] = 0; j.n_live[2] = 0; j.n_live[4] = 0; }      // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided, near)
     int c_split = n_pchunks;
     const int rest = best - max((int)((long long)best * j.drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
     if (rest >= ns / 8)                                      // (below an eighth of the points a second phase costs more than it saves)
         c_split = min(n_pchunks, (ns - rest + RS_PCH - 1) / RS_PCH);
     j.plan[0] = c_split; j.plan[1] = 0; j.plan[2] = 0;
+    j.plan[3] = j.far ? ransac_near_end(*j.far, ns, n_pchunks, j.a_permille) : 0; j.plan[4] = 0;     // near lists: where phase 1 ends, survivors
 }
 // largest count of a batch (prefix counts after phase 1, full counts after phase 2) -> *dst by atomic max, one atomic per
 // workgroup (one per wave on the same address cost 12 us for a 65,536-hypothesis batch)
@@ -583,37 +622,46 @@ __global__ void k_ransac_select(const TriView triples, int count, const int* __r
 // rule (a).  So the largest prefix count of the live ones is the batch's (plan[2]), and the list is built from them under the same
 // rules.  Phase 2's list holds the same hypotheses as k_ransac_select's,
 // in another order: counts are integer atomics, the order does not matter.  One workgroup: the live list is an eighth of a batch.
+// A NEAR hypothesis (RansacFarBound: `near`, *n_near entries, phase 1 over [c_far, plan[3])) has rest = the points behind its phase 1
+// plus ubf[h], which bounds its inliers in the F chunks it skipped: prefix + rest still bounds its full count from above and the
+// prefix is still a lower bound of it, so rules (a) and (b) hold as written.  Its survivors go to list2 (plan[4] of them).
 __global__ __launch_bounds__(1024)
-void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ n_live, const int* __restrict__ counts, int ns, float confidence,
-                          const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list) {
-    const int n = *n_live, c_split = plan[0], best = state[0], rest = ransac_rest(ns, c_split);
-    __shared__ int s_max, s_n;
-    if (threadIdx.x == 0) { s_max = 0; s_n = 0; }
+void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ n_live, const int* __restrict__ near, const int* __restrict__ n_near,
+                          const int* __restrict__ ubf, const int* __restrict__ counts, int ns, float confidence,
+                          const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list, int* __restrict__ list2) {
+    const int n = *n_live, n2 = near ? *n_near : 0, best = state[0], rest = ransac_rest(ns, plan[0]), rest2 = ransac_rest(ns, plan[3]);
+    __shared__ int s_max, s_n[2];
+    if (threadIdx.x == 0) { s_max = 0; s_n[0] = 0; s_n[1] = 0; }
     __syncthreads();
     int c = 0;
-    for (int i = threadIdx.x; i < n; i += 1024) c = max(c, counts[live[i]]);
+    for (int i = threadIdx.x; i < n + n2; i += 1024) c = max(c, counts[i < n ? live[i] : near[i - n]]);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) c = max(c, __shfl_xor(c, off, 64));
     if ((threadIdx.x & 63) == 0 && c > 0) atomicMax(&s_max, c);
     __syncthreads();
     const int in_batch = s_max, lane = threadIdx.x & 63;
-    for (int i0 = 0; i0 < n; i0 += 1024) {                       // (workgroup-uniform trip count: every lane reaches the ballot)
-        const int i = i0 + threadIdx.x;
-        bool keep = i < n && rest > 0;
-        int h = 0;
-        if (keep) {
-            h = live[i];
-            keep = ransac_keep(counts[h], rest, best, in_batch, ns, confidence);
+    for (int k = 0; k < 2; ++k) {                                    // the far list, then the near one
+        const int* const from = k ? near : live; int* const to = k ? list2 : list;
+        const int nk = k ? n2 : n;
+        for (int i0 = 0; i0 < nk; i0 += 1024) {                      // (workgroup-uniform trip count: every lane reaches the ballot)
+            const int i = i0 + threadIdx.x;
+            bool keep = i < nk;
+            int h = 0;
+            if (keep) {
+                h = from[i];
+                const int r = k ? rest2 + ubf[h] : rest;
+                keep = r > 0 && ransac_keep(counts[h], r, best, in_batch, ns, confidence);
+            }
+            const unsigned long long m = __ballot(keep);
+            if (!m) continue;
+            int at = 0;
+            if (lane == 0) at = atomicAdd(&s_n[k], __popcll(m));
+            at = __shfl(at, 0, 64);
+            if (keep) to[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
         }
-        const unsigned long long m = __ballot(keep);
-        if (!m) continue;
-        int at = 0;
-        if (lane == 0) at = atomicAdd(&s_n, __popcll(m));
-        at = __shfl(at, 0, 64);
-        if (keep) list[at + __popcll(m & ((1ull << lane) - 1ull))] = h;
     }
     __syncthreads();
-    if (threadIdx.x == 0) { plan[1] = s_n; plan[2] = in_batch; }
+    if (threadIdx.x == 0) { plan[1] = s_n[0]; plan[2] = in_batch; plan[4] = s_n[1]; }
 }
 
 // RansacPointOrder - the order of the scored points.  An inlier count does not depend on the order its points are scored in, and pq2
@@ -634,13 +682,24 @@ void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ 
 // thread in total - 782 blocks at 200k points, 11 us for both launches; 7,800 blocks and 6e7 cached loads at 2M points, where a
 // call's batches take milliseconds each.  A scan launch of its own pays from some 10M points on, which no caller has.)
 // Stream order puts the first batch's dispatches, which read pq2, in front of the two launches, and the second batch's behind.
+// Three classes (RansacFarBound, far != nullptr): the outliers split into F and M (see RansacFar), in the order [F | M | I], each class
+// in its original relative order, by the same scan over two ballot words per wave.  k_order_flags also keeps the ordering pose and
+// adds the F pairs to the count table's bins (one LDS histogram per block, its non-empty bins added to the table by integer atomics:
+// any order gives the same table); block 0 of k_order_scatter writes the class sizes and the table's running sums.
+// far == nullptr (TDV_RANSAC_ORDER=1): the two-way order, no F.
 constexpr int RO_BLOCK = 256;
 __global__ __launch_bounds__(RO_BLOCK)
 void k_order_flags(const float* __restrict__ pq, int ns, const int* __restrict__ state, const float* __restrict__ best12, float tau,
-                   unsigned long long* __restrict__ mask, int* __restrict__ cnt) {
-    const int i = blockIdx.x * RO_BLOCK + threadIdx.x;
-    __shared__ int s_w[RO_BLOCK / 64];
-    bool out = false;
+                   unsigned long long* __restrict__ mask, int* __restrict__ cnt, RansacFar* __restrict__ far, float rF2) {
+    const int i = blockIdx.x * RO_BLOCK + threadIdx.x, n_words = (int)gridDim.x * (RO_BLOCK / 64);
+    __shared__ int s_w[2][RO_BLOCK / 64];
+    __shared__ unsigned s_hist[RF_BINS];
+    if (far) {
+        for (int b = threadIdx.x; b < RF_BINS; b += RO_BLOCK) s_hist[b] = 0u;
+        if (blockIdx.x == 0 && threadIdx.x < 12) far->ord12[threadIdx.x] = best12[threadIdx.x];
+        __syncthreads();
+    }
+    bool out = false, is_far = false;
     if (i < ns) {
         out = true;
         if (state[0] != 0) {
@@ -649,36 +708,80 @@ void k_order_flags(const float* __restrict__ pq, int ns, const int* __restrict__
 #pragma unroll
             for (int e = 0; e < 12; ++e) r[e] = (v2f){best12[e], best12[e]};
             const Pair2 a{{g[0], g[0]}, {g[1], g[1]}, {g[2], g[2]}, {g[3], g[3]}, {g[4], g[4]}, {g[5], g[5]}};
-            out = !(ref_pair_d2(r, a).x < tau);
+            const float d2 = ref_pair_d2(r, a).x;
+            out = !(d2 < tau);
+            if (far) {
+                bool finite = true;
+#pragma unroll
+                for (int c = 0; c < 6; ++c) finite &= fabsf(g[c]) <= FLT_MAX;
+                is_far = out && finite && d2 >= rF2;               // (a NaN d2 compares false: M)
+                if (is_far) atomicAdd(&s_hist[rf_bin(d2)], 1u);
+            }
         }
     }
-    const unsigned long long m = __ballot(out);
-    if ((threadIdx.x & 63) == 0) { mask[i >> 6] = m; s_w[threadIdx.x >> 6] = __popcll(m); }     // (mask: RO_BLOCK / 64 words per block of the grid)
+    const unsigned long long m = __ballot(out), mf = __ballot(is_far);
+    if ((threadIdx.x & 63) == 0) {      // (mask: RO_BLOCK / 64 words per block of the grid, the F words behind the outlier words)
+        mask[i >> 6] = m; s_w[0][threadIdx.x >> 6] = __popcll(m);
+        if (far) { mask[n_words + (i >> 6)] = mf; s_w[1][threadIdx.x >> 6] = __popcll(mf); }
+    }
     __syncthreads();
     if (threadIdx.x == 0) {
-        int c = 0;
-        for (int w = 0; w < RO_BLOCK / 64; ++w) c += s_w[w];
+        int c = 0, cf = 0;
+        for (int w = 0; w < RO_BLOCK / 64; ++w) { c += s_w[0][w]; if (far) cf += s_w[1][w]; }
         cnt[blockIdx.x] = c;
+        if (far) cnt[gridDim.x + blockIdx.x] = cf;
     }
+    if (far)
+        for (int b = threadIdx.x; b < RF_BINS; b += RO_BLOCK) { const unsigned v = s_hist[b]; if (v) atomicAdd(&far->hist[b], v); }
 }
 __global__ __launch_bounds__(RO_BLOCK)
 void k_order_scatter(const float* __restrict__ pq, int ns, const unsigned long long* __restrict__ mask, const int* __restrict__ cnt,
-                     float* __restrict__ pq2) {
+                     float* __restrict__ pq2, RansacFar* __restrict__ far) {
     const int i = blockIdx.x * RO_BLOCK + threadIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    __shared__ int s_before[RO_BLOCK / 64], s_all[RO_BLOCK / 64], s_w[RO_BLOCK / 64];
-    int before = 0, all = 0;
-    for (int b = threadIdx.x; b < (int)gridDim.x; b += RO_BLOCK) { const int c = cnt[b]; all += c; if (b < (int)blockIdx.x) before += c; }
+    const int n_words = (int)gridDim.x * (RO_BLOCK / 64);
+    __shared__ int s_before[2][RO_BLOCK / 64], s_all[2][RO_BLOCK / 64], s_w[2][RO_BLOCK / 64];
+    int before = 0, all = 0, fbefore = 0, fall = 0;
+    for (int b = threadIdx.x; b < (int)gridDim.x; b += RO_BLOCK) {
+        const int c = cnt[b]; all += c; if (b < (int)blockIdx.x) before += c;
+        if (far) { const int f = cnt[gridDim.x + b]; fall += f; if (b < (int)blockIdx.x) fbefore += f; }
+    }
 #pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { before += __shfl_xor(before, off, 64); all += __shfl_xor(all, off, 64); }
-    const unsigned long long m = mask[i >> 6];
-    if (lane == 0) { s_before[wave] = before; s_all[wave] = all; s_w[wave] = __popcll(m); }
+    for (int off = 32; off > 0; off >>= 1) {
+        before += __shfl_xor(before, off, 64); all += __shfl_xor(all, off, 64);
+        fbefore += __shfl_xor(fbefore, off, 64); fall += __shfl_xor(fall, off, 64);
+    }
+    const unsigned long long m = mask[i >> 6], mf = far ? mask[n_words + (i >> 6)] : 0ull;
+    if (lane == 0) {
+        s_before[0][wave] = before; s_all[0][wave] = all; s_w[0][wave] = __popcll(m);
+        s_before[1][wave] = fbefore; s_all[1][wave] = fall; s_w[1][wave] = __popcll(mf);
+    }
     __syncthreads();
-    if (i >= ns) return;
     int out_before = 0, out_all = 0, rank = __popcll(m & ((1ull << lane) - 1ull));      // rank: the block's outliers in front of this point
-    for (int w = 0; w < RO_BLOCK / 64; ++w) { out_before += s_before[w]; out_all += s_all[w]; if (w < wave) rank += s_w[w]; }
-    const bool out = (m >> lane) & 1ull;
-    // outliers: [0, out_all) ; inliers behind them: the points in front of this one that are no outliers
-    const int pos = out ? out_before + rank : out_all + (i - out_before - rank);
+    int far_before = 0, far_all = 0, frank = __popcll(mf & ((1ull << lane) - 1ull));    // ... and its F pairs
+    for (int w = 0; w < RO_BLOCK / 64; ++w) {
+        out_before += s_before[0][w]; out_all += s_all[0][w]; if (w < wave) rank += s_w[0][w];
+        far_before += s_before[1][w]; far_all += s_all[1][w]; if (w < wave) frank += s_w[1][w];
+    }
+    if (far && blockIdx.x == 0) {        // the class sizes and the count table's running sums (workgroup-uniform branch)
+        __shared__ unsigned s_part[RO_BLOCK];
+        constexpr int PER = RF_BINS / RO_BLOCK;
+        unsigned v[PER], sum = 0u;
+#pragma unroll
+        for (int e = 0; e < PER; ++e) { v[e] = far->hist[threadIdx.x * PER + e]; sum += v[e]; }
+        s_part[threadIdx.x] = sum;
+        __syncthreads();
+        unsigned run = 0u;
+        for (int t = 0; t < (int)threadIdx.x; ++t) run += s_part[t];
+#pragma unroll
+        for (int e = 0; e < PER; ++e) { run += v[e]; far->cum[threadIdx.x * PER + e] = run; }
+        if (threadIdx.x == 0) { far->n_far = far_all; far->n_mid = out_all - far_all; far->c_far = far_all / RS_PCH; }
+    }
+    if (i >= ns) return;
+    const bool out = (m >> lane) & 1ull, is_far = (mf >> lane) & 1ull;
+    // F: [0, far_all) ; M: [far_all, out_all) ; inliers behind them: the points in front of this one that are no outliers
+    const int pos = is_far ? far_before + frank
+                  : out    ? far_all + (out_before + rank) - (far_before + frank)
+                           : out_all + (i - out_before - rank);
     const float4 a = reinterpret_cast<const float4*>(pq)[2 * (size_t)i], b = reinterpret_cast<const float4*>(pq)[2 * (size_t)i + 1];
     float* o = pq2 + (size_t)(pos >> 1) * 12 + (pos & 1);
     o[0] = a.x; o[2] = a.y; o[4] = a.z; o[6] = a.w; o[8] = b.x; o[10] = b.y;
@@ -692,14 +795,14 @@ void k_order_scatter(const float* __restrict__ pq, int ns, const unsigned long l
 // The winning hypothesis' 12 floats go to best12, and the host gets ONE record per batch - { best local index or -1, its count,
 // local stop index or -1, bad correspondence flag } - where it used to download every count and walk them.  The same launch
 // raises state[0] to the batch's largest full count, as k_ransac_best did (state == nullptr: a batch without bail-out).
-// live != nullptr (a bounded batch, confidence >= 0): only the live list is read.  A dead hypothesis has count 0: no new best
+// live != nullptr (a bounded batch, confidence >= 0): only the live lists - far and near - are read.  A dead hypothesis has count 0: no new best
 // (strict > on a best fitness >= 0), no exit (0 > confidence is false), nothing to raise.
 // One workgroup; the first batch and the live lists are a few thousand entries (a whole batch is walked only with the bound off).
 __global__ __launch_bounds__(1024)
 void k_ransac_finish(const TriView triples, int count, const int* __restrict__ counts, const int* __restrict__ live, const int* __restrict__ n_live,
-                     const float* __restrict__ hyp, int h_pad, int ns, float confidence, int it0,
+                     const int* __restrict__ near, const int* __restrict__ n_near, const float* __restrict__ hyp, int h_pad, int ns, float confidence, int it0,
                      int* __restrict__ state, int* __restrict__ sel, float* __restrict__ best12, const int* __restrict__ bad, int* __restrict__ rec) {
-    const int n = live ? *n_live : count;
+    const int n1 = live ? *n_live : count, n = n1 + (live && near ? *n_near : 0);      // (the near list behind the far one)
     const float fn = static_cast<float>((size_t)ns);
     __shared__ int s_stop, s_max;
     __shared__ unsigned long long s_best[16];
@@ -708,7 +811,7 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     int stop = INT_MAX, cmax = 0;
 #pragma unroll 4
     for (int i = threadIdx.x; i < n; i += 1024) {
-        const int h = live ? live[i] : i;
+        const int h = live ? (i < n1 ? live[i] : near[i - n1]) : i;
         if (!live && !triples.valid(h)) continue;                // a skipped iteration (registration.cpp:240)
         const int c = counts[h];
         cmax = max(cmax, c);
@@ -726,7 +829,7 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     unsigned long long best = 0ull;
 #pragma unroll 4
     for (int i = threadIdx.x; i < n; i += 1024) {
-        const int h = live ? live[i] : i;
+        const int h = live ? (i < n1 ? live[i] : near[i - n1]) : i;
         if (h > k_stop || (!live && !triples.valid(h))) continue;
         const float fit = static_cast<float>(counts[h]) / fn;    // registration.cpp:281
         if (!(fit > 0.f)) continue;
@@ -960,7 +1063,7 @@ __device__ __forceinline__ int rb_walk(const float* r, const float* __restrict__
     return ub;
 }
 // The hypothesis' band test and its bound threshold (k_ransac_hypotheses' E, from the same f32 operations)
-struct RbHyp { float r[12]; float tb; bool bounded; };
+struct RbHyp { float r[12]; float tb, E; bool bounded; };
 __device__ __forceinline__ RbHyp rb_load(const float* __restrict__ hyp, int h_pad, int h, bool valid, const unsigned* __restrict__ pmax,
                                          float sqrt_tau, float band_u, float margin) {
     RbHyp o;
@@ -969,9 +1072,73 @@ __device__ __forceinline__ RbHyp rb_load(const float* __restrict__ hyp, int h_pa
     const float A = ransac_band_reach(o.r, __uint_as_float(*pmax));
     const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
     o.bounded = E < 0.25f * sqrt_tau;                             // false for NaN (non-finite data or hypothesis)
+    o.E = E;
     const float sb = sqrt_tau + margin * E;
     o.tb = sb * sb * (1.0f + 1e-6f);
     return o;
+}
+// ------------------------------------------------------------------ RansacFarBound
+// Almost every hypothesis the leaf bound leaves alive is a near-perfect pose, and almost none of the ordering pose B's far outliers
+// (F of RansacFar) lies near its match under any such pose.  With Delta_h = max over the 8 corners c of the finite sources' bounding
+// box of |(R_h - R_B) c + (t_h - t_B)| - the displacement between the two poses is affine in the point and its norm convex, so the
+// corner maximum is the maximum over the box, which holds the source of every F pair - the triangle inequality gives
+// D_h(i) >= D_B(i) - Delta_h for D = |R p + t - q| in real arithmetic.  So only the F pairs with D_B < s + Delta_h can be inliers of
+// h, and the count table bounds their number: UB_F(h).  A live hypothesis whose UB_F is small goes on the batch's NEAR list: its
+// phase 1 skips the chunks wholly inside F (a chunk that straddles F's end is scored; its F pairs may be counted in UB_F as well,
+// which only loosens a valid bound), k_ransac_select_live adds UB_F(h) to its rest, and if it survives phase 2 scores the skipped
+// chunks too: a survivor's count is exact, a dropped one's partial, as for every other hypothesis of RansacPlan.
+//
+// Exactness, with u = 2^-24, A_h, A_B the poses' reaches (ransac_band_reach) and E = 16 u (A + s) their bands, both below s / 4 - with
+// either band off the hypothesis is far.  An F pair that UB_F(h) does not count has d2_B >= T in the reference arithmetic (the table
+// errs upward), T = ((s + Delta_f + 3 (E_h + E_B)) (1 + 4e-6))^2 (1 + 1e-6) in f32, Delta_f the f32 value of Delta_h.
+//   (1) Delta_f.  R_h - R_B and t_h - t_B round once each (<= u (|R_h| + |R_B|) per entry), the FMA chain over |c| <= P is within
+//       gamma_3 of its real value: per component within 5 u (A_h + A_B), in length 8.7 u (A_h + A_B); the squared norm and the
+//       square root add a factor (1 + 3 u).  Delta_h <= (1 + 3 u) Delta_f + 9 u (A_h + A_B).
+//   (2) the reference's rounding (RansacLeafBound's (2), both ways): sqrt(d2_ref) <= (1 + 3 u) D + 7 u A and, for h,
+//       D_h >= s + E_h gives d2_ref >= tau.
+//   sqrt(T) in real arithmetic is at least (s + Delta_f + 3 (E_h + E_B)) (1 + 4e-6) (1 - 4 u) (the sum's and the products' roundings),
+//   so D_B >= (sqrt(T) - 7 u A_B) / (1 + 3 u) >= (s + Delta_f + 3 (E_h + E_B)) (1 + 4e-6 - 8 u) - 7 u A_B, and with
+//   4e-6 > 11 u, 16 u A <= E:  D_B >= s + (1 + 3 u) Delta_f + 3 (E_h + E_B) - 0.5 E_B >= s + Delta_h + 2.4 E_h + 1.9 E_B
+//   > s + Delta_h + E_h.  Hence D_h >= s + E_h: the pair is no inlier of h in the reference arithmetic.  The margin 3 (E_h + E_B) is
+//   RansacLeafBound's 3 E for two poses; tests/test_ransac_far_bound_margin.py checks the chain in emulated f32 on the shell.
+// A box with no finite source decodes to NaN corners, a non-finite pose gives a NaN Delta: T is then no finite number and the
+// hypothesis is far.
+struct FarJob { const RansacFar* far; const unsigned* enc; int* near; int* n_near; int* ubf; int u_cut_permille; };    // far == nullptr: every live hypothesis is far
+// Whether the live hypothesis o goes on the near list; ub_f = UB_F(h) then.  best = the best count of the earlier batches.
+__device__ __forceinline__ bool rf_near(const RbHyp& o, const FarJob& f, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, int best, int& ub_f) {
+    if (!f.far || !o.bounded || f.far->c_far < 1) return false;              // (no band; skipping F saves less than a chunk)
+    float d[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) d[e] = f.far->ord12[e];
+    const float E_B = (band_u * ransac_band_reach(d, __uint_as_float(*pmax)) + band_u * sqrt_tau) * 1.0001f;
+    if (!(E_B < 0.25f * sqrt_tau)) return false;                             // the ordering pose's band is off
+#pragma unroll
+    for (int e = 0; e < 12; ++e) d[e] = o.r[e] - d[e];
+    float lo[3], hi[3], m2 = 0.f;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) { lo[c] = rl_dec(f.enc[c]); hi[c] = rl_dec(f.enc[6 + c]); }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        const float x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
+        float n2 = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { const float v = fmaf(d[c], x, fmaf(d[3 + c], y, fmaf(d[6 + c], z, d[9 + c]))); n2 = fmaf(v, v, n2); }
+        m2 = (n2 > m2 || n2 != n2) ? n2 : m2;                                // (a NaN stays)
+    }
+    const float sb = (sqrt_tau + sqrtf(m2) + 3.f * (o.E + E_B)) * (1.0f + 4e-6f), T = sb * sb * (1.0f + 1e-6f);
+    if (!(T <= FLT_MAX)) return false;
+    ub_f = (int)f.far->cum[rf_bin(T)];
+    return ub_f <= (int)((long long)best * f.u_cut_permille / 1000);
+}
+// A live hypothesis onto its list
+__device__ __forceinline__ void rf_append(bool is_live, const RbHyp& o, const FarJob& f, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, int best,
+                                          int lane, int h, int* __restrict__ live, int* __restrict__ n_live) {
+    int ub_f = 0;
+    const bool near = is_live && rf_near(o, f, pmax, sqrt_tau, band_u, best, ub_f);
+    rb_append(is_live && !near, lane, h, live, n_live);
+    if (!f.far) return;
+    rb_append(near, lane, h, f.near, f.n_near);
+    if (near) f.ubf[h] = ub_f;
 }
 // RB_ONE / RB_COARSE: a workgroup per 64 hypotheses of the batch.  RB_COARSE also zeroes the fine level's per-slot sums (acc) of
 // the hypotheses it leaves undecided and the ticket of its slot block.
@@ -980,7 +1147,7 @@ __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView triples, int count, const float* __restrict__ leaves, int n_lpairs,
                     const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
                     int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
-                    int* __restrict__ acc, int* __restrict__ ticket) {
+                    int* __restrict__ acc, int* __restrict__ ticket, const FarJob fj) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.x * 64 + lane;
     __shared__ int s_ub[64];
@@ -1003,7 +1170,7 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView trip
     const bool gated = valid && (!o.bounded || !walk);            // live without a walk
     const bool undecided = MODE == RB_COARSE && valid && !gated && total > best;
     const bool is_live = gated || (MODE == RB_ONE && valid && total > best);
-    rb_append(is_live, lane, h, live, n_live);
+    rf_append(is_live, o, fj, pmax, sqrt_tau, band_u, best, lane, h, live, n_live);
     if (MODE == RB_COARSE) { const int slot = rb_append(undecided, lane, h, und, n_und); if (undecided) acc[slot] = 0; }
 }
 // k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a fifth of the batch, too few workgroups to fill the chip with
@@ -1017,7 +1184,7 @@ __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* __restrict__ leaves, int n_lpairs,
                          const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state,
                          int* __restrict__ live, int* __restrict__ n_live, const int* __restrict__ und, const int* __restrict__ n_und,
-                         int* __restrict__ acc, int* __restrict__ ticket) {
+                         int* __restrict__ acc, int* __restrict__ ticket, const FarJob fj) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = *n_und, best = state[0];
     const int per_y = (n_lpairs + RB_FINE_Y - 1) / RB_FINE_Y, y0 = blockIdx.y * per_y, y1 = min(n_lpairs, y0 + per_y);
@@ -1043,7 +1210,7 @@ void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* 
     if (__shfl(arrived, 0, 64) != (int)gridDim.y - 1) return;    // not the last workgroup of this slot block
     const int total = h >= 0 ? atomicAdd(&acc[slot], 0) : 0;
     const bool is_live = h >= 0 && total > best;
-    rb_append(is_live, lane, h, live, n_live);
+    rf_append(is_live, o, fj, pmax, sqrt_tau, band_u, best, lane, h, live, n_live);
 }
 
 #ifdef TDV_STUDY
@@ -1125,23 +1292,24 @@ struct RansacBlock {
     unsigned pmax;                           // the largest |source coordinate| (bits of a non-negative float)
     unsigned long long rescored, scored;     // the fast pass' statistics: point pairs scored twice, (wave, chunk) pairs scored
     int state[2];                            // [0] the best count known so far (RansacPlan)
-    int plan[2][4];                          // per batch buffer: phase-1 chunks, survivors, largest prefix count (one word unused)
+    int plan[2][8];                          // per batch buffer: phase-1 chunks, survivors, largest prefix count; near lists: phase 1's end, survivors (three words unused)
     float best12[12];                        // the winning hypothesis
     double out2[2];                          // its error sum and inlier count
     int sel[4];                              // RansacFinish's loop state: best fitness (bits), its count, its iteration, stopped
     int rec[2][8];                           // per batch buffer: RansacFinish's record (4 ints; moved as 32 bytes under TDV_RANSAC_RECORD=copy)
+    RansacFar far;                           // RansacFarBound: the ordering pose, the class sizes, the count table
 };
 constexpr size_t kRansacReadBack = offsetof(RansacBlock, sel);
 static_assert(std::is_trivially_copyable<RansacBlock>::value, "memset, copied back");
 static_assert(offsetof(RansacBlock, rescored) % 8 == 0 && offsetof(RansacBlock, scored) == offsetof(RansacBlock, rescored) + 8, "the kernels index the two as one u64[2]");
 static_assert(offsetof(RansacBlock, out2) % 8 == 0 && offsetof(RansacBlock, out2) + sizeof(double[2]) == kRansacReadBack, "the part read back is a prefix that ends with out2");
-// RansacLeafBound's list lengths per batch buffer; ransac_plan zeroes both of a buffer through &n_live[q]: [0] and [2]
-struct RansacLive { int n_live[2], n_und[2]; };
-static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * sizeof(int), "ransac_plan's n_live[2]");
+// RansacLeafBound's and RansacFarBound's list lengths per batch buffer; ransac_plan zeroes a buffer's three through &n_live[q]: [0], [2] and [4]
+struct RansacLive { int n_live[2], n_und[2], n_near[2]; };
+static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * sizeof(int) && offsetof(RansacLive, n_near) == offsetof(RansacLive, n_live) + 4 * sizeof(int), "ransac_plan's n_live[2], n_live[4]");
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, merge, record_copy, order; int drop_permille; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, merge, record_copy, order, far; int drop_permille, a_permille, u_cut_permille; float far_radius; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1156,8 +1324,16 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     const bool bound_env_off = getenv("TDV_RANSAC_BOUND") && atoi(getenv("TDV_RANSAC_BOUND")) == 0;   // A/B knob
     k.bound = k.bailout && !k.merge && !bound_env_off;
     // RansacPointOrder: the best's outliers first, once per call after the first batch (the merged dispatch has no best12 by then)
-    const bool order_env_off = getenv("TDV_RANSAC_ORDER") && atoi(getenv("TDV_RANSAC_ORDER")) == 0;   // A/B knob
-    k.order = k.bailout && !k.merge && !order_env_off;
+    // TDV_RANSAC_ORDER: 0 the natural order, 1 the two-way order without skipping, unset (or anything else) the three classes of
+    // RansacFarBound, whose near lists need the bound's lists and box
+    const char* const order_env = getenv("TDV_RANSAC_ORDER");   // A/B knob
+    k.order = k.bailout && !k.merge && !(order_env && atoi(order_env) == 0);
+    k.far = k.order && k.bound && !(order_env && atoi(order_env) == 1);
+    // tuning knobs: F from far_radius thresholds on; a near list's phase 1 takes a_permille of I; near means UB_F <= u_cut_permille of the
+    // best count (profiles/r13/ransac_far_outliers.md)
+    k.far_radius = study_env("TDV_RANSAC_FAR_RADIUS") ? (float)atof(study_env("TDV_RANSAC_FAR_RADIUS")) : 4.f;
+    k.a_permille = study_env("TDV_RANSAC_FAR_A_PERMILLE") ? atoi(study_env("TDV_RANSAC_FAR_A_PERMILLE")) : 110;
+    k.u_cut_permille = study_env("TDV_RANSAC_FAR_UCUT_PERMILLE") ? atoi(study_env("TDV_RANSAC_FAR_UCUT_PERMILLE")) : 22;
     k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
     k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
     k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 50;   // tuning knob: phase 1 over the first N - 0.95 best points (natural order: 5 to 100 measured equal;
@@ -1170,8 +1346,9 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
 struct RansacBuf {
     float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the uploaded triples; bail-out: phase 2's list
     int *live, *und, *acc, *ticket;                   // RansacLeafBound: live list, undecided list, its fine sums and tickets
-    int* units;                                       // bail-out: job B's ticket words, [2 phases][8 XCDs][h_pad / RS_BLOCK], zeroed by the batch's k_ransac_hypotheses
-    int *plan, *rec, *n_live, *n_und;                 // this buffer's fields of the RansacBlock and of RansacLive
+    int *near, *list2, *ubf;                          // RansacFarBound: near list, its phase 2's list, UB_F per hypothesis
+    int* units;                                       // bail-out: job B's ticket words, [far, near][2 phases][8 XCDs][h_pad / RS_BLOCK], zeroed by the batch's k_ransac_hypotheses
+    int *plan, *rec, *n_live, *n_und, *n_near;        // this buffer's fields of the RansacBlock and of RansacLive
     void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
     hipEvent_t ev;                                    // the batch's end
 };
@@ -1197,7 +1374,8 @@ struct RansacRun {
     size_t tri_bytes;                                 // per triple: one packed word or an int4
     float *pq = nullptr, *pq2 = nullptr, *pq3 = nullptr, *leaves = nullptr, *cleaves = nullptr; double* slabs = nullptr;
     RansacBlock *d = nullptr, *h = nullptr; RansacLive* lv = nullptr;
-    unsigned long long* ord_mask = nullptr; int* ord_cnt = nullptr; bool ordered = false;     // RansacPointOrder: ballot words, block counts; done for this call
+    unsigned long long* ord_mask = nullptr; int* ord_cnt = nullptr; bool ordered = false;     // RansacPointOrder: ballot words, block counts (outliers, then F); done for this call
+    unsigned* enc = nullptr;                          // RansacLeafBound: the finite coordinates' bounds per axis
     RansacBuf buf[2] = {};
     RansacBatch pending = {}; bool has_pending = false;       // merged dispatch (study build): the batch whose phase 2 is not enqueued yet
     double wave_chunks = 0.0;                         // wave x chunk pairs the call would score without bail-out
@@ -1231,7 +1409,7 @@ struct RansacRun {
             for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list)); TDV_TRY(ws_alloc(ctx, (size_t)unit_words(), &B.units)); }
             TDV_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         }
-        if (k.order) { TDV_TRY(ws_alloc(ctx, (size_t)order_blocks() * (RO_BLOCK / 64), &ord_mask)); TDV_TRY(ws_alloc(ctx, (size_t)order_blocks(), &ord_cnt)); }
+        if (k.order) { TDV_TRY(ws_alloc(ctx, (size_t)2 * order_blocks() * (RO_BLOCK / 64), &ord_mask)); TDV_TRY(ws_alloc(ctx, (size_t)2 * order_blocks(), &ord_cnt)); }
         if (k.bound) {
             for (RansacBuf& B : buf) {
                 TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.live)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.und));
@@ -1239,6 +1417,7 @@ struct RansacRun {
             }
             TDV_TRY(ws_alloc(ctx, 1, &lv));
         }
+        if (k.far) for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.near)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list2)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.ubf)); }
         rblocks = (ns + 255) / 256; TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
         // pinned: the block | 2 x triples | 2 x counts (traced calls only)
         const size_t sz_blk = align_up(sizeof(RansacBlock), 64), sz_tri = align_up((size_t)batch * tri_bytes, 64), sz_cnt = trace ? align_up((size_t)batch * 4, 64) : 0;
@@ -1247,21 +1426,21 @@ struct RansacRun {
         if (trace) TDV_HIP(ctx, hipMemcpyAsync(&h->bad, &d->bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts (RansacFinish: the flag comes in the record)
         for (int q = 0; q < 2; ++q) {
             RansacBuf& B = buf[q];
-            B.plan = d->plan[q]; B.rec = d->rec[q]; B.n_live = lv ? &lv->n_live[q] : nullptr; B.n_und = lv ? &lv->n_und[q] : nullptr;
+            B.plan = d->plan[q]; B.rec = d->rec[q]; B.n_live = lv ? &lv->n_live[q] : nullptr; B.n_und = lv ? &lv->n_und[q] : nullptr; B.n_near = lv ? &lv->n_near[q] : nullptr;
             B.h_tri = ctx->pin + sz_blk + q * sz_tri; B.h_cnt = reinterpret_cast<int*>(ctx->pin + sz_blk + 2 * sz_tri + q * sz_cnt); B.h_rec = h->rec[q];
         }
         buf[0].ev = event_acquire(ctx); buf[1].ev = event_acquire(ctx);   // from the ctx's pool: no create/destroy per call
         if (!buf[0].ev || !buf[1].ev) { release_events(); return TDV_ERR_OOM; }
         return TDV_OK;
     }
-    int unit_words() const { return 2 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's
+    int unit_words() const { return 4 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's, then the near lists' two
     int order_blocks() const { return (ns + RO_BLOCK - 1) / RO_BLOCK; }
     void release_events() { for (RansacBuf& B : buf) event_release(ctx, B.ev); }
     // RansacLeafBound's summary of the pairs: fine and coarse leaves along the Morton order
     int leaf_summary() {
         const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_cleaves = (ns + RL_COARSE - 1) / RL_COARSE;
         n_lpairs = (n_leaves + 1) / 2; n_cpairs = (n_cleaves + 1) / 2;
-        unsigned* enc = nullptr; unsigned long long* keys = nullptr; unsigned* vals = nullptr;
+        unsigned long long* keys = nullptr; unsigned* vals = nullptr;
         TDV_TRY(ws_alloc(ctx, 12, &enc)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &keys)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &vals));
         TDV_TRY(ws_alloc(ctx, (size_t)n_lpairs * 32, &leaves)); TDV_TRY(ws_alloc(ctx, (size_t)n_cpairs * 32, &cleaves));
         TDV_HIP(ctx, hipMemsetAsync(leaves, 0, (size_t)n_lpairs * 32 * sizeof(float), s));
@@ -1287,7 +1466,8 @@ struct RansacRun {
     int hypotheses(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
         TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
-        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words() : 0};
+        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words() : 0,
+                           k.far && b.bounded ? &d->far : nullptr, k.a_permille};
         k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan);
         return TDV_OK;
     }
@@ -1300,7 +1480,7 @@ struct RansacRun {
         else
 #endif
         if (k.score_fast) {
-            const ScoreJob ja{B.hyp, B.counts, nullptr, nullptr, hb, range_cut(hb, n_pchunks).ranges, nullptr, nullptr};
+            const ScoreJob ja{B.hyp, B.counts, nullptr, nullptr, hb, range_cut(hb, n_pchunks).ranges, nullptr, nullptr, nullptr};
             const int gA = score_grid(hb, ja.ps);
             k_ransac_score_fast<<<gA, RS_BLOCK, 0, s>>>(ja, ja, gA, h_pad, pq2, n_pchunks, tau, &d->rescored);
             wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
@@ -1313,37 +1493,41 @@ struct RansacRun {
     // RansacLeafBound: the dead hypotheses out - the batch's live list
     void bound(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q]; const int bgrid = (b.cnt + 63) / 64;
+        const FarJob fj{k.far ? &d->far : nullptr, enc, B.near, B.n_near, B.ubf, k.u_cut_permille};
         if (k.one_level)
             k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
-                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr);
+                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr, fj);
         else {
             k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, cleaves, n_cpairs, &d->pmax, sqrt_tau, band_u,
-                                                                      d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket);
+                                                                      d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, fj);
             k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
-                                                                                  d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket);
+                                                                                  d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, fj);
         }
     }
     // RansacPointOrder: pq2 again from pq, the outliers of the best so far (best12, state[0]: the batches enqueued before) first
     void point_order() {
-        k_order_flags<<<order_blocks(), RO_BLOCK, 0, s>>>(pq, ns, d->state, d->best12, tau, ord_mask, ord_cnt);
-        k_order_scatter<<<order_blocks(), RO_BLOCK, 0, s>>>(pq, ns, ord_mask, ord_cnt, pq2);
+        RansacFar* const far = k.far ? &d->far : nullptr;
+        k_order_flags<<<order_blocks(), RO_BLOCK, 0, s>>>(pq, ns, d->state, d->best12, tau, ord_mask, ord_cnt, far, std::max(tau, k.far_radius * k.far_radius * tau));
+        k_order_scatter<<<order_blocks(), RO_BLOCK, 0, s>>>(pq, ns, ord_mask, ord_cnt, pq2, far);
         ordered = true;
     }
-    ScoreJob job_a(const RansacBatch& b) const { return ScoreJob{buf[b.q].hyp, buf[b.q].counts, buf[b.q].plan, nullptr, hyp_blocks(b.cnt), range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, nullptr, nullptr}; }
+    ScoreJob job_a(const RansacBatch& b) const { return ScoreJob{buf[b.q].hyp, buf[b.q].counts, buf[b.q].plan, nullptr, hyp_blocks(b.cnt), range_cut(hyp_blocks(b.cnt), n_pchunks).ranges, nullptr, nullptr, nullptr}; }
     // phase 1: the batch's hypotheses (job A) - or, bounded, its live list as a job B (resident workgroups that pull units) - over
     // the chunks its plan sets
     void phase1(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
-        const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, h_pad / RS_BLOCK, 0, B.n_live, B.units};
+        const int hbw = h_pad / RS_BLOCK;
+        const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, hbw, 0, B.n_live, B.units, nullptr};
+        const ScoreJob jn = k.far ? ScoreJob{B.hyp, B.counts, B.plan, B.near, hbw, 0, B.n_near, B.units + 16 * hbw, &d->far.c_far} : jl;   // the near list rides behind the far one
         const int g1 = score_grid(ja.hb, ja.ps);          // (a multiple of 8: job B's XCD numbering starts there)
         ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-        if (b.bounded) k_ransac_score_fast<<<unit_grid(cus), RS_BLOCK, 0, s>>>(jl, jl, 0, h_pad, pq2, n_pchunks, tau, &d->rescored);
+        if (b.bounded) k_ransac_score_fast<<<unit_grid(cus), RS_BLOCK, 0, s>>>(jn, jl, 0, h_pad, pq2, n_pchunks, tau, &d->rescored);
         else k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(ja, ja, g1, h_pad, pq2, n_pchunks, tau, &d->rescored);
     }
     // survivors of the batch: the in-batch bound first (largest prefix count), then the list (bounded: both in one launch over its live list)
     int select(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
-        if (b.bounded) k_ransac_select_live<<<1, 1024, 0, s>>>(B.live, B.n_live, B.counts, ns, confidence, d->state, B.plan, B.list);
+        if (b.bounded) k_ransac_select_live<<<1, 1024, 0, s>>>(B.live, B.n_live, k.far ? B.near : nullptr, B.n_near, B.ubf, B.counts, ns, confidence, d->state, B.plan, B.list, B.list2);
         else {
             k_ransac_best<<<(b.cnt + 1023) / 1024, 1024, 0, s>>>(tri(B), b.cnt, B.counts, B.plan + 2);
             k_ransac_select<<<(b.cnt + 255) / 256, 256, 0, s>>>(tri(B), b.cnt, B.counts, ns, confidence, d->state, B.plan, B.list);
@@ -1357,9 +1541,10 @@ struct RansacRun {
     // job B behind the phase 1 `a` of the next batch, g1 workgroups
     int phase2(const RansacBatch& b, const ScoreJob* a = nullptr, int g1 = 0) {
         const RansacBuf& B = buf[b.q]; const int hbw = h_pad / RS_BLOCK;
-        const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbw, 0, nullptr, B.units + 8 * hbw};
+        const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbw, 0, nullptr, B.units + 8 * hbw, nullptr};
+        const ScoreJob jn = k.far && b.bounded ? ScoreJob{B.hyp, B.counts, B.plan, B.list2, hbw, 0, nullptr, B.units + 24 * hbw, &d->far.c_far} : jb;   // the near list's survivors behind the far one's
         const int g2 = unit_grid(cus);
-        { ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE); k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(a ? *a : jb, jb, g1, h_pad, pq2, n_pchunks, tau, &d->rescored); }
+        { ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE); k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(a ? *a : jn, jb, g1, h_pad, pq2, n_pchunks, tau, &d->rescored); }
         TDV_CHECK_LAUNCH(ctx); return TDV_OK;
     }
     // the batch's end: RansacFinish and its record, or - traced - every count to the host; then the event.  with_state: the batch's
@@ -1371,7 +1556,7 @@ struct RansacRun {
             const bool live_only = b.bounded && confidence >= 0.f;      // (see k_ransac_finish)
             int* rec = k.record_copy ? B.rec : const_cast<int*>(B.h_rec);
             k_ransac_finish<<<1, 1024, 0, s>>>(tri(B), b.cnt, B.counts, live_only ? B.live : nullptr, live_only ? B.n_live : nullptr,
-                                               B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec);
+                                               k.far ? B.near : nullptr, B.n_near, B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec);
             TDV_CHECK_LAUNCH(ctx);
             if (k.record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(B.h_rec), B.rec, sizeof(d->rec[0]), hipMemcpyDeviceToHost, s));
         } else TDV_HIP(ctx, hipMemcpyAsync(B.h_cnt, B.counts, (size_t)b.cnt * 4, hipMemcpyDeviceToHost, s));
@@ -1396,10 +1581,12 @@ struct RansacRun {
     // ---- the device side of one batch: the four paths
     int enqueue(int q, int cnt, int it0) {
         const RansacBatch b{q, cnt, it0, k.bound && it0 != 0};
+        // RansacPointOrder, once per call: the first batch has set a best, nothing reads pq2 in between (in front of the batch's
+        // k_ransac_hypotheses, whose plan reads the class sizes)
+        if (k.order && it0 != 0 && !ordered) point_order();
         TDV_TRY(hypotheses(b));
         if (!k.bailout) { TDV_TRY(score_all(b)); return finish(b, false); }   // exact, traced, short or matrix-core calls: every test is scored
         if (k.merge) return enqueue_merged(b);
-        if (k.order && it0 != 0 && !ordered) point_order();  // once per call: the first batch has set a best, nothing reads pq2 in between
         if (b.bounded) bound(b);                             // bail-out with bound: phase 1 over the live list only
         phase1(b);
         TDV_TRY(select(b));
