@@ -62,6 +62,7 @@ ABI_SYMBOLS = [
     "tdv_cluster_default_params", "tdv_cluster_dbscan", "tdv_cluster_dbscan_dev",
     "tdv_remove_statistical_outlier", "tdv_remove_statistical_outlier_dev", "tdv_remove_radius_outlier", "tdv_remove_radius_outlier_dev",
     "tdv_iss_default_params", "tdv_iss_keypoints", "tdv_iss_keypoints_dev",
+    "tdv_ppf_default_params", "tdv_ppf_model_bytes", "tdv_ppf_model_dev", "tdv_ppf_match_dev", "tdv_ppf_match",
 ]
 
 
@@ -206,6 +207,53 @@ def _iss_result(r):
     return {k: getattr(r, k) for k, _ in IssResultC._fields_}
 
 
+TDV_PPF_MODEL_MAX = 2048
+TDV_PPF_POSES_MAX = 64
+TDV_PPF_KEYS_MAX = 1 << 24
+TDV_PPF_LDS_CELLS = 39000
+
+
+class PpfParamsC(C.Structure):
+    _fields_ = [("distance_step_relative", C.c_float), ("angle_bins", C.c_int), ("rotation_bins", C.c_int), ("ref_stride", C.c_int),
+                ("max_poses", C.c_int), ("cluster_translation_relative", C.c_float), ("cluster_rotation", C.c_float),
+                ("flip_model_normals", C.c_int)]
+
+
+class PpfModelInfoC(C.Structure):
+    _fields_ = [("diameter", C.c_float), ("distance_step", C.c_float), ("n_pairs", C.c_int), ("n_keys", C.c_int), ("nt", C.c_int)]
+
+
+class PpfPoseC(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("fitness", C.c_float), ("rmse", C.c_float), ("n_corr", C.c_int), ("votes", C.c_int),
+                ("members", C.c_int), ("ref", C.c_int), ("model_index", C.c_int), ("bin", C.c_int)]
+
+
+PPF_PEAK_DTYPE = np.dtype([("ref", np.int32), ("model_index", np.int32), ("bin", np.int32), ("votes", np.int32)])
+
+
+def ppf_params(**kw):
+    """tdv_ppf_default_params (step 0.05 of the diameter, 30 angle and 30 rotation bins, ref_stride 5, 8 poses, clusters within 0.1 of the
+    diameter and 2 pi / 30) with the given fields replaced."""
+    p = PpfParamsC()
+    lib().tdv_ppf_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(PpfParamsC._fields_):
+            raise TypeError("unknown PPF parameter %r" % k)
+        setattr(p, k, v)
+    return p
+
+
+def _ppf_info(i):
+    return {k: getattr(i, k) for k, _ in PpfModelInfoC._fields_}
+
+
+def _ppf_poses(poses, n):
+    """The poses of a PPF call: RegistrationResults, and one dict per pose with what they have no field for."""
+    res = [RegistrationResult(transformation=from_colmajor16(q.T), fitness=np.float32(q.fitness), rmse=np.float32(q.rmse), n_corr=q.n_corr)
+           for q in poses[:n]]
+    return res, [dict(votes=q.votes, members=q.members, ref=q.ref, model_index=q.model_index, bin=q.bin) for q in poses[:n]]
+
+
 _lib = None
 _lib_lock = threading.Lock()
 
@@ -247,6 +295,7 @@ def lib():
             l.tdv_plane_default_params.restype = None
             l.tdv_cluster_default_params.restype = None
             l.tdv_iss_default_params.restype = None
+            l.tdv_ppf_default_params.restype = None
             _lib = l
     return _lib
 
@@ -895,6 +944,65 @@ class Context:
                                                     _ptr(d_saliency), _ptr(d_eigenvalues), _ptr(d_support), _ptr(d_index), _ptr(d_out_xyz),
                                                     _ptr(d_out_attr)), "tdv_iss_keypoints_dev")
         return _iss_result(res)
+
+    # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
+    def ppf_model_bytes(self, nt, **params):
+        b = C.c_size_t()
+        _check(self._h, lib().tdv_ppf_model_bytes(int(nt), C.byref(ppf_params(**params)), C.byref(b)), "tdv_ppf_model_bytes")
+        return b.value
+
+    def ppf_model_dev(self, d_tgt, d_tgt_normals, nt, d_model, model_bytes, **params):
+        """tdv_ppf_model_dev: the table of the model into d_model (device, model_bytes); returns the info dict tdv_ppf_match_dev takes."""
+        info = PpfModelInfoC()
+        _check(self._h, lib().tdv_ppf_model_dev(self._h, _ptr(d_tgt), _ptr(d_tgt_normals), int(nt), C.byref(ppf_params(**params)), _ptr(d_model),
+                                                C.c_size_t(model_bytes), C.byref(info)), "tdv_ppf_model_dev")
+        return _ppf_info(info)
+
+    def ppf_model(self, tgt, tgt_normals, **params):
+        """The model table of host arrays, parsed from the buffer (rule 4's layout): dict(diameter, distance_step, n_pairs, n_keys, nt,
+        offsets int32[n_keys + 1], pair uint32[n_pairs] (i * nt + j), alpha_bits uint32[n_pairs], key uint32[n_pairs] - the key of every
+        entry, read off the offsets)."""
+        import torch
+        tgt = np.array(tgt, np.float32).reshape(-1, 3); tn = np.array(tgt_normals, np.float32).reshape(-1, 3)     # (copies: torch wants writable arrays)
+        nt = len(tgt)
+        nbytes = self.ppf_model_bytes(nt, **params)
+        dev = torch.device("cuda", self.device)
+        d_t, d_n = _upload_rows(self.device, tgt), _upload_rows(self.device, tn)
+        buf = torch.full((nbytes,), 0xA5, dtype=torch.uint8, device=dev)
+        torch.cuda.synchronize()
+        info = self.ppf_model_dev(d_t.data_ptr(), d_n.data_ptr(), nt, buf.data_ptr(), nbytes, **params)
+        w = buf.cpu().numpy().view(np.uint32)
+        nk, npairs, cap = info["n_keys"], info["n_pairs"], nt * (nt - 1) if nt >= 2 else 0
+        base = (nk + 1 + 3) // 4 * 4
+        offsets = w[:nk + 1].view(np.int32).copy()
+        return dict(info, offsets=offsets, pair=w[base:base + npairs].copy(), alpha_bits=w[base + cap:base + cap + npairs].copy(),
+                    key=np.repeat(np.arange(nk, dtype=np.uint32), np.diff(offsets)))
+
+    def ppf_match(self, src, src_normals, tgt, tgt_normals, thr, want_peaks=False, **params):
+        """tdv_ppf_match on host arrays: (poses as RegistrationResults ranked by cluster votes, one dict per pose: votes, members, ref,
+        model_index, bin); with want_peaks also the peaks (PPF_PEAK_DTYPE, one per reference point)."""
+        src = _f32(src).reshape(-1, 3); sn = _f32(src_normals).reshape(-1, 3); tgt = _f32(tgt).reshape(-1, 3); tn = _f32(tgt_normals).reshape(-1, 3)
+        p = ppf_params(**params)
+        poses = (PpfPoseC * TDV_PPF_POSES_MAX)()
+        n, nref = C.c_int(0), C.c_int(0)
+        peaks = np.zeros((len(src) + max(p.ref_stride, 1) - 1) // max(p.ref_stride, 1), PPF_PEAK_DTYPE) if want_peaks else None
+        _check(self._h, lib().tdv_ppf_match(self._h, _ptr(src), _ptr(sn), len(src), _ptr(tgt), _ptr(tn), len(tgt), C.c_float(thr), C.byref(p), poses,
+                                            C.byref(n), _ptr(peaks), C.byref(nref)), "tdv_ppf_match")
+        res, more = _ppf_poses(poses, n.value)
+        return (res, more, peaks[:nref.value]) if want_peaks else (res, more)
+
+    def ppf_match_dev(self, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, d_model, info, thr, d_peaks=None, **params):
+        """tdv_ppf_match_dev on device pointers against a table of ppf_model_dev (info: its dict, or ppf_model's - the fields of
+        tdv_ppf_model_info are taken, the rest ignored): (poses, their dicts, n_ref); d_peaks
+        (optional, device, 16 bytes per reference point) receives the peaks."""
+        ci = PpfModelInfoC(**{k: info[k] for k, _ in PpfModelInfoC._fields_})
+        poses = (PpfPoseC * TDV_PPF_POSES_MAX)()
+        n, nref = C.c_int(0), C.c_int(0)
+        _check(self._h, lib().tdv_ppf_match_dev(self._h, _ptr(d_src), _ptr(d_src_normals), int(ns), _ptr(d_tgt), _ptr(d_tgt_normals), int(nt),
+                                                _ptr(d_model), C.byref(ci), C.c_float(thr), C.byref(ppf_params(**params)), poses, C.byref(n),
+                                                _ptr(d_peaks), C.byref(nref)), "tdv_ppf_match_dev")
+        res, more = _ppf_poses(poses, n.value)
+        return res, more, nref.value
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

@@ -533,4 +533,64 @@ int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss
     return iss_run_dev(ctx, d_xyz, n, *params, d_attr, attr_width, result, d, nullptr);
 }
 
+// ---- PPF matching (ppf.hip)
+void tdv_ppf_default_params(tdv_ppf_params* p) {
+    if (!p) return;
+    p->distance_step_relative = 0.05f; p->angle_bins = 30; p->rotation_bins = 30; p->ref_stride = 5; p->max_poses = 8;
+    p->cluster_translation_relative = 0.1f; p->cluster_rotation = (float)(2.0 * 3.141592653589793 / 30.0); p->flip_model_normals = 0;
+}
+int tdv_ppf_model_bytes(int nt, const tdv_ppf_params* params, size_t* bytes) {
+    PpfPlan plan;
+    if (!bytes || !ppf_plan(params, nt, &plan)) return TDV_ERR_BAD_ARG;
+    *bytes = plan.bytes;
+    return TDV_OK;
+}
+// every argument of a match, before anything is enqueued (include/tdv_hip.h: tdv_ppf_match)
+static bool ppf_match_args_ok(const tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
+                              float thr, const tdv_ppf_params* params, const tdv_ppf_pose* out_poses, const int* n_poses, PpfPlan* plan) {
+    if (!ctx || !out_poses || !n_poses || ns < 0 || !ppf_plan(params, nt, plan)) return false;
+    if (ns > 0 && (!src || !src_normals)) return false;
+    if (nt > 0 && (!tgt || !tgt_normals)) return false;
+    return std::isfinite(thr) && thr > 0.f;
+}
+static bool ppf_model_ptr_ok(const void* d_model) { return d_model && (reinterpret_cast<uintptr_t>(d_model) & 3) == 0; }
+int tdv_ppf_model_dev(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params* params, void* d_model,
+                      size_t model_bytes, tdv_ppf_model_info* info) {
+    PpfPlan plan;
+    if (!ctx || !info || !ppf_plan(params, nt, &plan) || (nt > 0 && (!d_tgt || !d_tgt_normals)) || !ppf_model_ptr_ok(d_model) ||
+        model_bytes < plan.bytes)
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    return ppf_model_run(ctx, d_tgt, d_tgt_normals, nt, *params, plan, d_model, info);
+}
+int tdv_ppf_match_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
+                      const void* d_model, const tdv_ppf_model_info* info, float thr, const tdv_ppf_params* params, tdv_ppf_pose* out_poses,
+                      int* n_poses, tdv_ppf_peak* d_peaks, int* n_ref) {
+    PpfPlan plan;
+    if (!ppf_match_args_ok(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
+    if (!info || !ppf_model_ptr_ok(d_model) || info->nt != nt || info->n_keys != plan.n_keys || info->n_pairs < 0 ||
+        (size_t)info->n_pairs > plan.cap || !std::isfinite(info->diameter) || info->diameter < 0.f || !std::isfinite(info->distance_step) ||
+        info->distance_step < 0.f)
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    return ppf_match_run(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, d_model, *info, thr, *params, plan, out_poses, n_poses, d_peaks,
+                         nullptr, n_ref);
+}
+int tdv_ppf_match(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt, float thr,
+                  const tdv_ppf_params* params, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* peaks, int* n_ref) {
+    PpfPlan plan;
+    if (!ppf_match_args_ok(ctx, src, src_normals, ns, tgt, tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(begin(ctx));
+    float *d_src, *d_sn, *d_tgt, *d_tn;
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    TDV_TRY(upload(ctx, src_normals, (size_t)ns * 3, &d_sn));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
+    TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_tn));
+    void* d_model;
+    TDV_TRY(ws_alloc_bytes(ctx, plan.bytes, &d_model));
+    tdv_ppf_model_info info;
+    TDV_TRY(ppf_model_run(ctx, d_tgt, d_tn, nt, *params, plan, d_model, &info));
+    return ppf_match_run(ctx, d_src, d_sn, ns, d_tgt, d_tn, nt, d_model, info, thr, *params, plan, out_poses, n_poses, nullptr, peaks, n_ref);
+}
+
 }  // extern "C"

@@ -321,6 +321,17 @@ int iss_run_host(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params& pr
 int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& prm, const float* d_attr, int attr_width, tdv_iss_result* result,
                 IssOut d, const IssOut* h);
 
+// PPF matching (ppf.hip, include/tdv_hip.h: tdv_ppf_match).  PpfPlan: what the parameters alone fix (n_dist, n_keys, the table's layout for
+// nt points); ppf_plan is the parameter check of every entry point.  ppf_model_run builds the table (rule 4) into d_model and fills info;
+// ppf_match_run votes, clusters and scores (h_peaks: where a host call's peaks go).  Neither resets the workspace: the entry point did.
+struct PpfPlan { int n_dist, n_keys; size_t off_words, cap, bytes; };
+bool ppf_plan(const tdv_ppf_params* p, int nt, PpfPlan* plan);
+int ppf_model_run(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params& prm, const PpfPlan& plan,
+                  void* d_model, tdv_ppf_model_info* info);
+int ppf_match_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
+                  const void* d_model, const tdv_ppf_model_info& info, float thr, const tdv_ppf_params& prm, const PpfPlan& plan,
+                  tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks, tdv_ppf_peak* h_peaks, int* n_ref);
+
 // normals + FPFH in one go, sharing one spatial sort and one radius scan (batch path; identical results)
 // d_tie_ids / d_tie_ids_inv (optional, both or neither): neighbour lists are ordered by (d2, d_tie_ids[index]) instead of
 // (d2, index) — the results are those of the cloud permuted so that point i sits at position d_tie_ids[i]

@@ -757,6 +757,127 @@ int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss
                           int attr_width, tdv_iss_result* result, uint8_t* d_mask /* optional */, double* d_saliency /* optional */,
                           double* d_eigenvalues /* optional */, int* d_support /* optional */, int* d_index /* optional */,
                           float* d_out_xyz /* optional */, float* d_out_attr /* optional */);
+/* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
+ * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
+ * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
+ * every float that decides an integer is fixed by the rules below, so peaks, votes and clusters do not depend on the order the device works
+ * in.  "f32" means IEEE single precision, one rounding per operation, no contraction, the expression evaluated as written; atan2f is
+ * glibc's (csrc/libm_f32.hpp, held to the running libm by tests/test_libm_restatement.py).  PI = 3.14159274f, TWO_PI = 6.28318548f.
+ * dot(u, v) = (u.x * v.x + u.y * v.y) + u.z * v.z.  cross(u, v) = (u.y * v.z - u.z * v.y, u.z * v.x - u.x * v.z, u.x * v.y - u.y * v.x).
+ * norm(u) = sqrtf(dot(u, u)).  ang(u, v) = atan2f(norm(cross(u, v)), dot(u, v)), in [0, PI].
+ *  0. Usable point: a point (p, n) of either cloud is usable iff its six floats are finite and nn = dot(n, n) is > 0 and finite (a normal
+ *     whose squared length underflows to 0 counts as zero, one whose squared length overflows as non-finite).  An unusable point takes no
+ *     part in any pair, as first or as second point, and has no other effect.  With flip_model_normals every model normal is replaced by
+ *     -n (exact) before anything else: for a model whose normals came from tdv_estimate_normals with the origin inside the part - that call
+ *     turns normals towards the origin, so they point inward, while a scene's point at the camera.
+ *  1. Diameter: over the model points whose three coordinates are finite (the normal does not matter), e_a = max_a - min_a per axis in f32,
+ *     diameter = sqrtf((e_x * e_x + e_y * e_y) + e_z * e_z); 0 without such a point.  distance_step = distance_step_relative * diameter.
+ *     n_dist = (int)floorf(1.0f / distance_step_relative) + 1, n_keys = n_dist * A * A * A with A = angle_bins.
+ *  2. Pair feature of the ordered pair (a, b), a != b, both usable: d = p_b - p_a per component, len = norm(d), f1 = ang(n_a, d),
+ *     f2 = ang(n_b, d), f3 = ang(n_a, n_b) (the normals as they are, not normalised).  q0f = floorf(len / distance_step),
+ *     q_k = min((int)floorf(f_k / (PI / (float)A)), A - 1) for k = 1..3, key = ((q0 * A + q1) * A + q2) * A + q3 with q0 = (int)q0f.
+ *     The pair has no key unless len > 0, len is finite, q0f < (float)n_dist (false for the NaN and infinity of a zero step), none of f1,
+ *     f2, f3 is NaN, and the alpha of rule 3 is not NaN.
+ *  3. Alpha of the pair: the frame of a is the rotation that moves n_a onto +x.  norm_a = sqrtf(nn), u = n_a / norm_a per component;
+ *     neg = n_a.x < 0; w = neg ? -u : u (so w.x >= 0: the case n_a ~ -x, where the shortest rotation onto +x is ill-conditioned, is turned
+ *     into the case w ~ +x followed by the half turn diag(-1, 1, -1) about y); k = 1.0f + w.x, ca = w.y / k, cb = w.z / k.  The shortest
+ *     rotation of w onto +x has the rows (w.x, w.y, w.z), (-w.y, 1 - w.y * ca, -w.y * cb), (-w.z, -w.z * ca, 1 - w.z * cb); with neg, rows 0
+ *     and 2 change sign.  Applied to d in f32: t = w.y * d.y + w.z * d.z, y = (d.y - ca * t) - w.y * d.x, z = (d.z - cb * t) - w.z * d.x,
+ *     z = -z with neg; alpha = atan2f(-z, y).
+ *  4. Model table: every ordered pair (i, j) of the model that has a key, sorted by (key, i * nt + j) (the stable radix sort of
+ *     tdv_radix_sort_pairs_dev on the keys of the pairs in ascending i * nt + j: a total order), with its alpha as f32 bits.  Layout of
+ *     d_model, 32-bit words: offsets[n_keys + 1] (int: the entries of key k are [offsets[k], offsets[k + 1]); offsets[n_keys] = n_pairs),
+ *     padding to a multiple of 4 words, then two arrays of cap = nt * (nt - 1) words each: pair (i * nt + j) and alpha (f32 bits); an
+ *     entry's key is the k whose range holds it.
+ *     Entries beyond n_pairs are not written.  tdv_ppf_model_bytes gives the size; info carries diameter, distance_step, n_pairs, n_keys
+ *     and nt.  With a relative step the key space depends on the parameters only.  TDV_PPF_MODEL_MAX is 2048, not 4096: the table of a
+ *     4096-point model is 192 MiB and its sort needs 600 MiB of scratch, four times what 2048 takes, and a model for voting is sampled at
+ *     about the distance step anyway (OpenCV, PCL and Drost et al. all do): 2048 points at step 0.05 is already denser than that.
+ *  5. Voting: scene point r is a reference point iff r % ref_stride == 0; n_ref = ceil(ns / ref_stride), reference point q is scene point
+ *     q * ref_stride.  A usable reference point s_r owns nt * rotation_bins 32-bit counters, all 0 at first.  For every usable scene point
+ *     s_i, i != r (by index), whose pair (s_r, s_i) has a key (rule 2 with the MODEL's distance_step and n_dist): for every table entry
+ *     (i_m * nt + j_m, alpha_m) of that key, counter [i_m][bin(alpha_m - alpha_s)] += 1.  x = alpha_m - alpha_s in f32; x = x + TWO_PI if
+ *     x < -PI, else x = x - TWO_PI if x >= PI; bin = min(max((int)floorf((x + PI) / (TWO_PI / (float)rotation_bins)), 0), rotation_bins - 1).
+ *     One workgroup per reference point (in turn, where there are more reference points than workgroups); the counters sit in LDS when
+ *     nt * rotation_bins <= TDV_PPF_LDS_CELLS (39,000: 152.3 of the 160 KiB; the tile's staging takes the rest), else in a slab of the workspace per workgroup; the same
+ *     integers either way.  The slabs of a call take at most 128 MiB of the workspace (fewer workgroups where a slab is large; at least one).
+ *     A workgroup takes the scene points in tiles; each lane forms one pair's key and bucket, then the lanes share the
+ *     tile's table entries evenly, whatever bucket they come from.
+ *  6. Peak of reference point q: the counter with the most votes, ties to the lowest i_m, then the lowest bin (one maximum over
+ *     (votes << 32) | (0xFFFFFFFF - (i_m * rotation_bins + bin))).  tdv_ppf_peak = (ref = q * ref_stride, model_index, bin, votes);
+ *     votes = 0 (with model_index = bin = 0): none - an unusable reference point, or no vote.
+ *  7. Poses, clusters, score: on the host in f64 (IEEE double, the expression as written), from the f32 inputs converted exactly.
+ *     Frame of a point (p, n), as rule 3 in f64: norm = sqrt((n.x * n.x + n.y * n.y) + n.z * n.z), u = n / norm, neg = n.x < 0, w, k, ca, cb
+ *     and the rows as there: R.  Pose of a peak (scene point s, model point m): alpha_c = (float)(-pi + (bin + 0.5) * ((2 pi) /
+ *     rotation_bins)), the bin's centre rounded once to f32 (pi = 3.141592653589793); c = cos(alpha_c), sn = sin(alpha_c); M = Rx(-alpha_c)
+ *     R_s: M[0] = R_s[0], M[1] = c * R_s[1] + sn * R_s[2], M[2] = c * R_s[2] - sn * R_s[1]; Rot[i][j] = (R_m[0][i] * M[0][j] + R_m[1][i] *
+ *     M[1][j]) + R_m[2][i] * M[2][j]; t[i] = p_m[i] - ((Rot[i][0] * p_s[0] + Rot[i][1] * p_s[1]) + Rot[i][2] * p_s[2]): T = T_m^-1 Rx(-alpha)
+ *     T_s.  Clustering: the peaks with votes > 0 by votes descending, then ref ascending; each joins the first cluster (in founding order)
+ *     whose founder's pose is within both thresholds, else founds one: sqrt((dx * dx + dy * dy) + dz * dz) <= cluster_translation_relative *
+ *     diameter for the difference of the two t, and ((sum over i, then j, of RotA[i][j] * RotB[i][j], added in that order from 0.0) - 1) / 2
+ *     >= cos(cluster_rotation) (the angle between the rotations is at most cluster_rotation).  A cluster's votes are the sum of its
+ *     members' votes, its pose (T, ref, model_index, bin) is its founder's, rounded once to f32 and stored column-major.  Returned: the
+ *     max_poses clusters with the most votes, the earlier-founded first among equals.  Score of a returned pose: tdv_icp_correspondences
+ *     at (T, thr): n_corr is its count, fitness = (float)n_corr / (float)ns, rmse = (float)sqrt(S / n_corr) with S the sum of (double)d2[i]
+ *     over the accepted i in ascending order (0 when n_corr = 0): the numbers compare with every ICP result.  The ctx's ICP search switch
+ *     applies to that pass as it does to tdv_icp_correspondences, and tdv_ctx_last_icp_search afterwards reports that pass.
+ * tdv_ppf_model_dev builds the table once into a caller-owned device buffer (the pattern of tdv_prepare_model_dev: no handle, nothing
+ * kept in the ctx); tdv_ppf_match_dev votes against it (device pointers; out_poses, n_poses and n_ref are host memory; d_peaks, optional,
+ * receives n_ref peaks); tdv_ppf_match takes host arrays, builds the table itself in the workspace and returns the peaks (optional) in
+ * host memory.  Both read back twice: the peaks, then each returned pose's score.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params, out_poses or n_poses (match), info (model_dev, match_dev),
+ * bytes (model_bytes) or d_model; ns < 0; nt < 0; nt > TDV_PPF_MODEL_MAX; a NULL cloud or normal array with a count > 0; thr NaN, infinite or
+ * not > 0; distance_step_relative NaN, not > 0 or > 1; angle_bins outside [1, 64]; rotation_bins outside [1, 256]; n_keys >
+ * TDV_PPF_KEYS_MAX (2^24); ref_stride < 1; max_poses outside [1, TDV_PPF_POSES_MAX]; cluster_translation_relative NaN, infinite or < 0;
+ * cluster_rotation NaN, < 0 or > PI; flip_model_normals neither 0 nor 1; d_model not 4-byte aligned; model_bytes below
+ * tdv_ppf_model_bytes; an info that does not fit the call (info->nt != nt, n_keys other than the parameters give, n_pairs outside
+ * [0, nt * (nt - 1)], a diameter or distance_step that is NaN, infinite or < 0).  Accepted and empty (status OK, *n_poses = 0, *n_ref = 0,
+ * no peak written): ns == 0, nt < 2, or a table without pairs.  The call obeys the ctx's state rule (README, "What a context keeps
+ * between calls").  Not provided: PPF inside tdv_register_batch_dev (an ABI change), a batched (offsets) form, the C++ operator mirror,
+ * averaging the poses of a cluster, an absolute distance step, voting into neighbouring bins. */
+#define TDV_PPF_MODEL_MAX 2048
+#define TDV_PPF_POSES_MAX 64
+#define TDV_PPF_KEYS_MAX (1 << 24)
+#define TDV_PPF_LDS_CELLS 39000
+typedef struct tdv_ppf_params {
+    float distance_step_relative;        /* 0.05: the distance step as a share of the model's diameter */
+    int   angle_bins;                    /* 30: bins of the three feature angles over [0, pi] */
+    int   rotation_bins;                 /* 30: bins of alpha over [-pi, pi) */
+    int   ref_stride;                    /* 5 */
+    int   max_poses;                     /* 8 */
+    float cluster_translation_relative;  /* 0.1: of the diameter */
+    float cluster_rotation;              /* 2 pi / 30, radians */
+    int   flip_model_normals;            /* 0 */
+} tdv_ppf_params;
+typedef struct tdv_ppf_model_info {
+    float diameter;
+    float distance_step;
+    int   n_pairs;
+    int   n_keys;
+    int   nt;
+} tdv_ppf_model_info;
+typedef struct tdv_ppf_pose {
+    float T[16];            /* column-major */
+    float fitness, rmse;
+    int   n_corr;
+    int   votes;            /* of the cluster */
+    int   members;
+    int   ref, model_index, bin;   /* the founder's peak */
+} tdv_ppf_pose;
+typedef struct tdv_ppf_peak {
+    int ref, model_index, bin, votes;
+} tdv_ppf_peak;
+void tdv_ppf_default_params(tdv_ppf_params* p);
+int tdv_ppf_model_bytes(int nt, const tdv_ppf_params* params, size_t* bytes);
+int tdv_ppf_model_dev(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params* params, void* d_model,
+                      size_t model_bytes, tdv_ppf_model_info* info);
+int tdv_ppf_match_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals,
+                      int nt, const void* d_model, const tdv_ppf_model_info* info, float thr, const tdv_ppf_params* params,
+                      tdv_ppf_pose* out_poses /* host, [max_poses] */, int* n_poses, tdv_ppf_peak* d_peaks /* optional, device */,
+                      int* n_ref /* host, optional */);
+int tdv_ppf_match(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
+                  float thr, const tdv_ppf_params* params, tdv_ppf_pose* out_poses /* [max_poses] */, int* n_poses,
+                  tdv_ppf_peak* peaks /* optional, host, [ceil(ns / ref_stride)] */, int* n_ref /* optional */);
 int tdv_ransac_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt,
                    const float* d_fs, const float* d_ft, const int* d_corr,
                    float voxel_size, int max_iterations, float confidence, uint32_t seed,
