@@ -311,6 +311,7 @@ int tdv_ctx_set_ransac_score(tdv_ctx* ctx, int mode) {
 double tdv_ctx_last_ransac_rescore(tdv_ctx* ctx) { return ctx ? ctx->last_ransac_rescore : -1.0; }
 
 double tdv_ctx_last_ransac_scored(tdv_ctx* ctx) { return ctx ? ctx->last_ransac_scored : 1.0; }
+void tdv_ctx_last_ransac_bound(tdv_ctx* ctx, long long out[4]) { if (out) for (int e = 0; e < 4; ++e) out[e] = ctx ? ctx->last_ransac_bound[e] : 0; }
 
 int tdv_ctx_last_icp_search(tdv_ctx* ctx) { return ctx ? ctx->last_icp_search : 0; }
 int tdv_ctx_last_feature_match_path(tdv_ctx* ctx) { return ctx ? ctx->last_fm_path : 0; }

@@ -115,7 +115,8 @@ __device__ __forceinline__ float ransac_band_reach(const float* o, float P) {
 // Rows 12, 13 of hyp: the band of the fast scoring pass for this hypothesis (RansacBand below): mid and half-width of
 // the d2 interval inside which the FMA arithmetic and the reference's arithmetic might disagree on `d2 < tau`.
 __device__ __forceinline__ void ransac_hypothesis_lane(const float* __restrict__ pq, const int4 tr, const bool valid, const int h, const int h_pad,
-                                                       float* __restrict__ hyp, const unsigned* __restrict__ pmax, const float sqrt_tau, const float band_u) {
+                                                       float* __restrict__ hyp, const unsigned* __restrict__ pmax, const float sqrt_tau, const float band_u,
+                                                       float* o_out = nullptr) {
     float o[12];
     if (valid) {
         const int id[3] = {tr.x, tr.y, tr.z};
@@ -173,6 +174,9 @@ __device__ __forceinline__ void ransac_hypothesis_lane(const float* __restrict__
     }
     hyp[(size_t)12 * h_pad + h] = mid;
     hyp[(size_t)13 * h_pad + h] = half;
+    if (o_out)
+#pragma unroll
+        for (int k = 0; k < 12; ++k) o_out[k] = o[k];
 }
 // RansacPlan's set-up of a batch (see k_ransac_score_fast and k_ransac_select below), done by one thread of k_ransac_hypotheses:
 // stream order puts the previous batch's final state[0] in front of that kernel, and the bound and scoring kernels that read the
@@ -181,9 +185,13 @@ struct RansacFar;
 struct PlanJob { int* state; int* plan; int ns, n_pchunks, drop_permille; int* n_live; int* units; int n_units;   // units: the batch's ticket words (k_ransac_score_fast, job B)
                  const RansacFar* far; int a_permille; };                                                  // RansacFarBound: the classes, and the near lists' share of I in phase 1
 __device__ __forceinline__ void ransac_plan(const PlanJob& j);
+// What a bounded batch's hypotheses are judged by before the leaf walk (ransac_prejudge, beside k_ransac_bound): flags == nullptr in a batch without bound
+struct PreJob { int* flags; int* ubf; const RansacFar* far; const unsigned* enc; const float* best12; float live_radius; int u_cut_permille; };
+__device__ __forceinline__ void ransac_prejudge(const PreJob& j, const float* o, bool valid, int h, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u,
+                                                const int* __restrict__ state, int ns);
 __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, int count, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
-                                    float band_u /* E = band_u (A + s): kBandUnit or kBandUnitMatrix */, const PlanJob plan) {
+                                    float band_u /* E = band_u (A + s): kBandUnit or kBandUnitMatrix */, const PlanJob plan, const PreJob pre) {
     int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h == 0 && plan.plan) ransac_plan(plan);
     if (h < plan.n_units) plan.units[h] = 0;     // job B of this batch's two scoring dispatches draws its units from them (n_units <= h_pad)
@@ -192,7 +200,9 @@ __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView 
     bool valid = false;
     int4 tr = make_int4(0, 0, 0, 0);
     if (h < count) { tr = triples.load(h); valid = tr.w != 0; }
-    ransac_hypothesis_lane(pq, tr, valid, h, h_pad, hyp, pmax, sqrt_tau, band_u);
+    float o[12];
+    ransac_hypothesis_lane(pq, tr, valid, h, h_pad, hyp, pmax, sqrt_tau, band_u, o);
+    if (pre.flags) ransac_prejudge(pre, o, valid, h, pmax, sqrt_tau, band_u, plan.state, plan.ns);      // (uniform)
 }
 
 __device__ __forceinline__ unsigned long long shfl_u64_down(unsigned long long v, int o) {
@@ -553,7 +563,7 @@ __device__ __forceinline__ int ransac_near_end(const RansacFar& f, int ns, int n
 // (One thread of k_ransac_hypotheses makes the plan: a launch of its own - one thread behind a stream barrier - cost as much as k_ransac_best.)
 __device__ __forceinline__ void ransac_plan(const PlanJob& j) {
     const int best = j.state[0], ns = j.ns, n_pchunks = j.n_pchunks;
-    if (j.n_live) { j.n_live[0] = 0; j.n_live[2] = 0; j.n_live[4] = 0; }      // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided, near)
+    if (j.n_live) { j.n_live[0] = 0; j.n_live[2] = 0; j.n_live[4] = 0; j.n_live[6] = 0; }      // (RansacLeafBound: k_ransac_bound appends to them next: live, undecided, near; its close count)
     int c_split = n_pchunks;
     const int rest = best - max((int)((long long)best * j.drop_permille / 1000), 1);   // points left to phase 2: a hypothesis with under that share of the best count in the prefix is dropped
     if (rest >= ns / 8)                                      // (below an eighth of the points a second phase costs more than it saves)
@@ -794,14 +804,16 @@ void k_order_scatter(const float* __restrict__ pq, int ns, const unsigned long l
 // batch to batch on the device; once `stopped` is set the batches still in flight change nothing (the host discards them too).
 // The winning hypothesis' 12 floats go to best12, and the host gets ONE record per batch - { best local index or -1, its count,
 // local stop index or -1, bad correspondence flag } - where it used to download every count and walk them.  The same launch
-// raises state[0] to the batch's largest full count, as k_ransac_best did (state == nullptr: a batch without bail-out).
+// raises state[0] to the batch's largest full count, as k_ransac_best did (state == nullptr: a batch without bail-out), and
+// adds a bounded batch's list lengths to the call's counters (lists != nullptr; a batch behind the loop's stop adds nothing).
 // live != nullptr (a bounded batch, confidence >= 0): only the live lists - far and near - are read.  A dead hypothesis has count 0: no new best
 // (strict > on a best fitness >= 0), no exit (0 > confidence is false), nothing to raise.
 // One workgroup; the first batch and the live lists are a few thousand entries (a whole batch is walked only with the bound off).
 __global__ __launch_bounds__(1024)
 void k_ransac_finish(const TriView triples, int count, const int* __restrict__ counts, const int* __restrict__ live, const int* __restrict__ n_live,
                      const int* __restrict__ near, const int* __restrict__ n_near, const float* __restrict__ hyp, int h_pad, int ns, float confidence, int it0,
-                     int* __restrict__ state, int* __restrict__ sel, float* __restrict__ best12, const int* __restrict__ bad, int* __restrict__ rec) {
+                     int* __restrict__ state, int* __restrict__ sel, float* __restrict__ best12, const int* __restrict__ bad, int* __restrict__ rec,
+                     const int* __restrict__ lists, long long* __restrict__ bound) {
     const int n1 = live ? *n_live : count, n = n1 + (live && near ? *n_near : 0);      // (the near list behind the far one)
     const float fn = static_cast<float>((size_t)ns);
     __shared__ int s_stop, s_max;
@@ -844,6 +856,8 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     if (state && s_max > 0) atomicMax(state, s_max);
     int best_local = -1, best_count = 0, stop_local = -1;
     if (!sel[3]) {
+        // RansacBoundLists' counters (lists: the bounded batch's words of RansacLive): hypotheses bounded, close, on the fine list, live
+        if (lists) { bound[0] += count; bound[1] += lists[6]; bound[2] += lists[2]; bound[3] += lists[0] + lists[4]; }
         if (best != 0ull) {
             const int h = INT_MAX - (int)(unsigned)(best & 0xffffffffull);
             const float fit = __uint_as_float((unsigned)(best >> 32));
@@ -918,12 +932,23 @@ void k_leaf_bounds(const float* __restrict__ pq, int ns, unsigned* __restrict__ 
         else if (v != 0u) atomicMax(&enc[threadIdx.x], v);
     }
 }
-// 6-D Morton key of every pair (bit 6 b + c = bit b of coordinate c's cell); a non-finite coordinate takes cell 0
+// 6-D Morton key of every pair (bit 6 b + c = bit b of coordinate c's cell); a non-finite coordinate takes cell 0.
+// Class-major leaves (RansacBoundLists): bit RL_CLASS_BIT, above every Morton bit, is set for a pair that is no outlier of the
+// ordering pose (`outlier`: k_order_flags' ballot words, indexed by the original pair), so the sorted order is the pose's outliers
+// first and its inliers behind them, as k_order_scatter orders pq2, each class along its own Morton curve.  The inliers are true
+// pairs on a 3-D sheet of the 6-D space, the outliers mostly random pairs: leaves cut class by class have tighter boxes than leaves
+// that mix the two.  In the product library `outlier` is nullptr: the classes are off, and only the study build's
+// TDV_RANSAC_LEAF_CLASSES=1 passes the words (see ransac_knobs).  nullptr, TDV_RANSAC_ORDER=0 and a call without a best (every
+// word all ones) give class 0 everywhere: the plain Morton order.  Exactness needs no new argument: RansacLeafBound's proof is per leaf - a leaf's boxes hold its pairs,
+// whatever the grouping, and a leaf that straddles the class boundary is merely loose - and a coarse leaf is still the union of 4
+// consecutive fine leaves of the same sorted order, so "coarse-dead implies fine-dead" holds with its 5 E margin unchanged.
+constexpr int RL_CLASS_BIT = 6 * RL_BITS;
 __global__ __launch_bounds__(256)
-void k_leaf_keys(const float* __restrict__ pq, int ns, const unsigned* __restrict__ enc, unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
+void k_leaf_keys(const float* __restrict__ pq, int ns, const unsigned* __restrict__ enc, const unsigned long long* __restrict__ outlier,
+                 unsigned long long* __restrict__ keys, unsigned* __restrict__ vals) {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= ns) return;
-    unsigned key = 0u;
+    unsigned key = (outlier && !((outlier[i >> 6] >> (i & 63)) & 1ull)) ? 1u << RL_CLASS_BIT : 0u;
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
         const float lo = rl_dec(enc[c]), hi = rl_dec(enc[6 + c]);
@@ -1064,18 +1089,24 @@ __device__ __forceinline__ int rb_walk(const float* r, const float* __restrict__
 }
 // The hypothesis' band test and its bound threshold (k_ransac_hypotheses' E, from the same f32 operations)
 struct RbHyp { float r[12]; float tb, E; bool bounded; };
+__device__ __forceinline__ float rb_band(const float* r, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u) {
+    return (band_u * ransac_band_reach(r, __uint_as_float(*pmax)) + band_u * sqrt_tau) * 1.0001f;
+}
+__device__ __forceinline__ void rb_make(RbHyp& o, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, float margin);
 __device__ __forceinline__ RbHyp rb_load(const float* __restrict__ hyp, int h_pad, int h, bool valid, const unsigned* __restrict__ pmax,
                                          float sqrt_tau, float band_u, float margin) {
     RbHyp o;
 #pragma unroll
     for (int e = 0; e < 12; ++e) o.r[e] = valid ? hyp[(size_t)e * h_pad + h] : 0.f;
-    const float A = ransac_band_reach(o.r, __uint_as_float(*pmax));
-    const float E = (band_u * A + band_u * sqrt_tau) * 1.0001f;
+    rb_make(o, pmax, sqrt_tau, band_u, margin);
+    return o;
+}
+__device__ __forceinline__ void rb_make(RbHyp& o, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, float margin) {      // o.r is set
+    const float E = rb_band(o.r, pmax, sqrt_tau, band_u);
     o.bounded = E < 0.25f * sqrt_tau;                             // false for NaN (non-finite data or hypothesis)
     o.E = E;
     const float sb = sqrt_tau + margin * E;
     o.tb = sb * sb * (1.0f + 1e-6f);
-    return o;
 }
 // ------------------------------------------------------------------ RansacFarBound
 // Almost every hypothesis the leaf bound leaves alive is a near-perfect pose, and almost none of the ordering pose B's far outliers
@@ -1103,20 +1134,15 @@ __device__ __forceinline__ RbHyp rb_load(const float* __restrict__ hyp, int h_pa
 //   RansacLeafBound's 3 E for two poses; tests/test_ransac_far_bound_margin.py checks the chain in emulated f32 on the shell.
 // A box with no finite source decodes to NaN corners, a non-finite pose gives a NaN Delta: T is then no finite number and the
 // hypothesis is far.
-struct FarJob { const RansacFar* far; const unsigned* enc; int* near; int* n_near; int* ubf; int u_cut_permille; };    // far == nullptr: every live hypothesis is far
-// Whether the live hypothesis o goes on the near list; ub_f = UB_F(h) then.  best = the best count of the earlier batches.
-__device__ __forceinline__ bool rf_near(const RbHyp& o, const FarJob& f, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, int best, int& ub_f) {
-    if (!f.far || !o.bounded || f.far->c_far < 1) return false;              // (no band; skipping F saves less than a chunk)
+// Delta^2 between the poses r and ref (column-major R, then t): the largest squared displacement |(R - R_ref) c + (t - t_ref)|^2 over
+// the 8 corners c of the finite sources' bounding box (enc).  A NaN stays.
+__device__ __forceinline__ float rf_corner_max2(const float* r, const float* ref, const unsigned* __restrict__ enc) {
     float d[12];
 #pragma unroll
-    for (int e = 0; e < 12; ++e) d[e] = f.far->ord12[e];
-    const float E_B = (band_u * ransac_band_reach(d, __uint_as_float(*pmax)) + band_u * sqrt_tau) * 1.0001f;
-    if (!(E_B < 0.25f * sqrt_tau)) return false;                             // the ordering pose's band is off
-#pragma unroll
-    for (int e = 0; e < 12; ++e) d[e] = o.r[e] - d[e];
+    for (int e = 0; e < 12; ++e) d[e] = r[e] - ref[e];
     float lo[3], hi[3], m2 = 0.f;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) { lo[c] = rl_dec(f.enc[c]); hi[c] = rl_dec(f.enc[6 + c]); }
+    for (int c = 0; c < 3; ++c) { lo[c] = rl_dec(enc[c]); hi[c] = rl_dec(enc[6 + c]); }
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
         const float x = (k & 1) ? hi[0] : lo[0], y = (k & 2) ? hi[1] : lo[1], z = (k & 4) ? hi[2] : lo[2];
@@ -1125,20 +1151,82 @@ __device__ __forceinline__ bool rf_near(const RbHyp& o, const FarJob& f, const u
         for (int c = 0; c < 3; ++c) { const float v = fmaf(d[c], x, fmaf(d[3 + c], y, fmaf(d[6 + c], z, d[9 + c]))); n2 = fmaf(v, v, n2); }
         m2 = (n2 > m2 || n2 != n2) ? n2 : m2;                                // (a NaN stays)
     }
+    return m2;
+}
+// Whether the hypothesis o, if live, goes on the near list; ub_f = UB_F(h) then.  best = the best count of the earlier batches.
+// f.far == nullptr: every live hypothesis is far.
+__device__ __forceinline__ bool rf_near(const RbHyp& o, const PreJob& f, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, int best, int& ub_f) {
+    if (!f.far || !o.bounded || f.far->c_far < 1) return false;              // (no band; skipping F saves less than a chunk)
+    float b[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) b[e] = f.far->ord12[e];
+    const float E_B = rb_band(b, pmax, sqrt_tau, band_u);
+    if (!(E_B < 0.25f * sqrt_tau)) return false;                             // the ordering pose's band is off
+    const float m2 = rf_corner_max2(o.r, b, f.enc);
     const float sb = (sqrt_tau + sqrtf(m2) + 3.f * (o.E + E_B)) * (1.0f + 4e-6f), T = sb * sb * (1.0f + 1e-6f);
     if (!(T <= FLT_MAX)) return false;
     ub_f = (int)f.far->cum[rf_bin(T)];
     return ub_f <= (int)((long long)best * f.u_cut_permille / 1000);
 }
-// A live hypothesis onto its list
-__device__ __forceinline__ void rf_append(bool is_live, const RbHyp& o, const FarJob& f, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, int best,
-                                          int lane, int h, int* __restrict__ live, int* __restrict__ n_live) {
+// ------------------------------------------------------------------ RansacBoundLists
+// More than half of the hypotheses the coarse level leaves undecided end up live anyway: they are near-copies of the running best B
+// (d->best12), a few thresholds from it everywhere on the cloud, and the fine level walks every leaf for each of them only to say
+// so.  Putting a hypothesis on a live list needs no proof - only a dead verdict does: a live hypothesis is scored, and
+// k_ransac_select_live drops it by its count like any other.  So a hypothesis that is CLOSE to B goes live without a verdict of the
+// walk: live = close OR the walk's verdict, in the one-level walk and in the coarse level alike; a close hypothesis is never put on
+// the undecided list, whatever its coarse sum.  Close: valid, its band on, the gate open, B's own band on (E_B < s / 4, as in
+// rf_near), and Delta_h = rf_corner_max2 against B finite with sqrtf(Delta_h^2) <= radius * s (radius in thresholds: 20, measured
+// above 13 and 9 in every run - a wrongly live hypothesis costs about three fine walks, profiles/r14/ransac_bound_lists.md).  The rule reads
+// the running best, which every batch's k_ransac_finish writes in stream order: it depends neither on the point order nor on the
+// far bound nor on the number of levels, and two calls give the same lists.
+// Both judgements - close to B, near under the ordering pose - need the pose and a few words that are fixed once the batch is
+// enqueued (best12, state[0], the ordering pose, the box, the count table), not the walk: k_ransac_hypotheses makes them for every
+// hypothesis where it has the pose in registers (ransac_prejudge: flags[h], ubf[h]), and the bound kernels' tails read one word.
+// (Made in wave 0's tail behind the walk they cost the coarse level 28 us per batch: four dependent trips to memory during which
+// the workgroup's other 15 waves are gone and its slots cannot be given away.)
+enum { RB_CLOSE = 1, RB_NEAR = 2 };
+__device__ __forceinline__ bool rb_gate(int best, int ns) { return best >= ns / 32; }      // the walk's gate, see k_ransac_bound
+__device__ __forceinline__ bool rb_close(const RbHyp& o, const PreJob& j, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u) {
+    if (!(j.live_radius > 0.f)) return false;
+    float b[12];
+#pragma unroll
+    for (int e = 0; e < 12; ++e) b[e] = j.best12[e];
+    if (!(rb_band(b, pmax, sqrt_tau, band_u) < 0.25f * sqrt_tau)) return false;      // the best pose's band is off
+    const float m2 = rf_corner_max2(o.r, b, j.enc);
+    return m2 <= FLT_MAX && sqrtf(m2) <= j.live_radius * sqrt_tau;                   // (false for NaN)
+}
+__device__ __forceinline__ void ransac_prejudge(const PreJob& j, const float* r, bool valid, int h, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u,
+                                                const int* __restrict__ state, int ns) {
+    RbHyp o;
+#pragma unroll
+    for (int e = 0; e < 12; ++e) o.r[e] = valid ? r[e] : 0.f;
+    rb_make(o, pmax, sqrt_tau, band_u, 3.f);
+    const int best = state[0];
     int ub_f = 0;
-    const bool near = is_live && rf_near(o, f, pmax, sqrt_tau, band_u, best, ub_f);
-    rb_append(is_live && !near, lane, h, live, n_live);
-    if (!f.far) return;
-    rb_append(near, lane, h, f.near, f.n_near);
-    if (near) f.ubf[h] = ub_f;
+    const bool close = valid && o.bounded && rb_gate(best, ns) && rb_close(o, j, pmax, sqrt_tau, band_u);
+    const bool near = valid && rf_near(o, j, pmax, sqrt_tau, band_u, best, ub_f);
+    j.flags[h] = (close ? RB_CLOSE : 0) | (near ? RB_NEAR : 0);
+    if (near) j.ubf[h] = ub_f;
+}
+// A tail's appends - the far list, the near list, the undecided list - reserved by ONE vector atomic (lane k for list k: one trip to
+// memory, not three); returns the lane's slot on the undecided list.  near / und are false where their list is nullptr.
+struct ListJob { const int* flags; int* near; int* n_near; int* n_close; };      // near == nullptr: every live hypothesis is far
+__device__ __forceinline__ int rb_append3(bool far, bool near, bool und, int lane, int h, int* __restrict__ live, int* __restrict__ n_live,
+                                          int* __restrict__ nearl, int* __restrict__ n_near, int* __restrict__ undl, int* __restrict__ n_und) {
+    const unsigned long long m0 = __ballot(far), m1 = __ballot(near), m2 = __ballot(und);
+    if (!(m0 | m1 | m2)) return 0;
+    int at = 0;
+    if (lane < 3) {
+        const unsigned long long m = lane == 0 ? m0 : lane == 1 ? m1 : m2;
+        int* const n = lane == 0 ? n_live : lane == 1 ? n_near : n_und;
+        if (m) at = atomicAdd(n, __popcll(m));
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    const int a0 = __shfl(at, 0, 64) + __popcll(m0 & below), a1 = __shfl(at, 1, 64) + __popcll(m1 & below), a2 = __shfl(at, 2, 64) + __popcll(m2 & below);
+    if (far) live[a0] = h;
+    if (near) nearl[a1] = h;
+    if (und) undl[a2] = h;
+    return a2;
 }
 // RB_ONE / RB_COARSE: a workgroup per 64 hypotheses of the batch.  RB_COARSE also zeroes the fine level's per-slot sums (acc) of
 // the hypotheses it leaves undecided and the ticket of its slot block.
@@ -1147,7 +1235,7 @@ __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView triples, int count, const float* __restrict__ leaves, int n_lpairs,
                     const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
                     int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
-                    int* __restrict__ acc, int* __restrict__ ticket, const FarJob fj) {
+                    int* __restrict__ acc, int* __restrict__ ticket, const ListJob lj) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.x * 64 + lane;
     __shared__ int s_ub[64];
@@ -1159,7 +1247,9 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView trip
     // Gate: with the best under a 32nd of the points nothing is pruned (true share 0.02: best 0.017 N), and the walk - whose RB_SPLIT
     // partial sums each have to pass the best before a wave stops - cost 8.5 % there: every hypothesis is live without it.  At a true
     // share of 0.1 (best 0.09 N) it still prunes 14 % of the tests and gains a point.
-    const bool walk = best >= ns / 32;
+    const bool walk = rb_gate(best, ns);
+    int fl = 0;                                                   // ransac_prejudge's word, asked for in front of the walk: the tail does not wait for it
+    if (wave == 0 && valid) fl = lj.flags[h];
     const int per = (n_lpairs + RB_SPLIT - 1) / RB_SPLIT, k0 = __builtin_amdgcn_readfirstlane(wave) * per, k1 = min(n_lpairs, k0 + per);   // (uniform: scalar loads)
     const int ub = rb_walk(o.r, leaves, k0, k1, o.tb, best, !valid || !o.bounded || !walk);
     __syncthreads();                                 // (s_ub zeroed)
@@ -1168,13 +1258,18 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView trip
     if (wave != 0) return;
     const int total = s_ub[lane];
     const bool gated = valid && (!o.bounded || !walk);            // live without a walk
-    const bool undecided = MODE == RB_COARSE && valid && !gated && total > best;
-    const bool is_live = gated || (MODE == RB_ONE && valid && total > best);
-    rf_append(is_live, o, fj, pmax, sqrt_tau, band_u, best, lane, h, live, n_live);
-    if (MODE == RB_COARSE) { const int slot = rb_append(undecided, lane, h, und, n_und); if (undecided) acc[slot] = 0; }
+    const bool close = (fl & RB_CLOSE) != 0;                      // live whatever the walk said (RansacBoundLists)
+    const bool undecided = MODE == RB_COARSE && valid && !gated && !close && total > best;
+    const bool is_live = gated || close || (MODE == RB_ONE && valid && total > best);
+    const bool near = is_live && lj.near && (fl & RB_NEAR);
+    const unsigned long long mc = __ballot(close);
+    if (mc && lane == 0) atomicAdd(lj.n_close, __popcll(mc));
+    const int slot = rb_append3(is_live && !near, near, undecided, lane, h, live, n_live, lj.near, lj.n_near, und, n_und);
+    if (MODE == RB_COARSE && undecided) acc[slot] = 0;
 }
-// k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a fifth of the batch, too few workgroups to fill the chip with
-// one workgroup per 64 of them, so the leaf pairs are cut into RB_FINE_Y ranges as well (blockIdx.y); a workgroup adds its 64 partial
+// k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a tenth of the batch (a fifth before RansacBoundLists), too few
+// workgroups to fill the chip with one workgroup per 64 of them, so the leaf pairs are cut into gridDim.y ranges as well (blockIdx.y:
+// RB_FINE_Y of them unless the study build's TDV_RANSAC_FINE_Y says otherwise); a workgroup adds its 64 partial
 // sums to acc[slot], and the last workgroup of a slot block (ticket) decides: live on a total > best, dead
 // otherwise.  A partial sum that stopped early exceeds best alone, so a stop anywhere makes the total exceed it too; without one
 // the total is the full fine sum - the one-level walk's verdict.  The grid covers the whole batch (the host does not know
@@ -1184,10 +1279,10 @@ __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* __restrict__ leaves, int n_lpairs,
                          const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state,
                          int* __restrict__ live, int* __restrict__ n_live, const int* __restrict__ und, const int* __restrict__ n_und,
-                         int* __restrict__ acc, int* __restrict__ ticket, const FarJob fj) {
+                         int* __restrict__ acc, int* __restrict__ ticket, const ListJob lj) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int n = *n_und, best = state[0];
-    const int per_y = (n_lpairs + RB_FINE_Y - 1) / RB_FINE_Y, y0 = blockIdx.y * per_y, y1 = min(n_lpairs, y0 + per_y);
+    const int per_y = (n_lpairs + (int)gridDim.y - 1) / (int)gridDim.y, y0 = blockIdx.y * per_y, y1 = min(n_lpairs, y0 + per_y);
     const int per = (y1 - y0 + RB_SPLIT - 1) / RB_SPLIT;
     const int k0 = min(y1, y0 + __builtin_amdgcn_readfirstlane(wave) * per), k1 = min(y1, k0 + per);
     __shared__ int s_ub[64];
@@ -1210,7 +1305,8 @@ void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* 
     if (__shfl(arrived, 0, 64) != (int)gridDim.y - 1) return;    // not the last workgroup of this slot block
     const int total = h >= 0 ? atomicAdd(&acc[slot], 0) : 0;
     const bool is_live = h >= 0 && total > best;
-    rf_append(is_live, o, fj, pmax, sqrt_tau, band_u, best, lane, h, live, n_live);
+    const bool near = is_live && lj.near && (lj.flags[h] & RB_NEAR);
+    rb_append3(is_live && !near, near, false, lane, h, live, n_live, lj.near, lj.n_near, nullptr, nullptr);
 }
 
 #ifdef TDV_STUDY
@@ -1291,6 +1387,7 @@ struct RansacBlock {
     int bad;                                 // a correspondence index outside [0, nt) was met
     unsigned pmax;                           // the largest |source coordinate| (bits of a non-negative float)
     unsigned long long rescored, scored;     // the fast pass' statistics: point pairs scored twice, (wave, chunk) pairs scored
+    long long bound[4];                      // RansacBoundLists, over the call's bounded batches: hypotheses bounded, close, put on the fine list, live (far + near)
     int state[2];                            // [0] the best count known so far (RansacPlan)
     int plan[2][8];                          // per batch buffer: phase-1 chunks, survivors, largest prefix count; near lists: phase 1's end, survivors (three words unused)
     float best12[12];                        // the winning hypothesis
@@ -1303,13 +1400,15 @@ constexpr size_t kRansacReadBack = offsetof(RansacBlock, sel);
 static_assert(std::is_trivially_copyable<RansacBlock>::value, "memset, copied back");
 static_assert(offsetof(RansacBlock, rescored) % 8 == 0 && offsetof(RansacBlock, scored) == offsetof(RansacBlock, rescored) + 8, "the kernels index the two as one u64[2]");
 static_assert(offsetof(RansacBlock, out2) % 8 == 0 && offsetof(RansacBlock, out2) + sizeof(double[2]) == kRansacReadBack, "the part read back is a prefix that ends with out2");
-// RansacLeafBound's and RansacFarBound's list lengths per batch buffer; ransac_plan zeroes a buffer's three through &n_live[q]: [0], [2] and [4]
-struct RansacLive { int n_live[2], n_und[2], n_near[2]; };
-static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * sizeof(int) && offsetof(RansacLive, n_near) == offsetof(RansacLive, n_live) + 4 * sizeof(int), "ransac_plan's n_live[2], n_live[4]");
+// RansacLeafBound's and RansacFarBound's list lengths and RansacBoundLists' count of close hypotheses per batch buffer; ransac_plan zeroes
+// a buffer's four through &n_live[q]: [0], [2], [4] and [6], and k_ransac_finish reads them the same way
+struct RansacLive { int n_live[2], n_und[2], n_near[2], n_close[2]; };
+static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * sizeof(int) && offsetof(RansacLive, n_near) == offsetof(RansacLive, n_live) + 4 * sizeof(int) &&
+              offsetof(RansacLive, n_close) == offsetof(RansacLive, n_live) + 6 * sizeof(int), "ransac_plan's n_live[2], n_live[4], n_live[6]");
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, merge, record_copy, order, far; int drop_permille, a_permille, u_cut_permille; float far_radius; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, order, far; int drop_permille, a_permille, u_cut_permille, fine_y; float far_radius, live_radius; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1334,6 +1433,14 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     k.far_radius = study_env("TDV_RANSAC_FAR_RADIUS") ? (float)atof(study_env("TDV_RANSAC_FAR_RADIUS")) : 4.f;
     k.a_permille = study_env("TDV_RANSAC_FAR_A_PERMILLE") ? atoi(study_env("TDV_RANSAC_FAR_A_PERMILLE")) : 110;
     k.u_cut_permille = study_env("TDV_RANSAC_FAR_UCUT_PERMILLE") ? atoi(study_env("TDV_RANSAC_FAR_UCUT_PERMILLE")) : 22;
+    // RansacBoundLists: a hypothesis within live_radius thresholds of the running best is live unwalked (0: off); the fine level's grid
+    // cuts the leaf pairs into fine_y ranges (profiles/r14/ransac_bound_lists.md)
+    k.live_radius = study_env("TDV_RANSAC_LIVE_RADIUS") ? (float)atof(study_env("TDV_RANSAC_LIVE_RADIUS")) : 20.f;
+    k.fine_y = study_env("TDV_RANSAC_FINE_Y") ? std::min(std::max(atoi(study_env("TDV_RANSAC_FINE_Y")), 1), 64) : RB_FINE_Y;
+    // class-major leaves (k_leaf_keys): built and measured, off by default - on a 9,999-point cloud they take the live list from 4,317 to
+    // 4,063 hypotheses, one block of 1,024 fewer for the two-way order but not for the far and near lists together, and
+    // tests/test_gpu_ransac_far_bound.py holds the far bound strictly under the two-way order there
+    k.leaf_classes = study_env("TDV_RANSAC_LEAF_CLASSES") && atoi(study_env("TDV_RANSAC_LEAF_CLASSES")) == 1;
     k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
     k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
     k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 50;   // tuning knob: phase 1 over the first N - 0.95 best points (natural order: 5 to 100 measured equal;
@@ -1347,6 +1454,7 @@ struct RansacBuf {
     float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the uploaded triples; bail-out: phase 2's list
     int *live, *und, *acc, *ticket;                   // RansacLeafBound: live list, undecided list, its fine sums and tickets
     int *near, *list2, *ubf;                          // RansacFarBound: near list, its phase 2's list, UB_F per hypothesis
+    int* flags;                                       // RansacBoundLists: ransac_prejudge's word per hypothesis (RB_CLOSE, RB_NEAR)
     int* units;                                       // bail-out: job B's ticket words, [far, near][2 phases][8 XCDs][h_pad / RS_BLOCK], zeroed by the batch's k_ransac_hypotheses
     int *plan, *rec, *n_live, *n_und, *n_near;        // this buffer's fields of the RansacBlock and of RansacLive
     void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
@@ -1374,6 +1482,7 @@ struct RansacRun {
     size_t tri_bytes;                                 // per triple: one packed word or an int4
     float *pq = nullptr, *pq2 = nullptr, *pq3 = nullptr, *leaves = nullptr, *cleaves = nullptr; double* slabs = nullptr;
     RansacBlock *d = nullptr, *h = nullptr; RansacLive* lv = nullptr;
+    unsigned long long* leaf_keys = nullptr; unsigned* leaf_vals = nullptr; bool leaves_built = false;   // RansacLeafBound: the sort's keys and values; built for this call
     unsigned long long* ord_mask = nullptr; int* ord_cnt = nullptr; bool ordered = false;     // RansacPointOrder: ballot words, block counts (outliers, then F); done for this call
     unsigned* enc = nullptr;                          // RansacLeafBound: the finite coordinates' bounds per axis
     RansacBuf buf[2] = {};
@@ -1388,7 +1497,7 @@ struct RansacRun {
         TDV_TRY(ws_alloc(ctx, (size_t)ns_pad * 8, &pq)); TDV_TRY(ws_alloc(ctx, 1, &d));
         TDV_HIP(ctx, hipMemsetAsync(d, 0, sizeof(RansacBlock), s));
         k_gather_pq<<<(ns_pad + 255) / 256, 256, 0, s>>>(d_src, d_tgt, d_corr, ns, ns_pad, nt, pq, &d->bad, &d->pmax);
-        if (k.bound) TDV_TRY(leaf_summary());
+        if (k.bound) TDV_TRY(leaf_alloc());
 #ifdef TDV_STUDY
         if (k.score_mfma) TDV_TRY(mfma_pack(ctx, pq, ns, ns_pad, &pq3));
         else
@@ -1414,6 +1523,7 @@ struct RansacRun {
             for (RansacBuf& B : buf) {
                 TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.live)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.und));
                 TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.acc)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad / 64, &B.ticket));
+                TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.flags));
             }
             TDV_TRY(ws_alloc(ctx, 1, &lv));
         }
@@ -1436,20 +1546,29 @@ struct RansacRun {
     int unit_words() const { return 4 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's, then the near lists' two
     int order_blocks() const { return (ns + RO_BLOCK - 1) / RO_BLOCK; }
     void release_events() { for (RansacBuf& B : buf) event_release(ctx, B.ev); }
-    // RansacLeafBound's summary of the pairs: fine and coarse leaves along the Morton order
-    int leaf_summary() {
+    // RansacLeafBound's summary of the pairs: fine and coarse leaves along the class-major Morton order.  Its buffers ...
+    int leaf_alloc() {
         const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_cleaves = (ns + RL_COARSE - 1) / RL_COARSE;
         n_lpairs = (n_leaves + 1) / 2; n_cpairs = (n_cleaves + 1) / 2;
-        unsigned long long* keys = nullptr; unsigned* vals = nullptr;
-        TDV_TRY(ws_alloc(ctx, 12, &enc)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &keys)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &vals));
+        TDV_TRY(ws_alloc(ctx, 12, &enc)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &leaf_keys)); TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &leaf_vals));
         TDV_TRY(ws_alloc(ctx, (size_t)n_lpairs * 32, &leaves)); TDV_TRY(ws_alloc(ctx, (size_t)n_cpairs * 32, &cleaves));
+        return TDV_OK;
+    }
+    // ... and its build, once per call in front of the first bounded batch - nothing reads the leaves before - and behind
+    // point_order(), whose outlier words class the pairs (k_leaf_keys).  The sort takes its scratch (a table and one more set of
+    // keys and values, 12 ns bytes) from the workspace here, not in setup: on a context's first call that can reach hipMalloc with
+    // the first batch in flight - once per context, no effect on a result.
+    int leaf_build() {
+        const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF;
+        unsigned long long* const keys = leaf_keys; unsigned* const vals = leaf_vals;
         TDV_HIP(ctx, hipMemsetAsync(leaves, 0, (size_t)n_lpairs * 32 * sizeof(float), s));
         TDV_HIP(ctx, hipMemsetAsync(cleaves, 0, (size_t)n_cpairs * 32 * sizeof(float), s));
         TDV_HIP(ctx, hipMemsetAsync(enc, 0xff, 24, s)); TDV_HIP(ctx, hipMemsetAsync(enc + 6, 0, 24, s));
         k_leaf_bounds<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc);
-        k_leaf_keys<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc, keys, vals);
-        TDV_TRY(radix_sort_pairs_dev(ctx, keys, keys + ns, vals, vals + ns, (size_t)ns, 6 * RL_BITS));
+        k_leaf_keys<<<(ns + 255) / 256, 256, 0, s>>>(pq, ns, enc, k.leaf_classes && ordered ? ord_mask : nullptr, keys, vals);
+        TDV_TRY(radix_sort_pairs_dev(ctx, keys, keys + ns, vals, vals + ns, (size_t)ns, RL_CLASS_BIT + (k.leaf_classes ? 1 : 0)));
         k_leaf_build<<<(n_leaves * RL_LEAF + 255) / 256, 256, 0, s>>>(pq, ns, vals + ns, leaves, cleaves);
+        leaves_built = true;
         TDV_CHECK_LAUNCH(ctx); return TDV_OK;
     }
 
@@ -1468,7 +1587,8 @@ struct RansacRun {
         TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
         const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words() : 0,
                            k.far && b.bounded ? &d->far : nullptr, k.a_permille};
-        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan);
+        const PreJob pre{b.bounded ? B.flags : nullptr, B.ubf, k.far ? &d->far : nullptr, enc, d->best12, k.live_radius, k.u_cut_permille};
+        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
         return TDV_OK;
     }
     // every test of the batch, no plan: the exact kernel, the fast one, or (study build) the matrix cores
@@ -1493,15 +1613,15 @@ struct RansacRun {
     // RansacLeafBound: the dead hypotheses out - the batch's live list
     void bound(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q]; const int bgrid = (b.cnt + 63) / 64;
-        const FarJob fj{k.far ? &d->far : nullptr, enc, B.near, B.n_near, B.ubf, k.u_cut_permille};
+        const ListJob lj{B.flags, k.far ? B.near : nullptr, B.n_near, B.n_live + 6};
         if (k.one_level)
             k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
-                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr, fj);
+                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr, lj);
         else {
             k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, cleaves, n_cpairs, &d->pmax, sqrt_tau, band_u,
-                                                                      d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, fj);
-            k_ransac_bound_fine<<<dim3(bgrid, RB_FINE_Y), 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
-                                                                                  d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, fj);
+                                                                      d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, lj);
+            k_ransac_bound_fine<<<dim3(bgrid, k.fine_y), 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
+                                                                                  d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, lj);
         }
     }
     // RansacPointOrder: pq2 again from pq, the outliers of the best so far (best12, state[0]: the batches enqueued before) first
@@ -1556,7 +1676,8 @@ struct RansacRun {
             const bool live_only = b.bounded && confidence >= 0.f;      // (see k_ransac_finish)
             int* rec = k.record_copy ? B.rec : const_cast<int*>(B.h_rec);
             k_ransac_finish<<<1, 1024, 0, s>>>(tri(B), b.cnt, B.counts, live_only ? B.live : nullptr, live_only ? B.n_live : nullptr,
-                                               k.far ? B.near : nullptr, B.n_near, B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec);
+                                               k.far ? B.near : nullptr, B.n_near, B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec,
+                                               b.bounded ? B.n_live : nullptr, d->bound);
             TDV_CHECK_LAUNCH(ctx);
             if (k.record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(B.h_rec), B.rec, sizeof(d->rec[0]), hipMemcpyDeviceToHost, s));
         } else TDV_HIP(ctx, hipMemcpyAsync(B.h_cnt, B.counts, (size_t)b.cnt * 4, hipMemcpyDeviceToHost, s));
@@ -1584,6 +1705,7 @@ struct RansacRun {
         // RansacPointOrder, once per call: the first batch has set a best, nothing reads pq2 in between (in front of the batch's
         // k_ransac_hypotheses, whose plan reads the class sizes)
         if (k.order && it0 != 0 && !ordered) point_order();
+        if (b.bounded && !leaves_built) TDV_TRY(leaf_build());
         TDV_TRY(hypotheses(b));
         if (!k.bailout) { TDV_TRY(score_all(b)); return finish(b, false); }   // exact, traced, short or matrix-core calls: every test is scored
         if (k.merge) return enqueue_merged(b);
@@ -1657,6 +1779,7 @@ struct RansacRun {
             ctx->last_ransac_rescore = (double)h->rescored / (scored * (k.score_mfma ? 1.0 : (double)(RS_PCH / 2)));      // the FMA kernel counts point pairs scored twice, the matrix-core study kernel chunks
             ctx->last_ransac_scored = scored / wave_chunks;
         }
+        if (best_iter >= 0 || want_stats) for (int e = 0; e < 4; ++e) ctx->last_ransac_bound[e] = h->bound[e];
         if (best_iter < 0) return TDV_OK;
         pose_to_T16(h->best12, out->T);
         out->fitness = best_fitness; out->inliers = best_inliers; out->best_iteration = best_iter;
@@ -1692,6 +1815,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     const int status = r.loop(seed);
     (void)hipStreamSynchronize(r.s);   // a speculative batch may still be in flight after an early exit
     ctx->last_ransac_rescore = -1.0; ctx->last_ransac_scored = 1.0;
+    for (long long& v : ctx->last_ransac_bound) v = 0;
     r.release_events();
     return status != TDV_OK ? status : r.result(out);
 }

@@ -41,6 +41,7 @@ struct tdv_ctx {
     float icp_loss_scale = 0.f;   // its scale k (0 with L2)
     int ransac_score_mode = 0;    // TDV_RANSAC_SCORE_FAST (FMA pass + exact band) / _EXACT (the reference arithmetic only) / _MATRIX (tdv_ctx_set_ransac_score)
     double last_ransac_rescore = -1.0;   // fraction of (wave, 8-point chunk) pairs of the last RANSAC call that the fast pass scored again exactly (-1: exact mode)
+    long long last_ransac_bound[4] = {0, 0, 0, 0};   // the leaf-box bound's lists in the last RANSAC call: hypotheses bounded, close, on the fine list, live
     double last_ransac_scored = 1.0;     // share of the (hypothesis, point) tests the last RANSAC call evaluated (< 1: the exact bail-out left the rest out)
     int last_voxel_grouping = 0;   // 1: the table (k_vh_insert), 2: pixel windows (k_vs_group) - the last batched voxel call (tdv_ctx_last_voxel_grouping)
     int last_fm_path = 0;      // TDV_FM_PATH_* of the last descriptor match on this ctx (tdv_ctx_last_feature_match_path)

@@ -1079,6 +1079,12 @@ int tdv_load_ply_ascii(const char* path, float* out_xyz, float* out_rgb, int cap
 int tdv_load_mask_png(const char* path, uint8_t* out, long long capacity, int* width, int* height);
 int tdv_load_masks_from_dir(const char* dir, int width, int height, uint8_t* out, int capacity_masks, int* n_out, int* n_skipped);
 
+/* The leaf-box bound's lists in the last tdv_ransac* call on this ctx, added up over its bounded batches (every batch after the
+ * first of a call without a per-iteration trace): out[0] hypotheses bounded, out[1] of them close to the running best pose and
+ * therefore live without a walk, out[2] put on the fine level's list, out[3] live - the hypotheses that were scored at all.  All
+ * zero for a call without bounded batches or before any.  The counts are the same from call to call; they change no result. */
+void tdv_ctx_last_ransac_bound(tdv_ctx* ctx, long long out[4]);
+
 #ifdef __cplusplus
 }
 #endif
