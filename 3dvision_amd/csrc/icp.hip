@@ -330,71 +330,62 @@ __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table
     // The eight cells are probed TOGETHER, two consecutive table entries per cell and round trip: a wave waits once per step
     // of the longest probe run among its 512 cells, not once per step of every cell in turn (200k x 200k: 33.3 -> 30.6 us;
     // 800k sources: 81.9 -> 73.7 us; tools/studies/icp_grid_scaling.py).  Probing does not wrap (k_grid_insert).
-    unsigned tag[8], slot[8]; uint4 e[8];
+    // Every step's eight loads are UNCONDITIONAL and stand back to back, and only then is any of them looked at: a load under
+    // `if (pending & (1u << c))` becomes an exec-masked block of its own with a full wait (vmcnt(0)) in front of it, eight
+    // serial round trips per step instead of one.  A cell whose probe has ended reads table[0] instead - one cached line for all
+    // such lanes (64 lanes reloading 64 slots of their own cost the texture path more than the round trips saved) - and what
+    // it reads is not looked at.
+    unsigned tag[8], slot[8];
+    int j[8];
 #pragma unroll
     for (int c = 0; c < 8; ++c) {
         const unsigned long long key = grid_key(cx + ((c & 1) ? sx : 0), cy + ((c & 2) ? sy : 0), cz + ((c & 4) ? sz : 0));
         tag[c] = grid_tag(key);
         slot[c] = grid_slot(key, shift);
-        e[c] = *reinterpret_cast<const uint4*>(&table[slot[c]]);   // 16 bytes at an 8-byte-aligned address
+        j[c] = -1;
     }
     (void)mask;
-    int j[8];
-    unsigned pending = 0u;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        j[c] = -1;
-        if (e[c].x == tag[c]) j[c] = (int)e[c].y;
-        else if (e[c].x != GRID_EMPTY) {
-            if (e[c].z == tag[c]) j[c] = (int)e[c].w;
-            else if (e[c].z != GRID_EMPTY) { slot[c] += 2u; pending |= 1u << c; }
-        }
-    }
+    unsigned pending = 0xffu;
     while (pending) {
+        uint4 e[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) if (pending & (1u << c)) e[c] = *reinterpret_cast<const uint4*>(&table[slot[c]]);
+        for (int c = 0; c < 8; ++c) e[c] = *reinterpret_cast<const uint4*>(&table[(pending & (1u << c)) ? slot[c] : 0u]);   // 16 bytes at an 8-byte-aligned address
+        const unsigned was = pending;
+        pending = 0u;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            if (!(pending & (1u << c))) continue;
-            pending &= ~(1u << c);
-            if (e[c].x == tag[c]) j[c] = (int)e[c].y;
-            else if (e[c].x != GRID_EMPTY) {
-                if (e[c].z == tag[c]) j[c] = (int)e[c].w;
-                else if (e[c].z != GRID_EMPTY) { slot[c] += 2u; pending |= 1u << c; }
-            }
+            const bool on = (was & (1u << c)) != 0u;
+            const bool hit0 = on && e[c].x == tag[c], go1 = on && !hit0 && e[c].x != GRID_EMPTY;
+            const bool hit1 = go1 && e[c].z == tag[c], next = go1 && !hit1 && e[c].z != GRID_EMPTY;
+            j[c] = hit0 ? (int)e[c].y : hit1 ? (int)e[c].w : j[c];
+            slot[c] += next ? 2u : 0u;
+            pending |= next ? 1u << c : 0u;
         }
     }
     bd = INFINITY; bo = INT_MAX;
-    auto take = [&](const float4 t, int idx) {
+    auto take = [&](const float4 t, int idx, bool live) {
         const float ex = px - t.x, ey = py - t.y, ez = pz - t.z;
         const float d2 = ex * ex + (ey * ey + ez * ez);    // the scan's expression
-        if (d2 <= tau && (d2 < bd || (d2 == bd && idx < bo))) { bd = d2; bo = idx; }
+        if (live && d2 <= tau && (d2 < bd || (d2 == bd && idx < bo))) { bd = d2; bo = idx; }
     };
-    float4 first[8];
-#pragma unroll
-    for (int c = 0; c < 8; ++c) first[c] = j[c] >= 0 ? node[j[c]] : make_float4(0.f, 0.f, 0.f, __int_as_float(-1));   // the cells' first points, together
+    // the cells' lists (cells hold one or two points): the eight lists advance TOGETHER, one round trip per step of the longest
+    // list among a wave's 512 cells instead of a sum over the cells.  Again eight unconditional loads back to back (`if (nx[c]
+    // >= 0) t[c] = node[nx[c]]` serialises like the probes above): an empty cell and a list that has ended read node[0], which
+    // exists for every nt >= 1 and is one cached line for all such lanes, and take() is told not to count it.
     int nx[8];
     bool more = false;
 #pragma unroll
-    for (int c = 0; c < 8; ++c) {
-        nx[c] = -1;
-        if (j[c] < 0) continue;
-        take(first[c], j[c]);
-        nx[c] = __float_as_int(first[c].w);
-        more |= nx[c] >= 0;
-    }
-    // the rest of the lists (cells hold one or two points): the eight lists advance TOGETHER, one round trip per step of the
-    // longest list among a wave's 512 cells instead of a sum over the cells
+    for (int c = 0; c < 8; ++c) { nx[c] = j[c]; more |= nx[c] >= 0; }
     while (more) {
         float4 t[8];
 #pragma unroll
-        for (int c = 0; c < 8; ++c) if (nx[c] >= 0) t[c] = node[nx[c]];
+        for (int c = 0; c < 8; ++c) t[c] = node[nx[c] >= 0 ? nx[c] : 0];
         more = false;
 #pragma unroll
         for (int c = 0; c < 8; ++c) {
-            if (nx[c] < 0) continue;
-            take(t[c], nx[c]);
-            nx[c] = __float_as_int(t[c].w);
+            const bool live = nx[c] >= 0;
+            take(t[c], nx[c], live);
+            nx[c] = live ? __float_as_int(t[c].w) : -1;
             more |= nx[c] >= 0;
         }
     }
@@ -566,19 +557,37 @@ __device__ __forceinline__ CorrPt<MODE> corr_pt(const IcpArgs<MODE>& a, const fl
     } else return {};
 }
 
+// What a correspondence gathers from the target side, by the target's index: the point q, the normal n (point-to-plane, GICP,
+// colored ICP) and colored ICP's (I, d).  The FETCH half of corr_terms / acc_terms: a caller with several correspondences in hand
+// fetches them all before it looks at any (k_icp_accumulate), the others fetch and use (corr_terms, acc_terms).
+struct CorrTgt { float q[3], n[3]; float4 tc; };
+template <int MODE>
+__device__ __forceinline__ CorrTgt corr_fetch(int idx, const float* tgt, const float* tgt_normals, const CorrPt<MODE>& X) {
+    CorrTgt G;
+    if (MODE == 2) return G;
+    G.q[0] = tgt[3 * idx]; G.q[1] = tgt[3 * idx + 1]; G.q[2] = tgt[3 * idx + 2];
+    if (MODE != 1) { G.n[0] = tgt_normals[3 * idx]; G.n[1] = tgt_normals[3 * idx + 1]; G.n[2] = tgt_normals[3 * idx + 2]; }
+    if constexpr (MODE == 4) G.tc = reinterpret_cast<const float4*>(X.tgt_color)[idx];   // (Iq, d)
+    return G;
+}
+
+// point-to-plane's J = [p x n | n] (registration.cpp:346-349) and r = (p - q) . n (:351) from the fetched target
+__device__ __forceinline__ void corr_jr(float px, float py, float pz, const CorrTgt& G, float* J /* 6 */, float& r) {
+    const float nx = G.n[0], ny = G.n[1], nz = G.n[2];
+    J[0] = py * nz - pz * ny; J[1] = pz * nx - px * nz; J[2] = px * ny - py * nx; J[3] = nx; J[4] = ny; J[5] = nz;
+    const float ex = px - G.q[0], ey = py - G.q[1], ez = pz - G.q[2];
+    r = ex * nx + (ey * ny + ez * nz);
+}
+
 // One accepted correspondence, source point p (transformed) paired with target idx, in the float steps of registration.cpp: its
-// target q and, point-to-plane, J = [p x n | n] (:346-349) and r = (p - q) . n (:351).  Every path's sums and records are built
-// from these (acc_terms, ref_record), so that every path sees the same bits.
+// target q and, point-to-plane, J and r (corr_jr).  Every path's sums and records are built from these (acc_terms, ref_record), so
+// that every path sees the same bits.
 template <int MODE>
 __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx, const float* tgt, const float* tgt_normals,
                                            float* q /* 3 */, float* J /* 6 */, float& r) {
-    q[0] = tgt[3 * idx]; q[1] = tgt[3 * idx + 1]; q[2] = tgt[3 * idx + 2];
-    if (MODE == 0) {
-        const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
-        J[0] = py * nz - pz * ny; J[1] = pz * nx - px * nz; J[2] = px * ny - py * nx; J[3] = nx; J[4] = ny; J[5] = nz;
-        const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
-        r = ex * nx + (ey * ny + ez * nz);
-    }
+    const CorrTgt G = corr_fetch<MODE == 0 ? 0 : 1>(idx, tgt, tgt_normals, CorrPt<MODE == 0 ? 0 : 1>{});
+    q[0] = G.q[0]; q[1] = G.q[1]; q[2] = G.q[2];
+    if (MODE == 0) corr_jr(px, py, pz, G, J, r);
 }
 
 // the tree sums' terms of one accepted correspondence at squared distance d2, handed to put(k, term) for k = 0 .. acc_nv<MODE>() - 1:
@@ -594,16 +603,17 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // Mahalanobis residual sqrtf(fmaxf(0, e . g))) scales every term after the first two: (double)w * term, exact for the f32 products of
 // point-to-plane and GICP and for p and q; w * (P[a] * Q[b]) is rounded once.  Then point-to-point W = w, and last n_eff = (w > 0).
 // {1, d2} stay unweighted: n_corr, rmse and fitness are L2's.
+// This is the ADD half, from the target as corr_fetch<MODE> fetched it (G); acc_terms below fetches and adds.
 template <int MODE, bool ROBUST = false, class Put>
-__device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
-                                          IcpLoss L, CorrPt<MODE> X, Put put) {
+__device__ __forceinline__ void acc_terms_add(float px, float py, float pz, float d2, const CorrTgt& G, IcpLoss L, CorrPt<MODE> X, Put put) {
     put(0, 1.0); put(1, (double)d2);
     if (MODE == 2) return;
     if constexpr (MODE == 4) {
-        float q[3], J[6], en;
-        corr_terms<0>(px, py, pz, idx, tgt, tgt_normals, q, J, en);     // J = [p x n | n], en = (p - q) . n
+        float J[6], en;
+        const float* q = G.q;
+        corr_jr(px, py, pz, G, J, en);     // J = [p x n | n], en = (p - q) . n
         const float nx = J[3], ny = J[4], nz = J[5];
-        const float4 tc = reinterpret_cast<const float4*>(X.tgt_color)[idx];   // (Iq, d)
+        const float4 tc = G.tc;   // (Iq, d)
         const float lg = X.lg, lc = X.lc;
         // e_t = e - en n, the source point's offset projected on the target's tangent plane; g = (d . n) n - d = -m
         const float ex = px - q[0], ey = py - q[1], ez = pz - q[2];
@@ -632,8 +642,8 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
         return;
     }
     if constexpr (MODE == 3) {
-        const float qx = tgt[3 * idx], qy = tgt[3 * idx + 1], qz = tgt[3 * idx + 2];
-        const float nx = tgt_normals[3 * idx], ny = tgt_normals[3 * idx + 1], nz = tgt_normals[3 * idx + 2];
+        const float qx = G.q[0], qy = G.q[1], qz = G.q[2];
+        const float nx = G.n[0], ny = G.n[1], nz = G.n[2];
         const float c = X.c, ax = X.ax, ay = X.ay, az = X.az;
         // C = 2 I - c (a a^T + n n^T) in f32; M = C^-1 from the cofactors in f64 (C's condition number is about 1 / epsilon: in f32 the
         // cancellation in the cofactors and the determinant would cost ~1e-7 / epsilon of M), rounded to f32
@@ -668,8 +678,9 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
         if (ROBUST) put(29, w > 0.f ? 1.0 : 0.0);
         return;
     }
-    float q[3], J[6], r;
-    corr_terms<MODE>(px, py, pz, idx, tgt, tgt_normals, q, J, r);
+    float J[6], r;
+    const float* q = G.q;
+    if (MODE == 0) corr_jr(px, py, pz, G, J, r);
     float w = 1.f;
     if (ROBUST) w = loss_weight(L, MODE == 0 ? r : sqrtf(d2));
     const double wd = w;
@@ -697,6 +708,12 @@ __device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2
             for (int b = 0; b < 3; ++b) put(8 + a * 3 + b, ROBUST ? wd * (P[a] * Q[b]) : P[a] * Q[b]);
         if (ROBUST) { put(17, wd); put(18, w > 0.f ? 1.0 : 0.0); }
     }
+}
+
+template <int MODE, bool ROBUST = false, class Put>
+__device__ __forceinline__ void acc_terms(float px, float py, float pz, float d2, int idx, const float* tgt, const float* tgt_normals,
+                                          IcpLoss L, CorrPt<MODE> X, Put put) {
+    acc_terms_add<MODE, ROBUST>(px, py, pz, d2, corr_fetch<MODE>(idx, tgt, tgt_normals, X), L, X, put);
 }
 
 // this lane's sums += one accepted correspondence (p, target idx at squared distance best)
@@ -800,6 +817,63 @@ __device__ __forceinline__ void resolve_nn(int i, int ns_pad, int nsplit, const 
     }
 }
 
+// ---- the direct path's points of a lane (pruned / grid search: one (d2, target index) per source), fetched TOGETHER ----------------
+// A lane's points do not depend on one another, but a loop that takes them one by one waits three times per point: for the source
+// point and its d2, for its target index, and for the gather of that target.  At one wave per SIMD (196 blocks of 125 VGPRs at 200k
+// points) nothing else hides those waits.  So the work is cut in three: acc_fetch issues every point's source, d2 and index loads;
+// acc_points transforms and applies the acceptance test, issues every point's gathers (corr_pt, corr_fetch), and only then adds
+// the accepted points' terms into v[] in ascending point order - the f64 order of the loop it replaces.  All loads are
+// unconditional, from a clamped source index resp. target 0 for a rejected point: a load under `if (accepted)` is an exec-masked
+// block of its own with a full wait in front of it.
+constexpr int ACC_GROUP = 4;     // points fetched together (make_plan's acc_ppt)
+template <int P> struct AccSrc { float sx[P], sy[P], sz[P], d[P]; int c[P]; };
+
+// point q of the group is source i0 + 256 q of the ns points at src / pd2 / pidx (a point past the end reads the last one)
+template <int P>
+__device__ __forceinline__ AccSrc<P> acc_fetch(const float* __restrict__ src, const float* __restrict__ pd2, const int* __restrict__ pidx, int i0, int ns) {
+    AccSrc<P> S;
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        const int i = i0 + 256 * q, il = i < ns ? i : ns - 1;
+        S.sx[q] = src[3 * il]; S.sy[q] = src[3 * il + 1]; S.sz[q] = src[3 * il + 2];
+        S.d[q] = pd2[il]; S.c[q] = pidx[il];
+    }
+    return S;
+}
+
+// the first nq points of the group S (those below ns): outputs, gathers, then v[] += the accepted ones' terms.  off: where the
+// ns points start in the arrays laid out like the source points (corr_pt), in the caller's index type
+template <int MODE, bool ROBUST, int P, class Index>
+__device__ __forceinline__ void acc_points(double* v, const AccSrc<P>& S, int i0, int nq, int ns, const float* T, float tau_accept,
+                                           const float* __restrict__ tgt, const float* __restrict__ tgt_normals, IcpLoss loss,
+                                           const IcpArgs<MODE>& a, Index off,
+                                           int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc) {
+    float px[P], py[P], pz[P], best[P];
+    bool acc[P];
+    CorrPt<MODE> X[P];
+    CorrTgt G[P];
+#pragma unroll
+    for (int q = 0; q < P; ++q) {
+        const int i = i0 + 256 * q, il = i < ns ? i : ns - 1;
+        const bool valid = q < nq && i < ns;
+        acc_transform(T, S.sx[q], S.sy[q], S.sz[q], px[q], py[q], pz[q]);
+        best[q] = S.d[q] < FLT_MAX ? S.d[q] : FLT_MAX;          // resolve_nn's direct case: one split
+        const int idx = S.d[q] < FLT_MAX ? S.c[q] : 0;
+        acc[q] = valid && best[q] <= tau_accept;
+        if (valid) {
+            if (out_corr) out_corr[i] = idx;
+            if (out_d2) out_d2[i] = best[q];
+            if (out_acc) out_acc[i] = acc[q] ? 1 : 0;
+        }
+        X[q] = corr_pt(a, T, off + il);
+        G[q] = corr_fetch<MODE>(acc[q] ? idx : 0, tgt, tgt_normals, X[q]);
+    }
+    // (branches, not a select per sum: as one straight block the scheduler moves the gathers back down to their uses to save registers)
+#pragma unroll
+    for (int q = 0; q < P; ++q)
+        if (acc[q]) acc_terms_add<MODE, ROBUST>(px[q], py[q], pz[q], best[q], G[q], loss, X[q], [v](int k, double t) { v[k] += t; });
+}
+
 // One launch per iteration: every block reduces its points to one slab; the block that finishes LAST (atomic ticket) folds all
 // slabs in a fixed order, solves, and updates the state on the device.
 template <int MODE, int ACC_PPT, bool ROBUST = false>   // ACC_PPT source points per thread (summed per lane in index order); ROBUST: loss L
@@ -811,29 +885,37 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
                       IcpState* st, float tau_accept, int fixed_iterations, IcpLoss loss,
                       double* slabs, unsigned* ticket,
                       int* __restrict__ out_corr, float* __restrict__ out_d2, uint8_t* __restrict__ out_acc, IcpArgs<MODE> args) {
-    if (st->done) return;
+    if (st->done) return;       // (the loads below ahead of this wait: 0.2 us, the kernel's own spread - profiles/r15)
     const IcpArgs<MODE> a = args;
+    const int i0 = blockIdx.x * (256 * ACC_PPT) + threadIdx.x;
+    AccSrc<ACC_PPT> S;
+    if (direct) S = acc_fetch<ACC_PPT>(src, pd2, pchunk, i0, ns);   // (nsplit is 1 on that path: pd2 and pchunk hold one entry per source)
     const int iter0 = st->iter; const float rmse0 = st->rmse;
+    float T[12], Tb[4];
+    acc_load_pose(st, T, Tb);
     double v[ACC_NV];
 #pragma unroll
     for (int k = 0; k < ACC_NV; ++k) v[k] = 0.0;
-    float T[12], Tb[4];
-    acc_load_pose(st, T, Tb);
+    if (direct) acc_points<MODE, ROBUST>(v, S, i0, ACC_PPT, ns, T, tau_accept, tgt, tgt_normals, loss, a, 0, out_corr, out_d2, out_acc);
+    else {
+        // the brute-force scan's splits (nsplit > 1, one point per thread outside study runs) keep the loop that takes a lane's
+        // points one by one: resolve_nn's loads depend on the minimum over the splits
 #pragma unroll 1
-    for (int q = 0; q < ACC_PPT; ++q) {
-        const int i = blockIdx.x * (256 * ACC_PPT) + q * 256 + threadIdx.x;
-        if (i >= ns) continue;
-        float px, py, pz;
-        acc_transform(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
-        float best; int idx;
-        resolve_nn(i, ns_pad, nsplit, pd2, pchunk, direct, tx, ty, tz, px, py, pz, best, idx);
-        const bool acc = best <= tau_accept;
-        if (out_corr) out_corr[i] = idx;
-        if (out_d2) out_d2[i] = best;
-        if (out_acc) out_acc[i] = acc ? 1 : 0;
-        if (!acc) continue;
-        const CorrPt<MODE> X = corr_pt(a, T, i);
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, X);
+        for (int q = 0; q < ACC_PPT; ++q) {
+            const int i = i0 + q * 256;
+            if (i >= ns) continue;
+            float px, py, pz;
+            acc_transform(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
+            float best; int idx;
+            resolve_nn(i, ns_pad, nsplit, pd2, pchunk, direct, tx, ty, tz, px, py, pz, best, idx);
+            const bool acc = best <= tau_accept;
+            if (out_corr) out_corr[i] = idx;
+            if (out_d2) out_d2[i] = best;
+            if (out_acc) out_acc[i] = acc ? 1 : 0;
+            if (!acc) continue;
+            const CorrPt<MODE> X = corr_pt(a, T, i);
+            acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, X);
+        }
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
@@ -889,26 +971,24 @@ void k_icp_accumulate_multi(const float* __restrict__ src, const IcpInst* __rest
     IcpState* st = st_all + b;
     if (st->done) return;
     const IcpInst in = inst[b];
+    const int lb = blockIdx.x - in.acc_blk0;
+    const float* __restrict__ s0 = src + (size_t)in.src_off * 3;
+    const float* __restrict__ d0 = pd2 + in.src_off;
+    const int* __restrict__ c0 = pidx + in.src_off;
+    // as k_icp_accumulate's direct path, in groups of ACC_GROUP points (in.ppt is make_plan's 4 outside study runs: one group)
+    const int i0 = lb * (256 * in.ppt) + threadIdx.x;
+    AccSrc<ACC_GROUP> S = acc_fetch<ACC_GROUP>(s0, d0, c0, i0, in.ns);
     const int iter0 = st->iter; const float rmse0 = st->rmse;
+    float T[12], Tb[4];
+    acc_load_pose(st, T, Tb);
     double v[ACC_NV];
 #pragma unroll
     for (int k = 0; k < ACC_NV; ++k) v[k] = 0.0;
-    float T[12], Tb[4];
-    acc_load_pose(st, T, Tb);
-    const int lb = blockIdx.x - in.acc_blk0;
-    const float* __restrict__ s0 = src + (size_t)in.src_off * 3;
 #pragma unroll 1
-    for (int q = 0; q < in.ppt; ++q) {
-        const int i = lb * (256 * in.ppt) + q * 256 + threadIdx.x;
-        if (i >= in.ns) continue;
-        float px, py, pz;
-        acc_transform(T, s0[3 * i], s0[3 * i + 1], s0[3 * i + 2], px, py, pz);
-        const float d = pd2[in.src_off + i];
-        const float best = d < FLT_MAX ? d : FLT_MAX;
-        const int idx = d < FLT_MAX ? pidx[in.src_off + i] : 0;
-        if (!(best <= tau_accept)) continue;
-        const CorrPt<MODE> X = corr_pt(args, T, (size_t)in.src_off + i);
-        acc_add<MODE, ROBUST>(v, px, py, pz, best, idx, tgt, tgt_normals, loss, X);
+    for (int q0 = 0; q0 < in.ppt; q0 += ACC_GROUP) {
+        if (q0) S = acc_fetch<ACC_GROUP>(s0, d0, c0, i0 + 256 * q0, in.ns);
+        acc_points<MODE, ROBUST>(v, S, i0 + 256 * q0, in.ppt - q0, in.ns, T, tau_accept, tgt, tgt_normals, loss, args, (size_t)in.src_off,
+                                 (int*)nullptr, (float*)nullptr, (uint8_t*)nullptr);
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs + (size_t)in.acc_blk0 * ACC_NV, lb, in.acc_blocks, tickets + b, sh)) return;
