@@ -24,7 +24,7 @@
 // successful hook of the root it held, and its two arguments never rise.  Nothing waits for another lane.
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
-#include "cluster_walk.hpp"
+#include "sorted_cloud.hpp"
 #include <cfloat>
 #include <cmath>
 #include <cstring>
@@ -47,7 +47,7 @@ struct ClusterState {
 };
 
 // core_s[sorted position] and core[original index] = the point has at least min_points neighbours (itself included); parent[i] = i
-__global__ __launch_bounds__(64 * CL_WAVES) void k_cluster_count(ClusterCloud c, float eps2, int min_points, int* __restrict__ core_s,
+__global__ __launch_bounds__(64 * CL_WAVES) void k_cluster_count(SortedCloud c, float eps2, int min_points, int* __restrict__ core_s,
                                                                   int* __restrict__ core, int* __restrict__ parent) {
     const int lane = threadIdx.x & 63;
     const int sp = blockIdx.x * CL_WAVES + (threadIdx.x >> 6);
@@ -56,9 +56,9 @@ __global__ __launch_bounds__(64 * CL_WAVES) void k_cluster_count(ClusterCloud c,
     int cnt = 0;
     // A query that is not its own neighbour (d2(q, q) is NaN: a NaN or infinite coordinate) has none: every d2 to it is NaN or +inf, and
     // eps2 is finite.  Its walk would pass every box (a NaN gap counts as 0) only to count nothing.
-    if (cluster_d2(qx, qy, qz, qx, qy, qz) <= eps2) cluster_walk(c, qx, qy, qz, eps2, lane, [&](int leaf) {
+    if (d2_point<D2::DBSCAN>(qx, qy, qz, qx, qy, qz) <= eps2) walk_in_order<D2::DBSCAN>(c, qx, qy, qz, eps2, lane, [&](int leaf) {
         const int p = leaf * 64 + lane;                      // the arrays are padded to a multiple of 256
-        const bool nb = p < c.n && cluster_d2(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz) <= eps2;
+        const bool nb = p < c.n && d2_point<D2::DBSCAN>(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz) <= eps2;
         cnt += __popcll(__ballot(nb));
         return cnt >= min_points;
     });
@@ -105,7 +105,7 @@ __device__ __forceinline__ int cluster_unite(int* parent, int a, int b) {
 }
 
 // core queries: unions with the core neighbours of lower index; the others: bkey[original index] = their nearest core neighbour's key
-__global__ __launch_bounds__(64 * CL_WAVES) void k_cluster_link(ClusterCloud c, float eps2, const int* __restrict__ core_s, int* parent,
+__global__ __launch_bounds__(64 * CL_WAVES) void k_cluster_link(SortedCloud c, float eps2, const int* __restrict__ core_s, int* parent,
                                                                  unsigned long long* __restrict__ bkey) {
     const int lane = threadIdx.x & 63;
     const int sp = blockIdx.x * CL_WAVES + (threadIdx.x >> 6);
@@ -115,9 +115,9 @@ __global__ __launch_bounds__(64 * CL_WAVES) void k_cluster_link(ClusterCloud c, 
     const bool is_core = core_s[sp] != 0;                    // wave-uniform
     int mine = i;                                            // an ancestor of i (core queries)
     unsigned long long best = CL_NO_KEY;                     // per lane (the others)
-    if (cluster_d2(qx, qy, qz, qx, qy, qz) <= eps2) cluster_walk(c, qx, qy, qz, eps2, lane, [&](int leaf) {     // as in k_cluster_count
+    if (d2_point<D2::DBSCAN>(qx, qy, qz, qx, qy, qz) <= eps2) walk_in_order<D2::DBSCAN>(c, qx, qy, qz, eps2, lane, [&](int leaf) {     // as in k_cluster_count
         const int p = leaf * 64 + lane;
-        const float d2 = cluster_d2(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz);
+        const float d2 = d2_point<D2::DBSCAN>(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz);
         if (p < c.n && d2 <= eps2 && core_s[p]) {
             const int j = c.orig[p];
             if (is_core) {
@@ -285,14 +285,13 @@ int cluster_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_cluster_p
     SortedCloud sc;
     TDV_TRY(spatial_sort_cloud(ctx, d_xyz, n, sc));
     TDV_TRY(ws_alloc(ctx, (size_t)sc.pad, &core_s));
-    const ClusterCloud c{sc.sx, sc.sy, sc.sz, sc.orig, sc.lbox, sc.tbox, n, sc.n_leaf, sc.n_top};
     const float eps2 = std::min(prm.eps * prm.eps, FLT_MAX);    // finite: an infinite d2 never passes
     const int walk_blocks = (n + CL_WAVES - 1) / CL_WAVES;
 
     TDV_HIP(ctx, hipMemsetAsync(size, 0, (size_t)2 * n1 * sizeof(int), s));
     k_cluster_init<<<1, 64, 0, s>>>(st);
-    k_cluster_count<<<walk_blocks, 64 * CL_WAVES, 0, s>>>(c, eps2, prm.min_points, core_s, core, parent);
-    k_cluster_link<<<walk_blocks, 64 * CL_WAVES, 0, s>>>(c, eps2, core_s, parent, bkey);
+    k_cluster_count<<<walk_blocks, 64 * CL_WAVES, 0, s>>>(sc, eps2, prm.min_points, core_s, core, parent);
+    k_cluster_link<<<walk_blocks, 64 * CL_WAVES, 0, s>>>(sc, eps2, core_s, parent, bkey);
     k_cluster_flatten<<<nb, 256, 0, s>>>(core, parent, n, comp, is_root, st);
     TDV_CHECK_LAUNCH(ctx);
     TDV_TRY(exclusive_scan_dev(ctx, is_root, n, cid, &st->n_found));

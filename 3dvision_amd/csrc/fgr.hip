@@ -16,6 +16,7 @@
 //  (vi)  ransac_score_pose_dev: RANSAC's own winner scoring of that pose (k_gather_pq, k_ransac_rmse_partial, k_ransac_rmse_final).
 #include "tdv_internal.hpp"
 #include "philox.hpp"
+#include "fixed_tree.hpp"
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -115,24 +116,6 @@ __global__ __launch_bounds__(FGR_COMPACT_THREADS) void k_fgr_tuple_compact(const
     if (tid == 0) state[0] = (int)std::min(base + total, (long long)max_count);
 }
 
-// f64 sum over the 256 threads of a block, fixed order (wave shuffles, then the four waves in order); valid in thread 0
-__device__ __forceinline__ double fgr_block_sum(double v, double* lds4) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
-}
-__device__ __forceinline__ double fgr_block_max(double v, double* lds4) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmax(fmax(lds4[0], lds4[1]), fmax(lds4[2], lds4[3]));
-}
-
 // blocks [0, bs) sum 256 source points each, blocks [bs, bs + bt) target points: slabs[3 b + a]
 __global__ __launch_bounds__(256) void k_fgr_mean_partial(const float* __restrict__ src, int ns, const float* __restrict__ tgt, int nt,
                                                           int bs, double* __restrict__ slabs) {
@@ -141,7 +124,7 @@ __global__ __launch_bounds__(256) void k_fgr_mean_partial(const float* __restric
     const float* x = is_s ? src : tgt;
     const int n = is_s ? ns : nt, i = (is_s ? blockIdx.x : blockIdx.x - bs) * 256 + threadIdx.x;
     for (int a = 0; a < 3; ++a) {
-        const double v = fgr_block_sum(i < n ? (double)x[3 * i + a] : 0.0, lds4);
+        const double v = tree_block_sum(i < n ? (double)x[3 * i + a] : 0.0, lds4);
         if (threadIdx.x == 0) slabs[3 * (size_t)blockIdx.x + a] = v;
     }
 }
@@ -178,7 +161,7 @@ __global__ __launch_bounds__(256) void k_fgr_scale_partial(const float* __restri
         const double dx = (double)x[3 * i] - mu[0], dy = (double)x[3 * i + 1] - mu[1], dz = (double)x[3 * i + 2] - mu[2];
         r = sqrt((dx * dx + dy * dy) + dz * dz);
     }
-    const double m = fgr_block_max(r, lds4);
+    const double m = tree_block_max(r, lds4);
     if (threadIdx.x == 0) slabs[blockIdx.x] = m;
 }
 // norm[6] = sigma (1 with use_absolute_scale), norm[7] = mu's start value (1, or the scale with use_absolute_scale)
@@ -186,7 +169,7 @@ __global__ __launch_bounds__(256) void k_fgr_scale_final(const double* __restric
     __shared__ double lds4[4];
     double v = 0.0;
     for (int b = threadIdx.x; b < nb; b += 256) v = fmax(v, slabs[b]);
-    const double scale = fgr_block_max(v, lds4);
+    const double scale = tree_block_max(v, lds4);
     if (threadIdx.x == 0) { norm[6] = absolute ? 1.0 : scale; norm[7] = absolute ? scale : 1.0; }
 }
 

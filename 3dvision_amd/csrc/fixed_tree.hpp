@@ -1,8 +1,9 @@
-// The fixed f64 summation tree of include/tdv_hip.h (tdv_remove_statistical_outlier, rule 4), shared by the kernels that sum one f64 term
-// per point of a cloud in ORIGINAL index order: outlier.hip (cloud_mean, std_dev) and iss.hip (the cloud's resolution).  The term of
-// point i belongs to workgroup i / 256, thread i % 256; a workgroup sum is the shuffle tree over each wave, then (w0 + w1) + (w2 + w3);
-// one workgroup then adds the workgroup sums t, t + 256, ... into thread t and sums its 256 threads the same way.  One order, so two calls
-// give the same bits.  Device code for workgroups of 256 threads; include after `#pragma clang fp contract(off)`.
+// The fixed f64 summation tree of include/tdv_hip.h (tdv_remove_statistical_outlier, rule 4; tdv_segment_planes; tdv_fgr's means), shared
+// by the kernels that sum f64 terms per point of a cloud in index order: outlier.hip (cloud_mean, std_dev), iss.hip (the cloud's
+// resolution), plane.hip (the inlier sums) and fgr.hip (the clouds' means, first level).  The term of point i belongs to workgroup
+// i / 256, thread i % 256; a workgroup sum is the shuffle tree over each wave, then (w0 + w1) + (w2 + w3); one workgroup then adds the
+// workgroup sums t, t + 256, ... into thread t and sums its 256 threads the same way.  One order, so two calls give the same bits.
+// Device code for workgroups of 256 threads, compiled without contraction (the library's -ffp-contract=off).
 #pragma once
 #include "tdv_internal.hpp"
 
@@ -12,7 +13,7 @@ namespace {   // per translation unit, as the kernels that use it
 
 __device__ __forceinline__ double tree_nan() { return __longlong_as_double(0x7ff8000000000000ll); }
 
-// f64 sum over the 256 threads of a workgroup in plane.hip's fixed order (wave shuffles, then the four waves in order); valid in thread 0
+// f64 sum over the 256 threads of a workgroup in the fixed order (wave shuffles, then the four waves in order); valid in thread 0
 __device__ __forceinline__ double tree_block_sum(double v, double* lds4) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
@@ -20,6 +21,16 @@ __device__ __forceinline__ double tree_block_sum(double v, double* lds4) {
     if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
     __syncthreads();
     return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+// the largest of a workgroup's 256 values (order-free; fmax: a NaN never wins); valid in thread 0
+__device__ __forceinline__ double tree_block_max(double v, double* lds4) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(lds4[0], lds4[1]), fmax(lds4[2], lds4[3]));
 }
 
 __device__ __forceinline__ int tree_block_count(int v, int* lds4) {
@@ -30,10 +41,11 @@ __device__ __forceinline__ int tree_block_count(int v, int* lds4) {
     return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
 }
 
-// the nb workgroup sums (counts) added by one workgroup: thread t takes t, t + 256, ... in order, then the block sum; valid in thread 0
-__device__ __forceinline__ double tree_partials_sum(const double* __restrict__ part, int nb, double* lds4) {
+// the nb workgroup sums (counts) added by one workgroup: thread t takes t, t + 256, ... in order, then the block sum; valid in thread 0.
+// width, a: workgroup b's sum is entry a of its `width` sums, part[width * b + a]
+__device__ __forceinline__ double tree_partials_sum(const double* __restrict__ part, int nb, double* lds4, int width = 1, int a = 0) {
     double v = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) v += part[b];
+    for (int b = threadIdx.x; b < nb; b += 256) v += part[(size_t)width * b + a];
     return tree_block_sum(v, lds4);
 }
 

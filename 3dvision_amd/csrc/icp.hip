@@ -44,6 +44,7 @@
 // No float atomics anywhere: two runs give identical bits.
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
+#include "sorted_cloud.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -176,14 +177,6 @@ constexpr int PN_WAVES = PN_WAVES_VALUE;   // waves per workgroup (measured at 2
 // profiles/r2/history/icp_nn_points_per_wave.jsonl): 1: 0.131 ms, 4: 0.141, 8: 0.144, 16: 0.155, 32: 0.166 ms per launch.
 constexpr int PN_PTS = PN_PTS_VALUE;
 
-// lower bound of fl(d2) between point p and any point inside box idx (see knn.hip: box_lower_bound)
-__device__ __forceinline__ float point_box_lb(const float* __restrict__ box, int count, int idx, float px, float py, float pz) {
-    const float gx = fmaxf(0.f, fmaxf(box[idx] - px, px - box[(size_t)3 * count + idx]));
-    const float gy = fmaxf(0.f, fmaxf(box[(size_t)count + idx] - py, py - box[(size_t)4 * count + idx]));
-    const float gz = fmaxf(0.f, fmaxf(box[(size_t)2 * count + idx] - pz, pz - box[(size_t)5 * count + idx]));
-    return gx * gx + (gy * gy + gz * gz);
-}
-
 // One wave per source point at a time, PN_PTS consecutive points per wave (lane p keeps point p's result and the wave
 // stores them together).  The 4096-point boxes are tested one per lane and visited best-first (smallest lower
 // bound first, until it exceeds the bound); inside one, its 64 leaves (64 points each) are tested one per lane, and
@@ -191,11 +184,7 @@ __device__ __forceinline__ float point_box_lb(const float* __restrict__ box, int
 // threshold, then the best distance found so far.  Each lane keeps its own (d2, original index) minimum; the wave
 // minimum in that lexicographic order is the brute-force scan's answer (lowest index on ties).
 __global__ __launch_bounds__(64 * PN_WAVES)
-void k_icp_nn_pruned(const float* __restrict__ src, int ns,
-                     const float* __restrict__ tx, const float* __restrict__ ty, const float* __restrict__ tz,
-                     const int* __restrict__ torig, int nt,
-                     const float* __restrict__ lbox, int n_leaf, const float* __restrict__ tbox, int n_top,
-                     const IcpState* __restrict__ st, float tau,
+void k_icp_nn_pruned(const float* __restrict__ src, int ns, SortedCloud c /* the target */, const IcpState* __restrict__ st, float tau,
                      float* __restrict__ out_d2, int* __restrict__ out_idx) {
     if (st->done) return;
     const int lane = threadIdx.x & 63;
@@ -209,9 +198,9 @@ void k_icp_nn_pruned(const float* __restrict__ src, int ns,
     float B = tau;           // wave-uniform; a target passes iff d2 <= B
     float bd = INFINITY;     // this lane's best
     int bo = INT_MAX;
-    for (int tb = 0; tb < n_top; tb += 64) {
+    for (int tb = 0; tb < c.n_top; tb += 64) {
         const int t = tb + lane;
-        float lbt = t < n_top ? point_box_lb(tbox, n_top, t, px, py, pz) : INFINITY;
+        float lbt = t < c.n_top ? d2_box_bound<D2::REF>(c.tbox, c.n_top, t, px, py, pz) : INFINITY;
         while (true) {
             // best-first over the remaining 4096-point boxes of this group
             float m = lbt;
@@ -221,18 +210,18 @@ void k_icp_nn_pruned(const float* __restrict__ src, int ns,
             const int tl = __ffsll((long long)__ballot(lbt == m)) - 1;   // wave-uniform lane of that box
             if (lane == tl) lbt = INFINITY;                               // visited
             const int u = (tb + tl) * 64 + lane;
-            const float lbl = u < n_leaf ? point_box_lb(lbox, n_leaf, u, px, py, pz) : INFINITY;
-            unsigned long long lmask = __ballot(u < n_leaf && lbl <= B);
+            const float lbl = u < c.n_leaf ? d2_box_bound<D2::REF>(c.lbox, c.n_leaf, u, px, py, pz) : INFINITY;
+            unsigned long long lmask = __ballot(u < c.n_leaf && lbl <= B);
             while (lmask) {
                 const int bl = __ffsll((long long)lmask) - 1;
                 lmask &= lmask - 1;
                 if (__shfl(lbl, bl, 64) > B) continue;   // the bound may have dropped since the test
                 const int j = ((tb + tl) * 64 + bl) * 64 + lane;   // arrays are padded with +inf to a multiple of 256
-                float dx = px - tx[j], dy = py - ty[j], dz = pz - tz[j];
+                float dx = px - c.sx[j], dy = py - c.sy[j], dz = pz - c.sz[j];
                 float d2 = dx * dx + (dy * dy + dz * dz);
-                const bool cand = j < nt && d2 <= B && d2 <= bd;
+                const bool cand = j < c.n && d2 <= B && d2 <= bd;
                 if (__any(cand)) {
-                    const int o = torig[j];
+                    const int o = c.orig[j];
                     const bool take = cand && (d2 < bd || o < bo);
                     bd = take ? d2 : bd;
                     bo = take ? o : bo;
@@ -1690,7 +1679,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 k_icp_nn_grid<<<(ns + 255) / 256, 256, 0, s>>>(d_src, ns, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau, b.pd2, b.pchunk);
             else if (pl.direct)
                 k_icp_nn_pruned<<<(ns + PN_WAVES * PN_PTS - 1) / (PN_WAVES * PN_PTS), 64 * PN_WAVES, 0, s>>>(
-                    d_src, ns, st.sx, st.sy, st.sz, st.orig, nt, st.lbox, st.n_leaf, st.tbox, st.n_top, b.st, tau, b.pd2, b.pchunk);
+                    d_src, ns, st, b.st, tau, b.pd2, b.pchunk);
             else
                 k_icp_nn_scan<<<grid, NN_BLOCK, 0, s>>>(d_src, ns, p.ns_pad, b.tx, b.ty, b.tz, p.n_chunks,
                                                         p.chunks_per_split, b.st, b.pd2, b.pchunk);
@@ -1922,7 +1911,7 @@ int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const floa
         SortedCloud st{};
         TDV_TRY(spatial_sort_cloud(ctx, d_tgt, nt, st));
         k_icp_nn_pruned<<<(ns + PN_WAVES * PN_PTS - 1) / (PN_WAVES * PN_PTS), 64 * PN_WAVES, 0, s>>>(
-            d_src, ns, st.sx, st.sy, st.sz, st.orig, nt, st.lbox, st.n_leaf, st.tbox, st.n_top, b.st, tau, b.pd2, b.pchunk);
+            d_src, ns, st, b.st, tau, b.pd2, b.pchunk);
     } else {
         k_aos_to_soa_pad<<<(p.nt_pad + 255) / 256, 256, 0, s>>>(d_tgt, nt, p.nt_pad, INFINITY, b.tx, b.ty, b.tz);
         k_icp_nn_scan<<<dim3(p.blocks_x, p.nsplit), NN_BLOCK, 0, s>>>(d_src, ns, p.ns_pad, b.tx, b.ty, b.tz, p.n_chunks,

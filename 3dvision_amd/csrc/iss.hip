@@ -2,11 +2,11 @@
 //
 // The host enqueues everything up front; nothing returns to it between the kernels, and the call reads back once, at the end.
 //  (i)   spatial_sort_cloud: the cloud along a Morton curve with the boxes of its leaves and groups (knn.hip), once, for both walks.
-//  (ii)  default radii only: k_iss_nn is k_outlier_mean's walk (query_wave.hpp) at k = 2 and keeps entry 1 of the row, k_iss_partial sums the
+//  (ii)  default radii only: k_iss_nn is k_outlier_mean's walk (sorted_cloud.hpp: query_wave_collect) at k = 2 and keeps entry 1 of the row, k_iss_partial sums the
 //        valid ones per workgroup of 256 points in ORIGINAL index order (fixed_tree.hpp).
 //  (iii) k_iss_state: one workgroup adds the partials in the fixed tree and one lane writes the call's state block: the resolution, the two
 //        radii, their squares and the shift of rule 3.  Every later kernel reads them from there.
-//  (iv)  k_iss_scatter: one wave per query in curve order through cluster_walk at salient_radius.  Each lane takes one point of a passing
+//  (iv)  k_iss_scatter: one wave per query in curve order through walk_in_order at salient_radius.  Each lane takes one point of a passing
 //        leaf and adds its quantised differences into nine per-lane 64-bit integer accumulators and a count; the wave sums the ten
 //        integers with DPP adds (in pieces of 22 bits: no cross-lane 64-bit traffic).  A wave takes ISS_QPW queries in turn and parks the
 //        totals of query q in lane q, so that the f64 part (covariance, Jacobi sweeps, the saliency test) runs once per wave with ISS_QPW
@@ -17,8 +17,7 @@
 // point by (iv), flag by (v).
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
-#include "query_wave.hpp"
-#include "cluster_walk.hpp"
+#include "sorted_cloud.hpp"
 #include "fixed_tree.hpp"
 #include "flag_gather.hpp"
 #include <cfloat>
@@ -58,17 +57,15 @@ __device__ __forceinline__ float iss_r2(float r) {
 
 // rule 8: nn[original index] = sqrt of the d2 of entry 1 of the query's kNN list at k = 2; NaN where the list has fewer than two entries
 __global__ __launch_bounds__(64 * ISS_NN_WAVES)
-void k_iss_nn(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int* __restrict__ orig, int n,
-              int n_leaf, const float* __restrict__ lbox, int n_top, const float* __restrict__ tbox, int k, double* __restrict__ nn) {
+void k_iss_nn(SortedCloud c, int k, double* __restrict__ nn) {
     __shared__ unsigned long long rows[ISS_NN_WAVES][128];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sp = xcd_contiguous_block(blockIdx.x, gridDim.x) * ISS_NN_WAVES + wave;
-    if (sp >= n) return;                                                                  // wave-uniform
+    if (sp >= c.n) return;                                                                // wave-uniform
     unsigned long long key[2];
-    const int wcnt = query_wave_collect<2, QW_SEED_SPAN, QW_BEST_FIRST>(sx, sy, sz, orig, n, n_leaf, lbox, n_top, tbox, sp, nullptr, 0, INFINITY, 1,
-                                                                        k, nullptr, nullptr, 0, rows[wave], lane, key);
+    const int wcnt = query_wave_collect<2, QW_SEED_SPAN, QW_BEST_FIRST, false>(c, sp, INFINITY, 1, k, rows[wave], lane, key);
     const unsigned d2 = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(key[0] >> 32), 1);   // lane order is list order
-    if (lane == 0) nn[orig[sp]] = min(k, wcnt) >= 2 ? sqrt((double)__uint_as_float(d2)) : tree_nan();
+    if (lane == 0) nn[c.orig[sp]] = min(k, wcnt) >= 2 ? sqrt((double)__uint_as_float(d2)) : tree_nan();
 }
 
 // part[b], cnt[b] = the sum and the number of the valid nn over points [256 b, 256 b + 256)
@@ -134,7 +131,7 @@ __device__ __forceinline__ void iss_order(double& a, double& b) {      // a >= b
 
 // saliency[original index] (rules 2-6) for every point; support and the three eigenvalues where asked for
 __global__ __launch_bounds__(64 * ISS_WAVES)
-void k_iss_scatter(ClusterCloud c, const IssState* __restrict__ st, int min_neighbors, double gamma_21, double gamma_32,
+void k_iss_scatter(SortedCloud c, const IssState* __restrict__ st, int min_neighbors, double gamma_21, double gamma_32,
                    double* __restrict__ saliency, double* __restrict__ eig, int* __restrict__ support) {
     const int lane = threadIdx.x & 63;
     const int base = (xcd_contiguous_block(blockIdx.x, gridDim.x) * ISS_WAVES + (threadIdx.x >> 6)) * ISS_QPW;   // curve order
@@ -150,7 +147,7 @@ void k_iss_scatter(ClusterCloud c, const IssState* __restrict__ st, int min_neig
         unsigned long long a[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         int cnt = 0;
         // a query that is not its own neighbour (a NaN or infinite coordinate, a NaN radius) has none: as in k_cluster_count
-        if (cluster_d2(qx, qy, qz, qx, qy, qz) <= r2) cluster_walk(c, qx, qy, qz, r2, lane, [&](int leaf) {
+        if (d2_point<D2::DBSCAN>(qx, qy, qz, qx, qy, qz) <= r2) walk_in_order<D2::DBSCAN>(c, qx, qy, qz, r2, lane, [&](int leaf) {
             const int p = leaf * 64 + lane;                  // the arrays are padded to a multiple of 256
             const float dx = c.sx[p] - qx, dy = c.sy[p] - qy, dz = c.sz[p] - qz;
             if (p < c.n && (dx * dx + dy * dy) + dz * dz <= r2) {
@@ -201,7 +198,7 @@ void k_iss_scatter(ClusterCloud c, const IssState* __restrict__ st, int min_neig
 
 // rule 7: flag / mask[original index] = keypoint
 __global__ __launch_bounds__(64 * ISS_WAVES)
-void k_iss_nms(ClusterCloud c, const IssState* __restrict__ st, int min_neighbors, const double* __restrict__ saliency, int* __restrict__ flag,
+void k_iss_nms(SortedCloud c, const IssState* __restrict__ st, int min_neighbors, const double* __restrict__ saliency, int* __restrict__ flag,
                uint8_t* __restrict__ mask) {
     const int lane = threadIdx.x & 63;
     const int sp = xcd_contiguous_block(blockIdx.x, gridDim.x) * ISS_WAVES + (threadIdx.x >> 6);
@@ -214,9 +211,9 @@ void k_iss_nms(ClusterCloud c, const IssState* __restrict__ st, int min_neighbor
         const float qx = c.sx[sp], qy = c.sy[sp], qz = c.sz[sp];
         int cnt = 0;
         bool beaten = false;
-        if (cluster_d2(qx, qy, qz, qx, qy, qz) <= r2) cluster_walk(c, qx, qy, qz, r2, lane, [&](int leaf) {
+        if (d2_point<D2::DBSCAN>(qx, qy, qz, qx, qy, qz) <= r2) walk_in_order<D2::DBSCAN>(c, qx, qy, qz, r2, lane, [&](int leaf) {
             const int p = leaf * 64 + lane;
-            const bool nb = p < c.n && cluster_d2(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz) <= r2;
+            const bool nb = p < c.n && d2_point<D2::DBSCAN>(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz) <= r2;
             const double sj = nb ? saliency[c.orig[p]] : 0.0;
             cnt += __popcll(__ballot(nb));
             beaten = __ballot(sj > s) != 0;
@@ -292,15 +289,13 @@ int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& p
         TDV_TRY(ws_alloc(ctx, (size_t)n, &nn));
         TDV_TRY(ws_alloc(ctx, (size_t)nb, &part));
         TDV_TRY(ws_alloc(ctx, (size_t)nb, &cnt));
-        k_iss_nn<<<(n + ISS_NN_WAVES - 1) / ISS_NN_WAVES, 64 * ISS_NN_WAVES, 0, s>>>(sc.sx, sc.sy, sc.sz, sc.orig, n, sc.n_leaf, sc.lbox, sc.n_top, sc.tbox,
-                                                                                    std::min(2, n), nn);
+        k_iss_nn<<<(n + ISS_NN_WAVES - 1) / ISS_NN_WAVES, 64 * ISS_NN_WAVES, 0, s>>>(sc, std::min(2, n), nn);
         k_iss_partial<<<nb, 256, 0, s>>>(nn, n, part, cnt);
     }
     k_iss_state<<<1, 256, 0, s>>>(st, part, cnt, defaults ? nb : 0, defaults ? 1 : 0, prm.salient_radius, prm.non_max_radius);
-    const ClusterCloud c{sc.sx, sc.sy, sc.sz, sc.orig, sc.lbox, sc.tbox, n, sc.n_leaf, sc.n_top};
     const int per_wg = ISS_WAVES * ISS_QPW;
-    k_iss_scatter<<<(n + per_wg - 1) / per_wg, 64 * ISS_WAVES, 0, s>>>(c, st, prm.min_neighbors, prm.gamma_21, prm.gamma_32, d.saliency, d.eig, d.support);
-    k_iss_nms<<<(n + ISS_WAVES - 1) / ISS_WAVES, 64 * ISS_WAVES, 0, s>>>(c, st, prm.min_neighbors, d.saliency, flag, d.mask);
+    k_iss_scatter<<<(n + per_wg - 1) / per_wg, 64 * ISS_WAVES, 0, s>>>(sc, st, prm.min_neighbors, prm.gamma_21, prm.gamma_32, d.saliency, d.eig, d.support);
+    k_iss_nms<<<(n + ISS_WAVES - 1) / ISS_WAVES, 64 * ISS_WAVES, 0, s>>>(sc, st, prm.min_neighbors, d.saliency, flag, d.mask);
     k_iss_count<<<nb, 256, 0, s>>>(d.support, d.saliency, n, prm.min_neighbors, st);
     TDV_CHECK_LAUNCH(ctx);
     TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, &st->n_keypoints));

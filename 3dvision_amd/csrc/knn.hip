@@ -27,7 +27,7 @@
 #include "tdv_internal.hpp"
 #include "libm_f32.hpp"
 #include "device_linalg.hpp"
-#include "query_wave.hpp"
+#include "sorted_cloud.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -155,19 +155,13 @@ void k_top_boxes(const float* __restrict__ lb, int n_leaf, int n_top, float* __r
     else if (lane < 6) tb[(size_t)lane * n_top + u] = lane == 3 ? mx[0] : (lane == 4 ? mx[1] : mx[2]);
 }
 
-// ------------------------------------------------------------------ one wave per query: the walk itself is query_wave.hpp
-// lists[original index * stride + r] = the first min(k, found) targets in (d2, idx) order with d2 <= bound
-// (bound = bound[slot] if given, else bound0), cnt_out[original index] = their number.  Requires k <= 64*R - 64.
+// ------------------------------------------------------------------ one wave per query: the walk itself is sorted_cloud.hpp
+// lists[original index * stride + r] = the first min(k, found) targets in (d2, id) order with d2 <= bound0, cnt_out[original index] =
+// their number, for the query at sorted position qsel[slot] (qsel == nullptr: slot).  Requires k <= 64*R - 64.
 template <int R, int SEED_SPAN, bool BEST_FIRST>
 __global__ __launch_bounds__(64 * QW_WAVES)
-void k_query_wave(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz,
-                  const int* __restrict__ orig, int n, int n_leaf, const float* __restrict__ lbox, int n_top, const float* __restrict__ tbox,
-                  const int* __restrict__ qsel, int nqq, const float* __restrict__ bound, float bound0, int seed_own,
-                  int k, int stride, int* __restrict__ lists, int* __restrict__ cnt_out,
-                  const int* __restrict__ okey /* sorted position -> tie-break id (null: orig) */,
-                  const int* __restrict__ key2idx /* tie-break id -> array index written to the lists (null: the id itself) */,
-                  const int* __restrict__ inst_leaf = nullptr /* several clouds in one array: cloud b owns leaves [inst_leaf[b], inst_leaf[b + 1]) */,
-                  int n_inst = 0) {
+void k_query_wave(SortedCloud c, const int* __restrict__ qsel, int nqq, float bound0, int seed_own, int k, int stride,
+                  int* __restrict__ lists, int* __restrict__ cnt_out) {
     constexpr int ROW = 64 * R;
     __shared__ unsigned long long rows[QW_WAVES][ROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -175,16 +169,15 @@ void k_query_wave(const float* __restrict__ sx, const float* __restrict__ sy, co
     if (slot >= nqq) return;   // wave-uniform; no block-level barrier below
     const int sp = qsel ? qsel[slot] : slot;
     unsigned long long key[R];
-    const int wcnt = query_wave_collect<R, SEED_SPAN, BEST_FIRST>(sx, sy, sz, orig, n, n_leaf, lbox, n_top, tbox, sp, bound, slot, bound0, seed_own,
-                                                                  k, okey, inst_leaf, n_inst, rows[wave], lane, key);
-    const int i0 = orig[sp];
-    const int c = min(k, wcnt);
+    const int wcnt = query_wave_collect<R, SEED_SPAN, BEST_FIRST>(c, sp, bound0, seed_own, k, rows[wave], lane, key);
+    const int i0 = c.orig[sp];
+    const int cnt = min(k, wcnt);
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         const int e = r * 64 + lane;
-        if (e < c) lists[(size_t)i0 * stride + e] = key2idx ? key2idx[(int)(unsigned)key[r]] : (int)(unsigned)key[r];   // a row per query: coalesced
+        if (e < cnt) lists[(size_t)i0 * stride + e] = c.key2idx ? c.key2idx[(int)(unsigned)key[r]] : (int)(unsigned)key[r];   // a row per query: coalesced
     }
-    if (lane == 0) cnt_out[i0] = c;
+    if (lane == 0) cnt_out[i0] = cnt;
 }
 
 // ------------------------------------------------------------------ normals (registration.cpp:105-130)
@@ -243,14 +236,15 @@ void k_normals_from_lists(const float* __restrict__ xyz, int n, const int* __res
     normals[3 * (size_t)i] = nx; normals[3 * (size_t)i + 1] = ny; normals[3 * (size_t)i + 2] = nz;
 }
 
-// deficient[sp] = 1 if the radius list of the point at sorted position sp has fewer than k entries
-__global__ void k_flag_deficient(const int* __restrict__ orig, const int* __restrict__ cntA, int n, int k, int* __restrict__ flag) {
-    int sp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (sp < n) flag[sp] = cntA[orig[sp]] < k ? 1 : 0;
+// flag[t] = 1 if the radius list of point order[t] has fewer than k entries
+__global__ void k_flag_deficient(const int* __restrict__ order, const int* __restrict__ cntA, int n, int k, int* __restrict__ flag) {
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n) flag[t] = cntA[order[t]] < k ? 1 : 0;
 }
-__global__ void k_compact_flagged(const int* __restrict__ flag, const int* __restrict__ pos, int n, int* __restrict__ qsel) {
-    int sp = blockIdx.x * blockDim.x + threadIdx.x;
-    if (sp < n && flag[sp]) qsel[pos[sp]] = sp;   // ascending sorted positions: the subset stays spatially coherent
+// qsel = the sorted positions of the flagged points, in the order of t: position qpos[t] (qpos == nullptr: t itself)
+__global__ void k_compact_flagged(const int* __restrict__ flag, const int* __restrict__ pos, const int* __restrict__ qpos, int n, int* __restrict__ qsel) {
+    int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t < n && flag[t]) qsel[pos[t]] = qpos ? qpos[t] : t;   // ascending sorted positions: the subset stays spatially coherent
 }
 
 // ------------------------------------------------------------------ FPFH (registration.cpp:133-201)
@@ -512,29 +506,31 @@ void k_fpfh_pairs(const float* __restrict__ xyz, int n, const int* __restrict__ 
 
 namespace {
 
-struct ScanPlan { int n_pad, nt_pad, n_chunks, blocks_x; };
-
-ScanPlan make_scan_plan(int n) {
-    ScanPlan p;
-    p.n_pad = (int)align_up((size_t)n, KN_BLOCK);
-    p.nt_pad = (int)align_up((size_t)n, 16);
-    p.n_chunks = p.nt_pad / 16;          // 16-target chunks
-    p.blocks_x = p.n_pad / KN_BLOCK;
-    return p;
+// The boxes of the n_leaf 64-point leaves of a cloud whose coordinates are laid out, and of its 4096-point groups of 64 leaves (the
+// exact pruning of the searches)
+int build_boxes(tdv_ctx* ctx, SortedCloud& sc, int n_leaf) {
+    float *lbox, *tbox;
+    sc.n_leaf = n_leaf;
+    sc.n_top = (n_leaf + 63) / 64;
+    TDV_TRY(ws_alloc(ctx, (size_t)6 * sc.n_leaf, &lbox));
+    TDV_TRY(ws_alloc(ctx, (size_t)6 * sc.n_top, &tbox));
+    k_leaf_boxes<<<(sc.n_leaf + 3) / 4, 256, 0, ctx->stream>>>(sc.sx, sc.sy, sc.sz, sc.n_leaf, lbox);
+    k_top_boxes<<<sc.n_top, 64, 0, ctx->stream>>>(lbox, sc.n_leaf, sc.n_top, tbox);
+    TDV_CHECK_LAUNCH(ctx);
+    sc.lbox = lbox; sc.tbox = tbox;
+    return TDV_OK;
 }
 
-// okey / key2idx (optional): ties in (d2, id) order are broken by okey[position] instead of the array index, and the lists
-// receive key2idx[id] — the batch runs these stages on the voxel cloud in first-occurrence order (spatially coherent: the
-// gathers of the estimators stay local) while ordering every list as the reference's container order would.
-struct Sorted { float *sx, *sy, *sz; int* orig; float *lbox, *tbox; int n_leaf, n_top; const int* okey = nullptr; const int* key2idx = nullptr; };
+}  // namespace
 
-// Morton sort of the cloud: sorted SoA coordinates (padded with +inf) and the original index of each position
-int spatial_sort(tdv_ctx* ctx, const float* d_xyz, int n, const ScanPlan& p, Sorted& so) {
+// Morton sort of the cloud: sorted SoA coordinates (padded with +inf to a multiple of 256: the lists' rows and the estimators' grids
+// are sized by it) and the original index of each position
+int spatial_sort_cloud(tdv_ctx* ctx, const float* d_xyz, int n, SortedCloud& out) {
     hipStream_t s = ctx->stream;
-    const int pad = std::max(p.n_pad, (int)align_up((size_t)p.nt_pad, 16));   // multiple of 256 >= n: covers 8- and 16-target chunks
-    float* soa; float *part, *bbox; int *bucket_of, *hist, *cursor, *start, *d_total;
+    const int pad = (int)align_up((size_t)n, KN_BLOCK);
+    float *soa, *part, *bbox; int *orig, *bucket_of, *hist, *cursor, *start, *d_total;
     TDV_TRY(ws_alloc(ctx, (size_t)3 * pad, &soa));
-    TDV_TRY(ws_alloc(ctx, (size_t)pad, &so.orig));
+    TDV_TRY(ws_alloc(ctx, (size_t)pad, &orig));
     TDV_TRY(ws_alloc(ctx, (size_t)n, &bucket_of));
     // a few buckets per point for a surface sample (most cells of the grid are empty)
     static const int per_point = study_env("TDV_MORTON_BUCKETS_PER_POINT") ? atoi(study_env("TDV_MORTON_BUCKETS_PER_POINT")) : 8;
@@ -548,49 +544,27 @@ int spatial_sort(tdv_ctx* ctx, const float* d_xyz, int n, const ScanPlan& p, Sor
     const int bblocks = std::min(1024, (n + 255) / 256);
     TDV_TRY(ws_alloc(ctx, (size_t)bblocks * 6, &part));
     TDV_TRY(ws_alloc(ctx, 6, &bbox));
-    so.sx = soa; so.sy = soa + pad; so.sz = soa + 2 * (size_t)pad;
+    float *sx = soa, *sy = soa + pad, *sz = soa + 2 * (size_t)pad;
     TDV_HIP(ctx, hipMemsetAsync(hist, 0, (size_t)2 * nbuckets * 4, s));
     k_bbox_partial<<<bblocks, 256, 0, s>>>(d_xyz, n, part);
     k_bbox_final<<<1, 64, 0, s>>>(part, bblocks, bbox);
     k_morton_hist<<<(n + 255) / 256, 256, 0, s>>>(d_xyz, n, bbox, bits, bucket_of, hist);
     TDV_TRY(exclusive_scan_dev(ctx, hist, nbuckets, start, d_total));
-    k_morton_scatter<<<(pad + 255) / 256, 256, 0, s>>>(d_xyz, n, pad, bucket_of, start, cursor, so.sx, so.sy, so.sz, so.orig);
-    // bounding boxes of the 64-point leaves and of the 4096-point groups of 64 leaves (exact pruning of the searches)
-    so.n_leaf = (int)(align_up((size_t)n, 64) / 64);
-    so.n_top = (so.n_leaf + 63) / 64;
-    TDV_TRY(ws_alloc(ctx, (size_t)6 * so.n_leaf, &so.lbox));
-    TDV_TRY(ws_alloc(ctx, (size_t)6 * so.n_top, &so.tbox));
-    k_leaf_boxes<<<(so.n_leaf + 3) / 4, 256, 0, s>>>(so.sx, so.sy, so.sz, so.n_leaf, so.lbox);
-    k_top_boxes<<<so.n_top, 64, 0, s>>>(so.lbox, so.n_leaf, so.n_top, so.tbox);
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-
-}  // namespace
-
-int spatial_sort_cloud(tdv_ctx* ctx, const float* d_xyz, int n, SortedCloud& out) {
-    const ScanPlan p = make_scan_plan(n);
-    Sorted so;
-    TDV_TRY(spatial_sort(ctx, d_xyz, n, p, so));
-    out.sx = so.sx; out.sy = so.sy; out.sz = so.sz; out.orig = so.orig; out.lbox = so.lbox; out.tbox = so.tbox;
-    out.n = n; out.pad = std::max(p.n_pad, (int)align_up((size_t)p.nt_pad, 16));
-    out.n_leaf = so.n_leaf; out.n_top = so.n_top;
-    return TDV_OK;
+    k_morton_scatter<<<(pad + 255) / 256, 256, 0, s>>>(d_xyz, n, pad, bucket_of, start, cursor, sx, sy, sz, orig);
+    out = SortedCloud{};
+    out.sx = sx; out.sy = sy; out.sz = sz; out.orig = orig; out.n = n; out.pad = pad;
+    return build_boxes(ctx, out, (int)(align_up((size_t)n, 64) / 64));
 }
 
 namespace {
 
-// One k_query_wave launch: lists[original index * k + r] / cnt[original index] for all n queries
-// (qsel == nullptr) or for the nsel sorted positions in qsel (device).
-int query_to_lists(tdv_ctx* ctx, const Sorted& so, int n, const ScanPlan& p, int k, const float* bound, float bound0, int seed_own,
-                   int timer, const int* qsel, int nsel, int* lists, int* cnt) {
-    const int nqq = qsel ? nsel : n;
-    if (nqq <= 0) return TDV_OK;
-    hipStream_t s = ctx->stream;
-    const unsigned grid = (unsigned)((nqq + QW_WAVES - 1) / QW_WAVES);
+// The one launcher of k_query_wave: lists[original index * k + r] / cnt[original index] for the nq queries at the sorted positions
+// qsel (device; nullptr: positions 0 .. nq - 1)
+int query_to_lists(tdv_ctx* ctx, const SortedCloud& sc, int k, float bound0, int seed_own, int timer, const int* qsel, int nq, int* lists, int* cnt) {
+    if (nq <= 0) return TDV_OK;
+    const unsigned grid = (unsigned)((nq + QW_WAVES - 1) / QW_WAVES);
     ScopedTimer tm(ctx, timer);
-#define TDV_QW(RR) k_query_wave<RR, QW_SEED_SPAN, QW_BEST_FIRST><<<grid, 64 * QW_WAVES, 0, s>>>(so.sx, so.sy, so.sz, so.orig, n, so.n_leaf, so.lbox, so.n_top, so.tbox, \
-                                                            qsel, nqq, bound, bound0, seed_own, k, k, lists, cnt, so.okey, so.key2idx)
+#define TDV_QW(RR) k_query_wave<RR, QW_SEED_SPAN, QW_BEST_FIRST><<<grid, 64 * QW_WAVES, 0, ctx->stream>>>(sc, qsel, nq, bound0, seed_own, k, k, lists, cnt)
     if (k <= 64) TDV_QW(2);
     else if (k <= 192) TDV_QW(4);
     else if (k <= 448) TDV_QW(8);
@@ -601,14 +575,14 @@ int query_to_lists(tdv_ctx* ctx, const Sorted& so, int n, const ScanPlan& p, int
 }
 
 // radius search: every target with d2 <= r2, the first k in (d2, idx) order
-int radius_to_lists(tdv_ctx* ctx, const Sorted& so, int n, const ScanPlan& p, int k, float r2, int* lists, int* cnt) {
-    return query_to_lists(ctx, so, n, p, k, nullptr, r2, 0, TDV_TIMER_RADIUS, nullptr, 0, lists, cnt);
+int radius_to_lists(tdv_ctx* ctx, const SortedCloud& sc, int k, float r2, const int* qsel, int nq, int* lists, int* cnt) {
+    return query_to_lists(ctx, sc, k, r2, 0, TDV_TIMER_RADIUS, qsel, nq, lists, cnt);
 }
 
-// exact kNN lists of all queries (qsel == nullptr) or of the subset qsel: unbounded start from the query's own run
-// (an initial bound from a 768-point window in a separate kernel was measured slower at every size)
-int knn_to_lists(tdv_ctx* ctx, const Sorted& so, int n, const ScanPlan& p, int k, const int* qsel, int nsel, int* lists, int* cnt) {
-    return query_to_lists(ctx, so, n, p, k, nullptr, INFINITY, 1, TDV_TIMER_KNN, qsel, nsel, lists, cnt);
+// exact kNN lists: unbounded start from the query's own run (an initial bound from a 768-point window in a separate kernel was
+// measured slower at every size)
+int knn_to_lists(tdv_ctx* ctx, const SortedCloud& sc, int k, const int* qsel, int nq, int* lists, int* cnt) {
+    return query_to_lists(ctx, sc, k, INFINITY, 1, TDV_TIMER_KNN, qsel, nq, lists, cnt);
 }
 
 }  // namespace
@@ -617,19 +591,18 @@ int estimate_normals_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float* 
     if (!ctx || n < 0 || k <= 0 || k > 255 || (n > 0 && (!d_xyz || !d_normals))) return TDV_ERR_BAD_ARG;
     if (n == 0) return TDV_OK;
     const int kk = std::min(k, n);  // std::min(k, dists.size()), registration.cpp:74
-    const ScanPlan p = make_scan_plan(n);
-    Sorted so; int *lists, *cnt;
-    TDV_TRY(spatial_sort(ctx, d_xyz, n, p, so));
-    TDV_TRY(ws_alloc(ctx, (size_t)kk * p.n_pad, &lists));
-    TDV_TRY(ws_alloc(ctx, (size_t)p.n_pad, &cnt));
-    TDV_TRY(knn_to_lists(ctx, so, n, p, kk, nullptr, 0, lists, cnt));
-    k_normals_from_lists<<<p.blocks_x, KN_BLOCK, 0, ctx->stream>>>(d_xyz, n, so.orig, kk, nullptr, 0, nullptr, lists, kk, cnt, d_normals, d_knn, k);
+    SortedCloud sc; int *lists, *cnt;
+    TDV_TRY(spatial_sort_cloud(ctx, d_xyz, n, sc));
+    TDV_TRY(ws_alloc(ctx, (size_t)kk * sc.pad, &lists));
+    TDV_TRY(ws_alloc(ctx, (size_t)sc.pad, &cnt));
+    TDV_TRY(knn_to_lists(ctx, sc, kk, nullptr, n, lists, cnt));
+    k_normals_from_lists<<<sc.pad / KN_BLOCK, KN_BLOCK, 0, ctx->stream>>>(d_xyz, n, sc.orig, kk, nullptr, 0, nullptr, lists, kk, cnt, d_normals, d_knn, k);
     TDV_CHECK_LAUNCH(ctx);
     return TDV_OK;
 }
 
 namespace {
-int fpfh_from_lists(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, int n, const ScanPlan& p, const int* order, const int* nbr, const int* cnt,
+int fpfh_from_lists(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, int n, const int* order, const int* nbr, const int* cnt,
                     float* d_desc, int* d_nbr, int* d_nbr_cnt) {
     if ((size_t)n * 33 > 0xffffffffull) return TDV_ERR_BAD_ARG;   // k_fpfh addresses SPFH rows with 32-bit float offsets (130 M points)
     float* spfh;
@@ -657,24 +630,61 @@ int compute_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, i
     if (!ctx || n < 0 || (n > 0 && (!d_xyz || !d_normals || !d_desc))) return TDV_ERR_BAD_ARG;
     if (n == 0) return TDV_OK;
     const float r2 = radius * radius;  // registration.cpp:89
-    const ScanPlan p = make_scan_plan(n);
-    Sorted so; int *nbr, *cnt;
-    TDV_TRY(spatial_sort(ctx, d_xyz, n, p, so));
-    TDV_TRY(ws_alloc(ctx, (size_t)FP_MAXNN * p.n_pad, &nbr));
-    TDV_TRY(ws_alloc(ctx, (size_t)p.n_pad, &cnt));
-    TDV_TRY(radius_to_lists(ctx, so, n, p, FP_MAXNN, r2, nbr, cnt));
-    return fpfh_from_lists(ctx, d_xyz, d_normals, n, p, so.orig, nbr, cnt, d_desc, d_nbr, d_nbr_cnt);
+    SortedCloud sc; int *nbr, *cnt;
+    TDV_TRY(spatial_sort_cloud(ctx, d_xyz, n, sc));
+    TDV_TRY(ws_alloc(ctx, (size_t)FP_MAXNN * sc.pad, &nbr));
+    TDV_TRY(ws_alloc(ctx, (size_t)sc.pad, &cnt));
+    TDV_TRY(radius_to_lists(ctx, sc, FP_MAXNN, r2, nullptr, n, nbr, cnt));
+    return fpfh_from_lists(ctx, d_xyz, d_normals, n, sc.orig, nbr, cnt, d_desc, d_nbr, d_nbr_cnt);
 }
 
-// estimateNormals(k) followed by computeFPFH(radius) on the same cloud (src/pipeline.cpp:93-95), sharing one
-// spatial sort and ONE full scan: the radius lists are sorted by (d2, idx), so wherever a point has >= k
-// neighbours in radius its k nearest neighbours are the first k entries; only the deficient points (isolated
-// points, silhouette edges) go through a kNN scan, as a subset.  Results are identical to the two separate calls.
+namespace {
+
+// estimateNormals(k) followed by computeFPFH(radius) over the points of sc (src/pipeline.cpp:93-95), sharing ONE full scan: the radius
+// lists are sorted by (d2, id), so wherever a point has >= k neighbours in radius its k nearest neighbours are the first k entries; only
+// the deficient points (isolated points, silhouette edges) go through a kNN scan, as a subset.  Results are identical to the two
+// separate calls.  The n points are visited in the order order[t] (point indices: spatially coherent), and point order[t] sits at
+// sorted position qpos[t] (nullptr: t itself).  Requires k <= FP_MAXNN.
+int lists_normals_fpfh(tdv_ctx* ctx, const float* d_xyz, int n, const SortedCloud& sc, const int* qpos, const int* order, int k, float r2,
+                       float* d_normals, float* d_desc) {
+    hipStream_t s = ctx->stream;
+    const int rows = (int)align_up((size_t)n, KN_BLOCK);   // list rows and the grid of k_normals_from_lists: whole workgroups
+    int *nbr, *cnt, *flag, *pos, *qsel, *d_total, *listsK, *cntK;
+    TDV_TRY(ws_alloc(ctx, (size_t)FP_MAXNN * rows, &nbr));
+    TDV_TRY(ws_alloc(ctx, (size_t)rows, &cnt));
+    TDV_TRY(ws_alloc(ctx, (size_t)n, &flag));
+    TDV_TRY(ws_alloc(ctx, (size_t)n, &pos));
+    TDV_TRY(ws_alloc(ctx, (size_t)n, &qsel));
+    TDV_TRY(ws_alloc(ctx, 1, &d_total));
+    TDV_TRY(ws_alloc(ctx, (size_t)k * rows, &listsK));
+    TDV_TRY(ws_alloc(ctx, (size_t)rows, &cntK));
+    TDV_TRY(radius_to_lists(ctx, sc, FP_MAXNN, r2, qpos, n, nbr, cnt));                                 // radius lists of every point
+    k_flag_deficient<<<(n + 255) / 256, 256, 0, s>>>(order, cnt, n, k, flag);
+    TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, d_total));
+    k_compact_flagged<<<(n + 255) / 256, 256, 0, s>>>(flag, pos, qpos, n, qsel);
+    TDV_CHECK_LAUNCH(ctx);
+    TDV_TRY(pin_reserve(ctx, 64));
+    int* h_total = reinterpret_cast<int*>(ctx->pin);
+    TDV_HIP(ctx, hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));
+    TDV_HIP(ctx, hipStreamSynchronize(s));
+    const int nsel = *h_total;
+    if (study_env("TDV_DEBUG")) fprintf(stderr, "[tdv] normals_fpfh: n=%d deficient=%d (k=%d)\n", n, nsel, k);
+    TDV_TRY(knn_to_lists(ctx, sc, k, qsel, nsel, listsK, cntK));                                        // kNN lists of the points with fewer than k in radius
+    k_normals_from_lists<<<rows / KN_BLOCK, KN_BLOCK, 0, s>>>(d_xyz, n, order, k, nbr, FP_MAXNN, cnt, listsK, k, cntK, d_normals, nullptr, 0);
+    TDV_CHECK_LAUNCH(ctx);
+    return fpfh_from_lists(ctx, d_xyz, d_normals, n, order, nbr, cnt, d_desc, nullptr, nullptr);
+}
+
+}  // namespace
+
 __global__ void k_gather_ids(const int* __restrict__ orig, const int* __restrict__ ids, int n, int n_pad, int* __restrict__ okey) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p < n_pad) okey[p] = p < n ? ids[orig[p]] : INT_MAX;
 }
 
+// One cloud.  d_tie_ids / d_tie_ids_inv (optional, both or neither): ties in (d2, id) order are broken by d_tie_ids[point] instead of
+// the point's index, and the lists receive d_tie_ids_inv[id] - the batch runs these stages on the voxel cloud in first-occurrence order
+// (spatially coherent: the gathers of the estimators stay local) while ordering every list as the reference's container order would.
 int normals_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float radius, float* d_normals, float* d_desc,
                      const int* d_tie_ids, const int* d_tie_ids_inv) {
     if (!ctx || n < 0 || k <= 0 || k > 255 || (n > 0 && (!d_xyz || !d_normals || !d_desc))) return TDV_ERR_BAD_ARG;
@@ -686,41 +696,15 @@ int normals_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float radiu
         TDV_TRY(estimate_normals_dev(ctx, d_xyz, n, k, d_normals, nullptr));
         return compute_fpfh_dev(ctx, d_xyz, d_normals, n, radius, d_desc, nullptr, nullptr);
     }
-    const float r2 = radius * radius;
-    const ScanPlan p = make_scan_plan(n);
-    hipStream_t s = ctx->stream;
-    Sorted so; int *nbr, *cnt, *flag, *pos, *qsel, *d_total, *listsK, *cntK;
-    TDV_TRY(spatial_sort(ctx, d_xyz, n, p, so));
+    SortedCloud sc;
+    TDV_TRY(spatial_sort_cloud(ctx, d_xyz, n, sc));
     if (d_tie_ids) {
-        const int pad = std::max(p.n_pad, (int)align_up((size_t)p.nt_pad, 16));
         int* okey;
-        TDV_TRY(ws_alloc(ctx, (size_t)pad, &okey));
-        k_gather_ids<<<(pad + 255) / 256, 256, 0, s>>>(so.orig, d_tie_ids, n, pad, okey);
-        so.okey = okey; so.key2idx = d_tie_ids_inv;
+        TDV_TRY(ws_alloc(ctx, (size_t)sc.pad, &okey));
+        k_gather_ids<<<(sc.pad + 255) / 256, 256, 0, ctx->stream>>>(sc.orig, d_tie_ids, n, sc.pad, okey);
+        sc.okey = okey; sc.key2idx = d_tie_ids_inv;
     }
-    TDV_TRY(ws_alloc(ctx, (size_t)FP_MAXNN * p.n_pad, &nbr));
-    TDV_TRY(ws_alloc(ctx, (size_t)p.n_pad, &cnt));
-    TDV_TRY(radius_to_lists(ctx, so, n, p, FP_MAXNN, r2, nbr, cnt));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &flag));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &pos));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &qsel));
-    TDV_TRY(ws_alloc(ctx, 1, &d_total));
-    TDV_TRY(ws_alloc(ctx, (size_t)kk * p.n_pad, &listsK));
-    TDV_TRY(ws_alloc(ctx, (size_t)p.n_pad, &cntK));
-    k_flag_deficient<<<(n + 255) / 256, 256, 0, s>>>(so.orig, cnt, n, kk, flag);
-    TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, d_total));
-    k_compact_flagged<<<(n + 255) / 256, 256, 0, s>>>(flag, pos, n, qsel);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(pin_reserve(ctx, 64));
-    int* h_total = reinterpret_cast<int*>(ctx->pin);
-    TDV_HIP(ctx, hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
-    const int nsel = *h_total;
-    if (study_env("TDV_DEBUG")) fprintf(stderr, "[tdv] normals_fpfh: n=%d deficient=%d (k=%d)\n", n, nsel, kk);
-    TDV_TRY(knn_to_lists(ctx, so, n, p, kk, qsel, nsel, listsK, cntK));
-    k_normals_from_lists<<<p.blocks_x, KN_BLOCK, 0, s>>>(d_xyz, n, so.orig, kk, nbr, FP_MAXNN, cnt, listsK, kk, cntK, d_normals, nullptr, 0);
-    TDV_CHECK_LAUNCH(ctx);
-    return fpfh_from_lists(ctx, d_xyz, d_normals, n, p, so.orig, nbr, cnt, d_desc, nullptr, nullptr);
+    return lists_normals_fpfh(ctx, d_xyz, n, sc, nullptr, sc.orig, kk, radius * radius, d_normals, d_desc);
 }
 
 
@@ -749,14 +733,6 @@ __global__ void k_batch_layout(const float* __restrict__ xyz, const int* __restr
         sx[pos] = q; sy[pos] = q; sz[pos] = q; orig[pos] = INT_MAX;
         if (okey) okey[pos] = INT_MAX;
     }
-}
-__global__ void k_batch_flag_deficient(const int* __restrict__ cnt, int n, int k, int* __restrict__ flag) {
-    const int P = blockIdx.x * blockDim.x + threadIdx.x;
-    if (P < n) flag[P] = cnt[P] < k ? 1 : 0;
-}
-__global__ void k_batch_compact_flagged(const int* __restrict__ flag, const int* __restrict__ pos, const int* __restrict__ pos_of_point, int n, int* __restrict__ qsel) {
-    const int P = blockIdx.x * blockDim.x + threadIdx.x;
-    if (P < n && flag[P]) qsel[pos[P]] = pos_of_point[P];
 }
 
 // d_xyz: all clouds back to back (cloud b = points [h_voff[b], h_voff[b + 1]), every cloud with at least k points); d_voff: the
@@ -788,51 +764,15 @@ int normals_fpfh_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_voff, 
     TDV_TRY(ws_alloc(ctx, (size_t)n_clouds + 1, &d_leaf));
     TDV_HIP(ctx, hipMemcpyAsync(d_ppos, ppos.data(), ((size_t)n_clouds + 1) * 4, hipMemcpyHostToDevice, s));
     TDV_HIP(ctx, hipMemcpyAsync(d_leaf, leaf.data(), ((size_t)n_clouds + 1) * 4, hipMemcpyHostToDevice, s));
-    Sorted so;
-    so.sx = soa; so.sy = soa + total_pos; so.sz = soa + 2 * (size_t)total_pos; so.orig = orig;
-    k_batch_layout<<<(total_pos + 255) / 256, 256, 0, s>>>(d_xyz, d_voff, d_ppos, n_clouds, total_pos, d_tie_ids, so.sx, so.sy, so.sz, orig, okey, pos_of_point, iota);
-    so.n_leaf = total_pos / 64; so.n_top = (so.n_leaf + 63) / 64;
-    TDV_TRY(ws_alloc(ctx, (size_t)6 * so.n_leaf, &so.lbox));
-    TDV_TRY(ws_alloc(ctx, (size_t)6 * so.n_top, &so.tbox));
-    k_leaf_boxes<<<(so.n_leaf + 3) / 4, 256, 0, s>>>(so.sx, so.sy, so.sz, so.n_leaf, so.lbox);
-    k_top_boxes<<<so.n_top, 64, 0, s>>>(so.lbox, so.n_leaf, so.n_top, so.tbox);
-    TDV_CHECK_LAUNCH(ctx);
-    if (d_tie_ids) { so.okey = okey; so.key2idx = d_tie_ids_inv; }
-    const int n_pad = (int)align_up((size_t)n, KN_BLOCK);
-    int *nbr, *cnt, *flag, *pos, *qsel, *d_total, *listsK, *cntK;
-    TDV_TRY(ws_alloc(ctx, (size_t)FP_MAXNN * n_pad, &nbr));
-    TDV_TRY(ws_alloc(ctx, (size_t)n_pad, &cnt));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &flag));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &pos));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &qsel));
-    TDV_TRY(ws_alloc(ctx, 1, &d_total));
-    TDV_TRY(ws_alloc(ctx, (size_t)k * n_pad, &listsK));
-    TDV_TRY(ws_alloc(ctx, (size_t)n_pad, &cntK));
-    auto query = [&](int kk, float bound0, int seed_own, int timer, const int* sel, int nsel, int* lists, int* counts) -> int {
-        if (nsel <= 0) return TDV_OK;
-        const unsigned grid = (unsigned)((nsel + QW_WAVES - 1) / QW_WAVES);
-        ScopedTimer tm(ctx, timer);
-#define TDV_QWB(RR) k_query_wave<RR, QW_SEED_SPAN, QW_BEST_FIRST><<<grid, 64 * QW_WAVES, 0, s>>>(so.sx, so.sy, so.sz, so.orig, total_pos, so.n_leaf, so.lbox, so.n_top, so.tbox, \
-                                                            sel, nsel, nullptr, bound0, seed_own, kk, kk, lists, counts, so.okey, so.key2idx, d_leaf, n_clouds)
-        if (kk <= 64) TDV_QWB(2); else TDV_QWB(4);
-#undef TDV_QWB
-        TDV_CHECK_LAUNCH(ctx);
-        return TDV_OK;
-    };
-    TDV_TRY(query(FP_MAXNN, r2, 0, TDV_TIMER_RADIUS, pos_of_point, n, nbr, cnt));                       // radius lists of every point
-    k_batch_flag_deficient<<<(n + 255) / 256, 256, 0, s>>>(cnt, n, k, flag);
-    TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, d_total));
-    k_batch_compact_flagged<<<(n + 255) / 256, 256, 0, s>>>(flag, pos, pos_of_point, n, qsel);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(pin_reserve(ctx, 64));
-    int* h_total = reinterpret_cast<int*>(ctx->pin);
-    TDV_HIP(ctx, hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));                                                              // (also: ppos / leaf are host temporaries)
-    TDV_TRY(query(k, INFINITY, 1, TDV_TIMER_KNN, qsel, *h_total, listsK, cntK));                         // kNN lists of the points with fewer than k in radius
-    k_normals_from_lists<<<n_pad / KN_BLOCK, KN_BLOCK, 0, s>>>(d_xyz, n, iota, k, nbr, FP_MAXNN, cnt, listsK, k, cntK, d_normals, nullptr, 0);
-    TDV_CHECK_LAUNCH(ctx);
-    ScanPlan p = make_scan_plan(n);
-    return fpfh_from_lists(ctx, d_xyz, d_normals, n, p, iota, nbr, cnt, d_desc, nullptr, nullptr);
+    float *sx = soa, *sy = soa + total_pos, *sz = soa + 2 * (size_t)total_pos;
+    k_batch_layout<<<(total_pos + 255) / 256, 256, 0, s>>>(d_xyz, d_voff, d_ppos, n_clouds, total_pos, d_tie_ids, sx, sy, sz, orig, okey, pos_of_point, iota);
+    SortedCloud sc{};
+    sc.sx = sx; sc.sy = sy; sc.sz = sz; sc.orig = orig; sc.n = sc.pad = total_pos;   // every position is a point or NaN: none is cut off by n
+    sc.inst_leaf = d_leaf; sc.n_inst = n_clouds;
+    if (d_tie_ids) { sc.okey = okey; sc.key2idx = d_tie_ids_inv; }
+    TDV_TRY(build_boxes(ctx, sc, total_pos / 64));
+    // (the read-back inside also covers ppos / leaf, host temporaries)
+    return lists_normals_fpfh(ctx, d_xyz, n, sc, pos_of_point, iota, k, r2, d_normals, d_desc);
 }
 
 }  // namespace tdv

@@ -3,7 +3,7 @@
 // The host enqueues everything up front; nothing returns to it between the kernels, and the call reads back once, at the end.
 // Statistical filter:
 //  (i)   spatial_sort_cloud: the cloud along a Morton curve with the boxes of its leaves and groups (knn.hip).
-//  (ii)  k_outlier_mean: ONE WAVE PER QUERY in curve order, the walk of k_query_wave (query_wave.hpp).  When the walk ends the query's
+//  (ii)  k_outlier_mean: ONE WAVE PER QUERY in curve order, the walk of k_query_wave (sorted_cloud.hpp: query_wave_collect).  When the walk ends the query's
 //        sorted row is in the wave's registers: every lane takes the f64 square root of its entries, lane order is list order, and the
 //        k additions run serially over the lanes' values (readlane).  One f64 leaves the kernel per query: no n x k list is written.
 //  (iii) k_outlier_partial (pass 0): per workgroup of 256 points in ORIGINAL index order the f64 sum of the valid means (fixed_tree.hpp's
@@ -11,12 +11,11 @@
 //        partials (thread t takes t, t + 256, ... in order, then the same block sum) and one lane forms cloud_mean.
 //  (iv)  k_outlier_partial (pass 1) and k_outlier_tree again on (mean - cloud_mean)^2: std_dev and threshold in one lane.
 //  (v)   k_outlier_flag, exclusive_scan_dev, k_gather_flagged (flag_gather.hpp): mask, then index, xyz and rgb of the kept rows in ascending index.
-// Radius filter: k_outlier_count is k_cluster_count's walk (cluster_walk.hpp) with its early stop at nb_points + 1; then (v).
+// Radius filter: k_outlier_count is k_cluster_count's walk (sorted_cloud.hpp: walk_in_order) with its early stop at nb_points + 1; then (v).
 // No float atomics: the counts are integers, the f64 sums have the one order above, so two calls give the same bits.
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
-#include "query_wave.hpp"
-#include "cluster_walk.hpp"
+#include "sorted_cloud.hpp"
 #include "fixed_tree.hpp"
 #include "flag_gather.hpp"
 #include <cfloat>
@@ -44,22 +43,19 @@ __device__ __forceinline__ bool outlier_valid(double m) { return m > 0.0 && m < 
 // mean[original index] = rule 2 for every point, from the query's sorted row while it is in the wave
 template <int R>
 __global__ __launch_bounds__(64 * OL_MEAN_WAVES)
-void k_outlier_mean(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz, const int* __restrict__ orig,
-                    int n, int n_leaf, const float* __restrict__ lbox, int n_top, const float* __restrict__ tbox, int k,
-                    double* __restrict__ mean) {
+void k_outlier_mean(SortedCloud c, int k, double* __restrict__ mean) {
     constexpr int ROW = 64 * R;
     __shared__ unsigned long long rows[OL_MEAN_WAVES][ROW];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int sp = xcd_contiguous_block(blockIdx.x, gridDim.x) * OL_MEAN_WAVES + wave;   // curve order: an XCD works on one stretch
-    if (sp >= n) return;                                                                  // wave-uniform
+    if (sp >= c.n) return;                                                                // wave-uniform
     unsigned long long key[R];
-    const int wcnt = query_wave_collect<R, QW_SEED_SPAN, QW_BEST_FIRST>(sx, sy, sz, orig, n, n_leaf, lbox, n_top, tbox, sp, nullptr, 0, INFINITY, 1,
-                                                                        k, nullptr, nullptr, 0, rows[wave], lane, key);
-    const int c = min(k, wcnt);                                                           // count_i; wave-uniform
+    const int wcnt = query_wave_collect<R, QW_SEED_SPAN, QW_BEST_FIRST, false>(c, sp, INFINITY, 1, k, rows[wave], lane, key);
+    const int cnt = min(k, wcnt);                                                         // count_i; wave-uniform
     double s = 0.0;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        const int m = min(64, c - 64 * r);                                                // entries of the list in this register
+        const int m = min(64, cnt - 64 * r);                                              // entries of the list in this register
         if (m <= 0) break;
         const double d = sqrt((double)__uint_as_float((unsigned)(key[r] >> 32)));         // one square root per lane
         const int lo = (int)(unsigned)__double_as_longlong(d), hi = (int)(unsigned)(__double_as_longlong(d) >> 32);
@@ -69,7 +65,7 @@ void k_outlier_mean(const float* __restrict__ sx, const float* __restrict__ sy, 
             s += __longlong_as_double((long long)b);
         }
     }
-    if (lane == 0) mean[orig[sp]] = c > 0 ? s / (double)c : tree_nan();
+    if (lane == 0) mean[c.orig[sp]] = cnt > 0 ? s / (double)cnt : tree_nan();
 }
 
 // part[b] = the sum over points [256 b, 256 b + 256) of: pass 0, the valid means (cnt[b] = how many); pass 1, their squared deviations
@@ -126,7 +122,7 @@ __global__ __launch_bounds__(256) void k_outlier_flag(const double* __restrict__
 
 // Radius filter: cnt = the neighbours of the query (itself included) as far as the walk counted them: it stops once cap = nb_points + 1
 // are seen, and the count is saturated there.  flag / mask[original index] = kept (cnt > nb_points), count[original index] = cnt.
-__global__ __launch_bounds__(64 * OL_WAVES) void k_outlier_count(ClusterCloud c, float eps2, int nb_points, int cap, int* __restrict__ flag,
+__global__ __launch_bounds__(64 * OL_WAVES) void k_outlier_count(SortedCloud c, float eps2, int nb_points, int cap, int* __restrict__ flag,
                                                                  uint8_t* __restrict__ mask, int* __restrict__ count) {
     const int lane = threadIdx.x & 63;
     const int sp = blockIdx.x * OL_WAVES + (threadIdx.x >> 6);
@@ -134,9 +130,9 @@ __global__ __launch_bounds__(64 * OL_WAVES) void k_outlier_count(ClusterCloud c,
     const float qx = c.sx[sp], qy = c.sy[sp], qz = c.sz[sp];
     int cnt = 0;
     // a query that is not its own neighbour (a NaN or infinite coordinate) has none: as in k_cluster_count
-    if (cluster_d2(qx, qy, qz, qx, qy, qz) <= eps2) cluster_walk(c, qx, qy, qz, eps2, lane, [&](int leaf) {
+    if (d2_point<D2::DBSCAN>(qx, qy, qz, qx, qy, qz) <= eps2) walk_in_order<D2::DBSCAN>(c, qx, qy, qz, eps2, lane, [&](int leaf) {
         const int p = leaf * 64 + lane;                      // the arrays are padded to a multiple of 256
-        const bool nb = p < c.n && cluster_d2(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz) <= eps2;
+        const bool nb = p < c.n && d2_point<D2::DBSCAN>(c.sx[p], c.sy[p], c.sz[p], qx, qy, qz) <= eps2;
         cnt += __popcll(__ballot(nb));
         return cnt >= cap;
     });
@@ -157,7 +153,7 @@ __global__ __launch_bounds__(256) void k_outlier_radius_state(const float* __res
     int v = 0;
     if (i < n) {
         const float x = xyz[3 * (size_t)i], y = xyz[3 * (size_t)i + 1], z = xyz[3 * (size_t)i + 2];
-        v = cluster_d2(x, y, z, x, y, z) <= eps2 ? 1 : 0;
+        v = d2_point<D2::DBSCAN>(x, y, z, x, y, z) <= eps2 ? 1 : 0;
     }
     const int c = tree_block_count(v, ldc4);
     if (threadIdx.x == 0 && c) atomicAdd(&st->n_valid, c);
@@ -218,7 +214,7 @@ int outlier_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n,
         TDV_TRY(spatial_sort_cloud(ctx, d_xyz, n, sc));
         const int k = std::min(nb_neighbors, n);
         const unsigned grid = (unsigned)((n + OL_MEAN_WAVES - 1) / OL_MEAN_WAVES);
-#define TDV_OL_MEAN(RR) k_outlier_mean<RR><<<grid, 64 * OL_MEAN_WAVES, 0, s>>>(sc.sx, sc.sy, sc.sz, sc.orig, n, sc.n_leaf, sc.lbox, sc.n_top, sc.tbox, k, d.mean)
+#define TDV_OL_MEAN(RR) k_outlier_mean<RR><<<grid, 64 * OL_MEAN_WAVES, 0, s>>>(sc, k, d.mean)
         if (k <= 64) TDV_OL_MEAN(2);                              // the row widths of k_query_wave (knn.hip: query_to_lists)
         else if (k <= 192) TDV_OL_MEAN(4);
         else TDV_OL_MEAN(8);
@@ -230,12 +226,11 @@ int outlier_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n,
         k_outlier_flag<<<nb, 256, 0, s>>>(d.mean, n, st, flag, d.mask);
     } else {
         TDV_TRY(spatial_sort_cloud(ctx, d_xyz, n, sc));
-        const ClusterCloud c{sc.sx, sc.sy, sc.sz, sc.orig, sc.lbox, sc.tbox, n, sc.n_leaf, sc.n_top};
         const float eps2 = std::min(radius * radius, FLT_MAX);    // finite: an infinite d2 never passes (tdv_cluster_dbscan, rule 1)
         const int cap = nb_points == INT_MAX ? INT_MAX : nb_points + 1;
         k_outlier_init<<<1, 64, 0, s>>>(st);
         k_outlier_radius_state<<<nb, 256, 0, s>>>(d_xyz, n, eps2, st);
-        k_outlier_count<<<(n + OL_WAVES - 1) / OL_WAVES, 64 * OL_WAVES, 0, s>>>(c, eps2, nb_points, cap, flag, d.mask, d.count);
+        k_outlier_count<<<(n + OL_WAVES - 1) / OL_WAVES, 64 * OL_WAVES, 0, s>>>(sc, eps2, nb_points, cap, flag, d.mask, d.count);
     }
     TDV_CHECK_LAUNCH(ctx);
     TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, &st->n_kept));

@@ -17,6 +17,7 @@
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
 #include "philox.hpp"
+#include "fixed_tree.hpp"
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -67,16 +68,6 @@ __device__ __forceinline__ bool plane_hypothesis(const float* __restrict__ cand,
 
 __device__ __forceinline__ double plane_dist(double a, double b, double c, double d, double px, double py, double pz) {
     return fabs(((a * px + b * py) + c * pz) + d);
-}
-
-// f64 sum over the 256 threads of a workgroup, fixed order (wave shuffles, then the four waves in order); valid in thread 0
-__device__ __forceinline__ double plane_block_sum(double v, double* lds4) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
 }
 
 __global__ void k_plane_init(PlaneState* st, int n) {
@@ -214,16 +205,9 @@ __global__ __launch_bounds__(256) void k_plane_label(const float* __restrict__ c
     if (!acc) return;                                   // uniform over the launch
     const double v[4] = {in ? dist * dist : 0.0, in ? px : 0.0, in ? py : 0.0, in ? pz : 0.0};
     for (int a = 0; a < 4; ++a) {
-        const double s = plane_block_sum(v[a], lds4);
+        const double s = tree_block_sum(v[a], lds4);
         if (threadIdx.x == 0) part[4 * (size_t)blockIdx.x + a] = s;
     }
-}
-
-// fixed tree over the nb workgroups' `width` sums: thread i adds workgroups i, i + 256, ... in order, then plane_block_sum
-__device__ __forceinline__ double plane_tree(const double* __restrict__ part, int nb, int width, int a, double* lds4) {
-    double v = 0.0;
-    for (int b = threadIdx.x; b < nb; b += 256) v += part[(size_t)width * b + a];
-    return plane_block_sum(v, lds4);
 }
 
 __global__ __launch_bounds__(256) void k_plane_mean(PlaneState* st, const double* __restrict__ part, int nb) {
@@ -231,7 +215,7 @@ __global__ __launch_bounds__(256) void k_plane_mean(PlaneState* st, const double
     if (!st->accepted) return;
     const double cnt = (double)st->best_count;
     for (int a = 0; a < 4; ++a) {
-        const double s = plane_tree(part, nb, 4, a, lds4);
+        const double s = tree_partials_sum(part, nb, lds4, 4, a);
         if (threadIdx.x == 0) { if (a == 0) st->sd2 = s; else st->mean[a - 1] = s / cnt; }
         __syncthreads();
     }
@@ -252,7 +236,7 @@ __global__ __launch_bounds__(256) void k_plane_cov(const float* __restrict__ can
     }
     const double v[6] = {dx * dx, dx * dy, dx * dz, dy * dy, dy * dz, dz * dz};
     for (int a = 0; a < 6; ++a) {
-        const double s = plane_block_sum(v[a], lds4);
+        const double s = tree_block_sum(v[a], lds4);
         if (threadIdx.x == 0) part[6 * (size_t)blockIdx.x + a] = s;
     }
 }
@@ -312,7 +296,7 @@ __global__ __launch_bounds__(256) void k_plane_finish(PlaneState* st, const doub
     double C[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     if (refit) {
         for (int a = 0; a < 6; ++a) {
-            const double s = plane_tree(part, nb, 6, a, lds4);
+            const double s = tree_partials_sum(part, nb, lds4, 6, a);
             if (threadIdx.x == 0) C[a] = s;
             __syncthreads();
         }

@@ -1,6 +1,13 @@
-// The one-wave-per-query walk over a curve-ordered cloud (knn.hip builds the order and the boxes: spatial_sort_cloud), shared by every
-// kernel that needs a query's sorted neighbour row: k_query_wave (knn.hip: the lists of normals and FPFH) and k_outlier_mean
-// (outlier.hip: the mean neighbour distance, taken from the row while it is still in the wave).  Device code only.
+// The searches over a SortedCloud (tdv_internal.hpp; knn.hip builds it: spatial_sort_cloud), one wave per query.  Every kernel that looks
+// for a point's neighbours goes through this header: it takes the descriptor by value and uses
+//   d2_point / d2_box_bound   the distance of two points and its exact lower bound against a box, in one of two expression trees;
+//   walk_in_order             the two-level walk in curve order at a fixed radius: 64 group boxes per step, one per lane, then the 64
+//                             leaves of a group that passes (cluster.hip, outlier.hip's radius count, iss.hip);
+//   query_wave_collect        a query's sorted neighbour row (k_query_wave in knn.hip: the lists of normals and FPFH; k_outlier_mean and
+//                             k_iss_nn take their figure from the row while it is still in the wave).  Its bound drops as the row fills
+//                             and its seeded kNN start visits a group's leaves nearest first: a loop of its own, as is the best-first
+//                             group loop of ICP's pruned search (icp.hip).  Both use only the descriptor and the bound.
+// Device code only, compiled without contraction (the library's -ffp-contract=off).
 #pragma once
 #include "tdv_internal.hpp"
 #include <cmath>
@@ -15,19 +22,58 @@ __device__ __forceinline__ int xcd_contiguous_block(int b, int nwg) {
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (b >> 3);
 }
 
-// Lower bound on the reference's float d2 = dx*dx + (dy*dy + dz*dz) between ANY query inside [qmin,qmax] and ANY target
-// inside [bmin,bmax]: per-axis gaps by one float subtraction each, then the same expression tree.  Float subtraction,
-// multiplication and addition are monotone under round-to-nearest, so lb <= fl(d2) for every such pair — no margin
-// is needed, and "lb > bound" proves that nothing in the box can pass "d2 <= bound".
-__device__ __forceinline__ float box_lower_bound(const float* __restrict__ box, int count, int idx,
-                                                 const float (&qmin)[3], const float (&qmax)[3]) {
+// The two expression trees a squared distance is summed in: the reference's x + (y + z) (registration.cpp: kNN, radius lists, ICP) and
+// (x + y) + z (include/tdv_hip.h: tdv_cluster_dbscan rule 1, which the outlier radius filter and ISS share).
+enum class D2 { REF, DBSCAN };
+template <D2 TREE>
+__device__ __forceinline__ float d2_sum(float x, float y, float z) { return TREE == D2::REF ? x + (y + z) : (x + y) + z; }
+
+// d2 between the points p and q
+template <D2 TREE>
+__device__ __forceinline__ float d2_point(float px, float py, float pz, float qx, float qy, float qz) {
+    const float dx = px - qx, dy = py - qy, dz = pz - qz;
+    return d2_sum<TREE>(dx * dx, dy * dy, dz * dz);
+}
+
+// Lower bound of d2_point<TREE> between q and ANY point inside box idx of a [6][count] box array: per-axis gaps by one f32 subtraction
+// each, then the SAME expression tree.  f32 subtraction, multiplication and addition are monotone under round-to-nearest, so term by term
+// and sum by sum the bound never exceeds the fl(d2) of a point in the box: no margin is needed, and "bound > B" proves that nothing in
+// the box passes "d2 <= B".  That argument runs along one tree, which is why the bound takes the tree of the distance it guards: against
+// the other tree's d2 it could come out one rounding too high.  NaN gaps count as 0 (fmaxf): such a box is looked at.
+template <D2 TREE>
+__device__ __forceinline__ float d2_box_bound(const float* __restrict__ box, int count, int idx, float qx, float qy, float qz) {
+    const float q[3] = {qx, qy, qz};
     float g[3];
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-        float bmin = box[(size_t)a * count + idx], bmax = box[(size_t)(3 + a) * count + idx];
-        g[a] = fmaxf(0.f, fmaxf(bmin - qmax[a], qmin[a] - bmax));
+        const float bmin = box[(size_t)a * count + idx], bmax = box[(size_t)(3 + a) * count + idx];
+        g[a] = fmaxf(0.f, fmaxf(bmin - q[a], q[a] - bmax));
     }
-    return g[0] * g[0] + (g[1] * g[1] + g[2] * g[2]);
+    return d2_sum<TREE>(g[0] * g[0], g[1] * g[1], g[2] * g[2]);
+}
+
+// The two-level walk in curve order at a fixed bound: visit(leaf) for every leaf whose box may hold a point with d2_point<TREE> <= bound
+// of q, until it returns true.  64 group boxes per step, one per lane, then the 64 leaves of a group that passes.  Wave-uniform control
+// flow.  (query_wave_collect keeps a loop of its own: its bound drops as the row fills.  Run through this function, then with a leaf
+// range and a re-test of a dropped bound, the radius lists' k_query_wave<4> took 427 us against the parent's 383 us at 200k points:
+// profiles/r16/sorted_cloud_descriptor.md, section 3.)
+template <D2 TREE, class Visit>
+__device__ __forceinline__ void walk_in_order(const SortedCloud& c, float qx, float qy, float qz, float bound, int lane, Visit&& visit) {
+    for (int tb = 0; tb < c.n_top; tb += 64) {
+        const int t = tb + lane;
+        unsigned long long tmask = __ballot(t < c.n_top && d2_box_bound<TREE>(c.tbox, c.n_top, min(t, c.n_top - 1), qx, qy, qz) <= bound);
+        while (tmask) {
+            const int bt = __ffsll((long long)tmask) - 1;
+            tmask &= tmask - 1;
+            const int u = (tb + bt) * 64 + lane;
+            unsigned long long lmask = __ballot(u < c.n_leaf && d2_box_bound<TREE>(c.lbox, c.n_leaf, min(u, c.n_leaf - 1), qx, qy, qz) <= bound);
+            while (lmask) {
+                const int bl = __ffsll((long long)lmask) - 1;
+                lmask &= lmask - 1;
+                if (visit((tb + bt) * 64 + bl)) return;
+            }
+        }
+    }
 }
 
 // ------------------------------------------------------------------ one wave per query: walk, collect, select
@@ -101,20 +147,19 @@ __device__ __forceinline__ void load_sort_row(const unsigned long long* row, int
 }
 
 // The search of one query by one wave: walks the cloud for the query at sorted position sp, collects into `row` (LDS, 64 * R keys of
-// this wave) every target with d2 <= the bound (bound[slot] if given, else bound0, at the start; it drops to the k-th as the row fills) and leaves the row sorted in
+// this wave) every target with d2 <= the bound (bound0 at the start; it drops to the k-th as the row fills) and leaves the row sorted in
 // `key` (element e = r * 64 + lane; 64-bit keys d2 bits : tie-break id, ~0 past the end).  Returns the number of keys found (it may
 // exceed k: the first min(k, found) are the list).  Requires k <= 64 * R - 64.  Wave-uniform control flow; no block-level barrier.
-template <int R, int SEED_SPAN, bool BEST_FIRST>
-__device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, const float* __restrict__ sy, const float* __restrict__ sz,
-                                                  const int* __restrict__ orig, int n, int n_leaf, const float* __restrict__ lbox, int n_top,
-                                                  const float* __restrict__ tbox, int sp, const float* __restrict__ bound, int slot, float bound0,
-                                                  int seed_own, int k,
-                                                  const int* __restrict__ okey, const int* __restrict__ inst_leaf, int n_inst,
+// OPTIONAL = false: the caller's cloud is a single cloud whose ties break by original index (spatial_sort_cloud's, as it comes): the
+// descriptor's okey and inst_leaf are not looked at, and neither branch is compiled in.
+template <int R, int SEED_SPAN, bool BEST_FIRST, bool OPTIONAL = true>
+__device__ __forceinline__ int query_wave_collect(const SortedCloud& c, int sp, float bound0, int seed_own, int k,
                                                   unsigned long long* row, int lane, unsigned long long (&key)[R]) {
     constexpr int ROW = 64 * R;
-    const float qx = sx[sp], qy = sy[sp], qz = sz[sp];
-    const float qp[3] = {qx, qy, qz};
-    float B = bound ? bound[slot] : bound0;   // wave-uniform; only ever decreases
+    const float qx = c.sx[sp], qy = c.sy[sp], qz = c.sz[sp];
+    const int* okey = OPTIONAL ? c.okey : nullptr;
+    const int* inst_leaf = OPTIONAL ? c.inst_leaf : nullptr;
+    float B = bound0;                         // wave-uniform; only ever decreases
     int wcnt = 0;                             // wave-uniform fill of the row
 
     // keep the best k of the row (needs wcnt >= k) and drop the bound to the k-th.  No sort: the k-th smallest key is
@@ -132,10 +177,10 @@ __device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, 
             hi[r] = (unsigned)(key >> 32); lo[r] = (unsigned)key;
         }
         auto count_if = [&](auto pred) {
-            int c = 0;
+            int cnt = 0;
 #pragma unroll
-            for (int r = 0; r < R; ++r) c += __popcll(__ballot(has[r] && pred(r)));
-            return c;
+            for (int r = 0; r < R; ++r) cnt += __popcll(__ballot(has[r] && pred(r)));
+            return cnt;
         };
         unsigned kd = 0;   // k-th smallest distance bits: count(hi < kd) < k <= count(hi <= kd)
         for (int b = 31; b >= 0; --b) {
@@ -168,9 +213,8 @@ __device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, 
     // the 64 targets of one leaf, one per lane
     auto eval_leaf = [&](int leaf) {
         const int pidx = leaf * 64 + lane;   // arrays are padded with +inf to a multiple of 256
-        float dx = sx[pidx] - qx, dy = sy[pidx] - qy, dz = sz[pidx] - qz;   // (points[i] - query)
-        float d2 = dx * dx + (dy * dy + dz * dz);
-        bool acc = pidx < n && d2 <= B;
+        const float d2 = d2_point<D2::REF>(c.sx[pidx], c.sy[pidx], c.sz[pidx], qx, qy, qz);   // (points[i] - query)
+        bool acc = pidx < c.n && d2 <= B;
         unsigned long long am = __ballot(acc);
         if (!am) return;
         if (wcnt + __popcll(am) > ROW) {   // the row cannot take them all (wcnt > ROW - 64 >= k)
@@ -180,16 +224,16 @@ __device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, 
             if (!am) return;
         }
         const int at = wcnt + __popcll(am & ((1ull << lane) - 1ull));
-        if (acc) row[at] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)(okey ? okey[pidx] : orig[pidx]);
+        if (acc) row[at] = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)(okey ? okey[pidx] : c.orig[pidx]);
         wcnt += __popcll(am);
     };
 
     const int own = sp >> 6;
     // Several clouds in one array (the batch's small instances, each padded to whole leaves with NaN coordinates): the walk
     // stays inside the query's own cloud - boxes of other clouds are never looked at, whatever their coordinates.
-    int l_lo = 0, l_hi = n_leaf;
+    int l_lo = 0, l_hi = c.n_leaf;
     if (inst_leaf) {
-        int a = 0, z = n_inst;
+        int a = 0, z = c.n_inst;
         while (z - a > 1) { const int m = (a + z) >> 1; if (inst_leaf[m] <= own) a = m; else z = m; }
         l_lo = inst_leaf[a]; l_hi = inst_leaf[a + 1];
     }
@@ -203,11 +247,11 @@ __device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, 
     }
     // Validity is tracked explicitly (never through "+inf <= bound"): the bound itself is +inf while an unbounded
     // search has seen fewer than k points, or for an unbounded radius.
-    const int t_hi = inst_leaf ? ((l_hi - 1) >> 6) + 1 : n_top;
+    const int t_hi = inst_leaf ? ((l_hi - 1) >> 6) + 1 : c.n_top;
     for (int tb = inst_leaf ? (l_lo >> 6) : 0; tb < t_hi; tb += 64) {
         const int t = tb + lane;
         const bool t_valid = t < t_hi;
-        const float lbt = t_valid ? box_lower_bound(tbox, n_top, t, qp, qp) : INFINITY;
+        const float lbt = t_valid ? d2_box_bound<D2::REF>(c.tbox, c.n_top, t, qx, qy, qz) : INFINITY;
         unsigned long long tmask = __ballot(t_valid && lbt <= B);
         while (tmask) {
             const int bt = __ffsll((long long)tmask) - 1;
@@ -215,7 +259,7 @@ __device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, 
             if (__shfl(lbt, bt, 64) > B) continue;   // the bound may have dropped since the test
             const int u = (tb + bt) * 64 + lane;
             bool pending = u >= l_lo && u < l_hi && !(u >= seed_lo && u <= seed_hi);   // a leaf of this group (and cloud) not evaluated yet
-            const float lbl = pending ? box_lower_bound(lbox, n_leaf, u, qp, qp) : INFINITY;
+            const float lbl = pending ? d2_box_bound<D2::REF>(c.lbox, c.n_leaf, u, qx, qy, qz) : INFINITY;
             if (BEST_FIRST && seed_own) {
                 while (true) {   // nearest leaf first: the bound tightens before the far leaves are looked at
                     const bool cand = pending && lbl <= B;
@@ -227,7 +271,7 @@ __device__ __forceinline__ int query_wave_collect(const float* __restrict__ sx, 
                     if (lane == bl) pending = false;
                     eval_leaf((tb + bt) * 64 + bl);
                 }
-            } else {
+            } else {                                     // walk_in_order's leaf loop, with the re-test of a dropped bound
                 unsigned long long lmask = __ballot(pending && lbl <= B);
                 while (lmask) {
                     const int bl = __ffsll((long long)lmask) - 1;

@@ -302,10 +302,20 @@ int segment_sort_records_dev(tdv_ctx* ctx, uint4* rec, const int* d_seg_start, i
 int segment_sort_max_len();
 size_t sort_pow2(size_t n);
 int exclusive_scan_dev(tdv_ctx* ctx, const int* d_in, int n, int* d_out, int* d_total);  // sort.hip
-// Morton-ordered copy of a cloud with the bounding boxes of its 64-point leaves and 4096-point groups (workspace memory):
-// sx/sy/sz are padded with +inf to `pad` (a multiple of 256), orig[i] = original index of sorted position i.
-// Box arrays are [6][count]: min x,y,z then max x,y,z.
-struct SortedCloud { float *sx, *sy, *sz; int* orig; float *lbox, *tbox; int n, pad, n_leaf, n_top; };
+// A cloud in search order with the bounding boxes of its 64-point leaves and of its 4096-point groups of 64 leaves (workspace memory):
+// the one structure every neighbour search walks (sorted_cloud.hpp).  The kernels take it by value.  spatial_sort_cloud builds it in
+// Morton order with positions n..pad filled with +inf; the batch of small clouds (knn.hip: normals_fpfh_batch_dev) lays its clouds out
+// back to back, each padded to whole leaves with NaN, and names their leaf ranges in inst_leaf (there n == pad: every position is read).
+struct SortedCloud {
+    const float *sx, *sy, *sz;            // SoA coordinates of the `pad` positions (a multiple of 256)
+    const int* orig;                      // original index of a position (INT_MAX at a padding position)
+    const float *lbox, *tbox;             // leaf and group boxes, [6][n_leaf] and [6][n_top]: min x, y, z, then max x, y, z
+    int n, n_leaf, n_top, pad;            // (the three a walk reads side by side: one scalar load)
+    // optional: ties in (d2, id) order are broken by okey[position] instead of the original index, and the lists receive key2idx[id]
+    const int *okey = nullptr, *key2idx = nullptr;
+    // optional, several clouds in one array: cloud b owns leaves [inst_leaf[b], inst_leaf[b + 1]), and a query never leaves its cloud
+    const int* inst_leaf = nullptr; int n_inst = 0;
+};
 int spatial_sort_cloud(tdv_ctx* ctx, const float* d_xyz, int n, SortedCloud& out);
 
 // ISS keypoints (iss.hip, include/tdv_hip.h: tdv_iss_keypoints): the outputs of a call (each optional), the argument check of both entry

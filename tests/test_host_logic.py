@@ -220,7 +220,7 @@ def _f32(x):
 
 @pytest.mark.parametrize("scale", [1e-6, 1.0, 1e3, 1e15])
 def test_box_lower_bound_never_exceeds_a_distance(scale):
-    """csrc/knn.hip box_lower_bound / csrc/icp.hip point_box_lb: per-axis gap by ONE float subtraction, then the
+    """csrc/sorted_cloud.hpp d2_box_bound (D2::REF): per-axis gap by ONE float subtraction, then the
     reference's expression gx*gx + (gy*gy + gz*gz).  Float -, *, + are monotone under round-to-nearest, so the bound
     can never exceed fl(d2) of a point inside the box — with no safety margin.  Millions of random cases, including
     points on the box faces, queries inside the box, tiny and huge magnitudes."""
