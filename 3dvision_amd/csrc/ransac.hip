@@ -189,7 +189,10 @@ __device__ __forceinline__ void ransac_plan(const PlanJob& j);
 struct PreJob { int* flags; int* ubf; const RansacFar* far; const unsigned* enc; const float* best12; float live_radius; int u_cut_permille; };
 __device__ __forceinline__ void ransac_prejudge(const PreJob& j, const float* o, bool valid, int h, const unsigned* __restrict__ pmax, float sqrt_tau, float band_u,
                                                 const int* __restrict__ state, int ns);
-__global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, int count, int h_pad,
+// up != nullptr: the batch's triples as the host drew them, in pinned host memory, which the device reads as it is (it writes a
+// batch's record there).  Lane h loads its triple from there and stores it to `triples` for the batch's later kernels (the bound, the
+// select kernels and k_ransac_finish ask triples.valid(h)): the batch needs no copy in front of this kernel.
+__global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, const void* __restrict__ up, int count, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
                                     float band_u /* E = band_u (A + s): kBandUnit or kBandUnitMatrix */, const PlanJob plan, const PreJob pre) {
     int h = blockIdx.x * blockDim.x + threadIdx.x;
@@ -199,7 +202,19 @@ __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView 
     counts[h] = 0;                       // the scoring kernel adds its point-splits' counts here (one memset launch less per batch)
     bool valid = false;
     int4 tr = make_int4(0, 0, 0, 0);
-    if (h < count) { tr = triples.load(h); valid = tr.w != 0; }
+    if (h < count) {
+        if (up) {
+            if (triples.packed) {
+                const uint64_t w = static_cast<const uint64_t*>(up)[h];
+                const_cast<uint64_t*>(static_cast<const uint64_t*>(triples.p))[h] = w;
+                tr = TriView::unpack(w);
+            } else {
+                tr = static_cast<const int4*>(up)[h];
+                const_cast<int4*>(static_cast<const int4*>(triples.p))[h] = tr;
+            }
+        } else tr = triples.load(h);
+        valid = tr.w != 0;
+    }
     float o[12];
     ransac_hypothesis_lane(pq, tr, valid, h, h_pad, hyp, pmax, sqrt_tau, band_u, o);
     if (pre.flags) ransac_prejudge(pre, o, valid, h, pmax, sqrt_tau, band_u, plan.state, plan.ns);      // (uniform)
@@ -635,21 +650,75 @@ __global__ void k_ransac_select(const TriView triples, int count, const int* __r
 // A NEAR hypothesis (RansacFarBound: `near`, *n_near entries, phase 1 over [c_far, plan[3])) has rest = the points behind its phase 1
 // plus ubf[h], which bounds its inliers in the F chunks it skipped: prefix + rest still bounds its full count from above and the
 // prefix is still a lower bound of it, so rules (a) and (b) hold as written.  Its survivors go to list2 (plan[4] of them).
+// The register form of the two one-workgroup kernels (k_ransac_select_live, k_ransac_finish).  Both walk the live lists twice, and a
+// trip of the loops is a chain of two dependent loads - live[i], then counts[live[i]] - that ends in a reduction, which keeps the
+// trips apart: 7 trips x 2 round trips x 2 passes with the headline's 7,100 live hypotheses, on one workgroup.  So where the far and
+// the near list together hold at most LIVE_REG x 1,024 entries, thread t takes entries t, t + 1024, ... into registers at once: all the
+// list loads back to back, then all the gathers, and both passes work from the registers.  Every load is unconditional - one under
+// `if (i < n)` is an exec-masked block of its own with a full wait in front of it (icp.hip: acc_fetch): an entry past the end reads
+// live[0], whatever it holds, and gathers counts[0]; `on` says which entries count.  Longer lists keep the loops.
+constexpr int LIVE_REG = 8;
+struct LiveRegs { int h[LIVE_REG], c[LIVE_REG], u[LIVE_REG]; };     // hypothesis, its count, its UB_F (near entries; else not looked at)
+__device__ __forceinline__ bool live_on(int e, int tot) { return (int)threadIdx.x + e * 1024 < tot; }
+__device__ __forceinline__ bool live_is_near(int e, int n, int tot) { const int i = (int)threadIdx.x + e * 1024; return i >= n && i < tot; }
+// far list `live` (n entries), near list `near` behind it (n2 entries; nullptr with n2 == 0); ubf == nullptr: no u[]
+__device__ __forceinline__ void live_fetch(LiveRegs& L, const int* __restrict__ live, int n, const int* __restrict__ near, int n2,
+                                           const int* __restrict__ counts, const int* __restrict__ ubf) {
+    const int tot = n + n2;
+#pragma unroll
+    for (int e = 0; e < LIVE_REG; ++e) {
+        const int i = (int)threadIdx.x + e * 1024;
+        L.h[e] = *(live_is_near(e, n, tot) ? near + (i - n) : live + (i < n ? i : 0));
+    }
+#pragma unroll
+    for (int e = 0; e < LIVE_REG; ++e) L.c[e] = counts[live_on(e, tot) ? L.h[e] : 0];
+    if (ubf) {
+#pragma unroll
+        for (int e = 0; e < LIVE_REG; ++e) L.u[e] = *(live_is_near(e, n, tot) ? ubf + L.h[e] : counts);
+    }
+}
 __global__ __launch_bounds__(1024)
 void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ n_live, const int* __restrict__ near, const int* __restrict__ n_near,
                           const int* __restrict__ ubf, const int* __restrict__ counts, int ns, float confidence,
                           const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list, int* __restrict__ list2) {
     const int n = *n_live, n2 = near ? *n_near : 0, best = state[0], rest = ransac_rest(ns, plan[0]), rest2 = ransac_rest(ns, plan[3]);
+    const int tot = n + n2;
+    const bool in_regs = tot <= LIVE_REG * 1024;                     // (workgroup-uniform)
     __shared__ int s_max, s_n[2];
     if (threadIdx.x == 0) { s_max = 0; s_n[0] = 0; s_n[1] = 0; }
     __syncthreads();
     int c = 0;
-    for (int i = threadIdx.x; i < n + n2; i += 1024) c = max(c, counts[i < n ? live[i] : near[i - n]]);
+    LiveRegs L;
+    if (in_regs) {
+        live_fetch(L, live, n, near, n2, counts, near ? ubf : nullptr);
+#pragma unroll
+        for (int e = 0; e < LIVE_REG; ++e) c = max(c, live_on(e, tot) ? L.c[e] : 0);
+    } else
+        for (int i = threadIdx.x; i < tot; i += 1024) c = max(c, counts[i < n ? live[i] : near[i - n]]);
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) c = max(c, __shfl_xor(c, off, 64));
     if ((threadIdx.x & 63) == 0 && c > 0) atomicMax(&s_max, c);
     __syncthreads();
     const int in_batch = s_max, lane = threadIdx.x & 63;
+    if (in_regs) {
+        // no load from here on.  A wave's 64 entries may hold the far list's end and the near list's start: one ballot per list.
+#pragma unroll
+        for (int e = 0; e < LIVE_REG; ++e) {
+            if (e * 1024 >= tot) break;                              // (workgroup-uniform: every lane reaches the ballots)
+            const bool is_near = live_is_near(e, n, tot);
+            const int r = is_near ? rest2 + L.u[e] : rest;
+            const bool keep = live_on(e, tot) && r > 0 && ransac_keep(L.c[e], r, best, in_batch, ns, confidence);
+            for (int k = 0; k < 2; ++k) {
+                const bool mine = keep && is_near == (k == 1);
+                const unsigned long long m = __ballot(mine);
+                if (!m) continue;
+                int at = 0;
+                if (lane == 0) at = atomicAdd(&s_n[k], __popcll(m));
+                at = __shfl(at, 0, 64);
+                if (mine) (k ? list2 : list)[at + __popcll(m & ((1ull << lane) - 1ull))] = L.h[e];
+            }
+        }
+    } else
     for (int k = 0; k < 2; ++k) {                                    // the far list, then the near one
         const int* const from = k ? near : live; int* const to = k ? list2 : list;
         const int nk = k ? n2 : n;
@@ -821,6 +890,17 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     if (threadIdx.x == 0) { s_stop = INT_MAX; s_max = 0; }
     __syncthreads();
     int stop = INT_MAX, cmax = 0;
+    const bool in_regs = live && n <= LIVE_REG * 1024;           // the register form (see live_fetch); workgroup-uniform
+    LiveRegs L;
+    if (in_regs) {
+        live_fetch(L, live, n1, near, n - n1, counts, nullptr);
+#pragma unroll
+        for (int e = 0; e < LIVE_REG; ++e) {
+            if (!live_on(e, n)) continue;
+            cmax = max(cmax, L.c[e]);
+            if (static_cast<float>(L.c[e]) / fn > confidence) stop = min(stop, L.h[e]);
+        }
+    } else
 #pragma unroll 4
     for (int i = threadIdx.x; i < n; i += 1024) {
         const int h = live ? (i < n1 ? live[i] : near[i - n1]) : i;
@@ -839,6 +919,16 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     const int k_stop = s_stop;
     // the first largest fitness among the iterations up to k_stop (earlier = INT_MAX - h)
     unsigned long long best = 0ull;
+    if (in_regs) {
+#pragma unroll
+        for (int e = 0; e < LIVE_REG; ++e) {                     // from the registers: no load
+            if (!live_on(e, n) || L.h[e] > k_stop) continue;
+            const float fit = static_cast<float>(L.c[e]) / fn;   // registration.cpp:281
+            if (!(fit > 0.f)) continue;
+            const unsigned long long key = first_best_key(fit, INT_MAX - L.h[e]);
+            best = key > best ? key : best;
+        }
+    } else
 #pragma unroll 4
     for (int i = threadIdx.x; i < n; i += 1024) {
         const int h = live ? (i < n1 ? live[i] : near[i - n1]) : i;
@@ -1408,7 +1498,7 @@ static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * 
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, order, far; int drop_permille, a_permille, u_cut_permille, fine_y; float far_radius, live_radius; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far; int drop_permille, a_permille, u_cut_permille, fine_y; float far_radius, live_radius; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1443,6 +1533,7 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     k.leaf_classes = study_env("TDV_RANSAC_LEAF_CLASSES") && atoi(study_env("TDV_RANSAC_LEAF_CLASSES")) == 1;
     k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
     k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
+    k.upload_inline = study_env("TDV_RANSAC_UPLOAD") && !strcmp(study_env("TDV_RANSAC_UPLOAD"), "inline");   // A/B knob: the triples by a copy on the compute stream in front of k_ransac_hypotheses, not by the kernel's own loads from pinned memory
     k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 50;   // tuning knob: phase 1 over the first N - 0.95 best points (natural order: 5 to 100 measured equal;
                                                                                                                      // best's outliers first, round 12: 25, 50 and 75 above 100, profiles/r12/ransac_point_order.md)
     return k;
@@ -1451,7 +1542,7 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
 // One of the two sets of batch buffers: batch k+1 is drawn on the host and enqueued while the GPU scores batch k; results are
 // consumed in iteration order, so the outcome is that of the sequential loop.
 struct RansacBuf {
-    float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the uploaded triples; bail-out: phase 2's list
+    float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the triples on the device (k_ransac_hypotheses stores them); bail-out: phase 2's list
     int *live, *und, *acc, *ticket;                   // RansacLeafBound: live list, undecided list, its fine sums and tickets
     int *near, *list2, *ubf;                          // RansacFarBound: near list, its phase 2's list, UB_F per hypothesis
     int* flags;                                       // RansacBoundLists: ransac_prejudge's word per hypothesis (RB_CLOSE, RB_NEAR)
@@ -1580,15 +1671,26 @@ struct RansacRun {
         else idx.next_batch(cnt, static_cast<int*>(buf[q].h_tri));
         return cnt;
     }
-    // upload and hypotheses; one thread makes the batch's plan from the best count known now: full counts of the batches whose
+    // hypotheses, reading the triples where draw() put them.  The batch used to begin with a 512 KB copy of the triples on the compute
+    // stream: 17 us of copy with an engine switch on either side, 36 us in which no kernel ran (profiles/r17/ransac_batch_path.md).
+    // The host draws the triples into pinned memory, which the device can read, so k_ransac_hypotheses loads them from there and
+    // leaves the device copy behind for the batch's later kernels.
+    //  - buf[q].h_tri is written by draw(q) and must hold still until the batch's k_ransac_hypotheses has run.  The next draw into it is
+    //    for the batch after the next, and loop() waits for this batch's event before that.  A traced call's consume_trace reads it on
+    //    the host, behind the same event.
+    //  - After an early exit a batch that was drawn and enqueued may still read h_tri: ransac_run_dev synchronises the compute stream
+    //    on every way out of loop(), before the next entry point draws into the pinned block or lets pin_reserve move it.
+    //  - Traced calls and the merged dispatch (study build) read the same way; TDV_RANSAC_UPLOAD=inline (study build) is the copy on the
+    //    compute stream as it was.
+    // One thread makes the batch's plan from the best count known now: full counts of the batches whose
     // phase 2 has run, the prefix counts of a pending one (a lower bound of its full counts - a bound is all the rule needs)
     int hypotheses(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
-        TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
+        if (k.upload_inline) TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
         const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words() : 0,
                            k.far && b.bounded ? &d->far : nullptr, k.a_permille};
         const PreJob pre{b.bounded ? B.flags : nullptr, B.ubf, k.far ? &d->far : nullptr, enc, d->best12, k.live_radius, k.u_cut_permille};
-        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
+        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), k.upload_inline ? nullptr : B.h_tri, b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
         return TDV_OK;
     }
     // every test of the batch, no plan: the exact kernel, the fast one, or (study build) the matrix cores

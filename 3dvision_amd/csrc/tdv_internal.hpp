@@ -373,10 +373,12 @@ struct TriView {
     __host__ __device__ __forceinline__ bool valid(int h) const {
         return packed ? (static_cast<const uint64_t*>(p)[h] >> 63) != 0 : static_cast<const int4*>(p)[h].w != 0;
     }
+    __host__ __device__ static __forceinline__ int4 unpack(uint64_t w) {
+        return make_int4((int)(w & 0x1fffffu), (int)((w >> 21) & 0x1fffffu), (int)((w >> 42) & 0x1fffffu), (int)(w >> 63));
+    }
     __host__ __device__ __forceinline__ int4 load(int h) const {
         if (!packed) return static_cast<const int4*>(p)[h];
-        const uint64_t w = static_cast<const uint64_t*>(p)[h];
-        return make_int4((int)(w & 0x1fffffu), (int)((w >> 21) & 0x1fffffu), (int)((w >> 42) & 0x1fffffu), (int)(w >> 63));
+        return unpack(static_cast<const uint64_t*>(p)[h]);
     }
 };
 

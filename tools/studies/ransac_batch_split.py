@@ -3,6 +3,10 @@
 `rocprofv3 --kernel-trace --memory-copy-trace --output-format csv` wrote for `bench.py`, keeps the last RANSAC call (from its
 last k_gather_pq on) and prints, per batch (one k_ransac_hypotheses each), the mean device time of every kernel group and the
 mean wall time between two batches' k_ransac_hypotheses.
+With a copy trace it also prints the batch's path: every kernel of a batch in start order with the idle time in front of it (from
+the end of the kernel before it to its start, kernels only: what the compute stream waits), and per host-to-device copy its
+duration, the time from the end of the last kernel that started before it to its start, and the time from its end to the start of
+the next kernel.  Means over the bounded batches behind the first one (batches 3..n: the second builds the leaves).
     python tools/studies/ransac_batch_split.py <kernel_trace.csv> [<memory_copy_trace.csv>]"""
 import collections
 import csv
@@ -18,9 +22,11 @@ gathers = [i for i, r in enumerate(rows) if r[2].endswith("k_gather_pq")]
 rows = rows[gathers[-1]:]
 hyps = [r[0] for r in rows if r[2].endswith("k_ransac_hypotheses")]
 nb = len(hyps)
-rows = [r for r in rows if r[0] >= hyps[0]]
+rows = [r for r in rows if r[0] >= hyps[0] or r[2].startswith("copy")]
 groups = collections.OrderedDict()
 for s, e, n in rows:
+    if s < hyps[0]:
+        continue
     key = n.split("::")[-1]
     g = groups.setdefault(key, [0, 0])
     g[0] += 1; g[1] += e - s
@@ -32,3 +38,52 @@ for k, (c, t) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
     print("  %-28s %5d calls %9.1f us/batch %9.1f us/call" % (k, c, t / nb / 1e3, t / c / 1e3))
     busy += t
 print("  busy %.1f us/batch" % (busy / nb / 1e3))
+
+
+def mean(v):
+    return sum(v) / len(v) / 1e3 if v else float("nan")
+
+
+def spread(v):
+    return "%7.1f us (min %.1f, max %.1f, n %d)" % (mean(v), min(v) / 1e3, max(v) / 1e3, len(v)) if v else "      -"
+
+
+# ---- the batch's path.  A batch = the kernels from one k_ransac_hypotheses up to the next; the copy that feeds a batch is the
+# last host-to-device copy that ends before the next k_ransac_hypotheses starts (the parent: it sits in front of that kernel on
+# the compute stream; an upload stream: it ran somewhere under the batch before).
+if nb > 3:
+    kernels = [r for r in rows if not r[2].startswith("copy") and r[0] >= hyps[0]]
+    copies = [r for r in rows if r[2].startswith("copy") and "HOST_TO_DEVICE" in r[2].upper().replace(" ", "_")]
+    bounds = hyps + [kernels[-1][1] + 1]
+    gaps = collections.OrderedDict()        # (position in the batch, kernel) -> idle times in front of it
+    durs = collections.OrderedDict()
+    walls, idles = [], []
+    for b in range(2, nb - 1):              # batch b's kernels and the gap in front of batch b + 1's first kernel
+        ks = [r for r in kernels if bounds[b] <= r[0] < bounds[b + 1]]
+        nxt = [r for r in kernels if r[0] >= bounds[b + 1]][:1]
+        idle = 0
+        for pos, (prev, cur) in enumerate(zip(ks, ks[1:] + nxt)):
+            key = (pos, prev[2].split("::")[-1], cur[2].split("::")[-1])
+            gaps.setdefault(key, []).append(cur[0] - prev[1])
+            durs.setdefault((pos, prev[2].split("::")[-1]), []).append(prev[1] - prev[0])
+            idle += max(0, cur[0] - prev[1])
+        walls.append(bounds[b + 1] - bounds[b]); idles.append(idle)
+    print("the path of a bounded batch, batches 3..%d (kernel, its time, the idle time behind it up to the next kernel):" % (nb - 1))
+    for (pos, a, c), v in gaps.items():
+        print("  %2d %-24s %s   then idle %s -> %s" % (pos, a, spread(durs[(pos, a)]), spread(v), c))
+    print("  wall %s, no kernel running %s" % (spread(walls), spread(idles)))
+    cd, before, after, lead = [], [], [], []
+    for s, e, n in copies:
+        if not (hyps[2] <= e and s < hyps[-1]):
+            continue
+        prev_end = max([r[1] for r in kernels if r[0] <= s] or [s])
+        nxt_h = [h for h in hyps if h >= e]
+        nxt_k = [r[0] for r in kernels if r[0] >= e]
+        cd.append(e - s); before.append(s - prev_end)
+        if nxt_k: after.append(nxt_k[0] - e)
+        if nxt_h: lead.append(nxt_h[0] - e)
+    print("host-to-device copies inside the call behind batch 2: %d" % len(cd))
+    print("  duration                                   %s" % spread(cd))
+    print("  from the end of the last kernel started before it to its start (negative: a kernel is running) %s" % spread(before))
+    print("  from its end to the next kernel's start    %s" % spread(after))
+    print("  from its end to the next k_ransac_hypotheses %s" % spread(lead))
