@@ -63,6 +63,7 @@ ABI_SYMBOLS = [
     "tdv_remove_statistical_outlier", "tdv_remove_statistical_outlier_dev", "tdv_remove_radius_outlier", "tdv_remove_radius_outlier_dev",
     "tdv_iss_default_params", "tdv_iss_keypoints", "tdv_iss_keypoints_dev",
     "tdv_ppf_default_params", "tdv_ppf_model_bytes", "tdv_ppf_model_dev", "tdv_ppf_match_dev", "tdv_ppf_match",
+    "tdv_ppf_match_batch_dev",
 ]
 
 
@@ -1011,6 +1012,53 @@ class Context:
                                                 _ptr(d_peaks), C.byref(nref)), "tdv_ppf_match_dev")
         res, more = _ppf_poses(poses, n.value)
         return res, more, nref.value
+
+    def ppf_match_batch_dev(self, d_src, d_src_normals, offsets, d_tgt, d_tgt_normals, nt, d_model, info, thr, d_peaks=None, **params):
+        """tdv_ppf_match_batch_dev on device pointers: cloud b = rows [offsets[b], offsets[b + 1]) of d_src and d_src_normals, all against
+        one table of ppf_model_dev.  Returns ([(poses, their dicts) per instance, as ppf_match_dev returns them], peak offsets: int32
+        [n_instances + 1]); d_peaks (optional, device, 16 bytes per reference point of every instance) receives instance b's peaks from
+        peak offset b on."""
+        ci = PpfModelInfoC(**{k: info[k] for k, _ in PpfModelInfoC._fields_})
+        p = ppf_params(**params)
+        off = None if offsets is None else np.ascontiguousarray(offsets, np.int32)
+        n = 0 if off is None else len(off) - 1
+        slots = max(p.max_poses, 1)
+        poses = (PpfPoseC * max(n * slots, 1))()
+        n_poses = np.zeros(max(n, 1), np.int32)
+        peak_off = np.zeros(n + 1, np.int32)
+        _check(self._h, lib().tdv_ppf_match_batch_dev(self._h, _ptr(d_src), _ptr(d_src_normals), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals),
+                                                      int(nt), _ptr(d_model), C.byref(ci), C.c_float(thr), C.byref(p), poses, _ptr(n_poses),
+                                                      _ptr(d_peaks), _ptr(peak_off)), "tdv_ppf_match_batch_dev")
+        return [_ppf_poses(poses[b * slots:(b + 1) * slots], int(n_poses[b])) for b in range(n)], peak_off
+
+    def ppf_match_batch(self, sources, source_normals, tgt, tgt_normals, thr, want_peaks=False, **params):
+        """ppf_match_batch_dev on host clouds: lists of (n_b, 3) points and normals against one model, uploaded with torch; the table comes
+        from ppf_model_dev.  One (poses, dicts) per instance, with want_peaks (poses, dicts, peaks)."""
+        srcs, off = _instance_rows(sources)
+        nrms, noff = _instance_rows(source_normals)
+        if len(off) != len(noff) or (off != noff).any():
+            raise ValueError("ppf_match_batch: every instance needs as many normals as points")
+        import torch
+        tgt = np.array(tgt, np.float32).reshape(-1, 3); tn = np.array(tgt_normals, np.float32).reshape(-1, 3)     # (copies: torch wants writable arrays)
+        if len(tgt) != len(tn):
+            raise ValueError("ppf_match_batch: the model needs as many normals as points")
+        nt = len(tgt)
+        dev = torch.device("cuda", self.device)
+        d_src, d_sn, d_tgt, d_tn = (_upload_rows(self.device, a) for a in (srcs, nrms, tgt, tn))
+        nbytes = self.ppf_model_bytes(nt, **params)
+        buf = torch.zeros(nbytes, dtype=torch.uint8, device=dev)
+        stride = max(ppf_params(**params).ref_stride, 1)
+        n_ref = [(len(a) + stride - 1) // stride for a in srcs]
+        d_pk = torch.zeros(max(sum(n_ref), 1) * PPF_PEAK_DTYPE.itemsize, dtype=torch.uint8, device=dev) if want_peaks else None
+        torch.cuda.synchronize()
+        info = self.ppf_model_dev(d_tgt.data_ptr(), d_tn.data_ptr(), nt, buf.data_ptr(), nbytes, **params)
+        out, peak_off = self.ppf_match_batch_dev(d_src.data_ptr(), d_sn.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), nt, buf.data_ptr(), info,
+                                                 thr, d_peaks=None if d_pk is None else d_pk.data_ptr(), **params)
+        if not want_peaks:
+            return out
+        self.synchronize()
+        pk = d_pk.cpu().numpy().view(PPF_PEAK_DTYPE)
+        return [(res, more, pk[peak_off[b]:peak_off[b + 1]].copy()) for b, (res, more) in enumerate(out)]
 
     def ransac_dev(self, d_src, ns, d_tgt, nt, d_fs, d_ft, d_corr, voxel, max_iterations, confidence=0.999, seed=42, trace=False):
         """trace=True also returns the per-iteration inlier counts (host array) - and thereby makes the call evaluate every

@@ -554,6 +554,12 @@ static bool ppf_match_args_ok(const tdv_ctx* ctx, const float* src, const float*
     return std::isfinite(thr) && thr > 0.f;
 }
 static bool ppf_model_ptr_ok(const void* d_model) { return d_model && (reinterpret_cast<uintptr_t>(d_model) & 3) == 0; }
+// ... and the table with its info (tdv_ppf_match_dev, tdv_ppf_match_batch_dev)
+static bool ppf_model_info_ok(const void* d_model, const tdv_ppf_model_info* info, int nt, const PpfPlan& plan) {
+    return info && ppf_model_ptr_ok(d_model) && info->nt == nt && info->n_keys == plan.n_keys && info->n_pairs >= 0 &&
+           (size_t)info->n_pairs <= plan.cap && std::isfinite(info->diameter) && info->diameter >= 0.f && std::isfinite(info->distance_step) &&
+           info->distance_step >= 0.f;
+}
 int tdv_ppf_model_dev(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params* params, void* d_model,
                       size_t model_bytes, tdv_ppf_model_info* info) {
     PpfPlan plan;
@@ -568,13 +574,34 @@ int tdv_ppf_match_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_norma
                       int* n_poses, tdv_ppf_peak* d_peaks, int* n_ref) {
     PpfPlan plan;
     if (!ppf_match_args_ok(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
-    if (!info || !ppf_model_ptr_ok(d_model) || info->nt != nt || info->n_keys != plan.n_keys || info->n_pairs < 0 ||
-        (size_t)info->n_pairs > plan.cap || !std::isfinite(info->diameter) || info->diameter < 0.f || !std::isfinite(info->distance_step) ||
-        info->distance_step < 0.f)
-        return TDV_ERR_BAD_ARG;
+    if (!ppf_model_info_ok(d_model, info, nt, plan)) return TDV_ERR_BAD_ARG;
     TDV_TRY(begin(ctx));
     return ppf_match_run(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, d_model, *info, thr, *params, plan, out_poses, n_poses, d_peaks,
                          nullptr, n_ref);
+}
+int tdv_ppf_match_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances, const float* d_tgt,
+                            const float* d_tgt_normals, int nt, const void* d_model, const tdv_ppf_model_info* info, float thr,
+                            const tdv_ppf_params* params, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks, int* h_peak_offsets) {
+    PpfPlan plan;
+    if (n_instances < 0 || (n_instances > 0 && !h_src_offsets)) return TDV_ERR_BAD_ARG;
+    if (n_instances > 0 && h_src_offsets[0] != 0) return TDV_ERR_BAD_ARG;
+    for (int b = 0; b < n_instances; ++b)
+        if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
+    const int ns = n_instances > 0 ? h_src_offsets[n_instances] : 0;
+    if (!ppf_match_args_ok(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
+    if (!ppf_model_info_ok(d_model, info, nt, plan)) return TDV_ERR_BAD_ARG;
+    if ((long long)n_instances * params->max_poses > INT_MAX) return TDV_ERR_BAD_ARG;
+    std::vector<int> ref_off((size_t)n_instances + 1, 0);            // rule 5's n_ref per instance, summed
+    long long sum = 0;
+    for (int b = 0; b < n_instances; ++b) {
+        const long long n = h_src_offsets[b + 1] - h_src_offsets[b];
+        sum += (n + params->ref_stride - 1) / params->ref_stride;
+        if (sum > INT_MAX) return TDV_ERR_BAD_ARG;
+        ref_off[(size_t)b + 1] = (int)sum;
+    }
+    TDV_TRY(begin(ctx));
+    return ppf_match_batch_run(ctx, d_src, d_src_normals, h_src_offsets, ref_off.data(), n_instances, d_tgt, d_tgt_normals, nt, d_model, *info, thr,
+                               *params, plan, out_poses, n_poses, d_peaks, h_peak_offsets);
 }
 int tdv_ppf_match(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt, float thr,
                   const tdv_ppf_params* params, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* peaks, int* n_ref) {

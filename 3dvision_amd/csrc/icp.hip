@@ -45,6 +45,7 @@
 #include "tdv_internal.hpp"
 #include "device_linalg.hpp"
 #include "sorted_cloud.hpp"
+#include "lds_scan.hpp"
 #include <cfloat>
 #include <climits>
 #include <cmath>
@@ -101,14 +102,6 @@ __global__ void k_aos_to_soa_pad(const float* __restrict__ aos, int n, int n_pad
     if (i >= n_pad) return;
     if (i < n) { x[i] = aos[3 * i]; y[i] = aos[3 * i + 1]; z[i] = aos[3 * i + 2]; }
     else { x[i] = pad; y[i] = pad; z[i] = pad; }
-}
-
-__device__ __forceinline__ void transform_point(const float* __restrict__ T, float sx, float sy, float sz,
-                                                float& px, float& py, float& pz) {
-    // p = R*s + t with each row evaluated as r0*sx + (r1*sy + r2*sz), then + t (column-major T)
-    px = (T[0] * sx + (T[4] * sy + T[8] * sz)) + T[12];
-    py = (T[1] * sx + (T[5] * sy + T[9] * sz)) + T[13];
-    pz = (T[2] * sx + (T[6] * sy + T[10] * sz)) + T[14];
 }
 
 __global__ __launch_bounds__(NN_BLOCK)
@@ -1254,11 +1247,8 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
     __shared__ float rmeans[6];
     static_assert(!REF || SM_THREADS >= REF_TILE, "one point per thread and tile");
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int nt4 = (nt + 3) / 4;                          // targets in chunks of four, the last one padded with +inf (never a minimum)
-    for (int j = threadIdx.x; j < nt4 * 4; j += SM_THREADS) {
-        const bool in = j < nt;
-        tx[j] = in ? tgt[3 * j] : INFINITY; ty[j] = in ? tgt[3 * j + 1] : INFINITY; tz[j] = in ? tgt[3 * j + 2] : INFINITY;
-    }
+    const int nt4 = (nt + 3) / 4;                          // targets in chunks of four, the last one padded with +inf (lds_scan.hpp)
+    lds_stage_targets(tgt, nt, tx, ty, tz, SM_THREADS);
     if (threadIdx.x == 0) st = *st_in;
     __syncthreads();
     constexpr int NV = acc_nv<MODE, ROBUST>();
@@ -1274,33 +1264,7 @@ void k_icp_small(const float* __restrict__ src0, int ns0, const int* __restrict_
         for (int i = threadIdx.x; i < ns; i += SM_THREADS) {
             float px, py, pz;
             transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
-            // four targets per step (three 16-byte LDS reads at a wave-uniform address): the running minimum and the first CHUNK
-            // that reached it (strict <), then the lowest target of that chunk with that distance - the scan kernel's two-level argmin
-            float best = FLT_MAX; int bc = 0;
-            const float4* __restrict__ X4 = reinterpret_cast<const float4*>(tx);
-            const float4* __restrict__ Y4 = reinterpret_cast<const float4*>(ty);
-            const float4* __restrict__ Z4 = reinterpret_cast<const float4*>(tz);
-#pragma unroll 2
-            for (int c = 0; c < nt4; ++c) {
-                const float4 X = X4[c], Y = Y4[c], Z = Z4[c];
-                const float ax = px - X.x, ay = py - Y.x, az = pz - Z.x, bx = px - X.y, by = py - Y.y, bz = pz - Z.y;
-                const float cx = px - X.z, cy = py - Y.z, cz = pz - Z.z, ex = px - X.w, ey = py - Y.w, ez = pz - Z.w;
-                const float d0 = ax * ax + (ay * ay + az * az), d1 = bx * bx + (by * by + bz * bz);
-                const float d2 = cx * cx + (cy * cy + cz * cz), d3 = ex * ex + (ey * ey + ez * ez);
-                const float m = fminf(fminf(d0, d1), fminf(d2, d3));
-                if (m < best) { best = m; bc = c; }
-            }
-            int bi = 0;
-            if (best < FLT_MAX) {
-                bi = 4 * bc;
-#pragma unroll
-                for (int t = 3; t >= 0; --t) {
-                    const int j = 4 * bc + t;
-                    const float dx = px - tx[j], dy = py - ty[j], dz = pz - tz[j];
-                    if (dx * dx + (dy * dy + dz * dz) == best) bi = j;
-                }
-            }
-            sbest[i] = best; sidx[i] = best < FLT_MAX ? bi : 0;
+            lds_nearest(px, py, pz, tx, ty, tz, nt4, sbest[i], sidx[i]);     // the scan kernel's two-level argmin (lds_scan.hpp)
         }
         __syncthreads();
         if constexpr (REF) {

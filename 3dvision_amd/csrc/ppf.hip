@@ -7,17 +7,23 @@
 //  (iv)  k_ppf_offsets: offsets[k] = the lower bound of k in the sorted keys (one binary search per key; offsets[n_keys] = n_pairs, the
 //        first sentinel); k_ppf_model_fill: pair and alpha bits of every keyed entry (alpha is formed again from the pair).
 // Match (ppf_match_run):
-//  (v)   k_ppf_vote: one workgroup per reference point (grid-stride where there are more).  The counters are LDS (static: CELLS) or a slab
+//  (v)   k_ppf_vote: one workgroup per work item = (instance, reference point), items numbered in instance order (grid-stride where there
+//        are more; a single cloud is the batch of one, without the offset arrays).  The counters are LDS (static: CELLS) or a slab
 //        of the workspace (CELLS = 0).  A tile of PPF_THREADS scene points: each lane forms one pair's key, alpha and bucket; a block scan
 //        of the bucket lengths numbers the tile's table entries 0 .. total - 1, and the lanes take them round robin, finding an entry's
 //        pair by a binary search of the scanned lengths - so a long bucket is shared by the whole workgroup instead of stalling one lane.
 //        One integer atomic add per entry.  Then one packed-key maximum over the counters; lane 0 writes the peak and, beside it, the
 //        two points of the peak (12 floats) for the host's pose stage.  No ticket words, no spinning, no cooperative launch.
-//  (vi)  host, f64: poses of the peaks, clustering (rule 7); then icp_correspondences_dev per returned pose.
+//  (vi)  host, f64: poses of the peaks, clustering (rule 7: ppf_rank); then icp_correspondences_dev per returned pose.
+// Batch (ppf_match_batch_run): (v) once over every instance's reference points, one read-back of all peaks, (vi)'s ppf_rank per instance,
+//        then k_ppf_score: every returned pose of every instance against the model in LDS (lds_scan.hpp: the scan k_icp_small runs), one
+//        lane per source point, d2 and the accepted flag of every (pose, point) read back in one copy and summed as (vi) sums them.
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
 #include "libm_f32.hpp"
+#include "lds_scan.hpp"
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <algorithm>
@@ -183,12 +189,17 @@ __global__ __launch_bounds__(256) void k_ppf_model_fill(const float* __restrict_
 // What the host's pose stage needs of a peak: the scene point and the model point (normal as voted with: flipped where asked for)
 struct PpfPeakPoints { float ps[3], ns[3], pm[3], nm[3]; };
 
-// rules 5 and 6.  CELLS > 0: the counters are LDS (nt * R <= CELLS); CELLS == 0: slabs + blockIdx.x * nt * R.
+// The clouds of a voting launch.  A batch: instance b is rows [src_off[b], src_off[b + 1]) of src and nrm and owns the work items
+// [ref_off[b], ref_off[b + 1]) (device arrays of n_inst + 1 ints).  ref_off == nullptr: one cloud of ns rows, item = reference point.
+struct PpfClouds { const float* src; const float* nrm; int ns; const int* src_off; const int* ref_off; int n_inst; };
+
+// rules 5 and 6 for work items blockIdx.x, + gridDim.x, ...  CELLS > 0: the counters are LDS (nt * R <= CELLS); CELLS == 0: slabs +
+// blockIdx.x * nt * R.  peaks[item] and pts[item]; a peak's ref counts inside its instance.
 template <int CELLS>
 __global__ __launch_bounds__(PPF_THREADS)
-void k_ppf_vote(const float* __restrict__ src, const float* __restrict__ snrm, int ns, const float* __restrict__ tgt, const float* __restrict__ tnrm,
+void k_ppf_vote(PpfClouds cl, const float* __restrict__ tgt, const float* __restrict__ tnrm,
                 int nt, const int* __restrict__ offsets, const unsigned* __restrict__ pair, const unsigned* __restrict__ alpha, PpfQuant q,
-                int ref_stride, int n_ref, unsigned* __restrict__ slabs, tdv_ppf_peak* __restrict__ peaks, PpfPeakPoints* __restrict__ pts) {
+                int ref_stride, int n_items, unsigned* __restrict__ slabs, tdv_ppf_peak* __restrict__ peaks, PpfPeakPoints* __restrict__ pts) {
     __shared__ unsigned lds_acc[CELLS > 0 ? CELLS : 1];
     __shared__ unsigned s_start[PPF_THREADS], s_pref[PPF_THREADS];
     __shared__ float s_alpha[PPF_THREADS];
@@ -197,7 +208,19 @@ void k_ppf_vote(const float* __restrict__ src, const float* __restrict__ snrm, i
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int cells = nt * q.R;
     unsigned* acc = CELLS > 0 ? lds_acc : slabs + (size_t)blockIdx.x * (size_t)cells;
-    for (int r = blockIdx.x; r < n_ref; r += gridDim.x) {
+    for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
+        const float* __restrict__ src = cl.src; const float* __restrict__ snrm = cl.nrm;
+        int ns = cl.ns, r = item;
+        if (cl.ref_off) {                                            // the last instance b with ref_off[b] <= item: the one that has it
+            int lo = 0, hi = cl.n_inst;
+            while (hi - lo > 1) {
+                const int mid = (lo + hi) >> 1;
+                if (cl.ref_off[mid] <= item) lo = mid; else hi = mid;
+            }
+            const int row = cl.src_off[lo];
+            r = item - cl.ref_off[lo]; ns = cl.src_off[lo + 1] - row;
+            src += 3 * (size_t)row; snrm += 3 * (size_t)row;
+        }
         const int sr = r * ref_stride;
         const PpfPoint a = ppf_point(src, snrm, sr, false, true);    // workgroup-uniform
         unsigned long long best = 0;
@@ -271,8 +294,39 @@ void k_ppf_vote(const float* __restrict__ src, const float* __restrict__ snrm, i
                 pp.ps[0] = a.px; pp.ps[1] = a.py; pp.ps[2] = a.pz; pp.ns[0] = a.nx; pp.ns[1] = a.ny; pp.ns[2] = a.nz;
                 pp.pm[0] = m.px; pp.pm[1] = m.py; pp.pm[2] = m.pz; pp.nm[0] = m.nx; pp.nm[1] = m.ny; pp.nm[2] = m.nz;
             }
-            peaks[r] = pk; pts[r] = pp;
+            peaks[item] = pk; pts[item] = pp;
         }
+    }
+}
+
+// A returned pose of a batch: T (column-major), its instance, and where its rows start in d2 / accepted
+struct PpfSlot { float T[16]; int inst, pad; unsigned long long out; };
+constexpr int PPF_SCORE_THREADS = 256;
+static_assert(TDV_PPF_MODEL_MAX % 4 == 0, "the staged model is padded to fours");
+
+// rule 7's score pass for every pose slot of a batch: workgroup (x = slot, y) takes the slot's source points y * 256 + lane, + gridDim.y
+// * 256, ...; the model sits in LDS (lds_scan.hpp).  d2[out + i] is the nearest model point's squared distance (FLT_MAX: none) and
+// accepted[out + i] = d2 <= tau: per accepted row the bits of tdv_icp_correspondences at (T, thr), whichever search that call runs.
+__global__ __launch_bounds__(PPF_SCORE_THREADS)
+void k_ppf_score(const float* __restrict__ src0, const int* __restrict__ src_off, const float* __restrict__ tgt, int nt,
+                 const PpfSlot* __restrict__ slots, float tau, float* __restrict__ d2, uint8_t* __restrict__ accepted) {
+    __shared__ __attribute__((aligned(16))) float tx[TDV_PPF_MODEL_MAX], ty[TDV_PPF_MODEL_MAX], tz[TDV_PPF_MODEL_MAX];
+    const PpfSlot* __restrict__ sl = slots + blockIdx.x;
+    const int row = src_off[sl->inst], ns = src_off[sl->inst + 1] - row;
+    if ((long long)blockIdx.y * PPF_SCORE_THREADS >= (long long)ns) return;       // workgroup-uniform
+    lds_stage_targets(tgt, nt, tx, ty, tz, PPF_SCORE_THREADS);
+    __syncthreads();
+    float T[16];
+#pragma unroll
+    for (int k = 0; k < 16; ++k) T[k] = sl->T[k];
+    const float* __restrict__ src = src0 + 3 * (size_t)row;
+    const size_t out = (size_t)sl->out;
+    const int nt4 = (nt + 3) / 4;
+    for (long long i = (long long)blockIdx.y * PPF_SCORE_THREADS + threadIdx.x; i < (long long)ns; i += (long long)gridDim.y * PPF_SCORE_THREADS) {
+        float px, py, pz, best; int idx;
+        transform_point(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
+        lds_nearest(px, py, pz, tx, ty, tz, nt4, best, idx);
+        d2[out + (size_t)i] = best; accepted[out + (size_t)i] = best <= tau ? 1 : 0;
     }
 }
 
@@ -324,6 +378,85 @@ PpfQuant ppf_quant(const tdv_ppf_params& prm, const PpfPlan& plan, float step) {
     q.step = step; q.astep = PPF_PI / (float)prm.angle_bins; q.rstep = PPF_TWO_PI / (float)prm.rotation_bins;
     q.A = prm.angle_bins; q.R = prm.rotation_bins; q.n_dist = plan.n_dist; q.n_keys = plan.n_keys; q.flip = prm.flip_model_normals;
     return q;
+}
+
+// the table, as the kernels take it
+struct PpfTable { const int* offsets; const unsigned* pair; const unsigned* alpha; };
+PpfTable ppf_table(const void* d_model, const PpfPlan& plan) {
+    PpfTable t;
+    t.offsets = static_cast<const int*>(d_model);
+    t.pair = reinterpret_cast<const unsigned*>(t.offsets) + plan.off_words;
+    t.alpha = t.pair + plan.cap;
+    return t;
+}
+
+// the voting launch over n_items work items (a single cloud or a batch: PpfClouds): the counter variant and its grid cap (rule 5)
+int ppf_vote_launch(tdv_ctx* ctx, const PpfClouds& cl, int n_items, const float* d_tgt, const float* d_tgt_normals, int nt, const PpfTable& tb,
+                    const PpfQuant& q, int ref_stride, tdv_ppf_peak* peaks, PpfPeakPoints* pts) {
+    hipStream_t s = ctx->stream;
+    const int cells = nt * q.R;
+    if (cells <= PPF_LDS_SMALL) {
+        k_ppf_vote<PPF_LDS_SMALL><<<std::min(n_items, PPF_GRID_LDS), PPF_THREADS, 0, s>>>(cl, d_tgt, d_tgt_normals, nt, tb.offsets, tb.pair, tb.alpha, q,
+                                                                                         ref_stride, n_items, nullptr, peaks, pts);
+    } else if (cells <= TDV_PPF_LDS_CELLS) {
+        k_ppf_vote<TDV_PPF_LDS_CELLS><<<std::min(n_items, PPF_GRID_LDS), PPF_THREADS, 0, s>>>(cl, d_tgt, d_tgt_normals, nt, tb.offsets, tb.pair, tb.alpha,
+                                                                                             q, ref_stride, n_items, nullptr, peaks, pts);
+    } else {
+        const int grid = std::max(1, std::min(std::min(n_items, PPF_GRID_SLAB), (int)(PPF_SLAB_BYTES / ((size_t)cells * 4))));
+        unsigned* slabs;
+        TDV_TRY(ws_alloc(ctx, (size_t)grid * (size_t)cells, &slabs));
+        k_ppf_vote<0><<<grid, PPF_THREADS, 0, s>>>(cl, d_tgt, d_tgt_normals, nt, tb.offsets, tb.pair, tb.alpha, q, ref_stride, n_items, slabs, peaks, pts);
+    }
+    TDV_CHECK_LAUNCH(ctx);
+    return TDV_OK;
+}
+
+// rule 7 up to the score: the returned poses of one cloud's n_ref peaks, ranked, with T, votes, members and the founder's peak
+std::vector<tdv_ppf_pose> ppf_rank(const tdv_ppf_peak* pk, const PpfPeakPoints* pp, int n_ref, const tdv_ppf_params& prm, const tdv_ppf_model_info& info) {
+    std::vector<int> order;
+    for (int r = 0; r < n_ref; ++r) if (pk[r].votes > 0) order.push_back(r);
+    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pk[a].votes > pk[b].votes; });     // stable: ref ascending among equals
+    std::vector<Pose64> pose((size_t)n_ref);
+    for (int r : order) pose[r] = ppf_pose64(pp[r], pk[r].bin, prm.rotation_bins);
+    const double max_t = (double)prm.cluster_translation_relative * (double)info.diameter, min_c = std::cos((double)prm.cluster_rotation);
+    std::vector<PpfCluster> cl;
+    for (int r : order) {
+        size_t c = 0;
+        while (c < cl.size() && !ppf_within(pose[r], pose[cl[c].founder], max_t, min_c)) ++c;
+        if (c == cl.size()) cl.push_back({r, 0, 0});
+        cl[c].votes += pk[r].votes; cl[c].members += 1;
+    }
+    std::vector<int> top(cl.size());
+    for (size_t c = 0; c < cl.size(); ++c) top[c] = (int)c;
+    std::stable_sort(top.begin(), top.end(), [&](int a, int b) { return cl[a].votes > cl[b].votes; });
+    std::vector<tdv_ppf_pose> out(std::min(top.size(), (size_t)prm.max_poses));
+    for (size_t k = 0; k < out.size(); ++k) {
+        const PpfCluster& c = cl[top[k]];
+        const Pose64& P = pose[c.founder];
+        tdv_ppf_pose o{};
+        for (int i = 0; i < 3; ++i) {
+            for (int j = 0; j < 3; ++j) o.T[4 * j + i] = (float)P.R[i][j];
+            o.T[12 + i] = (float)P.t[i];
+        }
+        o.T[15] = 1.f;
+        o.votes = (int)std::min(c.votes, (long long)INT_MAX); o.members = c.members;
+        o.ref = pk[c.founder].ref; o.model_index = pk[c.founder].model_index; o.bin = pk[c.founder].bin;
+        out[k] = o;
+    }
+    return out;
+}
+
+// rule 7's score of a pose from its correspondence pass read back (d2: ns floats, unaligned; accepted: ns bytes) and the pass's count
+void ppf_score(tdv_ppf_pose* o, const char* d2, const uint8_t* accepted, int ns, int n_corr) {
+    double S = 0.0;
+    for (int i = 0; i < ns; ++i) {
+        float v;
+        std::memcpy(&v, d2 + (size_t)i * 4, 4);
+        if (accepted[i]) S += (double)v;
+    }
+    o->n_corr = n_corr;
+    o->fitness = (float)n_corr / (float)ns;
+    o->rmse = n_corr > 0 ? (float)std::sqrt(S / (double)n_corr) : 0.f;
 }
 
 }  // namespace
@@ -400,31 +533,15 @@ int ppf_match_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, 
     if (ns == 0 || nt < 2 || info.n_pairs == 0) return TDV_OK;
     hipStream_t s = ctx->stream;
     const int n_ref = (ns + prm.ref_stride - 1) / prm.ref_stride;
-    const int* offsets = static_cast<const int*>(d_model);
-    const unsigned* pair = reinterpret_cast<const unsigned*>(offsets) + plan.off_words;
-    const unsigned* alpha = pair + plan.cap;
-    const PpfQuant q = ppf_quant(prm, plan, info.distance_step);
-    const int cells = nt * prm.rotation_bins;
     const size_t peak_bytes = (size_t)n_ref * sizeof(tdv_ppf_peak), pts_bytes = (size_t)n_ref * sizeof(PpfPeakPoints);
     tdv_ppf_peak* peaks = d_peaks;
     PpfPeakPoints* pts;
     if (!peaks) TDV_TRY(ws_alloc(ctx, (size_t)n_ref, &peaks));
     TDV_TRY(ws_alloc(ctx, (size_t)n_ref, &pts));
     TDV_TRY(pin_reserve(ctx, std::max(peak_bytes + pts_bytes, (size_t)ns * 5 + 64)));
-    if (cells <= PPF_LDS_SMALL) {
-        k_ppf_vote<PPF_LDS_SMALL><<<std::min(n_ref, PPF_GRID_LDS), PPF_THREADS, 0, s>>>(d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, offsets, pair,
-                                                                                       alpha, q, prm.ref_stride, n_ref, nullptr, peaks, pts);
-    } else if (cells <= TDV_PPF_LDS_CELLS) {
-        k_ppf_vote<TDV_PPF_LDS_CELLS><<<std::min(n_ref, PPF_GRID_LDS), PPF_THREADS, 0, s>>>(d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, offsets,
-                                                                                           pair, alpha, q, prm.ref_stride, n_ref, nullptr, peaks, pts);
-    } else {
-        const int grid = std::max(1, std::min(std::min(n_ref, PPF_GRID_SLAB), (int)(PPF_SLAB_BYTES / ((size_t)cells * 4))));
-        unsigned* slabs;
-        TDV_TRY(ws_alloc(ctx, (size_t)grid * (size_t)cells, &slabs));
-        k_ppf_vote<0><<<grid, PPF_THREADS, 0, s>>>(d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, offsets, pair, alpha, q, prm.ref_stride, n_ref,
-                                                  slabs, peaks, pts);
-    }
-    TDV_CHECK_LAUNCH(ctx);
+    const PpfClouds one{d_src, d_src_normals, ns, nullptr, nullptr, 1};          // the batch of one
+    TDV_TRY(ppf_vote_launch(ctx, one, n_ref, d_tgt, d_tgt_normals, nt, ppf_table(d_model, plan), ppf_quant(prm, plan, info.distance_step),
+                            prm.ref_stride, peaks, pts));
     TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, peaks, peak_bytes, hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + peak_bytes, pts, pts_bytes, hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipStreamSynchronize(s));
@@ -434,39 +551,12 @@ int ppf_match_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, 
     std::memcpy(pp.data(), ctx->pin + peak_bytes, pts_bytes);
     if (h_peaks) std::memcpy(h_peaks, pk.data(), peak_bytes);
     if (n_ref_out) *n_ref_out = n_ref;
-
-    // rule 7: poses, clusters
-    std::vector<int> order;
-    for (int r = 0; r < n_ref; ++r) if (pk[r].votes > 0) order.push_back(r);
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return pk[a].votes > pk[b].votes; });     // stable: ref ascending among equals
-    std::vector<Pose64> pose((size_t)n_ref);
-    for (int r : order) pose[r] = ppf_pose64(pp[r], pk[r].bin, prm.rotation_bins);
-    const double max_t = (double)prm.cluster_translation_relative * (double)info.diameter, min_c = std::cos((double)prm.cluster_rotation);
-    std::vector<PpfCluster> cl;
-    for (int r : order) {
-        size_t c = 0;
-        while (c < cl.size() && !ppf_within(pose[r], pose[cl[c].founder], max_t, min_c)) ++c;
-        if (c == cl.size()) cl.push_back({r, 0, 0});
-        cl[c].votes += pk[r].votes; cl[c].members += 1;
-    }
-    std::vector<int> top(cl.size());
-    for (size_t c = 0; c < cl.size(); ++c) top[c] = (int)c;
-    std::stable_sort(top.begin(), top.end(), [&](int a, int b) { return cl[a].votes > cl[b].votes; });
-    const int n_out = (int)std::min(top.size(), (size_t)prm.max_poses);
+    std::vector<tdv_ppf_pose> poses = ppf_rank(pk.data(), pp.data(), n_ref, prm, info);
 
     // score: tdv_icp_correspondences at each returned pose
     const WsMark mark = ws_mark(ctx);
-    for (int k = 0; k < n_out; ++k) {
-        const PpfCluster& c = cl[top[k]];
-        const Pose64& P = pose[c.founder];
-        tdv_ppf_pose o{};
-        for (int i = 0; i < 3; ++i) {
-            for (int j = 0; j < 3; ++j) o.T[4 * j + i] = (float)P.R[i][j];
-            o.T[12 + i] = (float)P.t[i];
-        }
-        o.T[15] = 1.f;
-        o.votes = (int)std::min(c.votes, (long long)INT_MAX); o.members = c.members;
-        o.ref = pk[c.founder].ref; o.model_index = pk[c.founder].model_index; o.bin = pk[c.founder].bin;
+    for (size_t k = 0; k < poses.size(); ++k) {
+        tdv_ppf_pose& o = poses[k];
         ws_rewind(ctx, mark);
         IcpOutputs io;
         TDV_TRY(ws_alloc(ctx, (size_t)ns, &io.d2));
@@ -477,20 +567,99 @@ int ppf_match_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, 
         TDV_HIP(ctx, hipMemcpyAsync(h, io.d2, (size_t)ns * 4, hipMemcpyDeviceToHost, s));
         TDV_HIP(ctx, hipMemcpyAsync(h + (size_t)ns * 4, io.accepted, (size_t)ns, hipMemcpyDeviceToHost, s));
         TDV_HIP(ctx, hipStreamSynchronize(s));
-        const uint8_t* acc = reinterpret_cast<const uint8_t*>(h + (size_t)ns * 4);
-        double S = 0.0;
-        for (int i = 0; i < ns; ++i) {
-            float d2;
-            std::memcpy(&d2, h + (size_t)i * 4, 4);
-            if (acc[i]) S += (double)d2;
-        }
-        o.n_corr = n_corr;
-        o.fitness = (float)n_corr / (float)ns;
-        o.rmse = n_corr > 0 ? (float)std::sqrt(S / (double)n_corr) : 0.f;
+        ppf_score(&o, h, reinterpret_cast<const uint8_t*>(h + (size_t)ns * 4), ns, n_corr);
         out_poses[k] = o;
     }
-    *n_poses = n_out;
+    *n_poses = (int)poses.size();
+    return TDV_OK;
+}
+
+// Per instance, ppf_match_run: one voting launch over every instance's reference points, one read-back of all peaks, ppf_rank per instance,
+// one scoring launch over every returned pose, one read-back of their d2 / accepted rows.  h_ref_off[b]: the instances' reference offsets
+// (the entry point formed and checked them); out_poses, n_poses and h_peak_off as include/tdv_hip.h has them.
+int ppf_match_batch_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_off, const int* h_ref_off, int n_inst,
+                        const float* d_tgt, const float* d_tgt_normals, int nt, const void* d_model, const tdv_ppf_model_info& info, float thr,
+                        const tdv_ppf_params& prm, const PpfPlan& plan, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks,
+                        int* h_peak_off) {
+    for (int b = 0; b < n_inst; ++b) n_poses[b] = 0;
+    if (h_peak_off) for (int b = 0; b <= n_inst; ++b) h_peak_off[b] = 0;
+    const int n_items = n_inst > 0 ? h_ref_off[n_inst] : 0;
+    if (n_items == 0 || nt < 2 || info.n_pairs == 0) return TDV_OK;
+    hipStream_t s = ctx->stream;
+    const size_t n_off = (size_t)n_inst + 1;
+    const size_t off_bytes = align_up(2 * n_off * sizeof(int), 64);
+    const size_t peak_bytes = (size_t)n_items * sizeof(tdv_ppf_peak), pts_bytes = (size_t)n_items * sizeof(PpfPeakPoints);
+    int* d_off;                                                      // src_off[n_off], then ref_off[n_off]
+    tdv_ppf_peak* peaks = d_peaks;
+    PpfPeakPoints* pts;
+    TDV_TRY(ws_alloc(ctx, 2 * n_off, &d_off));
+    if (!peaks) TDV_TRY(ws_alloc(ctx, (size_t)n_items, &peaks));
+    TDV_TRY(ws_alloc(ctx, (size_t)n_items, &pts));
+    TDV_TRY(pin_reserve(ctx, off_bytes + peak_bytes + pts_bytes));
+    std::memcpy(ctx->pin, h_src_off, n_off * sizeof(int));
+    std::memcpy(ctx->pin + n_off * sizeof(int), h_ref_off, n_off * sizeof(int));
+    TDV_HIP(ctx, hipMemcpyAsync(d_off, ctx->pin, 2 * n_off * sizeof(int), hipMemcpyHostToDevice, s));
+    const PpfClouds cl{d_src, d_src_normals, 0, d_off, d_off + n_off, n_inst};
+    TDV_TRY(ppf_vote_launch(ctx, cl, n_items, d_tgt, d_tgt_normals, nt, ppf_table(d_model, plan), ppf_quant(prm, plan, info.distance_step),
+                            prm.ref_stride, peaks, pts));
+    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + off_bytes, peaks, peak_bytes, hipMemcpyDeviceToHost, s));
+    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + off_bytes + peak_bytes, pts, pts_bytes, hipMemcpyDeviceToHost, s));
+    TDV_HIP(ctx, hipStreamSynchronize(s));                           // read-back 1 of 2
+    std::vector<tdv_ppf_peak> pk((size_t)n_items);
+    std::vector<PpfPeakPoints> pp((size_t)n_items);
+    std::memcpy(pk.data(), ctx->pin + off_bytes, peak_bytes);
+    std::memcpy(pp.data(), ctx->pin + off_bytes + peak_bytes, pts_bytes);
+
+    // rule 7 per instance; a slot per returned pose, its rows of d2 / accepted one after the other
+    std::vector<tdv_ppf_pose> poses;
+    std::vector<PpfSlot> slots;
+    size_t rows = 0;
+    int ns_max = 0;
+    for (int b = 0; b < n_inst; ++b) {
+        const int r0 = h_ref_off[b], n_ref = h_ref_off[b + 1] - r0, ns = h_src_off[b + 1] - h_src_off[b];
+        const std::vector<tdv_ppf_pose> got = ppf_rank(pk.data() + r0, pp.data() + r0, n_ref, prm, info);
+        n_poses[b] = (int)got.size();
+        for (const tdv_ppf_pose& o : got) {
+            PpfSlot sl{};
+            std::memcpy(sl.T, o.T, sizeof(sl.T));
+            sl.inst = b; sl.out = rows;
+            rows += (size_t)ns;
+            slots.push_back(sl); poses.push_back(o);
+        }
+        if (!got.empty()) ns_max = std::max(ns_max, ns);
+    }
+    if (!slots.empty()) {
+        const size_t slot_bytes = align_up(slots.size() * sizeof(PpfSlot), 64);
+        PpfSlot* d_slots; float* d_d2; uint8_t* d_acc;
+        TDV_TRY(ws_alloc(ctx, slots.size(), &d_slots));
+        TDV_TRY(ws_alloc(ctx, rows, &d_d2));
+        TDV_TRY(ws_alloc(ctx, rows, &d_acc));
+        TDV_TRY(pin_reserve(ctx, slot_bytes + rows * 5));            // (the stream is idle: the staging may move)
+        std::memcpy(ctx->pin, slots.data(), slots.size() * sizeof(PpfSlot));
+        TDV_HIP(ctx, hipMemcpyAsync(d_slots, ctx->pin, slots.size() * sizeof(PpfSlot), hipMemcpyHostToDevice, s));
+        const unsigned gy = (unsigned)std::min<long long>(((long long)ns_max + PPF_SCORE_THREADS - 1) / PPF_SCORE_THREADS, 65535);
+        k_ppf_score<<<dim3((unsigned)slots.size(), gy), PPF_SCORE_THREADS, 0, s>>>(d_src, d_off, d_tgt, nt, d_slots, tau_le(thr), d_d2, d_acc);
+        TDV_CHECK_LAUNCH(ctx);
+        char* h_d2 = ctx->pin + slot_bytes;
+        const uint8_t* h_acc = reinterpret_cast<const uint8_t*>(h_d2 + rows * 4);
+        TDV_HIP(ctx, hipMemcpyAsync(h_d2, d_d2, rows * 4, hipMemcpyDeviceToHost, s));
+        TDV_HIP(ctx, hipMemcpyAsync(h_d2 + rows * 4, d_acc, rows, hipMemcpyDeviceToHost, s));
+        TDV_HIP(ctx, hipStreamSynchronize(s));                       // read-back 2 of 2
+        ctx->last_icp_search = TDV_ICP_SEARCH_BRUTE;
+        for (size_t k = 0; k < slots.size(); ++k) {
+            const int ns = h_src_off[slots[k].inst + 1] - h_src_off[slots[k].inst];
+            const uint8_t* acc = h_acc + slots[k].out;
+            int n_corr = 0;
+            for (int i = 0; i < ns; ++i) n_corr += acc[i] ? 1 : 0;
+            ppf_score(&poses[k], h_d2 + slots[k].out * 4, acc, ns, n_corr);
+        }
+    }
+    size_t k = 0;
+    for (int b = 0; b < n_inst; ++b)
+        for (int j = 0; j < n_poses[b]; ++j) out_poses[(size_t)b * (size_t)prm.max_poses + (size_t)j] = poses[k++];
+    if (h_peak_off) std::memcpy(h_peak_off, h_ref_off, n_off * sizeof(int));
     return TDV_OK;
 }
 
 }  // namespace tdv
+

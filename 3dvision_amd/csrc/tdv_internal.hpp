@@ -334,7 +334,8 @@ int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& p
 
 // PPF matching (ppf.hip, include/tdv_hip.h: tdv_ppf_match).  PpfPlan: what the parameters alone fix (n_dist, n_keys, the table's layout for
 // nt points); ppf_plan is the parameter check of every entry point.  ppf_model_run builds the table (rule 4) into d_model and fills info;
-// ppf_match_run votes, clusters and scores (h_peaks: where a host call's peaks go).  Neither resets the workspace: the entry point did.
+// ppf_match_run votes, clusters and scores (h_peaks: where a host call's peaks go); ppf_match_batch_run is it per instance of an offsets
+// batch (h_ref_off: the reference offsets the entry point formed from h_src_off and checked).  None resets the workspace: the entry point did.
 struct PpfPlan { int n_dist, n_keys; size_t off_words, cap, bytes; };
 bool ppf_plan(const tdv_ppf_params* p, int nt, PpfPlan* plan);
 int ppf_model_run(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params& prm, const PpfPlan& plan,
@@ -342,6 +343,10 @@ int ppf_model_run(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, 
 int ppf_match_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
                   const void* d_model, const tdv_ppf_model_info& info, float thr, const tdv_ppf_params& prm, const PpfPlan& plan,
                   tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks, tdv_ppf_peak* h_peaks, int* n_ref);
+int ppf_match_batch_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_off, const int* h_ref_off, int n_inst,
+                        const float* d_tgt, const float* d_tgt_normals, int nt, const void* d_model, const tdv_ppf_model_info& info, float thr,
+                        const tdv_ppf_params& prm, const PpfPlan& plan, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks,
+                        int* h_peak_off);
 
 // normals + FPFH in one go, sharing one spatial sort and one radius scan (batch path; identical results)
 // d_tie_ids / d_tie_ids_inv (optional, both or neither): neighbour lists are ordered by (d2, d_tie_ids[index]) instead of

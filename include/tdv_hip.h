@@ -599,7 +599,8 @@ int tdv_segment_planes_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_pl
  * noise points in ascending index; *n_labelled (optional) = the labelled ones.  grouped_xyz (optional, float[3n]): the rows of the
  * cloud in that order.  offsets (HOST memory in either entry point, room for offsets_capacity + 1 ints): cluster b is
  * [offsets[b], offsets[b + 1]) of order and grouped_xyz, offsets[n_clusters] = n_labelled - the (d_src, h_src_offsets) layout of
- * tdv_icp_batch_dev, tdv_gicp_batch_dev and tdv_voxel_downsample_batch_dev: cluster b goes straight into a batch call.  When
+ * tdv_icp_batch_dev, tdv_gicp_batch_dev, tdv_voxel_downsample_batch_dev and (with the clusters' normals laid out likewise)
+ * tdv_ppf_match_batch_dev, which finds the start poses the first two need: cluster b goes straight into a batch call.  When
  * n_clusters > offsets_capacity (NULL with capacity 0 is a query) the call returns TDV_ERR_BAD_ARG with result, labels, order,
  * grouped_xyz and n_labelled written and offsets untouched.
  * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params or result; a NULL cloud with n > 0; n < 0; eps not finite
@@ -833,8 +834,25 @@ int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss
  * tdv_ppf_model_bytes; an info that does not fit the call (info->nt != nt, n_keys other than the parameters give, n_pairs outside
  * [0, nt * (nt - 1)], a diameter or distance_step that is NaN, infinite or < 0).  Accepted and empty (status OK, *n_poses = 0, *n_ref = 0,
  * no peak written): ns == 0, nt < 2, or a table without pairs.  The call obeys the ctx's state rule (README, "What a context keeps
- * between calls").  Not provided: PPF inside tdv_register_batch_dev (an ABI change), a batched (offsets) form, the C++ operator mirror,
- * averaging the poses of a cluster, an absolute distance step, voting into neighbouring bins. */
+ * between calls").
+ * tdv_ppf_match_batch_dev is, per instance, tdv_ppf_match_dev: instance b is rows [h_src_offsets[b], h_src_offsets[b + 1]) of d_src and
+ * d_src_normals (the layout of tdv_icp_batch_dev and of tdv_cluster_dbscan_dev's output), and its poses (out_poses + b * max_poses, every
+ * field), n_poses[b] and peaks are byte for byte what tdv_ppf_match_dev returns for that cloud alone on the same ctx; a peak's ref counts
+ * inside its instance.  Instance b's peaks start at h_peak_offsets[b] = the sum over a < b of ceil(ns_a / ref_stride) (h_peak_offsets, optional,
+ * host, [n_instances + 1]; d_peaks, optional, device, [h_peak_offsets[n_instances]]).  An instance without points has n_poses[b] = 0 and no
+ * peak.  All instances' reference points vote in one launch (a workgroup takes work items = (instance, reference point) in instance order and
+ * finds an item's instance by binary search in the reference offsets, uploaded with the call) and all returned poses are scored in one
+ * launch: the model in LDS, one lane per source point, the brute scan of tdv_icp_correspondences.  Every search gives the same accepted
+ * rows and the scores use only those, so the ctx's ICP search switch does not enter the result; after a call that scored at least one
+ * pose tdv_ctx_last_icp_search reports TDV_ICP_SEARCH_BRUTE.  The call reads back twice in all: the peaks, then d2 and the accepted flag of
+ * every (returned pose, source point), summed on the host as rule 7 says: 5 bytes x the sum over b of n_poses[b] * ns_b of workspace and of
+ * pinned staging (8 poses of 256 instances of 1,446 points: 14.8 MB), neither capped nor chunked.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: the list of tdv_ppf_match_dev (ns being h_src_offsets[n_instances]), and
+ * n_instances < 0; NULL h_src_offsets with n_instances > 0; offsets that do not start at 0 or that decrease; a sum of reference points or
+ * n_instances * max_poses beyond INT_MAX.  Accepted and empty (status OK, every n_poses[b] = 0, every h_peak_offsets entry 0, no peak
+ * written): n_instances == 0, no instance with a point, nt < 2, or a table without pairs.  The call obeys the ctx's state rule.
+ * Not provided: PPF inside tdv_register_batch_dev (an ABI change), a host-array form of the batch, several models in one call, the C++
+ * operator mirror, averaging the poses of a cluster, an absolute distance step, voting into neighbouring bins. */
 #define TDV_PPF_MODEL_MAX 2048
 #define TDV_PPF_POSES_MAX 64
 #define TDV_PPF_KEYS_MAX (1 << 24)
@@ -875,6 +893,14 @@ int tdv_ppf_match_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_norma
                       int nt, const void* d_model, const tdv_ppf_model_info* info, float thr, const tdv_ppf_params* params,
                       tdv_ppf_pose* out_poses /* host, [max_poses] */, int* n_poses, tdv_ppf_peak* d_peaks /* optional, device */,
                       int* n_ref /* host, optional */);
+int tdv_ppf_match_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals,
+                            const int* h_src_offsets /* host, [n_instances + 1], starting at 0, non-decreasing */, int n_instances,
+                            const float* d_tgt, const float* d_tgt_normals, int nt, const void* d_model, const tdv_ppf_model_info* info,
+                            float thr, const tdv_ppf_params* params,
+                            tdv_ppf_pose* out_poses /* host, [n_instances * max_poses]: instance b's poses at b * max_poses */,
+                            int* n_poses /* host, [n_instances] */,
+                            tdv_ppf_peak* d_peaks /* optional, device, [sum of the instances' n_ref] */,
+                            int* h_peak_offsets /* optional, host, [n_instances + 1] */);
 int tdv_ppf_match(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
                   float thr, const tdv_ppf_params* params, tdv_ppf_pose* out_poses /* [max_poses] */, int* n_poses,
                   tdv_ppf_peak* peaks /* optional, host, [ceil(ns / ref_stride)] */, int* n_ref /* optional */);

@@ -14,6 +14,12 @@ scene's normals + FPFH and RANSAC (what the descriptor chain needs), and the pos
 tdv_icp_dev refinement for the best-fitness PPF pose and for RANSAC's.  Prints one JSON line.
 
     python tools/bench_ppf.py [--repeats 7] [--hyps 10000] [--icp-iters 50]
+
+With --instances B[,B...] it measures the batch instead: the test scene's instances (tests/ppf_scene.py: build(synth, seed, k), k = 1..B, one
+model) back to back on the device, the table built once; one tdv_ppf_match_batch_dev call against a loop of B tdv_ppf_match_dev calls, both
+warmed, alternating, --repeats rounds: median, minimum and maximum of each in ms, and whether both returned the same poses.
+
+    python tools/bench_ppf.py --instances 64,256 [--repeats 7]
 """
 import argparse
 import importlib
@@ -90,8 +96,65 @@ def compare(torch, ctx, synth, d, T_gt, voxel, score_thr, icp_thr, args, ppf_kw)
     return out
 
 
+def batch_against_loop(torch, tdv, ctx, synth, S, n_inst, args):
+    """One batch call against n_inst single calls on the same device buffers and table."""
+    dev = torch.device("cuda", 0)
+    scenes = [S.build(synth, args.seed, k) for k in range(1, n_inst + 1)]
+    off = np.zeros(n_inst + 1, np.int32)
+    off[1:] = np.cumsum([len(sc["scene"]) for sc in scenes])
+    up = lambda a: torch.from_numpy(np.array(a, np.float32)).to(dev)   # noqa: E731
+    d_src, d_sn = up(np.concatenate([sc["scene"] for sc in scenes])), up(np.concatenate([sc["scene_normals"] for sc in scenes]))
+    d_tgt, d_tn = up(scenes[0]["model"]), up(scenes[0]["model_normals"])
+    nt = int(d_tgt.shape[0])
+    nbytes = ctx.ppf_model_bytes(nt)
+    table = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+    torch.cuda.synchronize()
+    info = ctx.ppf_model_dev(d_tgt.data_ptr(), d_tn.data_ptr(), nt, table.data_ptr(), nbytes)
+    ps, pn, pt, ptn, ptab = d_src.data_ptr(), d_sn.data_ptr(), d_tgt.data_ptr(), d_tn.data_ptr(), table.data_ptr()
+    # (through ctypes directly: the Python wrappers' result objects would be timed with the calls)
+    lib, C = tdv.lib(), tdv.C
+    prm = tdv.ppf_params()
+    ci = tdv.PpfModelInfoC(**{k: info[k] for k, _ in tdv.PpfModelInfoC._fields_})
+    b_poses = (tdv.PpfPoseC * (n_inst * prm.max_poses))(); b_n = (C.c_int * n_inst)()
+    l_poses = (tdv.PpfPoseC * (n_inst * prm.max_poses))(); l_n = (C.c_int * n_inst)()
+    h_off = (C.c_int * (n_inst + 1))(*[int(v) for v in off])
+    V = C.c_void_p
+
+    def batch():
+        st = lib.tdv_ppf_match_batch_dev(ctx._h, V(ps), V(pn), h_off, n_inst, V(pt), V(ptn), nt, V(ptab), C.byref(ci), C.c_float(S.THR), C.byref(prm),
+                                         b_poses, b_n, None, None)
+        assert st == 0, st
+
+    def loop():
+        one = C.sizeof(tdv.PpfPoseC) * prm.max_poses
+        for b in range(n_inst):
+            st = lib.tdv_ppf_match_dev(ctx._h, V(ps + 12 * int(off[b])), V(pn + 12 * int(off[b])), int(off[b + 1] - off[b]), V(pt), V(ptn), nt, V(ptab),
+                                       C.byref(ci), C.c_float(S.THR), C.byref(prm), C.byref(l_poses, b * one), C.byref(l_n, 4 * b), None, None)
+            assert st == 0, st
+
+    runs = dict(batch=batch, loop=loop)
+    for f in runs.values():
+        f()
+    torch.cuda.synchronize()
+    same = list(b_n) == list(l_n) and all(bytes(b_poses[b * prm.max_poses + k]) == bytes(l_poses[b * prm.max_poses + k])
+                                          for b in range(n_inst) for k in range(b_n[b]))
+    times = {k: [] for k in runs}
+    for _ in range(args.repeats):
+        for k, f in runs.items():
+            t = time.perf_counter()
+            f()
+            torch.cuda.synchronize()
+            times[k].append(1e3 * (time.perf_counter() - t))
+    out = dict(instances=n_inst, points=int(off[-1]), nt=nt, poses=int(sum(b_n)), same_bytes=bool(same))
+    for k, v in times.items():
+        out[k] = dict(median_ms=round(float(np.median(v)), 3), min_ms=round(min(v), 3), max_ms=round(max(v), 3))
+    out["batch_below_loop_by_more_than_its_spread"] = bool(out["loop"]["median_ms"] - out["batch"]["median_ms"] > out["loop"]["max_ms"] - out["loop"]["min_ms"])
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--instances", type=str, default="", help="B[,B...]: time one batch call against B single calls, nothing else")
     ap.add_argument("--repeats", type=int, default=7)
     ap.add_argument("--hyps", type=int, default=10000)
     ap.add_argument("--icp-iters", type=int, default=50)
@@ -104,6 +167,11 @@ def main():
     import ppf_scene as S
     dev = torch.device("cuda", 0)
     ctx = tdv.Context(0)
+    if args.instances:
+        res = [batch_against_loop(torch, tdv, ctx, synth, S, int(b), args) for b in args.instances.split(",")]
+        ctx.close()
+        print(json.dumps(dict(tool="bench_ppf", batch=res)))
+        return
     res = {}
 
     # C4: instance 0 of bench_refine.py's scene, prepared on the device
