@@ -1116,6 +1116,19 @@ class Context:
                "tdv_study_probe")
         return d_out.cpu().numpy() if host else d_out
 
+    # op -> code of tdv_study_primitive (csrc/probe.hip: what each op takes in in0..in2 and writes to out0..out3)
+    STUDY_PRIMITIVE_OPS = {"exclusive_scan": 0, "sort_records": 1, "segment_sort": 2, "compact": 3, "tree_sum": 4, "tree_count": 5,
+                           "tree_block_max": 6}
+
+    def study_primitive(self, op, n, width=1, in0=None, in1=None, in2=None, out0=None, out1=None, out2=None, out3=None):
+        """One shared device primitive (csrc/sort.hip, flag_gather.hpp, fixed_tree.hpp) on device pointers (ints), as the table in
+        csrc/probe.hip lays them out; returns once the results are there.  The study library only: raises TdvError on the product
+        library, which has no such entry point."""
+        if not hasattr(lib(), "tdv_study_primitive"):
+            raise TdvError("study_primitive needs the study library (TDV_LIB_VARIANT=study); the product library has no probe")
+        _check(self._h, lib().tdv_study_primitive(self._h, self.STUDY_PRIMITIVE_OPS[op], C.c_longlong(n), C.c_longlong(width), _ptr(in0), _ptr(in1),
+                                                  _ptr(in2), _ptr(out0), _ptr(out1), _ptr(out2), _ptr(out3)), "tdv_study_primitive")
+
     def depth_to_cloud_dev(self, d_raw, d_mask, d_bgr, w, h, scale, fx, fy, cx, cy, zmax, d_xyz, d_rgb, capacity,
                            mask_mode=TDV_MASK_THRESHOLD10):
         n = C.c_int()

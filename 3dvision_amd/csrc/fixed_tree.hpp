@@ -4,6 +4,9 @@
 // i / 256, thread i % 256; a workgroup sum is the shuffle tree over each wave, then (w0 + w1) + (w2 + w3); one workgroup then adds the
 // workgroup sums t, t + 256, ... into thread t and sums its 256 threads the same way.  One order, so two calls give the same bits.
 // Device code for workgroups of 256 threads, compiled without contraction (the library's -ffp-contract=off).
+// Held to that order bit for bit: tests/fixed_tree_restatement.py restates it from the header's text, tests/test_gpu_primitives_probe.py
+// compares these functions with it through the study library's probe (probe.hip), tests/test_gpu_outlier.py and test_gpu_iss.py through
+// the product entry points.
 #pragma once
 #include "tdv_internal.hpp"
 

@@ -1,4 +1,6 @@
 // The generic device primitives: the radix sort of pairs (first), the bitonic sorts of 16-byte records and the exclusive scan (below).
+// Each has a direct test: tests/test_gpu_sort.py (the radix sort against a stable argsort), tests/test_gpu_primitives_probe.py (the
+// bitonic sorts at every shape of their launch chain and the scan up to three rounds of its last workgroup's loop, through probe.hip).
 //
 // Stable LSD radix sort of (64-bit key, 32-bit value) pairs on the low `end_bit` bits of the key, hand-written for gfx950 (round 4;
 // rounds 2-3 called rocPRIM's device radix sort here).  Used by the descriptor index build (csrc/fmatch_index.hip: two sorts of ~150k

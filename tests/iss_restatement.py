@@ -6,13 +6,16 @@ order, vectorised over points (numpy neither contracts nor reorders them).  Ever
 it byte for byte.
 
 Rule 8 (the default radii): the kNN list at k = 2 by the library's (d2 bits, index) key, as outlier_restatement builds its lists.  The
-resolution is summed with math.fsum (exact); `resolution_bound` bounds the device's fixed tree against it from the tree's depth alone.
+resolution comes twice: `resolution_in_tree_order` sums in the header's fixed order (the statistical filter's rule 4,
+tests/fixed_tree_restatement.py) and the device is held to its bytes; `resolution` sums with math.fsum (exact), and `resolution_bound`
+bounds the fixed tree - the device's and the restated one - against it from the tree's depth alone.
 """
 import math
 
 import numpy as np
 
 import cluster_restatement as CR
+import fixed_tree_restatement as FT
 import outlier_restatement as OR
 
 F = np.float32
@@ -201,6 +204,15 @@ def resolution(xyz, nn_of=nearest):
     valid = np.isfinite(nn)
     nv = int(valid.sum())
     return (np.float64(math.fsum(nn[valid])) / np.float64(nv) if nv else OR.NAN), nv, nn
+
+
+def resolution_in_tree_order(xyz, nn_of=nearest):
+    """(resolution, n_valid, nn): rule 8 as the header states it - the term of point i is nn_i where it is valid and +0.0 elsewhere, summed
+    in the fixed f64 tree of the statistical filter's rule 4, then one division."""
+    nn = nn_of(xyz) if len(np.asarray(xyz).reshape(-1, 3)) else np.zeros(0)
+    valid = np.isfinite(nn)
+    nv = int(valid.sum())
+    return (np.float64(FT.tree_sum(np.where(valid, nn, 0.0)) / np.float64(nv)) if nv else OR.NAN), nv, nn
 
 
 def default_radii(res):

@@ -4,14 +4,16 @@ rule by rule as the header states it.  It shares nothing with the device's searc
 `statistical_brute` is the definition read literally, O(n^2): per query every f32 d2, the (d2 bits, index) order, the first k.
 `statistical` takes its candidates from scipy's cKDTree: k nearest in f64 bound the k-th f32 d2 from above, a ball of a slightly larger
 radius holds every row that can reach the list, and the f32 expression and the (d2 bits, index) order decide among them.  Rows that are
-not clean (NaN, infinite, or so large that d2 could overflow) are done as in the brute variant.  The statistics are summed with
-math.fsum (exact): the device's fixed tree is held to them within a bound the GPU test derives.
+not clean (NaN, infinite, or so large that d2 could overflow) are done as in the brute variant.  The statistics come twice: summed with
+math.fsum (exact), and - under the key "tree" - in the header's own order (rule 4, tests/fixed_tree_restatement.py).  The device is held to
+the second byte for byte, and both the device and the second to the first within a bound derived below.
 """
 import math
 
 import numpy as np
 
 import cluster_restatement as CR
+import fixed_tree_restatement as FT
 
 F = np.float32
 NAN = np.float64(np.nan)
@@ -111,17 +113,40 @@ def _statistics(mean, std_ratio):
     return valid, nv, cloud_mean, std_dev, threshold, mask
 
 
+def _statistics_tree(mean, std_ratio):
+    """Rules 3-5 with rule 4's sums in the header's fixed order: the term of point i is its mean (pass 2: its squared deviation from the
+    restated cloud_mean) where it is valid and +0.0 elsewhere; division, square root, product and sum are single f64 operations."""
+    with np.errstate(invalid="ignore"):
+        valid = np.isfinite(mean) & (mean > 0)
+    nv = int(valid.sum())
+    safe = np.where(valid, mean, 0.0)
+    cloud_mean = FT.tree_sum(safe) / np.float64(nv) if nv > 0 else NAN
+    std_dev = NAN
+    if nv > 1:
+        dev = safe - cloud_mean
+        std_dev = np.sqrt(FT.tree_sum(np.where(valid, dev * dev, 0.0)) / np.float64(nv - 1))
+    with np.errstate(invalid="ignore"):
+        threshold = cloud_mean + np.float64(std_ratio) * std_dev
+        mask = valid & (mean < threshold)
+    return valid, nv, np.float64(cloud_mean), np.float64(std_dev), np.float64(threshold), mask
+
+
 def _statistical(xyz, nb_neighbors, std_ratio, rgb, means):
     xyz = np.asarray(xyz, F).reshape(-1, 3)
     mean = means(xyz, nb_neighbors) if len(xyz) else np.zeros(0)
-    valid, nv, cloud_mean, std_dev, threshold, mask = _statistics(mean, std_ratio)
-    index, rows, cols = _kept_rows(xyz, rgb, mask)
-    return dict(n_valid=nv, n_kept=int(mask.sum()), cloud_mean=cloud_mean, std_dev=std_dev, threshold=threshold, mask=mask.astype(np.uint8),
-                mean=mean, index=index, xyz=rows, rgb=cols, valid=valid)
+    out = []
+    for statistics in (_statistics, _statistics_tree):
+        valid, nv, cloud_mean, std_dev, threshold, mask = statistics(mean, std_ratio)
+        index, rows, cols = _kept_rows(xyz, rgb, mask)
+        out.append(dict(n_valid=nv, n_kept=int(mask.sum()), cloud_mean=cloud_mean, std_dev=std_dev, threshold=threshold,
+                        mask=mask.astype(np.uint8), mean=mean, index=index, xyz=rows, rgb=cols, valid=valid))
+    out[0]["tree"] = out[1]                                  # the exact-sum form, and the header's order under "tree"
+    return out[0]
 
 
 def statistical(xyz, nb_neighbors, std_ratio, rgb=None):
-    """dict(n_valid, n_kept, cloud_mean, std_dev, threshold, mask uint8[n], mean float64[n], index int32[n_kept], xyz, rgb, valid)."""
+    """dict(n_valid, n_kept, cloud_mean, std_dev, threshold, mask uint8[n], mean float64[n], index int32[n_kept], xyz, rgb, valid) with
+    exact sums, and under "tree" the same dict with rule 4's sums in the header's fixed order."""
     return _statistical(xyz, nb_neighbors, std_ratio, rgb, means_tree)
 
 

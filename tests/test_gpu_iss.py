@@ -2,10 +2,11 @@
 the device entry points, each test on a Context of its own.
 
 Byte for byte, with no gap condition: the four counts, mask, support, saliency and eigenvalues (f64 arrays: the integer sums and the fixed
-f64 schedule fix every bit), index and the keypoints' xyz / attr rows.  With the default radii the device's resolution is held to the
-restatement's exact-sum value within iss_restatement.resolution_bound (the fixed tree's depth times 2^-53, nothing measured), the reported
-radii to float32(6 * resolution) and float32(4 * resolution) of the REPORTED resolution, and everything else to the restatement run at
-the reported radii."""
+f64 schedule fix every bit), index and the keypoints' xyz / attr rows.  With the default radii the device's resolution is the bytes of
+rule 8 restated in the header's fixed order of additions (iss_restatement.resolution_in_tree_order), the radii are float32(6 * resolution)
+and float32(4 * resolution) of that RESTATED resolution, and everything else is the restatement run at those radii.  The device's and the
+restated resolution are also held to the exact-sum value within iss_restatement.resolution_bound (the fixed tree's depth times 2^-53,
+nothing measured)."""
 import ctypes as C
 import zlib
 
@@ -83,26 +84,31 @@ def check(ctx, pts, attr=None, what=None, ref=None, **params):
 
 
 def check_defaults(ctx, pts, attr=None, what=None, **params):
-    """Default radii: the resolution within the tree's bound of the exact-sum value, the radii made of the reported resolution, everything
-    else byte-equal to the restatement at the reported radii."""
+    """Default radii: the resolution is the restated tree order's bytes (and within the tree's bound of the exact-sum value), the radii
+    are made of the restated resolution, everything else is byte-equal to the restatement at those radii."""
     pts = np.ascontiguousarray(pts, F).reshape(-1, 3)
     n = len(pts)
     exact = R.resolution(pts)[0]
     bound = R.resolution_bound(exact, n)
-    ref = None
+    restated = np.float64(R.resolution_in_tree_order(pts)[0])
+    rs, rn = R.default_radii(restated)
+    if np.isnan(exact):
+        assert np.isnan(restated)
+    else:
+        assert abs(restated - exact) <= bound, (what, "the restated order against the exact sum", restated, exact, bound)
+    ref = R.iss(pts, attr, **dict(params, salient_radius=rs, non_max_radius=rn)) if np.isfinite(rs) and rs > 0 else \
+        R.iss(pts, attr, **dict(params, salient_radius=np.nan, non_max_radius=np.nan)) if np.isnan(rs) else None
+    same_radius = lambda a, b: F(a).tobytes() == F(b).tobytes() or (np.isnan(a) and np.isnan(b))      # noqa: E731
     for name, got in (("host", ctx.iss(pts, attr, **params)), ("dev", dev_call(ctx, pts, attr, **params))):
         res = np.float64(got["resolution"])
-        print(what, n, name, "resolution %.17g exact %.17g bound %.3g" % (res, exact, bound))
+        print(what, n, name, "resolution %.17g (%s) restated %.17g (%s) exact %.17g bound %.3g" % (res, res.tobytes().hex(), restated,
+                                                                                              restated.tobytes().hex(), exact, bound))
         if np.isnan(exact):
             assert np.isnan(res), (what, name, res)
         else:
             assert abs(res - exact) <= bound and bound <= 1e-12 * exact, (what, name, res, exact, bound)
-        rs, rn = R.default_radii(res)
-        same_radius = lambda a, b: F(a).tobytes() == F(b).tobytes() or (np.isnan(a) and np.isnan(b))      # noqa: E731
+            assert res.tobytes() == restated.tobytes(), (what, name, "device %.17g restated order %.17g" % (res, restated))
         assert same_radius(got["salient_radius"], rs) and same_radius(got["non_max_radius"], rn), (what, name, got["salient_radius"], rs)
-        if ref is None or F(ref["salient_radius"]).tobytes() != F(rs).tobytes():
-            ref = R.iss(pts, attr, **dict(params, salient_radius=rs, non_max_radius=rn)) if np.isfinite(rs) and rs > 0 else \
-                R.iss(pts, attr, **dict(params, salient_radius=np.nan, non_max_radius=np.nan)) if np.isnan(rs) else None
         if ref is not None:                                                # (a resolution of exactly 0 - every point a duplicate - has no given-radii form)
             same(ref, got, (what, n, "defaults", name))
     return ref
@@ -269,12 +275,15 @@ def _default_clouds(synth):
     yield "one point", rng.random((1, 3)).astype(F)
     yield "four points", rng.random((4, 3)).astype(F)
     yield "all nan", np.full((70, 3), np.nan, F)
+    yield "uniform 3000, not the exact sum", np.random.default_rng(43).random((3000, 3)).astype(F)
 
 
 def test_default_radii(ictx, synth):
     for what, pts in _default_clouds(synth):
         attr = np.random.default_rng(len(pts)).random((len(pts), 3)).astype(F)
         ref = check_defaults(ictx, pts, attr, what=what)
+        if what.endswith("not the exact sum"):                             # the fixed order's bits are not math.fsum's here: equality asks more than the bound
+            assert np.float64(R.resolution(pts)[0]).tobytes() != np.float64(R.resolution_in_tree_order(pts)[0]).tobytes()
         if what.startswith("object"):
             assert 0.01 * len(pts) < ref["n_keypoints"] < 0.1 * len(pts), (what, ref["n_keypoints"])      # a few percent
 

@@ -2,11 +2,13 @@
 of tests/outlier_restatement.py, from the host and the device entry points.
 
 Byte for byte: n_valid, n_kept, mask, index, the kept xyz / rgb rows, the radius counts and the per-point mean (an f64 array: rule 2
-fixes every bit of it).  cloud_mean, std_dev and threshold are held to the restatement's exact-sum values within the bounds of
-outlier_restatement.statistics_bounds, which come from the header's fixed tree alone (its depth times 2^-53, plus the way the error of
-cloud_mean enters the deviation sum: written out in that function's docstring; nothing in it is measured on the device, and it stays
-below 1e-12 relative).  The mask comparison is honest because of the gap condition, asserted for every case with no exception: the
-restatement alone shows that no valid mean lies within the threshold's bound of the restated threshold.  Every test runs on a Context of
+fixes every bit of it) - and cloud_mean, std_dev and threshold, against rule 4 restated in the header's own order of additions
+(outlier_restatement's "tree" form over tests/fixed_tree_restatement.py; a NaN where the restatement has one).  The three doubles of the
+device AND of that restatement are also held to the exact-sum values within the bounds of outlier_restatement.statistics_bounds, which
+come from the tree's depth alone (its depth times 2^-53, plus the way the error of cloud_mean enters the deviation sum: written out in that
+function's docstring; nothing in it is measured on the device, and it stays below 1e-12 relative).  With equal thresholds the mask needs
+no gap condition: test_means_on_the_threshold_and_tree_edges runs the inputs on which every mean lies at the threshold.  The older cases
+still assert the gap, which there makes the exact-sum mask the same mask.  Every test runs on a Context of
 its own."""
 import ctypes as C
 import math
@@ -33,6 +35,7 @@ NB_NEIGHBORS = [2, 20, 64, 65, 192, 193, 255]
 # The k of a case is its kind's index plus its size's, through NB_NEIGHBORS.  Two kinds are shifted: without it a grid of 64 or 65 points
 # met k = 2 (every mean is half the one pitch: no deviation, every mean ON the threshold; the shift puts k = 2 on the grid of 1000)
 # and the huge rows at 64 points met k = n (every list holds a 1e19 row): inputs that violate the gap condition whatever their seed.
+# test_means_on_the_threshold_and_tree_edges runs exactly those, against the restatement in the header's order, which needs no gap.
 K_SHIFT = {"grid": 6, "huge": 1}
 
 
@@ -60,7 +63,15 @@ def _same_doubles(ref, got, n, ratio, what):
             assert math.isnan(g), (what, key, g)
         else:
             assert abs(g - r) <= b, (what, key, r, g, b)
-            assert b <= 1e-12 * (abs(float(ref["cloud_mean"])) + abs(ratio) * float(ref["std_dev"]) + abs(r)), (what, key, b)
+            sd = float(ref["std_dev"]) if ref["n_valid"] > 1 else 0.0      # (one valid point: std_dev is NaN and the bounds are 0)
+            assert b <= 1e-12 * (abs(float(ref["cloud_mean"])) + abs(ratio) * sd + abs(r)), (what, key, b)
+        t = np.float64(ref["tree"][key])                                  # rule 4 in the header's own order: the same bytes
+        print(what, key, "restated in the header's order %.17g (%s) got (%s)" % (t, t.tobytes().hex(), np.float64(g).tobytes().hex()))
+        if np.isnan(t):
+            assert math.isnan(g) and math.isnan(r), (what, key, g)
+        else:
+            assert np.float64(g).tobytes() == t.tobytes(), (what, key, "device %.17g restated order %.17g" % (g, t))
+            assert abs(float(t) - r) <= b, (what, key, "the restated order against the exact sum", float(t), r, b)
 
 
 def _same(ref, got, what, per="mean"):
@@ -85,14 +96,18 @@ def _dev_call(ctx, statistical, pts, rgb, a, b):
     return res
 
 
-def check_stat(ctx, pts, k, ratio, rgb=None, what=None, ref=None):
+def check_stat(ctx, pts, k, ratio, rgb=None, what=None, ref=None, gap=True):
+    """Both entry points against the restatement in the header's order (ref["tree"]), byte for byte.  gap: the inputs are also asserted to
+    leave a gap at the threshold, and then the exact-sum form keeps the same rows."""
     pts = np.ascontiguousarray(pts, F).reshape(-1, 3)
     what = (what, len(pts), k, ratio)
     ref = ref or R.statistical(pts, k, ratio, rgb)
-    assert R.gap_ok(ref, len(pts), ratio), ("gap condition", what)
+    if gap:
+        assert R.gap_ok(ref, len(pts), ratio), ("gap condition", what)
+        assert ref["mask"].tobytes() == ref["tree"]["mask"].tobytes(), ("the two restatements keep different rows across a gap", what)
     for name, got in (("host", ctx.statistical_outlier(pts, k, ratio, rgb)), ("dev", _dev_call(ctx, True, pts, rgb, k, ratio))):
         _same_doubles(ref, got, len(pts), ratio, what + (name,))
-        _same(ref, got, what + (name,))
+        _same(ref["tree"], got, what + (name,))
     return ref
 
 
@@ -158,6 +173,45 @@ def test_fuzz(octx, kind):
         check_stat(octx, pts, k, ratio, rgb, what=kind)
         eps = 0.01 if kind == "grid" else _eps_for(pts, 8, rng)
         check_rad(octx, pts, (k // 8) if n < LARGE else 6, eps, rgb, what=kind)
+
+
+def _on_threshold_cases():
+    """(what, points, nb_neighbors, std_ratio): the inputs K_SHIFT steers the fuzz around, and the edges of the tree."""
+    rng = np.random.default_rng(61)
+    for n in (64, 65):                                                   # every mean is half a pitch: no deviation, every mean AT the threshold
+        yield "grid, k = 2", _make("grid", n, rng), 2, (2.0, 0.0, -0.5)[n % 3]
+    huge = _make("huge", 64, rng)
+    yield "huge rows, k = n", huge, 64, 1.0                              # every list holds a 1e19 row
+    a = rng.random((1, 3)).astype(F)
+    b, c = (a + F(0.25)).astype(F), (a - F(0.125)).astype(F)
+    yield "n_valid = 0", np.repeat(a, 10, 0), 3, 2.0                     # every list is copies of the query: mean 0, not valid
+    yield "n_valid = 1", np.concatenate([np.repeat(a, 3, 0), b]), 2, 2.0
+    yield "n_valid = 2", np.concatenate([np.repeat(a, 3, 0), b, c]), 2, 2.0
+    for n in (255, 256, 257, 65537):                                     # one workgroup short, full, two; 257 partials: two terms in thread 0
+        yield "uniform", rng.random((n, 3)).astype(F), 20 if n < 60000 else 4, 2.0
+
+
+@pytest.mark.parametrize("case", range(13))
+def test_means_on_the_threshold_and_tree_edges(octx, case):
+    """No gap condition: cloud_mean, std_dev and threshold are the restated order's bytes, so mask, index and the kept rows are held byte
+    for byte where every mean lies on the threshold, where n_valid is 0, 1 or 2, and at the sizes where the tree changes shape."""
+    cases = list(_on_threshold_cases())
+    assert len(cases) == 13 - 3
+    if case >= len(cases):                                               # the three grid / huge cases again, with colours
+        what, pts, k, ratio = cases[case - len(cases)]
+        rgb = np.random.default_rng(case).random((len(pts), 3)).astype(F)
+    else:
+        (what, pts, k, ratio), rgb = cases[case], None
+    ref = check_stat(octx, pts, k, ratio, rgb, what=what, gap=False)
+    nv = ref["tree"]["n_valid"]
+    print(what, len(pts), "n_valid", nv, "kept", ref["tree"]["n_kept"], "gap", R.gap_ok(ref, len(pts), ratio))
+    if what.startswith("n_valid"):
+        assert nv == int(what[-1]) and (nv > 1 or ref["tree"]["n_kept"] == 0)
+    if what == "uniform" and len(pts) == 256:                            # the fixed order's bits are not math.fsum's here: equality asks more than the bound
+        assert np.float64(ref["cloud_mean"]).tobytes() != np.float64(ref["tree"]["cloud_mean"]).tobytes()
+    if what.startswith("grid"):
+        mv = ref["mean"][ref["valid"]]
+        assert nv == len(pts) and np.ptp(mv) <= 1e-6 * mv.max()           # the means are one value up to the f32 rounding of the pitch
 
 
 def test_empty_cloud_and_open3d_shapes(octx):

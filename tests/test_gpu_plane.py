@@ -1,7 +1,7 @@
 """Plane segmentation on the device (include/tdv_hip.h: tdv_segment_planes), against the restatement of tests/plane_restatement.py.
 
 Labels, plane counts, winners, iterations run, inlier and candidate counts, the hypothesis' bits and the rest cloud read no sum: they
-are the restatement's exactly.  fitness and rmse agree to 1e-6 relative, the refit normal to 1e-6 rad and its offset to 1e-7 m (the
+are the restatement's exactly, and so is fitness, one rounded quotient of two of those counts.  rmse agrees to 1e-6 relative, the refit normal to 1e-6 rad and its offset to 1e-7 m (the
 f64 sum order and the eigen solver differ in the last places).  Every test runs on a Context of its own."""
 import ctypes as C
 import math
@@ -73,7 +73,7 @@ def _same(got, labels, ref, rest=None):
         for k in ("inliers", "candidates", "best_iteration", "iterations_run"):
             assert g[k] == r[k], (k, g[k], r[k])
         assert g["hypothesis"].tobytes() == r["hypothesis"].tobytes(), (g["hypothesis"], r["hypothesis"])
-        assert abs(g["fitness"] - r["fitness"]) <= 1e-6 * r["fitness"]
+        assert F(g["fitness"]).tobytes() == F(r["fitness"]).tobytes(), (g["fitness"], r["fitness"])      # (float)((double)count / m_k) of exact counts
         assert abs(g["rmse"] - r["rmse"]) <= 1e-6 * r["rmse"], (g["rmse"], r["rmse"])
         if r["plane64"] is None:
             assert g["plane"].tobytes() == r["hypothesis"].tobytes()
