@@ -64,6 +64,8 @@ ABI_SYMBOLS = [
     "tdv_iss_default_params", "tdv_iss_keypoints", "tdv_iss_keypoints_dev",
     "tdv_ppf_default_params", "tdv_ppf_model_bytes", "tdv_ppf_model_dev", "tdv_ppf_match_dev", "tdv_ppf_match",
     "tdv_ppf_match_batch_dev",
+    "tdv_farthest_point_down_sample", "tdv_farthest_point_down_sample_dev", "tdv_farthest_point_down_sample_batch_dev",
+    "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path",
 ]
 
 
@@ -206,6 +208,21 @@ def iss_params(**kw):
 
 def _iss_result(r):
     return {k: getattr(r, k) for k, _ in IssResultC._fields_}
+
+
+TDV_FPS_MAX_POINTS = 1 << 22
+TDV_FPS_WORKGROUP_LANES = 1024
+TDV_FPS_WORKGROUP_MAX = 16384
+TDV_FPS_AUTO, TDV_FPS_WORKGROUP, TDV_FPS_GRID = 0, 1, 2
+FPS_PATH = {"auto": TDV_FPS_AUTO, "workgroup": TDV_FPS_WORKGROUP, "grid": TDV_FPS_GRID}
+
+
+class FpsResultC(C.Structure):
+    _fields_ = [("n_usable", C.c_int), ("n_selected", C.c_int), ("path", C.c_int), ("cover_d2", C.c_float)]
+
+
+def _fps_result(r):
+    return dict(n_usable=r.n_usable, n_selected=r.n_selected, path=r.path, cover_d2=np.float32(r.cover_d2))
 
 
 TDV_PPF_MODEL_MAX = 2048
@@ -482,6 +499,15 @@ class Context:
         """Name of the search the last ICP / correspondence call ran ('brute', 'pruned', 'grid'; 'auto' before any)."""
         v = lib().tdv_ctx_last_icp_search(self._h)
         return {n: k for k, n in self.ICP_SEARCH.items()}[v]
+
+    def set_fps_path(self, mode):
+        """'auto' (default: the workgroup kernels up to TDV_FPS_WORKGROUP_MAX rows, the grid kernels above), 'workgroup' or 'grid': the
+        kernel family of farthest point sampling on this context; same bytes either way (tests and measurements)."""
+        _check(self._h, lib().tdv_ctx_set_fps_path(self._h, FPS_PATH[mode]), "tdv_ctx_set_fps_path")
+
+    def last_fps_path(self):
+        """'workgroup' or 'grid': the family the last farthest-point call on this context chose ('auto' before any)."""
+        return {v: k for k, v in FPS_PATH.items()}[int(lib().tdv_ctx_last_fps_path(self._h))]
 
     def workspace_high_water(self):
         """Bytes of device memory held by this ctx's workspace arenas (its batch lanes' included): the high-water mark so far."""
@@ -953,6 +979,89 @@ class Context:
                                                     _ptr(d_saliency), _ptr(d_eigenvalues), _ptr(d_support), _ptr(d_index), _ptr(d_out_xyz),
                                                     _ptr(d_out_attr)), "tdv_iss_keypoints_dev")
         return _iss_result(res)
+
+    # ---------------------------------------------------------------- farthest point sampling (include/tdv_hip.h: tdv_farthest_point_down_sample)
+    def fps(self, xyz, num_samples, start_index=0, attr=None):
+        """tdv_farthest_point_down_sample, every output: dict(n_usable, n_selected, path, cover_d2, index int32[n_selected] in selection
+        order, d2 float32[n_selected], xyz float32[n_selected, 3], attr float32[n_selected, width] or None).  attr: one row of floats per
+        point, gathered beside xyz."""
+        xyz = _f32(xyz).reshape(-1, 3); n = len(xyz)
+        width = 0
+        if attr is not None:
+            attr = _f32(attr)
+            if attr.ndim != 2 or len(attr) != n:
+                raise ValueError("tdv_farthest_point_down_sample: one attr row per point")
+            width = attr.shape[1]
+        res = FpsResultC()
+        m1 = max(min(int(num_samples), n), 1)
+        index = np.zeros(m1, np.int32); d2 = np.zeros(m1, np.float32); rows = np.zeros((m1, 3), np.float32)
+        cols = None if attr is None else np.zeros((m1, max(width, 1)), np.float32)
+        _check(self._h, lib().tdv_farthest_point_down_sample(self._h, _ptr(xyz), n, int(num_samples), int(start_index), _ptr(attr), width,
+                                                             C.byref(res), _ptr(index), _ptr(d2), _ptr(rows), _ptr(cols)),
+               "tdv_farthest_point_down_sample")
+        m = res.n_selected
+        return dict(_fps_result(res), index=index[:m], d2=d2[:m], xyz=rows[:m],
+                    attr=None if cols is None else cols.reshape(-1)[:m * width].reshape(m, width))
+
+    def farthest_point_down_sample(self, xyz, num_samples, start_index=0):
+        """Open3D's PointCloud.farthest_point_down_sample: the selected rows, in selection order."""
+        return self.fps(xyz, num_samples, start_index)["xyz"]
+
+    def fps_dev(self, d_xyz, n, num_samples, start_index=0, d_attr=None, attr_width=0, d_index=None, d_out_d2=None, d_out_xyz=None,
+                d_out_attr=None):
+        """tdv_farthest_point_down_sample_dev on device pointers: the result dict.  d_index (int32), d_out_d2 (float), d_out_xyz (3 floats)
+        and d_out_attr (attr_width floats) per sample, each of min(num_samples, n) entries, are optional; n_selected rows are written."""
+        res = FpsResultC()
+        _check(self._h, lib().tdv_farthest_point_down_sample_dev(self._h, _ptr(d_xyz), int(n), int(num_samples), int(start_index), _ptr(d_attr),
+                                                                 int(attr_width), C.byref(res), _ptr(d_index), _ptr(d_out_d2), _ptr(d_out_xyz),
+                                                                 _ptr(d_out_attr)), "tdv_farthest_point_down_sample_dev")
+        return _fps_result(res)
+
+    def fps_batch_dev(self, d_xyz, offsets, num_samples, d_attr=None, attr_width=0, d_index=None, d_out_d2=None, d_out_xyz=None, d_out_attr=None):
+        """tdv_farthest_point_down_sample_batch_dev on device pointers: cloud b = rows [offsets[b], offsets[b + 1]) of d_xyz and d_attr, each
+        sampled from its row 0.  Returns (one result dict per cloud, out offsets int32[n_clouds + 1]); cloud b's samples are rows
+        [out offsets[b], out offsets[b + 1]) of the optional device outputs (each of sum over b of min(num_samples, n_b) entries)."""
+        off = np.ascontiguousarray(offsets, np.int32)
+        n = len(off) - 1
+        res = (FpsResultC * max(n, 1))()
+        out_off = np.zeros(n + 1, np.int32)
+        _check(self._h, lib().tdv_farthest_point_down_sample_batch_dev(self._h, _ptr(d_xyz), _ptr(d_attr), int(attr_width), _ptr(off), n,
+                                                                       int(num_samples), res, _ptr(out_off), _ptr(d_index), _ptr(d_out_d2),
+                                                                       _ptr(d_out_xyz), _ptr(d_out_attr)),
+               "tdv_farthest_point_down_sample_batch_dev")
+        return [_fps_result(res[b]) for b in range(n)], out_off
+
+    def fps_batch(self, xyz, offsets, num_samples, attr=None):
+        """fps_batch_dev on host arrays (rows of all clouds back to back): one dict per cloud as fps() returns it, index inside the cloud."""
+        import torch
+        xyz = np.array(xyz, np.float32).reshape(-1, 3)
+        off = np.ascontiguousarray(offsets, np.int32)
+        width = 0
+        d_a = None
+        if attr is not None:
+            attr = np.array(attr, np.float32)
+            if attr.ndim != 2 or len(attr) != len(xyz):
+                raise ValueError("tdv_farthest_point_down_sample_batch_dev: one attr row per point")
+            width = attr.shape[1]
+            d_a = _upload_rows(self.device, attr, max(width, 1))
+        d_x = _upload_rows(self.device, xyz)
+        cap = max(int(np.minimum(np.diff(off), int(num_samples)).sum()) if len(off) > 1 else 0, 1)
+        dev = torch.device("cuda", self.device)
+        oi = torch.zeros(cap, dtype=torch.int32, device=dev); od = torch.zeros(cap, dtype=torch.float32, device=dev)
+        ox = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
+        oa = None if attr is None else torch.zeros((cap, max(width, 1)), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        res, out_off = self.fps_batch_dev(d_x.data_ptr(), off, num_samples, None if d_a is None else d_a.data_ptr(), width, oi.data_ptr(),
+                                          od.data_ptr(), ox.data_ptr(), None if oa is None else oa.data_ptr())
+        self.synchronize()
+        hi, hd, hx = oi.cpu().numpy(), od.cpu().numpy(), ox.cpu().numpy()
+        ha = None if oa is None else oa.cpu().numpy().reshape(-1)
+        out = []
+        for b, r in enumerate(res):
+            a, e = int(out_off[b]), int(out_off[b + 1])
+            out.append(dict(r, index=hi[a:e].copy(), d2=hd[a:e].copy(), xyz=hx[a:e].copy(),
+                            attr=None if ha is None else ha[a * width:e * width].reshape(e - a, width).copy()))
+        return out
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

@@ -533,6 +533,32 @@ int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss
     return iss_run_dev(ctx, d_xyz, n, *params, d_attr, attr_width, result, d, nullptr);
 }
 
+// ---- farthest point sampling (fps.hip)
+int tdv_farthest_point_down_sample(tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
+                                   tdv_fps_result* result, int* index, float* out_d2, float* out_xyz, float* out_attr) {
+    if (!fps_args_ok(ctx, xyz, n, num_samples, start_index, attr, attr_width, result, out_attr)) return TDV_ERR_BAD_ARG;
+    FpsOut h; h.index = index; h.d2 = out_d2; h.xyz = out_xyz; h.attr = out_attr;
+    return fps_run_host(ctx, xyz, n, num_samples, start_index, attr, attr_width, result, h);
+}
+
+int tdv_farthest_point_down_sample_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int start_index, const float* d_attr,
+                                       int attr_width, tdv_fps_result* result, int* d_index, float* d_out_d2, float* d_out_xyz,
+                                       float* d_out_attr) {
+    if (!fps_args_ok(ctx, d_xyz, n, num_samples, start_index, d_attr, attr_width, result, d_out_attr)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(fps_begin(ctx));
+    FpsOut d; d.index = d_index; d.d2 = d_out_d2; d.xyz = d_out_xyz; d.attr = d_out_attr;
+    return fps_run_dev(ctx, d_xyz, n, num_samples, start_index, d_attr, attr_width, result, d, nullptr);
+}
+
+int tdv_farthest_point_down_sample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_offsets,
+                                             int n_clouds, int num_samples, tdv_fps_result* results, int* h_out_offsets, int* d_index,
+                                             float* d_out_d2, float* d_out_xyz, float* d_out_attr) {
+    if (!fps_batch_args_ok(ctx, d_xyz, d_attr, attr_width, h_offsets, n_clouds, num_samples, results, h_out_offsets, d_out_attr)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(fps_begin(ctx));
+    FpsOut d; d.index = d_index; d.d2 = d_out_d2; d.xyz = d_out_xyz; d.attr = d_out_attr;
+    return fps_batch_run_dev(ctx, d_xyz, d_attr, attr_width, h_offsets, n_clouds, num_samples, results, h_out_offsets, d);
+}
+
 // ---- PPF matching (ppf.hip)
 void tdv_ppf_default_params(tdv_ppf_params* p) {
     if (!p) return;

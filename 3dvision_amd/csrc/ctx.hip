@@ -308,6 +308,13 @@ int tdv_ctx_set_ransac_score(tdv_ctx* ctx, int mode) {
     return TDV_OK;
 }
 
+int tdv_ctx_set_fps_path(tdv_ctx* ctx, int mode) {
+    if (!ctx || mode < TDV_FPS_AUTO || mode > TDV_FPS_GRID) return TDV_ERR_BAD_ARG;
+    ctx->fps_path = mode;
+    return TDV_OK;
+}
+int tdv_ctx_last_fps_path(tdv_ctx* ctx) { return ctx ? ctx->last_fps_path : 0; }
+
 double tdv_ctx_last_ransac_rescore(tdv_ctx* ctx) { return ctx ? ctx->last_ransac_rescore : -1.0; }
 
 double tdv_ctx_last_ransac_scored(tdv_ctx* ctx) { return ctx ? ctx->last_ransac_scored : 1.0; }

@@ -46,6 +46,8 @@ struct tdv_ctx {
     int last_voxel_grouping = 0;   // 1: the table (k_vh_insert), 2: pixel windows (k_vs_group) - the last batched voxel call (tdv_ctx_last_voxel_grouping)
     int last_fm_path = 0;      // TDV_FM_PATH_* of the last descriptor match on this ctx (tdv_ctx_last_feature_match_path)
     int last_batch_lanes = 0;  // host lanes the last tdv_register_batch_dev call on this ctx spread its instances over (tdv_ctx_last_batch_lanes)
+    int fps_path = 0;          // TDV_FPS_AUTO / _WORKGROUP / _GRID (tdv_ctx_set_fps_path)
+    int last_fps_path = 0;     // the family the last farthest-point call on this ctx chose (tdv_ctx_last_fps_path)
     int last_icp_search = 0; // the search the last ICP / correspondence call on this ctx actually ran (tdv_ctx_last_icp_search)
     unsigned* scan_ticket = nullptr;  // persistent device words: [0] exclusive_scan_dev's last-workgroup ticket, [1..] ICP's, [8] the tile ticket of depth.hip's chained scan
     unsigned long long* chain_status = nullptr;   // depth.hip k_depth_cloud_chain: one status word per tile, persistent (told apart by chain_epoch)
@@ -331,6 +333,22 @@ int iss_run_host(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params& pr
                  const IssOut& h);
 int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& prm, const float* d_attr, int attr_width, tdv_iss_result* result,
                 IssOut d, const IssOut* h);
+
+// Farthest point sampling (fps.hip, include/tdv_hip.h: tdv_farthest_point_down_sample): the outputs of a call (each optional), the
+// argument checks, and the calls.  fps_run_host resets the workspace itself; the entry points of the other two call fps_begin first.
+// fps_batch_run_dev: the clouds [h_off[b], h_off[b + 1]) of d_xyz, each from its row 0; per cloud fps_run_dev's bytes.
+struct FpsOut { int* index = nullptr; float* d2 = nullptr; float* xyz = nullptr; float* attr = nullptr; };
+bool fps_args_ok(const tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
+                 const tdv_fps_result* result, const float* out_attr);
+bool fps_batch_args_ok(const tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_off, int n_clouds,
+                       int num_samples, const tdv_fps_result* results, const int* h_out_off, const float* d_out_attr);
+int fps_begin(tdv_ctx* ctx);
+int fps_run_host(tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
+                 tdv_fps_result* result, const FpsOut& h);
+int fps_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int start_index, const float* d_attr, int attr_width,
+                tdv_fps_result* result, FpsOut d, const FpsOut* h);
+int fps_batch_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_off, int n_clouds, int num_samples,
+                      tdv_fps_result* results, int* h_out_off, FpsOut d);
 
 // PPF matching (ppf.hip, include/tdv_hip.h: tdv_ppf_match).  PpfPlan: what the parameters alone fix (n_dist, n_keys, the table's layout for
 // nt points); ppf_plan is the parameter check of every entry point.  ppf_model_run builds the table (rule 4) into d_model and fills info;

@@ -758,6 +758,80 @@ int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss
                           int attr_width, tdv_iss_result* result, uint8_t* d_mask /* optional */, double* d_saliency /* optional */,
                           double* d_eigenvalues /* optional */, int* d_support /* optional */, int* d_index /* optional */,
                           float* d_out_xyz /* optional */, float* d_out_attr /* optional */);
+/* Farthest point sampling (Open3D's PointCloud::farthest_point_down_sample(num_samples, start_index); the sampling step of PointNet++ and
+ * of the PPF pipelines): exactly num_samples points of a cloud, spread as evenly as a greedy rule manages - the one way here to thin a
+ * cloud to a COUNT (a model under TDV_PPF_MODEL_MAX, a cloud under the 2,048 points of the small ICP batch, clusters of one size for the
+ * batch entry points).  Prefix-stable: the first k entries of a K-sample are the k-sample.  The distance is f32 with one rounding per
+ * operation and the choice an integer maximum, so every output is fixed bit for bit whatever order the device works in:
+ *  1. Usable row: a row is usable iff its three coordinates are finite.  n_usable = the usable rows.  An unusable row is never selected
+ *     and takes no part in any distance.
+ *  2. Count: n_selected = min(num_samples, n_usable).
+ *  3. Distance: d2(j, s) = (dx * dx + dy * dy) + dz * dz in f32 without contraction, dx = p_j.x - p_s.x and likewise y, z, one rounding
+ *     each (rule 1 of tdv_cluster_dbscan).  Between usable rows it is never NaN and never -0; it is +inf on overflow, a distance like any
+ *     other.
+ *  4. Running minimum: m_j = +inf for every usable row at first; after sample s is taken, m_j = (d2(j, s) < m_j) ? d2(j, s) : m_j for
+ *     every usable j.
+ *  5. First sample: row start_index if it is usable, else the lowest usable index.
+ *  6. Every later sample: among the usable rows not yet selected the one with the largest m_j, ties to the lowest index: one maximum
+ *     over the 64-bit keys (bits(m_j) << 32) | (0xFFFFFFFF - j) - the bits of a non-negative f32 order as unsigned integers.  Selected
+ *     and unusable rows carry key 0.
+ *  7. No repeats: a selected row is never selected again.  This is the one deliberate difference from Open3D's loop, which on a cloud
+ *     with fewer than num_samples distinct points repeats one index, and with NaN or infinite rows selects those first.  On distinct
+ *     finite points the rule is Open3D's (strict >, the lowest index among equals), in f32 where Open3D works in f64.
+ *  8. Outputs, in selection order, each optional (NULL to skip), entries beyond n_selected not written: index (int[n_selected], original
+ *     row indices), out_d2 (float[n_selected]: the row's m at the moment it was selected: +inf for entry 0, non-increasing from entry 1
+ *     on), out_xyz (the selected rows), out_attr (the rows of one companion array of attr_width floats per point - normals, colours, FPFH
+ *     rows - as tdv_iss_keypoints; needs attr).
+ *  9. result: n_usable, n_selected, path (TDV_FPS_WORKGROUP or TDV_FPS_GRID: the kernel family the call's size and the ctx's switch
+ *     chose, also where nothing had to run), cover_d2 = the largest final m_j over the usable rows not selected, +0.0 without one: every
+ *     usable point lies within sqrt(cover_d2) of a sample (it is the maximum that would have chosen the next sample).
+ * Two kernel families give the same bytes.  Workgroup path: one workgroup of TDV_FPS_WORKGROUP_LANES lanes holds the whole cloud and the
+ * running minima in registers, up to TDV_FPS_WORKGROUP_MAX rows; one workgroup barrier per sample.  Grid path: any size, one launch per
+ * sample on the ctx's stream, the maximum through one 64-bit integer atomic per workgroup; no kernel waits for another workgroup.
+ * tdv_ctx_set_fps_path: TDV_FPS_AUTO (default: the workgroup path iff n <= TDV_FPS_WORKGROUP_MAX) or one of the two, for tests and
+ * measurements; tdv_ctx_last_fps_path: what the last call on the ctx chose (a batch: TDV_FPS_GRID if any of its clouds took the grid
+ * path, else TDV_FPS_WORKGROUP); 0 before the first call.
+ * tdv_farthest_point_down_sample takes host arrays and reads back twice (the result, then the n_selected rows);
+ * tdv_farthest_point_down_sample_dev takes device pointers and reads back once, the result.
+ * tdv_farthest_point_down_sample_batch_dev is, per cloud, tdv_farthest_point_down_sample_dev at start_index 0: cloud b is rows
+ * [h_offsets[b], h_offsets[b + 1]) of d_xyz and d_attr - the layout tdv_cluster_dbscan_dev writes and tdv_ppf_match_batch_dev and
+ * tdv_icp_batch_dev take - its index counts inside the cloud, and its outputs are rows [h_out_offsets[b], h_out_offsets[b + 1]) of
+ * d_index, d_out_d2, d_out_xyz and d_out_attr, packed back to back (h_out_offsets[b + 1] - h_out_offsets[b] = results[b].n_selected), so
+ * that they go into those batch entry points as they stand.  results[b] and cloud b's rows are byte for byte the single call's.  Clouds of
+ * at most TDV_FPS_WORKGROUP_MAX rows run together, one workgroup each; larger ones go through the grid path one after another.  The call
+ * reads back once (the per-cloud results), whatever n_clouds is.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx or result; a NULL cloud with n > 0; n < 0 or n > TDV_FPS_MAX_POINTS;
+ * num_samples < 0; start_index outside [0, n) when n > 0; attr_width < 0; attr_width > 0 with a NULL attr; out_attr without attr;
+ * TDV_FPS_WORKGROUP forced on a cloud above TDV_FPS_WORKGROUP_MAX; batch: n_clouds < 0, a NULL h_offsets or h_out_offsets, NULL results
+ * with n_clouds > 0, offsets that do not start at 0 or that decrease, a cloud above TDV_FPS_MAX_POINTS.  n == 0 and num_samples == 0 are
+ * accepted (zero counts; start_index is then not looked at when n == 0).  The ctx's ICP switches do not apply.  Not provided: the C++
+ * operator mirror, sampling inside tdv_register_batch_dev / tdv_refine_batch_dev (an ABI change), per-cloud sample counts or start rows
+ * in the batch form, other samplers (uniform, random, Poisson disk). */
+#define TDV_FPS_MAX_POINTS (1 << 22)
+#define TDV_FPS_WORKGROUP_LANES 1024
+#define TDV_FPS_WORKGROUP_MAX 16384   /* 16 rows per lane: csrc/fps.hip has the register report */
+#define TDV_FPS_AUTO 0
+#define TDV_FPS_WORKGROUP 1
+#define TDV_FPS_GRID 2
+typedef struct tdv_fps_result {
+    int   n_usable;
+    int   n_selected;
+    int   path;
+    float cover_d2;
+} tdv_fps_result;
+int tdv_farthest_point_down_sample(tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr /* optional */,
+                                   int attr_width, tdv_fps_result* result, int* index /* optional */, float* out_d2 /* optional */,
+                                   float* out_xyz /* optional */, float* out_attr /* optional */);
+int tdv_farthest_point_down_sample_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int start_index,
+                                       const float* d_attr /* optional */, int attr_width, tdv_fps_result* result, int* d_index /* optional */,
+                                       float* d_out_d2 /* optional */, float* d_out_xyz /* optional */, float* d_out_attr /* optional */);
+int tdv_farthest_point_down_sample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr /* optional */, int attr_width,
+                                             const int* h_offsets /* host, [n_clouds + 1], starting at 0, non-decreasing */, int n_clouds,
+                                             int num_samples, tdv_fps_result* results /* host, [n_clouds] */,
+                                             int* h_out_offsets /* host, [n_clouds + 1], written */, int* d_index /* optional */,
+                                             float* d_out_d2 /* optional */, float* d_out_xyz /* optional */, float* d_out_attr /* optional */);
+int tdv_ctx_set_fps_path(tdv_ctx* ctx, int mode);
+int tdv_ctx_last_fps_path(tdv_ctx* ctx);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
