@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "tdv_ppf_match_batch_dev",
     "tdv_farthest_point_down_sample", "tdv_farthest_point_down_sample_dev", "tdv_farthest_point_down_sample_batch_dev",
     "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path",
+    "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
 ]
 
 
@@ -225,6 +226,48 @@ def _fps_result(r):
     return dict(n_usable=r.n_usable, n_selected=r.n_selected, path=r.path, cover_d2=np.float32(r.cover_d2))
 
 
+TDV_POSE_SOURCE_ONTO_TARGET, TDV_POSE_MODEL_TO_CAMERA = 0, 1
+TDV_VERIFY_MAX_SPLAT = 3
+TDV_VERIFY_MAX_MODEL = 1 << 22
+TDV_VERIFY_MAX_POSES = 65536
+TDV_VERIFY_MAX_SIDE = 8192
+TDV_VERIFY_TILE_W = 128
+TDV_VERIFY_TILE_H = 128
+TDV_VERIFY_LANES = 1024
+POSE_DIRECTION = {"source_onto_target": TDV_POSE_SOURCE_ONTO_TARGET, "model_to_camera": TDV_POSE_MODEL_TO_CAMERA}
+
+
+class VerifyParamsC(C.Structure):
+    _fields_ = [("pose_direction", C.c_int), ("splat", C.c_int), ("tau", C.c_float), ("zmax", C.c_float)]
+
+
+class VerifyResultC(C.Structure):
+    _fields_ = [("n_projected", C.c_int), ("n_rendered", C.c_int), ("n_consistent", C.c_int), ("n_occluded", C.c_int),
+                ("n_violating", C.c_int), ("n_unknown", C.c_int), ("err_q20", C.c_ulonglong)]
+
+
+def verify_params(**kw):
+    """tdv_verify_default_params (T moves the camera's cloud onto the model, splat 1, tau 0.002 m, zmax 10 m) with the given fields replaced;
+    pose_direction also by name ('source_onto_target', 'model_to_camera')."""
+    p = VerifyParamsC()
+    lib().tdv_verify_default_params(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(VerifyParamsC._fields_):
+            raise TypeError("unknown verification parameter %r" % k)
+        setattr(p, k, POSE_DIRECTION[v] if k == "pose_direction" and isinstance(v, str) else v)
+    return p
+
+
+def _verify_result(r):
+    return {k: int(getattr(r, k)) for k, _ in VerifyResultC._fields_}
+
+
+def _poses16(poses):
+    """[n, 4, 4] row-major poses as the ABI's n x 16 column-major floats."""
+    poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
+    return np.ascontiguousarray(poses.transpose(0, 2, 1)).reshape(-1), len(poses)
+
+
 TDV_PPF_MODEL_MAX = 2048
 TDV_PPF_POSES_MAX = 64
 TDV_PPF_KEYS_MAX = 1 << 24
@@ -315,6 +358,7 @@ def lib():
             l.tdv_cluster_default_params.restype = None
             l.tdv_iss_default_params.restype = None
             l.tdv_ppf_default_params.restype = None
+            l.tdv_verify_default_params.restype = None
             _lib = l
     return _lib
 
@@ -1062,6 +1106,54 @@ class Context:
             out.append(dict(r, index=hi[a:e].copy(), d2=hd[a:e].copy(), xyz=hx[a:e].copy(),
                             attr=None if ha is None else ha[a * width:e * width].reshape(e - a, width).copy()))
         return out
+
+    # ---------------------------------------------------------------- pose verification (include/tdv_hip.h: tdv_verify_poses)
+    def verify_poses(self, model, poses, raw, scale, fx, fy, cx, cy, **params):
+        """tdv_verify_poses: the model ([n, 3]) splatted at every pose ([n_poses, 4, 4], row-major as everywhere at this level) into the
+        frame of the raw u16 depth image `raw` ([H, W]) and each rendered pixel classified against the observed depth
+        float(raw) * float(1.0 / scale): (one dict per pose of n_projected, n_rendered, n_consistent, n_occluded, n_violating, n_unknown,
+        err_q20 - all integers, n_rendered their sum over the four classes -, order int32[n_poses]: the pose indices by
+        n_consistent - n_violating descending, ties to the lower index).  params: verify_params' fields (pose_direction, splat, tau, zmax)."""
+        model = _f32(model).reshape(-1, 3)
+        raw = np.ascontiguousarray(raw, np.uint16)
+        h, w = raw.shape
+        t, n = _poses16(poses)
+        res = (VerifyResultC * max(n, 1))()
+        order = np.zeros(n, np.int32)
+        _check(self._h, lib().tdv_verify_poses(self._h, _ptr(model), len(model), _ptr(t), n, _ptr(raw), w, h, C.c_float(scale), C.c_float(fx),
+                                               C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)), res,
+                                               _ptr(order)), "tdv_verify_poses")
+        return [_verify_result(res[b]) for b in range(n)], order
+
+    def verify_poses_dev(self, d_model, n_model, poses, d_raw, w, h, scale, fx, fy, cx, cy, **params):
+        """tdv_verify_poses_dev: verify_poses with the model (float[3 n_model]) and the raw frame (uint16[w h]) as device pointers; the poses
+        and the results stay on the host.  One read-back."""
+        t, n = _poses16(poses)
+        res = (VerifyResultC * max(n, 1))()
+        order = np.zeros(n, np.int32)
+        _check(self._h, lib().tdv_verify_poses_dev(self._h, _ptr(d_model), int(n_model), _ptr(t), n, _ptr(d_raw), int(w), int(h), C.c_float(scale),
+                                                   C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)),
+                                                   res, _ptr(order)), "tdv_verify_poses_dev")
+        return [_verify_result(res[b]) for b in range(n)], order
+
+    def render_depth(self, model, pose, w, h, fx, fy, cx, cy, **params):
+        """tdv_render_depth: the rendered depth of the model at one pose, float32 [h, w], 0 where nothing rendered - per pixel the minimum
+        camera z over the model points whose splat square covers it (the z-buffer verify_poses classifies)."""
+        model = _f32(model).reshape(-1, 3)
+        out = np.zeros((int(h), int(w)), np.float32)
+        n = C.c_int()
+        _check(self._h, lib().tdv_render_depth(self._h, _ptr(model), len(model), _ptr(to_colmajor16(pose)), int(w), int(h), C.c_float(fx),
+                                               C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)), _ptr(out),
+                                               C.byref(n)), "tdv_render_depth")
+        return out
+
+    def render_depth_dev(self, d_model, n_model, pose, w, h, fx, fy, cx, cy, d_out_depth, **params):
+        """tdv_render_depth_dev: render_depth from a device model into the device image d_out_depth (float[w h]); returns n_rendered."""
+        n = C.c_int()
+        _check(self._h, lib().tdv_render_depth_dev(self._h, _ptr(d_model), int(n_model), _ptr(to_colmajor16(pose)), int(w), int(h), C.c_float(fx),
+                                                   C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)),
+                                                   _ptr(d_out_depth), C.byref(n)), "tdv_render_depth_dev")
+        return n.value
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

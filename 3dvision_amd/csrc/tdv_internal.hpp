@@ -350,6 +350,16 @@ int fps_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int st
 int fps_batch_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_off, int n_clouds, int num_samples,
                       tdv_fps_result* results, int* h_out_off, FpsOut d);
 
+// Pose verification (verify.hip, include/tdv_hip.h: tdv_verify_poses): the argument check of the four entry points (frame: the raw frame
+// resp. the depth output; results: what receives the per-pose output) and the two calls on device pointers.  Neither resets the workspace:
+// the entry point did.  Both read back once.
+bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
+                    float scale, float fx, float fy, const tdv_verify_params* p, const void* results);
+int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, int w, int h,
+                   float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& prm, tdv_verify_result* results, int* order);
+int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_pose, int w, int h, float fx, float fy, float cx, float cy,
+                         const tdv_verify_params& prm, float* d_out, int* n_rendered);
+
 // PPF matching (ppf.hip, include/tdv_hip.h: tdv_ppf_match).  PpfPlan: what the parameters alone fix (n_dist, n_keys, the table's layout for
 // nt points); ppf_plan is the parameter check of every entry point.  ppf_model_run builds the table (rule 4) into d_model and fills info;
 // ppf_match_run votes, clusters and scores (h_peaks: where a host call's peaks go); ppf_match_batch_run is it per instance of an offsets

@@ -1,0 +1,286 @@
+// Pose verification (include/tdv_hip.h: tdv_verify_poses): the model splatted at every candidate pose into a z-buffer and each rendered
+// pixel classified against the observed depth.  Candidates x model points is the hot loop; the z-buffer of a tile lives in LDS and is
+// built with LDS integer minimum atomics - no global atomic touches a depth, and no kernel waits for another workgroup.
+//   k_verify_init    the per-pose record: zero counts, an empty box
+//   k_verify_bounds  per pose n_projected and the box of the covered pixels, clipped to the frame: the exact min / max over the same u, v
+//                    the render computes (LDS atomics per workgroup, then integer atomics on the record - integers, the order is free)
+//   k_verify_plan    tiles per pose = the frame-aligned TDV_VERIFY_TILE_W x TDV_VERIFY_TILE_H tiles its box touches, and their exclusive
+//                    scan over the poses: the tile list, on the device
+//   k_verify_tiles   a fixed grid of workgroups walks the tile list (tile t of the list belongs to the pose p with off[p] <= t < off[p + 1]:
+//                    a search over the offsets); per tile: clear the LDS tile, project the model with the pose in uniform registers, apply
+//                    the covers that fall inside the tile (ds_min_u32), barrier, then classify the tile's pixels against the raw frame,
+//                    reduce the counts over the wave with DPP and add them to the pose's record; or, for tdv_render_depth, write the tile
+//                    out as f32.  The grid never needs the tile total on the host: the call reads back once, the records.
+// Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md 7, "Pose verification".
+#include "tdv_internal.hpp"
+#include <algorithm>
+#include <numeric>
+
+namespace tdv {
+namespace {
+
+constexpr int VT = TDV_VERIFY_LANES, TW = TDV_VERIFY_TILE_W, TH = TDV_VERIFY_TILE_H, TILE = TW * TH;
+constexpr unsigned EMPTY = 0xFFFFFFFFu;                     // above the bits of every positive finite f32
+constexpr int VERIFY_GRID = 512;                            // 256 CUs x the two workgroups of 64 KiB LDS a CU holds
+static_assert(TILE % (4 * VT) == 0 && (TW & (TW - 1)) == 0, "the clear and the pixel walk assume it");
+
+struct VerifyRec {                                          // one per pose (device)
+    int n_projected;
+    int u0, v0, u1, v1;                                     // the covered pixels' box inside the frame; u0 > u1: none
+    int cls[4];                                             // consistent, occluded, violating, unknown (render: cls[0] = rendered)
+    int pad;
+    unsigned long long err;
+};
+struct VerifyCam { float fx, fy, cx, cy, zmax, tau, inv_scale; int w, h, splat, direction; };
+struct Pose16 { float T[16]; };
+
+__device__ __forceinline__ Pose16 load_pose(const float* __restrict__ poses, int pose) {
+    Pose16 p;
+    const float* T = poses + (size_t)pose * 16;
+#pragma unroll
+    for (int k = 0; k < 16; ++k) p.T[k] = T[k];
+    return p;
+}
+
+// rules 1 to 3 of include/tdv_hip.h, as written there
+__device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& zc) {
+    const float* T = P.T;
+    float xc, yc;
+    if (c.direction == TDV_POSE_SOURCE_ONTO_TARGET) {
+        const float d0 = m0 - T[12], d1 = m1 - T[13], d2 = m2 - T[14];
+        xc = (T[0] * d0 + T[1] * d1) + T[2] * d2;
+        yc = (T[4] * d0 + T[5] * d1) + T[6] * d2;
+        zc = (T[8] * d0 + T[9] * d1) + T[10] * d2;
+    } else {
+        xc = ((T[0] * m0 + T[4] * m1) + T[8] * m2) + T[12];
+        yc = ((T[1] * m0 + T[5] * m1) + T[9] * m2) + T[13];
+        zc = ((T[2] * m0 + T[6] * m1) + T[10] * m2) + T[14];
+    }
+    if (!(fabsf(xc) < INFINITY && fabsf(yc) < INFINITY && zc > 0.f && zc <= c.zmax && zc < INFINITY)) return false;
+    const float uf = (xc * c.fx) / zc + c.cx, vf = (yc * c.fy) / zc + c.cy;
+    if (!(fabsf(uf) < 1048576.f && fabsf(vf) < 1048576.f)) return false;          // (false for NaN too)
+    u = (int)floorf(uf + 0.5f);
+    v = (int)floorf(vf + 0.5f);
+    return true;
+}
+
+__global__ void k_verify_init(VerifyRec* rec, int n_poses) {
+    const int p = blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= n_poses) return;
+    VerifyRec r{};
+    r.u0 = INT_MAX; r.v0 = INT_MAX; r.u1 = -1; r.v1 = -1;
+    rec[p] = r;
+}
+
+// workgroup (pose, chunk): the points chunk * 256 + lane, + chunks * 256, ...
+__global__ __launch_bounds__(256) void k_verify_bounds(const float* __restrict__ xyz, int n, const float* __restrict__ poses, int chunks, VerifyCam c,
+                                                       VerifyRec* rec) {
+    __shared__ int s[5];
+    const int pose = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
+    if (threadIdx.x < 5) s[threadIdx.x] = threadIdx.x == 0 ? 0 : threadIdx.x <= 2 ? INT_MAX : -1;
+    __syncthreads();
+    const Pose16 P = load_pose(poses, pose);
+    int cnt = 0, u0 = INT_MAX, v0 = INT_MAX, u1 = -1, v1 = -1;
+    for (int i = chunk * 256 + (int)threadIdx.x; i < n; i += chunks * 256) {
+        int u, v; float zc;
+        if (!verify_project(P, c, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], u, v, zc)) continue;
+        ++cnt;
+        const int a0 = max(u - c.splat, 0), a1 = min(u + c.splat, c.w - 1), b0 = max(v - c.splat, 0), b1 = min(v + c.splat, c.h - 1);
+        if (a0 > a1 || b0 > b1) continue;                    // the square reaches nothing inside the frame
+        u0 = min(u0, a0); u1 = max(u1, a1); v0 = min(v0, b0); v1 = max(v1, b1);
+    }
+    cnt = wave_sum_i32(cnt);
+    if ((threadIdx.x & 63) == 0 && cnt) atomicAdd(&s[0], cnt);
+    if (u0 <= u1) { atomicMin(&s[1], u0); atomicMin(&s[2], v0); atomicMax(&s[3], u1); atomicMax(&s[4], v1); }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        if (s[0]) atomicAdd(&rec[pose].n_projected, s[0]);
+        if (s[1] <= s[3]) {
+            atomicMin(&rec[pose].u0, s[1]); atomicMin(&rec[pose].v0, s[2]); atomicMax(&rec[pose].u1, s[3]); atomicMax(&rec[pose].v1, s[4]);
+        }
+    }
+}
+
+// off[p] = tiles of the poses before p, off[n_poses] = all tiles (at most 65536 poses x 64 x 64 tiles: an int)
+__global__ __launch_bounds__(1024) void k_verify_plan(const VerifyRec* rec, int n_poses, int* off) {
+    __shared__ int s[1024];
+    int carry = 0;
+    for (int base = 0; base < n_poses; base += 1024) {
+        const int p = base + (int)threadIdx.x;
+        int t = 0;
+        if (p < n_poses && rec[p].u0 <= rec[p].u1) t = (rec[p].u1 / TW - rec[p].u0 / TW + 1) * (rec[p].v1 / TH - rec[p].v0 / TH + 1);
+        s[threadIdx.x] = t;
+        __syncthreads();
+        for (int d = 1; d < 1024; d <<= 1) {
+            const int a = (int)threadIdx.x >= d ? s[threadIdx.x - d] : 0;
+            __syncthreads();
+            s[threadIdx.x] += a;
+            __syncthreads();
+        }
+        if (p < n_poses) off[p] = carry + s[threadIdx.x] - t;
+        carry += s[1023];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) off[n_poses] = carry;
+}
+
+// RENDER: the tile out as f32 into `out` (one pose) in place of the classification
+// (8 waves per SIMD asked for: two workgroups of 16 waves share a CU only while the SGPR count stays within 80)
+template <bool RENDER>
+__global__ __launch_bounds__(VT, 8) void k_verify_tiles(const float* __restrict__ xyz, int n, const float* __restrict__ poses, int n_poses,
+                                                     const int* __restrict__ off, VerifyCam c, const uint16_t* __restrict__ raw, VerifyRec* rec,
+                                                     float* __restrict__ out) {
+    __shared__ unsigned tile[TILE];
+    const int tid = threadIdx.x;
+    const int total = off[n_poses];
+    for (int t = blockIdx.x; t < total; t += gridDim.x) {
+        int lo = 0, hi = n_poses;                            // off[lo] <= t < off[hi]
+        while (hi - lo > 1) {
+            const int mid = (lo + hi) >> 1;
+            if (off[mid] <= t) lo = mid; else hi = mid;
+        }
+        const int pose = __builtin_amdgcn_readfirstlane(lo);
+        const int bu0 = rec[pose].u0, bu1 = rec[pose].u1, bv0 = rec[pose].v0;
+        const int tiles_x = bu1 / TW - bu0 / TW + 1, k = t - off[pose];
+        const int x0 = (bu0 / TW + k % tiles_x) * TW, y0 = (bv0 / TH + k / tiles_x) * TH;
+        const int xe = min(x0 + TW, c.w) - 1, ye = min(y0 + TH, c.h) - 1;      // the tile inside the frame: [x0, xe] x [y0, ye]
+        for (int i = tid; i < TILE / 4; i += VT) reinterpret_cast<uint4*>(tile)[i] = make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
+        __syncthreads();
+        const Pose16 P = load_pose(poses, pose);
+        for (int i = tid; i < n; i += VT) {
+            int u, v; float zc;
+            if (!verify_project(P, c, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], u, v, zc)) continue;
+            const int a0 = max(u - c.splat, x0), a1 = min(u + c.splat, xe), b0 = max(v - c.splat, y0), b1 = min(v + c.splat, ye);
+            const unsigned bits = __float_as_uint(zc);
+            for (int y = b0; y <= b1; ++y)
+                for (int x = a0; x <= a1; ++x) atomicMin(&tile[(y - y0) * TW + (x - x0)], bits);
+        }
+        __syncthreads();
+        int n0 = 0, n1 = 0, n2 = 0, n3 = 0;
+        unsigned long long err = 0;
+        for (int i = tid; i < TILE; i += VT) {
+            const unsigned b = tile[i];
+            const int x = x0 + (i & (TW - 1)), y = y0 + i / TW;
+            if (RENDER) {
+                if (x <= xe && y <= ye) out[(size_t)y * c.w + x] = b == EMPTY ? 0.f : __uint_as_float(b);
+                n0 += b != EMPTY;
+                continue;
+            }
+            if (b == EMPTY) continue;                        // (never set outside the frame)
+            const unsigned r = raw[(size_t)y * c.w + x];
+            const float zr = __uint_as_float(b), zo = (float)r * c.inv_scale;
+            if (!(r != 0 && zo <= c.zmax)) { ++n3; continue; }
+            const float diff = zo - zr;
+            if (fabsf(diff) <= c.tau) {
+                const float q = fabsf(diff) * 1048576.0f;
+                err += q >= 4294967296.0f ? 0xFFFFFFFFu : (unsigned)q;
+                ++n0;
+            } else if (diff < -c.tau) ++n1;
+            else ++n2;
+        }
+        // per lane at most 16 pixels: err < 2^36.  Its low 20 bits and the rest sum over the wave without leaving 32 bits.
+        n0 = wave_sum_i32(n0);
+        if (!RENDER) {
+            n1 = wave_sum_i32(n1); n2 = wave_sum_i32(n2); n3 = wave_sum_i32(n3);
+            const unsigned elo = (unsigned)wave_sum_i32((int)(err & 0xFFFFFu)), ehi = (unsigned)wave_sum_i32((int)(err >> 20));
+            err = (unsigned long long)elo + ((unsigned long long)ehi << 20);
+        }
+        if ((tid & 63) == 0) {
+            if (n0) atomicAdd(&rec[pose].cls[0], n0);
+            if (n1) atomicAdd(&rec[pose].cls[1], n1);
+            if (n2) atomicAdd(&rec[pose].cls[2], n2);
+            if (n3) atomicAdd(&rec[pose].cls[3], n3);
+            if (err) atomicAdd(&rec[pose].err, err);
+        }
+        __syncthreads();                                     // the next tile's clear
+    }
+}
+
+bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
+
+// the records of every pose on the device, everything enqueued: init, bounds, plan, tiles.  pin: poses up at [0], records down at *down.
+int verify_enqueue(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, float* d_out,
+                   const VerifyCam& cam, VerifyRec** rec_out, char** down) {
+    hipStream_t s = ctx->stream;
+    const size_t up_bytes = align_up((size_t)n_poses * 16 * sizeof(float), 256), down_bytes = (size_t)n_poses * sizeof(VerifyRec);
+    TDV_TRY(pin_reserve(ctx, up_bytes + down_bytes));
+    std::memcpy(ctx->pin, h_poses, (size_t)n_poses * 16 * sizeof(float));
+    float* d_poses; VerifyRec* rec; int* off;
+    TDV_TRY(ws_alloc(ctx, (size_t)n_poses * 16, &d_poses));
+    TDV_TRY(ws_alloc(ctx, (size_t)n_poses, &rec));
+    TDV_TRY(ws_alloc(ctx, (size_t)n_poses + 1, &off));
+    TDV_HIP(ctx, hipMemcpyAsync(d_poses, ctx->pin, (size_t)n_poses * 16 * sizeof(float), hipMemcpyHostToDevice, s));
+    k_verify_init<<<(n_poses + 255) / 256, 256, 0, s>>>(rec, n_poses);
+    const long long frame_tiles = (long long)((cam.w + TW - 1) / TW) * ((cam.h + TH - 1) / TH);
+    if (n_model > 0) {
+        const int chunks = std::max(1, std::min(64, (n_model + 2047) / 2048));
+        k_verify_bounds<<<n_poses * chunks, 256, 0, s>>>(d_model, n_model, d_poses, chunks, cam, rec);
+    }
+    if (n_model > 0 && frame_tiles > 0) {
+        k_verify_plan<<<1, 1024, 0, s>>>(rec, n_poses, off);
+        const int grid = (int)std::min<long long>(VERIFY_GRID, frame_tiles * n_poses);
+        if (d_out) k_verify_tiles<true><<<grid, VT, 0, s>>>(d_model, n_model, d_poses, n_poses, off, cam, d_raw, rec, d_out);
+        else k_verify_tiles<false><<<grid, VT, 0, s>>>(d_model, n_model, d_poses, n_poses, off, cam, d_raw, rec, d_out);
+    }
+    TDV_CHECK_LAUNCH(ctx);
+    *down = ctx->pin + up_bytes;
+    TDV_HIP(ctx, hipMemcpyAsync(*down, rec, down_bytes, hipMemcpyDeviceToHost, s));
+    *rec_out = rec;
+    return TDV_OK;
+}
+
+VerifyCam verify_cam(int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& p) {
+    return VerifyCam{fx, fy, cx, cy, p.zmax, p.tau, (float)(1.0 / (double)scale), w, h, p.splat, p.pose_direction};
+}
+
+}  // namespace
+
+// every argument, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth output
+bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
+                    float scale, float fx, float fy, const tdv_verify_params* p, const void* results) {
+    if (!ctx || !p || n_model < 0 || n_model > TDV_VERIFY_MAX_MODEL || n_poses < 0 || n_poses > TDV_VERIFY_MAX_POSES) return false;
+    if (w < 0 || w > TDV_VERIFY_MAX_SIDE || h < 0 || h > TDV_VERIFY_MAX_SIDE) return false;
+    if ((n_model > 0 && !model) || (n_poses > 0 && (!poses || !results)) || ((size_t)w * h > 0 && !frame)) return false;
+    if (p->splat < 0 || p->splat > TDV_VERIFY_MAX_SPLAT || !positive_finite(p->tau)) return false;
+    if (p->pose_direction != TDV_POSE_SOURCE_ONTO_TARGET && p->pose_direction != TDV_POSE_MODEL_TO_CAMERA) return false;
+    return positive_finite(scale) && positive_finite(fx) && positive_finite(fy);
+}
+
+int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, int w, int h,
+                   float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& prm, tdv_verify_result* results, int* order) {
+    if (n_poses == 0) return TDV_OK;
+    VerifyRec* rec; char* down;
+    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_poses, n_poses, d_raw, nullptr, verify_cam(w, h, scale, fx, fy, cx, cy, prm), &rec, &down));
+    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int p = 0; p < n_poses; ++p) {
+        VerifyRec r;
+        std::memcpy(&r, down + (size_t)p * sizeof(VerifyRec), sizeof(r));
+        tdv_verify_result& o = results[p];
+        o.n_projected = r.n_projected;
+        o.n_consistent = r.cls[0]; o.n_occluded = r.cls[1]; o.n_violating = r.cls[2]; o.n_unknown = r.cls[3];
+        o.n_rendered = r.cls[0] + r.cls[1] + r.cls[2] + r.cls[3];
+        o.err_q20 = r.err;
+    }
+    if (order) {
+        std::iota(order, order + n_poses, 0);
+        std::stable_sort(order, order + n_poses, [&](int a, int b) {
+            return results[a].n_consistent - results[a].n_violating > results[b].n_consistent - results[b].n_violating;
+        });
+    }
+    return TDV_OK;
+}
+
+int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_pose, int w, int h, float fx, float fy, float cx, float cy,
+                         const tdv_verify_params& prm, float* d_out, int* n_rendered) {
+    const size_t px = (size_t)w * h;
+    if (px > 0) TDV_HIP(ctx, hipMemsetAsync(d_out, 0, px * sizeof(float), ctx->stream));    // the pixels outside the pose's tiles
+    VerifyRec* rec; char* down;
+    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_pose, 1, nullptr, d_out, verify_cam(w, h, 1.f, fx, fy, cx, cy, prm), &rec, &down));
+    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VerifyRec r;
+    std::memcpy(&r, down, sizeof(r));
+    if (n_rendered) *n_rendered = r.cls[0];
+    return TDV_OK;
+}
+
+}  // namespace tdv

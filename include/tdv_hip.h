@@ -832,6 +832,87 @@ int tdv_farthest_point_down_sample_batch_dev(tdv_ctx* ctx, const float* d_xyz, c
                                              float* d_out_d2 /* optional */, float* d_out_xyz /* optional */, float* d_out_attr /* optional */);
 int tdv_ctx_set_fps_path(tdv_ctx* ctx, int mode);
 int tdv_ctx_last_fps_path(tdv_ctx* ctx);
+/* Pose verification (the hypothesis-verification stage of the bin-picking pipelines): the model is rendered as a point splat at each
+ * candidate pose into the camera's depth image, and every rendered pixel is classified against the observed depth: it agrees, something
+ * stands in front of it, or the camera saw through it.  The fitness of tdv_icp_correspondences asks how many scene points lie near the
+ * model; this asks whether the model, at the pose, is consistent with what the camera saw.  One call takes all of a frame's candidates.
+ * Every output is an integer and every float that decides one is fixed by the rules below, so the results do not depend on the order the
+ * device works in.  All in f32, one rounding per operation, no contraction, the order exactly as written.
+ *  1. Camera coordinates of model point m under T (column-major, t = T[12..14]):
+ *     TDV_POSE_SOURCE_ONTO_TARGET (T as every registration here returns it, camera/scene onto model): d = m - t per component, then
+ *       xc = (T[0]*d0 + T[1]*d1) + T[2]*d2
+ *       yc = (T[4]*d0 + T[5]*d1) + T[6]*d2
+ *       zc = (T[8]*d0 + T[9]*d1) + T[10]*d2
+ *     This is R^T (m - t).  The rotation block is taken as orthonormal and is not checked.
+ *     TDV_POSE_MODEL_TO_CAMERA (T as synth.py's poses):
+ *       xc = ((T[0]*m0 + T[4]*m1) + T[8]*m2) + T[12]
+ *       yc = ((T[1]*m0 + T[5]*m1) + T[9]*m2) + T[13]
+ *       zc = ((T[2]*m0 + T[6]*m1) + T[10]*m2) + T[14]
+ *  2. Usable: xc, yc, zc are finite and 0 < zc <= zmax.
+ *  3. Pixel: uf = (xc*fx)/zc + cx, vf = (yc*fy)/zc + cy.  The point is unusable if either is non-finite or has magnitude >= 2^20.
+ *     u = (int)floorf(uf + 0.5f), v likewise.  The point covers the pixels [u-splat, u+splat] x [v-splat, v+splat] clipped to the frame.
+ *     A point whose centre is outside the frame still covers what its square reaches inside.  n_projected counts the usable points
+ *     (rules 2 and 3), whether or not they cover a pixel of the frame.
+ *  4. Rendered depth of a pixel: the minimum zc over the points that cover it.  The u32 bit pattern of a positive f32 orders as the
+ *     float, so an integer minimum is exact and its order free.
+ *  5. Observed depth: zo = float(raw) * float(1.0 / scale), the rule of tdv_depth_preprocess.  It is valid iff raw != 0 and zo <= zmax.
+ *  6. Class of a rendered pixel with valid zo: take diff = zo - zr.  Exactly one class holds: consistent iff fabsf(diff) <= tau; occluded
+ *     iff diff < -tau; violating iff diff > tau.  A rendered pixel without a valid zo is unknown.
+ *  7. err_q20: the sum over the consistent pixels of (uint32)(fabsf(diff) * 1048576.0f), the product in f32 and truncated; a product of
+ *     2^32 or more counts as 0xFFFFFFFF.
+ * NaN or infinite rows of the model and non-finite entries of a pose fall out through the usable test: a pose of NaNs gives a result of
+ * zeros, not an error.  For every pose n_rendered == n_consistent + n_occluded + n_violating + n_unknown.  The result is defined over the
+ * whole frame: the kernels bound their work by each pose's pixel box, cut into tiles of TDV_VERIFY_TILE_W x TDV_VERIFY_TILE_H pixels
+ * whose z-buffer lives in LDS (csrc/verify.hip), and none of that shows in a result.
+ * h_order (optional): the pose indices by n_consistent - n_violating descending, ties to the lower index, computed on the host from the
+ * integers.  tdv_verify_poses_dev takes the model and the raw u16 frame (row-major, the frame tdv_depth_to_cloud_dev reads) as device
+ * pointers, the poses (n_poses x 16 floats, column-major each) and the results on the host, and reads back once; tdv_verify_poses takes
+ * host arrays for the model and the frame too.  tdv_render_depth_dev writes the rendered depth of one pose as f32 (width x height, 0 where
+ * nothing rendered) to device memory and the number of rendered pixels to *n_rendered (optional); it reads no frame, and of params it uses
+ * pose_direction, splat and zmax (tau is checked all the same).  tdv_render_depth is its host form.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params, poses (n_poses > 0), results (n_poses > 0), model
+ * (n_model > 0), frame or depth output (width * height > 0); n_model < 0 or > TDV_VERIFY_MAX_MODEL; n_poses < 0 or > TDV_VERIFY_MAX_POSES;
+ * width or height < 0 or > TDV_VERIFY_MAX_SIDE; splat outside [0, TDV_VERIFY_MAX_SPLAT]; tau <= 0 or non-finite; scale, fx or fy <= 0 or
+ * non-finite; an unknown pose_direction.  n_poses == 0 and n_model == 0 are valid and give zeros.  The ctx's switches do not apply.  Not
+ * provided: mesh rasterisation, per-instance masks, a splat chosen from the model's resolution, verification inside
+ * tdv_register_batch_dev, the C++ operator mirror. */
+#define TDV_POSE_SOURCE_ONTO_TARGET 0
+#define TDV_POSE_MODEL_TO_CAMERA 1
+#define TDV_VERIFY_MAX_SPLAT 3
+#define TDV_VERIFY_MAX_MODEL (1 << 22)
+#define TDV_VERIFY_MAX_POSES 65536
+#define TDV_VERIFY_MAX_SIDE 8192
+#define TDV_VERIFY_TILE_W 128   /* 128 x 128 u32 = 64 KiB of LDS per workgroup: two workgroups per CU (csrc/verify.hip) */
+#define TDV_VERIFY_TILE_H 128
+#define TDV_VERIFY_LANES 1024   /* lanes of the workgroup that renders a tile */
+typedef struct tdv_verify_params {
+    int   pose_direction;  /* TDV_POSE_SOURCE_ONTO_TARGET (default) or TDV_POSE_MODEL_TO_CAMERA */
+    int   splat;           /* half-width in pixels of the square each model point covers, 0..TDV_VERIFY_MAX_SPLAT; default 1 */
+    float tau;             /* depth agreement band in metres, > 0; default 0.002 */
+    float zmax;            /* as tdv_deproject: observed and rendered depths beyond it do not count; default 10 */
+} tdv_verify_params;
+void tdv_verify_default_params(tdv_verify_params* params);
+typedef struct tdv_verify_result {   /* one per pose; every field an integer */
+    int n_projected;     /* model points that pass the usable test (rules 2 and 3) */
+    int n_rendered;      /* pixels of the frame that got a rendered depth */
+    int n_consistent;    /* rendered pixels with a valid observed depth within tau */
+    int n_occluded;      /* ... observed nearer than rendered by more than tau (something in front: explained) */
+    int n_violating;     /* ... observed farther than rendered by more than tau (seen through: contradicts the pose) */
+    int n_unknown;       /* rendered pixels with no valid observed depth */
+    unsigned long long err_q20;   /* rule 7 */
+} tdv_verify_result;
+int tdv_verify_poses_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, const float* h_poses /* host, n_poses x 16 */, int n_poses,
+                         const uint16_t* d_raw_depth /* u16, width x height */, int width, int height, float scale, float fx, float fy, float cx,
+                         float cy, const tdv_verify_params* params, tdv_verify_result* h_results /* host, [n_poses] */,
+                         int* h_order /* optional, host, [n_poses] */);
+int tdv_verify_poses(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* poses, int n_poses, const uint16_t* raw_depth, int width,
+                     int height, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params* params,
+                     tdv_verify_result* results, int* order /* optional */);
+int tdv_render_depth_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, const float* h_pose /* host, 16 */, int width, int height, float fx,
+                         float fy, float cx, float cy, const tdv_verify_params* params, float* d_out_depth /* f32, width x height */,
+                         int* n_rendered /* optional, host */);
+int tdv_render_depth(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* pose, int width, int height, float fx, float fy, float cx,
+                     float cy, const tdv_verify_params* params, float* out_depth, int* n_rendered /* optional */);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
