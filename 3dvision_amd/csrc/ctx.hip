@@ -51,7 +51,9 @@ int pin_reserve(tdv_ctx* ctx, size_t bytes) {
     if (bytes <= ctx->pin_cap) return TDV_OK;
     if (ctx->pin) { TDV_HIP(ctx, hipStreamSynchronize(ctx->stream)); (void)hipHostFree(ctx->pin); ctx->pin = nullptr; ctx->pin_cap = 0; }
     size_t cap = align_up(bytes, (size_t)1 << 16);
-    TDV_HIP(ctx, hipHostMalloc((void**)&ctx->pin, cap, hipHostMallocDefault));
+    // coherent (fine-grained), stated and not left to the environment's default: the host reads a RANSAC batch's record, and waits for
+    // its sequence word, while the stream that wrote them is still running (ransac.hip: wait_batch)
+    TDV_HIP(ctx, hipHostMalloc((void**)&ctx->pin, cap, hipHostMallocCoherent));
     ctx->pin_cap = cap;
     return TDV_OK;
 }

@@ -28,6 +28,7 @@
 //  (vi)  k_ransac_rmse_partial / k_ransac_rmse_final: error sum of the winning hypothesis only, fixed-order reduction (per-workgroup
 //        slabs, then one workgroup over the slabs).
 #include "tdv_internal.hpp"
+#include "host_wait.hpp"
 #include "device_linalg.hpp"
 #include "ransac_cut.hpp"
 #include <cfloat>
@@ -462,6 +463,19 @@ __device__ __forceinline__ void score_stats(unsigned n_rescored, C chunks, unsig
     }
 }
 
+// TDV_TIMER_RANSAC_SCORE without events (an event on either side of the dispatch cost the batch 5.7 us each,
+// profiles/r18/ransac_no_events.md): with timing on the dispatch gets a {t0, t1} pair (all the t0 words of a call, then all its t1
+// words: two memsets set them to all ones and 0), and thread 0 of a workgroup stamps the constant-rate clock into it - a minimum into
+// t0 as its first action, a maximum into t1 as its last, on every way out (behind score_stats' barriers, where thread 0 is the
+// workgroup's last word).  Atomics without a return: nothing waits for them.  t0 is stamped by the first eight workgroups only, one per
+// XCD: workgroups are dispatched in order, so the first to start is among them, and the other workgroups do not begin by waiting for
+// the clock.  t1 - t0 is the first workgroup's start to the last workgroup's end, inside the dispatch.  The kernel is a template
+// over STAMP: with timing off the instance that runs is the kernel without any of this (measured: the stamps' code alone, never
+// executed, cost phase 2 1.5 us of 46).
+struct ScoreStamp { unsigned long long *t0, *t1; };
+template <bool STAMP> __device__ __forceinline__ void score_stamp_begin(const ScoreStamp& stamp) { if (STAMP && threadIdx.x == 0 && blockIdx.x < 8) atomicMin(stamp.t0, wall_clock64()); }
+template <bool STAMP> __device__ __forceinline__ void score_stamp_end(const ScoreStamp& stamp) { if (STAMP && threadIdx.x == 0) atomicMax(stamp.t1, wall_clock64()); }
+
 // Occupancy (round 4).  The loop keeps a chunk's 48 floats in SGPRs and the compiler took 106 of them: 7 waves per SIMD on paper, but a
 // workgroup is 16 waves (4 per SIMD), so ONE workgroup per CU - 4 waves per SIMD to hide the scalar loads of a loop whose waves walk the
 // same chunks nearly in step.  Capped at the 8-wave budget (80 SGPRs; 43 values spilled to VGPR lanes, all outside the chunk loop) two
@@ -469,10 +483,12 @@ __device__ __forceinline__ void score_stats(unsigned n_rescored, C chunks, unsig
 // with it (16 spills: 1,209-1,223, within a point of this), chunks of 2 (1,140), 512-thread workgroups (1,177), chunks of 4 without it (1,034);
 // and, at 8 waves, a loop that loads the NEXT pair of points while it computes one (12 SGPRs in flight instead of 48, two waits per chunk
 // instead of one wait on everything): 1,196-1,210 against 1,213-1,221 on one box - with two workgroups per CU the scalar loads are hidden already.
+template <bool STAMP>
 __global__ __launch_bounds__(RS_BLOCK) __attribute__((amdgpu_waves_per_eu(8, 8)))
 void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const int h_pad, const float* __restrict__ pq2,
-                         const int n_pchunks, const float tau, unsigned long long* __restrict__ rescored) {
+                         const int n_pchunks, const float tau, unsigned long long* __restrict__ rescored, const ScoreStamp stamp) {
     const int id = blockIdx.x;
+    score_stamp_begin<STAMP>(stamp);
     unsigned n_rescored = 0;     // wave-uniform
     unsigned chunks = 0;         // chunks this workgroup walked (workgroup-uniform)
     if (id < g1) {
@@ -484,11 +500,11 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
         constexpr int XR = RS_XCD_R, XH = 8 / RS_XCD_R;
         const int hbl = (a.hb + XH - 1) / XH;
         const int hblock = (k % hbl) * XH + xcd / XR, split = (k / hbl) * XR + xcd % XR;
-        if (hblock >= a.hb || split >= a.ps) return;                // (counts that are not multiples of the group sizes: the last groups are short)
+        if (hblock >= a.hb || split >= a.ps) { score_stamp_end<STAMP>(stamp); return; }   // (counts that are not multiples of the group sizes: the last groups are short)
         const int c_split = a.plan ? a.plan[0] : n_pchunks;
         const int per = (c_split + a.ps - 1) / a.ps;
         const int c0 = split * per, c1 = min(c_split, c0 + per);
-        if (c0 >= c1) return;                                    // workgroup-uniform (ids past hb * ps, a prefix shorter than ps chunks)
+        if (c0 >= c1) { score_stamp_end<STAMP>(stamp); return; }        // workgroup-uniform (ids past hb * ps, a prefix shorter than ps chunks)
         const int base = hblock * RS_BLOCK + threadIdx.x;
         const int cnt = score_range_fast(a.hyp, h_pad, base, pq2, c0, c1, tau, n_rescored);
         atomicAdd(&a.counts[base], cnt);
@@ -535,11 +551,13 @@ void k_ransac_score_fast(const ScoreJob a, const ScoreJob b, const int g1, const
                 if (base >= 0) atomicAdd(&j.counts[base], cnt);
             }
         }
-        if (!wave_chunks) return;
+        if (!wave_chunks) { score_stamp_end<STAMP>(stamp); return; }
         score_stats(n_rescored, wave_chunks, rescored, 1u);
+        score_stamp_end<STAMP>(stamp);
         return;
     }
     score_stats(n_rescored, chunks, rescored);
+    score_stamp_end<STAMP>(stamp);
 }
 
 // RansacFarBound's per-call state (the rules are with the bound kernels below).  The pairs are ordered [F | M | I] by the ORDERING
@@ -882,7 +900,7 @@ __global__ __launch_bounds__(1024)
 void k_ransac_finish(const TriView triples, int count, const int* __restrict__ counts, const int* __restrict__ live, const int* __restrict__ n_live,
                      const int* __restrict__ near, const int* __restrict__ n_near, const float* __restrict__ hyp, int h_pad, int ns, float confidence, int it0,
                      int* __restrict__ state, int* __restrict__ sel, float* __restrict__ best12, const int* __restrict__ bad, int* __restrict__ rec,
-                     const int* __restrict__ lists, long long* __restrict__ bound) {
+                     const int* __restrict__ lists, long long* __restrict__ bound, const int seq) {
     const int n1 = live ? *n_live : count, n = n1 + (live && near ? *n_near : 0);      // (the near list behind the far one)
     const float fn = static_cast<float>((size_t)ns);
     __shared__ int s_stop, s_max;
@@ -961,6 +979,10 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     }
     rec[0] = best_local; rec[1] = best_count; rec[2] = stop_local; rec[3] = *bad;
     __threadfence_system();                                      // (the record may live in pinned host memory)
+    // the batch's sequence number behind the record, the launch's last store: the host waits for this word instead of an event
+    // (RansacRun::wait_batch; seq == 0: the batch ends with an event)
+    // (relaxed: the fence above is the release, and a release store would write the L2 back a second time)
+    if (seq) __hip_atomic_store(rec + 4, seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
 // ------------------------------------------------------------------ RansacLeafBound
@@ -1498,7 +1520,7 @@ static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * 
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far; int drop_permille, a_permille, u_cut_permille, fine_y; float far_radius, live_radius; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far, end_event, timer_events; int drop_permille, a_permille, u_cut_permille, fine_y; float far_radius, live_radius; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1533,6 +1555,9 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     k.leaf_classes = study_env("TDV_RANSAC_LEAF_CLASSES") && atoi(study_env("TDV_RANSAC_LEAF_CLASSES")) == 1;
     k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
     k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
+    // A/B knobs (profiles/r18/ransac_no_events.md): the batch's end by an event as it was; the fast kernel's score timer by events as it was
+    k.end_event = traced || k.record_copy || (study_env("TDV_RANSAC_END") && !strcmp(study_env("TDV_RANSAC_END"), "event"));   // (a traced call's counts come by a copy: it keeps the event)
+    k.timer_events = study_env("TDV_RANSAC_TIMER") && !strcmp(study_env("TDV_RANSAC_TIMER"), "events");
     k.upload_inline = study_env("TDV_RANSAC_UPLOAD") && !strcmp(study_env("TDV_RANSAC_UPLOAD"), "inline");   // A/B knob: the triples by a copy on the compute stream in front of k_ransac_hypotheses, not by the kernel's own loads from pinned memory
     k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 50;   // tuning knob: phase 1 over the first N - 0.95 best points (natural order: 5 to 100 measured equal;
                                                                                                                      // best's outliers first, round 12: 25, 50 and 75 above 100, profiles/r12/ransac_point_order.md)
@@ -1549,7 +1574,8 @@ struct RansacBuf {
     int* units;                                       // bail-out: job B's ticket words, [far, near][2 phases][8 XCDs][h_pad / RS_BLOCK], zeroed by the batch's k_ransac_hypotheses
     int *plan, *rec, *n_live, *n_und, *n_near;        // this buffer's fields of the RansacBlock and of RansacLive
     void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
-    hipEvent_t ev;                                    // the batch's end
+    hipEvent_t ev;                                    // the batch's end where an event marks it (traced calls; study build: TDV_RANSAC_RECORD=copy, TDV_RANSAC_END=event)
+    int seq;                                          // ... and everywhere else the sequence number that k_ransac_finish stores behind the record (h_rec[4])
 };
 struct RansacBatch { int q, cnt, it0; bool bounded; };        // buffer q holds cnt hypotheses from iteration it0 on
 struct RangeCut { int per, ranges; };                 // chunks per point range, point ranges
@@ -1577,6 +1603,8 @@ struct RansacRun {
     unsigned long long* ord_mask = nullptr; int* ord_cnt = nullptr; bool ordered = false;     // RansacPointOrder: ballot words, block counts (outliers, then F); done for this call
     unsigned* enc = nullptr;                          // RansacLeafBound: the finite coordinates' bounds per axis
     RansacBuf buf[2] = {};
+    // TDV_TIMER_RANSAC_SCORE's stamps (score_stamp_begin): a {t0, t1} pair per dispatch of k_ransac_score_fast, nullptr with timing off
+    unsigned long long *stamps = nullptr, *h_stamps = nullptr; int n_stamps = 0, stamps_used = 0;
     RansacBatch pending = {}; bool has_pending = false;       // merged dispatch (study build): the batch whose phase 2 is not enqueued yet
     double wave_chunks = 0.0;                         // wave x chunk pairs the call would score without bail-out
     float best_fitness = 0.f; int best_iter = -1, best_inliers = 0, done_iters = 0; bool stop = false;   // the reference loop's state
@@ -1620,23 +1648,45 @@ struct RansacRun {
         }
         if (k.far) for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.near)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list2)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.ubf)); }
         rblocks = (ns + 255) / 256; TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
-        // pinned: the block | 2 x triples | 2 x counts (traced calls only)
+        // the score timer's stamps: two dispatches per batch and one to spare, {all ones, 0} each
+        if (ctx->timing && k.score_fast && !k.score_mfma && !k.timer_events) {
+            const int n_batches = max_iterations <= first_batch ? 1 : 1 + (int)(((size_t)(max_iterations - first_batch) + batch - 1) / batch);
+            n_stamps = 2 * n_batches + 1;
+            TDV_TRY(ws_alloc(ctx, (size_t)2 * n_stamps, &stamps));
+            TDV_HIP(ctx, hipMemsetAsync(stamps, 0xff, (size_t)n_stamps * 8, s));              // [n_stamps] t0, then [n_stamps] t1
+            TDV_HIP(ctx, hipMemsetAsync(stamps + n_stamps, 0, (size_t)n_stamps * 8, s));
+        }
+        // pinned: the block | 2 x triples | 2 x counts (traced calls only) | the stamps (timing on)
         const size_t sz_blk = align_up(sizeof(RansacBlock), 64), sz_tri = align_up((size_t)batch * tri_bytes, 64), sz_cnt = trace ? align_up((size_t)batch * 4, 64) : 0;
-        TDV_TRY(pin_reserve(ctx, sz_blk + 2 * sz_tri + 2 * sz_cnt));
+        TDV_TRY(pin_reserve(ctx, sz_blk + 2 * sz_tri + 2 * sz_cnt + (size_t)n_stamps * 16));
         h = reinterpret_cast<RansacBlock*>(ctx->pin); h->bad = 0;
+        h->rec[0][4] = h->rec[1][4] = 0;              // the sequence words: nothing of an earlier call (the stream is idle: ransac_run_dev)
+        h_stamps = reinterpret_cast<unsigned long long*>(ctx->pin + sz_blk + 2 * sz_tri + 2 * sz_cnt);
         if (trace) TDV_HIP(ctx, hipMemcpyAsync(&h->bad, &d->bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts (RansacFinish: the flag comes in the record)
         for (int q = 0; q < 2; ++q) {
             RansacBuf& B = buf[q];
             B.plan = d->plan[q]; B.rec = d->rec[q]; B.n_live = lv ? &lv->n_live[q] : nullptr; B.n_und = lv ? &lv->n_und[q] : nullptr; B.n_near = lv ? &lv->n_near[q] : nullptr;
             B.h_tri = ctx->pin + sz_blk + q * sz_tri; B.h_cnt = reinterpret_cast<int*>(ctx->pin + sz_blk + 2 * sz_tri + q * sz_cnt); B.h_rec = h->rec[q];
         }
-        buf[0].ev = event_acquire(ctx); buf[1].ev = event_acquire(ctx);   // from the ctx's pool: no create/destroy per call
-        if (!buf[0].ev || !buf[1].ev) { release_events(); return TDV_ERR_OOM; }
+        if (k.end_event) {
+            buf[0].ev = event_acquire(ctx); buf[1].ev = event_acquire(ctx);   // from the ctx's pool: no create/destroy per call
+            if (!buf[0].ev || !buf[1].ev) { release_events(); return TDV_ERR_OOM; }
+        }
         return TDV_OK;
+    }
+    // the next dispatch's stamp pair (nullptr: timing off, or - cannot happen - more dispatches than setup counted), and the
+    // slot its ScopedTimer gets: none where the stamps time it
+    ScoreStamp next_stamp() { if (!stamps || stamps_used >= n_stamps) return ScoreStamp{nullptr, nullptr}; const int e = stamps_used++; return ScoreStamp{stamps + e, stamps + n_stamps + e}; }
+    int score_slot() const { return stamps ? -1 : TDV_TIMER_RANSAC_SCORE; }
+    // a dispatch of k_ransac_score_fast: with timing on the instance that stamps, and the dispatch's pair
+    void launch_score(int grid, const ScoreJob& a, const ScoreJob& b, int g1) {
+        const ScoreStamp st = next_stamp();
+        if (st.t0) k_ransac_score_fast<true><<<grid, RS_BLOCK, 0, s>>>(a, b, g1, h_pad, pq2, n_pchunks, tau, &d->rescored, st);
+        else k_ransac_score_fast<false><<<grid, RS_BLOCK, 0, s>>>(a, b, g1, h_pad, pq2, n_pchunks, tau, &d->rescored, st);
     }
     int unit_words() const { return 4 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's, then the near lists' two
     int order_blocks() const { return (ns + RO_BLOCK - 1) / RO_BLOCK; }
-    void release_events() { for (RansacBuf& B : buf) event_release(ctx, B.ev); }
+    void release_events() { for (RansacBuf& B : buf) { event_release(ctx, B.ev); B.ev = nullptr; } }
     // RansacLeafBound's summary of the pairs: fine and coarse leaves along the class-major Morton order.  Its buffers ...
     int leaf_alloc() {
         const int n_leaves = (ns + RL_LEAF - 1) / RL_LEAF, n_cleaves = (ns + RL_COARSE - 1) / RL_COARSE;
@@ -1663,7 +1713,8 @@ struct RansacRun {
         TDV_CHECK_LAUNCH(ctx); return TDV_OK;
     }
 
-    // ---- a batch's steps.  TDV_TIMER_RANSAC_SCORE brackets every dispatch of a scoring kernel on its own.
+    // ---- a batch's steps.  TDV_TIMER_RANSAC_SCORE times every dispatch of a scoring kernel on its own: k_ransac_score_fast by its
+    // stamps, the others between two events.
     // host: the next cnt triples of the index stream into buffer q (i0, i1, i2, valid: registration.cpp:240)
     int draw(TripleStream& idx, int q, int it0) {
         const int cnt = std::min(it0 == 0 ? first_batch : batch, max_iterations - it0);
@@ -1676,8 +1727,8 @@ struct RansacRun {
     // The host draws the triples into pinned memory, which the device can read, so k_ransac_hypotheses loads them from there and
     // leaves the device copy behind for the batch's later kernels.
     //  - buf[q].h_tri is written by draw(q) and must hold still until the batch's k_ransac_hypotheses has run.  The next draw into it is
-    //    for the batch after the next, and loop() waits for this batch's event before that.  A traced call's consume_trace reads it on
-    //    the host, behind the same event.
+    //    for the batch after the next, and loop() waits for this batch's end (wait_batch) before that.  A traced call's consume_trace
+    //    reads it on the host, behind the batch's event.
     //  - After an early exit a batch that was drawn and enqueued may still read h_tri: ransac_run_dev synchronises the compute stream
     //    on every way out of loop(), before the next entry point draws into the pinned block or lets pin_reserve move it.
     //  - Traced calls and the merged dispatch (study build) read the same way; TDV_RANSAC_UPLOAD=inline (study build) is the copy on the
@@ -1696,7 +1747,7 @@ struct RansacRun {
     // every test of the batch, no plan: the exact kernel, the fast one, or (study build) the matrix cores
     int score_all(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q]; const int hb = hyp_blocks(b.cnt);
-        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
+        ScopedTimer tm(ctx, k.score_fast && !k.score_mfma ? score_slot() : TDV_TIMER_RANSAC_SCORE);
 #ifdef TDV_STUDY
         if (k.score_mfma) wave_chunks += mfma_score(s, B.hyp, h_pad, pq3, ns, b.cnt, tau, B.counts, &d->rescored);
         else
@@ -1704,7 +1755,7 @@ struct RansacRun {
         if (k.score_fast) {
             const ScoreJob ja{B.hyp, B.counts, nullptr, nullptr, hb, range_cut(hb, n_pchunks).ranges, nullptr, nullptr, nullptr};
             const int gA = score_grid(hb, ja.ps);
-            k_ransac_score_fast<<<gA, RS_BLOCK, 0, s>>>(ja, ja, gA, h_pad, pq2, n_pchunks, tau, &d->rescored);
+            launch_score(gA, ja, ja, gA);
             wave_chunks += (double)hb * (RS_BLOCK / 64) * (double)n_pchunks;
         } else {
             const RangeCut c = range_cut(h_pad / RS_HYP_PER_BLOCK, n_pchunks);
@@ -1742,9 +1793,9 @@ struct RansacRun {
         const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, hbw, 0, B.n_live, B.units, nullptr};
         const ScoreJob jn = k.far ? ScoreJob{B.hyp, B.counts, B.plan, B.near, hbw, 0, B.n_near, B.units + 16 * hbw, &d->far.c_far} : jl;   // the near list rides behind the far one
         const int g1 = score_grid(ja.hb, ja.ps);          // (a multiple of 8: job B's XCD numbering starts there)
-        ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE);
-        if (b.bounded) k_ransac_score_fast<<<unit_grid(cus), RS_BLOCK, 0, s>>>(jn, jl, 0, h_pad, pq2, n_pchunks, tau, &d->rescored);
-        else k_ransac_score_fast<<<g1, RS_BLOCK, 0, s>>>(ja, ja, g1, h_pad, pq2, n_pchunks, tau, &d->rescored);
+        ScopedTimer tm(ctx, score_slot());
+        if (b.bounded) launch_score(unit_grid(cus), jn, jl, 0);
+        else launch_score(g1, ja, ja, g1);
     }
     // survivors of the batch: the in-batch bound first (largest prefix count), then the list (bounded: both in one launch over its live list)
     int select(const RansacBatch& b) {
@@ -1766,25 +1817,53 @@ struct RansacRun {
         const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbw, 0, nullptr, B.units + 8 * hbw, nullptr};
         const ScoreJob jn = k.far && b.bounded ? ScoreJob{B.hyp, B.counts, B.plan, B.list2, hbw, 0, nullptr, B.units + 24 * hbw, &d->far.c_far} : jb;   // the near list's survivors behind the far one's
         const int g2 = unit_grid(cus);
-        { ScopedTimer tm(ctx, TDV_TIMER_RANSAC_SCORE); k_ransac_score_fast<<<g1 + g2, RS_BLOCK, 0, s>>>(a ? *a : jn, jb, g1, h_pad, pq2, n_pchunks, tau, &d->rescored); }
+        { ScopedTimer tm(ctx, score_slot()); launch_score(g1 + g2, a ? *a : jn, jb, g1); }
         TDV_CHECK_LAUNCH(ctx); return TDV_OK;
     }
-    // the batch's end: RansacFinish and its record, or - traced - every count to the host; then the event.  with_state: the batch's
-    // largest full count raises state[0] (a batch with bail-out)
+    // the batch's end: RansacFinish and its record, or - traced - every count to the host.  with_state: the batch's
+    // largest full count raises state[0] (a batch with bail-out).
+    // No event stands behind the batch: an event record kept the next batch's k_ransac_hypotheses 5.8 us away
+    // (profiles/r18/ransac_no_events.md).  k_ransac_finish stores the batch's sequence number - the ctx's counter, never 0, one more
+    // per batch, so no word an earlier batch or call left can match - behind its record, and loop() waits for that word.
     int finish(const RansacBatch& b, bool with_state) {
-        const RansacBuf& B = buf[b.q];
+        RansacBuf& B = buf[b.q];
         TDV_CHECK_LAUNCH(ctx);
+        B.seq = 0;
+        if (!k.end_event) { if (++ctx->ransac_seq <= 0) ctx->ransac_seq = 1; B.seq = ctx->ransac_seq; }
         if (!trace) {
             const bool live_only = b.bounded && confidence >= 0.f;      // (see k_ransac_finish)
             int* rec = k.record_copy ? B.rec : const_cast<int*>(B.h_rec);
             k_ransac_finish<<<1, 1024, 0, s>>>(tri(B), b.cnt, B.counts, live_only ? B.live : nullptr, live_only ? B.n_live : nullptr,
                                                k.far ? B.near : nullptr, B.n_near, B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec,
-                                               b.bounded ? B.n_live : nullptr, d->bound);
+                                               b.bounded ? B.n_live : nullptr, d->bound, B.seq);
             TDV_CHECK_LAUNCH(ctx);
             if (k.record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(B.h_rec), B.rec, sizeof(d->rec[0]), hipMemcpyDeviceToHost, s));
         } else TDV_HIP(ctx, hipMemcpyAsync(B.h_cnt, B.counts, (size_t)b.cnt * 4, hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipEventRecord(B.ev, s));
+        if (k.end_event) TDV_HIP(ctx, hipEventRecord(B.ev, s));
         return TDV_OK;
+    }
+    // The host's wait for the batch in buffer B.  With a sequence word: an acquire load in a spin (host_wait.hpp) until
+    // k_ransac_finish's last store - at system scope, behind its record and its system fence - has landed in the
+    // fine-grained pinned block; what the event gave is what this gives: every kernel of the batch has done its work (they run in
+    // stream order in front of that store), so the record is whole and the batch's h_tri may be drawn over.  The spin cannot hang:
+    // at intervals by the host's clock it asks the stream, and a stream that failed, or that ran dry without the word, ends the call.
+    // (The question is not free: asked about a stream that is still running, the runtime puts a marker behind the last command
+    // enqueued - the next batch's k_ransac_finish - and the kernel behind a marker starts 5.8 us late, which is the very gap the
+    // event left.  So it is asked rarely: a batch of 65,536 hypotheses over 200k pairs takes a third of a millisecond and ends before
+    // the first question; a longer one meets a marker per kRecordPollUs, a part in a thousand of its time.)
+    static constexpr int kRecordPollUs = 5000;
+    int wait_batch(const RansacBuf& B) {
+        if (k.end_event) return hipEventSynchronize(B.ev) == hipSuccess ? TDV_OK : TDV_ERR_LAUNCH;
+        hipError_t err = hipSuccess;
+        const int st = wait_for_word(B.h_rec + 4, B.seq, [&] {
+            err = hipStreamQuery(s);
+            if (err == hipErrorNotReady) { (void)hipGetLastError(); return 1; }     // (not an error: it must not meet the next TDV_CHECK_LAUNCH)
+            return err == hipSuccess ? 0 : -1;
+        }, kRecordPollUs);
+        if (st == HOST_WAIT_OK) return TDV_OK;
+        if (st == HOST_WAIT_FAILED) return set_err(ctx, err, "ransac: the stream, while waiting for a batch's record,", __LINE__);
+        std::snprintf(ctx->err, sizeof(ctx->err), "ransac: the stream ran dry and batch %d's record never came", B.seq);
+        return TDV_ERR_LAUNCH;
     }
     // Study build, TDV_RANSAC_MERGE=1: one scoring dispatch per batch - its phase 1 and, behind it, phase 2 of the batch before, whose
     // end follows.  Measured: a point of lane-op utilisation gained, but the counts reach the host a dispatch later and the call loses
@@ -1818,7 +1897,7 @@ struct RansacRun {
         return finish(b, true);
     }
 
-    // ---- the host side of one batch, after its event
+    // ---- the host side of one batch, after its end (wait_batch)
     // RansacFinish ran the loop of registration.cpp:281-290 on the device: its record
     void consume_record(const RansacBuf& B, int it0, int cnt) {
         const int k_best = B.h_rec[0], k_stop = B.h_rec[2];
@@ -1855,12 +1934,24 @@ struct RansacRun {
                 TDV_TRY(enqueue(nxt, cnt_next, it_next));
             } else if (has_pending) TDV_TRY(finish_pending());      // (merged dispatch) the last batch's phase 2 runs alone
             const RansacBuf& B = buf[cur];
-            if (hipEventSynchronize(B.ev) != hipSuccess) return TDV_ERR_LAUNCH;
+            TDV_TRY(wait_batch(B));
             if (trace ? h->bad : B.h_rec[3]) { std::snprintf(ctx->err, sizeof(ctx->err), "ransac: a correspondence index lies outside [0, %d)", nt); return TDV_ERR_BAD_ARG; }
             if (trace) TDV_TRY(consume_trace(B, it0, cnt_cur));
             else consume_record(B, it0, cnt_cur);
             cur = nxt; it0 = it_next; cnt_cur = cnt_next;
         }
+        return TDV_OK;
+    }
+
+    // TDV_TIMER_RANSAC_SCORE from the stamps: every dispatch of k_ransac_score_fast the call enqueued counts as a launch, and adds its
+    // last workgroup's end minus its first workgroup's start, in ticks of the constant-rate clock
+    int read_stamps() {
+        if (!ctx->wall_clock_khz) TDV_HIP(ctx, hipDeviceGetAttribute(&ctx->wall_clock_khz, hipDeviceAttributeWallClockRate, ctx->device));
+        unsigned long long ticks = 0ull;
+        for (int e = 0; e < stamps_used; ++e) if (h_stamps[n_stamps + e] > h_stamps[e]) ticks += h_stamps[n_stamps + e] - h_stamps[e];
+        TimerSlot& t = ctx->timers[TDV_TIMER_RANSAC_SCORE];
+        if (ctx->wall_clock_khz > 0) t.total_ms += (double)ticks / (double)ctx->wall_clock_khz;
+        t.launches += stamps_used;
         return TDV_OK;
     }
 
@@ -1875,7 +1966,11 @@ struct RansacRun {
             k_ransac_rmse_final<<<1, 256, 0, s>>>(slabs, rblocks, d->out2);
             TDV_CHECK_LAUNCH(ctx);
         }
-        if (best_iter >= 0 || want_stats) { TDV_HIP(ctx, hipMemcpyAsync(h, d, kRansacReadBack, hipMemcpyDeviceToHost, s)); TDV_HIP(ctx, hipStreamSynchronize(s)); }
+        if (best_iter >= 0 || want_stats) {
+            if (stamps_used) TDV_HIP(ctx, hipMemcpyAsync(h_stamps, stamps, (size_t)n_stamps * 16, hipMemcpyDeviceToHost, s));
+            TDV_HIP(ctx, hipMemcpyAsync(h, d, kRansacReadBack, hipMemcpyDeviceToHost, s)); TDV_HIP(ctx, hipStreamSynchronize(s));
+            if (stamps_used) TDV_TRY(read_stamps());
+        }
         if (want_stats) {
             const double scored = h->scored ? (double)h->scored : wave_chunks;
             ctx->last_ransac_rescore = (double)h->rescored / (scored * (k.score_mfma ? 1.0 : (double)(RS_PCH / 2)));      // the FMA kernel counts point pairs scored twice, the matrix-core study kernel chunks

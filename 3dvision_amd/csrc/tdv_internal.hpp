@@ -57,6 +57,8 @@ struct tdv_ctx {
     tdv_ctx* helper = nullptr;   // second stream + workspace of the batched pipeline's other lane (owned; created on first use)
     tdv::TimerSlot timers[TDV_TIMER_COUNT];
     std::vector<hipEvent_t> event_pool;
+    int ransac_seq = 0;          // the sequence number of the last RANSAC batch enqueued on this ctx (ransac.hip: the record's word [4]); never 0
+    int wall_clock_khz = 0;      // hipDeviceAttributeWallClockRate, read on first use (ransac.hip: the score timer's stamps)
 };
 
 namespace tdv {

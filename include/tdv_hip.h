@@ -163,7 +163,11 @@ const char* tdv_version(void);
 
 /* Kernel timing (HIP events on the ctx's stream around the dominant kernels).  Slots:
  * 0 = ICP nearest-neighbour scan, 1 = RANSAC scoring, 2 = feature match, 3 = kNN scan,
- * 4 = radius scan, 5 = depth+unproject, 6 = voxel, 7 = descriptor index.  Enabling adds one event pair per launch. */
+ * 4 = radius scan, 5 = depth+unproject, 6 = voxel, 7 = descriptor index.  Enabling adds one event pair per launch.
+ * Slot 1 is read without events where the fast scoring kernel runs (tdv_ransac* in its default mode): every dispatch stamps
+ * the device's constant-rate clock itself, and its time is the first workgroup's start to the last workgroup's end - inside the
+ * dispatch, so a little below what two events around it read (they read from one queue marker to the next), and without the
+ * idle time an event record puts between two kernels.  The exact kernel and the batched small-cloud pass stay on events. */
 #define TDV_TIMER_ICP_NN 0
 #define TDV_TIMER_RANSAC_SCORE 1
 #define TDV_TIMER_FEATURE_MATCH 2

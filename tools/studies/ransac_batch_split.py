@@ -7,19 +7,25 @@ With a copy trace it also prints the batch's path: every kernel of a batch in st
 the end of the kernel before it to its start, kernels only: what the compute stream waits), and per host-to-device copy its
 duration, the time from the end of the last kernel that started before it to its start, and the time from its end to the start of
 the next kernel.  Means over the bounded batches behind the first one (batches 3..n: the second builds the leaves).
-    python tools/studies/ransac_batch_split.py <kernel_trace.csv> [<memory_copy_trace.csv>]"""
+    python tools/studies/ransac_batch_split.py [--call K] <kernel_trace.csv> [<memory_copy_trace.csv>]
+--call K: the K-th RANSAC call of the trace instead of the last, counted over the k_gather_pq launches as Python indexes a list
+(-1, the default, is the last call, -3 the third from the end; tools/studies/ransac_event_gaps.py makes four)."""
 import collections
 import csv
 import sys
 
+argv = sys.argv[1:]
+call = -1                       # which RANSAC call of the trace, counted over its k_gather_pq launches (-1: the last)
+if argv and argv[0] == "--call":
+    call = int(argv[1]); argv = argv[2:]
 rows = []
-for f in sys.argv[1:]:
+for f in argv:
     for r in csv.DictReader(open(f)):
         name = r.get("Kernel_Name") or ("copy " + r.get("Direction", "?"))
         rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name.split("(")[0].split("<")[0].strip()))
 rows.sort()
 gathers = [i for i, r in enumerate(rows) if r[2].endswith("k_gather_pq")]
-rows = rows[gathers[-1]:]
+rows = rows[gathers[call]:gathers[call + 1] if call + 1 < 0 and call + 1 >= -len(gathers) else None]
 hyps = [r[0] for r in rows if r[2].endswith("k_ransac_hypotheses")]
 nb = len(hyps)
 rows = [r for r in rows if r[0] >= hyps[0] or r[2].startswith("copy")]
