@@ -67,6 +67,7 @@ ABI_SYMBOLS = [
     "tdv_farthest_point_down_sample", "tdv_farthest_point_down_sample_dev", "tdv_farthest_point_down_sample_batch_dev",
     "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path",
     "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
+    "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
 ]
 
 
@@ -262,6 +263,36 @@ def _verify_result(r):
     return {k: int(getattr(r, k)) for k, _ in VerifyResultC._fields_}
 
 
+TDV_MESH_CULL_NONE, TDV_MESH_CULL_BACK = 0, 1
+TDV_MESH_MAX_VERTICES = 1 << 22
+TDV_MESH_MAX_TRIANGLES = 1 << 22
+TDV_MESH_SUBPIXEL = 16
+TDV_MESH_COOP_PIXELS = 64
+TDV_MESH_QUEUE = 128
+MESH_CULL = {"none": TDV_MESH_CULL_NONE, "back": TDV_MESH_CULL_BACK}
+
+
+class MeshVerifyParamsC(C.Structure):
+    _fields_ = [("pose_direction", C.c_int), ("cull", C.c_int), ("tau", C.c_float), ("zmax", C.c_float)]
+
+
+def mesh_verify_params(**kw):
+    """tdv_mesh_verify_default_params (T moves the camera's cloud onto the model, no culling, tau 0.002 m, zmax 10 m) with the given fields
+    replaced; pose_direction and cull also by name ('source_onto_target', 'model_to_camera'; 'none', 'back')."""
+    p = MeshVerifyParamsC()
+    lib().tdv_mesh_verify_default_params(C.byref(p))
+    names = dict(pose_direction=POSE_DIRECTION, cull=MESH_CULL)
+    for k, v in kw.items():
+        if k not in dict(MeshVerifyParamsC._fields_):
+            raise TypeError("unknown mesh verification parameter %r" % k)
+        setattr(p, k, names[k][v] if k in names and isinstance(v, str) else v)
+    return p
+
+
+def _mesh(vertices, triangles):
+    return _f32(vertices).reshape(-1, 3), np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
+
+
 def _poses16(poses):
     """[n, 4, 4] row-major poses as the ABI's n x 16 column-major floats."""
     poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
@@ -359,6 +390,7 @@ def lib():
             l.tdv_iss_default_params.restype = None
             l.tdv_ppf_default_params.restype = None
             l.tdv_verify_default_params.restype = None
+            l.tdv_mesh_verify_default_params.restype = None
             _lib = l
     return _lib
 
@@ -1153,6 +1185,55 @@ class Context:
         _check(self._h, lib().tdv_render_depth_dev(self._h, _ptr(d_model), int(n_model), _ptr(to_colmajor16(pose)), int(w), int(h), C.c_float(fx),
                                                    C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)),
                                                    _ptr(d_out_depth), C.byref(n)), "tdv_render_depth_dev")
+        return n.value
+
+    # ---------------------------------------------------------------- pose verification from a mesh (include/tdv_hip.h: tdv_verify_poses_mesh)
+    def verify_poses_mesh(self, vertices, triangles, poses, raw, scale, fx, fy, cx, cy, **params):
+        """tdv_verify_poses_mesh: verify_poses with the model's faces rasterised - vertices [n, 3], triangles int [m, 3] - in place of a
+        point splat.  Returns what verify_poses returns; n_projected counts the usable triangles.  params: mesh_verify_params' fields
+        (pose_direction, cull, tau, zmax)."""
+        vtx, tri = _mesh(vertices, triangles)
+        raw = np.ascontiguousarray(raw, np.uint16)
+        h, w = raw.shape
+        t, n = _poses16(poses)
+        res = (VerifyResultC * max(n, 1))()
+        order = np.zeros(n, np.int32)
+        _check(self._h, lib().tdv_verify_poses_mesh(self._h, _ptr(vtx), len(vtx), _ptr(tri), len(tri), _ptr(t), n, _ptr(raw), w, h, C.c_float(scale),
+                                                    C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),
+                                                    C.byref(mesh_verify_params(**params)), res, _ptr(order)), "tdv_verify_poses_mesh")
+        return [_verify_result(res[b]) for b in range(n)], order
+
+    def verify_poses_mesh_dev(self, d_vertices, n_vertices, d_triangles, n_triangles, poses, d_raw, w, h, scale, fx, fy, cx, cy, **params):
+        """tdv_verify_poses_mesh_dev: verify_poses_mesh with the vertices (float[3 n_vertices]), the triangles (int32[3 n_triangles]) and the
+        raw frame (uint16[w h]) as device pointers; the poses and the results stay on the host.  One read-back."""
+        t, n = _poses16(poses)
+        res = (VerifyResultC * max(n, 1))()
+        order = np.zeros(n, np.int32)
+        _check(self._h, lib().tdv_verify_poses_mesh_dev(self._h, _ptr(d_vertices), int(n_vertices), _ptr(d_triangles), int(n_triangles), _ptr(t), n,
+                                                        _ptr(d_raw), int(w), int(h), C.c_float(scale), C.c_float(fx), C.c_float(fy), C.c_float(cx),
+                                                        C.c_float(cy), C.byref(mesh_verify_params(**params)), res, _ptr(order)),
+               "tdv_verify_poses_mesh_dev")
+        return [_verify_result(res[b]) for b in range(n)], order
+
+    def render_depth_mesh(self, vertices, triangles, pose, w, h, fx, fy, cx, cy, **params):
+        """tdv_render_depth_mesh: the rendered depth of the mesh at one pose, float32 [h, w], 0 where nothing rendered - per pixel the
+        minimum interpolated depth over the triangles that cover its centre (the z-buffer verify_poses_mesh classifies)."""
+        vtx, tri = _mesh(vertices, triangles)
+        out = np.zeros((int(h), int(w)), np.float32)
+        n = C.c_int()
+        _check(self._h, lib().tdv_render_depth_mesh(self._h, _ptr(vtx), len(vtx), _ptr(tri), len(tri), _ptr(to_colmajor16(pose)), int(w), int(h),
+                                                    C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),
+                                                    C.byref(mesh_verify_params(**params)), _ptr(out), C.byref(n)), "tdv_render_depth_mesh")
+        return out
+
+    def render_depth_mesh_dev(self, d_vertices, n_vertices, d_triangles, n_triangles, pose, w, h, fx, fy, cx, cy, d_out_depth, **params):
+        """tdv_render_depth_mesh_dev: render_depth_mesh from a device mesh into the device image d_out_depth (float[w h]); returns
+        n_rendered."""
+        n = C.c_int()
+        _check(self._h, lib().tdv_render_depth_mesh_dev(self._h, _ptr(d_vertices), int(n_vertices), _ptr(d_triangles), int(n_triangles),
+                                                        _ptr(to_colmajor16(pose)), int(w), int(h), C.c_float(fx), C.c_float(fy), C.c_float(cx),
+                                                        C.c_float(cy), C.byref(mesh_verify_params(**params)), _ptr(d_out_depth), C.byref(n)),
+               "tdv_render_depth_mesh_dev")
         return n.value
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)

@@ -362,6 +362,15 @@ int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float*
 int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_pose, int w, int h, float fx, float fy, float cx, float cy,
                          const tdv_verify_params& prm, float* d_out, int* n_rendered);
 
+// Pose verification from a mesh (verify_mesh.hip, include/tdv_hip.h: tdv_verify_poses_mesh): as the three above, for the mesh renderer.
+bool mesh_verify_args_ok(const tdv_ctx* ctx, const float* vtx, int nv, const int* tri, int nt, const float* poses, int n_poses, const void* frame,
+                         int w, int h, float scale, float fx, float fy, const tdv_mesh_verify_params* p, const void* results);
+int mesh_verify_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_poses, int n_poses,
+                        const uint16_t* d_raw, int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params& prm,
+                        tdv_verify_result* results, int* order);
+int mesh_render_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_pose, int w, int h, float fx, float fy,
+                        float cx, float cy, const tdv_mesh_verify_params& prm, float* d_out, int* n_rendered);
+
 // PPF matching (ppf.hip, include/tdv_hip.h: tdv_ppf_match).  PpfPlan: what the parameters alone fix (n_dist, n_keys, the table's layout for
 // nt points); ppf_plan is the parameter check of every entry point.  ppf_model_run builds the table (rule 4) into d_model and fills info;
 // ppf_match_run votes, clusters and scores (h_peaks: where a host call's peaks go); ppf_match_batch_run is it per instance of an offsets

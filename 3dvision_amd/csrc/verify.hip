@@ -12,57 +12,17 @@
 //                    reduce the counts over the wave with DPP and add them to the pose's record; or, for tdv_render_depth, write the tile
 //                    out as f32.  The grid never needs the tile total on the host: the call reads back once, the records.
 // Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md 7, "Pose verification".
-#include "tdv_internal.hpp"
+// The record, the projection, the tile list and the classify-and-reduce tail are verify_common.hpp's, shared with the mesh renderer
+// (verify_mesh.hip); the host side of a call that both renderers use - stage, plan, fetch, results and order - is defined at the end.
+#include "verify_common.hpp"
 #include <algorithm>
 #include <numeric>
 
 namespace tdv {
 namespace {
 
-constexpr int VT = TDV_VERIFY_LANES, TW = TDV_VERIFY_TILE_W, TH = TDV_VERIFY_TILE_H, TILE = TW * TH;
-constexpr unsigned EMPTY = 0xFFFFFFFFu;                     // above the bits of every positive finite f32
-constexpr int VERIFY_GRID = 512;                            // 256 CUs x the two workgroups of 64 KiB LDS a CU holds
-static_assert(TILE % (4 * VT) == 0 && (TW & (TW - 1)) == 0, "the clear and the pixel walk assume it");
-
-struct VerifyRec {                                          // one per pose (device)
-    int n_projected;
-    int u0, v0, u1, v1;                                     // the covered pixels' box inside the frame; u0 > u1: none
-    int cls[4];                                             // consistent, occluded, violating, unknown (render: cls[0] = rendered)
-    int pad;
-    unsigned long long err;
-};
-struct VerifyCam { float fx, fy, cx, cy, zmax, tau, inv_scale; int w, h, splat, direction; };
-struct Pose16 { float T[16]; };
-
-__device__ __forceinline__ Pose16 load_pose(const float* __restrict__ poses, int pose) {
-    Pose16 p;
-    const float* T = poses + (size_t)pose * 16;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) p.T[k] = T[k];
-    return p;
-}
-
-// rules 1 to 3 of include/tdv_hip.h, as written there
-__device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& zc) {
-    const float* T = P.T;
-    float xc, yc;
-    if (c.direction == TDV_POSE_SOURCE_ONTO_TARGET) {
-        const float d0 = m0 - T[12], d1 = m1 - T[13], d2 = m2 - T[14];
-        xc = (T[0] * d0 + T[1] * d1) + T[2] * d2;
-        yc = (T[4] * d0 + T[5] * d1) + T[6] * d2;
-        zc = (T[8] * d0 + T[9] * d1) + T[10] * d2;
-    } else {
-        xc = ((T[0] * m0 + T[4] * m1) + T[8] * m2) + T[12];
-        yc = ((T[1] * m0 + T[5] * m1) + T[9] * m2) + T[13];
-        zc = ((T[2] * m0 + T[6] * m1) + T[10] * m2) + T[14];
-    }
-    if (!(fabsf(xc) < INFINITY && fabsf(yc) < INFINITY && zc > 0.f && zc <= c.zmax && zc < INFINITY)) return false;
-    const float uf = (xc * c.fx) / zc + c.cx, vf = (yc * c.fy) / zc + c.cy;
-    if (!(fabsf(uf) < 1048576.f && fabsf(vf) < 1048576.f)) return false;          // (false for NaN too)
-    u = (int)floorf(uf + 0.5f);
-    v = (int)floorf(vf + 0.5f);
-    return true;
-}
+constexpr int VT = VERIFY_VT, TW = VERIFY_TW, TH = VERIFY_TH, TILE = VERIFY_TILE;
+constexpr unsigned EMPTY = VERIFY_EMPTY;
 
 __global__ void k_verify_init(VerifyRec* rec, int n_poses) {
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
@@ -83,7 +43,7 @@ __global__ __launch_bounds__(256) void k_verify_bounds(const float* __restrict__
     int cnt = 0, u0 = INT_MAX, v0 = INT_MAX, u1 = -1, v1 = -1;
     for (int i = chunk * 256 + (int)threadIdx.x; i < n; i += chunks * 256) {
         int u, v; float zc;
-        if (!verify_project(P, c, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], u, v, zc)) continue;
+        if (!verify_project<1>(P, c, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], u, v, zc)) continue;
         ++cnt;
         const int a0 = max(u - c.splat, 0), a1 = min(u + c.splat, c.w - 1), b0 = max(v - c.splat, 0), b1 = min(v + c.splat, c.h - 1);
         if (a0 > a1 || b0 > b1) continue;                    // the square reaches nothing inside the frame
@@ -134,99 +94,44 @@ __global__ __launch_bounds__(VT, 8) void k_verify_tiles(const float* __restrict_
     const int tid = threadIdx.x;
     const int total = off[n_poses];
     for (int t = blockIdx.x; t < total; t += gridDim.x) {
-        int lo = 0, hi = n_poses;                            // off[lo] <= t < off[hi]
-        while (hi - lo > 1) {
-            const int mid = (lo + hi) >> 1;
-            if (off[mid] <= t) lo = mid; else hi = mid;
-        }
-        const int pose = __builtin_amdgcn_readfirstlane(lo);
-        const int bu0 = rec[pose].u0, bu1 = rec[pose].u1, bv0 = rec[pose].v0;
-        const int tiles_x = bu1 / TW - bu0 / TW + 1, k = t - off[pose];
-        const int x0 = (bu0 / TW + k % tiles_x) * TW, y0 = (bv0 / TH + k / tiles_x) * TH;
-        const int xe = min(x0 + TW, c.w) - 1, ye = min(y0 + TH, c.h) - 1;      // the tile inside the frame: [x0, xe] x [y0, ye]
+        int x0, y0, xe, ye;                                  // the tile inside the frame: [x0, xe] x [y0, ye]
+        const int pose = verify_tile_of(off, n_poses, rec, c, t, x0, y0, xe, ye);
         for (int i = tid; i < TILE / 4; i += VT) reinterpret_cast<uint4*>(tile)[i] = make_uint4(EMPTY, EMPTY, EMPTY, EMPTY);
         __syncthreads();
         const Pose16 P = load_pose(poses, pose);
         for (int i = tid; i < n; i += VT) {
             int u, v; float zc;
-            if (!verify_project(P, c, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], u, v, zc)) continue;
+            if (!verify_project<1>(P, c, xyz[3 * (size_t)i], xyz[3 * (size_t)i + 1], xyz[3 * (size_t)i + 2], u, v, zc)) continue;
             const int a0 = max(u - c.splat, x0), a1 = min(u + c.splat, xe), b0 = max(v - c.splat, y0), b1 = min(v + c.splat, ye);
             const unsigned bits = __float_as_uint(zc);
             for (int y = b0; y <= b1; ++y)
                 for (int x = a0; x <= a1; ++x) atomicMin(&tile[(y - y0) * TW + (x - x0)], bits);
         }
         __syncthreads();
-        int n0 = 0, n1 = 0, n2 = 0, n3 = 0;
-        unsigned long long err = 0;
-        for (int i = tid; i < TILE; i += VT) {
-            const unsigned b = tile[i];
-            const int x = x0 + (i & (TW - 1)), y = y0 + i / TW;
-            if (RENDER) {
-                if (x <= xe && y <= ye) out[(size_t)y * c.w + x] = b == EMPTY ? 0.f : __uint_as_float(b);
-                n0 += b != EMPTY;
-                continue;
-            }
-            if (b == EMPTY) continue;                        // (never set outside the frame)
-            const unsigned r = raw[(size_t)y * c.w + x];
-            const float zr = __uint_as_float(b), zo = (float)r * c.inv_scale;
-            if (!(r != 0 && zo <= c.zmax)) { ++n3; continue; }
-            const float diff = zo - zr;
-            if (fabsf(diff) <= c.tau) {
-                const float q = fabsf(diff) * 1048576.0f;
-                err += q >= 4294967296.0f ? 0xFFFFFFFFu : (unsigned)q;
-                ++n0;
-            } else if (diff < -c.tau) ++n1;
-            else ++n2;
-        }
-        // per lane at most 16 pixels: err < 2^36.  Its low 20 bits and the rest sum over the wave without leaving 32 bits.
-        n0 = wave_sum_i32(n0);
-        if (!RENDER) {
-            n1 = wave_sum_i32(n1); n2 = wave_sum_i32(n2); n3 = wave_sum_i32(n3);
-            const unsigned elo = (unsigned)wave_sum_i32((int)(err & 0xFFFFFu)), ehi = (unsigned)wave_sum_i32((int)(err >> 20));
-            err = (unsigned long long)elo + ((unsigned long long)ehi << 20);
-        }
-        if ((tid & 63) == 0) {
-            if (n0) atomicAdd(&rec[pose].cls[0], n0);
-            if (n1) atomicAdd(&rec[pose].cls[1], n1);
-            if (n2) atomicAdd(&rec[pose].cls[2], n2);
-            if (n3) atomicAdd(&rec[pose].cls[3], n3);
-            if (err) atomicAdd(&rec[pose].err, err);
-        }
+        verify_tile_tail<RENDER>(tile, x0, y0, xe, ye, c, raw, rec, pose, out);
         __syncthreads();                                     // the next tile's clear
     }
 }
 
 bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
 
-// the records of every pose on the device, everything enqueued: init, bounds, plan, tiles.  pin: poses up at [0], records down at *down.
+// the records of every pose on the device, everything enqueued: init, bounds, plan, tiles, the records down
 int verify_enqueue(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, float* d_out,
-                   const VerifyCam& cam, VerifyRec** rec_out, char** down) {
+                   const VerifyCam& cam, VerifyStage* st) {
     hipStream_t s = ctx->stream;
-    const size_t up_bytes = align_up((size_t)n_poses * 16 * sizeof(float), 256), down_bytes = (size_t)n_poses * sizeof(VerifyRec);
-    TDV_TRY(pin_reserve(ctx, up_bytes + down_bytes));
-    std::memcpy(ctx->pin, h_poses, (size_t)n_poses * 16 * sizeof(float));
-    float* d_poses; VerifyRec* rec; int* off;
-    TDV_TRY(ws_alloc(ctx, (size_t)n_poses * 16, &d_poses));
-    TDV_TRY(ws_alloc(ctx, (size_t)n_poses, &rec));
-    TDV_TRY(ws_alloc(ctx, (size_t)n_poses + 1, &off));
-    TDV_HIP(ctx, hipMemcpyAsync(d_poses, ctx->pin, (size_t)n_poses * 16 * sizeof(float), hipMemcpyHostToDevice, s));
-    k_verify_init<<<(n_poses + 255) / 256, 256, 0, s>>>(rec, n_poses);
+    TDV_TRY(verify_stage(ctx, h_poses, n_poses, st));
     const long long frame_tiles = (long long)((cam.w + TW - 1) / TW) * ((cam.h + TH - 1) / TH);
     if (n_model > 0) {
         const int chunks = std::max(1, std::min(64, (n_model + 2047) / 2048));
-        k_verify_bounds<<<n_poses * chunks, 256, 0, s>>>(d_model, n_model, d_poses, chunks, cam, rec);
+        k_verify_bounds<<<n_poses * chunks, 256, 0, s>>>(d_model, n_model, st->d_poses, chunks, cam, st->rec);
     }
     if (n_model > 0 && frame_tiles > 0) {
-        k_verify_plan<<<1, 1024, 0, s>>>(rec, n_poses, off);
+        verify_plan(ctx, *st, n_poses);
         const int grid = (int)std::min<long long>(VERIFY_GRID, frame_tiles * n_poses);
-        if (d_out) k_verify_tiles<true><<<grid, VT, 0, s>>>(d_model, n_model, d_poses, n_poses, off, cam, d_raw, rec, d_out);
-        else k_verify_tiles<false><<<grid, VT, 0, s>>>(d_model, n_model, d_poses, n_poses, off, cam, d_raw, rec, d_out);
+        if (d_out) k_verify_tiles<true><<<grid, VT, 0, s>>>(d_model, n_model, st->d_poses, n_poses, st->off, cam, d_raw, st->rec, d_out);
+        else k_verify_tiles<false><<<grid, VT, 0, s>>>(d_model, n_model, st->d_poses, n_poses, st->off, cam, d_raw, st->rec, d_out);
     }
-    TDV_CHECK_LAUNCH(ctx);
-    *down = ctx->pin + up_bytes;
-    TDV_HIP(ctx, hipMemcpyAsync(*down, rec, down_bytes, hipMemcpyDeviceToHost, s));
-    *rec_out = rec;
-    return TDV_OK;
+    return verify_fetch(ctx, *st, n_poses);
 }
 
 VerifyCam verify_cam(int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& p) {
@@ -235,23 +140,30 @@ VerifyCam verify_cam(int w, int h, float scale, float fx, float fy, float cx, fl
 
 }  // namespace
 
-// every argument, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth output
-bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
-                    float scale, float fx, float fy, const tdv_verify_params* p, const void* results) {
-    if (!ctx || !p || n_model < 0 || n_model > TDV_VERIFY_MAX_MODEL || n_poses < 0 || n_poses > TDV_VERIFY_MAX_POSES) return false;
-    if (w < 0 || w > TDV_VERIFY_MAX_SIDE || h < 0 || h > TDV_VERIFY_MAX_SIDE) return false;
-    if ((n_model > 0 && !model) || (n_poses > 0 && (!poses || !results)) || ((size_t)w * h > 0 && !frame)) return false;
-    if (p->splat < 0 || p->splat > TDV_VERIFY_MAX_SPLAT || !positive_finite(p->tau)) return false;
-    if (p->pose_direction != TDV_POSE_SOURCE_ONTO_TARGET && p->pose_direction != TDV_POSE_MODEL_TO_CAMERA) return false;
-    return positive_finite(scale) && positive_finite(fx) && positive_finite(fy);
+// ---- what verify_mesh.hip shares (verify_common.hpp)
+int verify_stage(tdv_ctx* ctx, const float* h_poses, int n_poses, VerifyStage* st) {
+    hipStream_t s = ctx->stream;
+    const size_t up_bytes = align_up((size_t)n_poses * 16 * sizeof(float), 256), down_bytes = (size_t)n_poses * sizeof(VerifyRec);
+    TDV_TRY(pin_reserve(ctx, up_bytes + down_bytes));
+    std::memcpy(ctx->pin, h_poses, (size_t)n_poses * 16 * sizeof(float));
+    TDV_TRY(ws_alloc(ctx, (size_t)n_poses * 16, &st->d_poses));
+    TDV_TRY(ws_alloc(ctx, (size_t)n_poses, &st->rec));
+    TDV_TRY(ws_alloc(ctx, (size_t)n_poses + 1, &st->off));
+    TDV_HIP(ctx, hipMemcpyAsync(st->d_poses, ctx->pin, (size_t)n_poses * 16 * sizeof(float), hipMemcpyHostToDevice, s));
+    k_verify_init<<<(n_poses + 255) / 256, 256, 0, s>>>(st->rec, n_poses);
+    st->down = ctx->pin + up_bytes;
+    return TDV_OK;
 }
 
-int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, int w, int h,
-                   float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& prm, tdv_verify_result* results, int* order) {
-    if (n_poses == 0) return TDV_OK;
-    VerifyRec* rec; char* down;
-    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_poses, n_poses, d_raw, nullptr, verify_cam(w, h, scale, fx, fy, cx, cy, prm), &rec, &down));
-    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+void verify_plan(tdv_ctx* ctx, const VerifyStage& st, int n_poses) { k_verify_plan<<<1, 1024, 0, ctx->stream>>>(st.rec, n_poses, st.off); }
+
+int verify_fetch(tdv_ctx* ctx, const VerifyStage& st, int n_poses) {
+    TDV_CHECK_LAUNCH(ctx);
+    TDV_HIP(ctx, hipMemcpyAsync(st.down, st.rec, (size_t)n_poses * sizeof(VerifyRec), hipMemcpyDeviceToHost, ctx->stream));
+    return TDV_OK;
+}
+
+void verify_results(const char* down, int n_poses, tdv_verify_result* results, int* order) {
     for (int p = 0; p < n_poses; ++p) {
         VerifyRec r;
         std::memcpy(&r, down + (size_t)p * sizeof(VerifyRec), sizeof(r));
@@ -267,6 +179,33 @@ int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float*
             return results[a].n_consistent - results[a].n_violating > results[b].n_consistent - results[b].n_violating;
         });
     }
+}
+
+bool verify_common_args_ok(const tdv_ctx* ctx, const float* poses, int n_poses, const void* frame, int w, int h, float scale, float fx, float fy,
+                           float tau, int pose_direction, const void* results) {
+    if (!ctx || n_poses < 0 || n_poses > TDV_VERIFY_MAX_POSES) return false;
+    if (w < 0 || w > TDV_VERIFY_MAX_SIDE || h < 0 || h > TDV_VERIFY_MAX_SIDE) return false;
+    if ((n_poses > 0 && (!poses || !results)) || ((size_t)w * h > 0 && !frame)) return false;
+    if (!positive_finite(tau)) return false;
+    if (pose_direction != TDV_POSE_SOURCE_ONTO_TARGET && pose_direction != TDV_POSE_MODEL_TO_CAMERA) return false;
+    return positive_finite(scale) && positive_finite(fx) && positive_finite(fy);
+}
+
+// every argument, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth output
+bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
+                    float scale, float fx, float fy, const tdv_verify_params* p, const void* results) {
+    if (!p || n_model < 0 || n_model > TDV_VERIFY_MAX_MODEL || (n_model > 0 && !model)) return false;
+    if (p->splat < 0 || p->splat > TDV_VERIFY_MAX_SPLAT) return false;
+    return verify_common_args_ok(ctx, poses, n_poses, frame, w, h, scale, fx, fy, p->tau, p->pose_direction, results);
+}
+
+int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, int w, int h,
+                   float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& prm, tdv_verify_result* results, int* order) {
+    if (n_poses == 0) return TDV_OK;
+    VerifyStage st;
+    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_poses, n_poses, d_raw, nullptr, verify_cam(w, h, scale, fx, fy, cx, cy, prm), &st));
+    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    verify_results(st.down, n_poses, results, order);
     return TDV_OK;
 }
 
@@ -274,11 +213,11 @@ int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const 
                          const tdv_verify_params& prm, float* d_out, int* n_rendered) {
     const size_t px = (size_t)w * h;
     if (px > 0) TDV_HIP(ctx, hipMemsetAsync(d_out, 0, px * sizeof(float), ctx->stream));    // the pixels outside the pose's tiles
-    VerifyRec* rec; char* down;
-    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_pose, 1, nullptr, d_out, verify_cam(w, h, 1.f, fx, fy, cx, cy, prm), &rec, &down));
+    VerifyStage st;
+    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_pose, 1, nullptr, d_out, verify_cam(w, h, 1.f, fx, fy, cx, cy, prm), &st));
     TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     VerifyRec r;
-    std::memcpy(&r, down, sizeof(r));
+    std::memcpy(&r, st.down, sizeof(r));
     if (n_rendered) *n_rendered = r.cls[0];
     return TDV_OK;
 }

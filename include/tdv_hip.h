@@ -878,8 +878,8 @@ int tdv_ctx_last_fps_path(tdv_ctx* ctx);
  * (n_model > 0), frame or depth output (width * height > 0); n_model < 0 or > TDV_VERIFY_MAX_MODEL; n_poses < 0 or > TDV_VERIFY_MAX_POSES;
  * width or height < 0 or > TDV_VERIFY_MAX_SIDE; splat outside [0, TDV_VERIFY_MAX_SPLAT]; tau <= 0 or non-finite; scale, fx or fy <= 0 or
  * non-finite; an unknown pose_direction.  n_poses == 0 and n_model == 0 are valid and give zeros.  The ctx's switches do not apply.  Not
- * provided: mesh rasterisation, per-instance masks, a splat chosen from the model's resolution, verification inside
- * tdv_register_batch_dev, the C++ operator mirror. */
+ * provided: per-instance masks, a splat chosen from the model's resolution, verification inside tdv_register_batch_dev, the C++
+ * operator mirror.  A model that has faces is drawn by tdv_verify_poses_mesh, below. */
 #define TDV_POSE_SOURCE_ONTO_TARGET 0
 #define TDV_POSE_MODEL_TO_CAMERA 1
 #define TDV_VERIFY_MAX_SPLAT 3
@@ -917,6 +917,78 @@ int tdv_render_depth_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, co
                          int* n_rendered /* optional, host */);
 int tdv_render_depth(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* pose, int width, int height, float fx, float fy, float cx,
                      float cy, const tdv_verify_params* params, float* out_depth, int* n_rendered /* optional */);
+/* Pose verification from a triangle mesh: the second renderer beside the splat.  The same poses, frame, classification, result struct and
+ * one read-back; the model is an indexed triangle mesh (vertices n_vertices x 3 floats, triangles n_triangles x 3 ints) and its faces are
+ * rasterised: an exact silhouette (no rim of splat pixels), a depth interpolated over each face, and with TDV_MESH_CULL_BACK only the faces
+ * that look at the camera.  Every output is an integer or is fixed bit for bit: f32 and f64 as named, one rounding per operation, no
+ * contraction, the order exactly as written; the integers are exact.
+ *  M1. Vertex: camera coordinates, the usable test and uf, vf are rules 1 to 3 above (usable: xc, yc, zc finite, 0 < zc <= zmax, and
+ *      |uf|, |vf| < 2^20).  The snapped position is X = (int64)floorf(uf * 16.0f + 0.5f), Y likewise from vf (TDV_MESH_SUBPIXEL = 16:
+ *      multiples of 1/16 pixel).  Pixel (x, y) has its centre at (16 x, 16 y): the convention of rule 3's floorf(uf + 0.5f) and of
+ *      tdv_deproject.
+ *  M2. Triangle (a, b, c).  It is unusable if an index lies outside [0, n_vertices) - tested on the device before anything is read, so a
+ *      bad index reads no memory - or if one of its vertices is unusable.  There is NO near-plane clipping: a triangle with a vertex behind
+ *      the camera or beyond zmax is dropped whole.  A = (Xb - Xa) * (Yc - Ya) - (Yb - Ya) * (Xc - Xa) in int64 (exact: every factor is
+ *      below 2^26).  A == 0: unusable.  A > 0 means the normal (vb - va) x (vc - va) points away from the camera (image y grows
+ *      downwards): under TDV_MESH_CULL_BACK such a triangle is unusable.  A triangle with A < 0 - one that looks at the camera - has b and c
+ *      swapped and A negated, so every usable triangle goes on with A > 0.  (The rule as first drafted swapped the triangles with A > 0 instead,
+ *      which leaves every A negative and rule M4's "E > 0 inside" without a covered pixel; the swap is stated here as M4 needs it, and
+ *      nothing else changed.)
+ *  M3. n_projected is the number of usable triangles, whether or not they cover a pixel of the frame.
+ *  M4. Coverage.  After M2 each directed edge i -> j has E(P) = (Xj - Xi) * (Py - Yi) - (Yj - Yi) * (Px - Xi) at the pixel centre P, in
+ *      int64; w0 = E_bc, w1 = E_ca, w2 = E_ab, and w0 + w1 + w2 = A.  The pixel is covered iff for every edge E > 0, or E == 0 and the edge
+ *      owns its boundary.  An edge owns its boundary when Yj - Yi < 0, or Yj - Yi == 0 and Xj - Xi > 0 (with A > 0 and y downwards these
+ *      are the left edges and the horizontal top edge: the top-left rule).  Two usable triangles of one facing that share an edge walk it in
+ *      opposite directions, so a centre on it belongs to exactly one of them.
+ *  M5. Depth of a covered pixel, perspective-correct in f64: iz_i = 1.0 / (double)zc_i for the vertices after M2's swap;
+ *      s = ((double)w0 * iz_a + (double)w1 * iz_b) + (double)w2 * iz_c; zr = (float)((double)A / s).  zr lies within the vertices' depths:
+ *      positive, finite and <= zmax.
+ *  M6. Rendered depth of a pixel: the minimum zr over the triangles that cover it, taken over the u32 bits as in rule 4.  Only pixels of
+ *      the frame are rendered; a triangle partly or wholly outside the frame covers what it covers inside.
+ *  M7. Rules 5 to 7 and the classes are those above, unchanged (one implementation: csrc/verify_common.hpp).
+ * tdv_verify_result is reused: n_projected counts the usable triangles (M3), every other field keeps its meaning, and for every pose
+ * n_rendered == n_consistent + n_occluded + n_violating + n_unknown.  h_order is the splat's (same code).  A vertex of NaNs or infinities
+ * takes its triangles out through the usable test, a pose of NaNs gives a result of zeros.  Vertices no triangle names are never read.
+ * The result is defined over the whole frame.  The kernels (csrc/verify_mesh.hip) cut each pose's pixel box into the splat's tiles; in a
+ * tile a lane rasterises a triangle itself when the triangle's pixel box inside the tile holds at most TDV_MESH_COOP_PIXELS pixels, larger
+ * ones go through a queue of TDV_MESH_QUEUE setup records in LDS that the workgroup drains together, one pixel per lane.  Neither constant
+ * shows in a result; they are exported so that tests can stand on their edges.
+ * tdv_verify_poses_mesh_dev takes vertices, triangles and the raw frame as device pointers, poses and results on the host, and reads back
+ * once; tdv_verify_poses_mesh takes host arrays throughout.  tdv_render_depth_mesh_dev writes the rendered depth of one pose as f32 (0 where
+ * nothing rendered) and the number of rendered pixels; of params it uses pose_direction, cull and zmax (tau is checked all the same).
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params, poses (n_poses > 0), results (n_poses > 0), vertices
+ * (n_vertices > 0), triangles (n_triangles > 0), frame or depth output (width * height > 0); n_vertices < 0 or > TDV_MESH_MAX_VERTICES;
+ * n_triangles < 0 or > TDV_MESH_MAX_TRIANGLES; n_poses, width, height outside the splat's limits; an unknown cull or pose_direction; tau,
+ * scale, fx or fy <= 0 or non-finite.  n_triangles == 0, n_vertices == 0 and n_poses == 0 are valid and give zeros.  Not provided: mesh
+ * file loaders, near-plane clipping, per-instance masks, verification inside tdv_register_batch_dev, the C++ operator mirror. */
+#define TDV_MESH_CULL_NONE 0
+#define TDV_MESH_CULL_BACK 1
+#define TDV_MESH_MAX_VERTICES (1 << 22)
+#define TDV_MESH_MAX_TRIANGLES (1 << 22)
+#define TDV_MESH_SUBPIXEL 16      /* snapped positions are multiples of 1/16 pixel */
+#define TDV_MESH_COOP_PIXELS 64   /* a pixel box inside a tile of more pixels than this is rasterised by the workgroup together */
+#define TDV_MESH_QUEUE 128        /* setup records of 64 bytes in LDS: 8 KiB beside the 64 KiB tile (csrc/verify_mesh.hip) */
+typedef struct tdv_mesh_verify_params {
+    int   pose_direction;  /* TDV_POSE_SOURCE_ONTO_TARGET (default) or TDV_POSE_MODEL_TO_CAMERA */
+    int   cull;            /* TDV_MESH_CULL_NONE (default) or TDV_MESH_CULL_BACK (rule M2) */
+    float tau;             /* depth agreement band in metres, > 0; default 0.002 */
+    float zmax;            /* observed and rendered depths beyond it do not count; default 10 */
+} tdv_mesh_verify_params;
+void tdv_mesh_verify_default_params(tdv_mesh_verify_params* params);
+int tdv_verify_poses_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles,
+                              const float* h_poses /* host, n_poses x 16 */, int n_poses, const uint16_t* d_raw_depth /* u16, width x height */,
+                              int width, int height, float scale, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params,
+                              tdv_verify_result* h_results /* host, [n_poses] */, int* h_order /* optional, host, [n_poses] */);
+int tdv_verify_poses_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* poses,
+                          int n_poses, const uint16_t* raw_depth, int width, int height, float scale, float fx, float fy, float cx, float cy,
+                          const tdv_mesh_verify_params* params, tdv_verify_result* results, int* order /* optional */);
+int tdv_render_depth_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles,
+                              const float* h_pose /* host, 16 */, int width, int height, float fx, float fy, float cx, float cy,
+                              const tdv_mesh_verify_params* params, float* d_out_depth /* f32, width x height */,
+                              int* n_rendered /* optional, host */);
+int tdv_render_depth_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* pose, int width,
+                          int height, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params, float* out_depth,
+                          int* n_rendered /* optional */);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
