@@ -65,7 +65,7 @@ ABI_SYMBOLS = [
     "tdv_ppf_default_params", "tdv_ppf_model_bytes", "tdv_ppf_model_dev", "tdv_ppf_match_dev", "tdv_ppf_match",
     "tdv_ppf_match_batch_dev",
     "tdv_farthest_point_down_sample", "tdv_farthest_point_down_sample_dev", "tdv_farthest_point_down_sample_batch_dev",
-    "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path",
+    "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path", "tdv_ctx_set_icp_launches", "tdv_ctx_last_icp_launches",
     "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
     "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
 ]
@@ -575,6 +575,17 @@ class Context:
         """Name of the search the last ICP / correspondence call ran ('brute', 'pruned', 'grid'; 'auto' before any)."""
         v = lib().tdv_ctx_last_icp_search(self._h)
         return {n: k for k, n in self.ICP_SEARCH.items()}[v]
+
+    ICP_LAUNCHES = {"auto": 0, "two": 1, "one": 2}
+
+    def set_icp_launches(self, mode):
+        """'auto' (default: one launch per iteration where it measured faster), 'two' (search, then accumulation) or 'one' (both in one
+        kernel, where the path has it: hash grid, tree sums, point-to-plane or point-to-point); same bytes (tests and measurements)."""
+        _check(self._h, lib().tdv_ctx_set_icp_launches(self._h, self.ICP_LAUNCHES[mode]), "tdv_ctx_set_icp_launches")
+
+    def last_icp_launches(self):
+        """'one' if the last ICP call on this context ran the one-launch iteration, else 'two' ('auto' before any)."""
+        return {v: k for k, v in self.ICP_LAUNCHES.items()}[int(lib().tdv_ctx_last_icp_launches(self._h))]
 
     def set_fps_path(self, mode):
         """'auto' (default: the workgroup kernels up to TDV_FPS_WORKGROUP_MAX rows, the grid kernels above), 'workgroup' or 'grid': the

@@ -48,6 +48,16 @@ void reset_result(tdv_instance_result& r) {
     for (int i = 0; i < 16; ++i) r.T[i] = (i % 5 == 0) ? 1.f : 0.f;
 }
 
+// An instance's ICP on a lane of the batch keeps two launches per iteration whatever the ctx says: the other lanes' kernels run beside
+// it, and the one-launch iteration (icp.hip: k_icp_iterate) was measured faster only with the device to itself, one workgroup per CU.
+// With it in the lanes, C4's 256 instances of ~148k voxels (those from 150,000 up took it) ran at 707-709 instances/s against 712-716
+// (profiles/r19/icp_one_launch.md).
+struct TwoLaunchIcp {
+    tdv_ctx* c; int saved;
+    explicit TwoLaunchIcp(tdv_ctx* c_) : c(c_), saved(c_->icp_launches) { c->icp_launches = TDV_ICP_LAUNCHES_TWO; }
+    ~TwoLaunchIcp() { c->icp_launches = saved; }
+};
+
 // the ICP stage's outcome: the refined pose and its figures, and the instance done (status 0)
 void set_icp_result(tdv_instance_result& r, const tdv_icp_result& fine) {
     std::memcpy(r.T, fine.T, 64);
@@ -255,6 +265,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
                                prm->ransac_confidence, prm->seed, &coarse, nullptr));
         r.coarse_fitness = coarse.fitness; r.coarse_inliers = coarse.inliers;
         tdv_icp_result fine;
+        const TwoLaunchIcp two(c);
         TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, IcpObjective::plain(prm->point_to_plane), 0, &fine,
                             have_sorted ? &model_sorted : nullptr, have_grid ? &model_grid : nullptr));
         set_icp_result(r, fine);
@@ -425,6 +436,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         r.coarse_fitness = coarse.fitness; r.coarse_inliers = coarse.inliers;
         if (batched_icp) { std::memcpy(&coarse_T[(size_t)b * 16], coarse.T, 64); ws_rewind(c, mark); return TDV_OK; }
         tdv_icp_result fine;
+        const TwoLaunchIcp two(c);
         TDV_TRY(icp_run_dev(c, vx, v, d_model_xyz, d_model_normals, n_model, coarse.T, icp_thr, prm->icp_max_iterations, IcpObjective::plain(prm->point_to_plane), 0, &fine,
                             have_sorted ? &model_sorted : nullptr, have_grid ? &model_grid : nullptr));
         set_icp_result(r, fine);

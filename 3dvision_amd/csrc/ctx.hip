@@ -283,6 +283,13 @@ int tdv_ctx_set_icp_accumulation(tdv_ctx* ctx, int mode) {
     return TDV_OK;
 }
 
+int tdv_ctx_set_icp_launches(tdv_ctx* ctx, int mode) {
+    if (!ctx || mode < TDV_ICP_LAUNCHES_AUTO || mode > TDV_ICP_LAUNCHES_ONE) return TDV_ERR_BAD_ARG;
+    ctx->icp_launches = mode;
+    return TDV_OK;
+}
+int tdv_ctx_last_icp_launches(tdv_ctx* ctx) { return ctx ? ctx->last_icp_launches : TDV_ERR_BAD_ARG; }
+
 int tdv_ctx_set_icp_loss(tdv_ctx* ctx, int loss, float scale) {
     if (!ctx || loss < TDV_ICP_LOSS_L2 || loss > TDV_ICP_LOSS_CAUCHY) return TDV_ERR_BAD_ARG;
     if (loss != TDV_ICP_LOSS_L2 && !(std::isfinite(scale) && scale > 0.f)) return TDV_ERR_BAD_ARG;

@@ -23,6 +23,9 @@
 //    The block that finishes last (atomic ticket) folds the slabs in fixed order, one lane solves the 6x6 system
 //    (pivoted LDL^T) or the 3x3 Kabsch SVD, updates T on the device and evaluates convergence: two launches per
 //    iteration.
+//  * icp_iterate (hash grid, tree sums, point-to-plane or point-to-point, 150,000 to 262,144 sources): search and sums in ONE launch
+//    per iteration - the search keeps its shape, one lane per source point; the lanes hand float records over in LDS and the sixteen
+//    waves of the workgroup form the slab from them in icp_accumulate's f64 tree, bit for bit.
 //  * icp_nn_pruned (large clouds, same correspondences bit for bit): the target is put in Morton order once per
 //    call; ONE WAVE PER SOURCE POINT tests the target's 4096- and 64-point bounding boxes one per lane, visits them
 //    best-first, and evaluates the points of the boxes that can hold a neighbour within the bound one per lane
@@ -304,7 +307,8 @@ void k_grid_insert(const float* __restrict__ tgt, int nt, float inv_cell, GridEn
 
 // the search of one query point p: lowest (d2, original index) among the targets with d2 <= tau, (INFINITY, INT_MAX) if none
 __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table, const float4* __restrict__ node, unsigned mask, int shift,
-                                             float inv_cell, float px, float py, float pz, float tau, float& bd, int& bo) {
+                                             float inv_cell, float px, float py, float pz, float tau, float& bd, int& bo,
+                                             float* bq = nullptr /* 3: the winner's coordinates as node[] holds them, k_grid_insert's copy of the target's */) {
     const float gx = px * inv_cell, gy = py * inv_cell, gz = pz * inv_cell;
     const float kx = floorf(gx), ky = floorf(gy), kz = floorf(gz);
     const int cx = (int)kx, cy = (int)ky, cz = (int)kz;
@@ -348,7 +352,10 @@ __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table
     auto take = [&](const float4 t, int idx, bool live) {
         const float ex = px - t.x, ey = py - t.y, ez = pz - t.z;
         const float d2 = ex * ex + (ey * ey + ez * ez);    // the scan's expression
-        if (live && d2 <= tau && (d2 < bd || (d2 == bd && idx < bo))) { bd = d2; bo = idx; }
+        if (live && d2 <= tau && (d2 < bd || (d2 == bd && idx < bo))) {
+            bd = d2; bo = idx;
+            if (bq) { bq[0] = t.x; bq[1] = t.y; bq[2] = t.z; }
+        }
     };
     // the cells' lists (cells hold one or two points): the eight lists advance TOGETHER, one round trip per step of the longest
     // list among a wave's 512 cells instead of a sum over the cells.  Again eight unconditional loads back to back (`if (nx[c]
@@ -374,8 +381,9 @@ __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table
 }
 
 // One lane per source point.  (Running this search inside k_icp_accumulate - one launch per iteration, no correspondence
-// arrays in between - was measured slower, 110 us against 44 + 35 at 200k x 200k: that kernel's 29 double accumulators
-// leave too few waves per SIMD to hide the probes' latency.)
+// arrays in between - was measured slower twice, 110 us against 44 + 35 and later 56.5 against 49.6 at 200k x 200k: that kernel's 29
+// double accumulators and four points in flight leave one wave per SIMD to hide the probes' latency.  k_icp_iterate below fuses the
+// other way round: this kernel's shape and registers for the search, the sums formed afterwards from records in LDS.)
 __global__ __launch_bounds__(256)
 void k_icp_nn_grid(const float* __restrict__ src, int ns, const GridEntry* __restrict__ table, const float4* __restrict__ node,
                    unsigned mask, int shift, float inv_cell, const IcpState* __restrict__ st, float tau,
@@ -572,6 +580,58 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
     if (MODE == 0) corr_jr(px, py, pz, G, J, r);
 }
 
+// The float record of one correspondence at squared distance d2, ref_record's fields: point-to-plane {d2, J0 .. J5, r}, point-to-point
+// {d2, px, py, pz, qx, qy, qz, -}.  Everything the tree sums of MODE 0 and 1 need of a correspondence: k_icp_accumulate forms it in
+// registers, k_icp_iterate hands it from the lane that searched to the lanes that sum through LDS.
+constexpr int REC_WORDS = 8;
+struct CorrRec { float f[REC_WORDS]; };
+template <int MODE>
+__device__ __forceinline__ void corr_rec(float px, float py, float pz, float d2, const CorrTgt& G, CorrRec& R) {
+    static_assert(MODE == 0 || MODE == 1, "records exist for point-to-plane and point-to-point");
+    R.f[0] = d2;
+    if (MODE == 0) corr_jr(px, py, pz, G, R.f + 1, R.f[7]);
+    else { R.f[1] = px; R.f[2] = py; R.f[3] = pz; R.f[4] = G.q[0]; R.f[5] = G.q[1]; R.f[6] = G.q[2]; R.f[7] = 0.f; }
+}
+
+// The tree sums' terms of MODE 0 and 1 (acc_terms_add below states them) from the record of an accepted correspondence: the one
+// place their formulas stand.  A caller that wants a subset of the terms ignores the others in put (k is a constant after unrolling:
+// the products nobody takes are not formed).
+template <int MODE, bool ROBUST, class Put>
+__device__ __forceinline__ void rec_terms(const CorrRec& R, IcpLoss L, Put put) {
+    static_assert(MODE == 0 || MODE == 1, "records exist for point-to-plane and point-to-point");
+    const float d2 = R.f[0];
+    put(0, 1.0); put(1, (double)d2);
+    float w = 1.f;
+    if (ROBUST) w = loss_weight(L, MODE == 0 ? R.f[7] : sqrtf(d2));
+    const double wd = w;
+    if (MODE == 0) {
+        const float* J = R.f + 1;
+        const float r = R.f[7];
+        int k = 2;
+#pragma unroll
+        for (int a = 0; a < 6; ++a)
+#pragma unroll
+            for (int b = a; b < 6; ++b) put(k++, ROBUST ? wd * (double)(J[a] * J[b]) : (double)(J[a] * J[b]));
+#pragma unroll
+        for (int a = 0; a < 6; ++a) put(k++, ROBUST ? wd * (double)(J[a] * r) : (double)(J[a] * r));
+        if (ROBUST) put(29, w > 0.f ? 1.0 : 0.0);
+    } else {
+        const double P[3] = {R.f[1], R.f[2], R.f[3]}, Q[3] = {R.f[4], R.f[5], R.f[6]};
+        if (ROBUST) {
+            put(2, wd * P[0]); put(3, wd * P[1]); put(4, wd * P[2]);
+            put(5, wd * Q[0]); put(6, wd * Q[1]); put(7, wd * Q[2]);
+        } else {
+            put(2, P[0]); put(3, P[1]); put(4, P[2]);
+            put(5, Q[0]); put(6, Q[1]); put(7, Q[2]);
+        }
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) put(8 + a * 3 + b, ROBUST ? wd * (P[a] * Q[b]) : P[a] * Q[b]);
+        if (ROBUST) { put(17, wd); put(18, w > 0.f ? 1.0 : 0.0); }
+    }
+}
+
 // the tree sums' terms of one accepted correspondence at squared distance d2, handed to put(k, term) for k = 0 .. acc_nv<MODE>() - 1:
 // {1, d2, then MODE 0 the 21 upper-triangular J[a] * J[b] and the 6 J[a] * r, each product formed in float and widened; MODE 1 p, q
 // and the 9 p[a] * q[b], p and q widened first}.  put is the caller's way of combining them (+= into a lane's sums, = into a fresh
@@ -588,6 +648,12 @@ __device__ __forceinline__ void corr_terms(float px, float py, float pz, int idx
 // This is the ADD half, from the target as corr_fetch<MODE> fetched it (G); acc_terms below fetches and adds.
 template <int MODE, bool ROBUST = false, class Put>
 __device__ __forceinline__ void acc_terms_add(float px, float py, float pz, float d2, const CorrTgt& G, IcpLoss L, CorrPt<MODE> X, Put put) {
+    if constexpr (MODE == 0 || MODE == 1) {     // through the record, as the one-launch iteration forms them (rec_terms)
+        CorrRec R;
+        corr_rec<MODE>(px, py, pz, d2, G, R);
+        rec_terms<MODE, ROBUST>(R, L, put);
+        return;
+    }
     put(0, 1.0); put(1, (double)d2);
     if (MODE == 2) return;
     if constexpr (MODE == 4) {
@@ -660,36 +726,6 @@ __device__ __forceinline__ void acc_terms_add(float px, float py, float pz, floa
         if (ROBUST) put(29, w > 0.f ? 1.0 : 0.0);
         return;
     }
-    float J[6], r;
-    const float* q = G.q;
-    if (MODE == 0) corr_jr(px, py, pz, G, J, r);
-    float w = 1.f;
-    if (ROBUST) w = loss_weight(L, MODE == 0 ? r : sqrtf(d2));
-    const double wd = w;
-    if (MODE == 0) {
-        int k = 2;
-#pragma unroll
-        for (int a = 0; a < 6; ++a)
-#pragma unroll
-            for (int b = a; b < 6; ++b) put(k++, ROBUST ? wd * (double)(J[a] * J[b]) : (double)(J[a] * J[b]));
-#pragma unroll
-        for (int a = 0; a < 6; ++a) put(k++, ROBUST ? wd * (double)(J[a] * r) : (double)(J[a] * r));
-        if (ROBUST) put(29, w > 0.f ? 1.0 : 0.0);
-    } else {
-        const double P[3] = {px, py, pz}, Q[3] = {q[0], q[1], q[2]};
-        if (ROBUST) {
-            put(2, wd * P[0]); put(3, wd * P[1]); put(4, wd * P[2]);
-            put(5, wd * Q[0]); put(6, wd * Q[1]); put(7, wd * Q[2]);
-        } else {
-            put(2, P[0]); put(3, P[1]); put(4, P[2]);
-            put(5, Q[0]); put(6, Q[1]); put(7, Q[2]);
-        }
-#pragma unroll
-        for (int a = 0; a < 3; ++a)
-#pragma unroll
-            for (int b = 0; b < 3; ++b) put(8 + a * 3 + b, ROBUST ? wd * (P[a] * Q[b]) : P[a] * Q[b]);
-        if (ROBUST) { put(17, wd); put(18, w > 0.f ? 1.0 : 0.0); }
-    }
 }
 
 template <int MODE, bool ROBUST = false, class Put>
@@ -716,21 +752,20 @@ struct AccShared {
 // Every block reduces its lanes' sums v[] to its slab slabs[slab] (fixed order: wave64 DPP -> LDS); the block that takes the last
 // of nblocks tickets folds slabs[0 .. nblocks) in a fixed order into sh.tot[] and returns true (all its threads) - the result
 // does not depend on which block that is.  The caller's thread 0 of that block then resets *ticket and updates the state.
-template <int MODE, bool ROBUST = false>
-__device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, int slab, int nblocks, unsigned* ticket, AccShared& sh) {
-    constexpr int NV = acc_nv<MODE, ROBUST>();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int k = 0; k < NV; ++k) {
-        const double s = wave_sum_lane63(v[k]);
-        if (lane == 63) sh.red[wave][k] = s;
-    }
+// The first half's end: the four wave sums sh.red[0 .. 3][k] (lane 63 of accumulate wave g wrote red[g][k]) combined into slabs[slab].
+template <int NV>
+__device__ __forceinline__ void acc_slab_store(double* slabs, int slab, AccShared& sh) {
     __syncthreads();
     if (threadIdx.x < ACC_NV) {
         double s = 0.0;
         if (threadIdx.x < NV) s = (sh.red[0][threadIdx.x] + sh.red[1][threadIdx.x]) + (sh.red[2][threadIdx.x] + sh.red[3][threadIdx.x]);
         slabs[(size_t)slab * ACC_NV + threadIdx.x] = s;
     }
+}
+
+// The second half: ticket and fold, by a workgroup of 256 threads or more whose wave 0 wrote its slab (acc_slab_store).  Threads past
+// the first 256 only join the barriers.
+__device__ __forceinline__ bool acc_ticket_fold(double* slabs, int nblocks, unsigned* ticket, AccShared& sh) {
     // ---- last block: fold ----------------------------------------------------------------------------------------------
     // Release by the wave that wrote the slab (wave 0; thread 0 then moves the ticket), acquire by the block that folds.
     // __threadfence() by every thread was a write-back AND an invalidate of the XCD's L2 (buffer_wbl2 + buffer_inv) from all
@@ -742,7 +777,7 @@ __device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, in
     if (!sh.is_last) return false;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     const int vv = threadIdx.x & 31, g = threadIdx.x >> 5;
-    {
+    if (threadIdx.x < 256) {
         // slabs were written by other blocks of this launch: the agent-scope fence above makes them visible to plain loads
         // sixteen slab rows per thread and round, all loads of a round in flight together (the fold is a chain of round trips:
         // 196 blocks at 200k points were 7 rounds of 4 loads, now 2 rounds of 16); fixed order, as before
@@ -762,6 +797,19 @@ __device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, in
         sh.tot[vv] = ((sh.red[0][vv] + sh.red[1][vv]) + (sh.red[2][vv] + sh.red[3][vv])) + ((sh.red[4][vv] + sh.red[5][vv]) + (sh.red[6][vv] + sh.red[7][vv]));
     __syncthreads();
     return true;
+}
+
+template <int MODE, bool ROBUST = false>
+__device__ __forceinline__ bool acc_slab_fold(const double* v, double* slabs, int slab, int nblocks, unsigned* ticket, AccShared& sh) {
+    constexpr int NV = acc_nv<MODE, ROBUST>();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+    for (int k = 0; k < NV; ++k) {
+        const double s = wave_sum_lane63(v[k]);
+        if (lane == 63) sh.red[wave][k] = s;
+    }
+    acc_slab_store<NV>(slabs, slab, sh);
+    return acc_ticket_fold(slabs, nblocks, ticket, sh);
 }
 
 // thread 0 of the folding block: solve, update, stopping rule from the folded sums (pose as acc_load_pose read it)
@@ -901,6 +949,100 @@ void k_icp_accumulate(const float* __restrict__ src, int ns, int ns_pad,
     }
     __shared__ AccShared sh;
     if (!acc_slab_fold<MODE, ROBUST>(v, slabs, blockIdx.x, gridDim.x, ticket, sh)) return;
+    if (threadIdx.x != 0) return;
+    *ticket = 0u;   // ready for the next launch (stream order)
+    acc_finish<MODE, ROBUST>(sh, ns, st, fixed_iterations, iter0, rmse0, T, Tb);
+}
+
+// ---- one launch per iteration: k_icp_nn_grid and k_icp_accumulate<MODE, 4> in one kernel (MODE 0 and 1) ----------------------------
+// The search keeps its shape - one lane per source point, nothing but the search in its registers - and the sums do not live in the
+// searching lanes: every lane leaves the float record of its correspondence (corr_rec) in LDS, and after one barrier the sixteen waves
+// form the slab from the records.  Workgroup blk is slab blk of k_icp_accumulate<MODE, 4>: 1,024 consecutive source points, thread t
+// searching point blk * 1024 + t, which is point q = t >> 8 of that kernel's lane L = t & 255.
+//   search   p = acc_transform (transform_point's expression: the bits both of today's kernels see), grid_nearest, which also hands back
+//            the winner's coordinates as node[] holds them (k_grid_insert's copy of the target's: no gather of tgt is left); the normal
+//            by the found index (index 0 when nothing was found, unconditionally, as acc_points); the record, d2 = FLT_MAX for a point
+//            past ns or without a neighbour (tau_accept < FLT_MAX on this path, so the test where the terms are added rejects it).
+//   sums     wave w takes accumulate wave g = w & 3 (lanes 64 g .. 64 g + 63 of L) and the terms [8 s, 8 s + 8) of s = w >> 2.  A lane reads
+//            its four records in q order and adds the accepted ones' terms (rec_terms: the products formed in float and widened, as
+//            k_icp_accumulate forms them from the same record) into f64 sums that start at 0.0; wave_sum_lane63; lane 63 stores
+//            sh.red[g][k]; acc_slab_store combines the four.  Per term that is k_icp_accumulate's tree, lane by lane: the same q
+//            order in a lane, the same DPP order over the same 64 lanes, the same four-wave combine, the same slab - so the slab has
+//            its bits, and ticket, fold and update are its code (acc_ticket_fold, acc_finish).
+// Every barrier is reached by all 1,024 threads: st->done is uniform, and a lane past ns searches nothing but stays.
+constexpr int IT_THREADS = 1024;
+constexpr int IT_TERMS = 8;          // terms per wave (acc_nv <= 32 = 4 subsets of 8)
+template <int MODE> constexpr int rec_words() { return MODE == 0 ? 8 : 7; }
+
+// the sums of the terms [8 S, 8 S + 8) over this lane's four records, reduced over the wave into sh.red[g]
+template <int MODE, bool ROBUST, int S>
+__device__ __forceinline__ void it_sum_subset(const float (*rec)[IT_THREADS], int L, int g, float tau_accept, IcpLoss loss, AccShared& sh) {
+    constexpr int NV = acc_nv<MODE, ROBUST>(), K0 = IT_TERMS * S, NK = NV - K0 < IT_TERMS ? NV - K0 : IT_TERMS;
+    if constexpr (NK > 0) {
+        CorrRec R[ACC_GROUP];
+#pragma unroll
+        for (int q = 0; q < ACC_GROUP; ++q)
+#pragma unroll
+            for (int j = 0; j < rec_words<MODE>(); ++j) R[q].f[j] = rec[j][256 * q + L];
+        double v[NK];
+#pragma unroll
+        for (int k = 0; k < NK; ++k) v[k] = 0.0;
+#pragma unroll
+        for (int q = 0; q < ACC_GROUP; ++q)
+            if (R[q].f[0] <= tau_accept)
+                rec_terms<MODE, ROBUST>(R[q], loss, [&v](int k, double t) { if (k >= K0 && k < K0 + NK) v[k - K0] += t; });
+#pragma unroll
+        for (int k = 0; k < NK; ++k) {
+            const double s = wave_sum_lane63(v[k]);
+            if ((threadIdx.x & 63) == 63) sh.red[g][K0 + k] = s;
+        }
+    }
+}
+
+template <int MODE, bool ROBUST>
+__global__ __launch_bounds__(IT_THREADS)
+void k_icp_iterate(const float* __restrict__ src, int ns, const float* __restrict__ tgt_normals,
+                   const GridEntry* __restrict__ table, const float4* __restrict__ node, unsigned mask, int shift, float inv_cell,
+                   IcpState* st, float tau, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* ticket) {
+    static_assert(MODE == 0 || MODE == 1, "the one-launch iteration exists for point-to-plane and point-to-point");
+    static_assert(ACC_GROUP * 256 == IT_THREADS && 4 * IT_TERMS == ACC_NV, "a workgroup is one slab of k_icp_accumulate<MODE, 4>");
+    if (st->done) return;
+    __shared__ float rec[rec_words<MODE>()][IT_THREADS];
+    __shared__ AccShared sh;
+    const int iter0 = st->iter; const float rmse0 = st->rmse;
+    float T[12], Tb[4];
+    acc_load_pose(st, T, Tb);
+    // ---- search ------------------------------------------------------------------------------------------------------------
+    const int t = threadIdx.x, i = blockIdx.x * IT_THREADS + t;
+    CorrRec R;
+#pragma unroll
+    for (int j = 0; j < REC_WORDS; ++j) R.f[j] = 0.f;
+    R.f[0] = FLT_MAX;
+    if (i < ns) {
+        float px, py, pz;
+        acc_transform(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
+        float bd; int bo;
+        CorrTgt G;
+        grid_nearest(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo, G.q);
+        const bool found = bo != INT_MAX;
+        const int idx = found ? bo : 0;
+        if (MODE == 0) { G.n[0] = tgt_normals[3 * idx]; G.n[1] = tgt_normals[3 * idx + 1]; G.n[2] = tgt_normals[3 * idx + 2]; }
+        if (!found) G.q[0] = G.q[1] = G.q[2] = 0.f;
+        corr_rec<MODE>(px, py, pz, found ? bd : FLT_MAX, G, R);
+    }
+#pragma unroll
+    for (int j = 0; j < rec_words<MODE>(); ++j) rec[j][t] = R.f[j];
+    __syncthreads();
+    // ---- sums --------------------------------------------------------------------------------------------------------------
+    const int w = t >> 6, g = w & 3, L = 64 * g + (t & 63);
+    switch (w >> 2) {      // wave-uniform
+    case 0: it_sum_subset<MODE, ROBUST, 0>(rec, L, g, tau, loss, sh); break;
+    case 1: it_sum_subset<MODE, ROBUST, 1>(rec, L, g, tau, loss, sh); break;
+    case 2: it_sum_subset<MODE, ROBUST, 2>(rec, L, g, tau, loss, sh); break;
+    default: it_sum_subset<MODE, ROBUST, 3>(rec, L, g, tau, loss, sh); break;
+    }
+    acc_slab_store<acc_nv<MODE, ROBUST>()>(slabs, blockIdx.x, sh);
+    if (!acc_ticket_fold(slabs, gridDim.x, ticket, sh)) return;
     if (threadIdx.x != 0) return;
     *ticket = 0u;   // ready for the next launch (stream order)
     acc_finish<MODE, ROBUST>(sh, ns, st, fixed_iterations, iter0, rmse0, T, Tb);
@@ -1405,12 +1547,24 @@ struct IcpPlan {
     bool small;     // the whole loop in one launch (k_icp_small)
     CellGrid cg;    // the target's hash grid, searched when cg.usable
     NnPlan p;       // the scan's shape and the accumulation's acc_ppt / acc_blocks
+    bool one_launch;   // search and sums of an iteration in one kernel (k_icp_iterate), what ctx->last_icp_launches reports
 };
+
+// Source counts between which TDV_ICP_LAUNCHES_AUTO takes k_icp_iterate.  Measured (tools/studies/icp_grid_scaling.py --forms two,one,
+// a 200k-point target, us per iteration two launches / one, profiles/r19/icp_one_launch.md): 100k 32.0 / 35.1, 125k 31.8 / 34.8,
+// 150k 36.7 / 35.3, 175k 37.7 / 35.2, 200k 41.5 / 36.3, 225k 43.0 / 36.3, 250k 43.8 / 36.3, 262,144 44.1 / 37.3, 263,169 46.9 / 56.6,
+// 300k 49.8 / 61.0, 400k 61.8 / 63.6.  The kernel lasts about as long as ONE workgroup's 1,024 points take their CU (25.7 us for 13
+// workgroups), so it wins once the two launches' per-point part has outgrown that, and loses again from the 257th workgroup on: the
+// part has 256 CUs, and a CU that gets a second workgroup runs twice as long.
+constexpr int ONE_LAUNCH_MIN_SOURCES = 150000;
+constexpr int ONE_LAUNCH_MAX_SOURCES = 262144;      // 256 workgroups
 
 // Search: brute force for small problems (the two Morton sorts cost more than they save), the exact pruned walk for large ones, the
 // hash grid (tgt_grid if it was built for this nt and thr, else built here) on request or by size like the walk, used when its build
 // says the cells are small enough.  All give the same correspondences bit for bit.
-int icp_plan(tdv_ctx* ctx, const float* d_tgt, int ns, int nt, float thr, const CellGrid* tgt_grid, IcpPlan& pl) {
+// obj: the single call's objective; without it (a batch) the plan keeps two launches per iteration.
+int icp_plan(tdv_ctx* ctx, const float* d_tgt, int ns, int nt, float thr, const CellGrid* tgt_grid, IcpPlan& pl,
+             const IcpObjective* obj = nullptr) {
     const int mode = ctx->icp_search;
     const float tau = tau_le(thr);
     bool pruned = tau < FLT_MAX &&      // (unbounded threshold: keep the scan's handling of overflowing distances)
@@ -1430,7 +1584,12 @@ int icp_plan(tdv_ctx* ctx, const float* d_tgt, int ns, int nt, float thr, const 
     pl.p = make_plan(ns, nt);
     if (pruned) pl.p.nsplit = 1;
     else if (pl.small || !study_env("TDV_ICP_PPT")) { pl.p.acc_ppt = 1; pl.p.acc_blocks = (ns + 255) / 256; }   // (k_icp_small's tree is the 1's)
-    return TDV_OK;                                     // measured: 50k x 10k brute 7.6k vs 6.4k iters/s with 1 point per thread
+    // one launch per iteration: the hash grid, tree sums in slabs of 4 x 256 points, point-to-plane or point-to-point
+    const bool can_one = obj && pl.cg.usable && pl.p.acc_ppt == ACC_GROUP && ctx->icp_accumulate != TDV_ICP_ACCUMULATE_REFERENCE &&
+                         (obj->kind == ICP_POINT_TO_PLANE || obj->kind == ICP_POINT_TO_POINT);
+    pl.one_launch = can_one && (ctx->icp_launches == TDV_ICP_LAUNCHES_ONE ||
+                                (ctx->icp_launches == TDV_ICP_LAUNCHES_AUTO && ns >= ONE_LAUNCH_MIN_SOURCES && ns <= ONE_LAUNCH_MAX_SOURCES));
+    return TDV_OK;                                    // measured: 50k x 10k brute 7.6k vs 6.4k iters/s with 1 point per thread
 }
 
 struct IcpBuffers {
@@ -1585,8 +1744,9 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     if (ns == 0 || nt == 0) return TDV_OK;  // n_corr == 0 < 3 -> break at the first iteration
     const float tau = tau_le(thr);
     IcpPlan pl;
-    TDV_TRY(icp_plan(ctx, d_tgt, ns, nt, thr, tgt_grid, pl));
+    TDV_TRY(icp_plan(ctx, d_tgt, ns, nt, thr, tgt_grid, pl, &obj));
     ctx->last_icp_search = pl.search;
+    ctx->last_icp_launches = pl.one_launch ? TDV_ICP_LAUNCHES_ONE : TDV_ICP_LAUNCHES_TWO;
     const NnPlan& p = pl.p;
     const CellGrid& cg = pl.cg;
     const IcpLoss loss = ctx_loss(ctx);
@@ -1637,6 +1797,17 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     const float4* gnode = cg.usable ? reinterpret_cast<const float4*>(cg.node) : nullptr;
     const dim3 grid(p.blocks_x, p.nsplit);
     TDV_TRY(run_bursts(ctx, h, b.st, 1, max_iterations, fixed_iterations, [&]() {
+        if (pl.one_launch) {
+            ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);      // the whole iteration: one launch
+            icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto) {
+                constexpr int MODE = decltype(M)::value;
+                if constexpr (MODE == ICP_POINT_TO_PLANE || MODE == ICP_POINT_TO_POINT)      // (icp_plan's rule)
+                    k_icp_iterate<MODE, decltype(R)::value><<<p.acc_blocks, IT_THREADS, 0, s>>>(
+                        d_src, ns, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau,
+                        fixed_iterations, loss, b.slabs, b.ticket);
+            });
+            return;
+        }
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
             if (gtable)
@@ -1701,6 +1872,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
     }
     TDV_HIP(ctx, hipStreamSynchronize(s));
     ctx->last_icp_search = TDV_ICP_SEARCH_BRUTE;
+    ctx->last_icp_launches = TDV_ICP_LAUNCHES_TWO;
     for (int b = 0; b < n_prob; ++b) state_result(h[b], out[b]);
     return TDV_OK;
 }
@@ -1802,7 +1974,8 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const float4* gnode = reinterpret_cast<const float4*>(cg.node);
     const IcpLoss loss = ctx_loss(ctx);
     ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
-    TDV_TRY(run_bursts(ctx, h, d_st, n, max_iterations, fixed_iterations, [&]() {
+    ctx->last_icp_launches = TDV_ICP_LAUNCHES_TWO;
+    TDV_TRY(run_bursts(ctx, h, d_st, n,max_iterations, fixed_iterations, [&]() {
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
             k_icp_nn_grid_multi<<<nn_blocks, 256, 0, s>>>(d_src, d_inst, d_blk_nn, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, d_st, tau, pd2, pidx);

@@ -48,7 +48,9 @@ struct tdv_ctx {
     int last_batch_lanes = 0;  // host lanes the last tdv_register_batch_dev call on this ctx spread its instances over (tdv_ctx_last_batch_lanes)
     int fps_path = 0;          // TDV_FPS_AUTO / _WORKGROUP / _GRID (tdv_ctx_set_fps_path)
     int last_fps_path = 0;     // the family the last farthest-point call on this ctx chose (tdv_ctx_last_fps_path)
-    int last_icp_search = 0; // the search the last ICP / correspondence call on this ctx actually ran (tdv_ctx_last_icp_search)
+    int icp_launches = 0;      // TDV_ICP_LAUNCHES_AUTO / _TWO / _ONE (tdv_ctx_set_icp_launches)
+    int last_icp_launches = 0; // whether the last ICP call on this ctx ran the one-launch iteration (tdv_ctx_last_icp_launches)
+    int last_icp_search = 0;// the search the last ICP / correspondence call on this ctx actually ran (tdv_ctx_last_icp_search)
     unsigned* scan_ticket = nullptr;  // persistent device words: [0] exclusive_scan_dev's last-workgroup ticket, [1..] ICP's, [8] the tile ticket of depth.hip's chained scan
     unsigned long long* chain_status = nullptr;   // depth.hip k_depth_cloud_chain: one status word per tile, persistent (told apart by chain_epoch)
     size_t chain_cap = 0;

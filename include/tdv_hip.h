@@ -79,6 +79,19 @@ int tdv_ctx_set_icp_search(tdv_ctx* ctx, int mode);
 #define TDV_ICP_ACCUMULATE_TREE 0
 #define TDV_ICP_ACCUMULATE_REFERENCE 1
 int tdv_ctx_set_icp_accumulation(tdv_ctx* ctx, int mode);
+/* Launches per ICP iteration, for tests and measurements.  With the hash-grid search, TREE sums and a point-to-plane or point-to-point
+ * objective (L2 or a robust loss) a single call's iteration can run as ONE kernel, which searches one lane per source point and forms the
+ * sums from per-point records handed over in LDS, in the same f64 tree: the same bits as the TWO launches (search, then accumulation).
+ * AUTO (default) takes ONE inside the range of source counts where it measured faster (ICP); TWO and ONE ask for one form.
+ * ONE on a path that has no such kernel (GICP, colored ICP, another search, REFERENCE sums, the small-problem loop, batches) runs that
+ * path as it is.  tdv_ctx_last_icp_launches: TDV_ICP_LAUNCHES_ONE if the last tdv_icp* / tdv_gicp* / tdv_colored_icp* call on the ctx ran
+ * the one-launch kernel, else TDV_ICP_LAUNCHES_TWO (0 before any); TDV_ERR_BAD_ARG for a null ctx, as the setter for a null ctx or an
+ * unknown mode.  No environment variable selects it. */
+#define TDV_ICP_LAUNCHES_AUTO 0
+#define TDV_ICP_LAUNCHES_TWO 1
+#define TDV_ICP_LAUNCHES_ONE 2
+int tdv_ctx_set_icp_launches(tdv_ctx* ctx, int mode);
+int tdv_ctx_last_icp_launches(tdv_ctx* ctx);
 /* ICP robust loss: iteratively reweighted least squares, one weight w per accepted correspondence (d2 <= thr^2, unchanged), set
  * per ctx and honoured by tdv_icp, tdv_icp_dev, tdv_icp_batch_dev, tdv_refine_batch_dev and tdv_register_batch_dev (batch lanes
  * included).  tdv_icp_correspondences is unaffected.  L2 (default) gives every accepted correspondence weight 1: today's results,

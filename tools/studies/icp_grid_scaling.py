@@ -1,5 +1,39 @@
-"""k_icp_nn_grid against the number of source points (same 200k-point target): the fixed and the per-point part of its time."""
-import importlib, os, sys, json
+"""One ICP iteration on the hash-grid path against the number of source points (same 200k-point target): the fixed and the per-point
+part of the whole iteration, of the search launch, and - from a kernel trace - of every ICP kernel.
+
+    python tools/studies/icp_grid_scaling.py [--forms auto|two|one,...] [--rounds R] [--sizes N,N,...]
+        per source count and form (tdv_ctx_set_icp_launches; alternated, R rounds): iteration_us is a 100-iteration fixed run between two
+        events with timing off, nn_kernel_us is TDV_TIMER_ICP_NN per launch (with ONE launch that is the whole fused kernel).
+    rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/studies/icp_grid_scaling.py ...
+    python tools/studies/icp_grid_scaling.py --trace <kernel_trace.csv>
+        the trace of such a run split by kernel and workgroup count (one workgroup count per source count): mean us per launch of
+        k_icp_nn_grid, k_icp_accumulate and k_icp_iterate.  k_icp_accumulate at 12,500 sources is that kernel's fixed part."""
+import argparse, csv, importlib, os, sys, json
+
+SIZES = (12500, 25000, 50000, 100000, 200000, 400000, 800000)
+ap = argparse.ArgumentParser()
+ap.add_argument("--forms", default="auto")
+ap.add_argument("--rounds", type=int, default=1)
+ap.add_argument("--sizes", help="source counts instead of the standard seven (with --trace: the counts of the traced run)")
+ap.add_argument("--trace")
+args = ap.parse_args()
+if args.sizes: SIZES = tuple(int(n) for n in args.sizes.split(","))
+
+if args.trace:
+    acc = {}
+    for r in csv.DictReader(open(args.trace)):
+        name = r["Kernel_Name"].split("(")[0]
+        kern = next((k for k in ("k_icp_nn_grid", "k_icp_accumulate", "k_icp_iterate") if k in name and "_multi" not in name), None)
+        if not kern: continue
+        wgs = int(r["Grid_Size_X"]) // int(r["Workgroup_Size_X"])
+        acc.setdefault((kern, wgs), []).append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
+    pts = {"k_icp_nn_grid": 256, "k_icp_accumulate": 1024, "k_icp_iterate": 1024}
+    for (kern, wgs), d in sorted(acc.items()):
+        ns = [n for n in SIZES if (n + pts[kern] - 1) // pts[kern] == wgs]
+        d = sorted(d)[: max(1, len(d) * 9 // 10)]      # without the slowest tenth: first launches of a call
+        print(json.dumps({"kernel": kern, "workgroups": wgs, "ns": ns[0] if ns else None, "launches": len(d), "mean_us": sum(d) / len(d) / 1e3, "min_us": d[0] / 1e3}))
+    sys.exit(0)
+
 import numpy as np
 import torch
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", ".."))
@@ -10,13 +44,23 @@ ctx = tdv.Context(0); dev = torch.device("cuda", 0)
 tgt, nrm = synth.sample_object(nt, 42)
 voxel = float(np.float32(synth.mean_spacing(nt)))
 d_tgt = torch.from_numpy(tgt).to(dev); d_nrm = torch.from_numpy(nrm).to(dev)
-for ns in (12500, 25000, 50000, 100000, 200000, 400000, 800000):
+ctx.set_icp_search("grid")
+for ns in SIZES:
     src, T_gt = synth.make_scene(ns, 42)
     T0 = synth.perturb(T_gt, 42, angle_deg=0.3, trans=0.0005)
     d_src = torch.from_numpy(src).to(dev)
-    ctx.set_icp_search("grid")
-    ctx.icp_dev(d_src.data_ptr(), ns, d_tgt.data_ptr(), d_nrm.data_ptr(), nt, T0, voxel * 0.4, 10, True, fixed_iterations=True)
-    ctx.timing_enable(True); ctx.timing_read(tdv.TIMER_ICP_NN)
-    ctx.icp_dev(d_src.data_ptr(), ns, d_tgt.data_ptr(), d_nrm.data_ptr(), nt, T0, voxel * 0.4, 100, True, fixed_iterations=True)
-    ms, launches = ctx.timing_read(tdv.TIMER_ICP_NN); ctx.timing_enable(False)
-    print(json.dumps({"ns": ns, "search": ctx.last_icp_search(), "nn_kernel_us": ms / launches * 1e3, "ns_per_point": ms / launches * 1e6 / ns}))
+    run = lambda n: ctx.icp_dev(d_src.data_ptr(), ns, d_tgt.data_ptr(), d_nrm.data_ptr(), nt, T0, voxel * 0.4, n, True, fixed_iterations=True)
+    for rnd in range(args.rounds):
+        for form in args.forms.split(","):
+            if form != "auto": ctx.set_icp_launches(form)
+            run(10)
+            e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
+            e0.record(); run(100); e1.record(); e1.synchronize()
+            it_us = e0.elapsed_time(e1) * 10.0
+            ctx.timing_enable(True); ctx.timing_read(tdv.TIMER_ICP_NN)
+            run(100)
+            ms, launches = ctx.timing_read(tdv.TIMER_ICP_NN); ctx.timing_enable(False)
+            out = {"ns": ns, "form": form, "round": rnd, "search": ctx.last_icp_search(), "iteration_us": it_us, "nn_kernel_us": ms / launches * 1e3,
+                   "ns_per_point": ms / launches * 1e6 / ns}
+            if form != "auto": out["ran"] = ctx.last_icp_launches()
+            print(json.dumps(out), flush=True)
