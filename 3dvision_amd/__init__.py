@@ -101,6 +101,24 @@ class IcpResultC(C.Structure):
                 ("n_corr", C.c_int)]
 
 
+def _params(stage, kw):
+    """The parameter struct of a stage (_PARAMS below), filled by the library's tdv_*_default_params, with the fields in kw replaced."""
+    struct, default_fn_name, label, names = _PARAMS[stage]
+    p = struct()
+    getattr(lib(), default_fn_name)(C.byref(p))
+    fields = dict(struct._fields_)
+    for k, v in kw.items():
+        if k not in fields:
+            raise TypeError("unknown %s parameter %r" % (label, k))
+        setattr(p, k, names[k][v] if names and k in names and isinstance(v, str) else v)
+    return p
+
+
+def _fields_dict(r):
+    """A result struct as a dict of its fields."""
+    return {k: getattr(r, k) for k, _ in r._fields_}
+
+
 class FgrParamsC(C.Structure):
     _fields_ = [("division_factor", C.c_float), ("maximum_correspondence_distance", C.c_float), ("tuple_scale", C.c_float),
                 ("iteration_number", C.c_int), ("maximum_tuple_count", C.c_int), ("use_absolute_scale", C.c_int),
@@ -114,13 +132,7 @@ class FgrResultC(C.Structure):
 
 def fgr_params(**kw):
     """tdv_fgr_default_params with the given fields replaced (Open3D's FastGlobalRegistrationOption names)."""
-    p = FgrParamsC()
-    lib().tdv_fgr_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in dict(FgrParamsC._fields_):
-            raise TypeError("unknown FGR parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params("fgr", kw)
 
 
 TDV_PLANE_CHUNK = 1024
@@ -139,13 +151,7 @@ class PlaneResultC(C.Structure):
 
 def plane_params(**kw):
     """tdv_plane_default_params with the given fields replaced (Open3D's segment_plane names, plus max_planes, min_inliers, refit, seed)."""
-    p = PlaneParamsC()
-    lib().tdv_plane_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in dict(PlaneParamsC._fields_):
-            raise TypeError("unknown plane parameter %r" % k)
-        setattr(p, k, v)
-    return p
+    return _params("plane", kw)
 
 
 def _plane_results(res, n):
@@ -165,25 +171,11 @@ class ClusterResultC(C.Structure):
 
 def cluster_params(**kw):
     """tdv_cluster_default_params (min_cluster_size = 1; eps and min_points have no default) with the given fields replaced."""
-    p = ClusterParamsC()
-    lib().tdv_cluster_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in dict(ClusterParamsC._fields_):
-            raise TypeError("unknown cluster parameter %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-def _cluster_result(r):
-    return {k: getattr(r, k) for k, _ in ClusterResultC._fields_}
+    return _params("cluster", kw)
 
 
 class OutlierResultC(C.Structure):
     _fields_ = [("n_valid", C.c_int), ("n_kept", C.c_int), ("cloud_mean", C.c_double), ("std_dev", C.c_double), ("threshold", C.c_double)]
-
-
-def _outlier_result(r):
-    return {k: getattr(r, k) for k, _ in OutlierResultC._fields_}
 
 
 class IssParamsC(C.Structure):
@@ -199,17 +191,7 @@ class IssResultC(C.Structure):
 def iss_params(**kw):
     """tdv_iss_default_params (radii 0: from the cloud's resolution; gammas 0.975; min_neighbors 5) with the given fields replaced
     (Open3D's compute_iss_keypoints names)."""
-    p = IssParamsC()
-    lib().tdv_iss_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in dict(IssParamsC._fields_):
-            raise TypeError("unknown ISS parameter %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-def _iss_result(r):
-    return {k: getattr(r, k) for k, _ in IssResultC._fields_}
+    return _params("iss", kw)
 
 
 TDV_FPS_MAX_POINTS = 1 << 22
@@ -250,17 +232,13 @@ class VerifyResultC(C.Structure):
 def verify_params(**kw):
     """tdv_verify_default_params (T moves the camera's cloud onto the model, splat 1, tau 0.002 m, zmax 10 m) with the given fields replaced;
     pose_direction also by name ('source_onto_target', 'model_to_camera')."""
-    p = VerifyParamsC()
-    lib().tdv_verify_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in dict(VerifyParamsC._fields_):
-            raise TypeError("unknown verification parameter %r" % k)
-        setattr(p, k, POSE_DIRECTION[v] if k == "pose_direction" and isinstance(v, str) else v)
-    return p
+    return _params("verify", kw)
 
 
-def _verify_result(r):
-    return {k: int(getattr(r, k)) for k, _ in VerifyResultC._fields_}
+def _verify_results(res, n):
+    """One dict of ints per pose.  The names are taken once: a call converts hundreds of records, a third of a device call's time."""
+    names = [k for k, _ in VerifyResultC._fields_]
+    return [{k: int(getattr(r, k)) for k in names} for r in res[:n]]
 
 
 TDV_MESH_CULL_NONE, TDV_MESH_CULL_BACK = 0, 1
@@ -279,14 +257,7 @@ class MeshVerifyParamsC(C.Structure):
 def mesh_verify_params(**kw):
     """tdv_mesh_verify_default_params (T moves the camera's cloud onto the model, no culling, tau 0.002 m, zmax 10 m) with the given fields
     replaced; pose_direction and cull also by name ('source_onto_target', 'model_to_camera'; 'none', 'back')."""
-    p = MeshVerifyParamsC()
-    lib().tdv_mesh_verify_default_params(C.byref(p))
-    names = dict(pose_direction=POSE_DIRECTION, cull=MESH_CULL)
-    for k, v in kw.items():
-        if k not in dict(MeshVerifyParamsC._fields_):
-            raise TypeError("unknown mesh verification parameter %r" % k)
-        setattr(p, k, names[k][v] if k in names and isinstance(v, str) else v)
-    return p
+    return _params("mesh_verify", kw)
 
 
 def _mesh(vertices, triangles):
@@ -326,17 +297,7 @@ PPF_PEAK_DTYPE = np.dtype([("ref", np.int32), ("model_index", np.int32), ("bin",
 def ppf_params(**kw):
     """tdv_ppf_default_params (step 0.05 of the diameter, 30 angle and 30 rotation bins, ref_stride 5, 8 poses, clusters within 0.1 of the
     diameter and 2 pi / 30) with the given fields replaced."""
-    p = PpfParamsC()
-    lib().tdv_ppf_default_params(C.byref(p))
-    for k, v in kw.items():
-        if k not in dict(PpfParamsC._fields_):
-            raise TypeError("unknown PPF parameter %r" % k)
-        setattr(p, k, v)
-    return p
-
-
-def _ppf_info(i):
-    return {k: getattr(i, k) for k, _ in PpfModelInfoC._fields_}
+    return _params("ppf", kw)
 
 
 def _ppf_poses(poses, n):
@@ -345,6 +306,20 @@ def _ppf_poses(poses, n):
            for q in poses[:n]]
     return res, [dict(votes=q.votes, members=q.members, ref=q.ref, model_index=q.model_index, bin=q.bin) for q in poses[:n]]
 
+
+# The stages with a parameter struct: the struct, the library's function that fills in its defaults, the stage's name in the TypeError
+# of an unknown field, and per field the strings that stand for its values.  _params builds the struct from a row, and lib() declares
+# every row's function as returning nothing: a new stage is one row here.
+_PARAMS = {
+    "fgr": (FgrParamsC, "tdv_fgr_default_params", "FGR", None),
+    "plane": (PlaneParamsC, "tdv_plane_default_params", "plane", None),
+    "cluster": (ClusterParamsC, "tdv_cluster_default_params", "cluster", None),
+    "iss": (IssParamsC, "tdv_iss_default_params", "ISS", None),
+    "verify": (VerifyParamsC, "tdv_verify_default_params", "verification", dict(pose_direction=POSE_DIRECTION)),
+    "mesh_verify": (MeshVerifyParamsC, "tdv_mesh_verify_default_params", "mesh verification",
+                    dict(pose_direction=POSE_DIRECTION, cull=MESH_CULL)),
+    "ppf": (PpfParamsC, "tdv_ppf_default_params", "PPF", None),
+}
 
 _lib = None
 _lib_lock = threading.Lock()
@@ -384,13 +359,8 @@ def lib():
             l.tdv_ctx_last_ransac_rescore.restype = C.c_double
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
             l.tdv_ctx_last_ransac_bound.restype = None
-            l.tdv_fgr_default_params.restype = None
-            l.tdv_plane_default_params.restype = None
-            l.tdv_cluster_default_params.restype = None
-            l.tdv_iss_default_params.restype = None
-            l.tdv_ppf_default_params.restype = None
-            l.tdv_verify_default_params.restype = None
-            l.tdv_mesh_verify_default_params.restype = None
+            for _, default_fn_name, _, _ in _PARAMS.values():
+                getattr(l, default_fn_name).restype = None
             _lib = l
     return _lib
 
@@ -950,7 +920,7 @@ class Context:
         rows = np.empty((max(n, 1), 3), np.float32) if grouped else None
         _check(self._h, lib().tdv_cluster_dbscan(self._h, _ptr(xyz), n, C.byref(p), C.byref(res), _ptr(labels), _ptr(order), _ptr(rows),
                                                  _ptr(offsets), n, C.byref(nl)), "tdv_cluster_dbscan")
-        out = (dict(_cluster_result(res), n_labelled=nl.value), labels[:n], order[:n], offsets[:res.n_clusters + 1].copy())
+        out = (dict(_fields_dict(res), n_labelled=nl.value), labels[:n], order[:n], offsets[:res.n_clusters + 1].copy())
         return out + (rows[:n],) if grouped else out
 
     def cluster_dbscan(self, xyz, eps, min_points, min_cluster_size=1):
@@ -965,7 +935,7 @@ class Context:
         offsets = np.empty(n + 1, np.int32)
         _check(self._h, lib().tdv_cluster_dbscan_dev(self._h, _ptr(d_xyz), n, C.byref(p), C.byref(res), _ptr(d_labels), _ptr(d_order),
                                                      _ptr(d_grouped), _ptr(offsets), n, C.byref(nl)), "tdv_cluster_dbscan_dev")
-        return dict(_cluster_result(res), n_labelled=nl.value), offsets[:res.n_clusters + 1].copy()
+        return dict(_fields_dict(res), n_labelled=nl.value), offsets[:res.n_clusters + 1].copy()
 
     # ---------------------------------------------------------------- outlier removal (include/tdv_hip.h: tdv_remove_statistical_outlier)
     def _outlier_host(self, fn, what, xyz, rgb, a, b, per_point_dtype):
@@ -978,7 +948,7 @@ class Context:
         rows = np.zeros((max(n, 1), 3), np.float32); cols = None if rgb is None else np.zeros((max(n, 1), 3), np.float32)
         _check(self._h, fn(self._h, _ptr(xyz), _ptr(rgb), n, a, b, C.byref(res), _ptr(mask), _ptr(per), _ptr(index), _ptr(rows), _ptr(cols)), what)
         m = res.n_kept
-        return dict(_outlier_result(res), mask=mask[:n], per_point=per[:n], index=index[:m], xyz=rows[:m], rgb=None if cols is None else cols[:m])
+        return dict(_fields_dict(res), mask=mask[:n], per_point=per[:n], index=index[:m], xyz=rows[:m], rgb=None if cols is None else cols[:m])
 
     def statistical_outlier(self, xyz, nb_neighbors, std_ratio, rgb=None):
         """tdv_remove_statistical_outlier, every output: dict(n_valid, n_kept, cloud_mean, std_dev, threshold, mask uint8[n], mean float64[n],
@@ -1014,7 +984,7 @@ class Context:
         _check(self._h, lib().tdv_remove_statistical_outlier_dev(self._h, _ptr(d_xyz), _ptr(d_rgb), n, int(nb_neighbors), C.c_double(std_ratio),
                                                                  C.byref(res), _ptr(d_mask), _ptr(d_mean), _ptr(d_index), _ptr(d_out_xyz),
                                                                  _ptr(d_out_rgb)), "tdv_remove_statistical_outlier_dev")
-        return _outlier_result(res)
+        return _fields_dict(res)
 
     def remove_radius_outlier_dev(self, d_xyz, n, nb_points, radius, d_rgb=None, d_mask=None, d_count=None, d_index=None, d_out_xyz=None,
                                   d_out_rgb=None):
@@ -1023,7 +993,7 @@ class Context:
         _check(self._h, lib().tdv_remove_radius_outlier_dev(self._h, _ptr(d_xyz), _ptr(d_rgb), n, int(nb_points), C.c_float(radius), C.byref(res),
                                                             _ptr(d_mask), _ptr(d_count), _ptr(d_index), _ptr(d_out_xyz), _ptr(d_out_rgb)),
                "tdv_remove_radius_outlier_dev")
-        return _outlier_result(res)
+        return _fields_dict(res)
 
     # ---------------------------------------------------------------- ISS keypoints (include/tdv_hip.h: tdv_iss_keypoints)
     def iss(self, xyz, attr=None, **params):
@@ -1046,7 +1016,7 @@ class Context:
         _check(self._h, lib().tdv_iss_keypoints(self._h, _ptr(xyz), n, C.byref(p), _ptr(attr), width, C.byref(res), _ptr(mask), _ptr(sal), _ptr(eig),
                                                 _ptr(sup), _ptr(index), _ptr(rows), _ptr(cols)), "tdv_iss_keypoints")
         m = res.n_keypoints
-        return dict(_iss_result(res), mask=mask[:n], saliency=sal[:n], eigenvalues=eig[:n], support=sup[:n], index=index[:m], xyz=rows[:m],
+        return dict(_fields_dict(res), mask=mask[:n], saliency=sal[:n], eigenvalues=eig[:n], support=sup[:n], index=index[:m], xyz=rows[:m],
                     attr=None if cols is None else cols.reshape(-1)[:m * width].reshape(m, width))
 
     def compute_iss_keypoints(self, xyz, salient_radius=0.0, non_max_radius=0.0, gamma_21=0.975, gamma_32=0.975, min_neighbors=5):
@@ -1065,7 +1035,7 @@ class Context:
         _check(self._h, lib().tdv_iss_keypoints_dev(self._h, _ptr(d_xyz), n, C.byref(p), _ptr(d_attr), int(attr_width), C.byref(res), _ptr(d_mask),
                                                     _ptr(d_saliency), _ptr(d_eigenvalues), _ptr(d_support), _ptr(d_index), _ptr(d_out_xyz),
                                                     _ptr(d_out_attr)), "tdv_iss_keypoints_dev")
-        return _iss_result(res)
+        return _fields_dict(res)
 
     # ---------------------------------------------------------------- farthest point sampling (include/tdv_hip.h: tdv_farthest_point_down_sample)
     def fps(self, xyz, num_samples, start_index=0, attr=None):
@@ -1166,7 +1136,7 @@ class Context:
         _check(self._h, lib().tdv_verify_poses(self._h, _ptr(model), len(model), _ptr(t), n, _ptr(raw), w, h, C.c_float(scale), C.c_float(fx),
                                                C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)), res,
                                                _ptr(order)), "tdv_verify_poses")
-        return [_verify_result(res[b]) for b in range(n)], order
+        return _verify_results(res, n), order
 
     def verify_poses_dev(self, d_model, n_model, poses, d_raw, w, h, scale, fx, fy, cx, cy, **params):
         """tdv_verify_poses_dev: verify_poses with the model (float[3 n_model]) and the raw frame (uint16[w h]) as device pointers; the poses
@@ -1177,7 +1147,7 @@ class Context:
         _check(self._h, lib().tdv_verify_poses_dev(self._h, _ptr(d_model), int(n_model), _ptr(t), n, _ptr(d_raw), int(w), int(h), C.c_float(scale),
                                                    C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), C.byref(verify_params(**params)),
                                                    res, _ptr(order)), "tdv_verify_poses_dev")
-        return [_verify_result(res[b]) for b in range(n)], order
+        return _verify_results(res, n), order
 
     def render_depth(self, model, pose, w, h, fx, fy, cx, cy, **params):
         """tdv_render_depth: the rendered depth of the model at one pose, float32 [h, w], 0 where nothing rendered - per pixel the minimum
@@ -1212,7 +1182,7 @@ class Context:
         _check(self._h, lib().tdv_verify_poses_mesh(self._h, _ptr(vtx), len(vtx), _ptr(tri), len(tri), _ptr(t), n, _ptr(raw), w, h, C.c_float(scale),
                                                     C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),
                                                     C.byref(mesh_verify_params(**params)), res, _ptr(order)), "tdv_verify_poses_mesh")
-        return [_verify_result(res[b]) for b in range(n)], order
+        return _verify_results(res, n), order
 
     def verify_poses_mesh_dev(self, d_vertices, n_vertices, d_triangles, n_triangles, poses, d_raw, w, h, scale, fx, fy, cx, cy, **params):
         """tdv_verify_poses_mesh_dev: verify_poses_mesh with the vertices (float[3 n_vertices]), the triangles (int32[3 n_triangles]) and the
@@ -1224,7 +1194,7 @@ class Context:
                                                         _ptr(d_raw), int(w), int(h), C.c_float(scale), C.c_float(fx), C.c_float(fy), C.c_float(cx),
                                                         C.c_float(cy), C.byref(mesh_verify_params(**params)), res, _ptr(order)),
                "tdv_verify_poses_mesh_dev")
-        return [_verify_result(res[b]) for b in range(n)], order
+        return _verify_results(res, n), order
 
     def render_depth_mesh(self, vertices, triangles, pose, w, h, fx, fy, cx, cy, **params):
         """tdv_render_depth_mesh: the rendered depth of the mesh at one pose, float32 [h, w], 0 where nothing rendered - per pixel the
@@ -1258,7 +1228,7 @@ class Context:
         info = PpfModelInfoC()
         _check(self._h, lib().tdv_ppf_model_dev(self._h, _ptr(d_tgt), _ptr(d_tgt_normals), int(nt), C.byref(ppf_params(**params)), _ptr(d_model),
                                                 C.c_size_t(model_bytes), C.byref(info)), "tdv_ppf_model_dev")
-        return _ppf_info(info)
+        return _fields_dict(info)
 
     def ppf_model(self, tgt, tgt_normals, **params):
         """The model table of host arrays, parsed from the buffer (rule 4's layout): dict(diameter, distance_step, n_pairs, n_keys, nt,

@@ -155,8 +155,6 @@ int batch_voxels(tdv_ctx* ctx, int n_instances, const tdv_batch_params* prm, con
     return TDV_OK;
 }
 
-}  // namespace
-
 int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
                        const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
                        const float* d_model_fpfh, int n_model, tdv_instance_result* results) {
@@ -532,6 +530,8 @@ int refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks
     return TDV_OK;
 }
 
+}  // namespace
+
 }  // namespace tdv
 
 using namespace tdv;
@@ -541,10 +541,8 @@ extern "C" {
 int tdv_register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
                            const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
                            const float* d_model_fpfh, int n_model, tdv_instance_result* results) {
-    if (!ctx) return TDV_ERR_BAD_ARG;
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    TDV_TRY(icp_loss_check(ctx));
+    TDV_TRY(call_enter(ctx));
+    TDV_TRY(icp_loss_check(ctx));            // a refused call must not reset the workspace: ws_reset can wait on the stream and reallocate
     TDV_TRY(ws_reset(ctx));
     return register_batch_dev(ctx, d_raw, d_bgr, d_masks, n_instances, prm, d_model_xyz, d_model_normals, d_model_fpfh, n_model, results);
 }
@@ -558,9 +556,8 @@ int tdv_refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_b
     if (prm->icp_max_iterations < 0 || !(prm->voxel_size > 0.f)) return TDV_ERR_BAD_ARG;
     TDV_TRY(batch_check(prm, n_instances));
     (void)d_bgr;  // colours do not enter the registration chain
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    TDV_TRY(icp_loss_check(ctx));
+    TDV_TRY(call_enter(ctx));
+    TDV_TRY(icp_loss_check(ctx));            // as above
     TDV_TRY(ws_reset(ctx));
     return refine_batch_dev(ctx, d_raw, d_masks, n_instances, prm, h_T0, d_model_xyz, d_model_normals, n_model, results);
 }
@@ -575,9 +572,7 @@ int tdv_depth_to_cloud_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint
     if (mask_format != 0 && n_frames > 1) return TDV_ERR_BAD_ARG;   // a label image belongs to one frame
     if ((mask_format == 1 && n_instances > 255) || (mask_format == 2 && n_instances > 65535)) return TDV_ERR_BAD_ARG;   // instance b is label b + 1
     const int layout = mask_format == 0 ? 1 : (mask_format == 1 ? 0 : 2);
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    TDV_TRY(ws_reset(ctx));
+    TDV_TRY(call_begin(ctx));
     h_offsets[0] = 0;
     if (n_instances == 0 || (size_t)width * height == 0) { for (int b = 0; b <= n_instances; ++b) h_offsets[b] = 0; return TDV_OK; }
     int* d_off = nullptr;
@@ -595,9 +590,7 @@ int tdv_depth_to_cloud_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint
 int tdv_prepare_model_dev(tdv_ctx* ctx, const float* d_xyz, int n, float voxel_size, int voxel_order, int normals_k, float fpfh_radius_factor,
                           float* d_out_xyz, float* d_out_normals, float* d_out_fpfh, int* n_out) {
     if (!ctx || !n_out || n < 0 || (n > 0 && (!d_xyz || !d_out_xyz || !d_out_normals || !d_out_fpfh))) return TDV_ERR_BAD_ARG;
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    TDV_TRY(ws_reset(ctx));
+    TDV_TRY(call_begin(ctx));
     *n_out = 0;
     if (n == 0) return TDV_OK;
     int v = 0;

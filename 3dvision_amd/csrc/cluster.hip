@@ -230,12 +230,6 @@ __global__ __launch_bounds__(256) void k_cluster_gather(const float* __restrict_
     out[3 * (size_t)k] = xyz[3 * j]; out[3 * (size_t)k + 1] = xyz[3 * j + 1]; out[3 * (size_t)k + 2] = xyz[3 * j + 2];
 }
 
-int cluster_begin(tdv_ctx* ctx) {
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    return ws_reset(ctx);
-}
-
 // every argument, before anything is enqueued (include/tdv_hip.h: tdv_cluster_dbscan)
 bool cluster_args_ok(const tdv_ctx* ctx, const float* xyz, int n, const tdv_cluster_params* p, const tdv_cluster_result* result,
                      const int* offsets, int capacity) {
@@ -312,13 +306,11 @@ int cluster_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_cluster_p
         if (d_grouped) k_cluster_gather<<<nb, 256, 0, s>>>(d_xyz, d_order, n, d_grouped);
         TDV_CHECK_LAUNCH(ctx);
     }
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, st, sizeof(ClusterState), hipMemcpyDeviceToHost, s));
-    if (h_labels) TDV_HIP(ctx, hipMemcpyAsync(h_labels, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (h_order) TDV_HIP(ctx, hipMemcpyAsync(h_order, d_order, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (h_grouped) TDV_HIP(ctx, hipMemcpyAsync(h_grouped, d_grouped, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
+    TDV_TRY(download(ctx, h_labels, d_labels, (size_t)n));
+    TDV_TRY(download(ctx, h_order, d_order, (size_t)n));
+    TDV_TRY(download(ctx, h_grouped, d_grouped, (size_t)n * 3));
     ClusterState hs;
-    std::memcpy(&hs, ctx->pin, sizeof(hs));
+    TDV_TRY(fetch_state(ctx, st, &hs));
     *result = hs.res;
     if (n_labelled) *n_labelled = hs.n_labelled;
     if (hs.n_kept > capacity) {
@@ -327,8 +319,8 @@ int cluster_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_cluster_p
     }
     if (offsets) {
         int* h_offs = reinterpret_cast<int*>(ctx->pin + sizeof(ClusterState));
-        TDV_HIP(ctx, hipMemcpyAsync(h_offs, offs, (size_t)(hs.n_kept + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
+        TDV_TRY(download(ctx, h_offs, offs, (size_t)hs.n_kept + 1));
+        TDV_TRY(finish(ctx));
         std::memcpy(offsets, h_offs, (size_t)(hs.n_kept + 1) * sizeof(int));
     }
     return TDV_OK;
@@ -350,12 +342,11 @@ void tdv_cluster_default_params(tdv_cluster_params* p) {
 int tdv_cluster_dbscan(tdv_ctx* ctx, const float* xyz, int n, const tdv_cluster_params* params, tdv_cluster_result* result, int* labels,
                        int* order, float* grouped_xyz, int* offsets, int offsets_capacity, int* n_labelled) {
     if (!cluster_args_ok(ctx, xyz, n, params, result, offsets, offsets_capacity)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(cluster_begin(ctx));
-    float *d_xyz = nullptr, *d_grouped = nullptr;
+    TDV_TRY(call_begin(ctx));
+    float *d_xyz, *d_grouped = nullptr;
     int *d_labels = nullptr, *d_order = nullptr;
+    TDV_TRY(upload(ctx, xyz, (size_t)n * 3, &d_xyz));
     if (n > 0) {
-        TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &d_xyz));
-        TDV_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
         if (labels) TDV_TRY(ws_alloc(ctx, (size_t)n, &d_labels));
         if (order) TDV_TRY(ws_alloc(ctx, (size_t)n, &d_order));
         if (grouped_xyz) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &d_grouped));
@@ -367,7 +358,7 @@ int tdv_cluster_dbscan(tdv_ctx* ctx, const float* xyz, int n, const tdv_cluster_
 int tdv_cluster_dbscan_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_cluster_params* params, tdv_cluster_result* result,
                            int* d_labels, int* d_order, float* d_grouped_xyz, int* offsets, int offsets_capacity, int* n_labelled) {
     if (!cluster_args_ok(ctx, d_xyz, n, params, result, offsets, offsets_capacity)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(cluster_begin(ctx));
+    TDV_TRY(call_begin(ctx));
     return cluster_run_dev(ctx, d_xyz, n, *params, result, d_labels, d_order, d_grouped_xyz, offsets, offsets_capacity, n_labelled, nullptr,
                            nullptr, nullptr);
 }

@@ -56,8 +56,7 @@ int prepare(tdv_ctx* ctx, void* comm, int* world, int* rank) {
     if (!ctx || !comm) return TDV_ERR_BAD_ARG;
     std::call_once(g_once, resolve);
     if (!g_rccl.ok) { std::snprintf(ctx->err, sizeof(ctx->err), "RCCL (librccl.so.1) is not available in this process"); return TDV_ERR_NO_DEVICE; }
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
+    TDV_TRY(tdv::call_enter(ctx));
     TDV_RCCL(ctx, g_rccl.count(comm, world), "ncclCommCount");
     TDV_RCCL(ctx, g_rccl.rank(comm, rank), "ncclCommUserRank");
     return TDV_OK;

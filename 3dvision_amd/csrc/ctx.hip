@@ -58,6 +58,29 @@ int pin_reserve(tdv_ctx* ctx, size_t bytes) {
     return TDV_OK;
 }
 
+// ---- the frame of a public call (entry.hpp)
+int call_enter(tdv_ctx* ctx) {
+    if (!ctx) return TDV_ERR_BAD_ARG;
+    TDV_HIP(ctx, hipSetDevice(ctx->device));
+    ctx->err[0] = 0;
+    return TDV_OK;
+}
+
+int call_begin(tdv_ctx* ctx) {
+    TDV_TRY(call_enter(ctx));
+    return ws_reset(ctx);
+}
+
+int download_rows(tdv_ctx* ctx, size_t m, std::initializer_list<RowCopy> rows) {
+    bool any = false;
+    for (const RowCopy& r : rows) {
+        if (m == 0 || !r.host || !r.dev) continue;
+        TDV_HIP(ctx, hipMemcpyAsync(r.host, r.dev, m * r.row_bytes, hipMemcpyDeviceToHost, ctx->stream));
+        any = true;
+    }
+    return any ? finish(ctx) : TDV_OK;
+}
+
 static hipEvent_t get_event(tdv_ctx* ctx) {
     if (!ctx->event_pool.empty()) { hipEvent_t e = ctx->event_pool.back(); ctx->event_pool.pop_back(); return e; }
     hipEvent_t e = nullptr;
@@ -159,7 +182,7 @@ struct Mt19937 {
 };
 }  // namespace
 
-void mt19937_lemire_triples(uint32_t seed, uint64_t n, int count, uint64_t* out) {
+static void mt19937_lemire_triples(uint32_t seed, uint64_t n, int count, uint64_t* out) {
     Mt19937 g(seed);
     const uint32_t range = (uint32_t)n;      // n = 2^32 -> 0: the raw words
     uint32_t buf[3 * 1024];

@@ -927,7 +927,7 @@ void k_mask_resize_nn(const uint8_t* __restrict__ src, int sw, int sh, const int
     dst[b * (size_t)dw * dh + i] = src[b * (size_t)sw * sh + (size_t)y_ofs[y] * sw + x_ofs[x]];
 }
 
-void resize_nn_tables(int sw, int sh, int dw, int dh, int* x_ofs, int* y_ofs) {
+static void resize_nn_tables(int sw, int sh, int dw, int dh, int* x_ofs, int* y_ofs) {
     const double inv_scale_x = (double)dw / sw, inv_scale_y = (double)dh / sh;
     const double ifx = 1. / inv_scale_x, ify = 1. / inv_scale_y;
     for (int x = 0; x < dw; ++x) x_ofs[x] = std::min((int)std::floor(x * ifx), sw - 1);

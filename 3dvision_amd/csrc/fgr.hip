@@ -319,7 +319,8 @@ __global__ __launch_bounds__(FGR_OPT_THREADS) void k_fgr_optimize(const int2* __
     }
 }
 
-}  // namespace
+// want_pairs (tdv_fgr_correspondences): stop after the tuple test and leave the device pair lists in *pairs
+struct FgrPairs { const int2* mutual = nullptr; const int2* tuple = nullptr; int n_mutual = 0, n_tuple = 0; long long trials_run = 0; };
 
 int fgr_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, float voxel,
                 const tdv_fgr_params& prm, tdv_fgr_result* out, FgrPairs* pairs) {
@@ -419,4 +420,84 @@ int fgr_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, in
     return TDV_OK;
 }
 
+// every argument, before anything is enqueued (include/tdv_hip.h: tdv_fgr)
+bool fgr_args_ok(const tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft,
+                 float voxel_size, const tdv_fgr_params* p) {
+    if (!ctx || !p || ns < 0 || nt < 0) return false;
+    if (ns > 0 && (!src || !fs)) return false;
+    if (nt > 0 && (!tgt || !ft)) return false;
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0.f)) return false;
+    if (!std::isfinite(p->division_factor) || !(p->division_factor > 1.f)) return false;
+    if (!std::isfinite(p->tuple_scale) || !(p->tuple_scale > 0.f && p->tuple_scale <= 1.f)) return false;
+    if (!std::isfinite(p->maximum_correspondence_distance) || !(p->maximum_correspondence_distance > 0.f)) return false;
+    return p->iteration_number >= 0 && p->maximum_tuple_count >= 1;
+}
+
+void fgr_empty(tdv_fgr_result* out) {
+    std::memset(out, 0, sizeof(*out));
+    for (int i = 0; i < 16; ++i) out->T[i] = (i % 5 == 0) ? 1.f : 0.f;
+    out->degenerate = 1;
+}
+
+// host arrays: both clouds and their descriptors into the workspace
+struct FgrClouds { float *src, *tgt, *fs, *ft; };
+int fgr_upload(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft, FgrClouds* d) {
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d->src));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d->tgt));
+    TDV_TRY(upload(ctx, fs, (size_t)ns * 33, &d->fs));
+    return upload(ctx, ft, (size_t)nt * 33, &d->ft);
+}
+
+}  // namespace
+
 }  // namespace tdv
+
+using namespace tdv;
+
+extern "C" {
+
+void tdv_fgr_default_params(tdv_fgr_params* p) {
+    if (!p) return;
+    p->division_factor = 1.4f; p->maximum_correspondence_distance = 0.025f; p->tuple_scale = 0.95f; p->iteration_number = 64;
+    p->maximum_tuple_count = 1000; p->use_absolute_scale = 0; p->decrease_mu = 1; p->tuple_test = 1; p->seed = 42u;
+}
+
+int tdv_fgr(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft, float voxel_size,
+            const tdv_fgr_params* params, tdv_fgr_result* out) {
+    if (!out || !fgr_args_ok(ctx, src, ns, tgt, nt, fs, ft, voxel_size, params)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    if (ns == 0 || nt == 0) { fgr_empty(out); return TDV_OK; }
+    FgrClouds d;
+    TDV_TRY(fgr_upload(ctx, src, ns, tgt, nt, fs, ft, &d));
+    return fgr_run_dev(ctx, d.src, ns, d.tgt, nt, d.fs, d.ft, voxel_size, *params, out, nullptr);
+}
+
+int tdv_fgr_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, float voxel_size,
+                const tdv_fgr_params* params, tdv_fgr_result* out) {
+    if (!out || !fgr_args_ok(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, voxel_size, params)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    if (ns == 0 || nt == 0) { fgr_empty(out); return TDV_OK; }
+    return fgr_run_dev(ctx, d_src, ns, d_tgt, nt, d_fs, d_ft, voxel_size, *params, out, nullptr);
+}
+
+int tdv_fgr_correspondences(tdv_ctx* ctx, const float* src, int ns, const float* tgt, int nt, const float* fs, const float* ft,
+                            const tdv_fgr_params* params, int* out_mutual, int cap_mutual, int* out_tuple, int cap_tuple,
+                            int* n_mutual, int* n_tuple, long long* trials_run) {
+    if (!n_mutual || !n_tuple || !trials_run || cap_mutual < 0 || cap_tuple < 0 || (cap_mutual > 0 && !out_mutual) ||
+        (cap_tuple > 0 && !out_tuple) || !fgr_args_ok(ctx, src, ns, tgt, nt, fs, ft, 1.f, params))
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    *n_mutual = 0; *n_tuple = 0; *trials_run = 0;
+    if (ns == 0 || nt == 0) return TDV_OK;
+    FgrClouds d;
+    TDV_TRY(fgr_upload(ctx, src, ns, tgt, nt, fs, ft, &d));
+    FgrPairs pr;
+    TDV_TRY(fgr_run_dev(ctx, d.src, ns, d.tgt, nt, d.fs, d.ft, 1.f, *params, nullptr, &pr));
+    *n_mutual = pr.n_mutual; *n_tuple = pr.n_tuple; *trials_run = pr.trials_run;
+    if (pr.n_mutual > cap_mutual || pr.n_tuple > cap_tuple) return TDV_ERR_BAD_ARG;
+    TDV_TRY(download(ctx, reinterpret_cast<int2*>(out_mutual), pr.mutual, (size_t)pr.n_mutual));
+    TDV_TRY(download(ctx, reinterpret_cast<int2*>(out_tuple), pr.tuple, (size_t)pr.n_tuple));
+    return finish(ctx);
+}
+
+}  // extern "C"

@@ -45,6 +45,8 @@ static_assert(FPS_T == 1024 && FPS_RMAX == 16, "the owner arithmetic below (j & 
 struct FpsRec { int n_usable, n_selected; float cover_d2; int out_off; };
 // one cloud of a call: rows [in_off, in_off + n) of the arrays, start row, its record
 struct FpsCloud { int in_off, n, start, id; };
+// the outputs of a call (each optional)
+struct FpsOut { int* index = nullptr; float* d2 = nullptr; float* xyz = nullptr; float* attr = nullptr; };
 
 __device__ __forceinline__ bool fps_usable(float x, float y, float z) {       // rule 1 (NaN fails every comparison)
     return fabsf(x) < INFINITY && fabsf(y) < INFINITY && fabsf(z) < INFINITY;
@@ -355,8 +357,6 @@ int fps_launch_grid(tdv_ctx* ctx, const float* d_xyz, FpsCloud c, int k, float4*
 
 int fps_gather_blocks(long long elements) { return (int)std::max(1LL, std::min(64LL, (elements + 255) / 256)); }
 
-}  // namespace
-
 // every argument, before anything is enqueued (include/tdv_hip.h)
 bool fps_args_ok(const tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
                  const tdv_fps_result* result, const float* out_attr) {
@@ -377,12 +377,6 @@ bool fps_batch_args_ok(const tdv_ctx* ctx, const float* d_xyz, const float* d_at
     }
     if (h_off[n_clouds] > 0 && !d_xyz) return false;
     return fps_attr_ok(d_attr, attr_width, d_out_attr);
-}
-
-int fps_begin(tdv_ctx* ctx) {
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    return ws_reset(ctx);
 }
 
 // The whole call on device memory.  h (host entry point): where the device outputs go.
@@ -414,37 +408,27 @@ int fps_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int st
         k_fps_gather_attr<<<dim3(1, fps_gather_blocks((long long)cap * attr_width)), 256, 0, s>>>(c, nullptr, rec, d.index, d_attr, attr_width, d.attr);
         TDV_CHECK_LAUNCH(ctx);
     }
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, rec, sizeof(FpsRec), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
     FpsRec hr;
-    std::memcpy(&hr, ctx->pin, sizeof(hr));
+    TDV_TRY(fetch_state(ctx, rec, &hr));
     result->n_usable = hr.n_usable; result->n_selected = hr.n_selected; result->cover_d2 = hr.cover_d2;
-    // host entry point: the selected rows, n_selected of them (the device arrays hold nothing beyond)
-    const size_t m = (size_t)hr.n_selected;
-    if (h && m > 0 && (h->index || h->d2 || h->xyz || (h->attr && d.attr))) {
-        if (h->index) TDV_HIP(ctx, hipMemcpyAsync(h->index, d.index, m * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (h->d2) TDV_HIP(ctx, hipMemcpyAsync(h->d2, d.d2, m * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (h->xyz) TDV_HIP(ctx, hipMemcpyAsync(h->xyz, d.xyz, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (h->attr && d.attr) TDV_HIP(ctx, hipMemcpyAsync(h->attr, d.attr, m * (size_t)attr_width * sizeof(float), hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return TDV_OK;
+    // host entry point: the selected rows, n_selected of them
+    if (!h) return TDV_OK;
+    return download_rows(ctx, (size_t)hr.n_selected, {{h->index, d.index, sizeof(int)}, {h->d2, d.d2, sizeof(float)},
+                                                      {h->xyz, d.xyz, 3 * sizeof(float)}, {h->attr, d.attr, (size_t)attr_width * sizeof(float)}});
 }
 
 // host arrays: upload, device outputs for what is asked for, fps_run_dev
 int fps_run_host(tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
                  tdv_fps_result* result, const FpsOut& h) {
-    TDV_TRY(fps_begin(ctx));
-    float *d_xyz = nullptr, *d_attr = nullptr;
+    TDV_TRY(call_begin(ctx));
+    float *d_xyz, *d_attr = nullptr;
     FpsOut d;
+    TDV_TRY(upload(ctx, xyz, (size_t)n * 3, &d_xyz));
     if (n > 0) {
-        const size_t n3 = (size_t)n * 3, na = (size_t)n * (size_t)attr_width, cap = (size_t)std::max(std::min(num_samples, n), 1);
-        TDV_TRY(ws_alloc(ctx, n3, &d_xyz));
-        TDV_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (attr && na > 0 && h.attr) {                      // the rows are only ever gathered
-            TDV_TRY(ws_alloc(ctx, na, &d_attr));
-            TDV_HIP(ctx, hipMemcpyAsync(d_attr, attr, na * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            TDV_TRY(ws_alloc(ctx, cap * (size_t)attr_width, &d.attr));
+        const size_t cap = (size_t)std::max(std::min(num_samples, n), 1);
+        if (h.attr) {                                        // the rows are only ever gathered
+            TDV_TRY(upload(ctx, attr, (size_t)n * (size_t)attr_width, &d_attr));
+            if (d_attr) TDV_TRY(ws_alloc(ctx, cap * (size_t)attr_width, &d.attr));
         }
         if (h.index) TDV_TRY(ws_alloc(ctx, cap, &d.index));
         if (h.d2) TDV_TRY(ws_alloc(ctx, cap, &d.d2));
@@ -534,4 +518,37 @@ int fps_batch_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int
     return TDV_OK;
 }
 
+}  // namespace
+
 }  // namespace tdv
+
+using namespace tdv;
+
+extern "C" {
+
+int tdv_farthest_point_down_sample(tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
+                                   tdv_fps_result* result, int* index, float* out_d2, float* out_xyz, float* out_attr) {
+    if (!fps_args_ok(ctx, xyz, n, num_samples, start_index, attr, attr_width, result, out_attr)) return TDV_ERR_BAD_ARG;
+    FpsOut h; h.index = index; h.d2 = out_d2; h.xyz = out_xyz; h.attr = out_attr;
+    return fps_run_host(ctx, xyz, n, num_samples, start_index, attr, attr_width, result, h);
+}
+
+int tdv_farthest_point_down_sample_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int start_index, const float* d_attr,
+                                       int attr_width, tdv_fps_result* result, int* d_index, float* d_out_d2, float* d_out_xyz,
+                                       float* d_out_attr) {
+    if (!fps_args_ok(ctx, d_xyz, n, num_samples, start_index, d_attr, attr_width, result, d_out_attr)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    FpsOut d; d.index = d_index; d.d2 = d_out_d2; d.xyz = d_out_xyz; d.attr = d_out_attr;
+    return fps_run_dev(ctx, d_xyz, n, num_samples, start_index, d_attr, attr_width, result, d, nullptr);
+}
+
+int tdv_farthest_point_down_sample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_offsets,
+                                             int n_clouds, int num_samples, tdv_fps_result* results, int* h_out_offsets, int* d_index,
+                                             float* d_out_d2, float* d_out_xyz, float* d_out_attr) {
+    if (!fps_batch_args_ok(ctx, d_xyz, d_attr, attr_width, h_offsets, n_clouds, num_samples, results, h_out_offsets, d_out_attr)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    FpsOut d; d.index = d_index; d.d2 = d_out_d2; d.xyz = d_out_xyz; d.attr = d_out_attr;
+    return fps_batch_run_dev(ctx, d_xyz, d_attr, attr_width, h_offsets, n_clouds, num_samples, results, h_out_offsets, d);
+}
+
+}  // extern "C"

@@ -248,7 +248,11 @@ __global__ __launch_bounds__(256) void k_iss_count(const int* __restrict__ suppo
 
 bool iss_radius_ok(float r) { return std::isfinite(r) && r >= 0.f; }
 
-}  // namespace
+// the outputs of a call (each optional)
+struct IssOut {
+    uint8_t* mask = nullptr; double* saliency = nullptr; double* eig = nullptr; int* support = nullptr; int* index = nullptr;
+    float* xyz = nullptr; float* attr = nullptr;
+};
 
 // every argument, before anything is enqueued (include/tdv_hip.h)
 bool iss_args_ok(const tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params* p, const float* attr, int attr_width,
@@ -298,50 +302,35 @@ int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& p
     k_iss_nms<<<(n + ISS_WAVES - 1) / ISS_WAVES, 64 * ISS_WAVES, 0, s>>>(sc, st, prm.min_neighbors, d.saliency, flag, d.mask);
     k_iss_count<<<nb, 256, 0, s>>>(d.support, d.saliency, n, prm.min_neighbors, st);
     TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, &st->n_keypoints));
-    if (d.index || d.xyz || d.attr) k_gather_flagged<<<nb, 256, 0, s>>>(flag, pos, d_xyz, d_attr, attr_width, n, d.index, d.xyz, d.attr);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, st, sizeof(IssState), hipMemcpyDeviceToHost, s));
-    if (h && h->mask) TDV_HIP(ctx, hipMemcpyAsync(h->mask, d.mask, (size_t)n, hipMemcpyDeviceToHost, s));
-    if (h && h->saliency) TDV_HIP(ctx, hipMemcpyAsync(h->saliency, d.saliency, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (h && h->eig) TDV_HIP(ctx, hipMemcpyAsync(h->eig, d.eig, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (h && h->support) TDV_HIP(ctx, hipMemcpyAsync(h->support, d.support, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
+    TDV_TRY(compact_flagged(ctx, flag, n, pos, &st->n_keypoints, d_xyz, d_attr, attr_width, d.index, d.xyz, d.attr));
+    if (h) {
+        TDV_TRY(download(ctx, h->mask, d.mask, (size_t)n));
+        TDV_TRY(download(ctx, h->saliency, d.saliency, (size_t)n));
+        TDV_TRY(download(ctx, h->eig, d.eig, (size_t)n * 3));
+        TDV_TRY(download(ctx, h->support, d.support, (size_t)n));
+    }
     IssState hs;
-    std::memcpy(&hs, ctx->pin, sizeof(hs));
+    TDV_TRY(fetch_state(ctx, st, &hs));
     result->n_finite = hs.n_finite; result->n_supported = hs.n_supported; result->n_salient = hs.n_salient; result->n_keypoints = hs.n_keypoints;
     result->salient_radius = hs.salient_radius; result->non_max_radius = hs.non_max_radius; result->resolution = hs.resolution;
-    // host entry point: the keypoints' rows, n_keypoints of them (the device arrays hold nothing beyond)
-    const size_t m = (size_t)hs.n_keypoints;
-    if (h && m > 0 && (h->index || h->xyz || (h->attr && d.attr))) {
-        if (h->index) TDV_HIP(ctx, hipMemcpyAsync(h->index, d.index, m * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (h->xyz) TDV_HIP(ctx, hipMemcpyAsync(h->xyz, d.xyz, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (h->attr && d.attr) TDV_HIP(ctx, hipMemcpyAsync(h->attr, d.attr, m * (size_t)attr_width * sizeof(float), hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return TDV_OK;
-}
-
-int iss_begin(tdv_ctx* ctx) {
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    return ws_reset(ctx);
+    // host entry point: the keypoints' rows, n_keypoints of them
+    if (!h) return TDV_OK;
+    return download_rows(ctx, (size_t)hs.n_keypoints, {{h->index, d.index, sizeof(int)}, {h->xyz, d.xyz, 3 * sizeof(float)},
+                                                       {h->attr, d.attr, (size_t)attr_width * sizeof(float)}});
 }
 
 // host arrays: upload, device outputs for what is asked for, iss_run_dev
 int iss_run_host(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params& prm, const float* attr, int attr_width, tdv_iss_result* result,
                  const IssOut& h) {
-    TDV_TRY(iss_begin(ctx));
-    float *d_xyz = nullptr, *d_attr = nullptr;
+    TDV_TRY(call_begin(ctx));
+    float *d_xyz, *d_attr = nullptr;
     IssOut d;
+    const size_t n3 = (size_t)n * 3, na = (size_t)n * (size_t)attr_width;
+    TDV_TRY(upload(ctx, xyz, n3, &d_xyz));
     if (n > 0) {
-        const size_t n3 = (size_t)n * 3, na = (size_t)n * (size_t)attr_width;
-        TDV_TRY(ws_alloc(ctx, n3, &d_xyz));
-        TDV_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (attr && na > 0 && h.attr) {                      // the rows are only ever gathered
-            TDV_TRY(ws_alloc(ctx, na, &d_attr));
-            TDV_HIP(ctx, hipMemcpyAsync(d_attr, attr, na * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-            TDV_TRY(ws_alloc(ctx, na, &d.attr));
+        if (h.attr) {                                        // the rows are only ever gathered
+            TDV_TRY(upload(ctx, attr, na, &d_attr));
+            if (d_attr) TDV_TRY(ws_alloc(ctx, na, &d.attr));
         }
         if (h.mask) TDV_TRY(ws_alloc(ctx, align_up((size_t)n, 16), &d.mask));
         if (h.saliency) TDV_TRY(ws_alloc(ctx, (size_t)n, &d.saliency));
@@ -353,4 +342,34 @@ int iss_run_host(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params& pr
     return iss_run_dev(ctx, d_xyz, n, prm, d_attr, attr_width, result, d, &h);
 }
 
+}  // namespace
+
 }  // namespace tdv
+
+using namespace tdv;
+
+extern "C" {
+
+void tdv_iss_default_params(tdv_iss_params* p) {
+    if (!p) return;
+    p->salient_radius = 0.f; p->non_max_radius = 0.f; p->gamma_21 = 0.975; p->gamma_32 = 0.975; p->min_neighbors = 5;
+}
+
+int tdv_iss_keypoints(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params* params, const float* attr, int attr_width, tdv_iss_result* result,
+                      uint8_t* mask, double* saliency, double* eigenvalues, int* support, int* index, float* out_xyz, float* out_attr) {
+    if (!iss_args_ok(ctx, xyz, n, params, attr, attr_width, result, out_attr)) return TDV_ERR_BAD_ARG;
+    IssOut h; h.mask = mask; h.saliency = saliency; h.eig = eigenvalues; h.support = support; h.index = index; h.xyz = out_xyz; h.attr = out_attr;
+    return iss_run_host(ctx, xyz, n, *params, attr, attr_width, result, h);
+}
+
+int tdv_iss_keypoints_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params* params, const float* d_attr, int attr_width,
+                          tdv_iss_result* result, uint8_t* d_mask, double* d_saliency, double* d_eigenvalues, int* d_support, int* d_index,
+                          float* d_out_xyz, float* d_out_attr) {
+    if (!iss_args_ok(ctx, d_xyz, n, params, d_attr, attr_width, result, d_out_attr)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    IssOut d; d.mask = d_mask; d.saliency = d_saliency; d.eig = d_eigenvalues; d.support = d_support; d.index = d_index; d.xyz = d_out_xyz;
+    d.attr = d_out_attr;
+    return iss_run_dev(ctx, d_xyz, n, *params, d_attr, attr_width, result, d, nullptr);
+}
+
+}  // extern "C"

@@ -165,12 +165,6 @@ __global__ void k_outlier_init(OutlierState* st) {
     *st = z;
 }
 
-int outlier_begin(tdv_ctx* ctx) {
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    return ws_reset(ctx);
-}
-
 // every argument, before anything is enqueued (include/tdv_hip.h)
 bool outlier_cloud_ok(const tdv_ctx* ctx, const float* xyz, int n, const tdv_outlier_result* result) {
     return ctx && result && n >= 0 && (n == 0 || xyz);
@@ -233,43 +227,32 @@ int outlier_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n,
         k_outlier_count<<<(n + OL_WAVES - 1) / OL_WAVES, 64 * OL_WAVES, 0, s>>>(sc, eps2, nb_points, cap, flag, d.mask, d.count);
     }
     TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(exclusive_scan_dev(ctx, flag, n, pos, &st->n_kept));
-    if (d.index || d.xyz || d.rgb) k_gather_flagged<<<nb, 256, 0, s>>>(flag, pos, d_xyz, d_rgb, 3, n, d.index, d.xyz, d.rgb);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, st, sizeof(OutlierState), hipMemcpyDeviceToHost, s));
-    if (h && h->mask) TDV_HIP(ctx, hipMemcpyAsync(h->mask, d.mask, (size_t)n, hipMemcpyDeviceToHost, s));
-    if (h && h->mean) TDV_HIP(ctx, hipMemcpyAsync(h->mean, d.mean, (size_t)n * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (h && h->count) TDV_HIP(ctx, hipMemcpyAsync(h->count, d.count, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
+    TDV_TRY(compact_flagged(ctx, flag, n, pos, &st->n_kept, d_xyz, d_rgb, 3, d.index, d.xyz, d.rgb));
+    if (h) {
+        TDV_TRY(download(ctx, h->mask, d.mask, (size_t)n));
+        TDV_TRY(download(ctx, h->mean, d.mean, (size_t)n));
+        TDV_TRY(download(ctx, h->count, d.count, (size_t)n));
+    }
     OutlierState hs;
-    std::memcpy(&hs, ctx->pin, sizeof(hs));
+    TDV_TRY(fetch_state(ctx, st, &hs));
     result->n_valid = hs.n_valid; result->n_kept = hs.n_kept;
     if (statistical) { result->cloud_mean = hs.cloud_mean; result->std_dev = hs.std_dev; result->threshold = hs.threshold; }
-    // host entry points: the kept rows, n_kept of them (the device arrays hold nothing beyond)
-    const size_t m = (size_t)hs.n_kept;
-    if (h && m > 0 && (h->index || h->xyz || h->rgb)) {
-        if (h->index) TDV_HIP(ctx, hipMemcpyAsync(h->index, d.index, m * sizeof(int), hipMemcpyDeviceToHost, s));
-        if (h->xyz) TDV_HIP(ctx, hipMemcpyAsync(h->xyz, d.xyz, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        if (h->rgb && d.rgb) TDV_HIP(ctx, hipMemcpyAsync(h->rgb, d.rgb, m * 3 * sizeof(float), hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
-    }
-    return TDV_OK;
+    // host entry points: the kept rows, n_kept of them
+    if (!h) return TDV_OK;
+    return download_rows(ctx, (size_t)hs.n_kept, {{h->index, d.index, sizeof(int)}, {h->xyz, d.xyz, 3 * sizeof(float)},
+                                                  {h->rgb, d.rgb, 3 * sizeof(float)}});
 }
 
 // host arrays: upload, device outputs for what is asked for, outlier_run_dev
 int outlier_run_host(tdv_ctx* ctx, const float* xyz, const float* rgb, int n, int nb_neighbors, double std_ratio, int nb_points, float radius,
                      tdv_outlier_result* result, const OutlierOut& h) {
-    TDV_TRY(outlier_begin(ctx));
-    float *d_xyz = nullptr, *d_rgb = nullptr;
+    TDV_TRY(call_begin(ctx));
+    float *d_xyz, *d_rgb;
     OutlierOut d;
+    const size_t n3 = (size_t)n * 3;
+    TDV_TRY(upload(ctx, xyz, n3, &d_xyz));
+    TDV_TRY(upload(ctx, rgb, n3, &d_rgb));
     if (n > 0) {
-        const size_t n3 = (size_t)n * 3;
-        TDV_TRY(ws_alloc(ctx, n3, &d_xyz));
-        TDV_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (rgb) {
-            TDV_TRY(ws_alloc(ctx, n3, &d_rgb));
-            TDV_HIP(ctx, hipMemcpyAsync(d_rgb, rgb, n3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        }
         if (h.mask) TDV_TRY(ws_alloc(ctx, align_up((size_t)n, 16), &d.mask));
         if (h.mean) TDV_TRY(ws_alloc(ctx, (size_t)n, &d.mean));
         if (h.count) TDV_TRY(ws_alloc(ctx, (size_t)n, &d.count));
@@ -299,7 +282,7 @@ int tdv_remove_statistical_outlier_dev(tdv_ctx* ctx, const float* d_xyz, const f
                                        tdv_outlier_result* result, uint8_t* d_mask, double* d_mean, int* d_index, float* d_out_xyz,
                                        float* d_out_rgb) {
     if (!statistical_args_ok(ctx, d_xyz, n, nb_neighbors, std_ratio, result)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(outlier_begin(ctx));
+    TDV_TRY(call_begin(ctx));
     OutlierOut d; d.mask = d_mask; d.mean = d_mean; d.index = d_index; d.xyz = d_out_xyz; d.rgb = d_out_rgb;
     return outlier_run_dev(ctx, d_xyz, d_rgb, n, nb_neighbors, std_ratio, 0, 0.f, result, d, nullptr);
 }
@@ -314,7 +297,7 @@ int tdv_remove_radius_outlier(tdv_ctx* ctx, const float* xyz, const float* rgb, 
 int tdv_remove_radius_outlier_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, int nb_points, float radius,
                                   tdv_outlier_result* result, uint8_t* d_mask, int* d_count, int* d_index, float* d_out_xyz, float* d_out_rgb) {
     if (!radius_args_ok(ctx, d_xyz, n, nb_points, radius, result)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(outlier_begin(ctx));
+    TDV_TRY(call_begin(ctx));
     OutlierOut d; d.mask = d_mask; d.count = d_count; d.index = d_index; d.xyz = d_out_xyz; d.rgb = d_out_rgb;
     return outlier_run_dev(ctx, d_xyz, d_rgb, n, 0, 0.0, nb_points, radius, result, d, nullptr);
 }

@@ -338,12 +338,6 @@ __global__ __launch_bounds__(256) void k_plane_compact(const int* __restrict__ k
     if (out_idx) out_idx[o] = in_idx ? in_idx[j] : j;
 }
 
-int plane_begin(tdv_ctx* ctx) {
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    return ws_reset(ctx);
-}
-
 // every argument, before anything is enqueued (include/tdv_hip.h: tdv_segment_planes)
 bool plane_args_ok(const tdv_ctx* ctx, const float* xyz, int n, const tdv_plane_params* p, const tdv_plane_result* out, const int* n_planes) {
     if (!ctx || !p || !out || !n_planes || n < 0 || (n > 0 && !xyz)) return false;
@@ -359,8 +353,8 @@ int plane_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_plane_param
     if (d_labels && n > 0) TDV_HIP(ctx, hipMemsetAsync(d_labels, 0xFF, (size_t)n * sizeof(int), s));   // -1
     if (n < 3) {
         if (d_rest && n > 0) TDV_HIP(ctx, hipMemcpyAsync(d_rest, d_xyz, (size_t)n * 3 * sizeof(float), hipMemcpyDeviceToDevice, s));
-        if (h_labels && n > 0) TDV_HIP(ctx, hipMemcpyAsync(h_labels, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-        TDV_HIP(ctx, hipStreamSynchronize(s));
+        TDV_TRY(download(ctx, h_labels, d_labels, (size_t)n));
+        TDV_TRY(finish(ctx));
         *n_planes = 0;
         if (n_rest) *n_rest = n;
         return TDV_OK;
@@ -417,8 +411,8 @@ int plane_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_plane_param
         TDV_CHECK_LAUNCH(ctx);
     }
     TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, blk, rec_bytes, hipMemcpyDeviceToHost, s));
-    if (h_labels) TDV_HIP(ctx, hipMemcpyAsync(h_labels, d_labels, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
+    TDV_TRY(download(ctx, h_labels, d_labels, (size_t)n));
+    TDV_TRY(finish(ctx));
     PlaneState hs;
     std::memcpy(&hs, ctx->pin, sizeof(hs));
     std::memcpy(out, ctx->pin + sizeof(PlaneState), (size_t)hs.n_planes * sizeof(tdv_plane_result));
@@ -448,21 +442,18 @@ void tdv_plane_default_params(tdv_plane_params* p) {
 int tdv_segment_planes(tdv_ctx* ctx, const float* xyz, int n, const tdv_plane_params* params, tdv_plane_result* out, int* n_planes,
                        int* labels) {
     if (!plane_args_ok(ctx, xyz, n, params, out, n_planes)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(plane_begin(ctx));
-    float* d_xyz = nullptr;
+    TDV_TRY(call_begin(ctx));
+    float* d_xyz;
     int* d_labels = nullptr;
-    if (n > 0) {
-        TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &d_xyz));
-        TDV_HIP(ctx, hipMemcpyAsync(d_xyz, xyz, (size_t)n * 3 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-        if (labels) TDV_TRY(ws_alloc(ctx, (size_t)n, &d_labels));
-    }
+    TDV_TRY(upload(ctx, xyz, (size_t)n * 3, &d_xyz));
+    if (labels && n > 0) TDV_TRY(ws_alloc(ctx, (size_t)n, &d_labels));
     return plane_run_dev(ctx, d_xyz, n, *params, out, n_planes, d_labels, nullptr, nullptr, labels);
 }
 
 int tdv_segment_planes_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_plane_params* params, tdv_plane_result* out, int* n_planes,
                            int* d_labels, float* d_rest_xyz, int* n_rest) {
     if (!plane_args_ok(ctx, d_xyz, n, params, out, n_planes)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(plane_begin(ctx));
+    TDV_TRY(call_begin(ctx));
     return plane_run_dev(ctx, d_xyz, n, *params, out, n_planes, d_labels, d_rest_xyz, n_rest, nullptr);
 }
 

@@ -373,6 +373,9 @@ bool ppf_within(const Pose64& a, const Pose64& b, double max_t, double min_c) {
 
 struct PpfCluster { int founder; long long votes; int members; };
 
+// what the parameters alone fix (ppf_plan): n_dist, n_keys and the table's layout for nt points
+struct PpfPlan { int n_dist, n_keys; size_t off_words, cap, bytes; };
+
 PpfQuant ppf_quant(const tdv_ppf_params& prm, const PpfPlan& plan, float step) {
     PpfQuant q;
     q.step = step; q.astep = PPF_PI / (float)prm.angle_bins; q.rstep = PPF_TWO_PI / (float)prm.rotation_bins;
@@ -459,9 +462,7 @@ void ppf_score(tdv_ppf_pose* o, const char* d2, const uint8_t* accepted, int ns,
     o->rmse = n_corr > 0 ? (float)std::sqrt(S / (double)n_corr) : 0.f;
 }
 
-}  // namespace
-
-// every parameter (include/tdv_hip.h), and what they fix
+// every parameter (include/tdv_hip.h), and what they fix: the parameter check of every entry point
 bool ppf_plan(const tdv_ppf_params* p, int nt, PpfPlan* plan) {
     if (!p || nt < 0 || nt > TDV_PPF_MODEL_MAX) return false;
     if (!(p->distance_step_relative > 0.f) || !(p->distance_step_relative <= 1.f)) return false;
@@ -661,5 +662,104 @@ int ppf_match_batch_run(tdv_ctx* ctx, const float* d_src, const float* d_src_nor
     return TDV_OK;
 }
 
+// every argument of a match, before anything is enqueued (include/tdv_hip.h: tdv_ppf_match)
+bool ppf_match_args_ok(const tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt,
+                       float thr, const tdv_ppf_params* params, const tdv_ppf_pose* out_poses, const int* n_poses, PpfPlan* plan) {
+    if (!ctx || !out_poses || !n_poses || ns < 0 || !ppf_plan(params, nt, plan)) return false;
+    if (ns > 0 && (!src || !src_normals)) return false;
+    if (nt > 0 && (!tgt || !tgt_normals)) return false;
+    return std::isfinite(thr) && thr > 0.f;
+}
+bool ppf_model_ptr_ok(const void* d_model) { return d_model && (reinterpret_cast<uintptr_t>(d_model) & 3) == 0; }
+// ... and the table with its info (tdv_ppf_match_dev, tdv_ppf_match_batch_dev)
+bool ppf_model_info_ok(const void* d_model, const tdv_ppf_model_info* info, int nt, const PpfPlan& plan) {
+    return info && ppf_model_ptr_ok(d_model) && info->nt == nt && info->n_keys == plan.n_keys && info->n_pairs >= 0 &&
+           (size_t)info->n_pairs <= plan.cap && std::isfinite(info->diameter) && info->diameter >= 0.f && std::isfinite(info->distance_step) &&
+           info->distance_step >= 0.f;
+}
+
+}  // namespace
+
 }  // namespace tdv
 
+using namespace tdv;
+
+extern "C" {
+
+void tdv_ppf_default_params(tdv_ppf_params* p) {
+    if (!p) return;
+    p->distance_step_relative = 0.05f; p->angle_bins = 30; p->rotation_bins = 30; p->ref_stride = 5; p->max_poses = 8;
+    p->cluster_translation_relative = 0.1f; p->cluster_rotation = (float)(2.0 * 3.141592653589793 / 30.0); p->flip_model_normals = 0;
+}
+
+int tdv_ppf_model_bytes(int nt, const tdv_ppf_params* params, size_t* bytes) {
+    PpfPlan plan;
+    if (!bytes || !ppf_plan(params, nt, &plan)) return TDV_ERR_BAD_ARG;
+    *bytes = plan.bytes;
+    return TDV_OK;
+}
+
+int tdv_ppf_model_dev(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params* params, void* d_model,
+                      size_t model_bytes, tdv_ppf_model_info* info) {
+    PpfPlan plan;
+    if (!ctx || !info || !ppf_plan(params, nt, &plan) || (nt > 0 && (!d_tgt || !d_tgt_normals)) || !ppf_model_ptr_ok(d_model) ||
+        model_bytes < plan.bytes)
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    return ppf_model_run(ctx, d_tgt, d_tgt_normals, nt, *params, plan, d_model, info);
+}
+
+int tdv_ppf_match_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
+                      const void* d_model, const tdv_ppf_model_info* info, float thr, const tdv_ppf_params* params, tdv_ppf_pose* out_poses,
+                      int* n_poses, tdv_ppf_peak* d_peaks, int* n_ref) {
+    PpfPlan plan;
+    if (!ppf_match_args_ok(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
+    if (!ppf_model_info_ok(d_model, info, nt, plan)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    return ppf_match_run(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, d_model, *info, thr, *params, plan, out_poses, n_poses, d_peaks,
+                         nullptr, n_ref);
+}
+
+int tdv_ppf_match_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances, const float* d_tgt,
+                            const float* d_tgt_normals, int nt, const void* d_model, const tdv_ppf_model_info* info, float thr,
+                            const tdv_ppf_params* params, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks, int* h_peak_offsets) {
+    PpfPlan plan;
+    if (n_instances < 0 || (n_instances > 0 && !h_src_offsets)) return TDV_ERR_BAD_ARG;
+    if (n_instances > 0 && h_src_offsets[0] != 0) return TDV_ERR_BAD_ARG;
+    for (int b = 0; b < n_instances; ++b)
+        if (h_src_offsets[b + 1] < h_src_offsets[b]) return TDV_ERR_BAD_ARG;
+    const int ns = n_instances > 0 ? h_src_offsets[n_instances] : 0;
+    if (!ppf_match_args_ok(ctx, d_src, d_src_normals, ns, d_tgt, d_tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
+    if (!ppf_model_info_ok(d_model, info, nt, plan)) return TDV_ERR_BAD_ARG;
+    if ((long long)n_instances * params->max_poses > INT_MAX) return TDV_ERR_BAD_ARG;
+    std::vector<int> ref_off((size_t)n_instances + 1, 0);            // rule 5's n_ref per instance, summed
+    long long sum = 0;
+    for (int b = 0; b < n_instances; ++b) {
+        const long long n = h_src_offsets[b + 1] - h_src_offsets[b];
+        sum += (n + params->ref_stride - 1) / params->ref_stride;
+        if (sum > INT_MAX) return TDV_ERR_BAD_ARG;
+        ref_off[(size_t)b + 1] = (int)sum;
+    }
+    TDV_TRY(call_begin(ctx));
+    return ppf_match_batch_run(ctx, d_src, d_src_normals, h_src_offsets, ref_off.data(), n_instances, d_tgt, d_tgt_normals, nt, d_model, *info, thr,
+                               *params, plan, out_poses, n_poses, d_peaks, h_peak_offsets);
+}
+
+int tdv_ppf_match(tdv_ctx* ctx, const float* src, const float* src_normals, int ns, const float* tgt, const float* tgt_normals, int nt, float thr,
+                  const tdv_ppf_params* params, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* peaks, int* n_ref) {
+    PpfPlan plan;
+    if (!ppf_match_args_ok(ctx, src, src_normals, ns, tgt, tgt_normals, nt, thr, params, out_poses, n_poses, &plan)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    float *d_src, *d_sn, *d_tgt, *d_tn;
+    TDV_TRY(upload(ctx, src, (size_t)ns * 3, &d_src));
+    TDV_TRY(upload(ctx, src_normals, (size_t)ns * 3, &d_sn));
+    TDV_TRY(upload(ctx, tgt, (size_t)nt * 3, &d_tgt));
+    TDV_TRY(upload(ctx, tgt_normals, (size_t)nt * 3, &d_tn));
+    void* d_model;
+    TDV_TRY(ws_alloc_bytes(ctx, plan.bytes, &d_model));
+    tdv_ppf_model_info info;
+    TDV_TRY(ppf_model_run(ctx, d_tgt, d_tn, nt, *params, plan, d_model, &info));
+    return ppf_match_run(ctx, d_src, d_sn, ns, d_tgt, d_tn, nt, d_model, info, thr, *params, plan, out_poses, n_poses, nullptr, peaks, n_ref);
+}
+
+}  // extern "C"

@@ -38,8 +38,8 @@ extern "C" int tdv_study_probe(tdv_ctx* ctx, int op, long long n, const float* d
 //   1 sort_records      sort_records_dev(out0, n), in place            -                 -            -               uint4[n]          -                -                    -
 //   2 segment_sort      segment_sort_records_dev(out0, in0, n)         int[n + 1] starts -            -               uint4[width]      -                -                    -
 //                       n segments of a buffer of `width` records
-//   3 compact           exclusive_scan_dev(in0, n, pos, out3), then    int[n] flags      float[3n]    float[width n]  int[n] index      float[3n] rows   float[width n] rows  int[1] kept
-//                       k_gather_flagged: the tail of outlier and ISS  (0 / 1)           xyz, opt.    attr, optional  optional          opt., needs in1  opt., needs in2      optional
+//   3 compact           compact_flagged: exclusive_scan_dev(in0, n,    int[n] flags      float[3n]    float[width n]  int[n] index      float[3n] rows   float[width n] rows  int[1] kept
+//                       pos, out3), k_gather_flagged: outlier, ISS     (0 / 1)           xyz, opt.    attr, optional  optional          opt., needs in1  opt., needs in2      optional
 //   4 tree_sum          part[width b + a] = tree_block_sum of terms    double[n, width]  -            -               double[nb, width] double[width]    -                    -
 //                       [256 b .. 256 b + 255][a]; then out1[a] =                                                     part
 //                       tree_partials_sum(part, nb, lds4, width, a)
@@ -179,9 +179,7 @@ extern "C" int tdv_study_primitive(tdv_ctx* ctx, int op, long long n, long long 
         case 5: if (!in0 || !out0 || !out1) return TDV_ERR_BAD_ARG; break;
         default: if (!in0 || !out0) return TDV_ERR_BAD_ARG;
     }
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    TDV_TRY(ws_reset(ctx));
+    TDV_TRY(call_begin(ctx));
     hipStream_t s = ctx->stream;
     const int ni = (int)n, nb = (ni + 255) / 256;
     switch (op) {
@@ -202,12 +200,8 @@ extern "C" int tdv_study_primitive(tdv_ctx* ctx, int op, long long n, long long 
             int *pos, *kept = static_cast<int*>(out3);
             TDV_TRY(ws_alloc(ctx, (size_t)n, &pos));
             if (!kept) TDV_TRY(ws_alloc(ctx, 1, &kept));
-            const int* flag = static_cast<const int*>(in0);
-            TDV_TRY(exclusive_scan_dev(ctx, flag, ni, pos, kept));
-            if (out0 || out1 || out2)
-                k_gather_flagged<<<nb, 256, 0, s>>>(flag, pos, static_cast<const float*>(in1), static_cast<const float*>(in2), (int)width, ni,
-                                                    static_cast<int*>(out0), static_cast<float*>(out1), static_cast<float*>(out2));
-            TDV_CHECK_LAUNCH(ctx);
+            TDV_TRY(compact_flagged(ctx, static_cast<const int*>(in0), ni, pos, kept, static_cast<const float*>(in1), static_cast<const float*>(in2),
+                                    (int)width, static_cast<int*>(out0), static_cast<float*>(out1), static_cast<float*>(out2)));
             break;
         }
         case 4:
@@ -233,9 +227,7 @@ extern "C" int tdv_study_probe(tdv_ctx* ctx, int op, long long n, const float* d
     if (!ctx || op < 0 || op > 10 || n < 0 || n > (1ll << 31) - 256) return TDV_ERR_BAD_ARG;
     if (n == 0) return TDV_OK;
     if (!d_in || !d_out) return TDV_ERR_BAD_ARG;
-    TDV_HIP(ctx, hipSetDevice(ctx->device));
-    ctx->err[0] = 0;
-    TDV_TRY(ws_reset(ctx));
+    TDV_TRY(call_begin(ctx));
     switch (op) {
         case 0: TDV_TRY(launch<0>(ctx, n, d_in, d_out)); break;
         case 1: TDV_TRY(launch<1>(ctx, n, d_in, d_out)); break;

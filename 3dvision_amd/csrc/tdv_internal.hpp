@@ -224,11 +224,6 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
 // the f64 tree sum of (double)(err * err) over the inliers (sqrtf(d2) < 1.5 voxel) of the matches d_corr and the inlier count
 int ransac_score_pose_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const int* d_corr, const float* d_hyp12,
                           float voxel, double* d_out2);
-// Fast Global Registration (fgr.hip, include/tdv_hip.h: tdv_fgr).  want_pairs: stop after the tuple test and leave the device pair lists
-// in *pairs (mutual pairs as int2 at [0], tuple pairs at [1]) - for tdv_fgr_correspondences
-struct FgrPairs { const int2* mutual = nullptr; const int2* tuple = nullptr; int n_mutual = 0, n_tuple = 0; long long trials_run = 0; };
-int fgr_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, int nt, const float* d_fs, const float* d_ft, float voxel,
-                const tdv_fgr_params& prm, tdv_fgr_result* out, FgrPairs* pairs);
 // ransac_run_dev for many small clouds against one target in a handful of launches (ransac.hip): cloud b = points
 // [h_off[b], h_off[b+1]) of d_src with correspondences d_corr (same indexing); out[b].rmse is NOT evaluated (0).  *fell_back = 1:
 // nothing was computed (a cloud too large, too many hypotheses, or the index sampler ran out of draws) - use ransac_run_dev.
@@ -271,7 +266,6 @@ int depth_to_cloud_batch_emit(tdv_ctx* ctx, const uint16_t* d_raw, const int* d_
                               const int* d_offsets, float* d_xyz, float* d_rgb);
 // `stacked` above: 1 = one u8 mask per instance, 0 = one u8 label image (label = instance + 1), 2 = one u16 label image
 int mask_resize_nearest_dev(tdv_ctx* ctx, const uint8_t* d_src, int n_masks, int sw, int sh, int dw, int dh, uint8_t* d_dst);
-void resize_nn_tables(int sw, int sh, int dw, int dh, int* x_ofs, int* y_ofs);
 int depth_batch_nonzero_any(tdv_ctx* ctx, const uint16_t* d_raw, const int* d_frame_of, const uint8_t* d_masks, int layout, int w, int h, float scale,
                             int mask_mode, const int* h_inst, int n_list, int* h_flags);
 int estimate_normals_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float* d_normals, int* d_knn);
@@ -324,71 +318,6 @@ struct SortedCloud {
 };
 int spatial_sort_cloud(tdv_ctx* ctx, const float* d_xyz, int n, SortedCloud& out);
 
-// ISS keypoints (iss.hip, include/tdv_hip.h: tdv_iss_keypoints): the outputs of a call (each optional), the argument check of both entry
-// points, and the call on host arrays resp. on device pointers (h: where a host call's device outputs go; iss_begin resets the workspace)
-struct IssOut {
-    uint8_t* mask = nullptr; double* saliency = nullptr; double* eig = nullptr; int* support = nullptr; int* index = nullptr;
-    float* xyz = nullptr; float* attr = nullptr;
-};
-bool iss_args_ok(const tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params* p, const float* attr, int attr_width,
-                 const tdv_iss_result* result, const float* out_attr);
-int iss_begin(tdv_ctx* ctx);
-int iss_run_host(tdv_ctx* ctx, const float* xyz, int n, const tdv_iss_params& prm, const float* attr, int attr_width, tdv_iss_result* result,
-                 const IssOut& h);
-int iss_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, const tdv_iss_params& prm, const float* d_attr, int attr_width, tdv_iss_result* result,
-                IssOut d, const IssOut* h);
-
-// Farthest point sampling (fps.hip, include/tdv_hip.h: tdv_farthest_point_down_sample): the outputs of a call (each optional), the
-// argument checks, and the calls.  fps_run_host resets the workspace itself; the entry points of the other two call fps_begin first.
-// fps_batch_run_dev: the clouds [h_off[b], h_off[b + 1]) of d_xyz, each from its row 0; per cloud fps_run_dev's bytes.
-struct FpsOut { int* index = nullptr; float* d2 = nullptr; float* xyz = nullptr; float* attr = nullptr; };
-bool fps_args_ok(const tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
-                 const tdv_fps_result* result, const float* out_attr);
-bool fps_batch_args_ok(const tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_off, int n_clouds,
-                       int num_samples, const tdv_fps_result* results, const int* h_out_off, const float* d_out_attr);
-int fps_begin(tdv_ctx* ctx);
-int fps_run_host(tdv_ctx* ctx, const float* xyz, int n, int num_samples, int start_index, const float* attr, int attr_width,
-                 tdv_fps_result* result, const FpsOut& h);
-int fps_run_dev(tdv_ctx* ctx, const float* d_xyz, int n, int num_samples, int start_index, const float* d_attr, int attr_width,
-                tdv_fps_result* result, FpsOut d, const FpsOut* h);
-int fps_batch_run_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_attr, int attr_width, const int* h_off, int n_clouds, int num_samples,
-                      tdv_fps_result* results, int* h_out_off, FpsOut d);
-
-// Pose verification (verify.hip, include/tdv_hip.h: tdv_verify_poses): the argument check of the four entry points (frame: the raw frame
-// resp. the depth output; results: what receives the per-pose output) and the two calls on device pointers.  Neither resets the workspace:
-// the entry point did.  Both read back once.
-bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
-                    float scale, float fx, float fy, const tdv_verify_params* p, const void* results);
-int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, int w, int h,
-                   float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& prm, tdv_verify_result* results, int* order);
-int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_pose, int w, int h, float fx, float fy, float cx, float cy,
-                         const tdv_verify_params& prm, float* d_out, int* n_rendered);
-
-// Pose verification from a mesh (verify_mesh.hip, include/tdv_hip.h: tdv_verify_poses_mesh): as the three above, for the mesh renderer.
-bool mesh_verify_args_ok(const tdv_ctx* ctx, const float* vtx, int nv, const int* tri, int nt, const float* poses, int n_poses, const void* frame,
-                         int w, int h, float scale, float fx, float fy, const tdv_mesh_verify_params* p, const void* results);
-int mesh_verify_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_poses, int n_poses,
-                        const uint16_t* d_raw, int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params& prm,
-                        tdv_verify_result* results, int* order);
-int mesh_render_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_pose, int w, int h, float fx, float fy,
-                        float cx, float cy, const tdv_mesh_verify_params& prm, float* d_out, int* n_rendered);
-
-// PPF matching (ppf.hip, include/tdv_hip.h: tdv_ppf_match).  PpfPlan: what the parameters alone fix (n_dist, n_keys, the table's layout for
-// nt points); ppf_plan is the parameter check of every entry point.  ppf_model_run builds the table (rule 4) into d_model and fills info;
-// ppf_match_run votes, clusters and scores (h_peaks: where a host call's peaks go); ppf_match_batch_run is it per instance of an offsets
-// batch (h_ref_off: the reference offsets the entry point formed from h_src_off and checked).  None resets the workspace: the entry point did.
-struct PpfPlan { int n_dist, n_keys; size_t off_words, cap, bytes; };
-bool ppf_plan(const tdv_ppf_params* p, int nt, PpfPlan* plan);
-int ppf_model_run(tdv_ctx* ctx, const float* d_tgt, const float* d_tgt_normals, int nt, const tdv_ppf_params& prm, const PpfPlan& plan,
-                  void* d_model, tdv_ppf_model_info* info);
-int ppf_match_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt, const float* d_tgt_normals, int nt,
-                  const void* d_model, const tdv_ppf_model_info& info, float thr, const tdv_ppf_params& prm, const PpfPlan& plan,
-                  tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks, tdv_ppf_peak* h_peaks, int* n_ref);
-int ppf_match_batch_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_off, const int* h_ref_off, int n_inst,
-                        const float* d_tgt, const float* d_tgt_normals, int nt, const void* d_model, const tdv_ppf_model_info& info, float thr,
-                        const tdv_ppf_params& prm, const PpfPlan& plan, tdv_ppf_pose* out_poses, int* n_poses, tdv_ppf_peak* d_peaks,
-                        int* h_peak_off);
-
 // normals + FPFH in one go, sharing one spatial sort and one radius scan (batch path; identical results)
 // d_tie_ids / d_tie_ids_inv (optional, both or neither): neighbour lists are ordered by (d2, d_tie_ids[index]) instead of
 // (d2, index) — the results are those of the cloud permuted so that point i sits at position d_tie_ids[i]
@@ -398,13 +327,6 @@ int normals_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float radiu
 // the same for many small clouds stored back to back, in one set of launches (knn.hip); tie ids / their inverse are GLOBAL here
 int normals_fpfh_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_voff, const int* d_voff, int n_clouds, int k, float radius,
                            float* d_normals, float* d_desc, const int* d_tie_ids = nullptr, const int* d_tie_ids_inv = nullptr);
-
-// tdv_refine_batch_dev: register_batch_dev's clouds and voxels, then ICP of every instance from h_T0 + 16 b (batch.hip)
-int refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, int n_instances, const tdv_batch_params* prm, const float* h_T0,
-                     const float* d_model_xyz, const float* d_model_normals, int n_model, tdv_instance_result* results);
-int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr, const uint8_t* d_masks, int n_instances,
-                       const tdv_batch_params* prm, const float* d_model_xyz, const float* d_model_normals,
-                       const float* d_model_fpfh, int n_model, tdv_instance_result* results);
 
 // A RANSAC index triple in one 64-bit word, for clouds of at most 2^21 points: i0 in bits 0..20, i1 in 21..41, i2 in 42..62, bit 63 =
 // valid (the three indices differ, registration.cpp:240).  A batch is uploaded in this form where the cloud allows it, as int4
@@ -429,7 +351,6 @@ struct TriView {
 };
 
 // host helpers
-void mt19937_lemire_triples(uint32_t seed, uint64_t n, int count, uint64_t* out);
 void mt19937_raw(uint32_t seed, size_t count, uint32_t* out);
 // the same index stream, drawn incrementally (one (i0, i1, i2) triple per call) so that it can be produced batch by
 // batch while the GPU scores the previous batch
@@ -453,3 +374,5 @@ float tau_le(float thr);
 float tau_lt(float thr);
 
 }  // namespace tdv
+
+#include "entry.hpp"   // the frame of a public call: call_begin, upload / download, fetch_state, download_rows

@@ -191,7 +191,10 @@ bool verify_common_args_ok(const tdv_ctx* ctx, const float* poses, int n_poses, 
     return positive_finite(scale) && positive_finite(fx) && positive_finite(fy);
 }
 
-// every argument, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth output
+namespace {
+
+// every argument of the four entry points, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth
+// output; results: what receives the per-pose output
 bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
                     float scale, float fx, float fy, const tdv_verify_params* p, const void* results) {
     if (!p || n_model < 0 || n_model > TDV_VERIFY_MAX_MODEL || (n_model > 0 && !model)) return false;
@@ -222,4 +225,55 @@ int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const 
     return TDV_OK;
 }
 
+}  // namespace
+
 }  // namespace tdv
+
+using namespace tdv;
+
+extern "C" {
+
+void tdv_verify_default_params(tdv_verify_params* p) {
+    if (!p) return;
+    p->pose_direction = TDV_POSE_SOURCE_ONTO_TARGET; p->splat = 1; p->tau = 0.002f; p->zmax = 10.f;
+}
+
+int tdv_verify_poses_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw_depth, int width,
+                         int height, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params* params,
+                         tdv_verify_result* h_results, int* h_order) {
+    if (!verify_args_ok(ctx, d_model_xyz, n_model, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy, params, h_results)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    return verify_run_dev(ctx, d_model_xyz, n_model, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy, cx, cy, *params, h_results, h_order);
+}
+
+int tdv_verify_poses(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* poses, int n_poses, const uint16_t* raw_depth, int width,
+                     int height, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params* params, tdv_verify_result* results,
+                     int* order) {
+    if (!verify_args_ok(ctx, model_xyz, n_model, poses, n_poses, raw_depth, width, height, scale, fx, fy, params, results)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    float* d_model; uint16_t* d_raw;
+    TDV_TRY(upload(ctx, model_xyz, (size_t)n_model * 3, &d_model));
+    TDV_TRY(upload(ctx, raw_depth, (size_t)width * height, &d_raw));
+    return verify_run_dev(ctx, d_model, n_model, poses, n_poses, d_raw, width, height, scale, fx, fy, cx, cy, *params, results, order);
+}
+
+int tdv_render_depth_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, const float* h_pose, int width, int height, float fx, float fy, float cx,
+                         float cy, const tdv_verify_params* params, float* d_out_depth, int* n_rendered) {
+    if (!verify_args_ok(ctx, d_model_xyz, n_model, h_pose, 1, d_out_depth, width, height, 1.f, fx, fy, params, h_pose)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    return render_depth_run_dev(ctx, d_model_xyz, n_model, h_pose, width, height, fx, fy, cx, cy, *params, d_out_depth, n_rendered);
+}
+
+int tdv_render_depth(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* pose, int width, int height, float fx, float fy, float cx, float cy,
+                     const tdv_verify_params* params, float* out_depth, int* n_rendered) {
+    if (!verify_args_ok(ctx, model_xyz, n_model, pose, 1, out_depth, width, height, 1.f, fx, fy, params, pose)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    float *d_model, *d_out;
+    TDV_TRY(upload(ctx, model_xyz, (size_t)n_model * 3, &d_model));
+    TDV_TRY(ws_alloc(ctx, (size_t)width * height, &d_out));
+    TDV_TRY(render_depth_run_dev(ctx, d_model, n_model, pose, width, height, fx, fy, cx, cy, *params, d_out, n_rendered));
+    TDV_TRY(download(ctx, out_depth, d_out, (size_t)width * height));
+    return finish(ctx);
+}
+
+}  // extern "C"

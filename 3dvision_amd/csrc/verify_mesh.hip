@@ -200,9 +200,8 @@ int mesh_enqueue(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int
     return verify_fetch(ctx, *st, n_poses);
 }
 
-}  // namespace
-
-// every argument, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth output
+// every argument of the four entry points, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth
+// output; results: what receives the per-pose output
 bool mesh_verify_args_ok(const tdv_ctx* ctx, const float* vtx, int nv, const int* tri, int nt, const float* poses, int n_poses, const void* frame,
                          int w, int h, float scale, float fx, float fy, const tdv_mesh_verify_params* p, const void* results) {
     if (!p || nv < 0 || nv > TDV_MESH_MAX_VERTICES || nt < 0 || nt > TDV_MESH_MAX_TRIANGLES) return false;
@@ -235,4 +234,69 @@ int mesh_render_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_t
     return TDV_OK;
 }
 
+}  // namespace
+
 }  // namespace tdv
+
+using namespace tdv;
+
+extern "C" {
+
+void tdv_mesh_verify_default_params(tdv_mesh_verify_params* p) {
+    if (!p) return;
+    p->pose_direction = TDV_POSE_SOURCE_ONTO_TARGET; p->cull = TDV_MESH_CULL_NONE; p->tau = 0.002f; p->zmax = 10.f;
+}
+
+int tdv_verify_poses_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles, const float* h_poses,
+                              int n_poses, const uint16_t* d_raw_depth, int width, int height, float scale, float fx, float fy, float cx, float cy,
+                              const tdv_mesh_verify_params* params, tdv_verify_result* h_results, int* h_order) {
+    if (!mesh_verify_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy,
+                             params, h_results))
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    return mesh_verify_run_dev(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy, cx,
+                               cy, *params, h_results, h_order);
+}
+
+int tdv_verify_poses_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* poses, int n_poses,
+                          const uint16_t* raw_depth, int width, int height, float scale, float fx, float fy, float cx, float cy,
+                          const tdv_mesh_verify_params* params, tdv_verify_result* results, int* order) {
+    if (!mesh_verify_args_ok(ctx, vertices, n_vertices, triangles, n_triangles, poses, n_poses, raw_depth, width, height, scale, fx, fy, params,
+                             results))
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    float* d_vtx; int* d_tri; uint16_t* d_raw;
+    TDV_TRY(upload(ctx, vertices, (size_t)n_vertices * 3, &d_vtx));
+    TDV_TRY(upload(ctx, triangles, (size_t)n_triangles * 3, &d_tri));
+    TDV_TRY(upload(ctx, raw_depth, (size_t)width * height, &d_raw));
+    return mesh_verify_run_dev(ctx, d_vtx, n_vertices, d_tri, n_triangles, poses, n_poses, d_raw, width, height, scale, fx, fy, cx, cy, *params,
+                               results, order);
+}
+
+int tdv_render_depth_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles, const float* h_pose,
+                              int width, int height, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params,
+                              float* d_out_depth, int* n_rendered) {
+    if (!mesh_verify_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_pose, 1, d_out_depth, width, height, 1.f, fx, fy, params,
+                             h_pose))
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    return mesh_render_run_dev(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_pose, width, height, fx, fy, cx, cy, *params, d_out_depth,
+                               n_rendered);
+}
+
+int tdv_render_depth_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* pose, int width,
+                          int height, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params, float* out_depth,
+                          int* n_rendered) {
+    if (!mesh_verify_args_ok(ctx, vertices, n_vertices, triangles, n_triangles, pose, 1, out_depth, width, height, 1.f, fx, fy, params, pose))
+        return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    float *d_vtx, *d_out; int* d_tri;
+    TDV_TRY(upload(ctx, vertices, (size_t)n_vertices * 3, &d_vtx));
+    TDV_TRY(upload(ctx, triangles, (size_t)n_triangles * 3, &d_tri));
+    TDV_TRY(ws_alloc(ctx, (size_t)width * height, &d_out));
+    TDV_TRY(mesh_render_run_dev(ctx, d_vtx, n_vertices, d_tri, n_triangles, pose, width, height, fx, fy, cx, cy, *params, d_out, n_rendered));
+    TDV_TRY(download(ctx, out_depth, d_out, (size_t)width * height));
+    return finish(ctx);
+}
+
+}  // extern "C"
