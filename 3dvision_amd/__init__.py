@@ -68,6 +68,7 @@ ABI_SYMBOLS = [
     "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path", "tdv_ctx_set_icp_launches", "tdv_ctx_last_icp_launches",
     "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
     "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
+    "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
 ]
 
 
@@ -264,6 +265,31 @@ def _mesh(vertices, triangles):
     return _f32(vertices).reshape(-1, 3), np.ascontiguousarray(triangles, dtype=np.int32).reshape(-1, 3)
 
 
+TDV_MESH_SAMPLE_MAX = 1 << 24
+
+
+class MeshSampleParamsC(C.Structure):
+    _fields_ = [("seed", C.c_uint32), ("first_sample", C.c_uint64)]
+
+
+class MeshSampleResultC(C.Structure):
+    _fields_ = [("n_usable", C.c_int), ("n_degenerate", C.c_int), ("n_bad", C.c_int), ("n_sampled", C.c_int), ("weight_exponent", C.c_int),
+                ("area_max", C.c_float), ("total_weight", C.c_uint64)]
+
+
+def mesh_sample_params(**kw):
+    """tdv_mesh_sample_default_params (seed 0, first_sample 0) with the given fields replaced."""
+    return _params("mesh_sample", kw)
+
+
+def _mesh_sample_result(r):
+    """The result as a dict, with surface_area = ldexp(total_weight, weight_exponent - 31) (include/tdv_hip.h: one rounding)."""
+    import math
+    return dict(n_usable=r.n_usable, n_degenerate=r.n_degenerate, n_bad=r.n_bad, n_sampled=r.n_sampled, weight_exponent=r.weight_exponent,
+                area_max=np.float32(r.area_max), total_weight=int(r.total_weight),
+                surface_area=math.ldexp(float(int(r.total_weight)), r.weight_exponent - 31))
+
+
 def _poses16(poses):
     """[n, 4, 4] row-major poses as the ABI's n x 16 column-major floats."""
     poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
@@ -318,6 +344,7 @@ _PARAMS = {
     "verify": (VerifyParamsC, "tdv_verify_default_params", "verification", dict(pose_direction=POSE_DIRECTION)),
     "mesh_verify": (MeshVerifyParamsC, "tdv_mesh_verify_default_params", "mesh verification",
                     dict(pose_direction=POSE_DIRECTION, cull=MESH_CULL)),
+    "mesh_sample": (MeshSampleParamsC, "tdv_mesh_sample_default_params", "mesh sampling", None),
     "ppf": (PpfParamsC, "tdv_ppf_default_params", "PPF", None),
 }
 
@@ -1216,6 +1243,80 @@ class Context:
                                                         C.c_float(cy), C.byref(mesh_verify_params(**params)), _ptr(d_out_depth), C.byref(n)),
                "tdv_render_depth_mesh_dev")
         return n.value
+
+    # ---------------------------------------------------------------- mesh sampling (include/tdv_hip.h: tdv_mesh_sample_points)
+    def mesh_sample(self, vertices, triangles, n_samples, attr=None, seed=0, first_sample=0):
+        """tdv_mesh_sample_points, every output: the result's fields and surface_area, xyz float32[n_sampled, 3], normals float32[n_sampled, 3]
+        (the faces' outward unit normals), triangle int32[n_sampled], bary float32[n_sampled, 2] and attr float32[n_sampled, width] or None.
+        attr: one row of floats per vertex (vertex normals, colours), interpolated at every sample."""
+        vtx, tri = _mesh(vertices, triangles)
+        width = 0
+        if attr is not None:
+            attr = _f32(attr)
+            if attr.ndim != 2 or len(attr) != len(vtx):
+                raise ValueError("tdv_mesh_sample_points: one attr row per vertex")
+            width = attr.shape[1]
+        res = MeshSampleResultC()
+        m1 = max(int(n_samples), 1)
+        xyz = np.zeros((m1, 3), np.float32); nrm = np.zeros((m1, 3), np.float32); idx = np.zeros(m1, np.int32); bary = np.zeros((m1, 2), np.float32)
+        cols = None if attr is None else np.zeros((m1, max(width, 1)), np.float32)
+        p = mesh_sample_params(seed=seed, first_sample=first_sample)
+        _check(self._h, lib().tdv_mesh_sample_points(self._h, _ptr(vtx), len(vtx), _ptr(tri), len(tri), _ptr(attr), width, int(n_samples),
+                                                     C.byref(p), C.byref(res), _ptr(xyz), _ptr(nrm), _ptr(idx), _ptr(bary), _ptr(cols)),
+               "tdv_mesh_sample_points")
+        m = res.n_sampled
+        return dict(_mesh_sample_result(res), xyz=xyz[:m], normals=nrm[:m], triangle=idx[:m], bary=bary[:m],
+                    attr=None if cols is None else cols.reshape(-1)[:m * width].reshape(m, width))
+
+    def sample_points_uniformly(self, vertices, triangles, number_of_points, seed=0):
+        """Open3D's TriangleMesh.sample_points_uniformly: (points, normals), the normals the faces' own."""
+        r = self.mesh_sample(vertices, triangles, number_of_points, seed=seed)
+        return r["xyz"], r["normals"]
+
+    def mesh_sample_dev(self, d_vertices, n_vertices, d_triangles, n_triangles, n_samples, d_attr=None, attr_width=0, seed=0, first_sample=0,
+                        d_out_xyz=None, d_out_normals=None, d_out_triangle=None, d_out_bary=None, d_out_attr=None):
+        """tdv_mesh_sample_points_dev on device pointers: the result dict.  d_out_xyz and d_out_normals (3 floats), d_out_triangle (int32),
+        d_out_bary (2 floats) and d_out_attr (attr_width floats) per sample, each of n_samples entries, are optional; n_sampled rows are
+        written.  One read-back."""
+        res = MeshSampleResultC()
+        p = mesh_sample_params(seed=seed, first_sample=first_sample)
+        _check(self._h, lib().tdv_mesh_sample_points_dev(self._h, _ptr(d_vertices), int(n_vertices), _ptr(d_triangles), int(n_triangles), _ptr(d_attr),
+                                                         int(attr_width), int(n_samples), C.byref(p), C.byref(res), _ptr(d_out_xyz),
+                                                         _ptr(d_out_normals), _ptr(d_out_triangle), _ptr(d_out_bary), _ptr(d_out_attr)),
+               "tdv_mesh_sample_points_dev")
+        return _mesh_sample_result(res)
+
+    def mesh_model_dev(self, d_vertices, n_vertices, d_triangles, n_triangles, n_points, d_out_xyz, d_out_normals, oversample=8, seed=0):
+        """The even-spread model of a mesh, on the device: oversample * n_points uniform samples (mesh_sample_dev) thinned to n_points by
+        fps_dev from row 0, the face normals as the companion rows - sample_points_poisson_disk's oversample-and-eliminate with the
+        exact-count sampler.  d_out_xyz and d_out_normals (3 n_points floats each) go into ppf_model_dev and the ICP entry points as they
+        stand.  Returns the fps result dict (n_selected rows are written); the oversampled rows live in torch buffers for the call."""
+        import torch
+        n_over = int(oversample) * int(n_points)
+        if oversample < 1 or n_points < 0 or n_over > TDV_FPS_MAX_POINTS:
+            raise ValueError("mesh_model: oversample >= 1 and oversample * n_points <= TDV_FPS_MAX_POINTS")
+        dev = torch.device("cuda", self.device)
+        over = torch.empty((2, max(n_over, 1), 3), dtype=torch.float32, device=dev)
+        torch.cuda.current_stream(dev).synchronize()         # (a reused block: what torch last did with it is over before the ctx's stream writes it)
+        s = self.mesh_sample_dev(d_vertices, n_vertices, d_triangles, n_triangles, n_over, seed=seed, d_out_xyz=over[0].data_ptr(),
+                                 d_out_normals=over[1].data_ptr())
+        return self.fps_dev(over[0].data_ptr(), s["n_sampled"], n_points, 0, over[1].data_ptr(), 3, None, None, d_out_xyz, d_out_normals)
+
+    def mesh_model(self, vertices, triangles, n_points, oversample=8, seed=0):
+        """mesh_model_dev on host arrays: (points float32[m, 3], normals float32[m, 3], fps result dict), m = n_points unless the mesh has
+        no usable triangle."""
+        import torch
+        vtx, tri = _mesh(vertices, triangles)
+        dev = torch.device("cuda", self.device)
+        d_v = _upload_rows(self.device, vtx)
+        d_t = torch.from_numpy(tri if len(tri) else np.zeros((1, 3), np.int32)).to(dev)
+        out = torch.zeros((2, max(int(n_points), 1), 3), dtype=torch.float32, device=dev)
+        torch.cuda.synchronize()
+        r = self.mesh_model_dev(d_v.data_ptr(), len(vtx), d_t.data_ptr(), len(tri), n_points, out[0].data_ptr(), out[1].data_ptr(), oversample, seed)
+        self.synchronize()
+        h = out.cpu().numpy()
+        m = r["n_selected"]
+        return h[0, :m].copy(), h[1, :m].copy(), r
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

@@ -1002,6 +1002,83 @@ int tdv_render_depth_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_verti
 int tdv_render_depth_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* pose, int width,
                           int height, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params, float* out_depth,
                           int* n_rendered /* optional */);
+/* Mesh sampling (Open3D's TriangleMesh::sample_points_uniformly): n_samples points drawn uniformly over the surface of an indexed triangle
+ * mesh, each with the exact outward normal of its face - the step from a model that is a mesh (tdv_verify_poses_mesh) to the points and
+ * normals every other stage takes (tdv_ppf_model_dev, tdv_prepare_model_dev, the ICP entry points, the splat verifier).  Thinned with
+ * tdv_farthest_point_down_sample_dev it is the even-spread model of sample_points_poisson_disk (oversample and eliminate; the Python
+ * front end composes the two as Context.mesh_model).  The random numbers are counter-based, the choice of a triangle and the barycentric
+ * coordinates are integers, and the floats are f32 with one rounding per operation, no contraction, the expression evaluated as written
+ * (sqrtf and / correctly rounded), so every output is fixed bit for bit whatever order the device works in:
+ *  S1. Triangle (a, b, c) of vertex indices.  It is bad if an index lies outside [0, n_vertices) - tested on the device before any vertex is
+ *      read, so a bad index reads no memory - or if one of its nine coordinates is not finite.  Vertices no triangle names are never read.
+ *  S2. Normal and area: e1 = vb - va, e2 = vc - va per component; n = (e1y*e2z - e1z*e2y, e1z*e2x - e1x*e2z, e1x*e2y - e1y*e2x);
+ *      L = sqrtf((nx*nx + ny*ny) + nz*nz); area = 0.5f * L.  A non-finite area (an overflow, or the NaN of inf - inf) makes the triangle
+ *      bad.  The orientation is rule M2's (vb - va) x (vc - va): outwards for a mesh wound as tdv_verify_poses_mesh's TDV_MESH_CULL_BACK
+ *      expects.
+ *  S3. Integer weights.  area_max = the largest area over the triangles that are not bad: an order-free maximum over the u32 bits of a
+ *      non-negative f32; 0 without such a triangle.  area_max == 0: e = 0 and every weight is 0.  Otherwise e = floor(log2(area_max)), read
+ *      from the exponent field of (double)area_max (exact for f32 subnormals too), and w_t = (uint64)((double)area_t * 2^(31 - e)),
+ *      truncated; a bad triangle has w_t = 0.  The scaling is by a power of two and exact, w_t < 2^32, and the largest triangle has
+ *      w >= 2^31.  W = the sum of the w_t, below 2^54, and C_t = w_0 + ... + w_t, the inclusive prefix sum in triangle order: integers, so
+ *      any scan order gives the same C.  A triangle whose area is below 2^-32 of the largest has weight 0 and is never chosen: the price of
+ *      integer weights, stated and not hidden.  (Between 2^-32 and 2^-8 of the largest a weight carries fewer than 24 bits: its share of
+ *      the samples is its truncated weight's, off by less than 1 / w_t of itself.)
+ *  S4. Sample k of the call has the global index g = first_sample + k (uint64).  x = philox4x32_10(counter ((uint32)g, (uint32)(g >> 32),
+ *      0, 0), key (seed, 2)): key word 2 is this stage's tag (tdv_fgr draws with 0, tdv_segment_planes with 1).
+ *      target = mulhi64(((uint64)x0 << 32) | x1, W), the high 64 bits of the 128-bit product: in [0, W).  The sample's triangle is the
+ *      smallest t with C_t > target; a triangle of weight 0 can never be it.
+ *  S5. Barycentric coordinates on integers: i1 = x2 >> 8, i2 = x3 >> 8; if i1 + i2 > 2^24 then i1 = 2^24 - i1 and i2 = 2^24 - i2 (the
+ *      reflection of the unit square's far half onto the near one).  u = i1 * 2^-24, v = i2 * 2^-24, w = (2^24 - i1 - i2) * 2^-24: all
+ *      three exact in f32, none negative, and u + v + w == 1 exactly.
+ *  S6. Outputs of sample k, each optional (NULL to skip), rows beyond n_sampled not written:
+ *      out_xyz[3k..]      (w*va + u*vb) + v*vc per coordinate
+ *      out_normals[3k..]  n / L per component: the face normal of S2 (L > 0 where w_t > 0)
+ *      out_triangle[k]    t
+ *      out_bary[2k..]     (u, v)
+ *      out_attr[width k..] (w*Aa + u*Ab) + v*Ac per column of one per-vertex companion array attr (n_vertices x attr_width floats:
+ *                         vertex normals or colours, interpolated as Open3D interpolates them, not renormalised); needs attr.
+ *  S7. Sample g depends on the mesh, seed and g only: the rows of a call with (first_sample = f, n_samples = n) are rows f .. f + n - 1
+ *      of the call with (0, f + n).  A caller can draw in chunks, or extend a sample it has.
+ * result: n_bad (S1, S2), n_usable (w_t > 0), n_degenerate (not bad, w_t == 0: zero area, or below 2^-32 of the largest) - the three sum to
+ * n_triangles -, n_sampled = n_samples if n_usable > 0, else 0; weight_exponent = e, area_max, total_weight = W.  The surface area the
+ * weights stand for is ldexp((double)total_weight, weight_exponent - 31): one rounding, the conversion of W (below 2^54) to double; the
+ * scaling is exact.  n_triangles == 0 gives a result of zeros.  n_samples == 0 fills the mesh's fields and writes nothing.  A mesh without a
+ * usable triangle gives n_sampled == 0 and writes nothing.
+ * Kernels (csrc/mesh_sample.hip): one pass over the triangles (areas, n_bad, area_max through one u32 atomic maximum per workgroup),
+ * the weights and their 64-bit inclusive scan in three plain launches (workgroup sums, one workgroup over the sums, add back - no kernel
+ * waits on another workgroup), then one lane per sample: Philox, the 64 x 64 high product, a branch-free upper-bound search over C (22
+ * steps at most, the coarse ones over a table of at most 4,096 entries staged in LDS), three vertex fetches, the row stores.
+ * tdv_mesh_sample_points takes host arrays and reads back twice (the result, then the n_sampled rows); tdv_mesh_sample_points_dev takes
+ * device pointers, the result on the host, and reads back once, the result.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params or result; NULL vertices with n_vertices > 0 or NULL triangles
+ * with n_triangles > 0; n_vertices < 0 or > TDV_MESH_MAX_VERTICES; n_triangles < 0 or > TDV_MESH_MAX_TRIANGLES; n_samples < 0 or
+ * > TDV_MESH_SAMPLE_MAX; first_sample + n_samples beyond 2^64 - 1; attr_width < 0; attr_width > 0 with a NULL attr; out_attr without attr.
+ * The ctx's switches do not apply.  Not provided: mesh file loaders, per-triangle densities, blue-noise elimination other than farthest
+ * point sampling, the C++ operator mirror. */
+#define TDV_MESH_SAMPLE_MAX (1 << 24)
+typedef struct tdv_mesh_sample_params {
+    uint32_t seed;           /* default 0 */
+    uint64_t first_sample;   /* the global index of the call's sample 0 (S7); default 0 */
+} tdv_mesh_sample_params;
+void tdv_mesh_sample_default_params(tdv_mesh_sample_params* params);
+typedef struct tdv_mesh_sample_result {
+    int      n_usable;          /* triangles with weight > 0 */
+    int      n_degenerate;      /* indices in range, coordinates and area finite, weight 0 */
+    int      n_bad;             /* an index out of range, a non-finite coordinate or a non-finite area */
+    int      n_sampled;         /* n_samples if n_usable > 0, else 0 */
+    int      weight_exponent;   /* e of rule S3 */
+    float    area_max;
+    uint64_t total_weight;      /* W of rule S3 */
+} tdv_mesh_sample_result;
+int tdv_mesh_sample_points(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles,
+                           const float* attr /* optional, per vertex */, int attr_width, int n_samples, const tdv_mesh_sample_params* params,
+                           tdv_mesh_sample_result* result, float* out_xyz /* optional */, float* out_normals /* optional */,
+                           int* out_triangle /* optional */, float* out_bary /* optional */, float* out_attr /* optional */);
+int tdv_mesh_sample_points_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles,
+                               const float* d_attr /* optional, per vertex */, int attr_width, int n_samples,
+                               const tdv_mesh_sample_params* params, tdv_mesh_sample_result* result /* host */, float* d_out_xyz /* optional */,
+                               float* d_out_normals /* optional */, int* d_out_triangle /* optional */, float* d_out_bary /* optional */,
+                               float* d_out_attr /* optional */);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
