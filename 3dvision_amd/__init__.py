@@ -66,6 +66,7 @@ ABI_SYMBOLS = [
     "tdv_ppf_match_batch_dev",
     "tdv_farthest_point_down_sample", "tdv_farthest_point_down_sample_dev", "tdv_farthest_point_down_sample_batch_dev",
     "tdv_ctx_set_fps_path", "tdv_ctx_last_fps_path", "tdv_ctx_set_icp_launches", "tdv_ctx_last_icp_launches",
+    "tdv_ctx_set_icp_probe_cache", "tdv_ctx_last_icp_probe_misses",
     "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
     "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
     "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
@@ -583,6 +584,18 @@ class Context:
     def last_icp_launches(self):
         """'one' if the last ICP call on this context ran the one-launch iteration, else 'two' ('auto' before any)."""
         return {v: k for k, v in self.ICP_LAUNCHES.items()}[int(lib().tdv_ctx_last_icp_launches(self._h))]
+
+    ICP_PROBE_CACHE = {"auto": 0, "off": 1, "on": 2}
+
+    def set_icp_probe_cache(self, mode):
+        """'auto' (default: with the one-launch iteration, when the call may run four iterations or more), 'off' or 'on' (the single
+        call's grid search in either launch form, from two iterations on): whether the hash-grid search keeps each source point's probed
+        list heads between a call's iterations; same bytes (tests and measurements)."""
+        _check(self._h, lib().tdv_ctx_set_icp_probe_cache(self._h, self.ICP_PROBE_CACHE[mode]), "tdv_ctx_set_icp_probe_cache")
+
+    def last_icp_probe_misses(self):
+        """(point, iteration) pairs of the last ICP call on this context that probed the hash table; -1 if it ran without the probe cache."""
+        return int(lib().tdv_ctx_last_icp_probe_misses(self._h))
 
     def set_fps_path(self, mode):
         """'auto' (default: the workgroup kernels up to TDV_FPS_WORKGROUP_MAX rows, the grid kernels above), 'workgroup' or 'grid': the

@@ -51,11 +51,14 @@ void reset_result(tdv_instance_result& r) {
 // An instance's ICP on a lane of the batch keeps two launches per iteration whatever the ctx says: the other lanes' kernels run beside
 // it, and the one-launch iteration (icp.hip: k_icp_iterate) was measured faster only with the device to itself, one workgroup per CU.
 // With it in the lanes, C4's 256 instances of ~148k voxels (those from 150,000 up took it) ran at 707-709 instances/s against 712-716
-// (profiles/r19/icp_one_launch.md).
+// (profiles/r19/icp_one_launch.md).  The probe cache (icp.hip: grid_nearest<1>) was measured the same way, alone on the device, and stays
+// out of the lanes too: they run the search as it was.
 struct TwoLaunchIcp {
-    tdv_ctx* c; int saved;
-    explicit TwoLaunchIcp(tdv_ctx* c_) : c(c_), saved(c_->icp_launches) { c->icp_launches = TDV_ICP_LAUNCHES_TWO; }
-    ~TwoLaunchIcp() { c->icp_launches = saved; }
+    tdv_ctx* c; int saved, saved_cache;
+    explicit TwoLaunchIcp(tdv_ctx* c_) : c(c_), saved(c_->icp_launches), saved_cache(c_->icp_probe_cache) {
+        c->icp_launches = TDV_ICP_LAUNCHES_TWO; c->icp_probe_cache = TDV_ICP_PROBE_CACHE_OFF;
+    }
+    ~TwoLaunchIcp() { c->icp_launches = saved; c->icp_probe_cache = saved_cache; }
 };
 
 // the ICP stage's outcome: the refined pose and its figures, and the instance done (status 0)

@@ -313,6 +313,13 @@ int tdv_ctx_set_icp_launches(tdv_ctx* ctx, int mode) {
 }
 int tdv_ctx_last_icp_launches(tdv_ctx* ctx) { return ctx ? ctx->last_icp_launches : TDV_ERR_BAD_ARG; }
 
+int tdv_ctx_set_icp_probe_cache(tdv_ctx* ctx, int mode) {
+    if (!ctx || mode < TDV_ICP_PROBE_CACHE_AUTO || mode > TDV_ICP_PROBE_CACHE_ON) return TDV_ERR_BAD_ARG;
+    ctx->icp_probe_cache = mode;
+    return TDV_OK;
+}
+int tdv_ctx_last_icp_probe_misses(tdv_ctx* ctx) { return ctx ? ctx->last_icp_probe_misses : TDV_ERR_BAD_ARG; }
+
 int tdv_ctx_set_icp_loss(tdv_ctx* ctx, int loss, float scale) {
     if (!ctx || loss < TDV_ICP_LOSS_L2 || loss > TDV_ICP_LOSS_CAUCHY) return TDV_ERR_BAD_ARG;
     if (loss != TDV_ICP_LOSS_L2 && !(std::isfinite(scale) && scale > 0.f)) return TDV_ERR_BAD_ARG;

@@ -96,7 +96,7 @@ struct IcpState {
     int done;          // loop finished (converged / n_corr < 3)
     int iter;          // iterations evaluated
     int last_n_corr_applied;
-    int pad;
+    int probe_misses;  // lanes that probed the hash table over the call's iterations (the probe cache: grid_nearest); 0 without the cache
 };
 
 __global__ void k_aos_to_soa_pad(const float* __restrict__ aos, int n, int n_pad, float pad,
@@ -305,10 +305,34 @@ void k_grid_insert(const float* __restrict__ tgt, int nt, float inv_cell, GridEn
     if (threadIdx.x == 0) { if (s_new) atomicAdd(&flags[1], s_new); if (s_bad) atomicOr(&flags[0], 1); }
 }
 
-// the search of one query point p: lowest (d2, original index) among the targets with d2 <= tau, (INFINITY, INT_MAX) if none
+// ---- the probe cache: a source point's eight list heads, kept between the iterations of one call ---------------------------------
+// What the probes of grid_nearest find - j[0..7], each cell's list head or -1 - is a function of the point's cell (cx, cy, cz), its
+// three neighbour signs and the table, and the table does not change during a call.  After a call's first iterations the pose moves by
+// far less than half a cell, so nearly every point asks the same eight questions again.  Per source point the call's workspace keeps
+// the six integers packed into 8 bytes (18 bits per cell coordinate: |coordinate| < GRID_MAX_COORD = 2^17; three sign bits; a valid
+// bit) and the eight heads, struct of arrays: a wave's loads are whole lines.  The key array is zeroed (invalid) once per call
+// (icp_run_dev), so no head outlives its table.  A lane takes the cached heads only if the key it computes THIS iteration from this
+// iteration's pose equals the stored one: the heads are then the ones the probes would find, exactly.  A lane whose transformed point
+// is non-finite or outside GRID_MAX_COORD never hits and never stores.
+struct ProbeCache { uint2* key; uint4* head; int* misses; };      // key[ns]; head[2 ns]: heads 0-3 at [i], 4-7 at [ns + i]; misses: one word
+struct ProbeLane { uint2 key; uint4 h0, h1; };                     // what a lane loaded, early (beside its source point)
+constexpr unsigned PROBE_VALID = 0x80000000u;
+// PROBE: 0 no cache; 1 the cache; study build only - 2 the cached heads taken as they are, no compare and no probe loop (an upper bound
+// on the gain: the heads come from the call's first iteration, which runs 1); 3 the probe loop alone, no list walk (nothing is found)
+__device__ __forceinline__ ProbeLane probe_load(const ProbeCache& pc, int i, int ns) {
+    ProbeLane l;
+    l.key = pc.key[i]; l.h0 = pc.head[i]; l.h1 = pc.head[(size_t)ns + i];
+    return l;
+}
+
+// the search of one query point p: lowest (d2, original index) among the targets with d2 <= tau, (INFINITY, INT_MAX) if none.
+// PROBE != 0: point i's cached heads lc (probe_load) are taken where their key holds, the heads found otherwise are stored, and
+// `missed` tells whether this lane probed.
+template <int PROBE = 0>
 __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table, const float4* __restrict__ node, unsigned mask, int shift,
                                              float inv_cell, float px, float py, float pz, float tau, float& bd, int& bo,
-                                             float* bq = nullptr /* 3: the winner's coordinates as node[] holds them, k_grid_insert's copy of the target's */) {
+                                             float* bq = nullptr /* 3: the winner's coordinates as node[] holds them, k_grid_insert's copy of the target's */,
+                                             const ProbeCache* pc = nullptr, const ProbeLane* lc = nullptr, int i = 0, int ns = 0, bool* missed = nullptr) {
     const float gx = px * inv_cell, gy = py * inv_cell, gz = pz * inv_cell;
     const float kx = floorf(gx), ky = floorf(gy), kz = floorf(gz);
     const int cx = (int)kx, cy = (int)ky, cz = (int)kz;
@@ -332,6 +356,21 @@ __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table
     }
     (void)mask;
     unsigned pending = 0xffu;
+    bool hit = false, in_range = false;
+    uint2 key2 = make_uint2(0u, 0u);
+    if constexpr (PROBE == 1 || PROBE == 2) {
+        in_range = fabsf(gx) < GRID_MAX_COORD && fabsf(gy) < GRID_MAX_COORD && fabsf(gz) < GRID_MAX_COORD;      // false for NaN
+        key2.x = ((unsigned)cx & 0x3ffffu) | ((unsigned)cy << 18);
+        key2.y = (((unsigned)cy >> 14) & 0xfu) | (((unsigned)cz & 0x3ffffu) << 4) | (sx > 0 ? 1u << 22 : 0u) | (sy > 0 ? 1u << 23 : 0u) |
+                 (sz > 0 ? 1u << 24 : 0u) | PROBE_VALID;
+        hit = PROBE == 2 || (in_range && lc->key.x == key2.x && lc->key.y == key2.y);
+        if (hit) {
+            j[0] = (int)lc->h0.x; j[1] = (int)lc->h0.y; j[2] = (int)lc->h0.z; j[3] = (int)lc->h0.w;
+            j[4] = (int)lc->h1.x; j[5] = (int)lc->h1.y; j[6] = (int)lc->h1.z; j[7] = (int)lc->h1.w;
+            pending = 0u;      // this lane sits the loop out; a wave whose lanes all hit skips it
+        }
+        *missed = !hit;
+    }
     while (pending) {
         uint4 e[8];
 #pragma unroll
@@ -348,7 +387,18 @@ __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table
             pending |= next ? 1u << c : 0u;
         }
     }
+    if constexpr (PROBE == 1) {
+        if (!hit && in_range) {
+            pc->key[i] = key2;
+            pc->head[i] = make_uint4((unsigned)j[0], (unsigned)j[1], (unsigned)j[2], (unsigned)j[3]);
+            pc->head[(size_t)ns + i] = make_uint4((unsigned)j[4], (unsigned)j[5], (unsigned)j[6], (unsigned)j[7]);
+        }
+    }
     bd = INFINITY; bo = INT_MAX;
+    if constexpr (PROBE == 3) {      // the probes alone: their heads kept alive, nothing walked
+        if ((j[0] & j[1] & j[2] & j[3] & j[4] & j[5] & j[6] & j[7]) == 0x7ffffff1) bo = 0;
+        return;
+    }
     auto take = [&](const float4 t, int idx, bool live) {
         const float ex = px - t.x, ey = py - t.y, ez = pz - t.z;
         const float d2 = ex * ex + (ey * ey + ez * ez);    // the scan's expression
@@ -384,19 +434,44 @@ __device__ __forceinline__ void grid_nearest(const GridEntry* __restrict__ table
 // arrays in between - was measured slower twice, 110 us against 44 + 35 and later 56.5 against 49.6 at 200k x 200k: that kernel's 29
 // double accumulators and four points in flight leave one wave per SIMD to hide the probes' latency.  k_icp_iterate below fuses the
 // other way round: this kernel's shape and registers for the search, the sums formed afterwards from records in LDS.)
+// PROBE: the probe cache (grid_nearest); the lanes that probed are counted per workgroup and added to *pc.misses by one thread, only when
+// there are any (one add per WAVE, 782 to one word per launch at 50,000 sources, cost a short call 8 us per iteration).
+template <int PROBE = 0>
 __global__ __launch_bounds__(256)
 void k_icp_nn_grid(const float* __restrict__ src, int ns, const GridEntry* __restrict__ table, const float4* __restrict__ node,
                    unsigned mask, int shift, float inv_cell, const IcpState* __restrict__ st, float tau,
-                   float* __restrict__ out_d2, int* __restrict__ out_idx) {
+                   float* __restrict__ out_d2, int* __restrict__ out_idx, ProbeCache pc) {
     if (st->done) return;
     const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= ns) return;
-    float px, py, pz;
-    transform_point(st->T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
-    float bd; int bo;
-    grid_nearest(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo);
-    out_d2[i] = bo == INT_MAX ? FLT_MAX : bd;
-    out_idx[i] = bo == INT_MAX ? 0 : bo;
+    if constexpr (PROBE == 0) {
+        if (i >= ns) return;
+        float px, py, pz;
+        transform_point(st->T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
+        float bd; int bo;
+        grid_nearest(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo);
+        out_d2[i] = bo == INT_MAX ? FLT_MAX : bd;
+        out_idx[i] = bo == INT_MAX ? 0 : bo;
+    } else {
+        __shared__ int wave_misses[4];      // every thread reaches the barrier: st->done is uniform, a lane past ns searches nothing but stays
+        bool missed = false;
+        if (i < ns) {
+            const float s0 = src[3 * i], s1 = src[3 * i + 1], s2 = src[3 * i + 2];
+            const ProbeLane lc = probe_load(pc, i, ns);      // beside the source point: one wait for both
+            float px, py, pz;
+            transform_point(st->T, s0, s1, s2, px, py, pz);
+            float bd; int bo;
+            grid_nearest<PROBE>(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo, nullptr, &pc, &lc, i, ns, &missed);
+            out_d2[i] = bo == INT_MAX ? FLT_MAX : bd;
+            out_idx[i] = bo == INT_MAX ? 0 : bo;
+        }
+        const unsigned long long mm = __ballot(missed);
+        if ((threadIdx.x & 63) == 0) wave_misses[threadIdx.x >> 6] = __popcll(mm);
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            const int m = (wave_misses[0] + wave_misses[1]) + (wave_misses[2] + wave_misses[3]);
+            if (m) atomicAdd(pc.misses, m);
+        }
+    }
 }
 
 // Sum over the 64 lanes with DPP row operations on the two halves of the double (no LDS crossbar round trips, unlike
@@ -999,11 +1074,13 @@ __device__ __forceinline__ void it_sum_subset(const float (*rec)[IT_THREADS], in
     }
 }
 
-template <int MODE, bool ROBUST>
+// PROBE: the probe cache (grid_nearest).  Every wave leaves the number of its lanes that probed in LDS; after the barrier that is there
+// anyway thread 0 adds the workgroup's total to *pc.misses - only if it is not zero, so a converged iteration issues no atomic.
+template <int MODE, bool ROBUST, int PROBE = 0>
 __global__ __launch_bounds__(IT_THREADS)
 void k_icp_iterate(const float* __restrict__ src, int ns, const float* __restrict__ tgt_normals,
                    const GridEntry* __restrict__ table, const float4* __restrict__ node, unsigned mask, int shift, float inv_cell,
-                   IcpState* st, float tau, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* ticket) {
+                   IcpState* st, float tau, int fixed_iterations, IcpLoss loss, double* slabs, unsigned* ticket, ProbeCache pc) {
     static_assert(MODE == 0 || MODE == 1, "the one-launch iteration exists for point-to-plane and point-to-point");
     static_assert(ACC_GROUP * 256 == IT_THREADS && 4 * IT_TERMS == ACC_NV, "a workgroup is one slab of k_icp_accumulate<MODE, 4>");
     if (st->done) return;
@@ -1018,12 +1095,16 @@ void k_icp_iterate(const float* __restrict__ src, int ns, const float* __restric
 #pragma unroll
     for (int j = 0; j < REC_WORDS; ++j) R.f[j] = 0.f;
     R.f[0] = FLT_MAX;
+    bool missed = false;
     if (i < ns) {
+        const float s0 = src[3 * i], s1 = src[3 * i + 1], s2 = src[3 * i + 2];
+        ProbeLane lc;
+        if constexpr (PROBE != 0) lc = probe_load(pc, i, ns);      // beside the source point: one wait for both
         float px, py, pz;
-        acc_transform(T, src[3 * i], src[3 * i + 1], src[3 * i + 2], px, py, pz);
+        acc_transform(T, s0, s1, s2, px, py, pz);
         float bd; int bo;
         CorrTgt G;
-        grid_nearest(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo, G.q);
+        grid_nearest<PROBE>(table, node, mask, shift, inv_cell, px, py, pz, tau, bd, bo, G.q, &pc, &lc, i, ns, &missed);
         const bool found = bo != INT_MAX;
         const int idx = found ? bo : 0;
         if (MODE == 0) { G.n[0] = tgt_normals[3 * idx]; G.n[1] = tgt_normals[3 * idx + 1]; G.n[2] = tgt_normals[3 * idx + 2]; }
@@ -1032,7 +1113,20 @@ void k_icp_iterate(const float* __restrict__ src, int ns, const float* __restric
     }
 #pragma unroll
     for (int j = 0; j < rec_words<MODE>(); ++j) rec[j][t] = R.f[j];
+    __shared__ int wave_misses[IT_THREADS / 64];
+    if constexpr (PROBE != 0) {
+        const unsigned long long mm = __ballot(missed);
+        if ((t & 63) == 0) wave_misses[t >> 6] = __popcll(mm);
+    }
     __syncthreads();
+    if constexpr (PROBE != 0) {
+        if (t == 0) {
+            int m = 0;
+#pragma unroll
+            for (int k = 0; k < IT_THREADS / 64; ++k) m += wave_misses[k];
+            if (m) atomicAdd(pc.misses, m);
+        }
+    }
     // ---- sums --------------------------------------------------------------------------------------------------------------
     const int w = t >> 6, g = w & 3, L = 64 * g + (t & 63);
     switch (w >> 2) {      // wave-uniform
@@ -1548,6 +1642,7 @@ struct IcpPlan {
     CellGrid cg;    // the target's hash grid, searched when cg.usable
     NnPlan p;       // the scan's shape and the accumulation's acc_ppt / acc_blocks
     bool one_launch;   // search and sums of an iteration in one kernel (k_icp_iterate), what ctx->last_icp_launches reports
+    bool probe_cache;  // the grid search keeps each point's list heads between iterations (grid_nearest<1>)
 };
 
 // Source counts between which TDV_ICP_LAUNCHES_AUTO takes k_icp_iterate.  Measured (tools/studies/icp_grid_scaling.py --forms two,one,
@@ -1558,13 +1653,23 @@ struct IcpPlan {
 // part has 256 CUs, and a CU that gets a second workgroup runs twice as long.
 constexpr int ONE_LAUNCH_MIN_SOURCES = 150000;
 constexpr int ONE_LAUNCH_MAX_SOURCES = 262144;      // 256 workgroups
+// With the probe cache (grid_nearest<1>) the rule stays.  Over 100 iterations the cached kernel beats the cached and the uncached two
+// launches from 50,000 sources on (75k 20.8 / 21.7 / 30.4 us, 100k 21.6 / 22.6 / 31.5, 400k 40.1 / 41.3 / 61.2), but a call of four
+// iterations from a near start - the pipeline's - is a tie or loses 1 to 3 % against the uncached two launches at 75k to 125k, and at 300k
+// loses 12 %; inside the range the cached kernel is never behind (profiles/r22/icp_probe_cache.md, sections 5 and 6).
+//
+// Iterations a call must be allowed for TDV_ICP_PROBE_CACHE_AUTO to take the cache: the first iteration only fills it (a memset of the
+// keys, three more loads and a 40-byte store per point), every later one gains.  Measured per call at 200k x 200k against the uncached
+// call: 2 iterations +1 to +4 us, 3 iterations -2 to +3 us, 4 iterations -2 to -8 us, 8 iterations -30 us.
+constexpr int PROBE_CACHE_MIN_ITERATIONS = 4;
 
 // Search: brute force for small problems (the two Morton sorts cost more than they save), the exact pruned walk for large ones, the
 // hash grid (tgt_grid if it was built for this nt and thr, else built here) on request or by size like the walk, used when its build
 // says the cells are small enough.  All give the same correspondences bit for bit.
-// obj: the single call's objective; without it (a batch) the plan keeps two launches per iteration.
+// obj: the single call's objective and max_iterations its iteration limit; without them (a batch) the plan keeps two launches per
+// iteration and the uncached search.
 int icp_plan(tdv_ctx* ctx, const float* d_tgt, int ns, int nt, float thr, const CellGrid* tgt_grid, IcpPlan& pl,
-             const IcpObjective* obj = nullptr) {
+             const IcpObjective* obj = nullptr, int max_iterations = 0) {
     const int mode = ctx->icp_search;
     const float tau = tau_le(thr);
     bool pruned = tau < FLT_MAX &&      // (unbounded threshold: keep the scan's handling of overflowing distances)
@@ -1589,6 +1694,13 @@ int icp_plan(tdv_ctx* ctx, const float* d_tgt, int ns, int nt, float thr, const 
                          (obj->kind == ICP_POINT_TO_PLANE || obj->kind == ICP_POINT_TO_POINT);
     pl.one_launch = can_one && (ctx->icp_launches == TDV_ICP_LAUNCHES_ONE ||
                                 (ctx->icp_launches == TDV_ICP_LAUNCHES_AUTO && ns >= ONE_LAUNCH_MIN_SOURCES && ns <= ONE_LAUNCH_MAX_SOURCES));
+    // the probe cache: a single call's grid search (a batch's _multi kernels and register_batch's lanes keep the uncached search).  AUTO
+    // takes it with the one-launch iteration in a call long enough to gain from it (the two launches gain only from about eight
+    // iterations on: at 200k sources a call of four is 13 us slower with it); ON in either form from two iterations on (one iteration
+    // could only fill it).
+    pl.probe_cache = obj && pl.cg.usable &&
+                     ((ctx->icp_probe_cache == TDV_ICP_PROBE_CACHE_ON && max_iterations >= 2) ||
+                      (ctx->icp_probe_cache == TDV_ICP_PROBE_CACHE_AUTO && pl.one_launch && max_iterations >= PROBE_CACHE_MIN_ITERATIONS));
     return TDV_OK;                                    // measured: 50k x 10k brute 7.6k vs 6.4k iters/s with 1 point per thread
 }
 
@@ -1744,9 +1856,10 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     if (ns == 0 || nt == 0) return TDV_OK;  // n_corr == 0 < 3 -> break at the first iteration
     const float tau = tau_le(thr);
     IcpPlan pl;
-    TDV_TRY(icp_plan(ctx, d_tgt, ns, nt, thr, tgt_grid, pl, &obj));
+    TDV_TRY(icp_plan(ctx, d_tgt, ns, nt, thr, tgt_grid, pl, &obj, max_iterations));
     ctx->last_icp_search = pl.search;
     ctx->last_icp_launches = pl.one_launch ? TDV_ICP_LAUNCHES_ONE : TDV_ICP_LAUNCHES_TWO;
+    ctx->last_icp_probe_misses = -1;
     const NnPlan& p = pl.p;
     const CellGrid& cg = pl.cg;
     const IcpLoss loss = ctx_loss(ctx);
@@ -1796,22 +1909,51 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     const GridEntry* gtable = cg.usable ? reinterpret_cast<const GridEntry*>(cg.table) : nullptr;
     const float4* gnode = cg.usable ? reinterpret_cast<const float4*>(cg.node) : nullptr;
     const dim3 grid(p.blocks_x, p.nsplit);
+    // the probe cache of this call: keys invalid before the first iteration, so no head of another table, call or arena is ever taken
+    ProbeCache pc{};
+    const bool cached = pl.probe_cache;
+    if (cached) {
+        TDV_TRY(ws_alloc(ctx, (size_t)ns, &pc.key));
+        TDV_TRY(ws_alloc(ctx, (size_t)2 * ns, &pc.head));
+        pc.misses = &b.st->probe_misses;
+        TDV_HIP(ctx, hipMemsetAsync(pc.key, 0, (size_t)ns * sizeof(uint2), s));
+    }
+    // study build: TDV_ICP_PROBE_STUDY=heads / probe times the iteration without its probe loop resp. without its list walk (grid_nearest's
+    // PROBE 2 and 3: not results, an upper bound on what the cache can save); the call's first iteration fills the cache for `heads`
+    const char* probe_study = study_env("TDV_ICP_PROBE_STUDY");
+    const int study_probe = !(cached && probe_study) ? 0 : !strcmp(probe_study, "heads") ? 2 : !strcmp(probe_study, "probe") ? 3 : 0;
+    if (study_probe) TDV_HIP(ctx, hipMemsetAsync(pc.head, 0xff, (size_t)2 * ns * sizeof(uint4), s));      // (`heads` never compares: no head a lane did not store)
+    int iteration_no = 0;
+    (void)iteration_no;
+    // f(PROBE) for this iteration's form of the grid search
+    const auto probe_dispatch = [&](const auto& f) {
+#ifdef TDV_STUDY
+        if (study_probe && iteration_no > 0) return study_probe == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 3>{});
+#endif
+        return cached ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
+    };
     TDV_TRY(run_bursts(ctx, h, b.st, 1, max_iterations, fixed_iterations, [&]() {
         if (pl.one_launch) {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);      // the whole iteration: one launch
             icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto) {
                 constexpr int MODE = decltype(M)::value;
                 if constexpr (MODE == ICP_POINT_TO_PLANE || MODE == ICP_POINT_TO_POINT)      // (icp_plan's rule)
-                    k_icp_iterate<MODE, decltype(R)::value><<<p.acc_blocks, IT_THREADS, 0, s>>>(
-                        d_src, ns, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau,
-                        fixed_iterations, loss, b.slabs, b.ticket);
+                    probe_dispatch([&](auto P) {
+                        k_icp_iterate<MODE, decltype(R)::value, decltype(P)::value><<<p.acc_blocks, IT_THREADS, 0, s>>>(
+                            d_src, ns, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau,
+                            fixed_iterations, loss, b.slabs, b.ticket, pc);
+                    });
             });
+            ++iteration_no;
             return;
         }
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
             if (gtable)
-                k_icp_nn_grid<<<(ns + 255) / 256, 256, 0, s>>>(d_src, ns, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau, b.pd2, b.pchunk);
+                probe_dispatch([&](auto P) {
+                    k_icp_nn_grid<decltype(P)::value><<<(ns + 255) / 256, 256, 0, s>>>(d_src, ns, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau,
+                                                                                       b.pd2, b.pchunk, pc);
+                });
             else if (pl.direct)
                 k_icp_nn_pruned<<<(ns + PN_WAVES * PN_PTS - 1) / (PN_WAVES * PN_PTS), 64 * PN_WAVES, 0, s>>>(
                     d_src, ns, st, b.st, tau, b.pd2, b.pchunk);
@@ -1835,7 +1977,9 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 });
             }
         });
+        ++iteration_no;
     }));
+    if (cached) ctx->last_icp_probe_misses = h->probe_misses;
     state_result(*h, *out);
     return TDV_OK;
 }
@@ -1873,6 +2017,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
     TDV_HIP(ctx, hipStreamSynchronize(s));
     ctx->last_icp_search = TDV_ICP_SEARCH_BRUTE;
     ctx->last_icp_launches = TDV_ICP_LAUNCHES_TWO;
+    ctx->last_icp_probe_misses = -1;
     for (int b = 0; b < n_prob; ++b) state_result(h[b], out[b]);
     return TDV_OK;
 }
@@ -1975,6 +2120,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const IcpLoss loss = ctx_loss(ctx);
     ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
     ctx->last_icp_launches = TDV_ICP_LAUNCHES_TWO;
+    ctx->last_icp_probe_misses = -1;
     TDV_TRY(run_bursts(ctx, h, d_st, n,max_iterations, fixed_iterations, [&]() {
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
@@ -2043,7 +2189,7 @@ int icp_correspondences_dev(tdv_ctx* ctx, const float* d_src, int ns, const floa
     const float tau = tau_le(thr);
     if (grid.usable) {
         k_icp_nn_grid<<<(ns + 255) / 256, 256, 0, s>>>(d_src, ns, reinterpret_cast<const GridEntry*>(grid.table), reinterpret_cast<const float4*>(grid.node),
-                                                       grid.mask, grid.shift, grid.inv_cell, b.st, tau, b.pd2, b.pchunk);
+                                                       grid.mask, grid.shift, grid.inv_cell, b.st, tau, b.pd2, b.pchunk, ProbeCache{});
     } else if (pruned) {   // explicit request only: entries beyond the threshold come back as corr 0 / d2 FLT_MAX
         SortedCloud st{};
         TDV_TRY(spatial_sort_cloud(ctx, d_tgt, nt, st));

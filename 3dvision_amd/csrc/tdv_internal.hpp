@@ -50,6 +50,8 @@ struct tdv_ctx {
     int last_fps_path = 0;     // the family the last farthest-point call on this ctx chose (tdv_ctx_last_fps_path)
     int icp_launches = 0;      // TDV_ICP_LAUNCHES_AUTO / _TWO / _ONE (tdv_ctx_set_icp_launches)
     int last_icp_launches = 0; // whether the last ICP call on this ctx ran the one-launch iteration (tdv_ctx_last_icp_launches)
+    int icp_probe_cache = 0;   // TDV_ICP_PROBE_CACHE_AUTO / _OFF / _ON (tdv_ctx_set_icp_probe_cache)
+    int last_icp_probe_misses = -1;   // lanes that probed the hash table in the last ICP call, -1 if it ran without the probe cache
     int last_icp_search = 0;// the search the last ICP / correspondence call on this ctx actually ran (tdv_ctx_last_icp_search)
     unsigned* scan_ticket = nullptr;  // persistent device words: [0] exclusive_scan_dev's last-workgroup ticket, [1..] ICP's, [8] the tile ticket of depth.hip's chained scan
     unsigned long long* chain_status = nullptr;   // depth.hip k_depth_cloud_chain: one status word per tile, persistent (told apart by chain_epoch)

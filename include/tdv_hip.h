@@ -92,6 +92,21 @@ int tdv_ctx_set_icp_accumulation(tdv_ctx* ctx, int mode);
 #define TDV_ICP_LAUNCHES_ONE 2
 int tdv_ctx_set_icp_launches(tdv_ctx* ctx, int mode);
 int tdv_ctx_last_icp_launches(tdv_ctx* ctx);
+/* The probe cache of the hash-grid search, for tests and measurements.  The search probes an open-addressing table for the eight cells
+ * around a transformed source point; what it finds there (each cell's list head) depends only on the point's cell, on which side of the
+ * cell it sits per axis, and on the table.  With the cache a single call keeps every point's cell key and eight heads in its workspace
+ * and takes them in a later iteration whenever the key computed from that iteration's pose is the stored one - then they are the heads
+ * the probes would find, so correspondences and every sum keep their bits.  Keys are invalid at the start of every call.  AUTO
+ * (default) takes the cache where the one-launch iteration runs, when the call may run four iterations or more (the first only fills
+ * the cache; a shorter call measured no faster with it); ON takes it on the single call's grid path in either launch form from two
+ * iterations on; OFF never.  A call of one iteration, batches and tdv_register_batch_dev's instances run without it.  tdv_ctx_last_icp_probe_misses: the
+ * number of (point, iteration) pairs of the last ICP call on the ctx that probed the table (the rest took cached heads), -1 if the call
+ * ran without the cache; TDV_ERR_BAD_ARG for a null ctx, as the setter for a null ctx or an unknown mode. */
+#define TDV_ICP_PROBE_CACHE_AUTO 0
+#define TDV_ICP_PROBE_CACHE_OFF 1
+#define TDV_ICP_PROBE_CACHE_ON 2
+int tdv_ctx_set_icp_probe_cache(tdv_ctx* ctx, int mode);
+int tdv_ctx_last_icp_probe_misses(tdv_ctx* ctx);
 /* ICP robust loss: iteratively reweighted least squares, one weight w per accepted correspondence (d2 <= thr^2, unchanged), set
  * per ctx and honoured by tdv_icp, tdv_icp_dev, tdv_icp_batch_dev, tdv_refine_batch_dev and tdv_register_batch_dev (batch lanes
  * included).  tdv_icp_correspondences is unaffected.  L2 (default) gives every accepted correspondence weight 1: today's results,

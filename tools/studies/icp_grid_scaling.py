@@ -1,9 +1,15 @@
 """One ICP iteration on the hash-grid path against the number of source points (same 200k-point target): the fixed and the per-point
 part of the whole iteration, of the search launch, and - from a kernel trace - of every ICP kernel.
 
-    python tools/studies/icp_grid_scaling.py [--forms auto|two|one,...] [--rounds R] [--sizes N,N,...]
-        per source count and form (tdv_ctx_set_icp_launches; alternated, R rounds): iteration_us is a 100-iteration fixed run between two
-        events with timing off, nn_kernel_us is TDV_TIMER_ICP_NN per launch (with ONE launch that is the whole fused kernel).
+    python tools/studies/icp_grid_scaling.py [--forms auto|two|one,...] [--cache auto|off|on,...] [--rounds R] [--sizes N,N,...]
+                                             [--iters K] [--trans T,T,...] [--no-timer]
+        per source count, form (tdv_ctx_set_icp_launches) and probe-cache setting (tdv_ctx_set_icp_probe_cache; all alternated, R rounds):
+        iteration_us is a K-iteration fixed run (default 100) between two events with timing off, nn_kernel_us is TDV_TIMER_ICP_NN per
+        launch (with ONE launch that is the whole fused kernel), probe_misses what the cache reports for that run.  --trans: the start
+        pose's translation error(s) instead of 0.0005 (with --iters: calls whose pose moves by cells per iteration - the cache misses
+        everywhere).  On a library without the probe cache only --cache auto runs.
+        TDV_LIB_VARIANT=study TDV_ICP_PROBE_STUDY=heads|probe (with --cache on): the iteration without its probe loop resp. without its
+        list walk (csrc/icp.hip: grid_nearest's PROBE 2 and 3), the bound on what the cache can save.
     rocprofv3 --kernel-trace --output-format csv -d <dir> -- python tools/studies/icp_grid_scaling.py ...
     python tools/studies/icp_grid_scaling.py --trace <kernel_trace.csv>
         the trace of such a run split by kernel and workgroup count (one workgroup count per source count): mean us per launch of
@@ -13,6 +19,10 @@ import argparse, csv, importlib, os, sys, json
 SIZES = (12500, 25000, 50000, 100000, 200000, 400000, 800000)
 ap = argparse.ArgumentParser()
 ap.add_argument("--forms", default="auto")
+ap.add_argument("--cache", default="auto")
+ap.add_argument("--iters", type=int, default=100)
+ap.add_argument("--trans", default="0.0005")
+ap.add_argument("--no-timer", action="store_true", help="skip the timed run (TDV_TIMER_ICP_NN)")
 ap.add_argument("--rounds", type=int, default=1)
 ap.add_argument("--sizes", help="source counts instead of the standard seven (with --trace: the counts of the traced run)")
 ap.add_argument("--trace")
@@ -45,22 +55,31 @@ tgt, nrm = synth.sample_object(nt, 42)
 voxel = float(np.float32(synth.mean_spacing(nt)))
 d_tgt = torch.from_numpy(tgt).to(dev); d_nrm = torch.from_numpy(nrm).to(dev)
 ctx.set_icp_search("grid")
+K = args.iters
 for ns in SIZES:
+  for trans in (float(t) for t in args.trans.split(",")):
     src, T_gt = synth.make_scene(ns, 42)
-    T0 = synth.perturb(T_gt, 42, angle_deg=0.3, trans=0.0005)
+    T0 = synth.perturb(T_gt, 42, angle_deg=0.3, trans=trans)
     d_src = torch.from_numpy(src).to(dev)
     run = lambda n: ctx.icp_dev(d_src.data_ptr(), ns, d_tgt.data_ptr(), d_nrm.data_ptr(), nt, T0, voxel * 0.4, n, True, fixed_iterations=True)
     for rnd in range(args.rounds):
         for form in args.forms.split(","):
+          for cache in args.cache.split(","):
             if form != "auto": ctx.set_icp_launches(form)
-            run(10)
+            if cache != "auto": ctx.set_icp_probe_cache(cache)
+            run(min(K, 10))
+            reps = max(1, 100 // K)            # short calls: several between the two events
             e0 = torch.cuda.Event(enable_timing=True); e1 = torch.cuda.Event(enable_timing=True)
-            e0.record(); run(100); e1.record(); e1.synchronize()
-            it_us = e0.elapsed_time(e1) * 10.0
-            ctx.timing_enable(True); ctx.timing_read(tdv.TIMER_ICP_NN)
-            run(100)
-            ms, launches = ctx.timing_read(tdv.TIMER_ICP_NN); ctx.timing_enable(False)
-            out = {"ns": ns, "form": form, "round": rnd, "search": ctx.last_icp_search(), "iteration_us": it_us, "nn_kernel_us": ms / launches * 1e3,
-                   "ns_per_point": ms / launches * 1e6 / ns}
+            e0.record()
+            for _ in range(reps): r = run(K)
+            e1.record(); e1.synchronize()
+            out = {"ns": ns, "form": form, "cache": cache, "trans": trans, "iters": K, "round": rnd, "search": ctx.last_icp_search(),
+                   "iteration_us": e0.elapsed_time(e1) * 1e3 / (K * reps), "n_corr": r.n_corr}
+            if hasattr(ctx, "last_icp_probe_misses"): out["probe_misses"] = ctx.last_icp_probe_misses()
+            if not args.no_timer:
+                ctx.timing_enable(True); ctx.timing_read(tdv.TIMER_ICP_NN)
+                run(K)
+                ms, launches = ctx.timing_read(tdv.TIMER_ICP_NN); ctx.timing_enable(False)
+                out.update({"nn_kernel_us": ms / launches * 1e3, "ns_per_point": ms / launches * 1e6 / ns})
             if form != "auto": out["ran"] = ctx.last_icp_launches()
             print(json.dumps(out), flush=True)
