@@ -70,6 +70,8 @@ ABI_SYMBOLS = [
     "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
     "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
     "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
+    "tdv_voxel_downsample_normals", "tdv_voxel_downsample_normals_dev",
+    "tdv_icp_level_default", "tdv_icp_multiscale", "tdv_icp_multiscale_dev", "tdv_icp_multiscale_batch_dev",
 ]
 
 
@@ -101,6 +103,56 @@ class InstanceResultC(C.Structure):
 class IcpResultC(C.Structure):
     _fields_ = [("T", C.c_float * 16), ("fitness", C.c_float), ("rmse", C.c_float), ("iterations", C.c_int),
                 ("n_corr", C.c_int)]
+
+
+class IcpLevelC(C.Structure):
+    _fields_ = [("voxel_size", C.c_float), ("max_correspondence_distance", C.c_float), ("max_iterations", C.c_int),
+                ("relative_fitness", C.c_float), ("relative_rmse", C.c_float)]
+
+
+class IcpLevelResultC(C.Structure):
+    _fields_ = [("icp", IcpResultC), ("ns", C.c_int), ("nt", C.c_int)]
+
+
+TDV_ICP_MAX_LEVELS = 8
+TDV_ICP_POINT_TO_PLANE, TDV_ICP_POINT_TO_POINT, TDV_ICP_GICP = 0, 1, 3
+ICP_ESTIMATION = {"point_to_plane": TDV_ICP_POINT_TO_PLANE, "point_to_point": TDV_ICP_POINT_TO_POINT, "gicp": TDV_ICP_GICP}
+
+
+def icp_levels(voxel_sizes, max_correspondence_distances, max_iterations=None, relative_fitness=None, relative_rmse=None):
+    """The tdv_icp_level array of a multi-scale schedule (include/tdv_hip.h: tdv_icp_multiscale).  voxel_sizes sets the number of levels
+    (a voxel size of None or <= 0, last level only: the clouds as given); the other arguments are one value per level or a scalar for
+    all of them, None: the library's default (tdv_icp_level_default: 30 iterations, relative_fitness inf, relative_rmse 1e-6)."""
+    voxels = [-1.0 if v is None else float(v) for v in (voxel_sizes if isinstance(voxel_sizes, (list, tuple, np.ndarray)) else [voxel_sizes])]
+    n = len(voxels)
+
+    def per_level(x, name):
+        if x is None:
+            return [None] * n
+        x = list(np.atleast_1d(x))
+        if len(x) == 1:
+            x = x * n
+        if len(x) != n:
+            raise ValueError("icp_levels: %s has %d values for %d levels" % (name, len(x), n))
+        return x
+    dist = per_level(max_correspondence_distances, "max_correspondence_distances")
+    its = per_level(max_iterations, "max_iterations")
+    rf = per_level(relative_fitness, "relative_fitness")
+    rr = per_level(relative_rmse, "relative_rmse")
+    levels = (IcpLevelC * max(n, 1))()
+    for l in range(n):
+        lib().tdv_icp_level_default(C.byref(levels[l]))
+        levels[l].voxel_size = voxels[l]
+        if dist[l] is not None:
+            levels[l].max_correspondence_distance = float(dist[l])
+        if its[l] is not None:
+            levels[l].max_iterations = int(its[l])
+        if rf[l] is not None:
+            levels[l].relative_fitness = float(rf[l])
+        if rr[l] is not None:
+            levels[l].relative_rmse = float(rr[l])
+    levels.n_levels = n
+    return levels
 
 
 def _params(stage, kw):
@@ -387,6 +439,7 @@ def lib():
             l.tdv_ctx_last_ransac_rescore.restype = C.c_double
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
             l.tdv_ctx_last_ransac_bound.restype = None
+            l.tdv_icp_level_default.restype = None
             for _, default_fn_name, _, _ in _PARAMS.values():
                 getattr(l, default_fn_name).restype = None
             _lib = l
@@ -458,6 +511,26 @@ class RegistrationResult:
     iterations_run: int = 0
     n_corr: int = 0
     trace_inliers: Optional[np.ndarray] = None
+    levels: Optional[list] = None     # multi_scale_icp: one IcpLevelResult per level, coarse to fine
+
+
+@dataclass
+class IcpLevelResult(RegistrationResult):
+    """One level of a multi-scale ICP call: the level's ICP result and the points of its two clouds."""
+    ns: int = 0
+    nt: int = 0
+
+
+def _icp_level_results(res, n_levels, b=0):
+    """The n_levels level results of instance b as the RegistrationResult of the last level, with all of them in .levels."""
+    levels = []
+    for l in range(n_levels):
+        r = res[b * n_levels + l]
+        levels.append(IcpLevelResult(transformation=from_colmajor16(r.icp.T), fitness=np.float32(r.icp.fitness), rmse=np.float32(r.icp.rmse),
+                                     iterations=r.icp.iterations, n_corr=r.icp.n_corr, ns=r.ns, nt=r.nt))
+    last = levels[-1]
+    return RegistrationResult(transformation=last.transformation.copy(), fitness=last.fitness, rmse=last.rmse, iterations=last.iterations,
+                              n_corr=last.n_corr, levels=levels)
 
 
 def _icp_result(r):
@@ -710,6 +783,19 @@ class Context:
                                                    n, C.byref(m)), "tdv_voxel_downsample")
         return oxyz[:m.value].copy(), (None if orgb is None else orgb[:m.value].copy())
 
+    def voxel_downsample_normals(self, xyz, normals, voxel, rgb=None, order=TDV_VOXEL_ORDER_REFERENCE):
+        """voxel_downsample with the normals kept: (xyz, unit mean normals, rgb or None) per voxel (include/tdv_hip.h:
+        tdv_voxel_downsample_normals)."""
+        xyz = _f32(xyz); nrm = _f32(normals); rgb = _f32(rgb)
+        n = len(xyz)
+        oxyz = np.empty((max(n, 1), 3), np.float32)
+        onrm = np.empty((max(n, 1), 3), np.float32) if nrm is not None else None
+        orgb = np.empty((max(n, 1), 3), np.float32) if rgb is not None else None
+        m = C.c_int()
+        _check(self._h, lib().tdv_voxel_downsample_normals(self._h, _ptr(xyz), _ptr(nrm), _ptr(rgb), n, C.c_float(voxel), order, _ptr(oxyz),
+                                                           _ptr(onrm), _ptr(orgb), n, C.byref(m)), "tdv_voxel_downsample_normals")
+        return oxyz[:m.value].copy(), (None if onrm is None else onrm[:m.value].copy()), (None if orgb is None else orgb[:m.value].copy())
+
     # ---------------------------------------------------------------- R4
     def estimate_normals(self, xyz, k=30, want_knn=False):
         xyz = _f32(xyz); n = len(xyz)
@@ -828,6 +914,71 @@ class Context:
         d_tgt = _upload_rows(self.device, tgt); d_tn = _upload_rows(self.device, tn)
         return self.gicp_batch_dev(d_src.data_ptr(), d_sn.data_ptr(), off, d_tgt.data_ptr(), d_tn.data_ptr(), len(tgt), T0s, thr,
                                    max_iterations, epsilon)
+
+    # ---------------------------------------------------------------- multi-scale ICP (include/tdv_hip.h: tdv_icp_multiscale)
+    @staticmethod
+    def _schedule(voxel_sizes, max_correspondence_distances, max_iterations, relative_fitness, relative_rmse, levels):
+        if levels is None:
+            levels = icp_levels(voxel_sizes, max_correspondence_distances, max_iterations, relative_fitness, relative_rmse)
+        return levels, getattr(levels, "n_levels", len(levels))
+
+    def multi_scale_icp(self, source, target, voxel_sizes, max_correspondence_distances, init, max_iterations=None,
+                        estimation="point_to_plane", target_normals=None, source_normals=None, relative_fitness=float("inf"), relative_rmse=1e-6,
+                        epsilon=1e-3, levels=None):
+        """Coarse-to-fine ICP over a voxel pyramid (Open3D's multi_scale_icp): level l downsamples both clouds at voxel_sizes[l] (None or
+        <= 0, last level only: as given) and refines the pose of the level before within max_correspondence_distances[l].  Scalars
+        broadcast over the levels; `levels` (icp_levels) replaces the per-level arguments.  The result of the last level, every level's in
+        .levels (with its point counts ns, nt)."""
+        src = _f32(source); tgt = _f32(target); tn = _f32(target_normals); sn = _f32(source_normals)
+        lv, n_levels = self._schedule(voxel_sizes, max_correspondence_distances, max_iterations, relative_fitness, relative_rmse, levels)
+        res = (IcpLevelResultC * max(n_levels, 1))()
+        t0 = to_colmajor16(init)
+        _check(self._h, lib().tdv_icp_multiscale(self._h, _ptr(src), _ptr(sn), len(src), _ptr(tgt), _ptr(tn), len(tgt), _ptr(t0), lv, n_levels,
+                                                 ICP_ESTIMATION[estimation], C.c_float(epsilon), res), "tdv_icp_multiscale")
+        return _icp_level_results(res, n_levels)
+
+    def multi_scale_icp_dev(self, d_src, ns, d_tgt, d_tgt_normals, nt, init, voxel_sizes=None, max_correspondence_distances=None, max_iterations=None,
+                            estimation="point_to_plane", d_src_normals=None, relative_fitness=float("inf"), relative_rmse=1e-6, epsilon=1e-3,
+                            levels=None):
+        """multi_scale_icp on device pointers."""
+        lv, n_levels = self._schedule(voxel_sizes, max_correspondence_distances, max_iterations, relative_fitness, relative_rmse, levels)
+        res = (IcpLevelResultC * max(n_levels, 1))()
+        t0 = to_colmajor16(init)
+        _check(self._h, lib().tdv_icp_multiscale_dev(self._h, _ptr(d_src), _ptr(d_src_normals), ns, _ptr(d_tgt), _ptr(d_tgt_normals), nt, _ptr(t0),
+                                                     lv, n_levels, ICP_ESTIMATION[estimation], C.c_float(epsilon), res), "tdv_icp_multiscale_dev")
+        return _icp_level_results(res, n_levels)
+
+    def multi_scale_icp_batch_dev(self, d_src, offsets, d_tgt, d_tgt_normals, nt, T0s, voxel_sizes=None, max_correspondence_distances=None,
+                                  max_iterations=None, estimation="point_to_plane", d_src_normals=None, relative_fitness=float("inf"),
+                                  relative_rmse=1e-6, epsilon=1e-3, levels=None):
+        """multi_scale_icp of many clouds against one target in one call (device pointers, laid out as icp_batch_dev's).  Per instance
+        what multi_scale_icp_dev returns for that cloud, bit for bit."""
+        lv, n_levels = self._schedule(voxel_sizes, max_correspondence_distances, max_iterations, relative_fitness, relative_rmse, levels)
+        off, n, t0, _ = _icp_batch_args(offsets, T0s)
+        res = (IcpLevelResultC * max(n * n_levels, 1))()
+        _check(self._h, lib().tdv_icp_multiscale_batch_dev(self._h, _ptr(d_src), _ptr(d_src_normals), _ptr(off), n, _ptr(d_tgt), _ptr(d_tgt_normals),
+                                                           nt, _ptr(t0), lv, n_levels, ICP_ESTIMATION[estimation], C.c_float(epsilon), res),
+               "tdv_icp_multiscale_batch_dev")
+        return [_icp_level_results(res, n_levels, b) for b in range(n)]
+
+    def multi_scale_icp_batch(self, sources, target, voxel_sizes, max_correspondence_distances, T0s, max_iterations=None,
+                              estimation="point_to_plane", target_normals=None, source_normals=None, relative_fitness=float("inf"),
+                              relative_rmse=1e-6, epsilon=1e-3, levels=None):
+        """multi_scale_icp_batch_dev on host clouds: a list of (n_b, 3) arrays (and their normals, GICP) against one target, uploaded with
+        torch; the offsets are made here."""
+        srcs, off = _instance_rows(sources)
+        d_sn = None
+        if source_normals is not None:
+            sns, offn = _instance_rows(source_normals)
+            if list(offn) != list(off):
+                raise ValueError("multi_scale_icp_batch: one normal per source point")
+            d_sn = _upload_rows(self.device, sns)
+        tgt = _f32(target); tn = _f32(target_normals)
+        d_src = _upload_rows(self.device, srcs); d_tgt = _upload_rows(self.device, tgt)
+        d_tn = _upload_rows(self.device, tn) if tn is not None else None
+        return self.multi_scale_icp_batch_dev(d_src.data_ptr(), off, d_tgt.data_ptr(), None if d_tn is None else d_tn.data_ptr(), len(tgt), T0s,
+                                              voxel_sizes, max_correspondence_distances, max_iterations, estimation,
+                                              None if d_sn is None else d_sn.data_ptr(), relative_fitness, relative_rmse, epsilon, levels)
 
     # ---------------------------------------------------------------- colored ICP (include/tdv_hip.h: tdv_colored_icp)
     def color_gradients(self, xyz, rgb, normals, k=30):
@@ -1518,6 +1669,14 @@ class Context:
         m = C.c_int()
         _check(self._h, lib().tdv_voxel_downsample_dev(self._h, _ptr(d_xyz), _ptr(d_rgb), n, C.c_float(voxel), order, _ptr(d_out_xyz),
                                                        _ptr(d_out_rgb), capacity, C.byref(m)), "tdv_voxel_downsample_dev")
+        return m.value
+
+    def voxel_downsample_normals_dev(self, d_xyz, d_normals, n, voxel, d_out_xyz, d_out_normals, capacity, d_rgb=None, d_out_rgb=None,
+                                     order=TDV_VOXEL_ORDER_FIRST):
+        m = C.c_int()
+        _check(self._h, lib().tdv_voxel_downsample_normals_dev(self._h, _ptr(d_xyz), _ptr(d_normals), _ptr(d_rgb), n, C.c_float(voxel), order,
+                                                               _ptr(d_out_xyz), _ptr(d_out_normals), _ptr(d_out_rgb), capacity, C.byref(m)),
+               "tdv_voxel_downsample_normals_dev")
         return m.value
 
 

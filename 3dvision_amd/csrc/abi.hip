@@ -169,6 +169,28 @@ int tdv_voxel_downsample(tdv_ctx* ctx, const float* xyz, const float* rgb, int n
     return finish(ctx);
 }
 
+int tdv_voxel_downsample_normals(tdv_ctx* ctx, const float* xyz, const float* normals, const float* rgb, int n, float voxel_size, int order,
+                                 float* out_xyz, float* out_normals, float* out_rgb, int capacity, int* n_out) {
+    if (!ctx || !n_out || n < 0 || capacity < 0 || (n > 0 && (!xyz || !out_xyz)) || !(voxel_size > 0.f)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    *n_out = 0;
+    if (n == 0) return TDV_OK;
+    float *d_xyz, *d_nrm, *d_rgb, *d_oxyz = nullptr, *d_onrm = nullptr, *d_orgb = nullptr;
+    TDV_TRY(upload(ctx, xyz, (size_t)n * 3, &d_xyz));
+    TDV_TRY(upload(ctx, out_normals ? normals : nullptr, (size_t)n * 3, &d_nrm));
+    TDV_TRY(upload(ctx, rgb, (size_t)n * 3, &d_rgb));
+    const int cap = std::min(capacity, n);
+    if (cap) TDV_TRY(ws_alloc(ctx, (size_t)cap * 3, &d_oxyz));
+    if (d_nrm && cap) TDV_TRY(ws_alloc(ctx, (size_t)cap * 3, &d_onrm));
+    if (rgb && out_rgb && cap) TDV_TRY(ws_alloc(ctx, (size_t)cap * 3, &d_orgb));
+    int st = voxel_downsample_dev(ctx, d_xyz, d_rgb, n, voxel_size, order, d_oxyz, d_orgb, cap, n_out, nullptr, VoxelNormals{d_nrm, d_onrm});
+    if (st != TDV_OK) return st;
+    TDV_TRY(download(ctx, out_xyz, d_oxyz, (size_t)*n_out * 3));
+    TDV_TRY(download(ctx, out_normals, d_onrm, (size_t)*n_out * 3));
+    TDV_TRY(download(ctx, out_rgb, d_orgb, (size_t)*n_out * 3));
+    return finish(ctx);
+}
+
 int tdv_estimate_normals(tdv_ctx* ctx, const float* xyz, int n, int k, float* out_normals, int* out_knn) {
     if (n < 0 || k <= 0 || (n > 0 && (!xyz || !out_normals))) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
@@ -416,6 +438,11 @@ int tdv_voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rg
                              float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out) {
     TDV_TRY(call_begin(ctx));
     return voxel_downsample_dev(ctx, d_xyz, d_rgb, n, voxel_size, order, d_out_xyz, d_out_rgb, capacity, n_out);
+}
+int tdv_voxel_downsample_normals_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, const float* d_rgb, int n, float voxel_size, int order,
+                                     float* d_out_xyz, float* d_out_normals, float* d_out_rgb, int capacity, int* n_out) {
+    TDV_TRY(call_begin(ctx));
+    return voxel_downsample_dev(ctx, d_xyz, d_rgb, n, voxel_size, order, d_out_xyz, d_out_rgb, capacity, n_out, nullptr, VoxelNormals{d_normals, d_out_normals});
 }
 
 }  // extern "C"

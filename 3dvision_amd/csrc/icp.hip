@@ -91,6 +91,8 @@ struct IcpState {
     float T[16];       // current transform, column-major
     float res_T[16];   // result.transformation
     float fitness, rmse;
+    float rel_fitness, rel_rmse;   // the call's convergence criteria, written when the call initialises the state and never after; icp_update reads
+                                   // them where the call's are not the defaults (ICP_RUN_CRITERIA)
     int n_corr;        // accepted correspondences of the last evaluated iteration
     int applied;       // iterations whose update was applied
     int done;          // loop finished (converged / n_corr < 3)
@@ -98,6 +100,13 @@ struct IcpState {
     int last_n_corr_applied;
     int probe_misses;  // lanes that probed the hash table over the call's iterations (the probe cache: grid_nearest); 0 without the cache
 };
+// How a kernel's iteration ends (the kernels' `fixed_iterations` argument, which only icp_update looks at): bit 0 - run on whatever the
+// rule says (benchmarking); bit 1 - the call's criteria are not the defaults, read them from the state.  A call with the default
+// criteria takes the reference's rule as a constant and reads nothing more than it did: read in the tail of every iteration, the three
+// words cost the one-launch iteration at 200k points 1.2 % (a round trip to memory before the solve's result can be judged); read
+// before the block's slab goes out, 7 %; carried from the kernel's start, two SGPRs and with them an occupancy step of a robust
+// k_icp_iterate (profiles/r23/icp_multiscale.md).
+constexpr int ICP_RUN_FIXED = 1, ICP_RUN_CRITERIA = 2;
 
 __global__ void k_aos_to_soa_pad(const float* __restrict__ aos, int n, int n_pad, float pad,
                                  float* __restrict__ x, float* __restrict__ y, float* __restrict__ z) {
@@ -506,8 +515,14 @@ __device__ __forceinline__ double wave_sum(double v) {
 // ROBUST (weighted sums, acc_terms): tot[acc_nv - 1] counts the correspondences of weight > 0, and point-to-point divides by the
 // weight sum tot[17] instead of n_corr.
 // MODE 3 (GICP) and MODE 4 (colored ICP) solve their systems as point-to-plane does.
+// The stopping rule is Open3D's ICPConvergenceCriteria: done iff !fixed_iterations && iter > 0 && |prev_fitness - fitness| < rel_fitness
+// && |prev_rmse - rmse| < rel_rmse, prev_* being what the previous applied iteration of this call wrote.  The two bounds are the state's
+// (written by init_states, read here and nowhere else); rel_fitness = +inf with rel_rmse = 1e-6f is the reference's rule
+// (registration.cpp:406: two finite fitness values always differ by less than +inf), and a call with exactly these runs without
+// ICP_RUN_CRITERIA: the constant rule, nothing read.
 template <int MODE, bool REF = false, bool ROBUST = false>
-__device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_iterations, int iter, float prev_rmse, const float* Tcur, float* solve_ws /* LDS, 54 words */) {
+__device__ void icp_update(const double* tot, int ns, IcpState* st, int run /* ICP_RUN_* */, int iter, float prev_rmse, const float* Tcur, float* solve_ws /* LDS, 54 words */) {
+    const bool fixed_iterations = (run & ICP_RUN_FIXED) != 0;
     static_assert(!(REF && ROBUST), "reference-order sums have no loss");
     static_assert(!(REF && MODE == 3), "reference-order sums have no GICP");
     static_assert(!(REF && MODE == 4), "reference-order sums have no colored ICP");
@@ -553,10 +568,14 @@ __device__ void icp_update(const double* tot, int ns, IcpState* st, int fixed_it
     for (int i = 0; i < 16; ++i) { st->T[i] = Tn[i]; st->res_T[i] = Tn[i]; }
     const float rmse = sqrtf((float)tot[1] / (float)n_corr);
     st->rmse = rmse;
-    st->fitness = (float)n_corr / (float)ns;
+    const float fitness = (float)n_corr / (float)ns;
+    bool converged;
+    if (run & ICP_RUN_CRITERIA) converged = fabsf(st->fitness - fitness) < st->rel_fitness && fabsf(prev_rmse - rmse) < st->rel_rmse;
+    else converged = fabsf(prev_rmse - rmse) < 1e-6f;  // registration.cpp:406
+    st->fitness = fitness;
     st->applied = iter + 1;
     st->last_n_corr_applied = n_corr;
-    if (!fixed_iterations && iter > 0 && fabsf(prev_rmse - rmse) < 1e-6f) st->done = 1;  // registration.cpp:406
+    if (!fixed_iterations && iter > 0 && converged) st->done = 1;
 }
 
 
@@ -1720,10 +1739,13 @@ int alloc_buffers(tdv_ctx* ctx, const NnPlan& p, IcpBuffers& b) {
     return TDV_OK;
 }
 
-// n states before the first iteration: start pose T0s + 16 b (host, column-major), everything else 0
-void init_states(IcpState* h, const float* T0s, int n) {
+// n states before the first iteration: start pose T0s + 16 b (host, column-major), the call's convergence criteria, everything else 0
+void init_states(IcpState* h, const float* T0s, int n, float rel_fitness = INFINITY, float rel_rmse = 1e-6f) {
     std::memset(h, 0, (size_t)n * sizeof(IcpState));
-    for (int b = 0; b < n; ++b) { std::memcpy(h[b].T, T0s + 16 * (size_t)b, 64); std::memcpy(h[b].res_T, T0s + 16 * (size_t)b, 64); }
+    for (int b = 0; b < n; ++b) {
+        std::memcpy(h[b].T, T0s + 16 * (size_t)b, 64); std::memcpy(h[b].res_T, T0s + 16 * (size_t)b, 64);
+        h[b].rel_fitness = rel_fitness; h[b].rel_rmse = rel_rmse;
+    }
 }
 
 // the result before any iteration: registration.cpp:309-311
@@ -1740,6 +1762,11 @@ void state_result(const IcpState& h, tdv_icp_result& out) {
 
 // the ctx's loss as the kernels take it, and whether it is a robust one (the ROBUST instantiations)
 IcpLoss ctx_loss(const tdv_ctx* ctx) { return IcpLoss{ctx->icp_loss, ctx->icp_loss_scale}; }
+// the kernels' `fixed_iterations` argument (ICP_RUN_*) of a call
+int run_flags(int fixed_iterations, const IcpObjective& obj) {
+    const bool defaults = obj.rel_fitness == INFINITY && obj.rel_rmse == 1e-6f;
+    return (fixed_iterations ? ICP_RUN_FIXED : 0) | (defaults ? 0 : ICP_RUN_CRITERIA);
+}
 bool ctx_robust(const tdv_ctx* ctx) { return ctx->icp_loss != TDV_ICP_LOSS_L2; }
 
 // The kernels' extra arguments from an objective of kind MODE
@@ -1786,7 +1813,7 @@ void launch_icp_small(tdv_ctx* ctx, int n_prob, const float* d_src, int ns, cons
     icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto REF) {
         constexpr int MODE = decltype(M)::value;
         k_icp_small<MODE, decltype(REF)::value, decltype(R)::value><<<n_prob, SM_THREADS, 0, ctx->stream>>>(
-            d_src, ns, d_src_off, d_tgt, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, nt, st_in, tau, max_iterations, fixed_iterations, ctx_loss(ctx),
+            d_src, ns, d_src_off, d_tgt, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, nt, st_in, tau, max_iterations, run_flags(fixed_iterations, obj), ctx_loss(ctx),
             st_out, st_host, kernel_args<MODE>(obj));
     });
 }
@@ -1865,7 +1892,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
     const IcpLoss loss = ctx_loss(ctx);
     TDV_TRY(pin_reserve(ctx, 2 * sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    init_states(h, T0, 1);
+    init_states(h, T0, 1, obj.rel_fitness, obj.rel_rmse);
     hipStream_t s = ctx->stream;
     // small problems: the whole loop in one launch (k_icp_small), same bits as the launches below
     if (pl.small) {
@@ -1932,6 +1959,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
 #endif
         return cached ? f(std::integral_constant<int, 1>{}) : f(std::integral_constant<int, 0>{});
     };
+    const int run = run_flags(fixed_iterations, obj);
     TDV_TRY(run_bursts(ctx, h, b.st, 1, max_iterations, fixed_iterations, [&]() {
         if (pl.one_launch) {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);      // the whole iteration: one launch
@@ -1941,7 +1969,7 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                     probe_dispatch([&](auto P) {
                         k_icp_iterate<MODE, decltype(R)::value, decltype(P)::value><<<p.acc_blocks, IT_THREADS, 0, s>>>(
                             d_src, ns, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, gtable, gnode, cg.mask, cg.shift, cg.inv_cell, b.st, tau,
-                            fixed_iterations, loss, b.slabs, b.ticket, pc);
+                            run, loss, b.slabs, b.ticket, pc);
                     });
             });
             ++iteration_no;
@@ -1968,11 +1996,11 @@ int icp_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt, co
                 k_icp_flags<<<ref_blocks, 256, 0, s>>>(ns, p.ns_pad, p.nsplit, b.pd2, b.st, tau, ref_cnt);
                 k_icp_scan_counts<<<1, 1024, 0, s>>>(ref_cnt, ref_blocks, b.st, ref_off);
                 k_icp_rows<MODE><<<ref_blocks, 256, 0, s>>>(d_src, ns, p.ns_pad, d_tgt, nrm, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, ref_off, ref_rec);
-                k_icp_fold_ref<MODE><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, fixed_iterations);
+                k_icp_fold_ref<MODE><<<1, 64 + REF_TILE, 0, s>>>(ref_rec, ref_off + ref_blocks, ns, b.st, run);
             } else {
                 ppt_dispatch(p.acc_ppt, [&](auto P) {
                     k_icp_accumulate<MODE, decltype(P)::value, decltype(R)::value><<<p.acc_blocks, 256, 0, s>>>(
-                        d_src, ns, p.ns_pad, d_tgt, nrm, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, fixed_iterations, loss, b.slabs, b.ticket,
+                        d_src, ns, p.ns_pad, d_tgt, nrm, b.tx, b.ty, b.tz, p.nsplit, b.pd2, b.pchunk, direct, b.st, tau, run, loss, b.slabs, b.ticket,
                         nullptr, nullptr, nullptr, kernel_args<MODE>(obj));
                 });
             }
@@ -2003,7 +2031,7 @@ int icp_small_batch_dev(tdv_ctx* ctx, const float* d_src, const int* d_src_off, 
     TDV_TRY(ws_alloc(ctx, (size_t)2 * n_prob, &d_st));
     TDV_TRY(pin_reserve(ctx, (size_t)n_prob * sizeof(IcpState)));
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    init_states(h, T0s, n_prob);
+    init_states(h, T0s, n_prob, obj.rel_fitness, obj.rel_rmse);
     TDV_HIP(ctx, hipMemcpyAsync(d_st, h, (size_t)n_prob * sizeof(IcpState), hipMemcpyHostToDevice, s));
     if (max_iterations > 0) {
         ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
@@ -2093,7 +2121,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     const size_t up_bytes = st_bytes + inst_bytes + ((size_t)nn_blocks + acc_blocks) * sizeof(int);
     TDV_TRY(pin_reserve(ctx, up_bytes));      // (after cell_grid_build, which reads its flags back through the same staging)
     IcpState* h = reinterpret_cast<IcpState*>(ctx->pin);
-    init_states(h, T0s, n);
+    init_states(h, T0s, n, obj.rel_fitness, obj.rel_rmse);
     for (int b = 0; b < n; ++b) if (h_count[b] == 0) h[b].done = 1;   // no points: n_corr = 0 < 3, the result is the start pose
     std::memcpy(ctx->pin + st_bytes, inst.data(), inst_bytes);
     int* h_blk = reinterpret_cast<int*>(ctx->pin + st_bytes + inst_bytes);
@@ -2121,6 +2149,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
     ctx->last_icp_search = TDV_ICP_SEARCH_GRID;
     ctx->last_icp_launches = TDV_ICP_LAUNCHES_TWO;
     ctx->last_icp_probe_misses = -1;
+    const int run = run_flags(fixed_iterations, obj);
     TDV_TRY(run_bursts(ctx, h, d_st, n,max_iterations, fixed_iterations, [&]() {
         {
             ScopedTimer tm(ctx, TDV_TIMER_ICP_NN);
@@ -2129,7 +2158,7 @@ int icp_batch_run_dev(tdv_ctx* ctx, const float* d_src, const int* h_start, cons
         icp_dispatch(ctx, obj, d_tgt_normals, [&](auto M, auto R, auto) {      // (tree sums: see above)
             constexpr int MODE = decltype(M)::value;
             k_icp_accumulate_multi<MODE, decltype(R)::value><<<acc_blocks, 256, 0, s>>>(
-                d_src, d_inst, d_blk_acc, d_tgt, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, pd2, pidx, d_st, tau, fixed_iterations, loss, slabs, tickets,
+                d_src, d_inst, d_blk_acc, d_tgt, MODE == ICP_POINT_TO_POINT ? nullptr : d_tgt_normals, pd2, pidx, d_st, tau, run, loss, slabs, tickets,
                 kernel_args<MODE>(obj));
         });
     }));

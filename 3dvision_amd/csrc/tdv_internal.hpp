@@ -174,6 +174,10 @@ struct IcpObjective {
     const float* src_normals; float c;                            // GICP
     const float *src_rgb, *tgt_color; float lg, lc;               // colored ICP
     float param;                                                  // epsilon resp. lambda as the caller gave it (icp_objective_check)
+    // when the loop stops (icp.hip: icp_update): |fitness change| < rel_fitness and |rmse change| < rel_rmse.  The defaults are the
+    // reference's rule (registration.cpp:406) and what every entry point but the multi-scale ones passes.
+    float rel_fitness = INFINITY, rel_rmse = 1e-6f;
+    IcpObjective criteria(float fitness, float rmse) const { IcpObjective o = *this; o.rel_fitness = fitness; o.rel_rmse = rmse; return o; }
     static IcpObjective plain(int point_to_plane) { return {point_to_plane ? ICP_POINT_TO_PLANE : ICP_POINT_TO_POINT, nullptr, 0.f, nullptr, nullptr, 0.f, 0.f, 0.f}; }
     static IcpObjective gicp(const float* src_normals, float epsilon) { return {ICP_GICP, src_normals, 1.f - epsilon, nullptr, nullptr, 0.f, 0.f, epsilon}; }
     static IcpObjective colored(const float* src_rgb, const float* tgt_color, float lambda) {
@@ -280,20 +284,25 @@ int compute_fpfh_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, i
 // With TDV_VOXEL_ORDER_REFERENCE, `both` (optional) also receives the cloud in first-occurrence order and the permutation
 // between the two orders: out_xyz[p] == first_xyz[ref2first[p]], first2ref[ref2first[p]] == p (each of capacity entries).
 struct VoxelBothOrders { float* first_xyz; int* ref2first; int* first2ref; };
+// The second 3-wide companion of a cloud, its normals (include/tdv_hip.h: tdv_voxel_downsample_normals): the input rows and where a
+// voxel's unit mean goes, each laid out like the points' array beside it.  Both pointers or neither; they ride the points' one
+// grouping pass, as the colours do.
+struct VoxelNormals { const float* in = nullptr; float* out = nullptr; };
 int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                         float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both = nullptr);
+                         float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both = nullptr,
+                         VoxelNormals nrm = VoxelNormals{});
 
 // batch: every cloud's voxels in first-occurrence order with one memset + two launches (voxel.hip); the reference order per cloud
 // pinhole4 (optional: fx, fy, cx, cy) + h_seg_off (the clouds' offsets on the host): the clouds were unprojected from a depth image with these
 // intrinsics, in row-major pixel order - they are then grouped through pixel windows in LDS instead of the table (voxel.hip: k_vs_group)
 int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, int total, const int* d_seg_off, int n_clouds, float voxel,
                                float* d_first_xyz, int* d_rank, int4* d_leaders, int* h_voff, int* overflowed, int* d_voff_keep = nullptr,
-                               const float* pinhole4 = nullptr, const int* h_seg_off = nullptr);
+                               const float* pinhole4 = nullptr, const int* h_seg_off = nullptr, VoxelNormals nrm = VoxelNormals{} /* not with pinhole4 */);
 // the reference's container order of every cloud of a batch, computed on the device (voxel.hip); h_failed[b] != 0: finish cloud b with voxel_reference_order
 int voxel_reference_order_batch_dev(tdv_ctx* ctx, int n_clouds, const int* h_voff, const int* d_voff, const int4* d_leaders, const float* d_first_xyz,
                                     float* d_out_xyz, int* d_ref2first, int* d_first2ref, int* h_failed);
 int voxel_reference_order(tdv_ctx* ctx, int v, int n, const int4* d_leaders, const float* tmp_xyz, const float* tmp_rgb, const int* d_rank, int rank_base,
-                          float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both);
+                          float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both, VoxelNormals nrm = VoxelNormals{});
 
 int sort_records_dev(tdv_ctx* ctx, uint4* rec, size_t n_pow2);  // sort.hip: ascending bitonic sort, n_pow2 >= 2048
 // sort.hip: stable LSD radix sort (hand-written) of (key, value) pairs on the low end_bit bits of the 64-bit key; any n; scratch from the workspace

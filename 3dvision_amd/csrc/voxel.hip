@@ -20,16 +20,27 @@
 // point of every voxel changes a container, so the host receives 16 B per VOXEL (cell + input index) from the
 // device and nothing else: the cloud stays in HBM, which is what lets the batched chain run in the reference's order.
 #include "tdv_internal.hpp"
+#include <cfloat>
 #include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 #include <vector>
 #include <algorithm>
 
 namespace tdv {
 
+// A voxel's normal (include/tdv_hip.h, tdv_voxel_downsample_normals): the mean of its members' normals - the colours' expression, f32
+// sums in ascending input index divided by (float)count - brought to unit length in f32 without contraction, the squared length in the
+// reference's three-term order (sorted_cloud.hpp: d2_sum<D2::REF>).  A mean of length 0 (normals that cancel) or of a length that is
+// not finite (a NaN or infinite member, an overflowing square) stays as it is.
+__device__ __forceinline__ void voxel_unit_normal(float& mx, float& my, float& mz) {
+    const float l2 = mx * mx + (my * my + mz * mz);
+    const float l = sqrtf(l2);
+    if (l2 > 0.f && l <= FLT_MAX) { mx = mx / l; my = my / l; mz = mz / l; }
+}
 
 __global__ void k_voxel_records(const float* __restrict__ xyz, int n, int n_pow2, float inv, uint4* __restrict__ rec) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -84,8 +95,9 @@ __global__ void k_voxel_scatter(const uint4* __restrict__ rec_in, int n, unsigne
 // the leader flags, after which k_voxel_compact moves it there.
 // The bucket's records sorted by (cell, index), its voxels emitted.  `a` points at the bucket's records - in LDS (the normal case:
 // the workgroup's 256 buckets are one contiguous stretch of the record array, staged with coalesced loads) or in global memory.
+template <bool NRM>
 __device__ __forceinline__ void voxel_emit_bucket(uint4* a, int m, const float* __restrict__ xyz, const float* __restrict__ rgb,
-                                                  int* __restrict__ leader, float* __restrict__ mean_xyz, float* __restrict__ mean_rgb) {
+                                                  int* __restrict__ leader, float* __restrict__ mean_xyz, float* __restrict__ mean_rgb, VoxelNormals nrm) {
     for (int e = 1; e < m; ++e) {   // insertion sort by (x, y, z, index)
         const uint4 key = a[e];
         int f = e - 1;
@@ -94,7 +106,7 @@ __device__ __forceinline__ void voxel_emit_bucket(uint4* a, int m, const float* 
     }
     for (int e = 0; e < m;) {
         const uint4 r = a[e];
-        float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+        float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
         int cnt = 0;
         for (; e < m; ++e) {
             const uint4 q = a[e];
@@ -102,6 +114,7 @@ __device__ __forceinline__ void voxel_emit_bucket(uint4* a, int m, const float* 
             const size_t idx = q.w;
             ax += xyz[3 * idx]; ay += xyz[3 * idx + 1]; az += xyz[3 * idx + 2];        // registration.cpp:47-50, ascending input index
             if (rgb) { cr += rgb[3 * idx]; cg += rgb[3 * idx + 1]; cb += rgb[3 * idx + 2]; }
+            if (NRM) { nx += nrm.in[3 * idx]; ny += nrm.in[3 * idx + 1]; nz += nrm.in[3 * idx + 2]; }
             ++cnt;
         }
         const float fn = (float)cnt;
@@ -109,13 +122,19 @@ __device__ __forceinline__ void voxel_emit_bucket(uint4* a, int m, const float* 
         leader[l] = 1;
         mean_xyz[3 * l] = ax / fn; mean_xyz[3 * l + 1] = ay / fn; mean_xyz[3 * l + 2] = az / fn;   // :52-53
         if (rgb && mean_rgb) { mean_rgb[3 * l] = cr / fn; mean_rgb[3 * l + 1] = cg / fn; mean_rgb[3 * l + 2] = cb / fn; }
+        if (NRM) {
+            float mx = nx / fn, my = ny / fn, mz = nz / fn;
+            voxel_unit_normal(mx, my, mz);
+            nrm.out[3 * l] = mx; nrm.out[3 * l + 1] = my; nrm.out[3 * l + 2] = mz;
+        }
     }
 }
 constexpr int VX_LDS_REC = 1024;   // records of a workgroup's 256 buckets staged in LDS (16 KB); a denser stretch sorts in global memory
+template <bool NRM>
 __global__ __launch_bounds__(256)
 void k_voxel_bucket_emit(uint4* __restrict__ rec, const int* __restrict__ start, const int* __restrict__ hist, int nbuckets, int n_rec,
                          int* __restrict__ too_big, const float* __restrict__ xyz, const float* __restrict__ rgb,
-                         int* __restrict__ leader, float* __restrict__ mean_xyz, float* __restrict__ mean_rgb) {
+                         int* __restrict__ leader, float* __restrict__ mean_xyz, float* __restrict__ mean_rgb, VoxelNormals nrm /* out: parked at the leader, like mean_rgb */) {
     // The insertion sort is a chain of dependent loads and stores: through global memory every step is a round trip of about a
     // microsecond and the kernel's time was that of its fullest bucket (42 us at 200k points with lanes alive for 3 us on
     // average); through LDS a step costs a hundred cycles: 25 us.  (Staging the records' points in LDS as well, so that the sums
@@ -130,18 +149,20 @@ void k_voxel_bucket_emit(uint4* __restrict__ rec, const int* __restrict__ start,
     const int m = hist[b];
     if (m == 0) return;
     if (m > VX_MAX_BUCKET) { *too_big = 1; return; }
-    if (staged) voxel_emit_bucket(s_rec + (start[b] - base), m, xyz, rgb, leader, mean_xyz, mean_rgb);
-    else voxel_emit_bucket(rec + start[b], m, xyz, rgb, leader, mean_xyz, mean_rgb);
+    if (staged) voxel_emit_bucket<NRM>(s_rec + (start[b] - base), m, xyz, rgb, leader, mean_xyz, mean_rgb, nrm);
+    else voxel_emit_bucket<NRM>(rec + start[b], m, xyz, rgb, leader, mean_xyz, mean_rgb, nrm);
 }
 // out[rank[i]] = mean parked at leader i
 __global__ void k_voxel_compact(const int* __restrict__ leader, const int* __restrict__ rank, int n, const float* __restrict__ mean_xyz,
-                                const float* __restrict__ mean_rgb, int capacity, float* __restrict__ out_xyz, float* __restrict__ out_rgb) {
+                                const float* __restrict__ mean_rgb, int capacity, float* __restrict__ out_xyz, float* __restrict__ out_rgb,
+                                VoxelNormals nrm /* in: parked at the leaders; both NULL without normals */) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n || !leader[i]) return;
     const int slot = rank[i];
     if (slot >= capacity) return;
     out_xyz[3 * (size_t)slot] = mean_xyz[3 * (size_t)i]; out_xyz[3 * (size_t)slot + 1] = mean_xyz[3 * (size_t)i + 1]; out_xyz[3 * (size_t)slot + 2] = mean_xyz[3 * (size_t)i + 2];
     if (mean_rgb && out_rgb) { out_rgb[3 * (size_t)slot] = mean_rgb[3 * (size_t)i]; out_rgb[3 * (size_t)slot + 1] = mean_rgb[3 * (size_t)i + 1]; out_rgb[3 * (size_t)slot + 2] = mean_rgb[3 * (size_t)i + 2]; }
+    if (nrm.in && nrm.out) { nrm.out[3 * (size_t)slot] = nrm.in[3 * (size_t)i]; nrm.out[3 * (size_t)slot + 1] = nrm.in[3 * (size_t)i + 1]; nrm.out[3 * (size_t)slot + 2] = nrm.in[3 * (size_t)i + 2]; }
 }
 
 // leader[idx] = 1 for the smallest input index of each voxel
@@ -165,16 +186,17 @@ __global__ void k_voxel_leader_list(const int* __restrict__ leader, const int* _
 }
 
 // one lane per run head: sequential sum over the run (ascending input index), mean -> out[rank]
+template <bool NRM>
 __global__ __launch_bounds__(256)
 void k_voxel_means(const uint4* __restrict__ rec, int n, const float* __restrict__ xyz, const float* __restrict__ rgb,
-                   const int* __restrict__ rank, int capacity, float* __restrict__ out_xyz, float* __restrict__ out_rgb) {
+                   const int* __restrict__ rank, int capacity, float* __restrict__ out_xyz, float* __restrict__ out_rgb, VoxelNormals nrm) {
     int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     uint4 r = rec[p];
     if (p > 0) { uint4 q = rec[p - 1]; if (q.x == r.x && q.y == r.y && q.z == r.z) return; }
     const int slot = rank[r.w];
     if (slot >= capacity) return;
-    float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+    float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
     int cnt = 0;
     for (int e = p; e < n; ++e) {
         uint4 m = rec[e];
@@ -182,23 +204,30 @@ void k_voxel_means(const uint4* __restrict__ rec, int n, const float* __restrict
         const unsigned idx = m.w;
         ax += xyz[3 * (size_t)idx]; ay += xyz[3 * (size_t)idx + 1]; az += xyz[3 * (size_t)idx + 2];
         if (rgb) { cr += rgb[3 * (size_t)idx]; cg += rgb[3 * (size_t)idx + 1]; cb += rgb[3 * (size_t)idx + 2]; }
+        if (NRM) { nx += nrm.in[3 * (size_t)idx]; ny += nrm.in[3 * (size_t)idx + 1]; nz += nrm.in[3 * (size_t)idx + 2]; }
         ++cnt;
     }
     const float fn = (float)cnt;
     out_xyz[3 * (size_t)slot] = ax / fn; out_xyz[3 * (size_t)slot + 1] = ay / fn; out_xyz[3 * (size_t)slot + 2] = az / fn;
     if (rgb && out_rgb) { out_rgb[3 * (size_t)slot] = cr / fn; out_rgb[3 * (size_t)slot + 1] = cg / fn; out_rgb[3 * (size_t)slot + 2] = cb / fn; }
+    if (NRM) {
+        float mx = nx / fn, my = ny / fn, mz = nz / fn;
+        voxel_unit_normal(mx, my, mz);
+        nrm.out[3 * (size_t)slot] = mx; nrm.out[3 * (size_t)slot + 1] = my; nrm.out[3 * (size_t)slot + 2] = mz;
+    }
 }
 
 // out[p] = in[rank[order_first[p]]]
 __global__ void k_voxel_permute(const float* __restrict__ in_xyz, const float* __restrict__ in_rgb, const int* __restrict__ rank, int rank_base,
                                 const int* __restrict__ order_first, int v, float* __restrict__ out_xyz, float* __restrict__ out_rgb,
-                                int* __restrict__ ref2first, int* __restrict__ first2ref) {
+                                int* __restrict__ ref2first, int* __restrict__ first2ref, VoxelNormals nrm /* in: first-occurrence order; both NULL without normals */) {
     int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= v) return;
     int s = rank[order_first[p]] - rank_base;     // (rank_base: the cloud's first voxel when ranks count through several clouds)
     if (ref2first) { ref2first[p] = s; first2ref[s] = p; }
     out_xyz[3 * (size_t)p] = in_xyz[3 * (size_t)s]; out_xyz[3 * (size_t)p + 1] = in_xyz[3 * (size_t)s + 1]; out_xyz[3 * (size_t)p + 2] = in_xyz[3 * (size_t)s + 2];
     if (in_rgb && out_rgb) { out_rgb[3 * (size_t)p] = in_rgb[3 * (size_t)s]; out_rgb[3 * (size_t)p + 1] = in_rgb[3 * (size_t)s + 1]; out_rgb[3 * (size_t)p + 2] = in_rgb[3 * (size_t)s + 2]; }
+    if (nrm.in && nrm.out) { nrm.out[3 * (size_t)p] = nrm.in[3 * (size_t)s]; nrm.out[3 * (size_t)p + 1] = nrm.in[3 * (size_t)s + 1]; nrm.out[3 * (size_t)p + 2] = nrm.in[3 * (size_t)s + 2]; }
 }
 
 // ---- grouping through a hash table: memset + 2 kernels for any number of clouds (round 3; the default) -------------------
@@ -502,7 +531,7 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
 // the leaders per tile (tile_sums), [exclusive scan], emit with the scanned prefix (tile_prefix): with tens of thousands of tiles the
 // look-back's polling (device-scope loads in a loop from every tile in flight) slows the whole memory system down - 61 us of waiting
 // per tile and 51 us for a leader wave's gathers in a batch of 256 clouds, against 9 and 18 us for one cloud.
-template <int MODE>
+template <int MODE, bool NRM>
 __global__ __launch_bounds__(VH_BLOCK)
 void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb, int total, const int* __restrict__ seg_off, int nseg, float inv,
                    const int* __restrict__ voxel_of, const int* __restrict__ vcnt, const int* __restrict__ members,
@@ -512,7 +541,8 @@ void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb,
                    const int* __restrict__ overflow_flag, int* __restrict__ host_result /* optional, pinned host memory: {voxels, overflow flag} */,
                    int* __restrict__ tile_sums /* MODE 1 */, const int* __restrict__ tile_prefix /* MODE 2 */,
                    int leader_known /* voxel_of[g] IS the voxel's smallest index (k_vs_group): only the leaders look at counts and rows */,
-                   const float* __restrict__ mean_at /* with leader_known: the leaders' means are ready, at their own indices */) {
+                   const float* __restrict__ mean_at /* with leader_known: the leaders' means are ready, at their own indices */,
+                   VoxelNormals nrm /* NRM: the clouds' normals and their voxels' unit means, laid out like xyz and out_xyz (never with leader_known) */) {
     __shared__ int s_ticket, s_excl, s_wave[VH_BLOCK / 64];
     if (*overflow_flag == VS_FAILED) {          // k_vs_group gave up on a tile: voxel_of is not valid, nothing here may follow it - the caller redoes the call
         if (blockIdx.x == 0 && threadIdx.x == 0) { voff[nseg + 1] = VS_FAILED; if (host_result) { host_result[0] = 0; host_result[1] = VS_FAILED; __threadfence_system(); } }
@@ -612,7 +642,7 @@ void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb,
         return;
     }
     // ascending index order without moving anything: cnt rounds of "smallest index above the last one"
-    float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f;
+    float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
     int last = -1;
     for (int r = 0; r < cnt; ++r) {
         int nxt = VH_EMPTY;
@@ -622,6 +652,7 @@ void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb,
         const size_t idx = (size_t)nxt;
         ax += xyz[3 * idx]; ay += xyz[3 * idx + 1]; az += xyz[3 * idx + 2];        // registration.cpp:47-50, ascending input index
         if (rgb) { cr += rgb[3 * idx]; cg += rgb[3 * idx + 1]; cb += rgb[3 * idx + 2]; }
+        if (NRM) { nx += nrm.in[3 * idx]; ny += nrm.in[3 * idx + 1]; nz += nrm.in[3 * idx + 2]; }
     }
     const float fn = (float)cnt;
     const size_t o = (size_t)run;
@@ -629,6 +660,11 @@ void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb,
     if (run >= capacity) return;                          // the caller's buffer is too small: it learns the count and gets an error
     out_xyz[3 * o] = ax / fn; out_xyz[3 * o + 1] = ay / fn; out_xyz[3 * o + 2] = az / fn;   // :52-53
     if (rgb && out_rgb) { out_rgb[3 * o] = cr / fn; out_rgb[3 * o + 1] = cg / fn; out_rgb[3 * o + 2] = cb / fn; }
+    if (NRM) {
+        float mx = nx / fn, my = ny / fn, mz = nz / fn;
+        voxel_unit_normal(mx, my, mz);
+        nrm.out[3 * o] = mx; nrm.out[3 * o + 1] = my; nrm.out[3 * o + 2] = mz;
+    }
     if (leaders) { int cx, cy, cz; vh_cell(xyz, (size_t)g, inv, cx, cy, cz); leaders[o] = make_int4(cx, cy, cz, g - lo); }
 }
 
@@ -638,8 +674,11 @@ void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb,
 static int voxel_hash_first_order(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int total, const int* d_seg_off, int nseg, float voxel,
                                   float* d_out_xyz, float* d_out_rgb, int capacity, int* d_rank /* optional, total ints */,
                                   int4* d_leaders /* optional, capacity entries */, int* d_voff, int* h_result /* optional: pinned {voxels, overflow flag} */,
-                                  const VoxelPinhole* pinhole = nullptr, const int* h_seg_off = nullptr /* with pinhole: nseg + 1 host offsets */) {
+                                  const VoxelPinhole* pinhole = nullptr, const int* h_seg_off = nullptr /* with pinhole: nseg + 1 host offsets */,
+                                  VoxelNormals nrm = VoxelNormals{nullptr, nullptr} /* both or neither; never with pinhole */) {
     hipStream_t s = ctx->stream;
+    const bool with_nrm = nrm.in && nrm.out;
+    if (with_nrm && pinhole) return TDV_ERR_BAD_ARG;      // (k_vs_group sums the points only)
     const float inv = 1.0f / voxel;  // registration.cpp:32
     const bool grouped_by_pixels = pinhole && h_seg_off && d_seg_off;      // k_vs_group instead of the table (the caller redoes the call without it if a tile fails)
     const int tiles = (total + VH_ITEMS - 1) / VH_ITEMS;
@@ -680,19 +719,27 @@ static int voxel_hash_first_order(tdv_ctx* ctx, const float* d_xyz, const float*
     // (measured, us per call one pass / split: 184k points in pixel order 65 / 76; random order 250k 82 / 74, 500k 138 / 103, 1M 233 / 160, 4M 858 / 550;
     //  256 clouds of 184k 8,100 / 4,400 - tools/studies/voxel_split_threshold.py)
     static const int split_from = study_env("TDV_VOXEL_SPLIT_FROM") ? atoi(study_env("TDV_VOXEL_SPLIT_FROM")) : 224;   // tiles; tuning knob
+    // the finalize kernel of mode M, with the normals riding along (NRM) or not: the same grouping pass either way
+    const auto finalize = [&](auto M, int* tile_sums, const int* tile_prefix) {
+        constexpr int MODE = decltype(M)::value;
+        if (with_nrm)
+            k_vh_finalize<MODE, true><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
+                                                                 d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, tile_sums, tile_prefix, 0, mean_at, nrm);
+        else
+            k_vh_finalize<MODE, false><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
+                                                                  d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, tile_sums, tile_prefix,
+                                                                  grouped_by_pixels ? 1 : 0, mean_at, nrm);
+    };
     if (tiles < split_from)
-        k_vh_finalize<0><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
-                                                    d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, nullptr, nullptr, grouped_by_pixels ? 1 : 0, mean_at);
+        finalize(std::integral_constant<int, 0>{}, nullptr, nullptr);
     else {      // large inputs (a batch): count, scan, emit - launches without a wait inside
         int *tile_sums, *tile_prefix, *d_tot;
         TDV_TRY(ws_alloc(ctx, (size_t)tiles, &tile_sums));
         TDV_TRY(ws_alloc(ctx, (size_t)tiles, &tile_prefix));
         TDV_TRY(ws_alloc(ctx, 1, &d_tot));
-        k_vh_finalize<1><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
-                                                    d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, tile_sums, nullptr, grouped_by_pixels ? 1 : 0, mean_at);
+        finalize(std::integral_constant<int, 1>{}, tile_sums, nullptr);
         TDV_TRY(exclusive_scan_dev(ctx, tile_sums, tiles, tile_prefix, d_tot));
-        k_vh_finalize<2><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
-                                                    d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, nullptr, tile_prefix, grouped_by_pixels ? 1 : 0, mean_at);
+        finalize(std::integral_constant<int, 2>{}, nullptr, tile_prefix);
     }
     TDV_CHECK_LAUNCH(ctx);
     return TDV_OK;
@@ -785,22 +832,23 @@ private:
 }  // namespace
 
 static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                                 float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both);
+                                 float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both, VoxelNormals nrm);
 
 int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                         float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both) {
+                         float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both, VoxelNormals nrm) {
     if (!ctx || !n_out || n < 0 || capacity < 0 || !(voxel > 0.f) || (n > 0 && !d_xyz)) return TDV_ERR_BAD_ARG;
+    if (!nrm.in || !nrm.out) nrm = VoxelNormals{nullptr, nullptr};     // (as the colours: both arrays or no normals)
     if (order != TDV_VOXEL_ORDER_FIRST && order != TDV_VOXEL_ORDER_REFERENCE) return TDV_ERR_BAD_ARG;
     if (both && (order != TDV_VOXEL_ORDER_REFERENCE || !both->first_xyz || !both->ref2first || !both->first2ref)) return TDV_ERR_BAD_ARG;
     *n_out = 0;
     if (n == 0) return TDV_OK;
     const bool legacy = study_env("TDV_VOXEL_LEGACY") != nullptr || study_env("TDV_VOXEL_SORT") != nullptr;   // A/B knobs: the counting-sort path / the full sort (read per call: the tests switch it)
-    if (legacy) return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, false, both);
+    if (legacy) return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, false, both, nrm);
     // hash-table path (memset + 2 kernels); first-occurrence order lands in the caller's buffer directly
     hipStream_t s = ctx->stream;
     const bool ref = order == TDV_VOXEL_ORDER_REFERENCE;
     int *d_voff, *d_rank = nullptr; int4* d_leaders = nullptr;
-    float *tmp_xyz = d_out_xyz, *tmp_rgb = d_out_rgb;
+    float *tmp_xyz = d_out_xyz, *tmp_rgb = d_out_rgb, *tmp_nrm = nrm.out;
     int cap_first = capacity;
     TDV_TRY(ws_alloc(ctx, 3, &d_voff));
     if (ref) {
@@ -810,6 +858,7 @@ int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, i
         if (both) tmp_xyz = both->first_xyz; else TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &tmp_xyz));
         tmp_rgb = nullptr;
         if (d_rgb && d_out_rgb) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &tmp_rgb));
+        if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &tmp_nrm));
     }
     TDV_TRY(pin_reserve(ctx, 64));
     int* h = reinterpret_cast<int*>(ctx->pin);      // the finalize kernel stores {voxel count, overflow flag} here itself: a D2H copy of 8 bytes is a 9-us blit kernel
@@ -817,12 +866,12 @@ int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, i
     {
         ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
         TDV_TRY(voxel_hash_first_order(ctx, d_xyz, (d_rgb && d_out_rgb) ? d_rgb : nullptr, n, nullptr, 1, voxel, tmp_xyz, tmp_rgb, cap_first, d_rank, d_leaders,
-                                       d_voff, h));
+                                       d_voff, h, nullptr, nullptr, VoxelNormals{nrm.in, tmp_nrm}));
     }
     TDV_HIP(ctx, hipStreamSynchronize(s));
     if (h[0] < 0) { snprintf(ctx->err, sizeof(ctx->err), "voxel: the result did not reach the host"); return TDV_ERR_INTERNAL; }
     if (h[1] != VH_EMPTY)      // a voxel with more than VH_K members (a coarse grid): the counting-sort path takes any count
-        return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, false, both);
+        return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, false, both, nrm);
     const int v = h[0];
     *n_out = v;
     if (v > capacity) return TDV_ERR_BAD_ARG;
@@ -841,15 +890,16 @@ int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, i
         TDV_HIP(ctx, hipMemcpyAsync(d_voff1, h_voff1, 8, hipMemcpyHostToDevice, s));
         TDV_TRY(voxel_reference_order_batch_dev(ctx, 1, h_voff1, d_voff1, d_leaders, tmp_xyz, d_out_xyz, r2f, f2r, &failed));
         if (!failed) {
-            if (tmp_rgb && d_out_rgb) {
-                k_gather_rows3<<<(v + 255) / 256, 256, 0, s>>>(tmp_rgb, r2f, v, d_out_rgb);
+            if (tmp_rgb && d_out_rgb) k_gather_rows3<<<(v + 255) / 256, 256, 0, s>>>(tmp_rgb, r2f, v, d_out_rgb);
+            if (nrm.in) k_gather_rows3<<<(v + 255) / 256, 256, 0, s>>>(tmp_nrm, r2f, v, nrm.out);
+            if ((tmp_rgb && d_out_rgb) || nrm.in) {
                 TDV_CHECK_LAUNCH(ctx);
                 TDV_HIP(ctx, hipStreamSynchronize(s));
             }
             return TDV_OK;
         }
     }
-    return voxel_reference_order(ctx, v, n, d_leaders, tmp_xyz, tmp_rgb, d_rank, 0, d_out_xyz, d_out_rgb, both);
+    return voxel_reference_order(ctx, v, n, d_leaders, tmp_xyz, tmp_rgb, d_rank, 0, d_out_xyz, d_out_rgb, both, VoxelNormals{tmp_nrm, nrm.out});
 }
 
 // ---- the reference's container order ON THE DEVICE, for all clouds of a batch (round 3) ---------------------------------
@@ -1003,9 +1053,11 @@ int voxel_reference_order_batch_dev(tdv_ctx* ctx, int n_clouds, const int* h_vof
 // [h_voff[b], h_voff[b + 1]) of d_first_xyz (room for `total` points); d_rank / d_leaders (optional, `total` entries each) are what
 // voxel_reference_order needs.  *overflowed: a voxel held more than VH_K points - nothing of the output is valid, the caller
 // falls back to per-cloud calls.  d_voff_keep (optional): n_clouds + 2 device ints that receive the voxel offsets.  Synchronizes once.
+// nrm (optional): the clouds' normals, laid out like d_xyz, and their voxels' unit means, laid out like d_first_xyz - from the same pass.
 int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, int total, const int* d_seg_off, int n_clouds, float voxel,
                                float* d_first_xyz, int* d_rank, int4* d_leaders, int* h_voff, int* overflowed, int* d_voff_keep,
-                               const float* pinhole4, const int* h_seg_off) {
+                               const float* pinhole4, const int* h_seg_off, VoxelNormals nrm) {
+    if (nrm.in && nrm.out && pinhole4) return TDV_ERR_BAD_ARG;       // (the pixel windows sum the points only)
     if (!ctx || n_clouds < 1 || total < 0 || !(voxel > 0.f) || !h_voff || !overflowed) return TDV_ERR_BAD_ARG;
     *overflowed = 0;
     for (int b = 0; b <= n_clouds; ++b) h_voff[b] = 0;
@@ -1029,7 +1081,7 @@ int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, int total, cons
         {
             ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
             TDV_TRY(voxel_hash_first_order(ctx, d_xyz, nullptr, total, d_seg_off, n_clouds, voxel, d_first_xyz, nullptr, total, d_rank, d_leaders, d_voff, nullptr,
-                                           by_pixels ? &cam : nullptr, by_pixels ? seg_copy.data() : nullptr));
+                                           by_pixels ? &cam : nullptr, by_pixels ? seg_copy.data() : nullptr, nrm));
         }
         TDV_TRY(pin_reserve(ctx, ((size_t)n_clouds + 2) * 4));
         h = reinterpret_cast<int*>(ctx->pin);
@@ -1045,7 +1097,7 @@ int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, int total, cons
 }
 
 static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                                 float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both) {
+                                 float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both, VoxelNormals nrm) {
     if (!ctx || !n_out || n < 0 || capacity < 0 || !(voxel > 0.f) || (n > 0 && !d_xyz)) return TDV_ERR_BAD_ARG;
     if (order != TDV_VOXEL_ORDER_FIRST && order != TDV_VOXEL_ORDER_REFERENCE) return TDV_ERR_BAD_ARG;
     if (both && (order != TDV_VOXEL_ORDER_REFERENCE || !both->first_xyz || !both->ref2first || !both->first2ref)) return TDV_ERR_BAD_ARG;
@@ -1063,7 +1115,7 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
     static const bool force_sort = study_env("TDV_VOXEL_SORT") != nullptr;   // A/B knob: the full bitonic sort
     bool hashed = !force_sort && !full_sort;
     int* d_too_big = nullptr;
-    float *mean_xyz = nullptr, *mean_rgb = nullptr;     // hashed path: means parked at their leader's input index
+    float *mean_xyz = nullptr, *mean_rgb = nullptr, *mean_nrm = nullptr;     // hashed path: means parked at their leader's input index
     if (hashed) {
         // 9 launches (round 1: 15): one memset, cell histogram, scan (2), scatter, bucket sort + leaders + means, scan (2), compact
         size_t nb = 4096;
@@ -1076,11 +1128,17 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
         TDV_TRY(ws_alloc(ctx, (size_t)n, &rec_in));
         TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_xyz));
         if (d_rgb && d_out_rgb) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_rgb));
+        if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_nrm));
         TDV_HIP(ctx, hipMemsetAsync(zeroed, 0, (2 * nb + 1 + (size_t)n) * 4, s));
         k_voxel_hist<<<(n + 255) / 256, 256, 0, s>>>(d_xyz, n, inv, (unsigned)(nb - 1), rec_in, hist);
         TDV_TRY(exclusive_scan_dev(ctx, hist, (int)nb, start, d_tot2));
         k_voxel_scatter<<<(n + 255) / 256, 256, 0, s>>>(rec_in, n, (unsigned)(nb - 1), start, cursor, rec);
-        k_voxel_bucket_emit<<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(rec, start, hist, (int)nb, n, d_too_big, d_xyz, mean_rgb ? d_rgb : nullptr, leader, mean_xyz, mean_rgb);
+        if (nrm.in)
+            k_voxel_bucket_emit<true><<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(rec, start, hist, (int)nb, n, d_too_big, d_xyz, mean_rgb ? d_rgb : nullptr, leader, mean_xyz, mean_rgb,
+                                                                                 VoxelNormals{nrm.in, mean_nrm});
+        else
+            k_voxel_bucket_emit<false><<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(rec, start, hist, (int)nb, n, d_too_big, d_xyz, mean_rgb ? d_rgb : nullptr, leader, mean_xyz, mean_rgb,
+                                                                                  VoxelNormals{nullptr, nullptr});
     } else {
         TDV_TRY(ws_alloc(ctx, (size_t)n, &leader));
         k_voxel_records<<<(unsigned)((n_pow2 + 255) / 256), 256, 0, s>>>(d_xyz, n, (int)n_pow2, inv, rec);
@@ -1095,13 +1153,18 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
     if (hashed) TDV_HIP(ctx, hipMemcpyAsync(h_total + 1, d_too_big, 4, hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipStreamSynchronize(s));
     if (hashed && h_total[1])   // a bucket too large for the per-lane sort (very coarse grid): redo with the full sort
-        return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, true, both);
+        return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, true, both, nrm);
     const int v = *h_total;
     *n_out = v;
     if (v > capacity) return TDV_ERR_BAD_ARG;
+    // the voxels' means in first-occurrence order into o_*: moved from where the bucket kernel parked them, or summed over the sorted runs
+    const auto means = [&](int cap, float* o_xyz, float* o_rgb, float* o_nrm) {
+        if (hashed) k_voxel_compact<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, n, mean_xyz, mean_rgb, cap, o_xyz, o_rgb, VoxelNormals{mean_nrm, o_nrm});
+        else if (nrm.in) k_voxel_means<true><<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, cap, o_xyz, o_rgb, VoxelNormals{nrm.in, o_nrm});
+        else k_voxel_means<false><<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, cap, o_xyz, o_rgb, VoxelNormals{nullptr, nullptr});
+    };
     if (order == TDV_VOXEL_ORDER_FIRST) {
-        if (hashed) k_voxel_compact<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, n, mean_xyz, mean_rgb, capacity, d_out_xyz, d_out_rgb);
-        else k_voxel_means<<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, capacity, d_out_xyz, d_out_rgb);
+        means(capacity, d_out_xyz, d_out_rgb, nrm.out);
         TDV_CHECK_LAUNCH(ctx);
         TDV_HIP(ctx, hipStreamSynchronize(s));      // the device entry points return with their results in place (include/tdv_hip.h)
         return TDV_OK;
@@ -1111,22 +1174,23 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
     if (both) tmp_xyz = both->first_xyz;
     else TDV_TRY(ws_alloc(ctx, (size_t)v * 3, &tmp_xyz));
     if (d_rgb && d_out_rgb) TDV_TRY(ws_alloc(ctx, (size_t)v * 3, &tmp_rgb));
-    if (hashed) k_voxel_compact<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, n, mean_xyz, mean_rgb, v, tmp_xyz, tmp_rgb);
-    else k_voxel_means<<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, v, tmp_xyz, tmp_rgb);
+    float* tmp_nrm = nullptr;
+    if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)v * 3, &tmp_nrm));
+    means(v, tmp_xyz, tmp_rgb, tmp_nrm);
     TDV_CHECK_LAUNCH(ctx);
     // leaders (first point of every voxel: cell + input index) in input order, from the device; the host only replays those
     int4* d_leaders;
     TDV_TRY(ws_alloc(ctx, (size_t)v, &d_leaders));
     k_voxel_leader_list<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, d_xyz, inv, n, d_leaders);
     TDV_CHECK_LAUNCH(ctx);
-    return voxel_reference_order(ctx, v, n, d_leaders, tmp_xyz, tmp_rgb, rank, 0, d_out_xyz, d_out_rgb, both);
+    return voxel_reference_order(ctx, v, n, d_leaders, tmp_xyz, tmp_rgb, rank, 0, d_out_xyz, d_out_rgb, both, VoxelNormals{tmp_nrm, nrm.out});
 }
 
 // The reference's container order for v voxels held in first-occurrence order (tmp_*): leaders (cell + input index of the first
 // point of every voxel, at its first-occurrence rank) go to the host, which replays the container; d_rank[input index] =
 // first-occurrence rank.  out[p] = tmp[rank[leader index of the p-th voxel of the container]].
 int voxel_reference_order(tdv_ctx* ctx, int v, int n, const int4* d_leaders, const float* tmp_xyz, const float* tmp_rgb, const int* d_rank, int rank_base,
-                          float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both) {
+                          float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both, VoxelNormals nrm /* in: the voxels' normals in first-occurrence order */) {
     hipStream_t s = ctx->stream;
     int* d_order;
     TDV_TRY(ws_alloc(ctx, (size_t)v, &d_order));
@@ -1166,7 +1230,7 @@ int voxel_reference_order(tdv_ctx* ctx, int v, int n, const int4* d_leaders, con
     if (n_first != v) { snprintf(ctx->err, sizeof(ctx->err), "voxel: host replay listed %d voxels, device %d", n_first, v); return TDV_ERR_INTERNAL; }
     TDV_HIP(ctx, hipMemcpyAsync(d_order, order_pinned, (size_t)v * 4, hipMemcpyHostToDevice, s));
     k_voxel_permute<<<(v + 255) / 256, 256, 0, s>>>(tmp_xyz, tmp_rgb, d_rank, rank_base, d_order, v, d_out_xyz, d_out_rgb,
-                                                    both ? both->ref2first : nullptr, both ? both->first2ref : nullptr);
+                                                    both ? both->ref2first : nullptr, both ? both->first2ref : nullptr, nrm);
     TDV_CHECK_LAUNCH(ctx);
     TDV_HIP(ctx, hipStreamSynchronize(s));  // the pinned staging is reused by the next call
     return TDV_OK;

@@ -276,6 +276,17 @@ int tdv_depth_to_cloud_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint
 #define TDV_VOXEL_ORDER_REFERENCE 1
 int tdv_voxel_downsample(tdv_ctx* ctx, const float* xyz, const float* rgb, int n, float voxel_size, int order,
                          float* out_xyz, float* out_rgb, int capacity, int* n_out);
+/* The same grid with the normals kept (the reference drops them): what a coarse point-to-plane or GICP level needs (tdv_icp_multiscale).
+ * Points, colours, the voxel set and both orders are tdv_voxel_downsample's, bit for bit; the normals ride the same grouping pass as a
+ * second 3-wide companion.  A voxel's normal is the colours' expression applied to the normals - f32 sums in ascending input index, each
+ * divided by (float)count - and the mean m is then brought to unit length in f32 without contraction:
+ *   l2 = m_x * m_x + (m_y * m_y + m_z * m_z)      (the reference's three-term order),      l = sqrtf(l2)
+ *   l2 > 0 and l finite: m_x / l, m_y / l, m_z / l;  otherwise m as it is - zero where the members' normals cancel, NaN or infinite
+ *   where a member is (or where a square overflows).
+ * Input normals are taken as given (unit length is not checked).  normals == NULL or out_normals == NULL: no normals, the call is
+ * tdv_voxel_downsample.  rgb / out_rgb are optional as there. */
+int tdv_voxel_downsample_normals(tdv_ctx* ctx, const float* xyz, const float* normals, const float* rgb /* optional */, int n, float voxel_size,
+                                 int order, float* out_xyz, float* out_normals, float* out_rgb, int capacity, int* n_out);
 
 /* ---- R4a: normals ------------------------------------------------------------------------- */
 /* Replaces Registration::estimateNormals (src/registration.cpp:105-130): exact brute-force kNN
@@ -462,6 +473,61 @@ int tdv_colored_icp_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_s
                               const float* d_tgt, const float* d_tgt_normals, const float* d_tgt_color, int nt, const float* h_T0,
                               float distance_threshold, int max_iterations, float lambda_geometric, int fixed_iterations,
                               tdv_icp_result* out);
+/* Multi-scale ICP: coarse-to-fine refinement over a voxel pyramid (Open3D's t.pipelines.registration.multi_scale_icp).  A single-scale
+ * call accepts correspondences within one threshold, so its basin of convergence is a fraction of that threshold; a schedule starts with
+ * coarse clouds and a wide threshold and hands each level's pose to the next, finer one.
+ * A level: voxel_size > 0 - source and target are voxel-downsampled at that size in TDV_VOXEL_ORDER_FIRST with their normals kept
+ * (tdv_voxel_downsample_normals: the target's where it has any, the source's for GICP); voxel_size <= 0, the last level only - the
+ * clouds as given.  Then the ICP loop of the estimation from the pose the level before left (level 0: T0), with the level's
+ * max_correspondence_distance as distance_threshold, at most max_iterations iterations and the level's convergence criteria, which are
+ * Open3D's ICPConvergenceCriteria: the loop is done after an applied iteration iff it is not the first and
+ *   fabsf(prev_fitness - fitness) < relative_fitness  &&  fabsf(prev_rmse - rmse) < relative_rmse,
+ * prev_* being what the previous applied iteration of the same level left.  relative_fitness = +INFINITY with relative_rmse = 1e-6f is
+ * the rule of every other ICP entry point (registration.cpp:406); relative_rmse = 0 never fires.  A level that breaks on n_corr < 3, or
+ * that has 0 iterations or no points on either side, passes its pose on unchanged and reports fitness, rmse, iterations and n_corr 0, as
+ * tdv_icp_dev does.
+ * estimation: TDV_ICP_POINT_TO_PLANE (without target normals: point-to-point, as tdv_icp), TDV_ICP_POINT_TO_POINT, TDV_ICP_GICP (both
+ * normal arrays and epsilon as tdv_gicp; epsilon is ignored otherwise).  The ctx's search mode, accumulation mode, launch form, probe
+ * cache and robust loss apply at every level as they do to tdv_icp_dev; tdv_ctx_last_icp_* report the last level.
+ * THE CONTRACT: out[l] (the batch: out[b * n_levels + l]) is, bit for bit, what the stagewise public calls return on the same ctx -
+ * tdv_voxel_downsample_normals_dev(TDV_VOXEL_ORDER_FIRST) of the source and of the target, then tdv_icp_dev / tdv_gicp_dev from the
+ * level before's pose (with default criteria; other criteria have no stagewise entry point) - in T, fitness, rmse, iterations, n_corr and
+ * the level's point counts ns, nt.  The batch is per instance what the single call returns.
+ * What the one call saves: the batch builds the target's level once per level, takes all sources' levels from the batched voxel path
+ * (one set of launches per level; a level so coarse that a voxel holds more than 16 points is redone cloud by cloud on the path
+ * without that limit, as tdv_voxel_downsample_batch_dev does), iterates all instances together where tdv_icp_batch_dev would, and keeps the
+ * level clouds in the ctx's workspace (each level rewinds it: a call needs the room of its largest level; no allocation in steady state).
+ * Levels: 1 .. TDV_ICP_MAX_LEVELS; voxel sizes strictly decreasing, only the last may be <= 0; max_correspondence_distance > 0 and
+ * finite; max_iterations >= 0; relative_fitness > 0 or +INFINITY; relative_rmse >= 0.  Everything is checked before anything is
+ * enqueued: TDV_ERR_BAD_ARG (NaN anywhere, an unknown estimation, GICP without both normal arrays or under reference-order sums, a
+ * robust loss under reference-order sums, what tdv_icp_batch_dev checks) writes nothing to out.  ns == 0, nt == 0 and n_instances == 0
+ * behave as in tdv_icp_batch_dev. */
+typedef struct tdv_icp_level {
+    float voxel_size;                   /* > 0: the level's voxel grid; <= 0, last level only: the clouds as given            */
+    float max_correspondence_distance;  /* the level's distance_threshold: > 0, finite                                        */
+    int   max_iterations;               /* >= 0                                                                               */
+    float relative_fitness, relative_rmse;
+} tdv_icp_level;
+/* voxel_size -1, max_correspondence_distance 0 (the caller must set it), 30 iterations, relative_fitness +INFINITY, relative_rmse 1e-6f */
+void tdv_icp_level_default(tdv_icp_level* level);
+typedef struct tdv_icp_level_result {
+    tdv_icp_result icp;
+    int ns, nt;                         /* points of the level's source and target clouds                                     */
+} tdv_icp_level_result;
+#define TDV_ICP_MAX_LEVELS 8
+#define TDV_ICP_POINT_TO_PLANE 0
+#define TDV_ICP_POINT_TO_POINT 1
+#define TDV_ICP_GICP 3
+int tdv_icp_multiscale(tdv_ctx* ctx, const float* src, const float* src_normals /* GICP only */, int ns, const float* tgt,
+                       const float* tgt_normals /* may be NULL */, int nt, const float* T0, const tdv_icp_level* levels, int n_levels,
+                       int estimation, float epsilon, tdv_icp_level_result* out /* [n_levels] */);
+int tdv_icp_multiscale_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, int ns, const float* d_tgt,
+                           const float* d_tgt_normals, int nt, const float* T0, const tdv_icp_level* levels, int n_levels,
+                           int estimation, float epsilon, tdv_icp_level_result* out);
+/* clouds, offsets and start poses laid out as tdv_icp_batch_dev's (d_src_normals like d_src); out: n_instances * n_levels, instance-major */
+int tdv_icp_multiscale_batch_dev(tdv_ctx* ctx, const float* d_src, const float* d_src_normals, const int* h_src_offsets, int n_instances,
+                                 const float* d_tgt, const float* d_tgt_normals, int nt, const float* h_T0, const tdv_icp_level* levels,
+                                 int n_levels, int estimation, float epsilon, tdv_icp_level_result* out);
 /* Fast Global Registration (Zhou, Park, Koltun, ECCV 2016; Open3D's registration_fgr_based_on_feature_matching): a global pose from the
  * FPFH matches without hypotheses - mutual nearest descriptors, a tuple test, then iteration_number Geman-McClure weighted Gauss-Newton
  * steps under a graduated non-convexity schedule.  Open3D's options and defaults; its rand() and its pair order are replaced by the
@@ -1268,6 +1334,11 @@ int tdv_depth_to_cloud_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d
  * input index of its first point) to replay the reference's container — the cloud itself stays on the device. */
 int tdv_voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel_size, int order,
                              float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out /* host */);
+/* tdv_voxel_downsample_normals on device arrays: xyz, rgb and the voxel set as tdv_voxel_downsample_dev's, the voxels' unit mean normals
+ * beside them (d_normals == NULL or d_out_normals == NULL: no normals). */
+int tdv_voxel_downsample_normals_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_normals, const float* d_rgb /* optional */, int n,
+                                     float voxel_size, int order, float* d_out_xyz, float* d_out_normals, float* d_out_rgb, int capacity,
+                                     int* n_out /* host */);
 
 /* Registration::voxelDownsample (src/registration.cpp:29-60) for n_clouds clouds stored back to back at d_xyz (cloud b =
  * points [h_cloud_offsets[b], h_cloud_offsets[b+1]); host array of n_clouds + 1 entries starting at 0), in ONE set of launches:

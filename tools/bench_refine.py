@@ -16,8 +16,19 @@ ground truth.
 either way, and the default l2 measures what it always did.  --clutter-px N lets every mask bleed N pixels onto a bin floor: the
 background pixels of that ring get a flat depth --clutter-gap-mm behind the instance's farthest pixel (mask bleed at C4 size).
 
+--levels "v:d:it,..." adds a multi-scale schedule (tdv_icp_multiscale_batch_dev) on the same voxel clouds, coarse to fine: voxel size and
+correspondence distance of each level in multiples of the workload's voxel (v = 0: the clouds as given, last level only), and its
+iteration cap.  Two more rows alternate with the others:
+  multiscale        tdv_icp_multiscale_batch_dev, one call;
+  multiscale_chain  the same schedule composed by hand from public calls: per level tdv_voxel_downsample_normals_dev per cloud (every
+                    instance and the model), then tdv_icp_batch_dev from the level before's poses.
+Each reports instances/s, the iterations of every level and the same ground-truth check, and the call must equal the chain in bits.  The
+line then also carries the error of the unperturbed registration poses: the floor a refinement can reach.  Without --levels the tool
+prints exactly what it printed.
+
     python tools/bench_refine.py [--instances 256] [--repeats 5] [--icp-iters 50] [--order first|reference]
                                  [--loss l2|huber|tukey|cauchy --loss-scale K] [--clutter-px N --clutter-gap-mm G]
+                                 [--levels 4:8:20,2:3:20,0:0.4:50]
 """
 import argparse
 import importlib
@@ -74,6 +85,7 @@ def main():
     ap.add_argument("--loss-scale", type=float, default=None, help="its scale in metres (default: the acceptance threshold)")
     ap.add_argument("--clutter-px", type=int, default=0, help="mask bleed onto a bin floor, in pixels (0: none)")
     ap.add_argument("--clutter-gap-mm", type=float, default=2.0, help="the floor's distance behind each instance's farthest pixel")
+    ap.add_argument("--levels", default=None, help='multi-scale schedule "v:d:it,...": voxel and distance in multiples of the voxel (v = 0: as given), iterations')
     args = ap.parse_args()
     import torch
     bb = _bench_batch()
@@ -126,6 +138,44 @@ def main():
         return [x.transformation for x in r], [x.iterations for x in r], r
 
     runs = dict(refine=run_refine, icp_batch=run_batch, icp_loop=run_loop)
+    if args.levels:
+        sched = [tuple(float(x) for x in lv.split(":")) for lv in args.levels.split(",")]
+        ms_levels = tdv.icp_levels([v * voxel if v > 0 else None for v, _, _ in sched], [d * voxel for _, d, _ in sched], [int(it) for _, _, it in sched])
+        d_lsrc = torch.empty_like(d_xyz)                      # the chain's level clouds: instances back to back, and the model with its normals
+        d_lmx, d_lmn = torch.empty_like(d_mx), torch.empty_like(d_mn)
+        nv = np.diff(voff)
+
+        def run_multiscale():
+            r = ctx.multi_scale_icp_batch_dev(d_vx, voff, d_mx.data_ptr(), d_mn.data_ptr(), nm, T0s, levels=ms_levels)
+            return [x.transformation for x in r], [x.iterations for x in r], r
+
+        chain_phase = dict(pyramid=[], icp=[])                # seconds per call of the chain: its voxel calls, its ICP calls (all return synchronised)
+
+        def run_chain():
+            T = T0s
+            per_level = []
+            t_vox = t_icp = 0.0
+            for v, d, it in sched:
+                t0 = time.perf_counter()
+                if v > 0:
+                    loff = np.zeros(B + 1, np.int32)
+                    for b in range(B):
+                        m = ctx.voxel_downsample_normals_dev(d_vx + 12 * int(voff[b]), None, int(nv[b]), v * voxel, d_lsrc.data_ptr() + 12 * int(loff[b]), None,
+                                                             int(nv[b])) if nv[b] else 0
+                        loff[b + 1] = loff[b] + m
+                    lm = ctx.voxel_downsample_normals_dev(d_mx.data_ptr(), d_mn.data_ptr(), nm, v * voxel, d_lmx.data_ptr(), d_lmn.data_ptr(), nm)
+                    t1 = time.perf_counter()
+                    r = ctx.icp_batch_dev(d_lsrc.data_ptr(), loff, d_lmx.data_ptr(), d_lmn.data_ptr(), lm, T, d * voxel, int(it))
+                else:
+                    t1 = time.perf_counter()
+                    r = ctx.icp_batch_dev(d_vx, voff, d_mx.data_ptr(), d_mn.data_ptr(), nm, T, d * voxel, int(it))
+                t_vox += t1 - t0; t_icp += time.perf_counter() - t1
+                per_level.append(r)
+                T = np.stack([x.transformation for x in r])
+            chain_phase["pyramid"].append(t_vox); chain_phase["icp"].append(t_icp)
+            return [x.transformation for x in per_level[-1]], [x.iterations for x in per_level[-1]], per_level
+
+        runs.update(multiscale=run_multiscale, multiscale_chain=run_chain)
     for f in runs.values():           # warm-up: arena growth, code load
         f()
     torch.cuda.synchronize()
@@ -166,9 +216,41 @@ def main():
                batch_differs_from_single=differ[:16], refine_differs_from_batch=refine_differ[:16], off_ground_truth=far[:16])
     if args.loss != "l2" or args.clutter_px > 0:       # (the default run prints what it always printed)
         out.update(icp_loss=list(ctx.icp_loss()), clutter_px=args.clutter_px, clutter_gap_mm=args.clutter_gap_mm)
+    ms_fail = []
+    if args.levels:
+        def key(x):
+            return (x.transformation.tobytes(), np.float32(x.fitness).tobytes(), np.float32(x.rmse).tobytes(), x.iterations, x.n_corr)
+        _, _, rm = last["multiscale"]
+        _, _, rc = last["multiscale_chain"]
+        ms_differ = [b for b in range(B) if any(key(rm[b].levels[l]) != key(rc[l][b]) for l in range(len(sched)))]
+
+        def row(k, level_iters, Ts):
+            e = [synth.pose_error(T, Tg) for T, Tg in zip(Ts, wl["T_gt"])]
+            a = np.array([x[0] for x in e]); t_ = np.array([x[1] for x in e])
+            off_gt = [int(b) for b in np.nonzero(~((a <= args.max_angle) & (t_ <= args.max_trans)))[0]]
+            tt = np.array(times[k])
+            return dict(instances_per_s=dict(median=float(B / np.median(tt)), min=float(B / tt.max()), max=float(B / tt.min())),
+                        ms_per_call=dict(median=float(np.median(tt) * 1e3), min=float(tt.min() * 1e3), max=float(tt.max() * 1e3)),
+                        icp_iterations_per_level=[int(sum(x)) for x in level_iters],
+                        angle_to_gt_rad=dict(max=float(a.max()), mean=float(a.mean())), translation_to_gt_m=dict(max=float(t_.max()), mean=float(t_.mean())),
+                        off_ground_truth_count=len(off_gt), off_ground_truth=off_gt[:16])
+        e0 = [synth.pose_error(r["T"], Tg) for r, Tg in zip(reg, wl["T_gt"])]
+        out.update(levels=args.levels,
+                   level_points=[dict(source_mean=float(np.mean([rm[b].levels[l].ns for b in range(B)])), target=int(rm[0].levels[l].nt)) for l in range(len(sched))],
+                   multiscale=row("multiscale", [[rm[b].levels[l].iterations for b in range(B)] for l in range(len(sched))], last["multiscale"][0]),
+                   multiscale_chain=row("multiscale_chain", [[x.iterations for x in rc[l]] for l in range(len(sched))], last["multiscale_chain"][0]),
+                   multiscale_differs_from_chain=ms_differ[:16], off_ground_truth_count=len(far),
+                   chain_phase_ms={k: dict(median=float(np.median(v[1:]) * 1e3), min=float(min(v[1:]) * 1e3), max=float(max(v[1:]) * 1e3))
+                                   for k, v in chain_phase.items()},       # (without the warm-up call)
+                   registration_to_gt=dict(angle_rad=dict(max=float(max(x[0] for x in e0)), mean=float(np.mean([x[0] for x in e0]))),
+                                           translation_m=dict(max=float(max(x[1] for x in e0)), mean=float(np.mean([x[1] for x in e0])))))
+        if ms_differ:
+            ms_fail.append("%d instances of tdv_icp_multiscale_batch_dev differ from the chain of public calls" % len(ms_differ))
+        if out["multiscale"]["off_ground_truth_count"]:
+            ms_fail.append("%d multi-scale instances further than %.1e rad / %.1e m from ground truth" % (out["multiscale"]["off_ground_truth_count"], args.max_angle, args.max_trans))
     print(json.dumps(out))
     ctx.close()
-    fail = []
+    fail = ms_fail
     if differ:
         fail.append("%d instances of tdv_icp_batch_dev differ from tdv_icp_dev" % len(differ))
     if refine_differ:
