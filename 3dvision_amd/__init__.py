@@ -46,7 +46,7 @@ DEPTH_BATCH_MASK_PASSES = 1   # the B masks cross HBM once in tdv_depth_to_cloud
 
 # every symbol include/tdv_hip.h declares (checked by the CPU test-suite against the built library)
 ABI_SYMBOLS = [
-    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_last_ransac_bound", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
+    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_voxel_batch_redone", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_last_ransac_bound", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
     "tdv_ctx_destroy", "tdv_status_string", "tdv_last_error", "tdv_version", "tdv_timing_enable", "tdv_timing_read",
     "tdv_depth_preprocess", "tdv_deproject", "tdv_depth_to_cloud", "tdv_voxel_downsample", "tdv_estimate_normals",
     "tdv_compute_fpfh", "tdv_feature_match", "tdv_ransac", "tdv_icp", "tdv_icp_correspondences",
@@ -637,6 +637,11 @@ class Context:
     def last_voxel_grouping(self):
         """'table' or 'pixels': how the last batched voxel stage on this context grouped its points."""
         return {0: "none", 1: "table", 2: "pixels"}[int(lib().tdv_ctx_last_voxel_grouping(self._h))]
+
+    def last_voxel_batch_redone(self):
+        """Whether the last batched voxel pass on this context (voxel_downsample_batch_dev, a voxelised level of multi_scale_icp_batch_dev)
+        was redone cloud by cloud because a voxel held more points than the table's rows: 0 kept, 1 redone, -1 before any."""
+        return int(lib().tdv_ctx_last_voxel_batch_redone(self._h))
 
     def last_batch_lanes(self):
         """Host lanes the last register_batch_dev call on this context used."""

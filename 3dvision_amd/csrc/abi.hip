@@ -71,6 +71,7 @@ static int voxel_batch_impl(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud
     int overflowed = 0;
     TDV_TRY(voxel_downsample_batch_dev(ctx, d_xyz, total, d_off, n_clouds, voxel_size, d_out_xyz, nullptr, nullptr, h_voxel_offsets, &overflowed, nullptr,
                                        pinhole4, pinhole4 ? h_cloud_offsets : nullptr));
+    ctx->last_voxel_batch_redone = overflowed;
     if (!overflowed) return TDV_OK;
     // a voxel with more points than the table's member rows hold (a coarse grid): cloud by cloud on the path without that limit
     int at = 0;

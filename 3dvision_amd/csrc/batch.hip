@@ -144,6 +144,7 @@ int batch_voxels(tdv_ctx* ctx, int n_instances, const tdv_batch_params* prm, con
                                            vx.voff.data(), &overflowed, vx.d_voff, pinhole, off.data()));
         ws_rewind(ctx, vmark);
         vx.batched = !overflowed;
+        ctx->last_voxel_batch_redone = overflowed;
         // ... and their reference order, on the device too (the host replay stays as the fall-back of a cloud whose hash degenerates)
         const bool device_order_env = !(getenv("TDV_VOXEL_DEVICE_ORDER") && atoi(getenv("TDV_VOXEL_DEVICE_ORDER")) == 0);   // A/B knob (read per call: the tests switch it)
         if (vx.batched && want_ref && device_order_env && vx.voff[n_instances] > 0) {

@@ -362,6 +362,7 @@ void tdv_ctx_last_ransac_bound(tdv_ctx* ctx, long long out[4]) { if (out) for (i
 int tdv_ctx_last_icp_search(tdv_ctx* ctx) { return ctx ? ctx->last_icp_search : 0; }
 int tdv_ctx_last_feature_match_path(tdv_ctx* ctx) { return ctx ? ctx->last_fm_path : 0; }
 int tdv_ctx_last_voxel_grouping(tdv_ctx* ctx) { return ctx ? ctx->last_voxel_grouping : 0; }
+int tdv_ctx_last_voxel_batch_redone(tdv_ctx* ctx) { return ctx ? ctx->last_voxel_batch_redone : TDV_ERR_BAD_ARG; }
 int tdv_ctx_last_batch_lanes(tdv_ctx* ctx) { return ctx ? ctx->last_batch_lanes : 0; }
 unsigned long long tdv_ctx_workspace_bytes(tdv_ctx* ctx) {
     unsigned long long total = 0;

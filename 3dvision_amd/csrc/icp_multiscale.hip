@@ -78,6 +78,7 @@ int multiscale_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals,
                 if (!single)
                     TDV_TRY(voxel_downsample_batch_dev(ctx, d_src, total, d_off, n, lv.voxel_size, o_xyz, nullptr, nullptr, start.data(), &overflowed, nullptr,
                                                        nullptr, nullptr, VoxelNormals{gicp ? d_src_normals : nullptr, o_nrm}));
+                if (!single) ctx->last_voxel_batch_redone = overflowed;
                 if (overflowed) {
                     // one instance, or a voxel with more points than the table's member rows hold (a coarse level): cloud by cloud on the
                     // path without that limit, packed back to back as the batched path leaves them

@@ -44,6 +44,7 @@ struct tdv_ctx {
     long long last_ransac_bound[4] = {0, 0, 0, 0};   // the leaf-box bound's lists in the last RANSAC call: hypotheses bounded, close, on the fine list, live
     double last_ransac_scored = 1.0;     // share of the (hypothesis, point) tests the last RANSAC call evaluated (< 1: the exact bail-out left the rest out)
     int last_voxel_grouping = 0;   // 1: the table (k_vh_insert), 2: pixel windows (k_vs_group) - the last batched voxel call (tdv_ctx_last_voxel_grouping)
+    int last_voxel_batch_redone = -1;   // whether the caller of the last batched voxel pass (voxel_downsample_batch_dev) redid it cloud by cloud: 0 kept, 1 redone (tdv_ctx_last_voxel_batch_redone)
     int last_fm_path = 0;      // TDV_FM_PATH_* of the last descriptor match on this ctx (tdv_ctx_last_feature_match_path)
     int last_batch_lanes = 0;  // host lanes the last tdv_register_batch_dev call on this ctx spread its instances over (tdv_ctx_last_batch_lanes)
     int fps_path = 0;          // TDV_FPS_AUTO / _WORKGROUP / _GRID (tdv_ctx_set_fps_path)

@@ -171,6 +171,10 @@ int tdv_ctx_last_feature_match_path(tdv_ctx* ctx);
 #define TDV_VOXEL_GROUPING_TABLE 1
 #define TDV_VOXEL_GROUPING_PIXELS 2
 int tdv_ctx_last_voxel_grouping(tdv_ctx* ctx);
+/* Whether the last batched voxel pass on this ctx (tdv_voxel_downsample_batch*_dev, tdv_register_batch_dev, a voxelised level of
+ * tdv_icp_multiscale_batch_dev - there the last such level) kept its result (0) or found a voxel of more points than the table's member
+ * rows hold (16) and was redone cloud by cloud (1); -1 before any.  Same voxels either way.  TDV_ERR_BAD_ARG for a NULL ctx. */
+int tdv_ctx_last_voxel_batch_redone(tdv_ctx* ctx);
 /* Host lanes (the caller's thread + helper threads) the last tdv_register_batch_dev call on this ctx used (0 before any). */
 int tdv_ctx_last_batch_lanes(tdv_ctx* ctx);
 /* Device memory this ctx holds in its grow-only workspace arenas, its batch lanes' included: the high-water mark of every

@@ -15,6 +15,7 @@ void orc_compute_fpfh(const float*, const float*, int, float, float*, int*, int*
 void orc_feature_match(const float*, int, const float*, int, int*);
 void orc_ransac(const float*, int, const float*, int, const float*, const float*, const int*, float, int, float, float*, float*, float*, int*, int*, int*, int*);
 int orc_icp(const float*, int, const float*, const float*, int, const float*, float, int, int, float*, float*, float*, float*);
+int orc_icp_criteria(const float*, int, const float*, const float*, int, const float*, float, int, int, float*, float*, float*, float*, int, int*, float, float);
 void orc_bilateral_filter(const float*, float*, int, int, float, float);
 int orc_filter_duplicates(const float*, int, float, float*);
 void orc_demo_scene(int, int, float, uint16_t*, uint8_t*);
@@ -69,6 +70,8 @@ int main() {
     std::vector<float> tr(20 * 20);
     int it = orc_icp(src.data(), ns, tgt.data(), nrm.data(), nt, I, 0.2f, 20, 1, To, &fit, &rmse, tr.data());
     it += orc_icp(src.data(), ns, tgt.data(), nullptr, nt, I, 0.2f, 20, 1, To, &fit, &rmse, tr.data());
+    int amb = 0;
+    it += orc_icp_criteria(src.data(), ns, tgt.data(), nrm.data(), nt, I, 0.2f, 20, 1, To, &fit, &rmse, tr.data(), 1, &amb, 1e-2f, 1e-4f);
     std::vector<float> poses(16 * 10), kept(16 * 10);
     for (int p = 0; p < 10; ++p) { for (int i = 0; i < 16; ++i) poses[16 * p + i] = I[i]; poses[16 * p + 12] = 0.05f * (p % 4); }
     int k = orc_filter_duplicates(poses.data(), 10, 0.1f, kept.data());

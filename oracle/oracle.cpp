@@ -700,7 +700,8 @@ void orc_icp_correspondences(const float* src, int ns, const float* tgt, const f
 // midpoint (the device may then round the other way), else 0; *ambiguous_out (optional) ORs them over the run.
 static int icp_impl(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
                     const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
-                    float* T_out, float* fitness_out, float* rmse_out, float* trace, int exact, int* ambiguous_out) {
+                    float* T_out, float* fitness_out, float* rmse_out, float* trace, int exact, int* ambiguous_out,
+                    float rel_fitness, float rel_rmse) {
     if (ambiguous_out) *ambiguous_out = 0;
     const int depth = icp_tree_depth(ns);
     float T[16]; std::memcpy(T, T0, 64);
@@ -811,7 +812,7 @@ static int icp_impl(const float* src, int ns, const float* tgt, const float* tgt
             for (int r = 0; r < 3; ++r) delta[12 + r] = tm[r] - Rs[r];
         }
         mul44(delta, T, T);
-        float prev_rmse = res_rmse;
+        float prev_rmse = res_rmse, prev_fitness = res_fitness;
         res_rmse = std::sqrt(total_error / n_corr);
         res_fitness = static_cast<float>(n_corr) / ns;
         std::memcpy(res_T, T, 64);
@@ -821,7 +822,7 @@ static int icp_impl(const float* src, int ns, const float* tgt, const float* tgt
             std::memcpy(tr, T, 64); tr[16] = res_rmse; tr[17] = res_fitness; tr[18] = (float)n_corr; tr[19] = amb ? 1.f : 0.f;
         }
         if (amb && ambiguous_out) *ambiguous_out = 1;
-        if (iter > 0 && std::abs(prev_rmse - res_rmse) < 1e-6f) break;
+        if (iter > 0 && fabsf(prev_fitness - res_fitness) < rel_fitness && fabsf(prev_rmse - res_rmse) < rel_rmse) break;
     }
     std::memcpy(T_out, res_T, 64);
     *fitness_out = res_fitness; *rmse_out = res_rmse;
@@ -831,13 +832,23 @@ int orc_icp(const float* src, int ns, const float* tgt, const float* tgt_normals
             const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
             float* T_out, float* fitness_out, float* rmse_out, float* trace) {
     return icp_impl(src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, T_out, fitness_out, rmse_out,
-                    trace, 0, nullptr);
+                    trace, 0, nullptr, INFINITY, 1e-6f);
 }
 int orc_icp_ex(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
                const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
                float* T_out, float* fitness_out, float* rmse_out, float* trace, int exact, int* ambiguous_out) {
     return icp_impl(src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, T_out, fitness_out, rmse_out,
-                    trace, exact, ambiguous_out);
+                    trace, exact, ambiguous_out, INFINITY, 1e-6f);
+}
+// orc_icp_ex with the call's convergence criteria (csrc/icp.hip: icp_update): the loop ends after an applied iteration iter > 0 whose
+// fitness moved by less than rel_fitness and whose rmse moved by less than rel_rmse, both against what the previous applied
+// iteration left.  (+inf, 1e-6f) is the reference's rule, registration.cpp:406.
+int orc_icp_criteria(const float* src, int ns, const float* tgt, const float* tgt_normals, int nt,
+                     const float* T0, float distance_threshold, int max_iterations, int point_to_plane,
+                     float* T_out, float* fitness_out, float* rmse_out, float* trace, int exact, int* ambiguous_out,
+                     float rel_fitness, float rel_rmse) {
+    return icp_impl(src, ns, tgt, tgt_normals, nt, T0, distance_threshold, max_iterations, point_to_plane, T_out, fitness_out, rmse_out,
+                    trace, exact, ambiguous_out, rel_fitness, rel_rmse);
 }
 
 // exact sum of x[0..n) (math.fsum's value) -> *f64; rounded to f32 once -> *f32; *ambiguous: whether the sum lies within

@@ -39,6 +39,7 @@ def lib():
         _LIB.orc_self_adjoint_eig3.restype = C.c_int
         _LIB.orc_icp.restype = C.c_int
         _LIB.orc_icp_ex.restype = C.c_int
+        _LIB.orc_icp_criteria.restype = C.c_int
         _LIB.orc_filter_duplicates.restype = C.c_int
         _LIB.orc_load_ply.restype = C.c_int
         _LIB.orc_libm_f32_batch.restype = C.c_int
@@ -322,16 +323,19 @@ def icp_correspondences(src, tgt, tgt_normals, T, thr, point_to_plane=True):
                 ATA=ATA.reshape(6, 6), ATb=ATb)
 
 
-def icp(src, tgt, tgt_normals, T0, thr, max_iterations=200, point_to_plane=True, trace=False, exact=False):
+def icp(src, tgt, tgt_normals, T0, thr, max_iterations=200, point_to_plane=True, trace=False, exact=False,
+        relative_fitness=np.inf, relative_rmse=1e-6):
     """exact=True: the exact-sum mode (oracle.cpp: icp_impl), what the device's f64 tree sums give bit for bit unless the
     result's `ambiguous` is True (some sum within the tree's error bound of an f32 rounding midpoint; per iteration in
-    trace[:, 19])."""
+    trace[:, 19]).  relative_fitness, relative_rmse: the convergence criteria (both as f32): the loop ends after an applied
+    iteration > 0 that moved the fitness by less than the one and the rmse by less than the other."""
     src = _f32(src); tgt = _f32(tgt); tn = _f32(tgt_normals)
     T = np.zeros(16, np.float32); fit = C.c_float(); rmse = C.c_float(); amb = C.c_int()
     tr = np.zeros((max_iterations, 20), np.float32) if trace else None
     t0 = to_colmajor16(T0)
-    it = lib().orc_icp_ex(_p(src), len(src), _p(tgt), _p(tn), len(tgt), _p(t0), C.c_float(thr), max_iterations,
-                          int(point_to_plane), _p(T), C.byref(fit), C.byref(rmse), _p(tr), int(exact), C.byref(amb))
+    it = lib().orc_icp_criteria(_p(src), len(src), _p(tgt), _p(tn), len(tgt), _p(t0), C.c_float(thr), max_iterations,
+                                int(point_to_plane), _p(T), C.byref(fit), C.byref(rmse), _p(tr), int(exact), C.byref(amb),
+                                C.c_float(relative_fitness), C.c_float(relative_rmse))
     res = dict(T=from_colmajor16(T), fitness=np.float32(fit.value), rmse=np.float32(rmse.value), iterations=it)
     if exact:
         res["ambiguous"] = bool(amb.value)

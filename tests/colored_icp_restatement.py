@@ -158,12 +158,15 @@ def iteration_sums(orc, src, src_rgb, tgt, tgt_normals, tgt_color, T, thr, lam=L
     return out
 
 
-def colored_icp(orc, src, src_rgb, tgt, tgt_normals, tgt_color, T0, thr, max_iterations, lam=LAMBDA, kind="l2", scale=0.0, fixed=False):
+def colored_icp(orc, src, src_rgb, tgt, tgt_normals, tgt_color, T0, thr, max_iterations, lam=LAMBDA, kind="l2", scale=0.0, fixed=False,
+                relative_fitness=np.inf, relative_rmse=1e-6):
     """The device loop: a dict T, rmse, fitness, iterations, n_corr as a tdv_icp_result reads, ambiguous (some sum of an applied
-    iteration could round the other way on the device) and per-iteration (n_corr, n_eff) in counts."""
+    iteration could round the other way on the device) and per-iteration (n_corr, n_eff) in counts.
+    relative_fitness, relative_rmse (as f32): the convergence criteria of icp_update, the defaults being the reference's rule;
+    history: (rmse, fitness) after every applied iteration."""
     T = np.asarray(T0, F).copy()
     ns = len(src)
-    res = dict(T=T.copy(), rmse=F(0), fitness=F(0), iterations=0, n_corr=0, ambiguous=False, counts=[])
+    res = dict(T=T.copy(), rmse=F(0), fitness=F(0), iterations=0, n_corr=0, ambiguous=False, counts=[], history=[])
     for it in range(max_iterations):
         s = iteration_sums(orc, src, src_rgb, tgt, tgt_normals, tgt_color, T, thr, lam, kind, scale)
         res["counts"].append((s["n_corr"], s["n_eff"]))
@@ -173,10 +176,12 @@ def colored_icp(orc, src, src_rgb, tgt, tgt_normals, tgt_color, T0, thr, max_ite
             break
         res["ambiguous"] |= s["ambiguous"]
         T = L.mul44(L.delta_transform(orc, s, True, True), T)
-        prev = res["rmse"]
+        prev, prev_fit = res["rmse"], res["fitness"]
         rmse = F(np.sqrt(F(s["te"] / F(s["n_corr"]))))
-        res.update(T=T.copy(), rmse=rmse, fitness=F(F(s["n_corr"]) / F(ns)), iterations=it + 1, n_corr=s["n_corr"])
-        if not fixed and it > 0 and abs(F(prev - rmse)) < F(1e-6):
+        fit = F(F(s["n_corr"]) / F(ns))
+        res.update(T=T.copy(), rmse=rmse, fitness=fit, iterations=it + 1, n_corr=s["n_corr"])
+        res["history"].append((rmse, fit))
+        if not fixed and it > 0 and abs(F(prev_fit - fit)) < F(relative_fitness) and abs(F(prev - rmse)) < F(relative_rmse):
             break
     return res
 

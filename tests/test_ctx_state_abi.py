@@ -22,3 +22,9 @@ def test_null_ctx_is_refused_for_every_byte(tdv):
 
 def test_python_wrappers_exist(tdv):
     assert callable(tdv.Context.workspace_fill) and callable(tdv.Context.set_stream)
+
+
+def test_last_voxel_batch_redone_is_exported_listed_and_refuses_a_null_ctx(tdv):
+    assert hasattr(tdv.lib(), "tdv_ctx_last_voxel_batch_redone") and "tdv_ctx_last_voxel_batch_redone" in tdv.ABI_SYMBOLS
+    assert "int tdv_ctx_last_voxel_batch_redone(tdv_ctx* ctx);" in open(os.path.join(ROOT, "include", "tdv_hip.h")).read()
+    assert tdv.lib().tdv_ctx_last_voxel_batch_redone(None) == TDV_ERR_BAD_ARG and callable(tdv.Context.last_voxel_batch_redone)

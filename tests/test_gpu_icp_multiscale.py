@@ -13,8 +13,16 @@ not: one call crosses both kernel families.
   orc.icp(exact=True) wherever that is not flagged ambiguous;
 * what the schedule buys is a property of the fixture, asserted on the oracle alone (so that it cannot hide a device failure): from the
   6 deg / 10 mm start the oracle's single-scale error is at least 10x its three-level error on seeds 1 and 3 (measured: 16-17x);
-* the convergence criteria stop where the recorded per-iteration (fitness, rmse) say they must;
-* every refused call writes nothing."""
+* the convergence criteria stop where the recorded per-iteration (fitness, rmse) say they must (test_gpu_icp_criteria.py holds them to the
+  references on every ICP path);
+* every refused call writes nothing;
+* a batched voxel level says which way it went (tdv_ctx_last_voxel_batch_redone): clouds planted with at most 16 points in every voxel keep
+  the batched table - the NRM kernels under GICP - and one voxel of 17 points in one instance has the level redone cloud by cloud; either
+  way every instance is the single call, and one flipped source normal changes the GICP level's bytes;
+* robust loss, launch form and probe cache apply at every level as they do to the stagewise calls, and last_icp_launches /
+  last_icp_probe_misses report the last level;
+* NaN, +-inf and far-out rows of the source and of its normals go through the schedule as through the stagewise chain, and under
+  reference-order sums as through the oracle's own voxel grid and ICP."""
 import ctypes as C
 
 import numpy as np
@@ -311,3 +319,180 @@ def test_bad_arguments_write_nothing(tdv, ctx, scene, synth):
     r = ctx.multi_scale_icp_dev(ps, N, None, None, 0, p["T0"], levels=lv)
     assert all(l.iterations == 0 and l.nt == 0 and l.transformation.tobytes() == p["T0"].astype(F).tobytes() for l in r.levels)
     assert [l.ns for l in r.levels][2] == N
+
+
+# ---------------------------------------------------------------- which way the batched voxel level went
+PLANT_SIZES = (0, 1, 1025, 1300)          # back to back the third crosses point 1,024 and the fourth point 2,048 (the voxel kernels' tiles)
+ROW = 16                                  # member slots of a voxel in the batched table (csrc/voxel.hip: VH_K)
+
+
+def _f32_keys(pts, voxel):
+    return np.floor(pts * F(F(1.0) / F(voxel))).astype(np.int64)
+
+
+def _voxel_counts(pts, voxel):
+    return np.unique(_f32_keys(pts, voxel), axis=0, return_counts=True)[1] if len(pts) else np.zeros(0, np.int64)
+
+
+def _planted(pool, voxel, n, fullest, rng):
+    """n points of the pool with 1 .. ROW points in every voxel but the first, which gets `fullest`: shuffled."""
+    keys = _f32_keys(pool, voxel)
+    _, inv, cnt = np.unique(keys, axis=0, return_inverse=True, return_counts=True)
+    inv = inv.reshape(-1)
+    rich = [v for v in np.argsort(-cnt, kind="stable") if cnt[v] >= fullest]
+    assert rich, "no voxel of the pool holds %d points" % fullest
+    take, left = [], n
+    for j, v in enumerate([rich[0]] + [v for v in rng.permutation(len(cnt)) if v != rich[0]]):
+        k = fullest if j == 0 else int(min(cnt[v], 1 + (j % ROW), left))
+        k = min(k, left)
+        take.append(np.flatnonzero(inv == v)[:k]); left -= k
+        if left == 0:
+            break
+    assert left == 0, "the pool is too small for %d points" % n
+    idx = np.concatenate(take)
+    return pool[idx[rng.permutation(len(idx))]].copy()
+
+
+@pytest.fixture(scope="module")
+def planted(orc, synth, scene):
+    """Schedules A and B of one voxelised level plus the final one over clouds planted from a 20,000-point scan: in A every voxel of every
+    instance holds at most 16 points (one holds exactly 16), in B exactly one voxel of the 1,025-point instance holds 17.  Asserted on the
+    f32 keys; the source normals (GICP) are the oracle's estimates."""
+    sp = synth.mean_spacing(N)
+    voxel = F(4 * sp)
+    pool, T_gt = synth.make_scene(20000, 77)
+    T0 = synth.perturb(T_gt, seed=78, angle_deg=3.0, trans=0.005).astype(F)
+    out = dict(sched=[(voxel, F(8 * sp), 12), (None, F(1.5 * sp), 12)], T0=T0, voxel=voxel)
+    for name, fullest in (("A", ROW), ("B", ROW + 1)):
+        rng = np.random.default_rng(5)
+        clouds = [pool[:0], pool[7:8].copy(), _planted(pool, voxel, 1025, fullest, rng), _planted(pool[10000:], voxel, 1300, ROW, rng)]
+        counts = [_voxel_counts(c, voxel) for c in clouds]
+        over = [int((c > ROW).sum()) for c in counts]
+        assert [len(c) for c in clouds] == list(PLANT_SIZES)
+        assert over == ([0, 0, 0, 0] if name == "A" else [0, 0, 1, 0]) and max(int(c.max()) for c in counts[1:]) == fullest, (name, over)
+        normals = [np.zeros((0, 3), F), F([[0, 0, 1]])] + [np.asarray(orc.estimate_normals(c), F) for c in clouds[2:]]
+        out[name] = dict(clouds=clouds, normals=normals, off=np.concatenate([[0], np.cumsum(PLANT_SIZES)]).astype(np.int32))
+    return out
+
+
+@pytest.mark.parametrize("estimation", ["gicp", "point_to_plane"])
+def test_batched_voxel_level_reports_which_way_it_went(tdv, orc, scene, planted, estimation):
+    gicp = estimation == "gicp"
+    ctx = tdv.Context(0)
+    try:
+        assert ctx.last_voxel_batch_redone() == -1          # before any call
+        env = Env(ctx)
+        pt, ptn = env.up(scene["tgt"]), env.up(scene["nrm"])
+        lv = levels_of(tdv, planted["sched"])
+        T0s = np.stack([planted["T0"]] * len(PLANT_SIZES))
+        for name, redone in (("A", 0), ("B", 1), ("A", 0)):
+            p = planted[name]
+            src, sn = np.concatenate(p["clouds"]), np.concatenate(p["normals"])
+            got = ctx.multi_scale_icp_batch_dev(env.up(src), p["off"], pt, ptn, N, T0s, estimation=estimation, d_src_normals=env.up(sn) if gicp else None, levels=lv)
+            assert ctx.last_voxel_batch_redone() == redone, (name, ctx.last_voxel_batch_redone())
+            for b, (c, n) in enumerate(zip(p["clouds"], p["normals"])):
+                one = ctx.multi_scale_icp_dev(env.up(c), len(c), pt, ptn, N, planted["T0"], estimation=estimation, d_src_normals=env.up(n) if gicp else None, levels=lv)
+                assert ctx.last_voxel_batch_redone() == redone          # the single call has no batched voxel pass: the query keeps the batch's answer
+                assert [bits(l) for l in got[b].levels] == [bits(l) for l in one.levels], (estimation, name, "instance", b)
+                assert got[b].levels[0].ns == len(_voxel_counts(c, planted["voxel"])) and got[b].levels[1].ns == len(c), (name, b)
+            assert all(lv_.iterations >= 2 for b in (2, 3) for lv_ in got[b].levels), name
+            # the voxel stage alone, on the same clouds, goes the same way
+            o = env.out(3 * len(src), F)
+            voff = ctx.voxel_downsample_batch_dev(env.up(src), p["off"], float(planted["voxel"]), o.data_ptr())
+            assert ctx.last_voxel_batch_redone() == redone, (name, "voxel_downsample_batch_dev")
+            assert list(np.diff(voff)) == [lv_.ns for lv_ in (got[b].levels[0] for b in range(len(PLANT_SIZES)))]
+    finally:
+        ctx.close()
+
+
+def test_a_flipped_source_normal_changes_the_gicp_level(tdv, ctx, scene, planted):
+    """The GICP fixture does read the source normals of its voxelised level: one flipped normal changes that level's bytes."""
+    p = planted["A"]
+    env = Env(ctx)
+    pt, ptn = env.up(scene["tgt"]), env.up(scene["nrm"])
+    lv = levels_of(tdv, planted["sched"])
+    c, n = p["clouds"][2], p["normals"][2]
+    keys = _f32_keys(c, planted["voxel"])
+    i = next(i for i in range(len(c)) if 2 <= (keys == keys[i]).all(1).sum() <= 4 and np.abs(n[i]).max() > 0)      # a voxel of a few points: its mean normal turns
+    flipped = n.copy(); flipped[i] = -n[i]
+    runs = [ctx.multi_scale_icp_dev(env.up(c), len(c), pt, ptn, N, planted["T0"], estimation="gicp", d_src_normals=env.up(m), levels=lv) for m in (n, n, flipped)]
+    assert bits(runs[0].levels[0]) == bits(runs[1].levels[0])
+    assert bits(runs[0].levels[0]) != bits(runs[2].levels[0])
+    assert runs[0].levels[0].ns == runs[2].levels[0].ns
+
+
+# ---------------------------------------------------------------- the ctx's settings apply at every level
+LEVEL_SETTINGS = {          # what is set on the ctx, and what the queries report after the call (its last level, 3,000 x 3,000 through the grid)
+    "huber": dict(loss=("huber", 0.002), launches="two", misses=False),
+    "tukey": dict(loss=("tukey", 0.004), launches="two", misses=False),
+    "launches one": dict(set_launches="one", launches="one", misses=True),          # (AUTO takes the cache with the one-launch iteration)
+    "launches two": dict(set_launches="two", launches="two", misses=False),
+    "probe cache on": dict(cache="on", launches="two", misses=True),
+    "probe cache off": dict(set_launches="one", cache="off", launches="one", misses=False),
+}
+
+
+@pytest.mark.parametrize("setting", list(LEVEL_SETTINGS))
+def test_levels_run_under_the_ctx_settings(tdv, scene, setting):
+    """Robust loss, launch form and probe cache through the three-level schedule with the grid search: every level is the stagewise chain
+    on the same ctx, and last_icp_launches / last_icp_probe_misses report the last level."""
+    p, cfg = scene[1], LEVEL_SETTINGS[setting]
+    ctx = tdv.Context(0)
+    try:
+        ctx.set_icp_search("grid")
+        if "loss" in cfg:
+            ctx.set_icp_loss(*cfg["loss"])
+        ctx.set_icp_launches(cfg.get("set_launches", "auto")); ctx.set_icp_probe_cache(cfg.get("cache", "auto"))
+        env = Env(ctx)
+        chain = stagewise(ctx, env, p["src"], p["sn"], scene["tgt"], scene["nrm"], p["T0"], scene["sched"], "point_to_plane")
+        got = ctx.multi_scale_icp_dev(env.up(p["src"]), N, env.up(scene["tgt"]), env.up(scene["nrm"]), N, p["T0"], levels=levels_of(tdv, scene["sched"]))
+        assert (ctx.last_icp_search(), ctx.last_icp_launches()) == ("grid", cfg["launches"]), (setting, ctx.last_icp_search(), ctx.last_icp_launches())
+        misses = ctx.last_icp_probe_misses()
+        assert (misses >= got.levels[-1].ns) if cfg["misses"] else (misses == -1), (setting, misses)
+        for l, (lv, (ref, _, _)) in enumerate(zip(got.levels, chain)):
+            assert bits(lv) == ref, (setting, "level", l, lv, ref[1:])
+        assert all(lv.iterations >= 2 for lv in got.levels), [lv.iterations for lv in got.levels]
+        if "loss" in cfg:          # the loss does weigh: the same schedule without it ends elsewhere
+            ctx.set_icp_loss("l2")
+            plain = ctx.multi_scale_icp_dev(env.up(p["src"]), N, env.up(scene["tgt"]), env.up(scene["nrm"]), N, p["T0"], levels=levels_of(tdv, scene["sched"]))
+            assert bits(plain.levels[0]) != bits(got.levels[0])
+    finally:
+        ctx.close()
+
+
+POISON_ROWS = [0, 5, 17, 62, 63, 64, 100, 640, 1023, 1024]          # test_gpu_icp_probe_cache.py: test_non_finite_and_far_out_sources_in_a_wave
+POISON_VALS = [np.nan, np.inf, -np.inf, 3e7, -3e7, 1e19, -1e19, np.nan, np.inf, 2e3]
+
+
+def _poisoned(a):
+    a = a.copy()
+    for k, (r, v) in enumerate(zip(POISON_ROWS, POISON_VALS)):
+        a[r, k % 3] = F(v)
+    return a
+
+
+@pytest.mark.parametrize("estimation,accumulate", [("point_to_plane", "reference"), ("point_to_plane", "tree"), ("gicp", "tree")])
+def test_non_finite_rows_through_the_schedule(tdv, ctx, orc, scene, estimation, accumulate):
+    """NaN, +-inf and far-out coordinates in rows of the source (and, GICP, of its normals) through the three levels: each level is the
+    stagewise chain, and under reference-order sums it is orc.icp on the oracle's own voxel clouds, whose sizes are the level's ns, nt."""
+    p = scene[1]
+    gicp = estimation == "gicp"
+    src, sn = _poisoned(p["src"]), (_poisoned(p["sn"]) if gicp else p["sn"])
+    env = Env(ctx)
+    with Settings(ctx, "auto", accumulate):
+        chain = stagewise(ctx, env, src, sn, scene["tgt"], scene["nrm"], p["T0"], scene["sched"], estimation)
+        got = ctx.multi_scale_icp_dev(env.up(src), N, env.up(scene["tgt"]), env.up(scene["nrm"]), N, p["T0"], estimation=estimation,
+                                      d_src_normals=env.up(sn) if gicp else None, levels=levels_of(tdv, scene["sched"]))
+    for l, (lv, (ref, _, _)) in enumerate(zip(got.levels, chain)):
+        assert bits(lv) == ref, (estimation, accumulate, "level", l, lv, ref[1:])
+    assert all(lv.iterations >= 2 and lv.n_corr > 100 for lv in got.levels), [(lv.iterations, lv.n_corr) for lv in got.levels]      # the finite rest did register
+    T = p["T0"]
+    for l, (lv, (voxel, dist, iters)) in enumerate(zip(got.levels, scene["sched"])):
+        s_l, t_l, n_l = (src, scene["tgt"], scene["nrm"]) if voxel is None else \
+            (_oracle_first_order(orc, src, None, voxel)[0],) + _oracle_first_order(orc, scene["tgt"], scene["nrm"], voxel)
+        assert (lv.ns, lv.nt) == (len(s_l), len(t_l)), (estimation, "level", l, lv.ns, len(s_l), lv.nt, len(t_l))
+        if accumulate == "reference":
+            r = orc.icp(s_l, t_l, n_l, T, dist, iters, True)
+            assert (lv.transformation.tobytes(), F(lv.fitness).tobytes(), F(lv.rmse).tobytes(), lv.iterations) == \
+                   (r["T"].tobytes(), F(r["fitness"]).tobytes(), F(r["rmse"]).tobytes(), r["iterations"]), (estimation, "level", l)
+            T = r["T"] if r["iterations"] > 0 else T
