@@ -70,6 +70,7 @@ ABI_SYMBOLS = [
     "tdv_verify_default_params", "tdv_verify_poses", "tdv_verify_poses_dev", "tdv_render_depth", "tdv_render_depth_dev",
     "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
     "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
+    "tdv_tsdf_default_params", "tdv_tsdf_volume_bytes", "tdv_tsdf_reset_dev", "tdv_tsdf_integrate_dev", "tdv_tsdf_extract_dev", "tdv_tsdf_fuse",
     "tdv_voxel_downsample_normals", "tdv_voxel_downsample_normals_dev",
     "tdv_icp_level_default", "tdv_icp_multiscale", "tdv_icp_multiscale_dev", "tdv_icp_multiscale_batch_dev",
 ]
@@ -343,6 +344,33 @@ def _mesh_sample_result(r):
                 surface_area=math.ldexp(float(int(r.total_weight)), r.weight_exponent - 31))
 
 
+TDV_TSDF_MAX_SIDE = 1024
+TDV_TSDF_MAX_VOXELS = 1 << 27
+TDV_TSDF_HOST_MAX_VOXELS = 1 << 25
+TDV_TSDF_MAX_FRAMES = 64
+TDV_TSDF_TILE_X, TDV_TSDF_TILE_Y, TDV_TSDF_TILE_Z = 64, 8, 8
+
+
+class TsdfVolumeC(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("voxel_length", C.c_float), ("nx", C.c_int), ("ny", C.c_int), ("nz", C.c_int)]
+
+
+class TsdfParamsC(C.Structure):
+    _fields_ = [("trunc", C.c_float), ("max_weight", C.c_float), ("zmax", C.c_float), ("min_weight", C.c_float), ("pose_direction", C.c_int)]
+
+
+def tsdf_params(**kw):
+    """tdv_tsdf_default_params (trunc 0: four voxel lengths, max_weight 255, zmax 10 m, min_weight 1, poses take the volume's frame to the
+    camera's) with the given fields replaced; pose_direction also by name ('model_to_camera', 'source_onto_target')."""
+    return _params("tsdf", kw)
+
+
+def tsdf_volume_struct(origin, voxel_length, dims):
+    """The tdv_tsdf_volume of a grid of dims = (nx, ny, nz) voxels of voxel_length metres whose corner (not first centre) is origin."""
+    o = np.asarray(origin, np.float32).reshape(3)
+    return TsdfVolumeC((C.c_float * 3)(*[float(x) for x in o]), float(np.float32(voxel_length)), int(dims[0]), int(dims[1]), int(dims[2]))
+
+
 def _poses16(poses):
     """[n, 4, 4] row-major poses as the ABI's n x 16 column-major floats."""
     poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
@@ -399,6 +427,7 @@ _PARAMS = {
                     dict(pose_direction=POSE_DIRECTION, cull=MESH_CULL)),
     "mesh_sample": (MeshSampleParamsC, "tdv_mesh_sample_default_params", "mesh sampling", None),
     "ppf": (PpfParamsC, "tdv_ppf_default_params", "PPF", None),
+    "tsdf": (TsdfParamsC, "tdv_tsdf_default_params", "TSDF", dict(pose_direction=POSE_DIRECTION)),
 }
 
 _lib = None
@@ -436,6 +465,7 @@ def lib():
             l.tdv_version.restype = C.c_char_p
             l.tdv_ctx_get_stream.restype = C.c_void_p
             l.tdv_ctx_workspace_bytes.restype = C.c_ulonglong
+            l.tdv_tsdf_volume_bytes.restype = C.c_ulonglong
             l.tdv_ctx_last_ransac_rescore.restype = C.c_double
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
             l.tdv_ctx_last_ransac_bound.restype = None
@@ -1486,6 +1516,98 @@ class Context:
         h = out.cpu().numpy()
         m = r["n_selected"]
         return h[0, :m].copy(), h[1, :m].copy(), r
+
+    # ---------------------------------------------------------------- TSDF fusion (include/tdv_hip.h: tdv_tsdf_integrate_dev)
+    tsdf_params = staticmethod(tsdf_params)
+
+    def tsdf_volume(self, origin, voxel_length, dims):
+        """A fresh volume: (the tdv_tsdf_volume struct, its device buffer - a torch float32 tensor [nx*ny*nz, 2] of (tsdf, weight) pairs, voxel
+        (i, j, k) at row (k*ny + j)*nx + i, every pair (1, 0)).  The caller owns the tensor, as it owns tdv_ppf_model_dev's table."""
+        import torch
+        vol = tsdf_volume_struct(origin, voxel_length, dims)
+        nbytes = int(lib().tdv_tsdf_volume_bytes(C.byref(vol)))
+        if nbytes == 0:
+            raise ValueError("tsdf_volume: sides in [1, TDV_TSDF_MAX_SIDE], at most TDV_TSDF_MAX_VOXELS voxels, voxel_length > 0")
+        buf = torch.empty((nbytes // 8, 2), dtype=torch.float32, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(buf.device).synchronize()
+        self.tsdf_reset_dev(vol, buf.data_ptr())
+        self.synchronize()
+        return vol, buf
+
+    def tsdf_reset_dev(self, vol, d_volume):
+        """tdv_tsdf_reset_dev: every pair of the volume becomes (1, 0)."""
+        _check(self._h, lib().tdv_tsdf_reset_dev(self._h, C.byref(vol), _ptr(d_volume)), "tdv_tsdf_reset_dev")
+
+    def tsdf_integrate_dev(self, vol, d_volume, d_raw, poses, w, h, scale, fx, fy, cx, cy, want_counts=True, **params):
+        """tdv_tsdf_integrate_dev: the frames d_raw (uint16[n, h, w] on the device) taken at poses ([n, 4, 4], row-major) into the volume, in
+        one pass.  Returns int64[n], the voxels each frame updated, or None with want_counts=False (no read-back)."""
+        t, n = _poses16(poses)
+        counts = np.zeros(n, np.int64) if want_counts else None
+        _check(self._h, lib().tdv_tsdf_integrate_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_raw), n, int(w), int(h), C.c_float(scale),
+                                                     C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy), _ptr(t),
+                                                     C.byref(tsdf_params(**params)), _ptr(counts)), "tdv_tsdf_integrate_dev")
+        return counts
+
+    def tsdf_extract_dev(self, vol, d_volume, d_out_xyz, d_out_normals, capacity, **params):
+        """tdv_tsdf_extract_dev: the crossings of the volume into d_out_xyz and d_out_normals (optional), capacity rows each; returns
+        (n, fits): n rows were written, or, fits False, n rows are needed and none was written."""
+        n = C.c_int(-1)
+        st = lib().tdv_tsdf_extract_dev(self._h, C.byref(vol), _ptr(d_volume), C.byref(tsdf_params(**params)), _ptr(d_out_xyz),
+                                        _ptr(d_out_normals), int(capacity), C.byref(n))
+        if st == -2 and n.value > int(capacity) >= 0:
+            return n.value, False
+        _check(self._h, st, "tdv_tsdf_extract_dev")
+        return n.value, True
+
+    def tsdf_integrate(self, volume, frames, poses, intrinsics, **params):
+        """tsdf_integrate_dev on host frames (uint16[n, h, w]) into volume = tsdf_volume()'s pair; intrinsics = (scale, fx, fy, cx, cy)."""
+        import torch
+        frames = np.array(frames, np.uint16)                     # (a copy: torch wants a writable array)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        d_raw = torch.from_numpy(frames.view(np.int16) if frames.size else np.zeros((1, 1, 1), np.int16)).to(volume[1].device)
+        torch.cuda.synchronize()
+        counts = self.tsdf_integrate_dev(volume[0], volume[1].data_ptr(), d_raw.data_ptr(), poses, frames.shape[2], frames.shape[1], *intrinsics,
+                                         **params)
+        return counts
+
+    def tsdf_extract(self, volume, normals=True, **params):
+        """The crossings of volume = tsdf_volume()'s pair: (xyz float32[n, 3], normals float32[n, 3] or None)."""
+        import torch
+        n, _ = self.tsdf_extract_dev(volume[0], volume[1].data_ptr(), None, None, 0, **params)
+        out = torch.zeros((2 if normals else 1, max(n, 1), 3), dtype=torch.float32, device=volume[1].device)
+        torch.cuda.synchronize()
+        self.tsdf_extract_dev(volume[0], volume[1].data_ptr(), out[0].data_ptr(), out[1].data_ptr() if normals else None, n, **params)
+        self.synchronize()
+        h = out.cpu().numpy()
+        return h[0, :n].copy(), (h[1, :n].copy() if normals else None)
+
+    def tsdf_fuse(self, frames, poses, intrinsics, volume, normals=True, **params):
+        """tdv_tsdf_fuse on host arrays: frames uint16[n, h, w] taken at poses [n, 4, 4] with intrinsics = (scale, fx, fy, cx, cy), fused in
+        volume = (origin, voxel_length, dims) or a TsdfVolumeC: (xyz float32[m, 3], normals float32[m, 3] or None).  The first call asks for the
+        count, the second brings the rows."""
+        vol = volume if isinstance(volume, TsdfVolumeC) else tsdf_volume_struct(*volume)
+        frames = np.ascontiguousarray(frames, np.uint16)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        t, n = _poses16(poses)
+        if n != len(frames):
+            raise ValueError("tdv_tsdf_fuse: one pose per frame")
+        scale, fx, fy, cx, cy = intrinsics
+        p = tsdf_params(**params)
+
+        def call(xyz, nrm, capacity):
+            m = C.c_int(-1)
+            st = lib().tdv_tsdf_fuse(self._h, C.byref(vol), _ptr(frames), n, frames.shape[2], frames.shape[1], C.c_float(scale), C.c_float(fx),
+                                     C.c_float(fy), C.c_float(cx), C.c_float(cy), _ptr(t), C.byref(p), _ptr(xyz), _ptr(nrm), capacity, C.byref(m))
+            if not (st == -2 and m.value > capacity):
+                _check(self._h, st, "tdv_tsdf_fuse")
+            return m.value
+
+        m = call(None, None, 0)
+        xyz = np.zeros((m, 3), np.float32)
+        nrm = np.zeros((m, 3), np.float32) if normals else None
+        if m:
+            call(xyz, nrm, m)
+        return xyz, nrm
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

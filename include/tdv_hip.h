@@ -1164,6 +1164,83 @@ int tdv_mesh_sample_points_dev(tdv_ctx* ctx, const float* d_vertices, int n_vert
                                const tdv_mesh_sample_params* params, tdv_mesh_sample_result* result /* host */, float* d_out_xyz /* optional */,
                                float* d_out_normals /* optional */, int* d_out_triangle /* optional */, float* d_out_bary /* optional */,
                                float* d_out_attr /* optional */);
+/* TSDF fusion (Open3D's UniformTSDFVolume::integrate and extract_point_cloud; Curless and Levoy 1996): several raw depth frames taken at
+ * known camera poses are fused into one truncated signed distance volume, and the volume's zero crossings come out as one cloud whose
+ * normals are the gradient of the fused field - measured, not fitted to a neighbourhood.  Noise is averaged over the frames that saw a
+ * voxel and a surface seen twice comes out once.  A voxel's update depends on that voxel and one pixel per frame, and the frames apply
+ * in ascending index, so with f32, one rounding per operation, no contraction and the order exactly as written every output is fixed bit
+ * for bit whatever order the device works in (sqrtf and / correctly rounded).
+ * The volume is a caller-owned device buffer of nx*ny*nz pairs (f32 tsdf, f32 weight), tdv_tsdf_volume_bytes(vol) bytes; voxel (i, j, k)
+ * sits at pair index (k*ny + j)*nx + i.  The layout is public.  tdv_tsdf_reset_dev makes every pair (1.0f, 0.0f).
+ *  T1. Voxel centre: xw = origin[0] + ((float)i + 0.5f) * voxel_length, and yw (j, origin[1]), zw (k, origin[2]) likewise.
+ *  T2. Camera coordinates of the centre under the frame's pose T: rule 1 of tdv_verify_poses for params->pose_direction, the voxel
+ *      centre standing in for m.  TDV_POSE_MODEL_TO_CAMERA (the default): T takes the volume's frame to the camera's, Open3D's extrinsic.
+ *      TDV_POSE_SOURCE_ONTO_TARGET: T is the camera's pose in the volume's frame.
+ *  T3. Usable: xc, yc, zc are finite and 0 < zc <= zmax; uf = (xc*fx)/zc + cx and vf = (yc*fy)/zc + cy are finite and below 2^20 in
+ *      magnitude; u = (int)floorf(uf + 0.5f), v likewise, and 0 <= u < width, 0 <= v < height.
+ *  T4. Observed depth of frame f at (u, v): rule 5 of tdv_verify_poses, zo = float(raw) * float(1.0 / scale), valid iff raw != 0 and
+ *      zo <= zmax.
+ *  T5. Update: sdf = zo - zc, projective along z.  A voxel with sdf < -trunc is not touched (sdf == -trunc is updated).  Otherwise
+ *      t = fminf(1.0f, sdf / trunc); tsdf' = (tsdf*w + t) / (w + 1.0f); w' = fminf(w + 1.0f, max_weight).  trunc is params->trunc, or
+ *      4.0f * voxel_length where that is 0.  The frames of a call apply to a voxel in ascending frame index, and a call with frames A, B
+ *      leaves what a call with A and then a call with B leave.  h_n_updated[f] = the number of voxels frame f updated.
+ *  T6. Observed voxel: w >= min_weight.
+ *  T7. Crossings.  For an observed voxel a and its +x, +y or +z neighbour b, inside the volume and observed: they bracket the surface
+ *      iff (f_a < 0) != (f_b < 0) - zero counts as non-negative.  With r_a = fabsf(f_a), r_b = fabsf(f_b) the point is a's centre with its
+ *      coordinate on that axis replaced by (c_a*r_b + c_b*r_a) / (r_a + r_b), c_a and c_b the two centres' coordinates on the axis (T1);
+ *      the denominator is positive by construction.  Output order: ascending 3*voxel_index + axis (x = 0, y = 1, z = 2).
+ *  T8. Normal.  Per axis the gradient at a voxel is f(fwd) - f(bwd), its two neighbours on the axis; a neighbour outside the volume or not
+ *      observed is replaced by the voxel itself; if exactly one of the two is replaced the difference is multiplied by 2.0f; if both are,
+ *      it is 0.  The crossing's normal is n = g_a*r_b + g_b*r_a per component, L = sqrtf((nx*nx + ny*ny) + nz*nz), and the row is n / L per
+ *      component, or (0, 0, 0) where L is zero or not finite.  A positive tsdf is in front of the surface, so the normal points out of the
+ *      object, towards where it was seen from.
+ * tdv_tsdf_integrate_dev: d_raw holds n_frames u16 images (width x height, row-major) back to back on the device, h_poses n_frames x 16
+ * floats (column-major each) on the host; h_n_updated (optional, host, [n_frames]) costs the call its one read-back.  All frames of a call
+ * are integrated in one pass over the volume.  n_frames == 0 is valid and leaves the volume as it is.  NaN or infinite pose entries fall
+ * out through T3: such a frame updates nothing.
+ * tdv_tsdf_extract_dev: d_out_xyz and d_out_normals (optional) receive *n_out rows of 3 floats; capacity = their room in rows, n_out on
+ * the host.  If capacity is too small (NULL d_out_xyz with capacity 0 is a query) the call returns TDV_ERR_BAD_ARG with *n_out set to the
+ * needed count and no row written, as tdv_deproject does.  One read-back, the count.
+ * tdv_tsdf_fuse: host arrays throughout - reset, integrate and extract with the volume in the ctx's workspace; volumes above
+ * TDV_TSDF_HOST_MAX_VOXELS are refused.
+ * Kernels (csrc/tsdf.hip): integrate is one launch per call, a lane per voxel, the pair loaded and stored once (and not at all where no
+ * frame updates it), the poses read through scalar loads.  Extract stages tiles of TDV_TSDF_TILE_X x _Y x _Z voxels with their halo in
+ * LDS, counts the crossings per run of TDV_TSDF_TILE_X voxels along x, scans the counts (no atomic decides an output position) and
+ * writes the rows.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, vol, params, volume buffer, frames or poses (n_frames > 0), n_out,
+ * or d_out_xyz with capacity > 0; a side < 1 or > TDV_TSDF_MAX_SIDE; nx*ny*nz above TDV_TSDF_MAX_VOXELS (tdv_tsdf_fuse:
+ * TDV_TSDF_HOST_MAX_VOXELS); voxel_length, scale, fx or fy <= 0 or non-finite; trunc < 0 or non-finite; max_weight < 1 or non-finite;
+ * min_weight <= 0 or non-finite; n_frames < 0 or > TDV_TSDF_MAX_FRAMES; width or height < 0 or > TDV_VERIFY_MAX_SIDE; an unknown
+ * pose_direction; capacity < 0.  The ctx's switches do not apply.
+ * Not provided: colour, per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, mesh extraction and
+ * ray casting, the C++ operator mirror. */
+typedef struct tdv_tsdf_volume { float origin[3]; float voxel_length; int nx, ny, nz; } tdv_tsdf_volume;   /* 28 bytes */
+typedef struct tdv_tsdf_params {   /* 20 bytes */
+    float trunc;           /* truncation distance in metres; default 0, which means 4.0f * voxel_length */
+    float max_weight;      /* default 255 */
+    float zmax;            /* as tdv_deproject; default 10 */
+    float min_weight;      /* T6; default 1 */
+    int   pose_direction;  /* TDV_POSE_MODEL_TO_CAMERA (default) or TDV_POSE_SOURCE_ONTO_TARGET */
+} tdv_tsdf_params;
+#define TDV_TSDF_MAX_SIDE 1024
+#define TDV_TSDF_MAX_VOXELS (1 << 27)      /* 1 GiB of volume */
+#define TDV_TSDF_HOST_MAX_VOXELS (1 << 25) /* the host form keeps its volume in the ctx's workspace */
+#define TDV_TSDF_MAX_FRAMES 64             /* per integrate call */
+#define TDV_TSDF_TILE_X 64   /* the tile k_tsdf_extract stages in LDS; a wave owns a run of TILE_X voxels along x */
+#define TDV_TSDF_TILE_Y 8
+#define TDV_TSDF_TILE_Z 8
+void tdv_tsdf_default_params(tdv_tsdf_params* params);
+unsigned long long tdv_tsdf_volume_bytes(const tdv_tsdf_volume* vol);
+int tdv_tsdf_reset_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_volume);
+int tdv_tsdf_integrate_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_volume, const uint16_t* d_raw /* n_frames images */, int n_frames,
+                           int width, int height, float scale, float fx, float fy, float cx, float cy,
+                           const float* h_poses /* host, n_frames x 16 */, const tdv_tsdf_params* params,
+                           long long* h_n_updated /* optional, host, [n_frames] */);
+int tdv_tsdf_extract_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const tdv_tsdf_params* params, float* d_out_xyz,
+                         float* d_out_normals /* optional */, int capacity, int* n_out /* host */);
+int tdv_tsdf_fuse(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t* raw, int n_frames, int width, int height, float scale, float fx,
+                  float fy, float cx, float cy, const float* poses, const tdv_tsdf_params* params, float* out_xyz,
+                  float* out_normals /* optional */, int capacity, int* n_out);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
