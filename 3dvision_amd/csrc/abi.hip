@@ -26,7 +26,7 @@ int tdv_depth_preprocess(tdv_ctx* ctx, const uint16_t* raw, const uint8_t* mask,
     TDV_TRY(upload(ctx, raw, n, &d_raw));
     TDV_TRY(upload(ctx, mask, n, &d_mask));
     TDV_TRY(ws_alloc(ctx, n, &d_out));
-    TDV_TRY(depth_preprocess_dev(ctx, d_raw, d_mask, width, height, scale, mask_mode, d_out));
+    TDV_TRY(depth_preprocess_dev(ctx, DepthFrames::one(d_raw, d_mask, width, height, scale, mask_mode, 0.f), d_out));
     TDV_TRY(download(ctx, out_depth, d_out, n));
     return finish(ctx);
 }
@@ -119,7 +119,7 @@ int tdv_deproject(tdv_ctx* ctx, const float* depth, const uint8_t* bgr, int widt
     const size_t cap = (size_t)std::min<size_t>((size_t)capacity, n);
     if (out_xyz && cap) TDV_TRY(ws_alloc(ctx, cap * 3, &d_xyz));
     if (out_rgb && bgr && cap) TDV_TRY(ws_alloc(ctx, cap * 3, &d_rgb));
-    int st = depth_to_cloud_dev(ctx, nullptr, d_depth, nullptr, d_bgr, width, height, 1.f, 0, fx, fy, cx, cy, zmax,
+    int st = depth_to_cloud_dev(ctx, DepthFrames::one(nullptr, nullptr, width, height, 1.f, 0, zmax), d_depth, d_bgr, Pinhole{fx, fy, cx, cy},
                                 d_xyz, d_rgb, (int)cap, n_out);
     if (st != TDV_OK) return st;
     TDV_TRY(download(ctx, out_xyz, d_xyz, (size_t)*n_out * 3));
@@ -143,7 +143,7 @@ int tdv_depth_to_cloud(tdv_ctx* ctx, const uint16_t* raw, const uint8_t* mask, c
     const size_t cap = (size_t)std::min<size_t>((size_t)capacity, n);
     if (out_xyz && cap) TDV_TRY(ws_alloc(ctx, cap * 3, &d_xyz));
     if (out_rgb && bgr && cap) TDV_TRY(ws_alloc(ctx, cap * 3, &d_rgb));
-    int st = depth_to_cloud_dev(ctx, d_raw, nullptr, d_mask, d_bgr, width, height, scale, mask_mode, fx, fy, cx, cy, zmax,
+    int st = depth_to_cloud_dev(ctx, DepthFrames::one(d_raw, d_mask, width, height, scale, mask_mode, zmax), nullptr, d_bgr, Pinhole{fx, fy, cx, cy},
                                 d_xyz, d_rgb, (int)cap, n_out);
     if (st != TDV_OK) return st;
     TDV_TRY(download(ctx, out_xyz, d_xyz, (size_t)*n_out * 3));
@@ -432,7 +432,7 @@ int tdv_depth_to_cloud_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d
                            float fx, float fy, float cx, float cy, float zmax,
                            float* d_xyz, float* d_rgb, int capacity, int* n_out) {
     TDV_TRY(call_begin(ctx));
-    return depth_to_cloud_dev(ctx, d_raw, nullptr, d_mask, d_bgr, width, height, scale, mask_mode, fx, fy, cx, cy, zmax,
+    return depth_to_cloud_dev(ctx, DepthFrames::one(d_raw, d_mask, width, height, scale, mask_mode, zmax), nullptr, d_bgr, Pinhole{fx, fy, cx, cy},
                               d_xyz, d_rgb, capacity, n_out);
 }
 int tdv_voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel_size, int order,

@@ -76,12 +76,11 @@ struct BatchClouds {
 
 int batch_clouds(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, int n_instances, const tdv_batch_params* prm, BatchClouds& cl) {
     // all clouds of the frame in two launches (count + emit), back to back in one buffer
-    const int layout = prm->mask_format == 0 ? 1 : (prm->mask_format == 1 ? 0 : 2);            // depth.hip's `stacked` argument
     // masks of another size than the frame: nearest-neighbour resize first (src/pipeline.cpp:38-41)
     const int mw = prm->mask_width > 0 ? prm->mask_width : prm->width, mh = prm->mask_height > 0 ? prm->mask_height : prm->height;
     if (mw != prm->width || mh != prm->height) {
         uint8_t* resized;
-        const int n_masks = prm->mask_format == 0 ? n_instances : 1;
+        const int n_masks = mask_layout_of(prm->mask_format) == MaskLayout::Stacked ? n_instances : 1;
         TDV_TRY(ws_alloc(ctx, (size_t)n_masks * prm->width * prm->height + 16, &resized));
         resized = reinterpret_cast<uint8_t*>(align_up(reinterpret_cast<uintptr_t>(resized), 16));
         TDV_TRY(mask_resize_nearest_dev(ctx, d_masks, n_masks, mw, mh, prm->width, prm->height, resized));
@@ -89,23 +88,22 @@ int batch_clouds(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks, in
     }
     std::vector<int>& off = cl.off;
     off.assign((size_t)n_instances + 1, 0);
-    int* d_off = nullptr;
     const int* d_frame_of = nullptr;
     TDV_TRY(frame_map_dev(ctx, n_instances, prm->n_frames, prm->frame_of_instance, &d_frame_of));
-    TDV_TRY(depth_to_cloud_batch_count(ctx, d_raw, d_frame_of, d_masks, n_instances, layout, prm->width, prm->height, prm->scale_to_meters, prm->mask_mode,
-                                       prm->zmax, &d_off, off.data()));
+    const DepthFrames frames(d_raw, d_frame_of, d_masks, mask_layout_of(prm->mask_format), n_instances, prm->width, prm->height, prm->scale_to_meters,
+                             prm->mask_mode, prm->zmax);
+    DepthBatchPlan plan;
+    TDV_TRY(depth_to_cloud_batch_count(ctx, frames, &plan, off.data()));
     if (off[n_instances] > 0) {
         TDV_TRY(ws_alloc(ctx, (size_t)off[n_instances] * 3, &cl.xyz));
-        TDV_TRY(depth_to_cloud_batch_emit(ctx, d_raw, d_frame_of, d_masks, nullptr, n_instances, layout, prm->width, prm->height, prm->scale_to_meters,
-                                          prm->mask_mode, prm->fx, prm->fy, prm->cx, prm->cy, prm->zmax, d_off, cl.xyz, nullptr));
+        TDV_TRY(depth_to_cloud_batch_emit(ctx, frames, nullptr, Pinhole{prm->fx, prm->fy, prm->cx, prm->cy}, plan, cl.xyz, nullptr));
     }
     // instances without a point: status 1 when the masked depth image holds no non-zero value at all (pipeline.cpp:57-60),
     // status 2 when it does but nothing survives the z clip (:86-89)
     std::vector<int> empty_inst, empty_nonzero;
     for (int b = 0; b < n_instances; ++b) if (off[b + 1] == off[b]) empty_inst.push_back(b);
     empty_nonzero.assign(empty_inst.size(), 0);
-    TDV_TRY(depth_batch_nonzero_any(ctx, d_raw, d_frame_of, d_masks, layout, prm->width, prm->height, prm->scale_to_meters, prm->mask_mode,
-                                    empty_inst.data(), (int)empty_inst.size(), empty_nonzero.data()));
+    TDV_TRY(depth_batch_nonzero_any(ctx, frames, empty_inst.data(), (int)empty_inst.size(), empty_nonzero.data()));
     cl.empty_status.assign((size_t)n_instances, 0);
     for (size_t e = 0; e < empty_inst.size(); ++e) cl.empty_status[empty_inst[e]] = empty_nonzero[e] ? 2 : 1;
     return TDV_OK;
@@ -575,18 +573,17 @@ int tdv_depth_to_cloud_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint
     if (mask_format < 0 || mask_format > 2) return TDV_ERR_BAD_ARG;
     if (mask_format != 0 && n_frames > 1) return TDV_ERR_BAD_ARG;   // a label image belongs to one frame
     if ((mask_format == 1 && n_instances > 255) || (mask_format == 2 && n_instances > 65535)) return TDV_ERR_BAD_ARG;   // instance b is label b + 1
-    const int layout = mask_format == 0 ? 1 : (mask_format == 1 ? 0 : 2);
     TDV_TRY(call_begin(ctx));
     h_offsets[0] = 0;
     if (n_instances == 0 || (size_t)width * height == 0) { for (int b = 0; b <= n_instances; ++b) h_offsets[b] = 0; return TDV_OK; }
-    int* d_off = nullptr;
     const int* d_frame_of = nullptr;
     TDV_TRY(frame_map_dev(ctx, n_instances, n_frames, h_frame_of_instance, &d_frame_of));
-    TDV_TRY(depth_to_cloud_batch_count(ctx, d_raw, d_frame_of, d_masks, n_instances, layout, width, height, scale, mask_mode, zmax, &d_off, h_offsets));
+    const DepthFrames frames(d_raw, d_frame_of, d_masks, mask_layout_of(mask_format), n_instances, width, height, scale, mask_mode, zmax);
+    DepthBatchPlan plan;
+    TDV_TRY(depth_to_cloud_batch_count(ctx, frames, &plan, h_offsets));
     if ((long long)h_offsets[n_instances] > capacity || (h_offsets[n_instances] > 0 && !d_xyz)) return TDV_ERR_BAD_ARG;
     if (h_offsets[n_instances] > 0)
-        TDV_TRY(depth_to_cloud_batch_emit(ctx, d_raw, d_frame_of, d_masks, d_bgr, n_instances, layout, width, height, scale, mask_mode,
-                                          fx, fy, cx, cy, zmax, d_off, d_xyz, d_rgb));
+        TDV_TRY(depth_to_cloud_batch_emit(ctx, frames, d_bgr, Pinhole{fx, fy, cx, cy}, plan, d_xyz, d_rgb));
     TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return TDV_OK;
 }

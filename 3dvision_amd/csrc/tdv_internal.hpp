@@ -11,6 +11,7 @@
 #include <cstring>
 #include <vector>
 #include "tdv_hip.h"
+#include "depth_frames.hpp"
 
 namespace tdv {
 
@@ -54,11 +55,10 @@ struct tdv_ctx {
     int icp_probe_cache = 0;   // TDV_ICP_PROBE_CACHE_AUTO / _OFF / _ON (tdv_ctx_set_icp_probe_cache)
     int last_icp_probe_misses = -1;   // lanes that probed the hash table in the last ICP call, -1 if it ran without the probe cache
     int last_icp_search = 0;// the search the last ICP / correspondence call on this ctx actually ran (tdv_ctx_last_icp_search)
-    unsigned* scan_ticket = nullptr;  // persistent device words: [0] exclusive_scan_dev's last-workgroup ticket, [1..] ICP's, [8] the tile ticket of depth.hip's chained scan
-    unsigned long long* chain_status = nullptr;   // depth.hip k_depth_cloud_chain: one status word per tile, persistent (told apart by chain_epoch)
+    unsigned* scan_ticket = nullptr;  // persistent device words: [0] exclusive_scan_dev's last-workgroup ticket, [1..] ICP's, [8] the tile ticket of depth_cloud.hip's chained scan
+    unsigned long long* chain_status = nullptr;   // depth_cloud.hip k_depth_cloud_chain: one status word per tile, persistent (told apart by chain_epoch)
     size_t chain_cap = 0;
     unsigned chain_epoch = 0, chain_ticket_base = 0;   // calls so far; tickets handed out so far (the kernel's tile = ticket - base)
-    uint16_t* depth_bits = nullptr;   // validity bitmap between the two passes of the batched depth -> cloud (workspace memory of the current call)
     tdv_ctx* helper = nullptr;   // second stream + workspace of the batched pipeline's other lane (owned; created on first use)
     tdv::TimerSlot timers[TDV_TIMER_COUNT];
     std::vector<hipEvent_t> event_pool;
@@ -258,23 +258,6 @@ struct FmIndex {
 };
 int fm_index_build(tdv_ctx* ctx, const float* d_ft, int nt, FmIndex* out);
 int feature_match_indexed_dev(tdv_ctx* ctx, const float* d_fs, int ns, const FmIndex& ix, int* d_corr);
-int depth_preprocess_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_mask, int w, int h, float scale,
-                         int mask_mode, float* d_out);
-int bilateral_filter_dev(tdv_ctx* ctx, const float* d_in, float* d_out, int w, int h, float sigma_spatial, float sigma_range);
-int depth_to_cloud_dev(tdv_ctx* ctx, const uint16_t* d_raw, const float* d_depth_f32, const uint8_t* d_mask,
-                       const uint8_t* d_bgr, int w, int h, float scale, int mask_mode,
-                       float fx, float fy, float cx, float cy, float zmax,
-                       float* d_xyz, float* d_rgb, int capacity, int* n_out);
-int frame_map_dev(tdv_ctx* ctx, int n_inst, int n_frames, const int* h_frame_of, const int** d_frame_of);
-int depth_to_cloud_batch_count(tdv_ctx* ctx, const uint16_t* d_raw, const int* d_frame_of, const uint8_t* d_masks, int n_inst, int stacked, int w, int h,
-                               float scale, int mask_mode, float zmax, int** d_offsets_out, int* h_offsets);
-int depth_to_cloud_batch_emit(tdv_ctx* ctx, const uint16_t* d_raw, const int* d_frame_of, const uint8_t* d_masks, const uint8_t* d_bgr, int n_inst, int stacked,
-                              int w, int h, float scale, int mask_mode, float fx, float fy, float cx, float cy, float zmax,
-                              const int* d_offsets, float* d_xyz, float* d_rgb);
-// `stacked` above: 1 = one u8 mask per instance, 0 = one u8 label image (label = instance + 1), 2 = one u16 label image
-int mask_resize_nearest_dev(tdv_ctx* ctx, const uint8_t* d_src, int n_masks, int sw, int sh, int dw, int dh, uint8_t* d_dst);
-int depth_batch_nonzero_any(tdv_ctx* ctx, const uint16_t* d_raw, const int* d_frame_of, const uint8_t* d_masks, int layout, int w, int h, float scale,
-                            int mask_mode, const int* h_inst, int n_list, int* h_flags);
 int estimate_normals_dev(tdv_ctx* ctx, const float* d_xyz, int n, int k, float* d_normals, int* d_knn);
 // colour gradients of a cloud (color.hip, include/tdv_hip.h: tdv_color_gradients): float4 (I, d) per point from the kNN lists d_knn
 // (int[n * k], tdv_estimate_normals' for the same k) or, d_knn == nullptr, from estimate_normals_dev's search

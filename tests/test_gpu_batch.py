@@ -105,13 +105,16 @@ def test_all_instance_clouds_in_one_pass(ctx, tdv, synth, orc):
         label[(masks[b] > 0) & (label == 0)] = b + 1
     # label image: instance b = pixels with value b + 1 (overlaps resolved towards the lower label above)
     d_label = torch.from_numpy(label).to(dev)
-    off2 = ctx.depth_to_cloud_batch_dev(d_depth.data_ptr(), d_label.data_ptr(), None, 3, w, h, 1000.0, intr["fx"], intr["fy"],
-                                        intr["cx"], intr["cy"], 1.5, d_xyz.data_ptr(), None, cap, mask_format=1)
-    xyz2 = d_xyz.cpu().numpy()
+    d_rgb.zero_()
+    off2 = ctx.depth_to_cloud_batch_dev(d_depth.data_ptr(), d_label.data_ptr(), d_bgr.data_ptr(), 3, w, h, 1000.0, intr["fx"], intr["fy"],
+                                        intr["cx"], intr["cy"], 1.5, d_xyz.data_ptr(), d_rgb.data_ptr(), cap, mask_format=1)
+    xyz2 = d_xyz.cpu().numpy(); rgb2 = d_rgb.cpu().numpy()
     for b in range(3):
-        ref_xyz, _ = ctx.depth_to_cloud(depth, np.where(label == b + 1, 255, 0).astype(np.uint8), None, 1000.0, intr["fx"], intr["fy"],
-                                        intr["cx"], intr["cy"], 1.5)
+        binmask = np.where(label == b + 1, 255, 0).astype(np.uint8)
+        ref_xyz, _ = ctx.depth_to_cloud(depth, binmask, None, 1000.0, intr["fx"], intr["fy"], intr["cx"], intr["cy"], 1.5)
         assert off2[b + 1] - off2[b] == len(ref_xyz) and xyz2[off2[b]:off2[b + 1]].tobytes() == ref_xyz.tobytes()
+        orc_xyz, orc_rgb = orc.unproject(orc.depth_preprocess(depth, binmask, 1000.0), bgr, intr["fx"], intr["fy"], intr["cx"], intr["cy"], 1.5)
+        assert xyz2[off2[b]:off2[b + 1]].tobytes() == orc_xyz.tobytes() and rgb2[off2[b]:off2[b + 1]].tobytes() == orc_rgb.tobytes(), b
     with pytest.raises(tdv.TdvError):
         ctx.depth_to_cloud_batch_dev(d_depth.data_ptr(), d_masks.data_ptr(), None, 3, w, h, 1000.0, intr["fx"], intr["fy"], intr["cx"], intr["cy"],
                                      1.5, d_xyz.data_ptr(), None, 10)
@@ -159,18 +162,21 @@ def test_all_instance_clouds_camera_parameter_fuzz(ctx, orc, seed):
     if seed == 5: cx = 1.0e-6
     zmax = float(np.float32(rng.uniform(0.2, 2.5) * 1000.0 / scale))
     dev = torch.device("cuda", 0)
-    d_raw = torch.from_numpy(raw.view(np.int16)).to(dev); d_masks = torch.from_numpy(masks).to(dev)
+    bgr = rng.integers(0, 256, (h, w, 3)).astype(np.uint8)
+    d_raw = torch.from_numpy(raw.view(np.int16)).to(dev); d_masks = torch.from_numpy(masks).to(dev); d_bgr = torch.from_numpy(bgr).to(dev)
     cap = B * h * w
-    d_xyz = torch.zeros((cap + 1, 3), dtype=torch.float32, device=dev)
-    for shift in (0, 1):                      # output base 16-B aligned and not
-        out_ptr = d_xyz.data_ptr() + 4 * shift
-        off = ctx.depth_to_cloud_batch_dev(d_raw.data_ptr(), d_masks.data_ptr(), None, B, w, h, scale, fx, fy, cx, cy, zmax, out_ptr, None, cap)
-        flat = d_xyz.cpu().numpy().reshape(-1)[shift:]
+    d_xyz = torch.zeros((cap + 1, 3), dtype=torch.float32, device=dev); d_rgb = torch.zeros((cap + 1, 3), dtype=torch.float32, device=dev)
+    refs = [orc.unproject(orc.depth_preprocess(raw, masks[b], scale), bgr, fx, fy, cx, cy, zmax) for b in range(B)]
+    for shift in (0, 1):                      # output bases 16-B aligned and not
+        out_ptr = d_xyz.data_ptr() + 4 * shift; rgb_ptr = d_rgb.data_ptr() + 4 * shift
+        off = ctx.depth_to_cloud_batch_dev(d_raw.data_ptr(), d_masks.data_ptr(), d_bgr.data_ptr(), B, w, h, scale, fx, fy, cx, cy, zmax, out_ptr, rgb_ptr, cap)
+        flat = d_xyz.cpu().numpy().reshape(-1)[shift:]; flat_rgb = d_rgb.cpu().numpy().reshape(-1)[shift:]
         assert off[B] - off[B - 1] == 0
         for b in range(B):
-            ref_xyz, _ = orc.unproject(orc.depth_preprocess(raw, masks[b], scale), None, fx, fy, cx, cy, zmax)
+            ref_xyz, ref_rgb = refs[b]
             assert off[b + 1] - off[b] == len(ref_xyz)
             assert flat[3 * off[b]:3 * off[b + 1]].tobytes() == ref_xyz.tobytes(), (seed, b, shift)
+            assert flat_rgb[3 * off[b]:3 * off[b + 1]].tobytes() == ref_rgb.tobytes(), (seed, b, shift)
 
 
 def test_all_instance_clouds_mask_rules_every_byte_value(ctx, orc, tdv):
@@ -183,16 +189,19 @@ def test_all_instance_clouds_mask_rules_every_byte_value(ctx, orc, tdv):
     raw[:, ::7, ::5] = 0
     ramp = np.tile(np.arange(256, dtype=np.uint8), (h, 1))       # every byte value in every row
     dev = torch.device("cuda", 0)
-    d_raw = torch.from_numpy(raw.view(np.int16)).to(dev)
+    bgr = rng.integers(0, 256, (3, h, w, 3)).astype(np.uint8)    # one colour frame per depth frame
+    d_raw = torch.from_numpy(raw.view(np.int16)).to(dev); d_bgr = torch.from_numpy(bgr).to(dev)
     fx, fy, cx, cy, zmax, scale = 300.0, 310.0, 128.5, 15.5, 1.7, 1000.0
 
-    def run(masks_np, n_inst, mask_format, mask_mode, n_frames, fmap):
+    def run(masks_np, n_inst, mask_format, mask_mode, n_frames, fmap, colours=False):
         d_masks = torch.from_numpy(masks_np).to(dev)
         cap = n_inst * h * w
         d_xyz = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
-        off = ctx.depth_to_cloud_batch_dev(d_raw.data_ptr(), d_masks.data_ptr(), None, n_inst, w, h, scale, fx, fy, cx, cy, zmax, d_xyz.data_ptr(), None, cap,
+        d_rgb = torch.zeros((cap, 3), dtype=torch.float32, device=dev) if colours else None
+        off = ctx.depth_to_cloud_batch_dev(d_raw.data_ptr(), d_masks.data_ptr(), d_bgr.data_ptr() if colours else None, n_inst, w, h, scale, fx, fy, cx, cy, zmax,
+                                           d_xyz.data_ptr(), d_rgb.data_ptr() if colours else None, cap,
                                            mask_format=mask_format, mask_mode=mask_mode, n_frames=n_frames, frame_of_instance=fmap)
-        return off, d_xyz.cpu().numpy()
+        return off, d_xyz.cpu().numpy(), (d_rgb.cpu().numpy() if colours else None)
 
     def expect(frame, keep):
         depth = raw[frame].astype(np.float32) * np.float32(1.0 / scale)
@@ -203,12 +212,16 @@ def test_all_instance_clouds_mask_rules_every_byte_value(ctx, orc, tdv):
     stacked = np.stack([np.roll(ramp, 17 * b, axis=1) for b in range(5)])
     fmap = np.array([0, 1, 2, 1, 0], np.int32)
     for mode, rule in ((tdv.TDV_MASK_THRESHOLD10, lambda m: m > 10), (tdv.TDV_MASK_NONZERO, lambda m: m != 0)):
-        off, xyz = run(stacked, 5, 0, mode, 3, fmap)
+        off, xyz, rgb = run(stacked, 5, 0, mode, 3, fmap, colours=True)
         for b in range(5):
             ref = expect(fmap[b], rule(stacked[b]))
             assert off[b + 1] - off[b] == len(ref) and xyz[off[b]:off[b + 1]].tobytes() == ref.tobytes(), (mode, b)
+            # the oracle's own chain on a binary mask that states the rule (255 passes its `> 10`), with the instance's colour frame
+            orc_xyz, orc_rgb = orc.unproject(orc.depth_preprocess(raw[fmap[b]], np.where(rule(stacked[b]), 255, 0).astype(np.uint8), scale), bgr[fmap[b]],
+                                             fx, fy, cx, cy, zmax)
+            assert xyz[off[b]:off[b + 1]].tobytes() == orc_xyz.tobytes() and rgb[off[b]:off[b + 1]].tobytes() == orc_rgb.tobytes(), (mode, b)
     # one label image, 255 instances: instance b keeps the pixels whose value is b + 1 (value 0 belongs to nobody)
-    off, xyz = run(ramp, 255, 1, tdv.TDV_MASK_THRESHOLD10, 1, None)
+    off, xyz, _ = run(ramp, 255, 1, tdv.TDV_MASK_THRESHOLD10, 1, None)
     for b in (0, 1, 9, 10, 126, 127, 128, 199, 253, 254):
         ref = expect(0, ramp == b + 1)
         assert off[b + 1] - off[b] == len(ref) > 0 and xyz[off[b]:off[b + 1]].tobytes() == ref.tobytes(), b
@@ -303,5 +316,17 @@ def test_batch_resizes_mismatched_masks_and_takes_u16_labels(ctx, tdv, synth, or
                    x["T"].tobytes() == y["T"].tobytes() and x["coarse_inliers"] == y["coarse_inliers"] for x, y in zip(a, b))
     assert same(run(small, mask_width=w // 2, mask_height=h // 2), run(full))
     assert same(run(label.view(np.int16), mask_format=2), run(stacked_from_label))
+    bgr = np.random.default_rng(2).integers(0, 256, (h, w, 3)).astype(np.uint8)
+    d_label = torch.from_numpy(label.view(np.int16)).to(dev); d_bgr = torch.from_numpy(bgr).to(dev)
+    cap = int((label > 0).sum())
+    d_xyz = torch.zeros((cap, 3), dtype=torch.float32, device=dev); d_rgb = torch.zeros((cap, 3), dtype=torch.float32, device=dev)
+    cam = (intr["fx"], intr["fy"], intr["cx"], intr["cy"])
+    off = ctx.depth_to_cloud_batch_dev(d_depth.data_ptr(), d_label.data_ptr(), d_bgr.data_ptr(), 3, w, h, 1000.0, *cam, 1.5, d_xyz.data_ptr(), d_rgb.data_ptr(), cap,
+                                       mask_format=2)
+    xyz = d_xyz.cpu().numpy(); rgb = d_rgb.cpu().numpy()
+    for b in range(3):
+        orc_xyz, orc_rgb = orc.unproject(orc.depth_preprocess(depth, stacked_from_label[b], 1000.0), bgr, *cam, 1.5)
+        assert off[b + 1] - off[b] == len(orc_xyz) > 500
+        assert xyz[off[b]:off[b + 1]].tobytes() == orc_xyz.tobytes() and rgb[off[b]:off[b + 1]].tobytes() == orc_rgb.tobytes(), b
     with pytest.raises(tdv.TdvError):
         run(label.view(np.int16), mask_format=2, mask_width=w // 2, mask_height=h // 2)

@@ -193,7 +193,7 @@ def _err_null_cloud(tdv, ctx):
 
 ERRORS = [_err_deproject, _err_depth_to_cloud_dev, _err_voxel_dev, _err_icp_loss, _err_null_cloud]
 # every case after one of the five errors in turn, and every entry point that can return the error right before its own cases: those
-# share the most state with it (the chain ticket that depth.hip repairs after a failed launch, the voxel table, the ICP settings)
+# share the most state with it (the chain ticket that depth_cloud.hip repairs after a failed launch, the voxel table, the ICP settings)
 OWN = {_err_deproject: "deproject", _err_depth_to_cloud_dev: "depth_to_cloud", _err_voxel_dev: "voxel_", _err_icp_loss: "icp_", _err_null_cloud: "estimate_normals"}
 PAIRS = [(ERRORS[k % len(ERRORS)], name) for k, name in enumerate(NAMES)]
 PAIRS += [(err, name) for err in ERRORS for name in NAMES if name.startswith(OWN[err]) and (err, name) not in PAIRS]

@@ -1,4 +1,4 @@
-"""Study: one frame's depth -> cloud (csrc/depth.hip: k_depth_cloud_chain; TDV_DEPTH_THREE_PASS=1 with the study library = rounds 1-3).
+"""Study: one frame's depth -> cloud (csrc/depth_cloud.hip: k_depth_cloud_chain; TDV_DEPTH_THREE_PASS=1 with the study library = rounds 1-3).
 Prints tools/opbench.py's two depth rows."""
 import importlib, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
