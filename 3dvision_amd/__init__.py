@@ -71,6 +71,7 @@ ABI_SYMBOLS = [
     "tdv_mesh_verify_default_params", "tdv_verify_poses_mesh", "tdv_verify_poses_mesh_dev", "tdv_render_depth_mesh", "tdv_render_depth_mesh_dev",
     "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
     "tdv_tsdf_default_params", "tdv_tsdf_volume_bytes", "tdv_tsdf_reset_dev", "tdv_tsdf_integrate_dev", "tdv_tsdf_extract_dev", "tdv_tsdf_fuse",
+    "tdv_tsdf_extract_mesh_dev", "tdv_tsdf_fuse_mesh",
     "tdv_voxel_downsample_normals", "tdv_voxel_downsample_normals_dev",
     "tdv_icp_level_default", "tdv_icp_multiscale", "tdv_icp_multiscale_dev", "tdv_icp_multiscale_batch_dev",
 ]
@@ -349,6 +350,7 @@ TDV_TSDF_MAX_VOXELS = 1 << 27
 TDV_TSDF_HOST_MAX_VOXELS = 1 << 25
 TDV_TSDF_MAX_FRAMES = 64
 TDV_TSDF_TILE_X, TDV_TSDF_TILE_Y, TDV_TSDF_TILE_Z = 64, 8, 8
+TDV_TSDF_MC_MAX_TRIANGLES = 5
 
 
 class TsdfVolumeC(C.Structure):
@@ -369,6 +371,15 @@ def tsdf_volume_struct(origin, voxel_length, dims):
     """The tdv_tsdf_volume of a grid of dims = (nx, ny, nz) voxels of voxel_length metres whose corner (not first centre) is origin."""
     o = np.asarray(origin, np.float32).reshape(3)
     return TsdfVolumeC((C.c_float * 3)(*[float(x) for x in o]), float(np.float32(voxel_length)), int(dims[0]), int(dims[1]), int(dims[2]))
+
+
+def mesh_compact(vertices, normals, triangles):
+    """The mesh without the vertices no triangle refers to: the kept rows in their order, the triangles renumbered (numpy, on the host)."""
+    triangles = np.asarray(triangles, np.int32).reshape(-1, 3)
+    used = np.zeros(len(vertices), bool)
+    used[triangles.reshape(-1)] = True
+    new = (np.cumsum(used) - 1).astype(np.int32)
+    return vertices[used], (None if normals is None else normals[used]), new[triangles].reshape(-1, 3)
 
 
 def _poses16(poses):
@@ -1608,6 +1619,64 @@ class Context:
         if m:
             call(xyz, nrm, m)
         return xyz, nrm
+
+    def tsdf_extract_mesh_dev(self, vol, d_volume, d_out_vertices, d_out_normals, vertex_capacity, d_out_triangles, triangle_capacity, **params):
+        """tdv_tsdf_extract_mesh_dev: the volume's surface as a triangle mesh whose vertices are tsdf_extract_dev's rows - vertices and
+        normals (optional) into d_out_vertices / d_out_normals (vertex_capacity rows of 3 floats), the triangles into d_out_triangles
+        (triangle_capacity rows of 3 int32).  Returns (n_vertices, n_triangles, fits): with fits False that many rows are needed and
+        nothing was written."""
+        nv, nt = C.c_int(-1), C.c_int(-1)
+        st = lib().tdv_tsdf_extract_mesh_dev(self._h, C.byref(vol), _ptr(d_volume), C.byref(tsdf_params(**params)), _ptr(d_out_vertices),
+                                             _ptr(d_out_normals), int(vertex_capacity), C.byref(nv), _ptr(d_out_triangles), int(triangle_capacity),
+                                             C.byref(nt))
+        if st == -2 and ((nv.value > int(vertex_capacity) >= 0) or (nt.value > int(triangle_capacity) >= 0)):
+            return nv.value, nt.value, False
+        _check(self._h, st, "tdv_tsdf_extract_mesh_dev")
+        return nv.value, nt.value, True
+
+    def tsdf_extract_mesh(self, volume, normals=True, compact=False, **params):
+        """The mesh of volume = tsdf_volume()'s pair: (vertices float32[n, 3], normals float32[n, 3] or None, triangles int32[m, 3]).  The
+        vertices are tsdf_extract's rows; compact=True drops those no triangle refers to (mesh_compact)."""
+        import torch
+        vol, buf = volume
+        nv, nt, _ = self.tsdf_extract_mesh_dev(vol, buf.data_ptr(), None, None, 0, None, 0, **params)
+        out = torch.zeros((2 if normals else 1, max(nv, 1), 3), dtype=torch.float32, device=buf.device)
+        tri = torch.zeros((max(nt, 1), 3), dtype=torch.int32, device=buf.device)
+        torch.cuda.synchronize()
+        self.tsdf_extract_mesh_dev(vol, buf.data_ptr(), out[0].data_ptr(), out[1].data_ptr() if normals else None, nv, tri.data_ptr(), nt, **params)
+        self.synchronize()
+        h = out.cpu().numpy()
+        mesh = h[0, :nv].copy(), (h[1, :nv].copy() if normals else None), tri.cpu().numpy()[:nt].copy()
+        return mesh_compact(*mesh) if compact else mesh
+
+    def tsdf_fuse_mesh(self, frames, poses, intrinsics, volume, normals=True, compact=False, **params):
+        """tdv_tsdf_fuse_mesh on host arrays (tsdf_fuse's arguments): (vertices, normals or None, triangles int32[m, 3]).  The first call asks
+        for the counts, the second brings the rows."""
+        vol = volume if isinstance(volume, TsdfVolumeC) else tsdf_volume_struct(*volume)
+        frames = np.ascontiguousarray(frames, np.uint16)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        t, n = _poses16(poses)
+        if n != len(frames):
+            raise ValueError("tdv_tsdf_fuse_mesh: one pose per frame")
+        scale, fx, fy, cx, cy = intrinsics
+        p = tsdf_params(**params)
+
+        def call(xyz, nrm, vcap, tri, tcap):
+            nv, nt = C.c_int(-1), C.c_int(-1)
+            st = lib().tdv_tsdf_fuse_mesh(self._h, C.byref(vol), _ptr(frames), n, frames.shape[2], frames.shape[1], C.c_float(scale), C.c_float(fx),
+                                          C.c_float(fy), C.c_float(cx), C.c_float(cy), _ptr(t), C.byref(p), _ptr(xyz), _ptr(nrm), vcap, C.byref(nv),
+                                          _ptr(tri), tcap, C.byref(nt))
+            if not (st == -2 and (nv.value > vcap or nt.value > tcap)):
+                _check(self._h, st, "tdv_tsdf_fuse_mesh")
+            return nv.value, nt.value
+
+        nv, nt = call(None, None, 0, None, 0)
+        xyz = np.zeros((nv, 3), np.float32)
+        nrm = np.zeros((nv, 3), np.float32) if normals else None
+        tri = np.zeros((nt, 3), np.int32)
+        if nv:
+            call(xyz, nrm, nv, tri if nt else None, nt)
+        return mesh_compact(xyz, nrm, tri) if compact else (xyz, nrm, tri)
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

@@ -1194,6 +1194,33 @@ int tdv_mesh_sample_points_dev(tdv_ctx* ctx, const float* d_vertices, int n_vert
  *      it is 0.  The crossing's normal is n = g_a*r_b + g_b*r_a per component, L = sqrtf((nx*nx + ny*ny) + nz*nz), and the row is n / L per
  *      component, or (0, 0, 0) where L is zero or not finite.  A positive tsdf is in front of the surface, so the normal points out of the
  *      object, towards where it was seen from.
+ * The mesh (Open3D's extract_triangle_mesh; marching cubes, Lorensen and Cline 1987): vertex v of the mesh IS row v of
+ * tdv_tsdf_extract_dev's cloud, same bytes and same normals, and the new output is the triangle list over those rows.  A crossing that
+ * no triangle uses stays in the vertex array unreferenced (at the rim of the observed region, where a cell has an unobserved corner).
+ *  T9. Cell.  Cell (i, j, k) exists for 0 <= i < nx-1, 0 <= j < ny-1, 0 <= k < nz-1; a volume with a side of 1 has no cell.  Its corner q,
+ *      q = 0..7, is voxel (i + (q&1), j + ((q>>1)&1), k + ((q>>2)&1)).  The cell is usable iff all eight corners are observed (T6).  Its
+ *      case is the sum of 1 << q over the corners with f_q < 0; zero and negative zero count as non-negative, as in T7.
+ *  T10. Cell edge.  e = 4*axis + idx, and its owner is the corner at which it starts: x: idx = dy + 2*dz, owner (0, dy, dz); y: idx =
+ *      dx + 2*dz, owner (dx, 0, dz); z: idx = dx + 2*dy, owner (dx, dy, 0).  Its vertex is T7's crossing with key 3*voxel_index(owner) +
+ *      axis: in a usable cell every edge whose ends differ in sign is one of T7's crossings.  The vertex index is the rank of that key
+ *      among T7's keys, which is the row number in tdv_tsdf_extract_dev's output.
+ *  T11. The table (256 cases), by rule; tools/gen_tsdf_mc_table.py makes csrc/tsdf_mc_table.hpp from it.
+ *      1. Segments.  Each of the cube's six faces has 0, 2 or 4 edges that cross.  With 2, one segment joins them.  With 4 the two
+ *         negative corners lie on a diagonal, and each is cut off on its own: a segment joins the two face edges that meet at it.  A
+ *         face's segments depend on that face's four signs only, so the two cells that share a face draw the same segments.
+ *      2. Loops.  Every crossing edge lies on exactly two segments, so the segments chain into closed loops.
+ *      3. Direction.  A loop is listed from its smallest edge number.  With m_e the midpoint of edge e on the unit cube, N = the sum of
+ *         m_i x m_(i+1), cyclic over the loop, and D = the sum over the loop's edges of (the non-negative end - the negative end), the
+ *         direction is the one with N . D > 0 (it is never 0).
+ *      4. A case's loops come in ascending order of their smallest edge.
+ *      5. Triangles.  The loop is rotated to start at the first position r = 0, 1, ... for which no fan diagonal (m_0, m_i),
+ *         2 <= i <= n-2, joins two edges that lie on a common cube face (such an r exists); the triangles are then (m_0, m_i, m_(i+1))
+ *         for i = 1 .. n-2.  Without the rotation a diagonal inside an ambiguous face would be drawn by both cells that share the face.
+ *      820 triangles in all, at most TDV_TSDF_MC_MAX_TRIANGLES in a case; the mesh is watertight wherever the cells are usable.
+ *  T12. Output.  A triangle is a row of three int32 vertex indices.  Rows come in ascending cell index (k*ny + j)*nx + i, and within a
+ *      cell in the table's order.  (vb - va) x (vc - va) points to the non-negative side: T8's normal side, the front face under
+ *      TDV_MESH_CULL_BACK, tdv_mesh_sample_points' outward normal.  A triangle of zero area (a corner's value is exactly 0 and the three
+ *      crossings at it coincide) is emitted like any other; the sampler and the verifier set such triangles aside.
  * tdv_tsdf_integrate_dev: d_raw holds n_frames u16 images (width x height, row-major) back to back on the device, h_poses n_frames x 16
  * floats (column-major each) on the host; h_n_updated (optional, host, [n_frames]) costs the call its one read-back.  All frames of a call
  * are integrated in one pass over the volume.  n_frames == 0 is valid and leaves the volume as it is.  NaN or infinite pose entries fall
@@ -1203,17 +1230,23 @@ int tdv_mesh_sample_points_dev(tdv_ctx* ctx, const float* d_vertices, int n_vert
  * needed count and no row written, as tdv_deproject does.  One read-back, the count.
  * tdv_tsdf_fuse: host arrays throughout - reset, integrate and extract with the volume in the ctx's workspace; volumes above
  * TDV_TSDF_HOST_MAX_VOXELS are refused.
+ * tdv_tsdf_extract_mesh_dev: d_out_vertices and d_out_normals (optional) receive *n_vertices rows of 3 floats, tdv_tsdf_extract_dev's
+ * rows; d_out_triangles receives *n_triangles rows of 3 ints (T12).  If either capacity is too small (NULL outputs with capacity 0 are a
+ * query) the call returns TDV_ERR_BAD_ARG with both counts set and nothing written.  One read-back: both counts in one copy.
+ * tdv_tsdf_fuse_mesh: tdv_tsdf_fuse with the mesh outputs, host arrays throughout.
  * Kernels (csrc/tsdf.hip): integrate is one launch per call, a lane per voxel, the pair loaded and stored once (and not at all where no
  * frame updates it), the poses read through scalar loads.  Extract stages tiles of TDV_TSDF_TILE_X x _Y x _Z voxels with their halo in
  * LDS, counts the crossings per run of TDV_TSDF_TILE_X voxels along x, scans the counts (no atomic decides an output position) and
- * writes the rows.
+ * writes the rows.  The mesh counts the triangles of a run's cells in the same pass as its crossings, scans both, and a lane per cell
+ * writes the triangles; a vertex index is the run offset of the edge's owner voxel plus the crossings ranked before it, from ballots kept
+ * in LDS.  Its workspace is a few ints per run.
  * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, vol, params, volume buffer, frames or poses (n_frames > 0), n_out,
- * or d_out_xyz with capacity > 0; a side < 1 or > TDV_TSDF_MAX_SIDE; nx*ny*nz above TDV_TSDF_MAX_VOXELS (tdv_tsdf_fuse:
+ * n_vertices, n_triangles, or d_out_xyz / d_out_vertices / d_out_triangles with its capacity > 0; a side < 1 or > TDV_TSDF_MAX_SIDE; nx*ny*nz above TDV_TSDF_MAX_VOXELS (tdv_tsdf_fuse:
  * TDV_TSDF_HOST_MAX_VOXELS); voxel_length, scale, fx or fy <= 0 or non-finite; trunc < 0 or non-finite; max_weight < 1 or non-finite;
  * min_weight <= 0 or non-finite; n_frames < 0 or > TDV_TSDF_MAX_FRAMES; width or height < 0 or > TDV_VERIFY_MAX_SIDE; an unknown
  * pose_direction; capacity < 0.  The ctx's switches do not apply.
- * Not provided: colour, per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, mesh extraction and
- * ray casting, the C++ operator mirror. */
+ * Not provided: colour, per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, ray casting, the C++
+ * operator mirror. */
 typedef struct tdv_tsdf_volume { float origin[3]; float voxel_length; int nx, ny, nz; } tdv_tsdf_volume;   /* 28 bytes */
 typedef struct tdv_tsdf_params {   /* 20 bytes */
     float trunc;           /* truncation distance in metres; default 0, which means 4.0f * voxel_length */
@@ -1229,6 +1262,7 @@ typedef struct tdv_tsdf_params {   /* 20 bytes */
 #define TDV_TSDF_TILE_X 64   /* the tile k_tsdf_extract stages in LDS; a wave owns a run of TILE_X voxels along x */
 #define TDV_TSDF_TILE_Y 8
 #define TDV_TSDF_TILE_Z 8
+#define TDV_TSDF_MC_MAX_TRIANGLES 5        /* T11: the most triangles of one cell */
 void tdv_tsdf_default_params(tdv_tsdf_params* params);
 unsigned long long tdv_tsdf_volume_bytes(const tdv_tsdf_volume* vol);
 int tdv_tsdf_reset_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_volume);
@@ -1241,6 +1275,13 @@ int tdv_tsdf_extract_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* 
 int tdv_tsdf_fuse(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t* raw, int n_frames, int width, int height, float scale, float fx,
                   float fy, float cx, float cy, const float* poses, const tdv_tsdf_params* params, float* out_xyz,
                   float* out_normals /* optional */, int capacity, int* n_out);
+int tdv_tsdf_extract_mesh_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const tdv_tsdf_params* params,
+                              float* d_out_vertices, float* d_out_normals /* optional */, int vertex_capacity, int* n_vertices /* host */,
+                              int* d_out_triangles, int triangle_capacity, int* n_triangles /* host */);
+int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t* raw, int n_frames, int width, int height, float scale,
+                       float fx, float fy, float cx, float cy, const float* poses, const tdv_tsdf_params* params, float* out_vertices,
+                       float* out_normals /* optional */, int vertex_capacity, int* n_vertices, int* out_triangles, int triangle_capacity,
+                       int* n_triangles);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
