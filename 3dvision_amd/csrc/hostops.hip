@@ -101,6 +101,11 @@ int tdv_ransac_score_unit_block(int wg, int visit, int n_blk) {
     return tdv::score_unit_block(wg, visit, n_blk);
 }
 int tdv_ransac_score_unit_chunks(void) { return RS_UNIT; }
+// The batch schedule of a RANSAC call with bail-out (ransac_cut.hpp), for the CPU suite.
+int tdv_ransac_batch_size(int it0) {
+    if (it0 < 0) return TDV_ERR_BAD_ARG;
+    return tdv::ransac_batch_size(it0);
+}
 
 }  // extern "C"
 

@@ -193,13 +193,14 @@ __device__ __forceinline__ void ransac_prejudge(const PreJob& j, const float* o,
 // up != nullptr: the batch's triples as the host drew them, in pinned host memory, which the device reads as it is (it writes a
 // batch's record there).  Lane h loads its triple from there and stores it to `triples` for the batch's later kernels (the bound, the
 // select kernels and k_ransac_finish ask triples.valid(h)): the batch needs no copy in front of this kernel.
-__global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, const void* __restrict__ up, int count, int h_pad,
+// h_end: the hypothesis slots this batch covers (whole scoring blocks, the padding behind `count` as invalid lanes); h_pad is the stride.
+__global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, const void* __restrict__ up, int count, int h_end, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
                                     float band_u /* E = band_u (A + s): kBandUnit or kBandUnitMatrix */, const PlanJob plan, const PreJob pre) {
     int h = blockIdx.x * blockDim.x + threadIdx.x;
     if (h == 0 && plan.plan) ransac_plan(plan);
-    if (h < plan.n_units) plan.units[h] = 0;     // job B of this batch's two scoring dispatches draws its units from them (n_units <= h_pad)
-    if (h >= h_pad) return;
+    if (h < plan.n_units) plan.units[h] = 0;     // job B of this batch's two scoring dispatches draws its units from them (n_units <= h_end)
+    if (h >= h_end) return;
     counts[h] = 0;                       // the scoring kernel adds its point-splits' counts here (one memset launch less per batch)
     bool valid = false;
     int4 tr = make_int4(0, 0, 0, 0);
@@ -671,12 +672,18 @@ __global__ void k_ransac_select(const TriView triples, int count, const int* __r
 // The register form of the two one-workgroup kernels (k_ransac_select_live, k_ransac_finish).  Both walk the live lists twice, and a
 // trip of the loops is a chain of two dependent loads - live[i], then counts[live[i]] - that ends in a reduction, which keeps the
 // trips apart: 7 trips x 2 round trips x 2 passes with the headline's 7,100 live hypotheses, on one workgroup.  So where the far and
-// the near list together hold at most LIVE_REG x 1,024 entries, thread t takes entries t, t + 1024, ... into registers at once: all the
+// the near list together hold at most LIVE_MAX x 1,024 entries, thread t takes entries t, t + 1024, ... into registers at once: all the
 // list loads back to back, then all the gathers, and both passes work from the registers.  Every load is unconditional - one under
 // `if (i < n)` is an exec-masked block of its own with a full wait in front of it (icp.hip: acc_fetch): an entry past the end reads
 // live[0], whatever it holds, and gathers counts[0]; `on` says which entries count.  Longer lists keep the loops.
-constexpr int LIVE_REG = 8;
-struct LiveRegs { int h[LIVE_REG], c[LIVE_REG], u[LIVE_REG]; };     // hypothesis, its count, its UB_F (near entries; else not looked at)
+// The fetch goes in rounds of LIVE_REG entries per thread, a round's loads in flight together; a round the lists do not reach
+// (workgroup-uniform) is not fetched, so a batch of kRansacBatch - whose lists end inside the first - pays for one round as ever, and a
+// grown batch's lists (14k entries at 131,072 hypotheses) take two.
+#ifndef RS_LIVE_ROUNDS
+#define RS_LIVE_ROUNDS 2     // tuning builds: 1 is the form of one round, 8,192 entries
+#endif
+constexpr int LIVE_REG = 8, LIVE_ROUNDS = RS_LIVE_ROUNDS, LIVE_MAX = LIVE_REG * LIVE_ROUNDS;
+struct LiveRegs { int h[LIVE_MAX], c[LIVE_MAX], u[LIVE_MAX]; };     // hypothesis, its count, its UB_F (near entries; else not looked at)
 __device__ __forceinline__ bool live_on(int e, int tot) { return (int)threadIdx.x + e * 1024 < tot; }
 __device__ __forceinline__ bool live_is_near(int e, int n, int tot) { const int i = (int)threadIdx.x + e * 1024; return i >= n && i < tot; }
 // far list `live` (n entries), near list `near` behind it (n2 entries; nullptr with n2 == 0); ubf == nullptr: no u[]
@@ -684,15 +691,24 @@ __device__ __forceinline__ void live_fetch(LiveRegs& L, const int* __restrict__ 
                                            const int* __restrict__ counts, const int* __restrict__ ubf) {
     const int tot = n + n2;
 #pragma unroll
-    for (int e = 0; e < LIVE_REG; ++e) {
-        const int i = (int)threadIdx.x + e * 1024;
-        L.h[e] = *(live_is_near(e, n, tot) ? near + (i - n) : live + (i < n ? i : 0));
-    }
+    for (int r = 0; r < LIVE_ROUNDS; ++r) {
+        const int e0 = r * LIVE_REG;
+        if (r && e0 * 1024 >= tot) {                                 // (workgroup-uniform) nothing reaches this round: its entries are off
 #pragma unroll
-    for (int e = 0; e < LIVE_REG; ++e) L.c[e] = counts[live_on(e, tot) ? L.h[e] : 0];
-    if (ubf) {
+            for (int e = e0; e < e0 + LIVE_REG; ++e) { L.h[e] = 0; L.c[e] = 0; L.u[e] = 0; }
+            continue;
+        }
 #pragma unroll
-        for (int e = 0; e < LIVE_REG; ++e) L.u[e] = *(live_is_near(e, n, tot) ? ubf + L.h[e] : counts);
+        for (int e = e0; e < e0 + LIVE_REG; ++e) {
+            const int i = (int)threadIdx.x + e * 1024;
+            L.h[e] = *(live_is_near(e, n, tot) ? near + (i - n) : live + (i < n ? i : 0));
+        }
+#pragma unroll
+        for (int e = e0; e < e0 + LIVE_REG; ++e) L.c[e] = counts[live_on(e, tot) ? L.h[e] : 0];
+        if (ubf) {
+#pragma unroll
+            for (int e = e0; e < e0 + LIVE_REG; ++e) L.u[e] = *(live_is_near(e, n, tot) ? ubf + L.h[e] : counts);
+        }
     }
 }
 __global__ __launch_bounds__(1024)
@@ -701,7 +717,7 @@ void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ 
                           const int* __restrict__ state, int* __restrict__ plan, int* __restrict__ list, int* __restrict__ list2) {
     const int n = *n_live, n2 = near ? *n_near : 0, best = state[0], rest = ransac_rest(ns, plan[0]), rest2 = ransac_rest(ns, plan[3]);
     const int tot = n + n2;
-    const bool in_regs = tot <= LIVE_REG * 1024;                     // (workgroup-uniform)
+    const bool in_regs = tot <= LIVE_MAX * 1024;                     // (workgroup-uniform)
     __shared__ int s_max, s_n[2];
     if (threadIdx.x == 0) { s_max = 0; s_n[0] = 0; s_n[1] = 0; }
     __syncthreads();
@@ -710,7 +726,7 @@ void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ 
     if (in_regs) {
         live_fetch(L, live, n, near, n2, counts, near ? ubf : nullptr);
 #pragma unroll
-        for (int e = 0; e < LIVE_REG; ++e) c = max(c, live_on(e, tot) ? L.c[e] : 0);
+        for (int e = 0; e < LIVE_MAX; ++e) c = max(c, live_on(e, tot) ? L.c[e] : 0);
     } else
         for (int i = threadIdx.x; i < tot; i += 1024) c = max(c, counts[i < n ? live[i] : near[i - n]]);
 #pragma unroll
@@ -721,19 +737,23 @@ void k_ransac_select_live(const int* __restrict__ live, const int* __restrict__ 
     if (in_regs) {
         // no load from here on.  A wave's 64 entries may hold the far list's end and the near list's start: one ballot per list.
 #pragma unroll
-        for (int e = 0; e < LIVE_REG; ++e) {
-            if (e * 1024 >= tot) break;                              // (workgroup-uniform: every lane reaches the ballots)
+        for (int e = 0; e < LIVE_MAX; ++e) {
+            // (workgroup-uniform: every lane reaches the ballots.  `continue`, not `break`: with a way out of it the compiler does
+            // not unroll this loop, and L, indexed by a loop variable then, goes to scratch)
+            if (e * 1024 >= tot) continue;
             const bool is_near = live_is_near(e, n, tot);
             const int r = is_near ? rest2 + L.u[e] : rest;
             const bool keep = live_on(e, tot) && r > 0 && ransac_keep(L.c[e], r, best, in_batch, ns, confidence);
+#pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const bool mine = keep && is_near == (k == 1);
                 const unsigned long long m = __ballot(mine);
-                if (!m) continue;
-                int at = 0;
-                if (lane == 0) at = atomicAdd(&s_n[k], __popcll(m));
-                at = __shfl(at, 0, 64);
-                if (mine) (k ? list2 : list)[at + __popcll(m & ((1ull << lane) - 1ull))] = L.h[e];
+                if (m) {
+                    int at = 0;
+                    if (lane == 0) at = atomicAdd(&s_n[k], __popcll(m));
+                    at = __shfl(at, 0, 64);
+                    if (mine) (k ? list2 : list)[at + __popcll(m & ((1ull << lane) - 1ull))] = L.h[e];
+                }
             }
         }
     } else
@@ -896,11 +916,15 @@ void k_order_scatter(const float* __restrict__ pq, int ns, const unsigned long l
 // live != nullptr (a bounded batch, confidence >= 0): only the live lists - far and near - are read.  A dead hypothesis has count 0: no new best
 // (strict > on a best fitness >= 0), no exit (0 > confidence is false), nothing to raise.
 // One workgroup; the first batch and the live lists are a few thousand entries (a whole batch is walked only with the bound off).
+// LISTS == false (live_in == nullptr: no lists) is the kernel without the register form - what a call without bail-out runs, whose
+// path through the instance with it, 48 more registers' worth of code, measured 17 us per call longer (C4, profiles/r27 section 6).
+template <bool LISTS>
 __global__ __launch_bounds__(1024)
-void k_ransac_finish(const TriView triples, int count, const int* __restrict__ counts, const int* __restrict__ live, const int* __restrict__ n_live,
+void k_ransac_finish(const TriView triples, int count, const int* __restrict__ counts, const int* __restrict__ live_in, const int* __restrict__ n_live,
                      const int* __restrict__ near, const int* __restrict__ n_near, const float* __restrict__ hyp, int h_pad, int ns, float confidence, int it0,
                      int* __restrict__ state, int* __restrict__ sel, float* __restrict__ best12, const int* __restrict__ bad, int* __restrict__ rec,
                      const int* __restrict__ lists, long long* __restrict__ bound, const int seq) {
+    const int* const live = LISTS ? live_in : nullptr;
     const int n1 = live ? *n_live : count, n = n1 + (live && near ? *n_near : 0);      // (the near list behind the far one)
     const float fn = static_cast<float>((size_t)ns);
     __shared__ int s_stop, s_max;
@@ -908,12 +932,12 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     if (threadIdx.x == 0) { s_stop = INT_MAX; s_max = 0; }
     __syncthreads();
     int stop = INT_MAX, cmax = 0;
-    const bool in_regs = live && n <= LIVE_REG * 1024;           // the register form (see live_fetch); workgroup-uniform
+    const bool in_regs = live && n <= LIVE_MAX * 1024;           // the register form (see live_fetch); workgroup-uniform
     LiveRegs L;
     if (in_regs) {
         live_fetch(L, live, n1, near, n - n1, counts, nullptr);
 #pragma unroll
-        for (int e = 0; e < LIVE_REG; ++e) {
+        for (int e = 0; e < LIVE_MAX; ++e) {
             if (!live_on(e, n)) continue;
             cmax = max(cmax, L.c[e]);
             if (static_cast<float>(L.c[e]) / fn > confidence) stop = min(stop, L.h[e]);
@@ -939,7 +963,7 @@ void k_ransac_finish(const TriView triples, int count, const int* __restrict__ c
     unsigned long long best = 0ull;
     if (in_regs) {
 #pragma unroll
-        for (int e = 0; e < LIVE_REG; ++e) {                     // from the registers: no load
+        for (int e = 0; e < LIVE_MAX; ++e) {                     // from the registers: no load
             if (!live_on(e, n) || L.h[e] > k_stop) continue;
             const float fit = static_cast<float>(L.c[e]) / fn;   // registration.cpp:281
             if (!(fit > 0.f)) continue;
@@ -1520,7 +1544,7 @@ static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * 
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far, end_event, timer_events; int drop_permille, a_permille, u_cut_permille, fine_y; float far_radius, live_radius; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far, end_event, timer_events; int drop_permille, a_permille, u_cut_permille, fine_y, grown; float far_radius, live_radius; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1549,6 +1573,9 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     // cuts the leaf pairs into fine_y ranges (profiles/r14/ransac_bound_lists.md)
     k.live_radius = study_env("TDV_RANSAC_LIVE_RADIUS") ? (float)atof(study_env("TDV_RANSAC_LIVE_RADIUS")) : 20.f;
     k.fine_y = study_env("TDV_RANSAC_FINE_Y") ? std::min(std::max(atoi(study_env("TDV_RANSAC_FINE_Y")), 1), 64) : RB_FINE_Y;
+    // the batch schedule (ransac_cut.hpp: ransac_batch_size): the grown batch's size - kRansacBatch: no growth, the A/B.  (The fine
+    // level keeps fine_y ranges at either size: 2, 4 and 8 measured equal for a grown batch, profiles/r27/ransac_batch_growth.md.)
+    k.grown = study_env("TDV_RANSAC_GROWN") ? (int)align_up((size_t)std::min(std::max(atoi(study_env("TDV_RANSAC_GROWN")), kRansacBatch), 4 * kRansacBatch), RS_HYP_PER_BLOCK) : kRansacGrown;
     // class-major leaves (k_leaf_keys): built and measured, off by default - on a 9,999-point cloud they take the live list from 4,317 to
     // 4,063 hypotheses, one block of 1,024 fewer for the two-way order but not for the far and near lists together, and
     // tests/test_gpu_ransac_far_bound.py holds the far bound strictly under the two-way order there
@@ -1567,11 +1594,11 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
 // One of the two sets of batch buffers: batch k+1 is drawn on the host and enqueued while the GPU scores batch k; results are
 // consumed in iteration order, so the outcome is that of the sequential loop.
 struct RansacBuf {
-    float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses, their counts, the triples on the device (k_ransac_hypotheses stores them); bail-out: phase 2's list
+    float* hyp; int* counts; void* tri; int* list;    // [14][h_pad] hypotheses (h_pad: the call's largest batch, the stride; a batch fills its own slots()), their counts, the triples on the device (k_ransac_hypotheses stores them); bail-out: phase 2's list
     int *live, *und, *acc, *ticket;                   // RansacLeafBound: live list, undecided list, its fine sums and tickets
     int *near, *list2, *ubf;                          // RansacFarBound: near list, its phase 2's list, UB_F per hypothesis
     int* flags;                                       // RansacBoundLists: ransac_prejudge's word per hypothesis (RB_CLOSE, RB_NEAR)
-    int* units;                                       // bail-out: job B's ticket words, [far, near][2 phases][8 XCDs][h_pad / RS_BLOCK], zeroed by the batch's k_ransac_hypotheses
+    int* units;                                       // bail-out: job B's ticket words, [far, near][2 phases][8 XCDs][slots(cnt) / RS_BLOCK] of the batch in it - unit_words(cnt) words, which its k_ransac_hypotheses zeroes (room for unit_words(cap))
     int *plan, *rec, *n_live, *n_und, *n_near;        // this buffer's fields of the RansacBlock and of RansacLive
     void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
     hipEvent_t ev;                                    // the batch's end where an event marks it (traced calls; study build: TDV_RANSAC_RECORD=copy, TDV_RANSAC_END=event)
@@ -1595,7 +1622,7 @@ struct RansacRun {
     tdv_ctx* ctx; hipStream_t s; RansacKnobs k;
     int ns, nt, max_iterations; float confidence; int* trace;
     float tau, sqrt_tau, band_u;
-    int ns_pad, n_pchunks, batch, first_batch, h_pad, packed, rblocks, n_lpairs = 0, n_cpairs = 0, cus = 0;
+    int ns_pad, n_pchunks, batch, cap, h_pad, packed, rblocks, n_lpairs = 0, n_cpairs = 0, cus = 0;
     size_t tri_bytes;                                 // per triple: one packed word or an int4
     float *pq = nullptr, *pq2 = nullptr, *pq3 = nullptr, *leaves = nullptr, *cleaves = nullptr; double* slabs = nullptr;
     RansacBlock *d = nullptr, *h = nullptr; RansacLive* lv = nullptr;
@@ -1627,14 +1654,20 @@ struct RansacRun {
         }
         TDV_CHECK_LAUNCH(ctx);
         // batch size: enough hypotheses to fill the chip, bounded for early exit granularity
-        batch = std::min(std::max(max_iterations, 1), 65536);  // per-batch host sync is ~0.3 ms: amortise it
-        first_batch = k.bailout ? 8 * RS_HYP_PER_BLOCK : batch;    // with the bail-out a shorter first batch establishes a best count for the rest
-        h_pad = (int)align_up((size_t)batch, RS_HYP_PER_BLOCK); n_pchunks = ns_pad / RS_PCH;
+        batch = std::min(std::max(max_iterations, 1), kRansacBatch);  // per-batch host sync is ~0.3 ms: amortise it
+        // With the bail-out the sizes are the schedule's (ransac_cut.hpp: ransac_batch_size, the one statement of it): a shorter first
+        // batch establishes a best count for the rest, batches of kRansacBatch follow, and from iteration kRansacGrowAt on they grow.
+        // Here: how many batches the call has, and the largest of them (cap) - what the per-batch buffers hold.  A call that never
+        // reaches a grown batch allocates what it did before there was one; h_pad is the layout's stride, a batch's kernels cover
+        // its own slots().
+        int n_batches = 0; cap = batch;
+        for (int it = 0; it < max_iterations; ++n_batches) { const int c = std::min(batch_size(it), max_iterations - it); cap = std::max(cap, c); it += c; }
+        h_pad = (int)align_up((size_t)cap, RS_HYP_PER_BLOCK); n_pchunks = ns_pad / RS_PCH;
         packed = (uint64_t)ns <= kTriplePackMaxN;      // triples as one 64-bit word each (tdv_internal.hpp: triple_pack)
         tri_bytes = packed ? 8 : 16;
-        for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &B.hyp)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.counts)); TDV_TRY(ws_alloc_bytes(ctx, (size_t)batch * tri_bytes, &B.tri)); }
+        for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)14 * h_pad, &B.hyp)); TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.counts)); TDV_TRY(ws_alloc_bytes(ctx, (size_t)cap * tri_bytes, &B.tri)); }
         if (k.bailout) {
-            for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list)); TDV_TRY(ws_alloc(ctx, (size_t)unit_words(), &B.units)); }
+            for (RansacBuf& B : buf) { TDV_TRY(ws_alloc(ctx, (size_t)h_pad, &B.list)); TDV_TRY(ws_alloc(ctx, (size_t)unit_words(cap), &B.units)); }
             TDV_HIP(ctx, hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, ctx->device));
         }
         if (k.order) { TDV_TRY(ws_alloc(ctx, (size_t)2 * order_blocks() * (RO_BLOCK / 64), &ord_mask)); TDV_TRY(ws_alloc(ctx, (size_t)2 * order_blocks(), &ord_cnt)); }
@@ -1650,15 +1683,18 @@ struct RansacRun {
         rblocks = (ns + 255) / 256; TDV_TRY(ws_alloc(ctx, (size_t)2 * rblocks, &slabs));
         // the score timer's stamps: two dispatches per batch and one to spare, {all ones, 0} each
         if (ctx->timing && k.score_fast && !k.score_mfma && !k.timer_events) {
-            const int n_batches = max_iterations <= first_batch ? 1 : 1 + (int)(((size_t)(max_iterations - first_batch) + batch - 1) / batch);
             n_stamps = 2 * n_batches + 1;
             TDV_TRY(ws_alloc(ctx, (size_t)2 * n_stamps, &stamps));
             TDV_HIP(ctx, hipMemsetAsync(stamps, 0xff, (size_t)n_stamps * 8, s));              // [n_stamps] t0, then [n_stamps] t1
             TDV_HIP(ctx, hipMemsetAsync(stamps + n_stamps, 0, (size_t)n_stamps * 8, s));
         }
         // pinned: the block | 2 x triples | 2 x counts (traced calls only) | the stamps (timing on)
-        const size_t sz_blk = align_up(sizeof(RansacBlock), 64), sz_tri = align_up((size_t)batch * tri_bytes, 64), sz_cnt = trace ? align_up((size_t)batch * 4, 64) : 0;
-        TDV_TRY(pin_reserve(ctx, sz_blk + 2 * sz_tri + 2 * sz_cnt + (size_t)n_stamps * 16));
+        const size_t sz_blk = align_up(sizeof(RansacBlock), 64), sz_tri = align_up((size_t)cap * tri_bytes, 64), sz_cnt = trace ? align_up((size_t)cap * 4, 64) : 0;
+        // A call with bail-out reserves what the grown schedule needs (int4 triples), whatever its own length: pin_reserve grows by a
+        // free and an allocation behind a stream synchronise, and the block then moves once per context - in its first such call - and
+        // not at the start of a long call that follows shorter ones.
+        const size_t sz_grown = k.bailout ? 2 * align_up((size_t)k.grown * 16, 64) : 0;
+        TDV_TRY(pin_reserve(ctx, sz_blk + std::max(2 * sz_tri, sz_grown) + 2 * sz_cnt + (size_t)n_stamps * 16));
         h = reinterpret_cast<RansacBlock*>(ctx->pin); h->bad = 0;
         h->rec[0][4] = h->rec[1][4] = 0;              // the sequence words: nothing of an earlier call (the stream is idle: ransac_run_dev)
         h_stamps = reinterpret_cast<unsigned long long*>(ctx->pin + sz_blk + 2 * sz_tri + 2 * sz_cnt);
@@ -1684,7 +1720,12 @@ struct RansacRun {
         if (st.t0) k_ransac_score_fast<true><<<grid, RS_BLOCK, 0, s>>>(a, b, g1, h_pad, pq2, n_pchunks, tau, &d->rescored, st);
         else k_ransac_score_fast<false><<<grid, RS_BLOCK, 0, s>>>(a, b, g1, h_pad, pq2, n_pchunks, tau, &d->rescored, st);
     }
-    int unit_words() const { return 4 * 8 * (h_pad / RS_BLOCK); }     // per buffer: phase 1's and phase 2's, then the near lists' two
+    // The schedule: the size of the batch that starts at iteration it0 (its count is at most what is left of max_iterations) ...
+    int batch_size(int it0) const { return k.bailout ? ransac_batch_size(it0, k.grown) : batch; }
+    // ... and the hypothesis slots that a batch of cnt covers - its hypothesis kernel's grid, its blocks of ticket words: those of a
+    // batch of `batch` as ever, a grown batch's own.  h_pad, the largest batch's, is only the stride of the layout.
+    int slots(int cnt) const { return (int)align_up((size_t)std::max(cnt, batch), RS_HYP_PER_BLOCK); }
+    int unit_words(int cnt) const { return 4 * 8 * (slots(cnt) / RS_BLOCK); }     // per buffer: phase 1's and phase 2's, then the near lists' two
     int order_blocks() const { return (ns + RO_BLOCK - 1) / RO_BLOCK; }
     void release_events() { for (RansacBuf& B : buf) { event_release(ctx, B.ev); B.ev = nullptr; } }
     // RansacLeafBound's summary of the pairs: fine and coarse leaves along the class-major Morton order.  Its buffers ...
@@ -1717,7 +1758,7 @@ struct RansacRun {
     // stamps, the others between two events.
     // host: the next cnt triples of the index stream into buffer q (i0, i1, i2, valid: registration.cpp:240)
     int draw(TripleStream& idx, int q, int it0) {
-        const int cnt = std::min(it0 == 0 ? first_batch : batch, max_iterations - it0);
+        const int cnt = std::min(batch_size(it0), max_iterations - it0);
         if (packed) idx.next_batch_packed(cnt, static_cast<uint64_t*>(buf[q].h_tri));
         else idx.next_batch(cnt, static_cast<int*>(buf[q].h_tri));
         return cnt;
@@ -1738,10 +1779,10 @@ struct RansacRun {
     int hypotheses(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
         if (k.upload_inline) TDV_HIP(ctx, hipMemcpyAsync(B.tri, B.h_tri, (size_t)b.cnt * tri_bytes, hipMemcpyHostToDevice, s));
-        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words() : 0,
+        const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words(b.cnt) : 0,
                            k.far && b.bounded ? &d->far : nullptr, k.a_permille};
         const PreJob pre{b.bounded ? B.flags : nullptr, B.ubf, k.far ? &d->far : nullptr, enc, d->best12, k.live_radius, k.u_cut_permille};
-        k_ransac_hypotheses<<<(h_pad + 255) / 256, 256, 0, s>>>(pq, tri(B), k.upload_inline ? nullptr : B.h_tri, b.cnt, h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
+        k_ransac_hypotheses<<<(slots(b.cnt) + 255) / 256, 256, 0, s>>>(pq, tri(B), k.upload_inline ? nullptr : B.h_tri, b.cnt, slots(b.cnt), h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
         return TDV_OK;
     }
     // every test of the batch, no plan: the exact kernel, the fast one, or (study build) the matrix cores
@@ -1789,7 +1830,7 @@ struct RansacRun {
     // the chunks its plan sets
     void phase1(const RansacBatch& b) {
         const RansacBuf& B = buf[b.q];
-        const int hbw = h_pad / RS_BLOCK;
+        const int hbw = slots(b.cnt) / RS_BLOCK;
         const ScoreJob ja = job_a(b), jl{B.hyp, B.counts, B.plan, B.live, hbw, 0, B.n_live, B.units, nullptr};
         const ScoreJob jn = k.far ? ScoreJob{B.hyp, B.counts, B.plan, B.near, hbw, 0, B.n_near, B.units + 16 * hbw, &d->far.c_far} : jl;   // the near list rides behind the far one
         const int g1 = score_grid(ja.hb, ja.ps);          // (a multiple of 8: job B's XCD numbering starts there)
@@ -1813,7 +1854,7 @@ struct RansacRun {
     // phase 2 of batch b: the hypotheses on its list over the chunks its phase 1 left out - alone, or (merged dispatch) riding as
     // job B behind the phase 1 `a` of the next batch, g1 workgroups
     int phase2(const RansacBatch& b, const ScoreJob* a = nullptr, int g1 = 0) {
-        const RansacBuf& B = buf[b.q]; const int hbw = h_pad / RS_BLOCK;
+        const RansacBuf& B = buf[b.q]; const int hbw = slots(b.cnt) / RS_BLOCK;
         const ScoreJob jb{B.hyp, B.counts, B.plan, B.list, hbw, 0, nullptr, B.units + 8 * hbw, nullptr};
         const ScoreJob jn = k.far && b.bounded ? ScoreJob{B.hyp, B.counts, B.plan, B.list2, hbw, 0, nullptr, B.units + 24 * hbw, &d->far.c_far} : jb;   // the near list's survivors behind the far one's
         const int g2 = unit_grid(cus);
@@ -1833,9 +1874,10 @@ struct RansacRun {
         if (!trace) {
             const bool live_only = b.bounded && confidence >= 0.f;      // (see k_ransac_finish)
             int* rec = k.record_copy ? B.rec : const_cast<int*>(B.h_rec);
-            k_ransac_finish<<<1, 1024, 0, s>>>(tri(B), b.cnt, B.counts, live_only ? B.live : nullptr, live_only ? B.n_live : nullptr,
-                                               k.far ? B.near : nullptr, B.n_near, B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec,
-                                               b.bounded ? B.n_live : nullptr, d->bound, B.seq);
+            const auto kernel = live_only ? k_ransac_finish<true> : k_ransac_finish<false>;
+            kernel<<<1, 1024, 0, s>>>(tri(B), b.cnt, B.counts, live_only ? B.live : nullptr, live_only ? B.n_live : nullptr,
+                                      k.far ? B.near : nullptr, B.n_near, B.hyp, h_pad, ns, confidence, b.it0, with_state ? d->state : nullptr, d->sel, d->best12, &d->bad, rec,
+                                      b.bounded ? B.n_live : nullptr, d->bound, B.seq);
             TDV_CHECK_LAUNCH(ctx);
             if (k.record_copy) TDV_HIP(ctx, hipMemcpyAsync(const_cast<int*>(B.h_rec), B.rec, sizeof(d->rec[0]), hipMemcpyDeviceToHost, s));
         } else TDV_HIP(ctx, hipMemcpyAsync(B.h_cnt, B.counts, (size_t)b.cnt * 4, hipMemcpyDeviceToHost, s));

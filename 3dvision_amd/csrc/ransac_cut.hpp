@@ -31,4 +31,15 @@ __host__ __device__ __forceinline__ bool score_unit(int ticket, int r0, int r1, 
 // so the workgroups spread evenly over the blocks, and goes round once - any single workgroup reaches every block.
 __host__ __device__ __forceinline__ int score_unit_block(int wg, int visit, int n_blk) { return (int)(((unsigned)wg + (unsigned)visit) % (unsigned)n_blk); }
 
+// The batch schedule of a call with bail-out (ransac.hip: RansacRun), stated once: the size of the batch that starts at iteration it0
+// (the call's last batch is what is left of max_iterations).  A short first batch sets a best count for the bound; batches of
+// kRansacBatch keep the early exit's granularity while the call is young; from kRansacGrowAt on a batch holds `grown` hypotheses,
+// because a batch's one-workgroup kernels, its hypothesis kernel and the fine level's partly filled round cost per batch, not per
+// hypothesis (profiles/r27/ransac_batch_growth.md).  grown == kRansacBatch: no growth.
+constexpr int kRansacFirst = 8192, kRansacBatch = 65536, kRansacGrown = 131072;
+constexpr int kRansacGrowAt = kRansacFirst + 4 * kRansacBatch;     // 270,336: beyond every shape the per-batch tests are written around
+__host__ __device__ __forceinline__ int ransac_batch_size(int it0, int grown = kRansacGrown) {
+    return it0 == 0 ? kRansacFirst : it0 < kRansacGrowAt ? kRansacBatch : grown;
+}
+
 }  // namespace tdv

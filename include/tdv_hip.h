@@ -1614,6 +1614,10 @@ int tdv_filter_duplicates(const float* poses, int n, float min_distance, float* 
 int tdv_ransac_score_unit(int ticket, int r0, int r1, int xcd, int* c0, int* c1);
 int tdv_ransac_score_unit_block(int wg, int visit, int n_blk);
 int tdv_ransac_score_unit_chunks(void);
+/* Test aid (host only): the batch schedule of a RANSAC call that runs with the bail-out (more than 16,384 iterations, not traced, the
+ * fast scoring kernel).  The size of the batch that starts at iteration it0: 8,192 at 0, 65,536 while it0 < 270,336, the grown size
+ * from there on; the call's last batch is what is left of max_iterations.  TDV_ERR_BAD_ARG for it0 < 0. */
+int tdv_ransac_batch_size(int it0);
 /* Registration::loadReferenceModel (src/registration.cpp:416-461): ASCII PLY, x y z [r g b] per vertex.
  * Keeps the reference's behaviour: colours are detected by "red" appearing in any header line and are
  * divided by 255 when r > 1; the header loop consumes the line AFTER end_header, so the first vertex is

@@ -2,7 +2,9 @@
 """Study: where a bounded RANSAC batch's GPU time goes.  Reads the kernel trace (and, if given, the memory-copy trace) that
 `rocprofv3 --kernel-trace --memory-copy-trace --output-format csv` wrote for `bench.py`, keeps the last RANSAC call (from its
 last k_gather_pq on) and prints, per batch (one k_ransac_hypotheses each), the mean device time of every kernel group and the
-mean wall time between two batches' k_ransac_hypotheses.
+mean wall time between two batches' k_ransac_hypotheses.  A call with bail-out grows its batches late (csrc/ransac_cut.hpp), so the
+batches are also grouped by size - read off k_ransac_hypotheses' grid - with a row per kernel (the two scoring dispatches apart) and
+the wall per 65,536 hypotheses.
 With a copy trace it also prints the batch's path: every kernel of a batch in start order with the idle time in front of it (from
 the end of the kernel before it to its start, kernels only: what the compute stream waits), and per host-to-device copy its
 duration, the time from the end of the last kernel that started before it to its start, and the time from its end to the start of
@@ -22,11 +24,13 @@ rows = []
 for f in argv:
     for r in csv.DictReader(open(f)):
         name = r.get("Kernel_Name") or ("copy " + r.get("Direction", "?"))
-        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name.split("(")[0].split("<")[0].strip()))
+        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), name.split("(")[0].split("<")[0].strip(), int(r.get("Grid_Size_X") or r.get("Grid_Size") or 0)))
 rows.sort()
 gathers = [i for i, r in enumerate(rows) if r[2].endswith("k_gather_pq")]
 rows = rows[gathers[call]:gathers[call + 1] if call + 1 < 0 and call + 1 >= -len(gathers) else None]
 hyps = [r[0] for r in rows if r[2].endswith("k_ransac_hypotheses")]
+slots = [r[3] for r in rows if r[2].endswith("k_ransac_hypotheses")]      # the kernel's threads: the hypothesis slots its batch covers
+rows = [r[:3] for r in rows]
 nb = len(hyps)
 rows = [r for r in rows if r[0] >= hyps[0] or r[2].startswith("copy")]
 groups = collections.OrderedDict()
@@ -44,6 +48,34 @@ for k, (c, t) in sorted(groups.items(), key=lambda kv: -kv[1][1]):
     print("  %-28s %5d calls %9.1f us/batch %9.1f us/call" % (k, c, t / nb / 1e3, t / c / 1e3))
     busy += t
 print("  busy %.1f us/batch" % (busy / nb / 1e3))
+
+# ---- batches of differing size (a call with bail-out grows its batches late: csrc/ransac_cut.hpp).  A batch's size is read off its
+# k_ransac_hypotheses' grid - the slots it covers, which is the hypothesis count of every whole batch (the call's first and last
+# batch, and the second, which builds the leaves, are left out).  Per size: the mean time of every kernel per batch, the wall from
+# one k_ransac_hypotheses to the next, and that wall per 65,536 hypotheses.
+if nb > 4 and any(slots):
+    by_size = collections.OrderedDict()
+    for b in range(2, nb - 1):
+        by_size.setdefault(slots[b], []).append(b)
+    kern = [r for r in rows if not r[2].startswith("copy") and r[0] >= hyps[0]]
+    for size, bs in by_size.items():
+        per = collections.OrderedDict()
+        for b in bs:
+            seen = collections.Counter()
+            for s0, e0, n0 in kern:
+                if hyps[b] <= s0 < hyps[b + 1]:
+                    name = n0.split("::")[-1]
+                    seen[name] += 1                              # k_ransac_score_fast runs twice per batch: phase 1, phase 2
+                    per.setdefault("%s #%d" % (name, seen[name]), []).append(e0 - s0)
+        walls_b = [hyps[b + 1] - hyps[b] for b in bs]
+        wall = sum(walls_b) / len(walls_b) / 1e3
+        # (slots, not hypotheses: a batch cut short by the call's end covers the slots of a batch of 65,536 at least and would be
+        # grouped with those - today that can only be the call's last batch, which is left out)
+        print("batches of %d slots (= hypotheses of a whole batch): %d (batches %s), wall %.1f us (min %.1f, max %.1f), per 65,536 hypotheses %.1f us" %
+              (size, len(bs), "%d..%d" % (bs[0] + 1, bs[-1] + 1), wall, min(walls_b) / 1e3, max(walls_b) / 1e3, wall * 65536.0 / max(size, 1)))
+        for k, v in per.items():
+            print("    %-28s %4.1f launches/batch %9.1f us/batch %9.1f us/launch %9.1f us per 65,536" %
+                  (k, len(v) / len(bs), sum(v) / len(bs) / 1e3, sum(v) / len(v) / 1e3, sum(v) / len(bs) / 1e3 * 65536.0 / max(size, 1)))
 
 
 def mean(v):
