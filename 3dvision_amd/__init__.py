@@ -52,7 +52,7 @@ ABI_SYMBOLS = [
     "tdv_compute_fpfh", "tdv_feature_match", "tdv_ransac", "tdv_icp", "tdv_icp_correspondences",
     "tdv_icp_dev", "tdv_ransac_dev", "tdv_feature_match_dev", "tdv_estimate_normals_dev", "tdv_compute_fpfh_dev", "tdv_normals_fpfh_dev", "tdv_radix_sort_pairs_dev",
     "tdv_depth_to_cloud_dev", "tdv_voxel_downsample_dev", "tdv_sample_triples", "tdv_sample_triples_batch", "tdv_pose_compose",
-    "tdv_register_batch_dev", "tdv_prepare_model_dev", "tdv_bilateral_filter", "tdv_filter_duplicates", "tdv_ransac_score_unit", "tdv_ransac_score_unit_block", "tdv_ransac_score_unit_chunks", "tdv_ransac_batch_size", "tdv_load_ply_ascii", "tdv_load_mask_png", "tdv_load_masks_from_dir",
+    "tdv_register_batch_dev", "tdv_prepare_model_dev", "tdv_bilateral_filter", "tdv_filter_duplicates", "tdv_ransac_score_unit", "tdv_ransac_score_unit_block", "tdv_ransac_score_unit_chunks", "tdv_ransac_batch_size", "tdv_voxel_rules", "tdv_load_ply_ascii", "tdv_load_mask_png", "tdv_load_masks_from_dir",
     "tdv_depth_to_cloud_batch_dev", "tdv_broadcast_model", "tdv_gather_results", "tdv_mask_resize_nearest", "tdv_mask_resize_nearest_dev", "tdv_voxel_downsample_batch_dev", "tdv_voxel_downsample_batch_pinhole_dev",
     "tdv_icp_batch_dev", "tdv_refine_batch_dev", "tdv_ctx_set_icp_loss", "tdv_ctx_get_icp_loss",
     "tdv_gicp", "tdv_gicp_dev", "tdv_gicp_batch_dev",

@@ -46,18 +46,6 @@ int tdv_bilateral_filter(tdv_ctx* ctx, const float* depth, int width, int height
 }
 
 static int voxel_batch_impl(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size, const float* pinhole4,
-                            float* d_out_xyz, int* h_voxel_offsets);
-int tdv_voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size,
-                                   float* d_out_xyz, int* h_voxel_offsets) {
-    return voxel_batch_impl(ctx, d_xyz, h_cloud_offsets, n_clouds, voxel_size, nullptr, d_out_xyz, h_voxel_offsets);
-}
-int tdv_voxel_downsample_batch_pinhole_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size,
-                                           float fx, float fy, float cx, float cy, float* d_out_xyz, int* h_voxel_offsets) {
-    if (!(fx > 0.f) || !(fy > 0.f)) return TDV_ERR_BAD_ARG;
-    const float cam[4] = {fx, fy, cx, cy};
-    return voxel_batch_impl(ctx, d_xyz, h_cloud_offsets, n_clouds, voxel_size, cam, d_out_xyz, h_voxel_offsets);
-}
-static int voxel_batch_impl(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size, const float* pinhole4,
                             float* d_out_xyz, int* h_voxel_offsets) {
     if (!h_cloud_offsets || !h_voxel_offsets || n_clouds < 0) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
@@ -68,22 +56,17 @@ static int voxel_batch_impl(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud
     if (h_cloud_offsets[0] != 0 || (total > 0 && (!d_xyz || !d_out_xyz))) return TDV_ERR_BAD_ARG;
     int* d_off;
     TDV_TRY(upload(ctx, h_cloud_offsets, (size_t)n_clouds + 1, &d_off));
-    int overflowed = 0;
-    TDV_TRY(voxel_downsample_batch_dev(ctx, d_xyz, total, d_off, n_clouds, voxel_size, d_out_xyz, nullptr, nullptr, h_voxel_offsets, &overflowed, nullptr,
-                                       pinhole4, pinhole4 ? h_cloud_offsets : nullptr));
-    ctx->last_voxel_batch_redone = overflowed;
-    if (!overflowed) return TDV_OK;
-    // a voxel with more points than the table's member rows hold (a coarse grid): cloud by cloud on the path without that limit
-    int at = 0;
-    for (int b = 0; b < n_clouds; ++b) {
-        const int n = h_cloud_offsets[b + 1] - h_cloud_offsets[b];
-        int v = 0;
-        h_voxel_offsets[b] = at;
-        if (n > 0) TDV_TRY(voxel_downsample_dev(ctx, d_xyz + (size_t)h_cloud_offsets[b] * 3, nullptr, n, voxel_size, TDV_VOXEL_ORDER_FIRST, d_out_xyz + (size_t)at * 3, nullptr, n, &v));
-        at += v;
-    }
-    h_voxel_offsets[n_clouds] = at;
-    return finish(ctx);
+    return voxel_downsample_batch_dev(ctx, d_xyz, h_cloud_offsets, d_off, n_clouds, voxel_size, pinhole4, VoxelFirst{d_out_xyz}, h_voxel_offsets);   // (returns with the stream idle)
+}
+int tdv_voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size,
+                                   float* d_out_xyz, int* h_voxel_offsets) {
+    return voxel_batch_impl(ctx, d_xyz, h_cloud_offsets, n_clouds, voxel_size, nullptr, d_out_xyz, h_voxel_offsets);
+}
+int tdv_voxel_downsample_batch_pinhole_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_cloud_offsets, int n_clouds, float voxel_size,
+                                           float fx, float fy, float cx, float cy, float* d_out_xyz, int* h_voxel_offsets) {
+    if (!(fx > 0.f) || !(fy > 0.f)) return TDV_ERR_BAD_ARG;
+    const float cam[4] = {fx, fy, cx, cy};
+    return voxel_batch_impl(ctx, d_xyz, h_cloud_offsets, n_clouds, voxel_size, cam, d_out_xyz, h_voxel_offsets);
 }
 
 int tdv_mask_resize_nearest(tdv_ctx* ctx, const uint8_t* masks, int n_masks, int src_width, int src_height, int dst_width, int dst_height, uint8_t* out) {

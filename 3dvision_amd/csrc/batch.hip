@@ -118,17 +118,40 @@ struct BatchVoxels {
     std::vector<int> ref_failed;      // 1: instance b's reference order is (still) to be made by the host replay
 };
 
+// Instance b's voxels in the requested order out of a batched pass (vx.batched), on context c: first-occurrence order as it lies; the
+// reference order from the batch's device pass, or - an instance that pass could not order, or no such pass - replayed on the host
+// into `slot` (null: c's workspace).  both (optional, reference order only): the first-occurrence rows and the permutation.
+int batch_instance_voxels(tdv_ctx* c, const BatchVoxels& vx, const std::vector<int>& off, int b, bool want_ref, float* slot, VoxelBothOrders* both, float** out) {
+    const int v0 = vx.voff[b], v = vx.voff[b + 1] - v0;
+    float* first = vx.first + (size_t)v0 * 3;
+    *out = first;
+    if (!want_ref) return TDV_OK;
+    if (vx.ref && !vx.ref_failed[b]) {                   // ordered on the device with the rest of the batch
+        *out = vx.ref + (size_t)v0 * 3;
+        if (both) *both = VoxelBothOrders{first, vx.r2f + v0, vx.f2r + v0};
+        return TDV_OK;
+    }
+    if (!slot) TDV_TRY(ws_alloc(c, (size_t)v * 3, &slot));
+    if (both) {
+        both->first_xyz = first;
+        TDV_TRY(ws_alloc(c, (size_t)v, &both->ref2first));
+        TDV_TRY(ws_alloc(c, (size_t)v, &both->first2ref));
+    }
+    *out = slot;
+    return voxel_reference_order(c, v, off[b + 1] - off[b], vx.leaders + v0, first, nullptr, vx.rank + off[b], v0, slot, nullptr, both);
+}
+
 int batch_voxels(tdv_ctx* ctx, int n_instances, const tdv_batch_params* prm, const BatchClouds& cl, BatchVoxels& vx) {
     // voxels of ALL instances in first-occurrence order with one memset + two launches (voxel.hip, hash-table path); a lane then
     // only finishes its instance's reference order.  A voxel too full for the table's member rows (a very coarse grid) sends the
     // whole batch back to per-instance calls.
-    const bool batched_voxel_env = !(getenv("TDV_BATCH_VOXEL") && atoi(getenv("TDV_BATCH_VOXEL")) == 0);          // A/B knob (read per call: the tests switch it)
+    const VoxelKnobs knobs = voxel_knobs();
     const bool want_ref = prm->voxel_order == TDV_VOXEL_ORDER_REFERENCE;
     const std::vector<int>& off = cl.off;
     vx.voff.assign((size_t)n_instances + 1, 0);
     vx.ref_failed.assign((size_t)n_instances, 1);
     const int total_pts = off[n_instances];
-    if (batched_voxel_env && total_pts > 0 && !study_env("TDV_VOXEL_LEGACY") && !study_env("TDV_VOXEL_SORT")) {
+    if (knobs.batch && total_pts > 0 && !knobs.counting_sort && !knobs.full_sort) {
         TDV_TRY(ws_alloc(ctx, (size_t)total_pts * 3, &vx.first));
         if (want_ref) { TDV_TRY(ws_alloc(ctx, (size_t)total_pts, &vx.rank)); TDV_TRY(ws_alloc(ctx, (size_t)total_pts, &vx.leaders)); }
         int* d_off_inst;
@@ -138,14 +161,12 @@ int batch_voxels(tdv_ctx* ctx, int n_instances, const tdv_batch_params* prm, con
         const WsMark vmark = ws_mark(ctx);                   // the table and member rows are scratch: given back after the call
         int overflowed = 0;
         const float pinhole[4] = {prm->fx, prm->fy, prm->cx, prm->cy};     // the clouds come from this call's own unprojection: row-major pixel order, these intrinsics
-        TDV_TRY(voxel_downsample_batch_dev(ctx, cl.xyz, total_pts, d_off_inst, n_instances, prm->voxel_size, vx.first, vx.rank, vx.leaders,
-                                           vx.voff.data(), &overflowed, vx.d_voff, pinhole, off.data()));
+        TDV_TRY(voxel_downsample_batch_dev(ctx, cl.xyz, off.data(), d_off_inst, n_instances, prm->voxel_size, pinhole,
+                                           VoxelFirst{vx.first, nullptr, nullptr, total_pts, vx.rank, vx.leaders, vx.d_voff}, vx.voff.data(), nullptr, &overflowed));
         ws_rewind(ctx, vmark);
-        vx.batched = !overflowed;
-        ctx->last_voxel_batch_redone = overflowed;
+        vx.batched = !overflowed;            // (overflowed: every instance's own voxel_downsample_dev, on its lane's context)
         // ... and their reference order, on the device too (the host replay stays as the fall-back of a cloud whose hash degenerates)
-        const bool device_order_env = !(getenv("TDV_VOXEL_DEVICE_ORDER") && atoi(getenv("TDV_VOXEL_DEVICE_ORDER")) == 0);   // A/B knob (read per call: the tests switch it)
-        if (vx.batched && want_ref && device_order_env && vx.voff[n_instances] > 0) {
+        if (vx.batched && want_ref && knobs.device_order != 0 && vx.voff[n_instances] > 0) {
             const size_t tv = (size_t)vx.voff[n_instances];
             TDV_TRY(ws_alloc(ctx, tv * 3, &vx.ref));
             TDV_TRY(ws_alloc(ctx, tv, &vx.r2f));
@@ -196,7 +217,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
     BatchVoxels bv;
     TDV_TRY(batch_voxels(ctx, n_instances, prm, cl, bv));
     const std::vector<int>& voff = bv.voff;
-    float* vox_first_all = bv.first; int* vox_rank_all = bv.rank; int4* vox_leaders_all = bv.leaders;
+    float* vox_first_all = bv.first;
     float* vox_ref_all = bv.ref; int *vox_r2f_all = bv.r2f, *vox_f2r_all = bv.f2r;
     const std::vector<int>& ref_failed = bv.ref_failed;
     int* d_voff = bv.d_voff;
@@ -221,21 +242,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         VoxelBothOrders both{nullptr, nullptr, nullptr};
         if (batched_voxel) {
             v = voff[b + 1] - voff[b];
-            float* first = vox_first_all + (size_t)voff[b] * 3;
-            if (!want_ref) vx = first;
-            else if (vox_ref_all && !ref_failed[b]) {           // ordered on the device with the rest of the batch
-                vx = vox_ref_all + (size_t)voff[b] * 3;
-                if (coherent) both = VoxelBothOrders{first, vox_r2f_all + voff[b], vox_f2r_all + voff[b]};
-            } else {
-                TDV_TRY(ws_alloc(c, (size_t)v * 3, &vx));
-                if (coherent) {
-                    both.first_xyz = first;
-                    TDV_TRY(ws_alloc(c, (size_t)v, &both.ref2first));
-                    TDV_TRY(ws_alloc(c, (size_t)v, &both.first2ref));
-                }
-                TDV_TRY(voxel_reference_order(c, v, n, vox_leaders_all + voff[b], first, nullptr, vox_rank_all + off[b], voff[b], vx, nullptr,
-                                              coherent ? &both : nullptr));
-            }
+            TDV_TRY(batch_instance_voxels(c, bv, off, b, want_ref, nullptr, coherent ? &both : nullptr, &vx));
         } else {
             TDV_TRY(ws_alloc(c, (size_t)n * 3, &vx));
             if (coherent) {
@@ -496,10 +503,8 @@ int refine_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_masks
         if (want_ref && !ref && tv > 0) TDV_TRY(ws_alloc(ctx, tv * 3, &ref));
         for (int b = 0; b < n_instances; ++b) {
             start[b] = bv.voff[b]; count[b] = bv.voff[b + 1] - bv.voff[b];
-            const int n = off[b + 1] - off[b];
-            if (want_ref && n > 0 && (bv.ref_failed[b] || !bv.ref))
-                TDV_TRY(voxel_reference_order(ctx, count[b], n, bv.leaders + bv.voff[b], bv.first + (size_t)bv.voff[b] * 3, nullptr, bv.rank + off[b], bv.voff[b],
-                                              ref + (size_t)bv.voff[b] * 3, nullptr, nullptr));
+            float* at;
+            if (want_ref && off[b + 1] > off[b]) TDV_TRY(batch_instance_voxels(ctx, bv, off, b, true, ref + (size_t)bv.voff[b] * 3, nullptr, &at));
         }
         clouds = want_ref ? ref : bv.first;
     } else {

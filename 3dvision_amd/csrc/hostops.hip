@@ -2,6 +2,7 @@
 // reference-model loader, the duplicate-pose filter and the mask-directory loader.  Plain C++; no device code.
 #include "tdv_hip.h"
 #include "ransac_cut.hpp"
+#include "voxel_rules.hpp"
 #include <zlib.h>
 #include <algorithm>
 #include <cstdlib>
@@ -105,6 +106,17 @@ int tdv_ransac_score_unit_chunks(void) { return RS_UNIT; }
 int tdv_ransac_batch_size(int it0) {
     if (it0 < 0) return TDV_ERR_BAD_ARG;
     return tdv::ransac_batch_size(it0);
+}
+// The voxel stage's cell and the reference's key hash of it (voxel_rules.hpp: what every voxel kernel compiles), for the CPU suite.
+int tdv_voxel_rules(const float* xyz, int n, float voxel_size, int* out_cells, unsigned long long* out_codes) {
+    if (n < 0 || !(voxel_size > 0.f) || (n > 0 && (!xyz || !out_cells || !out_codes))) return TDV_ERR_BAD_ARG;
+    const float inv = 1.0f / voxel_size;  // registration.cpp:32
+    for (int i = 0; i < n; ++i) {
+        const int3 c = tdv::voxel_cell(xyz, (size_t)i, inv);
+        out_cells[3 * (size_t)i] = c.x; out_cells[3 * (size_t)i + 1] = c.y; out_cells[3 * (size_t)i + 2] = c.z;
+        out_codes[i] = tdv::voxel_key_code(c.x, c.y, c.z);
+    }
+    return TDV_OK;
 }
 
 }  // extern "C"

@@ -74,29 +74,9 @@ int multiscale_run(tdv_ctx* ctx, const float* d_src, const float* d_src_normals,
                 TDV_TRY(ws_alloc(ctx, (size_t)total * 3, &o_xyz));
                 if (gicp) TDV_TRY(ws_alloc(ctx, (size_t)total * 3, &o_nrm));
                 const WsMark m = ws_mark(ctx);
-                int overflowed = single ? 1 : 0;
-                if (!single)
-                    TDV_TRY(voxel_downsample_batch_dev(ctx, d_src, total, d_off, n, lv.voxel_size, o_xyz, nullptr, nullptr, start.data(), &overflowed, nullptr,
-                                                       nullptr, nullptr, VoxelNormals{gicp ? d_src_normals : nullptr, o_nrm}));
-                if (!single) ctx->last_voxel_batch_redone = overflowed;
-                if (overflowed) {
-                    // one instance, or a voxel with more points than the table's member rows hold (a coarse level): cloud by cloud on the
-                    // path without that limit, packed back to back as the batched path leaves them
-                    int at = 0;
-                    for (int b = 0; b < n; ++b) {
-                        const int nb = h_off[b + 1] - h_off[b];
-                        int v = 0;
-                        start[b] = at;
-                        if (nb > 0) {
-                            ws_rewind(ctx, m);
-                            TDV_TRY(voxel_downsample_dev(ctx, d_src + (size_t)h_off[b] * 3, nullptr, nb, lv.voxel_size, TDV_VOXEL_ORDER_FIRST, o_xyz + (size_t)at * 3,
-                                                         nullptr, nb, &v, nullptr,
-                                                         VoxelNormals{gicp ? d_src_normals + (size_t)h_off[b] * 3 : nullptr, gicp ? o_nrm + (size_t)at * 3 : nullptr}));
-                        }
-                        at += v;
-                    }
-                    start[n] = at;
-                }
+                // all instances at once; one instance, or a level too coarse for the table, cloud by cloud (voxel.hip) - packed the same way
+                TDV_TRY(voxel_downsample_batch_dev(ctx, d_src, h_off, d_off, n, lv.voxel_size, nullptr, VoxelFirst{o_xyz, nullptr, o_nrm}, start.data(),
+                                                   gicp ? d_src_normals : nullptr, nullptr, !single));
                 ws_rewind(ctx, m);
                 s_xyz = o_xyz; s_nrm = o_nrm;
             }

@@ -276,17 +276,43 @@ int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, i
                          float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both = nullptr,
                          VoxelNormals nrm = VoxelNormals{});
 
-// batch: every cloud's voxels in first-occurrence order with one memset + two launches (voxel.hip); the reference order per cloud
-// pinhole4 (optional: fx, fy, cx, cy) + h_seg_off (the clouds' offsets on the host): the clouds were unprojected from a depth image with these
-// intrinsics, in row-major pixel order - they are then grouped through pixel windows in LDS instead of the table (voxel.hip: k_vs_group)
-int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, int total, const int* d_seg_off, int n_clouds, float voxel,
-                               float* d_first_xyz, int* d_rank, int4* d_leaders, int* h_voff, int* overflowed, int* d_voff_keep = nullptr,
-                               const float* pinhole4 = nullptr, const int* h_seg_off = nullptr, VoxelNormals nrm = VoxelNormals{} /* not with pinhole4 */);
-// the reference's container order of every cloud of a batch, computed on the device (voxel.hip); h_failed[b] != 0: finish cloud b with voxel_reference_order
+// The voxels of one or several clouds in first-occurrence order, and what the reference order needs of them (voxel.hip: what a rung
+// of the grouping ladder leaves behind).  By value, like SortedCloud and DepthFrames.
+struct VoxelFirst {
+    float* xyz = nullptr; float* rgb = nullptr; float* nrm = nullptr;   // rows; rgb / nrm null for a cloud without that companion
+    int capacity = 0;                                                   // rows that fit (a batch: its points)
+    int* rank = nullptr;       // optional, per input point: the first-occurrence rank of a voxel's first point, counted through all clouds
+    int4* leaders = nullptr;   // optional, per voxel: the cell and the index (within its cloud) of its first point
+    int* d_voff = nullptr;     // optional, n_clouds + 2 device ints: the voxel offsets, then the rung's flag
+};
+// Every knob of the voxel stage, read in one place at the top of a call (voxel.hip: voxel_knobs).  LIVE knobs are real getenv()s, read
+// per call because the tests switch them inside a process; STUDY knobs go through study_env() and are dead code in the product library.
+struct VoxelKnobs {
+    bool pixels;         // live   TDV_VOXEL_PIXELS=0: clouds with intrinsics go to the table at once (parity tests)
+    int device_order;    // live   TDV_VOXEL_DEVICE_ORDER=0 / 1: the reference order by the host replay / the device periods; -1 (unset): by voxel count
+    bool batch;          // live   TDV_BATCH_VOXEL=0: a registration batch groups instance by instance
+    bool counting_sort;  // study  TDV_VOXEL_LEGACY: start the ladder at the counting sort
+    bool full_sort;      // study  TDV_VOXEL_SORT: start it at the full bitonic sort
+    bool real_map;       // study  TDV_VOXEL_REAL_MAP: a real std::unordered_map instead of the emulation
+    int split_from;      // study  TDV_VOXEL_SPLIT_FROM: tiles from which k_vh_finalize runs as count + scan + emit (224)
+};
+VoxelKnobs voxel_knobs();
+// Clouds stored back to back - cloud b = points [h_off[b], h_off[b + 1]) of d_xyz, d_off the same offsets on the device - all at once
+// (voxel.hip: pixel windows when pinhole4 = fx, fy, cx, cy says they were unprojected with these intrinsics in row-major pixel order,
+// else the table): cloud b's voxels at [h_voff[b], h_voff[b + 1]) of out.xyz (room for every point), in first-occurrence order;
+// out.rank / leaders / d_voff for a caller that goes on to the reference order.  d_normals (optional, not with pinhole4): the clouds'
+// normals, their voxels' unit means to out.nrm.  A voxel too full for the table: the clouds are redone one by one with
+// voxel_downsample_dev and packed back to back the same way - here, or (overflowed not null: it is told, and nothing of `out` is
+// valid) by a caller with lanes of its own.  batched = false: one by one at once (one cloud on its own; not recorded as a redone batch).
+int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_off, const int* d_off, int n_clouds, float voxel, const float* pinhole4,
+                               const VoxelFirst& out, int* h_voff, const float* d_normals = nullptr, int* overflowed = nullptr, bool batched = true);
+// voxel_order.hip.  The reference's container order of every cloud of a batch, computed on the device; h_failed[b] != 0: finish cloud b with voxel_reference_order
 int voxel_reference_order_batch_dev(tdv_ctx* ctx, int n_clouds, const int* h_voff, const int* d_voff, const int4* d_leaders, const float* d_first_xyz,
                                     float* d_out_xyz, int* d_ref2first, int* d_first2ref, int* h_failed);
 int voxel_reference_order(tdv_ctx* ctx, int v, int n, const int4* d_leaders, const float* tmp_xyz, const float* tmp_rgb, const int* d_rank, int rank_base,
                           float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both, VoxelNormals nrm = VoxelNormals{});
+int voxel_finish_reference(tdv_ctx* ctx, int n, int v, const VoxelFirst& first, float* d_out_xyz, float* d_out_rgb, float* d_out_nrm,
+                           const VoxelBothOrders* both, const VoxelKnobs& knobs);
 
 int sort_records_dev(tdv_ctx* ctx, uint4* rec, size_t n_pow2);  // sort.hip: ascending bitonic sort, n_pow2 >= 2048
 // sort.hip: stable LSD radix sort (hand-written) of (key, value) pairs on the low end_bit bits of the 64-bit key; any n; scratch from the workspace

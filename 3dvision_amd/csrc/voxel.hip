@@ -1,63 +1,43 @@
-// Voxel-grid downsample on gfx950 (HBM-bound: 24 B in + 24 B out per point, plus the sort).
+// Voxel-grid downsample on gfx950 (HBM-bound: 24 B in + 24 B out per point, plus the grouping).
 //
-// Replaces Registration::voxelDownsample (/root/reference/src/registration.cpp:29-60; key/hash
-// :15-27), which has no GPU entry point in the reference (src/pipeline.cpp:92 calls the CPU static).
-// Semantics kept: key = (int)floor(p * (1/voxel)) per axis, converted as x86 does (cvt_i32_x86: NaN and out of range -> INT_MIN); per-voxel mean = f32 sum of the member
-// points IN ASCENDING INPUT INDEX divided by float(count); colours likewise; normals dropped.
+// Replaces Registration::voxelDownsample (src/registration.cpp:29-60 of the reference), which has no GPU entry point there
+// (src/pipeline.cpp:92 calls the CPU static).  The rules - cell, mean, unit normal, key hash - are stated in voxel_rules.hpp; what this
+// file adds is GROUPING: the members of a voxel have to be summed in ascending input index, and the voxels come out in FIRST-OCCURRENCE
+// order (the order of their first points).  voxel_order.hip turns that into the reference's container order where it is asked for.
 //
-// The reference groups with std::unordered_map and emits voxels in that container's iteration
-// order.  Here grouping is by hashing + tiny per-bucket sorts (below), with a full sort as the fallback:
-//   1. k_voxel_records   : record (kx, ky, kz, idx) per point
-//   2. bitonic sort      : (sort.hip) ascending by (kx, ky, kz, idx) as unsigned words — members of a voxel
-//                          become one run, in ascending input index (LDS-tiled local passes,
-//                          global passes only for strides >= the 2048-record tile)
-//   3. k_voxel_heads     : run heads; a run's first record carries the voxel's smallest index
-//   4. exclusive scan    : (sort.hip) rank of every leader index = voxel position in FIRST-OCCURRENCE order
-//   5. k_voxel_means     : one lane per run, sequential sum in run order -> mean -> out[rank]
-// TDV_VOXEL_ORDER_FIRST stops here.  TDV_VOXEL_ORDER_REFERENCE additionally replays the
-// reference's container on the host (same key, same hash, the node-list manipulation of this libstdc++'s
-// std::unordered_map) to obtain its iteration order, and permutes the means on the device.  Only the first
-// point of every voxel changes a container, so the host receives 16 B per VOXEL (cell + input index) from the
-// device and nothing else: the cloud stays in HBM, which is what lets the batched chain run in the reference's order.
-#include "tdv_internal.hpp"
-#include <cfloat>
-#include <chrono>
-#include <cmath>
-#include <cstdlib>
-#include <mutex>
+// Four ways to group, tried as a ladder (voxel_first_order): a rung that cannot cope says so with one word, and the next one starts over.
+//   rung            default for                         hands over when                              cost
+//   pixel windows   clouds handed over with the         VS_FAILED: a tile off the pixel grid, a      no atomics, no member rows, no limit on a voxel's
+//   (k_vs_group)    intrinsics that unprojected them    window above VS_WIN_MAX (coarse voxels),     members; 73 KB of LDS per workgroup
+//                   (registration batches, the          rows too long for the halo, points not in
+//                   pinhole batch entry)                row-major pixel order
+//   table           every other call: one cloud or      a voxel of more than VH_K = 16 points        memset + 2 launches for any number of clouds;
+//   (k_vh_insert)   many (tdv_voxel_downsample*,        (the overflow word)                          bound by device-scope atomics (20 G/s)
+//                   multi-scale levels, model prep)
+//   counting sort   -  (TDV_VOXEL_LEGACY, study)        too_big: a hash bucket of more than          9 dependent launches, 0.10-0.12 ms for a cloud
+//   (one cloud)                                         VX_MAX_BUCKET = 96 records                   that HBM moves in a microsecond
+//   full sort       -  (TDV_VOXEL_SORT, study)          never                                        bitonic sort of (cell, index) records: 15 launches,
+//   (one cloud)                                                                                      global passes for strides >= the 2,048-record tile
+// The sorts take one cloud: a batch whose table overflows is redone cloud by cloud (voxel_downsample_batch_dev, or the caller's own
+// lanes), each cloud starting again at the table.
+#include "voxel_rules.hpp"
 #include <type_traits>
-#include <unordered_map>
 #include <vector>
-#include <algorithm>
 
 namespace tdv {
 
-// A voxel's normal (include/tdv_hip.h, tdv_voxel_downsample_normals): the mean of its members' normals - the colours' expression, f32
-// sums in ascending input index divided by (float)count - brought to unit length in f32 without contraction, the squared length in the
-// reference's three-term order (sorted_cloud.hpp: d2_sum<D2::REF>).  A mean of length 0 (normals that cancel) or of a length that is
-// not finite (a NaN or infinite member, an overflowing square) stays as it is.
-__device__ __forceinline__ void voxel_unit_normal(float& mx, float& my, float& mz) {
-    const float l2 = mx * mx + (my * my + mz * mz);
-    const float l = sqrtf(l2);
-    if (l2 > 0.f && l <= FLT_MAX) { mx = mx / l; my = my / l; mz = mz / l; }
+// the sort record of point i: its cell as unsigned words, then its index
+__device__ __forceinline__ uint4 voxel_record(const float* __restrict__ xyz, int i, float inv) {
+    const int4 c = voxel_cell(xyz, (size_t)i, inv, i);
+    return make_uint4((unsigned)c.x, (unsigned)c.y, (unsigned)c.z, (unsigned)c.w);
 }
-
 __global__ void k_voxel_records(const float* __restrict__ xyz, int n, int n_pow2, float inv, uint4* __restrict__ rec) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pow2) return;
-    uint4 r;
-    if (i < n) {
-        r.x = (unsigned)cvt_i32_x86(floorf(xyz[3 * i] * inv));
-        r.y = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 1] * inv));
-        r.z = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 2] * inv));
-        r.w = (unsigned)i;
-    } else {
-        r = make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);  // padding sorts last
-    }
-    rec[i] = r;
+    rec[i] = i < n ? voxel_record(xyz, i, inv) : make_uint4(0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu);  // padding sorts last
 }
 
-// ---- grouping by hashing (the default; the bitonic sort above is the fallback) -------------------------------------
+// ---- rungs 3 and 4: counting sort by cell hash, with the full bitonic sort (sort.hip) below it ---------------------------------
 // Members of a voxel only have to become one run in ascending input index; the order of the runs is irrelevant
 // (positions come from the leader scan).  So: bucket = hash(cell) into >= 2n buckets (counting sort, integer atomics),
 // then every bucket — a handful of records, possibly of several colliding cells — is insertion-sorted by
@@ -72,11 +52,7 @@ __device__ __forceinline__ unsigned voxel_hash(unsigned x, unsigned y, unsigned 
 __global__ void k_voxel_hist(const float* __restrict__ xyz, int n, float inv, unsigned mask, uint4* __restrict__ rec_in, int* __restrict__ hist) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    uint4 r;
-    r.x = (unsigned)cvt_i32_x86(floorf(xyz[3 * i] * inv));
-    r.y = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 1] * inv));
-    r.z = (unsigned)cvt_i32_x86(floorf(xyz[3 * i + 2] * inv));
-    r.w = (unsigned)i;
+    const uint4 r = voxel_record(xyz, i, inv);
     rec_in[i] = r;
     atomicAdd(&hist[voxel_hash(r.x, r.y, r.z) & mask], 1);
 }
@@ -106,27 +82,15 @@ __device__ __forceinline__ void voxel_emit_bucket(uint4* a, int m, const float* 
     }
     for (int e = 0; e < m;) {
         const uint4 r = a[e];
-        float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+        VoxelSum<NRM> sum;
         int cnt = 0;
-        for (; e < m; ++e) {
+        for (; e < m; ++e, ++cnt) {               // the run: ascending input index
             const uint4 q = a[e];
-            if (!(q.x == r.x && q.y == r.y && q.z == r.z)) break;
-            const size_t idx = q.w;
-            ax += xyz[3 * idx]; ay += xyz[3 * idx + 1]; az += xyz[3 * idx + 2];        // registration.cpp:47-50, ascending input index
-            if (rgb) { cr += rgb[3 * idx]; cg += rgb[3 * idx + 1]; cb += rgb[3 * idx + 2]; }
-            if (NRM) { nx += nrm.in[3 * idx]; ny += nrm.in[3 * idx + 1]; nz += nrm.in[3 * idx + 2]; }
-            ++cnt;
+            if (!same_cell(q, r)) break;
+            sum.add(xyz, rgb, nrm.in, (size_t)q.w);
         }
-        const float fn = (float)cnt;
-        const size_t l = r.w;
-        leader[l] = 1;
-        mean_xyz[3 * l] = ax / fn; mean_xyz[3 * l + 1] = ay / fn; mean_xyz[3 * l + 2] = az / fn;   // :52-53
-        if (rgb && mean_rgb) { mean_rgb[3 * l] = cr / fn; mean_rgb[3 * l + 1] = cg / fn; mean_rgb[3 * l + 2] = cb / fn; }
-        if (NRM) {
-            float mx = nx / fn, my = ny / fn, mz = nz / fn;
-            voxel_unit_normal(mx, my, mz);
-            nrm.out[3 * l] = mx; nrm.out[3 * l + 1] = my; nrm.out[3 * l + 2] = mz;
-        }
+        leader[r.w] = 1;
+        sum.emit(cnt, mean_xyz, mean_rgb, nrm.out, rgb != nullptr, (size_t)r.w);
     }
 }
 constexpr int VX_LDS_REC = 1024;   // records of a workgroup's 256 buckets staged in LDS (16 KB); a denser stretch sorts in global memory
@@ -160,9 +124,9 @@ __global__ void k_voxel_compact(const int* __restrict__ leader, const int* __res
     if (i >= n || !leader[i]) return;
     const int slot = rank[i];
     if (slot >= capacity) return;
-    out_xyz[3 * (size_t)slot] = mean_xyz[3 * (size_t)i]; out_xyz[3 * (size_t)slot + 1] = mean_xyz[3 * (size_t)i + 1]; out_xyz[3 * (size_t)slot + 2] = mean_xyz[3 * (size_t)i + 2];
-    if (mean_rgb && out_rgb) { out_rgb[3 * (size_t)slot] = mean_rgb[3 * (size_t)i]; out_rgb[3 * (size_t)slot + 1] = mean_rgb[3 * (size_t)i + 1]; out_rgb[3 * (size_t)slot + 2] = mean_rgb[3 * (size_t)i + 2]; }
-    if (nrm.in && nrm.out) { nrm.out[3 * (size_t)slot] = nrm.in[3 * (size_t)i]; nrm.out[3 * (size_t)slot + 1] = nrm.in[3 * (size_t)i + 1]; nrm.out[3 * (size_t)slot + 2] = nrm.in[3 * (size_t)i + 2]; }
+    copy_row3(out_xyz, (size_t)slot, mean_xyz, (size_t)i);
+    copy_row3_opt(out_rgb, (size_t)slot, mean_rgb, (size_t)i);
+    copy_row3_opt(nrm.out, (size_t)slot, nrm.in, (size_t)i);
 }
 
 // leader[idx] = 1 for the smallest input index of each voxel
@@ -171,7 +135,7 @@ __global__ void k_voxel_heads(const uint4* __restrict__ rec, int n, int* __restr
     if (p >= n) return;
     uint4 r = rec[p];
     bool head = true;
-    if (p > 0) { uint4 q = rec[p - 1]; head = !(q.x == r.x && q.y == r.y && q.z == r.z); }
+    if (p > 0) head = !same_cell(rec[p - 1], r);
     if (head) leader[r.w] = 1;
 }
 
@@ -180,9 +144,7 @@ __global__ void k_voxel_heads(const uint4* __restrict__ rec, int n, int* __restr
 __global__ void k_voxel_leader_list(const int* __restrict__ leader, const int* __restrict__ rank, const float* __restrict__ xyz, float inv,
                                     int n, int4* __restrict__ leaders) {
     int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n && leader[i])
-        leaders[rank[i]] = make_int4(cvt_i32_x86(floorf(xyz[3 * (size_t)i] * inv)), cvt_i32_x86(floorf(xyz[3 * (size_t)i + 1] * inv)),
-                                     cvt_i32_x86(floorf(xyz[3 * (size_t)i + 2] * inv)), i);
+    if (i < n && leader[i]) leaders[rank[i]] = voxel_cell(xyz, (size_t)i, inv, i);
 }
 
 // one lane per run head: sequential sum over the run (ascending input index), mean -> out[rank]
@@ -193,44 +155,21 @@ void k_voxel_means(const uint4* __restrict__ rec, int n, const float* __restrict
     int p = blockIdx.x * 256 + threadIdx.x;
     if (p >= n) return;
     uint4 r = rec[p];
-    if (p > 0) { uint4 q = rec[p - 1]; if (q.x == r.x && q.y == r.y && q.z == r.z) return; }
+    if (p > 0 && same_cell(rec[p - 1], r)) return;
     const int slot = rank[r.w];
     if (slot >= capacity) return;
-    float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    VoxelSum<NRM> sum;
     int cnt = 0;
-    for (int e = p; e < n; ++e) {
-        uint4 m = rec[e];
-        if (!(m.x == r.x && m.y == r.y && m.z == r.z)) break;
-        const unsigned idx = m.w;
-        ax += xyz[3 * (size_t)idx]; ay += xyz[3 * (size_t)idx + 1]; az += xyz[3 * (size_t)idx + 2];
-        if (rgb) { cr += rgb[3 * (size_t)idx]; cg += rgb[3 * (size_t)idx + 1]; cb += rgb[3 * (size_t)idx + 2]; }
-        if (NRM) { nx += nrm.in[3 * (size_t)idx]; ny += nrm.in[3 * (size_t)idx + 1]; nz += nrm.in[3 * (size_t)idx + 2]; }
-        ++cnt;
+    for (int e = p; e < n; ++e, ++cnt) {
+        const uint4 m = rec[e];
+        if (!same_cell(m, r)) break;
+        sum.add(xyz, rgb, nrm.in, (size_t)m.w);
     }
-    const float fn = (float)cnt;
-    out_xyz[3 * (size_t)slot] = ax / fn; out_xyz[3 * (size_t)slot + 1] = ay / fn; out_xyz[3 * (size_t)slot + 2] = az / fn;
-    if (rgb && out_rgb) { out_rgb[3 * (size_t)slot] = cr / fn; out_rgb[3 * (size_t)slot + 1] = cg / fn; out_rgb[3 * (size_t)slot + 2] = cb / fn; }
-    if (NRM) {
-        float mx = nx / fn, my = ny / fn, mz = nz / fn;
-        voxel_unit_normal(mx, my, mz);
-        nrm.out[3 * (size_t)slot] = mx; nrm.out[3 * (size_t)slot + 1] = my; nrm.out[3 * (size_t)slot + 2] = mz;
-    }
+    sum.emit(cnt, out_xyz, out_rgb, nrm.out, rgb != nullptr, (size_t)slot);
 }
 
-// out[p] = in[rank[order_first[p]]]
-__global__ void k_voxel_permute(const float* __restrict__ in_xyz, const float* __restrict__ in_rgb, const int* __restrict__ rank, int rank_base,
-                                const int* __restrict__ order_first, int v, float* __restrict__ out_xyz, float* __restrict__ out_rgb,
-                                int* __restrict__ ref2first, int* __restrict__ first2ref, VoxelNormals nrm /* in: first-occurrence order; both NULL without normals */) {
-    int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= v) return;
-    int s = rank[order_first[p]] - rank_base;     // (rank_base: the cloud's first voxel when ranks count through several clouds)
-    if (ref2first) { ref2first[p] = s; first2ref[s] = p; }
-    out_xyz[3 * (size_t)p] = in_xyz[3 * (size_t)s]; out_xyz[3 * (size_t)p + 1] = in_xyz[3 * (size_t)s + 1]; out_xyz[3 * (size_t)p + 2] = in_xyz[3 * (size_t)s + 2];
-    if (in_rgb && out_rgb) { out_rgb[3 * (size_t)p] = in_rgb[3 * (size_t)s]; out_rgb[3 * (size_t)p + 1] = in_rgb[3 * (size_t)s + 1]; out_rgb[3 * (size_t)p + 2] = in_rgb[3 * (size_t)s + 2]; }
-    if (nrm.in && nrm.out) { nrm.out[3 * (size_t)p] = nrm.in[3 * (size_t)s]; nrm.out[3 * (size_t)p + 1] = nrm.in[3 * (size_t)s + 1]; nrm.out[3 * (size_t)p + 2] = nrm.in[3 * (size_t)s + 2]; }
-}
 
-// ---- grouping through a hash table: memset + 2 kernels for any number of clouds (round 3; the default) -------------------
+// ---- rung 2: grouping through a hash table, memset + 2 kernels for any number of clouds (round 3) ------------------------------
 // The counting-sort path above is nine dependent launches whose waves wait >= 90 % of their cycles (profiles/r2: 0.10-0.12 ms
 // for a cloud that HBM moves in a microsecond).  This path is three, and takes B clouds stored back to back at once:
 //   memset            one fill (0x7f bytes) of [claim table | per-voxel count | scan descriptors | ticket | overflow flag]
@@ -244,7 +183,7 @@ __global__ void k_voxel_permute(const float* __restrict__ in_xyz, const float* _
 //                     index in it is the voxel's leader (an atomic min per point in k_vh_insert did the same for 5 us more).
 //                     Leader flags, workgroup scan, DECOUPLED LOOK-BACK over the workgroups' aggregates (single pass: no scan
 //                     launches) -> the leader's first-occurrence rank; the leader sums its voxel's points in ascending index
-//                     order (registration.cpp:47-50), divides and writes the mean at its rank.  Voxels of cloud b occupy
+//                     order (VoxelSum), divides and writes the mean at its rank.  Voxels of cloud b occupy
 //                     [voff[b], voff[b + 1]).  Count and overflow flag go straight into pinned host memory (no copy kernel).
 // Algorithmic bytes: 12 N in + 12 V out; the table adds 16 B per point of atomics and 4-68 B per voxel of member lists.
 constexpr int VH_K = 16;                       // member slots per voxel (one 64-B row)
@@ -258,9 +197,6 @@ __device__ __forceinline__ int vh_segment(const int* __restrict__ seg_off, int n
     while (hi - lo > 1) { const int m = (lo + hi) >> 1; if (seg_off[m] <= g) lo = m; else hi = m; }
     return lo;
 }
-__device__ __forceinline__ void vh_cell(const float* __restrict__ xyz, size_t g, float inv, int& cx, int& cy, int& cz) {
-    cx = cvt_i32_x86(floorf(xyz[3 * g] * inv)); cy = cvt_i32_x86(floorf(xyz[3 * g + 1] * inv)); cz = cvt_i32_x86(floorf(xyz[3 * g + 2] * inv));   // registration.cpp:33-36
-}
 
 __global__ __launch_bounds__(256)
 void k_vh_insert(const float* __restrict__ xyz, int total, const int* __restrict__ seg_off, int nseg, float inv, unsigned mask,
@@ -273,7 +209,8 @@ void k_vh_insert(const float* __restrict__ xyz, int total, const int* __restrict
     int cx = 0, cy = 0, cz = 0;
     if (active) {
         if (nseg > 1) { b = vh_segment(seg_off, nseg, g); lo = seg_off[b]; hi = seg_off[b + 1]; }
-        vh_cell(xyz, (size_t)g, inv, cx, cy, cz);
+        const int3 c = voxel_cell(xyz, (size_t)g, inv);
+        cx = c.x; cy = c.y; cz = c.z;
     }
     // Device-scope atomics are resolved beyond the XCDs' L2s and cost microseconds each; neighbouring points (one wave holds 64
     // consecutive ones, in image order neighbouring pixels) mostly share their voxels.  The wave therefore groups its lanes by
@@ -309,9 +246,8 @@ void k_vh_insert(const float* __restrict__ xyz, int total, const int* __restrict
             if (j == VH_EMPTY) { const int prev = atomicCAS(slot, VH_EMPTY, g); j = prev == VH_EMPTY ? g : prev; }   // of five groups that find their slot empty - cost a batch 30 % more: a device-scope atomic is dearer than a load + an atomic that mostly succeeds)
             if (j == g) break;
             if (j >= lo && j < hi) {                        // the same cloud: same cell?
-                int qx, qy, qz;
-                vh_cell(xyz, (size_t)j, inv, qx, qy, qz);
-                if (qx == cx && qy == cy && qz == cz) break;
+                const int3 q = voxel_cell(xyz, (size_t)j, inv);
+                if (q.x == cx && q.y == cy && q.z == cz) break;
             }
         }
         // The claimer is a member by being the claimer: it neither counts itself nor writes itself into the row (round 4).  Four of five
@@ -329,7 +265,7 @@ void k_vh_insert(const float* __restrict__ xyz, int total, const int* __restrict
     else *overflow = 1;                                 // (any value but the fill pattern)
 }
 
-// ---- grouping WITHOUT the table, for clouds that come from a pinhole depth image (round 4; the batch's clouds) ---------------
+// ---- rung 1: grouping WITHOUT the table, for clouds that come from a pinhole depth image (round 4) ------------------------------
 // k_vh_insert is bound by the chip's rate of device-scope atomics (20 G/s: profiles/r4/history/voxel_batch.md).  A cloud
 // unprojected from a depth image needs none: its points are in row-major pixel order, and all members of a voxel lie within a
 // few pixels of each other - two points of one voxel differ by less than the voxel size s in x, y and z, hence by
@@ -399,9 +335,8 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
     __syncthreads();
     // pass 1: pixel and tag of every loaded point (thread t holds points t, t + 1024, ...: the owned ones among them are its own in pass 3)
     unsigned pvu[VS_PER], pk[VS_PER];                                     // v << 16 | u; the cell relative to the first loaded point's, biased to the middle of its bit field
-    int cx0, cy0, cz0;
-    vh_cell(xyz, (size_t)l0, inv, cx0, cy0, cz0);
-    const long long ox = (long long)cx0 - (1 << (VS_KX - 1)), oy = (long long)cy0 - (1 << (VS_KY - 1)), oz = (long long)cz0 - (1 << (VS_KZ - 1));   // (a poisoned first point has cell INT_MIN)
+    const int3 c0 = voxel_cell(xyz, (size_t)l0, inv);
+    const long long ox = (long long)c0.x - (1 << (VS_KX - 1)), oy = (long long)c0.y - (1 << (VS_KY - 1)), oz = (long long)c0.z - (1 << (VS_KZ - 1));   // (a poisoned first point has cell INT_MIN)
     int umin = INT_MAX, umax = INT_MIN;
     float zmin = INFINITY, amax = 0.f, bmax = 0.f; bool bad = false;
 #pragma unroll
@@ -411,9 +346,8 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
         if (i < nl) {
             const size_t g = (size_t)(l0 + i);
             const float x = xyz[3 * g], y = xyz[3 * g + 1], z = xyz[3 * g + 2];
-            int cx, cy, cz;
-            vh_cell(xyz, g, inv, cx, cy, cz);
-            const long long rx = (long long)cx - ox, ry = (long long)cy - oy, rq = (long long)cz - oz;
+            const int3 c = voxel_cell(xyz, g, inv);
+            const long long rx = (long long)c.x - ox, ry = (long long)c.y - oy, rq = (long long)c.z - oz;
             if (rx < 0 || rx >= (1 << VS_KX) || ry < 0 || ry >= (1 << VS_KY) || rq < 0 || rq >= (1 << VS_KZ)) bad = true;     // a tile wider than the packed cell: the table
             pk[q] = (unsigned)rx | ((unsigned)ry << VS_KX) | ((unsigned)rq << (VS_KX + VS_KY));
             key[i] = pk[q];
@@ -511,18 +445,16 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
         const int g = l0 + li;
         voxel_of[g] = l0 + leader;
         if (leader == li) {
-            // the leader sums its voxel: itself, then the others as the window walk meets them - ascending input index, the order of
-            // registration.cpp:47-50 (the sum starts at 0, as there: a lone -0 becomes +0) - and divides by the count (:52-53)
-            float ax = 0.f, ay = 0.f, az = 0.f;
-            ax += xyz[3 * gp]; ay += xyz[3 * gp + 1]; az += pz;
+            // the leader sums its voxel (VoxelSum, points only): itself, then the others as the window walk meets them - ascending input index
+            VoxelSum<false> sum;
+            sum.add_point(xyz[3 * gp], xyz[3 * gp + 1], pz);
             if (others > 0)
                 for (int vv = va; vv <= vb; ++vv)
                     for (int uu = ua; uu <= ub; ++uu) {
                         const int m = (int)map[vv * ur + uu] - 1;
-                        if (member(m)) { const size_t gm = (size_t)(l0 + m); ax += xyz[3 * gm]; ay += xyz[3 * gm + 1]; az += xyz[3 * gm + 2]; }
+                        if (member(m)) sum.add(xyz, nullptr, nullptr, (size_t)(l0 + m));
                     }
-            const float fn = (float)(others + 1);
-            mean_at[3 * gp] = ax / fn; mean_at[3 * gp + 1] = ay / fn; mean_at[3 * gp + 2] = az / fn;
+            sum.emit(others + 1, mean_at, nullptr, nullptr, false, gp);
         }
     }
 }
@@ -531,6 +463,9 @@ void k_vs_group(const float* __restrict__ xyz, const int* __restrict__ seg_off, 
 // the leaders per tile (tile_sums), [exclusive scan], emit with the scanned prefix (tile_prefix): with tens of thousands of tiles the
 // look-back's polling (device-scope loads in a loop from every tile in flight) slows the whole memory system down - 61 us of waiting
 // per tile and 51 us for a leader wave's gathers in a batch of 256 clouds, against 9 and 18 us for one cloud.
+// (The parameters stay a scalar list: handed over as by-value descriptors - clouds, groups, scan state, VoxelFirst - the kernel kept its
+// registers, LDS and occupancy but gained address arithmetic on the descriptors' kernarg bases and moves in front of its gathers, 1 to
+// 6 instructions per instantiation: profiles/r28/voxel_rules.md.  The host side, voxel_group_hashed, takes the descriptors.)
 template <int MODE, bool NRM>
 __global__ __launch_bounds__(VH_BLOCK)
 void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb, int total, const int* __restrict__ seg_off, int nseg, float inv,
@@ -637,486 +572,144 @@ void k_vh_finalize(const float* __restrict__ xyz, const float* __restrict__ rgb,
         const size_t o = (size_t)run;
         if (rank_out) rank_out[g] = run;
         if (run >= capacity) return;
-        out_xyz[3 * o] = mean_at[3 * (size_t)g]; out_xyz[3 * o + 1] = mean_at[3 * (size_t)g + 1]; out_xyz[3 * o + 2] = mean_at[3 * (size_t)g + 2];
-        if (leaders) { int cx, cy, cz; vh_cell(xyz, (size_t)g, inv, cx, cy, cz); leaders[o] = make_int4(cx, cy, cz, g - lo); }
+        copy_row3(out_xyz, o, mean_at, (size_t)g);
+        if (leaders) leaders[o] = voxel_cell(xyz, (size_t)g, inv, g - lo);
         return;
     }
     // ascending index order without moving anything: cnt rounds of "smallest index above the last one"
-    float ax = 0.f, ay = 0.f, az = 0.f, cr = 0.f, cg = 0.f, cb = 0.f, nx = 0.f, ny = 0.f, nz = 0.f;
+    VoxelSum<NRM> sum;
     int last = -1;
     for (int r = 0; r < cnt; ++r) {
         int nxt = VH_EMPTY;
 #pragma unroll
         for (int q = 0; q < VH_K; ++q) nxt = (m[q] > last && m[q] < nxt) ? m[q] : nxt;
         last = nxt;
-        const size_t idx = (size_t)nxt;
-        ax += xyz[3 * idx]; ay += xyz[3 * idx + 1]; az += xyz[3 * idx + 2];        // registration.cpp:47-50, ascending input index
-        if (rgb) { cr += rgb[3 * idx]; cg += rgb[3 * idx + 1]; cb += rgb[3 * idx + 2]; }
-        if (NRM) { nx += nrm.in[3 * idx]; ny += nrm.in[3 * idx + 1]; nz += nrm.in[3 * idx + 2]; }
+        sum.add(xyz, rgb, nrm.in, (size_t)nxt);
     }
-    const float fn = (float)cnt;
     const size_t o = (size_t)run;
     if (rank_out) rank_out[g] = run;
     if (run >= capacity) return;                          // the caller's buffer is too small: it learns the count and gets an error
-    out_xyz[3 * o] = ax / fn; out_xyz[3 * o + 1] = ay / fn; out_xyz[3 * o + 2] = az / fn;   // :52-53
-    if (rgb && out_rgb) { out_rgb[3 * o] = cr / fn; out_rgb[3 * o + 1] = cg / fn; out_rgb[3 * o + 2] = cb / fn; }
-    if (NRM) {
-        float mx = nx / fn, my = ny / fn, mz = nz / fn;
-        voxel_unit_normal(mx, my, mz);
-        nrm.out[3 * o] = mx; nrm.out[3 * o + 1] = my; nrm.out[3 * o + 2] = mz;
-    }
-    if (leaders) { int cx, cy, cz; vh_cell(xyz, (size_t)g, inv, cx, cy, cz); leaders[o] = make_int4(cx, cy, cz, g - lo); }
+    sum.emit(cnt, out_xyz, out_rgb, nrm.out, rgb != nullptr, o);
+    if (leaders) leaders[o] = voxel_cell(xyz, (size_t)g, inv, g - lo);
 }
 
-// The hash-table path for B clouds stored back to back (d_seg_off: B + 1 device ints, nullptr for one cloud).  Outputs in
-// first-occurrence order, cloud b at [voff[b], voff[b + 1]) of d_out_xyz (capacity `total` points); d_voff: B + 1 ints.
-// *overflowed = 1: a voxel had more than VH_K members (the outputs are garbage, take the counting-sort path).
-static int voxel_hash_first_order(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int total, const int* d_seg_off, int nseg, float voxel,
-                                  float* d_out_xyz, float* d_out_rgb, int capacity, int* d_rank /* optional, total ints */,
-                                  int4* d_leaders /* optional, capacity entries */, int* d_voff, int* h_result /* optional: pinned {voxels, overflow flag} */,
-                                  const VoxelPinhole* pinhole = nullptr, const int* h_seg_off = nullptr /* with pinhole: nseg + 1 host offsets */,
-                                  VoxelNormals nrm = VoxelNormals{nullptr, nullptr} /* both or neither; never with pinhole */) {
+// ---- the ladder -----------------------------------------------------------------------------------------------------------------
+// What a rung is handed: one cloud (d_off null) or several stored back to back, with their optional companions.
+struct VoxelInput {
+    const float* xyz; const float* rgb; const float* nrm;   // rgb / nrm null: a cloud without that companion (nrm never with cam)
+    int total; int n_clouds; const int* d_off; const int* h_off;   // cloud b = points [off[b], off[b + 1]), on the device and on the host
+    const VoxelPinhole* cam;                                // the clouds are in row-major pixel order under these intrinsics, or null
+};
+enum VoxelRung { RUNG_PIXELS = 0, RUNG_TABLE, RUNG_COUNTING_SORT, RUNG_FULL_SORT, RUNG_CLOUD_BY_CLOUD };
+
+// Rungs 1 and 2, the pixel windows (by_pixels) and the table: memset, k_vs_group or k_vh_insert, k_vh_finalize.  Voxels of cloud b at
+// [h_voff[b], h_voff[b + 1]) of out.xyz.  *flag = the rung's overflow word: VH_EMPTY - grouped; VS_FAILED - a tile the pixel windows do
+// not cover; anything else - a voxel of more than VH_K points (in both cases nothing of `out` is valid).  Synchronizes once.
+static int voxel_group_hashed(tdv_ctx* ctx, const VoxelInput& in, float voxel, VoxelFirst out, bool by_pixels, int split_from, int* h_voff, int* flag) {
     hipStream_t s = ctx->stream;
-    const bool with_nrm = nrm.in && nrm.out;
-    if (with_nrm && pinhole) return TDV_ERR_BAD_ARG;      // (k_vs_group sums the points only)
+    const int total = in.total, nseg = in.n_clouds;
+    if (by_pixels && (in.nrm || !in.cam || !in.d_off || !in.h_off)) return TDV_ERR_BAD_ARG;      // (k_vs_group sums the points only)
     const float inv = 1.0f / voxel;  // registration.cpp:32
-    const bool grouped_by_pixels = pinhole && h_seg_off && d_seg_off;      // k_vs_group instead of the table (the caller redoes the call without it if a tile fails)
     const int tiles = (total + VH_ITEMS - 1) / VH_ITEMS;
-    // one fill: claim[slots] | vcnt[total] | desc[tiles] (u64) | ticket | overflow.  Grouped by pixels: no table, no counts, no member rows -
-    // only the scan descriptors, the ticket and the overflow word are filled, and the leaders' means take 12 B per point
-    size_t slots = 0, n_cnt = 0;
-    if (!grouped_by_pixels) { slots = 4096; while (slots < 2 * (size_t)total) slots <<= 1; n_cnt = (size_t)total; }
-    const size_t desc_at = (slots + n_cnt + 1) & ~(size_t)1;
-    const size_t n_fill = desc_at + 2 * (size_t)tiles + 2;
-    int* fill;
-    TDV_TRY(ws_alloc(ctx, n_fill, &fill));
-    int* claim = fill; int* vcnt = claim + slots;
-    unsigned long long* desc = reinterpret_cast<unsigned long long*>(fill + desc_at);
-    int* ticket = reinterpret_cast<int*>(desc + tiles);
-    int* overflow = ticket + 1;
-    int *members = nullptr, *voxel_of; float* mean_at = nullptr;
-    if (grouped_by_pixels) TDV_TRY(ws_alloc(ctx, (size_t)total * 3, &mean_at));
-    else TDV_TRY(ws_alloc(ctx, (size_t)total * VH_K, &members));
-    TDV_TRY(ws_alloc(ctx, (size_t)total, &voxel_of));
-    if (grouped_by_pixels) {
-        // tiles: consecutive VS_TILE-point stretches of every cloud (a tile never spans two clouds)
-        size_t nt = 0;
-        for (int b = 0; b < nseg; ++b) nt += (size_t)((h_seg_off[b + 1] - h_seg_off[b] + VS_TILE - 1) / VS_TILE);
-        int2* d_tiles;
-        TDV_TRY(ws_alloc(ctx, nt, &d_tiles));
-        TDV_TRY(pin_reserve(ctx, nt * sizeof(int2) + 64 + ((size_t)nseg + 2) * 4));   // (+ what the caller stages afterwards: the buffer must not move while the copy below is in flight)
-        int2* h_tiles = reinterpret_cast<int2*>(ctx->pin);
-        size_t k = 0;
-        for (int b = 0; b < nseg; ++b)
-            for (int g = h_seg_off[b]; g < h_seg_off[b + 1]; g += VS_TILE) h_tiles[k++] = make_int2(g, b);
-        TDV_HIP(ctx, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(int2), hipMemcpyHostToDevice, s));
-        TDV_HIP(ctx, hipMemsetAsync(fill, 0x7f, n_fill * 4, s));
-        k_vs_group<<<(unsigned)nt, VS_BLOCK, 0, s>>>(d_xyz, d_seg_off, d_tiles, inv, voxel, *pinhole, mean_at, voxel_of, overflow);
-    } else {
-        TDV_HIP(ctx, hipMemsetAsync(fill, 0x7f, n_fill * 4, s));
-        k_vh_insert<<<(total + 255) / 256, 256, 0, s>>>(d_xyz, total, d_seg_off, nseg, inv, (unsigned)(slots - 1), claim, vcnt, members, voxel_of, overflow);
+    if (!out.d_voff) TDV_TRY(ws_alloc(ctx, (size_t)nseg + 2, &out.d_voff));
+    // one cloud: the finalize kernel stores {voxel count, overflow flag} into pinned memory itself (a D2H copy of 8 bytes is a 9-us blit kernel)
+    int* h_result = nullptr;
+    if (!in.d_off) {
+        TDV_TRY(pin_reserve(ctx, 64));
+        h_result = reinterpret_cast<int*>(ctx->pin);
+        h_result[0] = -1; h_result[1] = 0;
     }
-    // (measured, us per call one pass / split: 184k points in pixel order 65 / 76; random order 250k 82 / 74, 500k 138 / 103, 1M 233 / 160, 4M 858 / 550;
-    //  256 clouds of 184k 8,100 / 4,400 - tools/studies/voxel_split_threshold.py)
-    static const int split_from = study_env("TDV_VOXEL_SPLIT_FROM") ? atoi(study_env("TDV_VOXEL_SPLIT_FROM")) : 224;   // tiles; tuning knob
-    // the finalize kernel of mode M, with the normals riding along (NRM) or not: the same grouping pass either way
-    const auto finalize = [&](auto M, int* tile_sums, const int* tile_prefix) {
-        constexpr int MODE = decltype(M)::value;
-        if (with_nrm)
-            k_vh_finalize<MODE, true><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
-                                                                 d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, tile_sums, tile_prefix, 0, mean_at, nrm);
-        else
-            k_vh_finalize<MODE, false><<<tiles, VH_BLOCK, 0, s>>>(d_xyz, d_rgb, total, d_seg_off, nseg, inv, voxel_of, vcnt, members, desc, ticket,
-                                                                  d_out_xyz, d_out_rgb, d_rank, d_leaders, d_voff, capacity, overflow, h_result, tile_sums, tile_prefix,
-                                                                  grouped_by_pixels ? 1 : 0, mean_at, nrm);
-    };
-    if (tiles < split_from)
-        finalize(std::integral_constant<int, 0>{}, nullptr, nullptr);
-    else {      // large inputs (a batch): count, scan, emit - launches without a wait inside
-        int *tile_sums, *tile_prefix, *d_tot;
-        TDV_TRY(ws_alloc(ctx, (size_t)tiles, &tile_sums));
-        TDV_TRY(ws_alloc(ctx, (size_t)tiles, &tile_prefix));
-        TDV_TRY(ws_alloc(ctx, 1, &d_tot));
-        finalize(std::integral_constant<int, 1>{}, tile_sums, nullptr);
-        TDV_TRY(exclusive_scan_dev(ctx, tile_sums, tiles, tile_prefix, d_tot));
-        finalize(std::integral_constant<int, 2>{}, nullptr, tile_prefix);
-    }
-    TDV_CHECK_LAUNCH(ctx);
-    return TDV_OK;
-}
-
-// out[p] = in[idx[p]] for rows of three floats
-__global__ void k_gather_rows3(const float* __restrict__ in, const int* __restrict__ idx, int n, float* __restrict__ out) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= n) return;
-    const size_t q = (size_t)idx[p];
-    out[3 * (size_t)p] = in[3 * q]; out[3 * (size_t)p + 1] = in[3 * q + 1]; out[3 * (size_t)p + 2] = in[3 * q + 2];
-}
-
-namespace {
-struct VoxelKey {
-    int x, y, z;
-    bool operator==(const VoxelKey& o) const { return x == o.x && y == o.y && z == o.z; }
-};
-struct VoxelKeyHash {  // the reference's combiner (registration.cpp:20-27)
-    size_t operator()(const VoxelKey& k) const {
-        size_t h = std::hash<int>()(k.x);
-        h ^= std::hash<int>()(k.y) + 0x9e3779b9 + (h << 6) + (h >> 2);
-        h ^= std::hash<int>()(k.z) + 0x9e3779b9 + (h << 6) + (h >> 2);
-        return h;
-    }
-};
-
-// The emulation below is tied to libstdc++'s <bits/hashtable.h> (it instantiates the library's own _Prime_rehash_policy):
-// with any other standard library the real std::unordered_map is used instead (the TDV_VOXEL_REAL_MAP path), which is
-// that library's order by construction.  tests/test_gpu_voxel.py holds the emulation against the real container, so a
-// toolchain bump that changes the node-list manipulation is caught.
-#ifdef __GLIBCXX__
-#define TDV_HAVE_LIBSTDCXX_EMULATION 1
-// Iteration order of a libstdc++ std::unordered_map (unique keys, std::__detail::_Mod_range_hashing, the library's own
-// _Prime_rehash_policy object) after inserting DISTINCT keys in a given sequence — the same node-list manipulation as
-// _Hashtable::_M_insert_unique_node / _M_insert_bucket_begin / _M_rehash_aux(unique) of <bits/hashtable.h>, on index
-// arrays instead of heap nodes.  Only first occurrences change a container, so replaying the leaders (first point of
-// every voxel, in input order) reproduces the reference's voxel order exactly, at a fraction of the cost of building
-// the real map over all points; tests compare it with the real container.
-class LibstdcxxInsertionOrder {
-public:
-    explicit LibstdcxxInsertionOrder(size_t expected) { next_.reserve(expected); code_.reserve(expected); buckets_.assign(1, EMPTY); }
-    void insert(size_t code) {   // a key not inserted before
-        const int node = (int)next_.size();
-        next_.push_back(NONE); code_.push_back(code);
-        const auto saved = policy_._M_state();
-        const std::pair<bool, std::size_t> rh = policy_._M_need_rehash(buckets_.size(), (size_t)node, 1);
-        if (rh.first) { try { rehash(rh.second); } catch (...) { policy_._M_reset(saved); throw; } }
-        const size_t bkt = code % buckets_.size();
-        if (buckets_[bkt] != EMPTY) {          // after the bucket's "before" node: the new node becomes the bucket's first
-            int& after = link(buckets_[bkt]);
-            next_[node] = after; after = node;
-        } else {                               // at the very beginning of the list
-            next_[node] = head_; head_ = node;
-            if (next_[node] != NONE) buckets_[code_[next_[node]] % buckets_.size()] = node;
-            buckets_[bkt] = BEFORE_BEGIN;
-        }
-    }
-    template <class F> void for_each(F&& f) const { for (int p = head_; p != NONE; p = next_[p]) f(p); }   // p = insertion rank
-private:
-    static constexpr int NONE = -1, EMPTY = -1, BEFORE_BEGIN = -2;
-    int& link(int before) { return before == BEFORE_BEGIN ? head_ : next_[before]; }
-    void rehash(size_t n) {
-        std::vector<int> nb(n, EMPTY);
-        int p = head_; head_ = NONE;
-        size_t bbegin_bkt = 0;
-        while (p != NONE) {
-            const int nxt = next_[p];
-            const size_t bkt = code_[p] % n;
-            if (nb[bkt] == EMPTY) {
-                next_[p] = head_; head_ = p;
-                nb[bkt] = BEFORE_BEGIN;
-                if (next_[p] != NONE) nb[bbegin_bkt] = p;
-                bbegin_bkt = bkt;
-            } else {
-                int& after = nb[bkt] == BEFORE_BEGIN ? head_ : next_[nb[bkt]];
-                next_[p] = after; after = p;
-            }
-            p = nxt;
-        }
-        buckets_.swap(nb);
-    }
-    std::vector<int> next_; std::vector<size_t> code_; std::vector<int> buckets_;
-    int head_ = NONE;
-    std::__detail::_Prime_rehash_policy policy_;
-};
-#else
-#define TDV_HAVE_LIBSTDCXX_EMULATION 0
-#endif
-}  // namespace
-
-static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                                 float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both, VoxelNormals nrm);
-
-int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                         float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both, VoxelNormals nrm) {
-    if (!ctx || !n_out || n < 0 || capacity < 0 || !(voxel > 0.f) || (n > 0 && !d_xyz)) return TDV_ERR_BAD_ARG;
-    if (!nrm.in || !nrm.out) nrm = VoxelNormals{nullptr, nullptr};     // (as the colours: both arrays or no normals)
-    if (order != TDV_VOXEL_ORDER_FIRST && order != TDV_VOXEL_ORDER_REFERENCE) return TDV_ERR_BAD_ARG;
-    if (both && (order != TDV_VOXEL_ORDER_REFERENCE || !both->first_xyz || !both->ref2first || !both->first2ref)) return TDV_ERR_BAD_ARG;
-    *n_out = 0;
-    if (n == 0) return TDV_OK;
-    const bool legacy = study_env("TDV_VOXEL_LEGACY") != nullptr || study_env("TDV_VOXEL_SORT") != nullptr;   // A/B knobs: the counting-sort path / the full sort (read per call: the tests switch it)
-    if (legacy) return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, false, both, nrm);
-    // hash-table path (memset + 2 kernels); first-occurrence order lands in the caller's buffer directly
-    hipStream_t s = ctx->stream;
-    const bool ref = order == TDV_VOXEL_ORDER_REFERENCE;
-    int *d_voff, *d_rank = nullptr; int4* d_leaders = nullptr;
-    float *tmp_xyz = d_out_xyz, *tmp_rgb = d_out_rgb, *tmp_nrm = nrm.out;
-    int cap_first = capacity;
-    TDV_TRY(ws_alloc(ctx, 3, &d_voff));
-    if (ref) {
-        cap_first = n;
-        TDV_TRY(ws_alloc(ctx, (size_t)n, &d_rank));
-        TDV_TRY(ws_alloc(ctx, (size_t)n, &d_leaders));
-        if (both) tmp_xyz = both->first_xyz; else TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &tmp_xyz));
-        tmp_rgb = nullptr;
-        if (d_rgb && d_out_rgb) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &tmp_rgb));
-        if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &tmp_nrm));
-    }
-    TDV_TRY(pin_reserve(ctx, 64));
-    int* h = reinterpret_cast<int*>(ctx->pin);      // the finalize kernel stores {voxel count, overflow flag} here itself: a D2H copy of 8 bytes is a 9-us blit kernel
-    h[0] = -1; h[1] = 0;
     {
         ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
-        TDV_TRY(voxel_hash_first_order(ctx, d_xyz, (d_rgb && d_out_rgb) ? d_rgb : nullptr, n, nullptr, 1, voxel, tmp_xyz, tmp_rgb, cap_first, d_rank, d_leaders,
-                                       d_voff, h, nullptr, nullptr, VoxelNormals{nrm.in, tmp_nrm}));
-    }
-    TDV_HIP(ctx, hipStreamSynchronize(s));
-    if (h[0] < 0) { snprintf(ctx->err, sizeof(ctx->err), "voxel: the result did not reach the host"); return TDV_ERR_INTERNAL; }
-    if (h[1] != VH_EMPTY)      // a voxel with more than VH_K members (a coarse grid): the counting-sort path takes any count
-        return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, false, both, nrm);
-    const int v = h[0];
-    *n_out = v;
-    if (v > capacity) return TDV_ERR_BAD_ARG;
-    if (!ref) return TDV_OK;
-    // The container order: on the device (the batch's way, ~17 rehash periods of small launches) when there are enough voxels for
-    // the host replay's 22 ns per voxel + two copies to cost more - measured cross-over around 10k voxels (tools/studies/voxel_probe.py);
-    // TDV_VOXEL_DEVICE_ORDER=0 / 1 forces either.  Colours ride along through the permutation.
-    const int dev_env = getenv("TDV_VOXEL_DEVICE_ORDER") ? atoi(getenv("TDV_VOXEL_DEVICE_ORDER")) : -1;   // (read per call: the tests switch it)
-    if (TDV_HAVE_LIBSTDCXX_EMULATION && (dev_env < 0 ? v >= 10000 : dev_env != 0)) {
-        int *r2f, *f2r; int failed = 1;
-        if (both) { r2f = both->ref2first; f2r = both->first2ref; }
-        else { TDV_TRY(ws_alloc(ctx, (size_t)v, &r2f)); TDV_TRY(ws_alloc(ctx, (size_t)v, &f2r)); }
-        int* d_voff1;
-        TDV_TRY(ws_alloc(ctx, 2, &d_voff1));
-        const int h_voff1[2] = {0, v};
-        TDV_HIP(ctx, hipMemcpyAsync(d_voff1, h_voff1, 8, hipMemcpyHostToDevice, s));
-        TDV_TRY(voxel_reference_order_batch_dev(ctx, 1, h_voff1, d_voff1, d_leaders, tmp_xyz, d_out_xyz, r2f, f2r, &failed));
-        if (!failed) {
-            if (tmp_rgb && d_out_rgb) k_gather_rows3<<<(v + 255) / 256, 256, 0, s>>>(tmp_rgb, r2f, v, d_out_rgb);
-            if (nrm.in) k_gather_rows3<<<(v + 255) / 256, 256, 0, s>>>(tmp_nrm, r2f, v, nrm.out);
-            if ((tmp_rgb && d_out_rgb) || nrm.in) {
-                TDV_CHECK_LAUNCH(ctx);
-                TDV_HIP(ctx, hipStreamSynchronize(s));
-            }
-            return TDV_OK;
+        // one fill: claim[slots] | vcnt[total] | desc[tiles] (u64) | ticket | overflow.  Grouped by pixels: no table, no counts, no member rows -
+        // only the scan descriptors, the ticket and the overflow word are filled, and the leaders' means take 12 B per point
+        size_t slots = 0, n_cnt = 0;
+        if (!by_pixels) { slots = 4096; while (slots < 2 * (size_t)total) slots <<= 1; n_cnt = (size_t)total; }
+        const size_t desc_at = (slots + n_cnt + 1) & ~(size_t)1;
+        const size_t n_fill = desc_at + 2 * (size_t)tiles + 2;
+        int* fill;
+        TDV_TRY(ws_alloc(ctx, n_fill, &fill));
+        int* claim = fill; int* vcnt = claim + slots;
+        unsigned long long* desc = reinterpret_cast<unsigned long long*>(fill + desc_at);
+        int* ticket = reinterpret_cast<int*>(desc + tiles);
+        int* overflow = ticket + 1;
+        int *members = nullptr, *voxel_of; float* mean_at = nullptr;
+        if (by_pixels) TDV_TRY(ws_alloc(ctx, (size_t)total * 3, &mean_at));
+        else TDV_TRY(ws_alloc(ctx, (size_t)total * VH_K, &members));
+        TDV_TRY(ws_alloc(ctx, (size_t)total, &voxel_of));
+        if (by_pixels) {
+            // tiles: consecutive VS_TILE-point stretches of every cloud (a tile never spans two clouds)
+            size_t nt = 0;
+            for (int b = 0; b < nseg; ++b) nt += (size_t)((in.h_off[b + 1] - in.h_off[b] + VS_TILE - 1) / VS_TILE);
+            int2* d_tiles;
+            TDV_TRY(ws_alloc(ctx, nt, &d_tiles));
+            TDV_TRY(pin_reserve(ctx, nt * sizeof(int2) + 64 + ((size_t)nseg + 2) * 4));   // (+ what is staged afterwards: the buffer must not move while the copy below is in flight)
+            int2* h_tiles = reinterpret_cast<int2*>(ctx->pin);
+            size_t k = 0;
+            for (int b = 0; b < nseg; ++b)
+                for (int g = in.h_off[b]; g < in.h_off[b + 1]; g += VS_TILE) h_tiles[k++] = make_int2(g, b);
+            TDV_HIP(ctx, hipMemcpyAsync(d_tiles, h_tiles, nt * sizeof(int2), hipMemcpyHostToDevice, s));
+            TDV_HIP(ctx, hipMemsetAsync(fill, 0x7f, n_fill * 4, s));
+            k_vs_group<<<(unsigned)nt, VS_BLOCK, 0, s>>>(in.xyz, in.d_off, d_tiles, inv, voxel, *in.cam, mean_at, voxel_of, overflow);
+        } else {
+            TDV_HIP(ctx, hipMemsetAsync(fill, 0x7f, n_fill * 4, s));
+            k_vh_insert<<<(total + 255) / 256, 256, 0, s>>>(in.xyz, total, in.d_off, nseg, inv, (unsigned)(slots - 1), claim, vcnt, members, voxel_of, overflow);
         }
-    }
-    return voxel_reference_order(ctx, v, n, d_leaders, tmp_xyz, tmp_rgb, d_rank, 0, d_out_xyz, d_out_rgb, both, VoxelNormals{tmp_nrm, nrm.out});
-}
-
-// ---- the reference's container order ON THE DEVICE, for all clouds of a batch (round 3) ---------------------------------
-// What the host replay above computes node by node has a closed form per rehash period.  Between two rehashes libstdc++ puts a
-// new node at the FRONT of its bucket's run, and a bucket that was empty at the FRONT of the whole list (_M_insert_bucket_begin);
-// a rehash walks the list front to back and re-inserts every node by the same rule (_M_rehash_aux).  So after a period with
-// bucket count B the list is the REVERSE of: the period's insertion sequence - the previous list front to back, then the new
-// keys in input order - grouped stably by bucket (code mod B), groups in order of first appearance.  With s(e) = position of
-// element e in that sequence (its previous rank, or its own index if it is new: the previous list holds exactly the elements
-// before it), first(b) = smallest s in bucket b, and F = the bucket sizes written at their first positions:
-//     rank(e) = m - 1 - ( exclusive_scan(F)[first(bucket(e))] + #{x in bucket(e) : s(x) < s(e)} ),        m = elements so far
-// One period = one memset + 3 small kernels + a scan over ALL clouds of the batch; ~17 periods reach 170k voxels (the bucket
-// counts 13, 29, 59, 127 ... are libstdc++'s, taken from its own _Prime_rehash_policy on the host: they depend on the element
-// count only).  Buckets hold their members' s in rows of RO_K; a fuller bucket (a degenerate hash) flags its cloud, which is then
-// finished by the host replay.  No leader leaves the device, the lanes of the batch never wait for the host.
-constexpr int RO_K = 16;
-__global__ void k_ro_codes(const int4* __restrict__ leaders, int total_v, unsigned long long* __restrict__ code) {
-    const int p = blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= total_v) return;
-    const int4 l = leaders[p];
-    // VoxelKeyHash (registration.cpp:20-27) with std::hash<int> = the value converted to size_t
-    unsigned long long h = (unsigned long long)(long long)l.x;
-    h ^= (unsigned long long)(long long)l.y + 0x9e3779b9ull + (h << 6) + (h >> 2);
-    h ^= (unsigned long long)(long long)l.z + 0x9e3779b9ull + (h << 6) + (h >> 2);
-    code[p] = h;
-}
-// grid (ceil(n_next / 256), clouds).  A cloud takes part in the period while it has elements past n_k; m = its elements so far.
-__global__ __launch_bounds__(256)
-void k_ro_insert(const unsigned long long* __restrict__ code, const int* __restrict__ rank, const int* __restrict__ voff, int n_k, int n_next, unsigned nb,
-                 int* __restrict__ fmax, int* __restrict__ cnt, int* __restrict__ rows, int* __restrict__ overflow) {
-    const int b = blockIdx.y, v0 = voff[b], v = voff[b + 1] - v0;
-    if (v <= n_k) return;
-    const int m = min(v, n_next), e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= m) return;
-    const size_t P = (size_t)v0 + e;
-    const int s = e < n_k ? rank[P] : e;
-    const size_t slot = (size_t)b * nb + (size_t)(code[P] % (unsigned long long)nb);
-    atomicMax(&fmax[slot], 0x7fffffff - s);                // first(b) = 0x7fffffff - fmax: a zero fill initialises it
-    const int pos = atomicAdd(&cnt[slot], 1);
-    if (pos < RO_K) rows[slot * RO_K + pos] = s; else overflow[b] = 1;
-}
-__global__ __launch_bounds__(256)
-void k_ro_first_sizes(const int* __restrict__ voff, int n_k, int n_next, unsigned nb, const int* __restrict__ fmax, const int* __restrict__ cnt, int* __restrict__ F) {
-    const int b = blockIdx.y;
-    if (voff[b + 1] - voff[b] <= n_k) return;
-    const unsigned k = blockIdx.x * 256 + threadIdx.x;
-    if (k >= nb) return;
-    const size_t slot = (size_t)b * nb + k;
-    const int c = cnt[slot];
-    if (c) F[(size_t)b * n_next + (0x7fffffff - fmax[slot])] = c;
-}
-__global__ __launch_bounds__(256)
-void k_ro_rank(const unsigned long long* __restrict__ code, int* __restrict__ rank, const int* __restrict__ voff, int n_k, int n_next, unsigned nb,
-               const int* __restrict__ fmax, const int* __restrict__ cnt, const int* __restrict__ rows, const int* __restrict__ S) {
-    const int b = blockIdx.y, v0 = voff[b], v = voff[b + 1] - v0;
-    if (v <= n_k) return;
-    const int m = min(v, n_next), e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= m) return;
-    const size_t P = (size_t)v0 + e;
-    const int s = e < n_k ? rank[P] : e;
-    const size_t slot = (size_t)b * nb + (size_t)(code[P] % (unsigned long long)nb);
-    const int first = 0x7fffffff - fmax[slot], c = min(cnt[slot], RO_K);
-    int before = S[(size_t)b * n_next + first] - S[(size_t)b * n_next];
-    const int* row = rows + slot * RO_K;
-    for (int q = 0; q < c; ++q) before += row[q] < s ? 1 : 0;
-    rank[P] = m - 1 - before;                                // in place: a lane reads and writes only its own element's rank
-}
-// out[voff[b] + rank] = first-order voxel; the permutation both ways (positions local to the cloud)
-__global__ __launch_bounds__(256)
-void k_ro_permute(const float* __restrict__ first_xyz, const int* __restrict__ rank, const int* __restrict__ voff, const int* __restrict__ skip,
-                  float* __restrict__ out_xyz, int* __restrict__ ref2first, int* __restrict__ first2ref) {
-    const int b = blockIdx.y, v0 = voff[b], v = voff[b + 1] - v0, e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= v || skip[b]) return;
-    const size_t P = (size_t)v0 + e, O = (size_t)v0 + rank[P];
-    out_xyz[3 * O] = first_xyz[3 * P]; out_xyz[3 * O + 1] = first_xyz[3 * P + 1]; out_xyz[3 * O + 2] = first_xyz[3 * P + 2];
-    if (ref2first) { ref2first[O] = e; first2ref[P] = (int)(O - v0); }
-}
-
-#if TDV_HAVE_LIBSTDCXX_EMULATION
-// (first element index, bucket count) of every rehash period a container of up to n_max elements goes through, from the
-// library's own policy object
-static void rehash_schedule(int n_max, std::vector<std::pair<int, unsigned>>& out) {
-    static std::mutex mu; static std::vector<std::pair<int, unsigned>> cache; static int cached_to = 0;
-    static std::__detail::_Prime_rehash_policy policy; static size_t buckets = 1;
-    std::lock_guard<std::mutex> lock(mu);
-    for (; cached_to < n_max; ++cached_to) {
-        const auto rh = policy._M_need_rehash(buckets, (size_t)cached_to, 1);
-        if (rh.first) { buckets = rh.second; cache.emplace_back(cached_to, (unsigned)buckets); }
-    }
-    out.clear();
-    for (auto& p : cache) if (p.first < n_max) out.push_back(p);
-}
-#endif
-
-// Reference order of every cloud of a batch on the device.  d_leaders / d_first_xyz / outputs are indexed by global first-
-// occurrence position (cloud b at [h_voff[b], h_voff[b + 1])); d_voff: the same offsets on the device.  h_failed[b] = 1: a
-// bucket of cloud b overflowed its row (or this build has no libstdc++): its slice of the outputs is untouched, the caller
-// finishes it with voxel_reference_order.
-int voxel_reference_order_batch_dev(tdv_ctx* ctx, int n_clouds, const int* h_voff, const int* d_voff, const int4* d_leaders, const float* d_first_xyz,
-                                    float* d_out_xyz, int* d_ref2first, int* d_first2ref, int* h_failed) {
-    for (int b = 0; b < n_clouds; ++b) h_failed[b] = TDV_HAVE_LIBSTDCXX_EMULATION ? 0 : 1;
-#if TDV_HAVE_LIBSTDCXX_EMULATION
-    const int total_v = h_voff[n_clouds];
-    if (total_v == 0) return TDV_OK;
-    int v_max = 0;
-    for (int b = 0; b < n_clouds; ++b) v_max = std::max(v_max, h_voff[b + 1] - h_voff[b]);
-    std::vector<std::pair<int, unsigned>> sched;
-    rehash_schedule(v_max, sched);
-    hipStream_t s = ctx->stream;
-    unsigned long long* code; int *rank, *d_overflow;
-    TDV_TRY(ws_alloc(ctx, (size_t)total_v, &code));
-    TDV_TRY(ws_alloc(ctx, (size_t)total_v, &rank));
-    TDV_TRY(ws_alloc(ctx, (size_t)n_clouds, &d_overflow));
-    TDV_HIP(ctx, hipMemsetAsync(d_overflow, 0, (size_t)n_clouds * 4, s));
-    k_ro_codes<<<(total_v + 255) / 256, 256, 0, s>>>(d_leaders, total_v, code);
-    const WsMark mark = ws_mark(ctx);
-    ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
-    for (size_t k = 0; k < sched.size(); ++k) {
-        const int n_k = sched[k].first, n_next = std::min(k + 1 < sched.size() ? sched[k + 1].first : v_max, v_max);
-        const unsigned nb = sched[k].second;
-        ws_rewind(ctx, mark);                                  // every period reuses the same scratch (stream order keeps them apart)
-        const size_t n_tab = (size_t)n_clouds * nb, n_F = (size_t)n_clouds * n_next;
-        if (n_F + 1 > 0x7fffffffull) { for (int b = 0; b < n_clouds; ++b) h_failed[b] = 1; return TDV_OK; }   // (beyond the 32-bit scan: host replay)
-        int *zero, *rows, *S, *d_tot;
-        TDV_TRY(ws_alloc(ctx, 2 * n_tab + n_F, &zero));       // fmax | cnt | F: one fill
-        TDV_TRY(ws_alloc(ctx, n_tab * RO_K, &rows));
-        TDV_TRY(ws_alloc(ctx, n_F, &S));
-        TDV_TRY(ws_alloc(ctx, 1, &d_tot));
-        int *fmax = zero, *cnt = zero + n_tab, *F = zero + 2 * n_tab;
-        TDV_HIP(ctx, hipMemsetAsync(zero, 0, (2 * n_tab + n_F) * 4, s));
-        const dim3 ge((n_next + 255) / 256, n_clouds), gb((nb + 255) / 256, n_clouds);
-        k_ro_insert<<<ge, 256, 0, s>>>(code, rank, d_voff, n_k, n_next, nb, fmax, cnt, rows, d_overflow);
-        k_ro_first_sizes<<<gb, 256, 0, s>>>(d_voff, n_k, n_next, nb, fmax, cnt, F);
-        TDV_TRY(exclusive_scan_dev(ctx, F, (int)n_F, S, d_tot));
-        k_ro_rank<<<ge, 256, 0, s>>>(code, rank, d_voff, n_k, n_next, nb, fmax, cnt, rows, S);
+        // the finalize kernel of mode M, with the normals riding along (NRM) or not: the same grouping pass either way
+        const auto finalize = [&](auto M, int* tile_sums, const int* tile_prefix) {
+            constexpr int MODE = decltype(M)::value;
+            const auto kernel = in.nrm ? k_vh_finalize<MODE, true> : k_vh_finalize<MODE, false>;
+            kernel<<<tiles, VH_BLOCK, 0, s>>>(in.xyz, in.rgb, total, in.d_off, nseg, inv, voxel_of, vcnt, members, desc, ticket, out.xyz, out.rgb, out.rank, out.leaders,
+                                              out.d_voff, out.capacity, overflow, h_result, tile_sums, tile_prefix, by_pixels ? 1 : 0, mean_at, VoxelNormals{in.nrm, out.nrm});
+        };
+        // (measured, us per call one pass / split: 184k points in pixel order 65 / 76; random order 250k 82 / 74, 500k 138 / 103, 1M 233 / 160, 4M 858 / 550;
+        //  256 clouds of 184k 8,100 / 4,400 - tools/studies/voxel_split_threshold.py)
+        if (tiles < split_from)
+            finalize(std::integral_constant<int, 0>{}, nullptr, nullptr);
+        else {      // large inputs (a batch): count, scan, emit - launches without a wait inside
+            int *tile_sums, *tile_prefix, *d_tot;
+            TDV_TRY(ws_alloc(ctx, (size_t)tiles, &tile_sums));
+            TDV_TRY(ws_alloc(ctx, (size_t)tiles, &tile_prefix));
+            TDV_TRY(ws_alloc(ctx, 1, &d_tot));
+            finalize(std::integral_constant<int, 1>{}, tile_sums, nullptr);
+            TDV_TRY(exclusive_scan_dev(ctx, tile_sums, tiles, tile_prefix, d_tot));
+            finalize(std::integral_constant<int, 2>{}, nullptr, tile_prefix);
+        }
         TDV_CHECK_LAUNCH(ctx);
     }
-    k_ro_permute<<<dim3((v_max + 255) / 256, n_clouds), 256, 0, s>>>(d_first_xyz, rank, d_voff, d_overflow, d_out_xyz, d_ref2first, d_first2ref);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(pin_reserve(ctx, (size_t)n_clouds * 4));
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, d_overflow, (size_t)n_clouds * 4, hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
-    std::memcpy(h_failed, ctx->pin, (size_t)n_clouds * 4);
-    ws_rewind(ctx, mark);
-#endif
-    return TDV_OK;
-}
-
-// All clouds of a batch at once (first-occurrence order; the reference order is finished per cloud with
-// voxel_reference_order).  d_seg_off: n_clouds + 1 device offsets into d_xyz.  Voxels of cloud b end up at
-// [h_voff[b], h_voff[b + 1]) of d_first_xyz (room for `total` points); d_rank / d_leaders (optional, `total` entries each) are what
-// voxel_reference_order needs.  *overflowed: a voxel held more than VH_K points - nothing of the output is valid, the caller
-// falls back to per-cloud calls.  d_voff_keep (optional): n_clouds + 2 device ints that receive the voxel offsets.  Synchronizes once.
-// nrm (optional): the clouds' normals, laid out like d_xyz, and their voxels' unit means, laid out like d_first_xyz - from the same pass.
-int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, int total, const int* d_seg_off, int n_clouds, float voxel,
-                               float* d_first_xyz, int* d_rank, int4* d_leaders, int* h_voff, int* overflowed, int* d_voff_keep,
-                               const float* pinhole4, const int* h_seg_off, VoxelNormals nrm) {
-    if (nrm.in && nrm.out && pinhole4) return TDV_ERR_BAD_ARG;       // (the pixel windows sum the points only)
-    if (!ctx || n_clouds < 1 || total < 0 || !(voxel > 0.f) || !h_voff || !overflowed) return TDV_ERR_BAD_ARG;
-    *overflowed = 0;
-    for (int b = 0; b <= n_clouds; ++b) h_voff[b] = 0;
-    if (total == 0) return TDV_OK;
-    hipStream_t s = ctx->stream;
-    int* d_voff = d_voff_keep;                               // (n_clouds + 2 ints; the caller's when it wants the offsets on the device afterwards)
-    if (!d_voff) TDV_TRY(ws_alloc(ctx, (size_t)n_clouds + 2, &d_voff));
-    TDV_TRY(pin_reserve(ctx, ((size_t)n_clouds + 2) * 4));
-    int* h = reinterpret_cast<int*>(ctx->pin);
-    // Clouds unprojected from a depth image with the given intrinsics (pinhole4 = fx, fy, cx, cy; h_seg_off = the clouds' offsets on the
-    // host) are grouped through pixel windows, without the table (k_vs_group); if a tile cannot be (coarse voxels, very long rows, a cloud
-    // that is not what the caller said) the call is redone through the table.  TDV_VOXEL_PIXELS=0 (parity tests): the table at once.
-    VoxelPinhole cam{};
-    const char* px_env = getenv("TDV_VOXEL_PIXELS");
-    bool by_pixels = pinhole4 && h_seg_off && !(px_env && atoi(px_env) == 0);
-    if (by_pixels) { cam.fx = pinhole4[0]; cam.fy = pinhole4[1]; cam.cx = pinhole4[2]; cam.cy = pinhole4[3]; by_pixels = cam.fx > 0.f && cam.fy > 0.f; }
-    std::vector<int> seg_copy;
-    if (by_pixels) seg_copy.assign(h_seg_off, h_seg_off + n_clouds + 1);          // (the pinned staging below is reused by the tile table)
-    for (int attempt = 0; attempt < 2; ++attempt) {
-        const WsMark mark = ws_mark(ctx);
-        {
-            ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
-            TDV_TRY(voxel_hash_first_order(ctx, d_xyz, nullptr, total, d_seg_off, n_clouds, voxel, d_first_xyz, nullptr, total, d_rank, d_leaders, d_voff, nullptr,
-                                           by_pixels ? &cam : nullptr, by_pixels ? seg_copy.data() : nullptr, nrm));
-        }
-        TDV_TRY(pin_reserve(ctx, ((size_t)n_clouds + 2) * 4));
-        h = reinterpret_cast<int*>(ctx->pin);
-        TDV_HIP(ctx, hipMemcpyAsync(h, d_voff, ((size_t)n_clouds + 2) * 4, hipMemcpyDeviceToHost, s));   // offsets, then the overflow flag
+    if (h_result) {
         TDV_HIP(ctx, hipStreamSynchronize(s));
-        ctx->last_voxel_grouping = by_pixels ? 2 : 1;
-        if (by_pixels && h[n_clouds + 1] == VS_FAILED) { by_pixels = false; ws_rewind(ctx, mark); continue; }   // a tile the pixel windows do not cover: the table
-        break;
+        if (h_result[0] < 0) { snprintf(ctx->err, sizeof(ctx->err), "voxel: the result did not reach the host"); return TDV_ERR_INTERNAL; }
+        *flag = h_result[1];
+        h_voff[0] = 0; h_voff[1] = h_result[0];
+        return TDV_OK;
     }
-    if (h[n_clouds + 1] != VH_EMPTY) { *overflowed = 1; return TDV_OK; }
-    std::memcpy(h_voff, h, ((size_t)n_clouds + 1) * 4);
+    TDV_TRY(pin_reserve(ctx, ((size_t)nseg + 2) * 4));
+    int* h = reinterpret_cast<int*>(ctx->pin);
+    TDV_HIP(ctx, hipMemcpyAsync(h, out.d_voff, ((size_t)nseg + 2) * 4, hipMemcpyDeviceToHost, s));   // offsets, then the overflow flag
+    TDV_HIP(ctx, hipStreamSynchronize(s));
+    *flag = h[nseg + 1];
+    if (*flag == VH_EMPTY) std::memcpy(h_voff, h, ((size_t)nseg + 1) * 4);
     return TDV_OK;
 }
 
-static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
-                                 float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, bool full_sort, const VoxelBothOrders* both, VoxelNormals nrm) {
-    if (!ctx || !n_out || n < 0 || capacity < 0 || !(voxel > 0.f) || (n > 0 && !d_xyz)) return TDV_ERR_BAD_ARG;
-    if (order != TDV_VOXEL_ORDER_FIRST && order != TDV_VOXEL_ORDER_REFERENCE) return TDV_ERR_BAD_ARG;
-    if (both && (order != TDV_VOXEL_ORDER_REFERENCE || !both->first_xyz || !both->ref2first || !both->first2ref)) return TDV_ERR_BAD_ARG;
-    *n_out = 0;
-    if (n == 0) return TDV_OK;
+// Rungs 3 and 4, one cloud through the counting sort (buckets of up to VX_MAX_BUCKET records: a fuller one sets *too_big and nothing of
+// `out` is valid) or the full bitonic sort (any cloud).  Both end in leader flags and their scan; the means are moved from where the
+// bucket kernel parked them, or summed over the sorted runs.  Synchronizes twice.
+static int voxel_group_sorted(tdv_ctx* ctx, const VoxelInput& in, float voxel, const VoxelFirst& out, bool full_sort, int* h_voff, int* too_big) {
     hipStream_t s = ctx->stream;
+    const int n = in.total;
     const float inv = 1.0f / voxel;  // registration.cpp:32
     const size_t n_pow2 = sort_pow2((size_t)n);
-    uint4* rec; int *leader, *rank, *d_total;
+    uint4* rec; int *leader, *rank = out.rank, *d_total;
     TDV_TRY(ws_alloc(ctx, n_pow2, &rec));
-    TDV_TRY(ws_alloc(ctx, (size_t)n, &rank));
+    if (!rank) TDV_TRY(ws_alloc(ctx, (size_t)n, &rank));
     TDV_TRY(ws_alloc(ctx, 1, &d_total));
     TDV_TRY(pin_reserve(ctx, 64));
     ScopedTimer tm(ctx, TDV_TIMER_VOXEL);
-    static const bool force_sort = study_env("TDV_VOXEL_SORT") != nullptr;   // A/B knob: the full bitonic sort
-    bool hashed = !force_sort && !full_sort;
     int* d_too_big = nullptr;
-    float *mean_xyz = nullptr, *mean_rgb = nullptr, *mean_nrm = nullptr;     // hashed path: means parked at their leader's input index
-    if (hashed) {
+    float *mean_xyz = nullptr, *mean_rgb = nullptr, *mean_nrm = nullptr;     // counting sort: means parked at their leader's input index
+    if (!full_sort) {
         // 9 launches (round 1: 15): one memset, cell histogram, scan (2), scatter, bucket sort + leaders + means, scan (2), compact
         size_t nb = 4096;
         while (nb < 2 * (size_t)n) nb <<= 1;
@@ -1127,21 +720,17 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
         TDV_TRY(ws_alloc(ctx, 1, &d_tot2));
         TDV_TRY(ws_alloc(ctx, (size_t)n, &rec_in));
         TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_xyz));
-        if (d_rgb && d_out_rgb) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_rgb));
-        if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_nrm));
+        if (in.rgb) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_rgb));
+        if (in.nrm) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &mean_nrm));
         TDV_HIP(ctx, hipMemsetAsync(zeroed, 0, (2 * nb + 1 + (size_t)n) * 4, s));
-        k_voxel_hist<<<(n + 255) / 256, 256, 0, s>>>(d_xyz, n, inv, (unsigned)(nb - 1), rec_in, hist);
+        k_voxel_hist<<<(n + 255) / 256, 256, 0, s>>>(in.xyz, n, inv, (unsigned)(nb - 1), rec_in, hist);
         TDV_TRY(exclusive_scan_dev(ctx, hist, (int)nb, start, d_tot2));
         k_voxel_scatter<<<(n + 255) / 256, 256, 0, s>>>(rec_in, n, (unsigned)(nb - 1), start, cursor, rec);
-        if (nrm.in)
-            k_voxel_bucket_emit<true><<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(rec, start, hist, (int)nb, n, d_too_big, d_xyz, mean_rgb ? d_rgb : nullptr, leader, mean_xyz, mean_rgb,
-                                                                                 VoxelNormals{nrm.in, mean_nrm});
-        else
-            k_voxel_bucket_emit<false><<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(rec, start, hist, (int)nb, n, d_too_big, d_xyz, mean_rgb ? d_rgb : nullptr, leader, mean_xyz, mean_rgb,
-                                                                                  VoxelNormals{nullptr, nullptr});
+        const auto emit = in.nrm ? k_voxel_bucket_emit<true> : k_voxel_bucket_emit<false>;
+        emit<<<(unsigned)((nb + 255) / 256), 256, 0, s>>>(rec, start, hist, (int)nb, n, d_too_big, in.xyz, in.rgb, leader, mean_xyz, mean_rgb, VoxelNormals{in.nrm, mean_nrm});
     } else {
         TDV_TRY(ws_alloc(ctx, (size_t)n, &leader));
-        k_voxel_records<<<(unsigned)((n_pow2 + 255) / 256), 256, 0, s>>>(d_xyz, n, (int)n_pow2, inv, rec);
+        k_voxel_records<<<(unsigned)((n_pow2 + 255) / 256), 256, 0, s>>>(in.xyz, n, (int)n_pow2, inv, rec);
         TDV_TRY(sort_records_dev(ctx, rec, n_pow2));
         TDV_HIP(ctx, hipMemsetAsync(leader, 0, (size_t)n * 4, s));
         k_voxel_heads<<<(n + 255) / 256, 256, 0, s>>>(rec, n, leader);
@@ -1150,89 +739,136 @@ static int voxel_downsample_impl(tdv_ctx* ctx, const float* d_xyz, const float* 
     int* h_total = reinterpret_cast<int*>(ctx->pin);
     h_total[1] = 0;
     TDV_HIP(ctx, hipMemcpyAsync(h_total, d_total, 4, hipMemcpyDeviceToHost, s));
-    if (hashed) TDV_HIP(ctx, hipMemcpyAsync(h_total + 1, d_too_big, 4, hipMemcpyDeviceToHost, s));
+    if (d_too_big) TDV_HIP(ctx, hipMemcpyAsync(h_total + 1, d_too_big, 4, hipMemcpyDeviceToHost, s));
     TDV_HIP(ctx, hipStreamSynchronize(s));
-    if (hashed && h_total[1])   // a bucket too large for the per-lane sort (very coarse grid): redo with the full sort
-        return voxel_downsample_impl(ctx, d_xyz, d_rgb, n, voxel, order, d_out_xyz, d_out_rgb, capacity, n_out, true, both, nrm);
-    const int v = *h_total;
-    *n_out = v;
-    if (v > capacity) return TDV_ERR_BAD_ARG;
-    // the voxels' means in first-occurrence order into o_*: moved from where the bucket kernel parked them, or summed over the sorted runs
-    const auto means = [&](int cap, float* o_xyz, float* o_rgb, float* o_nrm) {
-        if (hashed) k_voxel_compact<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, n, mean_xyz, mean_rgb, cap, o_xyz, o_rgb, VoxelNormals{mean_nrm, o_nrm});
-        else if (nrm.in) k_voxel_means<true><<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, cap, o_xyz, o_rgb, VoxelNormals{nrm.in, o_nrm});
-        else k_voxel_means<false><<<(n + 255) / 256, 256, 0, s>>>(rec, n, d_xyz, d_rgb, rank, cap, o_xyz, o_rgb, VoxelNormals{nullptr, nullptr});
-    };
-    if (order == TDV_VOXEL_ORDER_FIRST) {
-        means(capacity, d_out_xyz, d_out_rgb, nrm.out);
-        TDV_CHECK_LAUNCH(ctx);
-        TDV_HIP(ctx, hipStreamSynchronize(s));      // the device entry points return with their results in place (include/tdv_hip.h)
-        return TDV_OK;
+    *too_big = h_total[1];
+    if (*too_big) return TDV_OK;   // a bucket too large for the per-lane sort (very coarse grid)
+    h_voff[0] = 0; h_voff[1] = h_total[0];
+    if (!full_sort) k_voxel_compact<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, n, mean_xyz, mean_rgb, out.capacity, out.xyz, out.rgb, VoxelNormals{mean_nrm, out.nrm});
+    else {
+        const auto means = in.nrm ? k_voxel_means<true> : k_voxel_means<false>;
+        means<<<(n + 255) / 256, 256, 0, s>>>(rec, n, in.xyz, in.rgb, rank, out.capacity, out.xyz, out.rgb, VoxelNormals{in.nrm, out.nrm});
     }
-    // reference order: replay the container on the host to get its iteration order
-    float *tmp_xyz, *tmp_rgb = nullptr;
-    if (both) tmp_xyz = both->first_xyz;
-    else TDV_TRY(ws_alloc(ctx, (size_t)v * 3, &tmp_xyz));
-    if (d_rgb && d_out_rgb) TDV_TRY(ws_alloc(ctx, (size_t)v * 3, &tmp_rgb));
-    float* tmp_nrm = nullptr;
-    if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)v * 3, &tmp_nrm));
-    means(v, tmp_xyz, tmp_rgb, tmp_nrm);
+    // leaders (first point of every voxel: cell + input index) in first-occurrence order: all the reference order needs
+    if (out.leaders) k_voxel_leader_list<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, in.xyz, inv, n, out.leaders);
     TDV_CHECK_LAUNCH(ctx);
-    // leaders (first point of every voxel: cell + input index) in input order, from the device; the host only replays those
-    int4* d_leaders;
-    TDV_TRY(ws_alloc(ctx, (size_t)v, &d_leaders));
-    k_voxel_leader_list<<<(n + 255) / 256, 256, 0, s>>>(leader, rank, d_xyz, inv, n, d_leaders);
-    TDV_CHECK_LAUNCH(ctx);
-    return voxel_reference_order(ctx, v, n, d_leaders, tmp_xyz, tmp_rgb, rank, 0, d_out_xyz, d_out_rgb, both, VoxelNormals{tmp_nrm, nrm.out});
+    TDV_HIP(ctx, hipStreamSynchronize(s));      // the device entry points return with their results in place (include/tdv_hip.h)
+    return TDV_OK;
 }
 
-// The reference's container order for v voxels held in first-occurrence order (tmp_*): leaders (cell + input index of the first
-// point of every voxel, at its first-occurrence rank) go to the host, which replays the container; d_rank[input index] =
-// first-occurrence rank.  out[p] = tmp[rank[leader index of the p-th voxel of the container]].
-int voxel_reference_order(tdv_ctx* ctx, int v, int n, const int4* d_leaders, const float* tmp_xyz, const float* tmp_rgb, const int* d_rank, int rank_base,
-                          float* d_out_xyz, float* d_out_rgb, const VoxelBothOrders* both, VoxelNormals nrm /* in: the voxels' normals in first-occurrence order */) {
-    hipStream_t s = ctx->stream;
-    int* d_order;
-    TDV_TRY(ws_alloc(ctx, (size_t)v, &d_order));
-    // through pinned memory both ways (a pageable std::vector made these two copies staged ones: 2.3 MB + 0.6 MB per C4 instance)
-    const size_t pin_order_off = align_up((size_t)v * sizeof(int4), 64);
-    TDV_TRY(pin_reserve(ctx, pin_order_off + (size_t)v * 4));
-    const int4* leaders = reinterpret_cast<const int4*>(ctx->pin);
-    int* order_pinned = reinterpret_cast<int*>(ctx->pin + pin_order_off);
-    TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, d_leaders, (size_t)v * sizeof(int4), hipMemcpyDeviceToHost, s));
-    TDV_HIP(ctx, hipStreamSynchronize(s));
-    const bool real_map = !TDV_HAVE_LIBSTDCXX_EMULATION || study_env("TDV_VOXEL_REAL_MAP") != nullptr;   // A/B knob: a real std::unordered_map instead of the emulation
-    const auto t_host0 = std::chrono::steady_clock::now();
-    int n_first = 0;
-    struct { int* p; int* n; void push_back(int x) { p[(*n)++] = x; } } order_first{order_pinned, &n_first};
-    for (int r = 0; r < v; ++r)
-        if (leaders[r].w < 0 || leaders[r].w >= n) { snprintf(ctx->err, sizeof(ctx->err), "voxel: bad leader index %d", leaders[r].w); return TDV_ERR_INTERNAL; }
-    if (real_map) {
-        // later members of a voxel never change the container (grid[key] finds the node), so inserting the first
-        // occurrences in input order builds exactly the reference's table
-        std::unordered_map<VoxelKey, int, VoxelKeyHash> grid;
-        for (int r = 0; r < v; ++r) grid.emplace(VoxelKey{leaders[r].x, leaders[r].y, leaders[r].z}, leaders[r].w);
-        if ((int)grid.size() != v) {
-            snprintf(ctx->err, sizeof(ctx->err), "voxel: host replay found %zu voxels, device %d", grid.size(), v);
-            return TDV_ERR_INTERNAL;
-        }
-        for (auto& kv : grid) order_first.push_back(kv.second);
-    } else {
-#if TDV_HAVE_LIBSTDCXX_EMULATION
-        LibstdcxxInsertionOrder order((size_t)v);
-        VoxelKeyHash hasher;
-        for (int r = 0; r < v; ++r) order.insert(hasher(VoxelKey{leaders[r].x, leaders[r].y, leaders[r].z}));
-        order.for_each([&](int r) { order_first.push_back(leaders[r].w); });
-#endif
+// The one owner of the rungs: the voxels of these clouds in first-occurrence order, by the first rung that can do it.  A rung's failure
+// signal is read here and nowhere else; what a rung that handed over allocated is given back.  Several clouds have no rung below the
+// table: *done = RUNG_CLOUD_BY_CLOUD tells the caller to climb down with one cloud at a time.  The study knobs start one cloud lower.
+static int voxel_first_order(tdv_ctx* ctx, const VoxelInput& in, float voxel, const VoxelFirst& out, const VoxelKnobs& knobs, int* h_voff, VoxelRung* done) {
+    int rung = in.cam && knobs.pixels ? RUNG_PIXELS : RUNG_TABLE;
+    if (!in.d_off && knobs.counting_sort) rung = RUNG_COUNTING_SORT;
+    if (!in.d_off && knobs.full_sort) rung = RUNG_FULL_SORT;
+    const WsMark mark = ws_mark(ctx);
+    for (;; ++rung) {
+        ws_rewind(ctx, mark);
+        if (rung >= RUNG_COUNTING_SORT && in.d_off) rung = RUNG_CLOUD_BY_CLOUD;
+        int signal = 0;
+        if (rung <= RUNG_TABLE) {
+            TDV_TRY(voxel_group_hashed(ctx, in, voxel, out, rung == RUNG_PIXELS, knobs.split_from, h_voff, &signal));
+            signal = signal != VH_EMPTY;      // VS_FAILED: a tile off the pixel grid, coarse voxels, rows too long; else a voxel of more than VH_K points
+        } else if (rung <= RUNG_FULL_SORT)
+            TDV_TRY(voxel_group_sorted(ctx, in, voxel, out, rung == RUNG_FULL_SORT, h_voff, &signal));      // too_big: a bucket of more than VX_MAX_BUCKET records
+        if (!signal) break;
     }
-    if (study_env("TDV_DEBUG")) fprintf(stderr, "[tdv] voxel reference order: %d leaders replayed in %.3f ms (%s)\n", v,
-                                   std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_host0).count(), real_map ? "std::unordered_map" : "emulation");
-    if (n_first != v) { snprintf(ctx->err, sizeof(ctx->err), "voxel: host replay listed %d voxels, device %d", n_first, v); return TDV_ERR_INTERNAL; }
-    TDV_HIP(ctx, hipMemcpyAsync(d_order, order_pinned, (size_t)v * 4, hipMemcpyHostToDevice, s));
-    k_voxel_permute<<<(v + 255) / 256, 256, 0, s>>>(tmp_xyz, tmp_rgb, d_rank, rank_base, d_order, v, d_out_xyz, d_out_rgb,
-                                                    both ? both->ref2first : nullptr, both ? both->first2ref : nullptr, nrm);
-    TDV_CHECK_LAUNCH(ctx);
-    TDV_HIP(ctx, hipStreamSynchronize(s));  // the pinned staging is reused by the next call
+    *done = (VoxelRung)rung;
+    return TDV_OK;
+}
+
+VoxelKnobs voxel_knobs() {
+    const auto live = [](const char* name, int unset) { const char* e = getenv(name); return e ? atoi(e) : unset; };
+    const auto study = [](const char* name, int unset) { const char* e = study_env(name); return e ? atoi(e) : unset; };
+    VoxelKnobs k;
+    k.pixels = live("TDV_VOXEL_PIXELS", 1) != 0;
+    k.device_order = live("TDV_VOXEL_DEVICE_ORDER", -1);
+    k.batch = live("TDV_BATCH_VOXEL", 1) != 0;
+    k.counting_sort = study_env("TDV_VOXEL_LEGACY") != nullptr;
+    k.full_sort = study_env("TDV_VOXEL_SORT") != nullptr;
+    k.real_map = study_env("TDV_VOXEL_REAL_MAP") != nullptr;
+    k.split_from = study("TDV_VOXEL_SPLIT_FROM", 224);
+    return k;
+}
+
+// ---- the entry points ----------------------------------------------------------------------------------------------------------
+int voxel_downsample_dev(tdv_ctx* ctx, const float* d_xyz, const float* d_rgb, int n, float voxel, int order,
+                         float* d_out_xyz, float* d_out_rgb, int capacity, int* n_out, const VoxelBothOrders* both, VoxelNormals nrm) {
+    if (!ctx || !n_out || n < 0 || capacity < 0 || !(voxel > 0.f) || (n > 0 && !d_xyz)) return TDV_ERR_BAD_ARG;
+    if (!nrm.in || !nrm.out) nrm = VoxelNormals{nullptr, nullptr};     // (as the colours: both arrays or no normals)
+    if (!d_rgb || !d_out_rgb) { d_rgb = nullptr; d_out_rgb = nullptr; }
+    if (order != TDV_VOXEL_ORDER_FIRST && order != TDV_VOXEL_ORDER_REFERENCE) return TDV_ERR_BAD_ARG;
+    if (both && (order != TDV_VOXEL_ORDER_REFERENCE || !both->first_xyz || !both->ref2first || !both->first2ref)) return TDV_ERR_BAD_ARG;
+    *n_out = 0;
+    if (n == 0) return TDV_OK;
+    const VoxelKnobs knobs = voxel_knobs();
+    // first-occurrence order lands in the caller's buffers directly; the reference order goes through rows of their own
+    VoxelFirst first{d_out_xyz, d_out_rgb, nrm.out, capacity};
+    const bool ref = order == TDV_VOXEL_ORDER_REFERENCE;
+    if (ref) {
+        first.capacity = n;
+        TDV_TRY(ws_alloc(ctx, (size_t)n, &first.rank));
+        TDV_TRY(ws_alloc(ctx, (size_t)n, &first.leaders));
+        if (both) first.xyz = both->first_xyz; else TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &first.xyz));
+        if (d_rgb) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &first.rgb));
+        if (nrm.in) TDV_TRY(ws_alloc(ctx, (size_t)n * 3, &first.nrm));
+    }
+    int h_voff[2] = {0, 0};
+    VoxelRung done;
+    TDV_TRY(voxel_first_order(ctx, VoxelInput{d_xyz, d_rgb, nrm.in, n, 1, nullptr, nullptr, nullptr}, voxel, first, knobs, h_voff, &done));
+    const int v = h_voff[1];
+    *n_out = v;
+    if (v > capacity) return TDV_ERR_BAD_ARG;
+    if (!ref) return TDV_OK;
+    return voxel_finish_reference(ctx, n, v, first, d_out_xyz, d_out_rgb, nrm.out, both, knobs);
+}
+
+int voxel_downsample_batch_dev(tdv_ctx* ctx, const float* d_xyz, const int* h_off, const int* d_off, int n_clouds, float voxel, const float* pinhole4,
+                               const VoxelFirst& out, int* h_voff, const float* d_normals, int* overflowed, bool batched) {
+    if (!ctx || n_clouds < 1 || !h_off || !h_voff || !(voxel > 0.f) || h_off[n_clouds] < 0) return TDV_ERR_BAD_ARG;
+    const bool with_nrm = d_normals && out.nrm;
+    if (with_nrm && pinhole4) return TDV_ERR_BAD_ARG;       // (the pixel windows sum the points only)
+    const int total = h_off[n_clouds];
+    if (overflowed) *overflowed = 0;
+    for (int b = 0; b <= n_clouds; ++b) h_voff[b] = 0;
+    if (batched) {
+        VoxelRung done = RUNG_TABLE;
+        if (total > 0) {
+            // Clouds unprojected from a depth image with the given intrinsics are grouped through pixel windows, without the table
+            // (k_vs_group); if a tile cannot be (coarse voxels, very long rows, a cloud that is not what the caller said) the table takes over.
+            VoxelPinhole cam{};
+            if (pinhole4) { cam.fx = pinhole4[0]; cam.fy = pinhole4[1]; cam.cx = pinhole4[2]; cam.cy = pinhole4[3]; }
+            const bool has_cam = pinhole4 && cam.fx > 0.f && cam.fy > 0.f;
+            const std::vector<int> off_copy(h_off, h_off + n_clouds + 1);          // (a copy: the pinned staging is reused by the tile table)
+            VoxelFirst first = out;
+            first.rgb = nullptr; first.nrm = with_nrm ? out.nrm : nullptr; first.capacity = total;
+            TDV_TRY(voxel_first_order(ctx, VoxelInput{d_xyz, nullptr, with_nrm ? d_normals : nullptr, total, n_clouds, d_off, off_copy.data(), has_cam ? &cam : nullptr},
+                                      voxel, first, voxel_knobs(), h_voff, &done));
+            ctx->last_voxel_grouping = done == RUNG_PIXELS ? 2 : 1;
+        }
+        const int redo = done == RUNG_CLOUD_BY_CLOUD ? 1 : 0;
+        ctx->last_voxel_batch_redone = redo;
+        if (overflowed) *overflowed = redo;
+        if (!redo || overflowed) return TDV_OK;
+    }
+    // one cloud on its own, or a voxel with more points than the table's member rows hold (a coarse grid): cloud by cloud down the
+    // rest of the ladder, packed back to back as the batched pass leaves them
+    const WsMark mark = ws_mark(ctx);
+    int at = 0;
+    for (int b = 0; b < n_clouds; ++b) {
+        const int n = h_off[b + 1] - h_off[b];
+        int v = 0;
+        h_voff[b] = at;
+        if (n > 0) {
+            ws_rewind(ctx, mark);
+            TDV_TRY(voxel_downsample_dev(ctx, d_xyz + (size_t)h_off[b] * 3, nullptr, n, voxel, TDV_VOXEL_ORDER_FIRST, out.xyz + (size_t)at * 3, nullptr, n, &v, nullptr,
+                                         VoxelNormals{with_nrm ? d_normals + (size_t)h_off[b] * 3 : nullptr, with_nrm ? out.nrm + (size_t)at * 3 : nullptr}));
+        }
+        at += v;
+    }
+    h_voff[n_clouds] = at;
     return TDV_OK;
 }
 

@@ -1618,6 +1618,11 @@ int tdv_ransac_score_unit_chunks(void);
  * fast scoring kernel).  The size of the batch that starts at iteration it0: 8,192 at 0, 65,536 while it0 < 270,336, the grown size
  * from there on; the call's last batch is what is left of max_iterations.  TDV_ERR_BAD_ARG for it0 < 0. */
 int tdv_ransac_batch_size(int it0);
+/* Test aid (host only): the voxel stage's rules as every voxel kernel compiles them.  For each of n points xyz[3 i ...]: its cell
+ * (int)floor(p * (1 / voxel_size)) per axis, converted as x86 does (tdv_voxel_downsample), to out_cells[3 i ...], and the reference's
+ * key hash of that cell (src/registration.cpp:20-27, std::hash<int> the sign-extended value) to out_codes[i].  TDV_ERR_BAD_ARG for
+ * n < 0, a voxel_size that is not positive, or a NULL array with n > 0. */
+int tdv_voxel_rules(const float* xyz, int n, float voxel_size, int* out_cells, unsigned long long* out_codes);
 /* Registration::loadReferenceModel (src/registration.cpp:416-461): ASCII PLY, x y z [r g b] per vertex.
  * Keeps the reference's behaviour: colours are detected by "red" appearing in any header line and are
  * divided by 255 when r > 1; the header loop consumes the line AFTER end_header, so the first vertex is
