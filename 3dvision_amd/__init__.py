@@ -46,7 +46,7 @@ DEPTH_BATCH_MASK_PASSES = 1   # the B masks cross HBM once in tdv_depth_to_cloud
 
 # every symbol include/tdv_hip.h declares (checked by the CPU test-suite against the built library)
 ABI_SYMBOLS = [
-    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_voxel_batch_redone", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_last_ransac_bound", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
+    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_voxel_batch_redone", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_set_ransac_leaf_order", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_last_ransac_bound", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
     "tdv_ctx_destroy", "tdv_status_string", "tdv_last_error", "tdv_version", "tdv_timing_enable", "tdv_timing_read",
     "tdv_depth_preprocess", "tdv_deproject", "tdv_depth_to_cloud", "tdv_voxel_downsample", "tdv_estimate_normals",
     "tdv_compute_fpfh", "tdv_feature_match", "tdv_ransac", "tdv_icp", "tdv_icp_correspondences",
@@ -654,6 +654,11 @@ class Context:
         """'fast' (default: FMA pass, chunks inside the rounding band re-scored with the reference arithmetic) or 'exact'
         (the reference arithmetic only); same inlier counts."""
         _check(self._h, lib().tdv_ctx_set_ransac_score(self._h, {"fast": 0, "exact": 1, "matrix": 2}[mode]), "tdv_ctx_set_ransac_score")
+
+    def set_ransac_leaf_order(self, mode):
+        """'auto' (default: class-major leaves for a call with at least 50,000 pairs), 'morton' or 'classes': the order of the
+        leaves the leaf-box bound walks; same result, other list lengths."""
+        _check(self._h, lib().tdv_ctx_set_ransac_leaf_order(self._h, {"auto": 0, "morton": 1, "classes": 2}[mode]), "tdv_ctx_set_ransac_leaf_order")
 
     def last_ransac_rescore(self):
         """Fraction of the (hypothesis, point) tests the last RANSAC call scored a second time exactly (-1 in 'exact' mode)."""

@@ -347,6 +347,12 @@ int tdv_ctx_set_ransac_score(tdv_ctx* ctx, int mode) {
     return TDV_OK;
 }
 
+int tdv_ctx_set_ransac_leaf_order(tdv_ctx* ctx, int mode) {
+    if (!ctx || mode < TDV_RANSAC_LEAVES_AUTO || mode > TDV_RANSAC_LEAVES_CLASSES) return TDV_ERR_BAD_ARG;
+    ctx->ransac_leaf_order = mode;
+    return TDV_OK;
+}
+
 int tdv_ctx_set_fps_path(tdv_ctx* ctx, int mode) {
     if (!ctx || mode < TDV_FPS_AUTO || mode > TDV_FPS_GRID) return TDV_ERR_BAD_ARG;
     ctx->fps_path = mode;

@@ -1192,7 +1192,10 @@ constexpr int RB_SPLIT = 16;
 enum { RB_ONE = 0, RB_COARSE = 1 };
 // One wave's share [k0, k1) of the leaf pairs for its lane's hypothesis (r: column-major R, t): the sizes of the leaves that
 // may hold an inlier, added until the sum exceeds `best` (done).  tb = (s + margin E)^2 (1 + 1e-6).
-__device__ __forceinline__ int rb_walk(const float* r, const float* __restrict__ leaves, int k0, int k1, float tb, int best, bool done) {
+// LeafPtr: const float*, or - k_ransac_bound_fine - the same address in the constant address space (RbConstLeaves).
+typedef const float __attribute__((address_space(4)))* RbConstLeaves;
+template <typename LeafPtr>
+__device__ __forceinline__ int rb_walk(const float* r, const LeafPtr leaves, int k0, int k1, float tb, int best, bool done) {
     int ub = 0;
     v2f rr[12], ar[9];
 #pragma unroll
@@ -1201,7 +1204,7 @@ __device__ __forceinline__ int rb_walk(const float* r, const float* __restrict__
     for (int e = 0; e < 9; ++e) ar[e] = (v2f){fabsf(r[e]), fabsf(r[e])};
     for (int k = k0; k < k1; ++k) {
         if (((k - k0) & 7) == 0 && !__any(!done)) break;
-        const float* __restrict__ g = leaves + (size_t)k * 32;
+        const LeafPtr g = leaves + (size_t)k * 32;
         float v[32];
 #pragma unroll
         for (int e = 0; e < 32; ++e) v[e] = g[e];
@@ -1403,46 +1406,80 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView trip
     const int slot = rb_append3(is_live && !near, near, undecided, lane, h, live, n_live, lj.near, lj.n_near, und, n_und);
     if (MODE == RB_COARSE && undecided) acc[slot] = 0;
 }
-// k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a tenth of the batch (a fifth before RansacBoundLists), too few
-// workgroups to fill the chip with one workgroup per 64 of them, so the leaf pairs are cut into gridDim.y ranges as well (blockIdx.y:
-// RB_FINE_Y of them unless the study build's TDV_RANSAC_FINE_Y says otherwise); a workgroup adds its 64 partial
-// sums to acc[slot], and the last workgroup of a slot block (ticket) decides: live on a total > best, dead
-// otherwise.  A partial sum that stopped early exceeds best alone, so a stop anywhere makes the total exceed it too; without one
-// the total is the full fine sum - the one-level walk's verdict.  The grid covers the whole batch (the host does not know
-// how many hypotheses are undecided); the workgroups past the list return at once.
-constexpr int RB_FINE_Y = 4;
+// k_ransac_bound_fine: the undecided hypotheses over the fine leaves.  They are a tenth of the batch with Morton leaves, a
+// twenty-fifth with class-major ones - too few workgroups to fill the chip with one per 64 of them, and how few the host does not
+// know.  So the grid is the chip's (fine_grid: the workgroups it holds at once, whatever the batch), and every workgroup reads the
+// list's length and cuts the work alike (ransac_cut.hpp: fine_ranges): a unit is a slot block of 64 hypotheses over one of R ranges
+// of the leaf pairs, unit u is range u / nb of slot block u mod nb, and workgroup w takes the units w, w + gridDim.x, ...  (Until round 29 the grid was the batch's slot blocks times a
+// fixed 4 ranges: the kernel took two rounds of a 49-pair walk for any list from a third of the chip up, and a shorter list gained
+// nothing - profiles/r14/ransac_bound_lists.md, profiles/r29/ransac_leaf_classes.md.)  force_y > 0 (study build,
+// TDV_RANSAC_FINE_Y): R = force_y whatever the list, the A/B.
+// A workgroup adds its 64 partial sums to acc[slot], and the last of a slot block's R arrivals (ticket) decides: live on a
+// total > best, dead otherwise.  A partial sum that stopped early exceeds best alone, so a stop anywhere makes the total exceed it
+// too; without one the total is the full fine sum - the one-level walk's verdict, whatever the cut.  A unit whose range is empty
+// (fewer leaf pairs than ranges) still arrives.  No workgroup waits for another.
+// The kernel's one argument.  A unit reads what it needs from the kernel-argument segment itself (FineJobArg, the segment's address
+// made anew per unit): held in scalar registers from the kernel's start across every unit's walk, the pointers of the tail took the
+// kernel to 94 SGPRs, and above 80 a CU admits one workgroup of 16 waves, not two (measured: a list of 276 units took two rounds).
+struct FineJob {
+    const float* hyp; const float* leaves; const unsigned* pmax; const int* state; const int* und; const int* n_und;
+    int *live, *n_live, *acc, *ticket; ListJob lj;
+    int h_pad, n_lpairs, force_y; float sqrt_tau, band_u;
+};
+typedef const FineJob __attribute__((address_space(4)))* FineJobArg;
 __global__ __launch_bounds__(64 * RB_SPLIT)
-void k_ransac_bound_fine(const float* __restrict__ hyp, int h_pad, const float* __restrict__ leaves, int n_lpairs,
-                         const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state,
-                         int* __restrict__ live, int* __restrict__ n_live, const int* __restrict__ und, const int* __restrict__ n_und,
-                         int* __restrict__ acc, int* __restrict__ ticket, const ListJob lj) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int n = *n_und, best = state[0];
-    const int per_y = (n_lpairs + (int)gridDim.y - 1) / (int)gridDim.y, y0 = blockIdx.y * per_y, y1 = min(n_lpairs, y0 + per_y);
-    const int per = (y1 - y0 + RB_SPLIT - 1) / RB_SPLIT;
-    const int k0 = min(y1, y0 + __builtin_amdgcn_readfirstlane(wave) * per), k1 = min(y1, k0 + per);
+void k_ransac_bound_fine(const FineJob job) {
+    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int n = *job.n_und, best = job.state[0], n_lpairs = job.n_lpairs;
+    const int nb = (n + 63) / 64;                    // slot blocks on the list
+    int ranges = job.force_y > 0 ? job.force_y : 1;
+    if (job.force_y <= 0 && nb > 0) {               // fine_ranges, lane r - 1 asking for r ranges
+        unsigned long long key = fine_cut_key(lane + 1, nb, n_lpairs, (int)gridDim.x, RB_SPLIT);
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(key, off, 64); key = o < key ? o : key; }
+        ranges = __builtin_amdgcn_readfirstlane((int)(key & 127ull));
+    }
+    const int per_y = (n_lpairs + ranges - 1) / ranges, units = nb * ranges;      // (nb <= 2^25 / 64, ranges <= 64)
+    // (the leaves through the constant address space: nothing writes them while a batch's kernels run, and behind a unit's fence and
+    // atomics the compiler would not take that from the pointer itself - the walk's wave-uniform loads must stay scalar)
+    const RbConstLeaves leaves = (RbConstLeaves)job.leaves;
     __shared__ int s_ub[64];
-    const int xb = blockIdx.x;
-    if (xb * 64 >= n) return;                        // workgroup-uniform (the grid is sized for the whole batch)
-    const int slot = xb * 64 + lane;
-    const int h = slot < n ? und[slot] : -1;
-    if (wave == 0) s_ub[lane] = 0;
-    const RbHyp o = rb_load(hyp, h_pad, h, h >= 0, pmax, sqrt_tau, band_u, 3.f);
-    const int ub = rb_walk(o.r, leaves, k0, k1, o.tb, best, h < 0);
-    __syncthreads();                                 // (s_ub zeroed)
-    if (ub) atomicAdd(&s_ub[lane], ub);
-    __syncthreads();
-    if (wave != 0) return;
-    const int part = s_ub[lane];
-    if (h >= 0 && part) atomicAdd(&acc[slot], part);
-    __threadfence();
-    int arrived = 0;
-    if (lane == 0) arrived = atomicAdd(&ticket[xb], 1);
-    if (__shfl(arrived, 0, 64) != (int)gridDim.y - 1) return;    // not the last workgroup of this slot block
-    const int total = h >= 0 ? atomicAdd(&acc[slot], 0) : 0;
-    const bool is_live = h >= 0 && total > best;
-    const bool near = is_live && lj.near && (lj.flags[h] & RB_NEAR);
-    rb_append3(is_live && !near, near, false, lane, h, live, n_live, lj.near, lj.n_near, nullptr, nullptr);
+#pragma unroll 1
+    for (int u = blockIdx.x; u < units; u += (int)gridDim.x) {        // workgroup-uniform
+        FineJobArg j = (FineJobArg)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(j));                  // (made anew: what is read through it is read per unit and dies with the unit)
+        // (slot block fastest, as the old grid's x: the workgroups that start side by side walk the same range of the leaves)
+        const int y = u / nb, xb = u - y * nb;
+        const int y0 = min(n_lpairs, y * per_y), y1 = min(n_lpairs, y0 + per_y);
+        const int per = (y1 - y0 + RB_SPLIT - 1) / RB_SPLIT;
+        const int k0 = min(y1, y0 + wave * per), k1 = min(y1, k0 + per);
+        const int slot = xb * 64 + lane;
+        const int h = slot < n ? j->und[slot] : -1;
+        if (wave == 0) s_ub[lane] = 0;               // (behind wave 0's read of the unit before; the others add behind the barrier)
+        const RbHyp o = rb_load(j->hyp, j->h_pad, h, h >= 0, j->pmax, j->sqrt_tau, j->band_u, 3.f);
+        const int ub = rb_walk(o.r, leaves, k0, k1, o.tb, best, h < 0);
+        __syncthreads();                             // (s_ub zeroed)
+        if (ub) atomicAdd(&s_ub[lane], ub);
+        __syncthreads();
+        if (wave != 0) continue;
+        int tl = lane;                               // the tail's lane, made anew per unit as well: nothing the tail derives from it
+        asm volatile("" : "+v"(tl));                 // stays in registers across the walk (the kernel has 64 VGPRs at 8 waves per SIMD)
+        FineJobArg t = (FineJobArg)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(t));
+        const int tslot = xb * 64 + tl;
+        const int part = s_ub[tl];
+        int* const acc = t->acc;
+        if (h >= 0 && part) atomicAdd(&acc[tslot], part);
+        __threadfence();
+        int arrived = 0;
+        if (tl == 0) arrived = atomicAdd(&t->ticket[xb], 1);
+        if (__shfl(arrived, 0, 64) != ranges - 1) continue;           // not the last unit of this slot block
+        const int total = h >= 0 ? atomicAdd(&acc[tslot], 0) : 0;
+        const bool is_live = h >= 0 && total > best;
+        int* const nearl = t->lj.near;
+        const bool near = is_live && nearl && (t->lj.flags[h] & RB_NEAR);
+        rb_append3(is_live && !near, near, false, tl, h, t->live, t->n_live, nearl, t->lj.n_near, nullptr, nullptr);
+    }
 }
 
 #ifdef TDV_STUDY
@@ -1545,7 +1582,7 @@ static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
 struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far, end_event, timer_events; int drop_permille, a_permille, u_cut_permille, fine_y, grown; float far_radius, live_radius; };
-static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations) {
+static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations, int ns) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
     k.score_fast = !score_exact_env && ctx->ransac_score_mode != TDV_RANSAC_SCORE_EXACT;
@@ -1569,17 +1606,19 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     k.far_radius = study_env("TDV_RANSAC_FAR_RADIUS") ? (float)atof(study_env("TDV_RANSAC_FAR_RADIUS")) : 4.f;
     k.a_permille = study_env("TDV_RANSAC_FAR_A_PERMILLE") ? atoi(study_env("TDV_RANSAC_FAR_A_PERMILLE")) : 110;
     k.u_cut_permille = study_env("TDV_RANSAC_FAR_UCUT_PERMILLE") ? atoi(study_env("TDV_RANSAC_FAR_UCUT_PERMILLE")) : 22;
-    // RansacBoundLists: a hypothesis within live_radius thresholds of the running best is live unwalked (0: off); the fine level's grid
-    // cuts the leaf pairs into fine_y ranges (profiles/r14/ransac_bound_lists.md)
+    // RansacBoundLists: a hypothesis within live_radius thresholds of the running best is live unwalked (0: off); the fine level
+    // cuts the leaf pairs into as many ranges as its list's length asks for (fine_ranges) - fine_y > 0: into fine_y, whatever the list
     k.live_radius = study_env("TDV_RANSAC_LIVE_RADIUS") ? (float)atof(study_env("TDV_RANSAC_LIVE_RADIUS")) : 20.f;
-    k.fine_y = study_env("TDV_RANSAC_FINE_Y") ? std::min(std::max(atoi(study_env("TDV_RANSAC_FINE_Y")), 1), 64) : RB_FINE_Y;
+    k.fine_y = study_env("TDV_RANSAC_FINE_Y") ? std::min(std::max(atoi(study_env("TDV_RANSAC_FINE_Y")), 1), kFineMaxRanges) : 0;
     // the batch schedule (ransac_cut.hpp: ransac_batch_size): the grown batch's size - kRansacBatch: no growth, the A/B.  (The fine
-    // level keeps fine_y ranges at either size: 2, 4 and 8 measured equal for a grown batch, profiles/r27/ransac_batch_growth.md.)
+    // level cuts by its list, not by the batch.)
     k.grown = study_env("TDV_RANSAC_GROWN") ? (int)align_up((size_t)std::min(std::max(atoi(study_env("TDV_RANSAC_GROWN")), kRansacBatch), 4 * kRansacBatch), RS_HYP_PER_BLOCK) : kRansacGrown;
-    // class-major leaves (k_leaf_keys): built and measured, off by default - on a 9,999-point cloud they take the live list from 4,317 to
-    // 4,063 hypotheses, one block of 1,024 fewer for the two-way order but not for the far and near lists together, and
-    // tests/test_gpu_ransac_far_bound.py holds the far bound strictly under the two-way order there
-    k.leaf_classes = study_env("TDV_RANSAC_LEAF_CLASSES") && atoi(study_env("TDV_RANSAC_LEAF_CLASSES")) == 1;
+    // class-major leaves (k_leaf_keys): the context's mode (tdv_ctx_set_ransac_leaf_order), AUTO by the call's size
+    // (ransac_cut.hpp: kRansacLeafClassesMin - on a 9,999-point cloud they take the live list from 4,317 to 4,063 hypotheses, one block
+    // of 1,024 fewer for the two-way order but not for the far and near lists together, and tests/test_gpu_ransac_far_bound.py holds
+    // the far bound strictly under the two-way order there).  The study build's TDV_RANSAC_LEAF_CLASSES overrides: 1 on, else off.
+    k.leaf_classes = ctx->ransac_leaf_order == TDV_RANSAC_LEAVES_CLASSES || (ctx->ransac_leaf_order == TDV_RANSAC_LEAVES_AUTO && ns >= kRansacLeafClassesMin);
+    if (study_env("TDV_RANSAC_LEAF_CLASSES")) k.leaf_classes = atoi(study_env("TDV_RANSAC_LEAF_CLASSES")) == 1;
     k.one_level = study_env("TDV_RANSAC_BOUND_LEVELS") && atoi(study_env("TDV_RANSAC_BOUND_LEVELS")) == 1;   // A/B knob: the fine walk alone
     k.record_copy = study_env("TDV_RANSAC_RECORD") && !strcmp(study_env("TDV_RANSAC_RECORD"), "copy");   // the record by a 32-byte copy, not by the kernel's own stores into pinned memory
     // A/B knobs (profiles/r18/ransac_no_events.md): the batch's end by an event as it was; the fast kernel's score timer by events as it was
@@ -1616,6 +1655,9 @@ static int score_grid(int hb, int ps) { return 8 * ((hb + 8 / RS_XCD_R - 1) / (8
 // multiple of 8.  Only speed depends on it: the host knows neither how many hypotheses are listed nor how long phase 1 was, and
 // the workgroups pull their units, so any grid of at least 8 drains any list.
 static int unit_grid(int cus) { return std::max(8, (2 * cus + 7) / 8 * 8); }
+// k_ransac_bound_fine's workgroups: the same count - its workgroups have 16 waves too, two per CU at 8 waves per SIMD - and for the
+// same reason: they take their units by the list's length, which the host does not know.
+static int fine_grid(int cus) { return unit_grid(cus); }
 
 // One call of ransac_run_dev: what its steps share, and the steps in the order a batch takes them.
 struct RansacRun {
@@ -1814,8 +1856,8 @@ struct RansacRun {
         else {
             k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, cleaves, n_cpairs, &d->pmax, sqrt_tau, band_u,
                                                                       d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, lj);
-            k_ransac_bound_fine<<<dim3(bgrid, k.fine_y), 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
-                                                                                  d->state, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, lj);
+            const FineJob fj{B.hyp, leaves, &d->pmax, d->state, B.und, B.n_und, B.live, B.n_live, B.acc, B.ticket, lj, h_pad, n_lpairs, k.fine_y, sqrt_tau, band_u};
+            k_ransac_bound_fine<<<fine_grid(cus), 64 * RB_SPLIT, 0, s>>>(fj);
         }
     }
     // RansacPointOrder: pq2 again from pq, the outliers of the best so far (best12, state[0]: the batches enqueued before) first
@@ -2044,7 +2086,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     if (!d_corr_in) { TDV_TRY(ws_alloc(ctx, (size_t)ns, &d_match)); TDV_TRY(feature_match_dev(ctx, d_fs, ns, d_ft, nt, d_match)); }
     const int* d_corr = d_corr_in ? d_corr_in : d_match;
     RansacRun r;
-    r.ctx = ctx; r.s = ctx->stream; r.k = ransac_knobs(ctx, trace_inliers != nullptr, max_iterations);
+    r.ctx = ctx; r.s = ctx->stream; r.k = ransac_knobs(ctx, trace_inliers != nullptr, max_iterations, ns);
     r.ns = ns; r.nt = nt; r.max_iterations = max_iterations; r.confidence = confidence; r.trace = trace_inliers;
     r.tau = tau_lt(voxel * 1.5f);  // registration.cpp:213
     // sqrt(tau) rounded up: the boundary of `d2 < tau` in distance, for the band of the fast scoring pass

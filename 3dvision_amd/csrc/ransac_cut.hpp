@@ -42,4 +42,38 @@ __host__ __device__ __forceinline__ int ransac_batch_size(int it0, int grown = k
     return it0 == 0 ? kRansacFirst : it0 < kRansacGrowAt ? kRansacBatch : grown;
 }
 
+// The leaf order of a call whose context leaves it to the library (TDV_RANSAC_LEAVES_AUTO): class-major leaves from this many pairs
+// on, Morton leaves below.  Measured (profiles/r29/ransac_leaf_classes.md): the smallest size of the table from which the class-major
+// order never lies under the Morton order's range.  It cannot go below 30,001: the suite holds the product library's Morton lists at
+// 9,999 and 30,000 pairs against the study library's class-major ones (tests/test_gpu_ransac_far_bound.py:
+// test_best_found_in_the_bounded_batch, tests/test_gpu_ransac_bound_lists.py: test_main_shorter_fine_list_same_result), and on a
+// 9,999-pair cloud the scored share counts whole blocks of 1,024 hypotheses, which a strict inequality there rests on.
+constexpr int kRansacLeafClassesMin = 50000;
+static_assert(kRansacLeafClassesMin > 30000, "the suite compares Morton lists at 30,000 pairs");
+
+// The fine level's cut (k_ransac_bound_fine, round 29).  The undecided list has nb slot blocks of 64 hypotheses, the fine leaves
+// n_lpairs pairs, the grid `grid` workgroups of RB_SPLIT waves, as many as the chip holds at once.  A unit is (slot block, one of R
+// ranges of the leaf pairs); workgroup w takes the units w, w + grid, ...  Every workgroup derives R alike from the list's length:
+// the R that makes the longest workgroup's path shortest, counted in leaf pairs a wave walks - rounds of units, each a wave's share
+// of a range plus kFineUnitCost for the unit's fixed part (the pose's loads, two barriers, the ticket).  Few slot blocks get many
+// ranges, many get one and several units per workgroup.  A wave's share stays at kFineMinWalk pairs or more while R > 1.  Only
+// speed depends on R: the verdict of a slot block is its last arrival's, whatever the cut.
+constexpr int kFineUnitCost = 6, kFineMinWalk = 8, kFineMaxRanges = 64;
+// The cost of a cut into r ranges with r in its low 7 bits: the smallest key is the cut, the fewer ranges on equal cost.  All ones:
+// no such cut.  (A key per candidate, so that the device asks its 64 lanes at once: a scalar loop over the candidates, three integer
+// divisions each, cost the kernel 19 us per launch - profiles/r29/ransac_leaf_classes.md.)
+__host__ __device__ __forceinline__ unsigned long long fine_cut_key(int r, int nb, int n_lpairs, int grid, int waves) {
+    if (r < 1 || r > kFineMaxRanges) return ~0ull;
+    const int walk = ((n_lpairs + r - 1) / r + waves - 1) / waves;
+    if (r > 1 && walk < kFineMinWalk) return ~0ull;
+    const unsigned units = (unsigned)nb * (unsigned)r, rounds = (units + (unsigned)grid - 1u) / (unsigned)grid;      // (nb <= 2^25: a list of 2^31 slots)
+    return ((unsigned long long)rounds * (unsigned)(walk + kFineUnitCost)) << 7 | (unsigned)r;
+}
+__host__ __device__ __forceinline__ int fine_ranges(int nb, int n_lpairs, int grid, int waves) {
+    if (nb <= 0 || grid <= 0) return 1;
+    unsigned long long best = ~0ull;
+    for (int r = 1; r <= kFineMaxRanges; ++r) { const unsigned long long k = fine_cut_key(r, nb, n_lpairs, grid, waves); best = k < best ? k : best; }
+    return (int)(best & 127ull);
+}
+
 }  // namespace tdv

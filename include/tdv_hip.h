@@ -146,6 +146,14 @@ int tdv_ctx_get_icp_loss(tdv_ctx* ctx, int* loss, float* scale);
                                    * matrix cores (f32 MFMA), same band scheme, same counts; measured slower than FAST.  The product
                                    * library returns TDV_ERR_BAD_ARG for it */
 int tdv_ctx_set_ransac_score(tdv_ctx* ctx, int mode);
+/* The order of the leaves that RANSAC's leaf-box bound walks (a call with bail-out and bound).  MORTON: along the pairs' Morton
+ * curve.  CLASSES: class-major - the outliers of the ordering pose first, its inliers behind them, each class along its own Morton
+ * curve; tighter leaves, a shorter fine list.  AUTO (default): CLASSES for a call with at least 50,000 pairs, MORTON below.  The
+ * order changes which hypotheses the bound proves dead before they are scored, never a result. */
+#define TDV_RANSAC_LEAVES_AUTO 0
+#define TDV_RANSAC_LEAVES_MORTON 1
+#define TDV_RANSAC_LEAVES_CLASSES 2
+int tdv_ctx_set_ransac_leaf_order(tdv_ctx* ctx, int mode);
 /* Statistics of the last tdv_ransac* call on this ctx: the fraction of the (hypothesis, point) tests the FAST pass scored a second time
  * with the reference arithmetic - whole waves of 64 hypotheses on a pair of points that one of them has inside its rounding band
  * (until round 4: on the whole 8-point chunk) - (-1 if the call ran in EXACT mode or none has run). */

@@ -9,17 +9,30 @@ With a copy trace it also prints the batch's path: every kernel of a batch in st
 the end of the kernel before it to its start, kernels only: what the compute stream waits), and per host-to-device copy its
 duration, the time from the end of the last kernel that started before it to its start, and the time from its end to the start of
 the next kernel.  Means over the bounded batches behind the first one (batches 3..n: the second builds the leaves).
-    python tools/studies/ransac_batch_split.py [--call K] <kernel_trace.csv> [<memory_copy_trace.csv>]
+    python tools/studies/ransac_batch_split.py [--call K] [--fine-list F --bounded B [--points N]] <kernel_trace.csv> [<memory_copy_trace.csv>]
 --call K: the K-th RANSAC call of the trace instead of the last, counted over the k_gather_pq launches as Python indexes a list
-(-1, the default, is the last call, -3 the third from the end; tools/studies/ransac_event_gaps.py makes four)."""
+(-1, the default, is the last call, -3 the third from the end; tools/studies/ransac_event_gaps.py makes four).
+--fine-list F --bounded B: Context.last_ransac_bound()'s counters of the same call - hypotheses put on the fine level's list, hypotheses
+bounded.  A trace holds no list lengths, and the counters are sums over the call, so a batch's list is taken as the call's share F / B
+of its size; beside k_ransac_bound_fine's time the size rows then give that length, the time per listed hypothesis and its ratio
+to the ideal: the list's leaf-pair walks (--points N pairs, default 200,000: ceil(N / 32) fine leaves, two per walk) at the rate of
+the same batches' coarse level (every hypothesis over ceil(N / 128) coarse leaves, two per walk)."""
 import collections
 import csv
 import sys
 
 argv = sys.argv[1:]
 call = -1                       # which RANSAC call of the trace, counted over its k_gather_pq launches (-1: the last)
-if argv and argv[0] == "--call":
-    call = int(argv[1]); argv = argv[2:]
+fine_total = bounded_total = 0
+points = 200000
+while argv and argv[0] in ("--call", "--fine-list", "--bounded", "--points"):
+    if argv[0] == "--call": call = int(argv[1])
+    elif argv[0] == "--fine-list": fine_total = int(argv[1])
+    elif argv[0] == "--bounded": bounded_total = int(argv[1])
+    else: points = int(argv[1])
+    argv = argv[2:]
+n_lpairs = ((points + 31) // 32 + 1) // 2          # csrc/ransac.hip: leaf_alloc
+n_cpairs = ((points + 127) // 128 + 1) // 2
 rows = []
 for f in argv:
     for r in csv.DictReader(open(f)):
@@ -76,6 +89,14 @@ if nb > 4 and any(slots):
         for k, v in per.items():
             print("    %-28s %4.1f launches/batch %9.1f us/batch %9.1f us/launch %9.1f us per 65,536" %
                   (k, len(v) / len(bs), sum(v) / len(bs) / 1e3, sum(v) / len(v) / 1e3, sum(v) / len(bs) / 1e3 * 65536.0 / max(size, 1)))
+        fine_k, coarse_k = per.get("k_ransac_bound_fine #1"), per.get("k_ransac_bound #1")
+        if fine_total and bounded_total and fine_k and coarse_k:
+            listed = size * fine_total / bounded_total               # the call's share of a batch of this size
+            fine_us, coarse_us = sum(fine_k) / len(bs) / 1e3, sum(coarse_k) / len(bs) / 1e3
+            ideal_us = listed * n_lpairs / (size * n_cpairs / coarse_us)
+            print("    fine list %.0f hypotheses per batch (%.4f of it): k_ransac_bound_fine %.1f us = %.2f ns per listed hypothesis; at the coarse level's "
+                  "%.0f walks/us the list's %d leaf pairs take %.1f us: ratio %.2f" %
+                  (listed, fine_total / bounded_total, fine_us, fine_us * 1e3 / listed, size * n_cpairs / coarse_us, n_lpairs, ideal_us, fine_us / ideal_us))
 
 
 def mean(v):
