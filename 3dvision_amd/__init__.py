@@ -46,7 +46,7 @@ DEPTH_BATCH_MASK_PASSES = 1   # the B masks cross HBM once in tdv_depth_to_cloud
 
 # every symbol include/tdv_hip.h declares (checked by the CPU test-suite against the built library)
 ABI_SYMBOLS = [
-    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_voxel_batch_redone", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_set_ransac_leaf_order", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_last_ransac_bound", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
+    "tdv_device_count", "tdv_ctx_create", "tdv_ctx_set_stream", "tdv_ctx_set_icp_search", "tdv_ctx_set_icp_accumulation", "tdv_ctx_last_icp_search", "tdv_ctx_last_batch_lanes", "tdv_ctx_last_voxel_grouping", "tdv_ctx_last_voxel_batch_redone", "tdv_ctx_last_feature_match_path", "tdv_ctx_workspace_bytes", "tdv_ctx_workspace_fill", "tdv_ctx_set_ransac_score", "tdv_ctx_set_ransac_leaf_order", "tdv_ctx_set_ransac_triples", "tdv_ctx_last_ransac_staged", "tdv_ctx_last_ransac_rescore", "tdv_ctx_last_ransac_scored", "tdv_ctx_last_ransac_bound", "tdv_ctx_get_stream", "tdv_ctx_synchronize",
     "tdv_ctx_destroy", "tdv_status_string", "tdv_last_error", "tdv_version", "tdv_timing_enable", "tdv_timing_read",
     "tdv_depth_preprocess", "tdv_deproject", "tdv_depth_to_cloud", "tdv_voxel_downsample", "tdv_estimate_normals",
     "tdv_compute_fpfh", "tdv_feature_match", "tdv_ransac", "tdv_icp", "tdv_icp_correspondences",
@@ -659,6 +659,15 @@ class Context:
         """'auto' (default: class-major leaves for a call with at least 50,000 pairs), 'morton' or 'classes': the order of the
         leaves the leaf-box bound walks; same result, other list lengths."""
         _check(self._h, lib().tdv_ctx_set_ransac_leaf_order(self._h, {"auto": 0, "morton": 1, "classes": 2}[mode]), "tdv_ctx_set_ransac_leaf_order")
+
+    def set_ransac_triples(self, mode):
+        """'auto' (default: staged wherever a call can), 'direct' or 'staged': whether a batch's hypothesis kernel reads its index
+        triples from the host's pinned memory or finds them on the device, carried there by the batch before; same results."""
+        _check(self._h, lib().tdv_ctx_set_ransac_triples(self._h, {"auto": 0, "direct": 1, "staged": 2}[mode]), "tdv_ctx_set_ransac_triples")
+
+    def last_ransac_staged(self):
+        """Batches of the last RANSAC call on this context, of those its loop reached, that ran from staged triples."""
+        return int(lib().tdv_ctx_last_ransac_staged(self._h))
 
     def last_ransac_rescore(self):
         """Fraction of the (hypothesis, point) tests the last RANSAC call scored a second time exactly (-1 in 'exact' mode)."""

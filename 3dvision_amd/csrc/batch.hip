@@ -317,7 +317,7 @@ int register_batch_dev(tdv_ctx* ctx, const uint16_t* d_raw, const uint8_t* d_bgr
         for (int l = 1; l < L; ++l) {
             tdv_ctx* h = lane_ctx[l];
             h->timing = ctx->timing; h->icp_search = ctx->icp_search; h->icp_accumulate = ctx->icp_accumulate;
-            h->icp_loss = ctx->icp_loss; h->icp_loss_scale = ctx->icp_loss_scale; h->ransac_score_mode = ctx->ransac_score_mode; h->ransac_leaf_order = ctx->ransac_leaf_order; h->err[0] = 0;
+            h->icp_loss = ctx->icp_loss; h->icp_loss_scale = ctx->icp_loss_scale; h->ransac_score_mode = ctx->ransac_score_mode; h->ransac_leaf_order = ctx->ransac_leaf_order; h->ransac_triples = ctx->ransac_triples; h->err[0] = 0;
             workers.emplace_back([&, h, l]() {
                 try {
                     if (hipSetDevice(h->device) != hipSuccess) { status[l] = TDV_ERR_NO_DEVICE; return; }

@@ -353,6 +353,13 @@ int tdv_ctx_set_ransac_leaf_order(tdv_ctx* ctx, int mode) {
     return TDV_OK;
 }
 
+int tdv_ctx_set_ransac_triples(tdv_ctx* ctx, int mode) {
+    if (!ctx || mode < TDV_RANSAC_TRIPLES_AUTO || mode > TDV_RANSAC_TRIPLES_STAGED) return TDV_ERR_BAD_ARG;
+    ctx->ransac_triples = mode;
+    return TDV_OK;
+}
+int tdv_ctx_last_ransac_staged(tdv_ctx* ctx) { return ctx ? ctx->last_ransac_staged : 0; }
+
 int tdv_ctx_set_fps_path(tdv_ctx* ctx, int mode) {
     if (!ctx || mode < TDV_FPS_AUTO || mode > TDV_FPS_GRID) return TDV_ERR_BAD_ARG;
     ctx->fps_path = mode;

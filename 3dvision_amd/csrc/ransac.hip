@@ -193,6 +193,8 @@ __device__ __forceinline__ void ransac_prejudge(const PreJob& j, const float* o,
 // up != nullptr: the batch's triples as the host drew them, in pinned host memory, which the device reads as it is (it writes a
 // batch's record there).  Lane h loads its triple from there and stores it to `triples` for the batch's later kernels (the bound, the
 // select kernels and k_ransac_finish ask triples.valid(h)): the batch needs no copy in front of this kernel.
+// up == nullptr: `triples` holds them already - carried there by the coarse bound level of the batch before (RansacStage, the
+// default from a call's third batch on), or by a copy (study build, TDV_RANSAC_UPLOAD=inline).
 // h_end: the hypothesis slots this batch covers (whole scoring blocks, the padding behind `count` as invalid lanes); h_pad is the stride.
 __global__ void k_ransac_hypotheses(const float* __restrict__ pq, const TriView triples, const void* __restrict__ up, int count, int h_end, int h_pad,
                                     float* __restrict__ hyp, const unsigned* __restrict__ pmax, float sqrt_tau, int* __restrict__ counts,
@@ -1367,14 +1369,22 @@ __device__ __forceinline__ int rb_append3(bool far, bool near, bool und, int lan
     if (und) undl[a2] = h;
     return a2;
 }
+// RansacStage (round 30).  A batch's triples are drawn by the host into pinned memory, and k_ransac_hypotheses - every lane's pose
+// hangs behind its triple - read them from there at the link's rate.  They depend on nothing the device computes, so the host
+// draws a batch further ahead and the coarse level of batch n, which is bound by its arithmetic, carries batch n + 1's triples
+// across: thread i of its grid loads word i of the pinned slot in front of the walk and stores it to batch n + 1's device buffer
+// behind it, and batch n + 1's k_ransac_hypotheses reads the device copy (up == nullptr).  The carrier is an instance of its own
+// (STAGE, cnt >= 1): a coarse level with nothing to carry - the last batch's, a call that does not stage - runs the kernel as it was.
+// Packed triples only (one word each); see RansacRun::loop for who stages and for the hazards.
+struct StageJob { const uint64_t* src; uint64_t* dst; int cnt; };
 // RB_ONE / RB_COARSE: a workgroup per 64 hypotheses of the batch.  RB_COARSE also zeroes the fine level's per-slot sums (acc) of
 // the hypotheses it leaves undecided and the ticket of its slot block.
-template <int MODE>
+template <int MODE, bool STAGE = false>
 __global__ __launch_bounds__(64 * RB_SPLIT)
 void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView triples, int count, const float* __restrict__ leaves, int n_lpairs,
                     const unsigned* __restrict__ pmax, float sqrt_tau, float band_u, const int* __restrict__ state, int ns,
                     int* __restrict__ live, int* __restrict__ n_live, int* __restrict__ und, int* __restrict__ n_und,
-                    int* __restrict__ acc, int* __restrict__ ticket, const ListJob lj) {
+                    int* __restrict__ acc, int* __restrict__ ticket, const ListJob lj, const StageJob stage) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int h = blockIdx.x * 64 + lane;
     __shared__ int s_ub[64];
@@ -1389,8 +1399,20 @@ void k_ransac_bound(const float* __restrict__ hyp, int h_pad, const TriView trip
     const bool walk = rb_gate(best, ns);
     int fl = 0;                                                   // ransac_prejudge's word, asked for in front of the walk: the tail does not wait for it
     if (wave == 0 && valid) fl = lj.flags[h];
+    // RansacStage: this thread's word of the next batch's triples, asked of the host's memory behind the pose's loads (loads return in
+    // order: in front of them it would hold the pose back for the link's latency) and stored behind the walk, which needs no vector
+    // load - the link's latency lies under the walk.  The load is every thread's, its index clamped (a thread past the count loads the
+    // last word and stores nothing): behind a branch the compiler waits for it where the branch joins, in front of the walk.
+    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
+    uint64_t sw = 0;
+    if (STAGE) sw = stage.src[min(gid, stage.cnt - 1)];
     const int per = (n_lpairs + RB_SPLIT - 1) / RB_SPLIT, k0 = __builtin_amdgcn_readfirstlane(wave) * per, k1 = min(n_lpairs, k0 + per);   // (uniform: scalar loads)
     const int ub = rb_walk(o.r, leaves, k0, k1, o.tb, best, !valid || !o.bounded || !walk);
+    if (STAGE) {
+        if (gid < stage.cnt) stage.dst[gid] = sw;
+        const int all = gridDim.x * blockDim.x;      // (a next batch larger than this one's threads: the rest of it, word by word)
+        for (int i = gid + all; i < stage.cnt; i += all) stage.dst[i] = stage.src[i];
+    }
     __syncthreads();                                 // (s_ub zeroed)
     if (ub) atomicAdd(&s_ub[lane], ub);
     __syncthreads();
@@ -1581,7 +1603,7 @@ static_assert(offsetof(RansacLive, n_und) == offsetof(RansacLive, n_live) + 2 * 
 
 // Every switch of a call, read in one place.  TDV_RANSAC_SCORE=exact and TDV_RANSAC_BAILOUT are read once per process, the rest per
 // call (the tests switch them); study_env() is a constant nullptr in the product library.
-struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far, end_event, timer_events; int drop_permille, a_permille, u_cut_permille, fine_y, grown; float far_radius, live_radius; };
+struct RansacKnobs { bool score_fast, score_mfma, bailout, bound, one_level, leaf_classes, merge, record_copy, upload_inline, order, far, end_event, timer_events; int drop_permille, a_permille, u_cut_permille, fine_y, grown, triples; float far_radius, live_radius; };
 static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterations, int ns) {
     RansacKnobs k;
     static const bool score_exact_env = getenv("TDV_RANSAC_SCORE") && !strcmp(getenv("TDV_RANSAC_SCORE"), "exact");
@@ -1625,6 +1647,11 @@ static RansacKnobs ransac_knobs(const tdv_ctx* ctx, bool traced, int max_iterati
     k.end_event = traced || k.record_copy || (study_env("TDV_RANSAC_END") && !strcmp(study_env("TDV_RANSAC_END"), "event"));   // (a traced call's counts come by a copy: it keeps the event)
     k.timer_events = study_env("TDV_RANSAC_TIMER") && !strcmp(study_env("TDV_RANSAC_TIMER"), "events");
     k.upload_inline = study_env("TDV_RANSAC_UPLOAD") && !strcmp(study_env("TDV_RANSAC_UPLOAD"), "inline");   // A/B knob: the triples by a copy on the compute stream in front of k_ransac_hypotheses, not by the kernel's own loads from pinned memory
+    // RansacStage: the context's mode (tdv_ctx_set_ransac_triples; AUTO stages wherever a call can: RansacRun::setup); the study
+    // build's TDV_RANSAC_UPLOAD=staged / =direct overrides
+    k.triples = ctx->ransac_triples;
+    if (study_env("TDV_RANSAC_UPLOAD") && !strcmp(study_env("TDV_RANSAC_UPLOAD"), "staged")) k.triples = TDV_RANSAC_TRIPLES_STAGED;
+    if (study_env("TDV_RANSAC_UPLOAD") && !strcmp(study_env("TDV_RANSAC_UPLOAD"), "direct")) k.triples = TDV_RANSAC_TRIPLES_DIRECT;
     k.drop_permille = study_env("TDV_RANSAC_DROP_PERMILLE") ? atoi(study_env("TDV_RANSAC_DROP_PERMILLE")) : 50;   // tuning knob: phase 1 over the first N - 0.95 best points (natural order: 5 to 100 measured equal;
                                                                                                                      // best's outliers first, round 12: 25, 50 and 75 above 100, profiles/r12/ransac_point_order.md)
     return k;
@@ -1639,11 +1666,13 @@ struct RansacBuf {
     int* flags;                                       // RansacBoundLists: ransac_prejudge's word per hypothesis (RB_CLOSE, RB_NEAR)
     int* units;                                       // bail-out: job B's ticket words, [far, near][2 phases][8 XCDs][slots(cnt) / RS_BLOCK] of the batch in it - unit_words(cnt) words, which its k_ransac_hypotheses zeroes (room for unit_words(cap))
     int *plan, *rec, *n_live, *n_und, *n_near;        // this buffer's fields of the RansacBlock and of RansacLive
-    void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: triples, counts (traced calls), the record
+    void* h_tri; int* h_cnt; volatile int* h_rec;     // pinned: the slot that holds the triples of the batch in this buffer (RansacRun::slot_ptr), counts (traced calls), the record
+    bool staged;                                      // RansacStage: the batch in this buffer found its triples on the device
     hipEvent_t ev;                                    // the batch's end where an event marks it (traced calls; study build: TDV_RANSAC_RECORD=copy, TDV_RANSAC_END=event)
     int seq;                                          // ... and everywhere else the sequence number that k_ransac_finish stores behind the record (h_rec[4])
 };
-struct RansacBatch { int q, cnt, it0; bool bounded; };        // buffer q holds cnt hypotheses from iteration it0 on
+struct RansacBatch { int q, cnt, it0; bool bounded, staged; };        // buffer q holds cnt hypotheses from iteration it0 on; staged: their triples are on the device already
+struct RansacDrawn { int it0, cnt, slot; };           // a batch as the host drew it: cnt triples from iteration it0 on in pinned slot `slot`
 struct RangeCut { int per, ranges; };                 // chunks per point range, point ranges
 static RangeCut range_cut(int hb, int n_pchunks) {    // of a dispatch with hb hypothesis blocks (counts are added by atomics: the cut may differ per dispatch)
     const int per = (n_pchunks + point_ranges(hb, n_pchunks) - 1) / point_ranges(hb, n_pchunks);
@@ -1672,6 +1701,11 @@ struct RansacRun {
     unsigned long long* ord_mask = nullptr; int* ord_cnt = nullptr; bool ordered = false;     // RansacPointOrder: ballot words, block counts (outliers, then F); done for this call
     unsigned* enc = nullptr;                          // RansacLeafBound: the finite coordinates' bounds per axis
     RansacBuf buf[2] = {};
+    // RansacStage: the pinned triple slots (two; three in rotation where the call stages), whether it does, the batches drawn so
+    // far and where the next one starts, and the batches the loop reached that ran from staged triples
+    char* h_slots = nullptr; size_t sz_slot = 0; int n_slots = 2; bool stage = false;
+    int n_drawn = 0, it_drawn = 0, n_staged = 0;
+    void* slot_ptr(int slot) const { return h_slots + (size_t)slot * sz_slot; }
     // TDV_TIMER_RANSAC_SCORE's stamps (score_stamp_begin): a {t0, t1} pair per dispatch of k_ransac_score_fast, nullptr with timing off
     unsigned long long *stamps = nullptr, *h_stamps = nullptr; int n_stamps = 0, stamps_used = 0;
     RansacBatch pending = {}; bool has_pending = false;       // merged dispatch (study build): the batch whose phase 2 is not enqueued yet
@@ -1736,15 +1770,22 @@ struct RansacRun {
         // free and an allocation behind a stream synchronise, and the block then moves once per context - in its first such call - and
         // not at the start of a long call that follows shorter ones.
         const size_t sz_grown = k.bailout ? 2 * align_up((size_t)k.grown * 16, 64) : 0;
-        TDV_TRY(pin_reserve(ctx, sz_blk + std::max(2 * sz_tri, sz_grown) + 2 * sz_cnt + (size_t)n_stamps * 16));
+        const size_t tri_room = std::max(2 * sz_tri, sz_grown);
+        TDV_TRY(pin_reserve(ctx, sz_blk + tri_room + 2 * sz_cnt + (size_t)n_stamps * 16));
+        // RansacStage: who stages.  A call with the bound's coarse level (its carrier: so not traced, not short, no merged dispatch,
+        // not the one-level walk), packed triples (one word per thread; int4 triples keep the direct read), and three slots inside
+        // the room reserved above - the reservation's size is what it was: three packed slots of a grown batch are 3 MB of the
+        // 4 MB a call with bail-out asks for.  Its first batch and the batch behind an unbounded one read directly all the same.
+        stage = k.triples != TDV_RANSAC_TRIPLES_DIRECT && k.bound && !k.one_level && !k.upload_inline && !trace && packed && 3 * sz_tri <= tri_room;
+        n_slots = stage ? 3 : 2; sz_slot = sz_tri; h_slots = ctx->pin + sz_blk;
         h = reinterpret_cast<RansacBlock*>(ctx->pin); h->bad = 0;
         h->rec[0][4] = h->rec[1][4] = 0;              // the sequence words: nothing of an earlier call (the stream is idle: ransac_run_dev)
-        h_stamps = reinterpret_cast<unsigned long long*>(ctx->pin + sz_blk + 2 * sz_tri + 2 * sz_cnt);
+        h_stamps = reinterpret_cast<unsigned long long*>(ctx->pin + sz_blk + tri_room + 2 * sz_cnt);      // (behind the whole room: the third slot lies past 2 x sz_tri)
         if (trace) TDV_HIP(ctx, hipMemcpyAsync(&h->bad, &d->bad, 4, hipMemcpyDeviceToHost, s));   // lands before the first batch's counts (RansacFinish: the flag comes in the record)
         for (int q = 0; q < 2; ++q) {
             RansacBuf& B = buf[q];
             B.plan = d->plan[q]; B.rec = d->rec[q]; B.n_live = lv ? &lv->n_live[q] : nullptr; B.n_und = lv ? &lv->n_und[q] : nullptr; B.n_near = lv ? &lv->n_near[q] : nullptr;
-            B.h_tri = ctx->pin + sz_blk + q * sz_tri; B.h_cnt = reinterpret_cast<int*>(ctx->pin + sz_blk + 2 * sz_tri + q * sz_cnt); B.h_rec = h->rec[q];
+            B.h_tri = slot_ptr(q); B.staged = false; B.h_cnt = reinterpret_cast<int*>(ctx->pin + sz_blk + 2 * sz_tri + q * sz_cnt); B.h_rec = h->rec[q];
         }
         if (k.end_event) {
             buf[0].ev = event_acquire(ctx); buf[1].ev = event_acquire(ctx);   // from the ctx's pool: no create/destroy per call
@@ -1799,23 +1840,28 @@ struct RansacRun {
     // ---- a batch's steps.  TDV_TIMER_RANSAC_SCORE times every dispatch of a scoring kernel on its own: k_ransac_score_fast by its
     // stamps, the others between two events.
     // host: the next cnt triples of the index stream into buffer q (i0, i1, i2, valid: registration.cpp:240)
-    int draw(TripleStream& idx, int q, int it0) {
-        const int cnt = std::min(batch_size(it0), max_iterations - it0);
-        if (packed) idx.next_batch_packed(cnt, static_cast<uint64_t*>(buf[q].h_tri));
-        else idx.next_batch(cnt, static_cast<int*>(buf[q].h_tri));
-        return cnt;
+    // The batches are drawn in the call's order, each into the next slot of the rotation; the caller has seen to it that the slot's
+    // last readers are done (loop()).
+    RansacDrawn draw(TripleStream& idx) {
+        const RansacDrawn dn{it_drawn, std::min(batch_size(it_drawn), max_iterations - it_drawn), n_drawn % n_slots};
+        if (packed) idx.next_batch_packed(dn.cnt, static_cast<uint64_t*>(slot_ptr(dn.slot)));
+        else idx.next_batch(dn.cnt, static_cast<int*>(slot_ptr(dn.slot)));
+        ++n_drawn; it_drawn += dn.cnt;
+        return dn;
     }
     // hypotheses, reading the triples where draw() put them.  The batch used to begin with a 512 KB copy of the triples on the compute
     // stream: 17 us of copy with an engine switch on either side, 36 us in which no kernel ran (profiles/r17/ransac_batch_path.md).
     // The host draws the triples into pinned memory, which the device can read, so k_ransac_hypotheses loads them from there and
     // leaves the device copy behind for the batch's later kernels.
-    //  - buf[q].h_tri is written by draw(q) and must hold still until the batch's k_ransac_hypotheses has run.  The next draw into it is
+    //  - A batch's slot is written by draw() and must hold still until the batch's k_ransac_hypotheses has run.  The next draw into it is
     //    for the batch after the next, and loop() waits for this batch's end (wait_batch) before that.  A traced call's consume_trace
     //    reads it on the host, behind the batch's event.
-    //  - After an early exit a batch that was drawn and enqueued may still read h_tri: ransac_run_dev synchronises the compute stream
+    //  - After an early exit a batch that was drawn and enqueued may still read its slot: ransac_run_dev synchronises the compute stream
     //    on every way out of loop(), before the next entry point draws into the pinned block or lets pin_reserve move it.
     //  - Traced calls and the merged dispatch (study build) read the same way; TDV_RANSAC_UPLOAD=inline (study build) is the copy on the
     //    compute stream as it was.
+    //  - A staged batch (RansacStage) does not read its slot here at all: the coarse level of the batch before it has put the triples
+    //    into B.tri, in stream order in front of this kernel, which takes them from there (up == nullptr).
     // One thread makes the batch's plan from the best count known now: full counts of the batches whose
     // phase 2 has run, the prefix counts of a pending one (a lower bound of its full counts - a bound is all the rule needs)
     int hypotheses(const RansacBatch& b) {
@@ -1824,7 +1870,7 @@ struct RansacRun {
         const PlanJob plan{d->state, k.bailout ? B.plan : nullptr, ns, n_pchunks, k.drop_permille, b.bounded ? B.n_live : nullptr, B.units, k.bailout ? unit_words(b.cnt) : 0,
                            k.far && b.bounded ? &d->far : nullptr, k.a_permille};
         const PreJob pre{b.bounded ? B.flags : nullptr, B.ubf, k.far ? &d->far : nullptr, enc, d->best12, k.live_radius, k.u_cut_permille};
-        k_ransac_hypotheses<<<(slots(b.cnt) + 255) / 256, 256, 0, s>>>(pq, tri(B), k.upload_inline ? nullptr : B.h_tri, b.cnt, slots(b.cnt), h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
+        k_ransac_hypotheses<<<(slots(b.cnt) + 255) / 256, 256, 0, s>>>(pq, tri(B), k.upload_inline || b.staged ? nullptr : B.h_tri, b.cnt, slots(b.cnt), h_pad, B.hyp, &d->pmax, sqrt_tau, B.counts, band_u, plan, pre);
         return TDV_OK;
     }
     // every test of the batch, no plan: the exact kernel, the fast one, or (study build) the matrix cores
@@ -1847,15 +1893,20 @@ struct RansacRun {
         return TDV_OK;
     }
     // RansacLeafBound: the dead hypotheses out - the batch's live list
-    void bound(const RansacBatch& b) {
+    // next != nullptr (RansacStage): the batch behind b, drawn already; the coarse level carries its triples from their pinned slot
+    // into the other buffer's tri.  That buffer held the batch before b, whose kernels - the last readers of its tri - stand in
+    // front of this one in stream order.
+    void bound(const RansacBatch& b, const RansacDrawn* next) {
         const RansacBuf& B = buf[b.q]; const int bgrid = (b.cnt + 63) / 64;
         const ListJob lj{B.flags, k.far ? B.near : nullptr, B.n_near, B.n_live + 6};
         if (k.one_level)
             k_ransac_bound<RB_ONE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, leaves, n_lpairs, &d->pmax, sqrt_tau, band_u,
-                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr, lj);
+                                                                   d->state, ns, B.live, B.n_live, nullptr, nullptr, nullptr, nullptr, lj, StageJob{nullptr, nullptr, 0});
         else {
-            k_ransac_bound<RB_COARSE><<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, cleaves, n_cpairs, &d->pmax, sqrt_tau, band_u,
-                                                                      d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, lj);
+            const StageJob sj = next ? StageJob{static_cast<const uint64_t*>(slot_ptr(next->slot)), static_cast<uint64_t*>(buf[b.q ^ 1].tri), next->cnt} : StageJob{nullptr, nullptr, 0};
+            const auto kernel = next && next->cnt > 0 ? k_ransac_bound<RB_COARSE, true> : k_ransac_bound<RB_COARSE, false>;
+            kernel<<<bgrid, 64 * RB_SPLIT, 0, s>>>(B.hyp, h_pad, tri(B), b.cnt, cleaves, n_cpairs, &d->pmax, sqrt_tau, band_u,
+                                                   d->state, ns, B.live, B.n_live, B.und, B.n_und, B.acc, B.ticket, lj, sj);
             const FineJob fj{B.hyp, leaves, &d->pmax, d->state, B.und, B.n_und, B.live, B.n_live, B.acc, B.ticket, lj, h_pad, n_lpairs, k.fine_y, sqrt_tau, band_u};
             k_ransac_bound_fine<<<fine_grid(cus), 64 * RB_SPLIT, 0, s>>>(fj);
         }
@@ -1965,8 +2016,12 @@ struct RansacRun {
     int finish_pending() { has_pending = false; TDV_TRY(phase2(pending)); return finish(pending, true); }
 
     // ---- the device side of one batch: the four paths
-    int enqueue(int q, int cnt, int it0) {
-        const RansacBatch b{q, cnt, it0, k.bound && it0 != 0};
+    // dn: the batch, drawn; staged: the batch before it has carried its triples to the device; next: the batch behind it, drawn
+    // already, for this batch's coarse level to carry (nullptr: none, or not staged)
+    int enqueue(int q, const RansacDrawn& dn, bool staged, const RansacDrawn* next) {
+        const int cnt = dn.cnt, it0 = dn.it0;
+        buf[q].h_tri = slot_ptr(dn.slot); buf[q].staged = staged;
+        const RansacBatch b{q, cnt, it0, k.bound && it0 != 0, staged};
         // RansacPointOrder, once per call: the first batch has set a best, nothing reads pq2 in between (in front of the batch's
         // k_ransac_hypotheses, whose plan reads the class sizes)
         if (k.order && it0 != 0 && !ordered) point_order();
@@ -1974,7 +2029,7 @@ struct RansacRun {
         TDV_TRY(hypotheses(b));
         if (!k.bailout) { TDV_TRY(score_all(b)); return finish(b, false); }   // exact, traced, short or matrix-core calls: every test is scored
         if (k.merge) return enqueue_merged(b);
-        if (b.bounded) bound(b);                             // bail-out with bound: phase 1 over the live list only
+        if (b.bounded) bound(b, next);                       // bail-out with bound: phase 1 over the live list only
         phase1(b);
         TDV_TRY(select(b));
         TDV_TRY(phase2(b));
@@ -2007,22 +2062,42 @@ struct RansacRun {
             TDV_HIP(ctx, hipMemcpy2DAsync(d->best12, 4, B.hyp + batch_best, (size_t)h_pad * 4, 4, 12, hipMemcpyDeviceToDevice, s));
         return TDV_OK;
     }
+    // RansacStage, the host's side.  Where the call stages, the coarse level of a bounded batch n carries batch n + 1's triples to
+    // the device, so batch n + 1 is drawn before batch n is enqueued: the host draws two batches ahead of the one it waits for,
+    // into three pinned slots in rotation.
+    //  - The slot is fully drawn before the kernel that reads it is enqueued: draw() is host code that has returned.
+    //  - Batch m is drawn into slot m mod 3 in front of enqueue(m - 1), which follows wait_batch(m - 3).  The slot's last readers
+    //    - batch m - 3's own k_ransac_hypotheses, or batch m - 4's coarse level - ran in front of batch m - 3's record.
+    //  - The device buffer that batch n's coarse level writes was batch n - 1's: stream order protects it (bound()).
+    //  - An early stop leaves a batch drawn and perhaps staged that never runs: the staging kernel may still be reading the slot
+    //    when loop() returns, and ransac_run_dev's synchronise on every way out covers it as it covers a speculative batch.
+    //  - Nothing of this survives the call: slots, counters and flags are RansacRun's, a call's first batch is never staged.
+    // A batch is staged iff the call stages and the batch before it is bounded: not the first (it0 == 0), and not the second, which
+    // stands behind the unbounded first.
+    int enqueue_next(TripleStream& idx, int q, const RansacDrawn& dn, bool staged, RansacDrawn& ahead, bool& has_ahead) {
+        has_ahead = stage && k.bound && dn.it0 != 0 && dn.it0 + dn.cnt < max_iterations;
+        if (has_ahead) ahead = draw(idx);
+        return enqueue(q, dn, staged, has_ahead ? &ahead : nullptr);
+    }
     int loop(uint32_t seed) {
         TripleStream idx(seed, (uint64_t)ns);   // sequential over the whole run (registration.cpp:235-239)
-        int cur = 0, it0 = 0, cnt_cur = draw(idx, cur, it0);
-        TDV_TRY(enqueue(cur, cnt_cur, 0));
-        while (cnt_cur > 0 && !stop) {
-            const int nxt = cur ^ 1, it_next = it0 + cnt_cur; int cnt_next = 0;
+        int cur = 0;
+        RansacDrawn dc = draw(idx), ahead = {}; bool has_ahead = false;
+        TDV_TRY(enqueue_next(idx, cur, dc, false, ahead, has_ahead));
+        while (dc.cnt > 0 && !stop) {
+            const int nxt = cur ^ 1, it_next = dc.it0 + dc.cnt; RansacDrawn dn = {it_next, 0, 0};
             if (it_next < max_iterations) {             // overlap: draw and enqueue the next batch behind the current one
-                cnt_next = draw(idx, nxt, it_next);
-                TDV_TRY(enqueue(nxt, cnt_next, it_next));
+                const bool staged = has_ahead;          // (drawn when the current batch was enqueued, and carried by its coarse level)
+                dn = staged ? ahead : draw(idx);
+                TDV_TRY(enqueue_next(idx, nxt, dn, staged, ahead, has_ahead));
             } else if (has_pending) TDV_TRY(finish_pending());      // (merged dispatch) the last batch's phase 2 runs alone
             const RansacBuf& B = buf[cur];
             TDV_TRY(wait_batch(B));
             if (trace ? h->bad : B.h_rec[3]) { std::snprintf(ctx->err, sizeof(ctx->err), "ransac: a correspondence index lies outside [0, %d)", nt); return TDV_ERR_BAD_ARG; }
-            if (trace) TDV_TRY(consume_trace(B, it0, cnt_cur));
-            else consume_record(B, it0, cnt_cur);
-            cur = nxt; it0 = it_next; cnt_cur = cnt_next;
+            if (trace) TDV_TRY(consume_trace(B, dc.it0, dc.cnt));
+            else consume_record(B, dc.it0, dc.cnt);
+            n_staged += B.staged ? 1 : 0;
+            cur = nxt; dc = dn;
         }
         return TDV_OK;
     }
@@ -2097,6 +2172,7 @@ int ransac_run_dev(tdv_ctx* ctx, const float* d_src, int ns, const float* d_tgt,
     (void)hipStreamSynchronize(r.s);   // a speculative batch may still be in flight after an early exit
     ctx->last_ransac_rescore = -1.0; ctx->last_ransac_scored = 1.0;
     for (long long& v : ctx->last_ransac_bound) v = 0;
+    ctx->last_ransac_staged = r.n_staged;
     r.release_events();
     return status != TDV_OK ? status : r.result(out);
 }

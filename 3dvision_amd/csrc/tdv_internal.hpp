@@ -41,6 +41,8 @@ struct tdv_ctx {
     int icp_loss = 0;        // TDV_ICP_LOSS_L2 / _HUBER / _TUKEY / _CAUCHY (tdv_ctx_set_icp_loss)
     float icp_loss_scale = 0.f;   // its scale k (0 with L2)
     int ransac_leaf_order = 0;    // TDV_RANSAC_LEAVES_AUTO (class-major from kRansacLeafClassesMin pairs on) / _MORTON / _CLASSES (tdv_ctx_set_ransac_leaf_order)
+    int ransac_triples = 0;       // TDV_RANSAC_TRIPLES_AUTO (staged wherever a call can: ransac.hip, RansacStage) / _DIRECT / _STAGED (tdv_ctx_set_ransac_triples)
+    int last_ransac_staged = 0;   // batches of the last RANSAC call that ran from staged triples (tdv_ctx_last_ransac_staged)
     int ransac_score_mode = 0;   // TDV_RANSAC_SCORE_FAST (FMA pass + exact band) / _EXACT (the reference arithmetic only) / _MATRIX (tdv_ctx_set_ransac_score)
     double last_ransac_rescore = -1.0;   // fraction of (wave, 8-point chunk) pairs of the last RANSAC call that the fast pass scored again exactly (-1: exact mode)
     long long last_ransac_bound[4] = {0, 0, 0, 0};   // the leaf-box bound's lists in the last RANSAC call: hypotheses bounded, close, on the fine list, live

@@ -154,6 +154,18 @@ int tdv_ctx_set_ransac_score(tdv_ctx* ctx, int mode);
 #define TDV_RANSAC_LEAVES_MORTON 1
 #define TDV_RANSAC_LEAVES_CLASSES 2
 int tdv_ctx_set_ransac_leaf_order(tdv_ctx* ctx, int mode);
+/* How a RANSAC batch's index triples, which the host draws into pinned memory, reach the device.  DIRECT: the batch's hypothesis
+ * kernel reads them from the host's memory.  STAGED: the host draws a batch further ahead and the leaf-box bound's coarse level of
+ * the batch before carries them to the device while it walks, so the hypothesis kernel finds them there - in a call with bail-out
+ * and bound (more than 16,384 iterations, no trace) whose triples pack into one word (at most 2^21 pairs), for every batch behind
+ * the second; every other batch and call reads directly whatever the mode.  AUTO (default): STAGED.  Same results either way.
+ * tdv_ctx_last_ransac_staged: how many batches of the last tdv_ransac* call on this ctx, of those its loop reached, ran from staged
+ * triples (0 before any). */
+#define TDV_RANSAC_TRIPLES_AUTO 0
+#define TDV_RANSAC_TRIPLES_DIRECT 1
+#define TDV_RANSAC_TRIPLES_STAGED 2
+int tdv_ctx_set_ransac_triples(tdv_ctx* ctx, int mode);
+int tdv_ctx_last_ransac_staged(tdv_ctx* ctx);
 /* Statistics of the last tdv_ransac* call on this ctx: the fraction of the (hypothesis, point) tests the FAST pass scored a second time
  * with the reference arithmetic - whole waves of 64 hypotheses on a pair of points that one of them has inside its rounding band
  * (until round 4: on the whole 8-point chunk) - (-1 if the call ran in EXACT mode or none has run). */
