@@ -72,6 +72,8 @@ ABI_SYMBOLS = [
     "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
     "tdv_tsdf_default_params", "tdv_tsdf_volume_bytes", "tdv_tsdf_reset_dev", "tdv_tsdf_integrate_dev", "tdv_tsdf_extract_dev", "tdv_tsdf_fuse",
     "tdv_tsdf_extract_mesh_dev", "tdv_tsdf_fuse_mesh",
+    "tdv_odometry_default_params", "tdv_depth_maps_dev", "tdv_depth_maps", "tdv_depth_odometry_terms_dev", "tdv_depth_odometry_dev",
+    "tdv_depth_odometry", "tdv_depth_odometry_sequence_dev",
     "tdv_voxel_downsample_normals", "tdv_voxel_downsample_normals_dev",
     "tdv_icp_level_default", "tdv_icp_multiscale", "tdv_icp_multiscale_dev", "tdv_icp_multiscale_batch_dev",
 ]
@@ -373,6 +375,39 @@ def tsdf_volume_struct(origin, voxel_length, dims):
     return TsdfVolumeC((C.c_float * 3)(*[float(x) for x in o]), float(np.float32(voxel_length)), int(dims[0]), int(dims[1]), int(dims[2]))
 
 
+TDV_ODOM_MAX_LEVELS = 4
+ODOM_TERMS = 29   # O7's sums: 1, d2, 21 + 6
+
+
+class OdometryParamsC(C.Structure):
+    _fields_ = [("depth_diff", C.c_float), ("zmax", C.c_float), ("n_levels", C.c_int), ("max_iterations", C.c_int * TDV_ODOM_MAX_LEVELS)]
+
+
+class OdometryResultC(C.Structure):
+    _fields_ = [("T", C.c_float * 16), ("fitness", C.c_float), ("rmse", C.c_float), ("n_corr", C.c_int),
+                ("iterations", C.c_int * TDV_ODOM_MAX_LEVELS), ("n_corr_level", C.c_int * TDV_ODOM_MAX_LEVELS)]
+
+
+def odometry_params(**kw):
+    """tdv_odometry_default_params (depth_diff 0.03 m, zmax 10 m, 3 levels, 20 / 10 / 5 / 0 iterations on levels 0 to 3) with the given
+    fields replaced; max_iterations as a sequence of up to TDV_ODOM_MAX_LEVELS ints, level 0 first (the rest 0)."""
+    kw = dict(kw)
+    its = kw.pop("max_iterations", None)
+    p = _params("odometry", kw)
+    if its is not None:
+        its = [int(x) for x in its]
+        if len(its) > TDV_ODOM_MAX_LEVELS:
+            raise ValueError("max_iterations: at most TDV_ODOM_MAX_LEVELS entries")
+        p.max_iterations = (C.c_int * TDV_ODOM_MAX_LEVELS)(*(its + [0] * (TDV_ODOM_MAX_LEVELS - len(its))))
+    return p
+
+
+def _odometry_result(r):
+    """A tdv_odometry_result as a dict: T row-major [4, 4], fitness and rmse as float32, the per-level lists."""
+    return dict(T=from_colmajor16(r.T), fitness=np.float32(r.fitness), rmse=np.float32(r.rmse), n_corr=int(r.n_corr),
+                iterations=list(r.iterations), n_corr_level=list(r.n_corr_level))
+
+
 def mesh_compact(vertices, normals, triangles):
     """The mesh without the vertices no triangle refers to: the kept rows in their order, the triangles renumbered (numpy, on the host)."""
     triangles = np.asarray(triangles, np.int32).reshape(-1, 3)
@@ -439,6 +474,7 @@ _PARAMS = {
     "mesh_sample": (MeshSampleParamsC, "tdv_mesh_sample_default_params", "mesh sampling", None),
     "ppf": (PpfParamsC, "tdv_ppf_default_params", "PPF", None),
     "tsdf": (TsdfParamsC, "tdv_tsdf_default_params", "TSDF", dict(pose_direction=POSE_DIRECTION)),
+    "odometry": (OdometryParamsC, "tdv_odometry_default_params", "odometry", None),
 }
 
 _lib = None
@@ -1691,6 +1727,104 @@ class Context:
         if nv:
             call(xyz, nrm, nv, tri if nt else None, nt)
         return mesh_compact(xyz, nrm, tri) if compact else (xyz, nrm, tri)
+
+    # ---------------------------------------------------------------- depth odometry (include/tdv_hip.h: tdv_depth_odometry_dev)
+    odometry_params = staticmethod(odometry_params)
+
+    @staticmethod
+    def _cam(scale, fx, fy, cx, cy):
+        return C.c_float(scale), C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy)
+
+    def depth_maps_dev(self, d_raw, w, h, scale, fx, fy, cx, cy, d_vertex_map=None, d_normal_map=None, d_out_xyz=None, d_out_normals=None,
+                       capacity=0, want_count=True, **params):
+        """tdv_depth_maps_dev: the vertex and normal maps (device, w*h*3 floats each) of the frame d_raw (uint16[h, w] on the device) and the
+        rows of the pixels that have a normal into d_out_xyz / d_out_normals (capacity rows); every output optional.  Returns (n, fits): n
+        rows were written, or, fits False, n rows are needed and nothing was written; (None, True) with want_count=False (no read-back)."""
+        n = C.c_int(-1)
+        st = lib().tdv_depth_maps_dev(self._h, _ptr(d_raw), int(w), int(h), *self._cam(scale, fx, fy, cx, cy), C.byref(odometry_params(**params)),
+                                      _ptr(d_vertex_map), _ptr(d_normal_map), _ptr(d_out_xyz), _ptr(d_out_normals), int(capacity),
+                                      C.byref(n) if want_count else None)
+        if want_count and st == -2 and n.value > int(capacity) >= 0:
+            return n.value, False
+        _check(self._h, st, "tdv_depth_maps_dev")
+        return (n.value if want_count else None), True
+
+    def depth_maps(self, frame, intrinsics, **params):
+        """tdv_depth_maps on a host frame (uint16[h, w]), intrinsics = (scale, fx, fy, cx, cy): dict(vertex_map float32[h, w, 3], normal_map
+        float32[h, w, 3], xyz float32[n, 3], normals float32[n, 3]) - the maps and, in pixel order, the rows of the pixels with a normal.
+        The first call asks for the count, the second brings everything."""
+        frame = np.ascontiguousarray(frame, np.uint16)
+        h, w = frame.shape
+        p = odometry_params(**params)
+
+        def call(vm, nm, xyz, nrm, capacity):
+            n = C.c_int(-1)
+            st = lib().tdv_depth_maps(self._h, _ptr(frame), w, h, *self._cam(*intrinsics), C.byref(p), _ptr(vm), _ptr(nm), _ptr(xyz), _ptr(nrm),
+                                      capacity, C.byref(n))
+            if not (st == -2 and n.value > capacity):
+                _check(self._h, st, "tdv_depth_maps")
+            return n.value
+
+        n = call(None, None, None, None, 0)
+        out = dict(vertex_map=np.zeros((h, w, 3), np.float32), normal_map=np.zeros((h, w, 3), np.float32), xyz=np.zeros((n, 3), np.float32),
+                   normals=np.zeros((n, 3), np.float32))
+        call(out["vertex_map"], out["normal_map"], out["xyz"] if n else None, out["normals"] if n else None, n)
+        return out
+
+    def depth_odometry_terms_dev(self, d_raw_src, d_raw_tgt, w, h, scale, fx, fy, cx, cy, T, level, **params):
+        """tdv_depth_odometry_terms_dev: (float64[29], n_valid_src) - O7's sums for the pose T ([4, 4] row-major) at one level."""
+        sums = np.zeros(ODOM_TERMS, np.float64)
+        n = C.c_int(-1)
+        _check(self._h, lib().tdv_depth_odometry_terms_dev(self._h, _ptr(d_raw_src), _ptr(d_raw_tgt), int(w), int(h), *self._cam(scale, fx, fy, cx, cy),
+                                                           _ptr(to_colmajor16(T)), int(level), C.byref(odometry_params(**params)), _ptr(sums),
+                                                           C.byref(n)), "tdv_depth_odometry_terms_dev")
+        return sums, n.value
+
+    def depth_odometry_dev(self, d_raw_src, d_raw_tgt, w, h, scale, fx, fy, cx, cy, T0=None, **params):
+        """tdv_depth_odometry_dev: the motion that takes the source frame's camera coordinates to the target frame's, from T0 ([4, 4]
+        row-major, None: the identity), as _odometry_result's dict."""
+        r = OdometryResultC()
+        _check(self._h, lib().tdv_depth_odometry_dev(self._h, _ptr(d_raw_src), _ptr(d_raw_tgt), int(w), int(h), *self._cam(scale, fx, fy, cx, cy),
+                                                     None if T0 is None else _ptr(to_colmajor16(T0)), C.byref(odometry_params(**params)),
+                                                     C.byref(r)), "tdv_depth_odometry_dev")
+        return _odometry_result(r)
+
+    def depth_odometry(self, src, tgt, intrinsics, T0=None, **params):
+        """tdv_depth_odometry on host frames (uint16[h, w] each), intrinsics = (scale, fx, fy, cx, cy)."""
+        src, tgt = np.ascontiguousarray(src, np.uint16), np.ascontiguousarray(tgt, np.uint16)
+        if src.shape != tgt.shape or src.ndim != 2:
+            raise ValueError("tdv_depth_odometry: two frames of one size")
+        r = OdometryResultC()
+        _check(self._h, lib().tdv_depth_odometry(self._h, _ptr(src), _ptr(tgt), src.shape[1], src.shape[0], *self._cam(*intrinsics),
+                                                 None if T0 is None else _ptr(to_colmajor16(T0)), C.byref(odometry_params(**params)), C.byref(r)),
+               "tdv_depth_odometry")
+        return _odometry_result(r)
+
+    def depth_odometry_sequence_dev(self, d_raw, n_frames, w, h, scale, fx, fy, cx, cy, init=None, **params):
+        """tdv_depth_odometry_sequence_dev: frames d_raw (uint16[n, h, w] on the device), init ([n, 4, 4] row-major start poses of the pairs,
+        entry 0 unused, or None).  Returns (poses float32[n, 4, 4] row-major - camera k in camera 0's frame, what tsdf_integrate_dev takes
+        with pose_direction='source_onto_target' - and the pairs' results, entry 0 zeros)."""
+        n = int(n_frames)
+        t0 = None
+        if init is not None:
+            t0, m = _poses16(init)
+            if m != n:
+                raise ValueError("tdv_depth_odometry_sequence_dev: one start pose per frame")
+        poses = np.zeros((max(n, 1), 16), np.float32)
+        pairs = (OdometryResultC * max(n, 1))()
+        _check(self._h, lib().tdv_depth_odometry_sequence_dev(self._h, _ptr(d_raw), n, int(w), int(h), *self._cam(scale, fx, fy, cx, cy), _ptr(t0),
+                                                              C.byref(odometry_params(**params)), _ptr(poses), pairs),
+               "tdv_depth_odometry_sequence_dev")
+        return poses[:n].reshape(n, 4, 4).transpose(0, 2, 1).copy(), [_odometry_result(pairs[k]) for k in range(n)]
+
+    def depth_odometry_sequence(self, frames, intrinsics, init=None, **params):
+        """depth_odometry_sequence_dev on host frames (uint16[n, h, w])."""
+        import torch
+        frames = np.array(frames, np.uint16)                     # (a copy: torch wants a writable array)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        d_raw = torch.from_numpy(frames.view(np.int16) if frames.size else np.zeros((1, 1, 1), np.int16)).to(torch.device("cuda", self.device))
+        torch.cuda.synchronize()
+        return self.depth_odometry_sequence_dev(d_raw.data_ptr(), len(frames), frames.shape[2], frames.shape[1], *intrinsics, init=init, **params)
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

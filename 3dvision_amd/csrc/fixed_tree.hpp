@@ -1,6 +1,6 @@
 // The fixed f64 summation tree of include/tdv_hip.h (tdv_remove_statistical_outlier, rule 4; tdv_segment_planes; tdv_fgr's means), shared
 // by the kernels that sum f64 terms per point of a cloud in index order: outlier.hip (cloud_mean, std_dev), iss.hip (the cloud's
-// resolution), plane.hip (the inlier sums) and fgr.hip (the clouds' means, first level).  The term of point i belongs to workgroup
+// resolution), plane.hip (the inlier sums), fgr.hip (the clouds' means, first level) and odometry.hip (O7's 29 sums).  The term of point i belongs to workgroup
 // i / 256, thread i % 256; a workgroup sum is the shuffle tree over each wave, then (w0 + w1) + (w2 + w3); one workgroup then adds the
 // workgroup sums t, t + 256, ... into thread t and sums its 256 threads the same way.  One order, so two calls give the same bits.
 // Device code for workgroups of 256 threads, compiled without contraction (the library's -ffp-contract=off).
@@ -24,6 +24,23 @@ __device__ __forceinline__ double tree_block_sum(double v, double* lds4) {
     if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = v;
     __syncthreads();
     return (lds4[0] + lds4[1]) + (lds4[2] + lds4[3]);
+}
+
+// NV sums at once, each in tree_block_sum's order: the shuffles of all NV, then one trip through LDS (lds: 4 * NV doubles) instead of
+// NV; sum k is returned in thread k (k < NV), the other threads get +0.0
+template <int NV>
+__device__ __forceinline__ double tree_block_sums(double* v, double* lds) {
+#pragma unroll
+    for (int k = 0; k < NV; ++k)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) v[k] += __shfl_down(v[k], off, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0)
+#pragma unroll
+        for (int k = 0; k < NV; ++k) lds[(threadIdx.x >> 6) * NV + k] = v[k];
+    __syncthreads();
+    const int t = threadIdx.x;
+    return t < NV ? (lds[t] + lds[NV + t]) + (lds[2 * NV + t] + lds[3 * NV + t]) : 0.0;
 }
 
 // the largest of a workgroup's 256 values (order-free; fmax: a NaN never wins); valid in thread 0

@@ -49,10 +49,11 @@ __device__ __forceinline__ Pose16 load_pose(const float* __restrict__ poses, int
 
 // rules 1 to 3 of include/tdv_hip.h, as written there.  SUB 1: the splat's pixel (u, v) = floorf(uf + 0.5f); SUB 16: the mesh's snapped
 // position of rule M1, floorf(uf * 16.0f + 0.5f)
+// (xc, yc, zc): the point in camera coordinates (rule 1), for a caller that goes on with it (odometry.hip)
 template <int SUB>
-__device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& zc) {
+__device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& xc,
+                                               float& yc, float& zc) {
     const float* T = P.T;
-    float xc, yc;
     if (c.direction == TDV_POSE_SOURCE_ONTO_TARGET) {
         const float d0 = m0 - T[12], d1 = m1 - T[13], d2 = m2 - T[14];
         xc = (T[0] * d0 + T[1] * d1) + T[2] * d2;
@@ -74,6 +75,11 @@ __device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam&
         v = (int)floorf(vf * (float)SUB + 0.5f);
     }
     return true;
+}
+template <int SUB>
+__device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& zc) {
+    float xc, yc;
+    return verify_project<SUB>(P, c, m0, m1, m2, u, v, xc, yc, zc);
 }
 
 // tile t of the list: its pose and the tile's pixels inside the frame, [x0, xe] x [y0, ye] (every lane alike)

@@ -1302,6 +1302,105 @@ int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t*
                        float fx, float fy, float cx, float cy, const float* poses, const tdv_tsdf_params* params, float* out_vertices,
                        float* out_normals /* optional */, int vertex_capacity, int* n_vertices, int* out_triangles, int triangle_capacity,
                        int* n_triangles);
+/* Depth odometry (KinectFusion's tracking step, Newcombe et al. 2011; Open3D's compute_odometry_result_point_to_plane): the camera's
+ * motion between two raw depth frames of one sensor, on the device - the piece between "scan" and "fuse".  Two frames need no search
+ * structure: the pixel grid gives a vertex its neighbours, so a normal is one cross product, and the projection gives a source pixel its
+ * partner, so an iteration is one gather per pixel.  The terms, the solver and the update are point-to-plane ICP's own (tdv_icp).
+ * All arithmetic is f32, one rounding per operation, no contraction, the order exactly as written (sqrtf and / correctly rounded); the
+ * exceptions are the f64 sums of O7 and the pose chain of O9.  Every output is fixed bit for bit whatever order the device works in.
+ *  O1. Level 0 depth: z = float(raw) * float(1.0 / scale), rule 5 of tdv_verify_poses.  Valid iff raw != 0 && z <= zmax.  An invalid
+ *      pixel holds 0.0f (a valid one is > 0).
+ *  O2. Vertex of a valid pixel (u, v) at depth z: tdv_deproject's rule, x = (((float)u - cx) * z) / fx, y = (((float)v - cy) * z) / fy, z.
+ *  O3. Normal at (u, v).  Present iff u + 1 < w and v + 1 < h, the depths at (u, v), (u+1, v) and (u, v+1) are valid, and
+ *      fabsf(z(u+1, v) - z(u, v)) <= depth_diff and fabsf(z(u, v+1) - z(u, v)) <= depth_diff.  With a = V(u+1, v) - V(u, v) and
+ *      b = V(u, v+1) - V(u, v) per component, n = b x a = (b1*a2 - b2*a1, b2*a0 - b0*a2, b0*a1 - b1*a0),
+ *      L = sqrtf((n0*n0 + n1*n1) + n2*n2), and the row is n / L per component.  Absent where L is zero or not finite; an absent normal
+ *      is (0, 0, 0).  A front-on plane gives (0, 0, -1): towards the camera, the side T8's normals point to.
+ *  O4. Pyramid.  Level l+1 has (w/2) x (h/2) pixels (integer division).  Pixel (u, v) of it takes the pixels (2u, 2v), (2u+1, 2v),
+ *      (2u, 2v+1), (2u+1, 2v+1) of level l in that order: z0 is the first valid one, the members are the valid ones with
+ *      fabsf(z - z0) <= depth_diff, and z' is their f32 sum in that order divided by (float)count, or 0.0f if none is valid.
+ *      Intrinsics: fx' = fx*0.5f, fy' = fy*0.5f, cx' = (cx - 0.5f)*0.5f, cy' = (cy - 0.5f)*0.5f (a pixel's centre is its integer
+ *      coordinate, as u = floorf(uf + 0.5f) says).  O2 and O3 hold on every level with the level's depth and intrinsics.
+ *  O5. Association.  The pose T (column-major) takes source-camera coordinates to target-camera coordinates: Open3D's source-to-target
+ *      convention.  A source pixel with a valid vertex p has a partner iff: q = T p by rule 1 of tdv_verify_poses in its
+ *      TDV_POSE_MODEL_TO_CAMERA form; q is usable by rules 2 and 3 (zmax is params->zmax, the intrinsics the level's); its pixel
+ *      (u, v) lies inside the target frame; the target has a normal nt there (O3), with vertex pt (O2); fabsf(pt_z - q_z) <= depth_diff.
+ *  O6. Terms: exactly point-to-plane ICP's record with the transformed point q, the target point pt and the normal nt:
+ *      J = (q x nt, nt) = (qy*n2 - qz*n1, qz*n0 - qx*n2, qx*n1 - qy*n0, n0, n1, n2); e = q - pt per component; r = ex*n0 + (ey*n1 + ez*n2);
+ *      d2 = ex*ex + (ey*ey + ez*ez), as tdv_icp_correspondences' squared distance.  The 29 terms are
+ *      {1, d2, 21 x (double)(J[a]*J[b]) for a <= b in row order, 6 x (double)(J[a]*r)}, each product formed in f32 and widened.
+ *  O7. Sums.  Each of the 29 sums goes over the fixed f64 tree (tdv_remove_statistical_outlier, rule 4) in source-pixel index
+ *      i = v*w + u of the level, 256 per workgroup; a pixel without a partner contributes +0.0 to each.
+ *  O8. Iteration and level.  One iteration is point-to-plane ICP's on those sums: n_corr = the first sum; n_corr < 3 ends the level
+ *      and keeps the pose; else the 6 x 6 system (the 21 sums rounded to f32, symmetric) is solved for x against minus the 6 sums
+ *      rounded to f32 by the pivoted LDL^T, delta = (Rx(x0) Ry(x1) Rz(x2), x3..5), T' = delta * T (k ascending);
+ *      rmse = sqrtf((float)sum_d2 / (float)n_corr); fitness = (float)n_corr / (float)(the level's count of valid source pixels).  The
+ *      level ends after an iteration with iter > 0 && fabsf(prev_rmse - rmse) < 1e-6f, or after max_iterations[l].  Levels run from
+ *      the coarsest, n_levels - 1, to 0; each restarts the iteration state, T is carried.  max_iterations[l] == 0 skips the level.
+ *  O9. Sequence.  Frames 0 .. n-1; pair k has source k, target k-1 and start h_init[k] (or the identity).  P_0 = I and
+ *      P_k = P_(k-1) * T_k, formed on the host: each entry the f64 sum of four f64 products in index order, rounded once to f32.  P_k is
+ *      camera k's pose in camera 0's frame: TDV_POSE_SOURCE_ONTO_TARGET for tdv_tsdf_integrate_dev with the volume in camera 0's frame.
+ * tdv_depth_maps_dev: O1 to O3 of one frame at level 0.  Every output is optional.  d_vertex_map and d_normal_map are width*height*3
+ * floats, zeros at invalid pixels resp. absent normals.  d_out_xyz and d_out_normals receive, in pixel order, the rows of the pixels
+ * that have a normal - a cloud with normals and no neighbour search; they need n_out, which bounds them.  Count and capacity as
+ * tdv_tsdf_extract_dev: capacity = the room in rows, NULL rows with capacity 0 are a query, and a capacity that is too small returns
+ * TDV_ERR_BAD_ARG with *n_out set to the needed count and nothing written, the maps included.  One read-back, and only when n_out is
+ * asked for.  tdv_depth_maps is its host form.  Of params it uses depth_diff and zmax (the others are checked all the same).
+ * tdv_depth_odometry_terms_dev: the 29 sums of O7 for the pose h_T at one level and that level's count of valid source pixels
+ * (optional), exposed for parity tests as tdv_icp_correspondences is.
+ * tdv_depth_odometry_dev: O8 from h_T0 (NULL: the identity).  The frames are device pointers, the pose and the result on the host; one
+ * read-back.  The result holds T, then fitness, rmse and n_corr of the last level that applied an iteration (zeros if none did), and
+ * per level the iterations applied and the correspondences of its last applied iteration.  tdv_depth_odometry is its host form.
+ * tdv_depth_odometry_sequence_dev: d_raw holds n_frames images back to back; h_init (optional, n_frames x 16, entry 0 unused), h_poses
+ * (n_frames x 16) and h_pairs (optional, n_frames results, entry 0 zeros) on the host.  Per pair the result is, byte for byte, what
+ * tdv_depth_odometry_dev returns for that pair on the same ctx.  Each frame's pyramid is built once, all pairs iterate together - the
+ * launches of an iteration cover every pair still running - and the states come down once.
+ * Kernels (csrc/odometry.hip): one launch per iteration; per workgroup of 256 pixels one row of partial sums; the workgroup that takes
+ * the pair's last ticket folds the rows in O7's order and applies the update, so the next launch reads the new pose with no host round
+ * trip.  No float atomics.  The workspace keeps 16 bytes per pixel and level (depth and normal; vertices are recomputed, O2 gives the
+ * same bits): about 21 bytes per pixel of a frame at three levels.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: a NULL ctx, params, frames (width*height > 0), pose (terms), sums or result;
+ * rows without n_out, or capacity > 0 with both row pointers NULL; width or height < 0 or > TDV_VERIFY_MAX_SIDE; scale, fx or fy <= 0 or
+ * non-finite; depth_diff or zmax <= 0 or non-finite; n_levels outside [1, TDV_ODOM_MAX_LEVELS] or so many that a level would have a side
+ * of 0; a negative max_iterations; level outside [0, n_levels); n_frames < 0 or > TDV_TSDF_MAX_FRAMES; capacity < 0.  Valid, and
+ * returning the start pose with zeros: width*height == 0, n_frames of 0 or 1, a frame with no valid pixel.  NaN or infinite entries of a
+ * start pose fall out through O5: no partner, so the n_corr < 3 rule applies.  The ctx's ICP switches (search, loss, accumulation,
+ * launches) do not apply.
+ * Not provided: colour (hybrid) odometry, the information matrix, masks (a caller zeroes the pixels), frame-to-model tracking against
+ * the volume, the C++ operator mirror. */
+#define TDV_ODOM_MAX_LEVELS 4
+typedef struct tdv_odometry_params {   /* 28 bytes */
+    float depth_diff;                          /* O3, O4, O5: metres, > 0; default 0.03 (Open3D's) */
+    float zmax;                                /* as tdv_deproject; default 10 */
+    int   n_levels;                            /* 1 .. TDV_ODOM_MAX_LEVELS; default 3 */
+    int   max_iterations[TDV_ODOM_MAX_LEVELS]; /* per level, level 0 the finest; default {20, 10, 5, 0} */
+} tdv_odometry_params;
+typedef struct tdv_odometry_result {   /* 108 bytes */
+    float T[16];                               /* column-major, source camera to target camera */
+    float fitness, rmse;                       /* of the last level that applied an iteration */
+    int   n_corr;
+    int   iterations[TDV_ODOM_MAX_LEVELS];     /* iterations applied per level */
+    int   n_corr_level[TDV_ODOM_MAX_LEVELS];   /* partners of the level's last applied iteration */
+} tdv_odometry_result;
+void tdv_odometry_default_params(tdv_odometry_params* params);
+int tdv_depth_maps_dev(tdv_ctx* ctx, const uint16_t* d_raw, int width, int height, float scale, float fx, float fy, float cx, float cy,
+                       const tdv_odometry_params* params, float* d_vertex_map /* optional */, float* d_normal_map /* optional */,
+                       float* d_out_xyz /* optional */, float* d_out_normals /* optional */, int capacity, int* n_out /* optional, host */);
+int tdv_depth_maps(tdv_ctx* ctx, const uint16_t* raw, int width, int height, float scale, float fx, float fy, float cx, float cy,
+                   const tdv_odometry_params* params, float* vertex_map, float* normal_map, float* out_xyz, float* out_normals, int capacity,
+                   int* n_out);
+int tdv_depth_odometry_terms_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const uint16_t* d_raw_tgt, int width, int height, float scale,
+                                 float fx, float fy, float cx, float cy, const float* h_T /* host, 16 */, int level,
+                                 const tdv_odometry_params* params, double* h_sums /* host, [29] */, int* n_valid_src /* optional, host */);
+int tdv_depth_odometry_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const uint16_t* d_raw_tgt, int width, int height, float scale, float fx,
+                           float fy, float cx, float cy, const float* h_T0 /* optional, host, 16 */, const tdv_odometry_params* params,
+                           tdv_odometry_result* out /* host */);
+int tdv_depth_odometry(tdv_ctx* ctx, const uint16_t* raw_src, const uint16_t* raw_tgt, int width, int height, float scale, float fx, float fy,
+                       float cx, float cy, const float* T0 /* optional */, const tdv_odometry_params* params, tdv_odometry_result* out);
+int tdv_depth_odometry_sequence_dev(tdv_ctx* ctx, const uint16_t* d_raw /* n_frames images */, int n_frames, int width, int height, float scale,
+                                    float fx, float fy, float cx, float cy, const float* h_init /* optional, host, n_frames x 16 */,
+                                    const tdv_odometry_params* params, float* h_poses /* host, n_frames x 16 */,
+                                    tdv_odometry_result* h_pairs /* optional, host, [n_frames] */);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
