@@ -73,7 +73,8 @@ ABI_SYMBOLS = [
     "tdv_tsdf_default_params", "tdv_tsdf_volume_bytes", "tdv_tsdf_reset_dev", "tdv_tsdf_integrate_dev", "tdv_tsdf_extract_dev", "tdv_tsdf_fuse",
     "tdv_tsdf_extract_mesh_dev", "tdv_tsdf_fuse_mesh",
     "tdv_odometry_default_params", "tdv_depth_maps_dev", "tdv_depth_maps", "tdv_depth_odometry_terms_dev", "tdv_depth_odometry_dev",
-    "tdv_depth_odometry", "tdv_depth_odometry_sequence_dev",
+    "tdv_depth_odometry", "tdv_depth_odometry_sequence_dev", "tdv_depth_odometry_to_depth_dev", "tdv_depth_odometry_to_depth",
+    "tdv_tsdf_raycast_default_params", "tdv_tsdf_raycast_dev", "tdv_tsdf_raycast", "tdv_tsdf_track_dev", "tdv_tsdf_track_sequence_dev",
     "tdv_voxel_downsample_normals", "tdv_voxel_downsample_normals_dev",
     "tdv_icp_level_default", "tdv_icp_multiscale", "tdv_icp_multiscale_dev", "tdv_icp_multiscale_batch_dev",
 ]
@@ -408,6 +409,41 @@ def _odometry_result(r):
                 iterations=list(r.iterations), n_corr_level=list(r.n_corr_level))
 
 
+TDV_TSDF_RAYCAST_MAX_STEPS = 16384
+
+
+class TsdfRaycastParamsC(C.Structure):
+    _fields_ = [("zmin", C.c_float), ("max_steps", C.c_int)]
+
+
+class TsdfTrackResultC(C.Structure):
+    _fields_ = [("pose", C.c_float * 16), ("odom", OdometryResultC), ("n_hit", C.c_longlong)]
+
+
+def raycast_params(**kw):
+    """tdv_tsdf_raycast_default_params (zmin 0.05 m, max_steps 4096) with the given fields replaced."""
+    return _params("raycast", kw)
+
+
+def _track_result(r):
+    """A tdv_tsdf_track_result as a dict: pose row-major [4, 4], odom as _odometry_result's dict, n_hit."""
+    return dict(pose=from_colmajor16(r.pose), odom=_odometry_result(r.odom), n_hit=int(r.n_hit))
+
+
+def _split_params(kw, *stages):
+    """kw split by the parameter struct each name belongs to, in the order of `stages` (a name two stages share - zmax - goes to
+    every one of them): one dict per stage.  An unknown name raises TypeError."""
+    fields = [dict(_PARAMS[s][0]._fields_) for s in stages]
+    out = [dict() for _ in stages]
+    for k, v in kw.items():
+        hit = [i for i, f in enumerate(fields) if k in f]
+        if not hit:
+            raise TypeError("unknown parameter %r (stages: %s)" % (k, ", ".join(stages)))
+        for i in hit:
+            out[i][k] = v
+    return out
+
+
 def mesh_compact(vertices, normals, triangles):
     """The mesh without the vertices no triangle refers to: the kept rows in their order, the triangles renumbered (numpy, on the host)."""
     triangles = np.asarray(triangles, np.int32).reshape(-1, 3)
@@ -475,6 +511,7 @@ _PARAMS = {
     "ppf": (PpfParamsC, "tdv_ppf_default_params", "PPF", None),
     "tsdf": (TsdfParamsC, "tdv_tsdf_default_params", "TSDF", dict(pose_direction=POSE_DIRECTION)),
     "odometry": (OdometryParamsC, "tdv_odometry_default_params", "odometry", None),
+    "raycast": (TsdfRaycastParamsC, "tdv_tsdf_raycast_default_params", "ray cast", None),
 }
 
 _lib = None
@@ -1825,6 +1862,113 @@ class Context:
         d_raw = torch.from_numpy(frames.view(np.int16) if frames.size else np.zeros((1, 1, 1), np.int16)).to(torch.device("cuda", self.device))
         torch.cuda.synchronize()
         return self.depth_odometry_sequence_dev(d_raw.data_ptr(), len(frames), frames.shape[2], frames.shape[1], *intrinsics, init=init, **params)
+
+    def depth_odometry_to_depth_dev(self, d_raw_src, d_depth_tgt, w, h, scale, fx, fy, cx, cy, T0=None, **params):
+        """tdv_depth_odometry_to_depth_dev: depth_odometry_dev with the target as an f32 depth image on the device (float32[h, w], metres; rule
+        O10) - a ray cast of the volume (tsdf_raycast_dev) or a rendering (render_depth_dev)."""
+        r = OdometryResultC()
+        _check(self._h, lib().tdv_depth_odometry_to_depth_dev(self._h, _ptr(d_raw_src), _ptr(d_depth_tgt), int(w), int(h),
+                                                              *self._cam(scale, fx, fy, cx, cy), None if T0 is None else _ptr(to_colmajor16(T0)),
+                                                              C.byref(odometry_params(**params)), C.byref(r)), "tdv_depth_odometry_to_depth_dev")
+        return _odometry_result(r)
+
+    def depth_odometry_to_depth(self, src, depth_tgt, intrinsics, T0=None, **params):
+        """tdv_depth_odometry_to_depth on host arrays: src uint16[h, w], depth_tgt float32[h, w]; intrinsics = (scale, fx, fy, cx, cy)."""
+        src, depth_tgt = np.ascontiguousarray(src, np.uint16), np.ascontiguousarray(depth_tgt, np.float32)
+        if src.shape != depth_tgt.shape or src.ndim != 2:
+            raise ValueError("tdv_depth_odometry_to_depth: a frame and a depth image of one size")
+        r = OdometryResultC()
+        _check(self._h, lib().tdv_depth_odometry_to_depth(self._h, _ptr(src), _ptr(depth_tgt), src.shape[1], src.shape[0], *self._cam(*intrinsics),
+                                                          None if T0 is None else _ptr(to_colmajor16(T0)), C.byref(odometry_params(**params)),
+                                                          C.byref(r)), "tdv_depth_odometry_to_depth")
+        return _odometry_result(r)
+
+    # ---------------------------------------------------------------- TSDF ray casting and tracking (include/tdv_hip.h: tdv_tsdf_raycast_dev)
+    raycast_params = staticmethod(raycast_params)
+
+    def tsdf_raycast_dev(self, vol, d_volume, pose, w, h, fx, fy, cx, cy, d_depth=None, d_vertex_map=None, d_normal_map=None, want_count=True,
+                         **params):
+        """tdv_tsdf_raycast_dev: the volume seen from pose ([4, 4] row-major, params' pose_direction) into d_depth (float32[h, w], 0 where a
+        ray has no hit), d_vertex_map and d_normal_map (float32[h, w, 3], camera coordinates), every output optional.  params: the fields of
+        tsdf_params and of raycast_params.  Returns the number of rays that hit, or None with want_count=False (no read-back)."""
+        tp, rp = _split_params(params, "tsdf", "raycast")
+        n = C.c_longlong(-1)
+        _check(self._h, lib().tdv_tsdf_raycast_dev(self._h, C.byref(vol), _ptr(d_volume), int(w), int(h), C.c_float(fx), C.c_float(fy), C.c_float(cx),
+                                                   C.c_float(cy), _ptr(to_colmajor16(pose)), C.byref(tsdf_params(**tp)), C.byref(raycast_params(**rp)),
+                                                   _ptr(d_depth), _ptr(d_vertex_map), _ptr(d_normal_map), C.byref(n) if want_count else None),
+               "tdv_tsdf_raycast_dev")
+        return n.value if want_count else None
+
+    def tsdf_raycast(self, volume, pose, w, h, fx, fy, cx, cy, maps=True, **params):
+        """tdv_tsdf_raycast on a host volume: volume = (vol, buf) with vol = (origin, voxel_length, dims) or a TsdfVolumeC and buf float32
+        [nz, ny, nx, 2] (or anything of nx*ny*nz pairs).  Returns dict(depth float32[h, w], vertex_map and normal_map float32[h, w, 3] - with
+        maps - and n_hit)."""
+        vol, buf = volume
+        vol = vol if isinstance(vol, TsdfVolumeC) else tsdf_volume_struct(*vol)
+        buf = np.ascontiguousarray(buf, np.float32)
+        if buf.size != 2 * vol.nx * vol.ny * vol.nz:
+            raise ValueError("tdv_tsdf_raycast: a volume of nx*ny*nz pairs")
+        tp, rp = _split_params(params, "tsdf", "raycast")
+        w, h = int(w), int(h)
+        out = dict(depth=np.zeros((h, w), np.float32))
+        if maps:
+            out.update(vertex_map=np.zeros((h, w, 3), np.float32), normal_map=np.zeros((h, w, 3), np.float32))
+        n = C.c_longlong(-1)
+        _check(self._h, lib().tdv_tsdf_raycast(self._h, C.byref(vol), _ptr(buf), w, h, C.c_float(fx), C.c_float(fy), C.c_float(cx), C.c_float(cy),
+                                               _ptr(to_colmajor16(pose)), C.byref(tsdf_params(**tp)), C.byref(raycast_params(**rp)),
+                                               _ptr(out["depth"]), _ptr(out.get("vertex_map")), _ptr(out.get("normal_map")), C.byref(n)),
+               "tdv_tsdf_raycast")
+        out["n_hit"] = n.value
+        return out
+
+    @staticmethod
+    def _track_params(tsdf, ray, odom):
+        """The three parameter structs of a tracking call from three dicts (None: the defaults); tracking's poses are the camera's pose in
+        the volume's frame, so pose_direction defaults to 'source_onto_target' here."""
+        return tsdf_params(**dict(dict(pose_direction="source_onto_target"), **(tsdf or {}))), raycast_params(**(ray or {})), \
+            odometry_params(**(odom or {}))
+
+    def tsdf_track_dev(self, vol, d_volume, d_raw, guess, w, h, scale, fx, fy, cx, cy, tsdf=None, ray=None, odom=None):
+        """tdv_tsdf_track_dev: the raw frame d_raw (uint16[h, w] on the device) tracked against the volume from guess ([4, 4] row-major, the
+        camera's pose in the volume's frame).  tsdf, ray, odom: dicts of tsdf_params', raycast_params' and odometry_params' fields.  Returns
+        dict(pose [4, 4] row-major, odom, n_hit)."""
+        tp, rp, op = self._track_params(tsdf, ray, odom)
+        r = TsdfTrackResultC()
+        _check(self._h, lib().tdv_tsdf_track_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_raw), int(w), int(h), *self._cam(scale, fx, fy, cx, cy),
+                                                 _ptr(to_colmajor16(guess)), C.byref(tp), C.byref(rp), C.byref(op), C.byref(r)), "tdv_tsdf_track_dev")
+        return _track_result(r)
+
+    def tsdf_track(self, volume, frame, guess, intrinsics, tsdf=None, ray=None, odom=None):
+        """tsdf_track_dev on a host frame (uint16[h, w]) against volume = tsdf_volume()'s pair; intrinsics = (scale, fx, fy, cx, cy)."""
+        import torch
+        frame = np.array(frame, np.uint16)                       # (a copy: torch wants a writable array)
+        d_raw = torch.from_numpy(frame.view(np.int16) if frame.size else np.zeros((1, 1), np.int16)).to(volume[1].device)
+        torch.cuda.synchronize()
+        return self.tsdf_track_dev(volume[0], volume[1].data_ptr(), d_raw.data_ptr(), guess, frame.shape[1], frame.shape[0], *intrinsics,
+                                   tsdf=tsdf, ray=ray, odom=odom)
+
+    def tsdf_track_sequence_dev(self, vol, d_volume, d_raw, n_frames, w, h, scale, fx, fy, cx, cy, pose0=None, tsdf=None, ray=None, odom=None):
+        """tdv_tsdf_track_sequence_dev: frames d_raw (uint16[n, h, w] on the device) tracked against and fused into the volume one after the
+        other, frame 0 at pose0 ([4, 4] row-major, None: the identity).  Returns (poses float32[n, 4, 4] row-major, the frames' results as
+        tsdf_track_dev's dicts, entry 0 holding pose0 and zeros).  One read-back per frame."""
+        n = int(n_frames)
+        tp, rp, op = self._track_params(tsdf, ray, odom)
+        poses = np.zeros((max(n, 1), 16), np.float32)
+        res = (TsdfTrackResultC * max(n, 1))()
+        _check(self._h, lib().tdv_tsdf_track_sequence_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_raw), n, int(w), int(h),
+                                                          *self._cam(scale, fx, fy, cx, cy), None if pose0 is None else _ptr(to_colmajor16(pose0)),
+                                                          C.byref(tp), C.byref(rp), C.byref(op), _ptr(poses), res), "tdv_tsdf_track_sequence_dev")
+        return poses[:n].reshape(n, 4, 4).transpose(0, 2, 1).copy(), [_track_result(res[k]) for k in range(n)]
+
+    def tsdf_track_sequence(self, volume, frames, intrinsics, pose0=None, tsdf=None, ray=None, odom=None):
+        """tsdf_track_sequence_dev on host frames (uint16[n, h, w]) into volume = tsdf_volume()'s pair."""
+        import torch
+        frames = np.array(frames, np.uint16)                     # (a copy: torch wants a writable array)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        d_raw = torch.from_numpy(frames.view(np.int16) if frames.size else np.zeros((1, 1, 1), np.int16)).to(volume[1].device)
+        torch.cuda.synchronize()
+        return self.tsdf_track_sequence_dev(volume[0], volume[1].data_ptr(), d_raw.data_ptr(), len(frames), frames.shape[2], frames.shape[1],
+                                            *intrinsics, pose0=pose0, tsdf=tsdf, ray=ray, odom=odom)
 
     # ---------------------------------------------------------------- PPF matching (include/tdv_hip.h: tdv_ppf_match)
     def ppf_model_bytes(self, nt, **params):

@@ -1,10 +1,11 @@
-// Depth odometry on gfx950: include/tdv_hip.h (tdv_depth_odometry_dev) states every rule, O1 to O9.
+// Depth odometry on gfx950: include/tdv_hip.h (tdv_depth_odometry_dev) states every rule, O1 to O10.
 //
 // Two frames of one sensor need no search structure: the pixel grid gives a vertex its neighbours (a normal is one cross product, O3)
 // and the projection gives a source pixel its partner (O5).  Every float below is evaluated as the header writes it; the sums go over
 // the fixed f64 tree (fixed_tree.hpp) in pixel order, and the only atomics are integer counts and tickets, so nothing depends on the
 // order the device works in.
 //   k_od_depth0    O1: a lane per pixel, the raw u16 frame to f32 metres, 0 where invalid.  blockIdx.y = frame.
+//   k_od_depth0_f32  O10: the same from an f32 depth image - the target of tdv_depth_odometry_to_depth_dev and of tracking.
 //   k_od_down      O4: a lane per pixel of the coarser level, its block of four from the finer one.
 //   k_od_normals   O2 + O3: a lane per pixel; the +1 column and +1 row neighbours come from two more coalesced loads of the depth rows.
 //                  Counts the level's valid pixels (an integer atomic per workgroup).  MAPS: also the vertex map, the normal map and the
@@ -25,6 +26,7 @@
 #include "icp_terms.hpp"
 #include "fixed_tree.hpp"
 #include "flag_gather.hpp"
+#include "tsdf_track.hpp"
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -60,6 +62,15 @@ void k_od_depth0(const uint16_t* __restrict__ raw, int npx, float inv_scale, flo
     const uint16_t r = raw[o];
     const float d = scaled_depth(r, inv_scale);                                    // O1
     z[o] = (r != 0 && d <= zmax) ? d : 0.0f;
+}
+
+// O10: level 0 of one frame from an f32 depth image (a ray cast of the volume, a rendering), 0 where it holds no usable depth
+__global__ __launch_bounds__(OD_T)
+void k_od_depth0_f32(const float* __restrict__ depth, int npx, float zmax, float* __restrict__ z) {
+    const int i = blockIdx.x * OD_T + threadIdx.x;
+    if (i >= npx) return;
+    const float d = depth[i];
+    z[i] = (d > 0.f && d <= zmax) ? d : 0.0f;                                      // (false for NaN)
 }
 
 // fine: w x h pixels per frame, coarse: (w / 2) x (h / 2)
@@ -257,6 +268,14 @@ int od_depth0(tdv_ctx* ctx, const OdPyramid& py, const uint16_t* d_raw, int slot
     return TDV_OK;
 }
 
+// O10 for one frame, into the pyramid's slot `slot`: the other way to fill level 0
+int od_depth0(tdv_ctx* ctx, const OdPyramid& py, const float* d_depth, int slot, float zmax) {
+    const OdLevel& L = py.lv[0];
+    k_od_depth0_f32<<<od_blocks(L.npx), OD_T, 0, ctx->stream>>>(d_depth, L.npx, zmax, L.z + (size_t)slot * L.npx);
+    TDV_CHECK_LAUNCH(ctx);
+    return TDV_OK;
+}
+
 // O4 and O3 for every frame and level, once level 0's depths stand
 int od_build(tdv_ctx* ctx, const OdPyramid& py, float depth_diff) {
     hipStream_t s = ctx->stream;
@@ -377,6 +396,24 @@ bool od_maps_args_ok(const tdv_ctx* ctx, const void* raw, int w, int h, float sc
 
 }  // namespace
 
+// tsdf_track.hpp: the checks and the pair against an f32 target for tsdf_raycast.hip
+bool odometry_camera_ok(int w, int h, float scale, float fx, float fy) { return od_camera_ok(w, h, scale, fx, fy); }
+bool odometry_params_ok(const tdv_odometry_params* params, int w, int h) { return od_params_ok(params, w, h); }
+void odometry_empty_result(const float* h_T0, tdv_odometry_result* out) { od_empty_result(h_T0, out); }
+
+// od_pair with the target's level 0 by O10 (the target in slot 0, the source in slot 1)
+int odometry_pair_to_depth(tdv_ctx* ctx, const uint16_t* d_raw_src, const float* d_depth_tgt, int w, int h, float scale, float fx, float fy,
+                           float cx, float cy, const float* h_T0, const tdv_odometry_params& prm, tdv_odometry_result* out) {
+    OdPyramid py;
+    OdRun run;
+    TDV_TRY(od_alloc(ctx, 2, w, h, fx, fy, cx, cy, prm.n_levels, &py));
+    TDV_TRY(od_depth0(ctx, py, d_depth_tgt, 0, prm.zmax));
+    TDV_TRY(od_depth0(ctx, py, d_raw_src, 1, 1, scale, prm.zmax));
+    TDV_TRY(od_build(ctx, py, prm.depth_diff));
+    TDV_TRY(od_run_alloc(ctx, py, 1, h_T0, 16, &run));
+    return od_iterate(ctx, py, prm, 1, run, out);
+}
+
 }  // namespace tdv
 
 using namespace tdv;
@@ -469,6 +506,33 @@ int tdv_depth_odometry(tdv_ctx* ctx, const uint16_t* raw_src, const uint16_t* ra
     return od_pair(ctx, d_src, d_tgt, width, height, scale, fx, fy, cx, cy, T0, *params, out);
 }
 
+int tdv_depth_odometry_to_depth_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const float* d_depth_tgt, int width, int height, float scale,
+                                    float fx, float fy, float cx, float cy, const float* h_T0, const tdv_odometry_params* params,
+                                    tdv_odometry_result* out) {
+    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !out) return TDV_ERR_BAD_ARG;
+    const size_t npx = (size_t)width * height;
+    if (npx != 0 && (!d_raw_src || !d_depth_tgt)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    od_empty_result(h_T0, out);
+    if (npx == 0) return TDV_OK;
+    return odometry_pair_to_depth(ctx, d_raw_src, d_depth_tgt, width, height, scale, fx, fy, cx, cy, h_T0, *params, out);
+}
+
+int tdv_depth_odometry_to_depth(tdv_ctx* ctx, const uint16_t* raw_src, const float* depth_tgt, int width, int height, float scale, float fx,
+                                float fy, float cx, float cy, const float* T0, const tdv_odometry_params* params, tdv_odometry_result* out) {
+    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !out) return TDV_ERR_BAD_ARG;
+    const size_t npx = (size_t)width * height;
+    if (npx != 0 && (!raw_src || !depth_tgt)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    od_empty_result(T0, out);
+    if (npx == 0) return TDV_OK;
+    uint16_t* d_src;
+    float* d_tgt;
+    TDV_TRY(upload(ctx, raw_src, npx, &d_src));
+    TDV_TRY(upload(ctx, depth_tgt, npx, &d_tgt));
+    return odometry_pair_to_depth(ctx, d_src, d_tgt, width, height, scale, fx, fy, cx, cy, T0, *params, out);
+}
+
 int tdv_depth_odometry_sequence_dev(tdv_ctx* ctx, const uint16_t* d_raw, int n_frames, int width, int height, float scale, float fx, float fy,
                                     float cx, float cy, const float* h_init, const tdv_odometry_params* params, float* h_poses,
                                     tdv_odometry_result* h_pairs) {
@@ -494,16 +558,7 @@ int tdv_depth_odometry_sequence_dev(tdv_ctx* ctx, const uint16_t* d_raw, int n_f
     }
     // O9: P_0 = I, P_k = P_(k-1) T_k, each entry the f64 sum of four f64 products in index order, rounded once
     od_identity(h_poses);
-    for (int k = 1; k < n_frames; ++k) {
-        const float *A = h_poses + 16 * (size_t)(k - 1), *B = res[k].T;
-        float* Cm = h_poses + 16 * (size_t)k;
-        for (int j = 0; j < 4; ++j)
-            for (int i = 0; i < 4; ++i) {
-                double acc = (double)A[i] * (double)B[4 * j];
-                for (int q = 1; q < 4; ++q) acc = acc + (double)A[4 * q + i] * (double)B[4 * j + q];
-                Cm[4 * j + i] = (float)acc;
-            }
-    }
+    for (int k = 1; k < n_frames; ++k) pose_chain_product(h_poses + 16 * (size_t)(k - 1), res[k].T, h_poses + 16 * (size_t)k);
     if (h_pairs) std::memcpy(h_pairs, res.data(), (size_t)n_frames * sizeof(tdv_odometry_result));
     return TDV_OK;
 }

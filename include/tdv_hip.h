@@ -1265,8 +1265,8 @@ int tdv_mesh_sample_points_dev(tdv_ctx* ctx, const float* d_vertices, int n_vert
  * TDV_TSDF_HOST_MAX_VOXELS); voxel_length, scale, fx or fy <= 0 or non-finite; trunc < 0 or non-finite; max_weight < 1 or non-finite;
  * min_weight <= 0 or non-finite; n_frames < 0 or > TDV_TSDF_MAX_FRAMES; width or height < 0 or > TDV_VERIFY_MAX_SIDE; an unknown
  * pose_direction; capacity < 0.  The ctx's switches do not apply.
- * Not provided: colour, per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, ray casting, the C++
- * operator mirror. */
+ * Not provided: colour, per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, the C++ operator
+ * mirror.  Ray casting and tracking against the volume: tdv_tsdf_raycast_dev, below. */
 typedef struct tdv_tsdf_volume { float origin[3]; float voxel_length; int nx, ny, nz; } tdv_tsdf_volume;   /* 28 bytes */
 typedef struct tdv_tsdf_params {   /* 20 bytes */
     float trunc;           /* truncation distance in metres; default 0, which means 4.0f * voxel_length */
@@ -1302,6 +1302,79 @@ int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t*
                        float fx, float fy, float cx, float cy, const float* poses, const tdv_tsdf_params* params, float* out_vertices,
                        float* out_normals /* optional */, int vertex_capacity, int* n_vertices, int* out_triangles, int triangle_capacity,
                        int* n_triangles);
+/* TSDF ray casting and frame-to-model tracking (KinectFusion, Newcombe et al. 2011; Open3D's VoxelBlockGrid ray_cast): the fused volume
+ * seen from a camera pose - a depth image, a vertex map and a normal map without holes or splats - and the next frame registered against
+ * that view of the model instead of against the frame before, so that a sequence's drift is held by everything fused so far.  Every
+ * pixel's march is independent, every loop is bounded, and all arithmetic is f32, one rounding per operation, no contraction, the order
+ * exactly as written (sqrtf and / correctly rounded): every output is fixed bit for bit whatever order the device works in.  The rules
+ * continue T1 to T12; the odometry's are O1 to O10 below.
+ *  T13. Ray.  The point of pixel (u, v) at camera depth z is O2's vertex, c = ((((float)u - cx) * z) / fx, (((float)v - cy) * z) / fy, z).
+ *      Its volume-frame point p under the pose T (column-major): TDV_POSE_SOURCE_ONTO_TARGET - T is the camera's pose in the volume's
+ *      frame - p0 = ((T[0]*c0 + T[4]*c1) + T[8]*c2) + T[12], p1 = ((T[1]*c0 + T[5]*c1) + T[9]*c2) + T[13],
+ *      p2 = ((T[2]*c0 + T[6]*c1) + T[10]*c2) + T[14]: rule 1's model-to-camera form applied to c.  TDV_POSE_MODEL_TO_CAMERA: d = c -
+ *      (T[12], T[13], T[14]) per component and p0 = (T[0]*d0 + T[1]*d1) + T[2]*d2, p1 = (T[4]*d0 + T[5]*d1) + T[6]*d2,
+ *      p2 = (T[8]*d0 + T[9]*d1) + T[10]*d2: rule 1's other form.  The march runs in z, not in ray length: the z of a hit is directly the
+ *      depth image O1 to O3 and T4 work with.
+ *  T14. Field sample F(p).  Per axis a: g_a = (p_a - origin[a]) / voxel_length - 0.5f, i_a = floorf(g_a), t_a = g_a - i_a.  The sample is
+ *      known iff every g_a is finite, g_a >= 0 and g_a < (float)(n_a - 1), all eight voxels (i0 + dx, i1 + dy, i2 + dz), dx, dy, dz in
+ *      {0, 1}, are observed (T6), and the value below is not NaN; the g_a are judged as floats, before any conversion to int.  With
+ *      lerp(a, b, t) = a + t * (b - a): four lerps along x, x_(dy dz) = lerp(f(0, dy, dz), f(1, dy, dz), t_0); two along y,
+ *      y_dz = lerp(x_(0 dz), x_(1 dz), t_1); one along z, F = lerp(y_0, y_1, t_2).  A volume with a side of 1 has no known sample.
+ *  T15. March.  z_0 = zmin.  At sample k = 0, 1, ...: if !(z_k <= zmax) or k == max_steps the ray ends without a hit.  Otherwise
+ *      s_k = F(p(z_k)) by T13 and T14.  Unknown: z_(k+1) = z_k + trunc.  Known and s_k >= 0: z_(k+1) = z_k + fmaxf(s_k * trunc,
+ *      voxel_length), Open3D's ray-cast stride.  Known and s_k < 0: the ray ends, and it is a hit iff k > 0 and sample k-1 was known;
+ *      sample k-1 is then non-negative.  A back face, or a camera inside the surface, gives no hit.  trunc is T5's, zmax params->zmax.
+ *  T16. Hit depth: z = fminf(z_(k-1) + ((z_k - z_(k-1)) * s_(k-1)) / (s_(k-1) - s_k), z_k); the denominator is positive, and z > 0.
+ *  T17. Vertex: O2's vertex of (u, v) at that z.
+ *  T18. Normal.  With p the hit's volume-frame point (T13 at T16's z) and L = voxel_length: G_a = F(p + L e_a) - F(p - L e_a), only
+ *      component a of p changed.  The normal is absent, (0, 0, 0), if any of the six samples is unknown.  Into the camera's frame:
+ *      source-onto-target n0 = (T[0]*G0 + T[1]*G1) + T[2]*G2, n1 = (T[4]*G0 + T[5]*G1) + T[6]*G2, n2 = (T[8]*G0 + T[9]*G1) + T[10]*G2;
+ *      model-to-camera n0 = (T[0]*G0 + T[4]*G1) + T[8]*G2, n1 = (T[1]*G0 + T[5]*G1) + T[9]*G2, n2 = (T[2]*G0 + T[6]*G1) + T[10]*G2.  Then
+ *      T8's normalisation: L = sqrtf((n0*n0 + n1*n1) + n2*n2), the row n / L per component, (0, 0, 0) where L is zero or not finite.  A
+ *      surface seen from the front gets a normal towards the camera: O3's sign.
+ * tdv_tsdf_raycast_dev: the volume from h_pose (host, 16 floats, column-major, params->pose_direction).  Of params it uses trunc, zmax,
+ * min_weight and pose_direction (the others are checked all the same).  d_depth: width*height floats, 0.0f where the ray has no hit;
+ * d_vertex_map and d_normal_map: width*height*3 floats in camera coordinates, tdv_depth_maps_dev's layout, zeros where there is no hit
+ * resp. no normal.  Every output is optional; h_n_hit (optional, host) is the number of rays that hit - the non-zero depths - and costs
+ * the call its only read-back.  width*height == 0 is valid and writes nothing.  NaN or infinite pose entries fall out through T14: no
+ * sample is known, so nothing hits.  The step cap makes every ray finite whatever the arguments - a voxel_length below an ulp of z
+ * marches to the cap and ends.  tdv_tsdf_raycast is the host form: the volume (nx*ny*nz pairs) goes up through the ctx's workspace;
+ * volumes above TDV_TSDF_HOST_MAX_VOXELS are refused.
+ * Tracking.  tdv_tsdf_track_dev: one raw frame (device) against the volume from the guess G (host, 16 floats) - the camera's pose in the
+ * volume's frame, typically the frame before's; params->pose_direction must be TDV_POSE_SOURCE_ONTO_TARGET, the direction O9 produces.
+ *  K1. The volume is ray cast at G (T13 to T16) into a depth image in the ctx's workspace; n_hit is its count of hits.
+ *  K2. tdv_depth_odometry_to_depth_dev with the frame as the source and that image as the target, from the identity: odom.
+ *  K3. pose = G * odom.T by O9's product: each entry the f64 sum of four f64 products in index order, rounded once to f32.
+ * The result is byte for byte what the three public steps give on the same ctx, in one read-back.  width*height == 0: pose = G * I, zeros.
+ * tdv_tsdf_track_sequence_dev: d_raw holds n_frames images back to back.  Frame 0 is integrated (T1 to T5) at P_0 = h_pose0 (NULL: the
+ * identity); for k >= 1 frame k is tracked from the guess P_(k-1) and then integrated at P_k.  h_poses (host, n_frames x 16) receives the
+ * P_k, h_results (optional, host, [n_frames]) the frames' results, entry 0 holding P_0 and zeros.  The volume is taken as it is: a caller
+ * resets it first.  The cost is one read-back per frame - the pose has to reach the host for K3 and for integrate's h_poses.  Per frame
+ * the pose and the result, and the volume at the end, are byte for byte those of a loop over the public calls.  n_frames of 0 or 1 is
+ * valid.
+ * Kernel (csrc/tsdf_raycast.hip): one launch, a lane per pixel, a wave per 8 x 8 pixel tile so that neighbouring rays' eight pair loads
+ * share lines, a pair loaded as 8 bytes, the pose read through scalar loads; no LDS but the hit count's four ints and no atomic but that
+ * count's one per workgroup.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: as tdv_tsdf_extract_dev for ctx, vol, the volume buffer and params, as
+ * tdv_render_depth_dev for width, height, fx, fy and a NULL pose; a NULL ray, zmin <= 0 or non-finite, max_steps outside
+ * [1, TDV_TSDF_RAYCAST_MAX_STEPS]; the host form above TDV_TSDF_HOST_MAX_VOXELS.  Tracking also: as tdv_depth_odometry_dev for scale and
+ * odom, a NULL frame (width*height > 0), guess or result, a pose_direction other than TDV_POSE_SOURCE_ONTO_TARGET; the sequence: n_frames
+ * < 0 or > TDV_TSDF_MAX_FRAMES, NULL frames or h_poses with n_frames > 0.
+ * Not provided: colour, a sparse volume, adaptive refinement of the hit beyond T16's one interpolation, loop closure, a device-resident
+ * pose hand-off from tracking to integrate (the read-back per frame). */
+#define TDV_TSDF_RAYCAST_MAX_STEPS 16384
+typedef struct tdv_tsdf_raycast_params {   /* 8 bytes */
+    float zmin;            /* T15: where the march starts, metres, > 0; default 0.05 */
+    int   max_steps;       /* T15: the most samples of a ray, 1 .. TDV_TSDF_RAYCAST_MAX_STEPS; default 4096 */
+} tdv_tsdf_raycast_params;
+void tdv_tsdf_raycast_default_params(tdv_tsdf_raycast_params* params);
+int tdv_tsdf_raycast_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, int width, int height, float fx, float fy, float cx,
+                         float cy, const float* h_pose /* host, 16 */, const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray,
+                         float* d_depth /* optional */, float* d_vertex_map /* optional */, float* d_normal_map /* optional */,
+                         long long* h_n_hit /* optional, host */);
+int tdv_tsdf_raycast(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, int width, int height, float fx, float fy, float cx, float cy,
+                     const float* pose, const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, float* depth /* optional */,
+                     float* vertex_map /* optional */, float* normal_map /* optional */, long long* n_hit /* optional */);
 /* Depth odometry (KinectFusion's tracking step, Newcombe et al. 2011; Open3D's compute_odometry_result_point_to_plane): the camera's
  * motion between two raw depth frames of one sensor, on the device - the piece between "scan" and "fuse".  Two frames need no search
  * structure: the pixel grid gives a vertex its neighbours, so a normal is one cross product, and the projection gives a source pixel its
@@ -1340,6 +1413,8 @@ int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t*
  *  O9. Sequence.  Frames 0 .. n-1; pair k has source k, target k-1 and start h_init[k] (or the identity).  P_0 = I and
  *      P_k = P_(k-1) * T_k, formed on the host: each entry the f64 sum of four f64 products in index order, rounded once to f32.  P_k is
  *      camera k's pose in camera 0's frame: TDV_POSE_SOURCE_ONTO_TARGET for tdv_tsdf_integrate_dev with the volume in camera 0's frame.
+ *  O10. An f32 target.  Where the target is an f32 depth image d instead of a raw frame, its level 0 depth is z = d if d is not NaN and
+ *      0 < d <= zmax, else 0.0f.  O3 to O8 are unchanged; the source stays a raw frame (O1).
  * tdv_depth_maps_dev: O1 to O3 of one frame at level 0.  Every output is optional.  d_vertex_map and d_normal_map are width*height*3
  * floats, zeros at invalid pixels resp. absent normals.  d_out_xyz and d_out_normals receive, in pixel order, the rows of the pixels
  * that have a normal - a cloud with normals and no neighbour search; they need n_out, which bounds them.  Count and capacity as
@@ -1351,6 +1426,10 @@ int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t*
  * tdv_depth_odometry_dev: O8 from h_T0 (NULL: the identity).  The frames are device pointers, the pose and the result on the host; one
  * read-back.  The result holds T, then fitness, rmse and n_corr of the last level that applied an iteration (zeros if none did), and
  * per level the iterations applied and the correspondences of its last applied iteration.  tdv_depth_odometry is its host form.
+ * tdv_depth_odometry_to_depth_dev: tdv_depth_odometry_dev with the target given as an f32 depth image d_depth_tgt (width*height floats,
+ * metres along the camera's z, device) by O10 - what tdv_tsdf_raycast_dev writes, which is frame-to-model tracking, and also what
+ * tdv_render_depth_dev writes, which tracks a part against its own rendering.  Where the image holds exactly O1's depth of a raw frame
+ * the result is byte for byte tdv_depth_odometry_dev's with that frame as the target.  tdv_depth_odometry_to_depth is its host form.
  * tdv_depth_odometry_sequence_dev: d_raw holds n_frames images back to back; h_init (optional, n_frames x 16, entry 0 unused), h_poses
  * (n_frames x 16) and h_pairs (optional, n_frames results, entry 0 zeros) on the host.  Per pair the result is, byte for byte, what
  * tdv_depth_odometry_dev returns for that pair on the same ctx.  Each frame's pyramid is built once, all pairs iterate together - the
@@ -1366,8 +1445,8 @@ int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t*
  * returning the start pose with zeros: width*height == 0, n_frames of 0 or 1, a frame with no valid pixel.  NaN or infinite entries of a
  * start pose fall out through O5: no partner, so the n_corr < 3 rule applies.  The ctx's ICP switches (search, loss, accumulation,
  * launches) do not apply.
- * Not provided: colour (hybrid) odometry, the information matrix, masks (a caller zeroes the pixels), frame-to-model tracking against
- * the volume, the C++ operator mirror. */
+ * Not provided: colour (hybrid) odometry, the information matrix, masks (a caller zeroes the pixels), the C++ operator mirror.
+ * Frame-to-model tracking against the volume: tdv_tsdf_track_dev (K1 to K3, with tdv_tsdf_raycast_dev above). */
 #define TDV_ODOM_MAX_LEVELS 4
 typedef struct tdv_odometry_params {   /* 28 bytes */
     float depth_diff;                          /* O3, O4, O5: metres, > 0; default 0.03 (Open3D's) */
@@ -1401,6 +1480,27 @@ int tdv_depth_odometry_sequence_dev(tdv_ctx* ctx, const uint16_t* d_raw /* n_fra
                                     float fx, float fy, float cx, float cy, const float* h_init /* optional, host, n_frames x 16 */,
                                     const tdv_odometry_params* params, float* h_poses /* host, n_frames x 16 */,
                                     tdv_odometry_result* h_pairs /* optional, host, [n_frames] */);
+int tdv_depth_odometry_to_depth_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const float* d_depth_tgt /* O10 */, int width, int height,
+                                    float scale, float fx, float fy, float cx, float cy, const float* h_T0 /* optional, host, 16 */,
+                                    const tdv_odometry_params* params, tdv_odometry_result* out /* host */);
+int tdv_depth_odometry_to_depth(tdv_ctx* ctx, const uint16_t* raw_src, const float* depth_tgt, int width, int height, float scale, float fx,
+                                float fy, float cx, float cy, const float* T0 /* optional */, const tdv_odometry_params* params,
+                                tdv_odometry_result* out);
+/* Frame-to-model tracking, K1 to K3: stated with tdv_tsdf_raycast_dev above. */
+typedef struct tdv_tsdf_track_result {   /* 184 bytes */
+    float pose[16];                            /* K3: the camera's pose in the volume's frame, column-major */
+    tdv_odometry_result odom;                  /* K2: the frame against the ray cast; T takes the frame's camera to the guess's */
+    long long n_hit;                           /* K1: the rays of the guess's view that hit */
+} tdv_tsdf_track_result;
+int tdv_tsdf_track_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const uint16_t* d_raw, int width, int height,
+                       float scale, float fx, float fy, float cx, float cy, const float* h_guess /* host, 16 */,
+                       const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, const tdv_odometry_params* odom,
+                       tdv_tsdf_track_result* out /* host */);
+int tdv_tsdf_track_sequence_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_volume, const uint16_t* d_raw /* n_frames images */,
+                                int n_frames, int width, int height, float scale, float fx, float fy, float cx, float cy,
+                                const float* h_pose0 /* optional, host, 16 */, const tdv_tsdf_params* params,
+                                const tdv_tsdf_raycast_params* ray, const tdv_odometry_params* odom, float* h_poses /* host, n_frames x 16 */,
+                                tdv_tsdf_track_result* h_results /* optional, host, [n_frames] */);
 /* PPF matching (point-pair-feature voting: Drost, Ulrich, Navab, Ilic, CVPR 2010; OpenCV's ppf_match_3d, PCL's PPFRegistration): a third
  * global registration beside tdv_ransac and tdv_fgr, from points and normals only - no descriptors.  Conventions as there: source = scene,
  * target = model, T moves the source onto the target.  It returns up to max_poses ranked candidate poses.  The votes are integers and
