@@ -1,8 +1,11 @@
-// What the depth stage's host functions are called with (depth.hip, depth_cloud.hip, depth_batch.hip): the frames and their masks as one
-// descriptor, the camera, and the plan the batched count pass hands to the emit pass.
+// What the host functions of every stage that reads depth frames are called with: the pinhole and the camera of a frame with its one
+// check (verify*.hip, tsdf*.hip, odometry.hip), and for the depth stage (depth.hip, depth_cloud.hip, depth_batch.hip) the frames and
+// their masks as one descriptor and the plan the batched count pass hands to the emit pass.
 #pragma once
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
+#include "tdv_hip.h"
 
 struct tdv_ctx;
 
@@ -15,6 +18,27 @@ enum class MaskLayout : int {
     LabelU16 = 2,   // ONE u16 label image (the same rule, for more than 255 instances)
 };
 inline MaskLayout mask_layout_of(int mask_format) { return static_cast<MaskLayout>(mask_format); }
+
+struct Pinhole { float fx, fy, cx, cy; };
+
+inline bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
+// raw depth units -> metres, as cv::Mat::convertTo(CV_32F, 1.0/scale) forms the factor: the one place it is formed
+inline float depth_inv_scale(float scale) { return (float)(1.0 / (double)scale); }
+
+// The camera of a W x H depth frame as the entry points receive it; scale is 1 where a call has none (a rendering, a ray cast).
+struct FrameCamera {
+    int w, h;
+    float scale;
+    Pinhole k;
+    size_t npx() const { return (size_t)w * h; }
+    float inv_scale() const { return depth_inv_scale(scale); }
+};
+// what every entry point that takes a frame's camera asks of it: sides in [0, TDV_VERIFY_MAX_SIDE], fx, fy and - where the call has
+// one - scale finite and > 0 (cx and cy are free)
+inline bool frame_camera_ok(const FrameCamera& c, bool has_scale) {
+    if (c.w < 0 || c.w > TDV_VERIFY_MAX_SIDE || c.h < 0 || c.h > TDV_VERIFY_MAX_SIDE) return false;
+    return positive_finite(c.k.fx) && positive_finite(c.k.fy) && (!has_scale || positive_finite(c.scale));
+}
 
 // n_inst masks (or one label image) over one or several W x H depth frames stored back to back; one frame with an optional mask
 // is n_inst = 1, Stacked, frame_of = nullptr.  All pointers are device pointers.
@@ -30,13 +54,11 @@ struct DepthFrames {
     float zmax;
     DepthFrames(const uint16_t* raw_, const int* frame_of_, const uint8_t* masks_, MaskLayout layout_, int n_inst_, int w_, int h_, float scale, int mask_mode_, float zmax_)
         : raw(raw_), frame_of(frame_of_), masks(masks_), layout(layout_), n_inst(n_inst_), w(w_), h(h_), n((size_t)w_ * h_),
-          inv_scale((float)(1.0 / (double)scale)) /* cv::Mat::convertTo(CV_32F, 1.0/scale) */, mask_mode(mask_mode_), zmax(zmax_) {}
+          inv_scale(depth_inv_scale(scale)), mask_mode(mask_mode_), zmax(zmax_) {}
     static DepthFrames one(const uint16_t* raw, const uint8_t* mask, int w, int h, float scale, int mask_mode, float zmax) {
         return DepthFrames(raw, nullptr, mask, MaskLayout::Stacked, 1, w, h, scale, mask_mode, zmax);
     }
 };
-
-struct Pinhole { float fx, fy, cx, cy; };
 
 // What the batched count pass did, for the emit pass to continue: nothing is decided twice.  The pointers are workspace memory of the
 // current call.

@@ -10,19 +10,21 @@
 //   k_od_normals   O2 + O3: a lane per pixel; the +1 column and +1 row neighbours come from two more coalesced loads of the depth rows.
 //                  Counts the level's valid pixels (an integer atomic per workgroup).  MAPS: also the vertex map, the normal map and the
 //                  flag compact_flagged (flag_gather.hpp) gathers the rows by - the maps call.
-//   k_od_iterate   one launch per iteration, blockIdx.y = pair: O5 and O6 per source pixel (verify_common.hpp's verify_project, icp_terms.hpp's
-//                  corr_rec and rec_terms: the verifier's and point-to-plane ICP's own code), the workgroup's 29 sums by the tree, one
-//                  row of partials per workgroup; the workgroup that takes the pair's last ticket (agent scope) folds the rows in the
+//   k_od_iterate   one launch per iteration, blockIdx.y = pair: O5 and O6 per source pixel (frame_pose.hpp's pose_apply and
+//                  pinhole_project, icp_terms.hpp's corr_rec and rec_terms: the verifier's and point-to-plane ICP's own code), the
+//                  workgroup's 29 sums by the tree, one row of partials per workgroup; the workgroup that takes the pair's last ticket (agent scope) folds the rows in the
 //                  tree's order and applies icp_update in its tail.  The next launch reads the new pose: no host round trip.  A pair
 //                  that is done leaves at once.  TERMS: the folded sums go out instead (tdv_depth_odometry_terms_dev).
 //   k_od_level     between levels, a lane per pair: records what the level did and restarts the iteration state (O8).
 // The workspace keeps, per frame and level, the depth (4 bytes per pixel) and the normal map (12): vertices are recomputed from the
 // depth wherever they are needed, O2 gives the same bits.  Everything a kernel reads from the workspace is written by the call first:
 // depths and normals by the kernels above (every pixel of every level), counts and tickets by a memset, states by an upload.
+// On the host a pair is set up once (od_pair_setup) for the four pair entry points, the terms call and tracking; odometry_pair, its
+// parameter check and its empty result are what tsdf_raycast.hip calls (tsdf_track.hpp), under the names they have here.
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
-#include "verify_common.hpp"
-#include "depth_rules.hpp"
+#include "frame_pose.hpp"
+#include "tsdf_volume.hpp"
 #include "icp_terms.hpp"
 #include "fixed_tree.hpp"
 #include "flag_gather.hpp"
@@ -44,15 +46,10 @@ static_assert(OD_L == 4, "tdv_odometry_params.max_iterations, tdv_odometry_resul
 
 // one level of every frame of a call: frame f's depth at z + f * npx, its normal map at nrm + 3 * f * npx, its valid count at
 // nvalid[f * OD_L + level]
-struct OdLevel { int w, h, npx, level; float fx, fy, cx, cy; float* z; float* nrm; int* nvalid; };
+struct OdLevel { int w, h, npx, level; Pinhole k; float* z; float* nrm; int* nvalid; };
 // a pair's state on the device: ICP's record, and what the levels so far have left for the result
 struct OdState { IcpState s; float fitness, rmse; int n_corr; int iterations[OD_L]; int n_corr_level[OD_L]; };
 struct OdTerms { double sums[OD_NV]; int n_valid; int pad; };
-
-// O2: the vertex of pixel (u, v) at depth z, by depth_rules.hpp's rule
-__device__ __forceinline__ void od_vertex(int u, int v, float z, const OdLevel& L, float* V) {
-    emit_point((float)u, (float)v, z, L.cx, L.cy, PlainDiv{L.fx, L.fy}, V, (float*)nullptr, (const uint8_t*)nullptr, 0, (size_t)0);
-}
 
 __global__ __launch_bounds__(OD_T)
 void k_od_depth0(const uint16_t* __restrict__ raw, int npx, float inv_scale, float zmax, float* __restrict__ z) {
@@ -106,18 +103,18 @@ void k_od_normals(OdLevel L, float depth_diff, float* __restrict__ vertex_map, f
         const int u = i % L.w, v = i / L.w;
         const float z0 = z[i];
         valid = z0 > 0.f;
-        if (valid) od_vertex(u, v, z0, L, V);
+        if (valid) pinhole_vertex(u, v, z0, L.k, V);
         if (valid && u + 1 < L.w && v + 1 < L.h) {
             const float zu = z[i + 1], zv = z[i + L.w];
             if (zu > 0.f && zv > 0.f && fabsf(zu - z0) <= depth_diff && fabsf(zv - z0) <= depth_diff) {   // O3
                 float A[3], B[3];
-                od_vertex(u + 1, v, zu, L, A);
-                od_vertex(u, v + 1, zv, L, B);
+                pinhole_vertex(u + 1, v, zu, L.k, A);
+                pinhole_vertex(u, v + 1, zv, L.k, B);
                 const float a0 = A[0] - V[0], a1 = A[1] - V[1], a2 = A[2] - V[2];
                 const float b0 = B[0] - V[0], b1 = B[1] - V[1], b2 = B[2] - V[2];
                 const float n0 = b1 * a2 - b2 * a1, n1 = b2 * a0 - b0 * a2, n2 = b0 * a1 - b1 * a0;
-                const float len = sqrtf((n0 * n0 + n1 * n1) + n2 * n2);
-                if (len > 0.f && len < INFINITY) { n[0] = n0 / len; n[1] = n1 / len; n[2] = n2 / len; has = true; }
+                const Row3 unit = normalized_or_zero(n0, n1, n2, &has);
+                n[0] = unit.x; n[1] = unit.y; n[2] = unit.z;
             }
         }
         float* nm = (MAPS ? normal_map : L.nrm + 3 * (size_t)f * L.npx);
@@ -145,7 +142,6 @@ void k_od_iterate(OdLevel L, float zmax, float depth_diff, OdState* __restrict__
     OdState* st = st_all + p;
     if (!TERMS && st->s.done) return;                       // (every workgroup of the pair alike: only the tail of a launch writes it)
     const Pose16 P = load_pose(st->s.T, 0);                 // wave-uniform
-    const VerifyCam cam{L.fx, L.fy, L.cx, L.cy, zmax, 0.f, 0.f, L.w, L.h, 0, TDV_POSE_MODEL_TO_CAMERA};
     const float* zs = L.z + (size_t)(p + 1) * L.npx;
     const float* zt = L.z + (size_t)p * L.npx;
     const float* nt = L.nrm + 3 * (size_t)p * L.npx;
@@ -157,14 +153,15 @@ void k_od_iterate(OdLevel L, float zmax, float depth_diff, OdState* __restrict__
     if (z0 > 0.f) {
         float S[3], qx, qy, qz;
         int u, w;
-        od_vertex(i % L.w, i / L.w, z0, L, S);
-        if (verify_project<1>(P, cam, S[0], S[1], S[2], u, w, qx, qy, qz) && u >= 0 && u < L.w && w >= 0 && w < L.h) {      // O5
+        pinhole_vertex(i % L.w, i / L.w, z0, L.k, S);
+        pose_apply(P, S[0], S[1], S[2], qx, qy, qz);                                   // O5: the source vertex in the target's camera
+        if (pinhole_project<1>(L.k, zmax, qx, qy, qz, u, w) && u >= 0 && u < L.w && w >= 0 && w < L.h) {
             const size_t j = (size_t)w * L.w + u;
             CorrTgt G;
             G.n[0] = nt[3 * j]; G.n[1] = nt[3 * j + 1]; G.n[2] = nt[3 * j + 2];
             const float ztj = zt[j];
             if ((G.n[0] != 0.f || G.n[1] != 0.f || G.n[2] != 0.f) && fabsf(ztj - qz) <= depth_diff) {
-                od_vertex(u, w, ztj, L, G.q);
+                pinhole_vertex(u, w, ztj, L.k, G.q);
                 const float ex = qx - G.q[0], ey = qy - G.q[1], ez = qz - G.q[2];
                 CorrRec R;
                 corr_rec<0>(qx, qy, qz, ex * ex + (ey * ey + ez * ez), G, R);     // O6
@@ -219,40 +216,22 @@ __global__ void k_od_level(OdState* __restrict__ st_all, int n_pairs, int done_l
 }
 
 // ------------------------------------------------------------------------------------------------ host
-bool od_params_ok(const tdv_odometry_params* p, int w, int h) {
-    if (!p || !(p->depth_diff > 0.f) || !std::isfinite(p->depth_diff) || !(p->zmax > 0.f) || !std::isfinite(p->zmax)) return false;
-    if (p->n_levels < 1 || p->n_levels > OD_L) return false;
-    for (int l = 0; l < OD_L; ++l) if (p->max_iterations[l] < 0) return false;
-    if ((size_t)w * h != 0 && ((w >> (p->n_levels - 1)) < 1 || (h >> (p->n_levels - 1)) < 1)) return false;      // no level with a side of 0
-    return true;
-}
-bool od_camera_ok(int w, int h, float scale, float fx, float fy) {
-    return w >= 0 && h >= 0 && w <= TDV_VERIFY_MAX_SIDE && h <= TDV_VERIFY_MAX_SIDE && scale > 0.f && std::isfinite(scale) && fx > 0.f &&
-           std::isfinite(fx) && fy > 0.f && std::isfinite(fy);
-}
-
-void od_identity(float* T) { for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f; }
-
-// the start pose with zeros: what a pair without work returns
-void od_empty_result(const float* T0, tdv_odometry_result* out) {
-    std::memset(out, 0, sizeof(*out));
-    if (T0) std::memcpy(out->T, T0, 64); else od_identity(out->T);
-}
-
 struct OdPyramid { OdLevel lv[OD_L]; int n_levels, n_frames; int* nvalid; };
 
-// Workspace for n_frames frames of w x h at n_levels levels; O4's intrinsics.  Nothing is enqueued but the counts' memset.
-int od_alloc(tdv_ctx* ctx, int n_frames, int w, int h, float fx, float fy, float cx, float cy, int n_levels, OdPyramid* py) {
+// Workspace for n_frames frames of the camera's size at n_levels levels; O4's intrinsics.  Nothing is enqueued but the counts' memset.
+int od_alloc(tdv_ctx* ctx, int n_frames, const FrameCamera& cam, int n_levels, OdPyramid* py) {
     py->n_levels = n_levels; py->n_frames = n_frames;
     TDV_TRY(ws_alloc(ctx, (size_t)n_frames * OD_L, &py->nvalid));
     TDV_HIP(ctx, hipMemsetAsync(py->nvalid, 0, (size_t)n_frames * OD_L * sizeof(int), ctx->stream));
+    int w = cam.w, h = cam.h;
+    Pinhole k = cam.k;
     for (int l = 0; l < n_levels; ++l) {
         OdLevel& L = py->lv[l];
-        L.w = w; L.h = h; L.npx = w * h; L.level = l; L.fx = fx; L.fy = fy; L.cx = cx; L.cy = cy; L.nvalid = py->nvalid;
+        L.w = w; L.h = h; L.npx = w * h; L.level = l; L.k = k; L.nvalid = py->nvalid;
         TDV_TRY(ws_alloc(ctx, (size_t)n_frames * L.npx, &L.z));
         TDV_TRY(ws_alloc(ctx, (size_t)n_frames * L.npx * 3, &L.nrm));
         w /= 2; h /= 2;
-        fx = fx * 0.5f; fy = fy * 0.5f; cx = (cx - 0.5f) * 0.5f; cy = (cy - 0.5f) * 0.5f;
+        k = Pinhole{k.fx * 0.5f, k.fy * 0.5f, (k.cx - 0.5f) * 0.5f, (k.cy - 0.5f) * 0.5f};
     }
     return TDV_OK;
 }
@@ -260,10 +239,9 @@ int od_alloc(tdv_ctx* ctx, int n_frames, int w, int h, float fx, float fy, float
 unsigned od_blocks(int npx) { return (unsigned)((npx + OD_T - 1) / OD_T); }
 
 // O1 for `count` frames stored back to back at d_raw, into the pyramid's slots from `slot` on
-int od_depth0(tdv_ctx* ctx, const OdPyramid& py, const uint16_t* d_raw, int slot, int count, float scale, float zmax) {
+int od_depth0(tdv_ctx* ctx, const OdPyramid& py, const uint16_t* d_raw, int slot, int count, float inv_scale, float zmax) {
     const OdLevel& L = py.lv[0];
-    k_od_depth0<<<dim3(od_blocks(L.npx), count), OD_T, 0, ctx->stream>>>(d_raw, L.npx, (float)(1.0 / (double)scale), zmax,
-                                                                        L.z + (size_t)slot * L.npx);
+    k_od_depth0<<<dim3(od_blocks(L.npx), count), OD_T, 0, ctx->stream>>>(d_raw, L.npx, inv_scale, zmax, L.z + (size_t)slot * L.npx);
     TDV_CHECK_LAUNCH(ctx);
     return TDV_OK;
 }
@@ -290,11 +268,11 @@ int od_build(tdv_ctx* ctx, const OdPyramid& py, float depth_diff) {
 struct OdRun { OdState* st; double* part; unsigned* tickets; };
 
 // states from the start poses (h_T0: n_pairs x 16, or nullptr for identities), partial rows for the finest level, tickets at 0
-int od_run_alloc(tdv_ctx* ctx, const OdPyramid& py, int n_pairs, const float* h_T0, size_t t0_stride, OdRun* run) {
+int od_run_alloc(tdv_ctx* ctx, const OdPyramid& py, int n_pairs, const float* h_T0, OdRun* run) {
     std::vector<OdState> init((size_t)n_pairs);
     std::memset(init.data(), 0, init.size() * sizeof(OdState));
     for (int p = 0; p < n_pairs; ++p) {
-        if (h_T0) std::memcpy(init[p].s.T, h_T0 + (size_t)p * t0_stride, 64); else od_identity(init[p].s.T);
+        if (h_T0) std::memcpy(init[p].s.T, h_T0 + (size_t)p * 16, 64); else pose_identity(init[p].s.T);
         std::memcpy(init[p].s.res_T, init[p].s.T, 64);
     }
     TDV_TRY(upload(ctx, init.data(), init.size(), &run->st));
@@ -304,8 +282,11 @@ int od_run_alloc(tdv_ctx* ctx, const OdPyramid& py, int n_pairs, const float* h_
     return TDV_OK;
 }
 
-// O8 for n_pairs pairs together (pair p: frames p + 1 onto p), the results down in one read-back
-int od_iterate(tdv_ctx* ctx, const OdPyramid& py, const tdv_odometry_params& prm, int n_pairs, const OdRun& run, tdv_odometry_result* out) {
+// O8 for n_pairs pairs together (pair p: frames p + 1 onto p), the results down in one read-back.  rider (optional, tsdf_track.hpp):
+// the caller's bytes land behind the records in the pinned block - the offset is formed here, from the size reserved here - and come
+// down in the same enqueue, before the one wait.
+int od_iterate(tdv_ctx* ctx, const OdPyramid& py, const tdv_odometry_params& prm, int n_pairs, const OdRun& run, tdv_odometry_result* out,
+               const OdRider* rider) {
     hipStream_t s = ctx->stream;
     const unsigned pb = (unsigned)((n_pairs + 63) / 64);
     int prev = -1;
@@ -319,9 +300,12 @@ int od_iterate(tdv_ctx* ctx, const OdPyramid& py, const tdv_odometry_params& prm
     }
     k_od_level<<<pb, 64, 0, s>>>(run.st, n_pairs, prev);
     TDV_CHECK_LAUNCH(ctx);
-    TDV_TRY(pin_reserve(ctx, (size_t)n_pairs * sizeof(OdState)));
+    const size_t rec_bytes = align_up((size_t)n_pairs * sizeof(OdState), 16);
+    TDV_TRY(pin_reserve(ctx, rec_bytes + (rider ? rider->bytes : 0)));
     TDV_HIP(ctx, hipMemcpyAsync(ctx->pin, run.st, (size_t)n_pairs * sizeof(OdState), hipMemcpyDeviceToHost, s));
+    if (rider) TDV_HIP(ctx, hipMemcpyAsync(ctx->pin + rec_bytes, rider->d_src, rider->bytes, hipMemcpyDeviceToHost, s));
     TDV_TRY(finish(ctx));
+    if (rider) std::memcpy(rider->h_dst, ctx->pin + rec_bytes, rider->bytes);
     const OdState* h = reinterpret_cast<const OdState*>(ctx->pin);
     for (int p = 0; p < n_pairs; ++p) {
         std::memcpy(out[p].T, h[p].s.T, 64);
@@ -331,30 +315,28 @@ int od_iterate(tdv_ctx* ctx, const OdPyramid& py, const tdv_odometry_params& prm
     return TDV_OK;
 }
 
-// a pair from device frames (the target in slot 0, the source in slot 1)
-int od_pair(tdv_ctx* ctx, const uint16_t* d_src, const uint16_t* d_tgt, int w, int h, float scale, float fx, float fy, float cx, float cy,
-            const float* h_T0, const tdv_odometry_params& prm, tdv_odometry_result* out) {
-    OdPyramid py;
-    OdRun run;
-    TDV_TRY(od_alloc(ctx, 2, w, h, fx, fy, cx, cy, prm.n_levels, &py));
-    TDV_TRY(od_depth0(ctx, py, d_tgt, 0, 1, scale, prm.zmax));
-    TDV_TRY(od_depth0(ctx, py, d_src, 1, 1, scale, prm.zmax));
-    TDV_TRY(od_build(ctx, py, prm.depth_diff));
-    TDV_TRY(od_run_alloc(ctx, py, 1, h_T0, 16, &run));
-    return od_iterate(ctx, py, prm, 1, run, out);
+// A pair ready to iterate: the workspace, level 0 of the target (slot 0: O1 or O10, as the target comes) and of the source (slot 1), the
+// pyramid, and the run state from the start pose
+int od_pair_setup(tdv_ctx* ctx, const uint16_t* d_src, const OdTarget& tgt, const FrameCamera& cam, const float* h_T0,
+                  const tdv_odometry_params& prm, OdPyramid* py, OdRun* run) {
+    TDV_TRY(od_alloc(ctx, 2, cam, prm.n_levels, py));
+    TDV_TRY(tgt.raw ? od_depth0(ctx, *py, tgt.raw, 0, 1, cam.inv_scale(), prm.zmax) : od_depth0(ctx, *py, tgt.depth, 0, prm.zmax));
+    TDV_TRY(od_depth0(ctx, *py, d_src, 1, 1, cam.inv_scale(), prm.zmax));
+    TDV_TRY(od_build(ctx, *py, prm.depth_diff));
+    return od_run_alloc(ctx, *py, 1, h_T0, run);
 }
 
 // O2 and O3 of one frame (level 0): maps, rows and count.  host: every output is a host array and goes through the workspace.
-int od_maps(tdv_ctx* ctx, const uint16_t* d_raw, int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_odometry_params& prm,
-            float* vertex_map, float* normal_map, float* out_xyz, float* out_normals, int capacity, int* n_out, bool host) {
+int od_maps(tdv_ctx* ctx, const uint16_t* d_raw, const FrameCamera& cam, const tdv_odometry_params& prm, float* vertex_map, float* normal_map,
+            float* out_xyz, float* out_normals, int capacity, int* n_out, bool host) {
     hipStream_t s = ctx->stream;
-    OdLevel L{w, h, w * h, 0, fx, fy, cx, cy, nullptr, nullptr, nullptr};
-    const size_t npx = (size_t)L.npx;
+    OdLevel L{cam.w, cam.h, cam.w * cam.h, 0, cam.k, nullptr, nullptr, nullptr};
+    const size_t npx = cam.npx();
     float *d_vm = host ? nullptr : vertex_map, *d_nm = host ? nullptr : normal_map, *d_xyz = host ? nullptr : out_xyz,
           *d_nrm = host ? nullptr : out_normals;
     int *flag = nullptr, *pos = nullptr, *d_total = nullptr, total = 0;
     TDV_TRY(ws_alloc(ctx, npx, &L.z));
-    k_od_depth0<<<dim3(od_blocks(L.npx), 1), OD_T, 0, s>>>(d_raw, L.npx, (float)(1.0 / (double)scale), prm.zmax, L.z);
+    k_od_depth0<<<dim3(od_blocks(L.npx), 1), OD_T, 0, s>>>(d_raw, L.npx, cam.inv_scale(), prm.zmax, L.z);
     if (n_out) {
         // the count first, so that a capacity that is too small ends the call before anything is written
         TDV_TRY(ws_alloc(ctx, npx, &flag));
@@ -385,33 +367,65 @@ int od_maps(tdv_ctx* ctx, const uint16_t* d_raw, int w, int h, float scale, floa
     return finish(ctx);
 }
 
-bool od_maps_args_ok(const tdv_ctx* ctx, const void* raw, int w, int h, float scale, float fx, float fy, const tdv_odometry_params* prm,
-                     const float* out_xyz, const float* out_normals, int capacity, const int* n_out) {
-    if (!ctx || !od_camera_ok(w, h, scale, fx, fy) || !prm || !od_params_ok(prm, 0, 0) || capacity < 0) return false;
-    if ((size_t)w * h != 0 && !raw) return false;
+bool od_maps_args_ok(const tdv_ctx* ctx, const void* raw, const FrameCamera& cam, const tdv_odometry_params* prm, const float* out_xyz,
+                     const float* out_normals, int capacity, const int* n_out) {
+    if (!ctx || !frame_camera_ok(cam, true) || !prm || !odometry_params_ok(prm, 0, 0) || capacity < 0) return false;
+    if (cam.npx() != 0 && !raw) return false;
     if (capacity > 0 && !out_xyz && !out_normals) return false;
     if ((out_xyz || out_normals) && !n_out) return false;   // rows need the count: it is what bounds them
     return true;
 }
 
+// what the entry points with two frames check alike, before the call begins
+bool od_frames_args_ok(const tdv_ctx* ctx, const void* src, const OdTarget& tgt, const FrameCamera& cam, const tdv_odometry_params* prm) {
+    if (!ctx || !frame_camera_ok(cam, true) || !odometry_params_ok(prm, cam.w, cam.h)) return false;
+    return cam.npx() == 0 || (src && (tgt.raw || tgt.depth));
+}
+
+template <class T>
+int od_upload_in_place(tdv_ctx* ctx, const T** p, size_t n) {
+    T* d;
+    TDV_TRY(upload(ctx, *p, n, &d));
+    *p = d;
+    return TDV_OK;
+}
+
+// The four pair entry points after they have named their camera and target.  host: the frames are host arrays and go up first.
+int od_pair_call(tdv_ctx* ctx, const uint16_t* raw_src, OdTarget tgt, const FrameCamera& cam, const float* h_T0, const tdv_odometry_params* params,
+                 tdv_odometry_result* out, bool host) {
+    if (!od_frames_args_ok(ctx, raw_src, tgt, cam, params) || !out) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    odometry_empty_result(h_T0, out);
+    if (cam.npx() == 0) return TDV_OK;
+    if (host) {
+        TDV_TRY(od_upload_in_place(ctx, &raw_src, cam.npx()));
+        TDV_TRY(tgt.raw ? od_upload_in_place(ctx, &tgt.raw, cam.npx()) : od_upload_in_place(ctx, &tgt.depth, cam.npx()));
+    }
+    return odometry_pair(ctx, raw_src, tgt, cam, h_T0, *params, out);
+}
+
 }  // namespace
 
-// tsdf_track.hpp: the checks and the pair against an f32 target for tsdf_raycast.hip
-bool odometry_camera_ok(int w, int h, float scale, float fx, float fy) { return od_camera_ok(w, h, scale, fx, fy); }
-bool odometry_params_ok(const tdv_odometry_params* params, int w, int h) { return od_params_ok(params, w, h); }
-void odometry_empty_result(const float* h_T0, tdv_odometry_result* out) { od_empty_result(h_T0, out); }
+// ---- defined here once, and called under these names from here and from tsdf_raycast.hip (tsdf_track.hpp)
+bool odometry_params_ok(const tdv_odometry_params* p, int w, int h) {
+    if (!p || !positive_finite(p->depth_diff) || !positive_finite(p->zmax)) return false;
+    if (p->n_levels < 1 || p->n_levels > OD_L) return false;
+    for (int l = 0; l < OD_L; ++l) if (p->max_iterations[l] < 0) return false;
+    if ((size_t)w * h != 0 && ((w >> (p->n_levels - 1)) < 1 || (h >> (p->n_levels - 1)) < 1)) return false;      // no level with a side of 0
+    return true;
+}
 
-// od_pair with the target's level 0 by O10 (the target in slot 0, the source in slot 1)
-int odometry_pair_to_depth(tdv_ctx* ctx, const uint16_t* d_raw_src, const float* d_depth_tgt, int w, int h, float scale, float fx, float fy,
-                           float cx, float cy, const float* h_T0, const tdv_odometry_params& prm, tdv_odometry_result* out) {
+void odometry_empty_result(const float* T0, tdv_odometry_result* out) {
+    std::memset(out, 0, sizeof(*out));
+    if (T0) std::memcpy(out->T, T0, 64); else pose_identity(out->T);
+}
+
+int odometry_pair(tdv_ctx* ctx, const uint16_t* d_raw_src, const OdTarget& tgt, const FrameCamera& cam, const float* h_T0,
+                  const tdv_odometry_params& prm, tdv_odometry_result* out, const OdRider* rider) {
     OdPyramid py;
     OdRun run;
-    TDV_TRY(od_alloc(ctx, 2, w, h, fx, fy, cx, cy, prm.n_levels, &py));
-    TDV_TRY(od_depth0(ctx, py, d_depth_tgt, 0, prm.zmax));
-    TDV_TRY(od_depth0(ctx, py, d_raw_src, 1, 1, scale, prm.zmax));
-    TDV_TRY(od_build(ctx, py, prm.depth_diff));
-    TDV_TRY(od_run_alloc(ctx, py, 1, h_T0, 16, &run));
-    return od_iterate(ctx, py, prm, 1, run, out);
+    TDV_TRY(od_pair_setup(ctx, d_raw_src, tgt, cam, h_T0, prm, &py, &run));
+    return od_iterate(ctx, py, prm, 1, run, out, rider);
 }
 
 }  // namespace tdv
@@ -429,47 +443,41 @@ void tdv_odometry_default_params(tdv_odometry_params* p) {
 int tdv_depth_maps_dev(tdv_ctx* ctx, const uint16_t* d_raw, int width, int height, float scale, float fx, float fy, float cx, float cy,
                        const tdv_odometry_params* params, float* d_vertex_map, float* d_normal_map, float* d_out_xyz, float* d_out_normals,
                        int capacity, int* n_out) {
-    if (!od_maps_args_ok(ctx, d_raw, width, height, scale, fx, fy, params, d_out_xyz, d_out_normals, capacity, n_out)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!od_maps_args_ok(ctx, d_raw, cam, params, d_out_xyz, d_out_normals, capacity, n_out)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     if (n_out) *n_out = 0;
-    if ((size_t)width * height == 0) return TDV_OK;
-    return od_maps(ctx, d_raw, width, height, scale, fx, fy, cx, cy, *params, d_vertex_map, d_normal_map, d_out_xyz, d_out_normals, capacity,
-                   n_out, false);
+    if (cam.npx() == 0) return TDV_OK;
+    return od_maps(ctx, d_raw, cam, *params, d_vertex_map, d_normal_map, d_out_xyz, d_out_normals, capacity, n_out, false);
 }
 
 int tdv_depth_maps(tdv_ctx* ctx, const uint16_t* raw, int width, int height, float scale, float fx, float fy, float cx, float cy,
                    const tdv_odometry_params* params, float* vertex_map, float* normal_map, float* out_xyz, float* out_normals, int capacity,
                    int* n_out) {
-    if (!od_maps_args_ok(ctx, raw, width, height, scale, fx, fy, params, out_xyz, out_normals, capacity, n_out)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!od_maps_args_ok(ctx, raw, cam, params, out_xyz, out_normals, capacity, n_out)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     if (n_out) *n_out = 0;
-    const size_t npx = (size_t)width * height;
-    if (npx == 0) return TDV_OK;
+    if (cam.npx() == 0) return TDV_OK;
     uint16_t* d_raw;
-    TDV_TRY(upload(ctx, raw, npx, &d_raw));
-    return od_maps(ctx, d_raw, width, height, scale, fx, fy, cx, cy, *params, vertex_map, normal_map, out_xyz, out_normals, capacity, n_out, true);
+    TDV_TRY(upload(ctx, raw, cam.npx(), &d_raw));
+    return od_maps(ctx, d_raw, cam, *params, vertex_map, normal_map, out_xyz, out_normals, capacity, n_out, true);
 }
 
 int tdv_depth_odometry_terms_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const uint16_t* d_raw_tgt, int width, int height, float scale, float fx,
                                  float fy, float cx, float cy, const float* h_T, int level, const tdv_odometry_params* params, double* h_sums,
                                  int* n_valid_src) {
-    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !h_T || !h_sums || level < 0 ||
-        level >= params->n_levels)
-        return TDV_ERR_BAD_ARG;
-    const size_t npx = (size_t)width * height;
-    if (npx != 0 && (!d_raw_src || !d_raw_tgt)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    const OdTarget tgt{d_raw_tgt, nullptr};
+    if (!od_frames_args_ok(ctx, d_raw_src, tgt, cam, params) || !h_T || !h_sums || level < 0 || level >= params->n_levels) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     for (int k = 0; k < OD_NV; ++k) h_sums[k] = 0.0;
     if (n_valid_src) *n_valid_src = 0;
-    if (npx == 0) return TDV_OK;
+    if (cam.npx() == 0) return TDV_OK;
     OdPyramid py;
     OdRun run;
     OdTerms *d_terms, terms;
-    TDV_TRY(od_alloc(ctx, 2, width, height, fx, fy, cx, cy, params->n_levels, &py));
-    TDV_TRY(od_depth0(ctx, py, d_raw_tgt, 0, 1, scale, params->zmax));
-    TDV_TRY(od_depth0(ctx, py, d_raw_src, 1, 1, scale, params->zmax));
-    TDV_TRY(od_build(ctx, py, params->depth_diff));
-    TDV_TRY(od_run_alloc(ctx, py, 1, h_T, 16, &run));
+    TDV_TRY(od_pair_setup(ctx, d_raw_src, tgt, cam, h_T, *params, &py, &run));
     TDV_TRY(ws_alloc(ctx, 1, &d_terms));
     TDV_TRY(pin_reserve(ctx, sizeof(OdTerms)));
     const OdLevel& L = py.lv[level];
@@ -483,81 +491,51 @@ int tdv_depth_odometry_terms_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const 
 
 int tdv_depth_odometry_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const uint16_t* d_raw_tgt, int width, int height, float scale, float fx,
                            float fy, float cx, float cy, const float* h_T0, const tdv_odometry_params* params, tdv_odometry_result* out) {
-    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !out) return TDV_ERR_BAD_ARG;
-    const size_t npx = (size_t)width * height;
-    if (npx != 0 && (!d_raw_src || !d_raw_tgt)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(call_begin(ctx));
-    od_empty_result(h_T0, out);
-    if (npx == 0) return TDV_OK;
-    return od_pair(ctx, d_raw_src, d_raw_tgt, width, height, scale, fx, fy, cx, cy, h_T0, *params, out);
+    return od_pair_call(ctx, d_raw_src, OdTarget{d_raw_tgt, nullptr}, FrameCamera{width, height, scale, {fx, fy, cx, cy}}, h_T0, params, out, false);
 }
 
 int tdv_depth_odometry(tdv_ctx* ctx, const uint16_t* raw_src, const uint16_t* raw_tgt, int width, int height, float scale, float fx, float fy,
                        float cx, float cy, const float* T0, const tdv_odometry_params* params, tdv_odometry_result* out) {
-    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !out) return TDV_ERR_BAD_ARG;
-    const size_t npx = (size_t)width * height;
-    if (npx != 0 && (!raw_src || !raw_tgt)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(call_begin(ctx));
-    od_empty_result(T0, out);
-    if (npx == 0) return TDV_OK;
-    uint16_t *d_src, *d_tgt;
-    TDV_TRY(upload(ctx, raw_src, npx, &d_src));
-    TDV_TRY(upload(ctx, raw_tgt, npx, &d_tgt));
-    return od_pair(ctx, d_src, d_tgt, width, height, scale, fx, fy, cx, cy, T0, *params, out);
+    return od_pair_call(ctx, raw_src, OdTarget{raw_tgt, nullptr}, FrameCamera{width, height, scale, {fx, fy, cx, cy}}, T0, params, out, true);
 }
 
 int tdv_depth_odometry_to_depth_dev(tdv_ctx* ctx, const uint16_t* d_raw_src, const float* d_depth_tgt, int width, int height, float scale,
                                     float fx, float fy, float cx, float cy, const float* h_T0, const tdv_odometry_params* params,
                                     tdv_odometry_result* out) {
-    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !out) return TDV_ERR_BAD_ARG;
-    const size_t npx = (size_t)width * height;
-    if (npx != 0 && (!d_raw_src || !d_depth_tgt)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(call_begin(ctx));
-    od_empty_result(h_T0, out);
-    if (npx == 0) return TDV_OK;
-    return odometry_pair_to_depth(ctx, d_raw_src, d_depth_tgt, width, height, scale, fx, fy, cx, cy, h_T0, *params, out);
+    return od_pair_call(ctx, d_raw_src, OdTarget{nullptr, d_depth_tgt}, FrameCamera{width, height, scale, {fx, fy, cx, cy}}, h_T0, params, out, false);
 }
 
 int tdv_depth_odometry_to_depth(tdv_ctx* ctx, const uint16_t* raw_src, const float* depth_tgt, int width, int height, float scale, float fx,
                                 float fy, float cx, float cy, const float* T0, const tdv_odometry_params* params, tdv_odometry_result* out) {
-    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || !out) return TDV_ERR_BAD_ARG;
-    const size_t npx = (size_t)width * height;
-    if (npx != 0 && (!raw_src || !depth_tgt)) return TDV_ERR_BAD_ARG;
-    TDV_TRY(call_begin(ctx));
-    od_empty_result(T0, out);
-    if (npx == 0) return TDV_OK;
-    uint16_t* d_src;
-    float* d_tgt;
-    TDV_TRY(upload(ctx, raw_src, npx, &d_src));
-    TDV_TRY(upload(ctx, depth_tgt, npx, &d_tgt));
-    return odometry_pair_to_depth(ctx, d_src, d_tgt, width, height, scale, fx, fy, cx, cy, T0, *params, out);
+    return od_pair_call(ctx, raw_src, OdTarget{nullptr, depth_tgt}, FrameCamera{width, height, scale, {fx, fy, cx, cy}}, T0, params, out, true);
 }
 
 int tdv_depth_odometry_sequence_dev(tdv_ctx* ctx, const uint16_t* d_raw, int n_frames, int width, int height, float scale, float fx, float fy,
                                     float cx, float cy, const float* h_init, const tdv_odometry_params* params, float* h_poses,
                                     tdv_odometry_result* h_pairs) {
-    if (!ctx || !od_camera_ok(width, height, scale, fx, fy) || !od_params_ok(params, width, height) || n_frames < 0 ||
-        n_frames > TDV_TSDF_MAX_FRAMES || (n_frames > 0 && !h_poses))
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!ctx || !frame_camera_ok(cam, true) || !odometry_params_ok(params, width, height) || n_frames < 0 || n_frames > TDV_TSDF_MAX_FRAMES ||
+        (n_frames > 0 && !h_poses))
         return TDV_ERR_BAD_ARG;
-    const size_t npx = (size_t)width * height;
+    const size_t npx = cam.npx();
     if (npx != 0 && n_frames > 0 && !d_raw) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     if (n_frames == 0) return TDV_OK;
     const int n_pairs = n_frames - 1;
     std::vector<tdv_odometry_result> res((size_t)n_frames);
     std::memset(&res[0], 0, sizeof(res[0]));
-    for (int k = 1; k < n_frames; ++k) od_empty_result(h_init ? h_init + 16 * (size_t)k : nullptr, &res[k]);
+    for (int k = 1; k < n_frames; ++k) odometry_empty_result(h_init ? h_init + 16 * (size_t)k : nullptr, &res[k]);
     if (npx != 0 && n_pairs > 0) {
         OdPyramid py;
         OdRun run;
-        TDV_TRY(od_alloc(ctx, n_frames, width, height, fx, fy, cx, cy, params->n_levels, &py));
-        TDV_TRY(od_depth0(ctx, py, d_raw, 0, n_frames, scale, params->zmax));
+        TDV_TRY(od_alloc(ctx, n_frames, cam, params->n_levels, &py));
+        TDV_TRY(od_depth0(ctx, py, d_raw, 0, n_frames, cam.inv_scale(), params->zmax));
         TDV_TRY(od_build(ctx, py, params->depth_diff));
-        TDV_TRY(od_run_alloc(ctx, py, n_pairs, h_init ? h_init + 16 : nullptr, 16, &run));
-        TDV_TRY(od_iterate(ctx, py, *params, n_pairs, run, res.data() + 1));
+        TDV_TRY(od_run_alloc(ctx, py, n_pairs, h_init ? h_init + 16 : nullptr, &run));
+        TDV_TRY(od_iterate(ctx, py, *params, n_pairs, run, res.data() + 1, nullptr));
     }
     // O9: P_0 = I, P_k = P_(k-1) T_k, each entry the f64 sum of four f64 products in index order, rounded once
-    od_identity(h_poses);
+    pose_identity(h_poses);
     for (int k = 1; k < n_frames; ++k) pose_chain_product(h_poses + 16 * (size_t)(k - 1), res[k].T, h_poses + 16 * (size_t)k);
     if (h_pairs) std::memcpy(h_pairs, res.data(), (size_t)n_frames * sizeof(tdv_odometry_result));
     return TDV_OK;

@@ -9,11 +9,13 @@
 //                    pose reaches the lanes through scalar loads.  T15's march in z, T16's one interpolation, then T17 and T18 for the
 //                    maps that were asked for (MAPS) - six more samples, only on lanes that hit.  COUNT: the workgroup's hits by
 //                    fixed_tree.hpp's block count, one atomic per workgroup.  No LDS beyond that count's four ints.
-// Tracking (K1 to K3) is this kernel into a workspace image, odometry.hip's pair against that image (O10) and O9's product on the host;
-// the sequence adds tsdf.hip's integrate pass per frame.  Everything a kernel reads from the workspace is written by the call first.
+// The voxel, T14's grid coordinate, the default truncation and the normalisation are tsdf_volume.hpp's; T13's pose, T17's vertex and
+// T18's rotation are frame_pose.hpp's.
+// Tracking (K1 to K3) is this kernel into a workspace image, odometry.hip's pair against that image (O10, tsdf_track.hpp) with the hit
+// count as the rider of its read-back, and O9's product on the host; the sequence adds tsdf.hip's integrate pass per frame.  Everything a kernel reads from the workspace is written by the call first.
 #pragma clang fp contract(off)
 #include "tdv_internal.hpp"
-#include "depth_rules.hpp"
+#include "tsdf_volume.hpp"
 #include "fixed_tree.hpp"
 #include "tsdf_track.hpp"
 #include <cmath>
@@ -29,48 +31,35 @@ constexpr int RC_TILE = 8;
 static_assert(RC_TILE * RC_TILE == 64, "a wave owns one tile");
 static_assert(sizeof(tdv_tsdf_raycast_params) == 8 && sizeof(tdv_tsdf_track_result) == 184, "include/tdv_hip.h: the structs' layout");
 
-struct alignas(8) RcPair { float f, w; };                  // a voxel of the volume: 8 bytes, loaded whole (one global_load_dwordx2)
-struct RcRow3 { float x, y, z; };
-struct RcPose { float T[16]; };
-struct RcCam { float fx, fy, cx, cy; int w, h; };
+struct RcCam { Pinhole k; int w, h; };
 struct RcMarch { float zmin, zmax, trunc, min_weight; int max_steps, direction; };
 
 // T13: the volume-frame point of pixel (u, v) at camera depth z
-__device__ __forceinline__ void rc_point(int u, int v, float z, const RcCam& c, const RcPose& P, int direction, float* p) {
+__device__ __forceinline__ void rc_point(int u, int v, float z, const RcCam& c, const Pose16& P, int direction, float* p) {
     float C[3];
-    emit_point((float)u, (float)v, z, c.cx, c.cy, PlainDiv{c.fx, c.fy}, C, (float*)nullptr, (const uint8_t*)nullptr, 0, (size_t)0);      // O2
-    const float* T = P.T;
-    if (direction == TDV_POSE_SOURCE_ONTO_TARGET) {
-        p[0] = ((T[0] * C[0] + T[4] * C[1]) + T[8] * C[2]) + T[12];
-        p[1] = ((T[1] * C[0] + T[5] * C[1]) + T[9] * C[2]) + T[13];
-        p[2] = ((T[2] * C[0] + T[6] * C[1]) + T[10] * C[2]) + T[14];
-    } else {
-        const float d0 = C[0] - T[12], d1 = C[1] - T[13], d2 = C[2] - T[14];
-        p[0] = (T[0] * d0 + T[1] * d1) + T[2] * d2;
-        p[1] = (T[4] * d0 + T[5] * d1) + T[6] * d2;
-        p[2] = (T[8] * d0 + T[9] * d1) + T[10] * d2;
-    }
+    pinhole_vertex(u, v, z, c.k, C);                                               // O2
+    pose_out_of_camera(P, direction, C, p);
 }
 
 // one voxel: a single 8-byte load
-__device__ __forceinline__ RcPair rc_pair(const RcPair* __restrict__ a) {
+__device__ __forceinline__ TsdfVoxel rc_pair(const TsdfVoxel* __restrict__ a) {
     const unsigned long long q = *reinterpret_cast<const unsigned long long*>(a);                       // (two floats would be loaded apart)
-    return RcPair{__uint_as_float((unsigned)q), __uint_as_float((unsigned)(q >> 32))};
+    return TsdfVoxel{__uint_as_float((unsigned)q), __uint_as_float((unsigned)(q >> 32))};
 }
 
 __device__ __forceinline__ float rc_lerp(float a, float b, float t) { return a + t * (b - a); }
 
 // T14: the field at p; false where the sample is unknown.  The grid coordinates are checked as floats, so every index below is inside
 // the volume: 0 <= i <= n - 2 on each axis.
-__device__ __forceinline__ bool rc_sample(const tdv_tsdf_volume& V, float min_weight, const RcPair* __restrict__ vol, const float* p, float& s) {
-    const float g0 = (p[0] - V.origin[0]) / V.voxel_length - 0.5f, g1 = (p[1] - V.origin[1]) / V.voxel_length - 0.5f,
-                g2 = (p[2] - V.origin[2]) / V.voxel_length - 0.5f;
+__device__ __forceinline__ bool rc_sample(const tdv_tsdf_volume& V, float min_weight, const TsdfVoxel* __restrict__ vol, const float* p, float& s) {
+    const float g0 = tsdf_grid_coord(V.origin[0], p[0], V.voxel_length), g1 = tsdf_grid_coord(V.origin[1], p[1], V.voxel_length),
+                g2 = tsdf_grid_coord(V.origin[2], p[2], V.voxel_length);
     if (!(g0 >= 0.f && g0 < (float)(V.nx - 1) && g1 >= 0.f && g1 < (float)(V.ny - 1) && g2 >= 0.f && g2 < (float)(V.nz - 1))) return false;
     const float i0 = floorf(g0), i1 = floorf(g1), i2 = floorf(g2);
     const float t0 = g0 - i0, t1 = g1 - i1, t2 = g2 - i2;
     const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * V.ny;
-    const RcPair* a = vol + ((size_t)(int)i2 * V.ny + (size_t)(int)i1) * V.nx + (size_t)(int)i0;
-    const RcPair q000 = rc_pair(a), q100 = rc_pair(a + 1), q010 = rc_pair(a + sy), q110 = rc_pair(a + sy + 1), q001 = rc_pair(a + sz),
+    const TsdfVoxel* a = vol + ((size_t)(int)i2 * V.ny + (size_t)(int)i1) * V.nx + (size_t)(int)i0;
+    const TsdfVoxel q000 = rc_pair(a), q100 = rc_pair(a + 1), q010 = rc_pair(a + sy), q110 = rc_pair(a + sy + 1), q001 = rc_pair(a + sz),
                  q101 = rc_pair(a + sz + 1), q011 = rc_pair(a + sz + sy), q111 = rc_pair(a + sz + sy + 1);
     const float mw = min_weight;
     if (!((q000.w >= mw) & (q100.w >= mw) & (q010.w >= mw) & (q110.w >= mw) & (q001.w >= mw) & (q101.w >= mw) & (q011.w >= mw) & (q111.w >= mw)))
@@ -85,7 +74,7 @@ __device__ __forceinline__ bool rc_sample(const tdv_tsdf_volume& V, float min_we
 // blockIdx.x * 4 + wave = the tile, x fastest; lane = (v & 7) * 8 + (u & 7)
 template <bool MAPS, bool COUNT>
 __global__ __launch_bounds__(RC_T)
-void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, RcPose P, RcMarch m, const RcPair* __restrict__ vol, float* __restrict__ depth,
+void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, Pose16 P, RcMarch m, const TsdfVoxel* __restrict__ vol, float* __restrict__ depth,
                     float* __restrict__ vertex_map, float* __restrict__ normal_map, unsigned long long* __restrict__ n_hit) {
     __shared__ int s_cnt[4];
     const int lane = threadIdx.x & 63, tiles_x = (c.w + RC_TILE - 1) / RC_TILE;
@@ -112,11 +101,11 @@ void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, RcPose P, RcMarch m, const RcPai
         const size_t i = (size_t)v * c.w + u;
         if (depth) depth[i] = hit ? zh : 0.0f;
         if (MAPS) {
-            RcRow3 vr{0.f, 0.f, 0.f}, nr{0.f, 0.f, 0.f};
+            Row3 vr{0.f, 0.f, 0.f}, nr{0.f, 0.f, 0.f};
             if (hit) {
                 float C[3], p[3], G[3];
-                emit_point((float)u, (float)v, zh, c.cx, c.cy, PlainDiv{c.fx, c.fy}, C, (float*)nullptr, (const uint8_t*)nullptr, 0, (size_t)0);   // T17
-                vr = RcRow3{C[0], C[1], C[2]};
+                pinhole_vertex(u, v, zh, c.k, C);                                  // T17
+                vr = Row3{C[0], C[1], C[2]};
                 if (normal_map) {                                                  // T18
                     rc_point(u, v, zh, c, P, m.direction, p);
                     bool all = true;
@@ -131,24 +120,14 @@ void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, RcPose P, RcMarch m, const RcPai
                         G[a] = sf - sb;
                     }
                     if (all) {
-                        const float* T = P.T;
                         float n0, n1, n2;
-                        if (m.direction == TDV_POSE_SOURCE_ONTO_TARGET) {
-                            n0 = (T[0] * G[0] + T[1] * G[1]) + T[2] * G[2];
-                            n1 = (T[4] * G[0] + T[5] * G[1]) + T[6] * G[2];
-                            n2 = (T[8] * G[0] + T[9] * G[1]) + T[10] * G[2];
-                        } else {
-                            n0 = (T[0] * G[0] + T[4] * G[1]) + T[8] * G[2];
-                            n1 = (T[1] * G[0] + T[5] * G[1]) + T[9] * G[2];
-                            n2 = (T[2] * G[0] + T[6] * G[1]) + T[10] * G[2];
-                        }
-                        const float len = sqrtf((n0 * n0 + n1 * n1) + n2 * n2);
-                        if (len > 0.f && len < INFINITY) nr = RcRow3{n0 / len, n1 / len, n2 / len};      // (false for NaN)
+                        rotate_into_camera(P, m.direction, G, n0, n1, n2);
+                        nr = normalized_or_zero(n0, n1, n2);
                     }
                 }
             }
-            if (vertex_map) reinterpret_cast<RcRow3*>(vertex_map)[i] = vr;
-            if (normal_map) reinterpret_cast<RcRow3*>(normal_map)[i] = nr;
+            if (vertex_map) reinterpret_cast<Row3*>(vertex_map)[i] = vr;
+            if (normal_map) reinterpret_cast<Row3*>(normal_map)[i] = nr;
         }
     }
     if (COUNT) {
@@ -157,69 +136,63 @@ void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, RcPose P, RcMarch m, const RcPai
     }
 }
 
-bool rc_params_ok(const tdv_tsdf_raycast_params* r) {
-    return r && std::isfinite(r->zmin) && r->zmin > 0.f && r->max_steps >= 1 && r->max_steps <= TDV_TSDF_RAYCAST_MAX_STEPS;
-}
-bool rc_camera_ok(int w, int h, float fx, float fy) {
-    return w >= 0 && w <= TDV_VERIFY_MAX_SIDE && h >= 0 && h <= TDV_VERIFY_MAX_SIDE && std::isfinite(fx) && fx > 0.f && std::isfinite(fy) && fy > 0.f;
-}
-bool rc_args_ok(const tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, int w, int h, float fx, float fy, const float* pose,
+
+bool rc_params_ok(const tdv_tsdf_raycast_params* r) { return r && positive_finite(r->zmin) && r->max_steps >= 1 && r->max_steps <= TDV_TSDF_RAYCAST_MAX_STEPS; }
+bool rc_args_ok(const tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, const FrameCamera& cam, const float* pose,
                 const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray) {
-    return ctx && tsdf_voxels(vol) && volume && rc_camera_ok(w, h, fx, fy) && pose && tsdf_params_ok(params) && rc_params_ok(ray);
+    return ctx && tsdf_voxels(vol) && volume && frame_camera_ok(cam, false) && pose && tsdf_params_ok(params) && rc_params_ok(ray);
 }
 
-// The launch (w * h > 0).  d_n_hit: a workspace counter at 0, or nullptr.
-int rc_launch(tdv_ctx* ctx, const tdv_tsdf_volume& V, const float* d_volume, int w, int h, float fx, float fy, float cx, float cy,
-              const float* h_pose, const tdv_tsdf_params& prm, const tdv_tsdf_raycast_params& ray, float* d_depth, float* d_vm, float* d_nm,
-              unsigned long long* d_n_hit) {
-    const RcCam cam{fx, fy, cx, cy, w, h};
-    RcPose P;
-    std::memcpy(P.T, h_pose, sizeof(P.T));
-    const RcMarch m{ray.zmin, prm.zmax, prm.trunc == 0.f ? 4.0f * V.voxel_length : prm.trunc, prm.min_weight, ray.max_steps, prm.pose_direction};
-    const unsigned tiles = (unsigned)((w + RC_TILE - 1) / RC_TILE) * (unsigned)((h + RC_TILE - 1) / RC_TILE);      // at most 2^20
-    const unsigned blocks = (tiles + RC_T / 64 - 1) / (RC_T / 64);
-    const RcPair* vol = reinterpret_cast<const RcPair*>(d_volume);
+// The launch (cam.npx() > 0).  d_n_hit: nullptr, or where to leave a fresh workspace counter that the launch counts the hits into.
+int rc_launch(tdv_ctx* ctx, const tdv_tsdf_volume& V, const float* d_volume, const FrameCamera& fc, const float* h_pose, const tdv_tsdf_params& prm,
+              const tdv_tsdf_raycast_params& ray, float* d_depth, float* d_vm, float* d_nm, unsigned long long** d_n_hit) {
     hipStream_t s = ctx->stream;
+    unsigned long long* d_cnt = nullptr;
+    if (d_n_hit) {
+        TDV_TRY(ws_alloc(ctx, 1, &d_cnt));
+        TDV_HIP(ctx, hipMemsetAsync(d_cnt, 0, sizeof(unsigned long long), s));
+        *d_n_hit = d_cnt;
+    }
+    const RcCam cam{fc.k, fc.w, fc.h};
+    Pose16 P;
+    std::memcpy(P.T, h_pose, sizeof(P.T));
+    const RcMarch m{ray.zmin, prm.zmax, tsdf_trunc(prm, V), prm.min_weight, ray.max_steps, prm.pose_direction};
+    const unsigned tiles = (unsigned)((fc.w + RC_TILE - 1) / RC_TILE) * (unsigned)((fc.h + RC_TILE - 1) / RC_TILE);      // at most 2^20
+    const unsigned blocks = (tiles + RC_T / 64 - 1) / (RC_T / 64);
+    const TsdfVoxel* vol = reinterpret_cast<const TsdfVoxel*>(d_volume);
     const bool maps = d_vm || d_nm;
-    if (maps && d_n_hit) k_tsdf_raycast<true, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, d_n_hit);
+    if (maps && d_cnt) k_tsdf_raycast<true, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, d_cnt);
     else if (maps) k_tsdf_raycast<true, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, nullptr);
-    else if (d_n_hit) k_tsdf_raycast<false, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, d_n_hit);
+    else if (d_cnt) k_tsdf_raycast<false, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, d_cnt);
     else k_tsdf_raycast<false, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, nullptr);
     TDV_CHECK_LAUNCH(ctx);
     return TDV_OK;
 }
 
-int rc_counter(tdv_ctx* ctx, unsigned long long** d_cnt) {
-    TDV_TRY(ws_alloc(ctx, 1, d_cnt));
-    TDV_HIP(ctx, hipMemsetAsync(*d_cnt, 0, sizeof(unsigned long long), ctx->stream));
+// after the launch, where the hit count was asked for: the count down (one wait, which the downloads enqueued before it ride)
+int rc_hits(tdv_ctx* ctx, const unsigned long long* d_cnt, long long* h_n_hit) {
+    unsigned long long n = 0;
+    TDV_TRY(pin_reserve(ctx, sizeof(n)));
+    TDV_TRY(fetch_state(ctx, d_cnt, &n));
+    *h_n_hit = (long long)n;
     return TDV_OK;
 }
 
-void rc_identity(float* T) { for (int k = 0; k < 16; ++k) T[k] = (k % 5 == 0) ? 1.f : 0.f; }
-
-bool track_args_ok(const tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, int w, int h, float scale, float fx, float fy,
-                   const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, const tdv_odometry_params* odom) {
-    return ctx && tsdf_voxels(vol) && volume && odometry_camera_ok(w, h, scale, fx, fy) && tsdf_params_ok(params) &&
-           params->pose_direction == TDV_POSE_SOURCE_ONTO_TARGET && rc_params_ok(ray) && odometry_params_ok(odom, w, h);
+bool track_args_ok(const tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, const FrameCamera& cam, const tdv_tsdf_params* params,
+                   const tdv_tsdf_raycast_params* ray, const tdv_odometry_params* odom) {
+    return ctx && tsdf_voxels(vol) && volume && frame_camera_ok(cam, true) && tsdf_params_ok(params) &&
+           params->pose_direction == TDV_POSE_SOURCE_ONTO_TARGET && rc_params_ok(ray) && odometry_params_ok(odom, cam.w, cam.h);
 }
 
-constexpr size_t TRACK_PIN_HIT = (size_t)1 << 15;          // where the hit count lands in the pinned block: far above one pair's state record
-
-// K1 to K3 for one frame (w * h > 0): the hit count rides the odometry's read-back
-int track_frame(tdv_ctx* ctx, const tdv_tsdf_volume& V, const float* d_volume, const uint16_t* d_raw, int w, int h, float scale, float fx, float fy,
-                float cx, float cy, const float* h_guess, const tdv_tsdf_params& prm, const tdv_tsdf_raycast_params& ray,
-                const tdv_odometry_params& odom, tdv_tsdf_track_result* out) {
+// K1 to K3 for one frame (cam.npx() > 0): the hit count rides the odometry's read-back, so a tracked frame waits once
+int track_frame(tdv_ctx* ctx, const tdv_tsdf_volume& V, const float* d_volume, const uint16_t* d_raw, const FrameCamera& cam, const float* h_guess,
+                const tdv_tsdf_params& prm, const tdv_tsdf_raycast_params& ray, const tdv_odometry_params& odom, tdv_tsdf_track_result* out) {
     float* d_depth;
-    unsigned long long* d_cnt;
-    TDV_TRY(ws_alloc(ctx, (size_t)w * h, &d_depth));
-    TDV_TRY(rc_counter(ctx, &d_cnt));
-    TDV_TRY(pin_reserve(ctx, 2 * TRACK_PIN_HIT));            // the pair's state lands at the block's start, the count well behind it
-    TDV_TRY(rc_launch(ctx, V, d_volume, w, h, fx, fy, cx, cy, h_guess, prm, ray, d_depth, nullptr, nullptr, d_cnt));               // K1
-    char* pin_hit = reinterpret_cast<char*>(ctx->pin) + TRACK_PIN_HIT;
-    TDV_HIP(ctx, hipMemcpyAsync(pin_hit, d_cnt, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    TDV_TRY(odometry_pair_to_depth(ctx, d_raw, d_depth, w, h, scale, fx, fy, cx, cy, nullptr, odom, &out->odom));                  // K2
-    unsigned long long n_hit;
-    std::memcpy(&n_hit, pin_hit, sizeof(n_hit));             // (the pinned block did not move: the pair's own reserve is smaller)
+    unsigned long long *d_cnt, n_hit = 0;
+    TDV_TRY(ws_alloc(ctx, cam.npx(), &d_depth));
+    TDV_TRY(rc_launch(ctx, V, d_volume, cam, h_guess, prm, ray, d_depth, nullptr, nullptr, &d_cnt));                              // K1
+    const OdRider hits{d_cnt, sizeof(n_hit), &n_hit};
+    TDV_TRY(odometry_pair(ctx, d_raw, OdTarget{nullptr, d_depth}, cam, nullptr, odom, &out->odom, &hits));                        // K2
     out->n_hit = (long long)n_hit;
     pose_chain_product(h_guess, out->odom.T, out->pose);                                                                             // K3
     return TDV_OK;
@@ -247,70 +220,64 @@ void tdv_tsdf_raycast_default_params(tdv_tsdf_raycast_params* p) {
 int tdv_tsdf_raycast_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, int width, int height, float fx, float fy, float cx,
                          float cy, const float* h_pose, const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, float* d_depth,
                          float* d_vertex_map, float* d_normal_map, long long* h_n_hit) {
-    if (!rc_args_ok(ctx, vol, d_volume, width, height, fx, fy, h_pose, params, ray)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!rc_args_ok(ctx, vol, d_volume, cam, h_pose, params, ray)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     if (h_n_hit) *h_n_hit = 0;
-    if ((size_t)width * height == 0 || (!d_depth && !d_vertex_map && !d_normal_map && !h_n_hit)) return TDV_OK;
-    unsigned long long* d_cnt = nullptr;
-    if (h_n_hit) { TDV_TRY(rc_counter(ctx, &d_cnt)); TDV_TRY(pin_reserve(ctx, sizeof(unsigned long long))); }
-    TDV_TRY(rc_launch(ctx, *vol, d_volume, width, height, fx, fy, cx, cy, h_pose, *params, *ray, d_depth, d_vertex_map, d_normal_map, d_cnt));
-    if (!h_n_hit) return TDV_OK;
-    unsigned long long n = 0;
-    TDV_TRY(fetch_state(ctx, d_cnt, &n));
-    *h_n_hit = (long long)n;
-    return TDV_OK;
+    if (cam.npx() == 0 || (!d_depth && !d_vertex_map && !d_normal_map && !h_n_hit)) return TDV_OK;
+    unsigned long long* d_cnt;
+    TDV_TRY(rc_launch(ctx, *vol, d_volume, cam, h_pose, *params, *ray, d_depth, d_vertex_map, d_normal_map, h_n_hit ? &d_cnt : nullptr));
+    return h_n_hit ? rc_hits(ctx, d_cnt, h_n_hit) : TDV_OK;
 }
 
 int tdv_tsdf_raycast(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, int width, int height, float fx, float fy, float cx, float cy,
                      const float* pose, const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, float* depth, float* vertex_map,
                      float* normal_map, long long* n_hit) {
-    if (!rc_args_ok(ctx, vol, volume, width, height, fx, fy, pose, params, ray) || tsdf_voxels(vol) > (size_t)TDV_TSDF_HOST_MAX_VOXELS)
-        return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!rc_args_ok(ctx, vol, volume, cam, pose, params, ray) || tsdf_voxels(vol) > (size_t)TDV_TSDF_HOST_MAX_VOXELS) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     if (n_hit) *n_hit = 0;
-    const size_t npx = (size_t)width * height;
+    const size_t npx = cam.npx();
     if (npx == 0 || (!depth && !vertex_map && !normal_map && !n_hit)) return TDV_OK;
     float *d_volume, *d_depth = nullptr, *d_vm = nullptr, *d_nm = nullptr;
-    unsigned long long *d_cnt = nullptr, n = 0;
+    unsigned long long* d_cnt;
     TDV_TRY(upload(ctx, volume, tsdf_voxels(vol) * 2, &d_volume));
     if (depth) TDV_TRY(ws_alloc(ctx, npx, &d_depth));
     if (vertex_map) TDV_TRY(ws_alloc(ctx, npx * 3, &d_vm));
     if (normal_map) TDV_TRY(ws_alloc(ctx, npx * 3, &d_nm));
-    if (n_hit) { TDV_TRY(rc_counter(ctx, &d_cnt)); TDV_TRY(pin_reserve(ctx, sizeof(unsigned long long))); }
-    TDV_TRY(rc_launch(ctx, *vol, d_volume, width, height, fx, fy, cx, cy, pose, *params, *ray, d_depth, d_vm, d_nm, d_cnt));
+    TDV_TRY(rc_launch(ctx, *vol, d_volume, cam, pose, *params, *ray, d_depth, d_vm, d_nm, n_hit ? &d_cnt : nullptr));
     TDV_TRY(download(ctx, depth, d_depth, npx));
     TDV_TRY(download(ctx, vertex_map, d_vm, npx * 3));
     TDV_TRY(download(ctx, normal_map, d_nm, npx * 3));
-    if (!n_hit) return finish(ctx);
-    TDV_TRY(fetch_state(ctx, d_cnt, &n));
-    *n_hit = (long long)n;
-    return TDV_OK;
+    return n_hit ? rc_hits(ctx, d_cnt, n_hit) : finish(ctx);
 }
 
 int tdv_tsdf_track_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const uint16_t* d_raw, int width, int height,
                        float scale, float fx, float fy, float cx, float cy, const float* h_guess, const tdv_tsdf_params* params,
                        const tdv_tsdf_raycast_params* ray, const tdv_odometry_params* odom, tdv_tsdf_track_result* out) {
-    if (!track_args_ok(ctx, vol, d_volume, width, height, scale, fx, fy, params, ray, odom) || !h_guess || !out) return TDV_ERR_BAD_ARG;
-    if ((size_t)width * height != 0 && !d_raw) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!track_args_ok(ctx, vol, d_volume, cam, params, ray, odom) || !h_guess || !out) return TDV_ERR_BAD_ARG;
+    if (cam.npx() != 0 && !d_raw) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     track_empty(h_guess, out);
-    if ((size_t)width * height == 0) return TDV_OK;
-    return track_frame(ctx, *vol, d_volume, d_raw, width, height, scale, fx, fy, cx, cy, h_guess, *params, *ray, *odom, out);
+    if (cam.npx() == 0) return TDV_OK;
+    return track_frame(ctx, *vol, d_volume, d_raw, cam, h_guess, *params, *ray, *odom, out);
 }
 
 int tdv_tsdf_track_sequence_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_volume, const uint16_t* d_raw, int n_frames, int width,
                                 int height, float scale, float fx, float fy, float cx, float cy, const float* h_pose0,
                                 const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, const tdv_odometry_params* odom,
                                 float* h_poses, tdv_tsdf_track_result* h_results) {
-    if (!track_args_ok(ctx, vol, d_volume, width, height, scale, fx, fy, params, ray, odom) || n_frames < 0 || n_frames > TDV_TSDF_MAX_FRAMES ||
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!track_args_ok(ctx, vol, d_volume, cam, params, ray, odom) || n_frames < 0 || n_frames > TDV_TSDF_MAX_FRAMES ||
         (n_frames > 0 && (!h_poses || !d_raw)))
         return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     if (n_frames == 0) return TDV_OK;
-    const size_t npx = (size_t)width * height;
+    const size_t npx = cam.npx();
     std::vector<tdv_tsdf_track_result> res((size_t)n_frames);
     std::memset(&res[0], 0, sizeof(res[0]));
-    if (h_pose0) std::memcpy(res[0].pose, h_pose0, 64); else rc_identity(res[0].pose);
+    if (h_pose0) std::memcpy(res[0].pose, h_pose0, 64); else pose_identity(res[0].pose);
     std::memcpy(h_poses, res[0].pose, 64);
     const WsMark mark = ws_mark(ctx);
     for (int k = 0; k < n_frames; ++k) {
@@ -319,10 +286,10 @@ int tdv_tsdf_track_sequence_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float*
         ws_rewind(ctx, mark);                                // a frame's workspace is the last one's again: the stream orders the reuse
         if (k > 0) {
             track_empty(pose - 16, &res[k]);
-            if (npx != 0) TDV_TRY(track_frame(ctx, *vol, d_volume, frame, width, height, scale, fx, fy, cx, cy, pose - 16, *params, *ray, *odom, &res[k]));
+            if (npx != 0) TDV_TRY(track_frame(ctx, *vol, d_volume, frame, cam, pose - 16, *params, *ray, *odom, &res[k]));
             std::memcpy(pose, res[k].pose, 64);
         }
-        TDV_TRY(tsdf_integrate_frames(ctx, *vol, d_volume, frame, 1, width, height, scale, fx, fy, cx, cy, pose, *params, nullptr));
+        TDV_TRY(tsdf_integrate_frames(ctx, *vol, d_volume, frame, 1, cam, pose, *params, nullptr));
     }
     if (h_results) std::memcpy(h_results, res.data(), (size_t)n_frames * sizeof(tdv_tsdf_track_result));
     return TDV_OK;

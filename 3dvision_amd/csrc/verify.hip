@@ -12,8 +12,9 @@
 //                    reduce the counts over the wave with DPP and add them to the pose's record; or, for tdv_render_depth, write the tile
 //                    out as f32.  The grid never needs the tile total on the host: the call reads back once, the records.
 // Resource usage (hipcc -Rpass-analysis=kernel-resource-usage, gfx950): DESIGN.md 7, "Pose verification".
-// The record, the projection, the tile list and the classify-and-reduce tail are verify_common.hpp's, shared with the mesh renderer
-// (verify_mesh.hip); the host side of a call that both renderers use - stage, plan, fetch, results and order - is defined at the end.
+// The record, the projection (frame_pose.hpp's pose and pinhole), the tile list and the classify-and-reduce tail are verify_common.hpp's,
+// shared with the mesh renderer (verify_mesh.hip); the host side of a call that both renderers use - stage, plan, fetch, the wait with
+// results and order, the render's clear and count - is defined at the end.  The camera arrives as depth_frames.hpp's FrameCamera.
 #include "verify_common.hpp"
 #include <algorithm>
 #include <numeric>
@@ -113,8 +114,6 @@ __global__ __launch_bounds__(VT, 8) void k_verify_tiles(const float* __restrict_
     }
 }
 
-bool positive_finite(float v) { return std::isfinite(v) && v > 0.f; }
-
 // the records of every pose on the device, everything enqueued: init, bounds, plan, tiles, the records down
 int verify_enqueue(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, float* d_out,
                    const VerifyCam& cam, VerifyStage* st) {
@@ -132,10 +131,6 @@ int verify_enqueue(tdv_ctx* ctx, const float* d_model, int n_model, const float*
         else k_verify_tiles<false><<<grid, VT, 0, s>>>(d_model, n_model, st->d_poses, n_poses, st->off, cam, d_raw, st->rec, d_out);
     }
     return verify_fetch(ctx, *st, n_poses);
-}
-
-VerifyCam verify_cam(int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& p) {
-    return VerifyCam{fx, fy, cx, cy, p.zmax, p.tau, (float)(1.0 / (double)scale), w, h, p.splat, p.pose_direction};
 }
 
 }  // namespace
@@ -163,6 +158,9 @@ int verify_fetch(tdv_ctx* ctx, const VerifyStage& st, int n_poses) {
     return TDV_OK;
 }
 
+namespace {
+
+// records -> results, and the order
 void verify_results(const char* down, int n_poses, tdv_verify_result* results, int* order) {
     for (int p = 0; p < n_poses; ++p) {
         VerifyRec r;
@@ -181,48 +179,61 @@ void verify_results(const char* down, int n_poses, tdv_verify_result* results, i
     }
 }
 
-bool verify_common_args_ok(const tdv_ctx* ctx, const float* poses, int n_poses, const void* frame, int w, int h, float scale, float fx, float fy,
+}  // namespace
+
+int verify_finish(tdv_ctx* ctx, const VerifyStage& st, int n_poses, tdv_verify_result* results, int* order) {
+    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    verify_results(st.down, n_poses, results, order);
+    return TDV_OK;
+}
+
+int render_clear(tdv_ctx* ctx, const FrameCamera& cam, float* d_out) {
+    if (cam.npx() > 0) TDV_HIP(ctx, hipMemsetAsync(d_out, 0, cam.npx() * sizeof(float), ctx->stream));
+    return TDV_OK;
+}
+
+int render_finish(tdv_ctx* ctx, const VerifyStage& st, int* n_rendered) {
+    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    VerifyRec r;
+    std::memcpy(&r, st.down, sizeof(r));
+    if (n_rendered) *n_rendered = r.cls[0];
+    return TDV_OK;
+}
+
+bool verify_common_args_ok(const tdv_ctx* ctx, const float* poses, int n_poses, const void* frame, const FrameCamera& cam, bool has_scale,
                            float tau, int pose_direction, const void* results) {
-    if (!ctx || n_poses < 0 || n_poses > TDV_VERIFY_MAX_POSES) return false;
-    if (w < 0 || w > TDV_VERIFY_MAX_SIDE || h < 0 || h > TDV_VERIFY_MAX_SIDE) return false;
-    if ((n_poses > 0 && (!poses || !results)) || ((size_t)w * h > 0 && !frame)) return false;
-    if (!positive_finite(tau)) return false;
-    if (pose_direction != TDV_POSE_SOURCE_ONTO_TARGET && pose_direction != TDV_POSE_MODEL_TO_CAMERA) return false;
-    return positive_finite(scale) && positive_finite(fx) && positive_finite(fy);
+    if (!ctx || n_poses < 0 || n_poses > TDV_VERIFY_MAX_POSES || !frame_camera_ok(cam, has_scale)) return false;
+    if ((n_poses > 0 && (!poses || !results)) || (cam.npx() > 0 && !frame)) return false;
+    return positive_finite(tau) && pose_direction_ok(pose_direction);
 }
 
 namespace {
 
 // every argument of the four entry points, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth
 // output; results: what receives the per-pose output
-bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame, int w, int h,
-                    float scale, float fx, float fy, const tdv_verify_params* p, const void* results) {
+bool verify_args_ok(const tdv_ctx* ctx, const float* model, int n_model, const float* poses, int n_poses, const void* frame,
+                    const FrameCamera& cam, bool has_scale, const tdv_verify_params* p, const void* results) {
     if (!p || n_model < 0 || n_model > TDV_VERIFY_MAX_MODEL || (n_model > 0 && !model)) return false;
     if (p->splat < 0 || p->splat > TDV_VERIFY_MAX_SPLAT) return false;
-    return verify_common_args_ok(ctx, poses, n_poses, frame, w, h, scale, fx, fy, p->tau, p->pose_direction, results);
+    return verify_common_args_ok(ctx, poses, n_poses, frame, cam, has_scale, p->tau, p->pose_direction, results);
 }
 
-int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw, int w, int h,
-                   float scale, float fx, float fy, float cx, float cy, const tdv_verify_params& prm, tdv_verify_result* results, int* order) {
+int verify_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw,
+                   const FrameCamera& cam, const tdv_verify_params& prm, tdv_verify_result* results, int* order) {
     if (n_poses == 0) return TDV_OK;
     VerifyStage st;
-    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_poses, n_poses, d_raw, nullptr, verify_cam(w, h, scale, fx, fy, cx, cy, prm), &st));
-    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    verify_results(st.down, n_poses, results, order);
-    return TDV_OK;
+    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_poses, n_poses, d_raw, nullptr,
+                           verify_cam(cam, prm.zmax, prm.tau, prm.splat, prm.pose_direction), &st));
+    return verify_finish(ctx, st, n_poses, results, order);
 }
 
-int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_pose, int w, int h, float fx, float fy, float cx, float cy,
+int render_depth_run_dev(tdv_ctx* ctx, const float* d_model, int n_model, const float* h_pose, const FrameCamera& cam,
                          const tdv_verify_params& prm, float* d_out, int* n_rendered) {
-    const size_t px = (size_t)w * h;
-    if (px > 0) TDV_HIP(ctx, hipMemsetAsync(d_out, 0, px * sizeof(float), ctx->stream));    // the pixels outside the pose's tiles
+    TDV_TRY(render_clear(ctx, cam, d_out));
     VerifyStage st;
-    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_pose, 1, nullptr, d_out, verify_cam(w, h, 1.f, fx, fy, cx, cy, prm), &st));
-    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    VerifyRec r;
-    std::memcpy(&r, st.down, sizeof(r));
-    if (n_rendered) *n_rendered = r.cls[0];
-    return TDV_OK;
+    TDV_TRY(verify_enqueue(ctx, d_model, n_model, h_pose, 1, nullptr, d_out, verify_cam(cam, prm.zmax, prm.tau, prm.splat, prm.pose_direction),
+                           &st));
+    return render_finish(ctx, st, n_rendered);
 }
 
 }  // namespace
@@ -241,38 +252,42 @@ void tdv_verify_default_params(tdv_verify_params* p) {
 int tdv_verify_poses_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, const float* h_poses, int n_poses, const uint16_t* d_raw_depth, int width,
                          int height, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params* params,
                          tdv_verify_result* h_results, int* h_order) {
-    if (!verify_args_ok(ctx, d_model_xyz, n_model, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy, params, h_results)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!verify_args_ok(ctx, d_model_xyz, n_model, h_poses, n_poses, d_raw_depth, cam, true, params, h_results)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
-    return verify_run_dev(ctx, d_model_xyz, n_model, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy, cx, cy, *params, h_results, h_order);
+    return verify_run_dev(ctx, d_model_xyz, n_model, h_poses, n_poses, d_raw_depth, cam, *params, h_results, h_order);
 }
 
 int tdv_verify_poses(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* poses, int n_poses, const uint16_t* raw_depth, int width,
                      int height, float scale, float fx, float fy, float cx, float cy, const tdv_verify_params* params, tdv_verify_result* results,
                      int* order) {
-    if (!verify_args_ok(ctx, model_xyz, n_model, poses, n_poses, raw_depth, width, height, scale, fx, fy, params, results)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!verify_args_ok(ctx, model_xyz, n_model, poses, n_poses, raw_depth, cam, true, params, results)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     float* d_model; uint16_t* d_raw;
     TDV_TRY(upload(ctx, model_xyz, (size_t)n_model * 3, &d_model));
-    TDV_TRY(upload(ctx, raw_depth, (size_t)width * height, &d_raw));
-    return verify_run_dev(ctx, d_model, n_model, poses, n_poses, d_raw, width, height, scale, fx, fy, cx, cy, *params, results, order);
+    TDV_TRY(upload(ctx, raw_depth, cam.npx(), &d_raw));
+    return verify_run_dev(ctx, d_model, n_model, poses, n_poses, d_raw, cam, *params, results, order);
 }
 
 int tdv_render_depth_dev(tdv_ctx* ctx, const float* d_model_xyz, int n_model, const float* h_pose, int width, int height, float fx, float fy, float cx,
                          float cy, const tdv_verify_params* params, float* d_out_depth, int* n_rendered) {
-    if (!verify_args_ok(ctx, d_model_xyz, n_model, h_pose, 1, d_out_depth, width, height, 1.f, fx, fy, params, h_pose)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!verify_args_ok(ctx, d_model_xyz, n_model, h_pose, 1, d_out_depth, cam, false, params, h_pose)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
-    return render_depth_run_dev(ctx, d_model_xyz, n_model, h_pose, width, height, fx, fy, cx, cy, *params, d_out_depth, n_rendered);
+    return render_depth_run_dev(ctx, d_model_xyz, n_model, h_pose, cam, *params, d_out_depth, n_rendered);
 }
 
 int tdv_render_depth(tdv_ctx* ctx, const float* model_xyz, int n_model, const float* pose, int width, int height, float fx, float fy, float cx, float cy,
                      const tdv_verify_params* params, float* out_depth, int* n_rendered) {
-    if (!verify_args_ok(ctx, model_xyz, n_model, pose, 1, out_depth, width, height, 1.f, fx, fy, params, pose)) return TDV_ERR_BAD_ARG;
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!verify_args_ok(ctx, model_xyz, n_model, pose, 1, out_depth, cam, false, params, pose)) return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     float *d_model, *d_out;
     TDV_TRY(upload(ctx, model_xyz, (size_t)n_model * 3, &d_model));
-    TDV_TRY(ws_alloc(ctx, (size_t)width * height, &d_out));
-    TDV_TRY(render_depth_run_dev(ctx, d_model, n_model, pose, width, height, fx, fy, cx, cy, *params, d_out, n_rendered));
-    TDV_TRY(download(ctx, out_depth, d_out, (size_t)width * height));
+    TDV_TRY(ws_alloc(ctx, cam.npx(), &d_out));
+    TDV_TRY(render_depth_run_dev(ctx, d_model, n_model, pose, cam, *params, d_out, n_rendered));
+    TDV_TRY(download(ctx, out_depth, d_out, cam.npx()));
     return finish(ctx);
 }
 

@@ -1,10 +1,11 @@
 // What the two renderers of the pose verification share (include/tdv_hip.h: tdv_verify_poses, tdv_verify_poses_mesh): the per-pose record,
-// the camera, rules 1 to 3 (the projection), the tile list and the tail of a tile - rules 5 to 7, the classification of the tile's pixels
-// against the raw frame and their reduction into the record.  verify.hip splats points into the tile, verify_mesh.hip rasterises triangles;
-// everything around the tile's z-buffer is here, once.  The host part (the poses up, init, plan, the one read-back, the order) is defined in
-// verify.hip.
+// the kernels' camera, rules 1 to 3 (frame_pose.hpp's pose and projection), the tile list and the tail of a tile - rules 5 to 7, the
+// classification of the tile's pixels against the raw frame and their reduction into the record.  verify.hip splats points into the
+// tile, verify_mesh.hip rasterises triangles; everything around the tile's z-buffer is here, once.  The host part (the poses up, init, plan, the one read-back and wait, the order,
+// the render's clear and count) is defined in verify.hip.
 #pragma once
 #include "tdv_internal.hpp"
+#include "frame_pose.hpp"
 
 namespace tdv {
 
@@ -20,66 +21,39 @@ struct VerifyRec {                                          // one per pose (dev
     int pad;
     unsigned long long err;
 };
-struct VerifyCam { float fx, fy, cx, cy, zmax, tau, inv_scale; int w, h, splat, direction; };
-struct Pose16 { float T[16]; };
+struct VerifyCam { Pinhole k; float zmax, tau, inv_scale; int w, h, splat, direction; };
 
 // what a call holds on the device and in the pinned staging: the poses, a record per pose, the tile offsets; down: where the records land
 struct VerifyStage { float* d_poses; VerifyRec* rec; int* off; char* down; };
 
+// the kernels' camera from the entry point's (tau, splat: 0 where a renderer has none)
+inline VerifyCam verify_cam(const FrameCamera& c, float zmax, float tau, int splat, int direction) {
+    return VerifyCam{c.k, zmax, tau, c.inv_scale(), c.w, c.h, splat, direction};
+}
 // the poses up and a fresh record per pose, enqueued (pin: poses up at [0], records down at st->down)
 int verify_stage(tdv_ctx* ctx, const float* h_poses, int n_poses, VerifyStage* st);
 // k_verify_plan: the tile list of the records' boxes, enqueued
 void verify_plan(tdv_ctx* ctx, const VerifyStage& st, int n_poses);
 // the records down, enqueued; then the stream is to be synchronised
 int verify_fetch(tdv_ctx* ctx, const VerifyStage& st, int n_poses);
-// records -> results, and the order by n_consistent - n_violating descending, ties to the lower index (order: optional)
-void verify_results(const char* down, int n_poses, tdv_verify_result* results, int* order);
-// the arguments both renderers check alike: ctx, the pose and frame pointers and counts, tau, the direction, scale, fx, fy
-bool verify_common_args_ok(const tdv_ctx* ctx, const float* poses, int n_poses, const void* frame, int w, int h, float scale, float fx, float fy,
+// after either renderer's enqueue: the one wait, then records -> results and the order by n_consistent - n_violating descending, ties
+// to the lower index (order: optional)
+int verify_finish(tdv_ctx* ctx, const VerifyStage& st, int n_poses, tdv_verify_result* results, int* order);
+// tdv_render_depth*: zeros for the pixels outside the pose's tiles, enqueued before the renderer; and after it the one wait and the
+// record's count
+int render_clear(tdv_ctx* ctx, const FrameCamera& cam, float* d_out);
+int render_finish(tdv_ctx* ctx, const VerifyStage& st, int* n_rendered);
+// the arguments both renderers check alike: ctx, the pose and frame pointers and counts, the camera, tau, the direction
+bool verify_common_args_ok(const tdv_ctx* ctx, const float* poses, int n_poses, const void* frame, const FrameCamera& cam, bool has_scale,
                            float tau, int pose_direction, const void* results);
 
 #ifdef __HIPCC__
-__device__ __forceinline__ Pose16 load_pose(const float* __restrict__ poses, int pose) {
-    Pose16 p;
-    const float* T = poses + (size_t)pose * 16;
-#pragma unroll
-    for (int k = 0; k < 16; ++k) p.T[k] = T[k];
-    return p;
-}
-
-// rules 1 to 3 of include/tdv_hip.h, as written there.  SUB 1: the splat's pixel (u, v) = floorf(uf + 0.5f); SUB 16: the mesh's snapped
-// position of rule M1, floorf(uf * 16.0f + 0.5f)
-// (xc, yc, zc): the point in camera coordinates (rule 1), for a caller that goes on with it (odometry.hip)
-template <int SUB>
-__device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& xc,
-                                               float& yc, float& zc) {
-    const float* T = P.T;
-    if (c.direction == TDV_POSE_SOURCE_ONTO_TARGET) {
-        const float d0 = m0 - T[12], d1 = m1 - T[13], d2 = m2 - T[14];
-        xc = (T[0] * d0 + T[1] * d1) + T[2] * d2;
-        yc = (T[4] * d0 + T[5] * d1) + T[6] * d2;
-        zc = (T[8] * d0 + T[9] * d1) + T[10] * d2;
-    } else {
-        xc = ((T[0] * m0 + T[4] * m1) + T[8] * m2) + T[12];
-        yc = ((T[1] * m0 + T[5] * m1) + T[9] * m2) + T[13];
-        zc = ((T[2] * m0 + T[6] * m1) + T[10] * m2) + T[14];
-    }
-    if (!(fabsf(xc) < INFINITY && fabsf(yc) < INFINITY && zc > 0.f && zc <= c.zmax && zc < INFINITY)) return false;
-    const float uf = (xc * c.fx) / zc + c.cx, vf = (yc * c.fy) / zc + c.cy;
-    if (!(fabsf(uf) < 1048576.f && fabsf(vf) < 1048576.f)) return false;          // (false for NaN too)
-    if constexpr (SUB == 1) {
-        u = (int)floorf(uf + 0.5f);
-        v = (int)floorf(vf + 0.5f);
-    } else {
-        u = (int)floorf(uf * (float)SUB + 0.5f);             // |uf| < 2^20: within +-2^24 at SUB 16
-        v = (int)floorf(vf * (float)SUB + 0.5f);
-    }
-    return true;
-}
+// rules 1 to 3 of include/tdv_hip.h: the model point into the camera (frame_pose.hpp: pose_into_camera), then pinhole_project
 template <int SUB>
 __device__ __forceinline__ bool verify_project(const Pose16& P, const VerifyCam& c, float m0, float m1, float m2, int& u, int& v, float& zc) {
     float xc, yc;
-    return verify_project<SUB>(P, c, m0, m1, m2, u, v, xc, yc, zc);
+    pose_into_camera(P, c.direction, m0, m1, m2, xc, yc, zc);
+    return pinhole_project<SUB>(c.k, c.zmax, xc, yc, zc, u, v);
 }
 
 // tile t of the list: its pose and the tile's pixels inside the frame, [x0, xe] x [y0, ye] (every lane alike)

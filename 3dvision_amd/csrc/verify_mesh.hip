@@ -1,6 +1,7 @@
 // Pose verification from a triangle mesh (include/tdv_hip.h: tdv_verify_poses_mesh): the model's faces rasterised at every candidate pose
 // into the z-buffer that verify.hip fills with point squares, and the same classification after it (verify_common.hpp).  The shape is
-// verify.hip's: init, bounds, plan, tiles, one read-back; a tile's z-buffer lives in LDS and is built with LDS integer minimum atomics.
+// verify.hip's: init, bounds, plan, tiles, one read-back, and the host's ends around the enqueue are verify.hip's own functions; a tile's
+// z-buffer lives in LDS and is built with LDS integer minimum atomics.
 //   k_mesh_bounds  per pose n_projected (the usable triangles, rules M2 and M3) and a box of the pixels the usable triangles can cover,
 //                  clipped to the frame: the union of their pixel boxes - conservative, no result depends on it
 //   k_mesh_tiles   the fixed grid walks the tile list.  Per tile and per block of TDV_VERIFY_LANES triangles a lane sets its triangle up
@@ -177,10 +178,6 @@ __global__ __launch_bounds__(VT, 8) void k_mesh_tiles(const float* __restrict__ 
     }
 }
 
-VerifyCam mesh_cam(int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params& p) {
-    return VerifyCam{fx, fy, cx, cy, p.zmax, p.tau, (float)(1.0 / (double)scale), w, h, 0, p.pose_direction};
-}
-
 // the records of every pose on the device, everything enqueued: init, bounds, plan, tiles, the records down
 int mesh_enqueue(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_poses, int n_poses, const uint16_t* d_raw,
                  float* d_out, const VerifyCam& cam, int cull, VerifyStage* st) {
@@ -203,35 +200,30 @@ int mesh_enqueue(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int
 // every argument of the four entry points, before anything is enqueued (include/tdv_hip.h).  frame: the raw frame resp. the depth
 // output; results: what receives the per-pose output
 bool mesh_verify_args_ok(const tdv_ctx* ctx, const float* vtx, int nv, const int* tri, int nt, const float* poses, int n_poses, const void* frame,
-                         int w, int h, float scale, float fx, float fy, const tdv_mesh_verify_params* p, const void* results) {
+                         const FrameCamera& cam, bool has_scale, const tdv_mesh_verify_params* p, const void* results) {
     if (!p || nv < 0 || nv > TDV_MESH_MAX_VERTICES || nt < 0 || nt > TDV_MESH_MAX_TRIANGLES) return false;
     if ((nv > 0 && !vtx) || (nt > 0 && !tri)) return false;
     if (p->cull != TDV_MESH_CULL_NONE && p->cull != TDV_MESH_CULL_BACK) return false;
-    return verify_common_args_ok(ctx, poses, n_poses, frame, w, h, scale, fx, fy, p->tau, p->pose_direction, results);
+    return verify_common_args_ok(ctx, poses, n_poses, frame, cam, has_scale, p->tau, p->pose_direction, results);
 }
 
+// verify.hip's verify_run_dev and render_depth_run_dev with the mesh's enqueue between the shared ends (verify_common.hpp)
 int mesh_verify_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_poses, int n_poses,
-                        const uint16_t* d_raw, int w, int h, float scale, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params& prm,
-                        tdv_verify_result* results, int* order) {
+                        const uint16_t* d_raw, const FrameCamera& cam, const tdv_mesh_verify_params& prm, tdv_verify_result* results, int* order) {
     if (n_poses == 0) return TDV_OK;
     VerifyStage st;
-    TDV_TRY(mesh_enqueue(ctx, d_vtx, nv, d_tri, nt, h_poses, n_poses, d_raw, nullptr, mesh_cam(w, h, scale, fx, fy, cx, cy, prm), prm.cull, &st));
-    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    verify_results(st.down, n_poses, results, order);
-    return TDV_OK;
+    TDV_TRY(mesh_enqueue(ctx, d_vtx, nv, d_tri, nt, h_poses, n_poses, d_raw, nullptr, verify_cam(cam, prm.zmax, prm.tau, 0, prm.pose_direction),
+                         prm.cull, &st));
+    return verify_finish(ctx, st, n_poses, results, order);
 }
 
-int mesh_render_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_pose, int w, int h, float fx, float fy,
-                        float cx, float cy, const tdv_mesh_verify_params& prm, float* d_out, int* n_rendered) {
-    const size_t px = (size_t)w * h;
-    if (px > 0) TDV_HIP(ctx, hipMemsetAsync(d_out, 0, px * sizeof(float), ctx->stream));    // the pixels outside the pose's tiles
+int mesh_render_run_dev(tdv_ctx* ctx, const float* d_vtx, int nv, const int* d_tri, int nt, const float* h_pose, const FrameCamera& cam,
+                        const tdv_mesh_verify_params& prm, float* d_out, int* n_rendered) {
+    TDV_TRY(render_clear(ctx, cam, d_out));
     VerifyStage st;
-    TDV_TRY(mesh_enqueue(ctx, d_vtx, nv, d_tri, nt, h_pose, 1, nullptr, d_out, mesh_cam(w, h, 1.f, fx, fy, cx, cy, prm), prm.cull, &st));
-    TDV_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    VerifyRec r;
-    std::memcpy(&r, st.down, sizeof(r));
-    if (n_rendered) *n_rendered = r.cls[0];
-    return TDV_OK;
+    TDV_TRY(mesh_enqueue(ctx, d_vtx, nv, d_tri, nt, h_pose, 1, nullptr, d_out, verify_cam(cam, prm.zmax, prm.tau, 0, prm.pose_direction), prm.cull,
+                         &st));
+    return render_finish(ctx, st, n_rendered);
 }
 
 }  // namespace
@@ -250,52 +242,51 @@ void tdv_mesh_verify_default_params(tdv_mesh_verify_params* p) {
 int tdv_verify_poses_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles, const float* h_poses,
                               int n_poses, const uint16_t* d_raw_depth, int width, int height, float scale, float fx, float fy, float cx, float cy,
                               const tdv_mesh_verify_params* params, tdv_verify_result* h_results, int* h_order) {
-    if (!mesh_verify_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy,
-                             params, h_results))
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!mesh_verify_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_poses, n_poses, d_raw_depth, cam, true, params, h_results))
         return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
-    return mesh_verify_run_dev(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_poses, n_poses, d_raw_depth, width, height, scale, fx, fy, cx,
-                               cy, *params, h_results, h_order);
+    return mesh_verify_run_dev(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_poses, n_poses, d_raw_depth, cam, *params, h_results,
+                               h_order);
 }
 
 int tdv_verify_poses_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* poses, int n_poses,
                           const uint16_t* raw_depth, int width, int height, float scale, float fx, float fy, float cx, float cy,
                           const tdv_mesh_verify_params* params, tdv_verify_result* results, int* order) {
-    if (!mesh_verify_args_ok(ctx, vertices, n_vertices, triangles, n_triangles, poses, n_poses, raw_depth, width, height, scale, fx, fy, params,
-                             results))
+    const FrameCamera cam{width, height, scale, {fx, fy, cx, cy}};
+    if (!mesh_verify_args_ok(ctx, vertices, n_vertices, triangles, n_triangles, poses, n_poses, raw_depth, cam, true, params, results))
         return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     float* d_vtx; int* d_tri; uint16_t* d_raw;
     TDV_TRY(upload(ctx, vertices, (size_t)n_vertices * 3, &d_vtx));
     TDV_TRY(upload(ctx, triangles, (size_t)n_triangles * 3, &d_tri));
-    TDV_TRY(upload(ctx, raw_depth, (size_t)width * height, &d_raw));
-    return mesh_verify_run_dev(ctx, d_vtx, n_vertices, d_tri, n_triangles, poses, n_poses, d_raw, width, height, scale, fx, fy, cx, cy, *params,
-                               results, order);
+    TDV_TRY(upload(ctx, raw_depth, cam.npx(), &d_raw));
+    return mesh_verify_run_dev(ctx, d_vtx, n_vertices, d_tri, n_triangles, poses, n_poses, d_raw, cam, *params, results, order);
 }
 
 int tdv_render_depth_mesh_dev(tdv_ctx* ctx, const float* d_vertices, int n_vertices, const int* d_triangles, int n_triangles, const float* h_pose,
                               int width, int height, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params,
                               float* d_out_depth, int* n_rendered) {
-    if (!mesh_verify_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_pose, 1, d_out_depth, width, height, 1.f, fx, fy, params,
-                             h_pose))
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!mesh_verify_args_ok(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_pose, 1, d_out_depth, cam, false, params, h_pose))
         return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
-    return mesh_render_run_dev(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_pose, width, height, fx, fy, cx, cy, *params, d_out_depth,
-                               n_rendered);
+    return mesh_render_run_dev(ctx, d_vertices, n_vertices, d_triangles, n_triangles, h_pose, cam, *params, d_out_depth, n_rendered);
 }
 
 int tdv_render_depth_mesh(tdv_ctx* ctx, const float* vertices, int n_vertices, const int* triangles, int n_triangles, const float* pose, int width,
                           int height, float fx, float fy, float cx, float cy, const tdv_mesh_verify_params* params, float* out_depth,
                           int* n_rendered) {
-    if (!mesh_verify_args_ok(ctx, vertices, n_vertices, triangles, n_triangles, pose, 1, out_depth, width, height, 1.f, fx, fy, params, pose))
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!mesh_verify_args_ok(ctx, vertices, n_vertices, triangles, n_triangles, pose, 1, out_depth, cam, false, params, pose))
         return TDV_ERR_BAD_ARG;
     TDV_TRY(call_begin(ctx));
     float *d_vtx, *d_out; int* d_tri;
     TDV_TRY(upload(ctx, vertices, (size_t)n_vertices * 3, &d_vtx));
     TDV_TRY(upload(ctx, triangles, (size_t)n_triangles * 3, &d_tri));
-    TDV_TRY(ws_alloc(ctx, (size_t)width * height, &d_out));
-    TDV_TRY(mesh_render_run_dev(ctx, d_vtx, n_vertices, d_tri, n_triangles, pose, width, height, fx, fy, cx, cy, *params, d_out, n_rendered));
-    TDV_TRY(download(ctx, out_depth, d_out, (size_t)width * height));
+    TDV_TRY(ws_alloc(ctx, cam.npx(), &d_out));
+    TDV_TRY(mesh_render_run_dev(ctx, d_vtx, n_vertices, d_tri, n_triangles, pose, cam, *params, d_out, n_rendered));
+    TDV_TRY(download(ctx, out_depth, d_out, cam.npx()));
     return finish(ctx);
 }
 
