@@ -72,6 +72,8 @@ ABI_SYMBOLS = [
     "tdv_mesh_sample_default_params", "tdv_mesh_sample_points", "tdv_mesh_sample_points_dev",
     "tdv_tsdf_default_params", "tdv_tsdf_volume_bytes", "tdv_tsdf_reset_dev", "tdv_tsdf_integrate_dev", "tdv_tsdf_extract_dev", "tdv_tsdf_fuse",
     "tdv_tsdf_extract_mesh_dev", "tdv_tsdf_fuse_mesh",
+    "tdv_tsdf_color_bytes", "tdv_tsdf_color_reset_dev", "tdv_tsdf_integrate_color_dev", "tdv_tsdf_extract_color_dev",
+    "tdv_tsdf_extract_mesh_color_dev", "tdv_tsdf_raycast_color_dev", "tdv_tsdf_fuse_color",
     "tdv_odometry_default_params", "tdv_depth_maps_dev", "tdv_depth_maps", "tdv_depth_odometry_terms_dev", "tdv_depth_odometry_dev",
     "tdv_depth_odometry", "tdv_depth_odometry_sequence_dev", "tdv_depth_odometry_to_depth_dev", "tdv_depth_odometry_to_depth",
     "tdv_tsdf_raycast_default_params", "tdv_tsdf_raycast_dev", "tdv_tsdf_raycast", "tdv_tsdf_track_dev", "tdv_tsdf_track_sequence_dev",
@@ -453,6 +455,15 @@ def mesh_compact(vertices, normals, triangles):
     return vertices[used], (None if normals is None else normals[used]), new[triangles].reshape(-1, 3)
 
 
+def _colored_mesh(vertices, normals, triangles, rgb, compact):
+    """(vertices, normals, triangles, rgb); compact: mesh_compact, the colours of the dropped vertices dropped with them."""
+    if not compact:
+        return vertices, normals, triangles, rgb
+    used = np.zeros(len(vertices), bool)
+    used[np.asarray(triangles, np.int32).reshape(-1)] = True
+    return mesh_compact(vertices, normals, triangles) + (rgb[used],)
+
+
 def _poses16(poses):
     """[n, 4, 4] row-major poses as the ABI's n x 16 column-major floats."""
     poses = np.asarray(poses, np.float32).reshape(-1, 4, 4)
@@ -550,6 +561,7 @@ def lib():
             l.tdv_ctx_get_stream.restype = C.c_void_p
             l.tdv_ctx_workspace_bytes.restype = C.c_ulonglong
             l.tdv_tsdf_volume_bytes.restype = C.c_ulonglong
+            l.tdv_tsdf_color_bytes.restype = C.c_ulonglong
             l.tdv_ctx_last_ransac_rescore.restype = C.c_double
             l.tdv_ctx_last_ransac_scored.restype = C.c_double
             l.tdv_ctx_last_ransac_bound.restype = None
@@ -1765,6 +1777,130 @@ class Context:
             call(xyz, nrm, nv, tri if nt else None, nt)
         return mesh_compact(xyz, nrm, tri) if compact else (xyz, nrm, tri)
 
+    # ---------------------------------------------------------------- coloured TSDF fusion (include/tdv_hip.h: tdv_tsdf_integrate_color_dev)
+    def tsdf_color_volume(self, vol):
+        """A fresh colour volume for vol (tsdf_volume()'s struct): a torch float32 tensor [nx*ny*nz, 4] of (r, g, b, wc) quads on the
+        device, voxel (i, j, k) at row (k*ny + j)*nx + i, every quad (0, 0, 0, 0).  The caller owns the tensor."""
+        import torch
+        nbytes = int(lib().tdv_tsdf_color_bytes(C.byref(vol)))
+        if nbytes == 0:
+            raise ValueError("tsdf_color_volume: sides in [1, TDV_TSDF_MAX_SIDE], at most TDV_TSDF_MAX_VOXELS voxels, voxel_length > 0")
+        buf = torch.empty((nbytes // 16, 4), dtype=torch.float32, device=torch.device("cuda", self.device))
+        torch.cuda.current_stream(buf.device).synchronize()
+        self.tsdf_color_reset_dev(vol, buf.data_ptr())
+        self.synchronize()
+        return buf
+
+    def tsdf_color_reset_dev(self, vol, d_color):
+        """tdv_tsdf_color_reset_dev: every quad of the colour volume becomes (0, 0, 0, 0)."""
+        _check(self._h, lib().tdv_tsdf_color_reset_dev(self._h, C.byref(vol), _ptr(d_color)), "tdv_tsdf_color_reset_dev")
+
+    def tsdf_integrate_color_dev(self, vol, d_volume, d_color, d_raw, d_bgr, poses, w, h, scale, fx, fy, cx, cy, want_counts=True, **params):
+        """tdv_tsdf_integrate_color_dev: tsdf_integrate_dev with the colour volume d_color and the frames' images d_bgr (uint8[n, h, w, 3],
+        B, G, R, on the device).  Returns int64[n], the voxels each frame updated, or None with want_counts=False (no read-back)."""
+        t, n = _poses16(poses)
+        counts = np.zeros(n, np.int64) if want_counts else None
+        _check(self._h, lib().tdv_tsdf_integrate_color_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_color), _ptr(d_raw), _ptr(d_bgr), n, int(w),
+                                                           int(h), *self._cam(scale, fx, fy, cx, cy), _ptr(t), C.byref(tsdf_params(**params)),
+                                                           _ptr(counts)), "tdv_tsdf_integrate_color_dev")
+        return counts
+
+    def tsdf_extract_color_dev(self, vol, d_volume, d_color, d_out_xyz, d_out_normals, d_out_rgb, capacity, **params):
+        """tdv_tsdf_extract_color_dev: tsdf_extract_dev with the rows' colours (float32 RGB in [0, 1]) into d_out_rgb; returns (n, fits)."""
+        n = C.c_int(-1)
+        st = lib().tdv_tsdf_extract_color_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_color), C.byref(tsdf_params(**params)), _ptr(d_out_xyz),
+                                              _ptr(d_out_normals), _ptr(d_out_rgb), int(capacity), C.byref(n))
+        if st == -2 and n.value > int(capacity) >= 0:
+            return n.value, False
+        _check(self._h, st, "tdv_tsdf_extract_color_dev")
+        return n.value, True
+
+    def tsdf_extract_mesh_color_dev(self, vol, d_volume, d_color, d_out_vertices, d_out_normals, d_out_rgb, vertex_capacity, d_out_triangles,
+                                    triangle_capacity, **params):
+        """tdv_tsdf_extract_mesh_color_dev: tsdf_extract_mesh_dev with the vertices' colours into d_out_rgb; returns (n_vertices,
+        n_triangles, fits)."""
+        nv, nt = C.c_int(-1), C.c_int(-1)
+        st = lib().tdv_tsdf_extract_mesh_color_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_color), C.byref(tsdf_params(**params)),
+                                                   _ptr(d_out_vertices), _ptr(d_out_normals), _ptr(d_out_rgb), int(vertex_capacity), C.byref(nv),
+                                                   _ptr(d_out_triangles), int(triangle_capacity), C.byref(nt))
+        if st == -2 and ((nv.value > int(vertex_capacity) >= 0) or (nt.value > int(triangle_capacity) >= 0)):
+            return nv.value, nt.value, False
+        _check(self._h, st, "tdv_tsdf_extract_mesh_color_dev")
+        return nv.value, nt.value, True
+
+    def tsdf_integrate_color(self, volume, color, frames, images, poses, intrinsics, **params):
+        """tsdf_integrate_color_dev on host frames (uint16[n, h, w]) and images (uint8[n, h, w, 3], B, G, R) into volume = tsdf_volume()'s
+        pair and color = tsdf_color_volume()'s tensor; intrinsics = (scale, fx, fy, cx, cy)."""
+        import torch
+        frames = np.array(frames, np.uint16)                     # (a copy: torch wants a writable array)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        images = np.array(images, np.uint8).reshape(frames.shape + (3,))
+        d_raw = torch.from_numpy(frames.view(np.int16) if frames.size else np.zeros((1, 1, 1), np.int16)).to(volume[1].device)
+        d_bgr = torch.from_numpy(images if images.size else np.zeros((1, 1, 1, 3), np.uint8)).to(volume[1].device)
+        torch.cuda.synchronize()
+        return self.tsdf_integrate_color_dev(volume[0], volume[1].data_ptr(), color.data_ptr(), d_raw.data_ptr(), d_bgr.data_ptr(), poses,
+                                             frames.shape[2], frames.shape[1], *intrinsics, **params)
+
+    def tsdf_extract_color(self, volume, color, normals=True, **params):
+        """The coloured crossings of volume = tsdf_volume()'s pair and color = tsdf_color_volume()'s tensor: (xyz float32[n, 3], normals
+        float32[n, 3] or None, rgb float32[n, 3] in [0, 1] - what color_gradients and colored_icp take)."""
+        import torch
+        n, _ = self.tsdf_extract_color_dev(volume[0], volume[1].data_ptr(), color.data_ptr(), None, None, None, 0, **params)
+        out = torch.zeros((3, max(n, 1), 3), dtype=torch.float32, device=volume[1].device)
+        torch.cuda.synchronize()
+        self.tsdf_extract_color_dev(volume[0], volume[1].data_ptr(), color.data_ptr(), out[0].data_ptr(), out[1].data_ptr() if normals else None,
+                                    out[2].data_ptr(), n, **params)
+        self.synchronize()
+        h = out.cpu().numpy()
+        return h[0, :n].copy(), (h[1, :n].copy() if normals else None), h[2, :n].copy()
+
+    def tsdf_extract_mesh_color(self, volume, color, normals=True, compact=False, **params):
+        """The coloured mesh of volume and color: (vertices float32[n, 3], normals float32[n, 3] or None, triangles int32[m, 3], rgb
+        float32[n, 3]).  compact=True drops the vertices no triangle refers to, and their colours with them."""
+        import torch
+        vol, buf = volume
+        nv, nt, _ = self.tsdf_extract_mesh_color_dev(vol, buf.data_ptr(), color.data_ptr(), None, None, None, 0, None, 0, **params)
+        out = torch.zeros((3, max(nv, 1), 3), dtype=torch.float32, device=buf.device)
+        tri = torch.zeros((max(nt, 1), 3), dtype=torch.int32, device=buf.device)
+        torch.cuda.synchronize()
+        self.tsdf_extract_mesh_color_dev(vol, buf.data_ptr(), color.data_ptr(), out[0].data_ptr(), out[1].data_ptr() if normals else None,
+                                         out[2].data_ptr(), nv, tri.data_ptr(), nt, **params)
+        self.synchronize()
+        h = out.cpu().numpy()
+        return _colored_mesh(h[0, :nv].copy(), (h[1, :nv].copy() if normals else None), tri.cpu().numpy()[:nt].copy(), h[2, :nv].copy(), compact)
+
+    def tsdf_fuse_color(self, frames, images, poses, intrinsics, volume, normals=True, triangles=False, compact=False, **params):
+        """tdv_tsdf_fuse_color on host arrays: frames uint16[n, h, w] and images uint8[n, h, w, 3] (B, G, R) taken at poses [n, 4, 4] with
+        intrinsics = (scale, fx, fy, cx, cy), fused in volume = (origin, voxel_length, dims) or a TsdfVolumeC.  Returns (xyz float32[m, 3],
+        normals float32[m, 3] or None, rgb float32[m, 3]); with triangles=True (vertices, normals or None, triangles int32[t, 3], rgb), and
+        compact=True then drops the vertices no triangle refers to.  The first call asks for the counts, the second brings the rows."""
+        vol = volume if isinstance(volume, TsdfVolumeC) else tsdf_volume_struct(*volume)
+        frames = np.ascontiguousarray(frames, np.uint16)
+        frames = frames.reshape((-1,) + frames.shape[-2:])
+        images = np.ascontiguousarray(images, np.uint8).reshape(frames.shape + (3,))
+        t, n = _poses16(poses)
+        if n != len(frames):
+            raise ValueError("tdv_tsdf_fuse_color: one pose per frame")
+        scale, fx, fy, cx, cy = intrinsics
+        p = tsdf_params(**params)
+
+        def call(xyz, nrm, rgb, vcap, tri, tcap):
+            nv, nt = C.c_int(-1), C.c_int(0)
+            st = lib().tdv_tsdf_fuse_color(self._h, C.byref(vol), _ptr(frames), _ptr(images), n, frames.shape[2], frames.shape[1],
+                                           *self._cam(scale, fx, fy, cx, cy), _ptr(t), C.byref(p), _ptr(xyz), _ptr(nrm), _ptr(rgb), vcap, C.byref(nv),
+                                           _ptr(tri), tcap, C.byref(nt) if triangles else None)
+            if not (st == -2 and (nv.value > vcap or nt.value > tcap)):
+                _check(self._h, st, "tdv_tsdf_fuse_color")
+            return nv.value, nt.value
+
+        nv, nt = call(None, None, None, 0, None, 0)
+        xyz, rgb = np.zeros((nv, 3), np.float32), np.zeros((nv, 3), np.float32)
+        nrm = np.zeros((nv, 3), np.float32) if normals else None
+        tri = np.zeros((nt, 3), np.int32)
+        if nv:
+            call(xyz, nrm, rgb, nv, tri if nt else None, nt)
+        return _colored_mesh(xyz, nrm, tri, rgb, compact) if triangles else (xyz, nrm, rgb)
+
     # ---------------------------------------------------------------- depth odometry (include/tdv_hip.h: tdv_depth_odometry_dev)
     odometry_params = staticmethod(odometry_params)
 
@@ -1898,6 +2034,37 @@ class Context:
                                                    _ptr(d_depth), _ptr(d_vertex_map), _ptr(d_normal_map), C.byref(n) if want_count else None),
                "tdv_tsdf_raycast_dev")
         return n.value if want_count else None
+
+    def tsdf_raycast_color_dev(self, vol, d_volume, d_color, pose, w, h, fx, fy, cx, cy, d_depth=None, d_vertex_map=None, d_normal_map=None,
+                               d_rgb_map=None, want_count=True, **params):
+        """tdv_tsdf_raycast_color_dev: tsdf_raycast_dev with the colour volume d_color and d_rgb_map (float32[h, w, 3], RGB, zeros where a
+        ray has no hit or no colour; optional).  Returns the number of rays that hit, or None with want_count=False (no read-back)."""
+        tp, rp = _split_params(params, "tsdf", "raycast")
+        n = C.c_longlong(-1)
+        _check(self._h, lib().tdv_tsdf_raycast_color_dev(self._h, C.byref(vol), _ptr(d_volume), _ptr(d_color), int(w), int(h), C.c_float(fx),
+                                                         C.c_float(fy), C.c_float(cx), C.c_float(cy), _ptr(to_colmajor16(pose)),
+                                                         C.byref(tsdf_params(**tp)), C.byref(raycast_params(**rp)), _ptr(d_depth),
+                                                         _ptr(d_vertex_map), _ptr(d_normal_map), _ptr(d_rgb_map), C.byref(n) if want_count else None),
+               "tdv_tsdf_raycast_color_dev")
+        return n.value if want_count else None
+
+    def tsdf_raycast_color(self, volume, color, pose, w, h, fx, fy, cx, cy, maps=True, **params):
+        """tsdf_raycast_color_dev on volume = tsdf_volume()'s pair and color = tsdf_color_volume()'s tensor, the maps brought to the host:
+        dict(depth float32[h, w], rgb_map float32[h, w, 3], vertex_map and normal_map float32[h, w, 3] - with maps - and n_hit)."""
+        import torch
+        vol, buf = volume
+        w, h = int(w), int(h)
+        out = torch.zeros((3, max(w * h, 1), 3), dtype=torch.float32, device=buf.device)
+        depth = torch.zeros(max(w * h, 1), dtype=torch.float32, device=buf.device)
+        torch.cuda.synchronize()
+        n = self.tsdf_raycast_color_dev(vol, buf.data_ptr(), color.data_ptr(), pose, w, h, fx, fy, cx, cy, depth.data_ptr(),
+                                        out[0].data_ptr() if maps else None, out[1].data_ptr() if maps else None, out[2].data_ptr(), **params)
+        self.synchronize()
+        m = out.cpu().numpy()[:, :w * h].reshape(3, h, w, 3)
+        res = dict(depth=depth.cpu().numpy()[:w * h].reshape(h, w).copy(), rgb_map=m[2].copy(), n_hit=n)
+        if maps:
+            res.update(vertex_map=m[0].copy(), normal_map=m[1].copy())
+        return res
 
     def tsdf_raycast(self, volume, pose, w, h, fx, fy, cx, cy, maps=True, **params):
         """tdv_tsdf_raycast on a host volume: volume = (vol, buf) with vol = (origin, voxel_length, dims) or a TsdfVolumeC and buf float32

@@ -1,5 +1,5 @@
 // TSDF ray casting and frame-to-model tracking on gfx950: include/tdv_hip.h (tdv_tsdf_raycast_dev) states every rule, T13 to T18 and
-// K1 to K3.
+// K1 to K3; tdv_tsdf_raycast_color_dev adds T24.
 //
 // A pixel's march depends on that pixel, the pose and the volume only, every loop is bounded by the step cap, and every float below is
 // evaluated as the header writes it: nothing depends on the order the device works in.  The only atomic is the optional hit count.
@@ -8,7 +8,9 @@
 //                    four 16-byte loads per sample, all in flight before the one test of the eight weights.  The volume, the camera and the pose are kernel arguments: the
 //                    pose reaches the lanes through scalar loads.  T15's march in z, T16's one interpolation, then T17 and T18 for the
 //                    maps that were asked for (MAPS) - six more samples, only on lanes that hit.  COUNT: the workgroup's hits by
-//                    fixed_tree.hpp's block count, one atomic per workgroup.  No LDS beyond that count's four ints.
+//                    fixed_tree.hpp's block count, one atomic per workgroup.  No LDS beyond that count's four ints.  COL (T24): the
+//                    hit's colour from the colour volume - eight 16-byte loads once per ray, after T16, on lanes that hit - by the
+//                    sample's own cell (rc_cell) and lerps (rc_trilerp).
 // The voxel, T14's grid coordinate, the default truncation and the normalisation are tsdf_volume.hpp's; T13's pose, T17's vertex and
 // T18's rotation are frame_pose.hpp's.
 // Tracking (K1 to K3) is this kernel into a workspace image, odometry.hip's pair against that image (O10, tsdf_track.hpp) with the hit
@@ -49,33 +51,67 @@ __device__ __forceinline__ TsdfVoxel rc_pair(const TsdfVoxel* __restrict__ a) {
 
 __device__ __forceinline__ float rc_lerp(float a, float b, float t) { return a + t * (b - a); }
 
-// T14: the field at p; false where the sample is unknown.  The grid coordinates are checked as floats, so every index below is inside
-// the volume: 0 <= i <= n - 2 on each axis.
-__device__ __forceinline__ bool rc_sample(const tdv_tsdf_volume& V, float min_weight, const TsdfVoxel* __restrict__ vol, const float* p, float& s) {
+// T14's cell of p: false where a grid coordinate fails its condition; otherwise the voxel index of corner (i0, i1, i2) and t.  The grid
+// coordinates are checked as floats, so every index of the cell's eight voxels is inside the volume: 0 <= i <= n - 2 on each axis.
+__device__ __forceinline__ bool rc_cell(const tdv_tsdf_volume& V, const float* p, size_t& corner, float& t0, float& t1, float& t2) {
     const float g0 = tsdf_grid_coord(V.origin[0], p[0], V.voxel_length), g1 = tsdf_grid_coord(V.origin[1], p[1], V.voxel_length),
                 g2 = tsdf_grid_coord(V.origin[2], p[2], V.voxel_length);
     if (!(g0 >= 0.f && g0 < (float)(V.nx - 1) && g1 >= 0.f && g1 < (float)(V.ny - 1) && g2 >= 0.f && g2 < (float)(V.nz - 1))) return false;
     const float i0 = floorf(g0), i1 = floorf(g1), i2 = floorf(g2);
-    const float t0 = g0 - i0, t1 = g1 - i1, t2 = g2 - i2;
+    t0 = g0 - i0; t1 = g1 - i1; t2 = g2 - i2;
+    corner = ((size_t)(int)i2 * V.ny + (size_t)(int)i1) * V.nx + (size_t)(int)i0;
+    return true;
+}
+
+// T14's seven lerps over the eight values f[dx + 2 dy + 4 dz]
+__device__ __forceinline__ float rc_trilerp(const float* f, float t0, float t1, float t2) {
+    const float x00 = rc_lerp(f[0], f[1], t0), x10 = rc_lerp(f[2], f[3], t0), x01 = rc_lerp(f[4], f[5], t0), x11 = rc_lerp(f[6], f[7], t0);
+    const float y0 = rc_lerp(x00, x10, t1), y1 = rc_lerp(x01, x11, t1);
+    return rc_lerp(y0, y1, t2);
+}
+
+// T14: the field at p; false where the sample is unknown.
+__device__ __forceinline__ bool rc_sample(const tdv_tsdf_volume& V, float min_weight, const TsdfVoxel* __restrict__ vol, const float* p, float& s) {
+    size_t corner;
+    float t0, t1, t2;
+    if (!rc_cell(V, p, corner, t0, t1, t2)) return false;
     const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * V.ny;
-    const TsdfVoxel* a = vol + ((size_t)(int)i2 * V.ny + (size_t)(int)i1) * V.nx + (size_t)(int)i0;
+    const TsdfVoxel* a = vol + corner;
     const TsdfVoxel q000 = rc_pair(a), q100 = rc_pair(a + 1), q010 = rc_pair(a + sy), q110 = rc_pair(a + sy + 1), q001 = rc_pair(a + sz),
                  q101 = rc_pair(a + sz + 1), q011 = rc_pair(a + sz + sy), q111 = rc_pair(a + sz + sy + 1);
     const float mw = min_weight;
     if (!((q000.w >= mw) & (q100.w >= mw) & (q010.w >= mw) & (q110.w >= mw) & (q001.w >= mw) & (q101.w >= mw) & (q011.w >= mw) & (q111.w >= mw)))
         return false;                                                              // T6: eight loads in flight, one test
-    const float x00 = rc_lerp(q000.f, q100.f, t0), x10 = rc_lerp(q010.f, q110.f, t0), x01 = rc_lerp(q001.f, q101.f, t0),
-                x11 = rc_lerp(q011.f, q111.f, t0);
-    const float y0 = rc_lerp(x00, x10, t1), y1 = rc_lerp(x01, x11, t1);
-    s = rc_lerp(y0, y1, t2);
+    const float f[8] = {q000.f, q100.f, q010.f, q110.f, q001.f, q101.f, q011.f, q111.f};
+    s = rc_trilerp(f, t0, t1, t2);
     return s == s;                                                                 // a NaN is not a sample
 }
 
-// blockIdx.x * 4 + wave = the tile, x fastest; lane = (v & 7) * 8 + (u & 7)
-template <bool MAPS, bool COUNT>
+// T24: the colour at the hit's point p - T14's lerps per channel where the cell's eight voxels are coloured (T22), zeros otherwise.
+// Eight 16-byte loads, all in flight before the one test of the eight weights.
+__device__ __forceinline__ Row3 rc_colour(const tdv_tsdf_volume& V, const TsdfColour* __restrict__ col, const float* p) {
+    size_t corner;
+    float t0, t1, t2;
+    if (!rc_cell(V, p, corner, t0, t1, t2)) return Row3{0.f, 0.f, 0.f};
+    const size_t sy = (size_t)V.nx, sz = (size_t)V.nx * V.ny;
+    const TsdfColour* a = col + corner;
+    const TsdfColour q[8] = {tsdf_quad(a), tsdf_quad(a + 1), tsdf_quad(a + sy), tsdf_quad(a + sy + 1), tsdf_quad(a + sz), tsdf_quad(a + sz + 1),
+                             tsdf_quad(a + sz + sy), tsdf_quad(a + sz + sy + 1)};
+    bool all = true;
+    float r[8], g[8], b[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { all = all & tsdf_coloured(q[k]); r[k] = q[k].r; g[k] = q[k].g; b[k] = q[k].b; }
+    if (!all) return Row3{0.f, 0.f, 0.f};
+    return Row3{rc_trilerp(r, t0, t1, t2), rc_trilerp(g, t0, t1, t2), rc_trilerp(b, t0, t1, t2)};
+}
+
+// blockIdx.x * 4 + wave = the tile, x fastest; lane = (v & 7) * 8 + (u & 7).  COL (T24): rgb_map (not null) gets the colour of every
+// pixel from `col`, read once per ray and only at a hit; without COL both are unused and the kernel is the geometry-only one.
+template <bool MAPS, bool COUNT, bool COL>
 __global__ __launch_bounds__(RC_T)
 void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, Pose16 P, RcMarch m, const TsdfVoxel* __restrict__ vol, float* __restrict__ depth,
-                    float* __restrict__ vertex_map, float* __restrict__ normal_map, unsigned long long* __restrict__ n_hit) {
+                    float* __restrict__ vertex_map, float* __restrict__ normal_map, unsigned long long* __restrict__ n_hit,
+                    const TsdfColour* __restrict__ col, float* __restrict__ rgb_map) {
     __shared__ int s_cnt[4];
     const int lane = threadIdx.x & 63, tiles_x = (c.w + RC_TILE - 1) / RC_TILE;
     const int tile = (int)blockIdx.x * (RC_T / 64) + ((int)threadIdx.x >> 6);
@@ -129,6 +165,15 @@ void k_tsdf_raycast(tdv_tsdf_volume V, RcCam c, Pose16 P, RcMarch m, const TsdfV
             if (vertex_map) reinterpret_cast<Row3*>(vertex_map)[i] = vr;
             if (normal_map) reinterpret_cast<Row3*>(normal_map)[i] = nr;
         }
+        if (COL) {
+            Row3 cr{0.f, 0.f, 0.f};
+            if (hit) {
+                float p[3];
+                rc_point(u, v, zh, c, P, m.direction, p);
+                cr = rc_colour(V, col, p);
+            }
+            reinterpret_cast<Row3*>(rgb_map)[i] = cr;
+        }
     }
     if (COUNT) {
         const int n = tree_block_count(hit ? 1 : 0, s_cnt);
@@ -144,8 +189,10 @@ bool rc_args_ok(const tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* vol
 }
 
 // The launch (cam.npx() > 0).  d_n_hit: nullptr, or where to leave a fresh workspace counter that the launch counts the hits into.
+// d_color and d_rgb (both or neither): the colour volume and the map of T24.
 int rc_launch(tdv_ctx* ctx, const tdv_tsdf_volume& V, const float* d_volume, const FrameCamera& fc, const float* h_pose, const tdv_tsdf_params& prm,
-              const tdv_tsdf_raycast_params& ray, float* d_depth, float* d_vm, float* d_nm, unsigned long long** d_n_hit) {
+              const tdv_tsdf_raycast_params& ray, float* d_depth, float* d_vm, float* d_nm, unsigned long long** d_n_hit,
+              const float* d_color = nullptr, float* d_rgb = nullptr) {
     hipStream_t s = ctx->stream;
     unsigned long long* d_cnt = nullptr;
     if (d_n_hit) {
@@ -160,11 +207,18 @@ int rc_launch(tdv_ctx* ctx, const tdv_tsdf_volume& V, const float* d_volume, con
     const unsigned tiles = (unsigned)((fc.w + RC_TILE - 1) / RC_TILE) * (unsigned)((fc.h + RC_TILE - 1) / RC_TILE);      // at most 2^20
     const unsigned blocks = (tiles + RC_T / 64 - 1) / (RC_T / 64);
     const TsdfVoxel* vol = reinterpret_cast<const TsdfVoxel*>(d_volume);
+    const TsdfColour* col = reinterpret_cast<const TsdfColour*>(d_color);
     const bool maps = d_vm || d_nm;
-    if (maps && d_cnt) k_tsdf_raycast<true, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, d_cnt);
-    else if (maps) k_tsdf_raycast<true, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, nullptr);
-    else if (d_cnt) k_tsdf_raycast<false, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, d_cnt);
-    else k_tsdf_raycast<false, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, nullptr);
+    if (d_rgb) {
+        if (maps && d_cnt) k_tsdf_raycast<true, true, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, d_cnt, col, d_rgb);
+        else if (maps) k_tsdf_raycast<true, false, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, nullptr, col, d_rgb);
+        else if (d_cnt) k_tsdf_raycast<false, true, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, d_cnt, col, d_rgb);
+        else k_tsdf_raycast<false, false, true><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, nullptr, col, d_rgb);
+    }
+    else if (maps && d_cnt) k_tsdf_raycast<true, true, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, d_cnt, nullptr, nullptr);
+    else if (maps) k_tsdf_raycast<true, false, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, d_vm, d_nm, nullptr, nullptr, nullptr);
+    else if (d_cnt) k_tsdf_raycast<false, true, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, d_cnt, nullptr, nullptr);
+    else k_tsdf_raycast<false, false, false><<<blocks, RC_T, 0, s>>>(V, cam, P, m, vol, d_depth, nullptr, nullptr, nullptr, nullptr, nullptr);
     TDV_CHECK_LAUNCH(ctx);
     return TDV_OK;
 }
@@ -227,6 +281,19 @@ int tdv_tsdf_raycast_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* 
     if (cam.npx() == 0 || (!d_depth && !d_vertex_map && !d_normal_map && !h_n_hit)) return TDV_OK;
     unsigned long long* d_cnt;
     TDV_TRY(rc_launch(ctx, *vol, d_volume, cam, h_pose, *params, *ray, d_depth, d_vertex_map, d_normal_map, h_n_hit ? &d_cnt : nullptr));
+    return h_n_hit ? rc_hits(ctx, d_cnt, h_n_hit) : TDV_OK;
+}
+
+int tdv_tsdf_raycast_color_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const float* d_color, int width, int height, float fx,
+                               float fy, float cx, float cy, const float* h_pose, const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray,
+                               float* d_depth, float* d_vertex_map, float* d_normal_map, float* d_rgb_map, long long* h_n_hit) {
+    const FrameCamera cam{width, height, 1.f, {fx, fy, cx, cy}};
+    if (!rc_args_ok(ctx, vol, d_volume, cam, h_pose, params, ray) || !tsdf_colour_ok(d_color)) return TDV_ERR_BAD_ARG;
+    TDV_TRY(call_begin(ctx));
+    if (h_n_hit) *h_n_hit = 0;
+    if (cam.npx() == 0 || (!d_depth && !d_vertex_map && !d_normal_map && !d_rgb_map && !h_n_hit)) return TDV_OK;
+    unsigned long long* d_cnt;
+    TDV_TRY(rc_launch(ctx, *vol, d_volume, cam, h_pose, *params, *ray, d_depth, d_vertex_map, d_normal_map, h_n_hit ? &d_cnt : nullptr, d_color, d_rgb_map));
     return h_n_hit ? rc_hits(ctx, d_cnt, h_n_hit) : TDV_OK;
 }
 

@@ -1265,8 +1265,9 @@ int tdv_mesh_sample_points_dev(tdv_ctx* ctx, const float* d_vertices, int n_vert
  * TDV_TSDF_HOST_MAX_VOXELS); voxel_length, scale, fx or fy <= 0 or non-finite; trunc < 0 or non-finite; max_weight < 1 or non-finite;
  * min_weight <= 0 or non-finite; n_frames < 0 or > TDV_TSDF_MAX_FRAMES; width or height < 0 or > TDV_VERIFY_MAX_SIDE; an unknown
  * pose_direction; capacity < 0.  The ctx's switches do not apply.
- * Not provided: colour, per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, the C++ operator
- * mirror.  Ray casting and tracking against the volume: tdv_tsdf_raycast_dev, below. */
+ * Not provided: per-frame masks (a caller zeroes the pixels), per-frame weights, a hashed or sparse volume, the C++ operator mirror, a
+ * coloured sequence tracker (today a loop over tdv_tsdf_track_dev and tdv_tsdf_integrate_color_dev), a colour term in tracking and
+ * odometry.  Colour: tdv_tsdf_integrate_color_dev, below.  Ray casting and tracking against the volume: tdv_tsdf_raycast_dev, below. */
 typedef struct tdv_tsdf_volume { float origin[3]; float voxel_length; int nx, ny, nz; } tdv_tsdf_volume;   /* 28 bytes */
 typedef struct tdv_tsdf_params {   /* 20 bytes */
     float trunc;           /* truncation distance in metres; default 0, which means 4.0f * voxel_length */
@@ -1360,8 +1361,9 @@ int tdv_tsdf_fuse_mesh(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t*
  * [1, TDV_TSDF_RAYCAST_MAX_STEPS]; the host form above TDV_TSDF_HOST_MAX_VOXELS.  Tracking also: as tdv_depth_odometry_dev for scale and
  * odom, a NULL frame (width*height > 0), guess or result, a pose_direction other than TDV_POSE_SOURCE_ONTO_TARGET; the sequence: n_frames
  * < 0 or > TDV_TSDF_MAX_FRAMES, NULL frames or h_poses with n_frames > 0.
- * Not provided: colour, a sparse volume, adaptive refinement of the hit beyond T16's one interpolation, loop closure, a device-resident
- * pose hand-off from tracking to integrate (the read-back per frame). */
+ * Not provided: a sparse volume, adaptive refinement of the hit beyond T16's one interpolation, loop closure, a device-resident pose
+ * hand-off from tracking to integrate (the read-back per frame), a coloured sequence tracker (today a loop over tdv_tsdf_track_dev and
+ * tdv_tsdf_integrate_color_dev), a colour term in tracking and odometry.  The ray-cast colour: tdv_tsdf_raycast_color_dev, below. */
 #define TDV_TSDF_RAYCAST_MAX_STEPS 16384
 typedef struct tdv_tsdf_raycast_params {   /* 8 bytes */
     float zmin;            /* T15: where the march starts, metres, > 0; default 0.05 */
@@ -1375,6 +1377,74 @@ int tdv_tsdf_raycast_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* 
 int tdv_tsdf_raycast(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* volume, int width, int height, float fx, float fy, float cx, float cy,
                      const float* pose, const tdv_tsdf_params* params, const tdv_tsdf_raycast_params* ray, float* depth /* optional */,
                      float* vertex_map /* optional */, float* normal_map /* optional */, long long* n_hit /* optional */);
+/* Coloured TSDF fusion (Open3D's ColoredTSDFVolume; KinectFusion's colour volume): the frames' colour images are fused beside their depths,
+ * and the cloud, the mesh and the ray-cast view of the volume carry colours - float RGB in [0, 1], what tdv_color_gradients and
+ * tdv_colored_icp take, so a model scanned here can be the target of this library's Colored ICP.  No existing call changes: the pair
+ * volume's layout and every byte the calls above write stay as they are, and each call below is its plain counterpart plus the colour
+ * arguments.  The rules continue T1 to T18, under the same arithmetic: f32, one rounding per operation, no contraction, the order as
+ * written, / correctly rounded - every output is fixed bit for bit whatever order the device works in.
+ *  T19. Colour volume: a second caller-owned device buffer of nx*ny*nz quads (f32 r, f32 g, f32 b, f32 wc), 16 bytes each, the buffer
+ *      16-byte aligned, tdv_tsdf_color_bytes(vol) bytes (0 for a volume the checks refuse, as tdv_tsdf_volume_bytes); voxel (i, j, k) sits
+ *      at quad index (k*ny + j)*nx + i, the pair volume's index.  The layout is public.  tdv_tsdf_color_reset_dev makes every quad
+ *      (0, 0, 0, 0).  wc is the colour's own weight, not the pair's w: a volume may take some frames through tdv_tsdf_integrate_dev (no
+ *      colour image) and others through tdv_tsdf_integrate_color_dev.
+ *  T20. Pixel colour.  Frame f's colour image is width x height x 3 bytes, row-major, B, G, R at bytes 3*(v*width + u) + 0, 1, 2 - the
+ *      layout tdv_depth_to_cloud_dev takes.  A channel is (float)byte / 255.0f, the cloud's rule.
+ *  T21. Update.  A frame updates a voxel's quad exactly where T5 updates its pair, with the pixel at T3's (u, v): r' = (r*wc + c_r) /
+ *      (wc + 1.0f), g' and b' likewise, wc' = fminf(wc + 1.0f, max_weight).  The frames apply in ascending index, and a call with frames
+ *      A, B leaves what a call with A and then a call with B leave.  The pair volume and h_n_updated are byte for byte
+ *      tdv_tsdf_integrate_dev's.  Every stored channel stays in [0, 1] (from a reset volume, or any whose channels are in [0, 1] and whose
+ *      wc are not negative): rounding is monotone.  A pixel colour is the rounded quotient of 0 .. 255 by 255, so it lies in [0, 1]; with
+ *      r and c_r in [0, 1] the product r*wc rounds into [0, wc], wc being a float; the sum is then at most wc + 1 before its rounding
+ *      and at most the rounded wc + 1.0f - the divisor - after it (up to max_weight's range, 2^24, wc + 1.0f is exact besides); so the
+ *      quotient is at most 1 before its rounding and after, and nothing is negative.
+ *  T22. Coloured voxel: wc > 0.
+ *  T23. Crossing colour.  With a, b, r_a, r_b of T7: both voxels coloured - per channel (c_a*r_b + c_b*r_a) / (r_a + r_b), the point's own
+ *      interpolation with the voxels' channel values for the centres' coordinates; exactly one coloured - that voxel's colour; neither -
+ *      (0, 0, 0).  Row i of the colour output belongs to row i of tdv_tsdf_extract_dev's cloud; since vertex v of the mesh is row v, it is
+ *      the mesh's vertex colour too.
+ *  T24. Ray-cast colour.  At a hit, p is T18's point (T13 at T16's z) and g_a, i_a, t_a are T14's for p.  If T14's conditions on the g_a
+ *      hold and all eight voxels (i0 + dx, i1 + dy, i2 + dz) are coloured (T22), each channel is T14's seven lerps over the eight voxels'
+ *      channel values.  Otherwise, and where the ray has no hit, the value is (0, 0, 0).  Nothing is clamped (a lerp may leave [0, 1] by
+ *      a rounding).
+ * tdv_tsdf_integrate_color_dev: tdv_tsdf_integrate_dev with d_color, the colour volume, and d_bgr, the n_frames colour images back to
+ * back on the device.  tdv_tsdf_extract_color_dev and tdv_tsdf_extract_mesh_color_dev: their plain counterparts with d_color and
+ * d_out_rgb (capacity resp. vertex_capacity rows of 3 floats, r, g, b); the same capacity and query protocol; d_out_xyz, d_out_normals and
+ * the triangles get the bytes of the plain calls.  tdv_tsdf_raycast_color_dev: tdv_tsdf_raycast_dev with d_color and d_rgb_map (optional,
+ * width*height*3 floats, the vertex map's layout); depth, vertex map, normal map and h_n_hit are byte for byte the plain call's.
+ * tdv_tsdf_fuse_color, the host form: host frames and images in, vertices, normals (optional) and colours out, both volumes in the ctx's
+ * workspace (24 bytes a voxel); volumes above TDV_TSDF_HOST_MAX_VOXELS are refused.  Triangles are optional: with a NULL n_triangles
+ * (then out_triangles must be NULL and triangle_capacity 0) the call is the cloud's, tdv_tsdf_fuse's protocol; with n_triangles it is the
+ * mesh's, tdv_tsdf_fuse_mesh's protocol, where a NULL out_triangles with capacity 0 is a query for both counts.
+ * Kernels: the plain calls' own (csrc/tsdf.hip, csrc/tsdf_raycast.hip) with a compile-time colour switch.  Integrate keeps a voxel's quad
+ * in registers beside its pair across the frames of a call - one 16-byte load when the first frame updates the voxel, one store after
+ * the last, neither for a voxel no frame updates - and only updating lanes read their pixel's three bytes.  Extract stages no colour:
+ * a lane that owns a crossing loads the two quads in the emit pass; the count pass is the plain one.  The ray cast loads the eight quads
+ * once per ray, at a hit.
+ * TDV_ERR_BAD_ARG before anything is enqueued or written: everything the plain counterpart refuses; a NULL d_color, or one that is not
+ * 16-byte aligned; a NULL d_bgr (bgr) with n_frames > 0 and width*height > 0; a NULL d_out_rgb (out_rgb) with its capacity > 0;
+ * tdv_tsdf_fuse_color with a NULL n_triangles and a non-NULL out_triangles or a triangle_capacity other than 0.
+ * Not provided: compact (u8 or f16) colour storage - the f32 quad keeps the rules exact -, and what the two lists above name. */
+unsigned long long tdv_tsdf_color_bytes(const tdv_tsdf_volume* vol);
+int tdv_tsdf_color_reset_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_color);
+int tdv_tsdf_integrate_color_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, float* d_volume, float* d_color, const uint16_t* d_raw /* n_frames images */,
+                                 const uint8_t* d_bgr /* n_frames images */, int n_frames, int width, int height, float scale, float fx, float fy,
+                                 float cx, float cy, const float* h_poses /* host, n_frames x 16 */, const tdv_tsdf_params* params,
+                                 long long* h_n_updated /* optional, host, [n_frames] */);
+int tdv_tsdf_extract_color_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const float* d_color, const tdv_tsdf_params* params,
+                               float* d_out_xyz, float* d_out_normals /* optional */, float* d_out_rgb, int capacity, int* n_out /* host */);
+int tdv_tsdf_extract_mesh_color_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const float* d_color,
+                                    const tdv_tsdf_params* params, float* d_out_vertices, float* d_out_normals /* optional */, float* d_out_rgb,
+                                    int vertex_capacity, int* n_vertices /* host */, int* d_out_triangles, int triangle_capacity,
+                                    int* n_triangles /* host */);
+int tdv_tsdf_raycast_color_dev(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const float* d_volume, const float* d_color, int width, int height, float fx,
+                               float fy, float cx, float cy, const float* h_pose /* host, 16 */, const tdv_tsdf_params* params,
+                               const tdv_tsdf_raycast_params* ray, float* d_depth /* optional */, float* d_vertex_map /* optional */,
+                               float* d_normal_map /* optional */, float* d_rgb_map /* optional */, long long* h_n_hit /* optional, host */);
+int tdv_tsdf_fuse_color(tdv_ctx* ctx, const tdv_tsdf_volume* vol, const uint16_t* raw, const uint8_t* bgr, int n_frames, int width, int height,
+                        float scale, float fx, float fy, float cx, float cy, const float* poses, const tdv_tsdf_params* params, float* out_vertices,
+                        float* out_normals /* optional */, float* out_rgb, int vertex_capacity, int* n_vertices, int* out_triangles /* optional */,
+                        int triangle_capacity, int* n_triangles /* optional: NULL = the cloud only */);
 /* Depth odometry (KinectFusion's tracking step, Newcombe et al. 2011; Open3D's compute_odometry_result_point_to_plane): the camera's
  * motion between two raw depth frames of one sensor, on the device - the piece between "scan" and "fuse".  Two frames need no search
  * structure: the pixel grid gives a vertex its neighbours, so a normal is one cross product, and the projection gives a source pixel its
